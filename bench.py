@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: Monte Carlo trajectories/sec + apogee-match rate (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run measures the headline figure alone: it generates the shards, runs W warm-up and K timed passes of the
+headline build and prints the JSON line (value, ms_per_step, the roofline of those passes).  `--full` adds everything
+else described below - the secondary leg, the fp64 gate leg and the parity block, the CPU baseline, cfg5_share and
+api_end_to_end - each still switched off one by one with its own --no-* option.  `--dump-outputs DIR` writes what the
+last timed pass returned (the [16, n] summary and the [n] status words, the all-gathered ones when N > 1) as
+DIR/summary.npy and DIR/status.npy in float64, finite only (non-finite summary entries are 0 there and marked in
+DIR/summary_nonfinite.npy); the inputs depend on the arguments alone, so two builds can be compared output for output.
 
 One "step" = one pass of the hot path (rail kernel + RK4 flight kernel [+ RCCL all-gather of the
 per-sample summaries when N > 1]) over one batch of synthetic dispersions ALREADY RESIDENT in HBM.
@@ -148,6 +156,31 @@ def host_slice(db, m):
     hb.alt_grid = db.alt_grid.cpu().numpy().astype(np.float64)
     hb.wind = np.ascontiguousarray(db.wind[:, :, :m].double().cpu().numpy())
     return hb
+
+
+DUMP_BYTES = 60 * 10 ** 6      # --dump-outputs: what the .npy files may hold in all (under 64 MB with their headers)
+
+
+def dump_outputs(path, last, world):
+    """--dump-outputs: DIR/summary.npy ([16, m]) and DIR/status.npy ([m]: the int32 status words, exact in float64) of the
+    last timed pass, all ranks' samples rank after rank when N > 1.  Every file holds finite numbers only: a summary entry
+    that is NaN / +inf / -inf (the blown-up flights of the reference's dispersion model) is written as 0 and marked 1 / 2 / 3
+    in DIR/summary_nonfinite.npy (0 elsewhere), so the outputs stay exact.  Larger than DUMP_BYTES: a fixed, seeded sample
+    of the columns, their indices in DIR/sample_index.npy."""
+    summary, status = (t.cpu().numpy() for t in last)
+    if world > 1:     # the gathered summaries are rank-major rows [world x 16, n]: one column per sample instead
+        summary = np.concatenate(np.split(summary, world, axis=0), axis=1)
+    summary, status = summary.astype(np.float64), status.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    per_sample = (2 * summary.shape[0] + 2) * 8       # a summary column, its markers, its status word and its index
+    if status.size * per_sample > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(status.size, DUMP_BYTES // per_sample, replace=False))
+        summary, status = summary[:, idx], status[idx]
+        np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+    nonfinite = np.select([np.isnan(summary), summary == np.inf, summary == -np.inf], [1.0, 2.0, 3.0], 0.0)
+    np.save(os.path.join(path, "summary.npy"), np.where(nonfinite == 0, summary, 0.0))
+    np.save(os.path.join(path, "summary_nonfinite.npy"), nonfinite)
+    np.save(os.path.join(path, "status.npy"), status)
 
 
 def cfg5_share(eng, device, rocket, atm, wm, args, n=1250000, passes=2, subset=256):
@@ -309,7 +342,14 @@ def main():
     ap.add_argument("--short-overlap", type=int, default=-1, help="erpl_mc_set_short_flight_overlap (-1 = library default: 4; 0 = off)")
     ap.add_argument("--waves", type=int, default=0, help="fp32 kernel build: 2 or 3 waves per SIMD (0 = library default)")
     ap.add_argument("--chunk", type=int, default=-1, help="steps per launch between compactions (-1 = library default)")
+    ap.add_argument("--full", action="store_true", help="also run the secondary leg, the fp64 gate leg + parity, the CPU "
+                    "baseline, cfg5_share and api_end_to_end (the --no-* options above and --cpu-seconds select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed pass's summary and status to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if not args.full:     # a plain run: the headline leg and nothing else
+        args.no_second_leg = args.no_parity = args.no_cfg5 = args.no_api = True
+        args.cpu_seconds = 0.0
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` typed as is: this process becomes the launcher (it never touches the GPU) and the
@@ -506,8 +546,9 @@ def main():
             phys_total = float(tot.item())
         # results of the timed passes that are still in their output sets (a set is reused nbuf passes later): shard -> (summary, status)
         kept = {j: outs[k] for k, j in last_writer.items()}
+        k_last = nbuf if steps == 1 else (steps - 1) % nbuf     # the output set of the last timed pass (step() above)
         return {"steps": steps, "precision": precision, "prec": prec, "db": db, "elapsed": elapsed, "gpu_ms": gpu_ms, "depth": depth, "shards": S,
-                "kept": kept,
+                "kept": kept, "last": gath[k_last] if world > 1 else outs[k_last],
                 "summary": summary, "status": status, "rail_ms": rail_ms, "flight_ms": flight_ms,
                 "phys_steps": phys_steps, "wave_iters": wave_iters, "phys_total": phys_total}
 
@@ -568,6 +609,8 @@ def main():
         }
 
     main_leg = timed_leg(args.precision)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, main_leg["last"], world)
     second = None
     second_name = {"f64_fast": "f32", "f32": "f64_fast", "f64": "f64_fast"}[args.precision]
     if not args.no_second_leg:
@@ -602,7 +645,7 @@ def main():
                                       "reference's apogee_altitude on diverging samples (see its apogee_match_rate; DESIGN.md section 5)")
 
     # ---------------- parity + CPU baseline (N = 1 only, rank 0, outside the timed region) ----------------
-    if rank == 0 and world > 1:
+    if rank == 0 and world > 1 and args.full:
         out["cpu_baseline"] = None   # measured by the N = 1 run only (the host cores are shared by the ranks)
     if rank == 0 and world == 1 and not args.no_parity:
         # the fp64 reference-order gate kernel on the SAME shard: the per-sample reference for every timed build, and a

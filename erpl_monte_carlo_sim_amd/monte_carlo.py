@@ -160,7 +160,9 @@ class MonteCarloAnalyzer:
                 parts.append(eng.submit(db))
                 inflight.append((eng.last_ticket, db))
                 while len(inflight) > keep:
-                    retire(inflight.pop(0)[0])
+                    ticket, inputs = inflight.pop(0)
+                    retire(ticket)        # only once the batch has finished may its inputs go back to the allocator
+                    del inputs
         if inflight:
             eng.wait()
             retire(-1)
@@ -292,7 +294,9 @@ class MonteCarloAnalyzer:
                     parts.append(eng.submit(db))
                     inflight.append((eng.last_ticket, db))    # inputs outlive their batch
                 while len(inflight) > keep:
-                    eng.check(inflight.pop(0)[0])
+                    ticket, inputs = inflight.pop(0)
+                    eng.check(ticket)     # only once the batch has finished may its inputs go back to the allocator
+                    del inputs
             eng.wait()
             eng.check()                # host-blocking; raises if a lane hand-over timed out
             inflight.clear()

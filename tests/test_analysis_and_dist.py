@@ -307,6 +307,41 @@ def _bench_cmd(*extra):
     return [sys.executable, os.path.join(root, "bench.py"), *extra], env, root
 
 
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: the last timed pass's summary / status as float64 .npy files, the gathered block of
+    N ranks as one column per sample (rank after rank); above the size bound a fixed, seeded sample of the same columns
+    of both, with their indices.  Every file is finite: non-finite summary entries are 0 and marked 1 / 2 / 3 (NaN / +inf /
+    -inf) in summary_nonfinite.npy, from which the summary is rebuilt exactly."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    summ = torch.randn(2 * _abi.SUMMARY_DIM, 50, dtype=torch.float64)     # two ranks' gathered summaries
+    summ[3, 7], summ[20, 9], summ[5, 49] = float("nan"), float("inf"), -float("inf")
+    status = torch.arange(100, dtype=torch.int32) | _abi.ST_NAN
+    bench.dump_outputs(str(tmp_path / "whole"), (summ, status), 2)
+
+    def load(d):
+        arrays = {f[:-4]: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)}
+        assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in arrays.values())
+        marks = arrays["summary_nonfinite"]
+        summary = np.select([marks == 1, marks == 2, marks == 3], [np.nan, np.inf, -np.inf], arrays["summary"])
+        assert np.all(arrays["summary"][marks != 0] == 0)
+        return summary, arrays["status"], arrays.get("sample_index")
+    s, t, i = load("whole")
+    assert s.shape == (_abi.SUMMARY_DIM, 100) and i is None
+    assert np.array_equal(s, np.concatenate([summ[:_abi.SUMMARY_DIM].numpy(), summ[_abi.SUMMARY_DIM:].numpy()], axis=1),
+                          equal_nan=True)
+    assert np.isnan(s[3, 7]) and s[4, 59] == np.inf and s[5, 49] == -np.inf
+    assert np.array_equal(t, status.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 10 * (2 * _abi.SUMMARY_DIM + 2) * 8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), (summ, status), 2)
+    sa, ta, ia = load("a")
+    i = ia.astype(np.int64)
+    assert i.size == 10 and np.all(np.diff(i) > 0) and np.array_equal(ia, load("b")[2])
+    assert np.array_equal(sa, s[:, i], equal_nan=True) and np.array_equal(ta, t[i])
+
+
 def test_bench_refuses_more_gpus_than_visible():
     """`python bench.py --gpus 8` as the driver types it: the launcher counts the devices BEFORE starting ranks and
     says what is wrong (here: no GPU at all; on a one-GPU box: "8 GPUs requested, 1 visible"), rc != 0."""

@@ -279,6 +279,47 @@ def test_chunked_pipeline_and_lazy_results_equal_one_batch():
             assert np.array_equal(summ, ref[0], equal_nan=True) and np.array_equal(status, ref[1]), chunk
 
 
+_THREE_DEEP_CODE = r"""
+import os, sys
+sys.path.insert(0, %(root)r)
+sys.path.insert(0, os.path.join(%(root)r, "tests"))
+import numpy as np
+import erpl_monte_carlo_sim_amd as E
+from erpl_monte_carlo_sim_amd import flatten
+from erpl_monte_carlo_sim_amd.simulator import shared_engine
+import helpers as H
+res = []
+for chunk in (131072, 97, 97):
+    mc = E.MonteCarloAnalyzer(E.Rocket(), E.LiquidMotor(), E.StandardAtmosphere(), E.WindModel(), verbose=False)
+    mc.base_altitude_profile, mc.base_wind_profile = H.CSV_ALT, H.CSV_WIND
+    mc.precision = "f64_fast"
+    mc.n_trajectories = 3
+    mc.CHUNK = chunk
+    assert shared_engine(mc.device).get_overlap() == 3
+    params = flatten.generate_parameter_arrays(mc.uncertainty_params, 1000)
+    res.append(mc.run_batch_arrays(dict(H.EXAMPLE_IC), params)[:2])
+for summ, status in res[1:]:
+    bad = np.where(~(((summ == res[0][0]) | (np.isnan(summ) & np.isnan(res[0][0]))).all(axis=0) & (status == res[0][1])))[0]
+    assert bad.size == 0, ("samples differing from one batch", bad.size, bad[:10].tolist())
+print("ok")
+"""
+
+
+def test_chunked_pipeline_three_deep_in_a_fresh_process():
+    """The chunked pipeline at the HIP runtime's default of four hardware queues (GPU_MAX_HW_QUEUES=4, which the package
+    leaves alone: three batches in flight, no lane adoption) - the depth of any process that sets the variable or starts
+    torch.cuda before importing the package.  Eleven 97-sample chunks retire batches while later ones are prepared: the
+    inputs of a retired batch must not go back to the allocator before that batch has finished (they were, once, and a
+    worker's upload of the next chunk overwrote them: whole chunks came back with other samples' flights)."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _THREE_DEEP_CODE % {"root": root}], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, GPU_MAX_HW_QUEUES="4"))
+    assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-1000:], r.stderr[-2000:])
+
+
 def test_run_monte_carlo_device_sub_batches():
     """run_monte_carlo_device splits its samples into sub-batches handed to erpl_mc_submit_batch; the draws of a
     sub-batch depend on (seed, rank, index of the sub-batch) only."""

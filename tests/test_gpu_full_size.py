@@ -239,8 +239,8 @@ def test_bench_two_ranks_on_one_gpu(tmp_path, mode):
     extra = ["--total-samples", str(2 * n_rank)] if mode == "strong" else ["--samples-per-gpu", str(n_rank)]
     # typed exactly as the driver types the N = 1 run, with --gpus 2: bench.py starts its two ranks itself
     # (fresh children, the launching process never touches the GPU) and relays rank 0's line
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-           "--cpu-seconds", "0", "--no-parity", "--no-cfg5", "--no-api"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--full",
+           "--cpu-seconds", "0", "--no-parity", "--no-cfg5", "--no-api", "--dump-outputs", str(tmp_path / "dump")] + extra
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(ERPL_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT, timeout=900)
@@ -256,6 +256,13 @@ def test_bench_two_ranks_on_one_gpu(tmp_path, mode):
     assert d["value"] == pytest.approx(2 * n_rank * 4 / (d["ms_per_step"] * 4e-3), rel=1e-6)
     # every timed pass integrated a different shard (round 4); the counters are means over the passes' own tickets
     assert d["config"]["distinct_shards"] == 4 and d["roofline"]["rk4_steps_per_launch"] > 1000 * n_rank
+    # --dump-outputs on N ranks: rank 0 writes the gathered results of the last timed pass, one column per sample
+    files = sorted(os.listdir(tmp_path / "dump"))
+    assert files == ["status.npy", "summary.npy", "summary_nonfinite.npy"], files
+    s, m, t = (np.load(tmp_path / "dump" / f) for f in files[1:] + files[:1])
+    assert s.shape == m.shape == (_abi.SUMMARY_DIM, 2 * n_rank) and t.shape == (2 * n_rank,)
+    assert all(x.dtype == np.float64 and np.isfinite(x).all() for x in (s, m, t))
+    assert np.all(s[_abi.SUM_STEPS] > 0) and np.array_equal(t, np.round(t))
 
 
 def test_bench_gpus_8_on_a_one_gpu_box_fails_clearly():
@@ -271,6 +278,51 @@ def test_bench_gpus_8_on_a_one_gpu_box_fails_clearly():
     assert r.returncode != 0 and f"8 GPUs requested, {torch.cuda.device_count()} visible" in r.stderr, r.stderr[-1500:]
 
 
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) is the headline leg alone: the contract's keys and none of the blocks --full
+    adds.  `--dump-outputs` writes the last timed pass's results; with the same arguments two runs dump the same bits -
+    checked three batches deep (GPU_MAX_HW_QUEUES=4, the HIP default, which the package leaves alone when it is set) as
+    well as at the package's own depth - and with --shards 1 (every pass replays shard 0) the dumped status words give
+    the line's own end reasons."""
+    import json
+    n = 16384
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--samples-per-gpu", str(n)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    got = {}
+    for name, extra, queues in (("a", [], "4"), ("b", [], "4"), ("c", [], "24"), ("replay", ["--shards", "1"], "24")):
+        r = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / name)], env=dict(env, GPU_MAX_HW_QUEUES=queues),
+                           capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert r.returncode == 0, (r.stdout[-500:], r.stderr[-2000:])
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+            assert k in d, k
+        for k in ("f32", "f64_gate", "parity", "apogee_match_rate", "cpu_baseline", "cfg5_share", "api_end_to_end"):
+            assert k not in d, k
+        assert d["steps"] == 2 and d["dtype"] == "f64_fast" and d["unit"] == "trajectories/s"
+        assert d["config"]["passes_in_flight"] == (3 if queues == "4" else 8)
+        assert d["value"] == pytest.approx(n / (d["ms_per_step"] * 1e-3), rel=1e-6)
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["status.npy", "summary.npy", "summary_nonfinite.npy"], files
+        for f in files:
+            x = np.load(tmp_path / name / f)
+            assert x.dtype == np.float64 and np.isfinite(x).all(), f
+        s, t = np.load(tmp_path / name / "summary.npy"), np.load(tmp_path / name / "status.npy")
+        marks = np.load(tmp_path / name / "summary_nonfinite.npy")
+        s = np.select([marks == 1, marks == 2, marks == 3], [np.nan, np.inf, -np.inf], s)
+        assert s.shape == (_abi.SUMMARY_DIM, n) and t.shape == (n,)
+        assert np.array_equal(t, np.round(t)) and np.all(s[_abi.SUM_STEPS] > 0)
+        got[name] = d, s, t
+    (_, sa, ta), (_, sb, tb), (_, sc, tc) = got["a"], got["b"], got["c"]
+    assert np.array_equal(sa, sb, equal_nan=True) and np.array_equal(ta, tb)
+    assert np.array_equal(sa, sc, equal_nan=True) and np.array_equal(ta, tc)
+    d, _, t = got["replay"]
+    st = t.astype(np.int64)
+    assert d["end_reasons"] == {k: int(np.sum((st & 0xFF) == v)) for k, v in
+                                (("max_time", 0), ("ground", 1), ("altitude_100km", 2), ("coast", 3), ("apogee", 4))}
+
+
 def test_bench_line_with_one_replayed_shard_and_with_a_shard_per_pass():
     """`bench.py` on one GPU at a small size: the default integrates a different resident shard in every timed pass,
     `--shards 1` replays one (the method of rounds 1-3); either way ONE JSON line with the contract's keys, the roofline of
@@ -278,7 +330,7 @@ def test_bench_line_with_one_replayed_shard_and_with_a_shard_per_pass():
     which both methods run on the same samples: the same match report."""
     import json
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--samples-per-gpu", "16384",
-            "--cpu-seconds", "1", "--no-cfg5", "--no-api"]
+            "--full", "--cpu-seconds", "1", "--no-cfg5", "--no-api"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     got = {}
     for name, extra in (("per_pass", []), ("replay", ["--shards", "1"])):

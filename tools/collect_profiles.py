@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Distil gpurun_out/<tag>_* (written by tools/refresh_profiles.sh on the GPU box) into profiles/:
+"""Distil $PROFILE_RUNS/<tag>_* (default profile_runs/, written by tools/refresh_profiles.sh on the GPU box) into profiles/:
    tools/collect_profiles.py <tag> <round-prefix, e.g. r1>"""
 import collections
 import csv
@@ -10,7 +10,7 @@ import sys
 
 tag, pre = sys.argv[1], sys.argv[2]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-go = os.path.join(root, "gpurun_out")
+go = os.path.join(root, os.environ.get("PROFILE_RUNS", "profile_runs"))
 prof = os.path.join(root, "profiles")
 
 

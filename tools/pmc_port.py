@@ -7,7 +7,7 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = {}
 for prec in ("f32", "f64_fast"):
     rows = collections.defaultdict(dict)
-    for f in glob.glob(os.path.join(root, "gpurun_out", f"{tag}_port_{prec}", "**", "*counter_collection.csv"), recursive=True):
+    for f in glob.glob(os.path.join(root, os.environ.get("PROFILE_RUNS", "profile_runs"), f"{tag}_port_{prec}", "**", "*counter_collection.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
             if "erpl_flight" in r["Kernel_Name"]:
                 rows[r["Dispatch_Id"]][r["Counter_Name"]] = float(r["Counter_Value"])
