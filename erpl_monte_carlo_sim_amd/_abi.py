@@ -84,6 +84,41 @@ class ErplOut(C.Structure):
     ]
 
 
+# erpl_mc_analyze
+ANALYSIS_MAX_ROWS = 16
+ANALYSIS_MAX_Q = 8
+(WHY_NON_FINITE, WHY_APOGEE_HIGH, WHY_APOGEE_LOW, WHY_RANGE, WHY_FLIGHT_TIME, WHY_ENERGY) = (1 << k for k in range(6))
+WHY_NAMES = ("non_finite", "apogee_high", "apogee_low", "range", "flight_time", "energy_limit")   # lowest bit first
+END_NAMES = ("max_time", "ground_impact", "excessive_altitude", "coast_timeout", "apogee")
+
+_Q = C.c_double * ANALYSIS_MAX_Q
+
+
+class ErplAnalysisSpec(C.Structure):
+    _fields_ = [
+        ("max_apogee", C.c_double), ("min_apogee", C.c_double), ("max_range", C.c_double),
+        ("max_flight_time", C.c_double), ("energy_apogee", C.c_double),
+        ("n_rows", C.c_int32), ("rows", C.c_int32 * ANALYSIS_MAX_ROWS),
+        ("n_q", C.c_int32), ("q", _Q),
+    ]
+
+
+class ErplRowStats(C.Structure):
+    _fields_ = [
+        ("count", C.c_int64), ("mean", C.c_double), ("std", C.c_double), ("min", C.c_double), ("max", C.c_double),
+        ("quantile", _Q), ("order_lo", _Q), ("order_hi", _Q),
+    ]
+
+
+class ErplAnalysis(C.Structure):
+    _fields_ = [
+        ("n", C.c_int64), ("n_valid", C.c_int64), ("n_outliers", C.c_int64),
+        ("reason_counts", C.c_int64 * 6), ("termination_counts", C.c_int64 * 5),
+        ("n_status_nan", C.c_int64), ("n_incomplete", C.c_int64),
+        ("row", ErplRowStats * ANALYSIS_MAX_ROWS),
+    ]
+
+
 LIB_NAME = "liberpl_mc.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
@@ -97,7 +132,8 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_legacy_random_streams", "erpl_mc_legacy_wind_profiles", "erpl_mc_set_waves_per_simd",
            "erpl_mc_set_overlap", "erpl_mc_submit_batch", "erpl_mc_wait_batch", "erpl_mc_synchronize",
            "erpl_mc_debug_eval", "erpl_mc_synth_wind", "erpl_mc_set_adopt", "erpl_mc_get_overlap",
-           "erpl_mc_check_batch", "erpl_mc_set_adopt_spin", "erpl_mc_set_short_flight_overlap")
+           "erpl_mc_check_batch", "erpl_mc_set_adopt_spin", "erpl_mc_set_short_flight_overlap",
+           "erpl_mc_analysis_defaults", "erpl_mc_analyze")
 
 _lib = None
 
@@ -161,6 +197,9 @@ def load_library(path=None):
     lib.erpl_mc_debug_counters.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.erpl_mc_extract_histories.argtypes = [C.c_void_p, C.POINTER(ErplBatch), C.c_int64, C.c_void_p, C.c_int64,
                                               C.c_double, C.c_void_p, C.c_void_p]
+    lib.erpl_mc_analysis_defaults.argtypes = [C.POINTER(ErplAnalysisSpec)]
+    lib.erpl_mc_analyze.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplAnalysisSpec),
+                                    C.POINTER(ErplAnalysis), C.c_void_p, C.c_void_p]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if a declared symbol is not exported
         if name not in ("erpl_mc_last_error",):

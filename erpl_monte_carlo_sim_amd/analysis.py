@@ -153,3 +153,42 @@ def device_statistics(summary, status=None):
         if n_inc:   # a lane hand-over timed out: these samples were never integrated (include/erpl_mc.h)
             raise _abi.IncompleteBatch(f"{n_inc} sample(s) carry ERPL_ST_INCOMPLETE: refusing to compute statistics on them")
     return out
+
+
+def _row_dict(r, n_q):
+    return {"count": int(r.count), "mean": r.mean, "std": r.std, "min": r.min, "max": r.max,
+            "percentiles": list(r.quantile[:n_q]), "order_lo": list(r.order_lo[:n_q]), "order_hi": list(r.order_hi[:n_q])}
+
+
+def native_statistics(summary, status=None, engine=None, rows=None, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95)):
+    """`device_statistics` through the library's own kernels (erpl_mc_analyze) instead of torch ops: the same keys with
+    the same meaning, from a handful of streaming passes and an exact radix selection instead of three full sorts, plus
+    `reason_counts` (why samples were filtered), `outlier_reason_bits` (uint8 device tensor, _abi.WHY_*) and `rows`
+    (statistics of every requested summary row, with the two order statistics behind each percentile).
+    CUDA tensors only: `device_statistics` stays the implementation for CPU tensors."""
+    from . import _abi
+    if engine is None:
+        from .simulator import shared_engine
+        engine = shared_engine(summary.device)
+    named = (("apogee_altitude", _abi.SUM_APOGEE_ALT), ("range", _abi.SUM_RANGE), ("flight_time", _abi.SUM_FLIGHT_TIME))
+    wanted = [r for _, r in named] if rows is None else [int(r) for r in rows]
+    described = wanted + [r for _, r in named if r not in wanted]
+    quantiles = [float(q) for q in quantiles]
+    try:
+        res, why = engine.analyze(summary, status, rows=described, quantiles=quantiles, reasons=True)
+    except _abi.IncompleteBatch as e:
+        raise _abi.IncompleteBatch(f"{e}: refusing to compute statistics on them") from None
+    if res.n_valid == 0:
+        raise ValueError("No physically reasonable simulation results after outlier filtering")
+    stats = {r: _row_dict(res.row[j], len(quantiles)) for j, r in enumerate(described)}
+    out = {"n_samples": int(res.n_valid), "n_failed": 0, "n_outliers": int(res.n_outliers)}
+    for name, r in named:
+        out[name] = {k: stats[r][k] for k in ("mean", "std", "min", "max", "percentiles")}
+    out["valid_mask"] = why == 0
+    out["reason_counts"] = {name: int(res.reason_counts[k]) for k, name in enumerate(_abi.WHY_NAMES)}
+    out["outlier_reason_bits"] = why
+    out["rows"] = {r: stats[r] for r in wanted}
+    if status is not None:
+        out["termination_counts"] = {name: int(res.termination_counts[k]) for k, name in enumerate(_abi.END_NAMES)}
+        out["n_non_finite"] = int(res.n_status_nan)
+    return out

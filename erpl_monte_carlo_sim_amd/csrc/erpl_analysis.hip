@@ -1,0 +1,333 @@
+// erpl_analysis.hip — the device passes of erpl_mc_analyze: outlier filter, moments and exact order statistics of the
+// per-sample summary, replacing _filter_physics_outliers + _analyze_results of the reference (monte_carlo.py:337-473).
+//
+// Every pass streams rows of the [16][n] summary once, coalesced, on a grid that is a function of n alone:
+//   classify   reason byte of every sample from the three filter rows; counters per workgroup (no atomics)
+//   moments    per described row: masked sum / count / min / max, then (x - mean)^2 with the mean read on the device
+//   select     most-significant-digit radix selection of all order statistics of a row together: eight passes of one
+//              8-bit digit histogram per group of targets that still share a key prefix (LDS integer atomics, flushed to
+//              64-bit global bins), a small kernel between passes that fixes the next digit of every target
+// Sums are accumulated per thread in index order and reduced in a fixed tree; integer adds commute.  So the result is the
+// same bits in every call.  No floating-point atomics.  Compiled with -ffp-contract=off: (x - mean)^2 is rounded as np.std
+// rounds it.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "erpl_tables.h"
+
+namespace {
+
+constexpr int kWaves = ERPL_ANA_BLOCK / 64;
+
+__device__ __forceinline__ bool finite_bits(double v) {
+  return (__double_as_longlong(v) & 0x7ff0000000000000ll) != 0x7ff0000000000000ll;
+}
+// order-preserving map of a finite double onto an unsigned key (-0.0 sorts just below +0.0, which compare equal)
+__device__ __forceinline__ unsigned long long key_of(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  return b ^ ((b >> 63) ? ~0ull : (1ull << 63));
+}
+
+// ---- classify: one sample per thread and iteration; the counts of a wave are ballots (uniform), the workgroup's go to
+// its own slot of work->cpart
+__global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_classify(const ErplAnaArgs a) {
+  __shared__ unsigned long long s_cnt[kWaves][ERPL_ANA_COUNTERS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
+  const double* __restrict__ apo_p = a.summary + (int64_t)ERPL_SUM_APOGEE_ALT * n;
+  const double* __restrict__ rng_p = a.summary + (int64_t)ERPL_SUM_RANGE * n;
+  const double* __restrict__ ft_p = a.summary + (int64_t)ERPL_SUM_FLIGHT_TIME * n;
+  unsigned long long cnt[ERPL_ANA_COUNTERS];
+#pragma unroll
+  for (int k = 0; k < ERPL_ANA_COUNTERS; ++k) cnt[k] = 0ull;
+  // the loop bound is uniform over the wave: every lane takes part in every ballot
+  for (int64_t base = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + wave * 64; base < n; base += stride) {
+    const int64_t i = base + lane;
+    const bool in = i < n;
+    int why = 0, st = -1;
+    if (in) {
+      const double apo = apo_p[i], rng = rng_p[i], ft = ft_p[i];
+      if (!finite_bits(apo) || !finite_bits(rng) || !finite_bits(ft)) why |= ERPL_WHY_NON_FINITE;
+      if (apo > a.max_apogee) why |= ERPL_WHY_APOGEE_HIGH;
+      else if (apo < a.min_apogee) why |= ERPL_WHY_APOGEE_LOW;
+      if (rng > a.max_range) why |= ERPL_WHY_RANGE;
+      if (ft > a.max_flight_time) why |= ERPL_WHY_FLIGHT_TIME;
+      if (apo > a.energy_apogee) why |= ERPL_WHY_ENERGY;
+      a.why[i] = (uint8_t)why;
+      if (a.reasons) a.reasons[i] = (uint8_t)why;
+      if (a.status) st = a.status[i];
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) cnt[k] += __popcll(__ballot(in && (why & (1 << k))));
+    if (a.status) {
+#pragma unroll
+      for (int k = 0; k < 5; ++k) cnt[6 + k] += __popcll(__ballot(in && (st & 0xFF) == k));
+      cnt[11] += __popcll(__ballot(in && (st & ERPL_ST_NAN)));
+      cnt[12] += __popcll(__ballot(in && (st & ERPL_ST_INCOMPLETE)));
+    }
+    cnt[13] += __popcll(__ballot(in && why == 0));
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < ERPL_ANA_COUNTERS; ++k) s_cnt[wave][k] = cnt[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < ERPL_ANA_COUNTERS) {
+    unsigned long long s = 0ull;
+    for (int w = 0; w < kWaves; ++w) s += s_cnt[w][threadIdx.x];
+    a.work->cpart[blockIdx.x][threadIdx.x] = s;
+  }
+}
+
+// ---- moments.  SECOND = false: sum, count, min, max of the valid finite values of row rows[blockIdx.y];
+// SECOND = true: sum of (x - mean)^2 with the mean of the first pass.
+template <bool SECOND>
+__global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_moments(const ErplAnaArgs a) {
+  __shared__ double s_sum[kWaves], s_min[kWaves], s_max[kWaves];
+  __shared__ unsigned long long s_cnt[kWaves];
+  const int r = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
+  const double* __restrict__ x = a.summary + (int64_t)a.rows[r] * n;
+  const uint8_t* __restrict__ why = a.why;
+  const double mean = SECOND ? a.work->res.row[r].mean : 0.0;
+  double sum = 0.0, mn = INFINITY, mx = -INFINITY;
+  unsigned long long cnt = 0ull;
+  for (int64_t i = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + threadIdx.x; i < n; i += stride) {
+    const double v = x[i];
+    if (why[i] == 0 && finite_bits(v)) {
+      if (SECOND) {
+        const double d = v - mean;
+        sum += d * d;
+      } else {
+        sum += v;
+        ++cnt;
+        mn = v < mn ? v : mn;
+        mx = v > mx ? v : mx;
+      }
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    sum += __shfl_down(sum, off);
+    if (!SECOND) {
+      cnt += __shfl_down(cnt, off);
+      const double m0 = __shfl_down(mn, off), m1 = __shfl_down(mx, off);
+      mn = m0 < mn ? m0 : mn;
+      mx = m1 > mx ? m1 : mx;
+    }
+  }
+  if (lane == 0) { s_sum[wave] = sum; s_min[wave] = mn; s_max[wave] = mx; s_cnt[wave] = cnt; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kWaves; ++w) {
+      sum += s_sum[w];
+      if (!SECOND) { cnt += s_cnt[w]; mn = s_min[w] < mn ? s_min[w] : mn; mx = s_max[w] > mx ? s_max[w] : mx; }
+    }
+    a.work->psum[r][blockIdx.x] = sum;
+    if (!SECOND) { a.work->pcnt[r][blockIdx.x] = cnt; a.work->pmin[r][blockIdx.x] = mn; a.work->pmax[r][blockIdx.x] = mx; }
+  }
+}
+
+// Sum of the first `nb` doubles of p by one workgroup of ERPL_ANA_BLOCK threads: thread t adds its four neighbours in
+// index order, then the fixed tree.  Valid in thread 0.
+__device__ double block_sum(const double* p, int nb, double* s_wave) {
+  constexpr int per = ERPL_ANA_MAX_BLOCKS / ERPL_ANA_BLOCK;
+  double s = 0.0;
+  for (int k = 0; k < per; ++k) { const int j = threadIdx.x * per + k; if (j < nb) s += p[j]; }
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+  __syncthreads();   // s_wave may still be read from an earlier call
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) for (int w = 1; w < kWaves; ++w) s += s_wave[w];
+  return s;
+}
+
+// ---- after the first moment pass: workgroup r < n_rows finishes row r and sets up its selection; workgroup n_rows adds
+// up the classify counters
+__global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_finish_first(const ErplAnaArgs a, const int nb) {
+  __shared__ double s_wave[kWaves], s_min[kWaves], s_max[kWaves];
+  __shared__ unsigned long long s_cnt[ERPL_ANA_BLOCK];
+  ErplAnaWork* w = a.work;
+  if ((int)blockIdx.x == a.n_rows) {
+    // thread = (slice of 64 workgroups, counter)
+    const int c = threadIdx.x % ERPL_ANA_COUNTERS, slice = threadIdx.x / ERPL_ANA_COUNTERS;
+    constexpr int slices = ERPL_ANA_BLOCK / ERPL_ANA_COUNTERS, per = ERPL_ANA_MAX_BLOCKS / slices;
+    unsigned long long s = 0ull;
+    for (int k = 0; k < per; ++k) { const int j = slice * per + k; if (j < nb) s += w->cpart[j][c]; }
+    s_cnt[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x < ERPL_ANA_COUNTERS) {
+      for (int k = 1; k < slices; ++k) s += s_cnt[k * ERPL_ANA_COUNTERS + threadIdx.x];
+      w->res.counter[threadIdx.x] = s;
+    }
+    return;
+  }
+  const int r = blockIdx.x;
+  constexpr int per = ERPL_ANA_MAX_BLOCKS / ERPL_ANA_BLOCK;
+  const double sum = block_sum(w->psum[r], nb, s_wave);
+  unsigned long long cnt = 0ull;
+  double mn = INFINITY, mx = -INFINITY;
+  for (int k = 0; k < per; ++k) {
+    const int j = threadIdx.x * per + k;
+    if (j < nb) {
+      cnt += w->pcnt[r][j];
+      mn = w->pmin[r][j] < mn ? w->pmin[r][j] : mn;
+      mx = w->pmax[r][j] > mx ? w->pmax[r][j] : mx;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    cnt += __shfl_down(cnt, off);
+    const double m0 = __shfl_down(mn, off), m1 = __shfl_down(mx, off);
+    mn = m0 < mn ? m0 : mn;
+    mx = m1 > mx ? m1 : mx;
+  }
+  if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6] = cnt; s_min[threadIdx.x >> 6] = mn; s_max[threadIdx.x >> 6] = mx; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < kWaves; ++k) { cnt += s_cnt[k]; mn = s_min[k] < mn ? s_min[k] : mn; mx = s_max[k] > mx ? s_max[k] : mx; }
+    ErplAnaRow& o = w->res.row[r];
+    o.count = cnt; o.sum = sum; o.vmin = mn; o.vmax = mx; o.m2 = 0.0;
+    o.mean = sum / (double)cnt;   // NaN for an empty row; the host reports every double of such a row as NaN
+    // ranks of the two order statistics behind every quantile (np.percentile, linear)
+    ErplAnaSelect& s = w->sel[r];
+    for (int t = 0; t < ERPL_ANA_TARGETS; ++t) {
+      unsigned long long rank = 0ull;
+      if (cnt > 0ull && t < 2 * a.n_q) {
+        const double pos = a.q[t >> 1] * (double)(cnt - 1ull);
+        unsigned long long lo = (unsigned long long)floor(pos);
+        if (lo > cnt - 1ull) lo = cnt - 1ull;
+        rank = (t & 1) ? (lo + 1ull < cnt ? lo + 1ull : cnt - 1ull) : lo;
+      }
+      s.prefix[t] = 0ull; s.rank[t] = rank; s.leader[t] = 0;
+      o.key[t] = 0ull;
+    }
+  }
+}
+
+__global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_finish_second(const ErplAnaArgs a, const int nb) {
+  __shared__ double s_wave[kWaves];
+  const double m2 = block_sum(a.work->psum[blockIdx.x], nb, s_wave);
+  if (threadIdx.x == 0) a.work->res.row[blockIdx.x].m2 = m2;
+}
+
+// ---- one selection pass: histogram of the digit at `shift` of the keys that match a target's prefix above it.  Targets
+// with the same prefix see the same keys: only the first of them (its leader) keeps a histogram.
+__global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_histogram(const ErplAnaArgs a, const int shift) {
+  __shared__ unsigned int s_hist[ERPL_ANA_TARGETS][ERPL_ANA_BINS];   // 16 KB
+  __shared__ unsigned long long s_prefix[ERPL_ANA_TARGETS];
+  __shared__ int s_lead[ERPL_ANA_TARGETS];
+  __shared__ int s_nlead;
+  const int r = blockIdx.y, nt = 2 * a.n_q;
+  const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
+  const double* __restrict__ x = a.summary + (int64_t)a.rows[r] * n;
+  const uint8_t* __restrict__ why = a.why;
+  const ErplAnaSelect& sel = a.work->sel[r];
+  for (int k = threadIdx.x; k < ERPL_ANA_TARGETS * ERPL_ANA_BINS; k += ERPL_ANA_BLOCK) (&s_hist[0][0])[k] = 0u;
+  if (threadIdx.x == 0) {
+    int m = 0;
+    for (int t = 0; t < nt; ++t)
+      if (sel.leader[t] == t) { s_lead[m] = t; s_prefix[m] = sel.prefix[t]; ++m; }
+    s_nlead = m;
+  }
+  __syncthreads();
+  const int nlead = s_nlead;
+  // bits above the digit of this pass (none in the first pass: every key matches)
+  const unsigned long long above = shift >= 56 ? 0ull : (~0ull << (shift + 8));
+  const int64_t first = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + (threadIdx.x & ~63);
+  for (int64_t base = first; base < n; base += stride) {   // uniform over the wave (ballots below)
+    const int64_t i = base + (threadIdx.x & 63);
+    bool use = false;
+    unsigned long long key = 0ull;
+    if (i < n) {
+      const double v = x[i];
+      use = why[i] == 0 && finite_bits(v);
+      key = key_of(v);
+    }
+    const unsigned int digit = (unsigned int)(key >> shift) & (ERPL_ANA_BINS - 1);
+    for (int m = 0; m < nlead; ++m) {
+      const bool hit = use && ((key ^ s_prefix[m]) & above) == 0ull;
+      const unsigned long long mask = __ballot(hit);
+      if (mask == 0ull) continue;
+      // heavily tied data puts a whole wave into one bin: one add of the lane count instead of 64 serialised ones
+      const int lead_lane = __ffsll((long long)mask) - 1;
+      const unsigned int d0 = (unsigned int)__shfl((int)digit, lead_lane);
+      if (__ballot(hit && digit != d0) == 0ull) {
+        if ((int)(threadIdx.x & 63) == lead_lane) atomicAdd(&s_hist[s_lead[m]][d0], (unsigned int)__popcll(mask));
+      } else if (hit) {
+        atomicAdd(&s_hist[s_lead[m]][digit], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  for (int m = 0; m < nlead; ++m) {
+    const int t = s_lead[m];
+    for (int b = threadIdx.x; b < ERPL_ANA_BINS; b += ERPL_ANA_BLOCK) {
+      const unsigned int c = s_hist[t][b];
+      if (c) atomicAdd(&a.work->hist[r][t][b], (unsigned long long)c);
+    }
+  }
+}
+
+// ---- between the passes: wave t of workgroup r scans the histogram of target t's group, fixes the digit that holds its
+// rank and reduces the rank to that bin; then the groups are formed again and the histograms are cleared.
+__global__ __launch_bounds__(64 * ERPL_ANA_TARGETS) void erpl_ana_scan(const ErplAnaArgs a, const int shift) {
+  __shared__ unsigned long long s_prefix[ERPL_ANA_TARGETS];
+  const int r = blockIdx.x, t = threadIdx.x >> 6, lane = threadIdx.x & 63, nt = 2 * a.n_q;
+  ErplAnaSelect& sel = a.work->sel[r];
+  if (t < nt) {
+    const unsigned long long* h = a.work->hist[r][sel.leader[t]];
+    const unsigned long long rank = sel.rank[t];
+    unsigned long long c[4], s = 0ull;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { c[k] = h[lane * 4 + k]; s += c[k]; }
+    unsigned long long incl = s;
+    for (int off = 1; off < 64; off <<= 1) {
+      const unsigned long long up = __shfl_up(incl, off);
+      if (lane >= off) incl += up;
+    }
+    unsigned long long before = incl - s;
+    unsigned long long prefix = sel.prefix[t];
+    if (lane == 0) s_prefix[t] = prefix;   // stays if no bin holds the rank: an empty row
+    if (before <= rank && rank < incl) {   // exactly one lane
+      int d = 0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        if (rank >= before + c[k] && d == k) { before += c[k]; d = k + 1; }
+      prefix |= (unsigned long long)(lane * 4 + d) << shift;
+      sel.prefix[t] = prefix;
+      sel.rank[t] = rank - before;
+      a.work->res.row[r].key[t] = prefix;
+      s_prefix[t] = prefix;
+    }
+  }
+  __syncthreads();   // every histogram has been read, every prefix is known
+  if (lane == 0 && t < nt) {
+    int lead = t;
+    for (int u = t - 1; u >= 0; --u) if (s_prefix[u] == s_prefix[t]) lead = u;
+    sel.leader[t] = lead;
+  }
+  unsigned long long* h = &a.work->hist[r][0][0];
+  for (int k = threadIdx.x; k < ERPL_ANA_TARGETS * ERPL_ANA_BINS; k += 64 * ERPL_ANA_TARGETS) h[k] = 0ull;
+}
+
+}  // namespace
+
+int erpl_launch_analysis(const ErplAnaArgs& a, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t want = (a.n + ERPL_ANA_BLOCK - 1) / ERPL_ANA_BLOCK;
+  const int nb = (int)(want < ERPL_ANA_MAX_BLOCKS ? want : ERPL_ANA_MAX_BLOCKS);
+  hipError_t e = hipMemsetAsync(&a.work->hist[0][0][0], 0, sizeof(a.work->hist), st);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(erpl_ana_classify, dim3(nb), dim3(ERPL_ANA_BLOCK), 0, st, a);
+  if (a.n_rows > 0) hipLaunchKernelGGL(erpl_ana_moments<false>, dim3(nb, a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a);
+  hipLaunchKernelGGL(erpl_ana_finish_first, dim3(a.n_rows + 1), dim3(ERPL_ANA_BLOCK), 0, st, a, nb);
+  if (a.n_rows > 0) {
+    hipLaunchKernelGGL(erpl_ana_moments<true>, dim3(nb, a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a);
+    hipLaunchKernelGGL(erpl_ana_finish_second, dim3(a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a, nb);
+    if (a.n_q > 0)
+      for (int shift = 56; shift >= 0; shift -= 8) {
+        hipLaunchKernelGGL(erpl_ana_histogram, dim3(nb, a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a, shift);
+        hipLaunchKernelGGL(erpl_ana_scan, dim3(a.n_rows), dim3(64 * ERPL_ANA_TARGETS), 0, st, a, shift);
+      }
+  }
+  return (int)hipGetLastError();
+}

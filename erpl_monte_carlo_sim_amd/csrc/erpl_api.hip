@@ -284,6 +284,11 @@ struct erpl_ctx {
   bool profiling = false;
   long long profiled_runs = 0;
   hipEvent_t ev[3 * ERPL_PROFILE_RING] = {};
+  // erpl_mc_analyze: fixed block (partials, histograms, counters), one reason byte per sample, pinned copy of the result
+  ErplAnaWork* ana_work = nullptr;
+  uint8_t* ana_why = nullptr;
+  int64_t ana_cap = 0;
+  ErplAnaResult* ana_host = nullptr;
 };
 
 namespace {
@@ -545,6 +550,8 @@ int erpl_mc_destroy(erpl_ctx* c) {
   for (int i = 0; i < 3 * ERPL_PROFILE_RING; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
   for (int i = 0; i < ERPL_TICKET_RING; ++i) if (c->ring_done[i]) (void)hipEventDestroy(c->ring_done[i]);
   if (c->ring_counters) (void)hipHostFree(c->ring_counters);
+  (void)hipFree(c->ana_work); (void)hipFree(c->ana_why);
+  if (c->ana_host) (void)hipHostFree(c->ana_host);
   delete c;
   return ERPL_OK;
 }
@@ -1077,6 +1084,136 @@ int erpl_mc_ticket_stats(erpl_ctx* c, int64_t ticket, double* total_steps, doubl
   if (total_steps) *total_steps = (double)c->ring_counters[4 * ri + 1];
   if (wave_iterations) *wave_iterations = (double)c->ring_counters[4 * ri + 2];
   if (c->ring_counters[4 * ri + 3] != 0ull) return report_incomplete(ticket, c->ring_counters[4 * ri + 3]);
+  return ERPL_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------- erpl_mc_analyze
+namespace {
+
+// The only place the analysis workspace grows (the policy of erpl_mc_reserve): the fixed block with the first call, the
+// reason bytes when n exceeds what they have held before.  Freed by erpl_mc_destroy.
+int analysis_reserve(erpl_ctx* c, int64_t n) {
+  if (!c->ana_work) HIP_TRY(hipMalloc((void**)&c->ana_work, sizeof(ErplAnaWork)));
+  if (!c->ana_host) HIP_TRY(hipHostMalloc((void**)&c->ana_host, sizeof(ErplAnaResult), hipHostMallocDefault));
+  if (n <= c->ana_cap) return ERPL_OK;
+  HIP_TRY(hipDeviceSynchronize());   // an earlier analysis on another stream may still read the old bytes
+  (void)hipFree(c->ana_why);
+  c->ana_why = nullptr; c->ana_cap = 0;
+  HIP_TRY(hipMalloc((void**)&c->ana_why, (size_t)n));
+  c->ana_cap = n;
+  return ERPL_OK;
+}
+
+double double_of_key(unsigned long long k) {
+  const unsigned long long b = k ^ ((k >> 63) ? (1ull << 63) : ~0ull);
+  double v;
+  memcpy(&v, &b, sizeof(v));
+  return v;
+}
+
+int check_analysis_spec(const erpl_analysis_spec* s) {
+  const double bound[5] = {s->max_apogee, s->min_apogee, s->max_range, s->max_flight_time, s->energy_apogee};
+  const char* name[5] = {"max_apogee", "min_apogee", "max_range", "max_flight_time", "energy_apogee"};
+  for (int k = 0; k < 5; ++k)
+    if (std::isnan(bound[k])) return fail(ERPL_ERR_INVALID, "spec->%s is NaN", name[k]);
+  if (s->n_rows < 0 || s->n_rows > ERPL_ANALYSIS_MAX_ROWS)
+    return fail(ERPL_ERR_INVALID, "spec->n_rows = %d outside 0..%d", s->n_rows, ERPL_ANALYSIS_MAX_ROWS);
+  if (s->n_q < 0 || s->n_q > ERPL_ANALYSIS_MAX_Q)
+    return fail(ERPL_ERR_INVALID, "spec->n_q = %d outside 0..%d", s->n_q, ERPL_ANALYSIS_MAX_Q);
+  for (int j = 0; j < s->n_rows; ++j) {
+    if (s->rows[j] < 0 || s->rows[j] >= ERPL_SUMMARY_DIM)
+      return fail(ERPL_ERR_INVALID, "spec->rows[%d] = %d outside 0..%d", j, s->rows[j], ERPL_SUMMARY_DIM - 1);
+    for (int k = 0; k < j; ++k)
+      if (s->rows[k] == s->rows[j]) return fail(ERPL_ERR_INVALID, "spec->rows[%d] = %d is listed twice", j, s->rows[j]);
+  }
+  for (int j = 0; j < s->n_q; ++j)
+    if (!(s->q[j] >= 0.0 && s->q[j] <= 1.0)) return fail(ERPL_ERR_INVALID, "spec->q[%d] = %g outside [0, 1]", j, s->q[j]);
+  return ERPL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int erpl_mc_analysis_defaults(erpl_analysis_spec* spec) {
+  if (!spec) return fail(ERPL_ERR_INVALID, "spec is NULL");
+  memset(spec, 0, sizeof(*spec));
+  spec->max_apogee = 80000.0;        // monte_carlo.py:343-346
+  spec->min_apogee = 100.0;
+  spec->max_range = 200000.0;
+  spec->max_flight_time = 600.0;
+  const double v_max = 1200.0, g = 9.81;
+  const double h_max = v_max * v_max / (2 * g);   // monte_carlo.py:349-353: theoretical_max_altitude, then * 1.2
+  spec->energy_apogee = h_max * 1.2;
+  spec->n_rows = 3;
+  spec->rows[0] = ERPL_SUM_APOGEE_ALT; spec->rows[1] = ERPL_SUM_RANGE; spec->rows[2] = ERPL_SUM_FLIGHT_TIME;
+  spec->n_q = 5;
+  const double q[5] = {0.05, 0.25, 0.5, 0.75, 0.95};
+  for (int j = 0; j < 5; ++j) spec->q[j] = q[j];
+  return ERPL_OK;
+}
+
+int erpl_mc_analyze(erpl_ctx* c, const double* summary, const int32_t* status, int64_t n, const erpl_analysis_spec* spec,
+                    erpl_analysis* result, uint8_t* reasons, void* stream) {
+  // spec, n and the pointers before the context: the argument checks need no device
+  if (!spec) return fail(ERPL_ERR_INVALID, "spec is NULL");
+  int rc = check_analysis_spec(spec);
+  if (rc != ERPL_OK) return rc;
+  if (n <= 0) return fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
+  if (!summary) return fail(ERPL_ERR_INVALID, "summary is NULL");
+  if (!result) return fail(ERPL_ERR_INVALID, "result is NULL");
+  if (!c) return fail(ERPL_ERR_INVALID, "ctx is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  rc = analysis_reserve(c, n);
+  if (rc != ERPL_OK) return rc;
+  ErplAnaArgs a;
+  memset(&a, 0, sizeof(a));
+  a.summary = summary; a.status = status; a.why = c->ana_why; a.reasons = reasons; a.work = c->ana_work; a.n = n;
+  a.max_apogee = spec->max_apogee; a.min_apogee = spec->min_apogee; a.max_range = spec->max_range;
+  a.max_flight_time = spec->max_flight_time; a.energy_apogee = spec->energy_apogee;
+  a.n_rows = spec->n_rows; a.n_q = spec->n_q;
+  for (int j = 0; j < spec->n_rows; ++j) a.rows[j] = spec->rows[j];
+  for (int j = 0; j < spec->n_q; ++j) a.q[j] = spec->q[j];
+  const int le = erpl_launch_analysis(a, stream);
+  if (le != 0) return fail(ERPL_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)le));
+  HIP_TRY(hipMemcpyAsync(c->ana_host, &c->ana_work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+
+  const ErplAnaResult& d = *c->ana_host;
+  memset(result, 0, sizeof(*result));
+  result->n = n;
+  result->n_valid = (int64_t)d.counter[13];
+  result->n_outliers = n - result->n_valid;
+  for (int k = 0; k < 6; ++k) result->reason_counts[k] = (int64_t)d.counter[k];
+  for (int k = 0; k < 5; ++k) result->termination_counts[k] = (int64_t)d.counter[6 + k];
+  result->n_status_nan = (int64_t)d.counter[11];
+  result->n_incomplete = (int64_t)d.counter[12];
+  const double nan = NAN;
+  for (int j = 0; j < ERPL_ANALYSIS_MAX_ROWS; ++j) {
+    erpl_row_stats& o = result->row[j];
+    const bool described = j < spec->n_rows;
+    const ErplAnaRow& r = d.row[j];
+    o.count = described ? (int64_t)r.count : 0;
+    const bool any = described && r.count > 0ull;
+    const double cnt = (double)r.count;
+    o.mean = any ? r.mean : nan;
+    o.std = any ? sqrt(r.m2 / cnt) : nan;
+    o.min = any ? r.vmin : nan;
+    o.max = any ? r.vmax : nan;
+    for (int k = 0; k < ERPL_ANALYSIS_MAX_Q; ++k) {
+      if (!any || k >= spec->n_q) { o.quantile[k] = o.order_lo[k] = o.order_hi[k] = nan; continue; }
+      const double pos = spec->q[k] * (double)(r.count - 1ull);   // as on the device, which chose the ranks from it
+      const double lo = floor(pos);
+      o.order_lo[k] = double_of_key(r.key[2 * k]);
+      o.order_hi[k] = double_of_key(r.key[2 * k + 1]);
+      o.quantile[k] = o.order_lo[k] + (o.order_hi[k] - o.order_lo[k]) * (pos - lo);
+    }
+  }
+  if (result->n_incomplete > 0)
+    return fail(ERPL_ERR_INCOMPLETE, "%lld sample(s) carry ERPL_ST_INCOMPLETE: they were never integrated",
+                (long long)result->n_incomplete);
   return ERPL_OK;
 }
 

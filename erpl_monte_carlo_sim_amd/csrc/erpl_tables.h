@@ -154,3 +154,56 @@ int erpl_launch_debug_f64f(const ErplKArgs& a, const void* scalars, int what, in
 // a.n_traj = sample index, a.summary = out [m][ERPL_DIAG_DIM]
 int erpl_launch_extract_f64(const ErplKArgs& a, const void* scalars, double time_offset, void* stream);
 }
+
+// ---- erpl_mc_analyze: outlier filter + exact statistics on the summary (erpl_analysis.hip) ----
+#define ERPL_ANA_BLOCK 256        // threads per workgroup of the streaming passes
+#define ERPL_ANA_MAX_BLOCKS 1024  // their grid: min(this, ceil(n / ERPL_ANA_BLOCK)) - a function of n alone, so the
+                                  //   reduction has the same shape on every device and in every call (bitwise repeatable)
+#define ERPL_ANA_TARGETS (2 * ERPL_ANALYSIS_MAX_Q)   // order statistics selected per row: lo and hi of every quantile
+#define ERPL_ANA_BINS 256         // one 8-bit digit per selection pass, most significant first
+#define ERPL_ANA_COUNTERS 16      // [0..5] reason bits, [6..10] end codes, [11] ERPL_ST_NAN, [12] ERPL_ST_INCOMPLETE, [13] valid
+
+// What the device hands back (copied to a pinned block, finished on the host).
+struct ErplAnaRow {
+  unsigned long long count;                   // valid samples finite in this row
+  double sum, mean, m2, vmin, vmax;           // m2 = sum((x - mean)^2), second pass
+  unsigned long long key[ERPL_ANA_TARGETS];   // order-preserving keys of the selected order statistics
+};
+struct ErplAnaResult {
+  unsigned long long counter[ERPL_ANA_COUNTERS];
+  ErplAnaRow row[ERPL_ANALYSIS_MAX_ROWS];
+};
+// Selection state of one row: what is fixed of every target's key so far, its rank among the keys that share that
+// prefix, and the first target with the same prefix (targets that share a prefix share one histogram).
+struct ErplAnaSelect {
+  unsigned long long prefix[ERPL_ANA_TARGETS], rank[ERPL_ANA_TARGETS];
+  int32_t leader[ERPL_ANA_TARGETS];
+};
+// The fixed part of the workspace (the per-sample reason bytes are a second allocation that grows with n).
+struct ErplAnaWork {
+  ErplAnaResult res;
+  unsigned long long cpart[ERPL_ANA_MAX_BLOCKS][ERPL_ANA_COUNTERS];    // classify: counters per workgroup
+  double psum[ERPL_ANALYSIS_MAX_ROWS][ERPL_ANA_MAX_BLOCKS];            // moments: partials per row and workgroup
+  double pmin[ERPL_ANALYSIS_MAX_ROWS][ERPL_ANA_MAX_BLOCKS];
+  double pmax[ERPL_ANALYSIS_MAX_ROWS][ERPL_ANA_MAX_BLOCKS];
+  unsigned long long pcnt[ERPL_ANALYSIS_MAX_ROWS][ERPL_ANA_MAX_BLOCKS];
+  ErplAnaSelect sel[ERPL_ANALYSIS_MAX_ROWS];
+  unsigned long long hist[ERPL_ANALYSIS_MAX_ROWS][ERPL_ANA_TARGETS][ERPL_ANA_BINS];   // 64-bit digit histograms
+};
+struct ErplAnaArgs {
+  const double* summary;   // [ERPL_SUMMARY_DIM][n]
+  const int32_t* status;   // [n] or NULL
+  uint8_t* why;            // [n] workspace: reason bits of every sample
+  uint8_t* reasons;        // [n] caller's copy of the same, or NULL
+  ErplAnaWork* work;
+  int64_t n;
+  double max_apogee, min_apogee, max_range, max_flight_time, energy_apogee;
+  int32_t n_rows, n_q;
+  int32_t rows[ERPL_ANALYSIS_MAX_ROWS];
+  double q[ERPL_ANALYSIS_MAX_Q];
+};
+extern "C++" {
+// Enqueues every pass of erpl_mc_analyze on `stream`; afterwards a.work->res holds the device's part of the result.
+// Returns a hipError_t (0 = launched).
+int erpl_launch_analysis(const ErplAnaArgs& a, void* stream);
+}

@@ -251,6 +251,52 @@ class TrajectoryEngine:
         _abi.check(self.lib, rc, "erpl_mc_extract_histories")
         return out
 
+    def analysis_defaults(self):
+        """The reference's outlier bounds, rows and quantiles (erpl_mc_analysis_defaults)."""
+        spec = _abi.ErplAnalysisSpec()
+        _abi.check(self.lib, self.lib.erpl_mc_analysis_defaults(C.byref(spec)), "erpl_mc_analysis_defaults")
+        return spec
+
+    def analyze(self, summary, status=None, rows=None, quantiles=None, bounds=None, reasons=False):
+        """Outlier filter + exact statistics of a [16, n] summary on the device (erpl_mc_analyze), enqueued on the
+        current torch stream; blocks the host until the result is there.  rows: summary rows to describe (default
+        apogee, range, flight time); quantiles: fractions in [0, 1] (default 5/25/50/75/95 %); bounds: dict overriding
+        max_apogee / min_apogee / max_range / max_flight_time / energy_apogee.  Returns (_abi.ErplAnalysis, reason
+        bits [n] uint8 on the device or None).  Raises _abi.IncompleteBatch for status words with ST_INCOMPLETE."""
+        if not (summary.is_cuda and summary.device == self.device and summary.dtype == torch.float64
+                and summary.dim() == 2 and summary.shape[0] == _abi.SUMMARY_DIM and summary.is_contiguous()):
+            raise ValueError(f"summary must be a contiguous float64 [{_abi.SUMMARY_DIM}, n] tensor on {self.device}")
+        n = int(summary.shape[1])
+        if status is not None and not (status.device == self.device and status.dtype == torch.int32
+                                       and tuple(status.shape) == (n,) and status.is_contiguous()):
+            raise ValueError(f"status must be a contiguous int32 [n] tensor on {self.device}")
+        spec = self.analysis_defaults()
+        if rows is not None:
+            rows = [int(r) for r in rows]
+            if len(rows) > _abi.ANALYSIS_MAX_ROWS:
+                raise ValueError(f"at most {_abi.ANALYSIS_MAX_ROWS} rows")
+            spec.n_rows = len(rows)
+            spec.rows[:len(rows)] = rows
+        if quantiles is not None:
+            quantiles = [float(q) for q in quantiles]
+            if len(quantiles) > _abi.ANALYSIS_MAX_Q:
+                raise ValueError(f"at most {_abi.ANALYSIS_MAX_Q} quantiles")
+            spec.n_q = len(quantiles)
+            spec.q[:len(quantiles)] = quantiles
+        for key, val in (bounds or {}).items():
+            if key not in ("max_apogee", "min_apogee", "max_range", "max_flight_time", "energy_apogee"):
+                raise ValueError(f"unknown bound {key!r}")
+            setattr(spec, key, float(val))
+        why = torch.empty((n,), dtype=torch.uint8, device=self.device) if reasons else None
+        res = _abi.ErplAnalysis()
+        st = torch.cuda.current_stream(self.device)
+        rc = self.lib.erpl_mc_analyze(self._ctx, C.c_void_p(summary.data_ptr()),
+                                      C.c_void_p(status.data_ptr()) if status is not None else None, n, C.byref(spec),
+                                      C.byref(res), C.c_void_p(why.data_ptr()) if reasons else None,
+                                      C.c_void_p(st.cuda_stream))
+        _abi.check(self.lib, rc, "erpl_mc_analyze")
+        return res, why
+
     def set_profiling(self, enable=True):
         """Record HIP events around the two kernels on the launch stream (erpl_mc_set_profiling)."""
         _abi.check(self.lib, self.lib.erpl_mc_set_profiling(self._ctx, int(bool(enable))), "erpl_mc_set_profiling")

@@ -341,6 +341,70 @@ int erpl_mc_synth_wind(erpl_ctx* ctx, int64_t n, int32_t k, const double* normal
                        const double* rho, const double* innov, const double* base, const double* scale,
                        const double* mean_u, const double* mean_v, void* wind, int32_t precision, void* hip_stream);
 
+/* Outlier filter + statistics of a finished run ON THE DEVICE, replacing MonteCarloAnalyzer.
+ * _filter_physics_outliers + _analyze_results (monte_carlo.py:337-398, :400-473) for the scalar results:
+ * which samples are physically unreasonable and why, and count / mean / population std / min / max / quantiles
+ * of chosen summary rows over the samples that are left.
+ *
+ * Reason bits of sample i, in the order of the reason strings of monte_carlo.py:356-388, from the rows
+ * ERPL_SUM_APOGEE_ALT, ERPL_SUM_RANGE, ERPL_SUM_FLIGHT_TIME: NON_FINITE if one of the three is not finite;
+ * APOGEE_HIGH if apogee > max_apogee, otherwise APOGEE_LOW if apogee < min_apogee; RANGE if range > max_range;
+ * FLIGHT_TIME if flight_time > max_flight_time; ENERGY if apogee > energy_apogee (comparisons with NaN are false, as in
+ * Python).  A sample is valid iff it carries no bit.
+ *
+ * row[j] describes summary row spec->rows[j] over the samples that are valid AND finite in that row
+ * (monte_carlo.py:444-459 drops non-finite values): mean = sum / count, std = sqrt(sum((x - mean)^2) / count) in two
+ * passes (np.std), min / max exact.  For every q: pos = q * (count - 1), lo = floor(pos), hi = min(lo + 1, count - 1),
+ * order_lo / order_hi = the lo-th / hi-th smallest value, EXACT (radix selection on the bit patterns, no sort),
+ * quantile = order_lo + (order_hi - order_lo) * (pos - lo) (np.percentile, linear).  count == 0: every double of the
+ * row is NaN.  Sums are reduced in an order that depends on n alone and no floating-point atomics are used: two calls
+ * on the same inputs return the same bits. */
+#define ERPL_ANALYSIS_MAX_ROWS 16   /* = ERPL_SUMMARY_DIM */
+#define ERPL_ANALYSIS_MAX_Q 8
+
+enum { ERPL_WHY_NON_FINITE = 1, ERPL_WHY_APOGEE_HIGH = 2, ERPL_WHY_APOGEE_LOW = 4,
+       ERPL_WHY_RANGE = 8, ERPL_WHY_FLIGHT_TIME = 16, ERPL_WHY_ENERGY = 32 };
+
+typedef struct erpl_analysis_spec {
+  double max_apogee, min_apogee, max_range, max_flight_time, energy_apogee;  /* monte_carlo.py:343-353 */
+  int32_t n_rows;                        /* 0..ERPL_ANALYSIS_MAX_ROWS */
+  int32_t rows[ERPL_ANALYSIS_MAX_ROWS];  /* summary rows to describe, distinct, 0..15 */
+  int32_t n_q;                           /* 0..ERPL_ANALYSIS_MAX_Q */
+  double q[ERPL_ANALYSIS_MAX_Q];         /* quantile fractions in [0, 1] */
+} erpl_analysis_spec;
+
+typedef struct erpl_row_stats {
+  int64_t count;                         /* valid samples whose value in this row is finite */
+  double mean, std, min, max;            /* population std, as np.std */
+  double quantile[ERPL_ANALYSIS_MAX_Q];
+  double order_lo[ERPL_ANALYSIS_MAX_Q], order_hi[ERPL_ANALYSIS_MAX_Q];  /* the two order statistics behind it */
+} erpl_row_stats;
+
+typedef struct erpl_analysis {
+  int64_t n, n_valid, n_outliers;
+  int64_t reason_counts[6];              /* samples carrying each ERPL_WHY_* bit, lowest bit first */
+  int64_t termination_counts[5];         /* low status byte ERPL_END_*, over all n; zeros if status == NULL */
+  int64_t n_status_nan, n_incomplete;    /* ERPL_ST_NAN / ERPL_ST_INCOMPLETE words; zeros if status == NULL */
+  erpl_row_stats row[ERPL_ANALYSIS_MAX_ROWS];  /* row[j] describes spec->rows[j] */
+} erpl_analysis;
+
+/* Host only (no context, no device): the reference's bounds 80 km, 100 m, 200 km, 600 s and
+ * 1200^2 / (2 * 9.81) * 1.2 m (monte_carlo.py:343-353), rows {APOGEE_ALT, RANGE, FLIGHT_TIME},
+ * q {0.05, 0.25, 0.5, 0.75, 0.95} (monte_carlo.py:456). */
+int erpl_mc_analysis_defaults(erpl_analysis_spec* spec);
+/* summary [ERPL_SUMMARY_DIM][n], status [n] (may be NULL) and reasons [n] (may be NULL; receives the reason bits) are
+ * CALLER-OWNED device memory; spec and result are host memory.  The work is enqueued on `hip_stream` behind whatever is
+ * there (a batch handed over with erpl_mc_submit_batch is ordered into the stream with erpl_mc_wait_batch first) and the
+ * call returns when `result` is filled: it blocks the host on that stream.  The workspace (a fixed block of partials,
+ * histograms and counters plus one byte per sample) belongs to the context, grows only when n exceeds what it has held
+ * before and is freed by erpl_mc_destroy; calls on one context are serialised by the caller.
+ * Errors: ERPL_ERR_INVALID, before any device work and with a message that names the argument, for a NULL spec /
+ * summary / result / ctx (checked in that order, the context last), n <= 0, n_rows or n_q out of range, a row outside
+ * 0..15 or listed twice, a q outside [0, 1] or NaN, a NaN bound.  ERPL_ERR_INCOMPLETE, with `result` filled, if
+ * n_incomplete > 0: such samples were never integrated.  n_valid == 0 is no error. */
+int erpl_mc_analyze(erpl_ctx* ctx, const double* summary, const int32_t* status, int64_t n,
+                    const erpl_analysis_spec* spec, erpl_analysis* result, uint8_t* reasons, void* hip_stream);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
