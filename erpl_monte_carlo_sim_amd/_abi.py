@@ -7,7 +7,7 @@ been built (run `python -c "import __graft_entry__ as g; g.build()"` or
 import ctypes as C
 import os
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 STATE_DIM = 14
 IC_DIM = 13
 ROCKET_DIM = 2
@@ -119,6 +119,53 @@ class ErplAnalysis(C.Structure):
     ]
 
 
+# erpl_mc_histogram / erpl_mc_histogram_xy / erpl_mc_dispersion
+HIST_MAX_ROWS = 16
+HIST_MAX_BINS = 1024
+HIST2D_MAX_BINS = 256
+DISP_MAX_LEVELS = 8
+CENTRE_MEAN, CENTRE_POINT = 0, 1
+
+_HR_I = C.c_int32 * HIST_MAX_ROWS
+_HR_L = C.c_int64 * HIST_MAX_ROWS
+_HR_D = C.c_double * HIST_MAX_ROWS
+_LV_D = C.c_double * DISP_MAX_LEVELS
+
+
+class ErplHistSpec(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("rows", _HR_I), ("bins", _HR_I), ("lo", _HR_D), ("hi", _HR_D)]
+
+
+class ErplHistResult(C.Structure):
+    _fields_ = [("counted", _HR_L), ("below", _HR_L), ("above", _HR_L), ("lo", _HR_D), ("hi", _HR_D)]
+
+
+class ErplHist2dSpec(C.Structure):
+    _fields_ = [("row_x", C.c_int32), ("row_y", C.c_int32), ("bins_x", C.c_int32), ("bins_y", C.c_int32),
+                ("lo_x", C.c_double), ("hi_x", C.c_double), ("lo_y", C.c_double), ("hi_y", C.c_double)]
+
+
+class ErplHist2dResult(C.Structure):
+    _fields_ = [("counted", C.c_int64), ("outside", C.c_int64),
+                ("lo_x", C.c_double), ("hi_x", C.c_double), ("lo_y", C.c_double), ("hi_y", C.c_double)]
+
+
+class ErplDispersionSpec(C.Structure):
+    _fields_ = [("row_x", C.c_int32), ("row_y", C.c_int32), ("centre", C.c_int32), ("n_levels", C.c_int32),
+                ("cx", C.c_double), ("cy", C.c_double), ("level", _LV_D),
+                ("n_q", C.c_int32), ("reserved", C.c_int32), ("q", _Q)]
+
+
+class ErplDispersion(C.Structure):
+    _fields_ = [("count", C.c_int64),
+                ("mean_x", C.c_double), ("mean_y", C.c_double),
+                ("cov_xx", C.c_double), ("cov_xy", C.c_double), ("cov_yy", C.c_double),
+                ("var_major", C.c_double), ("var_minor", C.c_double), ("angle", C.c_double),
+                ("centre_x", C.c_double), ("centre_y", C.c_double),
+                ("k2", _LV_D), ("semi_major", _LV_D), ("semi_minor", _LV_D),
+                ("inside", C.c_int64 * DISP_MAX_LEVELS), ("miss", ErplRowStats)]
+
+
 LIB_NAME = "liberpl_mc.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
@@ -133,7 +180,9 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_set_overlap", "erpl_mc_submit_batch", "erpl_mc_wait_batch", "erpl_mc_synchronize",
            "erpl_mc_debug_eval", "erpl_mc_synth_wind", "erpl_mc_set_adopt", "erpl_mc_get_overlap",
            "erpl_mc_check_batch", "erpl_mc_set_adopt_spin", "erpl_mc_set_short_flight_overlap",
-           "erpl_mc_analysis_defaults", "erpl_mc_analyze")
+           "erpl_mc_analysis_defaults", "erpl_mc_analyze",
+           "erpl_mc_histogram_defaults", "erpl_mc_histogram", "erpl_mc_histogram_xy",
+           "erpl_mc_dispersion_defaults", "erpl_mc_dispersion")
 
 _lib = None
 
@@ -200,6 +249,14 @@ def load_library(path=None):
     lib.erpl_mc_analysis_defaults.argtypes = [C.POINTER(ErplAnalysisSpec)]
     lib.erpl_mc_analyze.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplAnalysisSpec),
                                     C.POINTER(ErplAnalysis), C.c_void_p, C.c_void_p]
+    lib.erpl_mc_histogram_defaults.argtypes = [C.POINTER(ErplHistSpec)]
+    lib.erpl_mc_histogram.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplHistSpec), C.c_void_p,
+                                      C.c_void_p, C.POINTER(ErplHistResult), C.c_void_p]
+    lib.erpl_mc_histogram_xy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplHist2dSpec), C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.POINTER(ErplHist2dResult), C.c_void_p]
+    lib.erpl_mc_dispersion_defaults.argtypes = [C.POINTER(ErplDispersionSpec)]
+    lib.erpl_mc_dispersion.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplDispersionSpec),
+                                       C.POINTER(ErplDispersion), C.c_void_p, C.c_void_p]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if a declared symbol is not exported
         if name not in ("erpl_mc_last_error",):

@@ -192,3 +192,42 @@ def native_statistics(summary, status=None, engine=None, rows=None, quantiles=(0
         out["termination_counts"] = {name: int(res.termination_counts[k]) for k, name in enumerate(_abi.END_NAMES)}
         out["n_non_finite"] = int(res.n_status_nan)
     return out
+
+
+def _engine_of(summary, engine):
+    if engine is None:
+        from .simulator import shared_engine
+        engine = shared_engine(summary.device)
+    return engine
+
+
+def native_distributions(summary, status=None, engine=None, bins=50, rows=None):
+    """The histograms `plot_results` draws (monte_carlo.py:568-592), counted on the device: erpl_mc_analyze for the reason
+    bytes, then erpl_mc_histogram over the samples that carry none - the filtered population `analysis['results']` holds.
+    rows: summary rows (default apogee, range, flight time); bins: one int or one per row.  Returns {row: {'edges',
+    'counts', 'counted'}} with NumPy arrays equal to np.histogram(valid finite values of the row, bins), plus
+    'valid_mask' (bool device tensor), 'outlier_reason_bits', 'n_samples' and 'n_outliers'."""
+    from . import _abi
+    engine = _engine_of(summary, engine)
+    rows = [_abi.SUM_APOGEE_ALT, _abi.SUM_RANGE, _abi.SUM_FLIGHT_TIME] if rows is None else [int(r) for r in rows]
+    res, why = engine.analyze(summary, status, rows=[], quantiles=[], reasons=True)
+    edges, counts, info = engine.histogram(summary, why, rows=rows, bins=bins)
+    out = {r: {"edges": edges[j], "counts": counts[j], "counted": int(info["counted"][j])} for j, r in enumerate(rows)}
+    out["valid_mask"] = why == 0
+    out["outlier_reason_bits"] = why
+    out["n_samples"], out["n_outliers"] = int(res.n_valid), int(res.n_outliers)
+    return out
+
+
+def landing_dispersion(summary, status=None, engine=None, target=None, levels=(0.5, 0.9, 0.99),
+                       quantiles=(0.5, 0.9, 0.95, 0.99)):
+    """Where the filtered population comes down (erpl_mc_analyze for the reason bytes, then erpl_mc_dispersion on the
+    impact point): mean, covariance, confidence ellipses with their empirical content and the miss distance about
+    `target` ((x, y), default the launch site at the origin) with its exact quantiles; 'cep' is the median miss distance.
+    The dict of TrajectoryEngine.dispersion plus 'n_samples' / 'n_outliers' of the filter."""
+    engine = _engine_of(summary, engine)
+    res, why = engine.analyze(summary, status, rows=[], quantiles=[], reasons=True)
+    out = engine.dispersion(summary, why, centre=(0.0, 0.0) if target is None else target, levels=levels,
+                            quantiles=quantiles)
+    out["n_samples"], out["n_outliers"] = int(res.n_valid), int(res.n_outliers)
+    return out

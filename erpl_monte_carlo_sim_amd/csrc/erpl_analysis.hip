@@ -331,3 +331,23 @@ int erpl_launch_analysis(const ErplAnaArgs& a, void* stream) {
   }
   return (int)hipGetLastError();
 }
+
+int erpl_launch_row_stats(const ErplAnaArgs& a, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t want = (a.n + ERPL_ANA_BLOCK - 1) / ERPL_ANA_BLOCK;
+  const int nb = (int)(want < ERPL_ANA_MAX_BLOCKS ? want : ERPL_ANA_MAX_BLOCKS);
+  if (a.n_rows <= 0) return 0;
+  hipError_t e = hipMemsetAsync(&a.work->hist[0][0][0], 0, sizeof(a.work->hist), st);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(erpl_ana_moments<false>, dim3(nb, a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a);
+  // a.n_rows workgroups: the one behind them, which adds up the classify counters, has nothing to add here
+  hipLaunchKernelGGL(erpl_ana_finish_first, dim3(a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a, nb);
+  hipLaunchKernelGGL(erpl_ana_moments<true>, dim3(nb, a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a);
+  hipLaunchKernelGGL(erpl_ana_finish_second, dim3(a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a, nb);
+  if (a.n_q > 0)
+    for (int shift = 56; shift >= 0; shift -= 8) {
+      hipLaunchKernelGGL(erpl_ana_histogram, dim3(nb, a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a, shift);
+      hipLaunchKernelGGL(erpl_ana_scan, dim3(a.n_rows), dim3(64 * ERPL_ANA_TARGETS), 0, st, a, shift);
+    }
+  return (int)hipGetLastError();
+}

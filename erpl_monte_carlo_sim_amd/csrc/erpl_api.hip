@@ -289,6 +289,12 @@ struct erpl_ctx {
   uint8_t* ana_why = nullptr;
   int64_t ana_cap = 0;
   ErplAnaResult* ana_host = nullptr;
+  // erpl_mc_histogram / _histogram2d / _dispersion: fixed block (partials, edges, bins, cells), pinned mirror of what the
+  // host reads and writes, one double per sample for the miss distance when the caller keeps none
+  ErplDistWork* dist_work = nullptr;
+  struct DistHost* dist_host = nullptr;
+  double* dist_miss = nullptr;
+  int64_t dist_cap = 0;
 };
 
 namespace {
@@ -552,6 +558,8 @@ int erpl_mc_destroy(erpl_ctx* c) {
   if (c->ring_counters) (void)hipHostFree(c->ring_counters);
   (void)hipFree(c->ana_work); (void)hipFree(c->ana_why);
   if (c->ana_host) (void)hipHostFree(c->ana_host);
+  (void)hipFree(c->dist_work); (void)hipFree(c->dist_miss);
+  if (c->dist_host) (void)hipHostFree(c->dist_host);
   delete c;
   return ERPL_OK;
 }
@@ -1214,6 +1222,317 @@ int erpl_mc_analyze(erpl_ctx* c, const double* summary, const int32_t* status, i
   if (result->n_incomplete > 0)
     return fail(ERPL_ERR_INCOMPLETE, "%lld sample(s) carry ERPL_ST_INCOMPLETE: they were never integrated",
                 (long long)result->n_incomplete);
+  return ERPL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------- erpl_mc_histogram, erpl_mc_histogram_xy, erpl_mc_dispersion
+struct DistHost {
+  ErplDistRange range;
+  double edges[ERPL_HIST_MAX_ROWS][ERPL_HIST_MAX_BINS + 1];
+  ErplDistHist hist;
+  unsigned long long counted2, outside2;
+  unsigned long long cells[ERPL_HIST2D_MAX_BINS * ERPL_HIST2D_MAX_BINS];
+  ErplDistMoments mom;
+};
+
+namespace {
+
+int dist_reserve(erpl_ctx* c, int64_t n_miss) {
+  if (!c->dist_work) HIP_TRY(hipMalloc((void**)&c->dist_work, sizeof(ErplDistWork)));
+  if (!c->dist_host) HIP_TRY(hipHostMalloc((void**)&c->dist_host, sizeof(DistHost), hipHostMallocDefault));
+  if (n_miss <= c->dist_cap) return ERPL_OK;
+  HIP_TRY(hipDeviceSynchronize());   // an earlier call on another stream may still read the old row
+  (void)hipFree(c->dist_miss);
+  c->dist_miss = nullptr; c->dist_cap = 0;
+  HIP_TRY(hipMalloc((void**)&c->dist_miss, (size_t)n_miss * sizeof(double)));
+  c->dist_cap = n_miss;
+  return ERPL_OK;
+}
+
+// lo / hi of one axis as the caller gave them: 1 = from the data, 0 = explicit, < 0 = refused
+int check_range(double lo, double hi, const char* lo_name, const char* hi_name, int j) {
+  char at[16] = "";
+  if (j >= 0) snprintf(at, sizeof(at), "[%d]", j);
+  if (std::isnan(lo) && std::isnan(hi)) return 1;
+  if (std::isnan(lo) || std::isnan(hi))
+    return fail(ERPL_ERR_INVALID, "spec->%s%s = %g, spec->%s%s = %g: both NaN (range from the data) or both finite", lo_name, at,
+                lo, hi_name, at, hi);
+  if (!std::isfinite(lo) || !std::isfinite(hi) || !std::isfinite(hi - lo))
+    return fail(ERPL_ERR_INVALID, "spec->%s%s = %g, spec->%s%s = %g: not a finite range", lo_name, at, lo, hi_name, at, hi);
+  if (lo > hi) return fail(ERPL_ERR_INVALID, "spec->%s%s = %g > spec->%s%s = %g", lo_name, at, lo, hi_name, at, hi);
+  return 0;
+}
+
+// The range in use: min / max found on the device for an automatic one ((0, 1) if nothing was counted), widened by a
+// half either side if empty.  false: hi - lo is not finite.
+bool settle_range(bool automatic, double found_lo, double found_hi, double* lo, double* hi) {
+  if (automatic) {
+    if (found_lo > found_hi) { found_lo = 0.0; found_hi = 1.0; }
+    *lo = found_lo; *hi = found_hi;
+  }
+  if (!std::isfinite(*hi - *lo)) return false;
+  if (*lo == *hi) { *lo -= 0.5; *hi += 0.5; }
+  return true;
+}
+
+// np.linspace(lo, hi, bins + 1): two roundings per edge (this file is compiled without contraction), the last edge exact
+void fill_edges(double lo, double hi, int bins, double* e) {
+  const double delta = hi - lo, div = (double)bins, step = delta / div;
+  if (step != 0.0) for (int i = 0; i < bins; ++i) e[i] = (double)i * step + lo;
+  else for (int i = 0; i < bins; ++i) e[i] = ((double)i / div) * delta + lo;
+  e[bins] = hi;
+}
+
+int check_row(int row, const char* name, int j) {
+  if (row >= 0 && row < ERPL_SUMMARY_DIM) return ERPL_OK;
+  if (j >= 0) return fail(ERPL_ERR_INVALID, "spec->%s[%d] = %d outside 0..%d", name, j, row, ERPL_SUMMARY_DIM - 1);
+  return fail(ERPL_ERR_INVALID, "spec->%s = %d outside 0..%d", name, row, ERPL_SUMMARY_DIM - 1);
+}
+
+}  // namespace
+
+extern "C" {
+
+int erpl_mc_histogram_defaults(erpl_hist_spec* spec) {
+  if (!spec) return fail(ERPL_ERR_INVALID, "spec is NULL");
+  memset(spec, 0, sizeof(*spec));
+  spec->n_rows = 3;
+  spec->rows[0] = ERPL_SUM_APOGEE_ALT; spec->rows[1] = ERPL_SUM_RANGE; spec->rows[2] = ERPL_SUM_FLIGHT_TIME;
+  for (int j = 0; j < ERPL_HIST_MAX_ROWS; ++j) { spec->bins[j] = 50; spec->lo[j] = spec->hi[j] = NAN; }   // monte_carlo.py:570
+  return ERPL_OK;
+}
+
+int erpl_mc_histogram(erpl_ctx* c, const double* summary, const uint8_t* mask, int64_t n, const erpl_hist_spec* spec,
+                      double* edges, int64_t* counts, erpl_hist_result* result, void* stream) {
+  if (!spec) return fail(ERPL_ERR_INVALID, "spec is NULL");
+  if (spec->n_rows < 1 || spec->n_rows > ERPL_HIST_MAX_ROWS)
+    return fail(ERPL_ERR_INVALID, "spec->n_rows = %d outside 1..%d", spec->n_rows, ERPL_HIST_MAX_ROWS);
+  ErplDistArgs a;
+  memset(&a, 0, sizeof(a));
+  bool any_auto = false;
+  for (int j = 0; j < spec->n_rows; ++j) {
+    int rc = check_row(spec->rows[j], "rows", j);
+    if (rc != ERPL_OK) return rc;
+    for (int k = 0; k < j; ++k)
+      if (spec->rows[k] == spec->rows[j]) return fail(ERPL_ERR_INVALID, "spec->rows[%d] = %d is listed twice", j, spec->rows[j]);
+    if (spec->bins[j] < 1 || spec->bins[j] > ERPL_HIST_MAX_BINS)
+      return fail(ERPL_ERR_INVALID, "spec->bins[%d] = %d outside 1..%d", j, spec->bins[j], ERPL_HIST_MAX_BINS);
+    rc = check_range(spec->lo[j], spec->hi[j], "lo", "hi", j);
+    if (rc < 0) return rc;
+    a.rows[j] = spec->rows[j]; a.partner[j] = -1; a.bins[j] = spec->bins[j]; a.automatic[j] = rc;
+    a.lo[j] = spec->lo[j]; a.hi[j] = spec->hi[j];
+    any_auto = any_auto || rc == 1;
+  }
+  if (n <= 0) return fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
+  if (!summary) return fail(ERPL_ERR_INVALID, "summary is NULL");
+  if (!edges) return fail(ERPL_ERR_INVALID, "edges is NULL");
+  if (!counts) return fail(ERPL_ERR_INVALID, "counts is NULL");
+  if (!result) return fail(ERPL_ERR_INVALID, "result is NULL");
+  if (!c) return fail(ERPL_ERR_INVALID, "ctx is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = dist_reserve(c, 0);
+  if (rc != ERPL_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  DistHost& h = *c->dist_host;
+  a.summary = summary; a.mask = mask; a.work = c->dist_work; a.n = n; a.n_rows = spec->n_rows;
+  if (any_auto) {
+    const int le = erpl_launch_dist_range(a, stream);
+    if (le != 0) return fail(ERPL_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)le));
+    HIP_TRY(hipMemcpyAsync(&h.range, &c->dist_work->range, sizeof(ErplDistRange), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  memset(h.edges, 0, sizeof(h.edges));
+  for (int j = 0; j < spec->n_rows; ++j) {
+    if (!settle_range(a.automatic[j] != 0, h.range.lo[j], h.range.hi[j], &a.lo[j], &a.hi[j]))
+      return fail(ERPL_ERR_INVALID, "spec->rows[%d] = %d: the range of the counted values, %g to %g, is wider than a double holds",
+                  j, spec->rows[j], a.lo[j], a.hi[j]);
+    fill_edges(a.lo[j], a.hi[j], a.bins[j], h.edges[j]);
+  }
+  HIP_TRY(hipMemcpyAsync(&c->dist_work->edges[0][0], &h.edges[0][0], (size_t)spec->n_rows * sizeof(h.edges[0]),
+                         hipMemcpyHostToDevice, st));
+  const int le = erpl_launch_dist_hist(a, stream);
+  if (le != 0) return fail(ERPL_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)le));
+  HIP_TRY(hipMemcpyAsync(&h.hist, &c->dist_work->hist, sizeof(ErplDistHist), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  memset(result, 0, sizeof(*result));
+  memcpy(edges, h.edges, (size_t)spec->n_rows * sizeof(h.edges[0]));
+  for (int j = 0; j < spec->n_rows; ++j) {
+    for (int k = 0; k < ERPL_HIST_MAX_BINS; ++k) counts[(size_t)j * ERPL_HIST_MAX_BINS + k] = (int64_t)h.hist.bins[j][k];
+    result->counted[j] = (int64_t)h.hist.counted[j];
+    result->below[j] = (int64_t)h.hist.below[j];
+    result->above[j] = (int64_t)h.hist.above[j];
+    result->lo[j] = a.lo[j]; result->hi[j] = a.hi[j];
+  }
+  return ERPL_OK;
+}
+
+int erpl_mc_histogram_xy(erpl_ctx* c, const double* summary, const uint8_t* mask, int64_t n, const erpl_hist2d_spec* spec,
+                        double* edges_x, double* edges_y, int64_t* counts, erpl_hist2d_result* result, void* stream) {
+  if (!spec) return fail(ERPL_ERR_INVALID, "spec is NULL");
+  int rc = check_row(spec->row_x, "row_x", -1);
+  if (rc != ERPL_OK) return rc;
+  rc = check_row(spec->row_y, "row_y", -1);
+  if (rc != ERPL_OK) return rc;
+  if (spec->row_x == spec->row_y) return fail(ERPL_ERR_INVALID, "spec->row_y = %d is listed twice (row_x)", spec->row_y);
+  if (spec->bins_x < 1 || spec->bins_x > ERPL_HIST2D_MAX_BINS)
+    return fail(ERPL_ERR_INVALID, "spec->bins_x = %d outside 1..%d", spec->bins_x, ERPL_HIST2D_MAX_BINS);
+  if (spec->bins_y < 1 || spec->bins_y > ERPL_HIST2D_MAX_BINS)
+    return fail(ERPL_ERR_INVALID, "spec->bins_y = %d outside 1..%d", spec->bins_y, ERPL_HIST2D_MAX_BINS);
+  const int auto_x = check_range(spec->lo_x, spec->hi_x, "lo_x", "hi_x", -1);
+  if (auto_x < 0) return auto_x;
+  const int auto_y = check_range(spec->lo_y, spec->hi_y, "lo_y", "hi_y", -1);
+  if (auto_y < 0) return auto_y;
+  if (n <= 0) return fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
+  if (!summary) return fail(ERPL_ERR_INVALID, "summary is NULL");
+  if (!edges_x) return fail(ERPL_ERR_INVALID, "edges_x is NULL");
+  if (!edges_y) return fail(ERPL_ERR_INVALID, "edges_y is NULL");
+  if (!counts) return fail(ERPL_ERR_INVALID, "counts is NULL");
+  if (!result) return fail(ERPL_ERR_INVALID, "result is NULL");
+  if (!c) return fail(ERPL_ERR_INVALID, "ctx is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  rc = dist_reserve(c, 0);
+  if (rc != ERPL_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  DistHost& h = *c->dist_host;
+  ErplDistArgs a;
+  memset(&a, 0, sizeof(a));
+  a.summary = summary; a.mask = mask; a.work = c->dist_work; a.n = n; a.n_rows = 2;
+  a.rows[0] = spec->row_x; a.rows[1] = spec->row_y; a.partner[0] = spec->row_y; a.partner[1] = spec->row_x;
+  a.bins[0] = spec->bins_x; a.bins[1] = spec->bins_y; a.automatic[0] = auto_x; a.automatic[1] = auto_y;
+  a.lo[0] = spec->lo_x; a.hi[0] = spec->hi_x; a.lo[1] = spec->lo_y; a.hi[1] = spec->hi_y;
+  if (auto_x || auto_y) {
+    const int le = erpl_launch_dist_range(a, stream);
+    if (le != 0) return fail(ERPL_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)le));
+    HIP_TRY(hipMemcpyAsync(&h.range, &c->dist_work->range, sizeof(ErplDistRange), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  for (int j = 0; j < 2; ++j) {
+    if (!settle_range(a.automatic[j] != 0, h.range.lo[j], h.range.hi[j], &a.lo[j], &a.hi[j]))
+      return fail(ERPL_ERR_INVALID, "spec->row_%s = %d: the range of the counted values, %g to %g, is wider than a double holds",
+                  j ? "y" : "x", a.rows[j], a.lo[j], a.hi[j]);
+    fill_edges(a.lo[j], a.hi[j], a.bins[j], h.edges[j]);
+  }
+  HIP_TRY(hipMemcpyAsync(&c->dist_work->edges[0][0], &h.edges[0][0], 2 * sizeof(h.edges[0]), hipMemcpyHostToDevice, st));
+  const int le = erpl_launch_dist_hist2d(a, stream);
+  if (le != 0) return fail(ERPL_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)le));
+  const size_t cells = (size_t)spec->bins_x * (size_t)spec->bins_y;
+  HIP_TRY(hipMemcpyAsync(&h.counted2, &c->dist_work->counted2, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h.cells, c->dist_work->cells, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  memcpy(edges_x, h.edges[0], (size_t)(spec->bins_x + 1) * sizeof(double));
+  memcpy(edges_y, h.edges[1], (size_t)(spec->bins_y + 1) * sizeof(double));
+  for (size_t k = 0; k < cells; ++k) counts[k] = (int64_t)h.cells[k];
+  memset(result, 0, sizeof(*result));
+  result->counted = (int64_t)h.counted2;
+  result->outside = (int64_t)h.outside2;
+  result->lo_x = a.lo[0]; result->hi_x = a.hi[0]; result->lo_y = a.lo[1]; result->hi_y = a.hi[1];
+  return ERPL_OK;
+}
+
+int erpl_mc_dispersion_defaults(erpl_dispersion_spec* spec) {
+  if (!spec) return fail(ERPL_ERR_INVALID, "spec is NULL");
+  memset(spec, 0, sizeof(*spec));
+  spec->row_x = ERPL_SUM_IMPACT_X; spec->row_y = ERPL_SUM_IMPACT_Y;
+  spec->centre = ERPL_CENTRE_POINT;   // the launch site
+  spec->n_levels = 3;
+  spec->level[0] = 0.5; spec->level[1] = 0.9; spec->level[2] = 0.99;
+  spec->n_q = 4;
+  spec->q[0] = 0.5; spec->q[1] = 0.9; spec->q[2] = 0.95; spec->q[3] = 0.99;   // quantile[0]: the CEP
+  return ERPL_OK;
+}
+
+int erpl_mc_dispersion(erpl_ctx* c, const double* summary, const uint8_t* mask, int64_t n, const erpl_dispersion_spec* spec,
+                       erpl_dispersion* result, double* miss, void* stream) {
+  if (!spec) return fail(ERPL_ERR_INVALID, "spec is NULL");
+  int rc = check_row(spec->row_x, "row_x", -1);
+  if (rc != ERPL_OK) return rc;
+  rc = check_row(spec->row_y, "row_y", -1);
+  if (rc != ERPL_OK) return rc;
+  if (spec->row_x == spec->row_y) return fail(ERPL_ERR_INVALID, "spec->row_y = %d is listed twice (row_x)", spec->row_y);
+  if (spec->centre != ERPL_CENTRE_MEAN && spec->centre != ERPL_CENTRE_POINT)
+    return fail(ERPL_ERR_INVALID, "spec->centre = %d: ERPL_CENTRE_MEAN or ERPL_CENTRE_POINT", spec->centre);
+  if (spec->centre == ERPL_CENTRE_POINT && !(std::isfinite(spec->cx) && std::isfinite(spec->cy)))
+    return fail(ERPL_ERR_INVALID, "spec->cx = %g, spec->cy = %g: not a finite point", spec->cx, spec->cy);
+  if (spec->n_levels < 0 || spec->n_levels > ERPL_DISP_MAX_LEVELS)
+    return fail(ERPL_ERR_INVALID, "spec->n_levels = %d outside 0..%d", spec->n_levels, ERPL_DISP_MAX_LEVELS);
+  for (int k = 0; k < spec->n_levels; ++k)
+    if (!(spec->level[k] > 0.0 && spec->level[k] < 1.0))
+      return fail(ERPL_ERR_INVALID, "spec->level[%d] = %g outside (0, 1)", k, spec->level[k]);
+  if (spec->n_q < 0 || spec->n_q > ERPL_ANALYSIS_MAX_Q)
+    return fail(ERPL_ERR_INVALID, "spec->n_q = %d outside 0..%d", spec->n_q, ERPL_ANALYSIS_MAX_Q);
+  for (int k = 0; k < spec->n_q; ++k)
+    if (!(spec->q[k] >= 0.0 && spec->q[k] <= 1.0)) return fail(ERPL_ERR_INVALID, "spec->q[%d] = %g outside [0, 1]", k, spec->q[k]);
+  if (n <= 0) return fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
+  if (!summary) return fail(ERPL_ERR_INVALID, "summary is NULL");
+  if (!result) return fail(ERPL_ERR_INVALID, "result is NULL");
+  if (!c) return fail(ERPL_ERR_INVALID, "ctx is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  rc = dist_reserve(c, miss ? 0 : n);
+  if (rc != ERPL_OK) return rc;
+  rc = analysis_reserve(c, n);   // the selection's block, and a row of zero bytes to stand in for a mask
+  if (rc != ERPL_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  ErplDispArgs d;
+  memset(&d, 0, sizeof(d));
+  d.summary = summary; d.mask = mask; d.work = c->dist_work; d.miss = miss ? miss : c->dist_miss; d.n = n;
+  d.row_x = spec->row_x; d.row_y = spec->row_y; d.centre = spec->centre; d.n_levels = spec->n_levels;
+  d.cx = spec->cx; d.cy = spec->cy;
+  for (int k = 0; k < spec->n_levels; ++k) d.k2[k] = -2.0 * log(1.0 - spec->level[k]);
+  int le = erpl_launch_dispersion(d, stream);
+  if (le != 0) return fail(ERPL_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)le));
+  // the miss distance as a one-row summary through the moment passes and the selection of erpl_mc_analyze
+  ErplAnaArgs a;
+  memset(&a, 0, sizeof(a));
+  a.summary = d.miss; a.work = c->ana_work; a.n = n; a.n_rows = 1; a.rows[0] = 0; a.n_q = spec->n_q;
+  for (int k = 0; k < spec->n_q; ++k) a.q[k] = spec->q[k];
+  if (mask) a.why = const_cast<uint8_t*>(mask);   // read only there
+  else { HIP_TRY(hipMemsetAsync(c->ana_why, 0, (size_t)n, st)); a.why = c->ana_why; }
+  le = erpl_launch_row_stats(a, stream);
+  if (le != 0) return fail(ERPL_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)le));
+  HIP_TRY(hipMemcpyAsync(&c->dist_host->mom, &c->dist_work->mom, sizeof(ErplDistMoments), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(c->ana_host, &c->ana_work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+
+  const ErplDistMoments& m = c->dist_host->mom;
+  const double nan = NAN;
+  memset(result, 0, sizeof(*result));
+  result->count = (int64_t)m.count;
+  const bool any = m.count > 0ull;
+  result->mean_x = any ? m.mean_x : nan; result->mean_y = any ? m.mean_y : nan;
+  result->cov_xx = any ? m.cov_xx : nan; result->cov_xy = any ? m.cov_xy : nan; result->cov_yy = any ? m.cov_yy : nan;
+  const double half = (m.cov_xx + m.cov_yy) / 2, diff = (m.cov_xx - m.cov_yy) / 2;
+  const double root = sqrt(diff * diff + m.cov_xy * m.cov_xy);
+  result->var_major = any ? half + root : nan;
+  result->var_minor = any ? half - root : nan;
+  result->angle = any ? 0.5 * atan2(2 * m.cov_xy, m.cov_xx - m.cov_yy) : nan;
+  result->centre_x = any ? m.centre_x : nan; result->centre_y = any ? m.centre_y : nan;
+  const bool solid = any && m.det > 0.0 && std::isfinite(m.det);
+  for (int k = 0; k < ERPL_DISP_MAX_LEVELS; ++k) {
+    const bool asked = k < spec->n_levels;
+    result->k2[k] = asked && any ? d.k2[k] : nan;
+    // a variance that rounding has taken below zero has no axis: 0, as the degenerate ellipse it is
+    result->semi_major[k] = asked && any ? sqrt(d.k2[k] * fmax(result->var_major, 0.0)) : nan;
+    result->semi_minor[k] = asked && any ? sqrt(d.k2[k] * fmax(result->var_minor, 0.0)) : nan;
+    result->inside[k] = !asked || !any ? 0 : (solid ? (int64_t)m.inside[k] : -1);
+  }
+  const ErplAnaRow& r = c->ana_host->row[0];
+  erpl_row_stats& o = result->miss;
+  o.count = (int64_t)r.count;
+  const bool some = r.count > 0ull;
+  o.mean = some ? r.mean : nan;
+  o.std = some ? sqrt(r.m2 / (double)r.count) : nan;
+  o.min = some ? r.vmin : nan;
+  o.max = some ? r.vmax : nan;
+  for (int k = 0; k < ERPL_ANALYSIS_MAX_Q; ++k) {
+    if (!some || k >= spec->n_q) { o.quantile[k] = o.order_lo[k] = o.order_hi[k] = nan; continue; }
+    const double pos = spec->q[k] * (double)(r.count - 1ull);
+    const double lo = floor(pos);
+    o.order_lo[k] = double_of_key(r.key[2 * k]);
+    o.order_hi[k] = double_of_key(r.key[2 * k + 1]);
+    o.quantile[k] = o.order_lo[k] + (o.order_hi[k] - o.order_lo[k]) * (pos - lo);
+  }
   return ERPL_OK;
 }
 

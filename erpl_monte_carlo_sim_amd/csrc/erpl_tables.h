@@ -206,4 +206,70 @@ extern "C++" {
 // Enqueues every pass of erpl_mc_analyze on `stream`; afterwards a.work->res holds the device's part of the result.
 // Returns a hipError_t (0 = launched).
 int erpl_launch_analysis(const ErplAnaArgs& a, void* stream);
+// The moment passes and the selection of erpl_launch_analysis WITHOUT classify, for a caller that brings its own mask:
+// a.why is read, never written (a byte of 0 = the sample counts), a.status / a.reasons and the bounds are not looked at.
+// erpl_mc_dispersion describes its derived miss-distance row with it (a.summary = that row, a.rows[0] = 0, a.n_rows = 1).
+// Afterwards a.work->res.row[] is filled; res.counter[] is left alone.
+int erpl_launch_row_stats(const ErplAnaArgs& a, void* stream);
+}
+
+// ---- erpl_mc_histogram / erpl_mc_histogram_xy / erpl_mc_dispersion (erpl_distributions.hip) ----
+// Grids are those of the analysis passes: min(ERPL_ANA_MAX_BLOCKS, ceil(n / ERPL_ANA_BLOCK)) workgroups of ERPL_ANA_BLOCK.
+#define ERPL_DIST_TILE_CELLS 4096   // 2-D grids up to this many cells are counted in an LDS tile (16 KB of 32-bit counts),
+                                    //   larger ones straight into the 64-bit global cells
+struct ErplDistRange {              // finished by erpl_dist_finish_range, read by the host
+  double lo[ERPL_HIST_MAX_ROWS], hi[ERPL_HIST_MAX_ROWS];
+};
+struct ErplDistHist {               // the 1-D result block the host copies back
+  unsigned long long counted[ERPL_HIST_MAX_ROWS], below[ERPL_HIST_MAX_ROWS], above[ERPL_HIST_MAX_ROWS];
+  unsigned long long bins[ERPL_HIST_MAX_ROWS][ERPL_HIST_MAX_BINS];
+};
+struct ErplDistMoments {            // dispersion: what the device hands back
+  unsigned long long count;
+  double mean_x, mean_y, sxx, sxy, syy;   // sums of dx dx, dx dy, dy dy about the mean
+  double cov_xx, cov_xy, cov_yy, det;
+  double centre_x, centre_y;
+  unsigned long long inside[ERPL_DISP_MAX_LEVELS];
+};
+struct ErplDistWork {
+  double pmin[ERPL_HIST_MAX_ROWS][ERPL_ANA_MAX_BLOCKS];      // range pass: partials per row and workgroup
+  double pmax[ERPL_HIST_MAX_ROWS][ERPL_ANA_MAX_BLOCKS];
+  ErplDistRange range;
+  double edges[ERPL_HIST_MAX_ROWS][ERPL_HIST_MAX_BINS + 1];  // written by the host (2-D: lines 0 and 1 are x and y)
+  ErplDistHist hist;
+  unsigned long long counted2, outside2;
+  unsigned long long cells[ERPL_HIST2D_MAX_BINS * ERPL_HIST2D_MAX_BINS];   // 2-D counts, x-major
+  double dsum[3][ERPL_ANA_MAX_BLOCKS];                       // dispersion: partial sums per workgroup
+  unsigned long long dcnt[ERPL_ANA_MAX_BLOCKS];
+  unsigned long long ipart[ERPL_ANA_MAX_BLOCKS][ERPL_DISP_MAX_LEVELS];     // ellipse contents per workgroup
+  ErplDistMoments mom;
+};
+struct ErplDistArgs {
+  const double* summary;   // [ERPL_SUMMARY_DIM][n]
+  const uint8_t* mask;     // [n] or NULL
+  ErplDistWork* work;
+  int64_t n;
+  int32_t n_rows;
+  int32_t rows[ERPL_HIST_MAX_ROWS];
+  int32_t partner[ERPL_HIST_MAX_ROWS];   // range pass: a second row that has to be finite too (2-D), or -1
+  int32_t bins[ERPL_HIST_MAX_ROWS];
+  int32_t automatic[ERPL_HIST_MAX_ROWS]; // range pass: rows whose range comes from the data
+  double lo[ERPL_HIST_MAX_ROWS], hi[ERPL_HIST_MAX_ROWS];   // bin passes: the range in use
+};
+struct ErplDispArgs {
+  const double* summary;
+  const uint8_t* mask;     // [n] or NULL
+  ErplDistWork* work;
+  double* miss;            // [n]: receives r, NaN where the sample is not counted
+  int64_t n;
+  int32_t row_x, row_y, centre, n_levels;
+  double cx, cy;
+  double k2[ERPL_DISP_MAX_LEVELS];
+};
+extern "C++" {
+// Each enqueues its passes on `stream` and returns a hipError_t (0 = launched).
+int erpl_launch_dist_range(const ErplDistArgs& a, void* stream);     // -> work->range
+int erpl_launch_dist_hist(const ErplDistArgs& a, void* stream);      // work->edges -> work->hist
+int erpl_launch_dist_hist2d(const ErplDistArgs& a, void* stream);    // work->edges[0..1] -> work->cells, counted2, outside2
+int erpl_launch_dispersion(const ErplDispArgs& a, void* stream);     // -> work->mom, a.miss
 }

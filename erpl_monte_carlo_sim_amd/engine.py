@@ -297,6 +297,128 @@ class TrajectoryEngine:
         _abi.check(self.lib, rc, "erpl_mc_analyze")
         return res, why
 
+    def _summary_and_mask(self, summary, mask):
+        """The host-side refusals of the distribution calls: there is no CPU path behind them."""
+        if not (summary.is_cuda and summary.device == self.device and summary.dtype == torch.float64
+                and summary.dim() == 2 and summary.shape[0] == _abi.SUMMARY_DIM and summary.is_contiguous()):
+            raise ValueError(f"summary must be a contiguous float64 [{_abi.SUMMARY_DIM}, n] tensor on {self.device}")
+        n = int(summary.shape[1])
+        if mask is not None and not (mask.device == self.device and mask.dtype == torch.uint8
+                                     and tuple(mask.shape) == (n,) and mask.is_contiguous()):
+            raise ValueError(f"mask must be a contiguous uint8 [n] tensor on {self.device}")
+        return n, C.c_void_p(mask.data_ptr()) if mask is not None else None
+
+    @staticmethod
+    def _range_of(r):
+        if r is None:
+            return float("nan"), float("nan")
+        lo, hi = r
+        return float(lo), float(hi)
+
+    def histogram(self, summary, mask=None, rows=None, bins=50, ranges=None):
+        """np.histogram of up to 16 rows of a [16, n] summary on the device (erpl_mc_histogram), enqueued on the current
+        torch stream; blocks the host until the counts are there.  mask: uint8 [n] on the device, a sample counts iff
+        its byte is 0 (the reason bits of `analyze`); rows: summary rows (default apogee, range, flight time); bins: one
+        int or one per row (1..1024); ranges: None (min / max of the counted values) or one (lo, hi) / None per row.
+        Returns (edges, counts, info): two lists of NumPy arrays, bins[j] + 1 float64 edges and bins[j] int64 counts per
+        row - equal to np.histogram(finite masked values, bins, range) - and a dict of per-row lists counted / below /
+        above / lo / hi."""
+        n, mask_p = self._summary_and_mask(summary, mask)
+        spec = _abi.ErplHistSpec()
+        _abi.check(self.lib, self.lib.erpl_mc_histogram_defaults(C.byref(spec)), "erpl_mc_histogram_defaults")
+        if rows is not None:
+            rows = [int(r) for r in rows]
+            if not 1 <= len(rows) <= _abi.HIST_MAX_ROWS:
+                raise ValueError(f"1 to {_abi.HIST_MAX_ROWS} rows")
+            spec.n_rows = len(rows)
+            spec.rows[:len(rows)] = rows
+        m = spec.n_rows
+        bins = [int(bins)] * m if np.isscalar(bins) else [int(b) for b in bins]
+        ranges = [None] * m if ranges is None else list(ranges)
+        if len(bins) != m or len(ranges) != m:
+            raise ValueError("bins and ranges: one entry per row")
+        for j in range(m):
+            spec.bins[j] = bins[j]
+            spec.lo[j], spec.hi[j] = self._range_of(ranges[j])
+        edges = np.zeros((m, _abi.HIST_MAX_BINS + 1), dtype=np.float64)
+        counts = np.zeros((m, _abi.HIST_MAX_BINS), dtype=np.int64)
+        res = _abi.ErplHistResult()
+        st = torch.cuda.current_stream(self.device)
+        rc = self.lib.erpl_mc_histogram(self._ctx, C.c_void_p(summary.data_ptr()), mask_p, n, C.byref(spec),
+                                        C.c_void_p(edges.ctypes.data), C.c_void_p(counts.ctypes.data), C.byref(res),
+                                        C.c_void_p(st.cuda_stream))
+        _abi.check(self.lib, rc, "erpl_mc_histogram")
+        info = {k: list(getattr(res, k)[:m]) for k in ("counted", "below", "above", "lo", "hi")}
+        return ([edges[j, :bins[j] + 1].copy() for j in range(m)], [counts[j, :bins[j]].copy() for j in range(m)], info)
+
+    def histogram2d(self, summary, mask=None, row_x=_abi.SUM_APOGEE_ALT, row_y=_abi.SUM_RANGE, bins=50, ranges=None):
+        """np.histogram2d of two rows of a [16, n] summary on the device (erpl_mc_histogram_xy).  bins: one int or
+        (bins_x, bins_y), up to 256 each; ranges: None or ((lo_x, hi_x) | None, (lo_y, hi_y) | None).  A sample is counted
+        iff its mask byte is 0 and both values are finite.  Returns (counts int64 [bins_x, bins_y], edges_x, edges_y,
+        info dict: counted, outside, lo_x, hi_x, lo_y, hi_y)."""
+        n, mask_p = self._summary_and_mask(summary, mask)
+        bx, by = (int(bins), int(bins)) if np.isscalar(bins) else (int(bins[0]), int(bins[1]))
+        rx, ry = (None, None) if ranges is None else ranges
+        spec = _abi.ErplHist2dSpec(int(row_x), int(row_y), bx, by, *self._range_of(rx), *self._range_of(ry))
+        cap = _abi.HIST2D_MAX_BINS
+        ex, ey = np.zeros(cap + 1, dtype=np.float64), np.zeros(cap + 1, dtype=np.float64)
+        counts = np.zeros(max(1, min(bx, cap)) * max(1, min(by, cap)), dtype=np.int64)   # out-of-range bins are refused below
+        res = _abi.ErplHist2dResult()
+        st = torch.cuda.current_stream(self.device)
+        rc = self.lib.erpl_mc_histogram_xy(self._ctx, C.c_void_p(summary.data_ptr()), mask_p, n, C.byref(spec),
+                                          C.c_void_p(ex.ctypes.data), C.c_void_p(ey.ctypes.data),
+                                          C.c_void_p(counts.ctypes.data), C.byref(res), C.c_void_p(st.cuda_stream))
+        _abi.check(self.lib, rc, "erpl_mc_histogram_xy")
+        info = {k: getattr(res, k) for k in ("counted", "outside", "lo_x", "hi_x", "lo_y", "hi_y")}
+        return counts.reshape(bx, by), ex[:bx + 1].copy(), ey[:by + 1].copy(), info
+
+    def dispersion(self, summary, mask=None, row_x=_abi.SUM_IMPACT_X, row_y=_abi.SUM_IMPACT_Y, centre=(0.0, 0.0),
+                   levels=(0.5, 0.9, 0.99), quantiles=(0.5, 0.9, 0.95, 0.99), miss=False):
+        """Where the vehicle lands (erpl_mc_dispersion): count, mean, population covariance and its principal axes of the
+        (row_x, row_y) cloud over the samples with mask byte 0 and both values finite, the confidence ellipses of `levels`
+        with the number of samples each one actually contains (-1 for a degenerate cloud), and the miss distance about
+        `centre` - a point (x, y), default the launch site, or None for the mean - as count / mean / std / min / max /
+        exact quantiles (with the default quantiles the first one is the CEP).  Returns a plain dict; miss=True adds
+        'miss_distance', the float64 [n] device tensor of r (NaN where a sample is not counted)."""
+        n, mask_p = self._summary_and_mask(summary, mask)
+        levels, quantiles = [float(p) for p in levels], [float(q) for q in quantiles]
+        if len(levels) > _abi.DISP_MAX_LEVELS:
+            raise ValueError(f"at most {_abi.DISP_MAX_LEVELS} levels")
+        if len(quantiles) > _abi.ANALYSIS_MAX_Q:
+            raise ValueError(f"at most {_abi.ANALYSIS_MAX_Q} quantiles")
+        spec = _abi.ErplDispersionSpec()
+        _abi.check(self.lib, self.lib.erpl_mc_dispersion_defaults(C.byref(spec)), "erpl_mc_dispersion_defaults")
+        spec.row_x, spec.row_y = int(row_x), int(row_y)
+        if centre is None:
+            spec.centre = _abi.CENTRE_MEAN
+        else:
+            spec.centre, spec.cx, spec.cy = _abi.CENTRE_POINT, float(centre[0]), float(centre[1])
+        spec.n_levels = len(levels)
+        spec.level[:len(levels)] = levels
+        spec.n_q = len(quantiles)
+        spec.q[:len(quantiles)] = quantiles
+        r = torch.empty((n,), dtype=torch.float64, device=self.device) if miss else None
+        res = _abi.ErplDispersion()
+        st = torch.cuda.current_stream(self.device)
+        rc = self.lib.erpl_mc_dispersion(self._ctx, C.c_void_p(summary.data_ptr()), mask_p, n, C.byref(spec), C.byref(res),
+                                         C.c_void_p(r.data_ptr()) if miss else None, C.c_void_p(st.cuda_stream))
+        _abi.check(self.lib, rc, "erpl_mc_dispersion")
+        nl, nq, m = len(levels), len(quantiles), res.miss
+        out = {"count": int(res.count), "rows": (int(row_x), int(row_y)),
+               "mean": [res.mean_x, res.mean_y],
+               "covariance": [[res.cov_xx, res.cov_xy], [res.cov_xy, res.cov_yy]],
+               "var_major": res.var_major, "var_minor": res.var_minor, "angle": res.angle,
+               "centre": [res.centre_x, res.centre_y],
+               "ellipses": [{"level": levels[k], "k2": res.k2[k], "semi_major": res.semi_major[k],
+                             "semi_minor": res.semi_minor[k], "inside": int(res.inside[k])} for k in range(nl)],
+               "miss": {"count": int(m.count), "mean": m.mean, "std": m.std, "min": m.min, "max": m.max,
+                        "q": quantiles, "quantiles": list(m.quantile[:nq]), "order_lo": list(m.order_lo[:nq]),
+                        "order_hi": list(m.order_hi[:nq])}}
+        out["cep"] = out["miss"]["quantiles"][quantiles.index(0.5)] if 0.5 in quantiles else None
+        if miss:
+            out["miss_distance"] = r
+        return out
+
     def set_profiling(self, enable=True):
         """Record HIP events around the two kernels on the launch stream (erpl_mc_set_profiling)."""
         _abi.check(self.lib, self.lib.erpl_mc_set_profiling(self._ctx, int(bool(enable))), "erpl_mc_set_profiling")

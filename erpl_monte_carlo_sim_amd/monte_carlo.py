@@ -14,7 +14,7 @@ import time
 import numpy as np
 import torch
 
-from . import _abi, analysis, dist, flatten, reports
+from . import _abi, analysis, dist, flatten, plots, reports
 from . import results as results_mod
 from .engine import DeviceBatch, TrajectoryEngine
 from .sampling import DEFAULT_UNCERTAINTY
@@ -338,6 +338,24 @@ class MonteCarloAnalyzer:
     def _save_report(self, analysis, output_dir):
         """monte_carlo.py:482-560 (same files, keys and text format)."""
         return reports.save_report(self, analysis, output_dir)
+
+    def plot_results(self, analysis, save_plots=True):
+        """monte_carlo.py:562-633: the three histograms (counted on the device) and range vs apogee, saved as
+        monte_carlo_distributions.png next to the report; prints the statistics; returns the output directory."""
+        return plots.plot_results(self, analysis, save_plots)
+
+    def plot_trajectory_cloud(self, analysis, save_plots=True, max_trajectories=50):
+        """monte_carlo.py:635-677: monte_carlo_trajectories.png."""
+        return plots.plot_trajectory_cloud(self, analysis, save_plots, max_trajectories)
+
+    def plot_trajectory_cloud_3d(self, analysis, save_plots=True, max_trajectories=50):
+        """monte_carlo.py:679-707: monte_carlo_trajectories_3d.png."""
+        return plots.plot_trajectory_cloud_3d(self, analysis, save_plots, max_trajectories)
+
+    def plot_landing_dispersion(self, analysis, save_plots=True, target=None):
+        """No reference counterpart: impact footprint, confidence ellipses and CEP about `target` (default the launch
+        site) as monte_carlo_landing.png, the numbers as landing_dispersion.json."""
+        return plots.plot_landing_dispersion(self, analysis, save_plots, target)
 
     def _filter_physics_outliers(self, results):
         """monte_carlo.py:337-398."""

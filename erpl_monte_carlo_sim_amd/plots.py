@@ -1,0 +1,277 @@
+"""Pictures of a Monte Carlo run: `plot_results`, `plot_trajectory_cloud` and `plot_trajectory_cloud_3d` of the reference
+(monte_carlo.py:562-707: same panels, titles, axis labels and file names) plus the landing dispersion, in two layers.
+
+Drawing functions take host data only - bin edges and counts, scatter points or a 2-D count grid, the dispersion dict,
+trajectories - and build `matplotlib.figure.Figure` objects directly: no pyplot state, no `plt.show`, no change of the
+global backend.  matplotlib is imported inside them, so the package imports without it.
+
+The `plot_*` functions behind the MonteCarloAnalyzer methods get that data from the device: the histograms are counted by
+erpl_mc_histogram over the samples the outlier filter keeps (the bars drawn over the device edges are what
+`ax.hist(values, bins=50)` draws), the fourth panel scatters the points as the reference does up to SCATTER_MAX valid
+samples and shows the erpl_mc_histogram_xy density above that, the landing picture comes from erpl_mc_histogram_xy and
+erpl_mc_dispersion.  No per-sample dicts are built for any of it.
+"""
+import json
+import math
+import os
+
+import numpy as np
+
+from . import _abi
+
+DPI = 300                 # monte_carlo.py:610
+SCATTER_MAX = 20000       # valid samples up to which the range-vs-apogee panel is a scatter plot, as the reference's
+DENSITY_BINS = 200        # bins per axis of the density that replaces it
+LANDING_BINS = 100        # bins per axis of the impact footprint
+
+HIST_PANELS = (("Apogee Altitude (m)", "Apogee Altitude Distribution"),
+               ("Range (m)", "Range Distribution"),
+               ("Flight Time (s)", "Flight Time Distribution"))
+
+
+def _figure(figsize):
+    from matplotlib.backends.backend_agg import FigureCanvasAgg
+    from matplotlib.figure import Figure
+    fig = Figure(figsize=figsize)
+    FigureCanvasAgg(fig)
+    return fig
+
+
+def _density(ax, counts, edges_x, edges_y, cmap="viridis"):
+    """A [bins_x, bins_y] count grid (x-major, as np.histogram2d) as an image; empty cells stay blank."""
+    grid = np.ma.masked_equal(np.asarray(counts).T, 0)
+    return ax.pcolormesh(np.asarray(edges_x), np.asarray(edges_y), grid, cmap=cmap, shading="flat")
+
+
+# ---------------------------------------------------------------------------------------------- drawing layer
+def distributions_figure(histograms, points=None, density=None):
+    """The four panels of `plot_results` (monte_carlo.py:565-604).  histograms: three (edges, counts) pairs for apogee,
+    range and flight time; fourth panel: points = (apogee, range) arrays to scatter, or density = (counts [bx, by],
+    edges_x, edges_y) of the same pair."""
+    fig = _figure((12, 10))
+    axes = fig.subplots(2, 2)
+    for ax, (edges, counts), (xlabel, title) in zip((axes[0, 0], axes[0, 1], axes[1, 0]), histograms, HIST_PANELS):
+        edges, counts = np.asarray(edges, dtype=np.float64), np.asarray(counts)
+        ax.bar(edges[:-1], counts, width=np.diff(edges), align="edge", alpha=0.7, edgecolor="black")
+        ax.set_xlabel(xlabel)
+        ax.set_ylabel("Frequency")
+        ax.set_title(title)
+        ax.grid(True, alpha=0.3)
+    ax = axes[1, 1]
+    if density is not None:
+        fig.colorbar(_density(ax, *density), ax=ax, label="Samples per cell")
+    elif points is not None:
+        ax.scatter(np.asarray(points[0]), np.asarray(points[1]), alpha=0.6, s=10)
+    ax.set_xlabel("Apogee Altitude (m)")
+    ax.set_ylabel("Range (m)")
+    ax.set_title("Range vs Apogee Altitude")
+    ax.grid(True, alpha=0.3)
+    fig.tight_layout()
+    return fig
+
+
+def trajectory_cloud_figure(trajectories):
+    """monte_carlo.py:635-668.  trajectories: result dicts; those with a 'trajectory' are drawn."""
+    fig = _figure((15, 6))
+    ax1, ax2 = fig.subplots(1, 2)
+    for result in trajectories:
+        if "trajectory" in result:
+            ax1.plot(result["trajectory"]["time"], result["trajectory"]["altitude"], alpha=0.3, linewidth=0.5, color="blue")
+    ax1.set_xlabel("Time (s)")
+    ax1.set_ylabel("Altitude (m)")
+    ax1.set_title(f"Trajectory Cloud - Altitude vs Time\n({len(trajectories)} trajectories)")
+    ax1.grid(True, alpha=0.3)
+    for result in trajectories:
+        if "trajectory" in result and "position" in result["trajectory"]:
+            pos = np.asarray(result["trajectory"]["position"])
+            ax2.plot(pos[:, 0], pos[:, 1], alpha=0.3, linewidth=0.5, color="red")
+    ax2.set_xlabel("East Position (m)")
+    ax2.set_ylabel("North Position (m)")
+    ax2.set_title(f"Ground Track Cloud\n({len(trajectories)} trajectories)")
+    ax2.grid(True, alpha=0.3)
+    ax2.axis("equal")
+    fig.tight_layout()
+    return fig
+
+
+def trajectory_cloud_3d_figure(trajectories):
+    """monte_carlo.py:679-699."""
+    from mpl_toolkits.mplot3d import Axes3D  # noqa: F401  (registers the projection on older matplotlib)
+    fig = _figure((10, 8))
+    ax = fig.add_subplot(111, projection="3d")
+    for result in trajectories:
+        if "trajectory" in result and "position" in result["trajectory"]:
+            pos = np.asarray(result["trajectory"]["position"])
+            ax.plot(pos[:, 0], pos[:, 1], pos[:, 2], alpha=0.3, linewidth=0.5)
+    ax.set_xlabel("East Position (m)")
+    ax.set_ylabel("North Position (m)")
+    ax.set_zlabel("Altitude (m)")
+    ax.set_title(f"3D Trajectory Cloud ({len(trajectories)} trajectories)")
+    ax.grid(True, alpha=0.3)
+    return fig
+
+
+def landing_figure(dispersion, density=None, points=None):
+    """Impact footprint: density = (counts [bx, by], edges_x, edges_y) of the impact point or points = (x, y) to scatter,
+    the confidence ellipses of the dispersion dict (TrajectoryEngine.dispersion: centred on 'mean', full axes
+    2 * semi_major by 2 * semi_minor, turned by 'angle') and the CEP circle about 'centre'."""
+    from matplotlib.patches import Circle, Ellipse
+    fig = _figure((9, 8))
+    ax = fig.subplots()
+    if density is not None:
+        fig.colorbar(_density(ax, *density, cmap="Greys"), ax=ax, label="Samples per cell")
+    elif points is not None:
+        ax.scatter(np.asarray(points[0]), np.asarray(points[1]), alpha=0.4, s=6, color="grey")
+    mean, centre = dispersion["mean"], dispersion["centre"]
+    colours = ("tab:green", "tab:orange", "tab:red", "tab:purple", "tab:brown", "tab:pink", "tab:olive", "tab:cyan")
+    for k, e in enumerate(dispersion["ellipses"]):
+        if not (np.isfinite(e["semi_major"]) and np.isfinite(e["semi_minor"])):
+            continue
+        share = f", holds {e['inside']} of {dispersion['count']}" if e["inside"] >= 0 else ""
+        ax.add_patch(Ellipse(xy=(mean[0], mean[1]), width=2 * e["semi_major"], height=2 * e["semi_minor"],
+                             angle=math.degrees(dispersion["angle"]), fill=False, linewidth=1.5,
+                             edgecolor=colours[k % len(colours)], label=f"{100 * e['level']:g} % ellipse{share}"))
+    cep = dispersion.get("cep")
+    if cep is not None and np.isfinite(cep):
+        ax.add_patch(Circle((centre[0], centre[1]), cep, fill=False, linestyle="--", linewidth=1.5, edgecolor="tab:blue",
+                            label=f"CEP {cep:.1f} m"))
+        ax.plot([centre[0]], [centre[1]], marker="+", color="tab:blue", markersize=10)
+    if np.isfinite(mean[0]) and np.isfinite(mean[1]):
+        ax.plot([mean[0]], [mean[1]], marker="x", color="black", markersize=8)
+    ax.set_xlabel("East Position (m)")
+    ax.set_ylabel("North Position (m)")
+    ax.set_title(f"Landing Dispersion ({dispersion['count']} impacts)")
+    ax.grid(True, alpha=0.3)
+    ax.set_aspect("equal", adjustable="datalim")
+    ax.autoscale_view()
+    if ax.get_legend_handles_labels()[0]:
+        ax.legend(loc="best", fontsize=8)
+    fig.tight_layout()
+    return fig
+
+
+def save_figure(fig, output_dir, name):
+    path = os.path.join(output_dir, name)
+    fig.savefig(path, dpi=DPI, bbox_inches="tight")
+    return path
+
+
+# ---------------------------------------------------------------------------------------------- device layer
+def device_inputs(analysis, device=None):
+    """(engine, summary [16, n] float64, status [n] int32 or None) - device tensors of an analysis dict: the gathered tensors of
+    `run_monte_carlo_device`, or ONE upload of the columns behind the LazyResults of `run_monte_carlo` (valid samples and
+    outliers alike: the filter on the device finds the same split).  A plain list of result dicts (`_analyze_results`)
+    is turned into columns first; rows it does not carry are NaN."""
+    import torch
+    from .simulator import shared_engine
+    if "summary" in analysis and hasattr(analysis["summary"], "is_cuda"):
+        summ, status = analysis["summary"], analysis.get("status")
+        eng = shared_engine(summ.device if summ.is_cuda else device)
+        summ = summ.to(device=eng.device, dtype=torch.float64).contiguous()
+        if status is not None:
+            status = status.to(device=eng.device, dtype=torch.int32).contiguous()
+        return eng, summ, status
+    eng = shared_engine(device)
+    results = analysis["results"]
+    table = getattr(results, "table", None)
+    if table is not None:
+        summ = torch.from_numpy(np.ascontiguousarray(table.summary, dtype=np.float64)).to(eng.device)
+        status = torch.from_numpy(np.ascontiguousarray(table.status).astype(np.int32)).to(eng.device)
+        return eng, summ, status
+    records = list(results) + list(analysis.get("outliers", []))
+    cols = np.full((_abi.SUMMARY_DIM, len(records)), np.nan)
+    for i, r in enumerate(records):
+        cols[_abi.SUM_APOGEE_ALT, i] = r.get("apogee_altitude", np.nan)
+        cols[_abi.SUM_RANGE, i] = r.get("range", np.nan)
+        cols[_abi.SUM_FLIGHT_TIME, i] = r.get("flight_time", np.nan)
+        pos = r.get("impact_position")
+        if pos is not None:
+            cols[_abi.SUM_IMPACT_X:_abi.SUM_IMPACT_Z + 1, i] = pos
+    return eng, torch.from_numpy(cols).to(eng.device), None
+
+
+_REPORT_KEYS = ("n_samples", "n_failed", "n_outliers", "apogee_altitude", "range", "flight_time")
+
+
+def _print_statistics(analysis):
+    """monte_carlo.py:619-631."""
+    print("\nMonte Carlo Analysis Results:")
+    print(f"Number of valid simulations: {analysis['n_samples']}")
+    print(f"Number of failed simulations: {analysis['n_failed']}")
+    print(f"Number of outlier simulations: {analysis['n_outliers']}")
+    for title, key in (("Apogee Altitude Statistics:", "apogee_altitude"), ("Range Statistics:", "range")):
+        st = analysis[key]
+        print(f"\n{title}")
+        print(f"  Mean: {st['mean']:.1f} m")
+        print(f"  Standard Deviation: {st['std']:.1f} m")
+        print(f"  95% Confidence Interval: [{st['percentiles'][0]:.1f}, {st['percentiles'][4]:.1f}] m")
+
+
+def plot_results(analyzer, analysis, save_plots=True):
+    """MonteCarloAnalyzer.plot_results (monte_carlo.py:562-633)."""
+    from . import analysis as analysis_mod
+    eng, summ, status = device_inputs(analysis, analyzer.device)
+    rows = [_abi.SUM_APOGEE_ALT, _abi.SUM_RANGE, _abi.SUM_FLIGHT_TIME]
+    dist = analysis_mod.native_distributions(summ, status, engine=eng, bins=50, rows=rows)
+    points = density = None
+    if dist["n_samples"] <= SCATTER_MAX:
+        pair = summ[[_abi.SUM_APOGEE_ALT, _abi.SUM_RANGE]][:, dist["valid_mask"]].cpu().numpy()
+        points = pair[:, np.isfinite(pair[0]) & np.isfinite(pair[1])]
+    else:
+        density = eng.histogram2d(summ, dist["outlier_reason_bits"], _abi.SUM_APOGEE_ALT, _abi.SUM_RANGE,
+                                  bins=DENSITY_BINS)[:3]
+    fig = distributions_figure([(dist[r]["edges"], dist[r]["counts"]) for r in rows], points=points, density=density)
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Plots saved to: {save_figure(fig, output_dir, 'monte_carlo_distributions.png')}")
+        if all(k in analysis for k in _REPORT_KEYS):
+            analyzer._save_report(analysis, output_dir)
+            print(f"Report saved to: {output_dir}")
+    if all(k in analysis for k in _REPORT_KEYS):
+        _print_statistics(analysis)
+    return output_dir
+
+
+def _trajectories_of(analysis, max_trajectories):
+    return list(analysis.get("results", [])[:max_trajectories])
+
+
+def plot_trajectory_cloud(analyzer, analysis, save_plots=True, max_trajectories=50):
+    """MonteCarloAnalyzer.plot_trajectory_cloud (monte_carlo.py:635-677); returns the output directory."""
+    fig = trajectory_cloud_figure(_trajectories_of(analysis, max_trajectories))
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Trajectory plots saved to: {save_figure(fig, output_dir, 'monte_carlo_trajectories.png')}")
+    return output_dir
+
+
+def plot_trajectory_cloud_3d(analyzer, analysis, save_plots=True, max_trajectories=50):
+    """MonteCarloAnalyzer.plot_trajectory_cloud_3d (monte_carlo.py:679-707); returns the output directory."""
+    fig = trajectory_cloud_3d_figure(_trajectories_of(analysis, max_trajectories))
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"3D trajectory plot saved to: {save_figure(fig, output_dir, 'monte_carlo_trajectories_3d.png')}")
+    return output_dir
+
+
+def plot_landing_dispersion(analyzer, analysis, save_plots=True, target=None):
+    """Impact footprint, confidence ellipses and CEP of the filtered population (no reference counterpart): writes
+    monte_carlo_landing.png and landing_dispersion.json (the dict of analysis.landing_dispersion); returns the output
+    directory."""
+    from .reports import to_serializable
+    eng, summ, status = device_inputs(analysis, analyzer.device)
+    res, why = eng.analyze(summ, status, rows=[], quantiles=[], reasons=True)
+    disp = eng.dispersion(summ, why, centre=(0.0, 0.0) if target is None else target)
+    disp["n_samples"], disp["n_outliers"] = int(res.n_valid), int(res.n_outliers)
+    density = eng.histogram2d(summ, why, _abi.SUM_IMPACT_X, _abi.SUM_IMPACT_Y, bins=LANDING_BINS)[:3]
+    fig = landing_figure(disp, density=density)
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Landing dispersion plot saved to: {save_figure(fig, output_dir, 'monte_carlo_landing.png')}")
+        with open(os.path.join(output_dir, "landing_dispersion.json"), "w") as fh:
+            json.dump(to_serializable(disp), fh, indent=2)
+    return output_dir

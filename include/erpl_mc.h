@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define ERPL_MC_ABI_VERSION 3
+#define ERPL_MC_ABI_VERSION 4
 
 #define ERPL_STATE_DIM 14   /* x y z vx vy vz q0(w) q1 q2 q3 wx wy wz propellant_fraction (simulator.py:130) */
 #define ERPL_IC_DIM 13      /* the same without propellant_fraction (always 1.0 at ignition, simulator.py:161) */
@@ -404,6 +404,109 @@ int erpl_mc_analysis_defaults(erpl_analysis_spec* spec);
  * n_incomplete > 0: such samples were never integrated.  n_valid == 0 is no error. */
 int erpl_mc_analyze(erpl_ctx* ctx, const double* summary, const int32_t* status, int64_t n,
                     const erpl_analysis_spec* spec, erpl_analysis* result, uint8_t* reasons, void* hip_stream);
+
+/* Distributions of a finished run ON THE DEVICE: what MonteCarloAnalyzer.plot_results draws from Python lists
+ * (monte_carlo.py:562-633: three `axes.hist(finite_values, bins=50)` and the range-vs-apogee cloud) and where the vehicle
+ * comes down.  Conventions of erpl_mc_analyze: `summary` is [ERPL_SUMMARY_DIM][n] caller-owned device memory; `mask` is
+ * [n] caller-owned device bytes - the `reasons` output of erpl_mc_analyze - a sample counts iff its byte is 0, NULL =
+ * every sample counts; specs and results are host memory; the work is enqueued on `hip_stream` behind what is there and
+ * the call returns when the result is filled; the workspace belongs to the context, grows only with n and is freed by
+ * erpl_mc_destroy.  ERPL_ERR_INVALID, before any device work and with a message that names the argument, for a bad
+ * argument; the context is checked last.  Integer atomics only, sums reduced in an order that depends on n alone: two
+ * calls on the same inputs return the same bytes.
+ *
+ * Bin edges and counts are those of np.histogram / np.histogram2d (NumPy 2.2) for `bins` equal-width bins over [lo, hi]:
+ * lo == hi widens to lo - 0.5, hi + 0.5; step = (hi - lo) / bins; edges[i] = (double)i * step + lo (two roundings, no
+ * FMA), edges[bins] = hi exactly; if step == 0 with hi != lo, edges[i] = ((double)i / bins) * (hi - lo) + lo.  Bin k
+ * holds the counted values with edges[k] <= x < edges[k + 1], the last bin also x == hi: the guess
+ * ((x - lo) / (hi - lo)) * bins is corrected against the edge values.  lo and hi both NaN = `range=None`: min / max of
+ * the counted values (no counted value: edges of (0, 1), zero counts); otherwise both finite, lo <= hi, hi - lo finite. */
+#define ERPL_HIST_MAX_ROWS 16     /* = ERPL_SUMMARY_DIM */
+#define ERPL_HIST_MAX_BINS 1024
+#define ERPL_HIST2D_MAX_BINS 256  /* per axis */
+#define ERPL_DISP_MAX_LEVELS 8
+
+typedef struct erpl_hist_spec {
+  int32_t n_rows;                       /* 1..ERPL_HIST_MAX_ROWS */
+  int32_t rows[ERPL_HIST_MAX_ROWS];     /* summary rows, distinct, 0..15 */
+  int32_t bins[ERPL_HIST_MAX_ROWS];     /* 1..ERPL_HIST_MAX_BINS */
+  double lo[ERPL_HIST_MAX_ROWS], hi[ERPL_HIST_MAX_ROWS];   /* both NaN: min / max of the counted values */
+} erpl_hist_spec;
+
+typedef struct erpl_hist_result {       /* entry j describes spec->rows[j] */
+  int64_t counted[ERPL_HIST_MAX_ROWS];  /* mask byte 0 and finite */
+  int64_t below[ERPL_HIST_MAX_ROWS], above[ERPL_HIST_MAX_ROWS];   /* counted values outside [lo, hi] */
+  double lo[ERPL_HIST_MAX_ROWS], hi[ERPL_HIST_MAX_ROWS];          /* the range in use (after widening lo == hi) */
+} erpl_hist_result;
+
+/* Host only: rows {APOGEE_ALT, RANGE, FLIGHT_TIME}, 50 bins each, range from the data (monte_carlo.py:568-592). */
+int erpl_mc_histogram_defaults(erpl_hist_spec* spec);
+/* np.histogram of up to 16 summary rows in one call.  A value is counted iff its mask byte is 0 and it is finite.
+ * edges: host double [n_rows][ERPL_HIST_MAX_BINS + 1], counts: host int64 [n_rows][ERPL_HIST_MAX_BINS]; row j uses the
+ * first bins[j] + 1 / bins[j] entries of its line, the rest is zero.  An automatic range whose hi - lo overflows is
+ * ERPL_ERR_INVALID naming the row (after the pass that found it). */
+int erpl_mc_histogram(erpl_ctx* ctx, const double* summary, const uint8_t* mask, int64_t n, const erpl_hist_spec* spec,
+                      double* edges, int64_t* counts, erpl_hist_result* result, void* hip_stream);
+
+typedef struct erpl_hist2d_spec {
+  int32_t row_x, row_y;                 /* distinct, 0..15 */
+  int32_t bins_x, bins_y;               /* 1..ERPL_HIST2D_MAX_BINS */
+  double lo_x, hi_x, lo_y, hi_y;        /* per axis as erpl_hist_spec */
+} erpl_hist2d_spec;
+
+typedef struct erpl_hist2d_result {
+  int64_t counted;                      /* mask byte 0 and both values finite */
+  int64_t outside;                      /* counted samples not inside the range on both axes */
+  double lo_x, hi_x, lo_y, hi_y;        /* the ranges in use */
+} erpl_hist2d_result;
+
+/* (Named _xy, not 2d: the names of this ABI are lower-case letters and underscores.)
+ * np.histogram2d of a pair of rows (range vs apogee, monte_carlo.py:594-602, when there are too many points to scatter;
+ * the impact footprint).  An automatic range is min / max over the counted samples.  edges_x: host double [bins_x + 1],
+ * edges_y: host double [bins_y + 1], counts: host int64 [bins_x][bins_y], x-major. */
+int erpl_mc_histogram_xy(erpl_ctx* ctx, const double* summary, const uint8_t* mask, int64_t n,
+                        const erpl_hist2d_spec* spec, double* edges_x, double* edges_y, int64_t* counts,
+                        erpl_hist2d_result* result, void* hip_stream);
+
+/* Landing dispersion (no reference counterpart) over the samples with mask byte 0 and finite row_x, row_y:
+ * count, mean and POPULATION covariance (two passes, the mean read on the device, fixed order); on the host
+ * var_major / var_minor = (cxx + cyy) / 2 +- sqrt(((cxx - cyy) / 2)^2 + cxy^2) and angle = 0.5 * atan2(2 cxy, cxx - cyy),
+ * the major axis from +x towards +y.  For every confidence level p in (0, 1): k2 = -2 log(1 - p) (chi-square quantile,
+ * two degrees of freedom), semi_major / semi_minor = sqrt(k2 * var_major / var_minor), and inside = the number of samples
+ * with (cyy dx dx - 2 cxy dx dy + cxx dy dy) / det <= k2, dx = x - mean_x, dy = y - mean_y, det = cxx cyy - cxy cxy - the
+ * EMPIRICAL content of the ellipse (the clouds are not Gaussian); -1 if det is not positive and finite.
+ * miss: r = sqrt(dx*dx + dy*dy) about the centre (ERPL_CENTRE_MEAN: the mean; ERPL_CENTRE_POINT: (cx, cy)) described as
+ * erpl_mc_analyze describes a row (exact order statistics); with the defaults quantile[0] is the CEP.
+ * count == 0: every double is NaN and every inside is 0; no error. */
+enum { ERPL_CENTRE_MEAN = 0, ERPL_CENTRE_POINT = 1 };
+
+typedef struct erpl_dispersion_spec {
+  int32_t row_x, row_y;                 /* distinct, 0..15 */
+  int32_t centre;                       /* ERPL_CENTRE_MEAN | ERPL_CENTRE_POINT */
+  int32_t n_levels;                     /* 0..ERPL_DISP_MAX_LEVELS */
+  double cx, cy;                        /* ERPL_CENTRE_POINT: finite */
+  double level[ERPL_DISP_MAX_LEVELS];   /* in (0, 1) */
+  int32_t n_q;                          /* 0..ERPL_ANALYSIS_MAX_Q */
+  int32_t reserved;
+  double q[ERPL_ANALYSIS_MAX_Q];        /* quantile fractions of the miss distance, in [0, 1] */
+} erpl_dispersion_spec;
+
+typedef struct erpl_dispersion {
+  int64_t count;
+  double mean_x, mean_y, cov_xx, cov_xy, cov_yy;
+  double var_major, var_minor, angle;
+  double centre_x, centre_y;            /* the centre of the miss distance in use */
+  double k2[ERPL_DISP_MAX_LEVELS], semi_major[ERPL_DISP_MAX_LEVELS], semi_minor[ERPL_DISP_MAX_LEVELS];
+  int64_t inside[ERPL_DISP_MAX_LEVELS];
+  erpl_row_stats miss;
+} erpl_dispersion;
+
+/* Host only: rows {IMPACT_X, IMPACT_Y}, ERPL_CENTRE_POINT at (0, 0) - the launch site -, levels {0.5, 0.9, 0.99},
+ * q {0.5, 0.9, 0.95, 0.99}. */
+int erpl_mc_dispersion_defaults(erpl_dispersion_spec* spec);
+/* miss: optional caller-owned device double [n] that receives r (NaN where the sample is not counted). */
+int erpl_mc_dispersion(erpl_ctx* ctx, const double* summary, const uint8_t* mask, int64_t n,
+                       const erpl_dispersion_spec* spec, erpl_dispersion* result, double* miss, void* hip_stream);
 
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
