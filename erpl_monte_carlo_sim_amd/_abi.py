@@ -166,6 +166,30 @@ class ErplDispersion(C.Structure):
                 ("inside", C.c_int64 * DISP_MAX_LEVELS), ("miss", ErplRowStats)]
 
 
+# erpl_mc_correlation
+CORR_MAX_FACTORS = 32
+CORR_MAX_ROWS = 16
+CORR_MAX_VARS = 48
+
+_CV_D = C.c_double * CORR_MAX_VARS
+_CM_D = (C.c_double * CORR_MAX_FACTORS) * CORR_MAX_ROWS
+_CR_D = C.c_double * CORR_MAX_ROWS
+
+
+class ErplCorrSpec(C.Structure):
+    _fields_ = [("n_factors", C.c_int32), ("n_rows", C.c_int32), ("rows", C.c_int32 * CORR_MAX_ROWS),
+                ("ranks", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ErplCorrResult(C.Structure):
+    _fields_ = [("n", C.c_int64), ("count", C.c_int64), ("n_masked", C.c_int64), ("n_non_finite", C.c_int64),
+                ("constant", C.c_int32 * CORR_MAX_VARS),
+                ("mean", _CV_D), ("std", _CV_D), ("min", _CV_D), ("max", _CV_D),
+                ("pearson", _CM_D), ("spearman", _CM_D), ("src", _CM_D), ("srrc", _CM_D),
+                ("r2", _CR_D), ("r2_rank", _CR_D),
+                ("regression_ok", C.c_int32), ("rank_regression_ok", C.c_int32)]
+
+
 LIB_NAME = "liberpl_mc.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
@@ -182,7 +206,8 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_check_batch", "erpl_mc_set_adopt_spin", "erpl_mc_set_short_flight_overlap",
            "erpl_mc_analysis_defaults", "erpl_mc_analyze",
            "erpl_mc_histogram_defaults", "erpl_mc_histogram", "erpl_mc_histogram_xy",
-           "erpl_mc_dispersion_defaults", "erpl_mc_dispersion")
+           "erpl_mc_dispersion_defaults", "erpl_mc_dispersion",
+           "erpl_mc_correlation_defaults", "erpl_mc_correlation")
 
 _lib = None
 
@@ -257,6 +282,9 @@ def load_library(path=None):
     lib.erpl_mc_dispersion_defaults.argtypes = [C.POINTER(ErplDispersionSpec)]
     lib.erpl_mc_dispersion.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplDispersionSpec),
                                        C.POINTER(ErplDispersion), C.c_void_p, C.c_void_p]
+    lib.erpl_mc_correlation_defaults.argtypes = [C.POINTER(ErplCorrSpec)]
+    lib.erpl_mc_correlation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplCorrSpec),
+                                        C.POINTER(ErplCorrResult), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if a declared symbol is not exported
         if name not in ("erpl_mc_last_error",):

@@ -231,3 +231,97 @@ def landing_dispersion(summary, status=None, engine=None, target=None, levels=(0
                             quantiles=quantiles)
     out["n_samples"], out["n_outliers"] = int(res.n_valid), int(res.n_outliers)
     return out
+
+
+# ---------------------------------------------------------------------------------- drivers: which dispersion drives what
+ROW_NAMES = ("apogee_altitude", "apogee_time", "first_apogee_altitude", "first_apogee_time", "range", "flight_time",
+             "rail_exit_time", "rail_exit_speed", "impact_x", "impact_y", "impact_z", "n_steps",
+             "rail_exit_angle_of_attack", "rail_exit_sideslip", "final_vz", "max_speed")   # _abi.SUM_* order
+
+_VEC_PARAMS = ("initial_position_offset", "initial_velocity_offset", "initial_attitude_offset",
+               "initial_angular_velocity_offset")
+_SCALAR_PARAMS = ("mass_multiplier", "thrust_multiplier", "wind_speed", "wind_direction", "density_multiplier")
+_MOTOR_INPUTS = ("motor_thrust", "motor_mass_flow_rate")
+
+
+def factors_from_results(results):
+    """The reference's per-sample `parameters` dicts (monte_carlo.py:156-179) of a list of result records as factor rows:
+    (float64 [F, n] NumPy array, names).  Names: `initial_position_offset[0]` ... `initial_angular_velocity_offset[2]`,
+    then mass_multiplier, thrust_multiplier, wind_speed, wind_direction, density_multiplier - `random_seed` is left out;
+    thrust_multiplier and density_multiplier, which the reference draws and then ignores, are kept on purpose: a
+    parameter without effect showing a correlation of about 0 is information - and, where the records carry
+    `motor_inputs`, the two motor inputs the kernel actually saw: motor_thrust and motor_mass_flow_rate.  A key that a
+    record does not carry is NaN there (listwise deletion then drops the sample)."""
+    records = [r for r in results if r is not None]
+    names = [f"{k}[{c}]" for k in _VEC_PARAMS for c in range(3)] + list(_SCALAR_PARAMS)
+    with_motor = any("motor_inputs" in r for r in records)
+    if with_motor:
+        names += list(_MOTOR_INPUTS)
+    out = np.full((len(names), len(records)), np.nan)
+    for i, r in enumerate(records):
+        p = r.get("parameters", {})
+        for j, k in enumerate(_VEC_PARAMS):
+            if k in p:
+                out[3 * j:3 * j + 3, i] = np.asarray(p[k], dtype=np.float64)
+        for j, k in enumerate(_SCALAR_PARAMS):
+            if k in p:
+                out[12 + j, i] = p[k]
+        if with_motor:
+            m = r.get("motor_inputs", {})
+            for j, k in enumerate(_MOTOR_INPUTS):
+                out[12 + len(_SCALAR_PARAMS) + j, i] = m.get(k, np.nan)
+    return out, names
+
+
+def summary_from_results(results):
+    """The [16, n] summary columns behind a list of result records (rows a record does not carry are NaN)."""
+    from . import _abi
+    from .results import SCALAR_COLUMNS
+    table, ids = getattr(results, "table", None), getattr(results, "ids", None)
+    if table is not None and ids is not None:
+        return np.ascontiguousarray(table.summary[:, ids], dtype=np.float64)
+    records = [r for r in results if r is not None]
+    cols = np.full((_abi.SUMMARY_DIM, len(records)), np.nan)
+    for i, r in enumerate(records):
+        for name, row in SCALAR_COLUMNS:
+            cols[row, i] = r.get(name, np.nan)
+        if r.get("impact_position") is not None:
+            cols[_abi.SUM_IMPACT_X:_abi.SUM_IMPACT_Z + 1, i] = r["impact_position"]
+        cols[_abi.SUM_STEPS, i] = r.get("n_steps", np.nan)
+    return cols
+
+
+def rank_drivers(corr, factor_names, ranks=True):
+    """For every row of a correlation dict the factor names sorted by |spearman| descending (|pearson| when
+    ranks=False), constant factors (NaN) last, ties and the constant ones in factor order."""
+    rho = np.abs(np.asarray(corr["spearman" if ranks else "pearson"], dtype=np.float64))
+    out = []
+    for j in range(rho.shape[0]):
+        key = np.where(np.isnan(rho[j]), -1.0, rho[j])
+        out.append([factor_names[f] for f in np.argsort(-key, kind="stable")])
+    return out
+
+
+def drivers(summary, factors, factor_names, status=None, engine=None, rows=None, ranks=True):
+    """Which input dispersion drives which outcome, on the device: erpl_mc_analyze for the reason bytes (as
+    `native_distributions`), then erpl_mc_correlation between the rows of `factors` (float64 [F, n] device tensor, e.g.
+    `run_monte_carlo_device(..., keep_factors=True)['factors']`) and summary rows `rows` (default apogee, range, flight
+    time) over the samples the filter keeps and whose factors and rows are all finite.  Returns the dict of
+    TrajectoryEngine.correlation plus 'factor_names', 'row_names', 'n_samples', 'n_outliers' and 'ranking': per row the
+    factor names by |spearman| descending (|pearson| when ranks=False), constant factors last.
+
+    Reading it: spearman / pearson are marginal, srrc / src are the effect with the other factors held fixed and
+    r2_rank / r2 say how much of the outcome the (rank-)linear model explains.  Factors that are affine images of one
+    another (see `sampling.synthetic_dispersions`: position_x and motor_thrust_multiplier with a non-zero position
+    sigma) cannot be separated: regression_ok = 0 and the coefficients are NaN, the correlations stay."""
+    engine = _engine_of(summary, engine)
+    factor_names = list(factor_names)
+    if len(factor_names) != int(factors.shape[0]):
+        raise ValueError(f"{len(factor_names)} factor names for {int(factors.shape[0])} factor rows")
+    res, why = engine.analyze(summary, status, rows=[], quantiles=[], reasons=True)
+    out = engine.correlation(factors, summary, why, rows=rows, ranks=ranks)
+    out["factor_names"] = factor_names
+    out["row_names"] = [ROW_NAMES[r] for r in out["rows"]]
+    out["n_samples"], out["n_outliers"] = int(res.n_valid), int(res.n_outliers)
+    out["ranking"] = rank_drivers(out, factor_names, ranks)
+    return out

@@ -295,6 +295,12 @@ struct erpl_ctx {
   struct DistHost* dist_host = nullptr;
   double* dist_miss = nullptr;
   int64_t dist_cap = 0;
+  // erpl_mc_correlation: fixed block (partials, the blocked Gram triangles), pinned mirror of its result part, and one
+  // buffer that grows with n * V: sort keys and indices, the rows of ranks, the population bytes, the sort's scratch
+  ErplCorrWork* corr_work = nullptr;
+  ErplCorrOut* corr_host = nullptr;
+  char* corr_buf = nullptr;
+  size_t corr_cap = 0;
 };
 
 namespace {
@@ -560,6 +566,8 @@ int erpl_mc_destroy(erpl_ctx* c) {
   if (c->ana_host) (void)hipHostFree(c->ana_host);
   (void)hipFree(c->dist_work); (void)hipFree(c->dist_miss);
   if (c->dist_host) (void)hipHostFree(c->dist_host);
+  (void)hipFree(c->corr_work); (void)hipFree(c->corr_buf);
+  if (c->corr_host) (void)hipHostFree(c->corr_host);
   delete c;
   return ERPL_OK;
 }
@@ -1532,6 +1540,209 @@ int erpl_mc_dispersion(erpl_ctx* c, const double* summary, const uint8_t* mask, 
     o.order_lo[k] = double_of_key(r.key[2 * k]);
     o.order_hi[k] = double_of_key(r.key[2 * k + 1]);
     o.quantile[k] = o.order_lo[k] + (o.order_hi[k] - o.order_lo[k]) * (pos - lo);
+  }
+  return ERPL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------- erpl_mc_correlation
+namespace {
+
+// S_ab of the blocked upper triangle the device hands back (erpl_tables.h)
+double gram_at(const double* g, int nbk, int a, int b) {
+  if (a > b) std::swap(a, b);
+  const int bi = a / 4, bj = b / 4;
+  return g[((bi * (2 * nbk - bi + 1)) / 2 + bj - bi) * 16 + (a % 4) * 4 + (b % 4)];
+}
+
+// corr (V x V, row-major) from the centred sums: unit diagonal, NaN where either variable is constant
+void corr_from_gram(const double* g, int V, const int32_t* constant, bool any, double* corr) {
+  const int nbk = (V + 3) / 4;
+  for (int a = 0; a < V; ++a)
+    for (int b = 0; b < V; ++b) {
+      double r = NAN;
+      if (any && !constant[a] && !constant[b])
+        r = a == b ? 1.0 : gram_at(g, nbk, a, b) / (sqrt(gram_at(g, nbk, a, a)) * sqrt(gram_at(g, nbk, b, b)));
+      corr[(size_t)a * V + b] = r;
+    }
+}
+
+// Standardised regression of every non-constant row on the non-constant factors: R_ff beta = r_fy by Cholesky.  The k-th
+// pivot is 1 - R^2 of factor k on the factors before it.  false: a pivot below 1e-10 or not finite (everything stays NaN).
+bool regress(const double* corr, int V, int F, int R, const int32_t* constant, double (*coef)[ERPL_CORR_MAX_FACTORS],
+             double* r2) {
+  int use[ERPL_CORR_MAX_FACTORS], m = 0;
+  for (int f = 0; f < F; ++f) if (!constant[f]) use[m++] = f;
+  static thread_local double L[ERPL_CORR_MAX_FACTORS][ERPL_CORR_MAX_FACTORS];
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double s = corr[(size_t)use[i] * V + use[j]];
+      for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+      if (i == j) {
+        if (!(s >= 1e-10) || !std::isfinite(s)) return false;
+        L[i][i] = sqrt(s);
+      } else {
+        L[i][j] = s / L[j][j];
+      }
+    }
+  for (int j = 0; j < R; ++j) {
+    if (constant[F + j]) continue;
+    double y[ERPL_CORR_MAX_FACTORS], beta[ERPL_CORR_MAX_FACTORS];
+    for (int i = 0; i < m; ++i) {
+      double s = corr[(size_t)(F + j) * V + use[i]];
+      for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
+      y[i] = s / L[i][i];
+    }
+    for (int i = m - 1; i >= 0; --i) {
+      double s = y[i];
+      for (int k = i + 1; k < m; ++k) s -= L[k][i] * beta[k];
+      beta[i] = s / L[i][i];
+    }
+    double fit = 0.0;
+    for (int i = 0; i < m; ++i) {
+      coef[j][use[i]] = beta[i];
+      fit += beta[i] * corr[(size_t)(F + j) * V + use[i]];
+    }
+    r2[j] = fit;
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int erpl_mc_correlation_defaults(erpl_corr_spec* spec) {
+  if (!spec) return fail(ERPL_ERR_INVALID, "spec is NULL");
+  memset(spec, 0, sizeof(*spec));
+  spec->n_rows = 3;
+  spec->rows[0] = ERPL_SUM_APOGEE_ALT; spec->rows[1] = ERPL_SUM_RANGE; spec->rows[2] = ERPL_SUM_FLIGHT_TIME;
+  spec->ranks = 1;
+  return ERPL_OK;
+}
+
+int erpl_mc_correlation(erpl_ctx* c, const double* factors, const double* summary, const uint8_t* mask, int64_t n,
+                        const erpl_corr_spec* spec, erpl_corr_result* result, double* corr, double* rank_corr,
+                        double* ranks_out, void* stream) {
+  if (!spec) return fail(ERPL_ERR_INVALID, "spec is NULL");
+  if (spec->n_factors < 1 || spec->n_factors > ERPL_CORR_MAX_FACTORS)
+    return fail(ERPL_ERR_INVALID, "spec->n_factors = %d outside 1..%d", spec->n_factors, ERPL_CORR_MAX_FACTORS);
+  if (spec->n_rows < 1 || spec->n_rows > ERPL_CORR_MAX_ROWS)
+    return fail(ERPL_ERR_INVALID, "spec->n_rows = %d outside 1..%d", spec->n_rows, ERPL_CORR_MAX_ROWS);
+  for (int j = 0; j < spec->n_rows; ++j) {
+    const int rc = check_row(spec->rows[j], "rows", j);
+    if (rc != ERPL_OK) return rc;
+    for (int k = 0; k < j; ++k)
+      if (spec->rows[k] == spec->rows[j]) return fail(ERPL_ERR_INVALID, "spec->rows[%d] = %d is listed twice", j, spec->rows[j]);
+  }
+  if (spec->ranks != 0 && spec->ranks != 1) return fail(ERPL_ERR_INVALID, "spec->ranks = %d: 0 or 1", spec->ranks);
+  if (!spec->ranks && rank_corr) return fail(ERPL_ERR_INVALID, "rank_corr is given but spec->ranks = 0");
+  if (!spec->ranks && ranks_out) return fail(ERPL_ERR_INVALID, "ranks_out is given but spec->ranks = 0");
+  if (n <= 0) return fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
+  if (spec->ranks && n > 0xffffffffll)
+    return fail(ERPL_ERR_INVALID, "n = %lld with spec->ranks = 1: the sort carries 32-bit sample indices", (long long)n);
+  if (!factors) return fail(ERPL_ERR_INVALID, "factors is NULL");
+  if (!summary) return fail(ERPL_ERR_INVALID, "summary is NULL");
+  if (!result) return fail(ERPL_ERR_INVALID, "result is NULL");
+  if (!c) return fail(ERPL_ERR_INVALID, "ctx is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int F = spec->n_factors, R = spec->n_rows, V = F + R;
+  const bool ranks = spec->ranks != 0;
+
+  ErplCorrArgs a;
+  memset(&a, 0, sizeof(a));
+  a.mask = mask; a.n = n; a.n_vars = V;
+  // the buffer: [keys 2n u64][ranks V n doubles unless the caller keeps them][idx 2n u32][scratch of the sort][pop n bytes]
+  size_t temp_bytes = 0;
+  if (ranks) {
+    const int le = erpl_launch_corr_ranks(a, nullptr, nullptr, nullptr, nullptr, nullptr, &temp_bytes, stream);
+    if (le != 0) return fail(ERPL_ERR_HIP, "radix sort sizing failed: %s", hipGetErrorString((hipError_t)le));
+    temp_bytes = (std::max(temp_bytes, (size_t)256) + 255) & ~(size_t)255;
+  }
+  const size_t un = (size_t)n;
+  const size_t off_ranks = ranks ? 16 * un : 0;
+  const size_t off_idx = off_ranks + (ranks && !ranks_out ? 8 * un * (size_t)V : 0);
+  const size_t off_temp = (off_idx + (ranks ? 8 * un : 0) + 255) & ~(size_t)255;
+  const size_t off_pop = off_temp + temp_bytes;
+  const size_t need = off_pop + un;
+  if (!c->corr_work) HIP_TRY(hipMalloc((void**)&c->corr_work, sizeof(ErplCorrWork)));
+  if (!c->corr_host) HIP_TRY(hipHostMalloc((void**)&c->corr_host, sizeof(ErplCorrOut), hipHostMallocDefault));
+  if (need > c->corr_cap) {
+    HIP_TRY(hipDeviceSynchronize());   // an earlier call on another stream may still read the old buffer
+    (void)hipFree(c->corr_buf);
+    c->corr_buf = nullptr; c->corr_cap = 0;
+    HIP_TRY(hipMalloc((void**)&c->corr_buf, need));
+    c->corr_cap = need;
+  }
+  a.work = c->corr_work;
+  a.pop = (uint8_t*)(c->corr_buf + off_pop);
+  for (int f = 0; f < F; ++f) a.var[f] = factors + (size_t)f * un;
+  for (int j = 0; j < R; ++j) a.var[F + j] = summary + (size_t)spec->rows[j] * un;
+
+  int le = erpl_launch_corr_population(a, stream);
+  if (le == 0) le = erpl_launch_corr_gram(a, 0, stream);
+  if (le != 0) return fail(ERPL_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)le));
+  if (ranks) {
+    double* rk = ranks_out ? ranks_out : (double*)(c->corr_buf + off_ranks);
+    for (int v = 0; v < V; ++v) {
+      le = erpl_launch_corr_ranks(a, a.var[v], rk + (size_t)v * un, (unsigned long long*)c->corr_buf,
+                                  (uint32_t*)(c->corr_buf + off_idx), c->corr_buf + off_temp, &temp_bytes, stream);
+      if (le != 0) return fail(ERPL_ERR_HIP, "rank pass failed: %s", hipGetErrorString((hipError_t)le));
+    }
+    ErplCorrArgs b = a;
+    for (int v = 0; v < V; ++v) b.var[v] = rk + (size_t)v * un;
+    le = erpl_launch_corr_gram(b, 1, stream);
+    if (le != 0) return fail(ERPL_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)le));
+  }
+  HIP_TRY(hipMemcpyAsync(c->corr_host, &c->corr_work->out, sizeof(ErplCorrOut), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+
+  const ErplCorrOut& h = *c->corr_host;
+  const double nan = NAN;
+  memset(result, 0, sizeof(*result));
+  result->n = n;
+  result->count = (int64_t)h.counter[0];
+  result->n_masked = (int64_t)h.counter[1];
+  result->n_non_finite = (int64_t)h.counter[2];
+  const bool any = h.counter[0] > 0ull;
+  const int nbk = (V + 3) / 4;
+  for (int v = 0; v < ERPL_CORR_MAX_VARS; ++v) {
+    const bool in = any && v < V;
+    result->constant[v] = in && h.vmin[v] == h.vmax[v] ? 1 : 0;
+    result->mean[v] = in ? h.mean[v] : nan;
+    result->std[v] = in ? sqrt(gram_at(h.gram[0], nbk, v, v) / (double)h.counter[0]) : nan;
+    result->min[v] = in ? h.vmin[v] : nan;
+    result->max[v] = in ? h.vmax[v] : nan;
+  }
+  for (int j = 0; j < ERPL_CORR_MAX_ROWS; ++j) {
+    for (int f = 0; f < ERPL_CORR_MAX_FACTORS; ++f)
+      result->pearson[j][f] = result->spearman[j][f] = result->src[j][f] = result->srrc[j][f] = nan;
+    result->r2[j] = result->r2_rank[j] = nan;
+  }
+  std::vector<double> own((size_t)V * V);
+  for (int pass = 0; pass < (ranks ? 2 : 1); ++pass) {
+    double* m = pass ? rank_corr : corr;
+    if (!m) m = own.data();
+    corr_from_gram(h.gram[pass], V, result->constant, any, m);
+    double (*rho)[ERPL_CORR_MAX_FACTORS] = pass ? result->spearman : result->pearson;
+    for (int j = 0; j < R; ++j)
+      for (int f = 0; f < F; ++f) rho[j][f] = m[(size_t)(F + j) * V + f];
+    bool ok = false;
+    if (any) {
+      erpl_corr_result fit;   // filled only if every pivot holds
+      for (int j = 0; j < ERPL_CORR_MAX_ROWS; ++j) {
+        for (int f = 0; f < ERPL_CORR_MAX_FACTORS; ++f) fit.src[j][f] = nan;
+        fit.r2[j] = nan;
+      }
+      ok = regress(m, V, F, R, result->constant, fit.src, fit.r2);
+      if (ok) {
+        memcpy(pass ? result->srrc : result->src, fit.src, sizeof(fit.src));
+        memcpy(pass ? result->r2_rank : result->r2, fit.r2, sizeof(fit.r2));
+      }
+    }
+    (pass ? result->rank_regression_ok : result->regression_ok) = ok ? 1 : 0;
   }
   return ERPL_OK;
 }

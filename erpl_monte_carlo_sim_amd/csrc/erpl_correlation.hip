@@ -1,0 +1,289 @@
+// erpl_correlation.hip — the device passes of erpl_mc_correlation: which input dispersion drives which outcome.  The
+// reference only records parameter_ranges_observed; this is Pearson / Spearman correlation between [F][n] factor rows
+// and rows of the [16][n] summary, next to erpl_mc_analyze.
+//
+//   population   one pass over the V rows: a byte per sample (0 = mask byte 0 and every variable finite) and the three
+//                counts (ballots, 64-bit integer atomics)
+//   moments      per variable: sum / min / max over the population, partials per workgroup, fixed tree (the shape of
+//                erpl_ana_moments)
+//   gram         the hot pass: V (V + 1) / 2 centred cross-product sums.  A workgroup stages a tile of ERPL_CORR_TILE
+//                samples x V centred values in LDS; a thread owns one 4 x 4 block of the upper triangle and every
+//                `slices`-th sample of the tile, 16 running sums in registers, accumulated in sample order; the slices
+//                are added in order through LDS, the workgroups' partials by one small kernel in workgroup order
+//   ranks        per variable: order-preserving keys (samples outside the population get the largest key), rocPRIM's
+//                radix sort of (key, sample index), then every sorted position finds the ends of its run of equal keys
+//                by galloping + bisection and scatters first + (len + 1) / 2 to its sample
+// Grids and tiles are functions of n and V alone, every floating-point sum has a fixed order: the same bits in every
+// call.  No floating-point atomics.  Compiled with -ffp-contract=off like its siblings: x - mean and the products are
+// rounded as the two-pass NumPy formula rounds them (plain fp64 vector multiplies and adds, no MFMA).
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <string.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "erpl_tables.h"
+
+namespace {
+
+constexpr int kWaves = ERPL_ANA_BLOCK / 64;
+constexpr int kStride = ERPL_CORR_NB * 4 + 2;   // doubles per staged sample: 16-byte aligned rows, spread over the banks
+typedef unsigned long long u64;
+
+__device__ __forceinline__ bool finite_bits(double v) {
+  return (__double_as_longlong(v) & 0x7ff0000000000000ll) != 0x7ff0000000000000ll;
+}
+// order-preserving map of a finite double onto an unsigned key; -0.0 and +0.0 share one key (they tie)
+__device__ __forceinline__ u64 key_of(double v) {
+  const u64 b = v == 0.0 ? 0ull : (u64)__double_as_longlong(v);
+  return b ^ ((b >> 63) ? ~0ull : (1ull << 63));
+}
+
+int grid_of(int64_t n) {
+  const int64_t want = (n + ERPL_ANA_BLOCK - 1) / ERPL_ANA_BLOCK;
+  return (int)(want < ERPL_ANA_MAX_BLOCKS ? want : ERPL_ANA_MAX_BLOCKS);
+}
+
+// ---- population: the byte of every sample and the three counts
+__global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_population(const ErplCorrArgs a) {
+  __shared__ u64 s_cnt[kWaves][3];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
+  u64 in = 0ull, masked = 0ull, bad = 0ull;   // uniform over the wave
+  for (int64_t base = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + wave * 64; base < n; base += stride) {
+    const int64_t i = base + lane;
+    int why = -1;
+    if (i < n) {
+      why = (a.mask && a.mask[i] != 0) ? 1 : 0;
+      if (why == 0)
+        for (int v = 0; v < a.n_vars; ++v)
+          if (!finite_bits(a.var[v][i])) why = 2;
+      a.pop[i] = (uint8_t)why;
+    }
+    in += __popcll(__ballot(why == 0));
+    masked += __popcll(__ballot(why == 1));
+    bad += __popcll(__ballot(why == 2));
+  }
+  if (lane == 0) { s_cnt[wave][0] = in; s_cnt[wave][1] = masked; s_cnt[wave][2] = bad; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    u64 s = 0ull;
+    for (int w = 0; w < kWaves; ++w) s += s_cnt[w][threadIdx.x];
+    if (s) atomicAdd(&a.work->out.counter[threadIdx.x], s);
+  }
+}
+
+// ---- first moments of variable blockIdx.y over the population
+__global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_moments(const ErplCorrArgs a) {
+  __shared__ double s_sum[kWaves], s_min[kWaves], s_max[kWaves];
+  const int v = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
+  const double* __restrict__ x = a.var[v];
+  const uint8_t* __restrict__ pop = a.pop;
+  double sum = 0.0, mn = INFINITY, mx = -INFINITY;
+  for (int64_t i = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + threadIdx.x; i < n; i += stride) {
+    if (pop[i] == 0) {
+      const double val = x[i];
+      sum += val;
+      mn = val < mn ? val : mn;
+      mx = val > mx ? val : mx;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    sum += __shfl_down(sum, off);
+    const double m0 = __shfl_down(mn, off), m1 = __shfl_down(mx, off);
+    mn = m0 < mn ? m0 : mn;
+    mx = m1 > mx ? m1 : mx;
+  }
+  if (lane == 0) { s_sum[wave] = sum; s_min[wave] = mn; s_max[wave] = mx; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kWaves; ++w) { sum += s_sum[w]; mn = s_min[w] < mn ? s_min[w] : mn; mx = s_max[w] > mx ? s_max[w] : mx; }
+    a.work->psum[v][blockIdx.x] = sum;
+    a.work->pmin[v][blockIdx.x] = mn;
+    a.work->pmax[v][blockIdx.x] = mx;
+  }
+}
+
+__global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_finish_moments(const ErplCorrArgs a, const int nb) {
+  __shared__ double s_sum[kWaves], s_min[kWaves], s_max[kWaves];
+  const int v = blockIdx.x;
+  ErplCorrWork* w = a.work;
+  constexpr int per = ERPL_ANA_MAX_BLOCKS / ERPL_ANA_BLOCK;
+  double sum = 0.0, mn = INFINITY, mx = -INFINITY;
+  for (int k = 0; k < per; ++k) {
+    const int j = threadIdx.x * per + k;
+    if (j < nb) {
+      sum += w->psum[v][j];
+      mn = w->pmin[v][j] < mn ? w->pmin[v][j] : mn;
+      mx = w->pmax[v][j] > mx ? w->pmax[v][j] : mx;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    sum += __shfl_down(sum, off);
+    const double m0 = __shfl_down(mn, off), m1 = __shfl_down(mx, off);
+    mn = m0 < mn ? m0 : mn;
+    mx = m1 > mx ? m1 : mx;
+  }
+  if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = sum; s_min[threadIdx.x >> 6] = mn; s_max[threadIdx.x >> 6] = mx; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < kWaves; ++k) { sum += s_sum[k]; mn = s_min[k] < mn ? s_min[k] : mn; mx = s_max[k] > mx ? s_max[k] : mx; }
+    const double c = (double)w->out.counter[0];
+    w->out.mean[v] = sum / c;   // NaN for an empty population; the host reports every double of it as NaN
+    w->out.vmin[v] = mn;
+    w->out.vmax[v] = mx;
+    w->rank_mean[v] = (c + 1.0) * 0.5;
+  }
+}
+
+// ---- gram: the centred cross-product sums of this workgroup's tiles, as a blocked upper triangle
+__global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_gram(const ErplCorrArgs a, const int which) {
+  // the staged tile; afterwards the 16 sums of every thread (256 * 16 doubles fit)
+  __shared__ __attribute__((aligned(16))) double s_c[ERPL_CORR_TILE * kStride];
+  static_assert(ERPL_CORR_TILE * kStride >= ERPL_ANA_BLOCK * 16, "the slice reduction reuses the tile");
+  static_assert(ERPL_ANA_BLOCK % ERPL_CORR_TILE == 0, "a thread stages one sample of the tile");
+  const int V = a.n_vars, nbk = (V + 3) / 4, nblk = nbk * (nbk + 1) / 2, vp = nbk * 4;
+  const int slices = ERPL_ANA_BLOCK / nblk;   // >= 3: at most 78 blocks
+  const int t = threadIdx.x, blk = t % nblk, slice = t / nblk;
+  const bool active = slice < slices;
+  int bi = 0, bj = blk;
+  while (bj >= nbk - bi) { bj -= nbk - bi; ++bi; }
+  bj += bi;
+  const double* __restrict__ mean = which ? a.work->rank_mean : a.work->out.mean;
+  const int64_t n = a.n;
+  const int ls = t % ERPL_CORR_TILE, lv = t / ERPL_CORR_TILE;
+  double acc[4][4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[p][q] = 0.0;
+  for (int64_t base = (int64_t)blockIdx.x * ERPL_CORR_TILE; base < n; base += (int64_t)gridDim.x * ERPL_CORR_TILE) {
+    __syncthreads();   // the tile before this one has been consumed
+    {
+      const int64_t i = base + ls;
+      const bool use = i < n && a.pop[i] == 0;   // a sample outside the population adds zeros: nothing
+      for (int v = lv; v < vp; v += ERPL_ANA_BLOCK / ERPL_CORR_TILE)
+        s_c[ls * kStride + v] = (use && v < V) ? a.var[v][i] - mean[v] : 0.0;
+    }
+    __syncthreads();
+    if (active) {
+      const int64_t left = n - base;
+      const int cnt = left < ERPL_CORR_TILE ? (int)left : ERPL_CORR_TILE;
+      for (int s = slice; s < cnt; s += slices) {
+        const double* row = s_c + s * kStride;
+        double x[4], y[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) { x[p] = row[4 * bi + p]; y[p] = row[4 * bj + p]; }
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) acc[p][q] += x[p] * y[q];
+      }
+    }
+  }
+  __syncthreads();
+  if (active) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) s_c[(slice * nblk + blk) * 16 + p * 4 + q] = acc[p][q];
+  }
+  __syncthreads();
+  for (int k = t; k < nblk * 16; k += ERPL_ANA_BLOCK) {
+    double s = 0.0;
+    for (int sl = 0; sl < slices; ++sl) s += s_c[sl * nblk * 16 + k];
+    a.work->gpart[blockIdx.x][k] = s;
+  }
+}
+
+__global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_finish_gram(const ErplCorrArgs a, const int which, const int nwg,
+                                                                        const int len) {
+  const int k = blockIdx.x * ERPL_ANA_BLOCK + threadIdx.x;
+  if (k >= len) return;
+  double s = 0.0;
+  for (int w = 0; w < nwg; ++w) s += a.work->gpart[w][k];
+  a.work->out.gram[which][k] = s;
+}
+
+// ---- ranks
+__global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_keys(const ErplCorrArgs a, const double* __restrict__ x,
+                                                                 u64* __restrict__ keys, uint32_t* __restrict__ idx) {
+  const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
+  for (int64_t i = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + threadIdx.x; i < n; i += stride) {
+    keys[i] = a.pop[i] == 0 ? key_of(x[i]) : ~0ull;   // no finite double maps to the largest key
+    idx[i] = (uint32_t)i;
+  }
+}
+
+// keys: sorted, the population first.  Position p of a run of equal keys [first, last] gets first + (len + 1) / 2 (1-based
+// mid-rank); both ends by galloping away from p, then bisection: O(log len) reads next to p.
+__global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_assign(const ErplCorrArgs a, const u64* __restrict__ keys,
+                                                                   const uint32_t* __restrict__ idx, double* __restrict__ rank) {
+  const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
+  const int64_t count = (int64_t)a.work->out.counter[0];
+  for (int64_t p = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + threadIdx.x; p < n; p += stride) {
+    const uint32_t i = idx[p];
+    if (p >= count) { rank[i] = NAN; continue; }
+    const u64 k = keys[p];
+    int64_t first = p, last = p;
+    if (p > 0 && keys[p - 1] == k) {
+      int64_t eq = p - 1, step = 1;   // keys[eq] == k
+      while (eq - step >= 0 && keys[eq - step] == k) { eq -= step; step <<= 1; }
+      int64_t ne = eq - step < 0 ? -1 : eq - step;   // keys[ne] != k, or before the row
+      while (eq - ne > 1) {
+        const int64_t m = ne + (eq - ne) / 2;
+        if (keys[m] == k) eq = m; else ne = m;
+      }
+      first = eq;
+    }
+    if (p + 1 < count && keys[p + 1] == k) {
+      int64_t eq = p + 1, step = 1;
+      while (eq + step < count && keys[eq + step] == k) { eq += step; step <<= 1; }
+      int64_t ne = eq + step < count ? eq + step : count;   // keys[ne] != k, or behind the population
+      while (ne - eq > 1) {
+        const int64_t m = eq + (ne - eq) / 2;
+        if (keys[m] == k) eq = m; else ne = m;
+      }
+      last = eq;
+    }
+    rank[i] = (double)first + (double)(last - first + 2) * 0.5;   // exact: integers and halves below 2^52
+  }
+}
+
+}  // namespace
+
+int erpl_launch_corr_population(const ErplCorrArgs& a, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = grid_of(a.n);
+  hipError_t e = hipMemsetAsync(&a.work->out.counter[0], 0, sizeof(a.work->out.counter), st);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(erpl_corr_population, dim3(nb), dim3(ERPL_ANA_BLOCK), 0, st, a);
+  hipLaunchKernelGGL(erpl_corr_moments, dim3(nb, a.n_vars), dim3(ERPL_ANA_BLOCK), 0, st, a);
+  hipLaunchKernelGGL(erpl_corr_finish_moments, dim3(a.n_vars), dim3(ERPL_ANA_BLOCK), 0, st, a, nb);
+  return (int)hipGetLastError();
+}
+
+int erpl_launch_corr_gram(const ErplCorrArgs& a, int which, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t want = (a.n + ERPL_CORR_TILE - 1) / ERPL_CORR_TILE;
+  const int nwg = (int)(want < ERPL_CORR_GRAM_MAX_BLOCKS ? want : ERPL_CORR_GRAM_MAX_BLOCKS);
+  const int nbk = (a.n_vars + 3) / 4, len = nbk * (nbk + 1) / 2 * 16;
+  hipLaunchKernelGGL(erpl_corr_gram, dim3(nwg), dim3(ERPL_ANA_BLOCK), 0, st, a, which);
+  hipLaunchKernelGGL(erpl_corr_finish_gram, dim3((len + ERPL_ANA_BLOCK - 1) / ERPL_ANA_BLOCK), dim3(ERPL_ANA_BLOCK), 0, st, a,
+                     which, nwg, len);
+  return (int)hipGetLastError();
+}
+
+int erpl_launch_corr_ranks(const ErplCorrArgs& a, const double* x, double* rank_row, unsigned long long* keys, uint32_t* idx,
+                           void* temp, size_t* temp_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)a.n;
+  if (!temp) return (int)rocprim::radix_sort_pairs(nullptr, *temp_bytes, keys, keys, idx, idx, n, 0, 64, st);   // sizing only
+  const int nb = grid_of(a.n);
+  hipLaunchKernelGGL(erpl_corr_keys, dim3(nb), dim3(ERPL_ANA_BLOCK), 0, st, a, x, keys, idx);
+  hipError_t e = rocprim::radix_sort_pairs(temp, *temp_bytes, keys, keys + n, idx, idx + n, n, 0, 64, st);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(erpl_corr_assign, dim3(nb), dim3(ERPL_ANA_BLOCK), 0, st, a, keys + n, idx + n, rank_row);
+  return (int)hipGetLastError();
+}

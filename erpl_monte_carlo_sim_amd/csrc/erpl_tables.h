@@ -273,3 +273,43 @@ int erpl_launch_dist_hist(const ErplDistArgs& a, void* stream);      // work->ed
 int erpl_launch_dist_hist2d(const ErplDistArgs& a, void* stream);    // work->edges[0..1] -> work->cells, counted2, outside2
 int erpl_launch_dispersion(const ErplDispArgs& a, void* stream);     // -> work->mom, a.miss
 }
+
+// ---- erpl_mc_correlation (erpl_correlation.hip) ----
+// The streaming passes use the grid of the analysis passes.  The Gram pass cuts the V x V matrix into 4 x 4 blocks
+// (upper triangle: at most 78) and the samples into tiles of ERPL_CORR_TILE; workgroup w takes tiles w, w + grid, ...
+// with grid = min(ERPL_CORR_GRAM_MAX_BLOCKS, ceil(n / ERPL_CORR_TILE)): functions of n and V alone.
+#define ERPL_CORR_TILE 128
+#define ERPL_CORR_GRAM_MAX_BLOCKS 512
+#define ERPL_CORR_NB ((ERPL_CORR_MAX_VARS + 3) / 4)                       // 4 x 4 blocks per side
+#define ERPL_CORR_GRAM_LEN (ERPL_CORR_NB * (ERPL_CORR_NB + 1) / 2 * 16)   // doubles of one blocked upper triangle
+struct ErplCorrOut {                // what the device hands back
+  unsigned long long counter[4];    // [0] population, [1] masked, [2] mask byte 0 but some variable not finite
+  double mean[ERPL_CORR_MAX_VARS], vmin[ERPL_CORR_MAX_VARS], vmax[ERPL_CORR_MAX_VARS];
+  double gram[2][ERPL_CORR_GRAM_LEN];   // centred cross-product sums, [0] of the values, [1] of the ranks; block (bi, bj),
+                                        //   bi <= bj, at ((bi * (2 NB - bi + 1)) / 2 + bj - bi) * 16, element (p, q) at p * 4 + q
+};
+struct ErplCorrWork {
+  ErplCorrOut out;
+  double rank_mean[ERPL_CORR_MAX_VARS];   // (count + 1) / 2 for every variable: the mean of mid-ranks, exact
+  double psum[ERPL_CORR_MAX_VARS][ERPL_ANA_MAX_BLOCKS];   // first moments: partials per variable and workgroup
+  double pmin[ERPL_CORR_MAX_VARS][ERPL_ANA_MAX_BLOCKS];
+  double pmax[ERPL_CORR_MAX_VARS][ERPL_ANA_MAX_BLOCKS];
+  double gpart[ERPL_CORR_GRAM_MAX_BLOCKS][ERPL_CORR_GRAM_LEN];   // Gram: one blocked triangle per workgroup
+};
+struct ErplCorrArgs {
+  const double* var[ERPL_CORR_MAX_VARS];   // [n] each: factor rows, then summary rows (or rows of ranks)
+  const uint8_t* mask;                     // [n] or NULL
+  uint8_t* pop;                            // [n] workspace: 0 = in the population, 1 = masked, 2 = not finite
+  ErplCorrWork* work;
+  int64_t n;
+  int32_t n_vars;
+};
+extern "C++" {
+// Each enqueues its passes on `stream` and returns a hipError_t (0 = launched).
+int erpl_launch_corr_population(const ErplCorrArgs& a, void* stream);   // -> a.pop, work->out.counter / mean / vmin / vmax, rank_mean
+int erpl_launch_corr_gram(const ErplCorrArgs& a, int which, void* stream);   // centred on out.mean (0) / rank_mean (1) -> out.gram[which]
+// Mid-ranks of x within the population into rank_row (NaN outside it).  keys / idx: two [n] buffers each; temp: the sort's
+// scratch of *temp_bytes.  With temp == NULL only *temp_bytes is set (nothing is enqueued).
+int erpl_launch_corr_ranks(const ErplCorrArgs& a, const double* x, double* rank_row, unsigned long long* keys, uint32_t* idx,
+                           void* temp, size_t* temp_bytes, void* stream);
+}

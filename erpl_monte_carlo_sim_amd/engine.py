@@ -419,6 +419,61 @@ class TrajectoryEngine:
             out["miss_distance"] = r
         return out
 
+    def correlation(self, factors, summary, mask=None, rows=None, ranks=True, want_ranks=False):
+        """Which factor drives which outcome (erpl_mc_correlation): Pearson and - with ranks=True - Spearman correlation
+        and the standardised (rank) regression coefficients between the rows of `factors` (float64 [F, n] on the device,
+        F <= 32) and summary rows `rows` (default apogee, range, flight time), over ONE population: mask byte 0 and every
+        factor and every requested row finite.  V = F + R variables, the factors first.  Returns a dict: count, n_masked,
+        n_non_finite, mean / std / min / max / constant (NumPy, length V), pearson / spearman / src / srrc ([R, F]),
+        r2 / r2_rank ([R]), regression_ok / rank_regression_ok, corr / rank_corr ([V, V]; rank_corr is None without
+        ranks) and, with want_ranks=True, 'ranks': the float64 [V, n] device tensor of mid-ranks (NaN outside the
+        population).  A constant variable (min == max) has NaN correlations; factors that are affine images of each other
+        leave the correlations in place and set regression_ok = 0 (every src / r2 NaN)."""
+        n, mask_p = self._summary_and_mask(summary, mask)
+        if not (factors.is_cuda and factors.device == self.device and factors.dtype == torch.float64
+                and factors.dim() == 2 and factors.shape[1] == n and factors.is_contiguous()):
+            raise ValueError(f"factors must be a contiguous float64 [F, n] tensor on {self.device}")
+        F = int(factors.shape[0])
+        if not 1 <= F <= _abi.CORR_MAX_FACTORS:
+            raise ValueError(f"1 to {_abi.CORR_MAX_FACTORS} factors")
+        if want_ranks and not ranks:
+            raise ValueError("want_ranks needs ranks=True")
+        spec = _abi.ErplCorrSpec()
+        _abi.check(self.lib, self.lib.erpl_mc_correlation_defaults(C.byref(spec)), "erpl_mc_correlation_defaults")
+        if rows is not None:
+            rows = [int(r) for r in rows]
+            if not 1 <= len(rows) <= _abi.CORR_MAX_ROWS:
+                raise ValueError(f"1 to {_abi.CORR_MAX_ROWS} rows")
+            spec.n_rows = len(rows)
+            spec.rows[:len(rows)] = rows
+        spec.n_factors, spec.ranks = F, int(bool(ranks))
+        R = spec.n_rows
+        V = F + R
+        corr = np.empty((V, V), dtype=np.float64)
+        rank_corr = np.empty((V, V), dtype=np.float64) if ranks else None
+        rk = torch.empty((V, n), dtype=torch.float64, device=self.device) if want_ranks else None
+        res = _abi.ErplCorrResult()
+        st = torch.cuda.current_stream(self.device)
+        rc = self.lib.erpl_mc_correlation(self._ctx, C.c_void_p(factors.data_ptr()), C.c_void_p(summary.data_ptr()), mask_p,
+                                          n, C.byref(spec), C.byref(res), C.c_void_p(corr.ctypes.data),
+                                          C.c_void_p(rank_corr.ctypes.data) if ranks else None,
+                                          C.c_void_p(rk.data_ptr()) if want_ranks else None, C.c_void_p(st.cuda_stream))
+        _abi.check(self.lib, rc, "erpl_mc_correlation")
+        out = {"n": int(res.n), "count": int(res.count), "n_masked": int(res.n_masked),
+               "n_non_finite": int(res.n_non_finite), "rows": list(spec.rows[:R]), "n_factors": F,
+               "constant": np.array(res.constant[:V], dtype=np.int32)}
+        for k in ("mean", "std", "min", "max"):
+            out[k] = np.array(getattr(res, k)[:V], dtype=np.float64)
+        for k in ("pearson", "spearman", "src", "srrc"):
+            out[k] = np.ctypeslib.as_array(getattr(res, k))[:R, :F].copy()
+        out["r2"] = np.array(res.r2[:R], dtype=np.float64)
+        out["r2_rank"] = np.array(res.r2_rank[:R], dtype=np.float64)
+        out["regression_ok"], out["rank_regression_ok"] = bool(res.regression_ok), bool(res.rank_regression_ok)
+        out["corr"], out["rank_corr"] = corr, rank_corr
+        if want_ranks:
+            out["ranks"] = rk
+        return out
+
     def set_profiling(self, enable=True):
         """Record HIP events around the two kernels on the launch stream (erpl_mc_set_profiling)."""
         _abi.check(self.lib, self.lib.erpl_mc_set_profiling(self._ctx, int(bool(enable))), "erpl_mc_set_profiling")

@@ -46,6 +46,7 @@ class MonteCarloAnalyzer:
         # "f64" = the reference-order gate kernel (the reference's arithmetic op for op); "f32" = first-descent
         # apogee / healthy flights only
         self.precision = "f64_fast"
+        self._motor_inputs = None            # [2, n] of the last run_batch_arrays: thrust and mass flow the kernels read
         self.n_trajectories = 50             # samples that carry a 'trajectory' (plots use the first 50)
         self.trajectory_stride = 20
         # simulator attributes a user could have changed on FlightSimulator
@@ -74,7 +75,8 @@ class MonteCarloAnalyzer:
 
     def _integrate_shard(self, initial_conditions, params, lo, hi, n_traj_global):
         """Integrate samples [lo, hi) of `params` (dict of arrays or list of dicts) on this rank's GPU; returns
-        (summary [16, hi-lo] device tensor, status [hi-lo] device tensor, captured trajectories or None).
+        (summary [16, hi-lo] device tensor, status [hi-lo] device tensor, captured trajectories or None, motor inputs
+        [2, hi-lo] NumPy: the thrust and mass-flow rows of the batches the kernels read, for analysis.factors_from_results).
 
         The samples that carry a trajectory (global index < n_traj_global: the first ones of the shard) go through
         the trajectory-capture build in a small batch of their own; everything else runs in chunks of CHUNK samples
@@ -90,9 +92,12 @@ class MonteCarloAnalyzer:
             return flatten.dispersed_batch(self.rocket, self.motor, self.wind_model, initial_conditions, take(a, b),
                                            self.base_altitude_profile, self.base_wind_profile, threads=threads)
         parts, traj, capture_inputs = [], None, None
+        motor_parts = []
         m = max(0, min(hi, n_traj_global) - lo)   # local samples 0..m-1 are captured
         if m > 0:
-            db = DeviceBatch.from_host(host_batch(lo, lo + m), eng.device, prec)
+            hb = host_batch(lo, lo + m)
+            motor_parts.append(hb.motor[[0, 2]].copy())
+            db = DeviceBatch.from_host(hb, eng.device, prec)
             dt = min(self.dt_initial, 0.005)
             cap = int(np.ceil(self.max_time / dt / self.trajectory_stride)) + 4
             ids = list(range(m))
@@ -144,7 +149,10 @@ class MonteCarloAnalyzer:
             # validation and the upload (335 MB of pageable memory per chunk: 70 ms at the 4.6 GB/s such a copy gets) in
             # the worker too: on the default stream of the engine's device, before the submission that follows it there
             with torch.cuda.device(eng.device):
-                return DeviceBatch.from_host(host_batch(a, b, threads=max(1, flatten.host_cores() // workers)), eng.device, prec)
+                hb = host_batch(a, b, threads=max(1, flatten.host_cores() // workers))
+                db = DeviceBatch.from_host(hb, eng.device, prec)
+                db.motor_inputs = hb.motor[[0, 2]].copy()   # 16 bytes per sample, kept beside the summary
+                return db
         with ThreadPoolExecutor(workers) as pool:
             todo = iter(chunks)
             ready = collections.deque()
@@ -158,6 +166,7 @@ class MonteCarloAnalyzer:
                 if c is not None:
                     ready.append(pool.submit(device_batch, *c))
                 parts.append(eng.submit(db))
+                motor_parts.append(db.motor_inputs)
                 inflight.append((eng.last_ticket, db))
                 while len(inflight) > keep:
                     ticket, inputs = inflight.pop(0)
@@ -169,9 +178,10 @@ class MonteCarloAnalyzer:
         if m > 0:
             torch.cuda.current_stream(eng.device).wait_stream(capture_stream)
             del capture_inputs
+        motor_inputs = np.concatenate(motor_parts, axis=1) if motor_parts else np.zeros((2, 0))
         if len(parts) == 1:
-            return parts[0][0], parts[0][1], traj
-        return torch.cat([p[0] for p in parts], dim=1), torch.cat([p[1] for p in parts]), traj
+            return parts[0][0], parts[0][1], traj, motor_inputs
+        return torch.cat([p[0] for p in parts], dim=1), torch.cat([p[1] for p in parts]), traj, motor_inputs
 
     def run_batch_arrays(self, initial_conditions, parameter_samples):
         """Integrate the given dispersed samples; returns (summary [16, n], status [n]) NumPy arrays
@@ -184,16 +194,22 @@ class MonteCarloAnalyzer:
         box = {}
 
         def runner(_unused):
-            summ, status, box["traj"] = self._integrate_shard(initial_conditions, parameter_samples, lo, hi,
-                                                              min(self.n_trajectories, n))
+            summ, status, box["traj"], box["motor"] = self._integrate_shard(initial_conditions, parameter_samples, lo, hi,
+                                                                            min(self.n_trajectories, n))
             return summ, status
         local = _Shard(hi - lo) if hi > lo else None
         summ, status = dist.run_local_shard(n, local, runner)
         TrajectoryEngine.raise_if_incomplete(status)
+        # the motor inputs of THIS rank's shard (they are not gathered: NaN for the samples of other ranks)
+        self._motor_inputs = np.full((2, n), np.nan)
+        if "motor" in box:
+            self._motor_inputs[:, lo:hi] = box["motor"]
         return summ, status, box.get("traj"), lo
 
-    def _sample_table(self, summ, status, parameter_samples, traj, lo):
+    def _sample_table(self, summ, status, parameter_samples, traj, lo, motor_inputs=None):
         """Columns of the run as a results.SampleTable (per-sample dicts are built on access)."""
+        if motor_inputs is None and self._motor_inputs is not None and self._motor_inputs.shape[1] == np.shape(summ)[1]:
+            motor_inputs = self._motor_inputs   # of the run_batch_arrays call that produced `summ`
         trajectories = {}
         if traj is not None:
             ids, tr, tlen = traj
@@ -206,7 +222,7 @@ class MonteCarloAnalyzer:
                     "altitude": rec[:, 3].copy(),
                     "position": rec[:, 1:4].copy(),
                 }
-        return results_mod.SampleTable(summ, status, parameter_samples, trajectories)
+        return results_mod.SampleTable(summ, status, parameter_samples, trajectories, motor_inputs=motor_inputs)
 
     def _result_dicts(self, summ, status, parameter_samples, traj, lo):
         """The eager list of per-sample dicts (what round 2 returned; kept as the cross-check of LazyResults)."""
@@ -231,7 +247,7 @@ class MonteCarloAnalyzer:
         else:           # per-sample RandomState(i) streams
             params = flatten.generate_parameter_arrays(self.uncertainty_params, n_samples)
         summ, status, traj, lo = self.run_batch_arrays(initial_conditions, params)
-        table = self._sample_table(summ, status, params, traj, lo)
+        table = self._sample_table(summ, status, params, traj, lo, motor_inputs=self._motor_inputs)
         if self.verbose:
             print(f"Completed {table.n} out of {n_samples} simulations")
         out = results_mod.analyze_table(table, verbose=self.verbose)
@@ -242,7 +258,8 @@ class MonteCarloAnalyzer:
                                   "cores_used": self.n_cores, "gpus_used": ws}
         return out
 
-    def run_monte_carlo_device(self, initial_conditions, n_samples, seed=1234, precision="f64_fast", planar=False):
+    def run_monte_carlo_device(self, initial_conditions, n_samples, seed=1234, precision="f64_fast", planar=False,
+                               keep_factors=False):
         """Throughput form for 100 k - 10 M samples (BASELINE configs 3-5): dispersions are drawn on the
         device (`sampling.synthetic_dispersions`, same distributions, torch generator), each rank
         integrates `n_samples / world` of them, summaries are all-gathered and the outlier filter +
@@ -254,8 +271,14 @@ class MonteCarloAnalyzer:
         finish in the reference-order kernel), and with them the reference's outlier filter and statistics;
         "f32" is ~2.7x faster but on diverging samples only its `first_apogee_altitude` is within 0.1 % (its
         `apogee_altitude` on ~17 %, its end reason on ~52 %: DESIGN.md section 5), so n_outliers and the
-        statistics differ from the reference's; "f64" runs everything in the reference-order gate kernel."""
+        statistics differ from the reference's; "f64" runs everything in the reference-order gate kernel.
+
+        keep_factors=True keeps the per-sample draws (`sampling.FACTOR_NAMES`) and adds out["factors"] (float64
+        [F, n_samples] on the device, sample order of out["summary"]) and out["factor_names"], the input of
+        `analysis.drivers`.  One rank only: factors are not gathered across ranks (ValueError before any work)."""
         from . import sampling
+        if keep_factors and dist.world()[1] > 1:
+            raise ValueError("keep_factors=True is limited to a world size of 1: factors are not gathered across ranks")
         eng = shared_engine(self.device)
         eng.set_config(self._config())
         rank, ws = dist.world()
@@ -268,7 +291,7 @@ class MonteCarloAnalyzer:
         # as soon as it is drawn: generation, up to `depth` integrations and their tails overlap on the GPU.
         m = max(hi - lo, 1)
         gen_s = 0.0
-        parts, inflight = [], []
+        parts, inflight, fparts, fnames = [], [], [], None
         starts = list(range(0, m, self.DEVICE_CHUNK))
         # Sub-batches drawn before any of them is submitted: a sample budget (4 M samples, ~10 GB of wind tables at
         # K = 100), not a count.  A generation kernel enqueued behind a running flight launch waits for its waves to
@@ -292,6 +315,9 @@ class MonteCarloAnalyzer:
                 gen_s += time.time() - tg
                 for db in group:
                     parts.append(eng.submit(db))
+                    if keep_factors:
+                        fparts.append(db.factors)
+                        fnames = db.factor_names
                     inflight.append((eng.last_ticket, db))    # inputs outlive their batch
                 while len(inflight) > keep:
                     ticket, inputs = inflight.pop(0)
@@ -323,6 +349,9 @@ class MonteCarloAnalyzer:
         torch.cuda.synchronize(eng.device)
         t3 = time.time()
         out["summary"], out["status"] = summ, status
+        if keep_factors:
+            fac = fparts[0] if len(fparts) == 1 else torch.cat(fparts, dim=1)
+            out["factors"], out["factor_names"] = fac[:, : hi - lo].contiguous(), list(fnames)
         out["performance"] = {"total_time": t3 - t0, "simulations_per_second": n_samples / (t3 - t0), "gpus_used": ws,
                               "precision": precision, "generate_s": gen_s, "integrate_and_gather_s": t2 - t0 - gen_s,
                               "statistics_s": t3 - t2, "sub_batches": len(parts), "in_flight": eng.get_overlap()}
@@ -356,6 +385,26 @@ class MonteCarloAnalyzer:
         """No reference counterpart: impact footprint, confidence ellipses and CEP about `target` (default the launch
         site) as monte_carlo_landing.png, the numbers as landing_dispersion.json."""
         return plots.plot_landing_dispersion(self, analysis, save_plots, target)
+
+    def drivers(self, analysis, rows=None):
+        """Which dispersion drives which outcome (no reference counterpart; its authors dug through single samples by
+        hand): `analysis.drivers` on either kind of analysis dict.  With 'factors' (run_monte_carlo_device(...,
+        keep_factors=True)) everything stays on the device; otherwise the parameters of analysis['results'] are
+        flattened with `analysis.factors_from_results` and uploaded."""
+        from . import analysis as ana
+        eng = shared_engine(self.device)
+        if "factors" in analysis:
+            return ana.drivers(analysis["summary"], analysis["factors"], analysis["factor_names"],
+                               status=analysis.get("status"), engine=eng, rows=rows)
+        fac, names = ana.factors_from_results(analysis["results"])
+        summ = ana.summary_from_results(analysis["results"])
+        return ana.drivers(torch.as_tensor(summ, device=eng.device).contiguous(),
+                           torch.as_tensor(fac, device=eng.device).contiguous(), names, engine=eng, rows=rows)
+
+    def plot_drivers(self, analysis, save_plots=True):
+        """No reference counterpart: one tornado chart (Spearman and SRRC of the strongest factors) per default row, saved
+        as monte_carlo_drivers.png in the output directory; returns that directory."""
+        return plots.plot_drivers(self, analysis, save_plots)
 
     def _filter_physics_outliers(self, results):
         """monte_carlo.py:337-398."""

@@ -150,6 +150,37 @@ def landing_figure(dispersion, density=None, points=None):
     return fig
 
 
+def drivers_figure(drivers, row, top=10):
+    """Tornado chart of one outcome: horizontal bars of `spearman` and `srrc` (pearson and src for a dict computed with
+    ranks=False) of its `top` strongest factors, strongest on top, R^2 of the (rank) regression in the title.  drivers:
+    the dict of analysis.drivers; row: an index into its rows or one of its row_names."""
+    j = drivers["row_names"].index(row) if isinstance(row, str) else int(row)
+    ranked = drivers["rank_corr"] is not None
+    rho = np.asarray(drivers["spearman" if ranked else "pearson"])[j]
+    beta = np.asarray(drivers["srrc" if ranked else "src"])[j]
+    r2 = float(np.asarray(drivers["r2_rank" if ranked else "r2"])[j])
+    names = list(drivers["factor_names"])
+    order = [names.index(k) for k in drivers["ranking"][j] if not np.isnan(rho[names.index(k)])][:int(top)]
+    fig = _figure((9, 0.45 * max(len(order), 1) + 2.0))
+    ax = fig.subplots()
+    y = np.arange(len(order))[::-1].astype(np.float64)
+    ax.barh(y + 0.2, rho[order], height=0.4, label="Spearman" if ranked else "Pearson", alpha=0.8, edgecolor="black")
+    ax.barh(y - 0.2, np.nan_to_num(beta[order]), height=0.4, label="SRRC" if ranked else "SRC", alpha=0.8,
+            edgecolor="black")
+    ax.set_yticks(y)
+    ax.set_yticklabels([names[f] for f in order])
+    ax.axvline(0.0, color="black", linewidth=0.8)
+    ax.set_xlim(-1.05, 1.05)
+    ax.set_xlabel("Rank correlation / standardised rank regression coefficient" if ranked
+                  else "Correlation / standardised regression coefficient")
+    fit = "regression singular" if np.isnan(r2) else f"R\u00b2 = {r2:.3f}"
+    ax.set_title(f"Drivers of {drivers['row_names'][j]} ({fit}, {drivers['count']} samples)")
+    ax.grid(True, axis="x", alpha=0.3)
+    ax.legend(loc="lower right")
+    fig.tight_layout()
+    return fig
+
+
 def save_figure(fig, output_dir, name):
     path = os.path.join(output_dir, name)
     fig.savefig(path, dpi=DPI, bbox_inches="tight")
@@ -274,4 +305,34 @@ def plot_landing_dispersion(analyzer, analysis, save_plots=True, target=None):
         print(f"Landing dispersion plot saved to: {save_figure(fig, output_dir, 'monte_carlo_landing.png')}")
         with open(os.path.join(output_dir, "landing_dispersion.json"), "w") as fh:
             json.dump(to_serializable(disp), fh, indent=2)
+    return output_dir
+
+
+def plot_drivers(analyzer, analysis, save_plots=True):
+    """One tornado chart per default row (apogee, range, flight time) of `MonteCarloAnalyzer.drivers(analysis)`, stacked
+    in monte_carlo_drivers.png; returns the output directory (None without save_plots)."""
+    import io
+
+    from matplotlib import image as mpimg
+    d = analyzer.drivers(analysis)
+    panels = [drivers_figure(d, j) for j in range(len(d["row_names"]))]
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        # the panels have different heights (one bar pair per factor drawn): render each, stack the images
+        images = []
+        for f in panels:
+            buf = io.BytesIO()
+            f.savefig(buf, dpi=DPI // 2, format="png")
+            buf.seek(0)
+            images.append(mpimg.imread(buf))
+        width = max(im.shape[1] for im in images)
+        sheet = np.ones((sum(im.shape[0] for im in images), width, 4), dtype=images[0].dtype)
+        at = 0
+        for im in images:
+            sheet[at:at + im.shape[0], :im.shape[1], :im.shape[2]] = im
+            at += im.shape[0]
+        path = os.path.join(output_dir, "monte_carlo_drivers.png")
+        mpimg.imsave(path, sheet)
+        print(f"Drivers plot saved to: {path}")
     return output_dir

@@ -33,8 +33,10 @@ class SampleTable:
     (dict of [n, 3] / [n] arrays, flatten.generate_parameter_arrays) or the reference's list of parameter
     dicts, and the captured trajectories {sample id: dict}."""
 
-    def __init__(self, summary, status, params, trajectories=None):
+    def __init__(self, summary, status, params, trajectories=None, motor_inputs=None):
         self.summary = np.asarray(summary, dtype=np.float64)
+        # [2, n] or None: the thrust and mass-flow rows the kernel read (after the motor perturbation), 16 bytes per sample
+        self.motor_inputs = None if motor_inputs is None else np.asarray(motor_inputs, dtype=np.float64)
         self.status = np.asarray(status)
         self.params = params
         self.trajectories = trajectories or {}
@@ -63,6 +65,9 @@ class SampleTable:
         r["parachute_deployed"] = bool(st & _abi.ST_CHUTE)
         r["simulation_id"] = int(i)
         r["parameters"] = self.parameters(i)
+        if self.motor_inputs is not None:
+            r["motor_inputs"] = {"motor_thrust": float(self.motor_inputs[0, i]),
+                                 "motor_mass_flow_rate": float(self.motor_inputs[1, i])}
         if i in self.trajectories:
             r["trajectory"] = self.trajectories[i]
         if with_reasons:

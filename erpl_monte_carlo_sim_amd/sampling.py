@@ -31,6 +31,14 @@ DEFAULT_UNCERTAINTY = {
 }
 
 
+# rows of DeviceBatch.factors, in order (the liquid motor's mass-flow multiplier is absent for a solid motor)
+FACTOR_NAMES = ("position_x", "position_y", "position_z", "velocity_x", "velocity_y", "velocity_z",
+                "attitude_roll", "attitude_pitch", "attitude_yaw",
+                "angular_velocity_x", "angular_velocity_y", "angular_velocity_z",
+                "mass_multiplier", "motor_thrust_multiplier", "motor_mass_flow_multiplier",
+                "wind_speed", "wind_direction", "wind_mean_u", "wind_mean_v")
+
+
 def _euler_to_quaternion(roll, pitch, yaw):
     cr, sr = torch.cos(roll / 2), torch.sin(roll / 2)
     cp, sp = torch.cos(pitch / 2), torch.sin(pitch / 2)
@@ -71,7 +79,16 @@ def synthetic_dispersions(n, rocket, motor, wind_model, base_initial_conditions,
     offset (monte_carlo.py:268-280); otherwise the synthetic power-law profile on
     linspace(0, 25000, n_wind_knots) (monte_carlo.py:282-288).  The AR(1) recursion runs in fp64 in one
     HIP kernel (erpl_mc_synth_wind); the table is stored in the working precision.  `planar=True`
-    zeroes every out-of-plane input (Set P).  Returns an engine.DeviceBatch resident on `device`."""
+    zeroes every out-of-plane input (Set P).  Returns an engine.DeviceBatch resident on `device`.
+
+    The draws are kept on the batch as `db.factors` (float64 [F, n] on the device) with `db.factor_names` (FACTOR_NAMES;
+    no `motor_mass_flow_multiplier` row for a solid motor): position, velocity, attitude (Euler) and angular velocity
+    as handed to the kernels, the mass multiplier, k_thrust, mdot / motor.mass_flow_rate, the two wind uniforms and
+    the mean wind they give - the input of erpl_mc_correlation.  Mind the joint law above: with a non-zero
+    `initial_position` sigma `position_x` is an exact affine image of `motor_thrust_multiplier` (both are z[0]) and
+    `position_y` of the liquid mass-flow multiplier (z[1]) - the reference's behaviour, not a bug.  With the default
+    sigma of 0 those columns are constant and the correlation drops them; otherwise its regression_ok = 0 says that
+    the two effects cannot be told apart."""
     import ctypes as C
 
     import numpy as np
@@ -163,4 +180,12 @@ def synthetic_dispersions(n, rocket, motor, wind_model, base_initial_conditions,
                                        C.c_void_p(st.cuda_stream))
     _abi.check(engine.lib, rc, "erpl_mc_synth_wind")
     _check_ranges(ic, rk, mt, mean_u, mean_v)
-    return DeviceBatch(ic, rk, mt, dev64(alt_np).contiguous(), wind, precision)
+    db = DeviceBatch(ic, rk, mt, dev64(alt_np).contiguous(), wind, precision)
+    liquid = motor_kind(motor) != _abi.MOTOR_SOLID
+    rows = [pos, vel, att, omg, mass_mult.view(1, n), k_thrust.view(1, n)]
+    if liquid:
+        rows.append((mdot / motor.mass_flow_rate).view(1, n))
+    rows += [wind_speed.view(1, n), wind_dir.view(1, n), mean_u.view(1, n), mean_v.view(1, n)]
+    db.factors = torch.cat([r.expand(r.shape[0], n) for r in rows]).contiguous()
+    db.factor_names = [k for k in FACTOR_NAMES if liquid or k != "motor_mass_flow_multiplier"]
+    return db

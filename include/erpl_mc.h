@@ -508,6 +508,65 @@ int erpl_mc_dispersion_defaults(erpl_dispersion_spec* spec);
 int erpl_mc_dispersion(erpl_ctx* ctx, const double* summary, const uint8_t* mask, int64_t n,
                        const erpl_dispersion_spec* spec, erpl_dispersion* result, double* miss, void* hip_stream);
 
+/* Which dispersion drives which outcome, ON THE DEVICE: Pearson and Spearman correlation and standardised regression
+ * coefficients between up to 32 per-sample input factors and up to 16 summary rows.  Conventions of erpl_mc_histogram:
+ * `factors` is [n_factors][n] and `summary` [ERPL_SUMMARY_DIM][n] caller-owned device memory; `mask` is the `reasons`
+ * output of erpl_mc_analyze - a sample counts iff its byte is 0, NULL = every sample counts; spec and result are host
+ * memory; the work is enqueued on `hip_stream` behind what is there and the call returns when the result is filled; the
+ * workspace belongs to the context, grows only with n * V and is freed by erpl_mc_destroy.  ERPL_ERR_INVALID, before any
+ * device work and with a message that names the argument, for a NULL spec / factors / summary / result, n <= 0 (with
+ * ranks = 1 also n >= 2^32: sample indices travel through the sort as 32-bit values), n_factors or n_rows out of range, a
+ * row outside 0..15 or listed twice, ranks not 0 or 1, rank_corr or ranks_out given with ranks = 0; the context is
+ * checked last.  No floating-point atomics; grids and tiles are functions of n and V alone and every sum is reduced in
+ * a fixed order: two calls on the same inputs return the same bytes.
+ *
+ * V = n_factors + n_rows variables: the factors first, then the rows in spec order.
+ * Population (ONE, listwise deletion): mask byte 0 AND every factor finite AND every requested row finite.  n_masked
+ * counts non-zero mask bytes, n_non_finite the samples with mask byte 0 and some non-finite variable;
+ * count + n_masked + n_non_finite == n.
+ * mean = sum / count; std = sqrt(S_vv / count) from the centred second pass; min / max exact; constant[v] = (min == max).
+ * corr[a][b] = S_ab / sqrt(S_aa S_bb), S the centred cross-product sums over the population: symmetric, unit diagonal,
+ * NaN where either variable is constant.  pearson[j][f] = corr[n_factors + j][f].
+ * ranks = 1: every variable is replaced by its mid-rank within the population (1-based, ties averaged - exact multiples
+ * of 0.5, scipy.stats.rankdata; -0.0 and +0.0 tie); ranks_out (device [V][n] or NULL) receives them, NaN outside the
+ * population; rank_corr / spearman are the same computation on the ranks.  ranks = 0: spearman, srrc, r2_rank are NaN.
+ * Regression (on the host, from corr): over the non-constant factors R_ff beta = r_fy by Cholesky for every non-constant
+ * row; src[j][f] = beta_f (NaN for a constant factor or row), r2[j] = sum beta_f r_fy.  The k-th pivot is 1 - R^2 of
+ * factor k on the factors before it: a pivot below 1e-10 or not finite means a factor without a separable effect -
+ * regression_ok = 0, every src / r2 NaN, correlations still returned, no error.  srrc / r2_rank /
+ * rank_regression_ok: the same on rank_corr.
+ * count == 0: every double NaN, both ok flags 0; count == 1: every variable constant.  Neither is an error. */
+#define ERPL_CORR_MAX_FACTORS 32
+#define ERPL_CORR_MAX_ROWS 16           /* = ERPL_SUMMARY_DIM */
+#define ERPL_CORR_MAX_VARS 48
+
+typedef struct erpl_corr_spec {
+  int32_t n_factors;                    /* 1..32 */
+  int32_t n_rows;                       /* 1..16 */
+  int32_t rows[ERPL_CORR_MAX_ROWS];     /* summary rows, distinct, 0..15 */
+  int32_t ranks;                        /* 0: Pearson + SRC only; 1: also Spearman + SRRC */
+  int32_t reserved;
+} erpl_corr_spec;
+
+typedef struct erpl_corr_result {
+  int64_t n, count, n_masked, n_non_finite;
+  int32_t constant[ERPL_CORR_MAX_VARS]; /* variable v (factors first, then rows): min == max over the population */
+  double mean[ERPL_CORR_MAX_VARS], std[ERPL_CORR_MAX_VARS], min[ERPL_CORR_MAX_VARS], max[ERPL_CORR_MAX_VARS];
+  double pearson [ERPL_CORR_MAX_ROWS][ERPL_CORR_MAX_FACTORS];
+  double spearman[ERPL_CORR_MAX_ROWS][ERPL_CORR_MAX_FACTORS];
+  double src     [ERPL_CORR_MAX_ROWS][ERPL_CORR_MAX_FACTORS];  /* standardised regression coefficients */
+  double srrc    [ERPL_CORR_MAX_ROWS][ERPL_CORR_MAX_FACTORS];  /* the same on ranks */
+  double r2[ERPL_CORR_MAX_ROWS], r2_rank[ERPL_CORR_MAX_ROWS];
+  int32_t regression_ok, rank_regression_ok;
+} erpl_corr_result;
+
+/* Host only: rows {APOGEE_ALT, RANGE, FLIGHT_TIME}, ranks = 1, n_factors = 0 (the caller fills it in). */
+int erpl_mc_correlation_defaults(erpl_corr_spec* spec);
+/* corr / rank_corr: host double [V][V] or NULL. */
+int erpl_mc_correlation(erpl_ctx* ctx, const double* factors, const double* summary, const uint8_t* mask, int64_t n,
+                        const erpl_corr_spec* spec, erpl_corr_result* result, double* corr, double* rank_corr,
+                        double* ranks_out, void* hip_stream);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
