@@ -155,6 +155,21 @@ def device_statistics(summary, status=None):
     return out
 
 
+def _engine_of(summary, engine):
+    if engine is None:
+        from .simulator import shared_engine
+        engine = shared_engine(summary.device)
+    return engine
+
+
+def _filter(summary, status, engine):
+    """First step of every function that works on the filtered population: (engine, erpl_mc_analyze result without row
+    statistics, reason bytes [n] uint8 on the device - the mask of the call that follows)."""
+    engine = _engine_of(summary, engine)
+    res, why = engine.analyze(summary, status, rows=[], quantiles=[], reasons=True)
+    return engine, res, why
+
+
 def _row_dict(r, n_q):
     return {"count": int(r.count), "mean": r.mean, "std": r.std, "min": r.min, "max": r.max,
             "percentiles": list(r.quantile[:n_q]), "order_lo": list(r.order_lo[:n_q]), "order_hi": list(r.order_hi[:n_q])}
@@ -167,9 +182,7 @@ def native_statistics(summary, status=None, engine=None, rows=None, quantiles=(0
     (statistics of every requested summary row, with the two order statistics behind each percentile).
     CUDA tensors only: `device_statistics` stays the implementation for CPU tensors."""
     from . import _abi
-    if engine is None:
-        from .simulator import shared_engine
-        engine = shared_engine(summary.device)
+    engine = _engine_of(summary, engine)
     named = (("apogee_altitude", _abi.SUM_APOGEE_ALT), ("range", _abi.SUM_RANGE), ("flight_time", _abi.SUM_FLIGHT_TIME))
     wanted = [r for _, r in named] if rows is None else [int(r) for r in rows]
     described = wanted + [r for _, r in named if r not in wanted]
@@ -194,13 +207,6 @@ def native_statistics(summary, status=None, engine=None, rows=None, quantiles=(0
     return out
 
 
-def _engine_of(summary, engine):
-    if engine is None:
-        from .simulator import shared_engine
-        engine = shared_engine(summary.device)
-    return engine
-
-
 def native_distributions(summary, status=None, engine=None, bins=50, rows=None):
     """The histograms `plot_results` draws (monte_carlo.py:568-592), counted on the device: erpl_mc_analyze for the reason
     bytes, then erpl_mc_histogram over the samples that carry none - the filtered population `analysis['results']` holds.
@@ -208,9 +214,8 @@ def native_distributions(summary, status=None, engine=None, bins=50, rows=None):
     'counts', 'counted'}} with NumPy arrays equal to np.histogram(valid finite values of the row, bins), plus
     'valid_mask' (bool device tensor), 'outlier_reason_bits', 'n_samples' and 'n_outliers'."""
     from . import _abi
-    engine = _engine_of(summary, engine)
     rows = [_abi.SUM_APOGEE_ALT, _abi.SUM_RANGE, _abi.SUM_FLIGHT_TIME] if rows is None else [int(r) for r in rows]
-    res, why = engine.analyze(summary, status, rows=[], quantiles=[], reasons=True)
+    engine, res, why = _filter(summary, status, engine)
     edges, counts, info = engine.histogram(summary, why, rows=rows, bins=bins)
     out = {r: {"edges": edges[j], "counts": counts[j], "counted": int(info["counted"][j])} for j, r in enumerate(rows)}
     out["valid_mask"] = why == 0
@@ -225,8 +230,7 @@ def landing_dispersion(summary, status=None, engine=None, target=None, levels=(0
     impact point): mean, covariance, confidence ellipses with their empirical content and the miss distance about
     `target` ((x, y), default the launch site at the origin) with its exact quantiles; 'cep' is the median miss distance.
     The dict of TrajectoryEngine.dispersion plus 'n_samples' / 'n_outliers' of the filter."""
-    engine = _engine_of(summary, engine)
-    res, why = engine.analyze(summary, status, rows=[], quantiles=[], reasons=True)
+    engine, res, why = _filter(summary, status, engine)
     out = engine.dispersion(summary, why, centre=(0.0, 0.0) if target is None else target, levels=levels,
                             quantiles=quantiles)
     out["n_samples"], out["n_outliers"] = int(res.n_valid), int(res.n_outliers)
@@ -314,11 +318,11 @@ def drivers(summary, factors, factor_names, status=None, engine=None, rows=None,
     r2_rank / r2 say how much of the outcome the (rank-)linear model explains.  Factors that are affine images of one
     another (see `sampling.synthetic_dispersions`: position_x and motor_thrust_multiplier with a non-zero position
     sigma) cannot be separated: regression_ok = 0 and the coefficients are NaN, the correlations stay."""
-    engine = _engine_of(summary, engine)
+    engine = _engine_of(summary, engine)   # (a missing GPU is reported before a wrong list of names)
     factor_names = list(factor_names)
     if len(factor_names) != int(factors.shape[0]):
         raise ValueError(f"{len(factor_names)} factor names for {int(factors.shape[0])} factor rows")
-    res, why = engine.analyze(summary, status, rows=[], quantiles=[], reasons=True)
+    engine, res, why = _filter(summary, status, engine)
     out = engine.correlation(factors, summary, why, rows=rows, ranks=ranks)
     out["factor_names"] = factor_names
     out["row_names"] = [ROW_NAMES[r] for r in out["rows"]]

@@ -1,0 +1,170 @@
+// erpl_host.h — what the host units of the C ABI share (erpl_api.hip, erpl_sampling.hip, erpl_stats_api.hip): the error
+// text behind erpl_mc_last_error, the context, and the host patterns that exist once.  Internal, never installed.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <functional>
+#include <thread>
+#include <vector>
+
+#include "erpl_tables.h"
+
+// Formats the text erpl_mc_last_error returns and hands `code` back.  The thread-local buffer is defined once, in
+// erpl_api.hip: a buffer per unit would leave the messages of the other units unread.
+__attribute__((visibility("hidden"))) int erpl_fail(int code, const char* fmt, ...);
+
+#define HIP_TRY(expr)                                                                          \
+  do {                                                                                         \
+    hipError_t e_ = (expr);                                                                    \
+    if (e_ != hipSuccess) return erpl_fail(ERPL_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+// an int-returning call of this library: its code is handed on (the text is already in place)
+#define ERPL_TRY(...)                    \
+  do {                                   \
+    const int rc_ = (__VA_ARGS__);       \
+    if (rc_ != ERPL_OK) return rc_;      \
+  } while (0)
+
+// expr: the int an erpl_launch_* returns (0 or a hipError_t)
+#define LAUNCH_TRY(expr, what)                                                                          \
+  do {                                                                                                  \
+    const int le_ = (expr);                                                                             \
+    if (le_ != 0) return erpl_fail(ERPL_ERR_HIP, what ": %s", hipGetErrorString((hipError_t)le_));      \
+  } while (0)
+#define KERNEL_TRY(expr) LAUNCH_TRY(expr, "kernel launch failed")
+
+// erpl_mc_histogram / _histogram_xy / _dispersion: pinned mirror of what the host reads and writes of ErplDistWork
+struct DistHost {
+  ErplDistRange range;
+  double edges[ERPL_HIST_MAX_ROWS][ERPL_HIST_MAX_BINS + 1];
+  ErplDistHist hist;
+  unsigned long long counted2, outside2;
+  unsigned long long cells[ERPL_HIST2D_MAX_BINS * ERPL_HIST2D_MAX_BINS];
+  ErplDistMoments mom;
+};
+
+// Slot 0 serves erpl_mc_run_batch (on the caller's stream); slots 0..depth-1 serve erpl_mc_submit_batch
+// round-robin, each on its own internal stream.  Whoever uses a slot first waits (on the device) for
+// the slot's previous batch and records `done` behind its own kernels.
+#define ERPL_TICKET_RING 256
+struct ErplSlot {
+  void* res_r[2] = {nullptr, nullptr};      // resume-queue records (see erpl_tables.h)
+  double* res_d[2] = {nullptr, nullptr};
+  int32_t* res_i[2] = {nullptr, nullptr};
+  unsigned long long* d_queue = nullptr;    // qcnt[ERPL_MAX_PHASES + 2], qhead[...], then the hand-over queue's two cursor arrays
+  void* ext_r = nullptr;                    // hand-over queue records (fp64 throughput build -> reference-order kernel),
+  double* ext_d = nullptr;                  //   allocated with the first ERPL_PREC_F64_FAST batch of the set
+  int32_t* ext_i = nullptr;
+  int64_t ext_cap = 0;
+  unsigned long long* d_counters = nullptr; // 16 words
+  int64_t cap = 0;
+  hipEvent_t done = nullptr;                // everything of the slot's latest batch has run
+  hipEvent_t main_done = nullptr;           // its main flight launch has (the sweep stream waits for this)
+  bool used = false;                        // `done` has been recorded at least once
+  int64_t ticket = 0;                       // last batch submitted through this slot
+  unsigned long long* own_counters = nullptr; // pinned: d_counters[0..3] of the slot's latest erpl_mc_run_batch
+  unsigned long long* h_counters = nullptr; // pinned host copy of d_counters[0..3] of the slot's latest batch: `own_counters`,
+                                            // or the ticket record of the batch (erpl_mc_submit_batch)
+  bool latest_is_run = false;               // the slot's latest batch came through erpl_mc_run_batch (no ticket record)
+  int64_t last_n = 0, seq = 0;              // its size and its position in the order of all batches of the context
+};
+
+struct erpl_ctx {
+  int device = 0;
+  int n_cu = 256;
+  bool has_cfg = false;
+  ErplTables h_tables;            // host copy (scalars are passed to the kernels by value)
+  ErplTables* d_tables = nullptr;
+  // Two workspaces ("sets") per lane of erpl_mc_submit_batch, used alternately: slot[lane] and
+  // slot[ERPL_MAX_OVERLAP + lane].  A batch with lane adoption runs its rail and main flight launch on the lane's
+  // main stream and its sweep launches (the few long trajectories nobody adopted) on the lane's sweep stream, so
+  // the lane's NEXT batch - on the other set - starts when the main launch is over and overlaps the sweeps:
+  // batches of equal length submitted together run in step, and without this the tails of a whole round of
+  // them met on an otherwise empty GPU before the next round could start.
+  ErplSlot slot[2 * ERPL_MAX_OVERLAP];
+  hipStream_t lane_stream[ERPL_MAX_OVERLAP] = {};
+  hipStream_t lane_sweep[ERPL_MAX_OVERLAP] = {};
+  hipEvent_t lane_in_ready[ERPL_MAX_OVERLAP] = {};
+  unsigned lane_uses[ERPL_MAX_OVERLAP] = {};   // batches the lane has taken: parity picks the set
+  int depth = 3;                  // slots erpl_mc_submit_batch cycles through (erpl_mc_create: 8 with enough hardware queues)
+  int64_t submitted = 0;          // tickets handed out
+  // One record per ticket: its own completion event and its own pinned copy of the batch's counters, so
+  // that erpl_mc_check_batch(T) waits for T alone and reports T's own lost records however often T's workspace has
+  // been reused since.  A ring of the last ERPL_TICKET_RING tickets; a record that leaves the ring unreported is
+  // latched in `recycled_incomplete`.
+  hipEvent_t ring_done[ERPL_TICKET_RING] = {};
+  int64_t ring_ticket[ERPL_TICKET_RING] = {};
+  unsigned long long* ring_counters = nullptr;   // pinned [ERPL_TICKET_RING][4]
+  int64_t acked = 0;                // tickets <= acked have been reported by a blocking check of ALL batches
+  int64_t recycled_incomplete = 0;  // first incomplete ticket that left the ring before such a check saw it
+  int last_slot = 0;              // slot of the most recent batch (erpl_mc_last_stats)
+  int64_t reserve_n = 0;          // erpl_mc_reserve request, applied to a slot when it is first used
+  int adopt_spin = 1 << 22;       // polls of an adopting lane for a claimed record's ready word (erpl_mc_set_adopt_spin)
+  int adopt = -1;                 // lane adoption: flying lanes at or below which a wave hands its lanes over; 0 = off; < 0 = by batch
+  int chunk = -1;                 // steps per launch between compactions; 0 = one launch; < 0 = by the batches seen so far
+  int short_depth = 4;            // erpl_mc_set_short_flight_overlap
+  double seen_mean_steps = 0.0;   // physics RK4 steps per trajectory of the most recent COMPLETED batch
+  int64_t seen_seq = 0, batches = 0;
+  int waves = 0;   // 0 = choose by batch size
+  // one wave per workgroup: a finished wave frees its slot for the next batch at once (measured 2-5 %
+  // over 256-thread workgroups, alone and overlapped); refill as soon as a lane is idle (best: 1..4)
+  int block = 64, max_blocks = 0, refill = 1;
+  bool profiling = false;
+  long long profiled_runs = 0;
+  hipEvent_t ev[3 * ERPL_PROFILE_RING] = {};
+  // erpl_mc_analyze: fixed block (partials, histograms, counters), one reason byte per sample, pinned copy of the result
+  ErplAnaWork* ana_work = nullptr;
+  uint8_t* ana_why = nullptr;
+  size_t ana_cap = 0;             // bytes, as every capacity erpl_grow keeps
+  ErplAnaResult* ana_host = nullptr;
+  // erpl_mc_histogram / _histogram2d / _dispersion: fixed block (partials, edges, bins, cells), pinned mirror of what the
+  // host reads and writes, one double per sample for the miss distance when the caller keeps none
+  ErplDistWork* dist_work = nullptr;
+  DistHost* dist_host = nullptr;
+  double* dist_miss = nullptr;
+  size_t dist_cap = 0;
+  // erpl_mc_correlation: fixed block (partials, the blocked Gram triangles), pinned mirror of its result part, and one
+  // buffer that grows with n * V: sort keys and indices, the rows of ranks, the population bytes, the sort's scratch
+  ErplCorrWork* corr_work = nullptr;
+  ErplCorrOut* corr_host = nullptr;
+  char* corr_buf = nullptr;
+  size_t corr_cap = 0;
+};
+
+// A fixed device block and its pinned mirror, both allocated with the first call that needs them and freed by erpl_mc_destroy.
+template <typename Dev, typename Host>
+int erpl_first_use(Dev*& dev, Host*& host) {
+  if (!dev) HIP_TRY(hipMalloc((void**)&dev, sizeof(Dev)));
+  if (!host) HIP_TRY(hipHostMalloc((void**)&host, sizeof(Host), hipHostMallocDefault));
+  return ERPL_OK;
+}
+
+// The only place a per-context device buffer grows (the policy of erpl_mc_reserve): never shrinks, freed by
+// erpl_mc_destroy.  An earlier call on another stream may still read the old buffer, hence the device synchronise.
+template <typename T>
+int erpl_grow(T*& p, size_t& cap, size_t bytes) {
+  if (bytes <= cap) return ERPL_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  (void)hipFree(p);
+  p = nullptr; cap = 0;
+  HIP_TRY(hipMalloc((void**)&p, bytes));
+  cap = bytes;
+  return ERPL_OK;
+}
+
+// The host pools: worker w of nthr takes the samples [n * w / nthr, n * (w + 1) / nthr) or every nthr-th table entry.
+inline int host_threads(int32_t requested, int64_t n) {
+  int nthr = requested > 0 ? requested : (int)std::thread::hardware_concurrency();
+  if (nthr < 1) nthr = 1;
+  if (requested <= 0 && nthr > 32) nthr = 32;   // containers often expose more cores than their quota
+  if ((int64_t)nthr * 64 > n) nthr = (int)((n + 63) / 64);   // at least 64 samples per thread
+  return nthr < 1 ? 1 : nthr;
+}
+inline void run_threads(int nthr, const std::function<void(int)>& work) {
+  if (nthr == 1) { work(0); return; }
+  std::vector<std::thread> pool;
+  for (int w = 0; w < nthr; ++w) pool.emplace_back(work, w);
+  for (auto& t : pool) t.join();
+}

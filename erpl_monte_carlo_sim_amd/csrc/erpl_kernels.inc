@@ -1,6 +1,6 @@
 // erpl_kernels.inc — the trajectory kernels, written once and compiled three times:
-//   erpl_k64.hip  : real = double, ERPL_FAITHFUL = 1, -ffp-contract=off  (correctness gate, cfg 2; one wave per SIMD; and a
-//                   256-register instantiation that finishes the blow-ups the fp64 throughput build hands over)
+//   erpl_k64.hip  : real = double, ERPL_FAITHFUL = 1, -ffp-contract=off  (correctness gate, cfg 2; one wave per SIMD; the
+//                   same instantiation finishes the blow-ups the fp64 throughput build hands over: ERPL_SWEEP_MINW)
 //   erpl_k64f.hip : real = double, ERPL_FAITHFUL = 0, ERPL_TWO_WAVE = 1   (fp64 throughput: the headline build)
 //   erpl_k32.hip  : real = float,  ERPL_FAITHFUL = 0                      (fp32 throughput: healthy flights / first apogee)
 //

@@ -1,0 +1,583 @@
+// erpl_stats_api.hip — host halves of the analysis entry points of the C ABI (include/erpl_mc.h): erpl_mc_analyze,
+// erpl_mc_histogram, erpl_mc_histogram_xy, erpl_mc_dispersion, erpl_mc_correlation and their defaults.  Argument checks,
+// workspace, launches (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip) and what the host finishes in
+// double precision.  The refusals come in one order everywhere - spec fields, n, pointers, context - and need no device.
+#include <math.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "erpl_host.h"
+
+namespace {
+
+int check_row(int row, const char* name, int j) {
+  if (row >= 0 && row < ERPL_SUMMARY_DIM) return ERPL_OK;
+  if (j >= 0) return erpl_fail(ERPL_ERR_INVALID, "spec->%s[%d] = %d outside 0..%d", name, j, row, ERPL_SUMMARY_DIM - 1);
+  return erpl_fail(ERPL_ERR_INVALID, "spec->%s = %d outside 0..%d", name, row, ERPL_SUMMARY_DIM - 1);
+}
+
+// spec->rows of any spec: summary rows in range, none listed twice (how many there may be is the entry point's own bound)
+int check_row_list(const int32_t* rows, int n_rows) {
+  for (int j = 0; j < n_rows; ++j) {
+    ERPL_TRY(check_row(rows[j], "rows", j));
+    for (int k = 0; k < j; ++k)
+      if (rows[k] == rows[j]) return erpl_fail(ERPL_ERR_INVALID, "spec->rows[%d] = %d is listed twice", j, rows[j]);
+  }
+  return ERPL_OK;
+}
+
+// spec->q of erpl_analysis_spec and erpl_dispersion_spec: at most ERPL_ANALYSIS_MAX_Q fractions in [0, 1]
+int check_quantiles(const double* q, int n_q) {
+  if (n_q < 0 || n_q > ERPL_ANALYSIS_MAX_Q)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->n_q = %d outside 0..%d", n_q, ERPL_ANALYSIS_MAX_Q);
+  for (int j = 0; j < n_q; ++j)
+    if (!(q[j] >= 0.0 && q[j] <= 1.0)) return erpl_fail(ERPL_ERR_INVALID, "spec->q[%d] = %g outside [0, 1]", j, q[j]);
+  return ERPL_OK;
+}
+
+double double_of_key(unsigned long long k) {
+  const unsigned long long b = k ^ ((k >> 63) ? (1ull << 63) : ~0ull);
+  double v;
+  memcpy(&v, &b, sizeof(v));
+  return v;
+}
+
+// What the host finishes of one described row: the population std from m2, the order statistics back from their sort keys
+// and the linear interpolation between them.  A row that is not described, or has no finite valid value, is all NaN.
+void finish_row_stats(const ErplAnaRow& r, const double* q, int n_q, bool described, erpl_row_stats& o) {
+  const double nan = NAN;
+  o.count = described ? (int64_t)r.count : 0;
+  const bool any = described && r.count > 0ull;
+  const double cnt = (double)r.count;
+  o.mean = any ? r.mean : nan;
+  o.std = any ? sqrt(r.m2 / cnt) : nan;
+  o.min = any ? r.vmin : nan;
+  o.max = any ? r.vmax : nan;
+  for (int k = 0; k < ERPL_ANALYSIS_MAX_Q; ++k) {
+    if (!any || k >= n_q) { o.quantile[k] = o.order_lo[k] = o.order_hi[k] = nan; continue; }
+    const double pos = q[k] * (double)(r.count - 1ull);   // as on the device, which chose the ranks from it
+    const double lo = floor(pos);
+    o.order_lo[k] = double_of_key(r.key[2 * k]);
+    o.order_hi[k] = double_of_key(r.key[2 * k + 1]);
+    o.quantile[k] = o.order_lo[k] + (o.order_hi[k] - o.order_lo[k]) * (pos - lo);
+  }
+}
+
+int check_analysis_spec(const erpl_analysis_spec* s) {
+  const double bound[5] = {s->max_apogee, s->min_apogee, s->max_range, s->max_flight_time, s->energy_apogee};
+  const char* name[5] = {"max_apogee", "min_apogee", "max_range", "max_flight_time", "energy_apogee"};
+  for (int k = 0; k < 5; ++k)
+    if (std::isnan(bound[k])) return erpl_fail(ERPL_ERR_INVALID, "spec->%s is NaN", name[k]);
+  if (s->n_rows < 0 || s->n_rows > ERPL_ANALYSIS_MAX_ROWS)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->n_rows = %d outside 0..%d", s->n_rows, ERPL_ANALYSIS_MAX_ROWS);
+  ERPL_TRY(check_row_list(s->rows, s->n_rows));
+  return check_quantiles(s->q, s->n_q);
+}
+
+}  // namespace
+
+extern "C" {
+
+int erpl_mc_analysis_defaults(erpl_analysis_spec* spec) {
+  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  memset(spec, 0, sizeof(*spec));
+  spec->max_apogee = 80000.0;        // monte_carlo.py:343-346
+  spec->min_apogee = 100.0;
+  spec->max_range = 200000.0;
+  spec->max_flight_time = 600.0;
+  const double v_max = 1200.0, g = 9.81;
+  const double h_max = v_max * v_max / (2 * g);   // monte_carlo.py:349-353: theoretical_max_altitude, then * 1.2
+  spec->energy_apogee = h_max * 1.2;
+  spec->n_rows = 3;
+  spec->rows[0] = ERPL_SUM_APOGEE_ALT; spec->rows[1] = ERPL_SUM_RANGE; spec->rows[2] = ERPL_SUM_FLIGHT_TIME;
+  spec->n_q = 5;
+  const double q[5] = {0.05, 0.25, 0.5, 0.75, 0.95};
+  for (int j = 0; j < 5; ++j) spec->q[j] = q[j];
+  return ERPL_OK;
+}
+
+int erpl_mc_analyze(erpl_ctx* c, const double* summary, const int32_t* status, int64_t n, const erpl_analysis_spec* spec,
+                    erpl_analysis* result, uint8_t* reasons, void* stream) {
+  // spec, n and the pointers before the context: the argument checks need no device
+  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  ERPL_TRY(check_analysis_spec(spec));
+  if (n <= 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
+  if (!summary) return erpl_fail(ERPL_ERR_INVALID, "summary is NULL");
+  if (!result) return erpl_fail(ERPL_ERR_INVALID, "result is NULL");
+  if (!c) return erpl_fail(ERPL_ERR_INVALID, "ctx is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  ERPL_TRY(erpl_first_use(c->ana_work, c->ana_host));
+  ERPL_TRY(erpl_grow(c->ana_why, c->ana_cap, (size_t)n));   // one reason byte per sample
+  ErplAnaArgs a;
+  memset(&a, 0, sizeof(a));
+  a.summary = summary; a.status = status; a.why = c->ana_why; a.reasons = reasons; a.work = c->ana_work; a.n = n;
+  a.max_apogee = spec->max_apogee; a.min_apogee = spec->min_apogee; a.max_range = spec->max_range;
+  a.max_flight_time = spec->max_flight_time; a.energy_apogee = spec->energy_apogee;
+  a.n_rows = spec->n_rows; a.n_q = spec->n_q;
+  for (int j = 0; j < spec->n_rows; ++j) a.rows[j] = spec->rows[j];
+  for (int j = 0; j < spec->n_q; ++j) a.q[j] = spec->q[j];
+  KERNEL_TRY(erpl_launch_analysis(a, stream));
+  HIP_TRY(hipMemcpyAsync(c->ana_host, &c->ana_work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+
+  const ErplAnaResult& d = *c->ana_host;
+  memset(result, 0, sizeof(*result));
+  result->n = n;
+  result->n_valid = (int64_t)d.counter[13];
+  result->n_outliers = n - result->n_valid;
+  for (int k = 0; k < 6; ++k) result->reason_counts[k] = (int64_t)d.counter[k];
+  for (int k = 0; k < 5; ++k) result->termination_counts[k] = (int64_t)d.counter[6 + k];
+  result->n_status_nan = (int64_t)d.counter[11];
+  result->n_incomplete = (int64_t)d.counter[12];
+  for (int j = 0; j < ERPL_ANALYSIS_MAX_ROWS; ++j) finish_row_stats(d.row[j], spec->q, spec->n_q, j < spec->n_rows, result->row[j]);
+  if (result->n_incomplete > 0)
+    return erpl_fail(ERPL_ERR_INCOMPLETE, "%lld sample(s) carry ERPL_ST_INCOMPLETE: they were never integrated",
+                (long long)result->n_incomplete);
+  return ERPL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------- erpl_mc_histogram, erpl_mc_histogram_xy, erpl_mc_dispersion
+namespace {
+
+// lo / hi of one axis as the caller gave them: 1 = from the data, 0 = explicit, < 0 = refused
+int check_range(double lo, double hi, const char* lo_name, const char* hi_name, int j) {
+  char at[16] = "";
+  if (j >= 0) snprintf(at, sizeof(at), "[%d]", j);
+  if (std::isnan(lo) && std::isnan(hi)) return 1;
+  if (std::isnan(lo) || std::isnan(hi))
+    return erpl_fail(ERPL_ERR_INVALID, "spec->%s%s = %g, spec->%s%s = %g: both NaN (range from the data) or both finite", lo_name, at,
+                lo, hi_name, at, hi);
+  if (!std::isfinite(lo) || !std::isfinite(hi) || !std::isfinite(hi - lo))
+    return erpl_fail(ERPL_ERR_INVALID, "spec->%s%s = %g, spec->%s%s = %g: not a finite range", lo_name, at, lo, hi_name, at, hi);
+  if (lo > hi) return erpl_fail(ERPL_ERR_INVALID, "spec->%s%s = %g > spec->%s%s = %g", lo_name, at, lo, hi_name, at, hi);
+  return 0;
+}
+
+// The range in use: min / max found on the device for an automatic one ((0, 1) if nothing was counted), widened by a
+// half either side if empty.  false: hi - lo is not finite.
+bool settle_range(bool automatic, double found_lo, double found_hi, double* lo, double* hi) {
+  if (automatic) {
+    if (found_lo > found_hi) { found_lo = 0.0; found_hi = 1.0; }
+    *lo = found_lo; *hi = found_hi;
+  }
+  if (!std::isfinite(*hi - *lo)) return false;
+  if (*lo == *hi) { *lo -= 0.5; *hi += 0.5; }
+  return true;
+}
+
+// np.linspace(lo, hi, bins + 1): two roundings per edge (this file is compiled without contraction), the last edge exact
+void fill_edges(double lo, double hi, int bins, double* e) {
+  const double delta = hi - lo, div = (double)bins, step = delta / div;
+  if (step != 0.0) for (int i = 0; i < bins; ++i) e[i] = (double)i * step + lo;
+  else for (int i = 0; i < bins; ++i) e[i] = ((double)i / div) * delta + lo;
+  e[bins] = hi;
+}
+
+// A histogram call from "args filled" to "edges on the device": the range pass if some axis is automatic, the range in use
+// and the np.linspace edges of every axis in the pinned mirror, and their upload.  too_wide(j): the caller's refusal of an
+// axis whose range is wider than a double holds - the entry points name their fields differently.
+template <typename Refuse>
+int dist_edges(erpl_ctx* c, ErplDistArgs& a, hipStream_t st, Refuse too_wide) {
+  DistHost& h = *c->dist_host;
+  bool any_auto = false;
+  for (int j = 0; j < a.n_rows; ++j) any_auto = any_auto || a.automatic[j] != 0;
+  if (any_auto) {
+    KERNEL_TRY(erpl_launch_dist_range(a, st));
+    HIP_TRY(hipMemcpyAsync(&h.range, &c->dist_work->range, sizeof(ErplDistRange), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  memset(h.edges, 0, (size_t)a.n_rows * sizeof(h.edges[0]));
+  for (int j = 0; j < a.n_rows; ++j) {
+    if (!settle_range(a.automatic[j] != 0, h.range.lo[j], h.range.hi[j], &a.lo[j], &a.hi[j])) return too_wide(j);
+    fill_edges(a.lo[j], a.hi[j], a.bins[j], h.edges[j]);
+  }
+  HIP_TRY(hipMemcpyAsync(&c->dist_work->edges[0][0], &h.edges[0][0], (size_t)a.n_rows * sizeof(h.edges[0]),
+                         hipMemcpyHostToDevice, st));
+  return ERPL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int erpl_mc_histogram_defaults(erpl_hist_spec* spec) {
+  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  memset(spec, 0, sizeof(*spec));
+  spec->n_rows = 3;
+  spec->rows[0] = ERPL_SUM_APOGEE_ALT; spec->rows[1] = ERPL_SUM_RANGE; spec->rows[2] = ERPL_SUM_FLIGHT_TIME;
+  for (int j = 0; j < ERPL_HIST_MAX_ROWS; ++j) { spec->bins[j] = 50; spec->lo[j] = spec->hi[j] = NAN; }   // monte_carlo.py:570
+  return ERPL_OK;
+}
+
+int erpl_mc_histogram(erpl_ctx* c, const double* summary, const uint8_t* mask, int64_t n, const erpl_hist_spec* spec,
+                      double* edges, int64_t* counts, erpl_hist_result* result, void* stream) {
+  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  if (spec->n_rows < 1 || spec->n_rows > ERPL_HIST_MAX_ROWS)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->n_rows = %d outside 1..%d", spec->n_rows, ERPL_HIST_MAX_ROWS);
+  ERPL_TRY(check_row_list(spec->rows, spec->n_rows));
+  ErplDistArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int j = 0; j < spec->n_rows; ++j) {
+    if (spec->bins[j] < 1 || spec->bins[j] > ERPL_HIST_MAX_BINS)
+      return erpl_fail(ERPL_ERR_INVALID, "spec->bins[%d] = %d outside 1..%d", j, spec->bins[j], ERPL_HIST_MAX_BINS);
+    const int rc = check_range(spec->lo[j], spec->hi[j], "lo", "hi", j);
+    if (rc < 0) return rc;
+    a.rows[j] = spec->rows[j]; a.partner[j] = -1; a.bins[j] = spec->bins[j]; a.automatic[j] = rc;
+    a.lo[j] = spec->lo[j]; a.hi[j] = spec->hi[j];
+  }
+  if (n <= 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
+  if (!summary) return erpl_fail(ERPL_ERR_INVALID, "summary is NULL");
+  if (!edges) return erpl_fail(ERPL_ERR_INVALID, "edges is NULL");
+  if (!counts) return erpl_fail(ERPL_ERR_INVALID, "counts is NULL");
+  if (!result) return erpl_fail(ERPL_ERR_INVALID, "result is NULL");
+  if (!c) return erpl_fail(ERPL_ERR_INVALID, "ctx is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  ERPL_TRY(erpl_first_use(c->dist_work, c->dist_host));
+  hipStream_t st = (hipStream_t)stream;
+  DistHost& h = *c->dist_host;
+  a.summary = summary; a.mask = mask; a.work = c->dist_work; a.n = n; a.n_rows = spec->n_rows;
+  ERPL_TRY(dist_edges(c, a, st, [&](int j) {
+    return erpl_fail(ERPL_ERR_INVALID, "spec->rows[%d] = %d: the range of the counted values, %g to %g, is wider than a double holds",
+                     j, spec->rows[j], a.lo[j], a.hi[j]);
+  }));
+  KERNEL_TRY(erpl_launch_dist_hist(a, stream));
+  HIP_TRY(hipMemcpyAsync(&h.hist, &c->dist_work->hist, sizeof(ErplDistHist), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  memset(result, 0, sizeof(*result));
+  memcpy(edges, h.edges, (size_t)spec->n_rows * sizeof(h.edges[0]));
+  for (int j = 0; j < spec->n_rows; ++j) {
+    for (int k = 0; k < ERPL_HIST_MAX_BINS; ++k) counts[(size_t)j * ERPL_HIST_MAX_BINS + k] = (int64_t)h.hist.bins[j][k];
+    result->counted[j] = (int64_t)h.hist.counted[j];
+    result->below[j] = (int64_t)h.hist.below[j];
+    result->above[j] = (int64_t)h.hist.above[j];
+    result->lo[j] = a.lo[j]; result->hi[j] = a.hi[j];
+  }
+  return ERPL_OK;
+}
+
+int erpl_mc_histogram_xy(erpl_ctx* c, const double* summary, const uint8_t* mask, int64_t n, const erpl_hist2d_spec* spec,
+                        double* edges_x, double* edges_y, int64_t* counts, erpl_hist2d_result* result, void* stream) {
+  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  ERPL_TRY(check_row(spec->row_x, "row_x", -1));
+  ERPL_TRY(check_row(spec->row_y, "row_y", -1));
+  if (spec->row_x == spec->row_y) return erpl_fail(ERPL_ERR_INVALID, "spec->row_y = %d is listed twice (row_x)", spec->row_y);
+  if (spec->bins_x < 1 || spec->bins_x > ERPL_HIST2D_MAX_BINS)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->bins_x = %d outside 1..%d", spec->bins_x, ERPL_HIST2D_MAX_BINS);
+  if (spec->bins_y < 1 || spec->bins_y > ERPL_HIST2D_MAX_BINS)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->bins_y = %d outside 1..%d", spec->bins_y, ERPL_HIST2D_MAX_BINS);
+  const int auto_x = check_range(spec->lo_x, spec->hi_x, "lo_x", "hi_x", -1);
+  if (auto_x < 0) return auto_x;
+  const int auto_y = check_range(spec->lo_y, spec->hi_y, "lo_y", "hi_y", -1);
+  if (auto_y < 0) return auto_y;
+  if (n <= 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
+  if (!summary) return erpl_fail(ERPL_ERR_INVALID, "summary is NULL");
+  if (!edges_x) return erpl_fail(ERPL_ERR_INVALID, "edges_x is NULL");
+  if (!edges_y) return erpl_fail(ERPL_ERR_INVALID, "edges_y is NULL");
+  if (!counts) return erpl_fail(ERPL_ERR_INVALID, "counts is NULL");
+  if (!result) return erpl_fail(ERPL_ERR_INVALID, "result is NULL");
+  if (!c) return erpl_fail(ERPL_ERR_INVALID, "ctx is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  ERPL_TRY(erpl_first_use(c->dist_work, c->dist_host));
+  hipStream_t st = (hipStream_t)stream;
+  DistHost& h = *c->dist_host;
+  ErplDistArgs a;
+  memset(&a, 0, sizeof(a));
+  a.summary = summary; a.mask = mask; a.work = c->dist_work; a.n = n; a.n_rows = 2;
+  a.rows[0] = spec->row_x; a.rows[1] = spec->row_y; a.partner[0] = spec->row_y; a.partner[1] = spec->row_x;
+  a.bins[0] = spec->bins_x; a.bins[1] = spec->bins_y; a.automatic[0] = auto_x; a.automatic[1] = auto_y;
+  a.lo[0] = spec->lo_x; a.hi[0] = spec->hi_x; a.lo[1] = spec->lo_y; a.hi[1] = spec->hi_y;
+  ERPL_TRY(dist_edges(c, a, st, [&](int j) {
+    return erpl_fail(ERPL_ERR_INVALID, "spec->row_%s = %d: the range of the counted values, %g to %g, is wider than a double holds",
+                     j ? "y" : "x", a.rows[j], a.lo[j], a.hi[j]);
+  }));
+  KERNEL_TRY(erpl_launch_dist_hist2d(a, stream));
+  const size_t cells = (size_t)spec->bins_x * (size_t)spec->bins_y;
+  HIP_TRY(hipMemcpyAsync(&h.counted2, &c->dist_work->counted2, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h.cells, c->dist_work->cells, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  memcpy(edges_x, h.edges[0], (size_t)(spec->bins_x + 1) * sizeof(double));
+  memcpy(edges_y, h.edges[1], (size_t)(spec->bins_y + 1) * sizeof(double));
+  for (size_t k = 0; k < cells; ++k) counts[k] = (int64_t)h.cells[k];
+  memset(result, 0, sizeof(*result));
+  result->counted = (int64_t)h.counted2;
+  result->outside = (int64_t)h.outside2;
+  result->lo_x = a.lo[0]; result->hi_x = a.hi[0]; result->lo_y = a.lo[1]; result->hi_y = a.hi[1];
+  return ERPL_OK;
+}
+
+int erpl_mc_dispersion_defaults(erpl_dispersion_spec* spec) {
+  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  memset(spec, 0, sizeof(*spec));
+  spec->row_x = ERPL_SUM_IMPACT_X; spec->row_y = ERPL_SUM_IMPACT_Y;
+  spec->centre = ERPL_CENTRE_POINT;   // the launch site
+  spec->n_levels = 3;
+  spec->level[0] = 0.5; spec->level[1] = 0.9; spec->level[2] = 0.99;
+  spec->n_q = 4;
+  spec->q[0] = 0.5; spec->q[1] = 0.9; spec->q[2] = 0.95; spec->q[3] = 0.99;   // quantile[0]: the CEP
+  return ERPL_OK;
+}
+
+int erpl_mc_dispersion(erpl_ctx* c, const double* summary, const uint8_t* mask, int64_t n, const erpl_dispersion_spec* spec,
+                       erpl_dispersion* result, double* miss, void* stream) {
+  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  ERPL_TRY(check_row(spec->row_x, "row_x", -1));
+  ERPL_TRY(check_row(spec->row_y, "row_y", -1));
+  if (spec->row_x == spec->row_y) return erpl_fail(ERPL_ERR_INVALID, "spec->row_y = %d is listed twice (row_x)", spec->row_y);
+  if (spec->centre != ERPL_CENTRE_MEAN && spec->centre != ERPL_CENTRE_POINT)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->centre = %d: ERPL_CENTRE_MEAN or ERPL_CENTRE_POINT", spec->centre);
+  if (spec->centre == ERPL_CENTRE_POINT && !(std::isfinite(spec->cx) && std::isfinite(spec->cy)))
+    return erpl_fail(ERPL_ERR_INVALID, "spec->cx = %g, spec->cy = %g: not a finite point", spec->cx, spec->cy);
+  if (spec->n_levels < 0 || spec->n_levels > ERPL_DISP_MAX_LEVELS)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->n_levels = %d outside 0..%d", spec->n_levels, ERPL_DISP_MAX_LEVELS);
+  for (int k = 0; k < spec->n_levels; ++k)
+    if (!(spec->level[k] > 0.0 && spec->level[k] < 1.0))
+      return erpl_fail(ERPL_ERR_INVALID, "spec->level[%d] = %g outside (0, 1)", k, spec->level[k]);
+  ERPL_TRY(check_quantiles(spec->q, spec->n_q));
+  if (n <= 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
+  if (!summary) return erpl_fail(ERPL_ERR_INVALID, "summary is NULL");
+  if (!result) return erpl_fail(ERPL_ERR_INVALID, "result is NULL");
+  if (!c) return erpl_fail(ERPL_ERR_INVALID, "ctx is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  ERPL_TRY(erpl_first_use(c->dist_work, c->dist_host));
+  if (!miss) ERPL_TRY(erpl_grow(c->dist_miss, c->dist_cap, (size_t)n * sizeof(double)));   // the caller keeps no miss distances
+  ERPL_TRY(erpl_first_use(c->ana_work, c->ana_host));                // the selection's block,
+  ERPL_TRY(erpl_grow(c->ana_why, c->ana_cap, (size_t)n));            // and a row of zero bytes to stand in for a mask
+  hipStream_t st = (hipStream_t)stream;
+  ErplDispArgs d;
+  memset(&d, 0, sizeof(d));
+  d.summary = summary; d.mask = mask; d.work = c->dist_work; d.miss = miss ? miss : c->dist_miss; d.n = n;
+  d.row_x = spec->row_x; d.row_y = spec->row_y; d.centre = spec->centre; d.n_levels = spec->n_levels;
+  d.cx = spec->cx; d.cy = spec->cy;
+  for (int k = 0; k < spec->n_levels; ++k) d.k2[k] = -2.0 * log(1.0 - spec->level[k]);
+  KERNEL_TRY(erpl_launch_dispersion(d, stream));
+  // the miss distance as a one-row summary through the moment passes and the selection of erpl_mc_analyze
+  ErplAnaArgs a;
+  memset(&a, 0, sizeof(a));
+  a.summary = d.miss; a.work = c->ana_work; a.n = n; a.n_rows = 1; a.rows[0] = 0; a.n_q = spec->n_q;
+  for (int k = 0; k < spec->n_q; ++k) a.q[k] = spec->q[k];
+  if (mask) a.why = const_cast<uint8_t*>(mask);   // read only there
+  else { HIP_TRY(hipMemsetAsync(c->ana_why, 0, (size_t)n, st)); a.why = c->ana_why; }
+  KERNEL_TRY(erpl_launch_row_stats(a, stream));
+  HIP_TRY(hipMemcpyAsync(&c->dist_host->mom, &c->dist_work->mom, sizeof(ErplDistMoments), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(c->ana_host, &c->ana_work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+
+  const ErplDistMoments& m = c->dist_host->mom;
+  const double nan = NAN;
+  memset(result, 0, sizeof(*result));
+  result->count = (int64_t)m.count;
+  const bool any = m.count > 0ull;
+  result->mean_x = any ? m.mean_x : nan; result->mean_y = any ? m.mean_y : nan;
+  result->cov_xx = any ? m.cov_xx : nan; result->cov_xy = any ? m.cov_xy : nan; result->cov_yy = any ? m.cov_yy : nan;
+  const double half = (m.cov_xx + m.cov_yy) / 2, diff = (m.cov_xx - m.cov_yy) / 2;
+  const double root = sqrt(diff * diff + m.cov_xy * m.cov_xy);
+  result->var_major = any ? half + root : nan;
+  result->var_minor = any ? half - root : nan;
+  result->angle = any ? 0.5 * atan2(2 * m.cov_xy, m.cov_xx - m.cov_yy) : nan;
+  result->centre_x = any ? m.centre_x : nan; result->centre_y = any ? m.centre_y : nan;
+  const bool solid = any && m.det > 0.0 && std::isfinite(m.det);
+  for (int k = 0; k < ERPL_DISP_MAX_LEVELS; ++k) {
+    const bool asked = k < spec->n_levels;
+    result->k2[k] = asked && any ? d.k2[k] : nan;
+    // a variance that rounding has taken below zero has no axis: 0, as the degenerate ellipse it is
+    result->semi_major[k] = asked && any ? sqrt(d.k2[k] * fmax(result->var_major, 0.0)) : nan;
+    result->semi_minor[k] = asked && any ? sqrt(d.k2[k] * fmax(result->var_minor, 0.0)) : nan;
+    result->inside[k] = !asked || !any ? 0 : (solid ? (int64_t)m.inside[k] : -1);
+  }
+  finish_row_stats(c->ana_host->row[0], spec->q, spec->n_q, true, result->miss);
+  return ERPL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------- erpl_mc_correlation
+namespace {
+
+// S_ab of the blocked upper triangle the device hands back (erpl_tables.h)
+double gram_at(const double* g, int nbk, int a, int b) {
+  if (a > b) std::swap(a, b);
+  const int bi = a / 4, bj = b / 4;
+  return g[((bi * (2 * nbk - bi + 1)) / 2 + bj - bi) * 16 + (a % 4) * 4 + (b % 4)];
+}
+
+// corr (V x V, row-major) from the centred sums: unit diagonal, NaN where either variable is constant
+void corr_from_gram(const double* g, int V, const int32_t* constant, bool any, double* corr) {
+  const int nbk = (V + 3) / 4;
+  for (int a = 0; a < V; ++a)
+    for (int b = 0; b < V; ++b) {
+      double r = NAN;
+      if (any && !constant[a] && !constant[b])
+        r = a == b ? 1.0 : gram_at(g, nbk, a, b) / (sqrt(gram_at(g, nbk, a, a)) * sqrt(gram_at(g, nbk, b, b)));
+      corr[(size_t)a * V + b] = r;
+    }
+}
+
+// Standardised regression of every non-constant row on the non-constant factors: R_ff beta = r_fy by Cholesky.  The k-th
+// pivot is 1 - R^2 of factor k on the factors before it.  false: a pivot below 1e-10 or not finite (everything stays NaN).
+bool regress(const double* corr, int V, int F, int R, const int32_t* constant, double (*coef)[ERPL_CORR_MAX_FACTORS],
+             double* r2) {
+  int use[ERPL_CORR_MAX_FACTORS], m = 0;
+  for (int f = 0; f < F; ++f) if (!constant[f]) use[m++] = f;
+  static thread_local double L[ERPL_CORR_MAX_FACTORS][ERPL_CORR_MAX_FACTORS];
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double s = corr[(size_t)use[i] * V + use[j]];
+      for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+      if (i == j) {
+        if (!(s >= 1e-10) || !std::isfinite(s)) return false;
+        L[i][i] = sqrt(s);
+      } else {
+        L[i][j] = s / L[j][j];
+      }
+    }
+  for (int j = 0; j < R; ++j) {
+    if (constant[F + j]) continue;
+    double y[ERPL_CORR_MAX_FACTORS], beta[ERPL_CORR_MAX_FACTORS];
+    for (int i = 0; i < m; ++i) {
+      double s = corr[(size_t)(F + j) * V + use[i]];
+      for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
+      y[i] = s / L[i][i];
+    }
+    for (int i = m - 1; i >= 0; --i) {
+      double s = y[i];
+      for (int k = i + 1; k < m; ++k) s -= L[k][i] * beta[k];
+      beta[i] = s / L[i][i];
+    }
+    double fit = 0.0;
+    for (int i = 0; i < m; ++i) {
+      coef[j][use[i]] = beta[i];
+      fit += beta[i] * corr[(size_t)(F + j) * V + use[i]];
+    }
+    r2[j] = fit;
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int erpl_mc_correlation_defaults(erpl_corr_spec* spec) {
+  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  memset(spec, 0, sizeof(*spec));
+  spec->n_rows = 3;
+  spec->rows[0] = ERPL_SUM_APOGEE_ALT; spec->rows[1] = ERPL_SUM_RANGE; spec->rows[2] = ERPL_SUM_FLIGHT_TIME;
+  spec->ranks = 1;
+  return ERPL_OK;
+}
+
+int erpl_mc_correlation(erpl_ctx* c, const double* factors, const double* summary, const uint8_t* mask, int64_t n,
+                        const erpl_corr_spec* spec, erpl_corr_result* result, double* corr, double* rank_corr,
+                        double* ranks_out, void* stream) {
+  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  if (spec->n_factors < 1 || spec->n_factors > ERPL_CORR_MAX_FACTORS)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->n_factors = %d outside 1..%d", spec->n_factors, ERPL_CORR_MAX_FACTORS);
+  if (spec->n_rows < 1 || spec->n_rows > ERPL_CORR_MAX_ROWS)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->n_rows = %d outside 1..%d", spec->n_rows, ERPL_CORR_MAX_ROWS);
+  ERPL_TRY(check_row_list(spec->rows, spec->n_rows));
+  if (spec->ranks != 0 && spec->ranks != 1) return erpl_fail(ERPL_ERR_INVALID, "spec->ranks = %d: 0 or 1", spec->ranks);
+  if (!spec->ranks && rank_corr) return erpl_fail(ERPL_ERR_INVALID, "rank_corr is given but spec->ranks = 0");
+  if (!spec->ranks && ranks_out) return erpl_fail(ERPL_ERR_INVALID, "ranks_out is given but spec->ranks = 0");
+  if (n <= 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
+  if (spec->ranks && n > 0xffffffffll)
+    return erpl_fail(ERPL_ERR_INVALID, "n = %lld with spec->ranks = 1: the sort carries 32-bit sample indices", (long long)n);
+  if (!factors) return erpl_fail(ERPL_ERR_INVALID, "factors is NULL");
+  if (!summary) return erpl_fail(ERPL_ERR_INVALID, "summary is NULL");
+  if (!result) return erpl_fail(ERPL_ERR_INVALID, "result is NULL");
+  if (!c) return erpl_fail(ERPL_ERR_INVALID, "ctx is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int F = spec->n_factors, R = spec->n_rows, V = F + R;
+  const bool ranks = spec->ranks != 0;
+
+  ErplCorrArgs a;
+  memset(&a, 0, sizeof(a));
+  a.mask = mask; a.n = n; a.n_vars = V;
+  // the buffer: [keys 2n u64][ranks V n doubles unless the caller keeps them][idx 2n u32][scratch of the sort][pop n bytes]
+  size_t temp_bytes = 0;
+  if (ranks) {
+    LAUNCH_TRY(erpl_launch_corr_ranks(a, nullptr, nullptr, nullptr, nullptr, nullptr, &temp_bytes, stream), "radix sort sizing failed");
+    temp_bytes = (std::max(temp_bytes, (size_t)256) + 255) & ~(size_t)255;
+  }
+  const size_t un = (size_t)n;
+  const size_t off_ranks = ranks ? 16 * un : 0;
+  const size_t off_idx = off_ranks + (ranks && !ranks_out ? 8 * un * (size_t)V : 0);
+  const size_t off_temp = (off_idx + (ranks ? 8 * un : 0) + 255) & ~(size_t)255;
+  const size_t off_pop = off_temp + temp_bytes;
+  const size_t need = off_pop + un;
+  ERPL_TRY(erpl_first_use(c->corr_work, c->corr_host));
+  ERPL_TRY(erpl_grow(c->corr_buf, c->corr_cap, need));
+  a.work = c->corr_work;
+  a.pop = (uint8_t*)(c->corr_buf + off_pop);
+  for (int f = 0; f < F; ++f) a.var[f] = factors + (size_t)f * un;
+  for (int j = 0; j < R; ++j) a.var[F + j] = summary + (size_t)spec->rows[j] * un;
+
+  KERNEL_TRY(erpl_launch_corr_population(a, stream));
+  KERNEL_TRY(erpl_launch_corr_gram(a, 0, stream));
+  if (ranks) {
+    double* rk = ranks_out ? ranks_out : (double*)(c->corr_buf + off_ranks);
+    for (int v = 0; v < V; ++v)
+      LAUNCH_TRY(erpl_launch_corr_ranks(a, a.var[v], rk + (size_t)v * un, (unsigned long long*)c->corr_buf,
+                                        (uint32_t*)(c->corr_buf + off_idx), c->corr_buf + off_temp, &temp_bytes, stream),
+                 "rank pass failed");
+    ErplCorrArgs b = a;
+    for (int v = 0; v < V; ++v) b.var[v] = rk + (size_t)v * un;
+    KERNEL_TRY(erpl_launch_corr_gram(b, 1, stream));
+  }
+  HIP_TRY(hipMemcpyAsync(c->corr_host, &c->corr_work->out, sizeof(ErplCorrOut), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+
+  const ErplCorrOut& h = *c->corr_host;
+  const double nan = NAN;
+  memset(result, 0, sizeof(*result));
+  result->n = n;
+  result->count = (int64_t)h.counter[0];
+  result->n_masked = (int64_t)h.counter[1];
+  result->n_non_finite = (int64_t)h.counter[2];
+  const bool any = h.counter[0] > 0ull;
+  const int nbk = (V + 3) / 4;
+  for (int v = 0; v < ERPL_CORR_MAX_VARS; ++v) {
+    const bool in = any && v < V;
+    result->constant[v] = in && h.vmin[v] == h.vmax[v] ? 1 : 0;
+    result->mean[v] = in ? h.mean[v] : nan;
+    result->std[v] = in ? sqrt(gram_at(h.gram[0], nbk, v, v) / (double)h.counter[0]) : nan;
+    result->min[v] = in ? h.vmin[v] : nan;
+    result->max[v] = in ? h.vmax[v] : nan;
+  }
+  for (int j = 0; j < ERPL_CORR_MAX_ROWS; ++j) {
+    for (int f = 0; f < ERPL_CORR_MAX_FACTORS; ++f)
+      result->pearson[j][f] = result->spearman[j][f] = result->src[j][f] = result->srrc[j][f] = nan;
+    result->r2[j] = result->r2_rank[j] = nan;
+  }
+  std::vector<double> own((size_t)V * V);
+  for (int pass = 0; pass < (ranks ? 2 : 1); ++pass) {
+    double* m = pass ? rank_corr : corr;
+    if (!m) m = own.data();
+    corr_from_gram(h.gram[pass], V, result->constant, any, m);
+    double (*rho)[ERPL_CORR_MAX_FACTORS] = pass ? result->spearman : result->pearson;
+    for (int j = 0; j < R; ++j)
+      for (int f = 0; f < F; ++f) rho[j][f] = m[(size_t)(F + j) * V + f];
+    bool ok = false;
+    if (any) {
+      erpl_corr_result fit;   // filled only if every pivot holds
+      for (int j = 0; j < ERPL_CORR_MAX_ROWS; ++j) {
+        for (int f = 0; f < ERPL_CORR_MAX_FACTORS; ++f) fit.src[j][f] = nan;
+        fit.r2[j] = nan;
+      }
+      ok = regress(m, V, F, R, result->constant, fit.src, fit.r2);
+      if (ok) {
+        memcpy(pass ? result->srrc : result->src, fit.src, sizeof(fit.src));
+        memcpy(pass ? result->r2_rank : result->r2, fit.r2, sizeof(fit.r2));
+      }
+    }
+    (pass ? result->rank_regression_ok : result->regression_ok) = ok ? 1 : 0;
+  }
+  return ERPL_OK;
+}
+
+}  // extern "C"

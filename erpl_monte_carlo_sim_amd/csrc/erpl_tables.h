@@ -1,4 +1,4 @@
-// erpl_tables.h — device-side constant tables shared by the host API (erpl_api.cpp) and the
+// erpl_tables.h — device-side constant tables shared by the host units (erpl_host.h) and the
 // kernel translation units.  Everything here is derived on the HOST in fp64 from erpl_config
 // with the reference's own expressions (so the values are bit-identical to what the Python
 // reference recomputes on every call), then staged to LDS / scalar registers by the kernels.
@@ -142,9 +142,9 @@ int erpl_launch_f32(const ErplKArgs& a, const void* scalars, int block, int max_
 int erpl_launch_f64f(const ErplKArgs& a, const void* scalars, int block, int max_blocks, int n_phases, void* stream, void** ev,
                     void* tail_stream, void* main_done);
 // The sweep of the fp64 throughput build's hand-over queue by the reference-order flight kernel (no rail launch): `a` is
-// the batch's argument block with the hand-over queue mapped as phase 1 (see ErplKArgs::ext_r).  Compiled for <= 256
-// registers (two waves per SIMD, spills to scratch: it makes a few steps per record) so that its workgroups start
-// beside the throughput build's waves instead of waiting for an empty SIMD.
+// the batch's argument block with the hand-over queue mapped as phase 1 (see ErplKArgs::ext_r).  It runs the gate's own
+// instantiation (one wave per SIMD, all 512 registers, no scratch: ERPL_SWEEP_MINW = 1 in erpl_kernels.inc, where the
+// copy capped at 256 registers that round 4 first shipped is measured against it and dropped).
 int erpl_launch_f64_sweep(const ErplKArgs& a, const void* scalars, int block, int max_blocks, void* stream);
 // known-answer evaluation of one device function per lane (erpl_mc_debug_eval); in / out are [rows][m]
 int erpl_launch_debug_f64(const ErplKArgs& a, const void* scalars, int what, int64_t m, const double* in, double* out, void* stream);

@@ -88,6 +88,44 @@ class TrajectoryEngine:
         _abi.check(self.lib, self.lib.erpl_mc_create(idx, C.byref(self._ctx)), "erpl_mc_create")
         self._cfg = None
 
+    def _call(self, name, *args):
+        """`name(ctx, *args)` of the library; a non-zero return raises with the library's own message (_abi.check)."""
+        _abi.check(self.lib, getattr(self.lib, name)(self._ctx, *args), name)
+
+    def _defaults(self, cls, fn_name):
+        """A spec struct as the library's `erpl_mc_*_defaults` fills it."""
+        spec = cls()
+        _abi.check(self.lib, getattr(self.lib, fn_name)(C.byref(spec)), fn_name)
+        return spec
+
+    @staticmethod
+    def _batch_struct(db, flags=0):
+        """The `erpl_batch` that points at the tensors of a DeviceBatch."""
+        b = _abi.ErplBatch()
+        b.n, b.precision, b.k_wind, b.flags = db.n, db.precision, db.k_wind, flags
+        b.ic, b.rocket, b.motor = db.ic.data_ptr(), db.rocket.data_ptr(), db.motor.data_ptr()
+        b.alt_grid = db.alt_grid.data_ptr() if db.k_wind else None
+        b.wind = db.wind.data_ptr() if db.k_wind else None
+        return b
+
+    def _check_summary(self, summary):
+        """The summary tensor every analysis call reads on the device (there is no CPU path behind them): returns n."""
+        if not (summary.is_cuda and summary.device == self.device and summary.dtype == torch.float64
+                and summary.dim() == 2 and summary.shape[0] == _abi.SUMMARY_DIM and summary.is_contiguous()):
+            raise ValueError(f"summary must be a contiguous float64 [{_abi.SUMMARY_DIM}, n] tensor on {self.device}")
+        return int(summary.shape[1])
+
+    @staticmethod
+    def _set_rows(spec, rows, lo, hi):
+        """Overrides spec.rows with `rows`, lo..hi of them (None: the library's default stays)."""
+        if rows is None:
+            return
+        rows = [int(r) for r in rows]
+        if not lo <= len(rows) <= hi:
+            raise ValueError(f"{lo} to {hi} rows" if lo else f"at most {hi} rows")
+        spec.n_rows = len(rows)
+        spec.rows[:len(rows)] = rows
+
     def close(self):
         if getattr(self, "_ctx", None) is not None and self._ctx.value:
             self.lib.erpl_mc_destroy(self._ctx)
@@ -100,29 +138,28 @@ class TrajectoryEngine:
             pass
 
     def set_config(self, cfg):
-        _abi.check(self.lib, self.lib.erpl_mc_set_config(self._ctx, C.byref(cfg)), "erpl_mc_set_config")
+        self._call("erpl_mc_set_config", C.byref(cfg))
         self._cfg = cfg
 
     def set_launch(self, block_threads=256, max_blocks=0, refill_threshold=1):
-        _abi.check(self.lib, self.lib.erpl_mc_set_launch(self._ctx, block_threads, max_blocks, refill_threshold),
-                   "erpl_mc_set_launch")
+        self._call("erpl_mc_set_launch", block_threads, max_blocks, refill_threshold)
 
     def set_waves_per_simd(self, waves):
         """fp32 flight-kernel build: 2 (256 VGPRs), 3 (168 VGPRs, three resident waves), 0 = by batch size."""
-        _abi.check(self.lib, self.lib.erpl_mc_set_waves_per_simd(self._ctx, int(waves)), "erpl_mc_set_waves_per_simd")
+        self._call("erpl_mc_set_waves_per_simd", int(waves))
 
     def set_chunk(self, chunk_steps):
         """Step-chunked launches with per-GPU compaction in between (0 = single launch; < 0 = the library decides
         per batch from the trajectory lengths of the batches it has finished: erpl_mc_set_chunk)."""
-        _abi.check(self.lib, self.lib.erpl_mc_set_chunk(self._ctx, int(chunk_steps)), "erpl_mc_set_chunk")
+        self._call("erpl_mc_set_chunk", int(chunk_steps))
 
     def set_adopt(self, lanes):
         """Lane adoption: waves down to `lanes` flying trajectories hand them to fuller waves (0 = off, < 0 = the
         library decides per batch: erpl_mc_set_adopt)."""
-        _abi.check(self.lib, self.lib.erpl_mc_set_adopt(self._ctx, int(lanes)), "erpl_mc_set_adopt")
+        self._call("erpl_mc_set_adopt", int(lanes))
 
     def reserve(self, n):
-        _abi.check(self.lib, self.lib.erpl_mc_reserve(self._ctx, n), "erpl_mc_reserve")
+        self._call("erpl_mc_reserve", n)
 
     def alloc_outputs(self, n):
         summary = torch.empty((_abi.SUMMARY_DIM, n), dtype=torch.float64, device=self.device)
@@ -132,7 +169,7 @@ class TrajectoryEngine:
     def set_short_flight_overlap(self, depth):
         """How many batches of short flights start side by side (erpl_mc_set_short_flight_overlap; default 4, 0 = no limit
         besides set_overlap).  Scheduling only."""
-        _abi.check(self.lib, self.lib.erpl_mc_set_short_flight_overlap(self._ctx, int(depth)), "erpl_mc_set_short_flight_overlap")
+        self._call("erpl_mc_set_short_flight_overlap", int(depth))
 
     def get_overlap(self):
         """Batches `submit()` keeps in flight at once (3, or 8 when the process has the hardware queues for it)."""
@@ -140,7 +177,7 @@ class TrajectoryEngine:
 
     def set_overlap(self, depth):
         """Batches `submit()` keeps in flight at once (erpl_mc_set_overlap; 1..8)."""
-        _abi.check(self.lib, self.lib.erpl_mc_set_overlap(self._ctx, int(depth)), "erpl_mc_set_overlap")
+        self._call("erpl_mc_set_overlap", int(depth))
 
     def submit(self, db, **kw):
         """Like run(), but on one of the library's internal streams (erpl_mc_submit_batch): the batch
@@ -153,22 +190,21 @@ class TrajectoryEngine:
         """Make `stream` (default: the current torch stream) wait on the device for a submitted batch
         (ticket < 0: for all of them).  The host does not block."""
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _abi.check(self.lib, self.lib.erpl_mc_wait_batch(self._ctx, int(ticket), C.c_void_p(st.cuda_stream)),
-                   "erpl_mc_wait_batch")
+        self._call("erpl_mc_wait_batch", int(ticket), C.c_void_p(st.cuda_stream))
 
     def synchronize(self):
         """Host-blocking wait for everything enqueued; raises _abi.IncompleteBatch if a lane hand-over timed out."""
-        _abi.check(self.lib, self.lib.erpl_mc_synchronize(self._ctx), "erpl_mc_synchronize")
+        self._call("erpl_mc_synchronize")
 
     def check(self, ticket=-1):
         """Where results are consumed: block the host until batch `ticket` (< 0: every submitted batch) has finished
         and raise _abi.IncompleteBatch if one of its lane hand-overs timed out (erpl_mc_check_batch).  wait() only
         orders a stream on the device; it reports batches that had ALREADY finished incomplete when it is called."""
-        _abi.check(self.lib, self.lib.erpl_mc_check_batch(self._ctx, int(ticket)), "erpl_mc_check_batch")
+        self._call("erpl_mc_check_batch", int(ticket))
 
     def set_adopt_spin(self, polls):
         """Test knob (erpl_mc_set_adopt_spin): < 0 makes every adopting lane give up at once."""
-        _abi.check(self.lib, self.lib.erpl_mc_set_adopt_spin(self._ctx, int(polls)), "erpl_mc_set_adopt_spin")
+        self._call("erpl_mc_set_adopt_spin", int(polls))
 
     @staticmethod
     def raise_if_incomplete(status):
@@ -185,15 +221,10 @@ class TrajectoryEngine:
         m = int(x.shape[1])
         rows = {_abi.DBG_ATMOSPHERE: 4, _abi.DBG_AERO: 5, _abi.DBG_RHS: 15}[what]
         out = torch.full((rows, m), float("nan"), dtype=torch.float64, device=self.device)
-        b = _abi.ErplBatch()
-        b.n, b.precision, b.k_wind, b.flags = db.n, db.precision, db.k_wind, 0
-        b.ic, b.rocket, b.motor = db.ic.data_ptr(), db.rocket.data_ptr(), db.motor.data_ptr()
-        b.alt_grid = db.alt_grid.data_ptr() if db.k_wind else None
-        b.wind = db.wind.data_ptr() if db.k_wind else None
+        b = self._batch_struct(db)
         st = torch.cuda.current_stream(self.device)
-        rc = self.lib.erpl_mc_debug_eval(self._ctx, C.byref(b), int(what), m, C.c_void_p(x.data_ptr()),
-                                         C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream))
-        _abi.check(self.lib, rc, "erpl_mc_debug_eval")
+        self._call("erpl_mc_debug_eval", C.byref(b), int(what), m, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()),
+                   C.c_void_p(st.cuda_stream))
         torch.cuda.synchronize(self.device)
         return out.cpu().numpy()
 
@@ -204,11 +235,7 @@ class TrajectoryEngine:
         asynchronous with respect to the host."""
         if summary is None or status is None:
             summary, status = self.alloc_outputs(db.n)
-        b = _abi.ErplBatch()
-        b.n, b.precision, b.k_wind, b.flags = db.n, db.precision, db.k_wind, flags
-        b.ic, b.rocket, b.motor = db.ic.data_ptr(), db.rocket.data_ptr(), db.motor.data_ptr()
-        b.alt_grid = db.alt_grid.data_ptr() if db.k_wind else None
-        b.wind = db.wind.data_ptr() if db.k_wind else None
+        b = self._batch_struct(db, flags)
         o = _abi.ErplOut()
         o.summary, o.status = summary.data_ptr(), status.data_ptr()
         traj = tlen = ids = None
@@ -222,12 +249,10 @@ class TrajectoryEngine:
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         if overlap:
             t = C.c_int64(0)
-            rc = self.lib.erpl_mc_submit_batch(self._ctx, C.byref(b), C.byref(o), C.c_void_p(st.cuda_stream), C.byref(t))
-            _abi.check(self.lib, rc, "erpl_mc_submit_batch")
+            self._call("erpl_mc_submit_batch", C.byref(b), C.byref(o), C.c_void_p(st.cuda_stream), C.byref(t))
             self.last_ticket = t.value
         else:
-            rc = self.lib.erpl_mc_run_batch(self._ctx, C.byref(b), C.byref(o), C.c_void_p(st.cuda_stream))
-            _abi.check(self.lib, rc, "erpl_mc_run_batch")
+            self._call("erpl_mc_run_batch", C.byref(b), C.byref(o), C.c_void_p(st.cuda_stream))
         if traj is not None:
             self._keep = ids
             return summary, status, traj, tlen
@@ -239,23 +264,15 @@ class TrajectoryEngine:
         traj = traj.contiguous()
         m = int(traj.shape[0])
         out = torch.empty((m, _abi.DIAG_DIM), dtype=torch.float64, device=self.device)
-        b = _abi.ErplBatch()
-        b.n, b.precision, b.k_wind, b.flags = db.n, db.precision, db.k_wind, 0
-        b.ic, b.rocket, b.motor = db.ic.data_ptr(), db.rocket.data_ptr(), db.motor.data_ptr()
-        b.alt_grid = db.alt_grid.data_ptr() if db.k_wind else None
-        b.wind = db.wind.data_ptr() if db.k_wind else None
+        b = self._batch_struct(db)
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        rc = self.lib.erpl_mc_extract_histories(self._ctx, C.byref(b), int(sample), C.c_void_p(traj.data_ptr()), m,
-                                                float(time_offset), C.c_void_p(out.data_ptr()),
-                                                C.c_void_p(st.cuda_stream))
-        _abi.check(self.lib, rc, "erpl_mc_extract_histories")
+        self._call("erpl_mc_extract_histories", C.byref(b), int(sample), C.c_void_p(traj.data_ptr()), m,
+                   float(time_offset), C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream))
         return out
 
     def analysis_defaults(self):
         """The reference's outlier bounds, rows and quantiles (erpl_mc_analysis_defaults)."""
-        spec = _abi.ErplAnalysisSpec()
-        _abi.check(self.lib, self.lib.erpl_mc_analysis_defaults(C.byref(spec)), "erpl_mc_analysis_defaults")
-        return spec
+        return self._defaults(_abi.ErplAnalysisSpec, "erpl_mc_analysis_defaults")
 
     def analyze(self, summary, status=None, rows=None, quantiles=None, bounds=None, reasons=False):
         """Outlier filter + exact statistics of a [16, n] summary on the device (erpl_mc_analyze), enqueued on the
@@ -263,20 +280,12 @@ class TrajectoryEngine:
         apogee, range, flight time); quantiles: fractions in [0, 1] (default 5/25/50/75/95 %); bounds: dict overriding
         max_apogee / min_apogee / max_range / max_flight_time / energy_apogee.  Returns (_abi.ErplAnalysis, reason
         bits [n] uint8 on the device or None).  Raises _abi.IncompleteBatch for status words with ST_INCOMPLETE."""
-        if not (summary.is_cuda and summary.device == self.device and summary.dtype == torch.float64
-                and summary.dim() == 2 and summary.shape[0] == _abi.SUMMARY_DIM and summary.is_contiguous()):
-            raise ValueError(f"summary must be a contiguous float64 [{_abi.SUMMARY_DIM}, n] tensor on {self.device}")
-        n = int(summary.shape[1])
+        n = self._check_summary(summary)
         if status is not None and not (status.device == self.device and status.dtype == torch.int32
                                        and tuple(status.shape) == (n,) and status.is_contiguous()):
             raise ValueError(f"status must be a contiguous int32 [n] tensor on {self.device}")
         spec = self.analysis_defaults()
-        if rows is not None:
-            rows = [int(r) for r in rows]
-            if len(rows) > _abi.ANALYSIS_MAX_ROWS:
-                raise ValueError(f"at most {_abi.ANALYSIS_MAX_ROWS} rows")
-            spec.n_rows = len(rows)
-            spec.rows[:len(rows)] = rows
+        self._set_rows(spec, rows, 0, _abi.ANALYSIS_MAX_ROWS)
         if quantiles is not None:
             quantiles = [float(q) for q in quantiles]
             if len(quantiles) > _abi.ANALYSIS_MAX_Q:
@@ -290,19 +299,14 @@ class TrajectoryEngine:
         why = torch.empty((n,), dtype=torch.uint8, device=self.device) if reasons else None
         res = _abi.ErplAnalysis()
         st = torch.cuda.current_stream(self.device)
-        rc = self.lib.erpl_mc_analyze(self._ctx, C.c_void_p(summary.data_ptr()),
-                                      C.c_void_p(status.data_ptr()) if status is not None else None, n, C.byref(spec),
-                                      C.byref(res), C.c_void_p(why.data_ptr()) if reasons else None,
-                                      C.c_void_p(st.cuda_stream))
-        _abi.check(self.lib, rc, "erpl_mc_analyze")
+        self._call("erpl_mc_analyze", C.c_void_p(summary.data_ptr()),
+                   C.c_void_p(status.data_ptr()) if status is not None else None, n, C.byref(spec), C.byref(res),
+                   C.c_void_p(why.data_ptr()) if reasons else None, C.c_void_p(st.cuda_stream))
         return res, why
 
     def _summary_and_mask(self, summary, mask):
         """The host-side refusals of the distribution calls: there is no CPU path behind them."""
-        if not (summary.is_cuda and summary.device == self.device and summary.dtype == torch.float64
-                and summary.dim() == 2 and summary.shape[0] == _abi.SUMMARY_DIM and summary.is_contiguous()):
-            raise ValueError(f"summary must be a contiguous float64 [{_abi.SUMMARY_DIM}, n] tensor on {self.device}")
-        n = int(summary.shape[1])
+        n = self._check_summary(summary)
         if mask is not None and not (mask.device == self.device and mask.dtype == torch.uint8
                                      and tuple(mask.shape) == (n,) and mask.is_contiguous()):
             raise ValueError(f"mask must be a contiguous uint8 [n] tensor on {self.device}")
@@ -324,14 +328,8 @@ class TrajectoryEngine:
         row - equal to np.histogram(finite masked values, bins, range) - and a dict of per-row lists counted / below /
         above / lo / hi."""
         n, mask_p = self._summary_and_mask(summary, mask)
-        spec = _abi.ErplHistSpec()
-        _abi.check(self.lib, self.lib.erpl_mc_histogram_defaults(C.byref(spec)), "erpl_mc_histogram_defaults")
-        if rows is not None:
-            rows = [int(r) for r in rows]
-            if not 1 <= len(rows) <= _abi.HIST_MAX_ROWS:
-                raise ValueError(f"1 to {_abi.HIST_MAX_ROWS} rows")
-            spec.n_rows = len(rows)
-            spec.rows[:len(rows)] = rows
+        spec = self._defaults(_abi.ErplHistSpec, "erpl_mc_histogram_defaults")
+        self._set_rows(spec, rows, 1, _abi.HIST_MAX_ROWS)
         m = spec.n_rows
         bins = [int(bins)] * m if np.isscalar(bins) else [int(b) for b in bins]
         ranges = [None] * m if ranges is None else list(ranges)
@@ -344,10 +342,9 @@ class TrajectoryEngine:
         counts = np.zeros((m, _abi.HIST_MAX_BINS), dtype=np.int64)
         res = _abi.ErplHistResult()
         st = torch.cuda.current_stream(self.device)
-        rc = self.lib.erpl_mc_histogram(self._ctx, C.c_void_p(summary.data_ptr()), mask_p, n, C.byref(spec),
-                                        C.c_void_p(edges.ctypes.data), C.c_void_p(counts.ctypes.data), C.byref(res),
-                                        C.c_void_p(st.cuda_stream))
-        _abi.check(self.lib, rc, "erpl_mc_histogram")
+        self._call("erpl_mc_histogram", C.c_void_p(summary.data_ptr()), mask_p, n, C.byref(spec),
+                   C.c_void_p(edges.ctypes.data), C.c_void_p(counts.ctypes.data), C.byref(res),
+                   C.c_void_p(st.cuda_stream))
         info = {k: list(getattr(res, k)[:m]) for k in ("counted", "below", "above", "lo", "hi")}
         return ([edges[j, :bins[j] + 1].copy() for j in range(m)], [counts[j, :bins[j]].copy() for j in range(m)], info)
 
@@ -365,10 +362,9 @@ class TrajectoryEngine:
         counts = np.zeros(max(1, min(bx, cap)) * max(1, min(by, cap)), dtype=np.int64)   # out-of-range bins are refused below
         res = _abi.ErplHist2dResult()
         st = torch.cuda.current_stream(self.device)
-        rc = self.lib.erpl_mc_histogram_xy(self._ctx, C.c_void_p(summary.data_ptr()), mask_p, n, C.byref(spec),
-                                          C.c_void_p(ex.ctypes.data), C.c_void_p(ey.ctypes.data),
-                                          C.c_void_p(counts.ctypes.data), C.byref(res), C.c_void_p(st.cuda_stream))
-        _abi.check(self.lib, rc, "erpl_mc_histogram_xy")
+        self._call("erpl_mc_histogram_xy", C.c_void_p(summary.data_ptr()), mask_p, n, C.byref(spec),
+                   C.c_void_p(ex.ctypes.data), C.c_void_p(ey.ctypes.data), C.c_void_p(counts.ctypes.data), C.byref(res),
+                   C.c_void_p(st.cuda_stream))
         info = {k: getattr(res, k) for k in ("counted", "outside", "lo_x", "hi_x", "lo_y", "hi_y")}
         return counts.reshape(bx, by), ex[:bx + 1].copy(), ey[:by + 1].copy(), info
 
@@ -386,8 +382,7 @@ class TrajectoryEngine:
             raise ValueError(f"at most {_abi.DISP_MAX_LEVELS} levels")
         if len(quantiles) > _abi.ANALYSIS_MAX_Q:
             raise ValueError(f"at most {_abi.ANALYSIS_MAX_Q} quantiles")
-        spec = _abi.ErplDispersionSpec()
-        _abi.check(self.lib, self.lib.erpl_mc_dispersion_defaults(C.byref(spec)), "erpl_mc_dispersion_defaults")
+        spec = self._defaults(_abi.ErplDispersionSpec, "erpl_mc_dispersion_defaults")
         spec.row_x, spec.row_y = int(row_x), int(row_y)
         if centre is None:
             spec.centre = _abi.CENTRE_MEAN
@@ -400,9 +395,8 @@ class TrajectoryEngine:
         r = torch.empty((n,), dtype=torch.float64, device=self.device) if miss else None
         res = _abi.ErplDispersion()
         st = torch.cuda.current_stream(self.device)
-        rc = self.lib.erpl_mc_dispersion(self._ctx, C.c_void_p(summary.data_ptr()), mask_p, n, C.byref(spec), C.byref(res),
-                                         C.c_void_p(r.data_ptr()) if miss else None, C.c_void_p(st.cuda_stream))
-        _abi.check(self.lib, rc, "erpl_mc_dispersion")
+        self._call("erpl_mc_dispersion", C.c_void_p(summary.data_ptr()), mask_p, n, C.byref(spec), C.byref(res),
+                   C.c_void_p(r.data_ptr()) if miss else None, C.c_void_p(st.cuda_stream))
         nl, nq, m = len(levels), len(quantiles), res.miss
         out = {"count": int(res.count), "rows": (int(row_x), int(row_y)),
                "mean": [res.mean_x, res.mean_y],
@@ -438,14 +432,8 @@ class TrajectoryEngine:
             raise ValueError(f"1 to {_abi.CORR_MAX_FACTORS} factors")
         if want_ranks and not ranks:
             raise ValueError("want_ranks needs ranks=True")
-        spec = _abi.ErplCorrSpec()
-        _abi.check(self.lib, self.lib.erpl_mc_correlation_defaults(C.byref(spec)), "erpl_mc_correlation_defaults")
-        if rows is not None:
-            rows = [int(r) for r in rows]
-            if not 1 <= len(rows) <= _abi.CORR_MAX_ROWS:
-                raise ValueError(f"1 to {_abi.CORR_MAX_ROWS} rows")
-            spec.n_rows = len(rows)
-            spec.rows[:len(rows)] = rows
+        spec = self._defaults(_abi.ErplCorrSpec, "erpl_mc_correlation_defaults")
+        self._set_rows(spec, rows, 1, _abi.CORR_MAX_ROWS)
         spec.n_factors, spec.ranks = F, int(bool(ranks))
         R = spec.n_rows
         V = F + R
@@ -454,11 +442,10 @@ class TrajectoryEngine:
         rk = torch.empty((V, n), dtype=torch.float64, device=self.device) if want_ranks else None
         res = _abi.ErplCorrResult()
         st = torch.cuda.current_stream(self.device)
-        rc = self.lib.erpl_mc_correlation(self._ctx, C.c_void_p(factors.data_ptr()), C.c_void_p(summary.data_ptr()), mask_p,
-                                          n, C.byref(spec), C.byref(res), C.c_void_p(corr.ctypes.data),
-                                          C.c_void_p(rank_corr.ctypes.data) if ranks else None,
-                                          C.c_void_p(rk.data_ptr()) if want_ranks else None, C.c_void_p(st.cuda_stream))
-        _abi.check(self.lib, rc, "erpl_mc_correlation")
+        self._call("erpl_mc_correlation", C.c_void_p(factors.data_ptr()), C.c_void_p(summary.data_ptr()), mask_p, n,
+                   C.byref(spec), C.byref(res), C.c_void_p(corr.ctypes.data),
+                   C.c_void_p(rank_corr.ctypes.data) if ranks else None,
+                   C.c_void_p(rk.data_ptr()) if want_ranks else None, C.c_void_p(st.cuda_stream))
         out = {"n": int(res.n), "count": int(res.count), "n_masked": int(res.n_masked),
                "n_non_finite": int(res.n_non_finite), "rows": list(spec.rows[:R]), "n_factors": F,
                "constant": np.array(res.constant[:V], dtype=np.int32)}
@@ -476,38 +463,36 @@ class TrajectoryEngine:
 
     def set_profiling(self, enable=True):
         """Record HIP events around the two kernels on the launch stream (erpl_mc_set_profiling)."""
-        _abi.check(self.lib, self.lib.erpl_mc_set_profiling(self._ctx, int(bool(enable))), "erpl_mc_set_profiling")
+        self._call("erpl_mc_set_profiling", int(bool(enable)))
 
     def last_kernel_ms(self):
         """(rail_ms, flight_ms) device durations of the last profiled run (synchronises on its end)."""
         a, b = C.c_float(), C.c_float()
-        _abi.check(self.lib, self.lib.erpl_mc_last_kernel_ms(self._ctx, C.byref(a), C.byref(b)),
-                   "erpl_mc_last_kernel_ms")
+        self._call("erpl_mc_last_kernel_ms", C.byref(a), C.byref(b))
         return a.value, b.value
 
     def kernel_ms_history(self, max_runs=_abi.PROFILE_RING):
         """Per-launch (rail_ms[], flight_ms[]) of the most recent profiled runs, oldest first."""
         m = min(int(max_runs), _abi.PROFILE_RING)
         ra, fa, n = (C.c_float * m)(), (C.c_float * m)(), C.c_int(0)
-        _abi.check(self.lib, self.lib.erpl_mc_kernel_ms_history(self._ctx, m, ra, fa, C.byref(n)),
-                   "erpl_mc_kernel_ms_history")
+        self._call("erpl_mc_kernel_ms_history", m, ra, fa, C.byref(n))
         return list(ra[:n.value]), list(fa[:n.value])
 
     def debug_counters(self):
         out = (C.c_double * 16)()
         torch.cuda.synchronize(self.device)
-        _abi.check(self.lib, self.lib.erpl_mc_debug_counters(self._ctx, out), "erpl_mc_debug_counters")
+        self._call("erpl_mc_debug_counters", out)
         return list(out)
 
     def last_stats(self):
         """(physics RK4 steps integrated, wave-iterations) of the last run (synchronises)."""
         a, b = C.c_double(), C.c_double()
         torch.cuda.synchronize(self.device)
-        _abi.check(self.lib, self.lib.erpl_mc_last_stats(self._ctx, C.byref(a), C.byref(b)), "erpl_mc_last_stats")
+        self._call("erpl_mc_last_stats", C.byref(a), C.byref(b))
         return a.value, b.value
 
     def ticket_stats(self, ticket):
         """(physics RK4 steps integrated, wave-iterations) of ONE submitted batch (waits for that batch alone)."""
         a, b = C.c_double(), C.c_double()
-        _abi.check(self.lib, self.lib.erpl_mc_ticket_stats(self._ctx, C.c_int64(ticket), C.byref(a), C.byref(b)), "erpl_mc_ticket_stats")
+        self._call("erpl_mc_ticket_stats", C.c_int64(ticket), C.byref(a), C.byref(b))
         return a.value, b.value

@@ -98,3 +98,33 @@ def rel_err(a, b):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
     return np.abs(a - b) / np.maximum(np.abs(b), 1e-300)
+
+
+def synthetic_summary(n, seed):
+    """A [16, n] float64 summary and an int32 status without any flight behind them, for the tests of the analysis
+    workspace: apogee uniform in 50..90000, range in 0..250000, flight time in 0..700 (about 60 % of the samples pass the
+    reference's outlier filter), impact x / y normal x 1000, three NaN and one inf at fixed places, end codes 0..4."""
+    rng = np.random.default_rng(seed)
+    summ = rng.normal(size=(_abi.SUMMARY_DIM, n))
+    summ[_abi.SUM_APOGEE_ALT] = rng.uniform(50.0, 90000.0, n)
+    summ[_abi.SUM_RANGE] = rng.uniform(0.0, 250000.0, n)
+    summ[_abi.SUM_FLIGHT_TIME] = rng.uniform(0.0, 700.0, n)
+    summ[_abi.SUM_IMPACT_X] = rng.normal(size=n) * 1000.0
+    summ[_abi.SUM_IMPACT_Y] = rng.normal(size=n) * 1000.0
+    summ[_abi.SUM_APOGEE_ALT, 5] = np.nan
+    summ[_abi.SUM_RANGE, n // 2] = np.nan
+    summ[_abi.SUM_IMPACT_X, n - 1] = np.nan
+    summ[_abi.SUM_FLIGHT_TIME, 7] = np.inf
+    status = rng.integers(0, 5, n).astype(np.int32)
+    return summ, status
+
+
+def same_nested(a, b):
+    """Equality of nested dicts / lists / tuples of numbers in which a NaN equals a NaN."""
+    if isinstance(a, dict):
+        return isinstance(b, dict) and a.keys() == b.keys() and all(same_nested(a[k], b[k]) for k in a)
+    if isinstance(a, (list, tuple)):
+        return isinstance(b, (list, tuple)) and len(a) == len(b) and all(same_nested(x, y) for x, y in zip(a, b))
+    if isinstance(a, float) and isinstance(b, float) and np.isnan(a) and np.isnan(b):
+        return True
+    return type(a) is type(b) and a == b

@@ -338,3 +338,19 @@ def test_python_layer_refuses_what_the_kernels_cannot_take(engine):
     out = analysis.native_statistics(ok + 500.0, rows=[_abi.SUM_IMPACT_Y], quantiles=[0.5], engine=engine)
     assert list(out["rows"]) == [_abi.SUM_IMPACT_Y] and out["rows"][_abi.SUM_IMPACT_Y]["percentiles"] == [500.0]
     assert out["apogee_altitude"]["mean"] == 500.0 and out["apogee_altitude"]["std"] == 0.0 and "termination_counts" not in out
+
+
+# ------------------------------------------------------------------ 10: the reason bytes grow with n and never shrink
+def test_workspace_regrow_gives_the_bytes_of_a_fresh_engine(engine):
+    """257 and 4099 samples are 2 and 17 workgroups of ERPL_ANA_BLOCK, one sample past a block boundary: the second call
+    replaces the first one's reason bytes, the third runs in the larger buffer.  The library promises repeatable bytes, so
+    each result equals, bit for bit, what a fresh engine gives for that call alone."""
+    from erpl_monte_carlo_sim_amd.engine import TrajectoryEngine
+    for n in (257, 4099, 257):
+        summ, status = H.synthetic_summary(n, 40 + n)
+        res, why, ds, dt = run(engine, summ, status)
+        assert 0 < res.n_valid < n
+        fresh = TrajectoryEngine(engine.device)
+        ref, ref_why = fresh.analyze(ds, dt, reasons=True)
+        fresh.close()
+        assert bytes(res) == bytes(ref) and torch.equal(why, ref_why), n

@@ -615,3 +615,46 @@ def test_python_layer_refuses_what_the_kernels_cannot_take(engine):
         engine.dispersion(ok, levels=[1.0])
     edges, counts, info = engine.histogram(ok, rows=[5], bins=4)          # a constant row: (-0.5, 0.5), bin 2
     assert list(edges[0]) == [-0.5, -0.25, 0.0, 0.25, 0.5] and list(counts[0]) == [0, 0, 8, 0]
+
+
+# ------------------------------------------------------------------ the workspaces on one engine: regrow and shared use
+def test_workspaces_regrow_and_are_shared_like_on_fresh_engines():
+    """analyze, dispersion and histogram in turn on ONE engine, at 257 and 4099 samples (2 and 17 workgroups of
+    ERPL_ANA_BLOCK, one sample past a block boundary): the reason bytes and the miss-distance row grow between the calls,
+    and dispersion without a mask takes the reason bytes `analyze` has just filled as its row of zeros.  The library
+    promises repeatable bytes, so every result equals what the same single call gives on a fresh engine - no tolerance."""
+    from erpl_monte_carlo_sim_amd.engine import TrajectoryEngine
+    dev = torch.device("cuda", 0)
+    data = {}
+    for n in (257, 4099):
+        summ, status = H.synthetic_summary(n, 40 + n)
+        data[n] = (torch.from_numpy(summ).to(dev), torch.from_numpy(status).to(dev))
+
+    def analyze(eng, n, reasons):
+        res, why = eng.analyze(*data[n], reasons=reasons)
+        assert 0 < res.n_valid < n
+        return bytes(res), None if why is None else why.cpu().numpy()
+
+    def dispersion(eng, n, _):
+        return eng.dispersion(data[n][0], None, miss=False)
+
+    def histogram(eng, n, _):
+        return eng.histogram(data[n][0])
+
+    calls = [(analyze, 257, True), (analyze, 4099, True), (dispersion, 257, None), (dispersion, 4099, None),
+             (histogram, 4099, None), (analyze, 257, False)]
+    one = TrajectoryEngine(dev)
+    got = [fn(one, n, arg) for fn, n, arg in calls]
+    one.close()
+    for (fn, n, arg), g in zip(calls, got):
+        fresh = TrajectoryEngine(dev)
+        ref = fn(fresh, n, arg)
+        fresh.close()
+        if fn is analyze:
+            assert g[0] == ref[0] and (g[1] is None) == (ref[1] is None) and (g[1] is None or np.array_equal(g[1], ref[1])), n
+        elif fn is dispersion:
+            assert g["count"] > 0 and H.same_nested(g, ref), (n, g, ref)
+        else:
+            for j in range(len(DEFAULT_ROWS)):
+                assert np.array_equal(g[0][j], ref[0][j]) and np.array_equal(g[1][j], ref[1][j]), (n, j)
+            assert H.same_nested(g[2], ref[2]), (n, g[2], ref[2])

@@ -97,7 +97,7 @@ def main():
                           "registers": sorted({(r[3], r[4]) for r in fl}), "lds_bytes": sorted({r[5] for r in fl}),
                           "scratch_bytes": sorted({r[6] for r in fl})}
         if sweep:
-            out["legs"][p]["handoff_sweep"] = {"kernel": "erpl_flight_f64 (reference-order kernel; its waves take a whole SIMD and wait for one: the dispatch lasts, the work is two steps per record)",
+            out["legs"][p]["handoff_sweep"] = {"kernel": "erpl_flight_f64 (reference-order kernel, the gate's own one-wave-per-SIMD instantiation, ERPL_SWEEP_MINW = 1: the dispatch lasts longer than the register-capped copy's did, none of it on the critical path; the work is two steps per record)",
                                                "dispatches": len(sweep), "sum_of_dispatch_ms": sum(e - s for s, e, *_ in sweep) / 1e6,
                                                "mean_dispatch_ms": sum(e - s for s, e, *_ in sweep) / 1e6 / len(sweep),
                                                "share_of_flight_dispatch_time": sum(e - s for s, e, *_ in sweep) / tot if tot else None}
