@@ -1,0 +1,181 @@
+// erpl_k_debug.h — kernel 3 (per-step diagnostic histories, gate build only) and the known-answer debug kernel.
+namespace {
+
+#if ERPL_FAITHFUL
+// ------------------------------------------------------------------------------------ kernel 3
+// FlightSimulator._extract_results per-step loop (simulator.py:511-552): one thread per stored
+// record of one trajectory.  a.traj = records [m][15], a.traj_cap = m, a.n_traj = sample index,
+// a.summary = out [m][ERPL_DIAG_DIM].
+__global__ __launch_bounds__(256) void erpl_extract_f64(const ErplKArgs a, const ErplScalars<real> S,
+                                                        const double time_offset) {
+  __shared__ LdsTables L;
+  __shared__ real alt_s[ERPL_MAX_WIND_KNOTS];
+  stage_tables(L, alt_s, a.tables, a.alt_grid, a.k_wind);
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.traj_cap) return;
+  Shared C;
+  C.S = &S; C.L = &L; C.alt = alt_s; C.has_wind = a.k_wind > 0; C.motor_kind = a.motor_kind;
+  const int64_t n = a.n, id = a.n_traj;
+  LaneParams p;
+  p.dry = (real)a.rocket[0 * n + id]; p.prop = (real)a.rocket[1 * n + id];
+  p.thrust = (real)a.motor[0 * n + id]; p.Ae = (real)a.motor[1 * n + id];
+  p.mdot = (real)a.motor[2 * n + id]; p.burn = a.motor[3 * n + id];
+  lane_params_finish(S, p);
+  const double* rec = a.traj + r * ERPL_TRAJ_DIM;
+  const double ts = rec[0] - time_offset;  // rail-shifted time (simulator.py:464, :543)
+  real y[14];
+#pragma unroll
+  for (int c = 0; c < 14; ++c) y[c] = (real)rec[1 + c];
+  double* o = a.summary + r * ERPL_DIAG_DIM;
+  {  // quaternion_to_euler on the stored quaternion (utils.py:139-144 via :46-70)
+    const real w = y[6], x = y[7], yy = y[8], z = y[9];
+    o[0] = atan2(2 * (w * x + yy * z), 1 - 2 * (x * x + yy * yy));
+    const real sinp = 2 * (w * yy - z * x);
+    o[1] = (fabs(sinp) >= 1) ? copysign(1.57079632679489661923, sinp) : asin(sinp);
+    o[2] = atan2(2 * (w * z + x * yy), 1 - 2 * (yy * yy + z * z));
+  }
+  real mass, cg, Ixx, Iyy;
+  mass_props(S, p, y[13], mass, cg, Ixx, Iyy);
+  o[3] = cg; o[4] = mass; o[5] = Ixx; o[6] = Iyy; o[7] = Iyy;
+  real T, P;
+  atmosphere(S, y[2], T, P);
+  const real rho = P / (S.Rg * T);
+  WindCache wc;
+  wc.lo = 1; wc.hi = 0; wc.x0 = 0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { wc.y0[c] = 0; wc.s[c] = 0; }
+  real wv[3];
+  wind_at(C, id, y[2], wc, wv);
+  const real vr0 = y[3] - wv[0], vr1 = y[4] - wv[1], vr2 = y[5] - wv[2];
+  real w = y[6], x = y[7], yy = y[8], z = y[9];
+  {
+    const real nrm = m_sqrt(((w * w + x * x) + yy * yy) + z * z);
+    if (nrm > (real)1e-12) { w = w / nrm; x = x / nrm; yy = yy / nrm; z = z / nrm; }
+    else { w = 1; x = 0; yy = 0; z = 0; }
+  }
+  const real R00 = 1 - 2 * (yy * yy + z * z), R01 = 2 * (x * yy - w * z), R02 = 2 * (x * z + w * yy);
+  const real R10 = 2 * (x * yy + w * z), R11 = 1 - 2 * (x * x + z * z), R12 = 2 * (yy * z - w * x);
+  const real R20 = 2 * (x * z - w * yy), R21 = 2 * (yy * z + w * x), R22 = 1 - 2 * (x * x + yy * yy);
+  const real vb0 = (R00 * vr0 + R10 * vr1) + R20 * vr2;
+  const real vb1 = (R01 * vr0 + R11 * vr1) + R21 * vr2;
+  const real vb2 = (R02 * vr0 + R12 * vr1) + R22 * vr2;
+  const real vn = m_sqrt((vr0 * vr0 + vr1 * vr1) + vr2 * vr2);
+  const real mach = vn / m_sqrt((real)(1.4 * 287.053) * T);
+  const bool a_dead = (m_abs(vb0) < (real)1e-6) && (m_abs(vb2) < (real)1e-6);
+  const real vxz = m_sqrt(vb0 * vb0 + vb2 * vb2);
+  const real alpha = a_dead ? (real)0 : m_atan2(vb2, vb0);
+  const real beta = (vxz < (real)1e-6) ? (real)0 : m_atan2(vb1, vxz);
+  MachCache mc;
+  mach_cache_clear(mc);
+  mach_lookup(C, mach, mc);
+  real cd, cl, cy, cm, cyaw, cp_dyn;
+  aero_coefficients(S, mach_rec_of(C, mc), mach, alpha, beta, cg, y[13] > 0, cd, cl, cy, cm, cyaw, cp_dyn);
+  const real qdyn = ((real)0.5 * rho) * (vn * vn);
+  real thrust = 0;  // motor.get_thrust(time[i], P) (motor.py:54-76 / :152-156)
+  if (!(ts < 0.0 || ts > p.burn)) {
+    if (C.motor_kind == ERPL_MOTOR_SOLID) thrust = solid_curve(C, (real)ts, p.thrust) + p.Ae * ((real)101325.0 - P);
+    else thrust = p.thrust - p.Ae * P;
+  }
+  o[8] = thrust;
+  o[9] = (qdyn * cd) * S.ref_area;
+  o[10] = cd; o[11] = cl; o[12] = cm;
+  o[13] = cp_dyn;
+  o[14] = (cp_dyn - cg) / S.ref_diam;
+  o[15] = alpha; o[16] = beta;
+}
+#endif  // ERPL_FAITHFUL
+
+// ------------------------------------------------------------------------------------ debug kernel
+// Known-answer evaluation on the device (erpl_mc_debug_eval; tests only): ONE function of the hot path
+// per lane, through the very device functions the flight kernel inlines.  Lane j takes the per-sample
+// parameters and wind table of sample j % n; in / out are [rows][m] doubles.
+//   ERPL_DBG_ATMOSPHERE  in: altitude                        out: T, P, rho, g
+//   ERPL_DBG_AERO        in: mach, alpha, beta, pf, power_on out: cd, cl, cy, cm, cyaw
+//   ERPL_DBG_RHS         in: t, y[14], chute                 out: dy[14], chute
+__global__ __launch_bounds__(256) void ERPL_CAT(erpl_debug_, ERPL_SUFFIX)(const ErplKArgs a, const ErplScalars<real> S,
+                                                                         const int what, const int64_t m,
+                                                                         const double* __restrict__ in,
+                                                                         double* __restrict__ out) {
+  __shared__ LdsTables L;
+  __shared__ real alt_s[ERPL_MAX_WIND_KNOTS];
+  stage_tables(L, alt_s, a.tables, a.alt_grid, a.k_wind);
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  Shared C;
+  C.S = &S; C.L = &L; C.alt = alt_s; C.has_wind = a.k_wind > 0; C.motor_kind = a.motor_kind;
+  const int64_t n = a.n, id = j % n;
+  LaneParams p;
+  p.dry = (real)a.rocket[0 * n + id]; p.prop = (real)a.rocket[1 * n + id];
+  p.thrust = (real)a.motor[0 * n + id]; p.Ae = (real)a.motor[1 * n + id];
+  p.mdot = (real)a.motor[2 * n + id]; p.burn = a.motor[3 * n + id];
+  lane_params_finish(S, p);
+  WindCache wc;
+  wc.lo = 1; wc.hi = 0; wc.x0 = 0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { wc.y0[c] = 0; wc.s[c] = 0; }
+  MachCache mc;
+  mach_cache_clear(mc);
+  AtmCache ac;
+  atm_cache_clear(ac);
+#if !ERPL_FAITHFUL
+  LaneRec lr;
+#if ERPL_FAST_F64
+  __shared__ real lane_wind[kLwSlots][kWave];   // launched with 64 threads per workgroup
+  lr.lw = &lane_wind[0][threadIdx.x];
+  lr.put_wind(wc);
+#endif
+#endif
+  if (what == ERPL_DBG_ATMOSPHERE) {
+    const real h = (real)in[j];
+    real T, P, rho, g;
+#if ERPL_FAITHFUL
+    atmosphere(S, h, T, P);
+    rho = m_div(P, S.Rg * T);
+    g = gravity_at(S, h);
+#else
+    real rT;
+    altitude_tables_reload(C, id, h, wc, ac);
+    fast_atmosphere(C, ac, h, T, rT, P);
+    rho = (P * S.inv_Rg) * rT;
+    const real re = (real)6.371e6;
+    const real r = re * m_rcp(re + h);
+    g = S.g0 * (r * r);
+#endif
+    out[0 * m + j] = (double)T; out[1 * m + j] = (double)P; out[2 * m + j] = (double)rho; out[3 * m + j] = (double)g;
+  } else if (what == ERPL_DBG_AERO) {
+    const real mach = (real)in[0 * m + j], alpha = (real)in[1 * m + j], beta = (real)in[2 * m + j];
+    const real pf = (real)in[3 * m + j];
+    mach_lookup(C, mach, mc);
+    real cd, cl, cy, cm, cyaw;
+#if ERPL_FAITHFUL
+    real mass, cg, Ixx, Iyy, cp_dyn;
+    mass_props(S, p, pf, mass, cg, Ixx, Iyy);
+    aero_coefficients(S, mach_rec_of(C, mc), mach, alpha, beta, cg, in[4 * m + j] > 0.0, cd, cl, cy, cm, cyaw, cp_dyn);
+#else
+    const real mp = p.prop * pf;
+    const real cg = (p.dry_cg + mp * S.prop_cg) * m_rcp(p.dry + mp);
+    real cma;
+    fast_aero(S, mach_rec_of(C, mc), mach, mach * mach, alpha, beta, pf, cg, cd, cl, cy, cma);
+    cm = cma * alpha; cyaw = cma * beta;
+#endif
+    out[0 * m + j] = (double)cd; out[1 * m + j] = (double)cl; out[2 * m + j] = (double)cy;
+    out[3 * m + j] = (double)cm; out[4 * m + j] = (double)cyaw;
+  } else {
+    const double t = in[0 * m + j];
+    real y[14], dy[14];
+#pragma unroll
+    for (int c = 0; c < 14; ++c) y[c] = (real)in[(1 + c) * m + j];
+    bool chute = in[15 * m + j] > 0.0;
+    StampSums ss;
+#if ERPL_FAITHFUL
+    rocket_dynamics(C, p, id, wc, mc, ac, chute, t, y, dy, ss);
+#else
+    rocket_dynamics(C, p, id, wc, mc, ac, chute, t, y, dy, ss, lr);
+#endif
+#pragma unroll
+    for (int c = 0; c < 14; ++c) out[c * m + j] = (double)dy[c];
+    out[14 * m + j] = chute ? 1.0 : 0.0;
+  }
+}
+
+}  // namespace

@@ -97,7 +97,7 @@ struct ErplKArgs {
   int64_t res_cap;
   unsigned long long* qcnt;    // [ERPL_MAX_PHASES + 2] records available to phase p (phase 0: n)
   unsigned long long* qhead;   // [ERPL_MAX_PHASES + 2] pop cursor of phase p
-  // Hand-over queue (fp64 throughput build -> reference-order kernel, ERPL_HANDOFF in erpl_kernels.inc): records of
+  // Hand-over queue (fp64 throughput build -> reference-order kernel, note [2] of erpl_k_config.h): records of
   // the lanes that left the RK4 loop at an unphysical speed, same layout and capacity as one resume-queue buffer.
   // The sweep launch of the reference-order kernel pops them as ITS phase 1: res_*[1] = ext_*, qcnt = ext_q
   // (ext_cnt = &ext_q[1]), qhead = ext_q + ERPL_EXT_Q.  NULL / unused in the other builds.
@@ -143,7 +143,7 @@ int erpl_launch_f64f(const ErplKArgs& a, const void* scalars, int block, int max
                     void* tail_stream, void* main_done);
 // The sweep of the fp64 throughput build's hand-over queue by the reference-order flight kernel (no rail launch): `a` is
 // the batch's argument block with the hand-over queue mapped as phase 1 (see ErplKArgs::ext_r).  It runs the gate's own
-// instantiation (one wave per SIMD, all 512 registers, no scratch: ERPL_SWEEP_MINW = 1 in erpl_kernels.inc, where the
+// instantiation (one wave per SIMD, all 512 registers, no scratch: ERPL_SWEEP_MINW = 1 in erpl_k_config.h, where the
 // copy capped at 256 registers that round 4 first shipped is measured against it and dropped).
 int erpl_launch_f64_sweep(const ErplKArgs& a, const void* scalars, int block, int max_blocks, void* stream);
 // known-answer evaluation of one device function per lane (erpl_mc_debug_eval); in / out are [rows][m]

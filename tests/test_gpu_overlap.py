@@ -141,7 +141,7 @@ def run_gpu(engine, cfg, hb, prec, flags=0):
 def test_f64_fast_cfg2_set_r_match_rate(engine, oracle):
     """BASELINE configs[1] (1 k reference-faithful samples) with the fp64 throughput build against the CPU
     oracle: the reference's apogee_altitude (global argmax) within 0.1 %, the first-descent apogee and the end reason
-    on EVERY sample (round 3: 99.7 %; round 4 hands the blow-ups to the reference-order kernel, ERPL_HANDOFF, and
+    on EVERY sample (round 3: 99.7 %; round 4 hands the blow-ups to the reference-order kernel, erpl_k_config.h [2], and
     tests/golden/sensitivity.json shows that a mere change of rounding pattern keeps 4000 / 4000 outcomes)."""
     hb = mc_batch("liquid", 1000)
     cfg = H.make_config("liquid")
@@ -710,7 +710,7 @@ def test_soak_every_overlapped_batch_equals_run_batch():
 def test_f64_fast_capture_continues_across_the_hand_over(engine, oracle):
     """Trajectory capture of DIVERGING samples in the fp64 throughput build: the records of a sample start in the
     throughput kernel and continue - same buffer, same stride phase - in the reference-order kernel the lane is handed
-    to when its speed passes 1e6 m/s (ERPL_HANDOFF).  Every-step capture against the CPU oracle: same number of records,
+    to when its speed passes 1e6 m/s (ERPL_HANDOFF_SPEED).  Every-step capture against the CPU oracle: same number of records,
     exact time stamps, states to 1e-6 up to the blow-up and class-equal (inf / NaN) beyond, identical summaries with
     and without capture."""
     hb = mc_batch("liquid", 48)                       # Set R recipe: every sample diverges (SURVEY fact 5)

@@ -4,10 +4,9 @@ simulator.py:488-490), first-descent apogee and end reason of every kernel build
 reference-order gate kernel (which tracks the CPU oracle / the Python reference on 100 % of the
 cfg-2 set), with the throughput of each build on the same batch.
 
-    python tools/diag_precision.py [--n 131072] [--mixed] [--out gpurun_out/precision.json]
+    python tools/diag_precision.py [--n 131072] [--out FILE]
 
-Builds compared: f64 (gate), f64_fast, f32 and - with --mixed - the experiment library
-liberpl_mc_mixed.so (fp32 RHS, fp64 state and RK4 combination; `make -C .../csrc mixed`).
+Builds compared: f64 (gate), f64_fast, f32.
 """
 import argparse
 import json
@@ -93,7 +92,6 @@ def timed(eng, db, flags, reps, overlap=0):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=131072)
-    ap.add_argument("--mixed", action="store_true")
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "precision.json"))
     ap.add_argument("--skip-set-p", action="store_true")
@@ -101,20 +99,14 @@ def main():
     dev = torch.device("cuda", 0)
     rocket, motor, atm, wm = models.Rocket(), models.LiquidMotor(), models.StandardAtmosphere(), models.WindModel()
     cfg = flatten.config_from_objects(rocket, motor, atm)
-    engines = {"product": TrajectoryEngine(dev)}
-    if args.mixed:
-        engines["mixed"] = TrajectoryEngine(dev, lib_path=os.path.join(ROOT, "erpl_monte_carlo_sim_amd", "csrc", "liberpl_mc_mixed.so"))
-    for e in engines.values():
-        e.set_config(cfg)
-    builds = [("f64", "product", _abi.PREC_F64), ("f64_fast", "product", _abi.PREC_F64_FAST), ("f32", "product", _abi.PREC_F32)]
-    if args.mixed:
-        builds.append(("mixed_f32rhs_f64state", "mixed", _abi.PREC_F32))
+    eng = TrajectoryEngine(dev)
+    eng.set_config(cfg)
+    builds = [("f64", _abi.PREC_F64), ("f64_fast", _abi.PREC_F64_FAST), ("f32", _abi.PREC_F32)]
     report = {}
 
     def run_all(tag, make_db, flags=0, time_reps=args.reps, overlaps=(0, 2, 3, 4)):
         res, rows = {}, {}
-        for name, ek, prec in builds:
-            eng = engines[ek]
+        for name, prec in builds:
             db = make_db(prec)
             s, t = eng.run(db, flags=flags)
             torch.cuda.synchronize()
@@ -129,7 +121,7 @@ def main():
                 row["traj_per_s" + (f"_overlap{ov}" if ov else "")] = db.n / ms * 1e3
             rows[name] = row
             print(tag, name, json.dumps(row), flush=True)
-        for name, _, _ in builds[1:]:
+        for name, _ in builds[1:]:
             rows[name]["vs_f64_gate"] = compare(res["f64"], res[name])
             print(tag, name, json.dumps(rows[name]["vs_f64_gate"]), flush=True)
         report[tag] = rows
