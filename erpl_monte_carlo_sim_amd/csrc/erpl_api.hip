@@ -206,8 +206,10 @@ static int hw_queues_env() {
 
 namespace {
 
-// Lane adoption can come on for this context: the second workspace and the sweep stream of a lane exist only then.
-bool may_adopt(const erpl_ctx* c) { return c->adopt > 0 || (c->adopt < 0 && hw_queues_env() >= 2 * c->depth + 2); }
+// The lanes of this context run their sweeps on a second stream (with a second workspace): lane adoption can come on and
+// the process has a hardware queue for every stream - two per lane, the caller's and one more of its own.  Without the
+// queues a lane keeps to its one stream and one workspace, with or without lane adoption (enqueue_batch).
+bool has_sweep_streams(const erpl_ctx* c) { return c->adopt != 0 && hw_queues_env() >= 2 * c->depth + 2; }
 
 void slot_free_workspace(ErplSlot& s) {
   for (int k = 0; k < 2; ++k) {
@@ -378,20 +380,30 @@ int enqueue_batch(erpl_ctx* c, int lane, const erpl_batch* b, const erpl_out* o,
   }
   // Lane adoption (erpl_mc_set_adopt): two sweep launches behind the main one fly out what no running wave
   // adopted - the first parks its own thin waves once more, the last one never parks.
-  // Automatic (erpl_mc_set_adopt < 0, the default): every batch handed over with erpl_mc_submit_batch while the lanes
-  // have hardware queues of their own (two streams each: 2 x depth + 2 with the caller's).  The sweeps run on the
-  // lane's second stream, so the next batch of the lane follows the main launch at once and the few long
-  // trajectories of a batch finish beside it (131 072 samples, fp32: 32.4 -> 20.8 ms one deep, 16.5 -> 10.8 two
-  // deep, 11.3 -> 9.0 three deep, 10.6 -> 9.0 eight deep; fp64 throughput build 44.7 -> 38.1 three deep, 37.7 ->
-  // 35.9 eight deep; the gate kernel 129 -> 116 three deep).  Without the queues the second stream of a lane
-  // lands on another lane's queue and the hand-overs cost more than they save (four queues, three deep: 11.4 ->
-  // 25.5 ms): off.  erpl_mc_run_batch runs on the caller's one stream, where a batch is bound by its own longest
+  // Automatic (erpl_mc_set_adopt < 0, the default), for batches handed over with erpl_mc_submit_batch:
+  // - The lanes have hardware queues of their own (two streams each: 2 x depth + 2 with the caller's).  The sweeps run
+  //   on the lane's second stream, so the next batch of the lane follows the main launch at once and the few long
+  //   trajectories of a batch finish beside it (131 072 samples, fp32: 32.4 -> 20.8 ms one deep, 16.5 -> 10.8 two
+  //   deep, 11.3 -> 9.0 three deep, 10.6 -> 9.0 eight deep; fp64 throughput build 44.7 -> 38.1 three deep, 37.7 ->
+  //   35.9 eight deep; the gate kernel 129 -> 116 three deep).
+  // - Fewer queues than that (the HIP default of four: the caller's stream + three lanes).  A second stream per lane
+  //   would land on another lane's queue, where the hand-overs cost more than they save (four queues, three deep:
+  //   11.4 -> 25.5 ms), so none is created: the sweeps of the fp64 throughput build follow the main launch on the
+  //   lane's own stream, with two or more batches in flight to fill the SIMDs beside them (bench shard, f64_fast,
+  //   three deep: 30.3 -> 28.2 ms per pass, lane utilisation 0.75 -> 0.98; with the capped hand-over sweep below
+  //   26.5).
+  // erpl_mc_run_batch runs on the caller's one stream with nothing beside it, where a batch is bound by its own longest
   // trajectory and the hand-overs only lengthen that (32.5 -> 36.1 ms): off.  Step chunks already re-pack every
   // lane, and chunk-parked records would be adopted straight back (measured 8x slower): exclusive.
   int adopt = c->adopt;
   // (limit: fp32 12 / 16 / 24 / 32 / 48 -> 9.30 / 9.05 / 9.00 / 8.93 / 8.97 ms; the one-wave-per-SIMD fp64 builds like it
   // higher - 24 / 40 / 48 / 56 -> 35.7 / 34.8 / 35.3 / 35.3 ms eight deep, 40.3 / 38.4 / 38.2 / 40.9 three deep)
-  if (adopt < 0) adopt = (sweep && hw_queues_env() >= 2 * in_flight + 2) ? (b->precision == ERPL_PREC_F32 ? 24 : 40) : 0;
+  if (adopt < 0) {
+    if (sweep) adopt = (hw_queues_env() >= 2 * in_flight + 2) ? (b->precision == ERPL_PREC_F32 ? 24 : 40) : 0;
+    // (one stream per lane: measured for the fp64 throughput build only, with the limit of the sweep-stream case; the
+    // fp32 build and the gate stay as they were until they are measured there too)
+    else adopt = (ticket > 0 && in_flight >= 2 && b->precision == ERPL_PREC_F64_FAST) ? 40 : 0;
+  }
   a.adopt_lanes = (o->n_traj == 0 && a.chunk_steps == 0) ? adopt : 0;
   a.adopt_spin = c->adopt_spin;
   if (a.adopt_lanes > 0 && n_phases < 3) n_phases = 3;
@@ -399,10 +411,16 @@ int enqueue_batch(erpl_ctx* c, int lane, const erpl_batch* b, const erpl_out* o,
   // with lane adoption the launches behind the main one hold the batch's few longest trajectories: they go to the
   // lane's sweep stream, and the lane's next batch (other set) follows the main launch at once
   hipStream_t tail = (sweep && a.adopt_lanes > 0) ? sweep : nullptr;
+  // the hand-over sweep of the fp64 throughput build: where it runs on the stream that also carries the lane's next
+  // batch (a submitted batch without a sweep stream, other batches filling the SIMDs meanwhile) the instantiation whose
+  // waves start beside the throughput kernel's; on a stream of its own, in erpl_mc_run_batch and for trajectory capture
+  // the gate's own (note [3] of erpl_k_config.h)
+  // (not with step chunks: long flights were not measured in this mode and keep the launch sequence they had)
+  const int sweep_waves = (ticket > 0 && !sweep && in_flight >= 2 && o->n_traj == 0 && a.chunk_steps == 0) ? 2 : 1;
   int lrc;
-  if (b->precision == ERPL_PREC_F64) lrc = erpl_launch_f64(a, &T.s64, c->block, max_blocks, n_phases, st, ev, tail, s.main_done);
-  else if (b->precision == ERPL_PREC_F64_FAST) lrc = erpl_launch_f64f(a, &T.s64, c->block, max_blocks, n_phases, st, ev, tail, s.main_done);
-  else lrc = erpl_launch_f32(a, &T.s32, c->block, max_blocks, n_phases, st, ev, tail, s.main_done);
+  if (b->precision == ERPL_PREC_F64) lrc = erpl_launch_f64(a, &T.s64, c->block, max_blocks, n_phases, st, ev, tail, s.main_done, sweep_waves);
+  else if (b->precision == ERPL_PREC_F64_FAST) lrc = erpl_launch_f64f(a, &T.s64, c->block, max_blocks, n_phases, st, ev, tail, s.main_done, sweep_waves);
+  else lrc = erpl_launch_f32(a, &T.s32, c->block, max_blocks, n_phases, st, ev, tail, s.main_done, sweep_waves);
   if (c->profiling && lrc == 0) c->profiled_runs++;
   KERNEL_TRY(lrc);
   hipStream_t last = tail ? tail : st;
@@ -414,6 +432,7 @@ int enqueue_batch(erpl_ctx* c, int lane, const erpl_batch* b, const erpl_out* o,
   s.latest_is_run = ticket <= 0;
   if (ticket > 0) s.ticket = ticket;   // (an erpl_mc_run_batch on this set leaves the ticket: its `done` is later and covers it)
   s.last_n = b->n;
+  s.last_adopt = a.adopt_lanes; s.last_sweep_waves = (b->precision == ERPL_PREC_F64_FAST) ? sweep_waves : 0; s.last_tail = tail != nullptr;
   s.seq = ++c->batches;
   c->last_slot = si;
   c->lane_uses[lane]++;
@@ -506,9 +525,9 @@ int erpl_mc_reserve(erpl_ctx* c, int64_t n) {
   // both workspaces of every lane in use now (erpl_mc_run_batch on lane 0 stays allocation-free, hence
   // graph-capturable, and no erpl_mc_submit_batch allocates in the middle of a run); lanes beyond the current depth
   // that have been used before grow too, fresh ones take the size on first use
-  // (the second workspace of a lane is only ever used with lane adoption on: without it, it is not allocated -
-  // a workspace costs 448 bytes per sample)
-  const bool adopt = may_adopt(c);
+  // (the second workspace of a lane is only ever used beside a sweep stream: without one the lane's next batch starts
+  // behind the sweeps anyway, and it is not allocated - a workspace costs 448 bytes per sample)
+  const bool adopt = has_sweep_streams(c);
   for (int i = 0; i < 2 * ERPL_MAX_OVERLAP; ++i) {
     if (i % ERPL_MAX_OVERLAP >= c->depth && !c->slot[i].d_queue) continue;
     if (i >= ERPL_MAX_OVERLAP && !adopt && !c->slot[i].d_queue) continue;
@@ -593,9 +612,9 @@ int erpl_mc_submit_batch(erpl_ctx* c, const erpl_batch* b, const erpl_out* o, vo
   }
   const int lane = (int)(c->submitted % depth);
   if (!c->lane_stream[lane]) HIP_TRY(hipStreamCreateWithFlags(&c->lane_stream[lane], hipStreamNonBlocking));
-  // the sweep stream only where lane adoption can come on: a stream takes a hardware queue, and with the HIP default
-  // of four a second one per lane would push the main streams onto shared queues
-  const bool adopt = may_adopt(c);
+  // the sweep stream only where the process has a hardware queue for it: with the HIP default of four (the caller's
+  // stream + three lanes) a second one per lane would push the main streams onto shared queues
+  const bool adopt = has_sweep_streams(c);
   if (adopt && !c->lane_sweep[lane]) HIP_TRY(hipStreamCreateWithFlags(&c->lane_sweep[lane], hipStreamNonBlocking));
   if (!c->lane_in_ready[lane]) HIP_TRY(hipEventCreateWithFlags(&c->lane_in_ready[lane], hipEventDisableTiming));
   // inputs written on the caller's stream so far are visible to the batch
@@ -778,6 +797,12 @@ int erpl_mc_debug_counters(erpl_ctx* c, double* out16) {
   unsigned long long h[16];
   ERPL_TRY(fetch_last_counters(c, h, 16));
   for (int i = 0; i < 16; ++i) out16[i] = (double)h[i];
+  // host side, in the words no kernel counts in: what the library sized itself for and how it scheduled that batch
+  const ErplSlot& ls = c->slot[c->last_slot];
+  int streams = 0;
+  for (int i = 0; i < ERPL_MAX_OVERLAP; ++i) streams += (c->lane_stream[i] != nullptr) + (c->lane_sweep[i] != nullptr);
+  out16[4] = (double)hw_queues_env(); out16[5] = (double)streams;
+  out16[6] = (double)ls.last_adopt; out16[7] = (double)(ls.last_sweep_waves + (ls.last_tail ? 16 : 0));
   return ERPL_OK;
 }
 

@@ -69,6 +69,8 @@ struct ErplSlot {
                                             // or the ticket record of the batch (erpl_mc_submit_batch)
   bool latest_is_run = false;               // the slot's latest batch came through erpl_mc_run_batch (no ticket record)
   int64_t last_n = 0, seq = 0;              // its size and its position in the order of all batches of the context
+  int last_adopt = 0, last_sweep_waves = 0; // how it was scheduled: adoption limit of its main launch, instantiation of its
+  bool last_tail = false;                   //   hand-over sweep, sweeps on the lane's second stream (erpl_mc_debug_counters)
 };
 
 struct erpl_ctx {
@@ -83,6 +85,8 @@ struct erpl_ctx {
   // the lane's NEXT batch - on the other set - starts when the main launch is over and overlaps the sweeps:
   // batches of equal length submitted together run in step, and without this the tails of a whole round of
   // them met on an otherwise empty GPU before the next round could start.
+  // Sweep streams and second sets exist only where the process has a hardware queue per stream (has_sweep_streams in
+  // erpl_api.hip); with fewer, the sweeps stay on the lane's main stream and the lane on its first set.
   ErplSlot slot[2 * ERPL_MAX_OVERLAP];
   hipStream_t lane_stream[ERPL_MAX_OVERLAP] = {};
   hipStream_t lane_sweep[ERPL_MAX_OVERLAP] = {};

@@ -54,12 +54,17 @@
 //     intermediate of ONE step comes near the overflow threshold (worst case ~1e180), and from above
 //     it a diverging sample has two steps left on average, 31 at most (profiles/r4_blowup_sizing.json: 99.8 % of the bench
 //     shard's samples pass it, 0.07 % of all steps are made beyond it).  No flight the model is valid for comes near it.
-// [3] Which instantiation flies the handed-over lanes (ERPL_SWEEP_MINW): 1 = the gate's own (one wave per SIMD, all 512
-//     registers, no scratch), 2 = a copy capped at 256 registers whose waves fit beside the throughput kernel's (612-772
-//     bytes of scratch per lane, saved and restored around every exit of its RK4 loop).  Round 4 first shipped 2 on the
-//     idea that a 512-register wave would wait for an empty SIMD; measured side by side it does not cost a thing (22.41 /
-//     23.30 ms per pass with 2, 22.81 / 22.68 with 1) and the capped copy wrote 258 MB and fetched 226 MB per pass where
-//     this one writes 48 and fetches 103.
+// [3] Which instantiation flies the handed-over lanes - both are compiled, the launcher's `waves` argument picks one per
+//     sweep (erpl_launch_f64_sweep): 1 = the gate's own (one wave per SIMD, all 512 registers, no scratch), 2 = a copy
+//     capped at 256 registers (ERPL_SWEEP_CAPPED_WAVES) whose waves fit beside the throughput kernel's (612-772 bytes of
+//     scratch per lane, saved and restored around every exit of its RK4 loop).  A 512-register wave starts only on a SIMD
+//     with no other wave on it, so its dispatch lasts until SIMDs have emptied (29 ms for 2 ms of work with eight batches
+//     in flight).  On a stream of its own - the lane's sweep stream, with a hardware queue per stream - that wait costs
+//     nothing (22.41 / 23.30 ms per pass with 2, 22.81 / 22.68 with 1) and the capped copy wrote 258 MB and fetched 226 MB
+//     per pass where the gate's own writes 48 and fetches 103: there, in erpl_mc_run_batch, in the gate build and for
+//     trajectory capture the gate's own runs.  Where the sweep shares its stream with the lane's next batch (submitted
+//     batches without a sweep stream: the HIP default of four hardware queues) the wait would hold that batch back
+//     while the other lanes keep every SIMD full: there the capped copy runs.  Same source, same flags, same bits.
 // [4] The register-capped fp32 build keeps the lane's clock (a double) in LDS through the RK4 loop: the compiler
 //     spilled exactly that pair to scratch and re-read it at every stage, and a scratch load is a vector-memory
 //     load - it shares the in-order counter with the table reloads, so every stage start waited for whatever
@@ -122,8 +127,8 @@ typedef float real;
 #ifndef ERPL_DENSE_WAVES
 #define ERPL_DENSE_WAVES 3
 #endif
-#ifndef ERPL_SWEEP_MINW
-#define ERPL_SWEEP_MINW 1   // [3]
+#ifndef ERPL_SWEEP_CAPPED_WAVES
+#define ERPL_SWEEP_CAPPED_WAVES 2   // [3]
 #endif
 // One wave per workgroup for the rail kernel too: with several batches in flight every SIMD is full of flight
 // waves, and a 256-thread workgroup only starts once FOUR wave slots of one CU are free together, while the batch's

@@ -91,7 +91,7 @@ template <typename T> __device__ __forceinline__ bool m_finite(T x) { return (x 
 // SPEC >= 0 compiles the two launch-constant switches of the RHS in: bit 0 = a wind table is present,
 // bit 1 = solid motor (thrust curve); SPEC < 0 reads them at run time (trajectory-capture build).
 // MINW = waves per SIMD the register allocator must leave room for (ERPL_FLIGHT_MIN_WAVES, ERPL_DENSE_WAVES,
-// ERPL_SWEEP_MINW in erpl_k_config.h).
+// ERPL_SWEEP_CAPPED_WAVES in erpl_k_config.h).
 #if ERPL_FAST_F64
 constexpr int kFlightBlock = kWave;   // per-lane LDS arrays of one wave: always 64-thread workgroups
 #else

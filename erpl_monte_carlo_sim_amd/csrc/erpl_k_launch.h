@@ -16,7 +16,7 @@
   } while (0)
 
 int ERPL_LAUNCH_NAME(const ErplKArgs& a0, const void* scalars, int block, int max_blocks, int n_phases,
-                     void* stream, void** ev, void* tail_stream, void* main_done) {
+                     void* stream, void** ev, void* tail_stream, void* main_done, int sweep_waves) {
   hipStream_t st = (hipStream_t)stream;
   if (a0.n <= 0) return 0;
   ErplKArgs a = a0;
@@ -60,7 +60,7 @@ int ERPL_LAUNCH_NAME(const ErplKArgs& a0, const void* scalars, int block, int ma
     g.res_r[1] = a0.ext_r; g.res_d[1] = a0.ext_d; g.res_i[1] = a0.ext_i;
     g.qcnt = a0.ext_q; g.qhead = a0.ext_q + ERPL_EXT_Q;
     g.phase = 1; g.chunk_steps = 0; g.adopt_lanes = 0;
-    const int rc = erpl_launch_f64_sweep(g, scalars, kWave, max_blocks, (void*)st);
+    const int rc = erpl_launch_f64_sweep(g, scalars, kWave, max_blocks, (void*)st, sweep_waves);
     if (rc != 0) return rc;
   }
 #endif
@@ -70,8 +70,9 @@ int ERPL_LAUNCH_NAME(const ErplKArgs& a0, const void* scalars, int block, int ma
 }
 
 #if ERPL_FAITHFUL
-// erpl_launch_f64_sweep (erpl_tables.h): the flight kernel alone (ERPL_SWEEP_MINW picks the instantiation), on the queue `a` maps
-int erpl_launch_f64_sweep(const ErplKArgs& a, const void* scalars, int block, int max_blocks, void* stream) {
+// erpl_launch_f64_sweep (erpl_tables.h): the flight kernel alone, on the queue `a` maps.  waves = 2 picks the instantiation
+// capped at 256 registers (note [3] of erpl_k_config.h); trajectory capture always runs the gate's own.
+int erpl_launch_f64_sweep(const ErplKArgs& a, const void* scalars, int block, int max_blocks, void* stream, int waves) {
   if (a.n <= 0) return 0;
   const ErplScalars<real> S = *(const ErplScalars<real>*)scalars;
   int64_t grid = (a.n + block - 1) / block;
@@ -79,8 +80,9 @@ int erpl_launch_f64_sweep(const ErplKArgs& a, const void* scalars, int block, in
   const dim3 g((unsigned)grid), b(block);
   hipStream_t st = (hipStream_t)stream;
   const size_t dyn_lds = 0;
-  if (a.n_traj > 0) ERPL_LAUNCH_FLIGHT(true, -1, ERPL_SWEEP_MINW);
-  else ERPL_LAUNCH_FLIGHT_SPEC(ERPL_SWEEP_MINW);
+  if (a.n_traj > 0) ERPL_LAUNCH_FLIGHT(true, -1, ERPL_FLIGHT_MIN_WAVES);
+  else if (waves >= ERPL_SWEEP_CAPPED_WAVES) ERPL_LAUNCH_FLIGHT_SPEC(ERPL_SWEEP_CAPPED_WAVES);
+  else ERPL_LAUNCH_FLIGHT_SPEC(ERPL_FLIGHT_MIN_WAVES);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }

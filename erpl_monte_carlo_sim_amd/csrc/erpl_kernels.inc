@@ -1,6 +1,8 @@
 // erpl_kernels.inc — the trajectory kernels, written once and compiled three times:
 //   erpl_k64.hip  : ERPL_FAITHFUL = 1, real = double, -ffp-contract=off  (correctness gate, cfg 2; one wave per SIMD; the
-//                   same instantiation finishes the blow-ups the fp64 throughput build hands over: ERPL_SWEEP_MINW)
+//                   same instantiation finishes the blow-ups the fp64 throughput build hands over, except where the
+//                   sweep shares a stream with the lane's next batch: there a copy capped at 256 registers, two waves
+//                   per SIMD, does - note [3] of erpl_k_config.h)
 //   erpl_k64f.hip : ERPL_FAST_F64 = 1, real = double                     (fp64 throughput: the headline build)
 //   erpl_k32.hip  : ERPL_FAST_F32 = 1, real = float                      (fp32 throughput: healthy flights / first apogee)
 //

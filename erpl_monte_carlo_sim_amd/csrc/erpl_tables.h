@@ -135,17 +135,19 @@ extern "C++" {
 // n_phases flight launches follow the rail launch (1 when a.chunk_steps <= 0).
 // tail_stream (or NULL): the launches behind the first go to that stream, after main_done (a hipEvent_t recorded on
 // `stream` behind the first launch).
+// sweep_waves: erpl_launch_f64f passes it on to erpl_launch_f64_sweep; the other two ignore it.
 int erpl_launch_f64(const ErplKArgs& a, const void* scalars, int block, int max_blocks, int n_phases, void* stream, void** ev,
-                    void* tail_stream, void* main_done);
+                    void* tail_stream, void* main_done, int sweep_waves);
 int erpl_launch_f32(const ErplKArgs& a, const void* scalars, int block, int max_blocks, int n_phases, void* stream, void** ev,
-                    void* tail_stream, void* main_done);
+                    void* tail_stream, void* main_done, int sweep_waves);
 int erpl_launch_f64f(const ErplKArgs& a, const void* scalars, int block, int max_blocks, int n_phases, void* stream, void** ev,
-                    void* tail_stream, void* main_done);
+                    void* tail_stream, void* main_done, int sweep_waves);
 // The sweep of the fp64 throughput build's hand-over queue by the reference-order flight kernel (no rail launch): `a` is
-// the batch's argument block with the hand-over queue mapped as phase 1 (see ErplKArgs::ext_r).  It runs the gate's own
-// instantiation (one wave per SIMD, all 512 registers, no scratch: ERPL_SWEEP_MINW = 1 in erpl_k_config.h, where the
-// copy capped at 256 registers that round 4 first shipped is measured against it and dropped).
-int erpl_launch_f64_sweep(const ErplKArgs& a, const void* scalars, int block, int max_blocks, void* stream);
+// the batch's argument block with the hand-over queue mapped as phase 1 (see ErplKArgs::ext_r).  waves = 1 runs the gate's
+// own instantiation (one wave per SIMD, all 512 registers, no scratch): sweeps on a stream of their own,
+// erpl_mc_run_batch, trajectory capture.  waves = 2 runs the copy capped at 256 registers, whose waves start beside the
+// throughput kernel's: sweeps on the stream that carries the lane's next batch (note [3] of erpl_k_config.h).
+int erpl_launch_f64_sweep(const ErplKArgs& a, const void* scalars, int block, int max_blocks, void* stream, int waves);
 // known-answer evaluation of one device function per lane (erpl_mc_debug_eval); in / out are [rows][m]
 int erpl_launch_debug_f64(const ErplKArgs& a, const void* scalars, int what, int64_t m, const double* in, double* out, void* stream);
 int erpl_launch_debug_f32(const ErplKArgs& a, const void* scalars, int what, int64_t m, const double* in, double* out, void* stream);

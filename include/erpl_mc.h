@@ -578,8 +578,12 @@ enum { ERPL_DBG_ATMOSPHERE = 0, ERPL_DBG_AERO = 1, ERPL_DBG_RHS = 2 };
 int erpl_mc_debug_eval(erpl_ctx* ctx, const erpl_batch* batch, int what, int64_t m, const double* in, double* out,
                        void* hip_stream);
 
-/* Raw device counters of the last run_batch (16 doubles): [0] queue head, [1] RK4 steps, [2] wave
- * iterations, [8..15] per-segment s_memtime sums of a -DERPL_STAMPS=1 diagnostic build (0 otherwise). */
+/* Raw device counters of the last batch (16 doubles): [0] queue head, [1] RK4 steps, [2] wave
+ * iterations, [3] records lost to a hand-over time-out, [8..15] per-segment s_memtime sums of a -DERPL_STAMPS=1
+ * diagnostic build (0 otherwise).  [4..7] come from the host: [4] the hardware queues the library sized itself for
+ * (GPU_MAX_HW_QUEUES as it read it, 4 when unset), [5] the streams it has created, [6] the lane-adoption limit of that
+ * batch's main launch (0 = off), [7] the hand-over sweep of an ERPL_PREC_F64_FAST batch: 1 = the 512-register
+ * instantiation, 2 = the one capped at 256 registers, + 16 when the sweeps ran on the lane's second stream. */
 int erpl_mc_debug_counters(erpl_ctx* ctx, double* out16);
 
 /* Kernel timing with HIP events recorded on the SAME stream as the kernels (enable before

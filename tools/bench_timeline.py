@@ -52,7 +52,7 @@ def main():
         if k in line and k != line["dtype"]:
             legs.append((k, line[k]["ms_per_step"]))
     suffix = {"f32": "f32", "f64_fast": "f64f", "f64": "f64"}
-    out = {"command": "GPU_MAX_HW_QUEUES=24 rocprofv3 --kernel-trace -- python3 bench.py --gpus 1 --steps %d --warmup %d" % (K, W),
+    out = {"command": "GPU_MAX_HW_QUEUES=%s rocprofv3 --kernel-trace -- python3 bench.py --gpus 1 --steps %d --warmup %d" % (line.get("config", {}).get("hw_queues", 24), K, W),
            "note": "union = total time during which at least one erpl_flight dispatch of the leg's timed passes is running; "
                    "bench_ms_per_step is what the same (profiled) run printed; registers = (VGPR_Count, Accum_VGPR_Count) as "
                    "rocprofv3 reports them for a wave64 kernel: half of the per-lane counts of profiles/r4_kernel_resource_usage.txt "
@@ -97,7 +97,11 @@ def main():
                           "registers": sorted({(r[3], r[4]) for r in fl}), "lds_bytes": sorted({r[5] for r in fl}),
                           "scratch_bytes": sorted({r[6] for r in fl})}
         if sweep:
-            out["legs"][p]["handoff_sweep"] = {"kernel": "erpl_flight_f64 (reference-order kernel, the gate's own one-wave-per-SIMD instantiation, ERPL_SWEEP_MINW = 1: the dispatch lasts longer than the register-capped copy's did, none of it on the critical path; the work is two steps per record)",
+            out["legs"][p]["handoff_sweep"] = {"kernel": "erpl_flight_f64 (reference-order kernel; `registers` tells the instantiation: about 240 = the gate's own, "
+                                                         "one wave per SIMD, whose dispatch lasts until SIMDs have emptied - none of it on the critical path on a stream of "
+                                                         "its own; 128 = the copy capped at 256 registers that runs where the sweep shares the lane's one stream, note [3] "
+                                                         "of erpl_k_config.h; the work is two steps per record)",
+                                               "registers": sorted({(r[3], r[4]) for r in sweep}), "scratch_bytes": sorted({r[6] for r in sweep}),
                                                "dispatches": len(sweep), "sum_of_dispatch_ms": sum(e - s for s, e, *_ in sweep) / 1e6,
                                                "mean_dispatch_ms": sum(e - s for s, e, *_ in sweep) / 1e6 / len(sweep),
                                                "share_of_flight_dispatch_time": sum(e - s for s, e, *_ in sweep) / tot if tot else None}
