@@ -775,7 +775,7 @@ int erpl_mc_extract_histories(erpl_ctx* c, const erpl_batch* b, int64_t sample, 
 int erpl_mc_debug_eval(erpl_ctx* c, const erpl_batch* b, int what, int64_t m, const double* in, double* out, void* stream) {
   if (!c || !b || !in || !out) return erpl_fail(ERPL_ERR_INVALID, "NULL argument");
   if (!c->has_cfg) return erpl_fail(ERPL_ERR_CONFIG, "erpl_mc_set_config has not been called");
-  if (what != ERPL_DBG_ATMOSPHERE && what != ERPL_DBG_AERO && what != ERPL_DBG_RHS) return erpl_fail(ERPL_ERR_INVALID, "unknown function %d", what);
+  if (what < ERPL_DBG_ATMOSPHERE || what > ERPL_DBG_RHS_SEQ) return erpl_fail(ERPL_ERR_INVALID, "unknown function %d", what);
   if (b->n < 1 || m < 0 || !b->rocket || !b->motor) return erpl_fail(ERPL_ERR_INVALID, "need at least one sample with parameters");
   if (!check_wind_args(b)) return erpl_fail(ERPL_ERR_INVALID, "bad wind arguments");
   if (m == 0) return ERPL_OK;

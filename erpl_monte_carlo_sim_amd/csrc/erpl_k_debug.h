@@ -92,6 +92,18 @@ __global__ __launch_bounds__(256) void erpl_extract_f64(const ErplKArgs a, const
 //   ERPL_DBG_ATMOSPHERE  in: altitude                        out: T, P, rho, g
 //   ERPL_DBG_AERO        in: mach, alpha, beta, pf, power_on out: cd, cl, cy, cm, cyaw
 //   ERPL_DBG_RHS         in: t, y[14], chute                 out: dy[14], chute
+//   ERPL_DBG_RHS_SEQ     as ERPL_DBG_RHS, but n lanes (one per sample): lane id evaluates the columns id, id + n,
+//                        id + 2n, ... < m in that order through ONE set of wind / Mach / atmosphere caches (and LDS wind
+//                        record) that is cleared before the first column only; the parachute latch comes from each
+//                        column's input, so the expected values are those of ERPL_DBG_RHS
+//   ERPL_DBG_MATH        in: x, y                            out: the ERPL_DBG_MATH_ROWS rows below, each through the
+//                        m_* function of this build (erpl_k_math.h), NaN where the build has none:
+//     0 m_rcp(x)            1 m_rsq(x)             2 m_sqrt_pos(x) (gate: m_sqrt)   3 m_exp2(x, x)
+//     4 m_log2(x, x)        5 m_exp(x)             6 m_pow(x, y)                    7 m_div(x, y)
+//     8 m_atan2(y, x)       9 m_clamp(x, -1, y)   10 alpha, 11 beta of m_aero_angles(y, x, r, y, |x|, r, x), r =
+//    v2 m_rsq(v2), v2 = max(x^2 + y^2, 1e-30) as the fast RHS forms them     12, 13 alpha, beta once more through the single
+//    m_atan2_half<false>(y, x, r, x), m_atan2_half<true>(y, |x|, r, x) (fp64 throughput build)
+//    14 m_next_up(x)       15 m_sqrt(x)
 __global__ __launch_bounds__(256) void ERPL_CAT(erpl_debug_, ERPL_SUFFIX)(const ErplKArgs a, const ErplScalars<real> S,
                                                                          const int what, const int64_t m,
                                                                          const double* __restrict__ in,
@@ -100,10 +112,11 @@ __global__ __launch_bounds__(256) void ERPL_CAT(erpl_debug_, ERPL_SUFFIX)(const 
   __shared__ real alt_s[ERPL_MAX_WIND_KNOTS];
   stage_tables(L, alt_s, a.tables, a.alt_grid, a.k_wind);
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= m) return;
+  const int64_t n = a.n;
+  if (j >= ((what == ERPL_DBG_RHS_SEQ) ? n : m)) return;
   Shared C;
   C.S = &S; C.L = &L; C.alt = alt_s; C.has_wind = a.k_wind > 0; C.motor_kind = a.motor_kind;
-  const int64_t n = a.n, id = j % n;
+  const int64_t id = j % n;   // (ERPL_DBG_RHS_SEQ: j < n, the lane's own sample)
   LaneParams p;
   p.dry = (real)a.rocket[0 * n + id]; p.prop = (real)a.rocket[1 * n + id];
   p.thrust = (real)a.motor[0 * n + id]; p.Ae = (real)a.motor[1 * n + id];
@@ -160,21 +173,51 @@ __global__ __launch_bounds__(256) void ERPL_CAT(erpl_debug_, ERPL_SUFFIX)(const 
 #endif
     out[0 * m + j] = (double)cd; out[1 * m + j] = (double)cl; out[2 * m + j] = (double)cy;
     out[3 * m + j] = (double)cm; out[4 * m + j] = (double)cyaw;
-  } else {
-    const double t = in[0 * m + j];
-    real y[14], dy[14];
+  } else if (what == ERPL_DBG_MATH) {
+    const real x = (real)in[0 * m + j], y = (real)in[1 * m + j];
+    real o[ERPL_DBG_MATH_ROWS];
 #pragma unroll
-    for (int c = 0; c < 14; ++c) y[c] = (real)in[(1 + c) * m + j];
-    bool chute = in[15 * m + j] > 0.0;
-    StampSums ss;
+    for (int k = 0; k < ERPL_DBG_MATH_ROWS; ++k) o[k] = (real)NAN;
+    o[0] = m_rcp(x);
+    o[5] = m_exp(x); o[6] = m_pow(x, y); o[7] = m_div(x, y); o[8] = m_atan2(y, x);
+    o[14] = m_next_up(x); o[15] = m_sqrt(x);
 #if ERPL_FAITHFUL
-    rocket_dynamics(C, p, id, wc, mc, ac, chute, t, y, dy, ss);
+    o[2] = m_sqrt(x);
 #else
-    rocket_dynamics(C, p, id, wc, mc, ac, chute, t, y, dy, ss, lr);
+    o[1] = m_rsq(x); o[2] = m_sqrt_pos(x);
+    o[3] = m_exp2(x, x); o[4] = m_log2(x, x);
+    o[9] = m_clamp(x, (real)-1, y);
+    {  // the angles as rocket_dynamics_at calls them: the lengths are the floored sum of squares times its m_rsq
+      const real v2 = m_max(x * x + y * y, (real)1e-30);
+      const real r = v2 * m_rsq(v2);
+      m_aero_angles(y, x, r, y, m_abs(x), r, x, o[10], o[11]);
+#if ERPL_FAST_F64
+      o[12] = m_atan2_half<false>(y, x, r, x);
+      o[13] = m_atan2_half<true>(y, m_abs(x), r, x);
+#endif
+    }
 #endif
 #pragma unroll
-    for (int c = 0; c < 14; ++c) out[c * m + j] = (double)dy[c];
-    out[14 * m + j] = chute ? 1.0 : 0.0;
+    for (int k = 0; k < ERPL_DBG_MATH_ROWS; ++k) out[k * m + j] = (double)o[k];
+  } else {
+    // ERPL_DBG_RHS: the one column j.  ERPL_DBG_RHS_SEQ: every n-th column from j on, the caches carried over.
+    const int64_t stride = (what == ERPL_DBG_RHS_SEQ) ? n : m;
+    for (int64_t col = j; col < m; col += stride) {
+      const double t = in[0 * m + col];
+      real y[14], dy[14];
+#pragma unroll
+      for (int c = 0; c < 14; ++c) y[c] = (real)in[(1 + c) * m + col];
+      bool chute = in[15 * m + col] > 0.0;
+      StampSums ss;
+#if ERPL_FAITHFUL
+      rocket_dynamics(C, p, id, wc, mc, ac, chute, t, y, dy, ss);
+#else
+      rocket_dynamics(C, p, id, wc, mc, ac, chute, t, y, dy, ss, lr);
+#endif
+#pragma unroll
+      for (int c = 0; c < 14; ++c) out[c * m + col] = (double)dy[c];
+      out[14 * m + col] = chute ? 1.0 : 0.0;
+    }
   }
 }
 

@@ -384,6 +384,7 @@ __global__ __launch_bounds__(kFlightBlock, MINW) void ERPL_CAT(erpl_flight_, ERP
 #endif
         const double th = tb + 0.5 * dt, tf = tb + dt;
         gates = ((tb <= burn) ? 1 : 0) | ((th <= burn) ? 2 : 0) | ((tf <= burn) ? 4 : 0);
+        gates = (tb >= 0.0) ? gates : 0;   // no thrust before t = 0 (motor.py:54-57 / :152-153); th, tf >= tb: dt > 0 (host-checked)
         if (C.motor_kind == ERPL_MOTOR_SOLID) { gate_t[0] = (real)tb; gate_t[1] = (real)th; gate_t[2] = (real)tf; }
       }
 #if ERPL_FAST_F32

@@ -107,7 +107,8 @@ int ERPL_CAT(erpl_launch_debug_, ERPL_SUFFIX)(const ErplKArgs& a, const void* sc
 #else
   const int block = 256;
 #endif
-  const int64_t grid = (m + block - 1) / block;
+  const int64_t lanes = (what == ERPL_DBG_RHS_SEQ) ? a.n : m;   // one lane per sample / per column
+  const int64_t grid = (lanes + block - 1) / block;
   hipLaunchKernelGGL(ERPL_CAT(erpl_debug_, ERPL_SUFFIX), dim3((unsigned)grid), dim3(block), 0, (hipStream_t)stream, a, S,
                      what, m, in, out);
   hipError_t e = hipGetLastError();

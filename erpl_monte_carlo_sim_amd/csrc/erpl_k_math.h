@@ -71,7 +71,9 @@ __device__ __forceinline__ double poly_coef(double c, double after) { asm("" : "
 // v_rcp_f64 seed (measured on MI355X: 4.6e-8 relative, tools/ubench/f64_seed.hip) + ONE cubic round
 // r (1 + e + e^2), e = 1 - a r: error e^3 ~ 1e-22, result within 1.0 ulp - the same as the two Newton rounds
 // of round 2 at three FMAs instead of four.  No denormal / overflow scaling: fast-path operands are
-// O(1e-6 .. 1e12); blow-ups go to inf/NaN as in the reference
+// O(1e-6 .. 1e12); blow-ups go to inf/NaN as in the reference (0 and +-inf give NaN: e = 1 - 0 * inf).
+// (The bounds of this file are asserted on the device against mpmath by tests/test_gpu_math.py; measured worst errors:
+// DESIGN.md section 5.)
 __device__ __forceinline__ double m_rcp(double a) {
   const double r = __builtin_amdgcn_rcp(a);
   const double e = __builtin_fma(-a, r, 1.0);
@@ -86,12 +88,14 @@ __device__ __forceinline__ double m_rsq(double x) {
   return __builtin_fma(y * e, __builtin_fma(0.375, e, 0.5), y);
 }
 // sqrt of a positive finite value as x rsq(x) (7 instructions; the library routine scales, fixes up and
-// classifies: 17).  +inf gives NaN where sqrt gives +inf: both callers feed a state that is past saving.
+// classifies: 17): within 2 * 1.24 + 0.5 = 2.98 ulp (the ulp of rsq(x) weighs up to two of the root's, and the product
+// rounds once).  0 and +inf give NaN where sqrt gives 0 and +inf: both callers feed a state that is past saving.
 __device__ __forceinline__ double m_sqrt_pos(double x) { return x * m_rsq(x); }
 __device__ __forceinline__ double m_clamp(double x, double lo, double hi) { return fmin(fmax(x, lo), hi); }
 // exp2 / log2 / atan for the operand ranges of this RHS, without the special-case ladders of a general
-// libm (those cost ~40 % of its instructions, and with one wave per SIMD every instruction is 4 cycles):
-// errors <= 2 ulp, NaN in -> NaN out, results overflow / underflow to inf / 0 through v_ldexp_f64.
+// libm (those cost ~40 % of its instructions, and with one wave per SIMD every instruction is 4 cycles);
+// NaN in -> NaN out, results overflow / underflow to inf / 0 through v_ldexp_f64.  Errors: m_exp2 <= 2 ulp (denormal
+// spacing below 2^-1022; integers exact); m_log2 and the angles are NOT within 2 ulp of the result - see each.
 // 2^x: x = n + f, |f| <= 1/2, 2^f by the degree-13 Taylor polynomial of exp(f ln 2) (next term 4e-18).
 __device__ __forceinline__ double m_exp2(double x, double early) {
   ERPL_POLY(exp2, early);
@@ -116,6 +120,9 @@ __device__ __forceinline__ double m_exp2(double x, double early) {
 }
 // log2 x, x > 0: x = 2^e m, m in [sqrt(1/2), sqrt 2), s = (m - 1)/(m + 1), |s| <= 0.1716,
 // log2 m = (2/ln 2) s (1 + s^2/3 + s^4/5 + ... + s^22/23)   (next term 6e-19)
+// Error: absolute, <= 1.5 ulp at max(|log2 x|, 1) (three roundings of O(ulp(1/2)) each in s q + e); in ulps of the
+// result that is up to ~3 where |log2 x| is just below a power of two (3.04 measured just under sqrt 2), never above 4.
+// Powers of two are exact (s == 0).
 __device__ __forceinline__ double m_log2(double x, double early) {
   ERPL_POLY(log2, early);
   int e = __builtin_amdgcn_frexp_exp(x);
@@ -143,7 +150,9 @@ __device__ __forceinline__ double m_log2(double x, double early) {
 // 2 atan(a), a = y / (r + |x|), |a| <= 1.  |a| > tan(pi/8) is folded once more with
 // atan a = pi/4 + atan((a - 1)/(a + 1)) - written on numerator and denominator so that ONE reciprocal
 // serves both cases - and the remaining |t| <= 0.4142 takes the 11-term minimax polynomial of fdlibm's
-// s_atan.c (valid to 7/16, < 1 ulp).
+// s_atan.c (valid to 7/16, < 1 ulp).  The angle as a whole - reciprocal, fold, pi/4 and the doubling on top of the
+// polynomial, and the rounding of the length r the caller supplies - is within 4 ulp of the result (3.0 measured, on the
+// fold), not 2: about 5e-16 rad.
 template <bool XPOS>
 __device__ __forceinline__ double m_atan2_half(double y, double x, double r, double early) {
   ERPL_POLY(atan, early);
@@ -225,8 +234,9 @@ __device__ __forceinline__ float m_exp(float x) { return __builtin_amdgcn_exp2f(
 __device__ __forceinline__ float m_pow(float x, float y) { return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x)); }
 __device__ __forceinline__ float m_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 __device__ __forceinline__ float m_rcp(float a) { return __builtin_amdgcn_rcpf(a); }
-// atan2 for finite, not-both-zero arguments: octant reduction + odd minimax polynomial on [0,1]
-// (max error 1.0e-7 rad), NaN-propagating.
+// atan2 for finite, not-both-zero arguments: octant reduction + odd minimax polynomial on [0,1], NaN-propagating.
+// |error| <= 4.5e-8 rad (the polynomial's own 4.44e-8) + 2.8 ulp of the result (reciprocal, quotient and the
+// pi/2 / pi reflections): fp32 angles past 2 rad are 2.4e-7 rad apart, the worst measured is 2.9e-7 rad at 2.57 rad.
 __device__ __forceinline__ float m_atan2(float y, float x) {
   float ax = fabsf(x), ay = fabsf(y);
   float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
@@ -244,7 +254,7 @@ __device__ __forceinline__ float m_atan2(float y, float x) {
   r = fmaf(r * s, a, a);
   r = (ay > ax) ? 1.57079632679489661923f - r : r;
   r = (x < 0.0f) ? 3.14159265358979323846f - r : r;
-  r = (mx != mx || mn != mn) ? (x + y) : r;  // NaN in -> NaN out (fmax/fmin drop NaNs)
+  r = (x != x || y != y) ? (x + y) : r;  // NaN in -> NaN out (fmax/fmin drop a NaN beside a number: mx, mn cannot tell)
   return copysignf(r, y);
 }
 // Aerodynamic angles of the fast RHS through the half angle: with r = sqrt(x^2 + y^2) supplied by the
@@ -252,7 +262,8 @@ __device__ __forceinline__ float m_atan2(float y, float x) {
 //   atan2(y, |x|) = 2 atan(y / (r + |x|)),  |y / (r + |x|)| <= 1,
 // so the [0,1] polynomial applies without octant reduction (no min/max, no pi/2 fix-up) and the sign
 // of y comes with the quotient.  Arguments are finite (q_dynamic > 0 has been tested).  XPOS: x >= 0.
-// Coefficients are twice those of m_atan2 (max error 2e-7 rad).
+// Coefficients are twice those of m_atan2: |error| <= 9e-8 rad (twice the polynomial's) + 3.5 ulp of the result
+// (3.7e-7 rad measured at 1.59 rad, where an fp32 ulp is 1.2e-7 rad).
 template <bool XPOS>
 __device__ __forceinline__ float m_atan2_half(float y, float x, float r, float /*early*/) {
   const float a = y * __builtin_amdgcn_rcpf(r + fabsf(x));

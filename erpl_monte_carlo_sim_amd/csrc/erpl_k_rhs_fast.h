@@ -123,7 +123,8 @@ __device__ __forceinline__ void rocket_dynamics_at(const Shared& C, LaneParams& 
   const real mach2 = (vn2 * rT) * (real)(1.0 / (1.4 * 287.053));
   const real qdyn = (S.q_of_PM2 * P) * mach2;
   // ---- thrust (:359-363) ----
-  const bool burning = (pf > 0) && (GATED ? gate_le_burn : (t <= p.burn));
+  // (the motor models give no thrust and no mass flow at t < 0 either: motor.py:54-57 / :152-153)
+  const bool burning = (pf > 0) && (GATED ? gate_le_burn : (t >= 0.0 && t <= p.burn));
   real thrust;
   if (C.motor_kind == ERPL_MOTOR_SOLID) {  // wave-uniform
     thrust = burning ? solid_curve(C, GATED ? gate_t : (real)t, p.thrust) + p.Ae * ((real)101325.0 - P) : (real)0;

@@ -86,7 +86,8 @@ __device__ __forceinline__ void rocket_dynamics(const Shared& C, const LaneParam
   const real mach = m_div(vn, m_sqrt((real)(1.4 * 287.053) * T));  // utils.py:152-157
   const real qdyn = kFaithful ? ((real)0.5 * rho) * (vn * vn) : ((real)0.5 * rho) * vn2;  // :352
   // thrust (:359-363, motor.py:54-76 / :152-156)
-  const bool burning = (pf > 0) && (t <= p.burn);
+  // (motor.py:54-57 / :152-153 gate thrust and mass flow with `time < 0 or time > burn_time`: t <= burn_time is :359, t >= 0 theirs)
+  const bool burning = (pf > 0) && (t >= 0.0) && (t <= p.burn);
   real thrust = 0;
   if (burning) {
     if (C.motor_kind == ERPL_MOTOR_SOLID) thrust = solid_curve(C, (real)t, p.thrust) + p.Ae * ((real)101325.0 - P);

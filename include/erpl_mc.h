@@ -573,8 +573,15 @@ int erpl_mc_correlation(erpl_ctx* ctx, const double* factors, const double* summ
  * [rows][m].   what = ERPL_DBG_ATMOSPHERE: in altitude -> out T, P, rho, g (environment.py:26-108);
  * ERPL_DBG_AERO: in mach, alpha, beta, propellant_fraction, power_on -> out cd, cl, cy, cm, cyaw
  * (rocket.py:138-218; the fast builds take power_on = propellant_fraction > 0 as the RHS does);
- * ERPL_DBG_RHS: in t, y[14], parachute latch -> out dy[14], latch (simulator.py:295-460). */
-enum { ERPL_DBG_ATMOSPHERE = 0, ERPL_DBG_AERO = 1, ERPL_DBG_RHS = 2 };
+ * ERPL_DBG_RHS: in t, y[14], parachute latch -> out dy[14], latch (simulator.py:295-460);
+ * ERPL_DBG_MATH: in x, y -> out ERPL_DBG_MATH_ROWS rows, one per arithmetic primitive of the build (m_rcp, m_rsq,
+ * m_sqrt_pos, m_exp2, m_log2, m_exp, m_pow, m_div, m_atan2, m_clamp, the aerodynamic angles, m_next_up, m_sqrt: the
+ * table is in csrc/erpl_k_debug.h), NaN where the build has none;
+ * ERPL_DBG_RHS_SEQ: the layout of ERPL_DBG_RHS, but batch->n lanes, one per sample: lane i evaluates the columns
+ * i, i + n, i + 2n, ... < m in that order through one set of cached wind / Mach / atmosphere intervals that is cleared
+ * before the first column only (the latch is each column's input: the values are those of ERPL_DBG_RHS). */
+enum { ERPL_DBG_ATMOSPHERE = 0, ERPL_DBG_AERO = 1, ERPL_DBG_RHS = 2, ERPL_DBG_MATH = 3, ERPL_DBG_RHS_SEQ = 4 };
+#define ERPL_DBG_MATH_ROWS 16
 int erpl_mc_debug_eval(erpl_ctx* ctx, const erpl_batch* batch, int what, int64_t m, const double* in, double* out,
                        void* hip_stream);
 

@@ -128,3 +128,22 @@ def same_nested(a, b):
     if isinstance(a, float) and isinstance(b, float) and np.isnan(a) and np.isnan(b):
         return True
     return type(a) is type(b) and a == b
+
+
+def ulp(ref, dtype):
+    """Spacing of the floating-point format `dtype` at |ref|: 2^(e - p + 1) for 2^e <= |ref| < 2^(e+1), with the
+    format's denormal spacing below its smallest normal number (and at 0)."""
+    fi = np.finfo(dtype)
+    a = np.abs(np.asarray(ref, dtype=np.float64))
+    _, e = np.frexp(a)                      # a = m 2^e with 1/2 <= m < 1
+    e = np.where(a > 0, np.maximum(e - 1, fi.minexp), fi.minexp)
+    return np.ldexp(1.0, e - fi.nmant)
+
+
+def ulp_error(got, ref_hi, ref_lo, dtype):
+    """|got - (ref_hi + ref_lo)| in ulps of `dtype` at the reference value (ref_hi + ref_lo: a high-precision
+    reference split into its float64 head and tail).  A NaN or infinite `got` at a finite reference counts as inf."""
+    got = np.asarray(got, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        err = np.abs((got - ref_hi) - ref_lo) / ulp(ref_hi, dtype)
+    return np.where(np.isnan(err), np.inf, err)

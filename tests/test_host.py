@@ -192,6 +192,10 @@ def test_header_and_ctypes_agree():
                       ("ERPL_MAX_MACH_KNOTS", _abi.MAX_MACH_KNOTS), ("ERPL_MAX_CURVE_KNOTS", _abi.MAX_CURVE_KNOTS),
                       ("ERPL_MAX_WIND_KNOTS", _abi.MAX_WIND_KNOTS), ("ERPL_MC_ABI_VERSION", _abi.ABI_VERSION)):
         assert re.search(rf"#define {name} {val}\b", hdr), name
+    assert re.search(rf"#define ERPL_DBG_MATH_ROWS {_abi.DBG_MATH_ROWS}\b", hdr)
+    for name, val in (("ATMOSPHERE", _abi.DBG_ATMOSPHERE), ("AERO", _abi.DBG_AERO), ("RHS", _abi.DBG_RHS),
+                      ("MATH", _abi.DBG_MATH), ("RHS_SEQ", _abi.DBG_RHS_SEQ)):
+        assert re.search(rf"\bERPL_DBG_{name} = {val}\b", hdr), name
 
 
 def test_struct_layout_matches_c_compiler(tmp_path):
