@@ -196,6 +196,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_
 
 # every symbol include/erpl_mc.h declares
 RS_GAUSS, RS_DOUBLE = 0, 1   # erpl_mc_legacy_random_streams ops
+LEGACY_DEVICE_MAX_OUTPUTS = 4096   # erpl_mc_legacy_random_streams_device: outputs per stream
 
 EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_mc_destroy",
            "erpl_mc_set_config", "erpl_mc_reserve", "erpl_mc_run_batch", "erpl_mc_set_launch",
@@ -208,7 +209,8 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_analysis_defaults", "erpl_mc_analyze",
            "erpl_mc_histogram_defaults", "erpl_mc_histogram", "erpl_mc_histogram_xy",
            "erpl_mc_dispersion_defaults", "erpl_mc_dispersion",
-           "erpl_mc_correlation_defaults", "erpl_mc_correlation")
+           "erpl_mc_correlation_defaults", "erpl_mc_correlation",
+           "erpl_mc_legacy_random_streams_device", "erpl_mc_legacy_wind_profiles_device")
 
 _lib = None
 
@@ -286,6 +288,10 @@ def load_library(path=None):
     lib.erpl_mc_correlation_defaults.argtypes = [C.POINTER(ErplCorrSpec)]
     lib.erpl_mc_correlation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplCorrSpec),
                                         C.POINTER(ErplCorrResult), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erpl_mc_legacy_random_streams_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                                         C.c_int32, C.c_void_p]
+    lib.erpl_mc_legacy_wind_profiles_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 9 + \
+        [C.c_int32, C.c_void_p]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if a declared symbol is not exported
         if name not in ("erpl_mc_last_error",):

@@ -1,7 +1,9 @@
-// erpl_host.h — what the host units of the C ABI share (erpl_api.hip, erpl_sampling.hip, erpl_stats_api.hip): the error
+// erpl_host.h — what the host units of the C ABI share (erpl_api.hip, erpl_sampling.hip, erpl_stats_api.hip,
+// erpl_legacy_device.hip): the error
 // text behind erpl_mc_last_error, the context, and the host patterns that exist once.  Internal, never installed.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include <functional>
@@ -135,6 +137,14 @@ struct erpl_ctx {
   ErplCorrOut* corr_host = nullptr;
   char* corr_buf = nullptr;
   size_t corr_cap = 0;
+  // erpl_mc_legacy_random_streams_device / _wind_profiles_device: one device buffer (flag, op tables, knot constants, the
+  // MT19937 states of a tile and two sets of its accepted pairs) and its pinned staging (the tables on their way up, r2
+  // down and f up, per set), both bounded by the tile; an event per set behind the tile's copy to the host
+  char* legacy_buf = nullptr;
+  size_t legacy_cap = 0;
+  char* legacy_pin = nullptr;
+  size_t legacy_pin_cap = 0;
+  hipEvent_t legacy_ev[2] = {};
 };
 
 // A fixed device block and its pinned mirror, both allocated with the first call that needs them and freed by erpl_mc_destroy.
@@ -157,6 +167,10 @@ int erpl_grow(T*& p, size_t& cap, size_t bytes) {
   cap = bytes;
   return ERPL_OK;
 }
+
+// The scale of an accepted pair of the legacy polar Gaussian (LegacyRS::next_gauss, and the host phase of the device
+// streams): the one copy, so that both go through the same libm log with the same rounding of the quotient.
+inline double legacy_gauss_scale(double r2) { return sqrt(-2.0 * log(r2) / r2); }
 
 // The host pools: worker w of nthr takes the samples [n * w / nthr, n * (w + 1) / nthr) or every nthr-th table entry.
 inline int host_threads(int32_t requested, int64_t n) {

@@ -46,7 +46,7 @@ struct LegacyRS {
       x2 = 2.0 * next_double() - 1.0;
       r2 = x1 * x1 + x2 * x2;
     } while (r2 >= 1.0 || r2 == 0.0);
-    const double f = sqrt(-2.0 * log(r2) / r2);
+    const double f = legacy_gauss_scale(r2);
     gauss = f * x1; has_gauss = true;
     return f * x2;
   }

@@ -5,6 +5,7 @@ stream; every number is produced by the hand-written HIP kernels behind `erpl_mc
 No CPU execution path exists here: if the HIP library or a GPU is missing, construction raises.
 """
 import ctypes as C
+import threading
 
 import numpy as np
 import torch
@@ -40,15 +41,23 @@ class DeviceBatch:
         return b
 
     @staticmethod
-    def from_host(hb, device, precision=_abi.PREC_F64):
-        """Upload a flatten.HostBatch.  The wind table is stored in the working precision."""
+    def from_host(hb, device, precision=_abi.PREC_F64, wind=None):
+        """Upload a flatten.HostBatch.  The wind table is stored in the working precision.  `wind`: the float64 [K, 3, n]
+        table already on the device (TrajectoryEngine.legacy_wind_device) of a batch built without one; it is checked
+        there and converted as an uploaded one is."""
         if hb.k_wind > _abi.MAX_WIND_KNOTS:
             raise _abi.ErplError(f"{hb.k_wind} wind knots exceed the ABI limit {_abi.MAX_WIND_KNOTS}")
         if hb.k_wind and not np.all(np.diff(hb.alt_grid) > 0):
             raise _abi.ErplError("altitude_profile must be strictly increasing")
         # (one reduction instead of an element-wise mask: a NaN or inf anywhere makes the sum non-finite; a finite table
         # whose sum overflows is re-checked element by element)
-        if hb.k_wind and not (np.all(np.isfinite(hb.alt_grid)) and (np.isfinite(np.sum(hb.wind)) or np.all(np.isfinite(hb.wind)))):
+        if hb.k_wind and hb.wind is None and wind is None:
+            raise _abi.ErplError("the batch was built without its wind table (with_wind=False) and none is given")
+        if wind is None:
+            finite = lambda: np.isfinite(np.sum(hb.wind)) or np.all(np.isfinite(hb.wind))
+        else:   # the same two reductions on the device
+            finite = lambda: bool(torch.isfinite(wind.sum())) or bool(torch.isfinite(wind).all())
+        if hb.k_wind and not (np.all(np.isfinite(hb.alt_grid)) and finite()):
             raise _abi.ErplError("wind profile must be finite")
         # The kernels assume what the reference silently assumes: finite inputs, positive masses and
         # mass flow, a finite burn time (a non-finite burn time would never leave the launch rail).
@@ -67,7 +76,9 @@ class DeviceBatch:
         motor = torch.as_tensor(np.ascontiguousarray(hb.motor), **f64)
         if hb.k_wind:
             alt = torch.as_tensor(np.ascontiguousarray(hb.alt_grid), **f64)
-            wind = torch.as_tensor(np.ascontiguousarray(hb.wind), device=device).to(wdt).contiguous()
+            if wind is None:
+                wind = torch.as_tensor(np.ascontiguousarray(hb.wind), device=device)
+            wind = wind.to(wdt).contiguous()
         else:
             alt, wind = None, None
         return DeviceBatch(ic, rocket, motor, alt, wind, precision)
@@ -87,6 +98,7 @@ class TrajectoryEngine:
         self._ctx = C.c_void_p()
         _abi.check(self.lib, self.lib.erpl_mc_create(idx, C.byref(self._ctx)), "erpl_mc_create")
         self._cfg = None
+        self._legacy_lock = threading.Lock()   # legacy_streams_device / legacy_wind_device: one workspace per context
 
     def _call(self, name, *args):
         """`name(ctx, *args)` of the library; a non-zero return raises with the library's own message (_abi.check)."""
@@ -461,6 +473,67 @@ class TrajectoryEngine:
         if want_ranks:
             out["ranks"] = rk
         return out
+
+    def _seeds_on_device(self, seeds):
+        """The 32-bit seeds of the device streams: n."""
+        if not (seeds.is_cuda and seeds.device == self.device and seeds.dtype in (torch.uint32, torch.int32)
+                and seeds.dim() == 1 and seeds.is_contiguous()):
+            raise ValueError(f"seeds must be a contiguous uint32 (or int32: the same 32 bits) [n] tensor on {self.device}")
+        return int(seeds.shape[0])
+
+    def legacy_streams_device(self, seeds, ops, threads=0):
+        """flatten.legacy_streams(by_output=True) on the device (erpl_mc_legacy_random_streams_device): the first len(ops)
+        outputs ('g' normal / 'u' uniform double) of np.random.RandomState(seed) for every seed of the uint32 [n] device
+        tensor `seeds`, bit for bit, as a float64 [len(ops), n] device tensor.  Enqueued on the current torch stream; blocks
+        the host until the tensor is filled (the libm log of every accepted pair runs on `threads` host threads)."""
+        n = self._seeds_on_device(seeds)
+        code = np.frombuffer(ops.encode(), dtype=np.uint8)
+        if not np.all((code == ord("g")) | (code == ord("u"))):
+            raise ValueError("ops: 'g' (normal) and 'u' (uniform double) only")
+        code = np.ascontiguousarray(np.where(code == ord("g"), _abi.RS_GAUSS, _abi.RS_DOUBLE).astype(np.uint8))
+        out = torch.empty((code.size, n), dtype=torch.float64, device=self.device)
+        st = torch.cuda.current_stream(self.device)
+        with self._legacy_lock:
+            self._call("erpl_mc_legacy_random_streams_device", C.c_void_p(seeds.data_ptr()), n,
+                       C.c_void_p(code.ctypes.data), int(code.size), C.c_void_p(out.data_ptr()), int(threads),
+                       C.c_void_p(st.cuda_stream))
+        return out
+
+    def legacy_wind_device(self, seeds, sigma, rho, innov, base=None, mean_scale=None, speed=None, cdir=None, sdir=None,
+                           threads=0):
+        """erpl_mc_legacy_wind_profiles on the device (erpl_mc_legacy_wind_profiles_device): the float64 [K, 3, n] wind
+        tables of the uint32 [n] device tensor `seeds`, bit for bit the host function's.  sigma / rho / innov [K] and
+        base [K, 3] or mean_scale [K] are host arrays; speed / cdir / sdir (without `base`) float64 [n] device tensors.
+        Enqueued on the current torch stream; blocks the host until the table is filled."""
+        n = self._seeds_on_device(seeds)
+        f = lambda v: np.ascontiguousarray(v, dtype=np.float64)
+        sigma, rho, innov = f(sigma), f(rho), f(innov)
+        K = sigma.size
+        if rho.size != K or innov.size != K:
+            raise ValueError("sigma, rho and innov: one entry per knot")
+        if base is not None:
+            base = f(base)
+            if base.shape != (K, 3):
+                raise ValueError("base must be [K, 3]")
+        else:
+            if mean_scale is None or speed is None or cdir is None or sdir is None:
+                raise ValueError("without base: mean_scale, speed, cdir and sdir")
+            mean_scale = f(mean_scale)
+            if mean_scale.size != K:
+                raise ValueError("mean_scale: one entry per knot")
+            for t in (speed, cdir, sdir):
+                if not (t.is_cuda and t.device == self.device and t.dtype == torch.float64 and tuple(t.shape) == (n,)
+                        and t.is_contiguous()):
+                    raise ValueError(f"speed, cdir and sdir must be contiguous float64 [n] tensors on {self.device}")
+        hp = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+        dp = lambda t: None if t is None or base is not None else C.c_void_p(t.data_ptr())
+        wind = torch.empty((K, 3, n), dtype=torch.float64, device=self.device)
+        st = torch.cuda.current_stream(self.device)
+        with self._legacy_lock:
+            self._call("erpl_mc_legacy_wind_profiles_device", C.c_void_p(seeds.data_ptr()), n, K, hp(sigma), hp(rho),
+                       hp(innov), hp(base), hp(mean_scale), dp(speed), dp(cdir), dp(sdir), C.c_void_p(wind.data_ptr()),
+                       int(threads), C.c_void_p(st.cuda_stream))
+        return wind
 
     def set_profiling(self, enable=True):
         """Record HIP events around the two kernels on the launch stream (erpl_mc_set_profiling)."""

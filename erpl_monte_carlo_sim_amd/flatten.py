@@ -424,6 +424,23 @@ def legacy_wind_profiles(wind_model, alt, seeds, base=None, speed=None, cdir=Non
     return out
 
 
+def legacy_wind_profiles_device(engine, wind_model, alt, seeds, base=None, speed=None, cdir=None, sdir=None, threads=0):
+    """legacy_wind_profiles with the table built on the engine's device (TrajectoryEngine.legacy_wind_device): same
+    arguments (host arrays), same bits, returned as a float64 [K, 3, n] device tensor on the current torch stream."""
+    import torch
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+    threads = threads if threads > 0 else host_cores()
+    sigma, rho, innov = knot_constants(wind_model, alt)
+    rho, innov = [0.0] + list(rho[1:]), [0.0] + list(innov[1:])
+    up = lambda v, dt: torch.as_tensor(np.ascontiguousarray(v, dtype=dt), device=engine.device)
+    d_seeds = up(seeds.view(np.int32), np.int32)   # the same 32 bits
+    if base is not None:
+        return engine.legacy_wind_device(d_seeds, sigma, rho, innov, base=base, threads=threads)
+    scale = [(np.float64(a) / 10.0) ** wind_model.power_law_exponent for a in alt]   # on scalars, as legacy_wind_profiles
+    return engine.legacy_wind_device(d_seeds, sigma, rho, innov, mean_scale=scale, speed=up(speed, np.float64),
+                                     cdir=up(cdir, np.float64), sdir=up(sdir, np.float64), threads=threads)
+
+
 def _ar1_profiles(wind_model, alt, g, mean_u=None, mean_v=None, base=None):
     """AR(1) turbulence of environment.py:161-198 / :242-263 for all samples: g [3K, n] holds each
     sample's normals in draw order (u, v, w per knot); returns [K, 3, n]."""
@@ -452,7 +469,7 @@ def _ar1_profiles(wind_model, alt, g, mean_u=None, mean_v=None, base=None):
 
 
 def dispersed_batch(rocket, motor, wind_model, base_initial_conditions, params_list,
-                    base_altitude_profile=None, base_wind_profile=None, planar=False, threads=0):
+                    base_altitude_profile=None, base_wind_profile=None, planar=False, threads=0, with_wind=True):
     """Per-sample inputs exactly as MonteCarloAnalyzer._run_single_simulation builds them
     (monte_carlo.py:228-288), for all samples at once: IC + offsets, masses x mass_multiplier, motor
     perturbed from a fresh RandomState(seed) with propellant mass / burn time re-synchronised
@@ -460,7 +477,10 @@ def dispersed_batch(rocket, motor, wind_model, base_initial_conditions, params_l
     the 100-knot synthetic profile).  `planar=True` zeroes every out-of-plane input (Set P, SURVEY
     §8d).  `params_list` is the reference's list of dicts or the dict of arrays of
     generate_parameter_arrays.  `threads`: host threads of the C generators (0 = all the process may use; callers that
-    prepare several batches side by side share them out)."""
+    prepare several batches side by side share them out).  `with_wind=False` leaves the wind table out (`wind` is None)
+    for a caller that builds it on the device: the batch still carries `alt_grid` and the per-sample `wind_speed`,
+    `wind_cos` and `wind_sin` the table is made from.  (The per-sample fallback for a non-positive mass flow returns its
+    table regardless.)"""
     reject_overrides(wind_model, "wind_model")
     use_base = base_wind_profile is not None and base_altitude_profile is not None
     alt = (np.asarray(base_altitude_profile, dtype=np.float64) if use_base else np.linspace(0, 25000, 100))
@@ -522,6 +542,10 @@ def dispersed_batch(rocket, motor, wind_model, base_initial_conditions, params_l
     # order, fp64), the per-knot constants and the sample-wise offsets as NumPy expressions
     speed, direction = P["wind_speed"], P["wind_direction"]
     cd, sd = np.cos(direction), np.sin(direction)
+    b.wind_speed, b.wind_cos, b.wind_sin = speed, cd, sd
+    if not with_wind:
+        b.wind = None
+        return b
     if use_base:
         w = legacy_wind_profiles(wind_model, alt, seeds, base=np.asarray(base_wind_profile, dtype=np.float64), threads=threads)
         w[:, 0, :] += speed * cd

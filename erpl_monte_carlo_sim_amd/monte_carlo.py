@@ -4,9 +4,10 @@
 signature and the structure of the returned analysis dict.  The ProcessPoolExecutor fan-out of the
 reference (one future per sample, results pickled back through pipes) becomes: flatten all samples
 into SoA tensors -> one `erpl_mc_run_batch` per GPU on this rank's shard -> one all-gather of the
-[16, n] summaries (RCCL when torch.distributed is initialised with "nccl").  Dispersion draws,
-motor perturbation and wind synthesis stay on the host and are bit-identical to the reference
-(flatten.py); the integration itself runs only on the GPU.
+[16, n] summaries (RCCL when torch.distributed is initialised with "nccl").  Dispersion draws and
+motor perturbation stay on the host, the per-sample wind tables are built on the device
+(`wind_on_device`; on the host without it); all are bit-identical to the reference (flatten.py);
+the integration itself runs only on the GPU.
 """
 import os
 import time
@@ -47,6 +48,10 @@ class MonteCarloAnalyzer:
         # apogee / healthy flights only
         self.precision = "f64_fast"
         self._motor_inputs = None            # [2, n] of the last run_batch_arrays: thrust and mass flow the kernels read
+        # run_monte_carlo's chunks: True = the per-sample wind tables are built on the device (erpl_mc_legacy_wind_profiles_
+        # device: drawn, scaled through the host's libm and finished in HBM, never uploaded), False = on the host
+        # (erpl_mc_legacy_wind_profiles) and uploaded.  Same bits either way (DESIGN.md section 4 has the timings)
+        self.wind_on_device = True
         self.n_trajectories = 50             # samples that carry a 'trajectory' (plots use the first 50)
         self.trajectory_stride = 20
         # simulator attributes a user could have changed on FlightSimulator
@@ -80,17 +85,33 @@ class MonteCarloAnalyzer:
 
         The samples that carry a trajectory (global index < n_traj_global: the first ones of the shard) go through
         the trajectory-capture build in a small batch of their own; everything else runs in chunks of CHUNK samples
-        handed to erpl_mc_submit_batch, so that the host builds chunk i+1 (MT19937 streams and AR(1) wind tables in
-        C threads, the rest as NumPy expressions) while the GPU integrates chunk i.  Samples are independent: the
+        handed to erpl_mc_submit_batch, so that the host builds chunk i+1 (MT19937 streams in C threads, the AR(1)
+        wind tables on the device with wind_on_device or in C threads without, the rest as NumPy expressions) while the
+        GPU integrates chunk i.  Samples are independent: the
         split does not change a single bit of the summaries (tested)."""
         eng = shared_engine(self.device)
         eng.set_config(self._config())
         prec = _abi.PRECISIONS[self.precision]
         take = (lambda a, b: {k: v[a:b] for k, v in params.items()}) if isinstance(params, dict) else (lambda a, b: params[a:b])
 
-        def host_batch(a, b, threads=0):
+        def host_batch(a, b, threads=0, with_wind=True):
             return flatten.dispersed_batch(self.rocket, self.motor, self.wind_model, initial_conditions, take(a, b),
-                                           self.base_altitude_profile, self.base_wind_profile, threads=threads)
+                                           self.base_altitude_profile, self.base_wind_profile, threads=threads,
+                                           with_wind=with_wind)
+
+        def device_wind(hb, a, b):
+            """The wind table flatten.dispersed_batch leaves out, built on the device on the current stream: the table
+            of erpl_mc_legacy_wind_profiles and the host's post-steps in fp64, products rounded first as NumPy does."""
+            seeds = np.asarray(take(a, b)["random_seed"] if isinstance(params, dict) else [p["random_seed"] for p in take(a, b)])
+            if self.base_wind_profile is not None and self.base_altitude_profile is not None:
+                w = flatten.legacy_wind_profiles_device(eng, self.wind_model, hb.alt_grid, seeds,
+                                                        base=np.asarray(self.base_wind_profile, dtype=np.float64))
+                up = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.float64), device=eng.device)
+                w[:, 0, :] += up(hb.wind_speed * hb.wind_cos)
+                w[:, 1, :] += up(hb.wind_speed * hb.wind_sin)
+                return w
+            return flatten.legacy_wind_profiles_device(eng, self.wind_model, hb.alt_grid, seeds, speed=hb.wind_speed,
+                                                       cdir=hb.wind_cos, sdir=hb.wind_sin)
         parts, traj, capture_inputs = [], None, None
         motor_parts = []
         m = max(0, min(hi, n_traj_global) - lo)   # local samples 0..m-1 are captured
@@ -146,11 +167,15 @@ class MonteCarloAnalyzer:
         chunks = [(a, min(hi, a + self.CHUNK)) for a in range(lo + m, hi, self.CHUNK)]
         workers = max(1, min(len(chunks), flatten.host_workers()))
         def device_batch(a, b):
-            # validation and the upload (335 MB of pageable memory per chunk: 70 ms at the 4.6 GB/s such a copy gets) in
-            # the worker too: on the default stream of the engine's device, before the submission that follows it there
+            # validation and the upload in the worker too: on the default stream of the engine's device, before the
+            # submission that follows it there.  With wind_on_device the 335 MB wind table of a chunk is built there by
+            # legacy_wind_device (the workers take turns at it: the engine holds a lock) and only the small rows go up;
+            # without it the table is built on the host and uploaded from pageable memory.
             with torch.cuda.device(eng.device):
-                hb = host_batch(a, b, threads=max(1, flatten.host_cores() // workers))
-                db = DeviceBatch.from_host(hb, eng.device, prec)
+                hb = host_batch(a, b, threads=max(1, flatten.host_cores() // workers), with_wind=not self.wind_on_device)
+                # (a batch that fell back to the per-sample loop carries its table: it goes up as before)
+                wind = device_wind(hb, a, b) if hb.wind is None else None
+                db = DeviceBatch.from_host(hb, eng.device, prec, wind=wind)
                 db.motor_inputs = hb.motor[[0, 2]].copy()   # 16 bytes per sample, kept beside the summary
                 return db
         with ThreadPoolExecutor(workers) as pool:

@@ -328,6 +328,32 @@ int erpl_mc_legacy_wind_profiles(const uint32_t* seeds, int64_t n, int32_t k, co
                                  const double* mean_scale, const double* speed, const double* cdir,
                                  const double* sdir, double* wind, int32_t threads);
 
+/* erpl_mc_legacy_random_streams on the device: out[j][i] (device double [m][n], the by_output layout) = output j of
+ * RandomState(seeds[i]), bit for bit what the host function returns - the per-sample streams of monte_carlo.py:157, :263.
+ * seeds: device [n]; ops: host [m], m <= ERPL_LEGACY_DEVICE_MAX_OUTPUTS.  The device seeds, twists, tempers, forms the
+ * 53-bit doubles and runs the polar rejection loop; the one step that is not exactly rounded, the libm log inside the
+ * scale sqrt(-2 log(r2) / r2) of an accepted pair, runs on `threads` host threads (<= 0: all cores) through the very
+ * function the host generator uses; the device multiplies.  Samples are worked in tiles, so the workspace (device memory
+ * and pinned staging of the context, growing only, freed by erpl_mc_destroy) does not grow with n, and no value depends
+ * on the tile.  The work is enqueued on hip_stream behind what is already there; the call returns when `out` is filled
+ * (it blocks the host on that stream).  Calls of these two functions on one context are serialised by the caller; they
+ * touch nothing but their own workspace, so another thread may submit and check batches of the context meanwhile.  A stream whose rejection
+ * loop does not end within 4096 tries of one pair fails the call with ERPL_ERR_INVALID and the sample's index. */
+#define ERPL_LEGACY_DEVICE_MAX_OUTPUTS 4096   /* >= 3 * ERPL_MAX_WIND_KNOTS */
+int erpl_mc_legacy_random_streams_device(erpl_ctx* ctx, const uint32_t* seeds, int64_t n, const uint8_t* ops, int32_t m,
+                                         double* out, int32_t threads, void* hip_stream);
+
+/* erpl_mc_legacy_wind_profiles on the device: same arguments, same two modes (base != NULL: perturb_wind_profile,
+ * environment.py:218-265; base == NULL: generate_stochastic_profile, environment.py:125-200), same operations in the same
+ * order, same bits - the wind table of monte_carlo.py:263 built where the flight kernels read it, never on the host.
+ * sigma / rho / innov / base / mean_scale: host; seeds / speed / cdir / sdir / wind: device; wind is double [k][3][n].
+ * Phases, workspace, stream and blocking as erpl_mc_legacy_random_streams_device: the normals are drawn as there and
+ * the AR(1) recursion runs in the finishing kernel. */
+int erpl_mc_legacy_wind_profiles_device(erpl_ctx* ctx, const uint32_t* seeds, int64_t n, int32_t k, const double* sigma,
+                                        const double* rho, const double* innov, const double* base,
+                                        const double* mean_scale, const double* speed, const double* cdir,
+                                        const double* sdir, double* wind, int32_t threads, void* hip_stream);
+
 /* On-device wind-table synthesis for the 100 k - 10 M throughput sets: the AR(1) turbulence
  * recursion over the k altitude knots of environment.py:161-198 / :242-263 plus the mean wind, for n
  * samples at once, from caller-supplied standard normals (counter-based device RNG; NOT the MT19937
