@@ -7,31 +7,16 @@
 //   select     most-significant-digit radix selection of all order statistics of a row together: eight passes of one
 //              8-bit digit histogram per group of targets that still share a key prefix (LDS integer atomics, flushed to
 //              64-bit global bins), a small kernel between passes that fixes the next digit of every target
-// Sums are accumulated per thread in index order and reduced in a fixed tree; integer adds commute.  So the result is the
-// same bits in every call.  No floating-point atomics.  Compiled with -ffp-contract=off: (x - mean)^2 is rounded as np.std
-// rounds it.
-#include <hip/hip_runtime.h>
-#include <math.h>
-
-#include "erpl_tables.h"
+// Sums are accumulated per thread in index order and reduced in the fixed order of erpl_stat_device.h; integer adds
+// commute.  So the result is the same bits in every call.  No floating-point atomics.  Compiled with -ffp-contract=off:
+// (x - mean)^2 is rounded as np.std rounds it.
+#include "erpl_stat_device.h"
 
 namespace {
-
-constexpr int kWaves = ERPL_ANA_BLOCK / 64;
-
-__device__ __forceinline__ bool finite_bits(double v) {
-  return (__double_as_longlong(v) & 0x7ff0000000000000ll) != 0x7ff0000000000000ll;
-}
-// order-preserving map of a finite double onto an unsigned key (-0.0 sorts just below +0.0, which compare equal)
-__device__ __forceinline__ unsigned long long key_of(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return b ^ ((b >> 63) ? ~0ull : (1ull << 63));
-}
 
 // ---- classify: one sample per thread and iteration; the counts of a wave are ballots (uniform), the workgroup's go to
 // its own slot of work->cpart
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_classify(const ErplAnaArgs a) {
-  __shared__ unsigned long long s_cnt[kWaves][ERPL_ANA_COUNTERS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
   const double* __restrict__ apo_p = a.summary + (int64_t)ERPL_SUM_APOGEE_ALT * n;
@@ -67,25 +52,15 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_classify(const ErplAn
     }
     cnt[13] += __popcll(__ballot(in && why == 0));
   }
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < ERPL_ANA_COUNTERS; ++k) s_cnt[wave][k] = cnt[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < ERPL_ANA_COUNTERS) {
-    unsigned long long s = 0ull;
-    for (int w = 0; w < kWaves; ++w) s += s_cnt[w][threadIdx.x];
-    a.work->cpart[blockIdx.x][threadIdx.x] = s;
-  }
+  const u64 s = counters_fold(cnt);
+  if (threadIdx.x < ERPL_ANA_COUNTERS) a.work->cpart[blockIdx.x][threadIdx.x] = s;
 }
 
 // ---- moments.  SECOND = false: sum, count, min, max of the valid finite values of row rows[blockIdx.y];
 // SECOND = true: sum of (x - mean)^2 with the mean of the first pass.
 template <bool SECOND>
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_moments(const ErplAnaArgs a) {
-  __shared__ double s_sum[kWaves], s_min[kWaves], s_max[kWaves];
-  __shared__ unsigned long long s_cnt[kWaves];
-  const int r = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = blockIdx.y;
   const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
   const double* __restrict__ x = a.summary + (int64_t)a.rows[r] * n;
   const uint8_t* __restrict__ why = a.why;
@@ -106,45 +81,17 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_moments(const ErplAna
       }
     }
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    sum += __shfl_down(sum, off);
-    if (!SECOND) {
-      cnt += __shfl_down(cnt, off);
-      const double m0 = __shfl_down(mn, off), m1 = __shfl_down(mx, off);
-      mn = m0 < mn ? m0 : mn;
-      mx = m1 > mx ? m1 : mx;
-    }
-  }
-  if (lane == 0) { s_sum[wave] = sum; s_min[wave] = mn; s_max[wave] = mx; s_cnt[wave] = cnt; }
-  __syncthreads();
+  if (SECOND) block_fold<Add>(sum);
+  else block_fold<Add, Add, Min, Max>(sum, cnt, mn, mx);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < kWaves; ++w) {
-      sum += s_sum[w];
-      if (!SECOND) { cnt += s_cnt[w]; mn = s_min[w] < mn ? s_min[w] : mn; mx = s_max[w] > mx ? s_max[w] : mx; }
-    }
     a.work->psum[r][blockIdx.x] = sum;
     if (!SECOND) { a.work->pcnt[r][blockIdx.x] = cnt; a.work->pmin[r][blockIdx.x] = mn; a.work->pmax[r][blockIdx.x] = mx; }
   }
 }
 
-// Sum of the first `nb` doubles of p by one workgroup of ERPL_ANA_BLOCK threads: thread t adds its four neighbours in
-// index order, then the fixed tree.  Valid in thread 0.
-__device__ double block_sum(const double* p, int nb, double* s_wave) {
-  constexpr int per = ERPL_ANA_MAX_BLOCKS / ERPL_ANA_BLOCK;
-  double s = 0.0;
-  for (int k = 0; k < per; ++k) { const int j = threadIdx.x * per + k; if (j < nb) s += p[j]; }
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-  __syncthreads();   // s_wave may still be read from an earlier call
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) for (int w = 1; w < kWaves; ++w) s += s_wave[w];
-  return s;
-}
-
 // ---- after the first moment pass: workgroup r < n_rows finishes row r and sets up its selection; workgroup n_rows adds
 // up the classify counters
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_finish_first(const ErplAnaArgs a, const int nb) {
-  __shared__ double s_wave[kWaves], s_min[kWaves], s_max[kWaves];
   __shared__ unsigned long long s_cnt[ERPL_ANA_BLOCK];
   ErplAnaWork* w = a.work;
   if ((int)blockIdx.x == a.n_rows) {
@@ -162,28 +109,11 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_finish_first(const Er
     return;
   }
   const int r = blockIdx.x;
-  constexpr int per = ERPL_ANA_MAX_BLOCKS / ERPL_ANA_BLOCK;
-  const double sum = block_sum(w->psum[r], nb, s_wave);
-  unsigned long long cnt = 0ull;
-  double mn = INFINITY, mx = -INFINITY;
-  for (int k = 0; k < per; ++k) {
-    const int j = threadIdx.x * per + k;
-    if (j < nb) {
-      cnt += w->pcnt[r][j];
-      mn = w->pmin[r][j] < mn ? w->pmin[r][j] : mn;
-      mx = w->pmax[r][j] > mx ? w->pmax[r][j] : mx;
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    cnt += __shfl_down(cnt, off);
-    const double m0 = __shfl_down(mn, off), m1 = __shfl_down(mx, off);
-    mn = m0 < mn ? m0 : mn;
-    mx = m1 > mx ? m1 : mx;
-  }
-  if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6] = cnt; s_min[threadIdx.x >> 6] = mn; s_max[threadIdx.x >> 6] = mx; }
-  __syncthreads();
+  double sum = thread_partials<Add>(w->psum[r], nb);
+  u64 cnt = thread_partials<Add>(w->pcnt[r], nb);
+  double mn = thread_partials<Min>(w->pmin[r], nb), mx = thread_partials<Max>(w->pmax[r], nb);
+  block_fold<Add, Add, Min, Max>(sum, cnt, mn, mx);
   if (threadIdx.x == 0) {
-    for (int k = 1; k < kWaves; ++k) { cnt += s_cnt[k]; mn = s_min[k] < mn ? s_min[k] : mn; mx = s_max[k] > mx ? s_max[k] : mx; }
     ErplAnaRow& o = w->res.row[r];
     o.count = cnt; o.sum = sum; o.vmin = mn; o.vmax = mx; o.m2 = 0.0;
     o.mean = sum / (double)cnt;   // NaN for an empty row; the host reports every double of such a row as NaN
@@ -204,8 +134,8 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_finish_first(const Er
 }
 
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_finish_second(const ErplAnaArgs a, const int nb) {
-  __shared__ double s_wave[kWaves];
-  const double m2 = block_sum(a.work->psum[blockIdx.x], nb, s_wave);
+  double m2 = thread_partials<Add>(a.work->psum[blockIdx.x], nb);
+  block_fold<Add>(m2);
   if (threadIdx.x == 0) a.work->res.row[blockIdx.x].m2 = m2;
 }
 
@@ -240,7 +170,7 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_histogram(const ErplA
     if (i < n) {
       const double v = x[i];
       use = why[i] == 0 && finite_bits(v);
-      key = key_of(v);
+      key = key_of_signed(v);
     }
     const unsigned int digit = (unsigned int)(key >> shift) & (ERPL_ANA_BINS - 1);
     for (int m = 0; m < nlead; ++m) {
@@ -311,15 +241,16 @@ __global__ __launch_bounds__(64 * ERPL_ANA_TARGETS) void erpl_ana_scan(const Erp
 
 }  // namespace
 
-int erpl_launch_analysis(const ErplAnaArgs& a, void* stream) {
+// moments, finish, moments, finish, eight selection passes; with `classify` the outlier filter in front of them and one
+// more workgroup in the first finish, which adds up its counters (without it: n_rows > 0)
+static int launch_passes(const ErplAnaArgs& a, const bool classify, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const int64_t want = (a.n + ERPL_ANA_BLOCK - 1) / ERPL_ANA_BLOCK;
-  const int nb = (int)(want < ERPL_ANA_MAX_BLOCKS ? want : ERPL_ANA_MAX_BLOCKS);
+  const int nb = grid_of(a.n);
   hipError_t e = hipMemsetAsync(&a.work->hist[0][0][0], 0, sizeof(a.work->hist), st);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(erpl_ana_classify, dim3(nb), dim3(ERPL_ANA_BLOCK), 0, st, a);
+  if (classify) hipLaunchKernelGGL(erpl_ana_classify, dim3(nb), dim3(ERPL_ANA_BLOCK), 0, st, a);
   if (a.n_rows > 0) hipLaunchKernelGGL(erpl_ana_moments<false>, dim3(nb, a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a);
-  hipLaunchKernelGGL(erpl_ana_finish_first, dim3(a.n_rows + 1), dim3(ERPL_ANA_BLOCK), 0, st, a, nb);
+  hipLaunchKernelGGL(erpl_ana_finish_first, dim3(a.n_rows + (classify ? 1 : 0)), dim3(ERPL_ANA_BLOCK), 0, st, a, nb);
   if (a.n_rows > 0) {
     hipLaunchKernelGGL(erpl_ana_moments<true>, dim3(nb, a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a);
     hipLaunchKernelGGL(erpl_ana_finish_second, dim3(a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a, nb);
@@ -332,22 +263,6 @@ int erpl_launch_analysis(const ErplAnaArgs& a, void* stream) {
   return (int)hipGetLastError();
 }
 
-int erpl_launch_row_stats(const ErplAnaArgs& a, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t want = (a.n + ERPL_ANA_BLOCK - 1) / ERPL_ANA_BLOCK;
-  const int nb = (int)(want < ERPL_ANA_MAX_BLOCKS ? want : ERPL_ANA_MAX_BLOCKS);
-  if (a.n_rows <= 0) return 0;
-  hipError_t e = hipMemsetAsync(&a.work->hist[0][0][0], 0, sizeof(a.work->hist), st);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(erpl_ana_moments<false>, dim3(nb, a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a);
-  // a.n_rows workgroups: the one behind them, which adds up the classify counters, has nothing to add here
-  hipLaunchKernelGGL(erpl_ana_finish_first, dim3(a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a, nb);
-  hipLaunchKernelGGL(erpl_ana_moments<true>, dim3(nb, a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a);
-  hipLaunchKernelGGL(erpl_ana_finish_second, dim3(a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a, nb);
-  if (a.n_q > 0)
-    for (int shift = 56; shift >= 0; shift -= 8) {
-      hipLaunchKernelGGL(erpl_ana_histogram, dim3(nb, a.n_rows), dim3(ERPL_ANA_BLOCK), 0, st, a, shift);
-      hipLaunchKernelGGL(erpl_ana_scan, dim3(a.n_rows), dim3(64 * ERPL_ANA_TARGETS), 0, st, a, shift);
-    }
-  return (int)hipGetLastError();
-}
+int erpl_launch_analysis(const ErplAnaArgs& a, void* stream) { return launch_passes(a, true, stream); }
+
+int erpl_launch_row_stats(const ErplAnaArgs& a, void* stream) { return a.n_rows > 0 ? launch_passes(a, false, stream) : 0; }

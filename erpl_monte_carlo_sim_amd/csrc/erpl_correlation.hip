@@ -4,8 +4,8 @@
 //
 //   population   one pass over the V rows: a byte per sample (0 = mask byte 0 and every variable finite) and the three
 //                counts (ballots, 64-bit integer atomics)
-//   moments      per variable: sum / min / max over the population, partials per workgroup, fixed tree (the shape of
-//                erpl_ana_moments)
+//   moments      per variable: sum / min / max over the population, partials per workgroup, the fixed order of
+//                erpl_stat_device.h
 //   gram         the hot pass: V (V + 1) / 2 centred cross-product sums.  A workgroup stages a tile of ERPL_CORR_TILE
 //                samples x V centred values in LDS; a thread owns one 4 x 4 block of the upper triangle and every
 //                `slices`-th sample of the tile, 16 running sums in registers, accumulated in sample order; the slices
@@ -13,43 +13,25 @@
 //   ranks        per variable: order-preserving keys (samples outside the population get the largest key), rocPRIM's
 //                radix sort of (key, sample index), then every sorted position finds the ends of its run of equal keys
 //                by galloping + bisection and scatters first + (len + 1) / 2 to its sample
-// Grids and tiles are functions of n and V alone, every floating-point sum has a fixed order: the same bits in every
-// call.  No floating-point atomics.  Compiled with -ffp-contract=off like its siblings: x - mean and the products are
-// rounded as the two-pass NumPy formula rounds them (plain fp64 vector multiplies and adds, no MFMA).
-#include <hip/hip_runtime.h>
-#include <math.h>
+// Grids and tiles are functions of n and V alone, every floating-point sum has a fixed order (the moments: the one of
+// erpl_stat_device.h; the Gram sums: their own, above): the same bits in every call.  No floating-point atomics.
+// Compiled with -ffp-contract=off like its siblings: x - mean and the products are rounded as the two-pass NumPy formula
+// rounds them (plain fp64 vector multiplies and adds, no MFMA).
 #include <string.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "erpl_tables.h"
+#include "erpl_stat_device.h"
 
 namespace {
 
-constexpr int kWaves = ERPL_ANA_BLOCK / 64;
 constexpr int kStride = ERPL_CORR_NB * 4 + 2;   // doubles per staged sample: 16-byte aligned rows, spread over the banks
-typedef unsigned long long u64;
-
-__device__ __forceinline__ bool finite_bits(double v) {
-  return (__double_as_longlong(v) & 0x7ff0000000000000ll) != 0x7ff0000000000000ll;
-}
-// order-preserving map of a finite double onto an unsigned key; -0.0 and +0.0 share one key (they tie)
-__device__ __forceinline__ u64 key_of(double v) {
-  const u64 b = v == 0.0 ? 0ull : (u64)__double_as_longlong(v);
-  return b ^ ((b >> 63) ? ~0ull : (1ull << 63));
-}
-
-int grid_of(int64_t n) {
-  const int64_t want = (n + ERPL_ANA_BLOCK - 1) / ERPL_ANA_BLOCK;
-  return (int)(want < ERPL_ANA_MAX_BLOCKS ? want : ERPL_ANA_MAX_BLOCKS);
-}
 
 // ---- population: the byte of every sample and the three counts
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_population(const ErplCorrArgs a) {
-  __shared__ u64 s_cnt[kWaves][3];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
-  u64 in = 0ull, masked = 0ull, bad = 0ull;   // uniform over the wave
+  u64 cnt[3] = {0ull, 0ull, 0ull};   // in, masked, non-finite: uniform over the wave
   for (int64_t base = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + wave * 64; base < n; base += stride) {
     const int64_t i = base + lane;
     int why = -1;
@@ -60,23 +42,16 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_population(const Erp
           if (!finite_bits(a.var[v][i])) why = 2;
       a.pop[i] = (uint8_t)why;
     }
-    in += __popcll(__ballot(why == 0));
-    masked += __popcll(__ballot(why == 1));
-    bad += __popcll(__ballot(why == 2));
+#pragma unroll
+    for (int k = 0; k < 3; ++k) cnt[k] += __popcll(__ballot(why == k));
   }
-  if (lane == 0) { s_cnt[wave][0] = in; s_cnt[wave][1] = masked; s_cnt[wave][2] = bad; }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    u64 s = 0ull;
-    for (int w = 0; w < kWaves; ++w) s += s_cnt[w][threadIdx.x];
-    if (s) atomicAdd(&a.work->out.counter[threadIdx.x], s);
-  }
+  const u64 s = counters_fold(cnt);
+  if (threadIdx.x < 3 && s) atomicAdd(&a.work->out.counter[threadIdx.x], s);
 }
 
 // ---- first moments of variable blockIdx.y over the population
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_moments(const ErplCorrArgs a) {
-  __shared__ double s_sum[kWaves], s_min[kWaves], s_max[kWaves];
-  const int v = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int v = blockIdx.y;
   const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
   const double* __restrict__ x = a.var[v];
   const uint8_t* __restrict__ pop = a.pop;
@@ -89,16 +64,8 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_moments(const ErplCo
       mx = val > mx ? val : mx;
     }
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    sum += __shfl_down(sum, off);
-    const double m0 = __shfl_down(mn, off), m1 = __shfl_down(mx, off);
-    mn = m0 < mn ? m0 : mn;
-    mx = m1 > mx ? m1 : mx;
-  }
-  if (lane == 0) { s_sum[wave] = sum; s_min[wave] = mn; s_max[wave] = mx; }
-  __syncthreads();
+  block_fold<Add, Min, Max>(sum, mn, mx);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < kWaves; ++w) { sum += s_sum[w]; mn = s_min[w] < mn ? s_min[w] : mn; mx = s_max[w] > mx ? s_max[w] : mx; }
     a.work->psum[v][blockIdx.x] = sum;
     a.work->pmin[v][blockIdx.x] = mn;
     a.work->pmax[v][blockIdx.x] = mx;
@@ -106,29 +73,12 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_moments(const ErplCo
 }
 
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_finish_moments(const ErplCorrArgs a, const int nb) {
-  __shared__ double s_sum[kWaves], s_min[kWaves], s_max[kWaves];
   const int v = blockIdx.x;
   ErplCorrWork* w = a.work;
-  constexpr int per = ERPL_ANA_MAX_BLOCKS / ERPL_ANA_BLOCK;
-  double sum = 0.0, mn = INFINITY, mx = -INFINITY;
-  for (int k = 0; k < per; ++k) {
-    const int j = threadIdx.x * per + k;
-    if (j < nb) {
-      sum += w->psum[v][j];
-      mn = w->pmin[v][j] < mn ? w->pmin[v][j] : mn;
-      mx = w->pmax[v][j] > mx ? w->pmax[v][j] : mx;
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    sum += __shfl_down(sum, off);
-    const double m0 = __shfl_down(mn, off), m1 = __shfl_down(mx, off);
-    mn = m0 < mn ? m0 : mn;
-    mx = m1 > mx ? m1 : mx;
-  }
-  if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = sum; s_min[threadIdx.x >> 6] = mn; s_max[threadIdx.x >> 6] = mx; }
-  __syncthreads();
+  double sum = thread_partials<Add>(w->psum[v], nb);
+  double mn = thread_partials<Min>(w->pmin[v], nb), mx = thread_partials<Max>(w->pmax[v], nb);
+  block_fold<Add, Min, Max>(sum, mn, mx);
   if (threadIdx.x == 0) {
-    for (int k = 1; k < kWaves; ++k) { sum += s_sum[k]; mn = s_min[k] < mn ? s_min[k] : mn; mx = s_max[k] > mx ? s_max[k] : mx; }
     const double c = (double)w->out.counter[0];
     w->out.mean[v] = sum / c;   // NaN for an empty population; the host reports every double of it as NaN
     w->out.vmin[v] = mn;
@@ -211,7 +161,7 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_keys(const ErplCorrA
                                                                  u64* __restrict__ keys, uint32_t* __restrict__ idx) {
   const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
   for (int64_t i = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + threadIdx.x; i < n; i += stride) {
-    keys[i] = a.pop[i] == 0 ? key_of(x[i]) : ~0ull;   // no finite double maps to the largest key
+    keys[i] = a.pop[i] == 0 ? key_of_tied(x[i]) : ~0ull;   // no finite double maps to the largest key
     idx[i] = (uint32_t)i;
   }
 }

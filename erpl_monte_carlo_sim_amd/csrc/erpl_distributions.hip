@@ -9,47 +9,12 @@
 //   hist2d     the same per axis; an LDS tile for grids of up to ERPL_DIST_TILE_CELLS cells, global integer atomics above
 //   dispersion two moment passes over two rows (mean, then the sums about it), then one pass that counts the content of
 //              every confidence ellipse with ballots and writes the miss distance the selection of erpl_analysis.hip reads
-// Sums are accumulated per thread in index order and reduced in a fixed tree; integer adds commute: the same bits in
-// every call.  No floating-point atomics.  Compiled with -ffp-contract=off: the guess, (x - mean)^2 and dx*dx + dy*dy are
-// rounded as NumPy rounds them.
-#include <hip/hip_runtime.h>
-#include <math.h>
-
-#include "erpl_tables.h"
+// Sums are accumulated per thread in index order and reduced in the fixed order of erpl_stat_device.h; integer adds commute:
+// the same bits in every call.  No floating-point atomics.  Compiled with -ffp-contract=off: the guess, (x - mean)^2 and
+// dx*dx + dy*dy are rounded as NumPy rounds them.
+#include "erpl_stat_device.h"
 
 namespace {
-
-constexpr int kWaves = ERPL_ANA_BLOCK / 64;
-typedef unsigned long long u64;
-
-__device__ __forceinline__ bool finite_bits(double v) {
-  return (__double_as_longlong(v) & 0x7ff0000000000000ll) != 0x7ff0000000000000ll;
-}
-
-// Sum of the first `nb` doubles of p by one workgroup of ERPL_ANA_BLOCK threads, in the shape of erpl_analysis.hip: thread t
-// adds its four neighbours in index order, then the fixed tree.  Valid in thread 0.
-__device__ double block_sum(const double* p, int nb, double* s_wave) {
-  constexpr int per = ERPL_ANA_MAX_BLOCKS / ERPL_ANA_BLOCK;
-  double s = 0.0;
-  for (int k = 0; k < per; ++k) { const int j = threadIdx.x * per + k; if (j < nb) s += p[j]; }
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-  __syncthreads();   // s_wave may still be read from an earlier call
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) for (int w = 1; w < kWaves; ++w) s += s_wave[w];
-  return s;
-}
-__device__ u64 block_count(const u64* p, int nb, int stride, u64* s_wave) {
-  constexpr int per = ERPL_ANA_MAX_BLOCKS / ERPL_ANA_BLOCK;
-  u64 s = 0ull;
-  for (int k = 0; k < per; ++k) { const int j = threadIdx.x * per + k; if (j < nb) s += p[(size_t)j * stride]; }
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) for (int w = 1; w < kWaves; ++w) s += s_wave[w];
-  return s;
-}
 
 // The bin of x in [lo, hi] among `bins` equal-width bins with edge values e[0..bins], as np.histogram finds it
 // (_histograms_impl.py: f_indices, then one step down and one step up against the edges).  The clamps cannot act for x in
@@ -64,8 +29,7 @@ __device__ __forceinline__ int bin_of(double x, double lo, double hi, int bins, 
 
 // ---- range: min / max of row rows[blockIdx.y] over the samples that count
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dist_range(const ErplDistArgs a) {
-  __shared__ double s_min[kWaves], s_max[kWaves];
-  const int j = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int j = blockIdx.y;
   if (!a.automatic[j]) return;
   const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
   const double* __restrict__ x = a.summary + (int64_t)a.rows[j] * n;
@@ -78,43 +42,19 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dist_range(const ErplDist
     if (y) use = use && finite_bits(y[i]);
     if (use) { mn = v < mn ? v : mn; mx = v > mx ? v : mx; }
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    const double m0 = __shfl_down(mn, off), m1 = __shfl_down(mx, off);
-    mn = m0 < mn ? m0 : mn;
-    mx = m1 > mx ? m1 : mx;
-  }
-  if (lane == 0) { s_min[wave] = mn; s_max[wave] = mx; }
-  __syncthreads();
+  block_fold<Min, Max>(mn, mx);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < kWaves; ++w) { mn = s_min[w] < mn ? s_min[w] : mn; mx = s_max[w] > mx ? s_max[w] : mx; }
     a.work->pmin[j][blockIdx.x] = mn;
     a.work->pmax[j][blockIdx.x] = mx;
   }
 }
 
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dist_finish_range(const ErplDistArgs a, const int nb) {
-  __shared__ double s_min[kWaves], s_max[kWaves];
   const int j = blockIdx.x;
   if (!a.automatic[j]) return;
-  constexpr int per = ERPL_ANA_MAX_BLOCKS / ERPL_ANA_BLOCK;
-  double mn = INFINITY, mx = -INFINITY;
-  for (int k = 0; k < per; ++k) {
-    const int b = threadIdx.x * per + k;
-    if (b < nb) {
-      const double p0 = a.work->pmin[j][b], p1 = a.work->pmax[j][b];
-      mn = p0 < mn ? p0 : mn;
-      mx = p1 > mx ? p1 : mx;
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    const double m0 = __shfl_down(mn, off), m1 = __shfl_down(mx, off);
-    mn = m0 < mn ? m0 : mn;
-    mx = m1 > mx ? m1 : mx;
-  }
-  if ((threadIdx.x & 63) == 0) { s_min[threadIdx.x >> 6] = mn; s_max[threadIdx.x >> 6] = mx; }
-  __syncthreads();
+  double mn = thread_partials<Min>(a.work->pmin[j], nb), mx = thread_partials<Max>(a.work->pmax[j], nb);
+  block_fold<Min, Max>(mn, mx);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < kWaves; ++w) { mn = s_min[w] < mn ? s_min[w] : mn; mx = s_max[w] > mx ? s_max[w] : mx; }
     a.work->range.lo[j] = mn;   // +inf / -inf: nothing counted
     a.work->range.hi[j] = mx;
   }
@@ -124,7 +64,6 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dist_finish_range(const E
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dist_hist(const ErplDistArgs a) {
   __shared__ double s_edge[ERPL_HIST_MAX_BINS + 1];
   __shared__ unsigned int s_cnt[ERPL_HIST_MAX_BINS];
-  __shared__ u64 s_tot[kWaves][3];
   const int j = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int bins = a.bins[j];
   const double lo = a.lo[j], hi = a.hi[j];
@@ -134,7 +73,7 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dist_hist(const ErplDistA
   for (int k = threadIdx.x; k <= bins; k += ERPL_ANA_BLOCK) s_edge[k] = a.work->edges[j][k];
   for (int k = threadIdx.x; k < bins; k += ERPL_ANA_BLOCK) s_cnt[k] = 0u;
   __syncthreads();
-  u64 counted = 0ull, below = 0ull, above = 0ull;   // uniform over the wave
+  u64 tot[3] = {0ull, 0ull, 0ull};   // counted, below, above: uniform over the wave
   for (int64_t base = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + wave * 64; base < n; base += stride) {
     const int64_t i = base + lane;
     bool use = false;
@@ -144,9 +83,9 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dist_hist(const ErplDistA
       use = finite_bits(v) && (!mask || mask[i] == 0);
     }
     const bool lt = use && v < lo, gt = use && v > hi, hit = use && !lt && !gt;
-    counted += __popcll(__ballot(use));
-    below += __popcll(__ballot(lt));
-    above += __popcll(__ballot(gt));
+    tot[0] += __popcll(__ballot(use));
+    tot[1] += __popcll(__ballot(lt));
+    tot[2] += __popcll(__ballot(gt));
     const u64 m = __ballot(hit);
     if (m == 0ull) continue;
     const int k = hit ? bin_of(v, lo, hi, bins, s_edge) : 0;
@@ -159,16 +98,13 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dist_hist(const ErplDistA
       atomicAdd(&s_cnt[k], 1u);
     }
   }
-  if (lane == 0) { s_tot[wave][0] = counted; s_tot[wave][1] = below; s_tot[wave][2] = above; }
-  __syncthreads();
+  const u64 s = counters_fold(tot);   // behind its barrier s_cnt is complete
   ErplDistHist& h = a.work->hist;
   for (int k = threadIdx.x; k < bins; k += ERPL_ANA_BLOCK) {
     const unsigned int c = s_cnt[k];
     if (c) atomicAdd(&h.bins[j][k], (u64)c);
   }
   if (threadIdx.x < 3) {
-    u64 s = 0ull;
-    for (int w = 0; w < kWaves; ++w) s += s_tot[w][threadIdx.x];
     u64* dst = threadIdx.x == 0 ? &h.counted[j] : (threadIdx.x == 1 ? &h.below[j] : &h.above[j]);
     if (s) atomicAdd(dst, s);
   }
@@ -179,7 +115,6 @@ template <bool TILE>
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dist_hist2d(const ErplDistArgs a) {
   __shared__ double s_ex[ERPL_HIST2D_MAX_BINS + 1], s_ey[ERPL_HIST2D_MAX_BINS + 1];
   __shared__ unsigned int s_cnt[TILE ? ERPL_DIST_TILE_CELLS : 1];
-  __shared__ u64 s_tot[kWaves][2];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int bx = a.bins[0], by = a.bins[1], cells = bx * by;
   const double lox = a.lo[0], hix = a.hi[0], loy = a.lo[1], hiy = a.hi[1];
@@ -191,7 +126,7 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dist_hist2d(const ErplDis
   for (int k = threadIdx.x; k <= by; k += ERPL_ANA_BLOCK) s_ey[k] = a.work->edges[1][k];
   if (TILE) for (int k = threadIdx.x; k < cells; k += ERPL_ANA_BLOCK) s_cnt[k] = 0u;
   __syncthreads();
-  u64 counted = 0ull, outside = 0ull;
+  u64 tot[2] = {0ull, 0ull};   // counted, outside: uniform over the wave
   for (int64_t base = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + wave * 64; base < n; base += stride) {
     const int64_t i = base + lane;
     bool use = false;
@@ -201,8 +136,8 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dist_hist2d(const ErplDis
       use = finite_bits(vx) && finite_bits(vy) && (!mask || mask[i] == 0);
     }
     const bool hit = use && vx >= lox && vx <= hix && vy >= loy && vy <= hiy;
-    counted += __popcll(__ballot(use));
-    outside += __popcll(__ballot(use && !hit));
+    tot[0] += __popcll(__ballot(use));
+    tot[1] += __popcll(__ballot(use && !hit));
     const u64 m = __ballot(hit);
     if (m == 0ull) continue;
     const int c = hit ? bin_of(vx, lox, hix, bx, s_ex) * by + bin_of(vy, loy, hiy, by, s_ey) : 0;
@@ -218,27 +153,19 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dist_hist2d(const ErplDis
       else atomicAdd(&a.work->cells[c], 1ull);
     }
   }
-  if (lane == 0) { s_tot[wave][0] = counted; s_tot[wave][1] = outside; }
-  __syncthreads();
+  const u64 s = counters_fold(tot);   // behind its barrier s_cnt is complete
   if (TILE)
     for (int k = threadIdx.x; k < cells; k += ERPL_ANA_BLOCK) {
       const unsigned int c = s_cnt[k];
       if (c) atomicAdd(&a.work->cells[k], (u64)c);
     }
-  if (threadIdx.x < 2) {
-    u64 s = 0ull;
-    for (int w = 0; w < kWaves; ++w) s += s_tot[w][threadIdx.x];
-    if (s) atomicAdd(threadIdx.x == 0 ? &a.work->counted2 : &a.work->outside2, s);
-  }
+  if (threadIdx.x < 2 && s) atomicAdd(threadIdx.x == 0 ? &a.work->counted2 : &a.work->outside2, s);
 }
 
 // ---- dispersion moments.  SECOND = false: sums of x and y and the count over the samples that count; SECOND = true:
 // sums of dx dx, dx dy, dy dy about the mean of the first pass.
 template <bool SECOND>
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_disp_moments(const ErplDispArgs a) {
-  __shared__ double s_sum[3][kWaves];
-  __shared__ u64 s_cnt[kWaves];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
   const double* __restrict__ x = a.summary + (int64_t)a.row_x * n;
   const double* __restrict__ y = a.summary + (int64_t)a.row_y * n;
@@ -257,16 +184,9 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_disp_moments(const ErplDi
       }
     }
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    s0 += __shfl_down(s0, off);
-    s1 += __shfl_down(s1, off);
-    if (SECOND) s2 += __shfl_down(s2, off);
-    else cnt += __shfl_down(cnt, off);
-  }
-  if (lane == 0) { s_sum[0][wave] = s0; s_sum[1][wave] = s1; s_sum[2][wave] = s2; s_cnt[wave] = cnt; }
-  __syncthreads();
+  if (SECOND) block_fold<Add, Add, Add>(s0, s1, s2);
+  else block_fold<Add, Add, Add>(s0, s1, cnt);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < kWaves; ++w) { s0 += s_sum[0][w]; s1 += s_sum[1][w]; s2 += s_sum[2][w]; cnt += s_cnt[w]; }
     a.work->dsum[0][blockIdx.x] = s0;
     a.work->dsum[1][blockIdx.x] = s1;
     if (SECOND) a.work->dsum[2][blockIdx.x] = s2;
@@ -276,13 +196,12 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_disp_moments(const ErplDi
 
 template <bool SECOND>
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_disp_finish(const ErplDispArgs a, const int nb) {
-  __shared__ double s_wave[kWaves];
-  __shared__ u64 s_cw[kWaves];
   ErplDistWork* w = a.work;
-  const double s0 = block_sum(w->dsum[0], nb, s_wave);
-  const double s1 = block_sum(w->dsum[1], nb, s_wave);
-  const double s2 = SECOND ? block_sum(w->dsum[2], nb, s_wave) : 0.0;
-  const u64 cnt = SECOND ? 0ull : block_count(w->dcnt, nb, 1, s_cw);
+  double s0 = thread_partials<Add>(w->dsum[0], nb), s1 = thread_partials<Add>(w->dsum[1], nb);
+  double s2 = SECOND ? thread_partials<Add>(w->dsum[2], nb) : 0.0;
+  u64 cnt = SECOND ? 0ull : thread_partials<Add>(w->dcnt, nb);
+  if (SECOND) block_fold<Add, Add, Add>(s0, s1, s2);
+  else block_fold<Add, Add, Add>(s0, s1, cnt);
   if (threadIdx.x != 0) return;
   ErplDistMoments& m = w->mom;
   if (!SECOND) {
@@ -302,7 +221,6 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_disp_finish(const ErplDis
 // ---- the content of every confidence ellipse (ballots: the counts of a wave are uniform; the workgroup's go to its own
 // slot of work->ipart) and the miss distance of every sample
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_disp_inside(const ErplDispArgs a) {
-  __shared__ u64 s_in[kWaves][ERPL_DISP_MAX_LEVELS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
   const double* __restrict__ x = a.summary + (int64_t)a.row_x * n;
@@ -337,29 +255,16 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_disp_inside(const ErplDis
         if (k < a.n_levels) in[k] += __popcll(__ballot(use && d2 <= a.k2[k]));
     }
   }
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < ERPL_DISP_MAX_LEVELS; ++k) s_in[wave][k] = in[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < ERPL_DISP_MAX_LEVELS) {
-    u64 s = 0ull;
-    for (int w = 0; w < kWaves; ++w) s += s_in[w][threadIdx.x];
-    a.work->ipart[blockIdx.x][threadIdx.x] = s;
-  }
+  const u64 s = counters_fold(in);
+  if (threadIdx.x < ERPL_DISP_MAX_LEVELS) a.work->ipart[blockIdx.x][threadIdx.x] = s;
 }
 
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_disp_finish_inside(const ErplDispArgs a, const int nb) {
-  __shared__ u64 s_cw[kWaves];
   for (int k = 0; k < ERPL_DISP_MAX_LEVELS; ++k) {
-    const u64 s = block_count(&a.work->ipart[0][k], nb, ERPL_DISP_MAX_LEVELS, s_cw);
+    u64 s = thread_partials<Add>(&a.work->ipart[0][k], nb, ERPL_DISP_MAX_LEVELS);
+    block_fold_again<Add>(s);   // the same scratch in every round
     if (threadIdx.x == 0) a.work->mom.inside[k] = s;
   }
-}
-
-int grid_of(int64_t n) {
-  const int64_t want = (n + ERPL_ANA_BLOCK - 1) / ERPL_ANA_BLOCK;
-  return (int)(want < ERPL_ANA_MAX_BLOCKS ? want : ERPL_ANA_MAX_BLOCKS);
 }
 
 }  // namespace

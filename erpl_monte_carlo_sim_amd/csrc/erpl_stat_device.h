@@ -1,0 +1,146 @@
+// erpl_stat_device.h — what the statistics units (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip) share:
+// the grid of their streaming passes, the order-preserving keys and THE fixed-order reduction.  Internal: never installed.
+//
+// The order is the contract: the last bit of every sum and the sign of a zero minimum depend on it, and "the same bits in
+// every call" rests on it.  It is defined here and nowhere else:
+//   1. a thread accumulates its own values in index order (the streaming loops of the units; thread_partials below);
+//   2. a wave folds with a __shfl_down tree over the offsets 32, 16, .. 1: lane l takes lane l + off as the incoming value;
+//   3. lane 0 of every wave parks its value in LDS;
+//   4. thread 0 folds the waves 1, 2, .. onto its own (wave 0), in that order.  The result is valid in thread 0 only.
+// The partials of the workgroups are folded the same way by one workgroup: thread t takes the partials t * kPer ..
+// t * kPer + kPer - 1 in index order, then steps 2 - 4.  In every step the value a thread holds is the running one.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "erpl_tables.h"
+
+namespace {
+
+typedef unsigned long long u64;
+constexpr int kWaves = ERPL_ANA_BLOCK / 64;
+constexpr int kPer = ERPL_ANA_MAX_BLOCKS / ERPL_ANA_BLOCK;   // partials per thread of a finishing workgroup
+
+// the grid of every streaming pass: a function of n alone
+inline int grid_of(int64_t n) {
+  const int64_t want = (n + ERPL_ANA_BLOCK - 1) / ERPL_ANA_BLOCK;
+  return (int)(want < ERPL_ANA_MAX_BLOCKS ? want : ERPL_ANA_MAX_BLOCKS);
+}
+
+__device__ __forceinline__ bool finite_bits(double v) {
+  return (__double_as_longlong(v) & 0x7ff0000000000000ll) != 0x7ff0000000000000ll;
+}
+
+// Two order-preserving maps of a finite double onto an unsigned key.  They differ in the zeros alone:
+//   key_of_signed   -0.0 sorts just below +0.0.  The selection of erpl_analysis.hip returns a value of the row, sign of a
+//                   zero included (double_of_key in erpl_stats_api.hip inverts the map).
+//   key_of_tied     -0.0 and +0.0 share one key.  The ranks of erpl_correlation.hip tie them, as scipy.stats.rankdata does.
+__device__ __forceinline__ u64 key_of_signed(double v) {
+  const u64 b = (u64)__double_as_longlong(v);
+  return b ^ ((b >> 63) ? ~0ull : (1ull << 63));
+}
+__device__ __forceinline__ u64 key_of_tied(double v) { return key_of_signed(v == 0.0 ? 0.0 : v); }
+
+// ---- the operations of a fold: of(running, incoming), and the value that leaves every other one as it is
+struct Add {
+  template <class T> __device__ static T of(T run, T in) { return run + in; }
+  template <class T> __device__ static T none() { return (T)0; }
+};
+struct Min {   // of two equal values (+0.0, -0.0) the running one stays
+  template <class T> __device__ static T of(T run, T in) { return in < run ? in : run; }
+  template <class T> __device__ static T none() {
+    static_assert(std::is_floating_point<T>::value, "an extreme of floating-point values: the identity is an infinity");
+    return (T)INFINITY;
+  }
+};
+struct Max {
+  template <class T> __device__ static T of(T run, T in) { return in > run ? in : run; }
+  template <class T> __device__ static T none() {
+    static_assert(std::is_floating_point<T>::value, "an extreme of floating-point values: the identity is an infinity");
+    return (T)-INFINITY;
+  }
+};
+
+// The folds take several values at once, each with its own operation: block_fold<Add, Min>(sum, mn).  The values are
+// independent, so their shuffles interleave and one pair of barriers serves them all.  Every value is a double or a u64;
+// LDS holds it as its 64 bits.
+template <class T>
+__device__ __forceinline__ u64 bits_of(T v) {
+  static_assert(sizeof(T) == sizeof(u64), "a double or a u64");
+  u64 b;
+  __builtin_memcpy(&b, &v, sizeof(b));
+  return b;
+}
+template <class T>
+__device__ __forceinline__ T from_bits(u64 b) {
+  T v;
+  __builtin_memcpy(&v, &b, sizeof(v));
+  return v;
+}
+
+// step 2.  Valid in lane 0.
+template <class... Op, class... T>
+__device__ __forceinline__ void wave_fold(T&... v) {
+  for (int off = 32; off > 0; off >>= 1) ((v = Op::of(v, __shfl_down(v, off))), ...);
+}
+
+// steps 2 - 4 over a workgroup of ERPL_ANA_BLOCK threads, all of which call it.  Valid in thread 0.  The LDS scratch
+// belongs to the combination of operations and types.  AGAIN: a kernel that calls one combination a second time passes
+// true from the second call on, and the scratch is guarded against the reads of the call before; a first call needs no
+// guard and pays for none.
+// Two unguarded calls of one combination in one kernel are a data race on s_wave: the second has to be block_fold_again.
+template <bool AGAIN, class... Op, class... T>
+__device__ __forceinline__ void block_fold_impl(T&... v) {
+  static_assert(sizeof...(Op) == sizeof...(T), "one operation per value");
+  __shared__ u64 s_wave[kWaves][sizeof...(T)];
+  wave_fold<Op...>(v...);
+  if (AGAIN) __syncthreads();   // s_wave may still be read from the call before
+  if ((threadIdx.x & 63) == 0) {
+    u64* slot = s_wave[threadIdx.x >> 6];
+    ((*slot++ = bits_of(v)), ...);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < kWaves; ++w) {
+      const u64* slot = s_wave[w];
+      ((v = Op::of(v, from_bits<T>(*slot++))), ...);
+    }
+}
+template <class... Op, class... T>
+__device__ __forceinline__ void block_fold(T&... v) { block_fold_impl<false, Op...>(v...); }
+template <class... Op, class... T>
+__device__ __forceinline__ void block_fold_again(T&... v) { block_fold_impl<true, Op...>(v...); }
+
+// step 1 of a finishing workgroup: what thread t makes of the partials t * kPer .. t * kPer + kPer - 1 among the first
+// nb <= ERPL_ANA_MAX_BLOCKS of p[0], p[stride], ..  block_fold does the rest.
+template <class Op, class T>
+__device__ __forceinline__ T thread_partials(const T* p, int nb, int stride = 1) {
+  T v = Op::template none<T>();
+  for (int k = 0; k < kPer; ++k) {
+    const int j = threadIdx.x * kPer + k;
+    if (j < nb) v = Op::of(v, p[(size_t)j * stride]);
+  }
+  return v;
+}
+
+// K counters a wave holds uniformly (sums of ballot counts): thread k < K returns counter k added over the waves, every
+// other thread 0.  Integer adds commute; the barrier inside also orders the LDS traffic of the caller's loop before what
+// follows the call.
+template <int K>
+__device__ __forceinline__ u64 counters_fold(const u64 (&cnt)[K]) {
+  __shared__ u64 s_cnt[kWaves][K];
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) s_cnt[threadIdx.x >> 6][k] = cnt[k];
+  }
+  __syncthreads();
+  u64 s = 0ull;
+  if (threadIdx.x < K)
+    for (int w = 0; w < kWaves; ++w) s += s_cnt[w][threadIdx.x];
+  return s;
+}
+
+}  // namespace

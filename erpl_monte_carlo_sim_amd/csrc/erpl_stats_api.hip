@@ -38,6 +38,7 @@ int check_quantiles(const double* q, int n_q) {
   return ERPL_OK;
 }
 
+// the inverse of key_of_signed (erpl_stat_device.h)
 double double_of_key(unsigned long long k) {
   const unsigned long long b = k ^ ((k >> 63) ? (1ull << 63) : ~0ull);
   double v;
