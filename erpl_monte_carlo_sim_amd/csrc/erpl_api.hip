@@ -391,7 +391,10 @@ int enqueue_batch(erpl_ctx* c, int lane, const erpl_batch* b, const erpl_out* o,
   //   11.4 -> 25.5 ms), so none is created: the sweeps of the fp64 throughput build follow the main launch on the
   //   lane's own stream, with two or more batches in flight to fill the SIMDs beside them (bench shard, f64_fast,
   //   three deep: 30.3 -> 28.2 ms per pass, lane utilisation 0.75 -> 0.98; with the capped hand-over sweep below
-  //   26.5).
+  //   26.5).  The lane's cycle there: main launch 40 ms, the two sweeps 3 + 12, the hand-over
+  //   sweep 8.  Raising the issue priority of the sweeps' waves (s_setprio 1 / 3) and capping the hand-over sweep's
+  //   grid at 1/2 .. 1/8 shortened those dispatches a little and the pass not at all (26.3 -> 26.3 .. 27.0 ms, parent
+  //   spread 0.9; profiles/tail_ab.json): the other lanes' waves lose what the tail gains.  Neither is in here.
   // erpl_mc_run_batch runs on the caller's one stream with nothing beside it, where a batch is bound by its own longest
   // trajectory and the hand-overs only lengthen that (32.5 -> 36.1 ms): off.  Step chunks already re-pack every
   // lane, and chunk-parked records would be adopted straight back (measured 8x slower): exclusive.
@@ -406,7 +409,11 @@ int enqueue_batch(erpl_ctx* c, int lane, const erpl_batch* b, const erpl_out* o,
   }
   a.adopt_lanes = (o->n_traj == 0 && a.chunk_steps == 0) ? adopt : 0;
   a.adopt_spin = c->adopt_spin;
-  if (a.adopt_lanes > 0 && n_phases < 3) n_phases = 3;
+  // two sweeps behind the main launch, the first with adoption still on; ONE where they share the lane's only stream and
+  // the lane's next batch waits behind them (bench shard at four queues, five rounds: 26.36 / 26.66 / 27.12 ms per pass
+  // min / median / max with two, 25.10 / 25.90 / 25.96 with one - DESIGN.md section 3.2)
+  const int adopt_phases = (ticket > 0 && !sweep) ? 2 : 3;
+  if (a.adopt_lanes > 0 && n_phases < adopt_phases) n_phases = adopt_phases;
   void** ev = c->profiling ? (void**)&c->ev[3 * (c->profiled_runs % ERPL_PROFILE_RING)] : nullptr;
   // with lane adoption the launches behind the main one hold the batch's few longest trajectories: they go to the
   // lane's sweep stream, and the lane's next batch (other set) follows the main launch at once

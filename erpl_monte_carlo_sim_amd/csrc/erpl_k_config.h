@@ -65,6 +65,8 @@
 //     trajectory capture the gate's own runs.  Where the sweep shares its stream with the lane's next batch (submitted
 //     batches without a sweep stream: the HIP default of four hardware queues) the wait would hold that batch back
 //     while the other lanes keep every SIMD full: there the capped copy runs.  Same source, same flags, same bits.
+//     It runs the full grid (n / 64 workgroups) at the default wave priority there too: 1/2, 1/4 and 1/8 of the grid
+//     with refill from the hand-over queue, and s_setprio 1 / 3 for its waves, measured no gain.
 // [4] The register-capped fp32 build keeps the lane's clock (a double) in LDS through the RK4 loop: the compiler
 //     spilled exactly that pair to scratch and re-read it at every stage, and a scratch load is a vector-memory
 //     load - it shares the in-order counter with the table reloads, so every stage start waited for whatever

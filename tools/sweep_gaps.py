@@ -6,7 +6,13 @@ starts - with one stream per lane (four hardware queues) that is the time the la
 
     tools/sweep_gaps.py <dir with *kernel_trace.csv> <out.json> [warmup passes to skip]
 
-Streams are told apart by the trace's Stream_Id column where it has one, by Queue_Id otherwise."""
+Streams are told apart by the trace's Stream_Id column where it has one, by Queue_Id otherwise.
+
+`lane_cycles` splits every stream's dispatches into batches (one per rail kernel) and reports, for the batches that carry
+the whole sequence rail, main launch, adoption sweeps, hand-over sweep on ONE stream (one stream per lane), the duration
+of each launch, the tail (end of the main launch to end of the hand-over sweep), the gap to the lane's next rail kernel
+and the lane cycle (rail start to next rail start).  A kernel trace has one interval per dispatch: when the last working
+wave of a dispatch ended is not in it."""
 import csv
 import glob
 import json
@@ -21,7 +27,8 @@ def load(dirname):
         for r in csv.DictReader(open(f)):
             key = r.get("Stream_Id") if r.get("Stream_Id") not in (None, "", "0") else r.get("Queue_Id")
             rows.append({"s": int(r["Start_Timestamp"]), "e": int(r["End_Timestamp"]), "name": r["Kernel_Name"], "key": key,
-                         "vgpr": int(r.get("VGPR_Count") or r.get("Arch_VGPR_Count") or 0), "scratch": int(r.get("Scratch_Size") or 0)})
+                         "vgpr": int(r.get("VGPR_Count") or r.get("Arch_VGPR_Count") or 0), "scratch": int(r.get("Scratch_Size") or 0),
+                         "grid": int(r.get("Grid_Size_X") or r.get("Grid_Size") or 0)})
     rows.sort(key=lambda r: r["s"])
     return rows
 
@@ -65,11 +72,35 @@ def main():
                 gap_end.append((nxt["s"] - r["e"]) / 1e6)
         shared += any(is_sweep(r["name"]) for r in rs) and any("erpl_rail_f64f" in r["name"] for r in rs)
     sweeps = [r for r in leg if is_sweep(r["name"])]
+    cyc = {k: [] for k in ("rail_ms", "main_ms", "adoption_sweep_1_ms", "adoption_sweep_2_ms", "handover_sweep_ms", "tail_ms",
+                           "handover_end_to_next_rail_start_ms", "lane_cycle_ms")}
+    grids = set()
+    for key, rs in by_key.items():
+        starts = [i for i, r in enumerate(rs) if "erpl_rail_f64f" in r["name"]]
+        for a, b in zip(starts, starts[1:] + [len(rs)]):
+            batch = [r for r in rs[a:b] if "erpl_flight_" in r["name"] or "erpl_rail_" in r["name"]]
+            fl = [r for r in batch[1:] if not is_sweep(r["name"])]
+            ho = [r for r in batch[1:] if is_sweep(r["name"])]
+            if len(ho) != 1 or not fl:
+                continue            # the sweeps of this batch ran on another stream
+            ms = lambda r: (r["e"] - r["s"]) / 1e6
+            cyc["rail_ms"].append(ms(batch[0]))
+            cyc["main_ms"].append(ms(fl[0]))
+            for j, name in ((1, "adoption_sweep_1_ms"), (2, "adoption_sweep_2_ms")):
+                if len(fl) > j:
+                    cyc[name].append(ms(fl[j]))
+            cyc["handover_sweep_ms"].append(ms(ho[0]))
+            cyc["tail_ms"].append((ho[0]["e"] - fl[0]["e"]) / 1e6)
+            grids.add(ho[0]["grid"])
+            if b < len(rs):
+                cyc["handover_end_to_next_rail_start_ms"].append((rs[b]["s"] - ho[0]["e"]) / 1e6)
+                cyc["lane_cycle_ms"].append((rs[b]["s"] - batch[0]["s"]) / 1e6)
     out = {"streams_with_dispatches": len(by_key), "streams_carrying_both_rail_and_sweep": int(shared),
            "sweep_registers": sorted({r["vgpr"] for r in sweeps}), "sweep_scratch_bytes": sorted({r["scratch"] for r in sweeps}),
            "sweep_dispatch_ms": stats(dur),
            "sweep_start_to_next_rail_start_on_its_stream_ms": stats(gap_start),
            "sweep_end_to_next_rail_start_on_its_stream_ms": stats(gap_end),
+           "lane_cycles": dict({k: stats(v) for k, v in cyc.items()}, handover_sweep_grid_threads=sorted(grids)),
            "note": "timed passes of the f64_fast leg only (the first %d passes are warm-up); a sweep on a stream of its own has its "
                    "next rail kernel two batches later or none at all" % skip}
     json.dump(out, open(out_path, "w"), indent=1)
