@@ -205,7 +205,7 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_legacy_random_streams", "erpl_mc_legacy_wind_profiles", "erpl_mc_set_waves_per_simd",
            "erpl_mc_set_overlap", "erpl_mc_submit_batch", "erpl_mc_wait_batch", "erpl_mc_synchronize",
            "erpl_mc_debug_eval", "erpl_mc_synth_wind", "erpl_mc_set_adopt", "erpl_mc_get_overlap",
-           "erpl_mc_check_batch", "erpl_mc_set_adopt_spin", "erpl_mc_set_short_flight_overlap",
+           "erpl_mc_check_batch", "erpl_mc_set_adopt_spin", "erpl_mc_set_sweep_pool", "erpl_mc_set_short_flight_overlap",
            "erpl_mc_analysis_defaults", "erpl_mc_analyze",
            "erpl_mc_histogram_defaults", "erpl_mc_histogram", "erpl_mc_histogram_xy",
            "erpl_mc_dispersion_defaults", "erpl_mc_dispersion",
@@ -261,6 +261,7 @@ def load_library(path=None):
     lib.erpl_mc_set_chunk.argtypes = [C.c_void_p, C.c_int]
     lib.erpl_mc_set_adopt.argtypes = [C.c_void_p, C.c_int]
     lib.erpl_mc_set_adopt_spin.argtypes = [C.c_void_p, C.c_int]
+    lib.erpl_mc_set_sweep_pool.argtypes = [C.c_void_p, C.c_int]
     lib.erpl_mc_check_batch.argtypes = [C.c_void_p, C.c_int64]
     lib.erpl_mc_get_overlap.argtypes = [C.c_void_p]
     lib.erpl_mc_get_overlap.restype = C.c_int

@@ -211,6 +211,42 @@ namespace {
 // queues a lane keeps to its one stream and one workspace, with or without lane adoption (enqueue_batch).
 bool has_sweep_streams(const erpl_ctx* c) { return c->adopt != 0 && hw_queues_env() >= 2 * c->depth + 2; }
 
+// Without those queues - the HIP default of four: the caller's stream + three lanes - a lane can still have a sweep stream
+// with a hardware queue of its own: the runtime keeps one pool of up to GPU_MAX_HW_QUEUES queues PER STREAM PRIORITY, so a
+// stream created at another priority than the default shares no queue with the lanes' main streams or the caller's
+// (tools/ubench/queue_pools.hip, profiles/queue_pools.txt: at four queues 8 default-priority streams run 4 kernels at a
+// time, 4 default + 4 of either other priority run 8).  The process then has at most 4 + 4 queues.
+// The greatest priority the device reports or the least made no difference that five rounds could tell (bench shard, ms per
+// pass, medians: 22.69 against 22.70 with the capped hand-over sweep, 23.07 against 23.26 with the 512-register one;
+// profiles/sweep_pool_ab.json): the greatest, so that the few waves of a tail are not the ones that wait.
+// The pool streams and the second workspaces (448 bytes per sample each) come with the first batch of at least this size.
+// Measured down to it, parent against this with the rule moved out of the way, ms per pass at 9 216 / 12 288 / 16 384 /
+// 32 768 / 65 536 samples: 12.2 -> 8.9, 12.4 -> 8.2, 13.0 -> 8.9, 14.3 -> 9.6, 17.3 -> 12.5 (profiles/sweep_pool_ab.json) -
+// it pays at every size tried: what a lane waits for is its own batch's few long trajectories, not a free SIMD.
+// Batches up to 8 192 samples were not measured and stay as they were: one stream per lane, nothing more allocated.
+constexpr int64_t kSweepPoolMinBatch = 9216;
+
+bool other_priority_pool(erpl_ctx* c) {
+  if (!c->pool_known) {
+    int least = 0, greatest = 0;
+    c->pool_exists = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest;
+    c->pool_prio = greatest;
+    c->pool_known = true;
+  }
+  return c->pool_exists;
+}
+
+// The lanes of this context take their sweep streams from the other priority pool (erpl_mc_set_sweep_pool): asked with the
+// size of a batch that is being submitted or reserved; once on, it stays on (the workspaces are there).
+// Not where has_sweep_streams() holds, not from 12 queues up (those processes stay as they were), and not where the
+// lanes' main streams share queues among themselves already (more lanes than queues besides the caller's).
+bool pool_sweep_streams(erpl_ctx* c, int64_t n) {
+  if (c->adopt == 0 || c->sweep_pool == 0 || has_sweep_streams(c)) return false;
+  if (hw_queues_env() >= 12 || c->depth + 1 > hw_queues_env()) return false;
+  if (!c->pool_on && (c->sweep_pool > 0 || n >= kSweepPoolMinBatch)) c->pool_on = other_priority_pool(c);
+  return c->pool_on;
+}
+
 void slot_free_workspace(ErplSlot& s) {
   for (int k = 0; k < 2; ++k) {
     (void)hipFree(s.res_r[k]); (void)hipFree(s.res_d[k]); (void)hipFree(s.res_i[k]);
@@ -321,8 +357,9 @@ void note_finished_batches(erpl_ctx* c) {
 
 // Rail + flight kernels of one batch through the lane's next set, on stream `st`; `sweep` (or NULL) = the stream
 // the launches behind the main one go to when the batch runs with lane adoption.
+// `pool`: that stream is from the other priority pool (pool_sweep_streams).
 int enqueue_batch(erpl_ctx* c, int lane, const erpl_batch* b, const erpl_out* o, hipStream_t st, int in_flight,
-                  hipStream_t sweep, int64_t ticket, unsigned long long* ring_slot = nullptr, hipEvent_t ring_done = nullptr) {
+                  hipStream_t sweep, bool pool, int64_t ticket, unsigned long long* ring_slot = nullptr, hipEvent_t ring_done = nullptr) {
   // two workspaces per lane only where the lane's next batch may start beside the sweeps of its previous one (a sweep
   // stream exists); erpl_mc_run_batch and lanes without lane adoption stay on their first set
   const int si = lane + ((sweep && (c->lane_uses[lane] & 1u)) ? ERPL_MAX_OVERLAP : 0);
@@ -387,8 +424,17 @@ int enqueue_batch(erpl_ctx* c, int lane, const erpl_batch* b, const erpl_out* o,
   //   deep, 11.3 -> 9.0 three deep, 10.6 -> 9.0 eight deep; fp64 throughput build 44.7 -> 38.1 three deep, 37.7 ->
   //   35.9 eight deep; the gate kernel 129 -> 116 three deep).
   // - Fewer queues than that (the HIP default of four: the caller's stream + three lanes).  A second stream per lane
-  //   would land on another lane's queue, where the hand-overs cost more than they save (four queues, three deep:
-  //   11.4 -> 25.5 ms), so none is created: the sweeps of the fp64 throughput build follow the main launch on the
+  //   of the default priority would land on another lane's queue, where the hand-overs cost more than they save (four
+  //   queues, three deep: 11.4 -> 25.5 ms).  One of ANOTHER stream priority has a queue of its own - the runtime keeps a
+  //   pool of queues per priority (pool_sweep_streams above) - and the lane runs as it does with 24 queues: sweeps and
+  //   hand-over sweep on that stream, second workspace, next batch directly behind the main launch, three flight
+  //   launches, the adoption limit of the sweep-stream case.  fp64 throughput build, from the first batch of
+  //   kSweepPoolMinBatch samples on (bench shard, five rounds, min / median / max: 24.97 / 25.81 / 26.22 -> 22.57 /
+  //   22.69 / 22.95 ms per pass; the same box with 24 queues 23.09 and 22.67; the gap from the end of a lane's main
+  //   launch to its next rail kernel is gone).  fp32 and the gate were not measured with it
+  //   and stay on the lane's one stream.
+  //   Without the pool streams (smaller batches, erpl_mc_set_sweep_pool(0), one stream priority on the device) no second
+  //   stream is created: the sweeps of the fp64 throughput build follow the main launch on the
   //   lane's own stream, with two or more batches in flight to fill the SIMDs beside them (bench shard, f64_fast,
   //   three deep: 30.3 -> 28.2 ms per pass, lane utilisation 0.75 -> 0.98; with the capped hand-over sweep below
   //   26.5).  The lane's cycle there: main launch 40 ms, the two sweeps 3 + 12, the hand-over
@@ -402,7 +448,8 @@ int enqueue_batch(erpl_ctx* c, int lane, const erpl_batch* b, const erpl_out* o,
   // (limit: fp32 12 / 16 / 24 / 32 / 48 -> 9.30 / 9.05 / 9.00 / 8.93 / 8.97 ms; the one-wave-per-SIMD fp64 builds like it
   // higher - 24 / 40 / 48 / 56 -> 35.7 / 34.8 / 35.3 / 35.3 ms eight deep, 40.3 / 38.4 / 38.2 / 40.9 three deep)
   if (adopt < 0) {
-    if (sweep) adopt = (hw_queues_env() >= 2 * in_flight + 2) ? (b->precision == ERPL_PREC_F32 ? 24 : 40) : 0;
+    // (a pool stream is handed in for the fp64 throughput build only: erpl_mc_submit_batch)
+    if (sweep) adopt = pool ? 40 : ((hw_queues_env() >= 2 * in_flight + 2) ? (b->precision == ERPL_PREC_F32 ? 24 : 40) : 0);
     // (one stream per lane: measured for the fp64 throughput build only, with the limit of the sweep-stream case; the
     // fp32 build and the gate stay as they were until they are measured there too)
     else adopt = (ticket > 0 && in_flight >= 2 && b->precision == ERPL_PREC_F64_FAST) ? 40 : 0;
@@ -423,7 +470,11 @@ int enqueue_batch(erpl_ctx* c, int lane, const erpl_batch* b, const erpl_out* o,
   // waves start beside the throughput kernel's; on a stream of its own, in erpl_mc_run_batch and for trajectory capture
   // the gate's own (note [3] of erpl_k_config.h)
   // (not with step chunks: long flights were not measured in this mode and keep the launch sequence they had)
-  const int sweep_waves = (ticket > 0 && !sweep && in_flight >= 2 && o->n_traj == 0 && a.chunk_steps == 0) ? 2 : 1;
+  // (on a sweep stream from the other priority pool the capped one again: at four queues the other lanes' main launches
+  // keep every SIMD busy, and the lane's set is free for its next batch but one only when the sweep is over - bench shard,
+  // five rounds, 22.57 / 22.69 / 22.95 ms per pass against 22.99 / 23.07 / 23.30 with the 512-register instantiation)
+  const bool beside = ticket > 0 && in_flight >= 2 && o->n_traj == 0 && a.chunk_steps == 0;
+  const int sweep_waves = (beside && (!sweep || pool)) ? 2 : 1;
   int lrc;
   if (b->precision == ERPL_PREC_F64) lrc = erpl_launch_f64(a, &T.s64, c->block, max_blocks, n_phases, st, ev, tail, s.main_done, sweep_waves);
   else if (b->precision == ERPL_PREC_F64_FAST) lrc = erpl_launch_f64f(a, &T.s64, c->block, max_blocks, n_phases, st, ev, tail, s.main_done, sweep_waves);
@@ -439,7 +490,7 @@ int enqueue_batch(erpl_ctx* c, int lane, const erpl_batch* b, const erpl_out* o,
   s.latest_is_run = ticket <= 0;
   if (ticket > 0) s.ticket = ticket;   // (an erpl_mc_run_batch on this set leaves the ticket: its `done` is later and covers it)
   s.last_n = b->n;
-  s.last_adopt = a.adopt_lanes; s.last_sweep_waves = (b->precision == ERPL_PREC_F64_FAST) ? sweep_waves : 0; s.last_tail = tail != nullptr;
+  s.last_adopt = a.adopt_lanes; s.last_sweep_waves = (b->precision == ERPL_PREC_F64_FAST) ? sweep_waves : 0; s.last_tail = tail != nullptr; s.last_pool = tail != nullptr && pool;
   s.seq = ++c->batches;
   c->last_slot = si;
   c->lane_uses[lane]++;
@@ -537,7 +588,8 @@ int erpl_mc_reserve(erpl_ctx* c, int64_t n) {
   // that have been used before grow too, fresh ones take the size on first use
   // (the second workspace of a lane is only ever used beside a sweep stream: without one the lane's next batch starts
   // behind the sweeps anyway, and it is not allocated - a workspace costs 448 bytes per sample)
-  const bool adopt = has_sweep_streams(c);
+  // (or takes its sweep stream from the other priority pool: the same rule as erpl_mc_submit_batch, by the size asked for)
+  const bool adopt = has_sweep_streams(c) || pool_sweep_streams(c, n);
   for (int i = 0; i < 2 * ERPL_MAX_OVERLAP; ++i) {
     if (i % ERPL_MAX_OVERLAP >= c->depth && !c->slot[i].d_queue) continue;
     if (i >= ERPL_MAX_OVERLAP && !adopt && !c->slot[i].d_queue) continue;
@@ -573,6 +625,14 @@ int erpl_mc_set_adopt(erpl_ctx* c, int lanes) {
   return ERPL_OK;
 }
 
+int erpl_mc_set_sweep_pool(erpl_ctx* c, int mode) {
+  if (!c) return erpl_fail(ERPL_ERR_INVALID, "null context");
+  if (mode < -1 || mode > 1) return erpl_fail(ERPL_ERR_INVALID, "sweep pool mode must be -1 (by batch size), 0 (never) or 1 (always)");
+  c->sweep_pool = mode;
+  if (mode == 0) c->pool_on = false;   // (streams and workspaces that exist stay; batches go back to the lane's one stream)
+  return ERPL_OK;
+}
+
 int erpl_mc_set_launch(erpl_ctx* c, int block_threads, int max_blocks, int refill_threshold) {
   if (!c) return erpl_fail(ERPL_ERR_INVALID, "NULL ctx");
   if (block_threads != 64 && block_threads != 128 && block_threads != 256)
@@ -588,7 +648,7 @@ int erpl_mc_run_batch(erpl_ctx* c, const erpl_batch* b, const erpl_out* o, void*
   int rc = check_batch(c, b, o);
   if (rc != ERPL_OK || b->n == 0) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  return enqueue_batch(c, 0, b, o, (hipStream_t)stream, 1, nullptr, 0);
+  return enqueue_batch(c, 0, b, o, (hipStream_t)stream, 1, nullptr, false, 0);
 }
 
 int erpl_mc_get_overlap(erpl_ctx* c) { return c ? c->depth : 0; }
@@ -623,9 +683,15 @@ int erpl_mc_submit_batch(erpl_ctx* c, const erpl_batch* b, const erpl_out* o, vo
   const int lane = (int)(c->submitted % depth);
   if (!c->lane_stream[lane]) HIP_TRY(hipStreamCreateWithFlags(&c->lane_stream[lane], hipStreamNonBlocking));
   // the sweep stream only where the process has a hardware queue for it: with the HIP default of four (the caller's
-  // stream + three lanes) a second one per lane would push the main streams onto shared queues
+  // stream + three lanes) a second one per lane of the same priority would push the main streams onto shared queues;
+  // one of another priority has a queue of its own (pool_sweep_streams: the fp64 throughput build, batches that fill the GPU)
   const bool adopt = has_sweep_streams(c);
-  if (adopt && !c->lane_sweep[lane]) HIP_TRY(hipStreamCreateWithFlags(&c->lane_sweep[lane], hipStreamNonBlocking));
+  const bool pool = !adopt && b->precision == ERPL_PREC_F64_FAST && pool_sweep_streams(c, b->n);
+  if ((adopt || pool) && !c->lane_sweep[lane]) {
+    if (pool) HIP_TRY(hipStreamCreateWithPriority(&c->lane_sweep[lane], hipStreamNonBlocking, c->pool_prio));
+    else HIP_TRY(hipStreamCreateWithFlags(&c->lane_sweep[lane], hipStreamNonBlocking));
+    c->lane_sweep_pool[lane] = pool;
+  }
   if (!c->lane_in_ready[lane]) HIP_TRY(hipEventCreateWithFlags(&c->lane_in_ready[lane], hipEventDisableTiming));
   // inputs written on the caller's stream so far are visible to the batch
   HIP_TRY(hipEventRecord(c->lane_in_ready[lane], (hipStream_t)stream));
@@ -647,8 +713,8 @@ int erpl_mc_submit_batch(erpl_ctx* c, const erpl_batch* b, const erpl_out* o, vo
     if (c->slot[i].h_counters == &c->ring_counters[4 * ri]) c->slot[i].h_counters = c->slot[i].own_counters;
   memset(&c->ring_counters[4 * ri], 0, 4 * sizeof(unsigned long long));
   c->ring_ticket[ri] = 0;
-  ERPL_TRY(enqueue_batch(c, lane, b, o, c->lane_stream[lane], depth, adopt ? c->lane_sweep[lane] : nullptr, t_new,
-                         &c->ring_counters[4 * ri], c->ring_done[ri]));
+  ERPL_TRY(enqueue_batch(c, lane, b, o, c->lane_stream[lane], depth, (adopt || pool) ? c->lane_sweep[lane] : nullptr,
+                         pool && c->lane_sweep_pool[lane], t_new, &c->ring_counters[4 * ri], c->ring_done[ri]));
   c->ring_ticket[ri] = t_new;
   ++c->submitted;
   if (ticket) *ticket = c->submitted;
@@ -812,7 +878,7 @@ int erpl_mc_debug_counters(erpl_ctx* c, double* out16) {
   int streams = 0;
   for (int i = 0; i < ERPL_MAX_OVERLAP; ++i) streams += (c->lane_stream[i] != nullptr) + (c->lane_sweep[i] != nullptr);
   out16[4] = (double)hw_queues_env(); out16[5] = (double)streams;
-  out16[6] = (double)ls.last_adopt; out16[7] = (double)(ls.last_sweep_waves + (ls.last_tail ? 16 : 0));
+  out16[6] = (double)ls.last_adopt; out16[7] = (double)(ls.last_sweep_waves + (ls.last_tail ? 16 : 0) + (ls.last_pool ? 32 : 0));
   return ERPL_OK;
 }
 

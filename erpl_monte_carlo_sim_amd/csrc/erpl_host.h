@@ -72,7 +72,8 @@ struct ErplSlot {
   bool latest_is_run = false;               // the slot's latest batch came through erpl_mc_run_batch (no ticket record)
   int64_t last_n = 0, seq = 0;              // its size and its position in the order of all batches of the context
   int last_adopt = 0, last_sweep_waves = 0; // how it was scheduled: adoption limit of its main launch, instantiation of its
-  bool last_tail = false;                   //   hand-over sweep, sweeps on the lane's second stream (erpl_mc_debug_counters)
+  bool last_tail = false, last_pool = false; //  hand-over sweep, sweeps on the lane's second stream, that stream from the
+                                            //   other priority pool (erpl_mc_debug_counters)
 };
 
 struct erpl_ctx {
@@ -88,10 +89,12 @@ struct erpl_ctx {
   // batches of equal length submitted together run in step, and without this the tails of a whole round of
   // them met on an otherwise empty GPU before the next round could start.
   // Sweep streams and second sets exist only where the process has a hardware queue per stream (has_sweep_streams in
-  // erpl_api.hip); with fewer, the sweeps stay on the lane's main stream and the lane on its first set.
+  // erpl_api.hip) or, at the HIP default of four queues, where the sweep streams come from the other stream-priority
+  // pool (pool_sweep_streams there); otherwise the sweeps stay on the lane's main stream and the lane on its first set.
   ErplSlot slot[2 * ERPL_MAX_OVERLAP];
   hipStream_t lane_stream[ERPL_MAX_OVERLAP] = {};
   hipStream_t lane_sweep[ERPL_MAX_OVERLAP] = {};
+  bool lane_sweep_pool[ERPL_MAX_OVERLAP] = {};   // lane_sweep[i] was created at the other pool's priority
   hipEvent_t lane_in_ready[ERPL_MAX_OVERLAP] = {};
   unsigned lane_uses[ERPL_MAX_OVERLAP] = {};   // batches the lane has taken: parity picks the set
   int depth = 3;                  // slots erpl_mc_submit_batch cycles through (erpl_mc_create: 8 with enough hardware queues)
@@ -109,6 +112,10 @@ struct erpl_ctx {
   int64_t reserve_n = 0;          // erpl_mc_reserve request, applied to a slot when it is first used
   int adopt_spin = 1 << 22;       // polls of an adopting lane for a claimed record's ready word (erpl_mc_set_adopt_spin)
   int adopt = -1;                 // lane adoption: flying lanes at or below which a wave hands its lanes over; 0 = off; < 0 = by batch
+  int sweep_pool = -1;            // erpl_mc_set_sweep_pool: -1 = from the first batch that fills the GPU, 0 = never, 1 = always
+  bool pool_on = false;           //   the lanes take their sweep streams from the other priority pool (latched)
+  bool pool_known = false, pool_exists = false;   // hipDeviceGetStreamPriorityRange has been asked; it reports two priorities
+  int pool_prio = 0;              //   the priority the pool streams are created at
   int chunk = -1;                 // steps per launch between compactions; 0 = one launch; < 0 = by the batches seen so far
   int short_depth = 4;            // erpl_mc_set_short_flight_overlap
   double seen_mean_steps = 0.0;   // physics RK4 steps per trajectory of the most recent COMPLETED batch

@@ -218,6 +218,11 @@ class TrajectoryEngine:
         """Test knob (erpl_mc_set_adopt_spin): < 0 makes every adopting lane give up at once."""
         self._call("erpl_mc_set_adopt_spin", int(polls))
 
+    def set_sweep_pool(self, mode):
+        """Sweep streams from the other stream-priority pool where a lane has one hardware queue (erpl_mc_set_sweep_pool):
+        -1 = from the first batch that fills the GPU on (the default), 0 = never, 1 = always.  Scheduling only."""
+        self._call("erpl_mc_set_sweep_pool", int(mode))
+
     @staticmethod
     def raise_if_incomplete(status):
         """Results whose status words still carry ST_INCOMPLETE were never integrated: refuse to hand them on."""

@@ -12,7 +12,11 @@ Streams are told apart by the trace's Stream_Id column where it has one, by Queu
 the whole sequence rail, main launch, adoption sweeps, hand-over sweep on ONE stream (one stream per lane), the duration
 of each launch, the tail (end of the main launch to end of the hand-over sweep), the gap to the lane's next rail kernel
 and the lane cycle (rail start to next rail start).  A kernel trace has one interval per dispatch: when the last working
-wave of a dispatch ended is not in it."""
+wave of a dispatch ended is not in it.
+
+`lanes` is the same split for every stream that carries rail kernels, wherever the sweeps of its batches ran (a lane
+with a sweep stream has them elsewhere): main launch, end of the main launch to the start of the lane's next rail kernel,
+and the lane cycle."""
 import csv
 import glob
 import json
@@ -95,12 +99,23 @@ def main():
             if b < len(rs):
                 cyc["handover_end_to_next_rail_start_ms"].append((rs[b]["s"] - ho[0]["e"]) / 1e6)
                 cyc["lane_cycle_ms"].append((rs[b]["s"] - batch[0]["s"]) / 1e6)
+    lanes = {k: [] for k in ("main_ms", "main_end_to_next_rail_start_ms", "lane_cycle_ms")}
+    for key, rs in by_key.items():
+        starts = [i for i, r in enumerate(rs) if "erpl_rail_f64f" in r["name"]]
+        for a, b in zip(starts, starts[1:]):
+            main = next((r for r in rs[a + 1:b] if "erpl_flight_" in r["name"] and not is_sweep(r["name"])), None)
+            if main is None:
+                continue
+            lanes["main_ms"].append((main["e"] - main["s"]) / 1e6)
+            lanes["main_end_to_next_rail_start_ms"].append((rs[b]["s"] - main["e"]) / 1e6)
+            lanes["lane_cycle_ms"].append((rs[b]["s"] - rs[a]["s"]) / 1e6)
     out = {"streams_with_dispatches": len(by_key), "streams_carrying_both_rail_and_sweep": int(shared),
            "sweep_registers": sorted({r["vgpr"] for r in sweeps}), "sweep_scratch_bytes": sorted({r["scratch"] for r in sweeps}),
            "sweep_dispatch_ms": stats(dur),
            "sweep_start_to_next_rail_start_on_its_stream_ms": stats(gap_start),
            "sweep_end_to_next_rail_start_on_its_stream_ms": stats(gap_end),
            "lane_cycles": dict({k: stats(v) for k, v in cyc.items()}, handover_sweep_grid_threads=sorted(grids)),
+           "lanes": {k: stats(v) for k, v in lanes.items()},
            "note": "timed passes of the f64_fast leg only (the first %d passes are warm-up); a sweep on a stream of its own has its "
                    "next rail kernel two batches later or none at all" % skip}
     json.dump(out, open(out_path, "w"), indent=1)
