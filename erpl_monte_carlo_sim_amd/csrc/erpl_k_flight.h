@@ -94,8 +94,10 @@ template <typename T> __device__ __forceinline__ bool m_finite(T x) { return (x 
 // ERPL_SWEEP_CAPPED_WAVES in erpl_k_config.h).
 #if ERPL_FAST_F64
 constexpr int kFlightBlock = kWave;   // per-lane LDS arrays of one wave: always 64-thread workgroups
+constexpr bool kStepsAcrossLoop = true;
 #else
 constexpr int kFlightBlock = 256;
+constexpr bool kStepsAcrossLoop = false;
 #endif
 template <bool TRAJ, int SPEC, int MINW>
 __global__ __launch_bounds__(kFlightBlock, MINW) void ERPL_CAT(erpl_flight_, ERPL_SUFFIX)(const ErplKArgs a, const ErplScalars<real> S) {
@@ -349,6 +351,10 @@ __global__ __launch_bounds__(kFlightBlock, MINW) void ERPL_CAT(erpl_flight_, ERP
 #if ERPL_FAST_F32
     if (ln.mode == kPhysics) *tl = ln.t;
 #endif
+    // total physics steps, fp64 throughput build: a lane that integrates when the loop is entered does so until it is
+    // left, one step per iteration, so its steps are the difference of ln.steps across the loop - not a 64-bit increment
+    // (two vector instructions) in every step
+    if (kStepsAcrossLoop && ln.mode == kPhysics) steps_done -= (unsigned long long)ln.steps;
     do {
     ++wave_iters;
     ended = false; nonfinite = false; alt_nan = false; latch_now = false; coast_out = false;
@@ -436,7 +442,7 @@ __global__ __launch_bounds__(kFlightBlock, MINW) void ERPL_CAT(erpl_flight_, ERP
       const double t_now = ln.t;
 #endif
       ln.steps++;
-      ++steps_done;
+      if (!kStepsAcrossLoop) ++steps_done;
       ERPL_STAMP(ss.seg[6], ss.last);  // final combine + normalise
       const real alt = yn[2], vz = yn[5];
       // ---- everything below is straight-line selects; the single branch at the end is taken only
@@ -487,6 +493,7 @@ __global__ __launch_bounds__(kFlightBlock, MINW) void ERPL_CAT(erpl_flight_, ERP
     } while (!TRAJ && __ballot(ended || nonfinite || (ln.mode == kPhysics && ln.steps >= ln.stop_steps)) == 0ull);
 #endif
     if (ln.mode == kPhysics) {
+      if (kStepsAcrossLoop) steps_done += (unsigned long long)ln.steps;   // (before the fast-forward of a non-finite lane below moves ln.steps)
 #if ERPL_FAST_F32
       ln.t = *tl;
 #endif

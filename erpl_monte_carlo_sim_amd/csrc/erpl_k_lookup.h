@@ -220,27 +220,43 @@ __device__ __forceinline__ void mass_props(const ErplScalars<real>& S, const Lan
 // leaves the interval (a NaN Mach always misses and lands on record 0, whose zero slopes
 // propagate the NaN exactly like np.interp does).
 #if ERPL_FAST_F64
+// A record of a workgroup table as the lane keeps it: its BYTE offset in the table.  The table's own LDS address is a
+// link-time constant that folds into the immediate offset of every read, so the lane's one register is the address
+// register of all of them (an index costs a multiply and a shift per RHS evaluation).  Records are 16-byte aligned.
+// They are read as 16-byte pairs: the alignment then belongs to the load itself (ds_read_b128 at base + immediate).
+typedef real RealPair __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ const RealPair* lds_record(const real* table, int byte_off) {
+  return (const RealPair*)((const char*)table + byte_off);
+}
+constexpr int kMachRecBytes = kMachRec * (int)sizeof(real), kAtmRecBytes = ERPL_ATM_REC * (int)sizeof(real);
+static_assert(kMachRecBytes % 16 == 0 && kAtmRecBytes % 16 == 0, "table records are read 16 bytes at a time");
 struct MachCache {
-  int idx;   // number of union knots <= the Mach numbers of the interval; the record is read from the shared table
+  int ro;   // kMachRecBytes x the number of union knots <= the Mach numbers of the interval; the record is read from the shared table
 };
-__device__ __forceinline__ void mach_cache_clear(MachCache& mc) { mc.idx = kMachEmpty; }
-__device__ __forceinline__ const real* mach_rec_of(const Shared& C, const MachCache& mc) { return &C.L->mach_rec[mc.idx * kMachRec + 2]; }
+__device__ __forceinline__ void mach_cache_clear(MachCache& mc) { mc.ro = kMachEmpty * kMachRecBytes; }
+__device__ __forceinline__ const real* mach_rec_of(const Shared& C, const MachCache& mc) { return (const real*)(lds_record(C.L->mach_rec, mc.ro) + 1); }
+// the eight np.interp values of the lane's interval, for the RHS
+__device__ __forceinline__ void mach_rec_load(const Shared& C, const MachCache& mc, real (&rec)[ERPL_MACH_REC]) {
+  const RealPair* r = lds_record(C.L->mach_rec, mc.ro);
+#pragma unroll
+  for (int k = 0; k < ERPL_MACH_REC / 2; ++k) { const RealPair v = r[1 + k]; rec[2 * k] = v.x; rec[2 * k + 1] = v.y; }
+}
 __device__ __forceinline__ bool mach_inside(const Shared& C, const MachCache& mc, real mach) {
-  const real* r = &C.L->mach_rec[mc.idx * kMachRec];
-  const real lo = r[0], hi = r[1];   // one 16-byte read, no short-circuit branch between the two
+  const RealPair r = *lds_record(C.L->mach_rec, mc.ro);
+  const real lo = r.x, hi = r.y;   // one 16-byte read, no short-circuit branch between the two
   return (mach >= lo) & (mach < hi);
 }
 __device__ __forceinline__ void mach_reload(const Shared& C, real mach, MachCache& mc) {
   const LdsTables& L = *C.L;
   const int n_union = cold_args()->n_union;
   // neighbour on the side the old interval was left, else count the knots (see the register variant below)
-  int idx = mc.idx + ((mach >= L.mach_rec[mc.idx * kMachRec + 1]) ? 1 : -1);
+  int idx = mc.ro / kMachRecBytes + ((mach >= lds_record(L.mach_rec, mc.ro)->y) ? 1 : -1);
   idx = (idx < 0) ? 0 : ((idx > n_union) ? n_union : idx);
   if (!(mach >= L.mach_rec[idx * kMachRec] && mach < L.mach_rec[idx * kMachRec + 1])) {
     idx = 0;
     for (int j = 0; j < n_union; ++j) idx += (mach >= L.union_knots[j]) ? 1 : 0;
   }
-  mc.idx = idx;
+  mc.ro = idx * kMachRecBytes;
 }
 #else
 struct MachCache {
@@ -308,7 +324,7 @@ struct AtmCache {
   real lo, hi;     // altitudes over which BOTH the layer record and the cached wind interval hold
   real alo, ahi;   // altitudes of the layer alone: a wind-knot crossing inside it leaves the record as it is
 #if ERPL_FAST_F64
-  int li;          // layer index: the record is read from the workgroup's table where it is used
+  int ro;          // kAtmRecBytes x the layer index: the record is read from the workgroup's table where it is used
 #else
   real r[10];  // aT bT Tlo Thi invTref eL href eH eM base
 #endif
@@ -316,7 +332,7 @@ struct AtmCache {
 __device__ __forceinline__ void atm_cache_clear(AtmCache& ac) {
   ac.lo = 1; ac.hi = 0; ac.alo = 1; ac.ahi = 0;
 #if ERPL_FAST_F64
-  ac.li = 0;
+  ac.ro = 0;
 #endif
 }
 
@@ -327,7 +343,7 @@ __device__ __forceinline__ void altitude_tables_reload(const Shared& C, int64_t 
     const int li = ((h > S.h_tropo) ? 1 : 0) + ((h > S.h_strat) ? 1 : 0) + ((h > (real)25000.0) ? 1 : 0) +
                    ((h > (real)32000.0) ? 1 : 0);  // NaN -> layer 0, whose formula propagates the NaN
 #if ERPL_FAST_F64
-    ac.li = li;
+    ac.ro = li * kAtmRecBytes;
 #else
 #pragma unroll
     for (int k = 0; k < 10; ++k) ac.r[k] = C.L->atm[li * ERPL_ATM_REC + k];

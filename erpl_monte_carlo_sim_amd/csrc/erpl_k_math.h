@@ -103,7 +103,7 @@ __device__ __forceinline__ double m_exp2(double x, double early) {
   const double n = __builtin_rint(x);
   const double f = x - n;
   double p = KS(0, 1.3691488853904128e-12, f);
-  p = __builtin_fma(p, f, KS(1, 2.5678435993488206e-11, p));
+  p = __builtin_fma(p, f, KS(1, 2.5678435993488206e-11, f));   // (anchored on f: p is still a scalar here)
   p = __builtin_fma(p, f, KS(2, 4.4455382718708116e-10, p));
   p = __builtin_fma(p, f, KS(3, 7.054911620801123e-09, p));
   p = __builtin_fma(p, f, KS(4, 1.01780860092397e-07, p));
@@ -133,7 +133,7 @@ __device__ __forceinline__ double m_log2(double x, double early) {
   const double s = (m - 1.0) * m_rcp(m + 1.0);
   const double z = s * s;
   double q = KS(0, 0.12545174268599682, z);
-  q = __builtin_fma(q, z, KS(1, 0.1373995277037108, q));
+  q = __builtin_fma(q, z, KS(1, 0.1373995277037108, z));   // (anchored on z: q is still a scalar here)
   q = __builtin_fma(q, z, KS(2, 0.15186263588304877, q));
   q = __builtin_fma(q, z, KS(3, 0.16972882833987804, q));
   q = __builtin_fma(q, z, KS(4, 0.19235933878519512, q));
@@ -164,8 +164,8 @@ __device__ __forceinline__ double m_atan2_half(double y, double x, double r, dou
   const double z = t * t, w = z * z;
   double s1 = KS(0, 1.62858201153657823623e-02, w);
   double s2 = KS(6, -3.65315727442169155270e-02, w);
-  s1 = __builtin_fma(s1, w, KS(1, 4.97687799461593236017e-02, s1));
-  s2 = __builtin_fma(s2, w, KS(7, -5.83357013379057348645e-02, s2));
+  s1 = __builtin_fma(s1, w, KS(1, 4.97687799461593236017e-02, w));   // (anchored on w: s1, s2 are still scalars here)
+  s2 = __builtin_fma(s2, w, KS(7, -5.83357013379057348645e-02, w));
   s1 = __builtin_fma(s1, w, KS(2, 6.66107313738753120669e-02, s1));
   s2 = __builtin_fma(s2, w, KS(8, -7.69187620504482999495e-02, s2));
   s1 = __builtin_fma(s1, w, KS(3, 9.09088713343650656196e-02, s1));
@@ -195,16 +195,18 @@ __device__ __forceinline__ void m_atan2_half_pair(double ya, double xa, double r
   const double za = ta * ta, zb = tb * tb, wa = za * za, wb = zb * zb;
   const double c0 = KS(0, 1.62858201153657823623e-02, wa), c6 = KS(6, -3.65315727442169155270e-02, wa);
   double s1a = c0, s2a = c6, s1b = c0, s2b = c6;
-#define ERPL_ATAN_STEP(i1_, v1_, i2_, v2_)                                    \
+  // (a1_, a2_: what the coefficients are anchored on - the chain values, except in the first step, where s1a and s2a
+  // are still the scalars c0 and c6 and an anchor on them would be a dead copy into vector registers)
+#define ERPL_ATAN_STEP(i1_, v1_, i2_, v2_, a1_, a2_)                          \
   {                                                                           \
-    const double k1 = KS(i1_, v1_, s1a), k2 = KS(i2_, v2_, s2a);              \
+    const double k1 = KS(i1_, v1_, a1_), k2 = KS(i2_, v2_, a2_);              \
     s1a = __builtin_fma(s1a, wa, k1); s2a = __builtin_fma(s2a, wa, k2);       \
     s1b = __builtin_fma(s1b, wb, k1); s2b = __builtin_fma(s2b, wb, k2);       \
   }
-  ERPL_ATAN_STEP(1, 4.97687799461593236017e-02, 7, -5.83357013379057348645e-02)
-  ERPL_ATAN_STEP(2, 6.66107313738753120669e-02, 8, -7.69187620504482999495e-02)
-  ERPL_ATAN_STEP(3, 9.09088713343650656196e-02, 9, -1.11111104054623557880e-01)
-  ERPL_ATAN_STEP(4, 1.42857142725034663711e-01, 10, -1.99999999998764832476e-01)
+  ERPL_ATAN_STEP(1, 4.97687799461593236017e-02, 7, -5.83357013379057348645e-02, wa, wa)
+  ERPL_ATAN_STEP(2, 6.66107313738753120669e-02, 8, -7.69187620504482999495e-02, s1a, s2a)
+  ERPL_ATAN_STEP(3, 9.09088713343650656196e-02, 9, -1.11111104054623557880e-01, s1a, s2a)
+  ERPL_ATAN_STEP(4, 1.42857142725034663711e-01, 10, -1.99999999998764832476e-01, s1a, s2a)
 #undef ERPL_ATAN_STEP
   {
     const double k1 = KS(5, 3.33333333333329318027e-01, s1a);

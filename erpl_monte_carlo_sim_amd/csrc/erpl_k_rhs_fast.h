@@ -5,7 +5,12 @@ namespace {
 // and pressure.
 __device__ __forceinline__ void fast_atmosphere(const Shared& C, const AtmCache& ac, real h, real& T, real& rT, real& P) {
 #if ERPL_FAST_F64
-  const real* r = &C.L->atm[ac.li * ERPL_ATM_REC];
+  real r[10];
+  {
+    const RealPair* q = lds_record(C.L->atm, ac.ro);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) { const RealPair v = q[k]; r[2 * k] = v.x; r[2 * k + 1] = v.y; }
+  }
 #else
   (void)C;
   const real* r = ac.r;
@@ -166,7 +171,13 @@ __device__ __forceinline__ void rocket_dynamics_at(const Shared& C, LaneParams& 
     const real mach = m_sqrt_pos(mach2);   // q_dynamic > 0: mach2 > 0
     if (!mach_inside(C, mc, mach)) { ERPL_RARE_BLOCK(); mach_reload(C, mach, mc); }  // rare, divergent
     real cd, cl, cy, cma;
-    fast_aero(S, mach_rec_of(C, mc), mach, mach2, alpha, beta, pf, cg, cd, cl, cy, cma);
+#if ERPL_FAST_F64
+    real mrec[ERPL_MACH_REC];
+    mach_rec_load(C, mc, mrec);
+#else
+    const real* mrec = mach_rec_of(C, mc);
+#endif
+    fast_aero(S, mrec, mach, mach2, alpha, beta, pf, cg, cd, cl, cy, cma);
     const real qs = qdyn * S.ref_area;
     const real drag = qs * cd, lift = qs * cl, side = qs * cy;
     fb0 += (sb * side - (ca * cb) * drag) - (sa * cb) * lift;
