@@ -206,26 +206,10 @@ static int hw_queues_env() {
 
 namespace {
 
-// The lanes of this context run their sweeps on a second stream (with a second workspace): lane adoption can come on and
-// the process has a hardware queue for every stream - two per lane, the caller's and one more of its own.  Without the
-// queues a lane keeps to its one stream and one workspace, with or without lane adoption (enqueue_batch).
-bool has_sweep_streams(const erpl_ctx* c) { return c->adopt != 0 && hw_queues_env() >= 2 * c->depth + 2; }
-
-// Without those queues - the HIP default of four: the caller's stream + three lanes - a lane can still have a sweep stream
-// with a hardware queue of its own: the runtime keeps one pool of up to GPU_MAX_HW_QUEUES queues PER STREAM PRIORITY, so a
-// stream created at another priority than the default shares no queue with the lanes' main streams or the caller's
-// (tools/ubench/queue_pools.hip, profiles/queue_pools.txt: at four queues 8 default-priority streams run 4 kernels at a
-// time, 4 default + 4 of either other priority run 8).  The process then has at most 4 + 4 queues.
-// The greatest priority the device reports or the least made no difference that five rounds could tell (bench shard, ms per
-// pass, medians: 22.69 against 22.70 with the capped hand-over sweep, 23.07 against 23.26 with the 512-register one;
-// profiles/sweep_pool_ab.json): the greatest, so that the few waves of a tail are not the ones that wait.
-// The pool streams and the second workspaces (448 bytes per sample each) come with the first batch of at least this size.
-// Measured down to it, parent against this with the rule moved out of the way, ms per pass at 9 216 / 12 288 / 16 384 /
-// 32 768 / 65 536 samples: 12.2 -> 8.9, 12.4 -> 8.2, 13.0 -> 8.9, 14.3 -> 9.6, 17.3 -> 12.5 (profiles/sweep_pool_ab.json) -
-// it pays at every size tried: what a lane waits for is its own batch's few long trajectories, not a free SIMD.
-// Batches up to 8 192 samples were not measured and stay as they were: one stream per lane, nothing more allocated.
-constexpr int64_t kSweepPoolMinBatch = 9216;
-
+// Whether the device has a second stream-priority pool, and the priority its streams are created at: asked when the lanes
+// are about to take pool streams (erpl_sweep_stream of erpl_plan.h), once.  The greatest priority the device reports or the
+// least made no difference that five rounds could tell: the greatest, so that the few waves of a
+// tail are not the ones that wait.
 bool other_priority_pool(erpl_ctx* c) {
   if (!c->pool_known) {
     int least = 0, greatest = 0;
@@ -234,17 +218,6 @@ bool other_priority_pool(erpl_ctx* c) {
     c->pool_known = true;
   }
   return c->pool_exists;
-}
-
-// The lanes of this context take their sweep streams from the other priority pool (erpl_mc_set_sweep_pool): asked with the
-// size of a batch that is being submitted or reserved; once on, it stays on (the workspaces are there).
-// Not where has_sweep_streams() holds, not from 12 queues up (those processes stay as they were), and not where the
-// lanes' main streams share queues among themselves already (more lanes than queues besides the caller's).
-bool pool_sweep_streams(erpl_ctx* c, int64_t n) {
-  if (c->adopt == 0 || c->sweep_pool == 0 || has_sweep_streams(c)) return false;
-  if (hw_queues_env() >= 12 || c->depth + 1 > hw_queues_env()) return false;
-  if (!c->pool_on && (c->sweep_pool > 0 || n >= kSweepPoolMinBatch)) c->pool_on = other_priority_pool(c);
-  return c->pool_on;
 }
 
 void slot_free_workspace(ErplSlot& s) {
@@ -341,28 +314,46 @@ void fill_common_args(const erpl_ctx* c, const erpl_batch* b, ErplKArgs& a) {
   a.dt_rail = T.dt_rail; a.dt_flight = T.dt_flight; a.max_time = T.max_time;
 }
 
-// Trajectory length is not known in advance: the scheduling choices that depend on it (step chunks, how many batches of
-// short flights start side by side) follow the batches this context has already FINISHED - their device step counter is
-// copied to pinned memory behind every batch.
-constexpr double kLongFlightSteps = 8192.0;
+// The step counter of the batches this context has FINISHED is copied to pinned memory behind every batch: what the
+// choices that depend on trajectory length follow (kLongFlightSteps of erpl_plan.h).
 void note_finished_batches(erpl_ctx* c) {
   for (int i = 0; i < 2 * ERPL_MAX_OVERLAP; ++i) {
     ErplSlot& q = c->slot[i];
     if (q.used && q.seq > c->seen_seq && q.last_n > 0 && hipEventQuery(q.done) == hipSuccess) {
-      c->seen_mean_steps = (double)q.h_counters[1] / (double)q.last_n;
+      c->sched.seen_mean_steps = (double)q.h_counters[1] / (double)q.last_n;
       c->seen_seq = q.seq;
     }
   }
 }
 
-// Rail + flight kernels of one batch through the lane's next set, on stream `st`; `sweep` (or NULL) = the stream
-// the launches behind the main one go to when the batch runs with lane adoption.
-// `pool`: that stream is from the other priority pool (pool_sweep_streams).
-int enqueue_batch(erpl_ctx* c, int lane, const erpl_batch* b, const erpl_out* o, hipStream_t st, int in_flight,
-                  hipStream_t sweep, bool pool, int64_t ticket, unsigned long long* ring_slot = nullptr, hipEvent_t ring_done = nullptr) {
-  // two workspaces per lane only where the lane's next batch may start beside the sweeps of its previous one (a sweep
-  // stream exists); erpl_mc_run_batch and lanes without lane adoption stay on their first set
-  const int si = lane + ((sweep && (c->lane_uses[lane] & 1u)) ? ERPL_MAX_OVERLAP : 0);
+// What the policy of erpl_plan.h is told: the context's settings and history, the process and `n` samples of `precision`.
+ErplPlanIn plan_inputs(const erpl_ctx* c, int precision, int64_t n) {
+  ErplPlanIn in;
+  static_cast<ErplSched&>(in) = c->sched;
+  in.queues = hw_queues_env(); in.n_cu = c->n_cu;
+  in.max_time = c->h_tables.max_time; in.dt_flight = c->h_tables.dt_flight;
+  in.precision = precision; in.n = n;
+  return in;
+}
+
+// The sweep stream of a lane for what is being submitted or reserved; latches the pool.
+ErplSweepKind lane_sweep_kind(erpl_ctx* c, const ErplPlanIn& in) {
+  return erpl_sweep_stream(in, c->pool_on, [c] { return other_priority_pool(c); });
+}
+
+// ... and a batch coming in through erpl_mc_run_batch or erpl_mc_submit_batch (before its sweep stream is known).
+ErplPlanIn batch_inputs(erpl_ctx* c, const erpl_batch* b, const erpl_out* o, bool submit, int in_flight) {
+  if (c->sched.chunk < 0) note_finished_batches(c);   // (automatic step chunks read seen_mean_steps)
+  ErplPlanIn in = plan_inputs(c, b->precision, b->n);
+  in.n_traj = o->n_traj; in.submit = submit; in.in_flight = in_flight;
+  return in;
+}
+
+// Rail + flight kernels of one batch as `plan` says, through the lane's next set, on stream `st` (and the lane's sweep
+// stream where the plan puts the launches behind the main one there); `ri` = the record of the batch's ticket in the
+// ring, or -1 for erpl_mc_run_batch, which has none.
+int enqueue_batch(erpl_ctx* c, int lane, const erpl_batch* b, const erpl_out* o, hipStream_t st, const ErplPlan& plan, int ri) {
+  const int si = lane + ((plan.rotate_sets && (c->lane_uses[lane] & 1u)) ? ERPL_MAX_OVERLAP : 0);
   ErplSlot& s = c->slot[si];
   ERPL_TRY(slot_init(s));
   ERPL_TRY(slot_reserve(s, (b->n > c->reserve_n) ? b->n : c->reserve_n));
@@ -375,7 +366,7 @@ int enqueue_batch(erpl_ctx* c, int lane, const erpl_batch* b, const erpl_out* o,
   for (int k = 0; k < 2; ++k) { a.res_r[k] = s.res_r[k]; a.res_d[k] = s.res_d[k]; a.res_i[k] = s.res_i[k]; }
   a.res_cap = s.cap;
   a.qcnt = s.d_queue; a.qhead = s.d_queue + (ERPL_MAX_PHASES + 2);
-  if (b->precision == ERPL_PREC_F64_FAST) {
+  if (plan.handoff) {
     ERPL_TRY(slot_reserve_handoff(s));
     a.ext_r = s.ext_r; a.ext_d = s.ext_d; a.ext_i = s.ext_i;
   }
@@ -385,112 +376,29 @@ int enqueue_batch(erpl_ctx* c, int lane, const erpl_batch* b, const erpl_out* o,
   a.traj_ids = o->traj_ids; a.traj = o->traj; a.traj_len = o->traj_len;
   a.counters = s.d_counters;
   a.refill_threshold = c->refill;
+  a.waves_per_simd = plan.waves_per_simd;
+  a.chunk_steps = plan.chunk_steps;
+  a.adopt_lanes = plan.adopt_lanes;
+  a.adopt_spin = c->adopt_spin;
   const ErplTables& T = c->h_tables;
   const int max_blocks = c->max_blocks > 0 ? c->max_blocks : c->n_cu * 8 * (256 / c->block);
-  // the three-wave build pays once three resident waves per SIMD stay busy: a batch that refills them a
-  // few times over (measured +4..12 % from 3 rounds up; between 1 and 3 rounds the rounding of "rounds"
-  // decides), or several batches in flight sharing the SIMDs (131 072 samples x 3 deep: +13 %)
-  const bool dense = b->n >= (int64_t)c->n_cu * 4 * 64 * 3 * 3 ||
-                     (in_flight >= 2 && b->n * in_flight >= (int64_t)c->n_cu * 4 * 64 * 3);
-  a.waves_per_simd = c->waves ? c->waves : (dense ? 3 : 2);
-  // step-chunked launches with compaction in between (erpl_mc_set_chunk); every lane ends within
-  // ceil(max_time / dt) + 1 steps, so that many steps' worth of chunks drains the queue
-  int n_phases = 1;
-  a.chunk_steps = 0;
-  // Automatic step chunks (erpl_mc_set_chunk < 0, the default): compaction between step-chunked launches pays when
-  // trajectories are long AND something else fills the GPU at every chunk barrier - i.e. for overlapped batches
-  // of long flights (measured three deep at 131 072 samples: 15 k-step flights -20 %, 42 k-step flights -17 %,
-  // 2.5 k-step flights +3 %).  Trajectory length is not known in advance, so the choice follows the batches this
-  // context has already finished: their device step counter is copied to pinned memory behind every batch.
-  // Results do not depend on the choice (bitwise).
-  int chunk_steps = c->chunk;
-  if (chunk_steps < 0) {
-    note_finished_batches(c);
-    chunk_steps = (in_flight >= 2 && o->n_traj == 0 && c->seen_mean_steps >= kLongFlightSteps) ? 2048 : 0;
-  }
-  if (chunk_steps > 0 && T.max_time > 0) {
-    const double max_steps = ceil(T.max_time / T.dt_flight) + 2.0;
-    double chunk = (double)chunk_steps;
-    if (ceil(max_steps / chunk) + 1.0 > (double)ERPL_MAX_PHASES) chunk = ceil(max_steps / (double)(ERPL_MAX_PHASES - 2));
-    a.chunk_steps = (int)chunk;
-    n_phases = (int)ceil(max_steps / chunk) + 1;
-  }
-  // Lane adoption (erpl_mc_set_adopt): two sweep launches behind the main one fly out what no running wave
-  // adopted - the first parks its own thin waves once more, the last one never parks.
-  // Automatic (erpl_mc_set_adopt < 0, the default), for batches handed over with erpl_mc_submit_batch:
-  // - The lanes have hardware queues of their own (two streams each: 2 x depth + 2 with the caller's).  The sweeps run
-  //   on the lane's second stream, so the next batch of the lane follows the main launch at once and the few long
-  //   trajectories of a batch finish beside it (131 072 samples, fp32: 32.4 -> 20.8 ms one deep, 16.5 -> 10.8 two
-  //   deep, 11.3 -> 9.0 three deep, 10.6 -> 9.0 eight deep; fp64 throughput build 44.7 -> 38.1 three deep, 37.7 ->
-  //   35.9 eight deep; the gate kernel 129 -> 116 three deep).
-  // - Fewer queues than that (the HIP default of four: the caller's stream + three lanes).  A second stream per lane
-  //   of the default priority would land on another lane's queue, where the hand-overs cost more than they save (four
-  //   queues, three deep: 11.4 -> 25.5 ms).  One of ANOTHER stream priority has a queue of its own - the runtime keeps a
-  //   pool of queues per priority (pool_sweep_streams above) - and the lane runs as it does with 24 queues: sweeps and
-  //   hand-over sweep on that stream, second workspace, next batch directly behind the main launch, three flight
-  //   launches, the adoption limit of the sweep-stream case.  fp64 throughput build, from the first batch of
-  //   kSweepPoolMinBatch samples on (bench shard, five rounds, min / median / max: 24.97 / 25.81 / 26.22 -> 22.57 /
-  //   22.69 / 22.95 ms per pass; the same box with 24 queues 23.09 and 22.67; the gap from the end of a lane's main
-  //   launch to its next rail kernel is gone).  fp32 and the gate were not measured with it
-  //   and stay on the lane's one stream.
-  //   Without the pool streams (smaller batches, erpl_mc_set_sweep_pool(0), one stream priority on the device) no second
-  //   stream is created: the sweeps of the fp64 throughput build follow the main launch on the
-  //   lane's own stream, with two or more batches in flight to fill the SIMDs beside them (bench shard, f64_fast,
-  //   three deep: 30.3 -> 28.2 ms per pass, lane utilisation 0.75 -> 0.98; with the capped hand-over sweep below
-  //   26.5).  The lane's cycle there: main launch 40 ms, the two sweeps 3 + 12, the hand-over
-  //   sweep 8.  Raising the issue priority of the sweeps' waves (s_setprio 1 / 3) and capping the hand-over sweep's
-  //   grid at 1/2 .. 1/8 shortened those dispatches a little and the pass not at all (26.3 -> 26.3 .. 27.0 ms, parent
-  //   spread 0.9; profiles/tail_ab.json): the other lanes' waves lose what the tail gains.  Neither is in here.
-  // erpl_mc_run_batch runs on the caller's one stream with nothing beside it, where a batch is bound by its own longest
-  // trajectory and the hand-overs only lengthen that (32.5 -> 36.1 ms): off.  Step chunks already re-pack every
-  // lane, and chunk-parked records would be adopted straight back (measured 8x slower): exclusive.
-  int adopt = c->adopt;
-  // (limit: fp32 12 / 16 / 24 / 32 / 48 -> 9.30 / 9.05 / 9.00 / 8.93 / 8.97 ms; the one-wave-per-SIMD fp64 builds like it
-  // higher - 24 / 40 / 48 / 56 -> 35.7 / 34.8 / 35.3 / 35.3 ms eight deep, 40.3 / 38.4 / 38.2 / 40.9 three deep)
-  if (adopt < 0) {
-    // (a pool stream is handed in for the fp64 throughput build only: erpl_mc_submit_batch)
-    if (sweep) adopt = pool ? 40 : ((hw_queues_env() >= 2 * in_flight + 2) ? (b->precision == ERPL_PREC_F32 ? 24 : 40) : 0);
-    // (one stream per lane: measured for the fp64 throughput build only, with the limit of the sweep-stream case; the
-    // fp32 build and the gate stay as they were until they are measured there too)
-    else adopt = (ticket > 0 && in_flight >= 2 && b->precision == ERPL_PREC_F64_FAST) ? 40 : 0;
-  }
-  a.adopt_lanes = (o->n_traj == 0 && a.chunk_steps == 0) ? adopt : 0;
-  a.adopt_spin = c->adopt_spin;
-  // two sweeps behind the main launch, the first with adoption still on; ONE where they share the lane's only stream and
-  // the lane's next batch waits behind them (bench shard at four queues, five rounds: 26.36 / 26.66 / 27.12 ms per pass
-  // min / median / max with two, 25.10 / 25.90 / 25.96 with one - DESIGN.md section 3.2)
-  const int adopt_phases = (ticket > 0 && !sweep) ? 2 : 3;
-  if (a.adopt_lanes > 0 && n_phases < adopt_phases) n_phases = adopt_phases;
   void** ev = c->profiling ? (void**)&c->ev[3 * (c->profiled_runs % ERPL_PROFILE_RING)] : nullptr;
-  // with lane adoption the launches behind the main one hold the batch's few longest trajectories: they go to the
-  // lane's sweep stream, and the lane's next batch (other set) follows the main launch at once
-  hipStream_t tail = (sweep && a.adopt_lanes > 0) ? sweep : nullptr;
-  // the hand-over sweep of the fp64 throughput build: where it runs on the stream that also carries the lane's next
-  // batch (a submitted batch without a sweep stream, other batches filling the SIMDs meanwhile) the instantiation whose
-  // waves start beside the throughput kernel's; on a stream of its own, in erpl_mc_run_batch and for trajectory capture
-  // the gate's own (note [3] of erpl_k_config.h)
-  // (not with step chunks: long flights were not measured in this mode and keep the launch sequence they had)
-  // (on a sweep stream from the other priority pool the capped one again: at four queues the other lanes' main launches
-  // keep every SIMD busy, and the lane's set is free for its next batch but one only when the sweep is over - bench shard,
-  // five rounds, 22.57 / 22.69 / 22.95 ms per pass against 22.99 / 23.07 / 23.30 with the 512-register instantiation)
-  const bool beside = ticket > 0 && in_flight >= 2 && o->n_traj == 0 && a.chunk_steps == 0;
-  const int sweep_waves = (beside && (!sweep || pool)) ? 2 : 1;
+  hipStream_t tail = plan.tail_on_sweep ? c->lane_sweep[lane] : nullptr;
   int lrc;
-  if (b->precision == ERPL_PREC_F64) lrc = erpl_launch_f64(a, &T.s64, c->block, max_blocks, n_phases, st, ev, tail, s.main_done, sweep_waves);
-  else if (b->precision == ERPL_PREC_F64_FAST) lrc = erpl_launch_f64f(a, &T.s64, c->block, max_blocks, n_phases, st, ev, tail, s.main_done, sweep_waves);
-  else lrc = erpl_launch_f32(a, &T.s32, c->block, max_blocks, n_phases, st, ev, tail, s.main_done, sweep_waves);
+  if (b->precision == ERPL_PREC_F64) lrc = erpl_launch_f64(a, &T.s64, c->block, max_blocks, plan.n_phases, st, ev, tail, s.main_done, plan.sweep_waves);
+  else if (b->precision == ERPL_PREC_F64_FAST) lrc = erpl_launch_f64f(a, &T.s64, c->block, max_blocks, plan.n_phases, st, ev, tail, s.main_done, plan.sweep_waves);
+  else lrc = erpl_launch_f32(a, &T.s32, c->block, max_blocks, plan.n_phases, st, ev, tail, s.main_done, plan.sweep_waves);
   if (c->profiling && lrc == 0) c->profiled_runs++;
   KERNEL_TRY(lrc);
   hipStream_t last = tail ? tail : st;
-  s.h_counters = ring_slot ? ring_slot : s.own_counters;
+  s.h_counters = ri >= 0 ? &c->ring_counters[4 * ri] : s.own_counters;
   HIP_TRY(hipMemcpyAsync(s.h_counters, s.d_counters, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, last));
   HIP_TRY(hipEventRecord(s.done, last));
-  if (ring_done) HIP_TRY(hipEventRecord(ring_done, last));
+  if (ri >= 0) HIP_TRY(hipEventRecord(c->ring_done[ri], last));
   s.used = true;
-  s.latest_is_run = ticket <= 0;
-  if (ticket > 0) s.ticket = ticket;   // (an erpl_mc_run_batch on this set leaves the ticket: its `done` is later and covers it)
+  s.latest_is_run = ri < 0;
   s.last_n = b->n;
-  s.last_adopt = a.adopt_lanes; s.last_sweep_waves = (b->precision == ERPL_PREC_F64_FAST) ? sweep_waves : 0; s.last_tail = tail != nullptr; s.last_pool = tail != nullptr && pool;
+  s.last_plan = plan;
   s.seq = ++c->batches;
   c->last_slot = si;
   c->lane_uses[lane]++;
@@ -530,8 +438,7 @@ int erpl_mc_create(int device, erpl_ctx** out) {
   c->device = device;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
-  // two streams per lane (main, sweep) + the caller's stream and one more of its own
-  c->depth = (hw_queues_env() >= 2 * ERPL_MAX_OVERLAP + 2) ? ERPL_MAX_OVERLAP : ((hw_queues_env() >= 12) ? (hw_queues_env() - 2) / 2 : 3);
+  c->sched.depth = erpl_default_depth(hw_queues_env());
   hipError_t e = hipMalloc((void**)&c->d_tables, sizeof(ErplTables));
   for (int i = 0; i < 3 * ERPL_PROFILE_RING && e == hipSuccess; ++i) e = hipEventCreate(&c->ev[i]);
   if (e != hipSuccess) { (void)erpl_mc_destroy(c); return erpl_fail(ERPL_ERR_HIP, "hipMalloc/hipEventCreate: %s", hipGetErrorString(e)); }
@@ -588,10 +495,10 @@ int erpl_mc_reserve(erpl_ctx* c, int64_t n) {
   // that have been used before grow too, fresh ones take the size on first use
   // (the second workspace of a lane is only ever used beside a sweep stream: without one the lane's next batch starts
   // behind the sweeps anyway, and it is not allocated - a workspace costs 448 bytes per sample)
-  // (or takes its sweep stream from the other priority pool: the same rule as erpl_mc_submit_batch, by the size asked for)
-  const bool adopt = has_sweep_streams(c) || pool_sweep_streams(c, n);
+  // (the same rule as erpl_mc_submit_batch, by the size asked for and for the build that can take a pool stream)
+  const bool adopt = lane_sweep_kind(c, plan_inputs(c, kSweepPoolPrecision, n)) != ERPL_SWEEP_NONE;
   for (int i = 0; i < 2 * ERPL_MAX_OVERLAP; ++i) {
-    if (i % ERPL_MAX_OVERLAP >= c->depth && !c->slot[i].d_queue) continue;
+    if (i % ERPL_MAX_OVERLAP >= c->sched.depth && !c->slot[i].d_queue) continue;
     if (i >= ERPL_MAX_OVERLAP && !adopt && !c->slot[i].d_queue) continue;
     ERPL_TRY(slot_init(c->slot[i]));
     ERPL_TRY(slot_reserve(c->slot[i], c->reserve_n));
@@ -601,14 +508,14 @@ int erpl_mc_reserve(erpl_ctx* c, int64_t n) {
 
 int erpl_mc_set_chunk(erpl_ctx* c, int chunk_steps) {
   if (!c) return erpl_fail(ERPL_ERR_INVALID, "NULL ctx");
-  c->chunk = chunk_steps < 0 ? -1 : chunk_steps;
+  c->sched.chunk = chunk_steps < 0 ? -1 : chunk_steps;
   return ERPL_OK;
 }
 
 int erpl_mc_set_waves_per_simd(erpl_ctx* c, int waves) {
   if (!c) return erpl_fail(ERPL_ERR_INVALID, "NULL ctx");
   if (waves != 0 && waves != 2 && waves != 3) return erpl_fail(ERPL_ERR_INVALID, "waves per SIMD must be 0 (auto), 2 or 3");
-  c->waves = waves;
+  c->sched.waves = waves;
   return ERPL_OK;
 }
 
@@ -621,14 +528,14 @@ int erpl_mc_set_adopt_spin(erpl_ctx* c, int polls) {
 int erpl_mc_set_adopt(erpl_ctx* c, int lanes) {
   if (!c) return erpl_fail(ERPL_ERR_INVALID, "null context");
   if (lanes > 63) return erpl_fail(ERPL_ERR_INVALID, "adopt lanes must be at most 63");
-  c->adopt = lanes < 0 ? -1 : lanes;
+  c->sched.adopt = lanes < 0 ? -1 : lanes;
   return ERPL_OK;
 }
 
 int erpl_mc_set_sweep_pool(erpl_ctx* c, int mode) {
   if (!c) return erpl_fail(ERPL_ERR_INVALID, "null context");
   if (mode < -1 || mode > 1) return erpl_fail(ERPL_ERR_INVALID, "sweep pool mode must be -1 (by batch size), 0 (never) or 1 (always)");
-  c->sweep_pool = mode;
+  c->sched.sweep_pool = mode;
   if (mode == 0) c->pool_on = false;   // (streams and workspaces that exist stay; batches go back to the lane's one stream)
   return ERPL_OK;
 }
@@ -648,17 +555,17 @@ int erpl_mc_run_batch(erpl_ctx* c, const erpl_batch* b, const erpl_out* o, void*
   int rc = check_batch(c, b, o);
   if (rc != ERPL_OK || b->n == 0) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  return enqueue_batch(c, 0, b, o, (hipStream_t)stream, 1, nullptr, false, 0);
+  return enqueue_batch(c, 0, b, o, (hipStream_t)stream, erpl_plan_batch(batch_inputs(c, b, o, false, 1)), -1);
 }
 
-int erpl_mc_get_overlap(erpl_ctx* c) { return c ? c->depth : 0; }
+int erpl_mc_get_overlap(erpl_ctx* c) { return c ? c->sched.depth : 0; }
 
 int erpl_mc_set_overlap(erpl_ctx* c, int depth) {
   if (!c) return erpl_fail(ERPL_ERR_INVALID, "NULL ctx");
   if (depth < 1 || depth > ERPL_MAX_OVERLAP) return erpl_fail(ERPL_ERR_INVALID, "overlap depth must be 1..%d", ERPL_MAX_OVERLAP);
   HIP_TRY(hipSetDevice(c->device));
   ERPL_TRY(wait_all_host(c));
-  c->depth = depth;
+  c->sched.depth = depth;
   return ERPL_OK;
 }
 
@@ -675,23 +582,22 @@ int erpl_mc_submit_batch(erpl_ctx* c, const erpl_batch* b, const erpl_out* o, vo
   if (b->n == 0) return ERPL_OK;
   HIP_TRY(hipSetDevice(c->device));
   // Short flights (erpl_mc_set_short_flight_overlap) go round fewer lanes: fewer streams busy at a time
-  int depth = c->depth;
+  int depth = c->sched.depth;
   if (c->short_depth > 0 && c->short_depth < depth) {
     note_finished_batches(c);
-    if (c->seen_mean_steps > 0.0 && c->seen_mean_steps < kLongFlightSteps) depth = c->short_depth;
+    if (c->sched.seen_mean_steps > 0.0 && c->sched.seen_mean_steps < kLongFlightSteps) depth = c->short_depth;
   }
+  ErplPlanIn in = batch_inputs(c, b, o, true, depth);
   const int lane = (int)(c->submitted % depth);
   if (!c->lane_stream[lane]) HIP_TRY(hipStreamCreateWithFlags(&c->lane_stream[lane], hipStreamNonBlocking));
-  // the sweep stream only where the process has a hardware queue for it: with the HIP default of four (the caller's
-  // stream + three lanes) a second one per lane of the same priority would push the main streams onto shared queues;
-  // one of another priority has a queue of its own (pool_sweep_streams: the fp64 throughput build, batches that fill the GPU)
-  const bool adopt = has_sweep_streams(c);
-  const bool pool = !adopt && b->precision == ERPL_PREC_F64_FAST && pool_sweep_streams(c, b->n);
-  if ((adopt || pool) && !c->lane_sweep[lane]) {
-    if (pool) HIP_TRY(hipStreamCreateWithPriority(&c->lane_sweep[lane], hipStreamNonBlocking, c->pool_prio));
+  // the lane's sweep stream, created with the first batch that gets one (a lane keeps the stream it has)
+  const ErplSweepKind kind = in.sweep = lane_sweep_kind(c, in);
+  if (kind != ERPL_SWEEP_NONE && !c->lane_sweep[lane]) {
+    if (kind == ERPL_SWEEP_POOL) HIP_TRY(hipStreamCreateWithPriority(&c->lane_sweep[lane], hipStreamNonBlocking, c->pool_prio));
     else HIP_TRY(hipStreamCreateWithFlags(&c->lane_sweep[lane], hipStreamNonBlocking));
-    c->lane_sweep_pool[lane] = pool;
+    c->lane_sweep_pool[lane] = kind == ERPL_SWEEP_POOL;
   }
+  in.lane_stream_pool = c->lane_sweep_pool[lane];
   if (!c->lane_in_ready[lane]) HIP_TRY(hipEventCreateWithFlags(&c->lane_in_ready[lane], hipEventDisableTiming));
   // inputs written on the caller's stream so far are visible to the batch
   HIP_TRY(hipEventRecord(c->lane_in_ready[lane], (hipStream_t)stream));
@@ -713,8 +619,7 @@ int erpl_mc_submit_batch(erpl_ctx* c, const erpl_batch* b, const erpl_out* o, vo
     if (c->slot[i].h_counters == &c->ring_counters[4 * ri]) c->slot[i].h_counters = c->slot[i].own_counters;
   memset(&c->ring_counters[4 * ri], 0, 4 * sizeof(unsigned long long));
   c->ring_ticket[ri] = 0;
-  ERPL_TRY(enqueue_batch(c, lane, b, o, c->lane_stream[lane], depth, (adopt || pool) ? c->lane_sweep[lane] : nullptr,
-                         pool && c->lane_sweep_pool[lane], t_new, &c->ring_counters[4 * ri], c->ring_done[ri]));
+  ERPL_TRY(enqueue_batch(c, lane, b, o, c->lane_stream[lane], erpl_plan_batch(in), ri));
   c->ring_ticket[ri] = t_new;
   ++c->submitted;
   if (ticket) *ticket = c->submitted;
@@ -878,7 +783,7 @@ int erpl_mc_debug_counters(erpl_ctx* c, double* out16) {
   int streams = 0;
   for (int i = 0; i < ERPL_MAX_OVERLAP; ++i) streams += (c->lane_stream[i] != nullptr) + (c->lane_sweep[i] != nullptr);
   out16[4] = (double)hw_queues_env(); out16[5] = (double)streams;
-  out16[6] = (double)ls.last_adopt; out16[7] = (double)(ls.last_sweep_waves + (ls.last_tail ? 16 : 0) + (ls.last_pool ? 32 : 0));
+  out16[6] = (double)ls.last_plan.adopt_lanes; out16[7] = (double)erpl_plan_word7(ls.last_plan);
   return ERPL_OK;
 }
 

@@ -10,6 +10,7 @@
 #include <thread>
 #include <vector>
 
+#include "erpl_plan.h"
 #include "erpl_tables.h"
 
 // Formats the text erpl_mc_last_error returns and hands `code` back.  The thread-local buffer is defined once, in
@@ -65,15 +66,12 @@ struct ErplSlot {
   hipEvent_t done = nullptr;                // everything of the slot's latest batch has run
   hipEvent_t main_done = nullptr;           // its main flight launch has (the sweep stream waits for this)
   bool used = false;                        // `done` has been recorded at least once
-  int64_t ticket = 0;                       // last batch submitted through this slot
   unsigned long long* own_counters = nullptr; // pinned: d_counters[0..3] of the slot's latest erpl_mc_run_batch
   unsigned long long* h_counters = nullptr; // pinned host copy of d_counters[0..3] of the slot's latest batch: `own_counters`,
                                             // or the ticket record of the batch (erpl_mc_submit_batch)
   bool latest_is_run = false;               // the slot's latest batch came through erpl_mc_run_batch (no ticket record)
   int64_t last_n = 0, seq = 0;              // its size and its position in the order of all batches of the context
-  int last_adopt = 0, last_sweep_waves = 0; // how it was scheduled: adoption limit of its main launch, instantiation of its
-  bool last_tail = false, last_pool = false; //  hand-over sweep, sweeps on the lane's second stream, that stream from the
-                                            //   other priority pool (erpl_mc_debug_counters)
+  ErplPlan last_plan;                       // how it was scheduled (erpl_mc_debug_counters words 6 and 7)
 };
 
 struct erpl_ctx {
@@ -88,16 +86,15 @@ struct erpl_ctx {
   // the lane's NEXT batch - on the other set - starts when the main launch is over and overlaps the sweeps:
   // batches of equal length submitted together run in step, and without this the tails of a whole round of
   // them met on an otherwise empty GPU before the next round could start.
-  // Sweep streams and second sets exist only where the process has a hardware queue per stream (has_sweep_streams in
-  // erpl_api.hip) or, at the HIP default of four queues, where the sweep streams come from the other stream-priority
-  // pool (pool_sweep_streams there); otherwise the sweeps stay on the lane's main stream and the lane on its first set.
+  // Sweep streams and second sets exist only where the process has a hardware queue per stream or, at the HIP default
+  // of four queues, where the sweep streams come from the other stream-priority pool (erpl_sweep_stream in erpl_plan.h);
+  // otherwise the sweeps stay on the lane's main stream and the lane on its first set.
   ErplSlot slot[2 * ERPL_MAX_OVERLAP];
   hipStream_t lane_stream[ERPL_MAX_OVERLAP] = {};
   hipStream_t lane_sweep[ERPL_MAX_OVERLAP] = {};
   bool lane_sweep_pool[ERPL_MAX_OVERLAP] = {};   // lane_sweep[i] was created at the other pool's priority
   hipEvent_t lane_in_ready[ERPL_MAX_OVERLAP] = {};
   unsigned lane_uses[ERPL_MAX_OVERLAP] = {};   // batches the lane has taken: parity picks the set
-  int depth = 3;                  // slots erpl_mc_submit_batch cycles through (erpl_mc_create: 8 with enough hardware queues)
   int64_t submitted = 0;          // tickets handed out
   // One record per ticket: its own completion event and its own pinned copy of the batch's counters, so
   // that erpl_mc_check_batch(T) waits for T alone and reports T's own lost records however often T's workspace has
@@ -111,16 +108,14 @@ struct erpl_ctx {
   int last_slot = 0;              // slot of the most recent batch (erpl_mc_last_stats)
   int64_t reserve_n = 0;          // erpl_mc_reserve request, applied to a slot when it is first used
   int adopt_spin = 1 << 22;       // polls of an adopting lane for a claimed record's ready word (erpl_mc_set_adopt_spin)
-  int adopt = -1;                 // lane adoption: flying lanes at or below which a wave hands its lanes over; 0 = off; < 0 = by batch
-  int sweep_pool = -1;            // erpl_mc_set_sweep_pool: -1 = from the first batch that fills the GPU, 0 = never, 1 = always
-  bool pool_on = false;           //   the lanes take their sweep streams from the other priority pool (latched)
+  // The scheduling settings and history of the context, in the struct the policy reads (erpl_plan.h; its defaults are the
+  // context's): depth (erpl_mc_create), adopt, sweep_pool, chunk, waves (their setters), seen_mean_steps.
+  ErplSched sched;
+  bool pool_on = false;           // the lanes take their sweep streams from the other priority pool (latched, erpl_sweep_stream)
   bool pool_known = false, pool_exists = false;   // hipDeviceGetStreamPriorityRange has been asked; it reports two priorities
   int pool_prio = 0;              //   the priority the pool streams are created at
-  int chunk = -1;                 // steps per launch between compactions; 0 = one launch; < 0 = by the batches seen so far
   int short_depth = 4;            // erpl_mc_set_short_flight_overlap
-  double seen_mean_steps = 0.0;   // physics RK4 steps per trajectory of the most recent COMPLETED batch
   int64_t seen_seq = 0, batches = 0;
-  int waves = 0;   // 0 = choose by batch size
   // one wave per workgroup: a finished wave frees its slot for the next batch at once (measured 2-5 %
   // over 256-thread workgroups, alone and overlapped); refill as soon as a lane is idle (best: 1..4)
   int block = 64, max_blocks = 0, refill = 1;

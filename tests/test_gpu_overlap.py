@@ -439,6 +439,40 @@ def test_default_overlap_depth_follows_the_hardware_queues(engine):
         eng.close()
 
 
+def test_scheduling_counters_follow_the_plan_table(engine):
+    """The library in this 24-queue process against the table tests/test_plan.py checks csrc/erpl_plan.h with: one
+    4 099-sample batch per row (words 6 and 7 of these rows do not depend on the size), scheduled as the row says, and
+    erpl_mc_debug_counters reports the row's adoption limit and sweep word."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan_cases.json")) as f:
+        table = json.load(f)
+    rows = {r["id"]: (dict(table["defaults"], **r["in"]), r["out"]) for r in table["cases"]}
+    assert int(os.environ["GPU_MAX_HW_QUEUES"]) == 24
+    engine.set_config(H.make_config("liquid"))
+    rocket, motor, wm = models.Rocket(), models.LiquidMotor(), models.WindModel()
+    dbs = {p: sampling.synthetic_dispersions(4099, rocket, motor, wm, H.EXAMPLE_IC, engine.device, precision=_abi.PRECISIONS[p],
+                                             seed=31, engine=engine) for p in ("f32", "f64_fast")}
+    depth = engine.get_overlap()
+    try:
+        engine.set_overlap(8)
+        for rid in ("R1", "R4", "S1", "S2", "S4", "S5"):
+            inp, out = rows[rid]
+            assert inp["queues"] == 24 and inp["depth"] == 8
+            engine.set_adopt(inp["adopt"])
+            engine.set_chunk(inp["chunk"])
+            capture = dict(traj_ids=list(range(inp["n_traj"])), traj_stride=50, traj_cap=64) if inp["n_traj"] else {}
+            engine.run(dbs[inp["precision"]], overlap=inp["entry"] == "submit", **capture)
+            engine.wait()
+            engine.synchronize()
+            dc = engine.debug_counters()
+            assert dc[3] == 0 and (int(dc[6]), int(dc[7])) == (out["w6"], out["w7"]), (rid, dc[3:8])
+    finally:
+        engine.set_adopt(-1)
+        engine.set_chunk(-1)
+        engine.set_overlap(depth)
+
+
 @pytest.mark.parametrize("depth", [1, 2, 5])
 def test_tickets_are_waitable_one_by_one_in_any_order(engine, depth):
     """Every lane alternates between two workspaces and runs a batch's sweep launches on a second stream, so two

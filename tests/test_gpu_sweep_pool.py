@@ -19,7 +19,7 @@ from test_gpu_four_queues import ROOT, _CHILD_HEAD, assert_same, engine, make_ba
 
 pytestmark = pytest.mark.gpu
 
-THRESHOLD = 9216      # kSweepPoolMinBatch of erpl_api.hip: the automatic rule switches the pool on from this batch size
+THRESHOLD = 9216      # kSweepPoolMinBatch of erpl_plan.h: the automatic rule switches the pool on from this batch size
 
 # two rounds over the same batches: the second one reuses every lane and both workspaces of each
 _FORCED_ON = r"""
