@@ -191,6 +191,29 @@ class ErplCorrResult(C.Structure):
                 ("regression_ok", C.c_int32), ("rank_regression_ok", C.c_int32)]
 
 
+# erpl_mc_bootstrap
+BOOT_MAX_ROWS = 4
+BOOT_ROW_EXTRA = 16
+BOOT_MAX_REPLICATES = 65536
+BOOT_MAX_STATS = BOOT_MAX_ROWS * (2 + ANALYSIS_MAX_Q)
+
+
+class ErplBootSpec(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("rows", C.c_int32 * BOOT_MAX_ROWS), ("n_q", C.c_int32),
+                ("replicates", C.c_int32), ("reserved", C.c_int32), ("q", _Q), ("level", C.c_double),
+                ("seed", C.c_uint64)]
+
+
+class ErplBootStat(C.Structure):
+    _fields_ = [("estimate", C.c_double), ("rep_mean", C.c_double), ("se", C.c_double), ("lo", C.c_double),
+                ("hi", C.c_double), ("finite", C.c_int64)]
+
+
+class ErplBootstrap(C.Structure):
+    _fields_ = [("n", C.c_int64), ("count", C.c_int64), ("n_masked", C.c_int64), ("n_non_finite", C.c_int64),
+                ("n_stats", C.c_int32), ("replicates", C.c_int32), ("stat", ErplBootStat * BOOT_MAX_STATS)]
+
+
 LIB_NAME = "liberpl_mc.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
@@ -210,6 +233,7 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_histogram_defaults", "erpl_mc_histogram", "erpl_mc_histogram_xy",
            "erpl_mc_dispersion_defaults", "erpl_mc_dispersion",
            "erpl_mc_correlation_defaults", "erpl_mc_correlation",
+           "erpl_mc_bootstrap_defaults", "erpl_mc_bootstrap", "erpl_mc_bootstrap_indices",
            "erpl_mc_legacy_random_streams_device", "erpl_mc_legacy_wind_profiles_device")
 
 _lib = None
@@ -289,6 +313,10 @@ def load_library(path=None):
     lib.erpl_mc_correlation_defaults.argtypes = [C.POINTER(ErplCorrSpec)]
     lib.erpl_mc_correlation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplCorrSpec),
                                         C.POINTER(ErplCorrResult), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erpl_mc_bootstrap_defaults.argtypes = [C.POINTER(ErplBootSpec)]
+    lib.erpl_mc_bootstrap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplBootSpec),
+                                      C.POINTER(ErplBootstrap), C.c_void_p, C.c_void_p]
+    lib.erpl_mc_bootstrap_indices.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]
     lib.erpl_mc_legacy_random_streams_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                                          C.c_int32, C.c_void_p]
     lib.erpl_mc_legacy_wind_profiles_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 9 + \

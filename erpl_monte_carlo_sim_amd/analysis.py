@@ -329,3 +329,60 @@ def drivers(summary, factors, factor_names, status=None, engine=None, rows=None,
     out["n_samples"], out["n_outliers"] = int(res.n_valid), int(res.n_outliers)
     out["ranking"] = rank_drivers(out, factor_names, ranks)
     return out
+
+
+# ---------------------------------------------------------------------------------- how sure the statistics are
+def bootstrap_indices(seed, replicate, m, first=0, count=None):
+    """The dense population indices (int64 NumPy array) replicate `replicate` of a bootstrap with `seed` draws from a
+    population of m, draws first .. first + count - 1 (default: all m): erpl_mc_bootstrap_indices, the host copy of the
+    device's draws.  Dense index d is the d-th sample, in sample order, that the filter keeps and whose requested rows are
+    all finite.  Needs the library, no GPU."""
+    from . import _abi
+    lib = _abi.load_library()
+    m, first = int(m), int(first)
+    count = m - first if count is None else int(count)
+    out = np.empty(max(count, 0), dtype=np.int64)
+    _abi.check(lib, lib.erpl_mc_bootstrap_indices(int(seed) & 0xFFFFFFFFFFFFFFFF, int(replicate), m, first, count,
+                                                  out.ctypes.data), "erpl_mc_bootstrap_indices")
+    return out
+
+
+def _interval(s):
+    return {k: s[k] for k in ("estimate", "se", "lo", "hi")}
+
+
+def confidence_intervals(summary, status=None, engine=None, rows=None, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95),
+                         replicates=2000, level=0.95, seed=0):
+    """Bootstrap confidence intervals of the statistics `native_statistics` reports, on the device: erpl_mc_analyze for
+    the reason bytes, then erpl_mc_bootstrap over the samples that carry none.  rows: up to 4 summary rows (default
+    apogee, range, flight time).  Returns, per row name (ROW_NAMES), {'mean': {estimate, se, lo, hi}, 'std': {..},
+    'percentiles': [{..}, ..]} - se the bootstrap standard error, (lo, hi) the `level` percentile interval - plus
+    'n_samples', 'n_outliers', 'count' (the population: kept and finite in every row), 'quantiles', 'level',
+    'replicates' and 'seed'."""
+    engine, res, why = _filter(summary, status, engine)
+    b = engine.bootstrap(summary, why, rows=rows, quantiles=quantiles, replicates=replicates, level=level, seed=seed)
+    out = {ROW_NAMES[r]: {"mean": _interval(s["mean"]), "std": _interval(s["std"]),
+                          "percentiles": [_interval(p) for p in s["quantiles"]]} for r, s in zip(b["rows"], b["stats"])}
+    out["n_samples"], out["n_outliers"], out["count"] = int(res.n_valid), int(res.n_outliers), b["count"]
+    out["quantiles"], out["level"], out["replicates"], out["seed"] = b["q"], b["level"], b["replicates"], b["seed"]
+    return out
+
+
+def cep_interval(summary, status=None, engine=None, target=None, quantiles=(0.5, 0.9, 0.95, 0.99), replicates=2000,
+                 level=0.95, seed=0):
+    """The CEP with its confidence interval: erpl_mc_analyze for the reason bytes, erpl_mc_dispersion for the miss distance
+    about `target` ((x, y), default the launch site) of every sample, then erpl_mc_bootstrap on that row (`extra`) with the
+    dispersion's quantile fractions.  Returns {'cep': {estimate, se, lo, hi} or None without 0.5 among the quantiles,
+    'quantiles': [{..}, ..] in the order of `quantiles`, 'mean': {..}, 'std': {..}, 'q', 'count', 'n_samples',
+    'n_outliers', 'level', 'replicates', 'seed'}; the estimates are the bits `landing_dispersion` reports."""
+    from . import _abi
+    engine, res, why = _filter(summary, status, engine)
+    quantiles = [float(q) for q in quantiles]
+    disp = engine.dispersion(summary, why, centre=(0.0, 0.0) if target is None else target, quantiles=quantiles, miss=True)
+    b = engine.bootstrap(summary, why, rows=[_abi.BOOT_ROW_EXTRA], quantiles=quantiles, replicates=replicates, level=level,
+                         seed=seed, extra=disp["miss_distance"])
+    s = b["stats"][0]
+    qs = [_interval(p) for p in s["quantiles"]]
+    return {"cep": qs[quantiles.index(0.5)] if 0.5 in quantiles else None, "quantiles": qs, "mean": _interval(s["mean"]),
+            "std": _interval(s["std"]), "q": quantiles, "count": b["count"], "n_samples": int(res.n_valid),
+            "n_outliers": int(res.n_outliers), "level": b["level"], "replicates": b["replicates"], "seed": b["seed"]}

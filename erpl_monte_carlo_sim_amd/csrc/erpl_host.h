@@ -48,6 +48,14 @@ struct DistHost {
   ErplDistMoments mom;
 };
 
+// erpl_mc_bootstrap: pinned copies of what its launches hand back - the population counters, the estimates (summary rows,
+// `extra`) and the summary over the replicates in groups of ERPL_ANALYSIS_MAX_ROWS statistics
+struct BootHost {
+  unsigned long long counter[4];
+  ErplAnaResult est[2];
+  ErplAnaResult sum[(ERPL_BOOT_MAX_STATS + ERPL_ANALYSIS_MAX_ROWS - 1) / ERPL_ANALYSIS_MAX_ROWS];
+};
+
 // Slot 0 serves erpl_mc_run_batch (on the caller's stream); slots 0..depth-1 serve erpl_mc_submit_batch
 // round-robin, each on its own internal stream.  Whoever uses a slot first waits (on the device) for
 // the slot's previous batch and records `done` behind its own kernels.
@@ -139,6 +147,11 @@ struct erpl_ctx {
   ErplCorrOut* corr_host = nullptr;
   char* corr_buf = nullptr;
   size_t corr_cap = 0;
+  // erpl_mc_bootstrap: pinned mirror of its results and one buffer that grows with n * n_rows and with the replicates:
+  // population bytes, the dense rows, their sorted copies and positions, sort keys and scratch, the replicate matrix
+  BootHost* boot_host = nullptr;
+  char* boot_buf = nullptr;
+  size_t boot_cap = 0;
   // erpl_mc_legacy_random_streams_device / _wind_profiles_device: one device buffer (flag, op tables, knot constants, the
   // MT19937 states of a tile and two sets of its accepted pairs) and its pinned staging (the tables on their way up, r2
   // down and f up, per set), both bounded by the tile; an event per set behind the tile's copy to the host

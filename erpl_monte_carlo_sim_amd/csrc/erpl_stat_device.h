@@ -1,5 +1,6 @@
-// erpl_stat_device.h — what the statistics units (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip) share:
-// the grid of their streaming passes, the order-preserving keys and THE fixed-order reduction.  Internal: never installed.
+// erpl_stat_device.h — what the statistics units (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip,
+// erpl_bootstrap.hip) share: the grid of their streaming passes, the order-preserving keys and THE fixed-order reduction.
+// Internal: never installed.
 //
 // The order is the contract: the last bit of every sum and the sign of a zero minimum depend on it, and "the same bits in
 // every call" rests on it.  It is defined here and nowhere else:

@@ -1,7 +1,8 @@
 // erpl_stats_api.hip — host halves of the analysis entry points of the C ABI (include/erpl_mc.h): erpl_mc_analyze,
-// erpl_mc_histogram, erpl_mc_histogram_xy, erpl_mc_dispersion, erpl_mc_correlation and their defaults.  Argument checks,
-// workspace, launches (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip) and what the host finishes in
-// double precision.  The refusals come in one order everywhere - spec fields, n, pointers, context - and need no device.
+// erpl_mc_histogram, erpl_mc_histogram_xy, erpl_mc_dispersion, erpl_mc_correlation, erpl_mc_bootstrap and their defaults.
+// Argument checks, workspace, launches (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip,
+// erpl_bootstrap.hip) and what the host finishes in double precision.  The refusals come in one order everywhere - spec
+// fields, n, pointers, context (erpl_mc_bootstrap: the order its header comment lists) - and need no device.
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "erpl_host.h"
+#include "erpl_philox.h"
 
 namespace {
 
@@ -577,6 +579,226 @@ int erpl_mc_correlation(erpl_ctx* c, const double* factors, const double* summar
       }
     }
     (pass ? result->rank_regression_ok : result->regression_ok) = ok ? 1 : 0;
+  }
+  return ERPL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------- erpl_mc_bootstrap
+namespace {
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" {
+
+int erpl_mc_bootstrap_defaults(erpl_boot_spec* spec) {
+  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  memset(spec, 0, sizeof(*spec));
+  spec->n_rows = 3;
+  spec->rows[0] = ERPL_SUM_APOGEE_ALT; spec->rows[1] = ERPL_SUM_RANGE; spec->rows[2] = ERPL_SUM_FLIGHT_TIME;
+  spec->n_q = 5;
+  const double q[5] = {0.05, 0.25, 0.5, 0.75, 0.95};   // erpl_mc_analysis_defaults
+  for (int j = 0; j < 5; ++j) spec->q[j] = q[j];
+  spec->replicates = 2000;
+  spec->level = 0.95;
+  spec->seed = 0;
+  return ERPL_OK;
+}
+
+int erpl_mc_bootstrap_indices(uint64_t seed, int64_t replicate, int64_t m, int64_t first, int64_t count, int64_t* out) {
+  if (!out) return erpl_fail(ERPL_ERR_INVALID, "out is NULL");
+  if (m <= 0 || m >= (1ll << 31)) return erpl_fail(ERPL_ERR_INVALID, "m = %lld outside 1..2^31 - 1", (long long)m);
+  if (replicate < 0 || replicate > 0xffffffffll)
+    return erpl_fail(ERPL_ERR_INVALID, "replicate = %lld outside 0..2^32 - 1", (long long)replicate);
+  if (first < 0) return erpl_fail(ERPL_ERR_INVALID, "first = %lld is negative", (long long)first);
+  if (count < 0) return erpl_fail(ERPL_ERR_INVALID, "count = %lld is negative", (long long)count);
+  if (first > m || count > m - first)
+    return erpl_fail(ERPL_ERR_INVALID, "first + count = %lld + %lld is beyond m = %lld", (long long)first, (long long)count,
+                     (long long)m);
+  for (int64_t t = first; t < first + count;) {
+    uint64_t A, B;
+    erpl_boot_pair(seed, (uint32_t)replicate, (uint64_t)(t >> 1), &A, &B);
+    if ((t & 1) == 0) {
+      out[t - first] = (int64_t)erpl_boot_index(A, (uint64_t)m);
+      ++t;
+      if (t >= first + count) break;
+    }
+    out[t - first] = (int64_t)erpl_boot_index(B, (uint64_t)m);
+    ++t;
+  }
+  return ERPL_OK;
+}
+
+int erpl_mc_bootstrap(erpl_ctx* c, const double* summary, const double* extra, const uint8_t* mask, int64_t n,
+                      const erpl_boot_spec* spec, erpl_bootstrap* result, double* replicates_out, void* stream) {
+  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  if (!summary) return erpl_fail(ERPL_ERR_INVALID, "summary is NULL");
+  if (!result) return erpl_fail(ERPL_ERR_INVALID, "result is NULL");
+  if (n <= 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
+  if (n >= (1ll << 31))
+    return erpl_fail(ERPL_ERR_INVALID, "n = %lld: the draws and the sort carry 31-bit sample indices", (long long)n);
+  if (spec->n_rows < 1 || spec->n_rows > ERPL_BOOT_MAX_ROWS)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->n_rows = %d outside 1..%d", spec->n_rows, ERPL_BOOT_MAX_ROWS);
+  if (spec->n_q < 0 || spec->n_q > ERPL_ANALYSIS_MAX_Q)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->n_q = %d outside 0..%d", spec->n_q, ERPL_ANALYSIS_MAX_Q);
+  if (spec->replicates < 1 || spec->replicates > ERPL_BOOT_MAX_REPLICATES)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->replicates = %d outside 1..%d", spec->replicates, ERPL_BOOT_MAX_REPLICATES);
+  for (int j = 0; j < spec->n_rows; ++j) {
+    if (spec->rows[j] < 0 || spec->rows[j] > ERPL_BOOT_ROW_EXTRA)
+      return erpl_fail(ERPL_ERR_INVALID, "spec->rows[%d] = %d outside 0..%d", j, spec->rows[j], ERPL_BOOT_ROW_EXTRA);
+    for (int k = 0; k < j; ++k)
+      if (spec->rows[k] == spec->rows[j]) return erpl_fail(ERPL_ERR_INVALID, "spec->rows[%d] = %d is listed twice", j, spec->rows[j]);
+  }
+  for (int j = 0; j < spec->n_rows; ++j)
+    if (spec->rows[j] == ERPL_BOOT_ROW_EXTRA && !extra)
+      return erpl_fail(ERPL_ERR_INVALID, "extra is NULL but spec->rows[%d] = %d (ERPL_BOOT_ROW_EXTRA)", j, spec->rows[j]);
+  ERPL_TRY(check_quantiles(spec->q, spec->n_q));
+  if (!(spec->level > 0.0 && spec->level < 1.0)) return erpl_fail(ERPL_ERR_INVALID, "spec->level = %g outside (0, 1)", spec->level);
+  if (!c) return erpl_fail(ERPL_ERR_INVALID, "ctx is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int R = spec->n_rows, nq = spec->n_q, ns = 2 + nq, n_stats = R * ns, B = spec->replicates;
+  const size_t un = (size_t)n, uB = (size_t)B;
+
+  // the buffer: [pop n bytes][src n u32][count][x, sorted R n doubles each][pos R n u32][keys 2n u64][idx 2n u32]
+  // [scratch of the select / the sort][zero bytes B][replicates n_stats B doubles unless the caller keeps them]
+  size_t temp_bytes = 0;
+  LAUNCH_TRY(erpl_boot_temp_bytes(n, &temp_bytes), "select / radix sort sizing failed");
+  temp_bytes = align256(std::max(temp_bytes, (size_t)256));
+  const size_t off_src = align256(un);
+  const size_t off_count = off_src + align256(4 * un);
+  const size_t off_x = off_count + 256;
+  const size_t off_sorted = off_x + (size_t)R * align256(8 * un);
+  const size_t off_pos = off_sorted + (size_t)R * align256(8 * un);
+  const size_t off_keys = off_pos + (size_t)R * align256(4 * un);
+  const size_t off_idx = off_keys + align256(16 * un);
+  const size_t off_temp = off_idx + align256(8 * un);
+  const size_t off_zero = off_temp + temp_bytes;
+  const size_t off_rep = off_zero + align256(uB);
+  const size_t need = off_rep + (replicates_out ? 0 : 8 * uB * (size_t)n_stats);
+  ERPL_TRY(erpl_first_use(c->corr_work, c->corr_host));   // the population pass and its counters
+  ERPL_TRY(erpl_first_use(c->ana_work, c->ana_host));     // the estimates and the summary over the replicates
+  if (!c->boot_host) HIP_TRY(hipHostMalloc((void**)&c->boot_host, sizeof(BootHost), hipHostMallocDefault));
+  ERPL_TRY(erpl_grow(c->boot_buf, c->boot_cap, need));
+  char* buf = c->boot_buf;
+  BootHost& h = *c->boot_host;
+
+  ErplBootPrep p;
+  memset(&p, 0, sizeof(p));
+  ErplCorrArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.mask = mask; pa.n = n; pa.n_vars = R; pa.work = c->corr_work; pa.pop = (uint8_t*)buf;
+  for (int j = 0; j < R; ++j) {
+    p.var[j] = spec->rows[j] == ERPL_BOOT_ROW_EXTRA ? extra : summary + (size_t)spec->rows[j] * un;
+    pa.var[j] = p.var[j];
+    p.x[j] = (double*)(buf + off_x + (size_t)j * align256(8 * un));
+    p.sorted[j] = (double*)(buf + off_sorted + (size_t)j * align256(8 * un));
+    p.pos[j] = (uint32_t*)(buf + off_pos + (size_t)j * align256(4 * un));
+  }
+  p.pop = pa.pop; p.src = (uint32_t*)(buf + off_src); p.count = (unsigned long long*)(buf + off_count);
+  p.keys = (unsigned long long*)(buf + off_keys); p.idx = (uint32_t*)(buf + off_idx);
+  p.temp = buf + off_temp; p.temp_bytes = temp_bytes; p.n = n; p.n_rows = R;
+  uint8_t* zero = (uint8_t*)(buf + off_zero);
+  double* rep = replicates_out ? replicates_out : (double*)(buf + off_rep);
+
+  KERNEL_TRY(erpl_launch_corr_population(pa, stream));
+  HIP_TRY(hipMemcpyAsync(h.counter, &c->corr_work->out.counter[0], sizeof(h.counter), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int64_t m = (int64_t)h.counter[0];
+  memset(result, 0, sizeof(*result));
+  result->n = n; result->count = m; result->n_masked = (int64_t)h.counter[1]; result->n_non_finite = (int64_t)h.counter[2];
+  result->n_stats = n_stats; result->replicates = B;
+  const double nan = NAN;
+  for (int s = 0; s < ERPL_BOOT_MAX_STATS; ++s) {
+    erpl_boot_stat& o = result->stat[s];
+    o.estimate = o.rep_mean = o.se = o.lo = o.hi = nan;
+    o.finite = 0;
+  }
+  if (m == 0) {
+    if (replicates_out) {   // every replicate of an empty population is NaN: the all-ones byte pattern is one
+      HIP_TRY(hipMemsetAsync(replicates_out, 0xff, 8 * uB * (size_t)n_stats, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    return ERPL_OK;
+  }
+
+  // the estimates, by the passes of erpl_mc_analyze over the n samples with the population bytes as the mask: the summary
+  // rows in one launch, `extra` as a one-row summary in a second
+  ErplAnaArgs e;
+  memset(&e, 0, sizeof(e));
+  e.summary = summary; e.why = pa.pop; e.work = c->ana_work; e.n = n; e.n_q = nq;
+  for (int k = 0; k < nq; ++k) e.q[k] = spec->q[k];
+  int est_of[ERPL_BOOT_MAX_ROWS], has_extra = 0;   // row j of the spec: est[0].row[est_of[j]], or est[1].row[0] (-1)
+  for (int j = 0; j < R; ++j) {
+    if (spec->rows[j] == ERPL_BOOT_ROW_EXTRA) { est_of[j] = -1; has_extra = 1; }
+    else { est_of[j] = e.n_rows; e.rows[e.n_rows++] = spec->rows[j]; }
+  }
+  if (e.n_rows > 0) {
+    KERNEL_TRY(erpl_launch_row_stats(e, stream));
+    HIP_TRY(hipMemcpyAsync(&h.est[0], &c->ana_work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, st));
+  }
+  if (has_extra) {
+    e.summary = extra; e.n_rows = 1; e.rows[0] = 0;
+    KERNEL_TRY(erpl_launch_row_stats(e, stream));
+    HIP_TRY(hipMemcpyAsync(&h.est[1], &c->ana_work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, st));
+  }
+
+  // prepare, then the replicates
+  p.m = m;
+  LAUNCH_TRY(erpl_launch_boot_compact(p, stream), "select failed");
+  LAUNCH_TRY(erpl_launch_boot_prepare(p, stream), "prepare failed");
+  ErplBootArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int j = 0; j < R; ++j) { a.x[j] = p.x[j]; a.sorted[j] = p.sorted[j]; a.pos[j] = p.pos[j]; }
+  a.rep = rep; a.seed = spec->seed; a.m = (uint32_t)m; a.n_rows = R; a.n_q = nq; a.replicates = B;
+  for (uint64_t top = (uint64_t)m - 1; top; top >>= 8) ++a.n_digits;
+  for (int k = 0; k < nq; ++k) {   // the ranks of erpl_ana_finish_first, the same in every replicate
+    const double pos = spec->q[k] * (double)(m - 1);
+    int64_t lo = (int64_t)floor(pos);
+    if (lo > m - 1) lo = m - 1;
+    a.rank[2 * k] = (uint32_t)lo;
+    a.rank[2 * k + 1] = (uint32_t)(lo + 1 < m ? lo + 1 : m - 1);
+    a.frac[k] = pos - floor(pos);
+  }
+  KERNEL_TRY(erpl_launch_boot_replicates(a, stream));
+
+  // the summary over the replicates: the [n_stats][B] matrix as rows of length B through the same passes, 16 at a time
+  const double tail = (1.0 - spec->level) / 2;
+  HIP_TRY(hipMemsetAsync(zero, 0, uB, st));
+  ErplAnaArgs g;
+  memset(&g, 0, sizeof(g));
+  g.why = zero; g.work = c->ana_work; g.n = B; g.n_q = 2; g.q[0] = tail; g.q[1] = 1.0 - tail;
+  for (int first = 0, k = 0; first < n_stats; first += ERPL_ANALYSIS_MAX_ROWS, ++k) {
+    g.summary = rep + (size_t)first * uB;
+    g.n_rows = std::min(n_stats - first, (int)ERPL_ANALYSIS_MAX_ROWS);
+    for (int j = 0; j < g.n_rows; ++j) g.rows[j] = j;
+    KERNEL_TRY(erpl_launch_row_stats(g, stream));
+    HIP_TRY(hipMemcpyAsync(&h.sum[k], &c->ana_work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+
+  for (int j = 0; j < R; ++j) {
+    erpl_row_stats est;
+    finish_row_stats(est_of[j] < 0 ? h.est[1].row[0] : h.est[0].row[est_of[j]], spec->q, nq, true, est);
+    for (int k = 0; k < ns; ++k) {
+      const int s = j * ns + k;
+      erpl_boot_stat& o = result->stat[s];
+      o.estimate = k == 0 ? est.mean : k == 1 ? est.std : est.quantile[k - 2];
+      const ErplAnaRow& row = h.sum[s / ERPL_ANALYSIS_MAX_ROWS].row[s % ERPL_ANALYSIS_MAX_ROWS];
+      erpl_row_stats over;
+      finish_row_stats(row, g.q, 2, true, over);
+      o.finite = over.count;
+      // the constant rule of erpl_mc_correlation: a statistic with min == max over its replicates has no spread, whatever
+      // sum / count makes of that value
+      const bool constant = over.count > 0 && row.vmin == row.vmax;
+      o.rep_mean = constant ? row.vmin : over.mean;
+      o.se = over.count == 0 ? nan : (constant ? 0.0 : sqrt(row.m2 / (double)(over.count - 1)));
+      o.lo = over.quantile[0];
+      o.hi = over.quantile[1];
+    }
   }
   return ERPL_OK;
 }

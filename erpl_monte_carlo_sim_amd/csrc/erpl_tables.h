@@ -315,3 +315,43 @@ int erpl_launch_corr_gram(const ErplCorrArgs& a, int which, void* stream);   // 
 int erpl_launch_corr_ranks(const ErplCorrArgs& a, const double* x, double* rank_row, unsigned long long* keys, uint32_t* idx,
                            void* temp, size_t* temp_bytes, void* stream);
 }
+
+// ---- erpl_mc_bootstrap (erpl_bootstrap.hip) ----
+// Prepare works on the dense population (m members, in sample order): per requested row the values x[d], the same values
+// ascending (sorted[p]) and the sorted position of every member (pos[d]).  The replicate kernel then needs 32-bit
+// positions only: the k-th smallest position a replicate drew names its k-th order statistic.
+struct ErplBootPrep {
+  const double* var[ERPL_BOOT_MAX_ROWS];   // [n] each: the requested rows (summary rows or `extra`)
+  const uint8_t* pop;                      // [n]: 0 = in the population (erpl_launch_corr_population)
+  uint32_t* src;                           // [n]: the sample of dense member d
+  unsigned long long* count;               // the select's own count of members (the host reads the population counter)
+  double* x[ERPL_BOOT_MAX_ROWS];           // [m] each
+  double* sorted[ERPL_BOOT_MAX_ROWS];      // [m] each
+  uint32_t* pos[ERPL_BOOT_MAX_ROWS];       // [m] each
+  unsigned long long* keys;                // [2 m] the sort's keys, in and out
+  uint32_t* idx;                           // [2 m] the dense indices that travel with them
+  void* temp;                              // scratch of the select and of the sort
+  size_t temp_bytes;
+  int64_t n, m;
+  int32_t n_rows;
+};
+struct ErplBootArgs {
+  const double* x[ERPL_BOOT_MAX_ROWS];
+  const double* sorted[ERPL_BOOT_MAX_ROWS];
+  const uint32_t* pos[ERPL_BOOT_MAX_ROWS];
+  double* rep;                             // [n_rows * (2 + n_q)][replicates]: statistic s of replicate b at s * replicates + b
+  unsigned long long seed;
+  uint32_t m;                              // 1 .. 2^31 - 1
+  int32_t n_rows, n_q, replicates;
+  int32_t n_digits;                        // 8-bit digits that hold m - 1: 0 (m == 1) .. 4
+  uint32_t rank[ERPL_ANA_TARGETS];         // targets 2 i and 2 i + 1: the ranks lo and hi behind quantile i, the same in
+  double frac[ERPL_ANALYSIS_MAX_Q];        //   every replicate; frac[i] = pos - lo
+};
+extern "C++" {
+// Each enqueues its passes on `stream` and returns a hipError_t (0 = launched).
+// The scratch both rocPRIM calls of prepare need for n elements (nothing is enqueued).
+int erpl_boot_temp_bytes(int64_t n, size_t* bytes);
+int erpl_launch_boot_compact(const ErplBootPrep& p, void* stream);    // pop -> src, *count
+int erpl_launch_boot_prepare(const ErplBootPrep& p, void* stream);    // src, var -> x, sorted, pos (p.m known)
+int erpl_launch_boot_replicates(const ErplBootArgs& a, void* stream); // -> a.rep; one workgroup per replicate
+}

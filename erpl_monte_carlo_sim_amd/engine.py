@@ -479,6 +479,54 @@ class TrajectoryEngine:
             out["ranks"] = rk
         return out
 
+    def bootstrap(self, summary, mask=None, rows=None, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), replicates=2000, level=0.95,
+                  seed=0, extra=None, want_replicates=False):
+        """How sure the statistics of a run are (erpl_mc_bootstrap): the non-parametric bootstrap of mean, std and
+        `quantiles` of up to 4 rows (summary rows, or _abi.BOOT_ROW_EXTRA for the float64 [n] device tensor `extra`;
+        default apogee, range, flight time) over ONE population: mask byte 0 and every requested row finite.  `replicates`
+        resamples of `count` draws each, drawn by Philox4x32-10 from `seed` (analysis.bootstrap_indices names the samples
+        a replicate drew).  Returns a dict: n, count, n_masked, n_non_finite, rows, q, level, replicates, seed and
+        'stats': per row {'mean': s, 'std': s, 'quantiles': [s, ..]} with s = {estimate, rep_mean, se, lo, hi, finite} -
+        `estimate` over the population itself (the bits of `analyze` where the populations coincide), se the standard
+        deviation and (lo, hi) the `level` percentile interval of the statistic over its finite replicates.
+        want_replicates=True adds 'replicate_values': the float64 [n_stats, replicates] device tensor, statistic
+        j * (2 + len(quantiles)) + k of row j (k = 0 mean, 1 std, 2 + i quantile i)."""
+        n, mask_p = self._summary_and_mask(summary, mask)
+        quantiles = [float(q) for q in quantiles]
+        if len(quantiles) > _abi.ANALYSIS_MAX_Q:
+            raise ValueError(f"at most {_abi.ANALYSIS_MAX_Q} quantiles")
+        if extra is not None and not (extra.is_cuda and extra.device == self.device and extra.dtype == torch.float64
+                                      and tuple(extra.shape) == (n,) and extra.is_contiguous()):
+            raise ValueError(f"extra must be a contiguous float64 [n] tensor on {self.device}")
+        spec = self._defaults(_abi.ErplBootSpec, "erpl_mc_bootstrap_defaults")
+        self._set_rows(spec, rows, 1, _abi.BOOT_MAX_ROWS)
+        spec.n_q = len(quantiles)
+        spec.q[:len(quantiles)] = quantiles
+        spec.replicates, spec.level, spec.seed = int(replicates), float(level), int(seed) & 0xFFFFFFFFFFFFFFFF
+        R, ns = spec.n_rows, 2 + len(quantiles)
+        if not 1 <= spec.replicates <= _abi.BOOT_MAX_REPLICATES:
+            raise ValueError(f"1 to {_abi.BOOT_MAX_REPLICATES} replicates")
+        rep = torch.empty((R * ns, spec.replicates), dtype=torch.float64, device=self.device) if want_replicates else None
+        res = _abi.ErplBootstrap()
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_bootstrap", C.c_void_p(summary.data_ptr()),
+                   C.c_void_p(extra.data_ptr()) if extra is not None else None, mask_p, n, C.byref(spec), C.byref(res),
+                   C.c_void_p(rep.data_ptr()) if want_replicates else None, C.c_void_p(st.cuda_stream))
+
+        def stat(s):
+            o = res.stat[s]
+            return {"estimate": o.estimate, "rep_mean": o.rep_mean, "se": o.se, "lo": o.lo, "hi": o.hi,
+                    "finite": int(o.finite)}
+
+        out = {"n": int(res.n), "count": int(res.count), "n_masked": int(res.n_masked),
+               "n_non_finite": int(res.n_non_finite), "rows": list(spec.rows[:R]), "q": quantiles,
+               "level": float(level), "replicates": int(res.replicates), "seed": int(spec.seed),
+               "stats": [{"mean": stat(j * ns), "std": stat(j * ns + 1),
+                          "quantiles": [stat(j * ns + 2 + i) for i in range(len(quantiles))]} for j in range(R)]}
+        if want_replicates:
+            out["replicate_values"] = rep
+        return out
+
     def _seeds_on_device(self, seeds):
         """The 32-bit seeds of the device streams: n."""
         if not (seeds.is_cuda and seeds.device == self.device and seeds.dtype in (torch.uint32, torch.int32)

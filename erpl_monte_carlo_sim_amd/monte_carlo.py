@@ -426,6 +426,20 @@ class MonteCarloAnalyzer:
         return ana.drivers(torch.as_tensor(summ, device=eng.device).contiguous(),
                            torch.as_tensor(fac, device=eng.device).contiguous(), names, engine=eng, rows=rows)
 
+    def confidence_intervals(self, analysis, replicates=2000, level=0.95, seed=0):
+        """How sure the statistics of an analysis are (no reference counterpart): `analysis.confidence_intervals` - bootstrap
+        standard errors and percentile intervals of mean, std and the five percentiles of apogee, range and flight time -
+        on either kind of analysis dict, as `drivers` takes its inputs: the device 'summary' / 'status' of
+        run_monte_carlo_device, or the summary columns of analysis['results'] uploaded."""
+        from . import analysis as ana
+        eng = shared_engine(self.device)
+        if "summary" in analysis:
+            return ana.confidence_intervals(analysis["summary"], status=analysis.get("status"), engine=eng,
+                                            replicates=replicates, level=level, seed=seed)
+        summ = ana.summary_from_results(analysis["results"])
+        return ana.confidence_intervals(torch.as_tensor(summ, device=eng.device).contiguous(), engine=eng,
+                                        replicates=replicates, level=level, seed=seed)
+
     def plot_drivers(self, analysis, save_plots=True):
         """No reference counterpart: one tornado chart (Spearman and SRRC of the strongest factors) per default row, saved
         as monte_carlo_drivers.png in the output directory; returns that directory."""

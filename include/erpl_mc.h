@@ -605,6 +605,76 @@ int erpl_mc_correlation(erpl_ctx* ctx, const double* factors, const double* summ
                         const erpl_corr_spec* spec, erpl_corr_result* result, double* corr, double* rank_corr,
                         double* ranks_out, void* hip_stream);
 
+/* How sure the statistics of a run are, ON THE DEVICE: the non-parametric bootstrap of mean, standard deviation and
+ * quantiles of up to four rows - B resamples of m draws with replacement, each reduced to its statistics, and per
+ * statistic the standard error and the percentile interval over the replicates.  The reference prints point estimates
+ * only.  Conventions of erpl_mc_correlation: `summary` is [ERPL_SUMMARY_DIM][n], `extra` [n] (NULL unless a row is
+ * ERPL_BOOT_ROW_EXTRA: a derived per-sample quantity such as the miss distance of erpl_mc_dispersion), `mask` the
+ * `reasons` of erpl_mc_analyze (NULL = every sample counts) and the optional `replicates_out` [n_stats][replicates], all
+ * caller-owned device memory; spec and result are host memory; the work is enqueued on `hip_stream` behind what is there
+ * and the call returns when the result is filled; the workspace belongs to the context, grows only (about
+ * 29 + 20 n_rows bytes per sample plus the sort's scratch, and 8 n_stats + 1 bytes per replicate when the caller keeps
+ * no replicates) and is freed by erpl_mc_destroy.  ERPL_ERR_INVALID, before any device work and with a message that
+ * names the argument, for: a NULL spec, summary or result; n <= 0 or n >= 2^31; n_rows, n_q or replicates out of range;
+ * a row outside 0..16 or listed twice; row 16 without `extra`; q outside [0, 1] or NaN; level not in (0, 1) - in this
+ * order, the context last.  No floating-point atomics, every sum in a fixed order: two calls on the same inputs return
+ * the same bytes in `result` and in `replicates_out`.
+ *
+ * Population (ONE, listwise deletion): mask byte 0 AND every requested row finite, in ascending sample order: dense index
+ * d is its d-th member, m = count.  n_masked and n_non_finite as in erpl_corr_result.  m == 0: every double NaN, every
+ * `finite` 0, no error.
+ * Draws: Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85),
+ * key (seed & 0xffffffff, seed >> 32), counter (j & 0xffffffff, j >> 32, b, 0) for pair j of replicate b; of the output
+ * words o0..o3, A = o0 | o1 << 32 is draw t = 2 j and B = o2 | o3 << 32 draw t = 2 j + 1; the dense index of a draw u is
+ * (u * m) >> 64 (bias at most m / 2^64).  Replicate b is the draws t = 0 .. m - 1: it does not depend on `replicates`.
+ * erpl_mc_bootstrap_indices is the same code on the host.
+ * Statistics of replicate b of row r, over its m drawn values: mean = sum / m and std = sqrt(sum((x - mean)^2) / m), each
+ * sum accumulated by thread t of 256 over the draws t, t + 256, .. and folded in the fixed order of the other analysis
+ * calls; quantile q: pos = q (m - 1), lo = floor(pos), hi = min(lo + 1, m - 1), order_lo + (order_hi - order_lo)(pos - lo)
+ * on the EXACT order statistics of the replicate.
+ * Per statistic, over its finite replicates (`finite` of them): rep_mean; se = sqrt(sum((theta - rep_mean)^2) /
+ * (finite - 1)), 0 for finite == 1, NaN for 0 (a statistic with min == max over its replicates: rep_mean is that value
+ * and se 0, an exact test as `constant` of erpl_mc_correlation is); lo / hi = the linear-interpolated quantiles (1 - level) / 2 and
+ * 1 - (1 - level) / 2 of the replicates (the percentile interval).  `estimate` is the statistic of the population itself,
+ * by the passes of erpl_mc_analyze: the same bits where the populations coincide. */
+#define ERPL_BOOT_MAX_ROWS 4
+#define ERPL_BOOT_ROW_EXTRA 16            /* row id of the optional caller-supplied device row `extra` */
+#define ERPL_BOOT_MAX_REPLICATES 65536
+#define ERPL_BOOT_MAX_STATS (ERPL_BOOT_MAX_ROWS * (2 + ERPL_ANALYSIS_MAX_Q))   /* 40 */
+
+typedef struct erpl_boot_spec {
+  int32_t n_rows;                        /* 1..ERPL_BOOT_MAX_ROWS */
+  int32_t rows[ERPL_BOOT_MAX_ROWS];      /* distinct; 0..15 = summary rows, ERPL_BOOT_ROW_EXTRA = `extra` */
+  int32_t n_q;                           /* 0..ERPL_ANALYSIS_MAX_Q */
+  int32_t replicates;                    /* B, 1..ERPL_BOOT_MAX_REPLICATES */
+  int32_t reserved;
+  double q[ERPL_ANALYSIS_MAX_Q];         /* quantile fractions in [0, 1] */
+  double level;                          /* confidence level in (0, 1) */
+  uint64_t seed;
+} erpl_boot_spec;
+
+typedef struct erpl_boot_stat {          /* one statistic of one row */
+  double estimate;                       /* over the population itself */
+  double rep_mean, se, lo, hi;           /* of its finite replicates */
+  int64_t finite;                        /* replicates that are finite */
+} erpl_boot_stat;
+
+typedef struct erpl_bootstrap {
+  int64_t n, count, n_masked, n_non_finite;   /* count + n_masked + n_non_finite == n */
+  int32_t n_stats, replicates;
+  erpl_boot_stat stat[ERPL_BOOT_MAX_STATS];   /* s = j * (2 + n_q) + k; k = 0 mean, 1 std, 2 + i quantile q[i], of spec->rows[j] */
+} erpl_bootstrap;
+
+/* Host only: rows {APOGEE_ALT, RANGE, FLIGHT_TIME}, the q of erpl_mc_analysis_defaults, 2000 replicates, level 0.95,
+ * seed 0. */
+int erpl_mc_bootstrap_defaults(erpl_boot_spec* spec);
+int erpl_mc_bootstrap(erpl_ctx* ctx, const double* summary, const double* extra, const uint8_t* mask, int64_t n,
+                      const erpl_boot_spec* spec, erpl_bootstrap* result, double* replicates_out, void* hip_stream);
+/* Host only, no context, no device: the dense population indices replicate `replicate` draws from a population of m,
+ * draws first .. first + count - 1, into out[count].  ERPL_ERR_INVALID for a NULL out, m <= 0 or m >= 2^31, a negative
+ * replicate, first or count, or first + count > m. */
+int erpl_mc_bootstrap_indices(uint64_t seed, int64_t replicate, int64_t m, int64_t first, int64_t count, int64_t* out);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
