@@ -214,6 +214,38 @@ class ErplBootstrap(C.Structure):
                 ("n_stats", C.c_int32), ("replicates", C.c_int32), ("stat", ErplBootStat * BOOT_MAX_STATS)]
 
 
+# erpl_mc_impact_density
+DENSITY_MAX_NODES = 512
+DENSITY_MAX_LEVELS = 8
+DENSITY_MAX_ZONES = 8
+DENSITY_MAX_VERTICES = 256
+BW_SCOTT, BW_MATRIX = 0, 1
+
+_ZV_D = C.c_double * DENSITY_MAX_VERTICES
+
+
+class ErplDensitySpec(C.Structure):
+    _fields_ = [("row_x", C.c_int32), ("row_y", C.c_int32), ("nodes_x", C.c_int32), ("nodes_y", C.c_int32),
+                ("lo_x", C.c_double), ("hi_x", C.c_double), ("lo_y", C.c_double), ("hi_y", C.c_double),
+                ("pad", C.c_double), ("bandwidth", C.c_int32), ("n_levels", C.c_int32), ("bw_scale", C.c_double),
+                ("h_xx", C.c_double), ("h_xy", C.c_double), ("h_yy", C.c_double),
+                ("level", C.c_double * DENSITY_MAX_LEVELS),
+                ("n_zones", C.c_int32), ("zone_first", C.c_int32 * (DENSITY_MAX_ZONES + 1)),
+                ("zone_x", _ZV_D), ("zone_y", _ZV_D)]
+
+
+class ErplDensity(C.Structure):
+    _fields_ = [("count", C.c_int64), ("solid", C.c_int32), ("peak_ix", C.c_int32), ("peak_iy", C.c_int32),
+                ("reserved", C.c_int32),
+                ("mean_x", C.c_double), ("mean_y", C.c_double),
+                ("cov_xx", C.c_double), ("cov_xy", C.c_double), ("cov_yy", C.c_double),
+                ("h_xx", C.c_double), ("h_xy", C.c_double), ("h_yy", C.c_double), ("det", C.c_double),
+                ("norm", C.c_double),
+                ("lo_x", C.c_double), ("hi_x", C.c_double), ("lo_y", C.c_double), ("hi_y", C.c_double),
+                ("peak", C.c_double), ("grid_mass", C.c_double),
+                ("zone_inside", C.c_int64 * DENSITY_MAX_ZONES), ("sample_density", ErplRowStats)]
+
+
 LIB_NAME = "liberpl_mc.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
@@ -234,6 +266,7 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_dispersion_defaults", "erpl_mc_dispersion",
            "erpl_mc_correlation_defaults", "erpl_mc_correlation",
            "erpl_mc_bootstrap_defaults", "erpl_mc_bootstrap", "erpl_mc_bootstrap_indices",
+           "erpl_mc_impact_density_defaults", "erpl_mc_impact_density",
            "erpl_mc_legacy_random_streams_device", "erpl_mc_legacy_wind_profiles_device")
 
 _lib = None
@@ -317,6 +350,9 @@ def load_library(path=None):
     lib.erpl_mc_bootstrap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplBootSpec),
                                       C.POINTER(ErplBootstrap), C.c_void_p, C.c_void_p]
     lib.erpl_mc_bootstrap_indices.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]
+    lib.erpl_mc_impact_density_defaults.argtypes = [C.POINTER(ErplDensitySpec)]
+    lib.erpl_mc_impact_density.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplDensitySpec), C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.POINTER(ErplDensity), C.c_void_p, C.c_void_p]
     lib.erpl_mc_legacy_random_streams_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                                          C.c_int32, C.c_void_p]
     lib.erpl_mc_legacy_wind_profiles_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 9 + \

@@ -237,6 +237,42 @@ def landing_dispersion(summary, status=None, engine=None, target=None, levels=(0
     return out
 
 
+def wilson_interval(k, n, level=0.95):
+    """The Wilson score interval (lo, hi) of a proportion k / n at confidence `level` (Wilson 1927): with p = k / n and z
+    the standard normal quantile of 1 - (1 - level) / 2, (p + z^2 / 2n -+ z sqrt(p (1 - p) / n + z^2 / 4n^2)) / (1 + z^2 / n),
+    clipped to [0, 1].  n == 0: (0, 1).  A pure host function."""
+    from statistics import NormalDist
+    k, n = int(k), int(n)
+    if not 0 <= k <= n:
+        raise ValueError(f"k = {k} outside 0..n = {n}")
+    if not 0.0 < level < 1.0:
+        raise ValueError(f"level = {level} outside (0, 1)")
+    if n == 0:
+        return 0.0, 1.0
+    z = NormalDist().inv_cdf(1.0 - (1.0 - level) / 2.0)
+    p, z2 = k / n, z * z
+    centre = p + z2 / (2 * n)
+    half = z * np.sqrt(p * (1.0 - p) / n + z2 / (4.0 * n * n))
+    lo, hi = (centre - half) / (1.0 + z2 / n), (centre + half) / (1.0 + z2 / n)
+    return (0.0 if k == 0 else max(0.0, float(lo))), (1.0 if k == n else min(1.0, float(hi)))
+
+
+def impact_probability(summary, status=None, engine=None, level=0.95, **kw):
+    """The impact probability map of the filtered population (erpl_mc_analyze for the reason bytes, then
+    erpl_mc_impact_density on the impact point): the dict of TrajectoryEngine.impact_density - keyword arguments as there
+    (nodes, ranges, pad, bandwidth, levels, zones, sample_density, rows) - plus 'n_samples' / 'n_outliers' of the filter
+    and, per zone, 'probability' = inside / count with its Wilson score interval 'interval' at `level` ('probability' is
+    NaN for an empty population)."""
+    engine, res, why = _filter(summary, status, engine)
+    out = engine.impact_density(summary, why, **kw)
+    out["n_samples"], out["n_outliers"] = int(res.n_valid), int(res.n_outliers)
+    out["interval_level"] = float(level)
+    for z in out["zones"]:
+        z["probability"] = z["inside"] / out["count"] if out["count"] else float("nan")
+        z["interval"] = wilson_interval(z["inside"], out["count"], level)
+    return out
+
+
 # ---------------------------------------------------------------------------------- drivers: which dispersion drives what
 ROW_NAMES = ("apogee_altitude", "apogee_time", "first_apogee_altitude", "first_apogee_time", "range", "flight_time",
              "rail_exit_time", "rail_exit_speed", "impact_x", "impact_y", "impact_z", "n_steps",

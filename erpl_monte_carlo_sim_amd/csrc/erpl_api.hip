@@ -469,6 +469,8 @@ int erpl_mc_destroy(erpl_ctx* c) {
   if (c->corr_host) (void)hipHostFree(c->corr_host);
   (void)hipFree(c->boot_buf);
   if (c->boot_host) (void)hipHostFree(c->boot_host);
+  (void)hipFree(c->dens_work); (void)hipFree(c->dens_buf);
+  if (c->dens_host) (void)hipHostFree(c->dens_host);
   (void)hipFree(c->legacy_buf);
   if (c->legacy_pin) (void)hipHostFree(c->legacy_pin);
   for (hipEvent_t e : c->legacy_ev) if (e) (void)hipEventDestroy(e);

@@ -56,6 +56,14 @@ struct BootHost {
   ErplAnaResult sum[(ERPL_BOOT_MAX_STATS + ERPL_ANALYSIS_MAX_ROWS - 1) / ERPL_ANALYSIS_MAX_ROWS];
 };
 
+// erpl_mc_impact_density: pinned mirror of what the host reads of ErplDensWork (moments, zone counts, peak) and writes
+// to it (grid nodes, zone vertices)
+struct DensHost {
+  ErplDensMoments mom;
+  ErplDensOut out;
+  ErplDensIn in;
+};
+
 // Slot 0 serves erpl_mc_run_batch (on the caller's stream); slots 0..depth-1 serve erpl_mc_submit_batch
 // round-robin, each on its own internal stream.  Whoever uses a slot first waits (on the device) for
 // the slot's previous batch and records `done` behind its own kernels.
@@ -152,6 +160,13 @@ struct erpl_ctx {
   BootHost* boot_host = nullptr;
   char* boot_buf = nullptr;
   size_t boot_cap = 0;
+  // erpl_mc_impact_density: fixed block (partials, grid nodes, zone vertices, results), its pinned mirror, and one buffer
+  // that grows with n and the node count: population bytes, dense indices, the select's scratch, whitened points and nodes,
+  // the sample row when the caller keeps none, the node densities and the partial sums of the slices
+  ErplDensWork* dens_work = nullptr;
+  DensHost* dens_host = nullptr;
+  char* dens_buf = nullptr;
+  size_t dens_cap = 0;
   // erpl_mc_legacy_random_streams_device / _wind_profiles_device: one device buffer (flag, op tables, knot constants, the
   // MT19937 states of a tile and two sets of its accepted pairs) and its pinned staging (the tables on their way up, r2
   // down and f up, per set), both bounded by the tile; an event per set behind the tile's copy to the host

@@ -25,8 +25,9 @@ typedef unsigned long long u64;
 constexpr int kWaves = ERPL_ANA_BLOCK / 64;
 constexpr int kPer = ERPL_ANA_MAX_BLOCKS / ERPL_ANA_BLOCK;   // partials per thread of a finishing workgroup
 
-// the grid of every streaming pass: a function of n alone
-inline int grid_of(int64_t n) {
+// the grid of every streaming pass: a function of n alone (also on the device: erpl_density.hip sizes the passes over its
+// dense population by the count the select left there)
+__host__ __device__ inline int grid_of(int64_t n) {
   const int64_t want = (n + ERPL_ANA_BLOCK - 1) / ERPL_ANA_BLOCK;
   return (int)(want < ERPL_ANA_MAX_BLOCKS ? want : ERPL_ANA_MAX_BLOCKS);
 }

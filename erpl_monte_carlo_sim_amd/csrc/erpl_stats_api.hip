@@ -804,3 +804,230 @@ int erpl_mc_bootstrap(erpl_ctx* c, const double* summary, const double* extra, c
 }
 
 }  // extern "C"
+
+// ------------------------------------------------- erpl_mc_impact_density
+namespace {
+
+// one axis of erpl_density_spec: 1 = from the data, 0 = explicit with lo < hi, < 0 = refused
+int check_density_range(double lo, double hi, const char* lo_name, const char* hi_name) {
+  const int rc = check_range(lo, hi, lo_name, hi_name, -1);
+  if (rc == 0 && !(lo < hi)) return erpl_fail(ERPL_ERR_INVALID, "spec->%s = %g >= spec->%s = %g", lo_name, lo, hi_name, hi);
+  return rc;
+}
+
+int check_density_spec(const erpl_density_spec* s) {
+  ERPL_TRY(check_row(s->row_x, "row_x", -1));
+  ERPL_TRY(check_row(s->row_y, "row_y", -1));
+  if (s->row_x == s->row_y) return erpl_fail(ERPL_ERR_INVALID, "spec->row_y = %d is listed twice (row_x)", s->row_y);
+  if (s->nodes_x < 2 || s->nodes_x > ERPL_DENSITY_MAX_NODES)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->nodes_x = %d outside 2..%d", s->nodes_x, ERPL_DENSITY_MAX_NODES);
+  if (s->nodes_y < 2 || s->nodes_y > ERPL_DENSITY_MAX_NODES)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->nodes_y = %d outside 2..%d", s->nodes_y, ERPL_DENSITY_MAX_NODES);
+  if (check_density_range(s->lo_x, s->hi_x, "lo_x", "hi_x") < 0) return ERPL_ERR_INVALID;
+  if (check_density_range(s->lo_y, s->hi_y, "lo_y", "hi_y") < 0) return ERPL_ERR_INVALID;
+  if (!(std::isfinite(s->pad) && s->pad >= 0.0)) return erpl_fail(ERPL_ERR_INVALID, "spec->pad = %g: finite and >= 0", s->pad);
+  if (s->bandwidth != ERPL_BW_SCOTT && s->bandwidth != ERPL_BW_MATRIX)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->bandwidth = %d: ERPL_BW_SCOTT or ERPL_BW_MATRIX", s->bandwidth);
+  if (s->bandwidth == ERPL_BW_SCOTT && !(std::isfinite(s->bw_scale) && s->bw_scale > 0.0))
+    return erpl_fail(ERPL_ERR_INVALID, "spec->bw_scale = %g: finite and > 0", s->bw_scale);
+  if (s->bandwidth == ERPL_BW_MATRIX) {
+    const bool finite = std::isfinite(s->h_xx) && std::isfinite(s->h_xy) && std::isfinite(s->h_yy);
+    const double det = s->h_xx * s->h_yy - s->h_xy * s->h_xy;
+    if (!(finite && s->h_xx > 0.0 && s->h_yy > 0.0 && det > 0.0 && std::isfinite(det)))
+      return erpl_fail(ERPL_ERR_INVALID, "spec->h_xx = %g, spec->h_xy = %g, spec->h_yy = %g: not a finite positive definite matrix",
+                       s->h_xx, s->h_xy, s->h_yy);
+  }
+  if (s->n_levels < 0 || s->n_levels > ERPL_DENSITY_MAX_LEVELS)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->n_levels = %d outside 0..%d", s->n_levels, ERPL_DENSITY_MAX_LEVELS);
+  for (int k = 0; k < s->n_levels; ++k)
+    if (!(s->level[k] > 0.0 && s->level[k] < 1.0))
+      return erpl_fail(ERPL_ERR_INVALID, "spec->level[%d] = %g outside (0, 1)", k, s->level[k]);
+  if (s->n_zones < 0 || s->n_zones > ERPL_DENSITY_MAX_ZONES)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->n_zones = %d outside 0..%d", s->n_zones, ERPL_DENSITY_MAX_ZONES);
+  if (s->n_zones > 0 && s->zone_first[0] != 0)
+    return erpl_fail(ERPL_ERR_INVALID, "spec->zone_first[0] = %d: the first zone starts at vertex 0", s->zone_first[0]);
+  for (int z = 0; z < s->n_zones; ++z) {
+    const int first = s->zone_first[z], end = s->zone_first[z + 1];
+    if (end < first)
+      return erpl_fail(ERPL_ERR_INVALID, "spec->zone_first[%d] = %d is below spec->zone_first[%d] = %d", z + 1, end, z, first);
+    if (end - first < 3)
+      return erpl_fail(ERPL_ERR_INVALID, "spec->zone_first[%d] = %d, spec->zone_first[%d] = %d: zone %d has %d vertices, a polygon needs 3",
+                       z, first, z + 1, end, z, end - first);
+    if (end > ERPL_DENSITY_MAX_VERTICES)
+      return erpl_fail(ERPL_ERR_INVALID, "spec->zone_first[%d] = %d: more than %d vertices together", z + 1, end,
+                       ERPL_DENSITY_MAX_VERTICES);
+    for (int v = first; v < end; ++v)
+      if (!(std::isfinite(s->zone_x[v]) && std::isfinite(s->zone_y[v])))
+        return erpl_fail(ERPL_ERR_INVALID, "spec->zone_x[%d] = %g, spec->zone_y[%d] = %g: not a finite vertex (zone %d)", v,
+                         s->zone_x[v], v, s->zone_y[v], z);
+  }
+  return ERPL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int erpl_mc_impact_density_defaults(erpl_density_spec* spec) {
+  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  memset(spec, 0, sizeof(*spec));
+  spec->row_x = ERPL_SUM_IMPACT_X; spec->row_y = ERPL_SUM_IMPACT_Y;
+  spec->nodes_x = spec->nodes_y = 128;
+  spec->lo_x = spec->hi_x = spec->lo_y = spec->hi_y = NAN;   // from the data
+  spec->pad = 3.0;
+  spec->bandwidth = ERPL_BW_SCOTT;
+  spec->bw_scale = 1.0;
+  spec->h_xx = spec->h_yy = 1.0;
+  spec->n_levels = 3;
+  spec->level[0] = 0.5; spec->level[1] = 0.9; spec->level[2] = 0.99;
+  return ERPL_OK;
+}
+
+int erpl_mc_impact_density(erpl_ctx* c, const double* summary, const uint8_t* mask, int64_t n, const erpl_density_spec* spec,
+                           double* grid_x, double* grid_y, double* density, erpl_density* result, double* sample_density,
+                           void* stream) {
+  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  ERPL_TRY(check_density_spec(spec));
+  if (n <= 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
+  if (n >= (1ll << 31)) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: the select carries 31-bit sample indices", (long long)n);
+  if (!summary) return erpl_fail(ERPL_ERR_INVALID, "summary is NULL");
+  if (!grid_x) return erpl_fail(ERPL_ERR_INVALID, "grid_x is NULL");
+  if (!grid_y) return erpl_fail(ERPL_ERR_INVALID, "grid_y is NULL");
+  if (!density) return erpl_fail(ERPL_ERR_INVALID, "density is NULL");
+  if (!result) return erpl_fail(ERPL_ERR_INVALID, "result is NULL");
+  if (!c) return erpl_fail(ERPL_ERR_INVALID, "ctx is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int nx = spec->nodes_x, ny = spec->nodes_y;
+  const size_t un = (size_t)n, nodes = (size_t)nx * (size_t)ny;
+  const bool want_samples = spec->n_levels > 0 || sample_density;
+
+  // the buffer: [pop n bytes][src n u32][count][scratch of the select][points n (x, y), then (u, v)][nodes (u, v)][node densities]
+  // [the sample row unless the caller keeps it][partial sums: at most TARGET_BLOCKS * TILE + queries, erpl_dens_slices]
+  size_t temp_bytes = 0;
+  LAUNCH_TRY(erpl_boot_temp_bytes(n, &temp_bytes), "select sizing failed");
+  temp_bytes = align256(std::max(temp_bytes, (size_t)256));
+  const size_t off_src = align256(un);
+  const size_t off_count = off_src + align256(4 * un);
+  const size_t off_temp = off_count + 256;
+  const size_t off_pts = off_temp + temp_bytes;
+  const size_t off_nodes = off_pts + align256(16 * un);
+  const size_t off_dens = off_nodes + align256(16 * nodes);
+  const size_t off_row = off_dens + align256(8 * nodes);
+  const size_t off_part = off_row + (want_samples && !sample_density ? align256(8 * un) : 0);
+  const size_t need = off_part + 8 * ((size_t)ERPL_DENS_TARGET_BLOCKS * ERPL_DENS_TILE + std::max(nodes, want_samples ? un : 0));
+  ERPL_TRY(erpl_first_use(c->dens_work, c->dens_host));
+  if (want_samples) ERPL_TRY(erpl_first_use(c->ana_work, c->ana_host));   // the selection's block
+  ERPL_TRY(erpl_grow(c->dens_buf, c->dens_cap, need));
+  char* buf = c->dens_buf;
+  DensHost& h = *c->dens_host;
+  uint32_t* src = (uint32_t*)(buf + off_src);
+  double* pts = (double*)(buf + off_pts);
+  double* nodes_uv = (double*)(buf + off_nodes);
+  double* dens = (double*)(buf + off_dens);
+  double* row = sample_density ? sample_density : (double*)(buf + off_row);
+  double* partial = (double*)(buf + off_part);
+
+  ErplDensArgs a;
+  memset(&a, 0, sizeof(a));
+  a.summary = summary; a.mask = mask; a.work = c->dens_work; a.pop = (uint8_t*)buf; a.n = n;
+  a.row_x = spec->row_x; a.row_y = spec->row_y; a.n_zones = spec->n_zones;
+  ErplBootPrep p;   // the select of erpl_mc_bootstrap: pop -> src and the count, in sample order
+  memset(&p, 0, sizeof(p));
+  p.pop = a.pop; p.src = src; p.count = (unsigned long long*)(buf + off_count); p.temp = buf + off_temp;
+  p.temp_bytes = temp_bytes; p.n = n;
+  KERNEL_TRY(erpl_launch_dens_population(a, stream));
+  LAUNCH_TRY(erpl_launch_boot_compact(p, stream), "select failed");
+  KERNEL_TRY(erpl_launch_dens_moments(a, src, p.count, pts, stream));
+  HIP_TRY(hipMemcpyAsync(&h.mom, &c->dens_work->mom, sizeof(ErplDensMoments), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+
+  // what the host settles in double: S, H, whether the estimate is solid, the map, the ranges and the nodes
+  const double nan = NAN;
+  const int64_t m = (int64_t)h.mom.count;
+  const bool any = m > 0;
+  memset(result, 0, sizeof(*result));
+  result->count = m;
+  result->mean_x = any ? h.mom.mean_x : nan; result->mean_y = any ? h.mom.mean_y : nan;
+  const double dof = (double)(m - 1);   // 0 for m == 1: S is NaN there
+  result->cov_xx = any ? h.mom.sxx / dof : nan; result->cov_xy = any ? h.mom.sxy / dof : nan;
+  result->cov_yy = any ? h.mom.syy / dof : nan;
+  double hxx = spec->h_xx, hxy = spec->h_xy, hyy = spec->h_yy;
+  if (spec->bandwidth == ERPL_BW_SCOTT) {
+    const double factor = spec->bw_scale * pow((double)m, -1.0 / 6.0), f2 = factor * factor;
+    hxx = f2 * result->cov_xx; hxy = f2 * result->cov_xy; hyy = f2 * result->cov_yy;
+  }
+  const double det = hxx * hyy - hxy * hxy;
+  const bool solid = any && std::isfinite(hxx) && std::isfinite(hxy) && std::isfinite(hyy) && std::isfinite(det) &&
+                     hxx > 0.0 && hyy > 0.0 && det > 1e-12 * hxx * hyy && !(spec->bandwidth == ERPL_BW_SCOTT && m < 3);
+  result->solid = solid ? 1 : 0;
+  result->h_xx = any ? hxx : nan; result->h_xy = any ? hxy : nan; result->h_yy = any ? hyy : nan;
+  result->det = any ? det : nan;
+  const double norm = solid ? 1.0 / ((double)m * (2.0 * M_PI) * sqrt(det)) : nan;
+  result->norm = norm;
+  const bool auto_x = std::isnan(spec->lo_x), auto_y = std::isnan(spec->lo_y);
+  const double pad_x = solid ? spec->pad * sqrt(hxx) : 0.0, pad_y = solid ? spec->pad * sqrt(hyy) : 0.0;
+  double lo_x = spec->lo_x, hi_x = spec->hi_x, lo_y = spec->lo_y, hi_y = spec->hi_y;
+  if (!settle_range(auto_x, h.mom.min_x - pad_x, h.mom.max_x + pad_x, &lo_x, &hi_x))
+    return erpl_fail(ERPL_ERR_INVALID, "spec->row_x = %d: the range of the counted values, %g to %g, is wider than a double holds",
+                     spec->row_x, lo_x, hi_x);
+  if (!settle_range(auto_y, h.mom.min_y - pad_y, h.mom.max_y + pad_y, &lo_y, &hi_y))
+    return erpl_fail(ERPL_ERR_INVALID, "spec->row_y = %d: the range of the counted values, %g to %g, is wider than a double holds",
+                     spec->row_y, lo_y, hi_y);
+  result->lo_x = lo_x; result->hi_x = hi_x; result->lo_y = lo_y; result->hi_y = hi_y;
+  memset(&h.in, 0, sizeof(h.in));
+  fill_edges(lo_x, hi_x, nx - 1, h.in.grid_x);   // np.linspace(lo, hi, nodes)
+  fill_edges(lo_y, hi_y, ny - 1, h.in.grid_y);
+  const int n_vert = spec->n_zones > 0 ? spec->zone_first[spec->n_zones] : 0;
+  memcpy(h.in.zone_x, spec->zone_x, (size_t)n_vert * sizeof(double));
+  memcpy(h.in.zone_y, spec->zone_y, (size_t)n_vert * sizeof(double));
+  for (int z = 0; z <= spec->n_zones; ++z) h.in.zone_first[z] = spec->zone_first[z];
+  HIP_TRY(hipMemcpyAsync(&c->dens_work->in, &h.in, sizeof(ErplDensIn), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(&c->dens_work->out, 0, sizeof(ErplDensOut), st));
+  if (spec->n_zones > 0) KERNEL_TRY(erpl_launch_dens_zones(a, stream));
+
+  if (solid) {
+    // H = C C': u = dx / c11, v = (dy - c21 u) / c22
+    const double c11 = sqrt(hxx), c21 = hxy / c11, c22 = sqrt(hyy - c21 * c21);
+    ErplDensMap map;
+    map.mean_x = h.mom.mean_x; map.mean_y = h.mom.mean_y;
+    map.w11 = 1.0 / c11; map.w22 = 1.0 / c22; map.w21 = -c21 * map.w11 * map.w22;
+    KERNEL_TRY(erpl_launch_dens_whiten(pts, m, map, stream));
+    KERNEL_TRY(erpl_launch_dens_nodes(c->dens_work, nx, ny, map, nodes_uv, stream));
+    KERNEL_TRY(erpl_launch_dens_pairs(nodes_uv, (int64_t)nodes, pts, m, norm, partial, dens, nullptr, stream));
+    KERNEL_TRY(erpl_launch_dens_peak(c->dens_work, dens, (int64_t)nodes, stream));
+  }
+  if (want_samples) {
+    KERNEL_TRY(erpl_launch_dens_fill_nan(row, n, stream));
+    if (solid) {
+      KERNEL_TRY(erpl_launch_dens_pairs(pts, m, pts, m, norm, partial, row, src, stream));
+      // the f_j as a one-row summary through the moment passes and the selection of erpl_mc_analyze
+      ErplAnaArgs r;
+      memset(&r, 0, sizeof(r));
+      r.summary = row; r.why = a.pop; r.work = c->ana_work; r.n = n; r.n_rows = 1; r.rows[0] = 0; r.n_q = spec->n_levels;
+      for (int k = 0; k < spec->n_levels; ++k) r.q[k] = 1.0 - spec->level[k];
+      KERNEL_TRY(erpl_launch_row_stats(r, stream));
+      HIP_TRY(hipMemcpyAsync(c->ana_host, &c->ana_work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, st));
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(&h.out, &c->dens_work->out, sizeof(ErplDensOut), hipMemcpyDeviceToHost, st));
+  if (solid) HIP_TRY(hipMemcpyAsync(density, dens, 8 * nodes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+
+  memcpy(grid_x, h.in.grid_x, (size_t)nx * sizeof(double));
+  memcpy(grid_y, h.in.grid_y, (size_t)ny * sizeof(double));
+  if (!solid) for (size_t k = 0; k < nodes; ++k) density[k] = nan;
+  for (int z = 0; z < ERPL_DENSITY_MAX_ZONES; ++z) result->zone_inside[z] = z < spec->n_zones ? (int64_t)h.out.zone_inside[z] : 0;
+  const double cell = ((hi_x - lo_x) / (double)(nx - 1)) * ((hi_y - lo_y) / (double)(ny - 1));
+  result->peak = solid ? h.out.peak : nan;
+  result->grid_mass = solid ? h.out.sum * cell : nan;
+  result->peak_ix = solid ? (int32_t)((int64_t)h.out.peak_at / ny) : -1;
+  result->peak_iy = solid ? (int32_t)((int64_t)h.out.peak_at % ny) : -1;
+  double q[ERPL_ANALYSIS_MAX_Q] = {0};
+  for (int k = 0; k < spec->n_levels; ++k) q[k] = 1.0 - spec->level[k];
+  const bool described = solid && want_samples;
+  finish_row_stats(described ? c->ana_host->row[0] : ErplAnaRow(), q, spec->n_levels, described, result->sample_density);
+  return ERPL_OK;
+}
+
+}  // extern "C"

@@ -355,3 +355,71 @@ int erpl_launch_boot_compact(const ErplBootPrep& p, void* stream);    // pop -> 
 int erpl_launch_boot_prepare(const ErplBootPrep& p, void* stream);    // src, var -> x, sorted, pos (p.m known)
 int erpl_launch_boot_replicates(const ErplBootArgs& a, void* stream); // -> a.rep; one workgroup per replicate
 }
+
+// ---- erpl_mc_impact_density (erpl_density.hip) ----
+// The streaming passes (moments, zones, fold, peak) use the grid of the analysis passes.  The pair kernel gives every
+// thread ERPL_DENS_Q queries and stages the sources in LDS tiles of ERPL_DENS_TILE (16 KB of (u, v) pairs, read back at
+// one address per wave: a broadcast); a workgroup owns ERPL_DENS_TILE queries and one slice of the sources.
+#define ERPL_DENS_Q 4
+#define ERPL_DENS_TILE (ERPL_DENS_Q * ERPL_ANA_BLOCK)   // 1024
+#define ERPL_DENS_TARGET_BLOCKS 1024   // the sources are cut into slices until the launch has about this many workgroups
+struct ErplDensMoments {            // what the moment passes hand back
+  unsigned long long count;               // the select's
+  double mean_x, mean_y, sxx, sxy, syy;   // sums of dx dx, dx dy, dy dy about the mean
+  double min_x, max_x, min_y, max_y;      // +inf / -inf: nothing counted
+};
+struct ErplDensOut {                // what the zone pass and the finish hand back
+  unsigned long long zone_inside[ERPL_DENSITY_MAX_ZONES];
+  double sum, peak, peak_at;        // over the nodes; peak_at = the x-major index of the first node that holds the peak
+};
+struct ErplDensMap {                // a point of the plane -> whitened coordinates: u = w11 dx, v = fma(w21, dx, w22 dy)
+  double mean_x, mean_y, w11, w21, w22;
+};
+struct ErplDensIn {                 // what the host writes: the nodes (np.linspace's arithmetic) and the zones of the spec
+  double grid_x[ERPL_DENSITY_MAX_NODES], grid_y[ERPL_DENSITY_MAX_NODES];
+  double zone_x[ERPL_DENSITY_MAX_VERTICES], zone_y[ERPL_DENSITY_MAX_VERTICES];
+  int32_t zone_first[ERPL_DENSITY_MAX_ZONES + 1];
+};
+struct ErplDensWork {
+  double psum[3][ERPL_ANA_MAX_BLOCKS];      // moments, node sum: partials per workgroup
+  double pext[4][ERPL_ANA_MAX_BLOCKS];      // min x, max x, min y, max y; [0] also the peak and the peak's node
+  unsigned long long zpart[ERPL_ANA_MAX_BLOCKS][ERPL_DENSITY_MAX_ZONES];   // zone contents per workgroup
+  ErplDensMoments mom;
+  ErplDensOut out;
+  ErplDensIn in;
+};
+struct ErplDensArgs {
+  const double* summary;   // [ERPL_SUMMARY_DIM][n]
+  const uint8_t* mask;     // [n] or NULL
+  ErplDensWork* work;
+  uint8_t* pop;            // [n] workspace: 0 = counted (read by the select, the zones and the row statistics)
+  int64_t n;
+  int32_t row_x, row_y, n_zones;
+};
+// How the sources of a query are cut: `slices` runs of *per_slice consecutive dense indices (the last one shorter).  A
+// function of m and the number of queries alone; the host sizes the partial sums with it and the launcher its grid.
+inline int erpl_dens_slices(int64_t m, int64_t queries, int64_t* per_slice) {   // m, queries >= 1
+  const int64_t t = (m + ERPL_DENS_TILE - 1) / ERPL_DENS_TILE, blocks = (queries + ERPL_DENS_TILE - 1) / ERPL_DENS_TILE;
+  const int64_t want = (ERPL_DENS_TARGET_BLOCKS + blocks - 1) / blocks, most = t < want ? t : want;
+  const int64_t tiles = (t + most - 1) / most;   // per slice, spread evenly
+  *per_slice = tiles * ERPL_DENS_TILE;
+  return (int)((t + tiles - 1) / tiles);
+}
+extern "C++" {
+// Each enqueues its passes on `stream` and returns a hipError_t (0 = launched).
+int erpl_launch_dens_population(const ErplDensArgs& a, void* stream);   // -> a.pop
+// src[d] = the sample of dense member d < *count (the select's outputs, on the device): the counted points, in sample order,
+// into xy[*count][2] and their moments, summed in an order that depends on them alone -> work->mom
+int erpl_launch_dens_moments(const ErplDensArgs& a, const uint32_t* src, const unsigned long long* count, double* xy,
+                             void* stream);
+int erpl_launch_dens_zones(const ErplDensArgs& a, void* stream);     // a.pop, work->in -> work->out.zone_inside
+int erpl_launch_dens_whiten(double* xy, int64_t m, const ErplDensMap& map, void* stream);   // xy[m][2] -> (u, v), in place
+// the nodes of work->in.grid_x x work->in.grid_y, x-major, into whitened coordinates uv[nx * ny][2]
+int erpl_launch_dens_nodes(const ErplDensWork* work, int nx, int ny, const ErplDensMap& map, double* uv, void* stream);
+// THE pair kernel and its fold: out[scatter ? scatter[q] : q] = norm * sum over the m sources of exp(-|qry[q] - src[i]|^2 / 2)
+// in the order of erpl_dens_slices; partial: erpl_dens_slices(m, queries) * queries doubles
+int erpl_launch_dens_pairs(const double* qry, int64_t queries, const double* src, int64_t m, double norm, double* partial,
+                           double* out, const uint32_t* scatter, void* stream);
+int erpl_launch_dens_peak(ErplDensWork* work, const double* density, int64_t nodes, void* stream);   // -> work->out.sum / peak / peak_at
+int erpl_launch_dens_fill_nan(double* row, int64_t n, void* stream);
+}

@@ -431,6 +431,78 @@ class TrajectoryEngine:
             out["miss_distance"] = r
         return out
 
+    def impact_density(self, summary, mask=None, rows=(_abi.SUM_IMPACT_X, _abi.SUM_IMPACT_Y), nodes=(128, 128), ranges=None,
+                       pad=3.0, bandwidth=None, levels=(0.5, 0.9, 0.99), zones=None, sample_density=False):
+        """The impact probability map (erpl_mc_impact_density): a Gaussian kernel density estimate of the (rows[0], rows[1])
+        cloud over the samples with mask byte 0 and both values finite, evaluated at the nodes[0] x nodes[1] nodes of a grid
+        (2..512 per axis).  ranges: None or ((lo_x, hi_x) | None, (lo_y, hi_y) | None), None = min / max of the counted
+        values -+ `pad` bandwidth standard deviations.  bandwidth: None = Scott's rule (scipy.stats.gaussian_kde's default),
+        a float = Scott's rule times that factor, a 2 x 2 matrix = H as given.  levels: contents of the highest-density
+        regions; zones: polygons, each an array of (x, y) vertices.  Returns a dict: count, solid, mean, covariance (divisor
+        count - 1), bandwidth_matrix, det, norm, ranges, grid_x, grid_y, density ([nodes_x, nodes_y], x-major), peak,
+        peak_node, grid_mass, levels, thresholds (density >= thresholds[k] is the region of content levels[k]),
+        sample_density_stats (count / mean / std / min / max / q / quantiles / order_lo / order_hi of the density at the
+        samples), zones ([{'vertices', 'inside'}]).  sample_density=True adds 'sample_density', the float64 [n] device
+        tensor of the density at every sample (NaN where it is not counted); with no levels and without it the pass over
+        all pairs of samples is skipped."""
+        n, mask_p = self._summary_and_mask(summary, mask)
+        levels = [float(p) for p in levels]
+        if len(levels) > _abi.DENSITY_MAX_LEVELS:
+            raise ValueError(f"at most {_abi.DENSITY_MAX_LEVELS} levels")
+        zones = [np.asarray(z, dtype=np.float64).reshape(-1, 2) for z in (zones or [])]
+        if len(zones) > _abi.DENSITY_MAX_ZONES:
+            raise ValueError(f"at most {_abi.DENSITY_MAX_ZONES} zones")
+        if sum(len(z) for z in zones) > _abi.DENSITY_MAX_VERTICES:
+            raise ValueError(f"at most {_abi.DENSITY_MAX_VERTICES} zone vertices together")
+        spec = self._defaults(_abi.ErplDensitySpec, "erpl_mc_impact_density_defaults")
+        spec.row_x, spec.row_y = int(rows[0]), int(rows[1])
+        spec.nodes_x, spec.nodes_y = int(nodes[0]), int(nodes[1])
+        rx, ry = (None, None) if ranges is None else ranges
+        (spec.lo_x, spec.hi_x), (spec.lo_y, spec.hi_y) = self._range_of(rx), self._range_of(ry)
+        spec.pad = float(pad)
+        if bandwidth is None or np.isscalar(bandwidth):
+            spec.bandwidth, spec.bw_scale = _abi.BW_SCOTT, 1.0 if bandwidth is None else float(bandwidth)
+        else:
+            hm = np.asarray(bandwidth, dtype=np.float64)
+            if hm.shape != (2, 2) or hm[0, 1] != hm[1, 0]:
+                raise ValueError("bandwidth: None, a factor or a symmetric 2 x 2 matrix")
+            spec.bandwidth, spec.h_xx, spec.h_xy, spec.h_yy = _abi.BW_MATRIX, hm[0, 0], hm[0, 1], hm[1, 1]
+        spec.n_levels = len(levels)
+        spec.level[:len(levels)] = levels
+        spec.n_zones, at = len(zones), 0
+        for z, poly in enumerate(zones):
+            spec.zone_first[z] = at
+            spec.zone_x[at:at + len(poly)] = poly[:, 0].tolist()
+            spec.zone_y[at:at + len(poly)] = poly[:, 1].tolist()
+            at += len(poly)
+        spec.zone_first[len(zones)] = at
+        cap = _abi.DENSITY_MAX_NODES
+        nx, ny = max(2, min(spec.nodes_x, cap)), max(2, min(spec.nodes_y, cap))   # out-of-range nodes are refused below
+        gx, gy = np.zeros(cap, dtype=np.float64), np.zeros(cap, dtype=np.float64)
+        dens = np.zeros(nx * ny, dtype=np.float64)
+        row = torch.empty((n,), dtype=torch.float64, device=self.device) if sample_density else None
+        res = _abi.ErplDensity()
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_impact_density", C.c_void_p(summary.data_ptr()), mask_p, n, C.byref(spec),
+                   C.c_void_p(gx.ctypes.data), C.c_void_p(gy.ctypes.data), C.c_void_p(dens.ctypes.data), C.byref(res),
+                   C.c_void_p(row.data_ptr()) if sample_density else None, C.c_void_p(st.cuda_stream))
+        nl, sd = len(levels), res.sample_density
+        out = {"count": int(res.count), "solid": bool(res.solid), "rows": (spec.row_x, spec.row_y),
+               "mean": [res.mean_x, res.mean_y],
+               "covariance": [[res.cov_xx, res.cov_xy], [res.cov_xy, res.cov_yy]],
+               "bandwidth_matrix": [[res.h_xx, res.h_xy], [res.h_xy, res.h_yy]], "det": res.det, "norm": res.norm,
+               "ranges": ((res.lo_x, res.hi_x), (res.lo_y, res.hi_y)),
+               "grid_x": gx[:nx].copy(), "grid_y": gy[:ny].copy(), "density": dens.reshape(nx, ny),
+               "peak": res.peak, "peak_node": (int(res.peak_ix), int(res.peak_iy)), "grid_mass": res.grid_mass,
+               "levels": levels, "thresholds": list(sd.quantile[:nl]),
+               "sample_density_stats": {"count": int(sd.count), "mean": sd.mean, "std": sd.std, "min": sd.min, "max": sd.max,
+                                        "q": [1.0 - p for p in levels], "quantiles": list(sd.quantile[:nl]),
+                                        "order_lo": list(sd.order_lo[:nl]), "order_hi": list(sd.order_hi[:nl])},
+               "zones": [{"vertices": poly, "inside": int(res.zone_inside[z])} for z, poly in enumerate(zones)]}
+        if sample_density:
+            out["sample_density"] = row
+        return out
+
     def correlation(self, factors, summary, mask=None, rows=None, ranks=True, want_ranks=False):
         """Which factor drives which outcome (erpl_mc_correlation): Pearson and - with ranks=True - Spearman correlation
         and the standardised (rank) regression coefficients between the rows of `factors` (float64 [F, n] on the device,

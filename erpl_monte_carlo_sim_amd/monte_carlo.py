@@ -440,6 +440,23 @@ class MonteCarloAnalyzer:
         return ana.confidence_intervals(torch.as_tensor(summ, device=eng.device).contiguous(), engine=eng,
                                         replicates=replicates, level=level, seed=seed)
 
+    def impact_probability(self, analysis, **kw):
+        """Where it comes down, as probabilities (no reference counterpart): `analysis.impact_probability` - the kernel
+        density of the impact points, the thresholds of the regions that hold 50 / 90 / 99 % of the landings and the
+        probability of landing inside `zones` - on either kind of analysis dict, as `confidence_intervals` takes its inputs."""
+        from . import analysis as ana
+        eng = shared_engine(self.device)
+        if "summary" in analysis:
+            return ana.impact_probability(analysis["summary"], status=analysis.get("status"), engine=eng, **kw)
+        summ = ana.summary_from_results(analysis["results"])
+        return ana.impact_probability(torch.as_tensor(summ, device=eng.device).contiguous(), engine=eng, **kw)
+
+    def plot_impact_probability(self, analysis, save_plots=True, zones=None):
+        """No reference counterpart: the impact probability map - filled contours of the regions that hold 50 / 90 / 99 % of
+        the landings, the outlines of `zones` with the probability of landing inside - as
+        monte_carlo_impact_probability.png, the numbers as impact_probability.json; returns the output directory."""
+        return plots.plot_impact_probability(self, analysis, save_plots, zones)
+
     def plot_drivers(self, analysis, save_plots=True):
         """No reference counterpart: one tornado chart (Spearman and SRRC of the strongest factors) per default row, saved
         as monte_carlo_drivers.png in the output directory; returns that directory."""

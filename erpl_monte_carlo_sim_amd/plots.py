@@ -181,6 +181,56 @@ def drivers_figure(drivers, row, top=10):
     return fig
 
 
+def impact_probability_figure(result, launch_site=(0.0, 0.0)):
+    """The impact probability map from the dict of analysis.impact_probability: filled contours of the density between its
+    thresholds (the band down to thresholds[k] is the region that holds levels[k] of the landings; the widest region is
+    drawn first), each labelled with its content, the outline of every zone labelled with its probability, the launch site
+    marked.  A result that is not solid draws the zones and the launch site only."""
+    from matplotlib.patches import Patch, Polygon
+    fig = _figure((9, 8))
+    ax = fig.subplots()
+    handles = []
+    pairs = sorted((t, p) for t, p in zip(result["thresholds"], result["levels"]) if np.isfinite(t) and t > 0.0)
+    cuts, contents = [], []
+    for t, p in pairs:   # ascending thresholds = descending content; equal thresholds keep the first
+        if not cuts or t > cuts[-1]:
+            cuts.append(t)
+            contents.append(p)
+    if result["solid"] and cuts:
+        dens = np.asarray(result["density"], dtype=np.float64)
+        top = max(float(np.max(dens)), cuts[-1]) * (1.0 + 1e-9) + np.finfo(np.float64).tiny
+        shades = [str(0.85 - 0.6 * k / max(len(cuts) - 1, 1)) for k in range(len(cuts))]
+        ax.contourf(np.asarray(result["grid_x"]), np.asarray(result["grid_y"]), dens.T, levels=cuts + [top], colors=shades)
+        ax.contour(np.asarray(result["grid_x"]), np.asarray(result["grid_y"]), dens.T, levels=cuts, colors="black",
+                   linewidths=0.6)
+        handles += [Patch(facecolor=c, edgecolor="black", label=f"{100 * p:g} % of landings") for c, p in zip(shades, contents)]
+    colours = ("tab:red", "tab:blue", "tab:green", "tab:orange", "tab:purple", "tab:brown", "tab:pink", "tab:olive")
+    for k, z in enumerate(result["zones"]):
+        label = f"zone {k}: {z['inside']} of {result['count']}"
+        if "probability" in z and np.isfinite(z["probability"]):
+            label = f"zone {k}: P = {z['probability']:.4g} [{z['interval'][0]:.4g}, {z['interval'][1]:.4g}]"
+        patch = Polygon(np.asarray(z["vertices"], dtype=np.float64), closed=True, fill=False, linewidth=1.5,
+                        edgecolor=colours[k % len(colours)], label=label)
+        ax.add_patch(patch)
+        handles.append(patch)
+    if launch_site is not None:
+        handles += ax.plot([launch_site[0]], [launch_site[1]], marker="*", color="black", markersize=12, linestyle="none",
+                           label="Launch site")
+    (lo_x, hi_x), (lo_y, hi_y) = result["ranges"]
+    if np.isfinite([lo_x, hi_x, lo_y, hi_y]).all():
+        ax.update_datalim([(lo_x, lo_y), (hi_x, hi_y)])
+    ax.set_xlabel("East Position (m)")
+    ax.set_ylabel("North Position (m)")
+    ax.set_title(f"Impact Probability ({result['count']} impacts)")
+    ax.grid(True, alpha=0.3)
+    ax.set_aspect("equal", adjustable="datalim")
+    ax.autoscale_view()
+    if handles:
+        ax.legend(handles=handles, loc="best", fontsize=8)
+    fig.tight_layout()
+    return fig
+
+
 def save_figure(fig, output_dir, name):
     path = os.path.join(output_dir, name)
     fig.savefig(path, dpi=DPI, bbox_inches="tight")
@@ -305,6 +355,23 @@ def plot_landing_dispersion(analyzer, analysis, save_plots=True, target=None):
         print(f"Landing dispersion plot saved to: {save_figure(fig, output_dir, 'monte_carlo_landing.png')}")
         with open(os.path.join(output_dir, "landing_dispersion.json"), "w") as fh:
             json.dump(to_serializable(disp), fh, indent=2)
+    return output_dir
+
+
+def plot_impact_probability(analyzer, analysis, save_plots=True, zones=None, **kw):
+    """The impact probability map of the filtered population (no reference counterpart): writes
+    monte_carlo_impact_probability.png and impact_probability.json (the dict of analysis.impact_probability without the
+    per-sample row); returns the output directory (None without save_plots)."""
+    from .reports import to_serializable
+    res = analyzer.impact_probability(analysis, zones=zones, **kw)
+    res.pop("sample_density", None)
+    fig = impact_probability_figure(res)
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Impact probability plot saved to: {save_figure(fig, output_dir, 'monte_carlo_impact_probability.png')}")
+        with open(os.path.join(output_dir, "impact_probability.json"), "w") as fh:
+            json.dump(to_serializable(res), fh, indent=2)
     return output_dir
 
 

@@ -675,6 +675,108 @@ int erpl_mc_bootstrap(erpl_ctx* ctx, const double* summary, const double* extra,
  * replicate, first or count, or first + count > m. */
 int erpl_mc_bootstrap_indices(uint64_t seed, int64_t replicate, int64_t m, int64_t first, int64_t count, int64_t* out);
 
+/* The impact probability map ON THE DEVICE (no reference counterpart): a Gaussian kernel density estimate of where the
+ * vehicle comes down, evaluated AT the nodes of a rectangular grid and at the impact points themselves, the thresholds of
+ * the highest-density regions that hold given fractions of the landings, and the number of landings inside given polygons
+ * (the range boundary, a keep-out zone).  Conventions of erpl_mc_dispersion: `summary` is [ERPL_SUMMARY_DIM][n] caller-owned
+ * device memory; `mask` is [n] caller-owned device bytes - the `reasons` of erpl_mc_analyze - NULL = every sample counts; a
+ * sample is COUNTED iff its mask byte is 0 and both rows are finite (m of them, in sample order); spec, result, grid_x,
+ * grid_y and density are host memory; the work is enqueued on `hip_stream` behind what is there and the call returns when
+ * the result is filled (it waits on that stream twice: the bandwidth and the ranges are settled on the host, in double,
+ * from the moments); the workspace belongs to the context, grows only with n and the node count (29 bytes per sample, 24 per
+ * node, 8 MiB of partial sums and the select's scratch) and is freed by erpl_mc_destroy.  ERPL_ERR_INVALID, before
+ * any device work and with a message that names the argument, for: a NULL spec; a row outside 0..15 or row_x == row_y;
+ * nodes outside 2..ERPL_DENSITY_MAX_NODES; on an axis lo and hi neither both NaN nor both finite with lo < hi; pad negative
+ * or not finite; bandwidth neither ERPL_BW_SCOTT nor ERPL_BW_MATRIX; ERPL_BW_SCOTT with bw_scale not finite or <= 0;
+ * ERPL_BW_MATRIX with h_xx, h_xy, h_yy not finite or not positive definite; n_levels outside 0..ERPL_DENSITY_MAX_LEVELS, a
+ * level outside (0, 1) or NaN; n_zones outside 0..ERPL_DENSITY_MAX_ZONES, zone_first[0] != 0, zone_first decreasing, a zone
+ * of fewer than 3 vertices, more than ERPL_DENSITY_MAX_VERTICES vertices together, a vertex that is not finite; n <= 0 or
+ * n >= 2^31; a NULL summary, grid_x, grid_y, density or result - in this order, the context last.  No floating-point
+ * atomics and every sum in a fixed order (below): two calls on the same inputs return the same bytes.
+ *
+ * Moments (two passes over the counted points gathered into a dense array, the mean read on the device, summed on the grid
+ * of m: what lies between the counted samples does not reach a sum): count, mean, min / max of both rows and the SAMPLE
+ * covariance S (divisor m - 1; NaN for m == 1).
+ * Bandwidth H: ERPL_BW_SCOTT: H = (bw_scale m^(-1/6))^2 S - the default of scipy.stats.gaussian_kde (Scott's and Silverman's
+ * factors coincide in two dimensions); ERPL_BW_MATRIX: H = (h_xx, h_xy, h_yy) as given.  det = h_xx h_yy - h_xy h_xy.
+ * Density: f(g) = norm * sum_i exp(-(g - x_i)' H^-1 (g - x_i) / 2), norm = 1 / (m 2 pi sqrt(det)).  The counted points and
+ * every query point are centred on the mean and mapped through the inverse of the Cholesky factor C of H (H = C C'):
+ * u = dx / c11, v = (dy - c21 u) / c22 as u = w11 dx, v = fma(w21, dx, w22 dy); the exponent of a pair is
+ * -0.5 fma(dv, dv, du du).
+ * Summation order (the contract: the bytes depend on the counted samples in their order and on the spec, nothing else): the
+ * sources of a query are cut into `slices` runs of `per_slice` consecutive dense indices, slices = ceil(t / ceil(t / min(t,
+ * ceil(1024 / ceil(queries / 1024))))) with t = ceil(m / 1024) and per_slice = 1024 ceil(t / that minimum) - functions of m
+ * and the number of queries alone; within a slice the terms are added in index order onto 0, the slices are added in slice
+ * order onto the first, and the sum is multiplied by norm once.  That covers the map, the row, peak, grid_mass, the moments
+ * and, of result->sample_density, count, min, max, order_lo / order_hi and quantile; its mean and std are summed over the
+ * [n] row as erpl_mc_analyze sums a row, in an order that depends on n: the same in every call on the same inputs, but the
+ * last bits may differ between the same counted samples with and without other samples between them.
+ * Grid: node (i, j) is (grid_x[i], grid_y[j]) with grid_x = np.linspace(lo_x, hi_x, nodes_x) (two roundings per node, the
+ * last one hi exactly), grid_y likewise; density is [nodes_x][nodes_y], x-major, the layout of erpl_mc_histogram_xy.  An
+ * automatic range on an axis is min - pad sqrt(h) .. max + pad sqrt(h) of the counted values, h = h_xx / h_yy (without the
+ * pad where the estimate is not solid; (0, 1) if nothing was counted); an empty range is widened by a half either side; a
+ * range wider than a double holds is ERPL_ERR_INVALID after the pass that found it.  peak is the largest node value and
+ * (peak_ix, peak_iy) the first node, in x-major order, that holds it; grid_mass = (sum of the node values) * cell area,
+ * cell area = ((hi_x - lo_x) / (nodes_x - 1)) * ((hi_y - lo_y) / (nodes_y - 1)): how much of the probability the grid covers.
+ * Density at the samples: f_j = f(x_j), own term included (as kde(kde.dataset)), into the optional caller-owned device row
+ * `sample_density` [n], NaN where the sample is not counted.  This pass costs m * m pair evaluations (seconds at 10^6
+ * counted points); it runs only if n_levels > 0 or the caller passes the row: n_levels = 0 and a NULL row skip it.
+ * Regions: the highest-density region of content p is {g : f(g) >= t_p} with t_p the (1 - p)-quantile of the f_j (Hyndman
+ * 1996).  result->sample_density describes the f_j as erpl_mc_analyze describes a row, with q[k] = 1 - level[k]: exact order
+ * statistics order_lo / order_hi, and quantile[k] = t_p of level[k].
+ * Zones: zone z is the simple polygon of the vertices zone_first[z] .. zone_first[z + 1] - 1 of zone_x[] / zone_y[];
+ * zone_inside[z] counts the counted samples inside by the even-odd crossing rule: for i = first .. last with j the vertex
+ * before i (the last one for i = first), the sample (x, y) flips sides if (vy[i] > y) != (vy[j] > y) and
+ * x < (vx[j] - vx[i]) * (y - vy[i]) / (vy[j] - vy[i]) + vx[i], every operation rounded on its own (IEEE division, no FMA):
+ * the count NumPy gives for the same expression, to the last sample.
+ * Not solid (solid = 0): m == 0, H not finite, det <= 1e-12 h_xx h_yy (all counted points on a line), or ERPL_BW_SCOTT with
+ * m < 3.  Then every density, peak, grid_mass, norm and every double of sample_density is NaN and peak_ix = peak_iy = -1;
+ * count, the moments that exist, the ranges, the grid nodes and the zone counts are valid.  Not an error. */
+#define ERPL_DENSITY_MAX_NODES 512      /* per axis */
+#define ERPL_DENSITY_MAX_LEVELS 8       /* = ERPL_ANALYSIS_MAX_Q */
+#define ERPL_DENSITY_MAX_ZONES 8
+#define ERPL_DENSITY_MAX_VERTICES 256   /* of all zones together */
+enum { ERPL_BW_SCOTT = 0, ERPL_BW_MATRIX = 1 };
+
+typedef struct erpl_density_spec {
+  int32_t row_x, row_y;                 /* distinct, 0..15 */
+  int32_t nodes_x, nodes_y;             /* 2..ERPL_DENSITY_MAX_NODES */
+  double lo_x, hi_x, lo_y, hi_y;        /* per axis: both NaN = from the data, or both finite with lo < hi */
+  double pad;                           /* automatic range: bandwidth standard deviations beyond min / max; finite, >= 0 */
+  int32_t bandwidth;                    /* ERPL_BW_SCOTT | ERPL_BW_MATRIX */
+  int32_t n_levels;                     /* 0..ERPL_DENSITY_MAX_LEVELS */
+  double bw_scale;                      /* ERPL_BW_SCOTT: finite, > 0 */
+  double h_xx, h_xy, h_yy;              /* ERPL_BW_MATRIX: finite, positive definite */
+  double level[ERPL_DENSITY_MAX_LEVELS];   /* contents of the highest-density regions, in (0, 1) */
+  int32_t n_zones;                      /* 0..ERPL_DENSITY_MAX_ZONES */
+  int32_t zone_first[ERPL_DENSITY_MAX_ZONES + 1];   /* zone z: vertices zone_first[z] .. zone_first[z + 1] - 1; [0] = 0 */
+  double zone_x[ERPL_DENSITY_MAX_VERTICES], zone_y[ERPL_DENSITY_MAX_VERTICES];
+} erpl_density_spec;
+
+typedef struct erpl_density {
+  int64_t count;                        /* m: mask byte 0 and both rows finite */
+  int32_t solid;                        /* 1: the densities are numbers */
+  int32_t peak_ix, peak_iy;             /* node of the peak, -1 if not solid */
+  int32_t reserved;
+  double mean_x, mean_y;
+  double cov_xx, cov_xy, cov_yy;        /* S, divisor m - 1 */
+  double h_xx, h_xy, h_yy, det;         /* H in use */
+  double norm;                          /* 1 / (m 2 pi sqrt(det)) */
+  double lo_x, hi_x, lo_y, hi_y;        /* the ranges in use */
+  double peak, grid_mass;
+  int64_t zone_inside[ERPL_DENSITY_MAX_ZONES];
+  erpl_row_stats sample_density;        /* of the f_j; quantile[k] = the threshold t_p of level[k] */
+} erpl_density;
+
+/* Host only: rows {IMPACT_X, IMPACT_Y}, 128 x 128 nodes, automatic ranges with pad 3, ERPL_BW_SCOTT with bw_scale 1 (h_xx =
+ * h_yy = 1, h_xy = 0 for a caller that switches to ERPL_BW_MATRIX), levels {0.5, 0.9, 0.99}, no zones. */
+int erpl_mc_impact_density_defaults(erpl_density_spec* spec);
+/* grid_x: host double [nodes_x], grid_y: host double [nodes_y], density: host double [nodes_x][nodes_y];
+ * sample_density: optional caller-owned device double [n]. */
+int erpl_mc_impact_density(erpl_ctx* ctx, const double* summary, const uint8_t* mask, int64_t n,
+                           const erpl_density_spec* spec, double* grid_x, double* grid_y, double* density,
+                           erpl_density* result, double* sample_density, void* hip_stream);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
