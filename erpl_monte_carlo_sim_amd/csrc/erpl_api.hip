@@ -461,16 +461,7 @@ int erpl_mc_destroy(erpl_ctx* c) {
   for (int i = 0; i < 3 * ERPL_PROFILE_RING; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
   for (int i = 0; i < ERPL_TICKET_RING; ++i) if (c->ring_done[i]) (void)hipEventDestroy(c->ring_done[i]);
   if (c->ring_counters) (void)hipHostFree(c->ring_counters);
-  (void)hipFree(c->ana_work); (void)hipFree(c->ana_why);
-  if (c->ana_host) (void)hipHostFree(c->ana_host);
-  (void)hipFree(c->dist_work); (void)hipFree(c->dist_miss);
-  if (c->dist_host) (void)hipHostFree(c->dist_host);
-  (void)hipFree(c->corr_work); (void)hipFree(c->corr_buf);
-  if (c->corr_host) (void)hipHostFree(c->corr_host);
-  (void)hipFree(c->boot_buf);
-  if (c->boot_host) (void)hipHostFree(c->boot_host);
-  (void)hipFree(c->dens_work); (void)hipFree(c->dens_buf);
-  if (c->dens_host) (void)hipHostFree(c->dens_host);
+  c->ana.release(); c->dist.release(); c->corr.release(); c->boot.release(); c->dens.release();
   (void)hipFree(c->legacy_buf);
   if (c->legacy_pin) (void)hipHostFree(c->legacy_pin);
   for (hipEvent_t e : c->legacy_ev) if (e) (void)hipEventDestroy(e);

@@ -1,6 +1,6 @@
 // erpl_host.h — what the host units of the C ABI share (erpl_api.hip, erpl_sampling.hip, erpl_stats_api.hip,
-// erpl_legacy_device.hip): the error
-// text behind erpl_mc_last_error, the context, and the host patterns that exist once.  Internal, never installed.
+// erpl_legacy_device.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
+// Internal, never installed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -8,9 +8,11 @@
 
 #include <functional>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "erpl_plan.h"
+#include "erpl_stat_layout.h"
 #include "erpl_tables.h"
 
 // Formats the text erpl_mc_last_error returns and hands `code` back.  The thread-local buffer is defined once, in
@@ -62,6 +64,40 @@ struct DensHost {
   ErplDensMoments mom;
   ErplDensOut out;
   ErplDensIn in;
+};
+
+// The only place a per-context device buffer grows (the policy of erpl_mc_reserve): never shrinks, freed by
+// erpl_mc_destroy.  An earlier call on another stream may still read the old buffer, hence the device synchronise.
+template <typename T>
+int erpl_grow(T*& p, size_t& cap, size_t bytes) {
+  if (bytes <= cap) return ERPL_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  (void)hipFree(p);
+  p = nullptr; cap = 0;
+  HIP_TRY(hipMalloc((void**)&p, bytes));
+  cap = bytes;
+  return ERPL_OK;
+}
+
+// What the context keeps for one statistics unit: a fixed device block (Dev = void: none) and its pinned mirror, both
+// allocated with the first call that needs them, and one device buffer that grows with the call (erpl_grow).
+template <typename Dev, typename Host>
+struct ErplStatUnit {
+  Dev* work = nullptr;
+  Host* host = nullptr;
+  char* buf = nullptr;
+  size_t cap = 0;                 // bytes, as every capacity erpl_grow keeps
+  int first_use() {
+    if constexpr (!std::is_void<Dev>::value)
+      if (!work) HIP_TRY(hipMalloc((void**)&work, sizeof(Dev)));
+    if (!host) HIP_TRY(hipHostMalloc((void**)&host, sizeof(Host), hipHostMallocDefault));
+    return ERPL_OK;
+  }
+  int grow(size_t bytes) { return erpl_grow(buf, cap, bytes); }
+  void release() {                // erpl_mc_destroy
+    (void)hipFree(work); (void)hipFree(buf);
+    if (host) (void)hipHostFree(host);
+  }
 };
 
 // Slot 0 serves erpl_mc_run_batch (on the caller's stream); slots 0..depth-1 serve erpl_mc_submit_batch
@@ -138,35 +174,15 @@ struct erpl_ctx {
   bool profiling = false;
   long long profiled_runs = 0;
   hipEvent_t ev[3 * ERPL_PROFILE_RING] = {};
-  // erpl_mc_analyze: fixed block (partials, histograms, counters), one reason byte per sample, pinned copy of the result
-  ErplAnaWork* ana_work = nullptr;
-  uint8_t* ana_why = nullptr;
-  size_t ana_cap = 0;             // bytes, as every capacity erpl_grow keeps
-  ErplAnaResult* ana_host = nullptr;
-  // erpl_mc_histogram / _histogram2d / _dispersion: fixed block (partials, edges, bins, cells), pinned mirror of what the
-  // host reads and writes, one double per sample for the miss distance when the caller keeps none
-  ErplDistWork* dist_work = nullptr;
-  DistHost* dist_host = nullptr;
-  double* dist_miss = nullptr;
-  size_t dist_cap = 0;
-  // erpl_mc_correlation: fixed block (partials, the blocked Gram triangles), pinned mirror of its result part, and one
-  // buffer that grows with n * V: sort keys and indices, the rows of ranks, the population bytes, the sort's scratch
-  ErplCorrWork* corr_work = nullptr;
-  ErplCorrOut* corr_host = nullptr;
-  char* corr_buf = nullptr;
-  size_t corr_cap = 0;
-  // erpl_mc_bootstrap: pinned mirror of its results and one buffer that grows with n * n_rows and with the replicates:
-  // population bytes, the dense rows, their sorted copies and positions, sort keys and scratch, the replicate matrix
-  BootHost* boot_host = nullptr;
-  char* boot_buf = nullptr;
-  size_t boot_cap = 0;
-  // erpl_mc_impact_density: fixed block (partials, grid nodes, zone vertices, results), its pinned mirror, and one buffer
-  // that grows with n and the node count: population bytes, dense indices, the select's scratch, whitened points and nodes,
-  // the sample row when the caller keeps none, the node densities and the partial sums of the slices
-  ErplDensWork* dens_work = nullptr;
-  DensHost* dens_host = nullptr;
-  char* dens_buf = nullptr;
-  size_t dens_cap = 0;
+  // The statistics units (ErplStatUnit above) and what grows in each.  erpl_mc_analyze: one reason byte per sample, also the
+  // row of zero bytes that stands in for a mask.  erpl_mc_histogram / _histogram_xy / _dispersion: the miss distance, one
+  // double per sample, when the caller keeps none.  erpl_mc_correlation, erpl_mc_bootstrap (no device block of its own: it
+  // runs on those of `corr` and `ana`) and erpl_mc_impact_density: the pieces of erpl_stat_layout.h.
+  ErplStatUnit<ErplAnaWork, ErplAnaResult> ana;
+  ErplStatUnit<ErplDistWork, DistHost> dist;
+  ErplStatUnit<ErplCorrWork, ErplCorrOut> corr;
+  ErplStatUnit<void, BootHost> boot;
+  ErplStatUnit<ErplDensWork, DensHost> dens;
   // erpl_mc_legacy_random_streams_device / _wind_profiles_device: one device buffer (flag, op tables, knot constants, the
   // MT19937 states of a tile and two sets of its accepted pairs) and its pinned staging (the tables on their way up, r2
   // down and f up, per set), both bounded by the tile; an event per set behind the tile's copy to the host
@@ -176,27 +192,6 @@ struct erpl_ctx {
   size_t legacy_pin_cap = 0;
   hipEvent_t legacy_ev[2] = {};
 };
-
-// A fixed device block and its pinned mirror, both allocated with the first call that needs them and freed by erpl_mc_destroy.
-template <typename Dev, typename Host>
-int erpl_first_use(Dev*& dev, Host*& host) {
-  if (!dev) HIP_TRY(hipMalloc((void**)&dev, sizeof(Dev)));
-  if (!host) HIP_TRY(hipHostMalloc((void**)&host, sizeof(Host), hipHostMallocDefault));
-  return ERPL_OK;
-}
-
-// The only place a per-context device buffer grows (the policy of erpl_mc_reserve): never shrinks, freed by
-// erpl_mc_destroy.  An earlier call on another stream may still read the old buffer, hence the device synchronise.
-template <typename T>
-int erpl_grow(T*& p, size_t& cap, size_t bytes) {
-  if (bytes <= cap) return ERPL_OK;
-  HIP_TRY(hipDeviceSynchronize());
-  (void)hipFree(p);
-  p = nullptr; cap = 0;
-  HIP_TRY(hipMalloc((void**)&p, bytes));
-  cap = bytes;
-  return ERPL_OK;
-}
 
 // The scale of an accepted pair of the legacy polar Gaussian (LegacyRS::next_gauss, and the host phase of the device
 // streams): the one copy, so that both go through the same libm log with the same rounding of the quotient.

@@ -1,0 +1,91 @@
+// erpl_stat_layout.h — how erpl_mc_correlation, erpl_mc_bootstrap and erpl_mc_impact_density cut the device buffer each of
+// them grows into pieces: pure functions of the call's sizes (no HIP; the scratch size of the rocPRIM calls comes in as a
+// number), so that tests/test_stat_layout.py checks every offset on the CPU, through erpl_stat_layout_table, before a kernel
+// writes through one.  Every piece starts at a multiple of 256 bytes; `need` is the end of the last one.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "erpl_tables.h"
+
+inline size_t erpl_align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// The pieces of a buffer, one after the other: take(bytes) is where the next one starts (no bytes: what the caller keeps).
+struct ErplCarve {
+  size_t at = 0, end = 0;   // where the next piece starts, where the last one ends
+  size_t take(size_t bytes) {
+    end = at + bytes;
+    at = erpl_align256(end);
+    return end - bytes;
+  }
+};
+// the scratch a rocPRIM call asked for as the piece it gets, and is told it has: never empty, whole lines of 256 bytes
+inline size_t erpl_scratch_piece(size_t temp_bytes) { return erpl_align256(temp_bytes < 256 ? 256 : temp_bytes); }
+
+// erpl_mc_correlation: [keys 2n u64][ranks V n doubles unless the caller keeps them][idx 2n u32][scratch of the sort] - these
+// four with spec->ranks only - [pop n bytes]
+struct ErplCorrLayout { size_t keys, ranks, idx, temp, pop, temp_bytes, need; };
+inline ErplCorrLayout erpl_corr_layout(int64_t n, int V, bool ranks, bool caller_keeps_ranks, size_t temp_bytes) {
+  const size_t un = (size_t)n;
+  ErplCarve c;
+  ErplCorrLayout l = {};
+  if (ranks) {
+    l.keys = c.take(16 * un);
+    l.ranks = c.take(caller_keeps_ranks ? 0 : 8 * un * (size_t)V);
+    l.idx = c.take(8 * un);
+    l.temp_bytes = erpl_scratch_piece(temp_bytes);
+    l.temp = c.take(l.temp_bytes);
+  }
+  l.pop = c.take(un);
+  l.need = c.end;
+  return l;
+}
+
+// erpl_mc_bootstrap: [pop n bytes][src n u32][count][x R rows of n doubles][sorted the same][pos R rows of n u32][keys 2n u64]
+// [idx 2n u32][scratch of the select / the sort][zero bytes B][replicates n_stats B doubles unless the caller keeps them]
+struct ErplBootLayout {
+  size_t pop, src, count, x[ERPL_BOOT_MAX_ROWS], sorted[ERPL_BOOT_MAX_ROWS], pos[ERPL_BOOT_MAX_ROWS], keys, idx, temp, zero, rep,
+      temp_bytes, need;
+};
+inline ErplBootLayout erpl_boot_layout(int64_t n, int R, int n_stats, int B, bool caller_keeps_replicates, size_t temp_bytes) {
+  const size_t un = (size_t)n, uB = (size_t)B;
+  ErplCarve c;
+  ErplBootLayout l = {};
+  l.pop = c.take(un);
+  l.src = c.take(4 * un);
+  l.count = c.take(8);
+  for (int j = 0; j < R; ++j) l.x[j] = c.take(8 * un);
+  for (int j = 0; j < R; ++j) l.sorted[j] = c.take(8 * un);
+  for (int j = 0; j < R; ++j) l.pos[j] = c.take(4 * un);
+  l.keys = c.take(16 * un);
+  l.idx = c.take(8 * un);
+  l.temp_bytes = erpl_scratch_piece(temp_bytes);
+  l.temp = c.take(l.temp_bytes);
+  l.zero = c.take(uB);
+  l.rep = c.take(caller_keeps_replicates ? 0 : 8 * uB * (size_t)n_stats);
+  l.need = c.end;
+  return l;
+}
+
+// erpl_mc_impact_density: [pop n bytes][src n u32][count][scratch of the select][points n (x, y), then (u, v)][nodes (u, v)]
+// [node densities][the sample row, if there is one and the caller does not keep it][partial sums: at most
+// ERPL_DENS_TARGET_BLOCKS * ERPL_DENS_TILE + queries doubles (erpl_dens_slices), queries = the nodes or the samples]
+struct ErplDensLayout { size_t pop, src, count, temp, pts, nodes, dens, row, part, temp_bytes, need; };
+inline ErplDensLayout erpl_dens_layout(int64_t n, int64_t nodes, bool want_samples, bool caller_keeps_row, size_t temp_bytes) {
+  const size_t un = (size_t)n, un_nodes = (size_t)nodes;
+  ErplCarve c;
+  ErplDensLayout l = {};
+  l.pop = c.take(un);
+  l.src = c.take(4 * un);
+  l.count = c.take(8);
+  l.temp_bytes = erpl_scratch_piece(temp_bytes);
+  l.temp = c.take(l.temp_bytes);
+  l.pts = c.take(16 * un);
+  l.nodes = c.take(16 * un_nodes);
+  l.dens = c.take(8 * un_nodes);
+  l.row = c.take(want_samples && !caller_keeps_row ? 8 * un : 0);
+  const size_t queries = want_samples && un > un_nodes ? un : un_nodes;
+  l.part = c.take(8 * ((size_t)ERPL_DENS_TARGET_BLOCKS * ERPL_DENS_TILE + queries));
+  l.need = c.end;
+  return l;
+}

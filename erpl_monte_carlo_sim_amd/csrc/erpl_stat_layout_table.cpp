@@ -1,0 +1,43 @@
+// erpl_stat_layout_table.cpp — prints what erpl_stat_layout.h lays out, for tests/test_stat_layout.py (host compiler only,
+// no HIP).  stdin, one request per line; stdout, one line per request: the offsets in the order of the struct, then the
+// scratch size the launches are told and `need`.
+//   corr <n> <V> <ranks> <caller_keeps_ranks> <temp_bytes>               -> keys ranks idx temp pop temp_bytes need
+//   boot <n> <R> <n_stats> <B> <caller_keeps_replicates> <temp_bytes>    -> pop src count x[R] sorted[R] pos[R] keys idx temp zero
+//                                                                           rep temp_bytes need
+//   dens <n> <nodes> <want_samples> <caller_keeps_row> <temp_bytes>      -> pop src count temp pts nodes dens row part temp_bytes need
+#include <stdio.h>
+
+#include <initializer_list>
+
+#include "erpl_stat_layout.h"
+
+static void put(size_t v, const char* end = " ") { printf("%zu%s", v, end); }
+
+int main() {
+  char line[256];
+  while (fgets(line, sizeof(line), stdin)) {
+    long long n, nodes;
+    int a, b, c, d;
+    size_t temp;
+    if (sscanf(line, "corr %lld %d %d %d %zu", &n, &a, &b, &c, &temp) == 5) {
+      const ErplCorrLayout l = erpl_corr_layout(n, a, b != 0, c != 0, temp);
+      for (size_t v : {l.keys, l.ranks, l.idx, l.temp, l.pop, l.temp_bytes}) put(v);
+      put(l.need, "\n");
+    } else if (sscanf(line, "boot %lld %d %d %d %d %zu", &n, &a, &b, &c, &d, &temp) == 6 && a >= 1 && a <= ERPL_BOOT_MAX_ROWS) {
+      const ErplBootLayout l = erpl_boot_layout(n, a, b, c, d != 0, temp);
+      for (size_t v : {l.pop, l.src, l.count}) put(v);
+      for (const size_t* rows : {l.x, l.sorted, l.pos})
+        for (int j = 0; j < a; ++j) put(rows[j]);
+      for (size_t v : {l.keys, l.idx, l.temp, l.zero, l.rep, l.temp_bytes}) put(v);
+      put(l.need, "\n");
+    } else if (sscanf(line, "dens %lld %lld %d %d %zu", &n, &nodes, &a, &b, &temp) == 5) {
+      const ErplDensLayout l = erpl_dens_layout(n, nodes, a != 0, b != 0, temp);
+      for (size_t v : {l.pop, l.src, l.count, l.temp, l.pts, l.nodes, l.dens, l.row, l.part, l.temp_bytes}) put(v);
+      put(l.need, "\n");
+    } else {
+      fprintf(stderr, "bad request: %s", line);
+      return 1;
+    }
+  }
+  return 0;
+}

@@ -1,8 +1,11 @@
 // erpl_stats_api.hip — host halves of the analysis entry points of the C ABI (include/erpl_mc.h): erpl_mc_analyze,
-// erpl_mc_histogram, erpl_mc_histogram_xy, erpl_mc_dispersion, erpl_mc_correlation, erpl_mc_bootstrap and their defaults.
-// Argument checks, workspace, launches (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip,
-// erpl_bootstrap.hip) and what the host finishes in double precision.  The refusals come in one order everywhere - spec
-// fields, n, pointers, context (erpl_mc_bootstrap: the order its header comment lists) - and need no device.
+// erpl_mc_histogram, erpl_mc_histogram_xy, erpl_mc_dispersion, erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density
+// and their defaults.  Argument checks, workspace, launches (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip,
+// erpl_bootstrap.hip, erpl_density.hip) and what the host finishes in double precision.  The refusals come in one order
+// everywhere - spec fields, n, pointers, context (erpl_mc_bootstrap: the order its header comment lists) - and need no
+// device; tests/golden/stats_refusals.json pins their texts.  What the entry points share comes first: the pieces of the
+// argument checks, describe_rows, the host finish of a described row and of a landing cloud.  The growing buffers are laid
+// out in erpl_stat_layout.h; the context keeps an ErplStatUnit per unit (erpl_host.h).
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -15,29 +18,82 @@
 
 namespace {
 
-int check_row(int row, const char* name, int j) {
-  if (row >= 0 && row < ERPL_SUMMARY_DIM) return ERPL_OK;
-  if (j >= 0) return erpl_fail(ERPL_ERR_INVALID, "spec->%s[%d] = %d outside 0..%d", name, j, row, ERPL_SUMMARY_DIM - 1);
-  return erpl_fail(ERPL_ERR_INVALID, "spec->%s = %d outside 0..%d", name, row, ERPL_SUMMARY_DIM - 1);
+// a pointer the call needs, refused by the name of the argument
+#define NEED_AS(p, name) do { if (!(p)) return erpl_fail(ERPL_ERR_INVALID, name " is NULL"); } while (0)
+#define NEED(p) NEED_AS(p, #p)
+
+// an integer field of a spec in lo..hi; j >= 0: element j of an array field
+int check_int(int v, const char* name, int j, int lo, int hi) {
+  if (v >= lo && v <= hi) return ERPL_OK;
+  if (j >= 0) return erpl_fail(ERPL_ERR_INVALID, "spec->%s[%d] = %d outside %d..%d", name, j, v, lo, hi);
+  return erpl_fail(ERPL_ERR_INVALID, "spec->%s = %d outside %d..%d", name, v, lo, hi);
 }
 
-// spec->rows of any spec: summary rows in range, none listed twice (how many there may be is the entry point's own bound)
-int check_row_list(const int32_t* rows, int n_rows) {
+// n_rows in lo..hi, then spec->rows of any spec: rows in 0..last, none listed twice
+int check_row_list(const int32_t* rows, int n_rows, int lo, int hi, int last = ERPL_SUMMARY_DIM - 1) {
+  ERPL_TRY(check_int(n_rows, "n_rows", -1, lo, hi));
   for (int j = 0; j < n_rows; ++j) {
-    ERPL_TRY(check_row(rows[j], "rows", j));
+    ERPL_TRY(check_int(rows[j], "rows", j, 0, last));
     for (int k = 0; k < j; ++k)
       if (rows[k] == rows[j]) return erpl_fail(ERPL_ERR_INVALID, "spec->rows[%d] = %d is listed twice", j, rows[j]);
   }
   return ERPL_OK;
 }
 
-// spec->q of erpl_analysis_spec and erpl_dispersion_spec: at most ERPL_ANALYSIS_MAX_Q fractions in [0, 1]
+// row_x / row_y of a spec about the landing plane: two different summary rows
+int check_row_pair(int row_x, int row_y) {
+  ERPL_TRY(check_int(row_x, "row_x", -1, 0, ERPL_SUMMARY_DIM - 1));
+  ERPL_TRY(check_int(row_y, "row_y", -1, 0, ERPL_SUMMARY_DIM - 1));
+  if (row_x == row_y) return erpl_fail(ERPL_ERR_INVALID, "spec->row_y = %d is listed twice (row_x)", row_y);
+  return ERPL_OK;
+}
+
+// spec->q of any spec: at most ERPL_ANALYSIS_MAX_Q fractions in [0, 1]
 int check_quantiles(const double* q, int n_q) {
-  if (n_q < 0 || n_q > ERPL_ANALYSIS_MAX_Q)
-    return erpl_fail(ERPL_ERR_INVALID, "spec->n_q = %d outside 0..%d", n_q, ERPL_ANALYSIS_MAX_Q);
+  ERPL_TRY(check_int(n_q, "n_q", -1, 0, ERPL_ANALYSIS_MAX_Q));
   for (int j = 0; j < n_q; ++j)
     if (!(q[j] >= 0.0 && q[j] <= 1.0)) return erpl_fail(ERPL_ERR_INVALID, "spec->q[%d] = %g outside [0, 1]", j, q[j]);
   return ERPL_OK;
+}
+
+// spec->level of erpl_dispersion_spec and erpl_density_spec: at most `most` contents in (0, 1)
+int check_levels(const double* level, int n_levels, int most) {
+  ERPL_TRY(check_int(n_levels, "n_levels", -1, 0, most));
+  for (int k = 0; k < n_levels; ++k)
+    if (!(level[k] > 0.0 && level[k] < 1.0)) return erpl_fail(ERPL_ERR_INVALID, "spec->level[%d] = %g outside (0, 1)", k, level[k]);
+  return ERPL_OK;
+}
+
+// n: at least one sample and, where sample indices are carried in fewer bits, at most `most` (`why` ends the refusal)
+int check_n(int64_t n, int64_t most = INT64_MAX, const char* why = "") {
+  if (n <= 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
+  if (n > most) return erpl_fail(ERPL_ERR_INVALID, "n = %lld%s", (long long)n, why);
+  return ERPL_OK;
+}
+
+// Rows of `summary` ([.][n]; rows == NULL: its first n_rows rows) through the moment passes and the selection of
+// erpl_mc_analyze with `why` as the mask (read only there), and the copy of what they find into the pinned `out`.
+int describe_rows(erpl_ctx* c, const double* summary, const uint8_t* why, int64_t n, const int32_t* rows, int n_rows,
+                  const double* q, int n_q, ErplAnaResult* out, hipStream_t st) {
+  ErplAnaArgs a;
+  memset(&a, 0, sizeof(a));
+  a.summary = summary; a.why = const_cast<uint8_t*>(why); a.work = c->ana.work; a.n = n; a.n_rows = n_rows; a.n_q = n_q;
+  for (int j = 0; j < n_rows; ++j) a.rows[j] = rows ? rows[j] : j;
+  for (int k = 0; k < n_q; ++k) a.q[k] = q[k];
+  KERNEL_TRY(erpl_launch_row_stats(a, st));
+  HIP_TRY(hipMemcpyAsync(out, &c->ana.work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, st));
+  return ERPL_OK;
+}
+
+// count, mean and covariance of a landing cloud into a result that has these fields: NaN when nothing was counted
+template <typename Result>
+bool finish_cloud(Result* r, unsigned long long count, double mean_x, double mean_y, double cov_xx, double cov_xy, double cov_yy) {
+  const bool any = count > 0ull;
+  const double nan = NAN;
+  r->count = (int64_t)count;
+  r->mean_x = any ? mean_x : nan; r->mean_y = any ? mean_y : nan;
+  r->cov_xx = any ? cov_xx : nan; r->cov_xy = any ? cov_xy : nan; r->cov_yy = any ? cov_yy : nan;
+  return any;
 }
 
 // the inverse of key_of_signed (erpl_stat_device.h)
@@ -74,9 +130,7 @@ int check_analysis_spec(const erpl_analysis_spec* s) {
   const char* name[5] = {"max_apogee", "min_apogee", "max_range", "max_flight_time", "energy_apogee"};
   for (int k = 0; k < 5; ++k)
     if (std::isnan(bound[k])) return erpl_fail(ERPL_ERR_INVALID, "spec->%s is NaN", name[k]);
-  if (s->n_rows < 0 || s->n_rows > ERPL_ANALYSIS_MAX_ROWS)
-    return erpl_fail(ERPL_ERR_INVALID, "spec->n_rows = %d outside 0..%d", s->n_rows, ERPL_ANALYSIS_MAX_ROWS);
-  ERPL_TRY(check_row_list(s->rows, s->n_rows));
+  ERPL_TRY(check_row_list(s->rows, s->n_rows, 0, ERPL_ANALYSIS_MAX_ROWS));
   return check_quantiles(s->q, s->n_q);
 }
 
@@ -85,7 +139,7 @@ int check_analysis_spec(const erpl_analysis_spec* s) {
 extern "C" {
 
 int erpl_mc_analysis_defaults(erpl_analysis_spec* spec) {
-  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  NEED(spec);
   memset(spec, 0, sizeof(*spec));
   spec->max_apogee = 80000.0;        // monte_carlo.py:343-346
   spec->min_apogee = 100.0;
@@ -105,28 +159,26 @@ int erpl_mc_analysis_defaults(erpl_analysis_spec* spec) {
 int erpl_mc_analyze(erpl_ctx* c, const double* summary, const int32_t* status, int64_t n, const erpl_analysis_spec* spec,
                     erpl_analysis* result, uint8_t* reasons, void* stream) {
   // spec, n and the pointers before the context: the argument checks need no device
-  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  NEED(spec);
   ERPL_TRY(check_analysis_spec(spec));
-  if (n <= 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
-  if (!summary) return erpl_fail(ERPL_ERR_INVALID, "summary is NULL");
-  if (!result) return erpl_fail(ERPL_ERR_INVALID, "result is NULL");
-  if (!c) return erpl_fail(ERPL_ERR_INVALID, "ctx is NULL");
+  ERPL_TRY(check_n(n));
+  NEED(summary); NEED(result); NEED_AS(c, "ctx");
   HIP_TRY(hipSetDevice(c->device));
-  ERPL_TRY(erpl_first_use(c->ana_work, c->ana_host));
-  ERPL_TRY(erpl_grow(c->ana_why, c->ana_cap, (size_t)n));   // one reason byte per sample
+  ERPL_TRY(c->ana.first_use());
+  ERPL_TRY(c->ana.grow((size_t)n));   // one reason byte per sample
   ErplAnaArgs a;
   memset(&a, 0, sizeof(a));
-  a.summary = summary; a.status = status; a.why = c->ana_why; a.reasons = reasons; a.work = c->ana_work; a.n = n;
+  a.summary = summary; a.status = status; a.why = (uint8_t*)c->ana.buf; a.reasons = reasons; a.work = c->ana.work; a.n = n;
   a.max_apogee = spec->max_apogee; a.min_apogee = spec->min_apogee; a.max_range = spec->max_range;
   a.max_flight_time = spec->max_flight_time; a.energy_apogee = spec->energy_apogee;
   a.n_rows = spec->n_rows; a.n_q = spec->n_q;
   for (int j = 0; j < spec->n_rows; ++j) a.rows[j] = spec->rows[j];
   for (int j = 0; j < spec->n_q; ++j) a.q[j] = spec->q[j];
   KERNEL_TRY(erpl_launch_analysis(a, stream));
-  HIP_TRY(hipMemcpyAsync(c->ana_host, &c->ana_work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipMemcpyAsync(c->ana.host, &c->ana.work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
 
-  const ErplAnaResult& d = *c->ana_host;
+  const ErplAnaResult& d = *c->ana.host;
   memset(result, 0, sizeof(*result));
   result->n = n;
   result->n_valid = (int64_t)d.counter[13];
@@ -186,12 +238,12 @@ void fill_edges(double lo, double hi, int bins, double* e) {
 // axis whose range is wider than a double holds - the entry points name their fields differently.
 template <typename Refuse>
 int dist_edges(erpl_ctx* c, ErplDistArgs& a, hipStream_t st, Refuse too_wide) {
-  DistHost& h = *c->dist_host;
+  DistHost& h = *c->dist.host;
   bool any_auto = false;
   for (int j = 0; j < a.n_rows; ++j) any_auto = any_auto || a.automatic[j] != 0;
   if (any_auto) {
     KERNEL_TRY(erpl_launch_dist_range(a, st));
-    HIP_TRY(hipMemcpyAsync(&h.range, &c->dist_work->range, sizeof(ErplDistRange), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&h.range, &c->dist.work->range, sizeof(ErplDistRange), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
   memset(h.edges, 0, (size_t)a.n_rows * sizeof(h.edges[0]));
@@ -199,7 +251,7 @@ int dist_edges(erpl_ctx* c, ErplDistArgs& a, hipStream_t st, Refuse too_wide) {
     if (!settle_range(a.automatic[j] != 0, h.range.lo[j], h.range.hi[j], &a.lo[j], &a.hi[j])) return too_wide(j);
     fill_edges(a.lo[j], a.hi[j], a.bins[j], h.edges[j]);
   }
-  HIP_TRY(hipMemcpyAsync(&c->dist_work->edges[0][0], &h.edges[0][0], (size_t)a.n_rows * sizeof(h.edges[0]),
+  HIP_TRY(hipMemcpyAsync(&c->dist.work->edges[0][0], &h.edges[0][0], (size_t)a.n_rows * sizeof(h.edges[0]),
                          hipMemcpyHostToDevice, st));
   return ERPL_OK;
 }
@@ -209,7 +261,7 @@ int dist_edges(erpl_ctx* c, ErplDistArgs& a, hipStream_t st, Refuse too_wide) {
 extern "C" {
 
 int erpl_mc_histogram_defaults(erpl_hist_spec* spec) {
-  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  NEED(spec);
   memset(spec, 0, sizeof(*spec));
   spec->n_rows = 3;
   spec->rows[0] = ERPL_SUM_APOGEE_ALT; spec->rows[1] = ERPL_SUM_RANGE; spec->rows[2] = ERPL_SUM_FLIGHT_TIME;
@@ -219,37 +271,30 @@ int erpl_mc_histogram_defaults(erpl_hist_spec* spec) {
 
 int erpl_mc_histogram(erpl_ctx* c, const double* summary, const uint8_t* mask, int64_t n, const erpl_hist_spec* spec,
                       double* edges, int64_t* counts, erpl_hist_result* result, void* stream) {
-  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
-  if (spec->n_rows < 1 || spec->n_rows > ERPL_HIST_MAX_ROWS)
-    return erpl_fail(ERPL_ERR_INVALID, "spec->n_rows = %d outside 1..%d", spec->n_rows, ERPL_HIST_MAX_ROWS);
-  ERPL_TRY(check_row_list(spec->rows, spec->n_rows));
+  NEED(spec);
+  ERPL_TRY(check_row_list(spec->rows, spec->n_rows, 1, ERPL_HIST_MAX_ROWS));
   ErplDistArgs a;
   memset(&a, 0, sizeof(a));
   for (int j = 0; j < spec->n_rows; ++j) {
-    if (spec->bins[j] < 1 || spec->bins[j] > ERPL_HIST_MAX_BINS)
-      return erpl_fail(ERPL_ERR_INVALID, "spec->bins[%d] = %d outside 1..%d", j, spec->bins[j], ERPL_HIST_MAX_BINS);
+    ERPL_TRY(check_int(spec->bins[j], "bins", j, 1, ERPL_HIST_MAX_BINS));
     const int rc = check_range(spec->lo[j], spec->hi[j], "lo", "hi", j);
     if (rc < 0) return rc;
     a.rows[j] = spec->rows[j]; a.partner[j] = -1; a.bins[j] = spec->bins[j]; a.automatic[j] = rc;
     a.lo[j] = spec->lo[j]; a.hi[j] = spec->hi[j];
   }
-  if (n <= 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
-  if (!summary) return erpl_fail(ERPL_ERR_INVALID, "summary is NULL");
-  if (!edges) return erpl_fail(ERPL_ERR_INVALID, "edges is NULL");
-  if (!counts) return erpl_fail(ERPL_ERR_INVALID, "counts is NULL");
-  if (!result) return erpl_fail(ERPL_ERR_INVALID, "result is NULL");
-  if (!c) return erpl_fail(ERPL_ERR_INVALID, "ctx is NULL");
+  ERPL_TRY(check_n(n));
+  NEED(summary); NEED(edges); NEED(counts); NEED(result); NEED_AS(c, "ctx");
   HIP_TRY(hipSetDevice(c->device));
-  ERPL_TRY(erpl_first_use(c->dist_work, c->dist_host));
+  ERPL_TRY(c->dist.first_use());
   hipStream_t st = (hipStream_t)stream;
-  DistHost& h = *c->dist_host;
-  a.summary = summary; a.mask = mask; a.work = c->dist_work; a.n = n; a.n_rows = spec->n_rows;
+  DistHost& h = *c->dist.host;
+  a.summary = summary; a.mask = mask; a.work = c->dist.work; a.n = n; a.n_rows = spec->n_rows;
   ERPL_TRY(dist_edges(c, a, st, [&](int j) {
     return erpl_fail(ERPL_ERR_INVALID, "spec->rows[%d] = %d: the range of the counted values, %g to %g, is wider than a double holds",
                      j, spec->rows[j], a.lo[j], a.hi[j]);
   }));
   KERNEL_TRY(erpl_launch_dist_hist(a, stream));
-  HIP_TRY(hipMemcpyAsync(&h.hist, &c->dist_work->hist, sizeof(ErplDistHist), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&h.hist, &c->dist.work->hist, sizeof(ErplDistHist), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   memset(result, 0, sizeof(*result));
   memcpy(edges, h.edges, (size_t)spec->n_rows * sizeof(h.edges[0]));
@@ -265,32 +310,23 @@ int erpl_mc_histogram(erpl_ctx* c, const double* summary, const uint8_t* mask, i
 
 int erpl_mc_histogram_xy(erpl_ctx* c, const double* summary, const uint8_t* mask, int64_t n, const erpl_hist2d_spec* spec,
                         double* edges_x, double* edges_y, int64_t* counts, erpl_hist2d_result* result, void* stream) {
-  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
-  ERPL_TRY(check_row(spec->row_x, "row_x", -1));
-  ERPL_TRY(check_row(spec->row_y, "row_y", -1));
-  if (spec->row_x == spec->row_y) return erpl_fail(ERPL_ERR_INVALID, "spec->row_y = %d is listed twice (row_x)", spec->row_y);
-  if (spec->bins_x < 1 || spec->bins_x > ERPL_HIST2D_MAX_BINS)
-    return erpl_fail(ERPL_ERR_INVALID, "spec->bins_x = %d outside 1..%d", spec->bins_x, ERPL_HIST2D_MAX_BINS);
-  if (spec->bins_y < 1 || spec->bins_y > ERPL_HIST2D_MAX_BINS)
-    return erpl_fail(ERPL_ERR_INVALID, "spec->bins_y = %d outside 1..%d", spec->bins_y, ERPL_HIST2D_MAX_BINS);
+  NEED(spec);
+  ERPL_TRY(check_row_pair(spec->row_x, spec->row_y));
+  ERPL_TRY(check_int(spec->bins_x, "bins_x", -1, 1, ERPL_HIST2D_MAX_BINS));
+  ERPL_TRY(check_int(spec->bins_y, "bins_y", -1, 1, ERPL_HIST2D_MAX_BINS));
   const int auto_x = check_range(spec->lo_x, spec->hi_x, "lo_x", "hi_x", -1);
   if (auto_x < 0) return auto_x;
   const int auto_y = check_range(spec->lo_y, spec->hi_y, "lo_y", "hi_y", -1);
   if (auto_y < 0) return auto_y;
-  if (n <= 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
-  if (!summary) return erpl_fail(ERPL_ERR_INVALID, "summary is NULL");
-  if (!edges_x) return erpl_fail(ERPL_ERR_INVALID, "edges_x is NULL");
-  if (!edges_y) return erpl_fail(ERPL_ERR_INVALID, "edges_y is NULL");
-  if (!counts) return erpl_fail(ERPL_ERR_INVALID, "counts is NULL");
-  if (!result) return erpl_fail(ERPL_ERR_INVALID, "result is NULL");
-  if (!c) return erpl_fail(ERPL_ERR_INVALID, "ctx is NULL");
+  ERPL_TRY(check_n(n));
+  NEED(summary); NEED(edges_x); NEED(edges_y); NEED(counts); NEED(result); NEED_AS(c, "ctx");
   HIP_TRY(hipSetDevice(c->device));
-  ERPL_TRY(erpl_first_use(c->dist_work, c->dist_host));
+  ERPL_TRY(c->dist.first_use());
   hipStream_t st = (hipStream_t)stream;
-  DistHost& h = *c->dist_host;
+  DistHost& h = *c->dist.host;
   ErplDistArgs a;
   memset(&a, 0, sizeof(a));
-  a.summary = summary; a.mask = mask; a.work = c->dist_work; a.n = n; a.n_rows = 2;
+  a.summary = summary; a.mask = mask; a.work = c->dist.work; a.n = n; a.n_rows = 2;
   a.rows[0] = spec->row_x; a.rows[1] = spec->row_y; a.partner[0] = spec->row_y; a.partner[1] = spec->row_x;
   a.bins[0] = spec->bins_x; a.bins[1] = spec->bins_y; a.automatic[0] = auto_x; a.automatic[1] = auto_y;
   a.lo[0] = spec->lo_x; a.hi[0] = spec->hi_x; a.lo[1] = spec->lo_y; a.hi[1] = spec->hi_y;
@@ -300,8 +336,8 @@ int erpl_mc_histogram_xy(erpl_ctx* c, const double* summary, const uint8_t* mask
   }));
   KERNEL_TRY(erpl_launch_dist_hist2d(a, stream));
   const size_t cells = (size_t)spec->bins_x * (size_t)spec->bins_y;
-  HIP_TRY(hipMemcpyAsync(&h.counted2, &c->dist_work->counted2, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(h.cells, c->dist_work->cells, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&h.counted2, &c->dist.work->counted2, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h.cells, c->dist.work->cells, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   memcpy(edges_x, h.edges[0], (size_t)(spec->bins_x + 1) * sizeof(double));
   memcpy(edges_y, h.edges[1], (size_t)(spec->bins_y + 1) * sizeof(double));
@@ -314,7 +350,7 @@ int erpl_mc_histogram_xy(erpl_ctx* c, const double* summary, const uint8_t* mask
 }
 
 int erpl_mc_dispersion_defaults(erpl_dispersion_spec* spec) {
-  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  NEED(spec);
   memset(spec, 0, sizeof(*spec));
   spec->row_x = ERPL_SUM_IMPACT_X; spec->row_y = ERPL_SUM_IMPACT_Y;
   spec->centre = ERPL_CENTRE_POINT;   // the launch site
@@ -327,56 +363,39 @@ int erpl_mc_dispersion_defaults(erpl_dispersion_spec* spec) {
 
 int erpl_mc_dispersion(erpl_ctx* c, const double* summary, const uint8_t* mask, int64_t n, const erpl_dispersion_spec* spec,
                        erpl_dispersion* result, double* miss, void* stream) {
-  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
-  ERPL_TRY(check_row(spec->row_x, "row_x", -1));
-  ERPL_TRY(check_row(spec->row_y, "row_y", -1));
-  if (spec->row_x == spec->row_y) return erpl_fail(ERPL_ERR_INVALID, "spec->row_y = %d is listed twice (row_x)", spec->row_y);
+  NEED(spec);
+  ERPL_TRY(check_row_pair(spec->row_x, spec->row_y));
   if (spec->centre != ERPL_CENTRE_MEAN && spec->centre != ERPL_CENTRE_POINT)
     return erpl_fail(ERPL_ERR_INVALID, "spec->centre = %d: ERPL_CENTRE_MEAN or ERPL_CENTRE_POINT", spec->centre);
   if (spec->centre == ERPL_CENTRE_POINT && !(std::isfinite(spec->cx) && std::isfinite(spec->cy)))
     return erpl_fail(ERPL_ERR_INVALID, "spec->cx = %g, spec->cy = %g: not a finite point", spec->cx, spec->cy);
-  if (spec->n_levels < 0 || spec->n_levels > ERPL_DISP_MAX_LEVELS)
-    return erpl_fail(ERPL_ERR_INVALID, "spec->n_levels = %d outside 0..%d", spec->n_levels, ERPL_DISP_MAX_LEVELS);
-  for (int k = 0; k < spec->n_levels; ++k)
-    if (!(spec->level[k] > 0.0 && spec->level[k] < 1.0))
-      return erpl_fail(ERPL_ERR_INVALID, "spec->level[%d] = %g outside (0, 1)", k, spec->level[k]);
+  ERPL_TRY(check_levels(spec->level, spec->n_levels, ERPL_DISP_MAX_LEVELS));
   ERPL_TRY(check_quantiles(spec->q, spec->n_q));
-  if (n <= 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
-  if (!summary) return erpl_fail(ERPL_ERR_INVALID, "summary is NULL");
-  if (!result) return erpl_fail(ERPL_ERR_INVALID, "result is NULL");
-  if (!c) return erpl_fail(ERPL_ERR_INVALID, "ctx is NULL");
+  ERPL_TRY(check_n(n));
+  NEED(summary); NEED(result); NEED_AS(c, "ctx");
   HIP_TRY(hipSetDevice(c->device));
-  ERPL_TRY(erpl_first_use(c->dist_work, c->dist_host));
-  if (!miss) ERPL_TRY(erpl_grow(c->dist_miss, c->dist_cap, (size_t)n * sizeof(double)));   // the caller keeps no miss distances
-  ERPL_TRY(erpl_first_use(c->ana_work, c->ana_host));                // the selection's block,
-  ERPL_TRY(erpl_grow(c->ana_why, c->ana_cap, (size_t)n));            // and a row of zero bytes to stand in for a mask
+  ERPL_TRY(c->dist.first_use());
+  if (!miss) ERPL_TRY(c->dist.grow((size_t)n * sizeof(double)));   // the caller keeps no miss distances
+  ERPL_TRY(c->ana.first_use());                                     // the selection's block,
+  ERPL_TRY(c->ana.grow((size_t)n));                                 // and a row of zero bytes to stand in for a mask
   hipStream_t st = (hipStream_t)stream;
   ErplDispArgs d;
   memset(&d, 0, sizeof(d));
-  d.summary = summary; d.mask = mask; d.work = c->dist_work; d.miss = miss ? miss : c->dist_miss; d.n = n;
+  d.summary = summary; d.mask = mask; d.work = c->dist.work; d.miss = miss ? miss : (double*)c->dist.buf; d.n = n;
   d.row_x = spec->row_x; d.row_y = spec->row_y; d.centre = spec->centre; d.n_levels = spec->n_levels;
   d.cx = spec->cx; d.cy = spec->cy;
   for (int k = 0; k < spec->n_levels; ++k) d.k2[k] = -2.0 * log(1.0 - spec->level[k]);
   KERNEL_TRY(erpl_launch_dispersion(d, stream));
   // the miss distance as a one-row summary through the moment passes and the selection of erpl_mc_analyze
-  ErplAnaArgs a;
-  memset(&a, 0, sizeof(a));
-  a.summary = d.miss; a.work = c->ana_work; a.n = n; a.n_rows = 1; a.rows[0] = 0; a.n_q = spec->n_q;
-  for (int k = 0; k < spec->n_q; ++k) a.q[k] = spec->q[k];
-  if (mask) a.why = const_cast<uint8_t*>(mask);   // read only there
-  else { HIP_TRY(hipMemsetAsync(c->ana_why, 0, (size_t)n, st)); a.why = c->ana_why; }
-  KERNEL_TRY(erpl_launch_row_stats(a, stream));
-  HIP_TRY(hipMemcpyAsync(&c->dist_host->mom, &c->dist_work->mom, sizeof(ErplDistMoments), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(c->ana_host, &c->ana_work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, st));
+  if (!mask) HIP_TRY(hipMemsetAsync(c->ana.buf, 0, (size_t)n, st));
+  ERPL_TRY(describe_rows(c, d.miss, mask ? mask : (const uint8_t*)c->ana.buf, n, nullptr, 1, spec->q, spec->n_q, c->ana.host, st));
+  HIP_TRY(hipMemcpyAsync(&c->dist.host->mom, &c->dist.work->mom, sizeof(ErplDistMoments), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
 
-  const ErplDistMoments& m = c->dist_host->mom;
+  const ErplDistMoments& m = c->dist.host->mom;
   const double nan = NAN;
   memset(result, 0, sizeof(*result));
-  result->count = (int64_t)m.count;
-  const bool any = m.count > 0ull;
-  result->mean_x = any ? m.mean_x : nan; result->mean_y = any ? m.mean_y : nan;
-  result->cov_xx = any ? m.cov_xx : nan; result->cov_xy = any ? m.cov_xy : nan; result->cov_yy = any ? m.cov_yy : nan;
+  const bool any = finish_cloud(result, m.count, m.mean_x, m.mean_y, m.cov_xx, m.cov_xy, m.cov_yy);
   const double half = (m.cov_xx + m.cov_yy) / 2, diff = (m.cov_xx - m.cov_yy) / 2;
   const double root = sqrt(diff * diff + m.cov_xy * m.cov_xy);
   result->var_major = any ? half + root : nan;
@@ -392,7 +411,7 @@ int erpl_mc_dispersion(erpl_ctx* c, const double* summary, const uint8_t* mask, 
     result->semi_minor[k] = asked && any ? sqrt(d.k2[k] * fmax(result->var_minor, 0.0)) : nan;
     result->inside[k] = !asked || !any ? 0 : (solid ? (int64_t)m.inside[k] : -1);
   }
-  finish_row_stats(c->ana_host->row[0], spec->q, spec->n_q, true, result->miss);
+  finish_row_stats(c->ana.host->row[0], spec->q, spec->n_q, true, result->miss);
   return ERPL_OK;
 }
 
@@ -466,7 +485,7 @@ bool regress(const double* corr, int V, int F, int R, const int32_t* constant, d
 extern "C" {
 
 int erpl_mc_correlation_defaults(erpl_corr_spec* spec) {
-  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  NEED(spec);
   memset(spec, 0, sizeof(*spec));
   spec->n_rows = 3;
   spec->rows[0] = ERPL_SUM_APOGEE_ALT; spec->rows[1] = ERPL_SUM_RANGE; spec->rows[2] = ERPL_SUM_FLIGHT_TIME;
@@ -477,22 +496,14 @@ int erpl_mc_correlation_defaults(erpl_corr_spec* spec) {
 int erpl_mc_correlation(erpl_ctx* c, const double* factors, const double* summary, const uint8_t* mask, int64_t n,
                         const erpl_corr_spec* spec, erpl_corr_result* result, double* corr, double* rank_corr,
                         double* ranks_out, void* stream) {
-  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
-  if (spec->n_factors < 1 || spec->n_factors > ERPL_CORR_MAX_FACTORS)
-    return erpl_fail(ERPL_ERR_INVALID, "spec->n_factors = %d outside 1..%d", spec->n_factors, ERPL_CORR_MAX_FACTORS);
-  if (spec->n_rows < 1 || spec->n_rows > ERPL_CORR_MAX_ROWS)
-    return erpl_fail(ERPL_ERR_INVALID, "spec->n_rows = %d outside 1..%d", spec->n_rows, ERPL_CORR_MAX_ROWS);
-  ERPL_TRY(check_row_list(spec->rows, spec->n_rows));
+  NEED(spec);
+  ERPL_TRY(check_int(spec->n_factors, "n_factors", -1, 1, ERPL_CORR_MAX_FACTORS));
+  ERPL_TRY(check_row_list(spec->rows, spec->n_rows, 1, ERPL_CORR_MAX_ROWS));
   if (spec->ranks != 0 && spec->ranks != 1) return erpl_fail(ERPL_ERR_INVALID, "spec->ranks = %d: 0 or 1", spec->ranks);
   if (!spec->ranks && rank_corr) return erpl_fail(ERPL_ERR_INVALID, "rank_corr is given but spec->ranks = 0");
   if (!spec->ranks && ranks_out) return erpl_fail(ERPL_ERR_INVALID, "ranks_out is given but spec->ranks = 0");
-  if (n <= 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
-  if (spec->ranks && n > 0xffffffffll)
-    return erpl_fail(ERPL_ERR_INVALID, "n = %lld with spec->ranks = 1: the sort carries 32-bit sample indices", (long long)n);
-  if (!factors) return erpl_fail(ERPL_ERR_INVALID, "factors is NULL");
-  if (!summary) return erpl_fail(ERPL_ERR_INVALID, "summary is NULL");
-  if (!result) return erpl_fail(ERPL_ERR_INVALID, "result is NULL");
-  if (!c) return erpl_fail(ERPL_ERR_INVALID, "ctx is NULL");
+  ERPL_TRY(check_n(n, spec->ranks ? 0xffffffffll : INT64_MAX, " with spec->ranks = 1: the sort carries 32-bit sample indices"));
+  NEED(factors); NEED(summary); NEED(result); NEED_AS(c, "ctx");
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   const int F = spec->n_factors, R = spec->n_rows, V = F + R;
@@ -501,41 +512,36 @@ int erpl_mc_correlation(erpl_ctx* c, const double* factors, const double* summar
   ErplCorrArgs a;
   memset(&a, 0, sizeof(a));
   a.mask = mask; a.n = n; a.n_vars = V;
-  // the buffer: [keys 2n u64][ranks V n doubles unless the caller keeps them][idx 2n u32][scratch of the sort][pop n bytes]
   size_t temp_bytes = 0;
-  if (ranks) {
+  if (ranks)
     LAUNCH_TRY(erpl_launch_corr_ranks(a, nullptr, nullptr, nullptr, nullptr, nullptr, &temp_bytes, stream), "radix sort sizing failed");
-    temp_bytes = (std::max(temp_bytes, (size_t)256) + 255) & ~(size_t)255;
-  }
+  const ErplCorrLayout at = erpl_corr_layout(n, V, ranks, ranks_out != nullptr, temp_bytes);
+  temp_bytes = at.temp_bytes;
   const size_t un = (size_t)n;
-  const size_t off_ranks = ranks ? 16 * un : 0;
-  const size_t off_idx = off_ranks + (ranks && !ranks_out ? 8 * un * (size_t)V : 0);
-  const size_t off_temp = (off_idx + (ranks ? 8 * un : 0) + 255) & ~(size_t)255;
-  const size_t off_pop = off_temp + temp_bytes;
-  const size_t need = off_pop + un;
-  ERPL_TRY(erpl_first_use(c->corr_work, c->corr_host));
-  ERPL_TRY(erpl_grow(c->corr_buf, c->corr_cap, need));
-  a.work = c->corr_work;
-  a.pop = (uint8_t*)(c->corr_buf + off_pop);
+  ERPL_TRY(c->corr.first_use());
+  ERPL_TRY(c->corr.grow(at.need));
+  char* buf = c->corr.buf;
+  a.work = c->corr.work;
+  a.pop = (uint8_t*)(buf + at.pop);
   for (int f = 0; f < F; ++f) a.var[f] = factors + (size_t)f * un;
   for (int j = 0; j < R; ++j) a.var[F + j] = summary + (size_t)spec->rows[j] * un;
 
   KERNEL_TRY(erpl_launch_corr_population(a, stream));
   KERNEL_TRY(erpl_launch_corr_gram(a, 0, stream));
   if (ranks) {
-    double* rk = ranks_out ? ranks_out : (double*)(c->corr_buf + off_ranks);
+    double* rk = ranks_out ? ranks_out : (double*)(buf + at.ranks);
     for (int v = 0; v < V; ++v)
-      LAUNCH_TRY(erpl_launch_corr_ranks(a, a.var[v], rk + (size_t)v * un, (unsigned long long*)c->corr_buf,
-                                        (uint32_t*)(c->corr_buf + off_idx), c->corr_buf + off_temp, &temp_bytes, stream),
+      LAUNCH_TRY(erpl_launch_corr_ranks(a, a.var[v], rk + (size_t)v * un, (unsigned long long*)(buf + at.keys),
+                                        (uint32_t*)(buf + at.idx), buf + at.temp, &temp_bytes, stream),
                  "rank pass failed");
     ErplCorrArgs b = a;
     for (int v = 0; v < V; ++v) b.var[v] = rk + (size_t)v * un;
     KERNEL_TRY(erpl_launch_corr_gram(b, 1, stream));
   }
-  HIP_TRY(hipMemcpyAsync(c->corr_host, &c->corr_work->out, sizeof(ErplCorrOut), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(c->corr.host, &c->corr.work->out, sizeof(ErplCorrOut), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
 
-  const ErplCorrOut& h = *c->corr_host;
+  const ErplCorrOut& h = *c->corr.host;
   const double nan = NAN;
   memset(result, 0, sizeof(*result));
   result->n = n;
@@ -586,16 +592,10 @@ int erpl_mc_correlation(erpl_ctx* c, const double* factors, const double* summar
 }  // extern "C"
 
 // ------------------------------------------------- erpl_mc_bootstrap
-namespace {
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-}  // namespace
-
 extern "C" {
 
 int erpl_mc_bootstrap_defaults(erpl_boot_spec* spec) {
-  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  NEED(spec);
   memset(spec, 0, sizeof(*spec));
   spec->n_rows = 3;
   spec->rows[0] = ERPL_SUM_APOGEE_ALT; spec->rows[1] = ERPL_SUM_RANGE; spec->rows[2] = ERPL_SUM_FLIGHT_TIME;
@@ -609,7 +609,7 @@ int erpl_mc_bootstrap_defaults(erpl_boot_spec* spec) {
 }
 
 int erpl_mc_bootstrap_indices(uint64_t seed, int64_t replicate, int64_t m, int64_t first, int64_t count, int64_t* out) {
-  if (!out) return erpl_fail(ERPL_ERR_INVALID, "out is NULL");
+  NEED(out);
   if (m <= 0 || m >= (1ll << 31)) return erpl_fail(ERPL_ERR_INVALID, "m = %lld outside 1..2^31 - 1", (long long)m);
   if (replicate < 0 || replicate > 0xffffffffll)
     return erpl_fail(ERPL_ERR_INVALID, "replicate = %lld outside 0..2^32 - 1", (long long)replicate);
@@ -634,78 +634,53 @@ int erpl_mc_bootstrap_indices(uint64_t seed, int64_t replicate, int64_t m, int64
 
 int erpl_mc_bootstrap(erpl_ctx* c, const double* summary, const double* extra, const uint8_t* mask, int64_t n,
                       const erpl_boot_spec* spec, erpl_bootstrap* result, double* replicates_out, void* stream) {
-  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
-  if (!summary) return erpl_fail(ERPL_ERR_INVALID, "summary is NULL");
-  if (!result) return erpl_fail(ERPL_ERR_INVALID, "result is NULL");
-  if (n <= 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
-  if (n >= (1ll << 31))
-    return erpl_fail(ERPL_ERR_INVALID, "n = %lld: the draws and the sort carry 31-bit sample indices", (long long)n);
-  if (spec->n_rows < 1 || spec->n_rows > ERPL_BOOT_MAX_ROWS)
-    return erpl_fail(ERPL_ERR_INVALID, "spec->n_rows = %d outside 1..%d", spec->n_rows, ERPL_BOOT_MAX_ROWS);
-  if (spec->n_q < 0 || spec->n_q > ERPL_ANALYSIS_MAX_Q)
-    return erpl_fail(ERPL_ERR_INVALID, "spec->n_q = %d outside 0..%d", spec->n_q, ERPL_ANALYSIS_MAX_Q);
-  if (spec->replicates < 1 || spec->replicates > ERPL_BOOT_MAX_REPLICATES)
-    return erpl_fail(ERPL_ERR_INVALID, "spec->replicates = %d outside 1..%d", spec->replicates, ERPL_BOOT_MAX_REPLICATES);
-  for (int j = 0; j < spec->n_rows; ++j) {
-    if (spec->rows[j] < 0 || spec->rows[j] > ERPL_BOOT_ROW_EXTRA)
-      return erpl_fail(ERPL_ERR_INVALID, "spec->rows[%d] = %d outside 0..%d", j, spec->rows[j], ERPL_BOOT_ROW_EXTRA);
-    for (int k = 0; k < j; ++k)
-      if (spec->rows[k] == spec->rows[j]) return erpl_fail(ERPL_ERR_INVALID, "spec->rows[%d] = %d is listed twice", j, spec->rows[j]);
-  }
+  NEED(spec); NEED(summary); NEED(result);
+  ERPL_TRY(check_n(n, (1ll << 31) - 1, ": the draws and the sort carry 31-bit sample indices"));
+  ERPL_TRY(check_int(spec->n_rows, "n_rows", -1, 1, ERPL_BOOT_MAX_ROWS));   // the three counts before the contents of rows and q
+  ERPL_TRY(check_int(spec->n_q, "n_q", -1, 0, ERPL_ANALYSIS_MAX_Q));
+  ERPL_TRY(check_int(spec->replicates, "replicates", -1, 1, ERPL_BOOT_MAX_REPLICATES));
+  ERPL_TRY(check_row_list(spec->rows, spec->n_rows, 1, ERPL_BOOT_MAX_ROWS, ERPL_BOOT_ROW_EXTRA));
   for (int j = 0; j < spec->n_rows; ++j)
     if (spec->rows[j] == ERPL_BOOT_ROW_EXTRA && !extra)
       return erpl_fail(ERPL_ERR_INVALID, "extra is NULL but spec->rows[%d] = %d (ERPL_BOOT_ROW_EXTRA)", j, spec->rows[j]);
   ERPL_TRY(check_quantiles(spec->q, spec->n_q));
   if (!(spec->level > 0.0 && spec->level < 1.0)) return erpl_fail(ERPL_ERR_INVALID, "spec->level = %g outside (0, 1)", spec->level);
-  if (!c) return erpl_fail(ERPL_ERR_INVALID, "ctx is NULL");
+  NEED_AS(c, "ctx");
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   const int R = spec->n_rows, nq = spec->n_q, ns = 2 + nq, n_stats = R * ns, B = spec->replicates;
   const size_t un = (size_t)n, uB = (size_t)B;
 
-  // the buffer: [pop n bytes][src n u32][count][x, sorted R n doubles each][pos R n u32][keys 2n u64][idx 2n u32]
-  // [scratch of the select / the sort][zero bytes B][replicates n_stats B doubles unless the caller keeps them]
   size_t temp_bytes = 0;
   LAUNCH_TRY(erpl_boot_temp_bytes(n, &temp_bytes), "select / radix sort sizing failed");
-  temp_bytes = align256(std::max(temp_bytes, (size_t)256));
-  const size_t off_src = align256(un);
-  const size_t off_count = off_src + align256(4 * un);
-  const size_t off_x = off_count + 256;
-  const size_t off_sorted = off_x + (size_t)R * align256(8 * un);
-  const size_t off_pos = off_sorted + (size_t)R * align256(8 * un);
-  const size_t off_keys = off_pos + (size_t)R * align256(4 * un);
-  const size_t off_idx = off_keys + align256(16 * un);
-  const size_t off_temp = off_idx + align256(8 * un);
-  const size_t off_zero = off_temp + temp_bytes;
-  const size_t off_rep = off_zero + align256(uB);
-  const size_t need = off_rep + (replicates_out ? 0 : 8 * uB * (size_t)n_stats);
-  ERPL_TRY(erpl_first_use(c->corr_work, c->corr_host));   // the population pass and its counters
-  ERPL_TRY(erpl_first_use(c->ana_work, c->ana_host));     // the estimates and the summary over the replicates
-  if (!c->boot_host) HIP_TRY(hipHostMalloc((void**)&c->boot_host, sizeof(BootHost), hipHostMallocDefault));
-  ERPL_TRY(erpl_grow(c->boot_buf, c->boot_cap, need));
-  char* buf = c->boot_buf;
-  BootHost& h = *c->boot_host;
+  const ErplBootLayout at = erpl_boot_layout(n, R, n_stats, B, replicates_out != nullptr, temp_bytes);
+  ERPL_TRY(c->corr.first_use());   // the population pass and its counters
+  ERPL_TRY(c->ana.first_use());    // the estimates and the summary over the replicates
+  ERPL_TRY(c->boot.first_use());
+  ERPL_TRY(c->boot.grow(at.need));
+  char* buf = c->boot.buf;
+  BootHost& h = *c->boot.host;
 
   ErplBootPrep p;
   memset(&p, 0, sizeof(p));
   ErplCorrArgs pa;
   memset(&pa, 0, sizeof(pa));
-  pa.mask = mask; pa.n = n; pa.n_vars = R; pa.work = c->corr_work; pa.pop = (uint8_t*)buf;
+  pa.mask = mask; pa.n = n; pa.n_vars = R; pa.work = c->corr.work; pa.pop = (uint8_t*)(buf + at.pop);
   for (int j = 0; j < R; ++j) {
     p.var[j] = spec->rows[j] == ERPL_BOOT_ROW_EXTRA ? extra : summary + (size_t)spec->rows[j] * un;
     pa.var[j] = p.var[j];
-    p.x[j] = (double*)(buf + off_x + (size_t)j * align256(8 * un));
-    p.sorted[j] = (double*)(buf + off_sorted + (size_t)j * align256(8 * un));
-    p.pos[j] = (uint32_t*)(buf + off_pos + (size_t)j * align256(4 * un));
+    p.x[j] = (double*)(buf + at.x[j]);
+    p.sorted[j] = (double*)(buf + at.sorted[j]);
+    p.pos[j] = (uint32_t*)(buf + at.pos[j]);
   }
-  p.pop = pa.pop; p.src = (uint32_t*)(buf + off_src); p.count = (unsigned long long*)(buf + off_count);
-  p.keys = (unsigned long long*)(buf + off_keys); p.idx = (uint32_t*)(buf + off_idx);
-  p.temp = buf + off_temp; p.temp_bytes = temp_bytes; p.n = n; p.n_rows = R;
-  uint8_t* zero = (uint8_t*)(buf + off_zero);
-  double* rep = replicates_out ? replicates_out : (double*)(buf + off_rep);
+  p.pop = pa.pop; p.src = (uint32_t*)(buf + at.src); p.count = (unsigned long long*)(buf + at.count);
+  p.keys = (unsigned long long*)(buf + at.keys); p.idx = (uint32_t*)(buf + at.idx);
+  p.temp = buf + at.temp; p.temp_bytes = at.temp_bytes; p.n = n; p.n_rows = R;
+  uint8_t* zero = (uint8_t*)(buf + at.zero);
+  double* rep = replicates_out ? replicates_out : (double*)(buf + at.rep);
 
   KERNEL_TRY(erpl_launch_corr_population(pa, stream));
-  HIP_TRY(hipMemcpyAsync(h.counter, &c->corr_work->out.counter[0], sizeof(h.counter), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h.counter, &c->corr.work->out.counter[0], sizeof(h.counter), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   const int64_t m = (int64_t)h.counter[0];
   memset(result, 0, sizeof(*result));
@@ -727,24 +702,14 @@ int erpl_mc_bootstrap(erpl_ctx* c, const double* summary, const double* extra, c
 
   // the estimates, by the passes of erpl_mc_analyze over the n samples with the population bytes as the mask: the summary
   // rows in one launch, `extra` as a one-row summary in a second
-  ErplAnaArgs e;
-  memset(&e, 0, sizeof(e));
-  e.summary = summary; e.why = pa.pop; e.work = c->ana_work; e.n = n; e.n_q = nq;
-  for (int k = 0; k < nq; ++k) e.q[k] = spec->q[k];
-  int est_of[ERPL_BOOT_MAX_ROWS], has_extra = 0;   // row j of the spec: est[0].row[est_of[j]], or est[1].row[0] (-1)
+  int32_t est_rows[ERPL_BOOT_MAX_ROWS];
+  int est_of[ERPL_BOOT_MAX_ROWS], n_est = 0, has_extra = 0;   // row j of the spec: est[0].row[est_of[j]], or est[1].row[0] (-1)
   for (int j = 0; j < R; ++j) {
     if (spec->rows[j] == ERPL_BOOT_ROW_EXTRA) { est_of[j] = -1; has_extra = 1; }
-    else { est_of[j] = e.n_rows; e.rows[e.n_rows++] = spec->rows[j]; }
+    else { est_of[j] = n_est; est_rows[n_est++] = spec->rows[j]; }
   }
-  if (e.n_rows > 0) {
-    KERNEL_TRY(erpl_launch_row_stats(e, stream));
-    HIP_TRY(hipMemcpyAsync(&h.est[0], &c->ana_work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, st));
-  }
-  if (has_extra) {
-    e.summary = extra; e.n_rows = 1; e.rows[0] = 0;
-    KERNEL_TRY(erpl_launch_row_stats(e, stream));
-    HIP_TRY(hipMemcpyAsync(&h.est[1], &c->ana_work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, st));
-  }
+  if (n_est > 0) ERPL_TRY(describe_rows(c, summary, pa.pop, n, est_rows, n_est, spec->q, nq, &h.est[0], st));
+  if (has_extra) ERPL_TRY(describe_rows(c, extra, pa.pop, n, nullptr, 1, spec->q, nq, &h.est[1], st));
 
   // prepare, then the replicates
   p.m = m;
@@ -766,18 +731,11 @@ int erpl_mc_bootstrap(erpl_ctx* c, const double* summary, const double* extra, c
   KERNEL_TRY(erpl_launch_boot_replicates(a, stream));
 
   // the summary over the replicates: the [n_stats][B] matrix as rows of length B through the same passes, 16 at a time
-  const double tail = (1.0 - spec->level) / 2;
+  const double tail = (1.0 - spec->level) / 2, interval[2] = {tail, 1.0 - tail};
   HIP_TRY(hipMemsetAsync(zero, 0, uB, st));
-  ErplAnaArgs g;
-  memset(&g, 0, sizeof(g));
-  g.why = zero; g.work = c->ana_work; g.n = B; g.n_q = 2; g.q[0] = tail; g.q[1] = 1.0 - tail;
-  for (int first = 0, k = 0; first < n_stats; first += ERPL_ANALYSIS_MAX_ROWS, ++k) {
-    g.summary = rep + (size_t)first * uB;
-    g.n_rows = std::min(n_stats - first, (int)ERPL_ANALYSIS_MAX_ROWS);
-    for (int j = 0; j < g.n_rows; ++j) g.rows[j] = j;
-    KERNEL_TRY(erpl_launch_row_stats(g, stream));
-    HIP_TRY(hipMemcpyAsync(&h.sum[k], &c->ana_work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, st));
-  }
+  for (int first = 0, k = 0; first < n_stats; first += ERPL_ANALYSIS_MAX_ROWS, ++k)
+    ERPL_TRY(describe_rows(c, rep + (size_t)first * uB, zero, B, nullptr, std::min(n_stats - first, (int)ERPL_ANALYSIS_MAX_ROWS),
+                           interval, 2, &h.sum[k], st));
   HIP_TRY(hipStreamSynchronize(st));
 
   for (int j = 0; j < R; ++j) {
@@ -789,7 +747,7 @@ int erpl_mc_bootstrap(erpl_ctx* c, const double* summary, const double* extra, c
       o.estimate = k == 0 ? est.mean : k == 1 ? est.std : est.quantile[k - 2];
       const ErplAnaRow& row = h.sum[s / ERPL_ANALYSIS_MAX_ROWS].row[s % ERPL_ANALYSIS_MAX_ROWS];
       erpl_row_stats over;
-      finish_row_stats(row, g.q, 2, true, over);
+      finish_row_stats(row, interval, 2, true, over);
       o.finite = over.count;
       // the constant rule of erpl_mc_correlation: a statistic with min == max over its replicates has no spread, whatever
       // sum / count makes of that value
@@ -816,13 +774,9 @@ int check_density_range(double lo, double hi, const char* lo_name, const char* h
 }
 
 int check_density_spec(const erpl_density_spec* s) {
-  ERPL_TRY(check_row(s->row_x, "row_x", -1));
-  ERPL_TRY(check_row(s->row_y, "row_y", -1));
-  if (s->row_x == s->row_y) return erpl_fail(ERPL_ERR_INVALID, "spec->row_y = %d is listed twice (row_x)", s->row_y);
-  if (s->nodes_x < 2 || s->nodes_x > ERPL_DENSITY_MAX_NODES)
-    return erpl_fail(ERPL_ERR_INVALID, "spec->nodes_x = %d outside 2..%d", s->nodes_x, ERPL_DENSITY_MAX_NODES);
-  if (s->nodes_y < 2 || s->nodes_y > ERPL_DENSITY_MAX_NODES)
-    return erpl_fail(ERPL_ERR_INVALID, "spec->nodes_y = %d outside 2..%d", s->nodes_y, ERPL_DENSITY_MAX_NODES);
+  ERPL_TRY(check_row_pair(s->row_x, s->row_y));
+  ERPL_TRY(check_int(s->nodes_x, "nodes_x", -1, 2, ERPL_DENSITY_MAX_NODES));
+  ERPL_TRY(check_int(s->nodes_y, "nodes_y", -1, 2, ERPL_DENSITY_MAX_NODES));
   if (check_density_range(s->lo_x, s->hi_x, "lo_x", "hi_x") < 0) return ERPL_ERR_INVALID;
   if (check_density_range(s->lo_y, s->hi_y, "lo_y", "hi_y") < 0) return ERPL_ERR_INVALID;
   if (!(std::isfinite(s->pad) && s->pad >= 0.0)) return erpl_fail(ERPL_ERR_INVALID, "spec->pad = %g: finite and >= 0", s->pad);
@@ -837,13 +791,8 @@ int check_density_spec(const erpl_density_spec* s) {
       return erpl_fail(ERPL_ERR_INVALID, "spec->h_xx = %g, spec->h_xy = %g, spec->h_yy = %g: not a finite positive definite matrix",
                        s->h_xx, s->h_xy, s->h_yy);
   }
-  if (s->n_levels < 0 || s->n_levels > ERPL_DENSITY_MAX_LEVELS)
-    return erpl_fail(ERPL_ERR_INVALID, "spec->n_levels = %d outside 0..%d", s->n_levels, ERPL_DENSITY_MAX_LEVELS);
-  for (int k = 0; k < s->n_levels; ++k)
-    if (!(s->level[k] > 0.0 && s->level[k] < 1.0))
-      return erpl_fail(ERPL_ERR_INVALID, "spec->level[%d] = %g outside (0, 1)", k, s->level[k]);
-  if (s->n_zones < 0 || s->n_zones > ERPL_DENSITY_MAX_ZONES)
-    return erpl_fail(ERPL_ERR_INVALID, "spec->n_zones = %d outside 0..%d", s->n_zones, ERPL_DENSITY_MAX_ZONES);
+  ERPL_TRY(check_levels(s->level, s->n_levels, ERPL_DENSITY_MAX_LEVELS));
+  ERPL_TRY(check_int(s->n_zones, "n_zones", -1, 0, ERPL_DENSITY_MAX_ZONES));
   if (s->n_zones > 0 && s->zone_first[0] != 0)
     return erpl_fail(ERPL_ERR_INVALID, "spec->zone_first[0] = %d: the first zone starts at vertex 0", s->zone_first[0]);
   for (int z = 0; z < s->n_zones; ++z) {
@@ -869,7 +818,7 @@ int check_density_spec(const erpl_density_spec* s) {
 extern "C" {
 
 int erpl_mc_impact_density_defaults(erpl_density_spec* spec) {
-  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  NEED(spec);
   memset(spec, 0, sizeof(*spec));
   spec->row_x = ERPL_SUM_IMPACT_X; spec->row_y = ERPL_SUM_IMPACT_Y;
   spec->nodes_x = spec->nodes_y = 128;
@@ -886,72 +835,51 @@ int erpl_mc_impact_density_defaults(erpl_density_spec* spec) {
 int erpl_mc_impact_density(erpl_ctx* c, const double* summary, const uint8_t* mask, int64_t n, const erpl_density_spec* spec,
                            double* grid_x, double* grid_y, double* density, erpl_density* result, double* sample_density,
                            void* stream) {
-  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "spec is NULL");
+  NEED(spec);
   ERPL_TRY(check_density_spec(spec));
-  if (n <= 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: need at least one sample", (long long)n);
-  if (n >= (1ll << 31)) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: the select carries 31-bit sample indices", (long long)n);
-  if (!summary) return erpl_fail(ERPL_ERR_INVALID, "summary is NULL");
-  if (!grid_x) return erpl_fail(ERPL_ERR_INVALID, "grid_x is NULL");
-  if (!grid_y) return erpl_fail(ERPL_ERR_INVALID, "grid_y is NULL");
-  if (!density) return erpl_fail(ERPL_ERR_INVALID, "density is NULL");
-  if (!result) return erpl_fail(ERPL_ERR_INVALID, "result is NULL");
-  if (!c) return erpl_fail(ERPL_ERR_INVALID, "ctx is NULL");
+  ERPL_TRY(check_n(n, (1ll << 31) - 1, ": the select carries 31-bit sample indices"));
+  NEED(summary); NEED(grid_x); NEED(grid_y); NEED(density); NEED(result); NEED_AS(c, "ctx");
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   const int nx = spec->nodes_x, ny = spec->nodes_y;
-  const size_t un = (size_t)n, nodes = (size_t)nx * (size_t)ny;
+  const size_t nodes = (size_t)nx * (size_t)ny;
   const bool want_samples = spec->n_levels > 0 || sample_density;
 
-  // the buffer: [pop n bytes][src n u32][count][scratch of the select][points n (x, y), then (u, v)][nodes (u, v)][node densities]
-  // [the sample row unless the caller keeps it][partial sums: at most TARGET_BLOCKS * TILE + queries, erpl_dens_slices]
   size_t temp_bytes = 0;
   LAUNCH_TRY(erpl_boot_temp_bytes(n, &temp_bytes), "select sizing failed");
-  temp_bytes = align256(std::max(temp_bytes, (size_t)256));
-  const size_t off_src = align256(un);
-  const size_t off_count = off_src + align256(4 * un);
-  const size_t off_temp = off_count + 256;
-  const size_t off_pts = off_temp + temp_bytes;
-  const size_t off_nodes = off_pts + align256(16 * un);
-  const size_t off_dens = off_nodes + align256(16 * nodes);
-  const size_t off_row = off_dens + align256(8 * nodes);
-  const size_t off_part = off_row + (want_samples && !sample_density ? align256(8 * un) : 0);
-  const size_t need = off_part + 8 * ((size_t)ERPL_DENS_TARGET_BLOCKS * ERPL_DENS_TILE + std::max(nodes, want_samples ? un : 0));
-  ERPL_TRY(erpl_first_use(c->dens_work, c->dens_host));
-  if (want_samples) ERPL_TRY(erpl_first_use(c->ana_work, c->ana_host));   // the selection's block
-  ERPL_TRY(erpl_grow(c->dens_buf, c->dens_cap, need));
-  char* buf = c->dens_buf;
-  DensHost& h = *c->dens_host;
-  uint32_t* src = (uint32_t*)(buf + off_src);
-  double* pts = (double*)(buf + off_pts);
-  double* nodes_uv = (double*)(buf + off_nodes);
-  double* dens = (double*)(buf + off_dens);
-  double* row = sample_density ? sample_density : (double*)(buf + off_row);
-  double* partial = (double*)(buf + off_part);
+  const ErplDensLayout at = erpl_dens_layout(n, (int64_t)nodes, want_samples, sample_density != nullptr, temp_bytes);
+  ERPL_TRY(c->dens.first_use());
+  if (want_samples) ERPL_TRY(c->ana.first_use());   // the selection's block
+  ERPL_TRY(c->dens.grow(at.need));
+  char* buf = c->dens.buf;
+  DensHost& h = *c->dens.host;
+  uint32_t* src = (uint32_t*)(buf + at.src);
+  double* pts = (double*)(buf + at.pts);
+  double* nodes_uv = (double*)(buf + at.nodes);
+  double* dens = (double*)(buf + at.dens);
+  double* row = sample_density ? sample_density : (double*)(buf + at.row);
+  double* partial = (double*)(buf + at.part);
 
   ErplDensArgs a;
   memset(&a, 0, sizeof(a));
-  a.summary = summary; a.mask = mask; a.work = c->dens_work; a.pop = (uint8_t*)buf; a.n = n;
+  a.summary = summary; a.mask = mask; a.work = c->dens.work; a.pop = (uint8_t*)(buf + at.pop); a.n = n;
   a.row_x = spec->row_x; a.row_y = spec->row_y; a.n_zones = spec->n_zones;
   ErplBootPrep p;   // the select of erpl_mc_bootstrap: pop -> src and the count, in sample order
   memset(&p, 0, sizeof(p));
-  p.pop = a.pop; p.src = src; p.count = (unsigned long long*)(buf + off_count); p.temp = buf + off_temp;
-  p.temp_bytes = temp_bytes; p.n = n;
+  p.pop = a.pop; p.src = src; p.count = (unsigned long long*)(buf + at.count); p.temp = buf + at.temp;
+  p.temp_bytes = at.temp_bytes; p.n = n;
   KERNEL_TRY(erpl_launch_dens_population(a, stream));
   LAUNCH_TRY(erpl_launch_boot_compact(p, stream), "select failed");
   KERNEL_TRY(erpl_launch_dens_moments(a, src, p.count, pts, stream));
-  HIP_TRY(hipMemcpyAsync(&h.mom, &c->dens_work->mom, sizeof(ErplDensMoments), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&h.mom, &c->dens.work->mom, sizeof(ErplDensMoments), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
 
   // what the host settles in double: S, H, whether the estimate is solid, the map, the ranges and the nodes
   const double nan = NAN;
   const int64_t m = (int64_t)h.mom.count;
-  const bool any = m > 0;
   memset(result, 0, sizeof(*result));
-  result->count = m;
-  result->mean_x = any ? h.mom.mean_x : nan; result->mean_y = any ? h.mom.mean_y : nan;
   const double dof = (double)(m - 1);   // 0 for m == 1: S is NaN there
-  result->cov_xx = any ? h.mom.sxx / dof : nan; result->cov_xy = any ? h.mom.sxy / dof : nan;
-  result->cov_yy = any ? h.mom.syy / dof : nan;
+  const bool any = finish_cloud(result, h.mom.count, h.mom.mean_x, h.mom.mean_y, h.mom.sxx / dof, h.mom.sxy / dof, h.mom.syy / dof);
   double hxx = spec->h_xx, hxy = spec->h_xy, hyy = spec->h_yy;
   if (spec->bandwidth == ERPL_BW_SCOTT) {
     const double factor = spec->bw_scale * pow((double)m, -1.0 / 6.0), f2 = factor * factor;
@@ -982,8 +910,8 @@ int erpl_mc_impact_density(erpl_ctx* c, const double* summary, const uint8_t* ma
   memcpy(h.in.zone_x, spec->zone_x, (size_t)n_vert * sizeof(double));
   memcpy(h.in.zone_y, spec->zone_y, (size_t)n_vert * sizeof(double));
   for (int z = 0; z <= spec->n_zones; ++z) h.in.zone_first[z] = spec->zone_first[z];
-  HIP_TRY(hipMemcpyAsync(&c->dens_work->in, &h.in, sizeof(ErplDensIn), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(&c->dens_work->out, 0, sizeof(ErplDensOut), st));
+  HIP_TRY(hipMemcpyAsync(&c->dens.work->in, &h.in, sizeof(ErplDensIn), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(&c->dens.work->out, 0, sizeof(ErplDensOut), st));
   if (spec->n_zones > 0) KERNEL_TRY(erpl_launch_dens_zones(a, stream));
 
   if (solid) {
@@ -993,24 +921,21 @@ int erpl_mc_impact_density(erpl_ctx* c, const double* summary, const uint8_t* ma
     map.mean_x = h.mom.mean_x; map.mean_y = h.mom.mean_y;
     map.w11 = 1.0 / c11; map.w22 = 1.0 / c22; map.w21 = -c21 * map.w11 * map.w22;
     KERNEL_TRY(erpl_launch_dens_whiten(pts, m, map, stream));
-    KERNEL_TRY(erpl_launch_dens_nodes(c->dens_work, nx, ny, map, nodes_uv, stream));
+    KERNEL_TRY(erpl_launch_dens_nodes(c->dens.work, nx, ny, map, nodes_uv, stream));
     KERNEL_TRY(erpl_launch_dens_pairs(nodes_uv, (int64_t)nodes, pts, m, norm, partial, dens, nullptr, stream));
-    KERNEL_TRY(erpl_launch_dens_peak(c->dens_work, dens, (int64_t)nodes, stream));
+    KERNEL_TRY(erpl_launch_dens_peak(c->dens.work, dens, (int64_t)nodes, stream));
   }
+  double q[ERPL_ANALYSIS_MAX_Q] = {0};   // the density below which 1 - level of the samples lie bounds the region of that content
+  for (int k = 0; k < spec->n_levels; ++k) q[k] = 1.0 - spec->level[k];
   if (want_samples) {
     KERNEL_TRY(erpl_launch_dens_fill_nan(row, n, stream));
     if (solid) {
       KERNEL_TRY(erpl_launch_dens_pairs(pts, m, pts, m, norm, partial, row, src, stream));
       // the f_j as a one-row summary through the moment passes and the selection of erpl_mc_analyze
-      ErplAnaArgs r;
-      memset(&r, 0, sizeof(r));
-      r.summary = row; r.why = a.pop; r.work = c->ana_work; r.n = n; r.n_rows = 1; r.rows[0] = 0; r.n_q = spec->n_levels;
-      for (int k = 0; k < spec->n_levels; ++k) r.q[k] = 1.0 - spec->level[k];
-      KERNEL_TRY(erpl_launch_row_stats(r, stream));
-      HIP_TRY(hipMemcpyAsync(c->ana_host, &c->ana_work->res, sizeof(ErplAnaResult), hipMemcpyDeviceToHost, st));
+      ERPL_TRY(describe_rows(c, row, a.pop, n, nullptr, 1, q, spec->n_levels, c->ana.host, st));
     }
   }
-  HIP_TRY(hipMemcpyAsync(&h.out, &c->dens_work->out, sizeof(ErplDensOut), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&h.out, &c->dens.work->out, sizeof(ErplDensOut), hipMemcpyDeviceToHost, st));
   if (solid) HIP_TRY(hipMemcpyAsync(density, dens, 8 * nodes, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
 
@@ -1023,10 +948,8 @@ int erpl_mc_impact_density(erpl_ctx* c, const double* summary, const uint8_t* ma
   result->grid_mass = solid ? h.out.sum * cell : nan;
   result->peak_ix = solid ? (int32_t)((int64_t)h.out.peak_at / ny) : -1;
   result->peak_iy = solid ? (int32_t)((int64_t)h.out.peak_at % ny) : -1;
-  double q[ERPL_ANALYSIS_MAX_Q] = {0};
-  for (int k = 0; k < spec->n_levels; ++k) q[k] = 1.0 - spec->level[k];
   const bool described = solid && want_samples;
-  finish_row_stats(described ? c->ana_host->row[0] : ErplAnaRow(), q, spec->n_levels, described, result->sample_density);
+  finish_row_stats(described ? c->ana.host->row[0] : ErplAnaRow(), q, spec->n_levels, described, result->sample_density);
   return ERPL_OK;
 }
 

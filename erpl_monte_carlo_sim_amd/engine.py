@@ -138,6 +138,21 @@ class TrajectoryEngine:
         spec.n_rows = len(rows)
         spec.rows[:len(rows)] = rows
 
+    @staticmethod
+    def _fractions(values, most, what):
+        """`values` (levels, quantiles) as a list of floats, `most` of them at the most."""
+        values = [float(v) for v in values]
+        if len(values) > most:
+            raise ValueError(f"at most {most} {what}")
+        return values
+
+    @staticmethod
+    def _row_stats_dict(r, q):
+        """An erpl_row_stats with the fractions `q` its order statistics belong to, as a plain dict."""
+        nq = len(q)
+        return {"count": int(r.count), "mean": r.mean, "std": r.std, "min": r.min, "max": r.max, "q": q,
+                "quantiles": list(r.quantile[:nq]), "order_lo": list(r.order_lo[:nq]), "order_hi": list(r.order_hi[:nq])}
+
     def close(self):
         if getattr(self, "_ctx", None) is not None and self._ctx.value:
             self.lib.erpl_mc_destroy(self._ctx)
@@ -305,9 +320,7 @@ class TrajectoryEngine:
         spec = self.analysis_defaults()
         self._set_rows(spec, rows, 0, _abi.ANALYSIS_MAX_ROWS)
         if quantiles is not None:
-            quantiles = [float(q) for q in quantiles]
-            if len(quantiles) > _abi.ANALYSIS_MAX_Q:
-                raise ValueError(f"at most {_abi.ANALYSIS_MAX_Q} quantiles")
+            quantiles = self._fractions(quantiles, _abi.ANALYSIS_MAX_Q, "quantiles")
             spec.n_q = len(quantiles)
             spec.q[:len(quantiles)] = quantiles
         for key, val in (bounds or {}).items():
@@ -395,11 +408,8 @@ class TrajectoryEngine:
         exact quantiles (with the default quantiles the first one is the CEP).  Returns a plain dict; miss=True adds
         'miss_distance', the float64 [n] device tensor of r (NaN where a sample is not counted)."""
         n, mask_p = self._summary_and_mask(summary, mask)
-        levels, quantiles = [float(p) for p in levels], [float(q) for q in quantiles]
-        if len(levels) > _abi.DISP_MAX_LEVELS:
-            raise ValueError(f"at most {_abi.DISP_MAX_LEVELS} levels")
-        if len(quantiles) > _abi.ANALYSIS_MAX_Q:
-            raise ValueError(f"at most {_abi.ANALYSIS_MAX_Q} quantiles")
+        levels = self._fractions(levels, _abi.DISP_MAX_LEVELS, "levels")
+        quantiles = self._fractions(quantiles, _abi.ANALYSIS_MAX_Q, "quantiles")
         spec = self._defaults(_abi.ErplDispersionSpec, "erpl_mc_dispersion_defaults")
         spec.row_x, spec.row_y = int(row_x), int(row_y)
         if centre is None:
@@ -415,7 +425,7 @@ class TrajectoryEngine:
         st = torch.cuda.current_stream(self.device)
         self._call("erpl_mc_dispersion", C.c_void_p(summary.data_ptr()), mask_p, n, C.byref(spec), C.byref(res),
                    C.c_void_p(r.data_ptr()) if miss else None, C.c_void_p(st.cuda_stream))
-        nl, nq, m = len(levels), len(quantiles), res.miss
+        nl = len(levels)
         out = {"count": int(res.count), "rows": (int(row_x), int(row_y)),
                "mean": [res.mean_x, res.mean_y],
                "covariance": [[res.cov_xx, res.cov_xy], [res.cov_xy, res.cov_yy]],
@@ -423,9 +433,7 @@ class TrajectoryEngine:
                "centre": [res.centre_x, res.centre_y],
                "ellipses": [{"level": levels[k], "k2": res.k2[k], "semi_major": res.semi_major[k],
                              "semi_minor": res.semi_minor[k], "inside": int(res.inside[k])} for k in range(nl)],
-               "miss": {"count": int(m.count), "mean": m.mean, "std": m.std, "min": m.min, "max": m.max,
-                        "q": quantiles, "quantiles": list(m.quantile[:nq]), "order_lo": list(m.order_lo[:nq]),
-                        "order_hi": list(m.order_hi[:nq])}}
+               "miss": self._row_stats_dict(res.miss, quantiles)}
         out["cep"] = out["miss"]["quantiles"][quantiles.index(0.5)] if 0.5 in quantiles else None
         if miss:
             out["miss_distance"] = r
@@ -446,9 +454,7 @@ class TrajectoryEngine:
         tensor of the density at every sample (NaN where it is not counted); with no levels and without it the pass over
         all pairs of samples is skipped."""
         n, mask_p = self._summary_and_mask(summary, mask)
-        levels = [float(p) for p in levels]
-        if len(levels) > _abi.DENSITY_MAX_LEVELS:
-            raise ValueError(f"at most {_abi.DENSITY_MAX_LEVELS} levels")
+        levels = self._fractions(levels, _abi.DENSITY_MAX_LEVELS, "levels")
         zones = [np.asarray(z, dtype=np.float64).reshape(-1, 2) for z in (zones or [])]
         if len(zones) > _abi.DENSITY_MAX_ZONES:
             raise ValueError(f"at most {_abi.DENSITY_MAX_ZONES} zones")
@@ -495,9 +501,7 @@ class TrajectoryEngine:
                "grid_x": gx[:nx].copy(), "grid_y": gy[:ny].copy(), "density": dens.reshape(nx, ny),
                "peak": res.peak, "peak_node": (int(res.peak_ix), int(res.peak_iy)), "grid_mass": res.grid_mass,
                "levels": levels, "thresholds": list(sd.quantile[:nl]),
-               "sample_density_stats": {"count": int(sd.count), "mean": sd.mean, "std": sd.std, "min": sd.min, "max": sd.max,
-                                        "q": [1.0 - p for p in levels], "quantiles": list(sd.quantile[:nl]),
-                                        "order_lo": list(sd.order_lo[:nl]), "order_hi": list(sd.order_hi[:nl])},
+               "sample_density_stats": self._row_stats_dict(sd, [1.0 - p for p in levels]),
                "zones": [{"vertices": poly, "inside": int(res.zone_inside[z])} for z, poly in enumerate(zones)]}
         if sample_density:
             out["sample_density"] = row
@@ -564,9 +568,7 @@ class TrajectoryEngine:
         want_replicates=True adds 'replicate_values': the float64 [n_stats, replicates] device tensor, statistic
         j * (2 + len(quantiles)) + k of row j (k = 0 mean, 1 std, 2 + i quantile i)."""
         n, mask_p = self._summary_and_mask(summary, mask)
-        quantiles = [float(q) for q in quantiles]
-        if len(quantiles) > _abi.ANALYSIS_MAX_Q:
-            raise ValueError(f"at most {_abi.ANALYSIS_MAX_Q} quantiles")
+        quantiles = self._fractions(quantiles, _abi.ANALYSIS_MAX_Q, "quantiles")
         if extra is not None and not (extra.is_cuda and extra.device == self.device and extra.dtype == torch.float64
                                       and tuple(extra.shape) == (n,) and extra.is_contiguous()):
             raise ValueError(f"extra must be a contiguous float64 [n] tensor on {self.device}")

@@ -1,12 +1,16 @@
 """Shared helpers: golden-fixture loading and batch construction (no reference access)."""
+import ctypes as C
 import json
 import os
+import subprocess
 
 import numpy as np
 
 from erpl_monte_carlo_sim_amd import _abi, flatten, models
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DUMMY = C.c_void_p(0x1000)      # stands in for a device pointer that an argument check never dereferences
 
 EXAMPLE_IC = {
     "position": [0.0, 0.0, 10.0],
@@ -24,6 +28,37 @@ UNCERTAINTY = {
     "mass_uncertainty": 0.02, "thrust_uncertainty": 0.03, "wind_speed_range": [0.0, 5.0],
     "wind_direction_range": [0.0, 2 * np.pi], "atmospheric_density_uncertainty": 0.05,
 }
+
+
+def load_lib():
+    """The package's own library for the tests of the C boundary that need no GPU, built first if it is not there."""
+    if not os.path.exists(_abi.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    return _abi.load_library()
+
+
+def check_struct_layouts(tmp_path, structs, macros):
+    """sizeof and the offset of EVERY field of the ctypes mirrors `structs` ((C name, _abi name), ..) and the values of
+    `macros` ((C macro, value in _abi), ..) == what gcc sees in include/erpl_mc.h."""
+    lines, want = [], []
+    for cname, pyname in structs:
+        cls = getattr(_abi, pyname)
+        lines.append(f'printf("%zu\\n", sizeof({cname}));')
+        want.append(C.sizeof(cls))
+        for field, _ in cls._fields_:
+            lines.append(f'printf("%zu\\n", offsetof({cname}, {field}));')
+            want.append(getattr(cls, field).offset)
+    for macro, val in tuple(macros) + (("ERPL_MC_ABI_VERSION", _abi.ABI_VERSION),):
+        lines.append(f'printf("%d\\n", (int){macro});')
+        want.append(val)
+    src = tmp_path / "sz.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "erpl_mc.h"\nint main(){' + "".join(lines) + "return 0;}\n")
+    exe = tmp_path / "sz"
+    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
+    assert [int(x) for x in out] == want
+    assert _abi.ABI_VERSION == 4
 
 
 def load_json(name):

@@ -1,6 +1,7 @@
-"""The inputs and the calls behind tests/golden/stats_bits.json: what test_gpu_stats_bits.py compares and what
-tools/record_stats_bits.py records.  Only the public TrajectoryEngine calls analyze, histogram, histogram2d, dispersion
-and correlation are used, so the same code runs on any build of the library.
+"""The inputs and the calls behind tests/golden/stats_bits.json and stats_host_bits.json: what test_gpu_stats_bits.py
+compares and what tools/record_stats_bits.py records.  Only the public TrajectoryEngine calls analyze, histogram,
+histogram2d, dispersion and correlation (collect_size) and bootstrap and impact_density (collect_host_size) are used, so
+the same code runs on any build of the library.
 
 Every double that a fixed-order reduction produces is kept as the hex pattern of its bits, every integer as it is, bulky
 outputs (bin counts, edges, V x V matrices, ranks, the miss distance, the reason bytes) as SHA-256 of their bytes."""
@@ -142,3 +143,72 @@ def collect_size(engine, n):
 
 def collect(engine):
     return {str(n): collect_size(engine, n) for n in SIZES}
+
+
+# ---- stats_host_bits.json: erpl_mc_bootstrap and erpl_mc_impact_density, whose host halves carve one buffer into pieces
+HOST_SIZES = (1, 65, 1025, 262144 + 300)    # the last: density alone, several source slices and the largest partial sums
+BOOT_SIZES = HOST_SIZES[:3]
+BOOT_ROWS = [_abi.SUM_APOGEE_ALT, _abi.SUM_RANGE, _abi.SUM_FLIGHT_TIME, _abi.BOOT_ROW_EXTRA]
+DENS_NODES = (33, 17)
+TRIANGLE = [(-1.0e3, -1.0e3), (2.0e3, 0.0), (0.0, 3.0e3)]
+# a 32-gon about (10, -20), vertices rounded to whole metres so that no libm decides a bit of them
+GON32 = [(10.0 + float(round(5.0e4 * np.cos(2 * np.pi * k / 32))), -20.0 + float(round(5.0e4 * np.sin(2 * np.pi * k / 32))))
+         for k in range(32)]
+
+
+def bootstrap_case(engine, summ, mask, want_replicates=True, **kw):
+    out = engine.bootstrap(summ, mask, replicates=64, seed=7, want_replicates=want_replicates, **kw)
+    rec = {k: int(out[k]) for k in ("n", "count", "n_masked", "n_non_finite", "replicates")}
+
+    def stat(s):
+        return {"finite": s["finite"], "bits": bits([s[k] for k in ("estimate", "rep_mean", "se", "lo", "hi")])}
+
+    rec["stats"] = [[stat(r["mean"]), stat(r["std"])] + [stat(s) for s in r["quantiles"]] for r in out["stats"]]
+    if want_replicates:
+        rec["replicate_values"] = digest(out["replicate_values"])
+    return rec
+
+
+def density_case(engine, summ, mask, sample_density=True, **kw):
+    d = engine.impact_density(summ, mask, nodes=DENS_NODES, zones=[TRIANGLE, GON32], sample_density=sample_density, **kw)
+    sd = d["sample_density_stats"]
+    rec = {"count": d["count"], "solid": d["solid"], "peak_node": list(d["peak_node"]),
+           "inside": [z["inside"] for z in d["zones"]],
+           "moments": bits(d["mean"] + d["covariance"][0] + d["covariance"][1]),
+           "bandwidth": bits(d["bandwidth_matrix"][0] + d["bandwidth_matrix"][1] + [d["det"], d["norm"]]),
+           "ranges": bits(d["ranges"]), "peak": bits([d["peak"], d["grid_mass"]]), "thresholds": bits(d["thresholds"]),
+           "grid": digest(np.concatenate([d["grid_x"], d["grid_y"]])), "density": digest(d["density"]),
+           "sample_density_stats": {"count": sd["count"], **{k: bits(sd[k]) for k in ("mean", "std", "min", "max", "quantiles",
+                                                                                       "order_lo", "order_hi")}}}
+    if sample_density:
+        rec["sample_density"] = digest(d["sample_density"])
+    return rec
+
+
+def collect_host_size(engine, n):
+    """Every bootstrap and impact_density call at size n -> a JSON-ready dict."""
+    summ_h, fac_h, mask_h, _ = make_inputs(n)
+    summ, fac, mask = (torch.from_numpy(a).to(engine.device) for a in (summ_h, fac_h, mask_h))
+    rec = {}
+    if n in BOOT_SIZES:
+        extra = fac[0].contiguous()          # holds a NaN from n = 65 on
+        rec["bootstrap"] = bootstrap_case(engine, summ, mask, rows=BOOT_ROWS, extra=extra)   # 28 statistics: groups of 16 + 12
+        if n == 1025:                        # no summary rows, no quantiles, the replicates in the library's own buffer
+            rec["bootstrap_extra_alone"] = bootstrap_case(engine, summ, mask, want_replicates=False, rows=[_abi.BOOT_ROW_EXTRA],
+                                                          extra=extra, quantiles=())
+        if n == 65:                          # the empty population: every replicate NaN
+            rec["bootstrap_empty"] = bootstrap_case(engine, summ, torch.ones_like(mask), rows=BOOT_ROWS, extra=extra)
+    rec["density"] = density_case(engine, summ, mask)
+    if n == 1025:
+        rec["density_no_samples"] = density_case(engine, summ, mask, sample_density=False, levels=())   # no all-pairs pass
+        rec["density_explicit"] = density_case(engine, summ, mask, ranges=((-5.0e3, 5.0e3), (-4.0e3, 6.0e3)),
+                                               bandwidth=[[4.0e4, 1.0e4], [1.0e4, 9.0e4]])
+    if n == 65:                              # row_y constant: not solid, the map is NaN, no error
+        flat = summ.clone()
+        flat[_abi.SUM_IMPACT_Y] = 3.0
+        rec["density_flat"] = density_case(engine, flat, mask)
+    return rec
+
+
+def collect_host(engine):
+    return {str(n): collect_host_size(engine, n) for n in HOST_SIZES}

@@ -2,21 +2,20 @@
 the default bounds, and the argument checks (which come before any device work and look at the context last)."""
 import ctypes as C
 import os
-import subprocess
 
 import pytest
 
+import helpers as H
 from erpl_monte_carlo_sim_amd import _abi, analysis
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+STRUCTS = (("erpl_analysis_spec", "ErplAnalysisSpec"), ("erpl_row_stats", "ErplRowStats"), ("erpl_analysis", "ErplAnalysis"))
+MACROS = (("ERPL_ANALYSIS_MAX_ROWS", _abi.ANALYSIS_MAX_ROWS), ("ERPL_ANALYSIS_MAX_Q", _abi.ANALYSIS_MAX_Q))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_abi.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _abi.load_library()
+    return H.load_lib()
 
 
 def defaults(lib):
@@ -26,24 +25,8 @@ def defaults(lib):
 
 
 def test_analysis_struct_layout_matches_c_compiler(tmp_path):
-    """sizeof / offsetof of the three new ctypes mirrors == what gcc sees in include/erpl_mc.h."""
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "erpl_mc.h"\n'
-                   'int main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %d %d\\n",'
-                   'sizeof(erpl_analysis_spec), sizeof(erpl_row_stats), sizeof(erpl_analysis),'
-                   'offsetof(erpl_analysis_spec, n_rows), offsetof(erpl_analysis_spec, rows), offsetof(erpl_analysis_spec, n_q),'
-                   'offsetof(erpl_analysis_spec, q), offsetof(erpl_row_stats, quantile), offsetof(erpl_row_stats, order_hi),'
-                   'offsetof(erpl_analysis, termination_counts), offsetof(erpl_analysis, n_incomplete), offsetof(erpl_analysis, row),'
-                   'ERPL_ANALYSIS_MAX_ROWS, ERPL_ANALYSIS_MAX_Q);return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
-    got = [C.sizeof(_abi.ErplAnalysisSpec), C.sizeof(_abi.ErplRowStats), C.sizeof(_abi.ErplAnalysis),
-           _abi.ErplAnalysisSpec.n_rows.offset, _abi.ErplAnalysisSpec.rows.offset, _abi.ErplAnalysisSpec.n_q.offset,
-           _abi.ErplAnalysisSpec.q.offset, _abi.ErplRowStats.quantile.offset, _abi.ErplRowStats.order_hi.offset,
-           _abi.ErplAnalysis.termination_counts.offset, _abi.ErplAnalysis.n_incomplete.offset, _abi.ErplAnalysis.row.offset,
-           _abi.ANALYSIS_MAX_ROWS, _abi.ANALYSIS_MAX_Q]
-    assert [int(x) for x in out] == got
+    """sizeof and the offset of every field of the three ctypes mirrors == what gcc sees in include/erpl_mc.h."""
+    H.check_struct_layouts(tmp_path, STRUCTS, MACROS)
 
 
 def test_reason_bits_match_the_header():
@@ -73,7 +56,7 @@ def test_defaults_are_the_pinned_host_bounds(lib):
 def test_argument_checks_come_before_any_device_work(lib):
     """spec, n and the pointers are checked before the context, so every refusal can be seen without a device: a
     non-NULL dummy that is never dereferenced stands in for the summary, and the context is NULL throughout."""
-    dummy = C.c_void_p(0x1000)
+    dummy = H.DUMMY
     res = _abi.ErplAnalysis()
 
     def call(spec, n=8, summary=dummy, result=res):

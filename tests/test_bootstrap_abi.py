@@ -4,27 +4,26 @@ come before any device work, in the order the header lists, and look at the cont
 pointer that is never dereferenced show them all) and the host copy of the draws against philox_ref."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import helpers as H
 from erpl_monte_carlo_sim_amd import _abi, analysis
 
 import philox_ref
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DUMMY = C.c_void_p(0x1000)
+DUMMY = H.DUMMY
 
 STRUCTS = (("erpl_boot_spec", "ErplBootSpec"), ("erpl_boot_stat", "ErplBootStat"), ("erpl_bootstrap", "ErplBootstrap"))
+MACROS = (("ERPL_BOOT_MAX_ROWS", _abi.BOOT_MAX_ROWS), ("ERPL_BOOT_ROW_EXTRA", _abi.BOOT_ROW_EXTRA),
+          ("ERPL_BOOT_MAX_REPLICATES", _abi.BOOT_MAX_REPLICATES), ("ERPL_BOOT_MAX_STATS", _abi.BOOT_MAX_STATS))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_abi.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _abi.load_library()
+    return H.load_lib()
 
 
 def test_philox_ref_reproduces_the_random123_known_answers():
@@ -45,25 +44,7 @@ def test_philox_ref_reproduces_the_random123_known_answers():
 
 def test_struct_layouts_match_the_c_compiler(tmp_path):
     """sizeof and the offset of EVERY field of the three ctypes mirrors == what gcc sees in include/erpl_mc.h."""
-    lines, want = [], []
-    for cname, pyname in STRUCTS:
-        cls = getattr(_abi, pyname)
-        lines.append(f'printf("%zu\\n", sizeof({cname}));')
-        want.append(C.sizeof(cls))
-        for field, _ in cls._fields_:
-            lines.append(f'printf("%zu\\n", offsetof({cname}, {field}));')
-            want.append(getattr(cls, field).offset)
-    for macro, val in (("ERPL_BOOT_MAX_ROWS", _abi.BOOT_MAX_ROWS), ("ERPL_BOOT_ROW_EXTRA", _abi.BOOT_ROW_EXTRA),
-                       ("ERPL_BOOT_MAX_REPLICATES", _abi.BOOT_MAX_REPLICATES), ("ERPL_BOOT_MAX_STATS", _abi.BOOT_MAX_STATS),
-                       ("ERPL_MC_ABI_VERSION", _abi.ABI_VERSION)):
-        lines.append(f'printf("%d\\n", (int){macro});')
-        want.append(val)
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "erpl_mc.h"\nint main(){' + "".join(lines) + "return 0;}\n")
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
-    assert [int(x) for x in out] == want
+    H.check_struct_layouts(tmp_path, STRUCTS, MACROS)
     assert (_abi.BOOT_MAX_ROWS, _abi.BOOT_ROW_EXTRA, _abi.BOOT_MAX_REPLICATES, _abi.BOOT_MAX_STATS) == (4, 16, 65536, 40)
     assert _abi.BOOT_ROW_EXTRA == _abi.SUMMARY_DIM and _abi.ABI_VERSION == 4
 

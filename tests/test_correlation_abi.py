@@ -3,47 +3,29 @@ gcc, the defaults, every argument check (they come before any device work and lo
 and a dummy pointer that is never dereferenced show them all), and the host helpers of analysis.drivers."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import helpers as H
 from erpl_monte_carlo_sim_amd import _abi, analysis
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DUMMY = C.c_void_p(0x1000)
+DUMMY = H.DUMMY
 
 STRUCTS = (("erpl_corr_spec", "ErplCorrSpec"), ("erpl_corr_result", "ErplCorrResult"))
+MACROS = (("ERPL_CORR_MAX_FACTORS", _abi.CORR_MAX_FACTORS), ("ERPL_CORR_MAX_ROWS", _abi.CORR_MAX_ROWS),
+          ("ERPL_CORR_MAX_VARS", _abi.CORR_MAX_VARS))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_abi.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _abi.load_library()
+    return H.load_lib()
 
 
 def test_struct_layouts_match_the_c_compiler(tmp_path):
     """sizeof and the offset of EVERY field of the two ctypes mirrors == what gcc sees in include/erpl_mc.h."""
-    lines, want = [], []
-    for cname, pyname in STRUCTS:
-        cls = getattr(_abi, pyname)
-        lines.append(f'printf("%zu\\n", sizeof({cname}));')
-        want.append(C.sizeof(cls))
-        for field, _ in cls._fields_:
-            lines.append(f'printf("%zu\\n", offsetof({cname}, {field}));')
-            want.append(getattr(cls, field).offset)
-    for macro, val in (("ERPL_CORR_MAX_FACTORS", _abi.CORR_MAX_FACTORS), ("ERPL_CORR_MAX_ROWS", _abi.CORR_MAX_ROWS),
-                       ("ERPL_CORR_MAX_VARS", _abi.CORR_MAX_VARS), ("ERPL_MC_ABI_VERSION", _abi.ABI_VERSION)):
-        lines.append(f'printf("%d\\n", (int){macro});')
-        want.append(val)
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "erpl_mc.h"\nint main(){' + "".join(lines) + "return 0;}\n")
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
-    assert [int(x) for x in out] == want
+    H.check_struct_layouts(tmp_path, STRUCTS, MACROS)
     assert (_abi.CORR_MAX_FACTORS, _abi.CORR_MAX_ROWS, _abi.CORR_MAX_VARS) == (32, 16, 48)
     assert _abi.CORR_MAX_ROWS == _abi.SUMMARY_DIM and _abi.ABI_VERSION == 4
 

@@ -5,50 +5,32 @@ the Wilson interval against its closed form and the figure drawn from a hand-mad
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import helpers as H
 from erpl_monte_carlo_sim_amd import _abi, analysis, plots
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN = float("nan")
-DUMMY = C.c_void_p(0x1000)
+DUMMY = H.DUMMY
 
 STRUCTS = (("erpl_density_spec", "ErplDensitySpec"), ("erpl_density", "ErplDensity"))
+MACROS = (("ERPL_DENSITY_MAX_NODES", _abi.DENSITY_MAX_NODES), ("ERPL_DENSITY_MAX_LEVELS", _abi.DENSITY_MAX_LEVELS),
+          ("ERPL_DENSITY_MAX_ZONES", _abi.DENSITY_MAX_ZONES),
+          ("ERPL_DENSITY_MAX_VERTICES", _abi.DENSITY_MAX_VERTICES), ("ERPL_BW_SCOTT", _abi.BW_SCOTT),
+          ("ERPL_BW_MATRIX", _abi.BW_MATRIX))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_abi.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _abi.load_library()
+    return H.load_lib()
 
 
 def test_struct_layouts_match_the_c_compiler(tmp_path):
     """sizeof and the offset of EVERY field of the two new ctypes mirrors == what gcc sees in include/erpl_mc.h."""
-    lines, want = [], []
-    for cname, pyname in STRUCTS:
-        cls = getattr(_abi, pyname)
-        lines.append(f'printf("%zu\\n", sizeof({cname}));')
-        want.append(C.sizeof(cls))
-        for field, _ in cls._fields_:
-            lines.append(f'printf("%zu\\n", offsetof({cname}, {field}));')
-            want.append(getattr(cls, field).offset)
-    for macro, val in (("ERPL_DENSITY_MAX_NODES", _abi.DENSITY_MAX_NODES), ("ERPL_DENSITY_MAX_LEVELS", _abi.DENSITY_MAX_LEVELS),
-                       ("ERPL_DENSITY_MAX_ZONES", _abi.DENSITY_MAX_ZONES),
-                       ("ERPL_DENSITY_MAX_VERTICES", _abi.DENSITY_MAX_VERTICES), ("ERPL_BW_SCOTT", _abi.BW_SCOTT),
-                       ("ERPL_BW_MATRIX", _abi.BW_MATRIX), ("ERPL_MC_ABI_VERSION", _abi.ABI_VERSION)):
-        lines.append(f'printf("%d\\n", (int){macro});')
-        want.append(val)
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "erpl_mc.h"\nint main(){' + "".join(lines) + "return 0;}\n")
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
-    assert [int(x) for x in out] == want
+    H.check_struct_layouts(tmp_path, STRUCTS, MACROS)
     assert (_abi.DENSITY_MAX_NODES, _abi.DENSITY_MAX_ZONES, _abi.DENSITY_MAX_VERTICES) == (512, 8, 256)
     assert _abi.ABI_VERSION == 4
 

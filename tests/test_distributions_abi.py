@@ -4,51 +4,32 @@ work and look at the context last, so a NULL context and a dummy pointer that is
 import ctypes as C
 import math
 import os
-import subprocess
 
 import pytest
 
+import helpers as H
 from erpl_monte_carlo_sim_amd import _abi
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN = float("nan")
-DUMMY = C.c_void_p(0x1000)
+DUMMY = H.DUMMY
 
 STRUCTS = (("erpl_hist_spec", "ErplHistSpec"), ("erpl_hist_result", "ErplHistResult"),
            ("erpl_hist2d_spec", "ErplHist2dSpec"), ("erpl_hist2d_result", "ErplHist2dResult"),
            ("erpl_dispersion_spec", "ErplDispersionSpec"), ("erpl_dispersion", "ErplDispersion"))
+MACROS = (("ERPL_HIST_MAX_ROWS", _abi.HIST_MAX_ROWS), ("ERPL_HIST_MAX_BINS", _abi.HIST_MAX_BINS),
+          ("ERPL_HIST2D_MAX_BINS", _abi.HIST2D_MAX_BINS), ("ERPL_DISP_MAX_LEVELS", _abi.DISP_MAX_LEVELS),
+          ("ERPL_CENTRE_MEAN", _abi.CENTRE_MEAN), ("ERPL_CENTRE_POINT", _abi.CENTRE_POINT))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_abi.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _abi.load_library()
+    return H.load_lib()
 
 
 def test_struct_layouts_match_the_c_compiler(tmp_path):
     """sizeof and the offset of EVERY field of the six new ctypes mirrors == what gcc sees in include/erpl_mc.h."""
-    lines, want = [], []
-    for cname, pyname in STRUCTS:
-        cls = getattr(_abi, pyname)
-        lines.append(f'printf("%zu\\n", sizeof({cname}));')
-        want.append(C.sizeof(cls))
-        for field, _ in cls._fields_:
-            lines.append(f'printf("%zu\\n", offsetof({cname}, {field}));')
-            want.append(getattr(cls, field).offset)
-    for macro, val in (("ERPL_HIST_MAX_ROWS", _abi.HIST_MAX_ROWS), ("ERPL_HIST_MAX_BINS", _abi.HIST_MAX_BINS),
-                       ("ERPL_HIST2D_MAX_BINS", _abi.HIST2D_MAX_BINS), ("ERPL_DISP_MAX_LEVELS", _abi.DISP_MAX_LEVELS),
-                       ("ERPL_CENTRE_MEAN", _abi.CENTRE_MEAN), ("ERPL_CENTRE_POINT", _abi.CENTRE_POINT),
-                       ("ERPL_MC_ABI_VERSION", _abi.ABI_VERSION)):
-        lines.append(f'printf("%d\\n", (int){macro});')
-        want.append(val)
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "erpl_mc.h"\nint main(){' + "".join(lines) + "return 0;}\n")
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
-    assert [int(x) for x in out] == want
+    H.check_struct_layouts(tmp_path, STRUCTS, MACROS)
     assert _abi.ABI_VERSION == 4
 
 

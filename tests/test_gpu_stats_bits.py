@@ -4,7 +4,12 @@ The file was recorded by tools/record_stats_bits.py on the commit before the red
 erpl_distributions.hip and erpl_correlation.hip moved into erpl_stat_device.h.  The last bit of every sum and the sign of
 a zero minimum depend on the order of the reduction, so equality here pins that order: inputs and calls are those of
 stats_bits_cases.py (rows of standard_normal * 10**uniform(-3, 6), NaN and +-inf planted, one non-negative row with +0.0
-near its front and -0.0 near its end), at the smallest sizes that reach every level of the fold."""
+near its front and -0.0 near its end), at the smallest sizes that reach every level of the fold.
+
+tests/golden/stats_host_bits.json does the same for bootstrap and impact_density (collect_host_size), recorded with
+`tools/record_stats_bits.py --host` on the commit before their host halves moved onto the layouts of
+csrc/erpl_stat_layout.h: every branch of the two entry points, and at 262 444 samples the one density call with several
+source slices and partial sums near the bound of their piece."""
 import json
 import os
 
@@ -18,6 +23,7 @@ import stats_bits_cases as cases
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stats_bits.json")
+HOST_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stats_host_bits.json")
 
 
 @pytest.fixture(scope="module")
@@ -33,6 +39,13 @@ def engine():
 def golden():
     assert os.path.getsize(GOLDEN) <= 64 * 1024
     with open(GOLDEN) as f:
+        return json.load(f)
+
+
+@pytest.fixture(scope="module")
+def host_golden():
+    assert os.path.getsize(HOST_GOLDEN) <= 64 * 1024
+    with open(HOST_GOLDEN) as f:
         return json.load(f)
 
 
@@ -69,4 +82,22 @@ def test_inputs_can_tell_summation_orders_apart(n):
 def test_same_bits_as_recorded(engine, golden, n):
     got = json.loads(json.dumps(cases.collect_size(engine, n)))
     diff = differences(got, golden[str(n)], f"n={n}")
+    assert not diff, "\n".join(diff[:40])
+
+
+def test_the_host_recording_covers_the_sizes_and_branches(host_golden):
+    assert sorted(host_golden) == sorted(str(n) for n in cases.HOST_SIZES)
+    assert set(host_golden["1"]) == {"bootstrap", "density"}
+    assert set(host_golden["65"]) == {"bootstrap", "bootstrap_empty", "density", "density_flat"}
+    assert set(host_golden["1025"]) == {"bootstrap", "bootstrap_extra_alone", "density", "density_no_samples", "density_explicit"}
+    assert set(host_golden[str(cases.HOST_SIZES[-1])]) == {"density"}
+    assert host_golden["65"]["bootstrap_empty"]["count"] == 0 and not host_golden["65"]["density_flat"]["solid"]
+    assert all(host_golden[str(n)]["density"]["solid"] for n in cases.HOST_SIZES[1:])
+    assert host_golden[str(cases.HOST_SIZES[-1])]["density"]["count"] > 200000
+
+
+@pytest.mark.parametrize("n", cases.HOST_SIZES)
+def test_same_host_bits_as_recorded(engine, host_golden, n):
+    got = json.loads(json.dumps(cases.collect_host_size(engine, n)))
+    diff = differences(got, host_golden[str(n)], f"n={n}")
     assert not diff, "\n".join(diff[:40])
