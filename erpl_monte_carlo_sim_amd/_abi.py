@@ -35,6 +35,12 @@ FLAG_CAPTURE_POSITION_ONLY = 2
  SUM_IMPACT_Z, SUM_STEPS, SUM_RAIL_EXIT_AOA, SUM_RAIL_EXIT_SIDESLIP, SUM_FINAL_VZ,
  SUM_MAX_SPEED) = range(16)
 
+# rows of the flight envelope (erpl_mc_flight_envelope), double [ENV_DIM][n_traj]
+ENV_DIM = 16
+(ENV_MAX_Q, ENV_MAX_Q_TIME, ENV_MAX_Q_ALT, ENV_MAX_Q_MACH, ENV_MAX_MACH, ENV_MAX_Q_ALPHA, ENV_MAX_AXIAL_ACCEL,
+ ENV_MIN_STABILITY, ENV_MAX_OMEGA, ENV_MAX_QUAT_DEV, ENV_BURNOUT_TIME, ENV_BURNOUT_ALT, ENV_BURNOUT_SPEED,
+ ENV_BURNOUT_STABILITY, ENV_APOGEE_RECORD, ENV_USABLE) = range(16)
+
 END_MAX_TIME, END_GROUND, END_ALTITUDE, END_COAST, END_APOGEE = range(5)
 ST_APOGEE_LATCHED, ST_CHUTE, ST_NAN, ST_INCOMPLETE = 1 << 8, 1 << 9, 1 << 10, 1 << 11
 ERR_INCOMPLETE = -5
@@ -256,7 +262,7 @@ LEGACY_DEVICE_MAX_OUTPUTS = 4096   # erpl_mc_legacy_random_streams_device: outpu
 EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_mc_destroy",
            "erpl_mc_set_config", "erpl_mc_reserve", "erpl_mc_run_batch", "erpl_mc_set_launch",
            "erpl_mc_last_stats", "erpl_mc_ticket_stats", "erpl_mc_set_profiling", "erpl_mc_last_kernel_ms",
-           "erpl_mc_kernel_ms_history", "erpl_mc_debug_counters", "erpl_mc_extract_histories", "erpl_mc_set_chunk",
+           "erpl_mc_kernel_ms_history", "erpl_mc_debug_counters", "erpl_mc_extract_histories", "erpl_mc_flight_envelope", "erpl_mc_set_chunk",
            "erpl_mc_legacy_random_streams", "erpl_mc_legacy_wind_profiles", "erpl_mc_set_waves_per_simd",
            "erpl_mc_set_overlap", "erpl_mc_submit_batch", "erpl_mc_wait_batch", "erpl_mc_synchronize",
            "erpl_mc_debug_eval", "erpl_mc_synth_wind", "erpl_mc_set_adopt", "erpl_mc_get_overlap",
@@ -332,6 +338,7 @@ def load_library(path=None):
     lib.erpl_mc_debug_counters.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.erpl_mc_extract_histories.argtypes = [C.c_void_p, C.POINTER(ErplBatch), C.c_int64, C.c_void_p, C.c_int64,
                                               C.c_double, C.c_void_p, C.c_void_p]
+    lib.erpl_mc_flight_envelope.argtypes = [C.c_void_p, C.POINTER(ErplBatch), C.POINTER(ErplOut), C.c_void_p, C.c_void_p]
     lib.erpl_mc_analysis_defaults.argtypes = [C.POINTER(ErplAnalysisSpec)]
     lib.erpl_mc_analyze.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplAnalysisSpec),
                                     C.POINTER(ErplAnalysis), C.c_void_p, C.c_void_p]

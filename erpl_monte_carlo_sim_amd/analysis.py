@@ -273,6 +273,41 @@ def impact_probability(summary, status=None, engine=None, level=0.95, **kw):
     return out
 
 
+# ---------------------------------------------------------------------------------- the flight envelope
+ENVELOPE_NAMES = ("max_q", "max_q_time", "max_q_altitude", "max_q_mach", "max_mach", "max_q_alpha", "max_axial_acceleration",
+                  "min_stability_margin", "max_angular_rate", "max_quaternion_norm_deviation", "burnout_time",
+                  "burnout_altitude", "burnout_speed", "burnout_stability_margin", "apogee_record",
+                  "usable_records")   # _abi.ENV_* order
+
+
+def envelope_statistics(envelope, mask=None, engine=None, rows=None, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95)):
+    """Statistics of a flight envelope (float64 [16, m] on the device, TrajectoryEngine.flight_envelope) over the columns
+    whose `mask` byte is 0 (uint8 [m] on the device - the reason bytes of the outlier filter; None: every column): the
+    kept columns are described by erpl_mc_analyze under infinite bounds, so the order statistics are exact and the sums
+    are reduced in its fixed order.  What is left of that filter is its finiteness rule on rows 0, 4 and 5: a column
+    whose max_q, max_mach or max_q_alpha is not finite - a trajectory without a usable record - counts in no row; beyond
+    that a row counts its finite values (the burnout rows of a flight that ends before burnout are NaN).  rows: _abi.ENV_*
+    indices (default all 16).  Returns {name: {'count', 'mean', 'std', 'min', 'max', 'quantiles'}}, names from
+    ENVELOPE_NAMES; every number of a row without a counted value is NaN."""
+    from . import _abi
+    engine = _engine_of(envelope, engine)
+    rows = list(range(_abi.ENV_DIM)) if rows is None else [int(r) for r in rows]
+    quantiles = [float(q) for q in quantiles]
+    if mask is not None:
+        envelope = envelope[:, mask == 0].contiguous()
+    if envelope.shape[1] == 0:
+        nan = float("nan")
+        return {ENVELOPE_NAMES[r]: {"count": 0, "mean": nan, "std": nan, "min": nan, "max": nan,
+                                    "quantiles": [nan] * len(quantiles)} for r in rows}
+    inf = float("inf")
+    res, _ = engine.analyze(envelope, None, rows=rows, quantiles=quantiles,
+                            bounds={"max_apogee": inf, "min_apogee": -inf, "max_range": inf, "max_flight_time": inf,
+                                    "energy_apogee": inf})
+    return {ENVELOPE_NAMES[r]: {"count": int(res.row[j].count), "mean": res.row[j].mean, "std": res.row[j].std,
+                                "min": res.row[j].min, "max": res.row[j].max,
+                                "quantiles": list(res.row[j].quantile[:len(quantiles)])} for j, r in enumerate(rows)}
+
+
 # ---------------------------------------------------------------------------------- drivers: which dispersion drives what
 ROW_NAMES = ("apogee_altitude", "apogee_time", "first_apogee_altitude", "first_apogee_time", "range", "flight_time",
              "rail_exit_time", "rail_exit_speed", "impact_x", "impact_y", "impact_z", "n_steps",

@@ -748,6 +748,36 @@ int erpl_mc_extract_histories(erpl_ctx* c, const erpl_batch* b, int64_t sample, 
   return ERPL_OK;
 }
 
+int erpl_mc_flight_envelope(erpl_ctx* c, const erpl_batch* b, const erpl_out* o, double* envelope, void* stream) {
+  if (!b) return erpl_fail(ERPL_ERR_INVALID, "NULL batch");
+  if (!o) return erpl_fail(ERPL_ERR_INVALID, "NULL out");
+  if (!envelope) return erpl_fail(ERPL_ERR_INVALID, "NULL envelope");
+  if (b->precision != ERPL_PREC_F64 && b->precision != ERPL_PREC_F64_FAST)
+    return erpl_fail(ERPL_ERR_INVALID, "precision = %d: the flight envelope needs a batch with fp64 wind tables", b->precision);
+  if (b->n <= 0) return erpl_fail(ERPL_ERR_INVALID, "batch n = %lld: at least one sample", (long long)b->n);
+  if (o->n_traj < 0 || o->n_traj > 2147483647LL)
+    return erpl_fail(ERPL_ERR_INVALID, "n_traj = %lld out of range 0..2^31 - 1", (long long)o->n_traj);
+  if (o->n_traj > 0) {
+    if (o->traj_cap < 1) return erpl_fail(ERPL_ERR_INVALID, "traj_cap = %lld: at least one record per trajectory", (long long)o->traj_cap);
+    if (!o->traj_ids) return erpl_fail(ERPL_ERR_INVALID, "NULL traj_ids");
+    if (!o->traj) return erpl_fail(ERPL_ERR_INVALID, "NULL traj");
+    if (!o->traj_len) return erpl_fail(ERPL_ERR_INVALID, "NULL traj_len");
+    if (!b->rocket) return erpl_fail(ERPL_ERR_INVALID, "NULL rocket");
+    if (!b->motor) return erpl_fail(ERPL_ERR_INVALID, "NULL motor");
+    if (!check_wind_args(b)) return erpl_fail(ERPL_ERR_INVALID, "bad wind arguments (k_wind, alt_grid, wind)");
+  }
+  if (!c) return erpl_fail(ERPL_ERR_INVALID, "NULL ctx");
+  if (!c->has_cfg) return erpl_fail(ERPL_ERR_CONFIG, "erpl_mc_set_config has not been called");
+  if (o->n_traj == 0) return ERPL_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  ErplKArgs a;
+  fill_common_args(c, b, a);
+  a.summary = envelope;
+  a.n_traj = o->n_traj; a.traj_ids = o->traj_ids; a.traj_cap = o->traj_cap; a.traj = o->traj; a.traj_len = o->traj_len;
+  KERNEL_TRY(erpl_launch_envelope_f64(a, &c->h_tables.s64, stream));
+  return ERPL_OK;
+}
+
 int erpl_mc_debug_eval(erpl_ctx* c, const erpl_batch* b, int what, int64_t m, const double* in, double* out, void* stream) {
   if (!c || !b || !in || !out) return erpl_fail(ERPL_ERR_INVALID, "NULL argument");
   if (!c->has_cfg) return erpl_fail(ERPL_ERR_CONFIG, "erpl_mc_set_config has not been called");

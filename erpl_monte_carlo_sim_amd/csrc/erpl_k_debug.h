@@ -1,45 +1,28 @@
-// erpl_k_debug.h — kernel 3 (per-step diagnostic histories, gate build only) and the known-answer debug kernel.
+// erpl_k_debug.h — the evaluation of one stored record and kernel 3 on top of it (per-step diagnostic histories, gate build
+// only), and the known-answer debug kernel.
 namespace {
 
 #if ERPL_FAITHFUL
-// ------------------------------------------------------------------------------------ kernel 3
-// FlightSimulator._extract_results per-step loop (simulator.py:511-552): one thread per stored
-// record of one trajectory.  a.traj = records [m][15], a.traj_cap = m, a.n_traj = sample index,
-// a.summary = out [m][ERPL_DIAG_DIM].
-__global__ __launch_bounds__(256) void erpl_extract_f64(const ErplKArgs a, const ErplScalars<real> S,
-                                                        const double time_offset) {
-  __shared__ LdsTables L;
-  __shared__ real alt_s[ERPL_MAX_WIND_KNOTS];
-  stage_tables(L, alt_s, a.tables, a.alt_grid, a.k_wind);
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= a.traj_cap) return;
-  Shared C;
-  C.S = &S; C.L = &L; C.alt = alt_s; C.has_wind = a.k_wind > 0; C.motor_kind = a.motor_kind;
-  const int64_t n = a.n, id = a.n_traj;
-  LaneParams p;
-  p.dry = (real)a.rocket[0 * n + id]; p.prop = (real)a.rocket[1 * n + id];
-  p.thrust = (real)a.motor[0 * n + id]; p.Ae = (real)a.motor[1 * n + id];
-  p.mdot = (real)a.motor[2 * n + id]; p.burn = a.motor[3 * n + id];
-  lane_params_finish(S, p);
-  const double* rec = a.traj + r * ERPL_TRAJ_DIM;
-  const double ts = rec[0] - time_offset;  // rail-shifted time (simulator.py:464, :543)
-  real y[14];
-#pragma unroll
-  for (int c = 0; c < 14; ++c) y[c] = (real)rec[1 + c];
-  double* o = a.summary + r * ERPL_DIAG_DIM;
-  {  // quaternion_to_euler on the stored quaternion (utils.py:139-144 via :46-70)
-    const real w = y[6], x = y[7], yy = y[8], z = y[9];
-    o[0] = atan2(2 * (w * x + yy * z), 1 - 2 * (x * x + yy * yy));
-    const real sinp = 2 * (w * yy - z * x);
-    o[1] = (fabs(sinp) >= 1) ? copysign(1.57079632679489661923, sinp) : asin(sinp);
-    o[2] = atan2(2 * (w * z + x * yy), 1 - 2 * (yy * yy + z * z));
-  }
+// ------------------------------------------------------------------------------------ one stored record
+// What FlightSimulator._extract_results evaluates for ONE stored state (simulator.py:511-552) besides the Euler angles,
+// in the reference's operation order: mass properties, atmosphere, wind, relative velocity in the body frame, Mach,
+// aerodynamic angles and coefficients, dynamic pressure, thrust at the rail-shifted time ts, drag and stability margin.
+// Kernel 3 stores these per record; the envelope kernel (erpl_k_envelope.h) reduces them per trajectory.  The wind and
+// Mach intervals are looked up afresh for every record: the values do not depend on what a thread evaluated before.
+struct RecordEval {
   real mass, cg, Ixx, Iyy;
-  mass_props(S, p, y[13], mass, cg, Ixx, Iyy);
-  o[3] = cg; o[4] = mass; o[5] = Ixx; o[6] = Iyy; o[7] = Iyy;
-  real T, P;
-  atmosphere(S, y[2], T, P);
-  const real rho = P / (S.Rg * T);
+  real T, P, rho;
+  real vb0, vb1, vb2, vn, mach;
+  real alpha, beta;
+  real cd, cl, cy, cm, cyaw, cp_dyn;
+  real qdyn, thrust, drag, margin;
+};
+__device__ __forceinline__ void record_eval(const Shared& C, const LaneParams& p, int64_t id, double ts,
+                                            const real (&y)[14], RecordEval& e) {
+  const ErplScalars<real>& S = *C.S;
+  mass_props(S, p, y[13], e.mass, e.cg, e.Ixx, e.Iyy);
+  atmosphere(S, y[2], e.T, e.P);
+  e.rho = e.P / (S.Rg * e.T);
   WindCache wc;
   wc.lo = 1; wc.hi = 0; wc.x0 = 0;
 #pragma unroll
@@ -56,32 +39,76 @@ __global__ __launch_bounds__(256) void erpl_extract_f64(const ErplKArgs a, const
   const real R00 = 1 - 2 * (yy * yy + z * z), R01 = 2 * (x * yy - w * z), R02 = 2 * (x * z + w * yy);
   const real R10 = 2 * (x * yy + w * z), R11 = 1 - 2 * (x * x + z * z), R12 = 2 * (yy * z - w * x);
   const real R20 = 2 * (x * z - w * yy), R21 = 2 * (yy * z + w * x), R22 = 1 - 2 * (x * x + yy * yy);
-  const real vb0 = (R00 * vr0 + R10 * vr1) + R20 * vr2;
-  const real vb1 = (R01 * vr0 + R11 * vr1) + R21 * vr2;
-  const real vb2 = (R02 * vr0 + R12 * vr1) + R22 * vr2;
-  const real vn = m_sqrt((vr0 * vr0 + vr1 * vr1) + vr2 * vr2);
-  const real mach = vn / m_sqrt((real)(1.4 * 287.053) * T);
-  const bool a_dead = (m_abs(vb0) < (real)1e-6) && (m_abs(vb2) < (real)1e-6);
-  const real vxz = m_sqrt(vb0 * vb0 + vb2 * vb2);
-  const real alpha = a_dead ? (real)0 : m_atan2(vb2, vb0);
-  const real beta = (vxz < (real)1e-6) ? (real)0 : m_atan2(vb1, vxz);
+  e.vb0 = (R00 * vr0 + R10 * vr1) + R20 * vr2;
+  e.vb1 = (R01 * vr0 + R11 * vr1) + R21 * vr2;
+  e.vb2 = (R02 * vr0 + R12 * vr1) + R22 * vr2;
+  e.vn = m_sqrt((vr0 * vr0 + vr1 * vr1) + vr2 * vr2);
+  e.mach = e.vn / m_sqrt((real)(1.4 * 287.053) * e.T);
+  const bool a_dead = (m_abs(e.vb0) < (real)1e-6) && (m_abs(e.vb2) < (real)1e-6);
+  const real vxz = m_sqrt(e.vb0 * e.vb0 + e.vb2 * e.vb2);
+  e.alpha = a_dead ? (real)0 : m_atan2(e.vb2, e.vb0);
+  e.beta = (vxz < (real)1e-6) ? (real)0 : m_atan2(e.vb1, vxz);
   MachCache mc;
   mach_cache_clear(mc);
-  mach_lookup(C, mach, mc);
-  real cd, cl, cy, cm, cyaw, cp_dyn;
-  aero_coefficients(S, mach_rec_of(C, mc), mach, alpha, beta, cg, y[13] > 0, cd, cl, cy, cm, cyaw, cp_dyn);
-  const real qdyn = ((real)0.5 * rho) * (vn * vn);
-  real thrust = 0;  // motor.get_thrust(time[i], P) (motor.py:54-76 / :152-156)
+  mach_lookup(C, e.mach, mc);
+  aero_coefficients(S, mach_rec_of(C, mc), e.mach, e.alpha, e.beta, e.cg, y[13] > 0, e.cd, e.cl, e.cy, e.cm, e.cyaw, e.cp_dyn);
+  e.qdyn = ((real)0.5 * e.rho) * (e.vn * e.vn);
+  e.thrust = 0;  // motor.get_thrust(time[i], P) (motor.py:54-76 / :152-156)
   if (!(ts < 0.0 || ts > p.burn)) {
-    if (C.motor_kind == ERPL_MOTOR_SOLID) thrust = solid_curve(C, (real)ts, p.thrust) + p.Ae * ((real)101325.0 - P);
-    else thrust = p.thrust - p.Ae * P;
+    if (C.motor_kind == ERPL_MOTOR_SOLID) e.thrust = solid_curve(C, (real)ts, p.thrust) + p.Ae * ((real)101325.0 - e.P);
+    else e.thrust = p.thrust - p.Ae * e.P;
   }
-  o[8] = thrust;
-  o[9] = (qdyn * cd) * S.ref_area;
-  o[10] = cd; o[11] = cl; o[12] = cm;
-  o[13] = cp_dyn;
-  o[14] = (cp_dyn - cg) / S.ref_diam;
-  o[15] = alpha; o[16] = beta;
+  e.drag = (e.qdyn * e.cd) * S.ref_area;
+  e.margin = (e.cp_dyn - e.cg) / S.ref_diam;
+}
+
+// The per-sample parameters of sample `id` of a batch of n, as the flight kernel's lanes load them.
+__device__ __forceinline__ void lane_params_of(const ErplKArgs& a, const ErplScalars<real>& S, int64_t id, LaneParams& p) {
+  const int64_t n = a.n;
+  p.dry = (real)a.rocket[0 * n + id]; p.prop = (real)a.rocket[1 * n + id];
+  p.thrust = (real)a.motor[0 * n + id]; p.Ae = (real)a.motor[1 * n + id];
+  p.mdot = (real)a.motor[2 * n + id]; p.burn = a.motor[3 * n + id];
+  lane_params_finish(S, p);
+}
+
+// ------------------------------------------------------------------------------------ kernel 3
+// FlightSimulator._extract_results per-step loop (simulator.py:511-552): one thread per stored
+// record of one trajectory.  a.traj = records [m][15], a.traj_cap = m, a.n_traj = sample index,
+// a.summary = out [m][ERPL_DIAG_DIM].
+__global__ __launch_bounds__(256) void erpl_extract_f64(const ErplKArgs a, const ErplScalars<real> S,
+                                                        const double time_offset) {
+  __shared__ LdsTables L;
+  __shared__ real alt_s[ERPL_MAX_WIND_KNOTS];
+  stage_tables(L, alt_s, a.tables, a.alt_grid, a.k_wind);
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.traj_cap) return;
+  Shared C;
+  C.S = &S; C.L = &L; C.alt = alt_s; C.has_wind = a.k_wind > 0; C.motor_kind = a.motor_kind;
+  const int64_t id = a.n_traj;
+  LaneParams p;
+  lane_params_of(a, S, id, p);
+  const double* rec = a.traj + r * ERPL_TRAJ_DIM;
+  const double ts = rec[0] - time_offset;  // rail-shifted time (simulator.py:464, :543)
+  real y[14];
+#pragma unroll
+  for (int c = 0; c < 14; ++c) y[c] = (real)rec[1 + c];
+  double* o = a.summary + r * ERPL_DIAG_DIM;
+  {  // quaternion_to_euler on the stored quaternion (utils.py:139-144 via :46-70)
+    const real w = y[6], x = y[7], yy = y[8], z = y[9];
+    o[0] = atan2(2 * (w * x + yy * z), 1 - 2 * (x * x + yy * yy));
+    const real sinp = 2 * (w * yy - z * x);
+    o[1] = (fabs(sinp) >= 1) ? copysign(1.57079632679489661923, sinp) : asin(sinp);
+    o[2] = atan2(2 * (w * z + x * yy), 1 - 2 * (yy * yy + z * z));
+  }
+  RecordEval e;
+  record_eval(C, p, id, ts, y, e);
+  o[3] = e.cg; o[4] = e.mass; o[5] = e.Ixx; o[6] = e.Iyy; o[7] = e.Iyy;
+  o[8] = e.thrust;
+  o[9] = e.drag;
+  o[10] = e.cd; o[11] = e.cl; o[12] = e.cm;
+  o[13] = e.cp_dyn;
+  o[14] = e.margin;
+  o[15] = e.alpha; o[16] = e.beta;
 }
 #endif  // ERPL_FAITHFUL
 

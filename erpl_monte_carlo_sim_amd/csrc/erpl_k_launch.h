@@ -1,5 +1,5 @@
 // erpl_k_launch.h — the host side of a kernel unit: erpl_launch_<suffix> (rail + flight launches of one batch), the
-// gate unit's sweep and extract launchers, the debug launcher.
+// gate unit's sweep, extract and envelope launchers, the debug launcher.
 
 // One flight launch, from g, b, dyn_lds, st, a, S of the launcher that uses it.  SPEC >= 0 compiles the two launch
 // constants of the RHS in (bit 0 = a wind table is present, bit 1 = solid motor); trajectory capture reads them at run
@@ -93,6 +93,14 @@ int erpl_launch_extract_f64(const ErplKArgs& a, const void* scalars, double time
   const int block = 256;
   const int64_t grid = (a.traj_cap + block - 1) / block;
   hipLaunchKernelGGL(erpl_extract_f64, dim3((unsigned)grid), dim3(block), 0, (hipStream_t)stream, a, S, time_offset);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+int erpl_launch_envelope_f64(const ErplKArgs& a, const void* scalars, void* stream) {
+  if (a.n_traj <= 0) return 0;
+  const ErplScalars<real> S = *(const ErplScalars<real>*)scalars;
+  hipLaunchKernelGGL(erpl_envelope_f64, dim3((unsigned)a.n_traj), dim3(kEnvBlock), 0, (hipStream_t)stream, a, S);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }

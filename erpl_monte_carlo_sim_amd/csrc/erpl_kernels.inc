@@ -15,7 +15,8 @@
 // interval tables only when a lane leaves its interval, and uses wave ballots to refill finished lanes from
 // the queue, to hand the last lanes of a thinning wave to fuller waves (lane adoption) and (with step-chunked
 // launches) to park still-flying lanes densely for the next launch.  Kernel 3 (fp64 only) evaluates the
-// per-step diagnostic histories of _extract_results (:496-552).
+// per-step diagnostic histories of _extract_results (:496-552); kernel 4 (fp64 only) reduces every captured trajectory
+// of a batch to its flight envelope through the same per-record evaluation.
 //
 // ERPL_FAITHFUL keeps the reference's operation order (double normalisation, trig of
 // atan2, IEEE divisions); the two throughput builds allow algebraically identical shortcuts (no trig, reciprocal
@@ -35,5 +36,8 @@
 #endif
 #include "erpl_k_rail.h"     // kernel 1
 #include "erpl_k_flight.h"   // kernel 2, Lane and its record helpers
-#include "erpl_k_debug.h"    // kernel 3 (gate only) and the known-answer debug kernel
-#include "erpl_k_launch.h"   // host: erpl_launch_<suffix>, the sweep, extract and debug launchers
+#include "erpl_k_debug.h"    // one stored record's evaluation, kernel 3 (gate only) and the known-answer debug kernel
+#if ERPL_FAITHFUL
+#include "erpl_k_envelope.h" // kernel 4 (gate only): the flight envelope of every captured trajectory
+#endif
+#include "erpl_k_launch.h"   // host: erpl_launch_<suffix>, the sweep, extract, envelope and debug launchers

@@ -155,6 +155,9 @@ int erpl_launch_debug_f64f(const ErplKArgs& a, const void* scalars, int what, in
 // extraction of the per-step diagnostic histories (fp64 only): a.traj = records, a.traj_cap = m,
 // a.n_traj = sample index, a.summary = out [m][ERPL_DIAG_DIM]
 int erpl_launch_extract_f64(const ErplKArgs& a, const void* scalars, double time_offset, void* stream);
+// the flight envelope of every captured trajectory (fp64 only): a.n_traj / traj_ids / traj_cap / traj / traj_len as
+// erpl_out has them, a.summary = envelope [ERPL_ENV_DIM][n_traj]; one workgroup per trajectory (n_traj < 2^31)
+int erpl_launch_envelope_f64(const ErplKArgs& a, const void* scalars, void* stream);
 }
 
 // ---- erpl_mc_analyze: outlier filter + exact statistics on the summary (erpl_analysis.hip) ----

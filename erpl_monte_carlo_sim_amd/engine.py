@@ -303,6 +303,32 @@ class TrajectoryEngine:
                    float(time_offset), C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream))
         return out
 
+    def flight_envelope(self, db, traj_ids, traj, traj_len, stream=None):
+        """The flight envelope of every captured trajectory (erpl_mc_flight_envelope): maximum dynamic pressure with its
+        time, altitude and Mach number, maximum Mach number, q-alpha, axial acceleration, the smallest stability margin,
+        the largest angular rate and quaternion-norm drift, the state at burnout, the apogee record and the usable prefix
+        (rows _abi.ENV_*; the definitions are in include/erpl_mc.h).  `db` is the batch the records came from (fp64 wind
+        tables), traj_ids int64 [m], traj float64 [m, cap, 15] and traj_len int64 [m] the capture of run(..., traj_ids=...)
+        on the device.  Returns float64 [16, m] on the device; asynchronous on `stream` (default: the current stream)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype == dtype and t.is_contiguous()
+        if not (ok(traj, torch.float64) and traj.dim() == 3 and traj.shape[2] == _abi.TRAJ_DIM):
+            raise ValueError(f"traj must be a contiguous float64 [m, cap, {_abi.TRAJ_DIM}] tensor on {self.device}")
+        m, cap = int(traj.shape[0]), int(traj.shape[1])
+        if not (ok(traj_ids, torch.int64) and tuple(traj_ids.shape) == (m,)):
+            raise ValueError(f"traj_ids must be a contiguous int64 [m] tensor on {self.device}")
+        if not (ok(traj_len, torch.int64) and tuple(traj_len.shape) == (m,)):
+            raise ValueError(f"traj_len must be a contiguous int64 [m] tensor on {self.device}")
+        env = torch.empty((_abi.ENV_DIM, m), dtype=torch.float64, device=self.device)
+        if m == 0:   # (an empty tensor has no address to hand over)
+            return env
+        b = self._batch_struct(db)
+        o = _abi.ErplOut()
+        o.n_traj, o.traj_ids, o.traj_cap = m, traj_ids.data_ptr(), cap
+        o.traj, o.traj_len = traj.data_ptr(), traj_len.data_ptr()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_flight_envelope", C.byref(b), C.byref(o), C.c_void_p(env.data_ptr()), C.c_void_p(st.cuda_stream))
+        return env
+
     def analysis_defaults(self):
         """The reference's outlier bounds, rows and quantiles (erpl_mc_analysis_defaults)."""
         return self._defaults(_abi.ErplAnalysisSpec, "erpl_mc_analysis_defaults")

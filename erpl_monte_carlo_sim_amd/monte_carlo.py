@@ -382,6 +382,70 @@ class MonteCarloAnalyzer:
                               "statistics_s": t3 - t2, "sub_batches": len(parts), "in_flight": eng.get_overlap()}
         return out
 
+    def flight_envelope(self, initial_conditions, n_samples, stride=10, seed=1234, precision="f64_fast", planar=False,
+                        capture_bytes=4 << 30):
+        """What the vehicle goes through on the way up, for every sample of a dispersion run: the samples of
+        `run_monte_carlo_device` (same draws: sub-batch j from seed + rank + 1000003 * j) are flown with EVERY trajectory
+        captured at every `stride`-th step and each capture is reduced on the device to its flight envelope
+        (TrajectoryEngine.flight_envelope: max-Q and where it falls, maximum Mach number, q-alpha, axial acceleration,
+        smallest stability margin, burnout state, ...).  The envelope is that of the stored records: stride = 1 is the
+        flight's own, a larger stride can miss a peak between two records.
+
+        A capture holds cap * 120 bytes per sample, cap = the records a flight to max_time can write at this stride, so
+        no capture can overflow; a sub-batch has capture_bytes // (cap * 120) samples (at most DEVICE_CHUNK) and its
+        capture buffer is released as soon as its envelope is computed.  One rank only: envelopes are not gathered across
+        ranks (ValueError before any work).
+
+        Returns a dict: 'summary' [16, n] / 'status' [n] of the capturing run itself (where the sub-batches coincide these
+        are run_monte_carlo_device's: bit for bit with precision="f64" and, measured, on planar "f64_fast" sets; on
+        diverging "f64_fast" samples to 5e-8 relative with the same end reasons, because the capture instantiation of the
+        throughput build fuses a few products differently - DESIGN.md section 4), 'envelope' float64 [16, n] on the
+        device with 'envelope_names' (analysis.ENVELOPE_NAMES, rows _abi.ENV_*), 'reasons' (uint8 [n], the outlier
+        filter's reason bits), 'n_samples' / 'n_outliers' of that filter, 'statistics' (analysis.envelope_statistics
+        over the samples that pass it) and 'performance'."""
+        from . import sampling
+        if dist.world()[1] > 1:
+            raise ValueError("flight_envelope is limited to a world size of 1: envelopes are not gathered across ranks")
+        n_samples, stride = int(n_samples), int(stride)
+        if n_samples < 1 or stride < 1:
+            raise ValueError("n_samples and stride must be at least 1")
+        eng = shared_engine(self.device)
+        eng.set_config(self._config())
+        rank = dist.world()[0]
+        prec = _abi.PRECISIONS[precision]
+        dt = min(self.dt_initial, 0.005)
+        cap = int(np.ceil(self.max_time / dt / stride)) + 4
+        per_batch = max(1, min(self.DEVICE_CHUNK, int(capture_bytes) // (cap * _abi.TRAJ_DIM * 8)))
+        torch.cuda.synchronize(eng.device)
+        t0 = time.time()
+        summs, stats, envs = [], [], []
+        for j, a in enumerate(range(0, n_samples, per_batch)):
+            nb = min(per_batch, n_samples - a)
+            db = sampling.synthetic_dispersions(
+                nb, self.rocket, self.motor, self.wind_model, initial_conditions, eng.device, precision=prec,
+                seed=seed + rank + 1000003 * j, uncertainty=self.uncertainty_params,
+                base_altitude_profile=self.base_altitude_profile, base_wind_profile=self.base_wind_profile,
+                planar=planar, engine=eng)
+            summ, status, traj, tlen = eng.run(db, traj_ids=np.arange(nb), traj_stride=stride, traj_cap=cap)
+            envs.append(eng.flight_envelope(db, eng._keep, traj, tlen))
+            summs.append(summ)
+            stats.append(status)
+            del traj, tlen, db   # (stream-ordered: the allocator hands the capture buffer on behind the envelope kernel)
+        eng.synchronize()        # host-blocking; raises if a lane hand-over timed out
+        cat = lambda parts, dim: parts[0] if len(parts) == 1 else torch.cat(parts, dim=dim).contiguous()
+        summ, status, env = cat(summs, 1), cat(stats, 0), cat(envs, 1)
+        torch.cuda.synchronize(eng.device)
+        t1 = time.time()
+        _, res, why = analysis._filter(summ, status, eng)
+        out = {"summary": summ, "status": status, "envelope": env, "envelope_names": list(analysis.ENVELOPE_NAMES),
+               "reasons": why, "n_samples": int(res.n_valid), "n_outliers": int(res.n_outliers),
+               "statistics": analysis.envelope_statistics(env, why, engine=eng)}
+        t2 = time.time()
+        out["performance"] = {"total_time": t2 - t0, "capture_and_envelope_s": t1 - t0, "statistics_s": t2 - t1,
+                              "precision": precision, "stride": stride, "records_per_sample": cap,
+                              "sub_batches": len(envs), "sub_batch_samples": per_batch}
+        return out
+
     def run_optimized_monte_carlo(self, initial_conditions, n_samples=1000, chunk_size=None):
         return self.run_monte_carlo(initial_conditions, n_samples, optimized=True)
 

@@ -313,6 +313,52 @@ int erpl_mc_ticket_stats(erpl_ctx* ctx, int64_t ticket, double* total_steps, dou
 int erpl_mc_extract_histories(erpl_ctx* ctx, const erpl_batch* batch, int64_t sample, const double* traj,
                               int64_t m, double time_offset, double* out, void* hip_stream);
 
+/* The flight envelope of every captured trajectory of a run ON THE DEVICE (no reference counterpart; the reference's
+ * analyze_outlier.py digs the same numbers out of one dumped flight by hand): what the vehicle went through on the way
+ * up - maximum dynamic pressure and where it falls, maximum Mach number, the q-alpha bending-load indicator, axial
+ * acceleration, the smallest stability margin, the state at burnout.
+ * `batch` is the batch the records came from: its rocket, motor, alt_grid and wind are read, ic is not.  `out` is the
+ * erpl_out of that run: n_traj, traj_ids, traj_cap, traj and traj_len are read; summary, status and traj_stride are not.
+ * `envelope` is CALLER-OWNED device memory, double [ERPL_ENV_DIM][n_traj], structure of arrays like a summary (and
+ * accepted wherever a summary [ERPL_SUMMARY_DIM][n] is: erpl_mc_analyze under infinite bounds, erpl_mc_histogram, ...).
+ * Asynchronous on `hip_stream` like erpl_mc_extract_histories: no workspace, no host result, no host wait.  Records of
+ * any build's capture are accepted (they are doubles); the per-record evaluation is that of the ERPL_PREC_F64 build, so
+ * the batch must carry fp64 wind tables (ERPL_PREC_F64 or ERPL_PREC_F64_FAST).
+ *
+ * Trajectory j has len = traj_len[j] records rec[r][ERPL_TRAJ_DIM] of sample id = traj_ids[j] (ids are trusted, as
+ * erpl_mc_run_batch trusts them):
+ *   usable prefix u = the index of the first record with a non-finite time or state entry, len if there is none; only
+ *     records r < u take part anywhere.  USABLE = u; with u == 0 every other row is NaN.
+ *   ts(r) = rec[r][0] - rec[0][0]: record 0 of a capture carries the rail-exit time.
+ *   apogee record a = the first index of the largest altitude rec[r][3] over r < u (APOGEE_RECORD); ascent window: r <= a.
+ *   burnout record b = the first r < u with ts(r) > burn_time[id] (the motor's own time test, motor.py:54-76 / :152-156;
+ *     propellant_fraction never reaches 0 in this model); none: the four BURNOUT_* rows are NaN.
+ *   Per record, through the device functions of erpl_mc_extract_histories, same operations, same order, no contraction:
+ *     atmosphere and wind at z, v_rel, its body-frame components vb, Mach, q = (0.5 rho) * (|v_rel| * |v_rel|), alpha, beta,
+ *     the coefficients, thrust at ts, drag, mass, margin = (cp_dyn - cg) / reference_diameter,
+ *     alpha_total = atan2(sqrt(vb1*vb1 + vb2*vb2), vb0).
+ *   A quantity of a record takes part in a maximum or minimum only if it is FINITE (the blow-ups of this model produce
+ *   inf and NaN in late records); ties go to the lowest record index; a row without any finite candidate is NaN.
+ *   Over the ascent window: MAX_Q with MAX_Q_TIME / MAX_Q_ALT / MAX_Q_MACH = ts, z, Mach of the same record; MAX_MACH;
+ *     MAX_Q_ALPHA = max q * alpha_total; MAX_AXIAL_ACCEL = max (thrust - drag) / mass; MIN_STABILITY = min margin.
+ *   Over all usable records: MAX_OMEGA = max of max(|wx|, |wy|, |wz|);
+ *     MAX_QUAT_DEV = max |sqrt(((w*w + x*x) + y*y) + z*z) - 1|.
+ *   At record b: BURNOUT_TIME = ts(b), BURNOUT_ALT = z, BURNOUT_SPEED = sqrt((vx*vx + vy*vy) + vz*vz),
+ *     BURNOUT_STABILITY = margin.
+ * The envelope is that of the STORED records: with traj_stride = 1 the flight's own; a larger stride can miss a peak
+ * between two records.  The bytes of column j depend only on the trajectory's own records and its sample's parameters
+ * (no atomics; every reduction orders its candidates by value, then record index).
+ * Errors: ERPL_ERR_INVALID, before any device work and with a message that names the argument, in this order: NULL batch /
+ * out / envelope; a precision other than the two fp64 values; batch->n <= 0; n_traj < 0 or >= 2^31; with n_traj > 0:
+ * traj_cap < 1, NULL traj_ids / traj / traj_len / rocket / motor, bad wind arguments; the context last (without a config:
+ * ERPL_ERR_CONFIG).  n_traj == 0 is a no-op that returns ERPL_OK. */
+#define ERPL_ENV_DIM 16   /* = ERPL_SUMMARY_DIM: an envelope [ERPL_ENV_DIM][n_traj] is accepted wherever a summary is */
+enum { ERPL_ENV_MAX_Q = 0, ERPL_ENV_MAX_Q_TIME = 1, ERPL_ENV_MAX_Q_ALT = 2, ERPL_ENV_MAX_Q_MACH = 3,
+       ERPL_ENV_MAX_MACH = 4, ERPL_ENV_MAX_Q_ALPHA = 5, ERPL_ENV_MAX_AXIAL_ACCEL = 6, ERPL_ENV_MIN_STABILITY = 7,
+       ERPL_ENV_MAX_OMEGA = 8, ERPL_ENV_MAX_QUAT_DEV = 9, ERPL_ENV_BURNOUT_TIME = 10, ERPL_ENV_BURNOUT_ALT = 11,
+       ERPL_ENV_BURNOUT_SPEED = 12, ERPL_ENV_BURNOUT_STABILITY = 13, ERPL_ENV_APOGEE_RECORD = 14, ERPL_ENV_USABLE = 15 };
+int erpl_mc_flight_envelope(erpl_ctx* ctx, const erpl_batch* batch, const erpl_out* out, double* envelope, void* hip_stream);
+
 /* Host-side input preparation (no device work): the first `m` outputs of NumPy's legacy
  * `np.random.RandomState(seed)` for each of `n` integer seeds, bit for bit - the reference draws
  * every sample's dispersions, motor perturbation and wind turbulence from such per-sample streams
