@@ -252,6 +252,20 @@ class ErplDensity(C.Structure):
                 ("zone_inside", C.c_int64 * DENSITY_MAX_ZONES), ("sample_density", ErplRowStats)]
 
 
+# erpl_mc_corridor_resample / erpl_mc_corridor_bands
+CORRIDOR_MAX_CHANNELS = 8
+CORRIDOR_MAX_NODES = 4096
+(CH_X, CH_Y, CH_Z, CH_DOWNRANGE, CH_VX, CH_VY, CH_VZ, CH_SPEED) = range(8)
+CH_COUNT = 8
+CORRIDOR_HOLD_END = 1
+
+
+class ErplCorridorSpec(C.Structure):
+    _fields_ = [("n_channels", C.c_int32), ("channels", C.c_int32 * CORRIDOR_MAX_CHANNELS),
+                ("n_nodes", C.c_int32), ("flags", C.c_int32), ("t0", C.c_double), ("dt", C.c_double),
+                ("n_q", C.c_int32), ("reserved", C.c_int32), ("q", _Q)]
+
+
 LIB_NAME = "liberpl_mc.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
@@ -273,6 +287,7 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_correlation_defaults", "erpl_mc_correlation",
            "erpl_mc_bootstrap_defaults", "erpl_mc_bootstrap", "erpl_mc_bootstrap_indices",
            "erpl_mc_impact_density_defaults", "erpl_mc_impact_density",
+           "erpl_mc_corridor_defaults", "erpl_mc_corridor_resample", "erpl_mc_corridor_bands",
            "erpl_mc_legacy_random_streams_device", "erpl_mc_legacy_wind_profiles_device")
 
 _lib = None
@@ -360,6 +375,11 @@ def load_library(path=None):
     lib.erpl_mc_impact_density_defaults.argtypes = [C.POINTER(ErplDensitySpec)]
     lib.erpl_mc_impact_density.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplDensitySpec), C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.POINTER(ErplDensity), C.c_void_p, C.c_void_p]
+    lib.erpl_mc_corridor_defaults.argtypes = [C.POINTER(ErplCorridorSpec)]
+    lib.erpl_mc_corridor_resample.argtypes = [C.c_void_p, C.POINTER(ErplOut), C.POINTER(ErplCorridorSpec), C.c_void_p, C.c_int64,
+                                              C.c_int64, C.c_void_p]
+    lib.erpl_mc_corridor_bands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(ErplCorridorSpec),
+                                           C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
     lib.erpl_mc_legacy_random_streams_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                                          C.c_int32, C.c_void_p]
     lib.erpl_mc_legacy_wind_profiles_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 9 + \

@@ -308,6 +308,41 @@ def envelope_statistics(envelope, mask=None, engine=None, rows=None, quantiles=(
                                 "quantiles": list(res.row[j].quantile[:len(quantiles)])} for j, r in enumerate(rows)}
 
 
+# ---------------------------------------------------------------------------------- the trajectory corridor
+CORRIDOR_CHANNEL_NAMES = ("x", "y", "z", "downrange", "vx", "vy", "vz", "speed")   # _abi.CH_* order
+
+
+def corridor_channels(channels):
+    """Channel names or _abi.CH_* indices as a list of indices."""
+    out = []
+    for c in channels:
+        if isinstance(c, str):
+            if c not in CORRIDOR_CHANNEL_NAMES:
+                raise ValueError(f"unknown channel {c!r}: one of {CORRIDOR_CHANNEL_NAMES}")
+            c = CORRIDOR_CHANNEL_NAMES.index(c)
+        out.append(int(c))
+    return out
+
+
+def trajectory_corridor(values, channels=("z", "downrange", "speed"), t0=0.0, dt=1.0,
+                        quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), mask=None, engine=None, m=None):
+    """The time-resolved bands of a resampled matrix (float64 [C, T, ld] on the device, TrajectoryEngine.corridor_resample
+    with these `channels`, `t0` and `dt`) over the columns whose `mask` byte is 0 (uint8 [m] on the device - the reason bytes
+    of the outlier filter; None: every column), by one erpl_mc_corridor_bands call.  Returns a dict: 'time' [T] (the nodes
+    t0 + k dt), 'q', 'channels' (names), 'n_counted' and, per channel name, {'count', 'mean', 'std', 'min', 'max'} as
+    arrays [T] and 'quantiles' [n_q, T]; at a node without a counted finite value every number is NaN."""
+    engine = _engine_of(values, engine)
+    idx = corridor_channels(channels)
+    if len(idx) != int(values.shape[0]):
+        raise ValueError(f"{len(idx)} channels for a matrix of {int(values.shape[0])}")
+    b = engine.corridor_bands(values, mask, quantiles=quantiles, m=m)
+    out = {"time": float(t0) + np.arange(int(values.shape[1]), dtype=np.float64) * float(dt), "q": b["q"],
+           "channels": [CORRIDOR_CHANNEL_NAMES[c] for c in idx], "n_counted": b["n_counted"]}
+    for j, c in enumerate(idx):
+        out[CORRIDOR_CHANNEL_NAMES[c]] = {k: b[k][j] for k in ("count", "mean", "std", "min", "max", "quantiles")}
+    return out
+
+
 # ---------------------------------------------------------------------------------- drivers: which dispersion drives what
 ROW_NAMES = ("apogee_altitude", "apogee_time", "first_apogee_altitude", "first_apogee_time", "range", "flight_time",
              "rail_exit_time", "rail_exit_speed", "impact_x", "impact_y", "impact_z", "n_steps",

@@ -120,13 +120,7 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_finish_first(const Er
     // ranks of the two order statistics behind every quantile (np.percentile, linear)
     ErplAnaSelect& s = w->sel[r];
     for (int t = 0; t < ERPL_ANA_TARGETS; ++t) {
-      unsigned long long rank = 0ull;
-      if (cnt > 0ull && t < 2 * a.n_q) {
-        const double pos = a.q[t >> 1] * (double)(cnt - 1ull);
-        unsigned long long lo = (unsigned long long)floor(pos);
-        if (lo > cnt - 1ull) lo = cnt - 1ull;
-        rank = (t & 1) ? (lo + 1ull < cnt ? lo + 1ull : cnt - 1ull) : lo;
-      }
+      const unsigned long long rank = cnt > 0ull && t < 2 * a.n_q ? select_rank(cnt, a.q[t >> 1], t) : 0ull;
       s.prefix[t] = 0ull; s.rank[t] = rank; s.leader[t] = 0;
       o.key[t] = 0ull;
     }
@@ -160,8 +154,6 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_histogram(const ErplA
   }
   __syncthreads();
   const int nlead = s_nlead;
-  // bits above the digit of this pass (none in the first pass: every key matches)
-  const unsigned long long above = shift >= 56 ? 0ull : (~0ull << (shift + 8));
   const int64_t first = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + (threadIdx.x & ~63);
   for (int64_t base = first; base < n; base += stride) {   // uniform over the wave (ballots below)
     const int64_t i = base + (threadIdx.x & 63);
@@ -172,20 +164,7 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_histogram(const ErplA
       use = why[i] == 0 && finite_bits(v);
       key = key_of_signed(v);
     }
-    const unsigned int digit = (unsigned int)(key >> shift) & (ERPL_ANA_BINS - 1);
-    for (int m = 0; m < nlead; ++m) {
-      const bool hit = use && ((key ^ s_prefix[m]) & above) == 0ull;
-      const unsigned long long mask = __ballot(hit);
-      if (mask == 0ull) continue;
-      // heavily tied data puts a whole wave into one bin: one add of the lane count instead of 64 serialised ones
-      const int lead_lane = __ffsll((long long)mask) - 1;
-      const unsigned int d0 = (unsigned int)__shfl((int)digit, lead_lane);
-      if (__ballot(hit && digit != d0) == 0ull) {
-        if ((int)(threadIdx.x & 63) == lead_lane) atomicAdd(&s_hist[s_lead[m]][d0], (unsigned int)__popcll(mask));
-      } else if (hit) {
-        atomicAdd(&s_hist[s_lead[m]][digit], 1u);
-      }
-    }
+    select_count(s_hist, s_lead, s_prefix, nlead, use, key, shift);
   }
   __syncthreads();
   for (int m = 0; m < nlead; ++m) {
@@ -206,23 +185,11 @@ __global__ __launch_bounds__(64 * ERPL_ANA_TARGETS) void erpl_ana_scan(const Erp
   if (t < nt) {
     const unsigned long long* h = a.work->hist[r][sel.leader[t]];
     const unsigned long long rank = sel.rank[t];
-    unsigned long long c[4], s = 0ull;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { c[k] = h[lane * 4 + k]; s += c[k]; }
-    unsigned long long incl = s;
-    for (int off = 1; off < 64; off <<= 1) {
-      const unsigned long long up = __shfl_up(incl, off);
-      if (lane >= off) incl += up;
-    }
-    unsigned long long before = incl - s;
-    unsigned long long prefix = sel.prefix[t];
+    unsigned long long prefix = sel.prefix[t], before = 0ull;
+    int d = 0;
     if (lane == 0) s_prefix[t] = prefix;   // stays if no bin holds the rank: an empty row
-    if (before <= rank && rank < incl) {   // exactly one lane
-      int d = 0;
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        if (rank >= before + c[k] && d == k) { before += c[k]; d = k + 1; }
-      prefix |= (unsigned long long)(lane * 4 + d) << shift;
+    if (select_scan(h, rank, lane, &d, &before)) {   // exactly one lane
+      prefix |= (unsigned long long)d << shift;
       sel.prefix[t] = prefix;
       sel.rank[t] = rank - before;
       a.work->res.row[r].key[t] = prefix;
@@ -230,11 +197,7 @@ __global__ __launch_bounds__(64 * ERPL_ANA_TARGETS) void erpl_ana_scan(const Erp
     }
   }
   __syncthreads();   // every histogram has been read, every prefix is known
-  if (lane == 0 && t < nt) {
-    int lead = t;
-    for (int u = t - 1; u >= 0; --u) if (s_prefix[u] == s_prefix[t]) lead = u;
-    sel.leader[t] = lead;
-  }
+  if (lane == 0 && t < nt) sel.leader[t] = select_leader(s_prefix, t);
   unsigned long long* h = &a.work->hist[r][0][0];
   for (int k = threadIdx.x; k < ERPL_ANA_TARGETS * ERPL_ANA_BINS; k += 64 * ERPL_ANA_TARGETS) h[k] = 0ull;
 }

@@ -183,6 +183,8 @@ struct erpl_ctx {
   ErplStatUnit<ErplCorrWork, ErplCorrOut> corr;
   ErplStatUnit<void, BootHost> boot;
   ErplStatUnit<ErplDensWork, DensHost> dens;
+  // erpl_mc_corridor_bands: the row records its kernel hands back, nothing else (no fixed block, no pinned mirror)
+  ErplStatUnit<void, char> corridor;
   // erpl_mc_legacy_random_streams_device / _wind_profiles_device: one device buffer (flag, op tables, knot constants, the
   // MT19937 states of a tile and two sets of its accepted pairs) and its pinned staging (the tables on their way up, r2
   // down and f up, per set), both bounded by the tile; an event per set behind the tile's copy to the host

@@ -1,5 +1,5 @@
 // erpl_stat_device.h — what the statistics units (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip,
-// erpl_bootstrap.hip) share: the grid of their streaming passes, the order-preserving keys and THE fixed-order reduction.
+// erpl_bootstrap.hip, erpl_density.hip, erpl_corridor.hip) share: the grid of their streaming passes, the order-preserving keys, THE fixed-order reduction and the steps of the radix selection.
 // Internal: never installed.
 //
 // The order is the contract: the last bit of every sum and the sign of a zero minimum depend on it, and "the same bits in
@@ -143,6 +143,71 @@ __device__ __forceinline__ u64 counters_fold(const u64 (&cnt)[K]) {
   if (threadIdx.x < K)
     for (int w = 0; w < kWaves; ++w) s += s_cnt[w][threadIdx.x];
   return s;
+}
+
+// ---- the most-significant-digit radix selection of erpl_analysis.hip and erpl_corridor.hip: one 8-bit digit per pass, a
+// histogram per group of targets that still share a key prefix.  The units differ in where the histograms live (64-bit
+// global bins behind LDS tiles there, LDS alone here); what a pass decides is written once, below.
+
+// The rank of target t among the cnt > 0 counted values of a row: targets 2 i and 2 i + 1 are the two order statistics
+// behind quantile q (np.percentile, linear): lo = floor(q (cnt - 1)) and min(lo + 1, cnt - 1).
+__device__ __forceinline__ u64 select_rank(u64 cnt, double q, int t) {
+  const double pos = q * (double)(cnt - 1ull);
+  u64 lo = (u64)floor(pos);
+  if (lo > cnt - 1ull) lo = cnt - 1ull;
+  return (t & 1) ? (lo + 1ull < cnt ? lo + 1ull : cnt - 1ull) : lo;
+}
+
+// One key into the LDS histograms of a pass: hist[lead[m]] counts the digit at `shift` of the keys that match
+// prefix[m] above it, m < nlead.  Every lane of the wave calls it (ballots); use = false: the lane brings no key.
+__device__ __forceinline__ void select_count(unsigned int (*hist)[ERPL_ANA_BINS], const int* lead, const u64* prefix, int nlead,
+                                             bool use, u64 key, int shift) {
+  // bits above the digit of this pass (none in the first pass: every key matches)
+  const u64 above = shift >= 56 ? 0ull : (~0ull << (shift + 8));
+  const unsigned int digit = (unsigned int)(key >> shift) & (ERPL_ANA_BINS - 1);
+  for (int m = 0; m < nlead; ++m) {
+    const bool hit = use && ((key ^ prefix[m]) & above) == 0ull;
+    const u64 mask = __ballot(hit);
+    if (mask == 0ull) continue;
+    // heavily tied data puts a whole wave into one bin: one add of the lane count instead of 64 serialised ones
+    const int lead_lane = __ffsll((long long)mask) - 1;
+    const unsigned int d0 = (unsigned int)__shfl((int)digit, lead_lane);
+    if (__ballot(hit && digit != d0) == 0ull) {
+      if ((int)(threadIdx.x & 63) == lead_lane) atomicAdd(&hist[lead[m]][d0], (unsigned int)__popcll(mask));
+    } else if (hit) {
+      atomicAdd(&hist[lead[m]][digit], 1u);
+    }
+  }
+}
+
+// A wave scans the ERPL_ANA_BINS counts h of a target's group for the bin that holds `rank`.  True in exactly one lane
+// (in none if the histogram is empty): there *digit is the bin and *below the count of keys in the bins before it.
+template <class Count>
+__device__ __forceinline__ bool select_scan(const Count* h, u64 rank, int lane, int* digit, u64* below) {
+  u64 c[4], s = 0ull;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { c[k] = (u64)h[lane * 4 + k]; s += c[k]; }
+  u64 incl = s;
+  for (int off = 1; off < 64; off <<= 1) {
+    const u64 up = __shfl_up(incl, off);
+    if (lane >= off) incl += up;
+  }
+  u64 before = incl - s;
+  if (!(before <= rank && rank < incl)) return false;
+  int d = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    if (rank >= before + c[k] && d == k) { before += c[k]; d = k + 1; }
+  *digit = lane * 4 + d;
+  *below = before;
+  return true;
+}
+
+// the first target that shares target t's prefix: the one that keeps the histogram of the group
+__device__ __forceinline__ int select_leader(const u64* prefix, int t) {
+  int lead = t;
+  for (int u = t - 1; u >= 0; --u) if (prefix[u] == prefix[t]) lead = u;
+  return lead;
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
 // erpl_stats_api.hip — host halves of the analysis entry points of the C ABI (include/erpl_mc.h): erpl_mc_analyze,
-// erpl_mc_histogram, erpl_mc_histogram_xy, erpl_mc_dispersion, erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density
-// and their defaults.  Argument checks, workspace, launches (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip,
-// erpl_bootstrap.hip, erpl_density.hip) and what the host finishes in double precision.  The refusals come in one order
+// erpl_mc_histogram, erpl_mc_histogram_xy, erpl_mc_dispersion, erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density,
+// erpl_mc_corridor_resample, erpl_mc_corridor_bands and their defaults.  Argument checks, workspace, launches
+// (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip, erpl_bootstrap.hip, erpl_density.hip, erpl_corridor.hip)
+// and what the host finishes in double precision.  The refusals come in one order
 // everywhere - spec fields, n, pointers, context (erpl_mc_bootstrap: the order its header comment lists) - and need no
 // device; tests/golden/stats_refusals.json pins their texts.  What the entry points share comes first: the pieces of the
 // argument checks, describe_rows, the host finish of a described row and of a landing cloud.  The growing buffers are laid
@@ -950,6 +951,101 @@ int erpl_mc_impact_density(erpl_ctx* c, const double* summary, const uint8_t* ma
   result->peak_iy = solid ? (int32_t)((int64_t)h.out.peak_at % ny) : -1;
   const bool described = solid && want_samples;
   finish_row_stats(described ? c->ana.host->row[0] : ErplAnaRow(), q, spec->n_levels, described, result->sample_density);
+  return ERPL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------- erpl_mc_corridor_resample, erpl_mc_corridor_bands
+namespace {
+
+// every field of the spec, for both calls: channels, nodes, flags, t0, dt, quantiles - in that order
+int check_corridor_spec(const erpl_corridor_spec* s) {
+  ERPL_TRY(check_int(s->n_channels, "n_channels", -1, 1, ERPL_CORRIDOR_MAX_CHANNELS));
+  for (int j = 0; j < s->n_channels; ++j) {
+    ERPL_TRY(check_int(s->channels[j], "channels", j, 0, ERPL_CH_COUNT - 1));
+    for (int k = 0; k < j; ++k)
+      if (s->channels[k] == s->channels[j])
+        return erpl_fail(ERPL_ERR_INVALID, "spec->channels[%d] = %d is listed twice", j, s->channels[j]);
+  }
+  ERPL_TRY(check_int(s->n_nodes, "n_nodes", -1, 1, ERPL_CORRIDOR_MAX_NODES));
+  if (s->flags & ~ERPL_CORRIDOR_HOLD_END) return erpl_fail(ERPL_ERR_INVALID, "spec->flags = %d: ERPL_CORRIDOR_HOLD_END or 0", s->flags);
+  if (!std::isfinite(s->t0)) return erpl_fail(ERPL_ERR_INVALID, "spec->t0 = %g is not finite", s->t0);
+  if (!(std::isfinite(s->dt) && s->dt > 0.0)) return erpl_fail(ERPL_ERR_INVALID, "spec->dt = %g: finite and > 0", s->dt);
+  return check_quantiles(s->q, s->n_q);
+}
+
+}  // namespace
+
+extern "C" {
+
+int erpl_mc_corridor_defaults(erpl_corridor_spec* spec) {
+  NEED(spec);
+  memset(spec, 0, sizeof(*spec));
+  spec->n_channels = 3;
+  spec->channels[0] = ERPL_CH_Z; spec->channels[1] = ERPL_CH_DOWNRANGE; spec->channels[2] = ERPL_CH_SPEED;
+  spec->n_nodes = 256;
+  spec->t0 = 0.0; spec->dt = 1.0;
+  spec->n_q = 5;
+  const double q[5] = {0.05, 0.25, 0.5, 0.75, 0.95};   // erpl_mc_analysis_defaults
+  for (int j = 0; j < 5; ++j) spec->q[j] = q[j];
+  return ERPL_OK;
+}
+
+int erpl_mc_corridor_resample(erpl_ctx* c, const erpl_out* out, const erpl_corridor_spec* spec, double* values, int64_t ld,
+                              int64_t col0, void* stream) {
+  NEED(spec);
+  ERPL_TRY(check_corridor_spec(spec));
+  NEED(out);
+  if (out->n_traj < 0 || out->n_traj > 2147483647LL)
+    return erpl_fail(ERPL_ERR_INVALID, "n_traj = %lld out of range 0..2^31 - 1", (long long)out->n_traj);
+  if (col0 < 0) return erpl_fail(ERPL_ERR_INVALID, "col0 = %lld is negative", (long long)col0);
+  if (ld < out->n_traj || col0 > ld - out->n_traj)
+    return erpl_fail(ERPL_ERR_INVALID, "ld = %lld is below col0 + n_traj = %lld + %lld", (long long)ld, (long long)col0,
+                     (long long)out->n_traj);
+  NEED(values);
+  if (out->n_traj > 0) {
+    if (out->traj_cap < 1)
+      return erpl_fail(ERPL_ERR_INVALID, "traj_cap = %lld: at least one record per trajectory", (long long)out->traj_cap);
+    NEED_AS(out->traj, "traj"); NEED_AS(out->traj_len, "traj_len");
+  }
+  NEED_AS(c, "ctx");
+  if (out->n_traj == 0) return ERPL_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  ErplCorridorResampleArgs a;
+  memset(&a, 0, sizeof(a));
+  a.traj = out->traj; a.traj_len = out->traj_len; a.values = values;
+  a.n_traj = out->n_traj; a.traj_cap = out->traj_cap; a.ld = ld; a.col0 = col0;
+  a.n_channels = spec->n_channels; a.n_nodes = spec->n_nodes; a.hold = (spec->flags & ERPL_CORRIDOR_HOLD_END) ? 1 : 0;
+  for (int j = 0; j < spec->n_channels; ++j) a.channels[j] = spec->channels[j];
+  a.t0 = spec->t0; a.dt = spec->dt;
+  KERNEL_TRY(erpl_launch_corridor_resample(a, stream));
+  return ERPL_OK;
+}
+
+int erpl_mc_corridor_bands(erpl_ctx* c, const double* values, const uint8_t* mask, int64_t m, int64_t ld,
+                           const erpl_corridor_spec* spec, erpl_row_stats* bands, int64_t* n_counted, void* stream) {
+  NEED(spec);
+  ERPL_TRY(check_corridor_spec(spec));
+  if (m <= 0 || m > 2147483647LL) return erpl_fail(ERPL_ERR_INVALID, "m = %lld outside 1..2^31 - 1", (long long)m);
+  if (ld < m) return erpl_fail(ERPL_ERR_INVALID, "ld = %lld is below m = %lld", (long long)ld, (long long)m);
+  NEED(values); NEED(bands); NEED_AS(c, "ctx");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int rows = spec->n_channels * spec->n_nodes;
+  // one piece: a row record per (channel, node) and the record of the column count behind them
+  const size_t bytes = ((size_t)rows + 1) * sizeof(ErplAnaRow);
+  ERPL_TRY(c->corridor.grow(bytes));
+  ErplCorridorBandsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.values = values; a.mask = mask; a.out = (ErplAnaRow*)c->corridor.buf; a.m = m; a.ld = ld; a.rows = rows; a.n_q = spec->n_q;
+  for (int k = 0; k < spec->n_q; ++k) a.q[k] = spec->q[k];
+  KERNEL_TRY(erpl_launch_corridor_bands(a, stream));
+  std::vector<ErplAnaRow> h((size_t)rows + 1);
+  HIP_TRY(hipMemcpyAsync(h.data(), a.out, bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int r = 0; r < rows; ++r) finish_row_stats(h[(size_t)r], spec->q, spec->n_q, true, bands[r]);
+  if (n_counted) *n_counted = (int64_t)h[(size_t)rows].count;
   return ERPL_OK;
 }
 

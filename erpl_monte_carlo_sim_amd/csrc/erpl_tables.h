@@ -426,3 +426,31 @@ int erpl_launch_dens_pairs(const double* qry, int64_t queries, const double* src
 int erpl_launch_dens_peak(ErplDensWork* work, const double* density, int64_t nodes, void* stream);   // -> work->out.sum / peak / peak_at
 int erpl_launch_dens_fill_nan(double* row, int64_t n, void* stream);
 }
+
+// ---- erpl_mc_corridor_resample / erpl_mc_corridor_bands (erpl_corridor.hip) ----
+// Both kernels use workgroups of ERPL_ANA_BLOCK threads: one per trajectory (resample), one per row (c, k) of the matrix
+// (bands).  The bands kernel hands back one ErplAnaRow per row - what the passes of erpl_mc_analyze hand back for a row of
+// a summary, so the host finishes both the same way - and one more record behind them whose `count` is the number of
+// columns with mask byte 0.
+struct ErplCorridorResampleArgs {
+  const double* traj;        // [n_traj][traj_cap][ERPL_TRAJ_DIM]
+  const int64_t* traj_len;   // [n_traj]
+  double* values;            // [n_channels][n_nodes][ld]
+  int64_t n_traj, traj_cap, ld, col0;
+  int32_t n_channels, n_nodes, hold;
+  int32_t channels[ERPL_CORRIDOR_MAX_CHANNELS];
+  double t0, dt;
+};
+struct ErplCorridorBandsArgs {
+  const double* values;      // [rows][ld]
+  const uint8_t* mask;       // [m] or NULL
+  ErplAnaRow* out;           // [rows + 1]
+  int64_t m, ld;             // m < 2^31: the digit histograms are 32-bit LDS counters
+  int32_t rows, n_q;
+  double q[ERPL_ANALYSIS_MAX_Q];
+};
+extern "C++" {
+// Each enqueues one kernel on `stream` and returns a hipError_t (0 = launched).
+int erpl_launch_corridor_resample(const ErplCorridorResampleArgs& a, void* stream);   // 1 <= n_traj < 2^31
+int erpl_launch_corridor_bands(const ErplCorridorBandsArgs& a, void* stream);
+}

@@ -329,6 +329,99 @@ class TrajectoryEngine:
         self._call("erpl_mc_flight_envelope", C.byref(b), C.byref(o), C.c_void_p(env.data_ptr()), C.c_void_p(st.cuda_stream))
         return env
 
+    def corridor_spec(self, channels=None, nodes=None, t0=None, dt=None, hold=False, quantiles=None):
+        """The library's erpl_corridor_spec (erpl_mc_corridor_defaults: altitude, downrange, speed; 256 nodes 1 s apart
+        from 0; 5/25/50/75/95 %) with what is given overridden.  channels: _abi.CH_* indices."""
+        spec = self._defaults(_abi.ErplCorridorSpec, "erpl_mc_corridor_defaults")
+        if channels is not None:
+            channels = [int(c) for c in channels]
+            if not 1 <= len(channels) <= _abi.CORRIDOR_MAX_CHANNELS:
+                raise ValueError(f"1 to {_abi.CORRIDOR_MAX_CHANNELS} channels")
+            spec.n_channels = len(channels)
+            spec.channels[:len(channels)] = channels
+        if nodes is not None:
+            spec.n_nodes = int(nodes)
+        if t0 is not None:
+            spec.t0 = float(t0)
+        if dt is not None:
+            spec.dt = float(dt)
+        spec.flags = _abi.CORRIDOR_HOLD_END if hold else 0
+        if quantiles is not None:
+            quantiles = self._fractions(quantiles, _abi.ANALYSIS_MAX_Q, "quantiles")
+            spec.n_q = len(quantiles)
+            spec.q[:len(quantiles)] = quantiles
+        return spec
+
+    def corridor_resample(self, traj, traj_len, channels=None, nodes=None, t0=None, dt=None, hold=False, out=None, col0=0,
+                          stream=None):
+        """Captured trajectories onto one time grid (erpl_mc_corridor_resample; the definitions are in include/erpl_mc.h):
+        traj float64 [m, cap, 15] and traj_len int64 [m] are the capture of run(..., traj_ids=...) on the device;
+        channels _abi.CH_* (default altitude, downrange, speed), nodes / t0 / dt the grid t_k = t0 + k dt (default 256
+        nodes 1 s apart from 0); hold: a trajectory that ended keeps its last value behind its end instead of NaN.
+        Trajectory j fills column col0 + j of `out`, a float64 [C, T, ld] device tensor (default: a new one with ld = m,
+        NaN everywhere); the other columns are left alone.  Returns `out`; asynchronous on `stream` (default: the
+        current stream)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype == dtype and t.is_contiguous()
+        if not (ok(traj, torch.float64) and traj.dim() == 3 and traj.shape[2] == _abi.TRAJ_DIM):
+            raise ValueError(f"traj must be a contiguous float64 [m, cap, {_abi.TRAJ_DIM}] tensor on {self.device}")
+        m, cap = int(traj.shape[0]), int(traj.shape[1])
+        if not (ok(traj_len, torch.int64) and tuple(traj_len.shape) == (m,)):
+            raise ValueError(f"traj_len must be a contiguous int64 [m] tensor on {self.device}")
+        spec = self.corridor_spec(channels, nodes, t0, dt, hold)
+        shape = (spec.n_channels, spec.n_nodes)
+        col0 = int(col0)
+        if out is None:
+            out = torch.full(shape + (col0 + m,), float("nan"), dtype=torch.float64, device=self.device)
+        if not (ok(out, torch.float64) and out.dim() == 3 and tuple(out.shape[:2]) == shape):
+            raise ValueError(f"out must be a contiguous float64 [{shape[0]}, {shape[1]}, ld] tensor on {self.device}")
+        ld = int(out.shape[2])
+        if col0 < 0 or col0 + m > ld:
+            raise ValueError(f"columns {col0}..{col0 + m} do not fit ld = {ld}")
+        if m == 0:   # (an empty tensor has no address to hand over)
+            return out
+        o = _abi.ErplOut()
+        o.n_traj, o.traj_cap, o.traj, o.traj_len = m, cap, traj.data_ptr(), traj_len.data_ptr()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_corridor_resample", C.byref(o), C.byref(spec), C.c_void_p(out.data_ptr()), ld, col0,
+                   C.c_void_p(st.cuda_stream))
+        return out
+
+    def corridor_bands(self, values, mask=None, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), m=None):
+        """Every (channel, node) row of a resampled matrix described at once (erpl_mc_corridor_bands): values float64
+        [C, T, ld] on the device, of which the first m columns are read (default ld); mask uint8 [m] on the device, a
+        column counts iff its byte is 0 (the reason bits of `analyze`).  Enqueued on the current torch stream; blocks
+        the host until the result is there.  Returns a dict of NumPy arrays: 'count' int64 [C, T]; 'mean', 'std', 'min',
+        'max' float64 [C, T]; 'quantiles', 'order_lo', 'order_hi' float64 [C, n_q, T]; and 'q', 'n_counted'."""
+        if not (torch.is_tensor(values) and values.is_cuda and values.device == self.device and values.dtype == torch.float64
+                and values.dim() == 3 and values.is_contiguous()):
+            raise ValueError(f"values must be a contiguous float64 [C, T, ld] tensor on {self.device}")
+        n_ch, n_nodes, ld = (int(s) for s in values.shape)
+        m = ld if m is None else int(m)
+        if mask is not None and not (torch.is_tensor(mask) and mask.device == self.device and mask.dtype == torch.uint8
+                                     and tuple(mask.shape) == (m,) and mask.is_contiguous()):
+            raise ValueError(f"mask must be a contiguous uint8 [m] tensor on {self.device}")
+        if not 1 <= n_ch <= _abi.CORRIDOR_MAX_CHANNELS:
+            raise ValueError(f"1 to {_abi.CORRIDOR_MAX_CHANNELS} channels")
+        # (the bands look at the shape of the matrix alone: which channels its rows hold is the caller's knowledge)
+        spec = self.corridor_spec(range(n_ch), n_nodes, quantiles=quantiles)
+        nq = spec.n_q
+        rows = n_ch * n_nodes
+        bands = (_abi.ErplRowStats * rows)()
+        counted = C.c_int64(0)
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_corridor_bands", C.c_void_p(values.data_ptr()), C.c_void_p(mask.data_ptr()) if mask is not None else None,
+                   m, ld, C.byref(spec), C.cast(bands, C.c_void_p), C.byref(counted), C.c_void_p(st.cuda_stream))
+        # erpl_row_stats is 29 eight-byte words: count, mean, std, min, max, then three arrays of ANALYSIS_MAX_Q
+        raw = np.frombuffer(bands, dtype=np.float64).reshape(n_ch, n_nodes, 5 + 3 * _abi.ANALYSIS_MAX_Q)
+        Q = _abi.ANALYSIS_MAX_Q
+        out = {"count": np.frombuffer(bands, dtype=np.int64).reshape(n_ch, n_nodes, -1)[:, :, 0].copy(),
+               "mean": raw[:, :, 1].copy(), "std": raw[:, :, 2].copy(), "min": raw[:, :, 3].copy(), "max": raw[:, :, 4].copy()}
+        for k, name in enumerate(("quantiles", "order_lo", "order_hi")):
+            out[name] = np.ascontiguousarray(raw[:, :, 5 + k * Q: 5 + k * Q + nq].transpose(0, 2, 1))
+        out["q"] = list(spec.q[:nq])
+        out["n_counted"] = int(counted.value)
+        return out
+
     def analysis_defaults(self):
         """The reference's outlier bounds, rows and quantiles (erpl_mc_analysis_defaults)."""
         return self._defaults(_abi.ErplAnalysisSpec, "erpl_mc_analysis_defaults")

@@ -403,9 +403,33 @@ class MonteCarloAnalyzer:
         device with 'envelope_names' (analysis.ENVELOPE_NAMES, rows _abi.ENV_*), 'reasons' (uint8 [n], the outlier
         filter's reason bits), 'n_samples' / 'n_outliers' of that filter, 'statistics' (analysis.envelope_statistics
         over the samples that pass it) and 'performance'."""
+        envs = []
+        eng, summ, status, run = self._captured_run(
+            "flight_envelope", "envelopes", initial_conditions, n_samples, stride, seed, precision, planar, capture_bytes,
+            lambda eng, db, a, traj, tlen: envs.append(eng.flight_envelope(db, eng._keep, traj, tlen)))
+        env = envs[0] if len(envs) == 1 else torch.cat(envs, dim=1).contiguous()
+        torch.cuda.synchronize(eng.device)
+        t1 = time.time()
+        _, res, why = analysis._filter(summ, status, eng)
+        out = {"summary": summ, "status": status, "envelope": env, "envelope_names": list(analysis.ENVELOPE_NAMES),
+               "reasons": why, "n_samples": int(res.n_valid), "n_outliers": int(res.n_outliers),
+               "statistics": analysis.envelope_statistics(env, why, engine=eng)}
+        t2 = time.time()
+        out["performance"] = {"total_time": t2 - run["t0"], "capture_and_envelope_s": t1 - run["t0"], "statistics_s": t2 - t1,
+                              "precision": precision, "stride": run["stride"], "records_per_sample": run["cap"],
+                              "sub_batches": len(envs), "sub_batch_samples": run["per_batch"]}
+        return out
+
+    def _captured_run(self, who, what, initial_conditions, n_samples, stride, seed, precision, planar, capture_bytes, reduce):
+        """The capturing loop of `flight_envelope` and `trajectory_corridor`: the samples of run_monte_carlo_device (sub-batch
+        j from seed + rank + 1000003 * j) flown with every trajectory captured at every `stride`-th step, in sub-batches of
+        capture_bytes // (cap * 120) samples (at most DEVICE_CHUNK); `reduce(eng, db, first_sample, traj, traj_len)`
+        enqueues what the caller makes of a sub-batch's capture, and the capture buffer is released behind it.  One rank
+        only (`who` / `what` word the refusal).  Returns (engine, summary [16, n], status [n], {'t0', 'stride', 'cap',
+        'per_batch', 'sub_batches'}) once everything has run."""
         from . import sampling
         if dist.world()[1] > 1:
-            raise ValueError("flight_envelope is limited to a world size of 1: envelopes are not gathered across ranks")
+            raise ValueError(f"{who} is limited to a world size of 1: {what} are not gathered across ranks")
         n_samples, stride = int(n_samples), int(stride)
         if n_samples < 1 or stride < 1:
             raise ValueError("n_samples and stride must be at least 1")
@@ -418,7 +442,7 @@ class MonteCarloAnalyzer:
         per_batch = max(1, min(self.DEVICE_CHUNK, int(capture_bytes) // (cap * _abi.TRAJ_DIM * 8)))
         torch.cuda.synchronize(eng.device)
         t0 = time.time()
-        summs, stats, envs = [], [], []
+        summs, stats = [], []
         for j, a in enumerate(range(0, n_samples, per_batch)):
             nb = min(per_batch, n_samples - a)
             db = sampling.synthetic_dispersions(
@@ -427,24 +451,66 @@ class MonteCarloAnalyzer:
                 base_altitude_profile=self.base_altitude_profile, base_wind_profile=self.base_wind_profile,
                 planar=planar, engine=eng)
             summ, status, traj, tlen = eng.run(db, traj_ids=np.arange(nb), traj_stride=stride, traj_cap=cap)
-            envs.append(eng.flight_envelope(db, eng._keep, traj, tlen))
+            reduce(eng, db, a, traj, tlen)
             summs.append(summ)
             stats.append(status)
-            del traj, tlen, db   # (stream-ordered: the allocator hands the capture buffer on behind the envelope kernel)
+            del traj, tlen, db   # (stream-ordered: the allocator hands the capture buffer on behind the caller's kernel)
         eng.synchronize()        # host-blocking; raises if a lane hand-over timed out
         cat = lambda parts, dim: parts[0] if len(parts) == 1 else torch.cat(parts, dim=dim).contiguous()
-        summ, status, env = cat(summs, 1), cat(stats, 0), cat(envs, 1)
+        return eng, cat(summs, 1), cat(stats, 0), {"t0": t0, "stride": stride, "cap": cap, "per_batch": per_batch,
+                                                   "sub_batches": len(summs)}
+
+    def trajectory_corridor(self, initial_conditions, n_samples, stride=10, seed=1234, precision="f64_fast", planar=False,
+                            capture_bytes=4 << 30, nodes=256, t_end=None, channels=("z", "downrange", "speed"),
+                            quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), hold=True):
+        """Where the vehicle is at time t and how wide the spread is there, for a whole dispersion run: the samples of
+        `flight_envelope` (same draws, same sub-batches, every trajectory captured at every `stride`-th step) are brought
+        onto `nodes` time nodes from 0 to `t_end` (default max_time) on the device, each sub-batch into its window of
+        columns of one [C, T, n] matrix (TrajectoryEngine.corridor_resample; the capture is released behind the kernel),
+        and every (channel, node) row is described over the samples that pass the outlier filter by one
+        erpl_mc_corridor_bands call.  channels: names of analysis.CORRIDOR_CHANNEL_NAMES; hold: a flight that has ended
+        stays where it landed (its last record) instead of leaving the population - without it the bands behind the
+        first landing describe the flights still in the air.  Values between two records are linear interpolations of
+        the STORED records.  One rank only (ValueError before any work).
+
+        Returns the dict of analysis.trajectory_corridor ('time', 'q', 'channels', per channel 'count' / 'mean' / 'std' /
+        'min' / 'max' [T] and 'quantiles' [n_q, T]) plus 'summary', 'status', 'reasons', 'n_samples' / 'n_outliers' of the
+        filter, 'values' (the resampled matrix, on the device) and 'performance'."""
+        nodes = int(nodes)
+        if nodes < 2:
+            raise ValueError("at least 2 nodes")
+        t_end = float(self.max_time if t_end is None else t_end)
+        if not (np.isfinite(t_end) and t_end > 0.0):
+            raise ValueError("t_end must be finite and positive")
+        idx = analysis.corridor_channels(channels)
+        step = t_end / (nodes - 1)
+        box = {}
+
+        def resample(eng, db, a, traj, tlen):
+            if "values" not in box:
+                box["values"] = torch.full((len(idx), nodes, int(n_samples)), float("nan"), dtype=torch.float64,
+                                           device=eng.device)
+            eng.corridor_resample(traj, tlen, idx, nodes, 0.0, step, hold=hold, out=box["values"], col0=a)
+
+        eng, summ, status, run = self._captured_run("trajectory_corridor", "corridors", initial_conditions, n_samples,
+                                                    stride, seed, precision, planar, capture_bytes, resample)
         torch.cuda.synchronize(eng.device)
         t1 = time.time()
         _, res, why = analysis._filter(summ, status, eng)
-        out = {"summary": summ, "status": status, "envelope": env, "envelope_names": list(analysis.ENVELOPE_NAMES),
-               "reasons": why, "n_samples": int(res.n_valid), "n_outliers": int(res.n_outliers),
-               "statistics": analysis.envelope_statistics(env, why, engine=eng)}
+        out = analysis.trajectory_corridor(box["values"], idx, 0.0, step, quantiles=quantiles, mask=why, engine=eng)
         t2 = time.time()
-        out["performance"] = {"total_time": t2 - t0, "capture_and_envelope_s": t1 - t0, "statistics_s": t2 - t1,
-                              "precision": precision, "stride": stride, "records_per_sample": cap,
-                              "sub_batches": len(envs), "sub_batch_samples": per_batch}
+        out.update({"summary": summ, "status": status, "reasons": why, "values": box["values"],
+                    "n_samples": int(res.n_valid), "n_outliers": int(res.n_outliers)})
+        out["performance"] = {"total_time": t2 - run["t0"], "capture_and_resample_s": t1 - run["t0"], "bands_s": t2 - t1,
+                              "precision": precision, "stride": run["stride"], "records_per_sample": run["cap"],
+                              "sub_batches": run["sub_batches"], "sub_batch_samples": run["per_batch"]}
         return out
+
+    def plot_trajectory_corridor(self, corridor, save_plots=True):
+        """No reference counterpart: the corridor of `trajectory_corridor` - per channel the median, the outer and inner
+        quantile bands and the sample count over time - as monte_carlo_corridor.png in the output directory; returns that
+        directory."""
+        return plots.plot_trajectory_corridor(self, corridor, save_plots)
 
     def run_optimized_monte_carlo(self, initial_conditions, n_samples=1000, chunk_size=None):
         return self.run_monte_carlo(initial_conditions, n_samples, optimized=True)

@@ -231,6 +231,46 @@ def impact_probability_figure(result, launch_site=(0.0, 0.0)):
     return fig
 
 
+CORRIDOR_LABELS = {"x": "x (m)", "y": "y (m)", "z": "Altitude (m)", "downrange": "Downrange (m)", "vx": "vx (m/s)",
+                   "vy": "vy (m/s)", "vz": "vz (m/s)", "speed": "Speed (m/s)"}
+
+
+def corridor_figure(result):
+    """The flight corridor from the dict of analysis.trajectory_corridor: one panel per channel over time - the median line
+    (the quantile nearest 0.5), the band between the outermost pair of quantiles and, with four or more quantiles, the band
+    between the next pair inside it - and the number of samples behind every node on a twin axis."""
+    names = list(result["channels"])
+    q = np.asarray(result["q"], dtype=np.float64)
+    t = np.asarray(result["time"], dtype=np.float64)
+    fig = _figure((10, 3.2 * len(names) + 0.6))
+    axes = np.atleast_1d(fig.subplots(len(names), 1, sharex=True))
+    order = np.argsort(q)
+    mid = int(np.argmin(np.abs(q - 0.5))) if len(q) else None
+    for ax, name in zip(axes, names):
+        ch = result[name]
+        quant = np.asarray(ch["quantiles"], dtype=np.float64)
+        for depth, alpha in ((0, 0.2), (1, 0.35)):   # the outer pair, then the inner one
+            if len(q) >= 2 * (depth + 1):
+                lo, hi = order[depth], order[len(q) - 1 - depth]
+                ax.fill_between(t, quant[lo], quant[hi], alpha=alpha, color="tab:blue", linewidth=0,
+                                label=f"{100 * q[lo]:g} - {100 * q[hi]:g} %")
+        if mid is not None:
+            ax.plot(t, quant[mid], color="tab:blue", linewidth=1.5, label=f"{100 * q[mid]:g} %")
+        else:
+            ax.plot(t, np.asarray(ch["mean"], dtype=np.float64), color="tab:blue", linewidth=1.5, label="mean")
+        ax.set_ylabel(CORRIDOR_LABELS.get(name, name))
+        ax.grid(True, alpha=0.3)
+        twin = ax.twinx()
+        twin.plot(t, np.asarray(ch["count"]), color="gray", linewidth=0.8, linestyle=":")
+        twin.set_ylabel("Samples")
+        twin.set_ylim(bottom=0)
+    axes[0].set_title(f"Trajectory Corridor ({int(result.get('n_counted', 0))} samples)")
+    axes[0].legend(loc="best", fontsize=8)
+    axes[-1].set_xlabel("Time (s)")
+    fig.tight_layout()
+    return fig
+
+
 def save_figure(fig, output_dir, name):
     path = os.path.join(output_dir, name)
     fig.savefig(path, dpi=DPI, bbox_inches="tight")
@@ -372,6 +412,17 @@ def plot_impact_probability(analyzer, analysis, save_plots=True, zones=None, **k
         print(f"Impact probability plot saved to: {save_figure(fig, output_dir, 'monte_carlo_impact_probability.png')}")
         with open(os.path.join(output_dir, "impact_probability.json"), "w") as fh:
             json.dump(to_serializable(res), fh, indent=2)
+    return output_dir
+
+
+def plot_trajectory_corridor(analyzer, corridor, save_plots=True):
+    """The corridor of MonteCarloAnalyzer.trajectory_corridor (no reference counterpart) as monte_carlo_corridor.png;
+    returns the output directory (None without save_plots)."""
+    fig = corridor_figure(corridor)
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Trajectory corridor plot saved to: {save_figure(fig, output_dir, 'monte_carlo_corridor.png')}")
     return output_dir
 
 

@@ -823,6 +823,77 @@ int erpl_mc_impact_density(erpl_ctx* ctx, const double* summary, const uint8_t* 
                            const erpl_density_spec* spec, double* grid_x, double* grid_y, double* density,
                            erpl_density* result, double* sample_density, void* hip_stream);
 
+/* The trajectory corridor of a run ON THE DEVICE: where the vehicle is at time t and how wide the spread is there - the
+ * nominal trajectory with its quantile bands of altitude, downrange, speed, .. over time (the reference's
+ * plot_trajectory_cloud, monte_carlo.py, draws the first 50 result records as lines and says nothing about the rest).
+ * Two calls, because a large run is captured in sub-batches whose records are released at once:
+ * erpl_mc_corridor_resample brings the captured trajectories of one sub-batch onto ONE time grid, into a window of columns
+ * of a caller-owned matrix - n_channels * n_nodes * 8 bytes per trajectory against traj_cap * 120 bytes of records - and
+ * erpl_mc_corridor_bands, once at the end, describes every (channel, node) row of that matrix.
+ *
+ * The grid: node k lies at t_k = t0 + (double)k * dt (two roundings), k < n_nodes.  The channels of a record rec[15]
+ * (absolute time, x y z, vx vy vz, ..): the state entry itself for ERPL_CH_X / _Y / _Z / _VX / _VY / _VZ,
+ * sqrt(x*x + y*y) for ERPL_CH_DOWNRANGE, sqrt((vx*vx + vy*vy) + vz*vz) for ERPL_CH_SPEED.
+ *
+ * erpl_mc_corridor_resample.  `out` is the erpl_out of the capturing run: n_traj, traj_cap, traj and traj_len are read;
+ * traj_ids, summary, status and traj_stride are not (no batch and no config: the channels are functions of the record
+ * alone).  `values` is CALLER-OWNED device memory, double [n_channels][n_nodes][ld]; trajectory j writes the elements
+ * (c, k, col0 + j), c < n_channels, k < n_nodes; columns outside [col0, col0 + n_traj) are not touched.  Asynchronous on
+ * `hip_stream` like erpl_mc_flight_envelope: no workspace, no host result, no host wait.  Per trajectory:
+ *   len = traj_len[j] clamped to [0, traj_cap]; usable prefix u = the index of the first record r < len with a non-finite
+ *     time or state entry, len if there is none (erpl_mc_flight_envelope's); ts(r) = rec[r][0] - rec[0][0].
+ *   The value at node k is NaN if u == 0, t_k < 0 or t_k > ts(u - 1) - except that with ERPL_CORRIDOR_HOLD_END in
+ *     spec->flags and u == len a node with t_k > ts(u - 1) takes the channel value of record u - 1 (the vehicle lies where
+ *     it landed; a trajectory cut off by a non-finite record never holds).
+ *   Otherwise r = the largest index < u with ts(r) <= t_k, by bisection (lo = 0, hi = u; mid = lo + (hi - lo) / 2 goes to
+ *     lo if ts(mid) <= t_k, else to hi, until hi - lo == 1; r = lo): time stamps are trusted to increase, and whatever
+ *     they hold the search never leaves [0, u).  r == u - 1: the value is ch(r) exactly.  Otherwise
+ *     w = (t_k - ts(r)) / (ts(r + 1) - ts(r)) and the value is ch(r) + (ch(r + 1) - ch(r)) * w: IEEE division, no
+ *     contraction, this order - the channel is evaluated at the two records, then interpolated.
+ *   The bytes of a column depend on its own trajectory and the spec alone.
+ *
+ * erpl_mc_corridor_bands.  Row (c, k) is the m doubles at values + (c * n_nodes + k) * ld (ld >= m: the padding is not
+ * read).  `mask` is [m] caller-owned device bytes - the `reasons` of erpl_mc_analyze when every sample was captured - a
+ * column counts iff its byte is 0; NULL: every column counts.  bands (host, [n_channels * n_nodes]): bands[c * n_nodes +
+ * k] describes the counted FINITE values of row (c, k) exactly as erpl_mc_analyze describes a row of a summary: count,
+ * mean = sum / count, population std in two passes, min, max, order_lo / order_hi exact, quantile linear; count == 0:
+ * every double of the record is NaN.  n_counted (host, may be NULL) receives the number of columns with mask byte 0.
+ * Blocks the host on `hip_stream` like erpl_mc_analyze; the workspace ((n_channels * n_nodes + 1) row records of 176
+ * bytes) belongs to the context, grows only and is freed by erpl_mc_destroy.
+ * Reduction order: one workgroup of 256 threads per row; thread t accumulates the values t, t + 256, .. of the row in
+ * index order; then a wave folds with a shuffle-down tree over the offsets 32 .. 1 and thread 0 folds the four waves in
+ * order (the fixed-order fold of every statistics call).  The order depends on m alone; there are no floating-point
+ * atomics (the digit histograms of the selection are integer LDS counters): two calls return the same bytes.
+ *
+ * Errors: ERPL_ERR_INVALID, before any device work and with a message that names the argument, in this order:
+ *   both calls: NULL spec; n_channels outside 1..8; a channel outside 0..ERPL_CH_COUNT - 1 or listed twice; n_nodes outside
+ *     1..ERPL_CORRIDOR_MAX_NODES; a flag other than ERPL_CORRIDOR_HOLD_END; t0 not finite; dt not finite or <= 0; n_q outside
+ *     0..ERPL_ANALYSIS_MAX_Q; a q outside [0, 1] or NaN (reserved is not looked at);
+ *   resample, then: NULL out; n_traj < 0 or >= 2^31; col0 < 0; ld < col0 + n_traj; NULL values; with n_traj > 0:
+ *     traj_cap < 1, NULL traj, NULL traj_len; the context last.  n_traj == 0 is a no-op that returns ERPL_OK.
+ *   bands, then: m <= 0 or >= 2^31 (32-bit digit counters); ld < m; NULL values; NULL bands; the context last. */
+#define ERPL_CORRIDOR_MAX_CHANNELS 8
+#define ERPL_CORRIDOR_MAX_NODES 4096
+enum { ERPL_CH_X = 0, ERPL_CH_Y = 1, ERPL_CH_Z = 2, ERPL_CH_DOWNRANGE = 3,
+       ERPL_CH_VX = 4, ERPL_CH_VY = 5, ERPL_CH_VZ = 6, ERPL_CH_SPEED = 7, ERPL_CH_COUNT = 8 };
+enum { ERPL_CORRIDOR_HOLD_END = 1 };   /* spec.flags */
+typedef struct erpl_corridor_spec {
+  int32_t n_channels;                    /* 1..ERPL_CORRIDOR_MAX_CHANNELS */
+  int32_t channels[ERPL_CORRIDOR_MAX_CHANNELS];   /* distinct, 0..ERPL_CH_COUNT - 1 */
+  int32_t n_nodes;                       /* 1..ERPL_CORRIDOR_MAX_NODES */
+  int32_t flags;                         /* ERPL_CORRIDOR_HOLD_END or 0 */
+  double t0, dt;                         /* finite, dt > 0 */
+  int32_t n_q;                           /* 0..ERPL_ANALYSIS_MAX_Q */
+  int32_t reserved;
+  double q[ERPL_ANALYSIS_MAX_Q];         /* quantile fractions in [0, 1] */
+} erpl_corridor_spec;
+/* Host only: channels {Z, DOWNRANGE, SPEED}, 256 nodes, t0 = 0, dt = 1 s, no flags, q {0.05, 0.25, 0.5, 0.75, 0.95}. */
+int erpl_mc_corridor_defaults(erpl_corridor_spec* spec);
+int erpl_mc_corridor_resample(erpl_ctx* ctx, const erpl_out* out, const erpl_corridor_spec* spec, double* values,
+                              int64_t ld, int64_t col0, void* hip_stream);
+int erpl_mc_corridor_bands(erpl_ctx* ctx, const double* values, const uint8_t* mask, int64_t m, int64_t ld,
+                           const erpl_corridor_spec* spec, erpl_row_stats* bands, int64_t* n_counted, void* hip_stream);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
