@@ -266,6 +266,30 @@ class ErplCorridorSpec(C.Structure):
                 ("n_q", C.c_int32), ("reserved", C.c_int32), ("q", _Q)]
 
 
+# erpl_mc_sobol
+SOBOL_MAX_FACTORS = 32
+SOBOL_MAX_ROWS = 4
+SOBOL_ROW_EXTRA = 16
+SOBOL_MAX_REPLICATES = 65536
+SOBOL_MAX_STATS = SOBOL_MAX_ROWS * (2 + 2 * SOBOL_MAX_FACTORS)
+
+
+class ErplSobolSpec(C.Structure):
+    _fields_ = [("n_factors", C.c_int32), ("n_rows", C.c_int32), ("rows", C.c_int32 * SOBOL_MAX_ROWS),
+                ("replicates", C.c_int32), ("reserved", C.c_int32), ("level", C.c_double), ("seed", C.c_uint64)]
+
+
+class ErplSobolRow(C.Structure):
+    _fields_ = [("count", C.c_int64), ("n_masked", C.c_int64), ("n_non_finite", C.c_int64),
+                ("constant", C.c_int32), ("reserved", C.c_int32), ("mean", ErplBootStat), ("variance", ErplBootStat),
+                ("first", ErplBootStat * SOBOL_MAX_FACTORS), ("total", ErplBootStat * SOBOL_MAX_FACTORS)]
+
+
+class ErplSobol(C.Structure):
+    _fields_ = [("n_base", C.c_int64), ("n_factors", C.c_int32), ("n_rows", C.c_int32), ("replicates", C.c_int32),
+                ("n_stats", C.c_int32), ("row", ErplSobolRow * SOBOL_MAX_ROWS)]
+
+
 LIB_NAME = "liberpl_mc.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
@@ -288,6 +312,7 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_bootstrap_defaults", "erpl_mc_bootstrap", "erpl_mc_bootstrap_indices",
            "erpl_mc_impact_density_defaults", "erpl_mc_impact_density",
            "erpl_mc_corridor_defaults", "erpl_mc_corridor_resample", "erpl_mc_corridor_bands",
+           "erpl_mc_sobol_defaults", "erpl_mc_sobol",
            "erpl_mc_legacy_random_streams_device", "erpl_mc_legacy_wind_profiles_device")
 
 _lib = None
@@ -380,6 +405,9 @@ def load_library(path=None):
                                               C.c_int64, C.c_void_p]
     lib.erpl_mc_corridor_bands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(ErplCorridorSpec),
                                            C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
+    lib.erpl_mc_sobol_defaults.argtypes = [C.POINTER(ErplSobolSpec)]
+    lib.erpl_mc_sobol.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(ErplSobolSpec),
+                                  C.POINTER(ErplSobol), C.c_void_p, C.c_void_p]
     lib.erpl_mc_legacy_random_streams_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                                          C.c_int32, C.c_void_p]
     lib.erpl_mc_legacy_wind_profiles_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 9 + \

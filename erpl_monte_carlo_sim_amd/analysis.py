@@ -492,3 +492,39 @@ def cep_interval(summary, status=None, engine=None, target=None, quantiles=(0.5,
     return {"cep": qs[quantiles.index(0.5)] if 0.5 in quantiles else None, "quantiles": qs, "mean": _interval(s["mean"]),
             "std": _interval(s["std"]), "q": quantiles, "count": b["count"], "n_samples": int(res.n_valid),
             "n_outliers": int(res.n_outliers), "level": b["level"], "replicates": b["replicates"], "seed": b["seed"]}
+
+
+# ---------------------------------------------------------------------------------- variance-based sensitivity
+def rank_total_effects(total, group_names):
+    """For every row of `total` ([R, k] total-effect indices) the group names by ST descending, NaN last, ties and the NaN
+    ones in group order."""
+    total = np.asarray(total, dtype=np.float64)
+    out = []
+    for j in range(total.shape[0]):
+        key = np.where(np.isnan(total[j]), -np.inf, total[j])
+        out.append([group_names[f] for f in np.argsort(-key, kind="stable")])
+    return out
+
+
+def sobol_indices(summary, n_base, group_names, mask=None, engine=None, rows=None, extra=None, replicates=1000, level=0.95,
+                  seed=0):
+    """First-order and total-effect Sobol indices of a pick-freeze run, on the device (TrajectoryEngine.sobol,
+    erpl_mc_sobol): `summary` is the float64 [16, (k + 2) n_base] device tensor of the design flown block by block - A, B,
+    then A with group i taken from B for every name of `group_names` (MonteCarloAnalyzer.sobol_indices flies it).  mask:
+    uint8 [n_base] device tensor, byte 0 = the design row counts.  Returns the engine's dict plus 'group_names',
+    'row_names', 'ranking' (per row the group names by total effect descending, NaN last), 'sum_first' ([R], the sum of
+    the first-order estimates) and 'interaction' = 1 - sum_first: the share of the variance no factor explains alone.
+
+    Reading it: first[i] is the share of the output's variance that fixing group i alone would remove, total[i] the share
+    that remains while everything BUT group i is fixed - interactions included, which no regression coefficient sees.
+    total = 0 exactly: the group does not reach the output at all."""
+    engine = _engine_of(summary, engine)
+    group_names = [str(g) for g in group_names]
+    out = engine.sobol(summary, n_base, len(group_names), mask=mask, rows=rows, extra=extra, replicates=replicates,
+                       level=level, seed=seed)
+    out["group_names"] = group_names
+    out["row_names"] = ["extra" if r >= len(ROW_NAMES) else ROW_NAMES[r] for r in out["rows"]]
+    out["ranking"] = rank_total_effects(out["total"]["estimate"], group_names)
+    out["sum_first"] = out["first"]["estimate"].sum(axis=1)
+    out["interaction"] = 1.0 - out["sum_first"]
+    return out

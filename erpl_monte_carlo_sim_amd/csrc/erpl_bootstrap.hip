@@ -224,6 +224,12 @@ int erpl_boot_temp_bytes(int64_t n, size_t* bytes) {
   return 0;
 }
 
+int erpl_boot_select_bytes(int64_t n, size_t* bytes) {
+  return (int)rocprim::select(nullptr, *bytes, rocprim::counting_iterator<uint32_t>(0u),
+                              rocprim::make_transform_iterator((const uint8_t*)nullptr, InPopulation()), (uint32_t*)nullptr,
+                              (unsigned long long*)nullptr, (size_t)n, (hipStream_t)0);
+}
+
 int erpl_launch_boot_compact(const ErplBootPrep& p, void* stream) {
   size_t bytes = p.temp_bytes;
   return (int)rocprim::select(p.temp, bytes, rocprim::counting_iterator<uint32_t>(0u),

@@ -66,6 +66,15 @@ struct DensHost {
   ErplDensIn in;
 };
 
+// erpl_mc_sobol: pinned copies of what its launches hand back - per row the population counters and the extremes of the
+// blocks A and B (erpl_launch_corr_population), the sums of the estimates and the summary over the replicates
+struct SobolHost {
+  unsigned long long counter[ERPL_SOBOL_MAX_ROWS][4];
+  double vmin[ERPL_SOBOL_MAX_ROWS][2], vmax[ERPL_SOBOL_MAX_ROWS][2];
+  ErplSobolOut out;
+  ErplAnaRow bands[ERPL_SOBOL_MAX_STATS + 1];
+};
+
 // The only place a per-context device buffer grows (the policy of erpl_mc_reserve): never shrinks, freed by
 // erpl_mc_destroy.  An earlier call on another stream may still read the old buffer, hence the device synchronise.
 template <typename T>
@@ -177,7 +186,7 @@ struct erpl_ctx {
   // The statistics units (ErplStatUnit above) and what grows in each.  erpl_mc_analyze: one reason byte per sample, also the
   // row of zero bytes that stands in for a mask.  erpl_mc_histogram / _histogram_xy / _dispersion: the miss distance, one
   // double per sample, when the caller keeps none.  erpl_mc_correlation, erpl_mc_bootstrap (no device block of its own: it
-  // runs on those of `corr` and `ana`) and erpl_mc_impact_density: the pieces of erpl_stat_layout.h.
+  // runs on those of `corr` and `ana`), erpl_mc_impact_density and erpl_mc_sobol: the pieces of erpl_stat_layout.h.
   ErplStatUnit<ErplAnaWork, ErplAnaResult> ana;
   ErplStatUnit<ErplDistWork, DistHost> dist;
   ErplStatUnit<ErplCorrWork, ErplCorrOut> corr;
@@ -185,6 +194,9 @@ struct erpl_ctx {
   ErplStatUnit<ErplDensWork, DensHost> dens;
   // erpl_mc_corridor_bands: the row records its kernel hands back, nothing else (no fixed block, no pinned mirror)
   ErplStatUnit<void, char> corridor;
+  // erpl_mc_sobol: the partial sums of its estimates and the row records of its summary in the fixed block, the pieces of
+  // erpl_stat_layout.h in the buffer; its population pass runs on the block of `corr`
+  ErplStatUnit<ErplSobolWork, SobolHost> sobol;
   // erpl_mc_legacy_random_streams_device / _wind_profiles_device: one device buffer (flag, op tables, knot constants, the
   // MT19937 states of a tile and two sets of its accepted pairs) and its pinned staging (the tables on their way up, r2
   // down and f up, per set), both bounded by the tile; an event per set behind the tile's copy to the host

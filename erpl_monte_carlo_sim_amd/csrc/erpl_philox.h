@@ -1,5 +1,6 @@
-// erpl_philox.h — the draws of erpl_mc_bootstrap, one definition for the host (erpl_mc_bootstrap_indices) and the device
-// (erpl_boot_replicate in erpl_bootstrap.hip).  Internal: never installed.
+// erpl_philox.h — the draws of erpl_mc_bootstrap and erpl_mc_sobol, one definition for the host (erpl_mc_bootstrap_indices)
+// and the device (erpl_boot_replicate in erpl_bootstrap.hip, erpl_sobol_replicate in erpl_sobol.hip).  Internal: never
+// installed.
 //
 // The generator is Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC 2011):
 // ten rounds of two 32 x 32 -> 64 bit multiplies (0xD2511F53, 0xCD9E8D57), the key bumped by (0x9E3779B9, 0xBB67AE85)

@@ -1,5 +1,5 @@
-// erpl_stat_layout.h — how erpl_mc_correlation, erpl_mc_bootstrap and erpl_mc_impact_density cut the device buffer each of
-// them grows into pieces: pure functions of the call's sizes (no HIP; the scratch size of the rocPRIM calls comes in as a
+// erpl_stat_layout.h — how erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density and erpl_mc_sobol cut the device
+// buffer each of them grows into pieces: pure functions of the call's sizes (no HIP; the scratch size of the rocPRIM calls comes in as a
 // number), so that tests/test_stat_layout.py checks every offset on the CPU, through erpl_stat_layout_table, before a kernel
 // writes through one.  Every piece starts at a multiple of 256 bytes; `need` is the end of the last one.
 #pragma once
@@ -86,6 +86,27 @@ inline ErplDensLayout erpl_dens_layout(int64_t n, int64_t nodes, bool want_sampl
   l.row = c.take(want_samples && !caller_keeps_row ? 8 * un : 0);
   const size_t queries = want_samples && un > un_nodes ? un : un_nodes;
   l.part = c.take(8 * ((size_t)ERPL_DENS_TARGET_BLOCKS * ERPL_DENS_TILE + queries));
+  l.need = c.end;
+  return l;
+}
+
+// erpl_mc_sobol over n design rows, k factors, R output rows: [pop R rows of n bytes, row r at pop + r n][src R rows of n u32]
+// [counts R u64][rec R rows of n (k + 2) doubles][scratch of the select][replicates R (2 + 2 k) B doubles unless the caller
+// keeps them]
+struct ErplSobolLayout {
+  size_t pop, src[ERPL_SOBOL_MAX_ROWS], count, rec[ERPL_SOBOL_MAX_ROWS], temp, rep, temp_bytes, need;
+};
+inline ErplSobolLayout erpl_sobol_layout(int64_t n, int k, int R, int B, bool caller_keeps_replicates, size_t temp_bytes) {
+  const size_t un = (size_t)n, uB = (size_t)B, uk = (size_t)k, uR = (size_t)R;
+  ErplCarve c;
+  ErplSobolLayout l = {};
+  l.pop = c.take(uR * un);
+  for (int j = 0; j < R; ++j) l.src[j] = c.take(4 * un);
+  l.count = c.take(8 * uR);
+  for (int j = 0; j < R; ++j) l.rec[j] = c.take(8 * un * (uk + 2));
+  l.temp_bytes = erpl_scratch_piece(temp_bytes);
+  l.temp = c.take(l.temp_bytes);
+  l.rep = c.take(caller_keeps_replicates ? 0 : 8 * uB * uR * (2 + 2 * uk));
   l.need = c.end;
   return l;
 }

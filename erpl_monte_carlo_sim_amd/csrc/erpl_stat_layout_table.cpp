@@ -5,6 +5,7 @@
 //   boot <n> <R> <n_stats> <B> <caller_keeps_replicates> <temp_bytes>    -> pop src count x[R] sorted[R] pos[R] keys idx temp zero
 //                                                                           rep temp_bytes need
 //   dens <n> <nodes> <want_samples> <caller_keeps_row> <temp_bytes>      -> pop src count temp pts nodes dens row part temp_bytes need
+//   sobol <n> <k> <R> <B> <caller_keeps_replicates> <temp_bytes>         -> pop src[R] count rec[R] temp rep temp_bytes need
 #include <stdio.h>
 
 #include <initializer_list>
@@ -33,6 +34,14 @@ int main() {
     } else if (sscanf(line, "dens %lld %lld %d %d %zu", &n, &nodes, &a, &b, &temp) == 5) {
       const ErplDensLayout l = erpl_dens_layout(n, nodes, a != 0, b != 0, temp);
       for (size_t v : {l.pop, l.src, l.count, l.temp, l.pts, l.nodes, l.dens, l.row, l.part, l.temp_bytes}) put(v);
+      put(l.need, "\n");
+    } else if (sscanf(line, "sobol %lld %d %d %d %d %zu", &n, &a, &b, &c, &d, &temp) == 6 && b >= 1 && b <= ERPL_SOBOL_MAX_ROWS) {
+      const ErplSobolLayout l = erpl_sobol_layout(n, a, b, c, d != 0, temp);
+      put(l.pop);
+      for (int j = 0; j < b; ++j) put(l.src[j]);
+      put(l.count);
+      for (int j = 0; j < b; ++j) put(l.rec[j]);
+      for (size_t v : {l.temp, l.rep, l.temp_bytes}) put(v);
       put(l.need, "\n");
     } else {
       fprintf(stderr, "bad request: %s", line);

@@ -1,7 +1,8 @@
 // erpl_stats_api.hip — host halves of the analysis entry points of the C ABI (include/erpl_mc.h): erpl_mc_analyze,
 // erpl_mc_histogram, erpl_mc_histogram_xy, erpl_mc_dispersion, erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density,
-// erpl_mc_corridor_resample, erpl_mc_corridor_bands and their defaults.  Argument checks, workspace, launches
-// (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip, erpl_bootstrap.hip, erpl_density.hip, erpl_corridor.hip)
+// erpl_mc_corridor_resample, erpl_mc_corridor_bands, erpl_mc_sobol and their defaults.  Argument checks, workspace, launches
+// (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip, erpl_bootstrap.hip, erpl_density.hip, erpl_corridor.hip,
+// erpl_sobol.hip)
 // and what the host finishes in double precision.  The refusals come in one order
 // everywhere - spec fields, n, pointers, context (erpl_mc_bootstrap: the order its header comment lists) - and need no
 // device; tests/golden/stats_refusals.json pins their texts.  What the entry points share comes first: the pieces of the
@@ -1046,6 +1047,150 @@ int erpl_mc_corridor_bands(erpl_ctx* c, const double* values, const uint8_t* mas
   HIP_TRY(hipStreamSynchronize(st));
   for (int r = 0; r < rows; ++r) finish_row_stats(h[(size_t)r], spec->q, spec->n_q, true, bands[r]);
   if (n_counted) *n_counted = (int64_t)h[(size_t)rows].count;
+  return ERPL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------- erpl_mc_sobol
+extern "C" {
+
+int erpl_mc_sobol_defaults(erpl_sobol_spec* spec) {
+  NEED(spec);
+  memset(spec, 0, sizeof(*spec));
+  spec->n_rows = 3;   // outputs every flight has, tumbling or not
+  spec->rows[0] = ERPL_SUM_FIRST_APOGEE_ALT; spec->rows[1] = ERPL_SUM_FIRST_APOGEE_TIME; spec->rows[2] = ERPL_SUM_RAIL_EXIT_SPEED;
+  spec->replicates = 1000;
+  spec->level = 0.95;
+  spec->seed = 0;
+  return ERPL_OK;
+}
+
+int erpl_mc_sobol(erpl_ctx* c, const double* summary, const double* extra, const uint8_t* mask, int64_t n_base, int64_t ld,
+                  const erpl_sobol_spec* spec, erpl_sobol* result, double* replicates_out, void* stream) {
+  NEED(spec); NEED(summary); NEED(result);
+  if (n_base <= 0) return erpl_fail(ERPL_ERR_INVALID, "n_base = %lld: need at least one design row", (long long)n_base);
+  ERPL_TRY(check_int(spec->n_factors, "n_factors", -1, 1, ERPL_SOBOL_MAX_FACTORS));
+  const int k = spec->n_factors;
+  if (n_base >= ((1ll << 31) + k + 1) / (k + 2))   // (k + 2) n_base >= 2^31, without the product
+    return erpl_fail(ERPL_ERR_INVALID, "(spec->n_factors + 2) * n_base = %d * %lld is 2^31 or more: the records carry 31-bit indices",
+                     k + 2, (long long)n_base);
+  const int64_t flights = (int64_t)(k + 2) * n_base;
+  if (ld < flights)
+    return erpl_fail(ERPL_ERR_INVALID, "ld = %lld is below (spec->n_factors + 2) * n_base = %lld", (long long)ld, (long long)flights);
+  ERPL_TRY(check_row_list(spec->rows, spec->n_rows, 1, ERPL_SOBOL_MAX_ROWS, ERPL_SOBOL_ROW_EXTRA));
+  for (int j = 0; j < spec->n_rows; ++j)
+    if (spec->rows[j] == ERPL_SOBOL_ROW_EXTRA && !extra)
+      return erpl_fail(ERPL_ERR_INVALID, "extra is NULL but spec->rows[%d] = %d (ERPL_SOBOL_ROW_EXTRA)", j, spec->rows[j]);
+  ERPL_TRY(check_int(spec->replicates, "replicates", -1, 0, ERPL_SOBOL_MAX_REPLICATES));
+  if (replicates_out && spec->replicates == 0) return erpl_fail(ERPL_ERR_INVALID, "replicates_out is given but spec->replicates = 0");
+  if (spec->replicates > 0 && !(spec->level > 0.0 && spec->level < 1.0))
+    return erpl_fail(ERPL_ERR_INVALID, "spec->level = %g outside (0, 1)", spec->level);
+  NEED_AS(c, "ctx");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int R = spec->n_rows, ns = 2 + 2 * k, n_stats = R * ns, B = spec->replicates;
+  const size_t un = (size_t)n_base, uB = (size_t)B;
+
+  size_t temp_bytes = 0;
+  LAUNCH_TRY(erpl_boot_select_bytes(n_base, &temp_bytes), "select sizing failed");
+  const ErplSobolLayout at = erpl_sobol_layout(n_base, k, R, B, replicates_out != nullptr, temp_bytes);
+  ERPL_TRY(c->corr.first_use());   // the population pass and its counters
+  ERPL_TRY(c->sobol.first_use());
+  ERPL_TRY(c->sobol.grow(at.need));
+  char* buf = c->sobol.buf;
+  SobolHost& h = *c->sobol.host;
+
+  ErplSobolArgs a;
+  memset(&a, 0, sizeof(a));
+  a.work = c->sobol.work; a.rep = replicates_out ? replicates_out : (double*)(buf + at.rep);
+  a.seed = spec->seed; a.n_base = n_base; a.n_rows = R; a.k = k; a.replicates = B;
+  // per row: the population bytes, its counters and the extremes of the blocks A and B, then the select
+  for (int j = 0; j < R; ++j) {
+    a.var[j] = spec->rows[j] == ERPL_SOBOL_ROW_EXTRA ? extra : summary + (size_t)spec->rows[j] * (size_t)ld;
+    a.src[j] = (uint32_t*)(buf + at.src[j]);
+    a.rec[j] = (double*)(buf + at.rec[j]);
+    ErplCorrArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.mask = mask; pa.n = n_base; pa.n_vars = k + 2; pa.work = c->corr.work; pa.pop = (uint8_t*)(buf + at.pop) + (size_t)j * un;
+    for (int b = 0; b < k + 2; ++b) pa.var[b] = a.var[j] + (size_t)b * un;
+    KERNEL_TRY(erpl_launch_corr_population(pa, stream));
+    HIP_TRY(hipMemcpyAsync(h.counter[j], &c->corr.work->out.counter[0], sizeof(h.counter[j]), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h.vmin[j], &c->corr.work->out.vmin[0], sizeof(h.vmin[j]), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h.vmax[j], &c->corr.work->out.vmax[0], sizeof(h.vmax[j]), hipMemcpyDeviceToHost, st));
+    ErplBootPrep p;
+    memset(&p, 0, sizeof(p));
+    p.pop = pa.pop; p.src = (uint32_t*)(buf + at.src[j]); p.count = (unsigned long long*)(buf + at.count) + j;
+    p.temp = buf + at.temp; p.temp_bytes = at.temp_bytes; p.n = n_base;
+    LAUNCH_TRY(erpl_launch_boot_compact(p, stream), "select failed");
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+
+  const double nan = NAN;
+  memset(result, 0, sizeof(*result));
+  result->n_base = n_base; result->n_factors = k; result->n_rows = R; result->replicates = B; result->n_stats = n_stats;
+  for (int j = 0; j < ERPL_SOBOL_MAX_ROWS; ++j) {
+    erpl_sobol_row& o = result->row[j];
+    erpl_boot_stat* stats = &o.mean;   // mean, variance, first[], total[]: one run of erpl_boot_stat
+    for (int s = 0; s < 2 + 2 * ERPL_SOBOL_MAX_FACTORS; ++s) {
+      stats[s].estimate = stats[s].rep_mean = stats[s].se = stats[s].lo = stats[s].hi = nan;
+      stats[s].finite = 0;
+    }
+    if (j >= R) continue;
+    o.count = (int64_t)h.counter[j][0]; o.n_masked = (int64_t)h.counter[j][1]; o.n_non_finite = (int64_t)h.counter[j][2];
+    a.m[j] = (uint32_t)h.counter[j][0];
+  }
+
+  KERNEL_TRY(erpl_launch_sobol_records(a, stream));
+  KERNEL_TRY(erpl_launch_sobol_estimates(a, stream));
+  HIP_TRY(hipMemcpyAsync(&h.out, &c->sobol.work->out, sizeof(ErplSobolOut), hipMemcpyDeviceToHost, st));
+  if (B > 0) {
+    KERNEL_TRY(erpl_launch_sobol_replicates(a, stream));
+    // the summary over the replicates: the [n_stats][B] matrix as rows of length B through the one-launch row kernel
+    const double tail = (1.0 - spec->level) / 2;
+    ErplCorridorBandsArgs g;
+    memset(&g, 0, sizeof(g));
+    g.values = a.rep; g.out = c->sobol.work->bands; g.m = B; g.ld = B; g.rows = n_stats; g.n_q = 2;
+    g.q[0] = tail; g.q[1] = 1.0 - tail;
+    KERNEL_TRY(erpl_launch_corridor_bands(g, stream));
+    HIP_TRY(hipMemcpyAsync(h.bands, c->sobol.work->bands, (size_t)n_stats * sizeof(ErplAnaRow), hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+
+  const double tail = (1.0 - spec->level) / 2, interval[2] = {tail, 1.0 - tail};
+  for (int j = 0; j < R; ++j) {
+    erpl_sobol_row& o = result->row[j];
+    erpl_boot_stat* stats = &o.mean;
+    const bool any = o.count > 0;
+    const double dm = (double)o.count, dm2 = 2.0 * dm;
+    const double lo = fmin(h.vmin[j][0], h.vmin[j][1]), hi = fmax(h.vmax[j][0], h.vmax[j][1]);
+    o.constant = any && lo == hi ? 1 : 0;
+    if (any) {
+      const double* sum = h.out.sum[j];
+      const double V = o.constant ? 0.0 : sum[1] / dm2;
+      const bool flat = o.constant || V == 0.0;
+      stats[0].estimate = h.out.f0[j];
+      stats[1].estimate = V;
+      for (int i = 0; i < k; ++i) {
+        stats[2 + i].estimate = flat ? nan : (sum[2 + i] / dm) / V;
+        stats[2 + ERPL_SOBOL_MAX_FACTORS + i].estimate = flat ? nan : (sum[2 + k + i] / dm2) / V;
+      }
+    }
+    if (B == 0) continue;
+    for (int s = 0; s < ns; ++s) {   // statistic s of the matrix -> its place in the row (total[] starts behind first[32])
+      erpl_boot_stat& t = stats[s < 2 + k ? s : s - k + ERPL_SOBOL_MAX_FACTORS];
+      const ErplAnaRow& row = h.bands[j * ns + s];
+      erpl_row_stats over;
+      finish_row_stats(row, interval, 2, true, over);
+      t.finite = over.count;
+      // the constant rule of erpl_mc_bootstrap: a statistic with min == max over its replicates has no spread
+      const bool same = over.count > 0 && row.vmin == row.vmax;
+      t.rep_mean = same ? row.vmin : over.mean;
+      t.se = over.count == 0 ? nan : (same ? 0.0 : sqrt(row.m2 / (double)(over.count - 1)));
+      t.lo = over.quantile[0];
+      t.hi = over.quantile[1];
+    }
+  }
   return ERPL_OK;
 }
 

@@ -354,6 +354,8 @@ extern "C++" {
 // Each enqueues its passes on `stream` and returns a hipError_t (0 = launched).
 // The scratch both rocPRIM calls of prepare need for n elements (nothing is enqueued).
 int erpl_boot_temp_bytes(int64_t n, size_t* bytes);
+// The scratch of the select alone (erpl_mc_sobol compacts its populations with erpl_launch_boot_compact and sorts nothing).
+int erpl_boot_select_bytes(int64_t n, size_t* bytes);
 int erpl_launch_boot_compact(const ErplBootPrep& p, void* stream);    // pop -> src, *count
 int erpl_launch_boot_prepare(const ErplBootPrep& p, void* stream);    // src, var -> x, sorted, pos (p.m known)
 int erpl_launch_boot_replicates(const ErplBootArgs& a, void* stream); // -> a.rep; one workgroup per replicate
@@ -453,4 +455,38 @@ extern "C++" {
 // Each enqueues one kernel on `stream` and returns a hipError_t (0 = launched).
 int erpl_launch_corridor_resample(const ErplCorridorResampleArgs& a, void* stream);   // 1 <= n_traj < 2^31
 int erpl_launch_corridor_bands(const ErplCorridorBandsArgs& a, void* stream);
+}
+
+// ---- erpl_mc_sobol (erpl_sobol.hip) ----
+// Prepare compacts the population of every requested row into RECORDS: rec[r][d][0 .. k + 1] = the k + 2 block values
+// (A, B, AB_0 .. AB_k-1) of dense member d of row r, contiguous.  A draw of the replicate kernel is then one contiguous
+// read of (k + 2) * 8 bytes.  Sums are indexed like the statistics of a row: slot 0 the sum of yA and yB, 1 the sum of the
+// centred squares, 2 + i the sum of (yB - f0) d_i, 2 + k + i the sum of d_i d_i.
+#define ERPL_SOBOL_CHUNK 8                                    // factors whose sums a thread carries through one sweep
+#define ERPL_SOBOL_SLOTS (2 + 2 * ERPL_SOBOL_MAX_FACTORS)     // 66
+struct ErplSobolOut {               // the estimates: what the device hands back
+  double f0[ERPL_SOBOL_MAX_ROWS];                      // slot 0 / (2 m)
+  double sum[ERPL_SOBOL_MAX_ROWS][ERPL_SOBOL_SLOTS];
+};
+struct ErplSobolWork {
+  ErplSobolOut out;
+  double part[ERPL_SOBOL_MAX_ROWS][ERPL_SOBOL_SLOTS][ERPL_ANA_MAX_BLOCKS];   // partials per row, slot and workgroup
+  ErplAnaRow bands[ERPL_SOBOL_MAX_STATS + 1];          // the summary over the replicates (erpl_launch_corridor_bands)
+};
+struct ErplSobolArgs {
+  const double* var[ERPL_SOBOL_MAX_ROWS];   // block 0 of the requested row: block b, design row j at var[r][b * n_base + j]
+  const uint32_t* src[ERPL_SOBOL_MAX_ROWS]; // [m[r]]: the design row of dense member d
+  double* rec[ERPL_SOBOL_MAX_ROWS];         // [m[r]][k + 2]
+  ErplSobolWork* work;
+  double* rep;                              // [n_rows * (2 + 2 k)][replicates]: statistic s of replicate b at s * replicates + b
+  unsigned long long seed;
+  int64_t n_base;
+  uint32_t m[ERPL_SOBOL_MAX_ROWS];          // (k + 2) * m < 2^31
+  int32_t n_rows, k, replicates;
+};
+extern "C++" {
+// Each enqueues its passes on `stream` and returns a hipError_t (0 = launched).
+int erpl_launch_sobol_records(const ErplSobolArgs& a, void* stream);      // var, src -> rec
+int erpl_launch_sobol_estimates(const ErplSobolArgs& a, void* stream);    // rec -> work->out
+int erpl_launch_sobol_replicates(const ErplSobolArgs& a, void* stream);   // rec -> a.rep; one workgroup per (replicate, row)
 }

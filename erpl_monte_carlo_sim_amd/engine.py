@@ -720,6 +720,69 @@ class TrajectoryEngine:
             out["replicate_values"] = rep
         return out
 
+    def sobol(self, summary, n_base, n_factors, mask=None, rows=None, extra=None, replicates=1000, level=0.95, seed=0,
+              want_replicates=False):
+        """Variance-based sensitivity of a pick-freeze run (erpl_mc_sobol): first-order (Saltelli 2010) and total-effect
+        (Jansen) indices of k = `n_factors` factors on up to 4 rows (summary rows, or _abi.SOBOL_ROW_EXTRA for `extra`;
+        default first apogee altitude and time, rail-exit speed).  `summary` is the float64 [16, ld] device tensor of the
+        concatenated design, ld >= (k + 2) n_base: columns [0, n_base) block A, [n_base, 2 n_base) block B, then AB_0 ..
+        AB_k-1 (A with factor i taken from B); `extra` float64 [ld] likewise; `mask` uint8 [n_base], byte 0 = the design
+        row counts.  One population per row: mask byte 0 and all k + 2 values of the row finite.  `replicates` bootstrap
+        resamples of whole design rows (0: estimates only), drawn as erpl_mc_bootstrap draws them from `seed`.
+        Returns a dict of NumPy arrays: rows, count / n_masked / n_non_finite / constant ([R]), and mean, variance ([R]),
+        first, total ([R, k]) each as a dict {estimate, rep_mean, se, lo, hi, finite}; n_base, n_factors, replicates,
+        level, seed.  want_replicates=True adds 'replicate_values': the float64 [R (2 + 2 k), replicates] device tensor,
+        statistic j (2 + 2 k) + {0: mean, 1: variance, 2 + i: first i, 2 + k + i: total i} of row j."""
+        ld = self._check_summary(summary)
+        n_base, k = int(n_base), int(n_factors)
+        if not 1 <= k <= _abi.SOBOL_MAX_FACTORS:
+            raise ValueError(f"1 to {_abi.SOBOL_MAX_FACTORS} factors")
+        if n_base < 1 or (k + 2) * n_base > ld:
+            raise ValueError(f"summary holds {ld} flights: fewer than (n_factors + 2) * n_base = {(k + 2) * n_base}")
+        if mask is not None and not (mask.device == self.device and mask.dtype == torch.uint8
+                                     and tuple(mask.shape) == (n_base,) and mask.is_contiguous()):
+            raise ValueError(f"mask must be a contiguous uint8 [n_base] tensor on {self.device}")
+        if extra is not None and not (extra.is_cuda and extra.device == self.device and extra.dtype == torch.float64
+                                      and tuple(extra.shape) == (ld,) and extra.is_contiguous()):
+            raise ValueError(f"extra must be a contiguous float64 [ld] tensor on {self.device}")
+        spec = self._defaults(_abi.ErplSobolSpec, "erpl_mc_sobol_defaults")
+        self._set_rows(spec, rows, 1, _abi.SOBOL_MAX_ROWS)
+        spec.n_factors, spec.replicates, spec.level = k, int(replicates), float(level)
+        spec.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if not 0 <= spec.replicates <= _abi.SOBOL_MAX_REPLICATES:
+            raise ValueError(f"0 to {_abi.SOBOL_MAX_REPLICATES} replicates")
+        if want_replicates and spec.replicates == 0:
+            raise ValueError("want_replicates needs replicates > 0")
+        R, ns = spec.n_rows, 2 + 2 * k
+        rep = torch.empty((R * ns, spec.replicates), dtype=torch.float64, device=self.device) if want_replicates else None
+        res = _abi.ErplSobol()
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_sobol", C.c_void_p(summary.data_ptr()), C.c_void_p(extra.data_ptr()) if extra is not None else None,
+                   C.c_void_p(mask.data_ptr()) if mask is not None else None, n_base, ld, C.byref(spec), C.byref(res),
+                   C.c_void_p(rep.data_ptr()) if want_replicates else None, C.c_void_p(st.cuda_stream))
+
+        def stats(pick):
+            """One field group of every row as {key: array}: pick(row) is an erpl_boot_stat or an array of k of them."""
+            keys = ("estimate", "rep_mean", "se", "lo", "hi", "finite")
+            out = {}
+            for key in keys:
+                vals = []
+                for j in range(R):
+                    s = pick(res.row[j])
+                    vals.append(getattr(s, key) if isinstance(s, _abi.ErplBootStat) else [getattr(s[i], key) for i in range(k)])
+                out[key] = np.array(vals, dtype=np.int64 if key == "finite" else np.float64)
+            return out
+
+        out = {"n_base": int(res.n_base), "n_factors": k, "rows": list(spec.rows[:R]), "replicates": int(res.replicates),
+               "level": float(level), "seed": int(spec.seed)}
+        for key in ("count", "n_masked", "n_non_finite", "constant"):
+            out[key] = np.array([getattr(res.row[j], key) for j in range(R)], dtype=np.int64)
+        out["mean"], out["variance"] = stats(lambda r: r.mean), stats(lambda r: r.variance)
+        out["first"], out["total"] = stats(lambda r: r.first), stats(lambda r: r.total)
+        if want_replicates:
+            out["replicate_values"] = rep
+        return out
+
     def _seeds_on_device(self, seeds):
         """The 32-bit seeds of the device streams: n."""
         if not (seeds.is_cuda and seeds.device == self.device and seeds.dtype in (torch.uint32, torch.int32)

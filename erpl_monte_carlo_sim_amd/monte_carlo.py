@@ -570,6 +570,98 @@ class MonteCarloAnalyzer:
         return ana.confidence_intervals(torch.as_tensor(summ, device=eng.device).contiguous(), engine=eng,
                                         replicates=replicates, level=level, seed=seed)
 
+    def sobol_indices(self, initial_conditions, n_base=16384, groups=None, rows=None, seed=1234, precision="f64_fast",
+                      planar=False, filter_outliers=False, replicates=1000, level=0.95, bootstrap_seed=0):
+        """Which dispersion drives what, interactions included (no reference counterpart; at its 4 k flights/s nobody
+        flies (k + 2) n_base flights for it): the variance-based (Sobol) first-order and total-effect indices of `groups`
+        of inputs on summary rows `rows` (default first apogee altitude and time, rail-exit speed: outputs every flight
+        has) from a pick-freeze design, with bootstrap intervals - `analysis.sobol_indices` on a design flown here.
+
+        The design is drawn under the INDEPENDENT law of `sampling.synthetic_dispersions(draws=...)` - a deliberate
+        deviation from the reference's joint law, for this analysis alone: factors that share a normal cannot be frozen one
+        at a time.  groups: None = `sampling.primitive_groups` (position, velocity, attitude, angular_velocity, mass,
+        dead_draw, motor_thrust, motor_mass_flow, wind_speed, wind_direction, turbulence), a list of those names, or a
+        mapping name -> rows of the primitive tensor (disjoint, at most 32).  A and B are `sampling.primitive_draws` at
+        `seed` and `seed + 1`; block b of the k + 2 blocks (A, B, A with group i from B) is flown through eng.submit in
+        sub-batches of at most DEVICE_CHUNK, inputs released per ticket, as run_monte_carlo_device does.
+        filter_outliers=True masks a design row when erpl_mc_analyze gives ANY of its k + 2 flights a reason.
+        One rank only (ValueError before any work): a design is not gathered across ranks.
+
+        Returns the dict of `analysis.sobol_indices` plus 'groups' ({name: rows}), 'summary' (float64 [16, (k + 2)
+        n_base] on the device, block-major), 'status', 'mask' (or None) and 'performance'."""
+        from . import analysis as ana, sampling
+        from .flatten import motor_kind
+        if dist.world()[1] > 1:
+            raise ValueError("sobol_indices is limited to a world size of 1: a design is not gathered across ranks")
+        n_base = int(n_base)
+        if n_base < 1:
+            raise ValueError("n_base: at least one design row")
+        use_base = self.base_wind_profile is not None and self.base_altitude_profile is not None
+        K = len(self.base_altitude_profile) if use_base else 100   # synthetic_dispersions' default grid
+        every = sampling.primitive_groups(K, motor_kind(self.motor) != _abi.MOTOR_SOLID)
+        if groups is None:
+            groups = every
+        elif not hasattr(groups, "items"):
+            unknown = [g for g in groups if g not in every]
+            if unknown:
+                raise ValueError(f"unknown group(s) {unknown}: one of {list(every)}")
+            groups = {g: every[g] for g in groups}
+        items = sampling.check_groups(groups, sampling.primitive_rows(K))
+        k = len(items)
+        if (k + 2) * n_base >= 2 ** 31:
+            raise ValueError(f"(k + 2) * n_base = {(k + 2) * n_base} is 2^31 or more")
+        eng = shared_engine(self.device)
+        eng.set_config(self._config())
+        prec = _abi.PRECISIONS[precision]
+        torch.cuda.synchronize(eng.device)
+        t0 = time.time()
+        A = sampling.primitive_draws(n_base, K, eng.device, seed)
+        B = sampling.primitive_draws(n_base, K, eng.device, seed + 1)
+        parts, inflight = [], []
+        keep = 2 * eng.get_overlap()
+        for P in sampling.pick_freeze_blocks(A, B, dict(items)):
+            for a in range(0, n_base, self.DEVICE_CHUNK):
+                cnt = min(self.DEVICE_CHUNK, n_base - a)
+                db = sampling.synthetic_dispersions(
+                    cnt, self.rocket, self.motor, self.wind_model, initial_conditions, eng.device, precision=prec,
+                    uncertainty=self.uncertainty_params, base_altitude_profile=self.base_altitude_profile,
+                    base_wind_profile=self.base_wind_profile, planar=planar, engine=eng,
+                    draws=P[:, a:a + cnt].contiguous())
+                parts.append(eng.submit(db))
+                inflight.append((eng.last_ticket, db))    # inputs outlive their batch
+                while len(inflight) > keep:
+                    ticket, inputs = inflight.pop(0)
+                    eng.check(ticket)
+                    del inputs
+        eng.wait()
+        eng.check()                # host-blocking; raises if a lane hand-over timed out
+        inflight.clear()
+        summ = torch.cat([p[0] for p in parts], dim=1).contiguous()
+        status = torch.cat([p[1] for p in parts]).contiguous()
+        torch.cuda.synchronize(eng.device)
+        t1 = time.time()
+        mask = None
+        if filter_outliers:
+            for b in range(k + 2):
+                cols = slice(b * n_base, (b + 1) * n_base)
+                _, why = eng.analyze(summ[:, cols].contiguous(), status[cols].contiguous(), reasons=True)
+                mask = why.clone() if mask is None else mask | why
+        out = ana.sobol_indices(summ, n_base, [name for name, _ in items], mask=mask, engine=eng, rows=rows,
+                                replicates=replicates, level=level, seed=bootstrap_seed)
+        torch.cuda.synchronize(eng.device)
+        t2 = time.time()
+        out["groups"] = {name: list(r) for name, r in items}
+        out["summary"], out["status"], out["mask"] = summ, status, mask
+        flights = (k + 2) * n_base
+        out["performance"] = {"flights": flights, "fly_s": t1 - t0, "flights_per_second": flights / max(t1 - t0, 1e-9),
+                              "indices_s": t2 - t1, "precision": precision, "sub_batches": len(parts)}
+        return out
+
+    def plot_sobol(self, sobol, save_plots=True):
+        """No reference counterpart: paired first-order / total-effect bars with their bootstrap intervals, one panel per
+        row, saved as monte_carlo_sobol.png in the output directory; returns that directory."""
+        return plots.plot_sobol(self, sobol, save_plots)
+
     def impact_probability(self, analysis, **kw):
         """Where it comes down, as probabilities (no reference counterpart): `analysis.impact_probability` - the kernel
         density of the impact points, the thresholds of the regions that hold 50 / 90 / 99 % of the landings and the

@@ -271,6 +271,41 @@ def corridor_figure(result):
     return fig
 
 
+def sobol_figure(result):
+    """The dict of analysis.sobol_indices as paired bars: per row one panel, per group the first-order index S1 and the
+    total-effect index ST side by side in the order of `group_names`, their bootstrap percentile intervals (lo, hi) as
+    whiskers where there are replicates.  A NaN index (a constant row, an empty population) draws no bar."""
+    names = list(result["group_names"])
+    rows = list(result["row_names"])
+    k = len(names)
+    fig = _figure((max(6.0, 0.9 * k + 2.0), 3.0 * len(rows) + 0.8))
+    axes = np.atleast_1d(fig.subplots(len(rows), 1, sharex=True))
+    x = np.arange(k, dtype=np.float64)
+    for j, (ax, row) in enumerate(zip(axes, rows)):
+        for which, label, shift, color in (("first", "S1 (first order)", -0.2, "tab:blue"),
+                                           ("total", "ST (total effect)", 0.2, "tab:orange")):
+            est = np.asarray(result[which]["estimate"], dtype=np.float64)[j]
+            lo = np.asarray(result[which]["lo"], dtype=np.float64)[j]
+            hi = np.asarray(result[which]["hi"], dtype=np.float64)[j]
+            ax.bar(x + shift, np.nan_to_num(est, nan=0.0), width=0.4, color=color, label=label)
+            have = np.isfinite(est) & np.isfinite(lo) & np.isfinite(hi)
+            if have.any():
+                # a percentile interval need not hold the estimate: the whisker never has a negative arm
+                err = np.vstack([np.maximum(est - lo, 0.0), np.maximum(hi - est, 0.0)])[:, have]
+                ax.errorbar((x + shift)[have], est[have], yerr=err, fmt="none", ecolor="black", capsize=3, linewidth=0.8)
+        ax.axhline(0.0, color="black", linewidth=0.6)
+        count = int(np.asarray(result["count"])[j])
+        ax.set_ylabel(row)
+        ax.set_title(f"{row}: {count} design rows, interaction {float(np.asarray(result['interaction'])[j]):.3f}", fontsize=9)
+        ax.grid(True, axis="y", alpha=0.3)
+    axes[0].legend(loc="best", fontsize=8)
+    axes[-1].set_xticks(x)
+    axes[-1].set_xticklabels(names, rotation=45, ha="right")
+    fig.suptitle(f"Sobol indices ({int(result['n_base'])} x {k + 2} flights)")
+    fig.tight_layout()
+    return fig
+
+
 def save_figure(fig, output_dir, name):
     path = os.path.join(output_dir, name)
     fig.savefig(path, dpi=DPI, bbox_inches="tight")
@@ -453,4 +488,15 @@ def plot_drivers(analyzer, analysis, save_plots=True):
         path = os.path.join(output_dir, "monte_carlo_drivers.png")
         mpimg.imsave(path, sheet)
         print(f"Drivers plot saved to: {path}")
+    return output_dir
+
+
+def plot_sobol(analyzer, sobol, save_plots=True):
+    """The indices of MonteCarloAnalyzer.sobol_indices (no reference counterpart) as monte_carlo_sobol.png; returns the
+    output directory (None without save_plots)."""
+    fig = sobol_figure(sobol)
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Sobol indices plot saved to: {save_figure(fig, output_dir, 'monte_carlo_sobol.png')}")
     return output_dir

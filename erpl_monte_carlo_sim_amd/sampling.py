@@ -59,10 +59,74 @@ def _check_ranges(ic, rk, mt, mean_u, mean_v):
                              "masses and mass flow): check the uncertainty table")
 
 
+def primitive_rows(K):
+    """Rows of the primitive tensor of the independent law for K wind knots: 14 dispersion normals, 3 motor normals, 3 K
+    turbulence normals, 2 uniforms."""
+    return 17 + 3 * int(K) + 2
+
+
+def primitive_draws(n, K, device, seed):
+    """The float64 [17 + 3 K + 2, n] primitives of the independent law (`synthetic_dispersions(draws=...)`) on `device`,
+    from torch's counter-based generator at `seed`: normals, and in the last two rows uniforms in [0, 1)."""
+    device = torch.device(device)
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(seed))
+    z = torch.randn((17 + 3 * int(K), int(n)), generator=gen, dtype=torch.float64, device=device)
+    uni = torch.rand((2, int(n)), generator=gen, dtype=torch.float64, device=device)
+    return torch.cat([z, uni]).contiguous()
+
+
+def primitive_groups(K, liquid=True):
+    """The default factors of a pick-freeze design: an ordered mapping group name -> rows of the primitive tensor.  Rows 16
+    (and 15 for a solid motor: its burn-time and impulse draws, drawn then unused) belong to no group."""
+    K = int(K)
+    groups = {"position": [0, 1, 2], "velocity": [3, 4, 5], "attitude": [6, 7, 8], "angular_velocity": [9, 10, 11],
+              "mass": [12], "dead_draw": [13], "motor_thrust": [14]}
+    if liquid:
+        groups["motor_mass_flow"] = [15]
+    groups["wind_speed"] = [17 + 3 * K]
+    groups["wind_direction"] = [17 + 3 * K + 1]
+    groups["turbulence"] = list(range(17, 17 + 3 * K))
+    return groups
+
+
+def check_groups(groups, n_rows):
+    """`groups` as a list of (name, rows): at most 32, each non-empty, rows inside the primitive tensor, none shared."""
+    items = [(str(name), [int(r) for r in rows]) for name, rows in dict(groups).items()]
+    if not 1 <= len(items) <= _abi.SOBOL_MAX_FACTORS:
+        raise ValueError(f"1 to {_abi.SOBOL_MAX_FACTORS} groups")
+    seen = {}
+    for name, rows in items:
+        if not rows:
+            raise ValueError(f"group {name!r} is empty")
+        for r in rows:
+            if not 0 <= r < n_rows:
+                raise ValueError(f"group {name!r}: row {r} outside 0..{n_rows - 1}")
+            if r in seen:
+                raise ValueError(f"groups must be disjoint: row {r} is in {seen[r]!r} and in {name!r}")
+            seen[r] = name
+    return items
+
+
+def pick_freeze_blocks(A, B, groups):
+    """The k + 2 primitive tensors of the pick-freeze design of A and B ([rows, n] each), block by block: A, B, then for
+    every group g of `groups` A with the rows of g taken from B.  A generator: one extra copy at a time."""
+    if A.shape != B.shape:
+        raise ValueError("A and B: the same shape")
+    items = check_groups(groups, int(A.shape[0]))
+    yield A
+    yield B
+    for _, rows in items:
+        AB = A.clone()
+        idx = torch.tensor(rows, dtype=torch.long, device=A.device)
+        AB[idx] = B[idx]
+        yield AB
+
+
 def synthetic_dispersions(n, rocket, motor, wind_model, base_initial_conditions, device,
                           precision=_abi.PREC_F32, seed=1234, uncertainty=None,
                           base_altitude_profile=None, base_wind_profile=None, planar=False,
-                          n_wind_knots=100, engine=None):
+                          n_wind_knots=100, engine=None, draws=None):
     """n dispersed samples with the distributions of monte_carlo.py:156-179 / :225-288, drawn with
     torch's counter-based device generator straight into the SoA tensors the kernels read.
 
@@ -88,7 +152,15 @@ def synthetic_dispersions(n, rocket, motor, wind_model, base_initial_conditions,
     `initial_position` sigma `position_x` is an exact affine image of `motor_thrust_multiplier` (both are z[0]) and
     `position_y` of the liquid mass-flow multiplier (z[1]) - the reference's behaviour, not a bug.  With the default
     sigma of 0 those columns are constant and the correlation drops them; otherwise its regression_ok = 0 says that
-    the two effects cannot be told apart."""
+    the two effects cannot be told apart.
+
+    draws: None (the joint law above, drawn here from `seed`), or a float64 [17 + 3 K + 2, n] device tensor of primitives
+    (`primitive_draws`) for an INDEPENDENT law: rows 0..13 the dispersion normals (row 13 the reference's dead thrust draw),
+    rows 14..16 the motor normals, rows 17..17 + 3 K - 1 the turbulence normals (knot k, component c at 17 + 3 k + c), the
+    last two rows the uniforms in [0, 1) of wind speed and direction; `seed` is not used.  This is a deliberate deviation
+    from the reference, for the variance-based sensitivity analysis alone (MonteCarloAnalyzer.sobol_indices): a
+    pick-freeze design needs factors that can be frozen one at a time, and under the joint law z[0] is the thrust
+    multiplier, `position_x` and the first turbulence innovation at once."""
     import ctypes as C
 
     import numpy as np
@@ -113,9 +185,16 @@ def synthetic_dispersions(n, rocket, motor, wind_model, base_initial_conditions,
     K = len(alt_np)
     if K > _abi.MAX_WIND_KNOTS:
         raise _abi.ErplError(f"{K} wind knots exceed the ABI limit {_abi.MAX_WIND_KNOTS}")
-    rows = max(3 * K, 14)
-    z = torch.randn((rows, n), generator=gen, dtype=f64, device=device)   # the shared normal stream
-    uni = torch.rand((2, n), generator=gen, dtype=f64, device=device)
+    if draws is None:
+        rows = max(3 * K, 14)
+        z = torch.randn((rows, n), generator=gen, dtype=f64, device=device)   # the shared normal stream
+        uni = torch.rand((2, n), generator=gen, dtype=f64, device=device)
+        z_motor, z_wind = z, z
+    else:
+        if not (torch.is_tensor(draws) and draws.device == device and draws.dtype == f64
+                and tuple(draws.shape) == (primitive_rows(K), n)):
+            raise ValueError(f"draws must be a float64 [{primitive_rows(K)}, {n}] tensor on {device}: 17 + 3 K + 2 rows")
+        z, z_motor, z_wind, uni = draws[0:14], draws[14:17], draws[17:17 + 3 * K], draws[17 + 3 * K:]
 
     ic0 = base_initial_conditions
     pos = col(ic0.get("position", [0.0] * 3)) + col(u["initial_position"]) * z[0:3]
@@ -140,13 +219,13 @@ def synthetic_dispersions(n, rocket, motor, wind_model, base_initial_conditions,
     rk = torch.stack([dry, prop]).contiguous()
 
     # motor perturbation (motor.py:95-125 / :171-186) + re-sync of burn time (monte_carlo.py:258-260)
-    k_thrust = 1.0 + motor.thrust_uncertainty * z[0]
+    k_thrust = 1.0 + motor.thrust_uncertainty * z_motor[0]
     if motor_kind(motor) == _abi.MOTOR_SOLID:   # z[1], z[2]: burn-time and impulse multipliers, drawn then overwritten / unused
         mdot = 4.26 * k_thrust
         row0 = k_thrust
         ae = motor.nozzle_exit_area * k_thrust
     else:
-        mdot = motor.mass_flow_rate * (1.0 + motor.mass_flow_uncertainty * z[1])
+        mdot = motor.mass_flow_rate * (1.0 + motor.mass_flow_uncertainty * z_motor[1])
         row0 = motor.thrust_vacuum * k_thrust
         ae = (motor.thrust_vacuum * k_thrust - motor.thrust_sea_level * k_thrust) / 101325.0
     burn = prop / mdot
@@ -167,7 +246,7 @@ def synthetic_dispersions(n, rocket, motor, wind_model, base_initial_conditions,
         scale_d = dev64([(np.float64(a) / 10.0) ** wind_model.power_law_exponent for a in alt_np])  # environment.py:118-123
     mean_u = (wind_speed * torch.cos(wind_dir)).contiguous()
     mean_v = (torch.zeros_like(wind_speed) if planar else wind_speed * torch.sin(wind_dir)).contiguous()
-    g = z[: 3 * K].contiguous()
+    g = z_wind[: 3 * K].contiguous()
     if planar:
         g = g.clone()
         g.view(K, 3, n)[:, 1, :] = 0.0      # no cross-wind turbulence either

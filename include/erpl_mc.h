@@ -894,6 +894,82 @@ int erpl_mc_corridor_resample(erpl_ctx* ctx, const erpl_out* out, const erpl_cor
 int erpl_mc_corridor_bands(erpl_ctx* ctx, const double* values, const uint8_t* mask, int64_t m, int64_t ld,
                            const erpl_corridor_spec* spec, erpl_row_stats* bands, int64_t* n_counted, void* hip_stream);
 
+/* Which dispersion drives what, without assuming a linear or monotone response, ON THE DEVICE: the variance-based (Sobol)
+ * decomposition of up to four outputs over k factors - first-order indices S1 and total-effect indices ST from a
+ * pick-freeze (Saltelli) design of (k + 2) n_base flights, each with its bootstrap standard error and percentile interval.
+ * The reference has nothing like it.  The call is design-agnostic: a "factor" may be a group of inputs; what was frozen
+ * in which block is the caller's business.
+ *
+ * Input.  `summary` is [ERPL_SUMMARY_DIM][ld], what a concatenated run of the design returns: block b of row r, design row
+ * j, sits at r * ld + b * n_base + j; block 0 is A, block 1 is B, block 2 + i is AB_i (A with factor i taken from B);
+ * ld >= (k + 2) n_base.  `extra` is [ld] with the same block layout (NULL unless a row is ERPL_SOBOL_ROW_EXTRA), `mask`
+ * [n_base] (byte 0: the design row counts; NULL: every one does), the optional `replicates_out` [n_stats][replicates].
+ * Conventions of erpl_mc_bootstrap: these buffers are caller-owned device memory; spec and result are host memory; the
+ * work is enqueued on `hip_stream` behind what is there and the call returns when the result is filled; the workspace
+ * belongs to the context, grows only (about n_rows (5 + 8 (k + 2)) bytes per design row plus the select's scratch, and
+ * 8 n_stats bytes per replicate when the caller keeps none) and is freed by erpl_mc_destroy.
+ *
+ * Population: ONE PER OUTPUT ROW.  Design row j is in P_r iff its mask byte is 0 AND all k + 2 values of row r are finite;
+ * P_r in ascending j, dense index d its d-th member, m = count.  n_masked and n_non_finite as in erpl_corr_result.
+ * Estimators over P_r, every operation rounded on its own (no FMA), with d_i = yAB_i - yA:
+ *   f0   = (sum of yA and yB) / (2 m)                         mean
+ *   V    = (sum (yA - f0)^2 + (yB - f0)^2) / (2 m)            variance, a second pass
+ *   S1_i = (sum (yB - f0) d_i / m) / V                        Saltelli et al. 2010, centred
+ *   ST_i = (sum d_i d_i / (2 m)) / V                          Jansen 1999
+ * m == 0: every double NaN, every `finite` 0, no error.  `constant`: min == max over the 2 m values of the blocks A and B
+ * (an exact test, as `constant` of erpl_mc_correlation): S1 and ST are NaN, `mean` is returned, `variance` is 0.
+ * Bootstrap: the draws of erpl_mc_bootstrap, unchanged - replicate b of row r is the draws t = 0 .. m_r - 1 with key
+ * `seed`, dense index (u m_r) >> 64; what erpl_mc_bootstrap_indices returns for (seed, b, m_r).  Replicate b does not
+ * depend on `replicates`.  A replicate resamples whole design rows: all k + 2 values of a drawn d go together.  It
+ * recomputes f0, V, S1 and ST with its own f0; V == 0 gives NaN indices.  Per statistic rep_mean, se, lo, hi and finite
+ * exactly as erpl_mc_bootstrap documents them; `estimate` is the estimator over P_r itself.  replicates = 0: estimates
+ * only.
+ * Summation order: a replicate is one workgroup of 256 threads, thread t accumulating the draws t, t + 256, .. in order
+ * (per draw: yA, then yB); the estimates run over the grid of the other analysis calls (a function of m alone), thread
+ * by thread in index order; both are folded in their fixed order.  No floating-point atomics: two calls on the same
+ * inputs return the same bytes in `result` and in `replicates_out`.
+ *
+ * Errors: ERPL_ERR_INVALID, before any device work and with a message that names the argument, in this order: a NULL spec,
+ * summary or result; n_base <= 0; n_factors outside 1..32; (n_factors + 2) n_base >= 2^31; ld < (n_factors + 2) n_base;
+ * n_rows outside 1..4; a row outside 0..16 or listed twice; row 16 without `extra`; replicates outside 0..65536;
+ * replicates_out with replicates == 0; level not in (0, 1) (looked at only when replicates > 0); the context last. */
+#define ERPL_SOBOL_MAX_FACTORS 32
+#define ERPL_SOBOL_MAX_ROWS 4
+#define ERPL_SOBOL_ROW_EXTRA 16          /* = ERPL_BOOT_ROW_EXTRA */
+#define ERPL_SOBOL_MAX_REPLICATES 65536
+#define ERPL_SOBOL_MAX_STATS (ERPL_SOBOL_MAX_ROWS * (2 + 2 * ERPL_SOBOL_MAX_FACTORS))   /* 264 */
+
+typedef struct erpl_sobol_spec {
+  int32_t n_factors;                     /* k, 1..ERPL_SOBOL_MAX_FACTORS */
+  int32_t n_rows;                        /* 1..ERPL_SOBOL_MAX_ROWS */
+  int32_t rows[ERPL_SOBOL_MAX_ROWS];     /* distinct; 0..15 = summary rows, ERPL_SOBOL_ROW_EXTRA = `extra` */
+  int32_t replicates;                    /* B, 0..ERPL_SOBOL_MAX_REPLICATES; 0 = estimates only */
+  int32_t reserved;
+  double level;                          /* confidence level in (0, 1) */
+  uint64_t seed;
+} erpl_sobol_spec;
+
+typedef struct erpl_sobol_row {
+  int64_t count, n_masked, n_non_finite; /* count + n_masked + n_non_finite == n_base */
+  int32_t constant, reserved;            /* min == max over the 2 count values of the blocks A and B */
+  erpl_boot_stat mean, variance;         /* f0, V */
+  erpl_boot_stat first[ERPL_SOBOL_MAX_FACTORS], total[ERPL_SOBOL_MAX_FACTORS];   /* S1_i, ST_i */
+} erpl_sobol_row;
+
+typedef struct erpl_sobol {
+  int64_t n_base;
+  int32_t n_factors, n_rows, replicates, n_stats;   /* n_stats = n_rows (2 + 2 k) */
+  erpl_sobol_row row[ERPL_SOBOL_MAX_ROWS];          /* of spec->rows[j] */
+} erpl_sobol;
+
+/* Host only: rows {FIRST_APOGEE_ALT, FIRST_APOGEE_TIME, RAIL_EXIT_SPEED}, 1000 replicates, level 0.95, seed 0,
+ * n_factors = 0 (the caller fills it in). */
+int erpl_mc_sobol_defaults(erpl_sobol_spec* spec);
+/* replicates_out: statistic s of replicate b at s * replicates + b, s = j (2 + 2 k) + {0: f0, 1: V, 2 + i: S1_i,
+ * 2 + k + i: ST_i} of spec->rows[j]. */
+int erpl_mc_sobol(erpl_ctx* ctx, const double* summary, const double* extra, const uint8_t* mask, int64_t n_base, int64_t ld,
+                  const erpl_sobol_spec* spec, erpl_sobol* result, double* replicates_out, void* hip_stream);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
