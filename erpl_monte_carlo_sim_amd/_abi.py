@@ -290,6 +290,39 @@ class ErplSobol(C.Structure):
                 ("n_stats", C.c_int32), ("row", ErplSobolRow * SOBOL_MAX_ROWS)]
 
 
+# erpl_mc_dependence
+DEP_MAX_FACTORS = 32
+DEP_MAX_ROWS = 4
+DEP_ROW_EXTRA = 16
+DEP_MAX_CLASSES = 64
+DEP_MAX_CELLS = 64
+DEP_MAX_SHIFTS = 4096
+
+
+class ErplDepSpec(C.Structure):
+    _fields_ = [("n_factors", C.c_int32), ("n_rows", C.c_int32), ("rows", C.c_int32 * DEP_MAX_ROWS),
+                ("classes", C.c_int32), ("cells", C.c_int32), ("shifts", C.c_int32), ("reserved", C.c_int32),
+                ("level", C.c_double), ("seed", C.c_uint64)]
+
+
+class ErplDepMeasure(C.Structure):
+    _fields_ = [("estimate", C.c_double), ("null_mean", C.c_double), ("null_hi", C.c_double), ("exceed", C.c_int64)]
+
+
+class ErplDepPair(C.Structure):
+    _fields_ = [("classes_used", C.c_int32), ("cells_used", C.c_int32), ("delta_num", C.c_int64),
+                ("delta", ErplDepMeasure), ("ks_max", ErplDepMeasure), ("ks_median", ErplDepMeasure), ("mi", ErplDepMeasure),
+                ("eta2", C.c_double), ("eta2_adj", C.c_double), ("f_stat", C.c_double)]
+
+
+class ErplDependence(C.Structure):
+    _fields_ = [("n", C.c_int64), ("count", C.c_int64), ("n_masked", C.c_int64), ("n_non_finite", C.c_int64),
+                ("n_factors", C.c_int32), ("n_rows", C.c_int32), ("classes", C.c_int32), ("cells", C.c_int32),
+                ("shifts", C.c_int32), ("reserved", C.c_int32),
+                ("row_mean", C.c_double * DEP_MAX_ROWS), ("row_ss", C.c_double * DEP_MAX_ROWS),
+                ("pair", (ErplDepPair * DEP_MAX_FACTORS) * DEP_MAX_ROWS)]
+
+
 LIB_NAME = "liberpl_mc.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
@@ -313,6 +346,7 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_impact_density_defaults", "erpl_mc_impact_density",
            "erpl_mc_corridor_defaults", "erpl_mc_corridor_resample", "erpl_mc_corridor_bands",
            "erpl_mc_sobol_defaults", "erpl_mc_sobol",
+           "erpl_mc_dependence_defaults", "erpl_mc_dependence",
            "erpl_mc_legacy_random_streams_device", "erpl_mc_legacy_wind_profiles_device")
 
 _lib = None
@@ -408,6 +442,9 @@ def load_library(path=None):
     lib.erpl_mc_sobol_defaults.argtypes = [C.POINTER(ErplSobolSpec)]
     lib.erpl_mc_sobol.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(ErplSobolSpec),
                                   C.POINTER(ErplSobol), C.c_void_p, C.c_void_p]
+    lib.erpl_mc_dependence_defaults.argtypes = [C.POINTER(ErplDepSpec)]
+    lib.erpl_mc_dependence.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplDepSpec),
+                                       C.POINTER(ErplDependence), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.erpl_mc_legacy_random_streams_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                                          C.c_int32, C.c_void_p]
     lib.erpl_mc_legacy_wind_profiles_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 9 + \

@@ -166,8 +166,8 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_keys(const ErplCorrA
   }
 }
 
-// keys: sorted, the population first.  Position p of a run of equal keys [first, last] gets first + (len + 1) / 2 (1-based
-// mid-rank); both ends by galloping away from p, then bisection: O(log len) reads next to p.
+// keys: sorted, the population first.  Position p of a run of equal keys [first, last] (run_of_key in erpl_stat_device.h)
+// gets first + (len + 1) / 2 (1-based mid-rank).
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_assign(const ErplCorrArgs a, const u64* __restrict__ keys,
                                                                    const uint32_t* __restrict__ idx, double* __restrict__ rank) {
   const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
@@ -175,28 +175,8 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corr_assign(const ErplCor
   for (int64_t p = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + threadIdx.x; p < n; p += stride) {
     const uint32_t i = idx[p];
     if (p >= count) { rank[i] = NAN; continue; }
-    const u64 k = keys[p];
-    int64_t first = p, last = p;
-    if (p > 0 && keys[p - 1] == k) {
-      int64_t eq = p - 1, step = 1;   // keys[eq] == k
-      while (eq - step >= 0 && keys[eq - step] == k) { eq -= step; step <<= 1; }
-      int64_t ne = eq - step < 0 ? -1 : eq - step;   // keys[ne] != k, or before the row
-      while (eq - ne > 1) {
-        const int64_t m = ne + (eq - ne) / 2;
-        if (keys[m] == k) eq = m; else ne = m;
-      }
-      first = eq;
-    }
-    if (p + 1 < count && keys[p + 1] == k) {
-      int64_t eq = p + 1, step = 1;
-      while (eq + step < count && keys[eq + step] == k) { eq += step; step <<= 1; }
-      int64_t ne = eq + step < count ? eq + step : count;   // keys[ne] != k, or behind the population
-      while (ne - eq > 1) {
-        const int64_t m = eq + (ne - eq) / 2;
-        if (keys[m] == k) eq = m; else ne = m;
-      }
-      last = eq;
-    }
+    int64_t first, last;
+    run_of_key(keys, p, count, &first, &last);
     rank[i] = (double)first + (double)(last - first + 2) * 0.5;   // exact: integers and halves below 2^52
   }
 }

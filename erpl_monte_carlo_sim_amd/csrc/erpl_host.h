@@ -75,6 +75,14 @@ struct SobolHost {
   ErplAnaRow bands[ERPL_SOBOL_MAX_STATS + 1];
 };
 
+// erpl_mc_dependence: pinned copies of what its launches hand back - the population counters, the moments of the requested
+// rows (summary rows, `extra`) and the record of every (row, factor) pair's own table
+struct DepHost {
+  unsigned long long counter[4];
+  ErplAnaResult rows[2];
+  ErplDepEst est[ERPL_DEP_MAX_ROWS * ERPL_DEP_MAX_FACTORS];
+};
+
 // The only place a per-context device buffer grows (the policy of erpl_mc_reserve): never shrinks, freed by
 // erpl_mc_destroy.  An earlier call on another stream may still read the old buffer, hence the device synchronise.
 template <typename T>
@@ -197,6 +205,9 @@ struct erpl_ctx {
   // erpl_mc_sobol: the partial sums of its estimates and the row records of its summary in the fixed block, the pieces of
   // erpl_stat_layout.h in the buffer; its population pass runs on the block of `corr`
   ErplStatUnit<ErplSobolWork, SobolHost> sobol;
+  // erpl_mc_dependence: the records of the pairs' own tables in the fixed block, the pieces of erpl_stat_layout.h in the
+  // buffer; its population pass runs on the block of `corr`, its row moments on that of `ana`
+  ErplStatUnit<ErplDepWork, DepHost> dep;
   // erpl_mc_legacy_random_streams_device / _wind_profiles_device: one device buffer (flag, op tables, knot constants, the
   // MT19937 states of a tile and two sets of its accepted pairs) and its pinned staging (the tables on their way up, r2
   // down and f up, per set), both bounded by the tile; an event per set behind the tile's copy to the host

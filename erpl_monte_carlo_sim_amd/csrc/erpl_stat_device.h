@@ -1,5 +1,7 @@
 // erpl_stat_device.h — what the statistics units (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip,
-// erpl_bootstrap.hip, erpl_density.hip, erpl_corridor.hip, erpl_sobol.hip) share: the grid of their streaming passes, the order-preserving keys, THE fixed-order reduction and the steps of the radix selection.
+// erpl_bootstrap.hip, erpl_density.hip, erpl_corridor.hip, erpl_sobol.hip, erpl_dependence.hip) share: the grid of their
+// streaming passes, the order-preserving keys, the run of equal keys behind a mid-rank, THE fixed-order reduction and the
+// steps of the radix selection.
 // Internal: never installed.
 //
 // The order is the contract: the last bit of every sum and the sign of a zero minimum depend on it, and "the same bits in
@@ -45,6 +47,37 @@ __device__ __forceinline__ u64 key_of_signed(double v) {
   return b ^ ((b >> 63) ? ~0ull : (1ull << 63));
 }
 __device__ __forceinline__ u64 key_of_tied(double v) { return key_of_signed(v == 0.0 ? 0.0 : v); }
+
+// The rank step of erpl_correlation.hip and erpl_dependence.hip: keys[0 .. count - 1] ascending, p < count.  The run of keys
+// equal to keys[p] is [*first, *last]; both ends by galloping away from p, then bisection: O(log len) reads next to p.  The
+// 1-based mid-rank of the run is *first + (len + 1) / 2, and 2 rank - 1 = *first + *last + 1.
+__device__ __forceinline__ void run_of_key(const u64* __restrict__ keys, const int64_t p, const int64_t count, int64_t* first_out,
+                                           int64_t* last_out) {
+  const u64 k = keys[p];
+  int64_t first = p, last = p;
+  if (p > 0 && keys[p - 1] == k) {
+    int64_t eq = p - 1, step = 1;   // keys[eq] == k
+    while (eq - step >= 0 && keys[eq - step] == k) { eq -= step; step <<= 1; }
+    int64_t ne = eq - step < 0 ? -1 : eq - step;   // keys[ne] != k, or before the row
+    while (eq - ne > 1) {
+      const int64_t m = ne + (eq - ne) / 2;
+      if (keys[m] == k) eq = m; else ne = m;
+    }
+    first = eq;
+  }
+  if (p + 1 < count && keys[p + 1] == k) {
+    int64_t eq = p + 1, step = 1;
+    while (eq + step < count && keys[eq + step] == k) { eq += step; step <<= 1; }
+    int64_t ne = eq + step < count ? eq + step : count;   // keys[ne] != k, or behind the population
+    while (ne - eq > 1) {
+      const int64_t m = eq + (ne - eq) / 2;
+      if (keys[m] == k) eq = m; else ne = m;
+    }
+    last = eq;
+  }
+  *first_out = first;
+  *last_out = last;
+}
 
 // ---- the operations of a fold: of(running, incoming), and the value that leaves every other one as it is
 struct Add {

@@ -1,7 +1,8 @@
-// erpl_stat_layout.h — how erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density and erpl_mc_sobol cut the device
-// buffer each of them grows into pieces: pure functions of the call's sizes (no HIP; the scratch size of the rocPRIM calls comes in as a
-// number), so that tests/test_stat_layout.py checks every offset on the CPU, through erpl_stat_layout_table, before a kernel
-// writes through one.  Every piece starts at a multiple of 256 bytes; `need` is the end of the last one.
+// erpl_stat_layout.h — how erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density, erpl_mc_sobol and
+// erpl_mc_dependence cut the device buffer each of them grows into pieces: pure functions of the call's sizes (no HIP; the
+// scratch size of the rocPRIM calls comes in as a number), so that tests/test_stat_layout.py and
+// tests/test_dependence_layout.py check every offset on the CPU, through erpl_stat_layout_table, before a kernel writes
+// through one.  Every piece starts at a multiple of 256 bytes; `need` is the end of the last one.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -107,6 +108,36 @@ inline ErplSobolLayout erpl_sobol_layout(int64_t n, int k, int R, int B, bool ca
   l.temp_bytes = erpl_scratch_piece(temp_bytes);
   l.temp = c.take(l.temp_bytes);
   l.rep = c.take(caller_keeps_replicates ? 0 : 8 * uB * uR * (2 + 2 * uk));
+  l.need = c.end;
+  return l;
+}
+
+// erpl_mc_dependence over n samples, F factors, R rows, M classes, H cells, P shifts: [pop n bytes][src n u32][count][yd R rows
+// of n doubles][xc F rows of x_stride class bytes][yext R rows of y_stride cell bytes, extended: 2 n + 32 of them are
+// written][keys 2n u64][idx 2n u32][scratch of the select / the sort][cstat R F M 6 doubles][tab R F M H int64][null
+// R F 4 P doubles].  The strides are multiples of 16: the table kernel reads 16 class bytes per load.
+struct ErplDepLayout {
+  size_t pop, src, count, yd[ERPL_DEP_MAX_ROWS], xc, yext, keys, idx, temp, cstat, tab, null, x_stride, y_stride, temp_bytes, need;
+};
+inline ErplDepLayout erpl_dep_layout(int64_t n, int F, int R, int M, int H, int P, size_t temp_bytes) {
+  const size_t un = (size_t)n, pairs = (size_t)F * (size_t)R;
+  ErplCarve c;
+  ErplDepLayout l = {};
+  l.pop = c.take(un);
+  l.src = c.take(4 * un);
+  l.count = c.take(8);
+  for (int j = 0; j < R; ++j) l.yd[j] = c.take(8 * un);
+  l.x_stride = (un + 15) & ~(size_t)15;
+  l.y_stride = (2 * un + 32 + 15) & ~(size_t)15;
+  l.xc = c.take(l.x_stride * (size_t)F);
+  l.yext = c.take(l.y_stride * (size_t)R);
+  l.keys = c.take(16 * un);
+  l.idx = c.take(8 * un);
+  l.temp_bytes = erpl_scratch_piece(temp_bytes);
+  l.temp = c.take(l.temp_bytes);
+  l.cstat = c.take(8 * 6 * pairs * (size_t)M);
+  l.tab = c.take(8 * pairs * (size_t)M * (size_t)H);
+  l.null = c.take(8 * 4 * pairs * (size_t)P);
   l.need = c.end;
   return l;
 }

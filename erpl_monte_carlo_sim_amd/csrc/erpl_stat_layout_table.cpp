@@ -6,6 +6,8 @@
 //                                                                           rep temp_bytes need
 //   dens <n> <nodes> <want_samples> <caller_keeps_row> <temp_bytes>      -> pop src count temp pts nodes dens row part temp_bytes need
 //   sobol <n> <k> <R> <B> <caller_keeps_replicates> <temp_bytes>         -> pop src[R] count rec[R] temp rep temp_bytes need
+//   dep <n> <F> <R> <M> <H> <P> <temp_bytes>                             -> pop src count yd[R] xc yext keys idx temp cstat tab null
+//                                                                           x_stride y_stride temp_bytes need
 #include <stdio.h>
 
 #include <initializer_list>
@@ -18,7 +20,7 @@ int main() {
   char line[256];
   while (fgets(line, sizeof(line), stdin)) {
     long long n, nodes;
-    int a, b, c, d;
+    int a, b, c, d, e;
     size_t temp;
     if (sscanf(line, "corr %lld %d %d %d %zu", &n, &a, &b, &c, &temp) == 5) {
       const ErplCorrLayout l = erpl_corr_layout(n, a, b != 0, c != 0, temp);
@@ -42,6 +44,12 @@ int main() {
       put(l.count);
       for (int j = 0; j < b; ++j) put(l.rec[j]);
       for (size_t v : {l.temp, l.rep, l.temp_bytes}) put(v);
+      put(l.need, "\n");
+    } else if (sscanf(line, "dep %lld %d %d %d %d %d %zu", &n, &a, &b, &c, &d, &e, &temp) == 7 && b >= 1 && b <= ERPL_DEP_MAX_ROWS) {
+      const ErplDepLayout l = erpl_dep_layout(n, a, b, c, d, e, temp);
+      for (size_t v : {l.pop, l.src, l.count}) put(v);
+      for (int j = 0; j < b; ++j) put(l.yd[j]);
+      for (size_t v : {l.xc, l.yext, l.keys, l.idx, l.temp, l.cstat, l.tab, l.null, l.x_stride, l.y_stride, l.temp_bytes}) put(v);
       put(l.need, "\n");
     } else {
       fprintf(stderr, "bad request: %s", line);

@@ -1,8 +1,8 @@
 // erpl_stats_api.hip — host halves of the analysis entry points of the C ABI (include/erpl_mc.h): erpl_mc_analyze,
 // erpl_mc_histogram, erpl_mc_histogram_xy, erpl_mc_dispersion, erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density,
-// erpl_mc_corridor_resample, erpl_mc_corridor_bands, erpl_mc_sobol and their defaults.  Argument checks, workspace, launches
-// (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip, erpl_bootstrap.hip, erpl_density.hip, erpl_corridor.hip,
-// erpl_sobol.hip)
+// erpl_mc_corridor_resample, erpl_mc_corridor_bands, erpl_mc_sobol, erpl_mc_dependence and their defaults.  Argument checks,
+// workspace, launches (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip, erpl_bootstrap.hip, erpl_density.hip,
+// erpl_corridor.hip, erpl_sobol.hip, erpl_dependence.hip)
 // and what the host finishes in double precision.  The refusals come in one order
 // everywhere - spec fields, n, pointers, context (erpl_mc_bootstrap: the order its header comment lists) - and need no
 // device; tests/golden/stats_refusals.json pins their texts.  What the entry points share comes first: the pieces of the
@@ -1191,6 +1191,197 @@ int erpl_mc_sobol(erpl_ctx* c, const double* summary, const double* extra, const
       t.hi = over.quantile[1];
     }
   }
+  return ERPL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------- erpl_mc_dependence
+namespace {
+
+// What the host makes of the P null values of one measure: the mean in ascending p, the quantile `level` with np.quantile's
+// linear interpolation (its _lerp: a + (b - a) t, from t = 1/2 on b - (b - a) (1 - t)), and the values >= estimate.
+void finish_null(const double* v, int P, double level, std::vector<double>& sorted, erpl_dep_measure& o) {
+  double sum = 0.0;
+  int64_t exceed = 0;
+  for (int p = 0; p < P; ++p) {
+    sum += v[p];
+    exceed += v[p] >= o.estimate ? 1 : 0;
+  }
+  sorted.assign(v, v + P);
+  std::sort(sorted.begin(), sorted.end());
+  const double pos = (double)(P - 1) * level, below = floor(pos), t = pos - below;
+  const int lo = (int)below, hi = lo + 1 < P ? lo + 1 : P - 1;
+  const double a = sorted[lo], b = sorted[hi], diff = b - a;
+  o.null_mean = sum / (double)P;
+  o.null_hi = t >= 0.5 ? b - diff * (1.0 - t) : a + diff * t;
+  o.exceed = exceed;
+}
+
+}  // namespace
+
+extern "C" {
+
+int erpl_mc_dependence_defaults(erpl_dep_spec* spec) {
+  NEED(spec);
+  memset(spec, 0, sizeof(*spec));
+  spec->n_rows = 3;
+  spec->rows[0] = ERPL_SUM_APOGEE_ALT; spec->rows[1] = ERPL_SUM_RANGE; spec->rows[2] = ERPL_SUM_FLIGHT_TIME;
+  spec->classes = spec->cells = 16;
+  spec->shifts = 200;
+  spec->level = 0.95;
+  spec->seed = 0;
+  return ERPL_OK;
+}
+
+int erpl_mc_dependence(erpl_ctx* c, const double* factors, const double* summary, const double* extra, const uint8_t* mask,
+                       int64_t n, const erpl_dep_spec* spec, erpl_dependence* result, int64_t* tables, double* class_stats,
+                       double* null_out, void* stream) {
+  NEED(spec); NEED(factors); NEED(summary); NEED(result);
+  ERPL_TRY(check_n(n, (1ll << 31) - 1, ": the sort and the tables carry 31-bit sample indices"));
+  ERPL_TRY(check_int(spec->n_factors, "n_factors", -1, 1, ERPL_DEP_MAX_FACTORS));
+  ERPL_TRY(check_row_list(spec->rows, spec->n_rows, 1, ERPL_DEP_MAX_ROWS, ERPL_DEP_ROW_EXTRA));
+  for (int j = 0; j < spec->n_rows; ++j)
+    if (spec->rows[j] == ERPL_DEP_ROW_EXTRA && !extra)
+      return erpl_fail(ERPL_ERR_INVALID, "extra is NULL but spec->rows[%d] = %d (ERPL_DEP_ROW_EXTRA)", j, spec->rows[j]);
+  ERPL_TRY(check_int(spec->classes, "classes", -1, 2, ERPL_DEP_MAX_CLASSES));
+  ERPL_TRY(check_int(spec->cells, "cells", -1, 2, ERPL_DEP_MAX_CELLS));
+  ERPL_TRY(check_int(spec->shifts, "shifts", -1, 0, ERPL_DEP_MAX_SHIFTS));
+  if (null_out && spec->shifts == 0) return erpl_fail(ERPL_ERR_INVALID, "null_out is given but spec->shifts = 0");
+  if (spec->shifts > 0 && !(spec->level > 0.0 && spec->level < 1.0))
+    return erpl_fail(ERPL_ERR_INVALID, "spec->level = %g outside (0, 1)", spec->level);
+  NEED_AS(c, "ctx");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int F = spec->n_factors, R = spec->n_rows, M = spec->classes, H = spec->cells, P = spec->shifts;
+  const size_t un = (size_t)n, pairs = (size_t)F * R, n_cstat = pairs * M * 6, n_tab = pairs * M * H, n_null = pairs * 4 * (size_t)P;
+
+  size_t temp_bytes = 0;
+  LAUNCH_TRY(erpl_boot_temp_bytes(n, &temp_bytes), "select / radix sort sizing failed");
+  const ErplDepLayout at = erpl_dep_layout(n, F, R, M, H, P, temp_bytes);
+  ERPL_TRY(c->corr.first_use());   // the population pass and its counters
+  ERPL_TRY(c->ana.first_use());    // the moments of the rows
+  ERPL_TRY(c->dep.first_use());
+  ERPL_TRY(c->dep.grow(at.need));
+  char* buf = c->dep.buf;
+  DepHost& h = *c->dep.host;
+
+  ErplDepArgs a;
+  memset(&a, 0, sizeof(a));
+  ErplCorrArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.mask = mask; pa.n = n; pa.n_vars = F + R; pa.work = c->corr.work; pa.pop = (uint8_t*)(buf + at.pop);
+  for (int f = 0; f < F; ++f) a.var[f] = factors + (size_t)f * un;
+  for (int j = 0; j < R; ++j) {
+    a.var[F + j] = spec->rows[j] == ERPL_DEP_ROW_EXTRA ? extra : summary + (size_t)spec->rows[j] * un;
+    a.yd[j] = (double*)(buf + at.yd[j]);
+  }
+  for (int v = 0; v < F + R; ++v) pa.var[v] = a.var[v];
+  KERNEL_TRY(erpl_launch_corr_population(pa, stream));
+  HIP_TRY(hipMemcpyAsync(h.counter, &c->corr.work->out.counter[0], sizeof(h.counter), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int64_t m = (int64_t)h.counter[0];
+
+  const double nan = NAN;
+  memset(result, 0, sizeof(*result));
+  result->n = n; result->count = m; result->n_masked = (int64_t)h.counter[1]; result->n_non_finite = (int64_t)h.counter[2];
+  result->n_factors = F; result->n_rows = R; result->classes = M; result->cells = H; result->shifts = P;
+  for (int j = 0; j < ERPL_DEP_MAX_ROWS; ++j) {
+    result->row_mean[j] = result->row_ss[j] = nan;
+    for (int f = 0; f < ERPL_DEP_MAX_FACTORS; ++f) {
+      erpl_dep_pair& o = result->pair[j][f];
+      for (erpl_dep_measure* q : {&o.delta, &o.ks_max, &o.ks_median, &o.mi}) q->estimate = q->null_mean = q->null_hi = nan;
+      o.eta2 = o.eta2_adj = o.f_stat = nan;
+    }
+  }
+  const bool nulls = P > 0 && m >= 2;
+  if (null_out && !nulls) std::fill(null_out, null_out + n_null, nan);
+  if (m == 0) {   // nothing counted: empty tables, empty classes
+    if (tables) std::fill(tables, tables + n_tab, (int64_t)0);
+    if (class_stats)
+      for (size_t k = 0; k < n_cstat; ++k) class_stats[k] = k % 6 == 0 ? 0.0 : nan;
+    return ERPL_OK;
+  }
+
+  // mean and sum((y - mean)^2) of every row, by the passes of erpl_mc_analyze with the population bytes as the mask: the
+  // summary rows in one launch, `extra` as a one-row summary in a second
+  int32_t est_rows[ERPL_DEP_MAX_ROWS];
+  int est_of[ERPL_DEP_MAX_ROWS], n_est = 0, has_extra = 0;   // row j of the spec: rows[0].row[est_of[j]], or rows[1].row[0] (-1)
+  for (int j = 0; j < R; ++j) {
+    if (spec->rows[j] == ERPL_DEP_ROW_EXTRA) { est_of[j] = -1; has_extra = 1; }
+    else { est_of[j] = n_est; est_rows[n_est++] = spec->rows[j]; }
+  }
+  if (n_est > 0) ERPL_TRY(describe_rows(c, summary, pa.pop, n, est_rows, n_est, nullptr, 0, &h.rows[0], st));
+  if (has_extra) ERPL_TRY(describe_rows(c, extra, pa.pop, n, nullptr, 1, nullptr, 0, &h.rows[1], st));
+
+  ErplBootPrep p;
+  memset(&p, 0, sizeof(p));
+  p.pop = pa.pop; p.src = (uint32_t*)(buf + at.src); p.count = (unsigned long long*)(buf + at.count);
+  p.temp = buf + at.temp; p.temp_bytes = at.temp_bytes; p.n = n;
+  LAUNCH_TRY(erpl_launch_boot_compact(p, stream), "select failed");
+  a.src = p.src; a.xc = (uint8_t*)(buf + at.xc); a.yext = (uint8_t*)(buf + at.yext);
+  a.keys = (unsigned long long*)(buf + at.keys); a.idx = (uint32_t*)(buf + at.idx);
+  a.temp = buf + at.temp; a.temp_bytes = at.temp_bytes;
+  a.cstat = (double*)(buf + at.cstat); a.tab = (long long*)(buf + at.tab); a.null = (double*)(buf + at.null);
+  a.work = c->dep.work; a.seed = spec->seed; a.x_stride = at.x_stride; a.y_stride = at.y_stride;
+  a.m = (uint32_t)m; a.n_factors = F; a.n_rows = R; a.classes = M; a.cells = H; a.shifts = P;
+  LAUNCH_TRY(erpl_launch_dep_classes(a, stream), "class pass failed");
+  KERNEL_TRY(erpl_launch_dep_tables(a, stream));
+
+  std::vector<double> cstat(n_cstat), own_null;
+  HIP_TRY(hipMemcpyAsync(h.est, c->dep.work->est, pairs * sizeof(ErplDepEst), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(cstat.data(), a.cstat, n_cstat * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (tables) HIP_TRY(hipMemcpyAsync(tables, a.tab, n_tab * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  const double* null_values = null_out;
+  if (nulls) {
+    if (!null_out) { own_null.resize(n_null); null_values = own_null.data(); }
+    HIP_TRY(hipMemcpyAsync(const_cast<double*>(null_values), a.null, n_null * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+
+  std::vector<double> sorted;
+  const double dm = (double)m;
+  for (int j = 0; j < R; ++j) {
+    const ErplAnaRow& row = est_of[j] < 0 ? h.rows[1].row[0] : h.rows[0].row[est_of[j]];
+    const bool constant = row.vmin == row.vmax;
+    result->row_mean[j] = row.mean;
+    result->row_ss[j] = row.m2;
+    for (int f = 0; f < F; ++f) {
+      const size_t pr = (size_t)j * F + f;
+      const ErplDepEst& e = h.est[pr];
+      erpl_dep_pair& o = result->pair[j][f];
+      o.classes_used = e.classes_used; o.cells_used = e.cells_used; o.delta_num = e.delta_num;
+      erpl_dep_measure* ms[4] = {&o.delta, &o.ks_max, &o.ks_median, &o.mi};
+      for (int k = 0; k < 4; ++k) {
+        ms[k]->estimate = e.v[k];
+        if (nulls) finish_null(null_values + (pr * 4 + k) * (size_t)P, P, spec->level, sorted, *ms[k]);
+      }
+      // the variance share: B over the classes in ascending order
+      double* cs = cstat.data() + pr * M * 6;
+      double between = 0.0;
+      for (int cl = 0; cl < M; ++cl) {
+        if (cs[cl * 6] > 0.0) {
+          const double dev = cs[cl * 6 + 1] - row.mean;
+          between += cs[cl * 6] * (dev * dev);
+          cs[cl * 6 + 2] = sqrt(cs[cl * 6 + 2] / cs[cl * 6]);   // the population std of the class
+        }
+      }
+      const int k = e.classes_used;
+      if (!constant) {
+        if (k < 2) {
+          o.eta2 = 0.0;
+        } else {
+          o.eta2 = between / row.m2;
+          if (m > k) {
+            const double dfw = (double)(m - k);
+            o.eta2_adj = 1.0 - ((1.0 - o.eta2) * (dm - 1.0)) / dfw;
+            o.f_stat = (between / (double)(k - 1)) / ((row.m2 - between) / dfw);
+          }
+        }
+      }
+    }
+  }
+  if (class_stats) memcpy(class_stats, cstat.data(), n_cstat * sizeof(double));
   return ERPL_OK;
 }
 

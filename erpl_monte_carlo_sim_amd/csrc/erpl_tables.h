@@ -490,3 +490,41 @@ int erpl_launch_sobol_records(const ErplSobolArgs& a, void* stream);      // var
 int erpl_launch_sobol_estimates(const ErplSobolArgs& a, void* stream);    // rec -> work->out
 int erpl_launch_sobol_replicates(const ErplSobolArgs& a, void* stream);   // rec -> a.rep; one workgroup per (replicate, row)
 }
+
+// ---- erpl_mc_dependence (erpl_dependence.hip) ----
+// Everything works on the dense population (m members, in sample order).  Per variable the (key_of_tied, dense index) pairs
+// are sorted and every member gets its class byte from its mid-rank; a factor's class bytes lie at xc + f * x_stride, an
+// outcome's cell bytes at yext + j * y_stride, EXTENDED: byte k holds the cell of member k mod m for every k < 2 m + 32, so
+// that the table kernel reads the cells d + s .. d + s + 15 of a shifted pairing without a wrap.
+struct ErplDepEst {                 // what the table of the run itself (no shift) hands back for one (row, factor)
+  long long delta_num;
+  int32_t classes_used, cells_used;
+  double v[4];                      // delta, ks_max, ks_median, mi
+};
+struct ErplDepWork {
+  ErplDepEst est[ERPL_DEP_MAX_ROWS * ERPL_DEP_MAX_FACTORS];   // pair (j, f) at j * n_factors + f
+};
+struct ErplDepArgs {
+  const double* var[ERPL_DEP_MAX_FACTORS + ERPL_DEP_MAX_ROWS];   // [n] each: the factors, then the requested rows
+  const uint32_t* src;              // [m]: the sample of dense member d (erpl_launch_boot_compact)
+  double* yd[ERPL_DEP_MAX_ROWS];    // [m] each: the requested rows, dense
+  uint8_t* xc;                      // [n_factors][x_stride]
+  uint8_t* yext;                    // [n_rows][y_stride]
+  unsigned long long* keys;         // [2 m] the sort's keys, in and out
+  uint32_t* idx;                    // [2 m] the dense indices that travel with them
+  void* temp;                       // scratch of the sort
+  size_t temp_bytes;
+  double* cstat;                    // [n_rows][n_factors][classes][6]: count, mean, sum (y - mean)^2, x_lo, x_hi, x_median
+  long long* tab;                   // [n_rows][n_factors][classes][cells]
+  double* null;                     // [n_rows][n_factors][4][shifts]
+  ErplDepWork* work;
+  unsigned long long seed;
+  size_t x_stride, y_stride;        // multiples of 16 (erpl_dep_layout)
+  uint32_t m;                       // 1 .. 2^31 - 1
+  int32_t n_factors, n_rows, classes, cells, shifts;
+};
+extern "C++" {
+// Each enqueues its passes on `stream` and returns a hipError_t (0 = launched).
+int erpl_launch_dep_classes(const ErplDepArgs& a, void* stream);   // var, src -> yd, xc, yext, cstat
+int erpl_launch_dep_tables(const ErplDepArgs& a, void* stream);    // xc, yext -> tab, work->est, null; one workgroup per table
+}

@@ -783,6 +783,77 @@ class TrajectoryEngine:
             out["replicate_values"] = rep
         return out
 
+    def dependence(self, factors, summary, mask=None, rows=None, extra=None, classes=16, cells=16, shifts=200, level=0.95,
+                   seed=0, want_tables=False, want_curves=True, want_null=False):
+        """Given-data sensitivity of ONE ordinary run (erpl_mc_dependence), no extra flights: for every row of `factors`
+        (float64 [F, n] on the device, F <= 32) and up to 4 rows (summary rows, or _abi.DEP_ROW_EXTRA for the float64 [n]
+        device tensor `extra`; default apogee, range, flight time) the first-order variance share eta2 (correlation ratio),
+        Borgonovo's delta, the PAWN Kolmogorov-Smirnov statistics and the mutual information, over ONE population: mask
+        byte 0 and every factor and requested row finite.  Factors are cut into `classes` and outcomes into `cells` equal-
+        count classes of their mid-ranks (2..64).  `shifts` cyclic re-pairings (0..4096, drawn from `seed` as
+        erpl_mc_bootstrap draws) give every measure the value a factor without any effect would get at this size.
+        Returns a dict: n, count, n_masked, n_non_finite, rows, n_factors, classes, cells, shifts, level, seed, row_mean /
+        row_ss ([R]), classes_used / cells_used / delta_num / eta2 / eta2_adj / f_stat ([R, F]) and delta, ks_max,
+        ks_median, mi, each {estimate, null_mean, null_hi, exceed} of [R, F] arrays (null_hi: the quantile `level` of the
+        null values).  want_curves adds 'class_stats' ([R, F, classes, 6]: count, mean, std, x_lo, x_hi, x_median of
+        every class, the main-effect curve), want_tables 'tables' (int64 [R, F, classes, cells]), want_null 'null_values'
+        ([R, F, 4, shifts]: delta, ks_max, ks_median, mi).  A pick-freeze design is not an ordinary run: use `sobol`."""
+        n, mask_p = self._summary_and_mask(summary, mask)
+        if not (factors.is_cuda and factors.device == self.device and factors.dtype == torch.float64
+                and factors.dim() == 2 and factors.shape[1] == n and factors.is_contiguous()):
+            raise ValueError(f"factors must be a contiguous float64 [F, n] tensor on {self.device}")
+        F = int(factors.shape[0])
+        if not 1 <= F <= _abi.DEP_MAX_FACTORS:
+            raise ValueError(f"1 to {_abi.DEP_MAX_FACTORS} factors")
+        if extra is not None and not (extra.is_cuda and extra.device == self.device and extra.dtype == torch.float64
+                                      and tuple(extra.shape) == (n,) and extra.is_contiguous()):
+            raise ValueError(f"extra must be a contiguous float64 [n] tensor on {self.device}")
+        spec = self._defaults(_abi.ErplDepSpec, "erpl_mc_dependence_defaults")
+        self._set_rows(spec, rows, 1, _abi.DEP_MAX_ROWS)
+        spec.n_factors, spec.classes, spec.cells, spec.shifts = F, int(classes), int(cells), int(shifts)
+        spec.level, spec.seed = float(level), int(seed) & 0xFFFFFFFFFFFFFFFF
+        if not (2 <= spec.classes <= _abi.DEP_MAX_CLASSES and 2 <= spec.cells <= _abi.DEP_MAX_CELLS):
+            raise ValueError(f"2 to {_abi.DEP_MAX_CLASSES} classes and 2 to {_abi.DEP_MAX_CELLS} cells")
+        if not 0 <= spec.shifts <= _abi.DEP_MAX_SHIFTS:
+            raise ValueError(f"0 to {_abi.DEP_MAX_SHIFTS} shifts")
+        if want_null and spec.shifts == 0:
+            raise ValueError("want_null needs shifts > 0")
+        R, M, H, P = spec.n_rows, spec.classes, spec.cells, spec.shifts
+        tables = np.empty((R, F, M, H), dtype=np.int64) if want_tables else None
+        curves = np.empty((R, F, M, 6), dtype=np.float64) if want_curves else None
+        null = np.empty((R, F, 4, P), dtype=np.float64) if want_null else None
+        res = _abi.ErplDependence()
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_dependence", C.c_void_p(factors.data_ptr()), C.c_void_p(summary.data_ptr()),
+                   C.c_void_p(extra.data_ptr()) if extra is not None else None, mask_p, n, C.byref(spec), C.byref(res),
+                   C.c_void_p(tables.ctypes.data) if want_tables else None,
+                   C.c_void_p(curves.ctypes.data) if want_curves else None,
+                   C.c_void_p(null.ctypes.data) if want_null else None, C.c_void_p(st.cuda_stream))
+
+        def grid(pick, dtype=np.float64):
+            return np.array([[pick(res.pair[j][f]) for f in range(F)] for j in range(R)], dtype=dtype)
+
+        out = {"n": int(res.n), "count": int(res.count), "n_masked": int(res.n_masked), "n_non_finite": int(res.n_non_finite),
+               "rows": list(spec.rows[:R]), "n_factors": F, "classes": M, "cells": H, "shifts": P, "level": float(level),
+               "seed": int(spec.seed), "row_mean": np.array(res.row_mean[:R], dtype=np.float64),
+               "row_ss": np.array(res.row_ss[:R], dtype=np.float64),
+               "classes_used": grid(lambda p: p.classes_used, np.int64), "cells_used": grid(lambda p: p.cells_used, np.int64),
+               "delta_num": grid(lambda p: p.delta_num, np.int64)}
+        for key in ("eta2", "eta2_adj", "f_stat"):
+            out[key] = grid(lambda p, key=key: getattr(p, key))
+        for key in ("delta", "ks_max", "ks_median", "mi"):
+            out[key] = {"estimate": grid(lambda p, key=key: getattr(p, key).estimate),
+                        "null_mean": grid(lambda p, key=key: getattr(p, key).null_mean),
+                        "null_hi": grid(lambda p, key=key: getattr(p, key).null_hi),
+                        "exceed": grid(lambda p, key=key: getattr(p, key).exceed, np.int64)}
+        if want_tables:
+            out["tables"] = tables
+        if want_curves:
+            out["class_stats"] = curves
+        if want_null:
+            out["null_values"] = null
+        return out
+
     def _seeds_on_device(self, seeds):
         """The 32-bit seeds of the device streams: n."""
         if not (seeds.is_cuda and seeds.device == self.device and seeds.dtype in (torch.uint32, torch.int32)

@@ -662,6 +662,27 @@ class MonteCarloAnalyzer:
         row, saved as monte_carlo_sobol.png in the output directory; returns that directory."""
         return plots.plot_sobol(self, sobol, save_plots)
 
+    def given_data_sensitivity(self, analysis, rows=None, **kw):
+        """Which dispersion drives what without assuming a monotone response, from the run itself (no reference
+        counterpart, no extra flights): `analysis.given_data_sensitivity` - eta2 with its main-effect curves, delta, the
+        KS statistics and the mutual information, each next to its null band - on either kind of analysis dict, exactly
+        as `drivers` takes its inputs.  kw: classes, cells, shifts, level, seed, want_tables, want_null."""
+        from . import analysis as ana
+        eng = shared_engine(self.device)
+        if "factors" in analysis:
+            return ana.given_data_sensitivity(analysis["summary"], analysis["factors"], analysis["factor_names"],
+                                              status=analysis.get("status"), engine=eng, rows=rows, **kw)
+        fac, names = ana.factors_from_results(analysis["results"])
+        summ = ana.summary_from_results(analysis["results"])
+        return ana.given_data_sensitivity(torch.as_tensor(summ, device=eng.device).contiguous(),
+                                          torch.as_tensor(fac, device=eng.device).contiguous(), names, engine=eng, rows=rows,
+                                          **kw)
+
+    def plot_given_data_sensitivity(self, sensitivity, save_plots=True, top=4):
+        """No reference counterpart: per row the delta of every factor with its null band and the main-effect curves of the
+        `top` factors, saved as monte_carlo_given_data.png in the output directory; returns that directory."""
+        return plots.plot_given_data_sensitivity(self, sensitivity, save_plots, top)
+
     def impact_probability(self, analysis, **kw):
         """Where it comes down, as probabilities (no reference counterpart): `analysis.impact_probability` - the kernel
         density of the impact points, the thresholds of the regions that hold 50 / 90 / 99 % of the landings and the

@@ -306,6 +306,53 @@ def sobol_figure(result):
     return fig
 
 
+def given_data_figure(result, top=4):
+    """The dict of analysis.given_data_sensitivity: per row two panels.  Left: delta of every factor as a bar, in the order
+    of `factor_names`, with the null band - a tick at null_mean and a line up to null_hi - where there are shifts; a bar
+    that does not clear its band is indistinguishable from no effect.  Right: the main-effect curves (the conditional mean
+    of the row along the class centres, +- the conditional std as a band) of the `top` factors of the row's ranking, each
+    against the factor's rank-scaled axis (class index / classes) so that factors of different units share it."""
+    names = list(result["factor_names"])
+    rows = list(result["row_names"])
+    k = len(names)
+    fig = _figure((max(9.0, 0.5 * k + 7.0), 3.2 * len(rows) + 0.8))
+    axes = np.asarray(fig.subplots(len(rows), 2, squeeze=False))
+    x = np.arange(k, dtype=np.float64)
+    delta = result["delta"]
+    for j, row in enumerate(rows):
+        ax = axes[j, 0]
+        est = np.asarray(delta["estimate"], dtype=np.float64)[j]
+        mean = np.asarray(delta["null_mean"], dtype=np.float64)[j]
+        hi = np.asarray(delta["null_hi"], dtype=np.float64)[j]
+        ax.bar(x, np.nan_to_num(est, nan=0.0), width=0.6, color="tab:blue", label="delta")
+        have = np.isfinite(mean) & np.isfinite(hi)
+        if have.any():
+            ax.errorbar(x[have], mean[have], yerr=np.vstack([np.zeros(int(have.sum())), np.maximum(hi[have] - mean[have], 0.0)]),
+                        fmt="_", color="black", ecolor="black", capsize=3, linewidth=0.8,
+                        label=f"null mean .. {100 * float(result['level']):g} %")
+        ax.set_ylabel(row)
+        ax.set_title(f"{row}: delta of {int(result['count'])} samples", fontsize=9)
+        ax.set_xticks(x)
+        ax.set_xticklabels(names if j == len(rows) - 1 else [""] * k, rotation=45, ha="right")
+        ax.grid(True, axis="y", alpha=0.3)
+        if j == 0:
+            ax.legend(loc="best", fontsize=8)
+        ax = axes[j, 1]
+        for name in list(result["ranking"][j])[:top]:
+            c = result["curves"][j][name]
+            m, s = np.asarray(c["mean"], dtype=np.float64), np.asarray(c["std"], dtype=np.float64)
+            u = (np.arange(len(m)) + 0.5) / max(len(m), 1)
+            (line,) = ax.plot(u, m, marker="o", markersize=3, linewidth=1.2, label=name)
+            ax.fill_between(u, m - s, m + s, alpha=0.12, color=line.get_color(), linewidth=0)
+        ax.set_title(f"{row}: main effects", fontsize=9)
+        ax.set_xlabel("factor quantile" if j == len(rows) - 1 else "")
+        ax.grid(True, alpha=0.3)
+        ax.legend(loc="best", fontsize=7)
+    fig.suptitle(f"Given-data sensitivity ({int(result['classes'])} x {int(result['cells'])} classes, {int(result['shifts'])} shifts)")
+    fig.tight_layout()
+    return fig
+
+
 def save_figure(fig, output_dir, name):
     path = os.path.join(output_dir, name)
     fig.savefig(path, dpi=DPI, bbox_inches="tight")
@@ -499,4 +546,15 @@ def plot_sobol(analyzer, sobol, save_plots=True):
     if save_plots:
         output_dir = analyzer._create_output_directory()
         print(f"Sobol indices plot saved to: {save_figure(fig, output_dir, 'monte_carlo_sobol.png')}")
+    return output_dir
+
+
+def plot_given_data_sensitivity(analyzer, sensitivity, save_plots=True, top=4):
+    """The measures of MonteCarloAnalyzer.given_data_sensitivity (no reference counterpart) as monte_carlo_given_data.png;
+    returns the output directory (None without save_plots)."""
+    fig = given_data_figure(sensitivity, top)
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Given-data sensitivity plot saved to: {save_figure(fig, output_dir, 'monte_carlo_given_data.png')}")
     return output_dir

@@ -970,6 +970,101 @@ int erpl_mc_sobol_defaults(erpl_sobol_spec* spec);
 int erpl_mc_sobol(erpl_ctx* ctx, const double* summary, const double* extra, const uint8_t* mask, int64_t n_base, int64_t ld,
                   const erpl_sobol_spec* spec, erpl_sobol* result, double* replicates_out, void* hip_stream);
 
+/* Which dispersion drives what, from the (factor, outcome) pairs of ONE ordinary run, ON THE DEVICE: the given-data
+ * sensitivity measures - the first-order variance share eta^2 (the correlation ratio, Plischke 2010) with its main-effect
+ * curve, Borgonovo's moment-independent delta, the PAWN Kolmogorov-Smirnov statistics and the mutual information - of up to
+ * 32 factors on up to 4 outcomes, each with the value a factor without any effect would get at this sample size.  No extra
+ * flights: it fills the gap between erpl_mc_correlation (linear / monotone dependence only) and erpl_mc_sobol (needs a
+ * pick-freeze design).  The reference has nothing like it.
+ *
+ * Input, conventions of erpl_mc_correlation and erpl_mc_bootstrap: `factors` [n_factors][n], `summary`
+ * [ERPL_SUMMARY_DIM][n], `extra` [n] (NULL unless a row is ERPL_DEP_ROW_EXTRA) and `mask` [n] (NULL: every sample counts)
+ * are caller-owned device memory; spec, result and the optional outputs `tables`, `class_stats`, `null_out` are HOST
+ * memory, each may be NULL.  The work is enqueued on `hip_stream` behind what is there and the call returns when the
+ * result is filled; the workspace belongs to the context, grows only (about n (29 + 8 n_rows + n_factors + 2 n_rows) bytes
+ * plus the sort's scratch and the outputs) and is freed by erpl_mc_destroy.
+ *
+ * Population: ONE, by listwise deletion - mask byte 0 AND every factor finite AND every requested row finite - in ascending
+ * sample order; dense index d is its d-th member, m = count; n_masked and n_non_finite as in erpl_corr_result.
+ * Classes: every variable gets its exact 1-based mid-rank r within the population (ties averaged, -0.0 ties with +0.0, as
+ * erpl_mc_correlation).  A factor's class is c = ((2 r - 1) classes) div (2 m), an outcome's cell h = ((2 r - 1) cells)
+ * div (2 m), in integers: tied values share a class, a constant variable lies in class (classes div 2) alone.
+ * Tables: T[c][h] counts the members with class c and cell h; n_c its row sums, col_h its column sums, cumT and cumcol the
+ * running sums over h.  In exact 64-bit integers (m < 2^31), then IEEE double operations without contraction:
+ *   delta_num = sum_c sum_h |m T[c][h] - n_c col_h|,  delta = (double)delta_num / ((2.0 (double)m) (double)m)
+ *   ks_c      = (double)max_h |m cumT[c][h] - n_c cumcol_h| / ((double)m (double)n_c)   for every non-empty class
+ *   ks_max    = the largest ks_c;  ks_median = the median of the ks_c (the mean of the two middle ones)
+ *   mi        = sum over the non-empty cells of ((double)T / (double)m) log(((double)T (double)m) / ((double)n_c (double)col_h))
+ * mi is summed in this order: thread t of 256 takes the cells t q .. t q + q - 1 (c-major, q = ceil(classes cells / 256))
+ * in ascending order, the threads are folded in the fixed order of the other analysis calls; it uses the device log.
+ * Null: for p < shifts the shift is s_p = 1 + (draw t = p of replicate 0 among m - 1 of erpl_mc_bootstrap), that is
+ * erpl_mc_bootstrap_indices(seed, 0, m - 1, p, 1)[0] + 1, in 1..m - 1; null table p pairs class byte d of the factor with
+ * cell byte (d + s_p) mod m of the outcome.  The samples of an ordinary run are exchangeable, so a cyclic re-pairing is a
+ * draw under independence that keeps both margins to the count.  A PICK-FREEZE DESIGN (erpl_mc_sobol) IS NOT SUCH A RUN:
+ * its blocks repeat each other's inputs.  The four measures of every null table are formed by the workgroup that built it,
+ * by the operations above.  Per measure: null_mean, the mean of the null values in ascending p; null_hi, their quantile
+ * `level` (linear interpolation, as np.quantile); exceed, the number of null values >= estimate.  shifts == 0 or m < 2:
+ * NaN, NaN and 0.
+ * Variance share: per (row, factor, class) count, sum and, in a second pass, sum (y - mean_c)^2: the members of the class
+ * in the sort's (key, dense index) order, thread t of 256 taking members t, t + 256, .., folded in the fixed order.  With
+ * row_mean and row_ss = sum (y - row_mean)^2 (the passes of erpl_mc_analyze), B = sum_c n_c (mean_c - row_mean)^2 over c
+ * ascending and k = classes_used: eta2 = B / row_ss, eta2_adj = 1 - (1 - eta2) (m - 1) / (m - k), f_stat = (B / (k - 1)) /
+ * ((row_ss - B) / (m - k)).  A constant row: all three NaN; k < 2: eta2 = 0, the others NaN; m <= k: eta2_adj, f_stat NaN.
+ * count == 0: every double NaN, every integer 0, no error.  No floating-point atomics: two calls on the same inputs return
+ * the same bytes in `result` and in the three optional outputs.
+ * Optional outputs: tables int64 [n_rows][n_factors][classes][cells]; class_stats double [n_rows][n_factors][classes][6] =
+ * count, mean, std (population, two passes), x_lo, x_hi (the smallest and largest factor value of the class) and x_median
+ * (the factor value of the middle member in sorted order, the lower of two) - the main-effect curve; an empty class has
+ * count 0 and NaN elsewhere; null_out double [n_rows][n_factors][4][shifts]: the null values of delta, ks_max, ks_median, mi.
+ *
+ * Errors: ERPL_ERR_INVALID, before any device work and with a message that names the argument, in this order: a NULL spec,
+ * factors, summary or result; n <= 0 or n >= 2^31; n_factors outside 1..32; n_rows outside 1..4; a row outside 0..16 or
+ * listed twice; row 16 without `extra`; classes outside 2..64; cells outside 2..64; shifts outside 0..4096; null_out with
+ * shifts == 0; level not in (0, 1) (looked at only when shifts > 0); the context last. */
+#define ERPL_DEP_MAX_FACTORS 32
+#define ERPL_DEP_MAX_ROWS 4
+#define ERPL_DEP_ROW_EXTRA 16            /* = ERPL_BOOT_ROW_EXTRA: the caller's device row `extra`, e.g. the miss distance */
+#define ERPL_DEP_MAX_CLASSES 64          /* M: classes of a factor */
+#define ERPL_DEP_MAX_CELLS 64            /* H: cells of an outcome */
+#define ERPL_DEP_MAX_SHIFTS 4096         /* P: null re-pairings */
+
+typedef struct erpl_dep_spec {
+  int32_t n_factors;                     /* 1..ERPL_DEP_MAX_FACTORS */
+  int32_t n_rows;                        /* 1..ERPL_DEP_MAX_ROWS */
+  int32_t rows[ERPL_DEP_MAX_ROWS];       /* distinct; 0..15 = summary rows, ERPL_DEP_ROW_EXTRA = `extra` */
+  int32_t classes, cells;                /* 2..64 each */
+  int32_t shifts;                        /* 0..ERPL_DEP_MAX_SHIFTS; 0 = no null */
+  int32_t reserved;
+  double level;                          /* in (0, 1); looked at only if shifts > 0 */
+  uint64_t seed;
+} erpl_dep_spec;
+
+typedef struct erpl_dep_measure {
+  double estimate, null_mean, null_hi;
+  int64_t exceed;                        /* null values >= estimate */
+} erpl_dep_measure;
+
+typedef struct erpl_dep_pair {           /* one (row, factor) */
+  int32_t classes_used, cells_used;      /* non-empty classes / cells */
+  int64_t delta_num;                     /* the exact integer numerator of delta */
+  erpl_dep_measure delta, ks_max, ks_median, mi;
+  double eta2, eta2_adj, f_stat;
+} erpl_dep_pair;
+
+typedef struct erpl_dependence {
+  int64_t n, count, n_masked, n_non_finite;   /* count + n_masked + n_non_finite == n */
+  int32_t n_factors, n_rows, classes, cells, shifts, reserved;
+  double row_mean[ERPL_DEP_MAX_ROWS], row_ss[ERPL_DEP_MAX_ROWS];   /* mean and sum((y - mean)^2) of the row */
+  erpl_dep_pair pair[ERPL_DEP_MAX_ROWS][ERPL_DEP_MAX_FACTORS];     /* of spec->rows[j] and factor f */
+} erpl_dependence;
+
+/* Host only: rows {APOGEE_ALT, RANGE, FLIGHT_TIME}, classes = cells = 16, 200 shifts, level 0.95, seed 0, n_factors = 0 (the
+ * caller fills it in). */
+int erpl_mc_dependence_defaults(erpl_dep_spec* spec);
+int erpl_mc_dependence(erpl_ctx* ctx, const double* factors, const double* summary, const double* extra,
+                       const uint8_t* mask, int64_t n, const erpl_dep_spec* spec, erpl_dependence* result,
+                       int64_t* tables, double* class_stats, double* null_out, void* hip_stream);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
