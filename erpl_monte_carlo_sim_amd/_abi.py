@@ -323,6 +323,40 @@ class ErplDependence(C.Structure):
                 ("pair", (ErplDepPair * DEP_MAX_FACTORS) * DEP_MAX_ROWS)]
 
 
+# erpl_mc_compare
+CMP_MAX_ROWS = 4
+CMP_ROW_EXTRA = 16
+CMP_MAX_PERMUTATIONS = 4096
+CMP_ENERGY_MAX_POINTS = 65536
+
+
+class ErplCmpSpec(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("rows", C.c_int32 * CMP_MAX_ROWS), ("n_q", C.c_int32), ("row_x", C.c_int32),
+                ("row_y", C.c_int32), ("permutations", C.c_int32), ("reserved", C.c_int32),
+                ("q", C.c_double * ANALYSIS_MAX_Q), ("level", C.c_double), ("seed", C.c_uint64)]
+
+
+class ErplCmpTest(C.Structure):
+    _fields_ = [("statistic", C.c_double), ("p_value", C.c_double), ("null_mean", C.c_double), ("null_hi", C.c_double),
+                ("exceed", C.c_int64)]
+
+
+class ErplCmpRow(C.Structure):
+    _fields_ = [("mean_a", C.c_double), ("std_a", C.c_double), ("mean_b", C.c_double), ("std_b", C.c_double),
+                ("quantile_a", C.c_double * ANALYSIS_MAX_Q), ("quantile_b", C.c_double * ANALYSIS_MAX_Q),
+                ("shift", C.c_double * ANALYSIS_MAX_Q), ("ks_num", C.c_int64), ("u2_a", C.c_int64), ("ks_at", C.c_double),
+                ("ks_sign", C.c_int32), ("reserved", C.c_int32), ("prob_superiority", C.c_double),
+                ("ks", ErplCmpTest), ("mw", ErplCmpTest), ("cvm", ErplCmpTest)]
+
+
+class ErplCompare(C.Structure):
+    _fields_ = [("n_a", C.c_int64), ("n_b", C.c_int64), ("count_a", C.c_int64), ("count_b", C.c_int64),
+                ("n_masked_a", C.c_int64), ("n_masked_b", C.c_int64), ("n_non_finite_a", C.c_int64),
+                ("n_non_finite_b", C.c_int64), ("n_rows", C.c_int32), ("n_q", C.c_int32), ("permutations", C.c_int32),
+                ("bivariate", C.c_int32), ("row", ErplCmpRow * CMP_MAX_ROWS),
+                ("d_ab", C.c_double), ("d_aa", C.c_double), ("d_bb", C.c_double), ("energy", ErplCmpTest)]
+
+
 LIB_NAME = "liberpl_mc.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
@@ -347,6 +381,7 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_corridor_defaults", "erpl_mc_corridor_resample", "erpl_mc_corridor_bands",
            "erpl_mc_sobol_defaults", "erpl_mc_sobol",
            "erpl_mc_dependence_defaults", "erpl_mc_dependence",
+           "erpl_mc_compare_defaults", "erpl_mc_compare", "erpl_mc_compare_labels",
            "erpl_mc_legacy_random_streams_device", "erpl_mc_legacy_wind_profiles_device")
 
 _lib = None
@@ -445,6 +480,10 @@ def load_library(path=None):
     lib.erpl_mc_dependence_defaults.argtypes = [C.POINTER(ErplDepSpec)]
     lib.erpl_mc_dependence.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplDepSpec),
                                        C.POINTER(ErplDependence), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erpl_mc_compare_defaults.argtypes = [C.POINTER(ErplCmpSpec)]
+    lib.erpl_mc_compare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_void_p, C.POINTER(ErplCmpSpec), C.POINTER(ErplCompare), C.c_void_p, C.c_void_p]
+    lib.erpl_mc_compare_labels.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]
     lib.erpl_mc_legacy_random_streams_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                                          C.c_int32, C.c_void_p]
     lib.erpl_mc_legacy_wind_profiles_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 9 + \

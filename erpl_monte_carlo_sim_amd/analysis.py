@@ -594,3 +594,61 @@ def finish_given_data(out):
                                 "count": cs[j, f, used, 0].astype(np.int64)}
         out["curves"].append(per_factor)
     return out
+
+
+# ---------------------------------------------------------------------------------- two runs: the same law?
+def permutation_labels(seed, permutation, m_a, m_b):
+    """Side A (True) of permutation `permutation` of erpl_mc_compare with `seed`, for m_a + m_b pooled members (A's counted
+    samples in sample order, then B's): erpl_mc_compare_labels, the host copy of the device's labels.  Exactly m_a are
+    True.  Needs the library, no GPU."""
+    from . import _abi
+    lib = _abi.load_library()
+    out = np.empty(max(int(m_a) + int(m_b), 0), dtype=np.uint8)
+    _abi.check(lib, lib.erpl_mc_compare_labels(int(seed) & 0xFFFFFFFFFFFFFFFF, int(permutation), int(m_a), int(m_b),
+                                               out.ctypes.data), "erpl_mc_compare_labels")
+    return out.astype(bool)
+
+
+COMPARE_TESTS = (("ks", "Kolmogorov-Smirnov"), ("mw", "Mann-Whitney"), ("cvm", "Cramer-von Mises"))
+
+
+def compare_runs(a, b, status_a=None, status_b=None, engine=None, **kw):
+    """Two runs side by side: each summary ([16, n] float64 on the device, with its status or None, as `native_statistics`
+    takes them) goes through the outlier filter of erpl_mc_analyze, then erpl_mc_compare tests the two filtered populations
+    (keywords of TrajectoryEngine.compare: rows, quantiles, xy, permutations, level, seed, keep_null, extra_a, extra_b).
+    Returns that dict plus 'n_samples_a' / 'n_samples_b' / 'n_outliers_a' / 'n_outliers_b', per row 'name', 'p_values'
+    ({ks, mw, cvm}) and 'verdict', and 'energy_verdict': one line each, at 1 - level.  Without permutations there are no
+    p-values and the verdicts say so."""
+    engine, res_a, why_a = _filter(a, status_a, engine)
+    _, res_b, why_b = _filter(b, status_b, engine)
+    out = engine.compare(a, b, mask_a=why_a, mask_b=why_b, **kw)
+    out["n_samples_a"], out["n_samples_b"] = int(res_a.n_valid), int(res_b.n_valid)
+    out["n_outliers_a"], out["n_outliers_b"] = int(res_a.n_outliers), int(res_b.n_outliers)
+    return finish_comparison(out)
+
+
+def finish_comparison(out):
+    """Row names, p-values and the one-line verdicts of a TrajectoryEngine.compare dict (in place; returns it)."""
+    alpha = 1.0 - out["level"]
+    tested = out["permutations"] > 0 and out["count_a"] > 0 and out["count_b"] > 0
+    for r, row in zip(out["rows"], out["row"]):
+        row["name"] = ROW_NAMES[r] if 0 <= r < len(ROW_NAMES) else "extra"
+        row["p_values"] = {k: row[k]["p_value"] for k, _ in COMPARE_TESTS}
+        if not tested:
+            row["verdict"] = f"{row['name']}: not tested (no permutations or an empty run)"
+            continue
+        hit = [full for k, full in COMPARE_TESTS if row[k]["p_value"] <= alpha]
+        shift = row["mean_b"] - row["mean_a"]
+        row["verdict"] = (f"{row['name']}: differs at {alpha:.3g} ({', '.join(hit)}; mean shift {shift:+.6g}, "
+                          f"P(A > B) = {row['prob_superiority']:.3f})" if hit else
+                          f"{row['name']}: no difference at {alpha:.3g} (smallest p = {min(row['p_values'].values()):.3g})")
+    e = out.get("energy")
+    if e is None:
+        out["energy_verdict"] = "impact clouds: not tested"
+    elif not tested:
+        out["energy_verdict"] = f"impact clouds: E = {e['statistic']:.6g}, not tested (no permutations)"
+    else:
+        out["energy_verdict"] = (f"impact clouds: {'differ' if e['p_value'] <= alpha else 'no difference'} at {alpha:.3g} "
+                                 f"(E = {e['statistic']:.6g}, null {100 * out['level']:.0f} % = {e['null_hi']:.6g}, "
+                                 f"p = {e['p_value']:.3g})")
+    return out

@@ -83,6 +83,13 @@ struct DepHost {
   ErplDepEst est[ERPL_DEP_MAX_ROWS * ERPL_DEP_MAX_FACTORS];
 };
 
+// erpl_mc_compare: pinned copies of what its launches hand back - per side the population counters and the moments and order
+// statistics of the requested rows (summary rows, `extra`)
+struct CmpHost {
+  unsigned long long counter[2][4];
+  ErplAnaResult rows[2][2];
+};
+
 // The only place a per-context device buffer grows (the policy of erpl_mc_reserve): never shrinks, freed by
 // erpl_mc_destroy.  An earlier call on another stream may still read the old buffer, hence the device synchronise.
 template <typename T>
@@ -208,6 +215,11 @@ struct erpl_ctx {
   // erpl_mc_dependence: the records of the pairs' own tables in the fixed block, the pieces of erpl_stat_layout.h in the
   // buffer; its population pass runs on the block of `corr`, its row moments on that of `ana`
   ErplStatUnit<ErplDepWork, DepHost> dep;
+  // erpl_mc_compare: two buffers, both laid out by erpl_compare_layout - `cmp_pop` for the populations of the two runs, sized
+  // by (n_a, n_b), and `cmp` for the pooled members, sized once the populations are counted; its population pass runs on
+  // the block of `corr`, its row moments on that of `ana`
+  ErplStatUnit<void, CmpHost> cmp;
+  ErplStatUnit<void, char> cmp_pop;
   // erpl_mc_legacy_random_streams_device / _wind_profiles_device: one device buffer (flag, op tables, knot constants, the
   // MT19937 states of a tile and two sets of its accepted pairs) and its pinned staging (the tables on their way up, r2
   // down and f up, per set), both bounded by the tile; an event per set behind the tile's copy to the host

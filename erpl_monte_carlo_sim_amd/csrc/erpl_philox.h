@@ -1,6 +1,6 @@
-// erpl_philox.h — the draws of erpl_mc_bootstrap and erpl_mc_sobol, one definition for the host (erpl_mc_bootstrap_indices)
-// and the device (erpl_boot_replicate in erpl_bootstrap.hip, erpl_sobol_replicate in erpl_sobol.hip).  Internal: never
-// installed.
+// erpl_philox.h — the draws of erpl_mc_bootstrap, erpl_mc_sobol and erpl_mc_compare, one definition for the host
+// (erpl_mc_bootstrap_indices, erpl_mc_compare_labels) and the device (erpl_boot_replicate in erpl_bootstrap.hip,
+// erpl_sobol_replicate in erpl_sobol.hip, the label passes of erpl_compare.hip).  Internal: never installed.
 //
 // The generator is Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC 2011):
 // ten rounds of two 32 x 32 -> 64 bit multiplies (0xD2511F53, 0xCD9E8D57), the key bumped by (0x9E3779B9, 0xBB67AE85)
@@ -9,6 +9,8 @@
 //   counter  (j & 0xffffffff, j >> 32, b, 0): b the replicate, j the index of a PAIR of draws
 //   words    o0..o3 -> A = o0 | o1 << 32 (draw 2j), B = o2 | o3 << 32 (draw 2j + 1)
 //   index    (u * m) >> 64 of a 64-bit draw u: a dense population index below m, bias at most m / 2^64
+//   label    erpl_mc_compare: the key of pooled member i in permutation p is draw i of replicate p; side A is the m_a members
+//            with the smallest (key, i) pairs.  With (thr_key, thr_idx) the m_a-th smallest pair, the label is one comparison.
 #pragma once
 #include <stdint.h>
 
@@ -49,4 +51,16 @@ ERPL_PHILOX_HD uint64_t erpl_boot_index(uint64_t u, uint64_t m) {
 #else
   return (uint64_t)(((unsigned __int128)u * m) >> 64);
 #endif
+}
+
+// the 64-bit draw t of replicate b
+ERPL_PHILOX_HD uint64_t erpl_boot_draw(uint64_t seed, uint32_t b, uint64_t t) {
+  uint64_t A, B;
+  erpl_boot_pair(seed, b, t >> 1, &A, &B);
+  return (t & 1) ? B : A;
+}
+
+// erpl_mc_compare: is the pooled member i with the key `key` on side A, (thr_key, thr_idx) being the m_a-th smallest pair?
+ERPL_PHILOX_HD bool erpl_cmp_label(uint64_t key, uint64_t i, uint64_t thr_key, uint64_t thr_idx) {
+  return key < thr_key || (key == thr_key && i <= thr_idx);
 }

@@ -1,7 +1,7 @@
 // erpl_stat_device.h — what the statistics units (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip,
-// erpl_bootstrap.hip, erpl_density.hip, erpl_corridor.hip, erpl_sobol.hip, erpl_dependence.hip) share: the grid of their
-// streaming passes, the order-preserving keys, the run of equal keys behind a mid-rank, THE fixed-order reduction and the
-// steps of the radix selection.
+// erpl_bootstrap.hip, erpl_density.hip, erpl_corridor.hip, erpl_sobol.hip, erpl_dependence.hip, erpl_compare.hip) share:
+// the grid of their streaming passes, the order-preserving keys, the run of equal keys behind a mid-rank, THE fixed-order
+// reduction and the steps of the radix selection.
 // Internal: never installed.
 //
 // The order is the contract: the last bit of every sum and the sign of a zero minimum depend on it, and "the same bits in

@@ -1,8 +1,9 @@
-// erpl_stat_layout.h — how erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density, erpl_mc_sobol and
-// erpl_mc_dependence cut the device buffer each of them grows into pieces: pure functions of the call's sizes (no HIP; the
-// scratch size of the rocPRIM calls comes in as a number), so that tests/test_stat_layout.py and
-// tests/test_dependence_layout.py check every offset on the CPU, through erpl_stat_layout_table, before a kernel writes
-// through one.  Every piece starts at a multiple of 256 bytes; `need` is the end of the last one.
+// erpl_stat_layout.h — how erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density, erpl_mc_sobol,
+// erpl_mc_dependence and erpl_mc_compare cut the device buffer each of them grows into pieces: pure functions of the call's
+// sizes (no HIP; the scratch size of the rocPRIM calls comes in as a number), so that tests/test_stat_layout.py,
+// tests/test_dependence_layout.py and tests/test_compare_layout.py check every offset on the CPU, through
+// erpl_stat_layout_table, before a kernel writes through one.  Every piece starts at a multiple of 256 bytes; `need` is the
+// end of the last one.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -139,5 +140,60 @@ inline ErplDepLayout erpl_dep_layout(int64_t n, int F, int R, int M, int H, int 
   l.tab = c.take(8 * pairs * (size_t)M * (size_t)H);
   l.null = c.take(8 * 4 * pairs * (size_t)P);
   l.need = c.end;
+  return l;
+}
+
+// erpl_mc_compare keeps TWO buffers, because the pooled size N = m_a + m_b is known only after the populations are counted.
+// The population buffer, a function of (n_a, n_b): [pop_a n_a bytes][src_a n_a u32][pop_b n_b bytes][src_b n_b u32][counts 2 u64]
+// [scratch of the select]; pop_need is its end.
+// The pooled buffer, a function of (N, R, P, bivariate): [val R rows of N doubles][xy N (x, y), bivariate][keys 2N u64][idx 2N u32]
+// [scratch of the sort][sidx R rows of N u32][r2e R rows of N u64][thr words 64 (key, index)][bits N wb u64][cnt chunks wb 64
+// u32][part chunks wb 64 records of 64 bytes][rank R words 64 records][at_value R doubles][epart tiles slices wb 64 3 doubles,
+// bivariate][eout words 64 3 doubles]; words = ceil((P + 1) / 64), wb = erpl_cmp_block_words, chunks = erpl_cmp_chunks, tiles =
+// ceil(N / ERPL_CMP_TILE), slices = erpl_cmp_slices (erpl_tables.h).  N == 0: the pooled buffer is empty, need = 0.
+struct ErplCompareLayout {
+  size_t pop_a, src_a, pop_b, src_b, count, sel_temp, sel_bytes, pop_need;
+  size_t val[ERPL_CMP_MAX_ROWS], xy, keys, idx, temp, sidx[ERPL_CMP_MAX_ROWS], r2e[ERPL_CMP_MAX_ROWS], thr, bits, cnt, part, rank,
+      at_value, epart, eout, temp_bytes, need;
+  int words, wb, chunks, slices;
+};
+inline ErplCompareLayout erpl_compare_layout(int64_t n_a, int64_t n_b, int64_t N, int R, int P, bool bivariate, size_t select_bytes,
+                                             size_t sort_bytes) {
+  const size_t ua = (size_t)n_a, ub = (size_t)n_b, uN = (size_t)N, uR = (size_t)R;
+  ErplCompareLayout l = {};
+  ErplCarve c;
+  l.pop_a = c.take(ua);
+  l.src_a = c.take(4 * ua);
+  l.pop_b = c.take(ub);
+  l.src_b = c.take(4 * ub);
+  l.count = c.take(16);
+  l.sel_bytes = erpl_scratch_piece(select_bytes);
+  l.sel_temp = c.take(l.sel_bytes);
+  l.pop_need = c.end;
+  l.words = erpl_cmp_words(P);
+  if (N <= 0) return l;
+  int64_t len, per_slice;
+  l.wb = erpl_cmp_block_words(N, P);
+  l.chunks = erpl_cmp_chunks(N, l.wb, &len);
+  l.slices = erpl_cmp_slices(N, l.wb, &per_slice);
+  const size_t cols = (size_t)l.wb * 64, all = (size_t)l.words * 64, tiles = (uN + ERPL_CMP_TILE - 1) / ERPL_CMP_TILE;
+  ErplCarve d;
+  for (int j = 0; j < R; ++j) l.val[j] = d.take(8 * uN);
+  l.xy = d.take(bivariate ? 16 * uN : 0);
+  l.keys = d.take(16 * uN);
+  l.idx = d.take(8 * uN);
+  l.temp_bytes = erpl_scratch_piece(sort_bytes);
+  l.temp = d.take(l.temp_bytes);
+  for (int j = 0; j < R; ++j) l.sidx[j] = d.take(4 * uN);
+  for (int j = 0; j < R; ++j) l.r2e[j] = d.take(8 * uN);
+  l.thr = d.take(16 * all);
+  l.bits = d.take(8 * uN * (size_t)l.wb);
+  l.cnt = d.take(4 * (size_t)l.chunks * cols);
+  l.part = d.take(64 * (size_t)l.chunks * cols);
+  l.rank = d.take(64 * uR * all);
+  l.at_value = d.take(8 * uR);
+  l.epart = d.take(bivariate ? 8 * 3 * cols * tiles * (size_t)l.slices : 0);
+  l.eout = d.take(8 * 3 * all);
+  l.need = d.end;
   return l;
 }

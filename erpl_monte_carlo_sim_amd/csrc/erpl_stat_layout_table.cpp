@@ -8,6 +8,10 @@
 //   sobol <n> <k> <R> <B> <caller_keeps_replicates> <temp_bytes>         -> pop src[R] count rec[R] temp rep temp_bytes need
 //   dep <n> <F> <R> <M> <H> <P> <temp_bytes>                             -> pop src count yd[R] xc yext keys idx temp cstat tab null
 //                                                                           x_stride y_stride temp_bytes need
+//   cmp <n_a> <n_b> <N> <R> <P> <bivariate> <select_bytes> <sort_bytes>  -> pop_a src_a pop_b src_b count sel_temp sel_bytes pop_need
+//                                                                           val[R] xy keys idx temp sidx[R] r2e[R] thr bits cnt part
+//                                                                           rank at_value epart eout temp_bytes words wb chunks
+//                                                                           slices need
 #include <stdio.h>
 
 #include <initializer_list>
@@ -19,9 +23,9 @@ static void put(size_t v, const char* end = " ") { printf("%zu%s", v, end); }
 int main() {
   char line[256];
   while (fgets(line, sizeof(line), stdin)) {
-    long long n, nodes;
+    long long n, nodes, big;
     int a, b, c, d, e;
-    size_t temp;
+    size_t temp, temp2;
     if (sscanf(line, "corr %lld %d %d %d %zu", &n, &a, &b, &c, &temp) == 5) {
       const ErplCorrLayout l = erpl_corr_layout(n, a, b != 0, c != 0, temp);
       for (size_t v : {l.keys, l.ranks, l.idx, l.temp, l.pop, l.temp_bytes}) put(v);
@@ -50,6 +54,17 @@ int main() {
       for (size_t v : {l.pop, l.src, l.count}) put(v);
       for (int j = 0; j < b; ++j) put(l.yd[j]);
       for (size_t v : {l.xc, l.yext, l.keys, l.idx, l.temp, l.cstat, l.tab, l.null, l.x_stride, l.y_stride, l.temp_bytes}) put(v);
+      put(l.need, "\n");
+    } else if (sscanf(line, "cmp %lld %lld %lld %d %d %d %zu %zu", &n, &nodes, &big, &a, &b, &c, &temp, &temp2) == 8 && a >= 1 &&
+               a <= ERPL_CMP_MAX_ROWS) {
+      const ErplCompareLayout l = erpl_compare_layout(n, nodes, big, a, b, c != 0, temp, temp2);
+      for (size_t v : {l.pop_a, l.src_a, l.pop_b, l.src_b, l.count, l.sel_temp, l.sel_bytes, l.pop_need}) put(v);
+      for (int j = 0; j < a; ++j) put(l.val[j]);
+      for (size_t v : {l.xy, l.keys, l.idx, l.temp}) put(v);
+      for (const size_t* rows : {l.sidx, l.r2e})
+        for (int j = 0; j < a; ++j) put(rows[j]);
+      for (size_t v : {l.thr, l.bits, l.cnt, l.part, l.rank, l.at_value, l.epart, l.eout, l.temp_bytes}) put(v);
+      for (int v : {l.words, l.wb, l.chunks, l.slices}) put((size_t)v);
       put(l.need, "\n");
     } else {
       fprintf(stderr, "bad request: %s", line);

@@ -1,8 +1,8 @@
 // erpl_stats_api.hip — host halves of the analysis entry points of the C ABI (include/erpl_mc.h): erpl_mc_analyze,
 // erpl_mc_histogram, erpl_mc_histogram_xy, erpl_mc_dispersion, erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density,
-// erpl_mc_corridor_resample, erpl_mc_corridor_bands, erpl_mc_sobol, erpl_mc_dependence and their defaults.  Argument checks,
-// workspace, launches (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip, erpl_bootstrap.hip, erpl_density.hip,
-// erpl_corridor.hip, erpl_sobol.hip, erpl_dependence.hip)
+// erpl_mc_corridor_resample, erpl_mc_corridor_bands, erpl_mc_sobol, erpl_mc_dependence, erpl_mc_compare and their defaults.
+// Argument checks, workspace, launches (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip, erpl_bootstrap.hip,
+// erpl_density.hip, erpl_corridor.hip, erpl_sobol.hip, erpl_dependence.hip, erpl_compare.hip)
 // and what the host finishes in double precision.  The refusals come in one order
 // everywhere - spec fields, n, pointers, context (erpl_mc_bootstrap: the order its header comment lists) - and need no
 // device; tests/golden/stats_refusals.json pins their texts.  What the entry points share comes first: the pieces of the
@@ -1382,6 +1382,286 @@ int erpl_mc_dependence(erpl_ctx* c, const double* factors, const double* summary
     }
   }
   if (class_stats) memcpy(class_stats, cstat.data(), n_cstat * sizeof(double));
+  return ERPL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------- erpl_mc_compare
+namespace {
+
+typedef unsigned __int128 u128;
+
+// mean (ascending p) and the order statistic `level` (finish_null's interpolation) of the P null values of one test
+void cmp_null(const std::vector<double>& v, double level, std::vector<double>& sorted, erpl_cmp_test& o) {
+  const int P = (int)v.size();
+  double sum = 0.0;
+  for (int p = 0; p < P; ++p) sum += v[p];
+  sorted = v;
+  std::sort(sorted.begin(), sorted.end());
+  const double pos = (double)(P - 1) * level, below = floor(pos), t = pos - below;
+  const int lo = (int)below, hi = lo + 1 < P ? lo + 1 : P - 1;
+  const double a = sorted[lo], b = sorted[hi], diff = b - a;
+  o.null_mean = sum / (double)P;
+  o.null_hi = t >= 0.5 ? b - diff * (1.0 - t) : a + diff * t;
+  o.p_value = (double)(o.exceed + 1) / (double)(P + 1);
+}
+
+// T of Cramer-von Mises from the exact sums of (2 r - 2 c)^2: G = 3 (m_a S_A + m_b S_B) - 2 m_a m_b (4 m_a m_b - 1) over
+// 12 m_a m_b N, in integers while they fit (N <= 2^30: G < 2^124)
+double cmp_cvm(const ErplCmpRank& r, int64_t m_a, int64_t m_b) {
+  const int64_t N = m_a + m_b;
+  const u128 sa = ((u128)r.sa_hi << 64) | r.sa_lo, sb = ((u128)r.sb_hi << 64) | r.sb_lo;
+  if (N <= (1ll << 30)) {
+    const u128 mm = (u128)m_a * (u128)m_b;
+    const __int128 g = (__int128)(3 * ((u128)m_a * sa + (u128)m_b * sb)) - (__int128)(2 * mm * (4 * mm - 1));
+    return (double)g / (double)(12 * mm * (u128)N);
+  }
+  const long double la = (long double)m_a, lb = (long double)m_b, ln = (long double)N;
+  const long double u = (la * (long double)sa + lb * (long double)sb) / 4.0L;
+  return (double)(u / (la * lb * ln) - (4.0L * la * lb - 1.0L) / (6.0L * ln));
+}
+
+}  // namespace
+
+extern "C" {
+
+int erpl_mc_compare_defaults(erpl_cmp_spec* spec) {
+  NEED(spec);
+  memset(spec, 0, sizeof(*spec));
+  spec->n_rows = 3;
+  spec->rows[0] = ERPL_SUM_APOGEE_ALT; spec->rows[1] = ERPL_SUM_RANGE; spec->rows[2] = ERPL_SUM_FLIGHT_TIME;
+  spec->n_q = 5;
+  const double q[5] = {0.05, 0.25, 0.5, 0.75, 0.95};   // erpl_mc_analysis_defaults
+  for (int j = 0; j < 5; ++j) spec->q[j] = q[j];
+  spec->row_x = ERPL_SUM_IMPACT_X; spec->row_y = ERPL_SUM_IMPACT_Y;
+  spec->permutations = 999;
+  spec->level = 0.95;
+  spec->seed = 0;
+  return ERPL_OK;
+}
+
+int erpl_mc_compare_labels(uint64_t seed, int64_t permutation, int64_t m_a, int64_t m_b, uint8_t* out) {
+  NEED(out);
+  if (m_a < 0) return erpl_fail(ERPL_ERR_INVALID, "m_a = %lld is negative", (long long)m_a);
+  if (m_b < 0) return erpl_fail(ERPL_ERR_INVALID, "m_b = %lld is negative", (long long)m_b);
+  if (m_a >= (1ll << 32) || m_b >= (1ll << 32) || m_a + m_b == 0 || m_a + m_b >= (1ll << 32))
+    return erpl_fail(ERPL_ERR_INVALID, "m_a + m_b = %lld outside 1..2^32 - 1", (long long)(m_a + m_b));
+  if (permutation < 0 || permutation > 0xffffffffll)
+    return erpl_fail(ERPL_ERR_INVALID, "permutation = %lld outside 0..2^32 - 1", (long long)permutation);
+  const uint64_t N = (uint64_t)(m_a + m_b);
+  if (m_a == 0 || m_b == 0) {
+    memset(out, m_a > 0 ? 1 : 0, N);
+    return ERPL_OK;
+  }
+  std::vector<std::pair<uint64_t, uint64_t>> key(N);
+  for (uint64_t i = 0; i < N; ++i) key[i] = {erpl_boot_draw(seed, (uint32_t)permutation, i), i};
+  std::vector<std::pair<uint64_t, uint64_t>> pick(key);
+  std::nth_element(pick.begin(), pick.begin() + (m_a - 1), pick.end());
+  const std::pair<uint64_t, uint64_t> thr = pick[m_a - 1];   // the m_a-th smallest (key, i) pair
+  for (uint64_t i = 0; i < N; ++i) out[i] = erpl_cmp_label(key[i].first, i, thr.first, thr.second) ? 1 : 0;
+  return ERPL_OK;
+}
+
+int erpl_mc_compare(erpl_ctx* c, const double* summary_a, const uint8_t* mask_a, int64_t n_a, const double* summary_b,
+                    const uint8_t* mask_b, int64_t n_b, const double* extra_a, const double* extra_b, const erpl_cmp_spec* spec,
+                    erpl_compare* result, double* null_out, void* stream) {
+  NEED(spec); NEED(summary_a); NEED(summary_b); NEED(result);
+  if (n_a <= 0 || n_a >= (1ll << 31))
+    return erpl_fail(ERPL_ERR_INVALID, "n_a = %lld outside 1..2^31 - 1: the sort carries 32-bit pooled indices", (long long)n_a);
+  if (n_b <= 0 || n_b >= (1ll << 31))
+    return erpl_fail(ERPL_ERR_INVALID, "n_b = %lld outside 1..2^31 - 1: the sort carries 32-bit pooled indices", (long long)n_b);
+  ERPL_TRY(check_row_list(spec->rows, spec->n_rows, 1, ERPL_CMP_MAX_ROWS, ERPL_CMP_ROW_EXTRA));
+  for (int j = 0; j < spec->n_rows; ++j)
+    if (spec->rows[j] == ERPL_CMP_ROW_EXTRA && !(extra_a && extra_b))
+      return erpl_fail(ERPL_ERR_INVALID, "%s is NULL but spec->rows[%d] = %d (ERPL_CMP_ROW_EXTRA)", extra_a ? "extra_b" : "extra_a", j,
+                       spec->rows[j]);
+  ERPL_TRY(check_quantiles(spec->q, spec->n_q));
+  const bool biv = spec->row_x >= 0;
+  if (biv) ERPL_TRY(check_row_pair(spec->row_x, spec->row_y));
+  ERPL_TRY(check_int(spec->permutations, "permutations", -1, 0, ERPL_CMP_MAX_PERMUTATIONS));
+  if (null_out && spec->permutations == 0) return erpl_fail(ERPL_ERR_INVALID, "null_out is given but spec->permutations = 0");
+  if (spec->permutations > 0 && !(spec->level > 0.0 && spec->level < 1.0))
+    return erpl_fail(ERPL_ERR_INVALID, "spec->level = %g outside (0, 1)", spec->level);
+  NEED_AS(c, "ctx");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int R = spec->n_rows, nq = spec->n_q, P = spec->permutations, V = R + (biv ? 2 : 0);
+  const int64_t n_of[2] = {n_a, n_b};
+  const double* summary_of[2] = {summary_a, summary_b};
+  const double* extra_of[2] = {extra_a, extra_b};
+  const uint8_t* mask_of[2] = {mask_a, mask_b};
+  const size_t n_null = (size_t)(3 * R + 1) * (size_t)P;
+
+  size_t select_bytes = 0;
+  LAUNCH_TRY(erpl_boot_select_bytes(std::max(n_a, n_b), &select_bytes), "select sizing failed");
+  const ErplCompareLayout pl = erpl_compare_layout(n_a, n_b, 0, R, P, biv, select_bytes, 0);
+  ERPL_TRY(c->corr.first_use());   // the population passes and their counters
+  ERPL_TRY(c->ana.first_use());    // the moments and order statistics of the rows
+  ERPL_TRY(c->cmp.first_use());
+  ERPL_TRY(c->cmp_pop.grow(pl.pop_need));
+  char* pbuf = c->cmp_pop.buf;
+  CmpHost& h = *c->cmp.host;
+
+  ErplCmpArgs a;
+  memset(&a, 0, sizeof(a));
+  uint8_t* pop_of[2] = {(uint8_t*)(pbuf + pl.pop_a), (uint8_t*)(pbuf + pl.pop_b)};
+  uint32_t* src_of[2] = {(uint32_t*)(pbuf + pl.src_a), (uint32_t*)(pbuf + pl.src_b)};
+  for (int s = 0; s < 2; ++s) {
+    const size_t un = (size_t)n_of[s];
+    const double** var = s == 0 ? a.var_a : a.var_b;
+    for (int j = 0; j < R; ++j) var[j] = spec->rows[j] == ERPL_CMP_ROW_EXTRA ? extra_of[s] : summary_of[s] + (size_t)spec->rows[j] * un;
+    if (biv) { var[R] = summary_of[s] + (size_t)spec->row_x * un; var[R + 1] = summary_of[s] + (size_t)spec->row_y * un; }
+    ErplCorrArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.mask = mask_of[s]; pa.n = n_of[s]; pa.n_vars = V; pa.work = c->corr.work; pa.pop = pop_of[s];
+    for (int v = 0; v < V; ++v) pa.var[v] = var[v];
+    KERNEL_TRY(erpl_launch_corr_population(pa, stream));
+    HIP_TRY(hipMemcpyAsync(h.counter[s], &c->corr.work->out.counter[0], sizeof(h.counter[s]), hipMemcpyDeviceToHost, st));
+    ErplBootPrep p;
+    memset(&p, 0, sizeof(p));
+    p.pop = pop_of[s]; p.src = src_of[s]; p.count = (unsigned long long*)(pbuf + pl.count) + s;
+    p.temp = pbuf + pl.sel_temp; p.temp_bytes = pl.sel_bytes; p.n = n_of[s];
+    LAUNCH_TRY(erpl_launch_boot_compact(p, stream), "select failed");
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  const int64_t m_a = (int64_t)h.counter[0][0], m_b = (int64_t)h.counter[1][0], N = m_a + m_b;
+  const bool both = m_a > 0 && m_b > 0;
+  if (biv && both && N > ERPL_CMP_ENERGY_MAX_POINTS)
+    return erpl_fail(ERPL_ERR_INVALID,
+                     "the bivariate test pools %lld + %lld members, more than ERPL_CMP_ENERGY_MAX_POINTS = %d (its cost grows with "
+                     "N^2 P): spec->row_x = -1 runs the rank tests alone",
+                     (long long)m_a, (long long)m_b, ERPL_CMP_ENERGY_MAX_POINTS);
+
+  const double nan = NAN;
+  memset(result, 0, sizeof(*result));
+  result->n_a = n_a; result->n_b = n_b; result->count_a = m_a; result->count_b = m_b;
+  result->n_masked_a = (int64_t)h.counter[0][1]; result->n_masked_b = (int64_t)h.counter[1][1];
+  result->n_non_finite_a = (int64_t)h.counter[0][2]; result->n_non_finite_b = (int64_t)h.counter[1][2];
+  result->n_rows = R; result->n_q = nq; result->permutations = P; result->bivariate = biv && both ? 1 : 0;
+  auto blank = [nan](erpl_cmp_test& t) { t.statistic = t.p_value = t.null_mean = t.null_hi = nan; t.exceed = 0; };
+  for (int j = 0; j < ERPL_CMP_MAX_ROWS; ++j) {
+    erpl_cmp_row& o = result->row[j];
+    o.mean_a = o.std_a = o.mean_b = o.std_b = o.ks_at = o.prob_superiority = nan;
+    for (int k = 0; k < ERPL_ANALYSIS_MAX_Q; ++k) o.quantile_a[k] = o.quantile_b[k] = o.shift[k] = nan;
+    blank(o.ks); blank(o.mw); blank(o.cvm);
+  }
+  result->d_ab = result->d_aa = result->d_bb = nan;
+  blank(result->energy);
+
+  // per side: mean, std and quantiles, by the passes of erpl_mc_analyze over the side's samples with its population bytes
+  // as the mask: the summary rows in one launch, `extra` as a one-row summary in a second
+  int32_t est_rows[ERPL_CMP_MAX_ROWS];
+  int est_of[ERPL_CMP_MAX_ROWS], n_est = 0, has_extra = 0;   // row j of the spec: rows[s][0].row[est_of[j]], or rows[s][1].row[0] (-1)
+  for (int j = 0; j < R; ++j) {
+    if (spec->rows[j] == ERPL_CMP_ROW_EXTRA) { est_of[j] = -1; has_extra = 1; }
+    else { est_of[j] = n_est; est_rows[n_est++] = spec->rows[j]; }
+  }
+  for (int s = 0; s < 2; ++s) {
+    if (n_est > 0) ERPL_TRY(describe_rows(c, summary_of[s], pop_of[s], n_of[s], est_rows, n_est, spec->q, nq, &h.rows[s][0], st));
+    if (has_extra) ERPL_TRY(describe_rows(c, extra_of[s], pop_of[s], n_of[s], nullptr, 1, spec->q, nq, &h.rows[s][1], st));
+  }
+  auto finish_sides = [&]() {
+    for (int j = 0; j < R; ++j) {
+      erpl_row_stats sa, sb;
+      finish_row_stats(est_of[j] < 0 ? h.rows[0][1].row[0] : h.rows[0][0].row[est_of[j]], spec->q, nq, true, sa);
+      finish_row_stats(est_of[j] < 0 ? h.rows[1][1].row[0] : h.rows[1][0].row[est_of[j]], spec->q, nq, true, sb);
+      erpl_cmp_row& o = result->row[j];
+      o.mean_a = sa.mean; o.std_a = sa.std; o.mean_b = sb.mean; o.std_b = sb.std;
+      for (int k = 0; k < nq; ++k) {
+        o.quantile_a[k] = sa.quantile[k]; o.quantile_b[k] = sb.quantile[k];
+        o.shift[k] = sb.quantile[k] - sa.quantile[k];
+      }
+    }
+  };
+  if (!both) {   // an empty side: counts, the other side's description, NaN elsewhere
+    if (null_out) HIP_TRY(hipMemsetAsync(null_out, 0xff, 8 * n_null, st));   // the all-ones byte pattern is a NaN
+    HIP_TRY(hipStreamSynchronize(st));
+    finish_sides();
+    return ERPL_OK;
+  }
+
+  size_t sort_bytes = 0;
+  LAUNCH_TRY(erpl_boot_temp_bytes(N, &sort_bytes), "radix sort sizing failed");
+  const ErplCompareLayout at = erpl_compare_layout(n_a, n_b, N, R, P, biv, select_bytes, sort_bytes);
+  ERPL_TRY(c->cmp.grow(at.need));
+  char* buf = c->cmp.buf;
+  a.src_a = src_of[0]; a.src_b = src_of[1];
+  for (int j = 0; j < R; ++j) {
+    a.val[j] = (double*)(buf + at.val[j]);
+    a.sidx[j] = (uint32_t*)(buf + at.sidx[j]);
+    a.r2e[j] = (unsigned long long*)(buf + at.r2e[j]);
+  }
+  a.xy = (double*)(buf + at.xy);
+  a.keys = (unsigned long long*)(buf + at.keys); a.idx = (uint32_t*)(buf + at.idx);
+  a.temp = buf + at.temp; a.temp_bytes = at.temp_bytes;
+  a.thr = (unsigned long long*)(buf + at.thr); a.bits = (unsigned long long*)(buf + at.bits);
+  a.cnt = (uint32_t*)(buf + at.cnt); a.part = (ErplCmpRank*)(buf + at.part); a.rank = (ErplCmpRank*)(buf + at.rank);
+  a.at_value = (double*)(buf + at.at_value); a.epart = (double*)(buf + at.epart); a.eout = (double*)(buf + at.eout);
+  a.seed = spec->seed; a.N = (uint64_t)N; a.m_a = (uint64_t)m_a;
+  a.n_rows = R; a.bivariate = biv ? 1 : 0; a.permutations = P; a.words = at.words; a.wb = at.wb;
+  LAUNCH_TRY(erpl_launch_cmp_prepare(a, stream), "rank pass failed");
+  for (int w0 = 0; w0 < at.words; w0 += at.wb)   // the permutations in blocks of wb words: the label bits of one block at a time
+    KERNEL_TRY(erpl_launch_cmp_block(a, w0, std::min(at.wb, at.words - w0), stream));
+
+  const size_t Q = (size_t)P + 1, all = (size_t)at.words * 64;
+  std::vector<ErplCmpRank> rank((size_t)R * all);
+  std::vector<double> eout(3 * all), at_value(R), null_host(n_null, nan), values(P), sorted;
+  HIP_TRY(hipMemcpyAsync(rank.data(), a.rank, rank.size() * sizeof(ErplCmpRank), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(at_value.data(), a.at_value, R * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (biv) HIP_TRY(hipMemcpyAsync(eout.data(), a.eout, eout.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  finish_sides();
+
+  const double da = (double)m_a, db = (double)m_b;
+  const int64_t mm = m_a * m_b;   // < 2^62
+  for (int j = 0; j < R; ++j) {
+    const ErplCmpRank* rk = rank.data() + (size_t)j * all;
+    erpl_cmp_row& o = result->row[j];
+    auto u2 = [&](const ErplCmpRank& r) { return (int64_t)r.sum2r - m_a * (m_a + 1); };
+    auto mw = [&](const ErplCmpRank& r) { const int64_t v = u2(r) - mm; return v < 0 ? -v : v; };
+    o.ks_num = rk[0].k; o.u2_a = u2(rk[0]); o.ks_at = at_value[j]; o.ks_sign = (int32_t)rk[0].sign;
+    o.prob_superiority = (double)o.u2_a / ((2.0 * da) * db);
+    o.ks.statistic = (double)rk[0].k / (da * db);
+    o.mw.statistic = (double)mw(rk[0]);
+    o.cvm.statistic = cmp_cvm(rk[0], m_a, m_b);
+    if (P == 0) continue;
+    double* nk = null_host.data() + (size_t)(3 * j) * P;
+    for (size_t q = 1; q < Q; ++q) {
+      const double t = cmp_cvm(rk[q], m_a, m_b);
+      nk[q - 1] = (double)rk[q].k; nk[P + q - 1] = (double)u2(rk[q]); nk[2 * (size_t)P + q - 1] = t;
+      o.ks.exceed += rk[q].k >= rk[0].k ? 1 : 0;
+      o.mw.exceed += mw(rk[q]) >= mw(rk[0]) ? 1 : 0;
+      o.cvm.exceed += t >= o.cvm.statistic ? 1 : 0;
+    }
+    for (size_t q = 1; q < Q; ++q) values[q - 1] = (double)rk[q].k / (da * db);
+    cmp_null(values, spec->level, sorted, o.ks);
+    for (size_t q = 1; q < Q; ++q) values[q - 1] = (double)mw(rk[q]);
+    cmp_null(values, spec->level, sorted, o.mw);
+    values.assign(nk + 2 * (size_t)P, nk + 3 * (size_t)P);
+    cmp_null(values, spec->level, sorted, o.cvm);
+  }
+  if (biv) {
+    auto energy = [&](size_t q, double* aa, double* ab, double* bb) {
+      *aa = eout[3 * q] / (da * da); *ab = eout[3 * q + 1] / (da * db); *bb = eout[3 * q + 2] / (db * db);
+      return (2.0 * *ab - *aa) - *bb;
+    };
+    double aa, ab, bb;
+    result->energy.statistic = energy(0, &result->d_aa, &result->d_ab, &result->d_bb);
+    if (P > 0) {
+      double* ne = null_host.data() + (size_t)(3 * R) * P;
+      for (size_t q = 1; q < Q; ++q) {
+        ne[q - 1] = energy(q, &aa, &ab, &bb);
+        result->energy.exceed += ne[q - 1] >= result->energy.statistic ? 1 : 0;
+      }
+      values.assign(ne, ne + P);
+      cmp_null(values, spec->level, sorted, result->energy);
+    }
+  }
+  if (null_out) {
+    HIP_TRY(hipMemcpyAsync(null_out, null_host.data(), 8 * n_null, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
   return ERPL_OK;
 }
 

@@ -528,3 +528,74 @@ extern "C++" {
 int erpl_launch_dep_classes(const ErplDepArgs& a, void* stream);   // var, src -> yd, xc, yext, cstat
 int erpl_launch_dep_tables(const ErplDepArgs& a, void* stream);    // xc, yext -> tab, work->est, null; one workgroup per table
 }
+
+// ---- erpl_mc_compare (erpl_compare.hip) ----
+// Everything works on the POOLED dense members (N = m_a + m_b: A's in sample order, then B's).  Replicate q = 0 is the
+// observed labelling ("identity": i < m_a), replicate q = p + 1 permutation p; the labels of 64 replicates of one member are
+// one word of the bit matrix bits[i][word].  Permutations are processed in blocks of `wb` words so that the matrix stays
+// below ERPL_CMP_BITS_MAX_BYTES: block k holds the words k wb .. k wb + wb - 1, and every pass below runs once per block.
+#define ERPL_CMP_TILE 256               // members per workgroup of the pair pass = sources per LDS stage
+#define ERPL_CMP_TARGET_BLOCKS 1024     // the sources are cut into slices until the pair launch has about this many workgroups
+#define ERPL_CMP_MAX_CHUNKS 1024        // waves that share the walk along one sorted order, per word
+#define ERPL_CMP_CHUNK_MIN 256          // sorted positions a wave walks at least
+#define ERPL_CMP_BITS_MAX_BYTES ((size_t)256 << 20)
+#define ERPL_CMP_PART_MAX_COLUMNS 16384 // chunks x words of a block: the chunk records stay below 64 MiB
+struct ErplCmpRank {                    // one replicate of one row: exact integers
+  long long k;                          // max |N c_A - m_a t| over the class ends (-1: none seen)
+  long long at;                         // the first sorted position that reaches it
+  long long sign;                       // of N c_A - m_a t there
+  unsigned long long sum2r;             // sum of 2 r over side A
+  unsigned long long sa_lo, sa_hi, sb_lo, sb_hi;   // sums of (2 r - 2 c)^2 over side A / side B, 128 bits each
+};
+inline int erpl_cmp_words(int P) { return (P + 1 + 63) / 64; }
+inline int erpl_cmp_block_words(int64_t N, int P) {
+  const int64_t W = erpl_cmp_words(P), fit = (int64_t)(ERPL_CMP_BITS_MAX_BYTES / 8) / (N > 0 ? N : 1);
+  return (int)(fit < 1 ? 1 : (fit < W ? fit : W));
+}
+// how the sorted order of a row is cut: `chunks` runs of *len consecutive positions (the last one shorter)
+inline int erpl_cmp_chunks(int64_t N, int wb, int64_t* len) {   // N >= 1
+  int64_t most = ERPL_CMP_PART_MAX_COLUMNS / wb;
+  if (most > ERPL_CMP_MAX_CHUNKS) most = ERPL_CMP_MAX_CHUNKS;
+  int64_t want = (N + ERPL_CMP_CHUNK_MIN - 1) / ERPL_CMP_CHUNK_MIN;
+  if (want > most) want = most;
+  *len = (N + want - 1) / want;
+  return (int)((N + *len - 1) / *len);
+}
+// how the sources of the pair pass are cut: `slices` runs of *per_slice consecutive pooled members (the last one shorter)
+inline int erpl_cmp_slices(int64_t N, int wb, int64_t* per_slice) {   // N >= 1
+  const int64_t tiles = (N + ERPL_CMP_TILE - 1) / ERPL_CMP_TILE;
+  const int64_t want = (ERPL_CMP_TARGET_BLOCKS + tiles * wb - 1) / (tiles * wb), most = tiles < want ? tiles : want;
+  const int64_t per = (tiles + most - 1) / most;   // stages per slice, spread evenly
+  *per_slice = per * ERPL_CMP_TILE;
+  return (int)((tiles + per - 1) / per);
+}
+struct ErplCmpArgs {
+  const double* var_a[ERPL_CMP_MAX_ROWS + 2];   // [n_a] each: the requested rows, then x and y (bivariate)
+  const double* var_b[ERPL_CMP_MAX_ROWS + 2];
+  const uint32_t* src_a;                // [m_a]: the sample of A's dense member d (erpl_launch_boot_compact)
+  const uint32_t* src_b;
+  double* val[ERPL_CMP_MAX_ROWS];       // [N] each: the requested rows, pooled
+  double* xy;                           // [N][2], bivariate
+  unsigned long long* keys;             // [2 N] the sort's keys, in and out
+  uint32_t* idx;                        // [2 N] the pooled indices that travel with them
+  void* temp;                           // scratch of the sort
+  size_t temp_bytes;
+  uint32_t* sidx[ERPL_CMP_MAX_ROWS];    // [N] each: the pooled member at every sorted position
+  unsigned long long* r2e[ERPL_CMP_MAX_ROWS];   // [N] each: 2 r of the position, bit 63: the last position of its tie class
+  unsigned long long* thr;              // [words 64][2]: (key, index) of the m_a-th smallest pair of replicate q (q = 0 unused)
+  unsigned long long* bits;             // [N][wb]
+  uint32_t* cnt;                        // [chunks][wb 64]: A members per chunk, then their exclusive prefix over the chunks
+  ErplCmpRank* part;                    // [chunks][wb 64]
+  ErplCmpRank* rank;                    // [n_rows][words 64]
+  double* at_value;                     // [n_rows]: the row value at rank[j][0].at
+  double* epart;                        // [tiles slices][wb][64][3]: S_AA, S_AB, S_BB
+  double* eout;                         // [words 64][3]
+  unsigned long long seed;
+  uint64_t N, m_a;                      // 1 <= m_a < N < 2^32
+  int32_t n_rows, bivariate, permutations, words, wb;
+};
+extern "C++" {
+// Each enqueues its passes on `stream` and returns a hipError_t (0 = launched).
+int erpl_launch_cmp_prepare(const ErplCmpArgs& a, void* stream);           // src, var -> val, xy, sidx, r2e, thr
+int erpl_launch_cmp_block(const ErplCmpArgs& a, int w0, int wl, void* stream);   // the words w0 .. w0 + wl - 1 -> rank, at_value, eout
+}

@@ -854,6 +854,95 @@ class TrajectoryEngine:
             out["null_values"] = null
         return out
 
+    def compare(self, summary_a, summary_b, mask_a=None, mask_b=None, rows=None, extra_a=None, extra_b=None,
+                quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), xy=(_abi.SUM_IMPACT_X, _abi.SUM_IMPACT_Y), permutations=999, level=0.95,
+                seed=0, keep_null=False, knots=512):
+        """Did two runs come from the same law (erpl_mc_compare)?  Two [16, n] summaries with their own n and masks; up to 4
+        rows (summary rows, or _abi.CMP_ROW_EXTRA for the float64 device tensors extra_a / extra_b; default apogee, range,
+        flight time), per row the Kolmogorov-Smirnov, Mann-Whitney and Cramer-von Mises statistics and the shift function at
+        `quantiles`; xy = (row_x, row_y) adds the energy statistic of the two impact clouds (None: off; at most
+        _abi.CMP_ENERGY_MAX_POINTS pooled points).  Every statistic is recomputed under `permutations` relabellings of the
+        pooled members (0..4096, labels: analysis.permutation_labels).  ONE population per run: mask byte 0 and every
+        requested row (and x, y) finite.
+        Returns a dict: n_a, n_b, count_a, count_b, n_masked_*, n_non_finite_*, rows, q, xy, permutations, level, seed,
+        'row': per row {mean_a, std_a, mean_b, std_b, quantile_a, quantile_b, shift, ks_num, u2_a, ks_at, ks_sign,
+        prob_superiority, ks, mw, cvm} with each test {statistic, p_value, null_mean, null_hi, exceed}, 'energy' (a test, or
+        None) with d_ab / d_aa / d_bb, and what a plot needs WITHOUT the samples: 'ecdf' = {levels [K], a [R, K], b [R, K]}, the
+        order statistics floor(level (m - 1)) of each side's population on a fixed grid of K = min(knots, 512, count) levels,
+        and 'cloud_a' / 'cloud_b' = {mean, cov} of the impact points (torch on the device; knots=0 leaves both out).  keep_null=True adds 'null_values', the float64
+        [3 R + 1, permutations] device tensor (rows 3 j, 3 j + 1, 3 j + 2: K, 2 U_A, T of row j; the last: E)."""
+        n_a, mask_a_p = self._summary_and_mask(summary_a, mask_a)
+        n_b, mask_b_p = self._summary_and_mask(summary_b, mask_b)
+        quantiles = self._fractions(quantiles, _abi.ANALYSIS_MAX_Q, "quantiles")
+        for extra, n, name in ((extra_a, n_a, "extra_a"), (extra_b, n_b, "extra_b")):
+            if extra is not None and not (extra.is_cuda and extra.device == self.device and extra.dtype == torch.float64
+                                          and tuple(extra.shape) == (n,) and extra.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous float64 [n] tensor on {self.device}")
+        spec = self._defaults(_abi.ErplCmpSpec, "erpl_mc_compare_defaults")
+        self._set_rows(spec, rows, 1, _abi.CMP_MAX_ROWS)
+        spec.n_q = len(quantiles)
+        spec.q[:len(quantiles)] = quantiles
+        spec.row_x, spec.row_y = (-1, -1) if xy is None else (int(xy[0]), int(xy[1]))
+        spec.permutations, spec.level, spec.seed = int(permutations), float(level), int(seed) & 0xFFFFFFFFFFFFFFFF
+        if not 0 <= spec.permutations <= _abi.CMP_MAX_PERMUTATIONS:
+            raise ValueError(f"0 to {_abi.CMP_MAX_PERMUTATIONS} permutations")
+        if keep_null and spec.permutations == 0:
+            raise ValueError("keep_null needs permutations > 0")
+        R, P = spec.n_rows, spec.permutations
+        null = torch.empty((3 * R + 1, P), dtype=torch.float64, device=self.device) if keep_null else None
+        res = _abi.ErplCompare()
+        st = torch.cuda.current_stream(self.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        self._call("erpl_mc_compare", ptr(summary_a), mask_a_p, n_a, ptr(summary_b), mask_b_p, n_b, ptr(extra_a), ptr(extra_b),
+                   C.byref(spec), C.byref(res), ptr(null), C.c_void_p(st.cuda_stream))
+
+        def test(t):
+            return {"statistic": t.statistic, "p_value": t.p_value, "null_mean": t.null_mean, "null_hi": t.null_hi,
+                    "exceed": int(t.exceed)}
+
+        nq = len(quantiles)
+        row_ids = list(spec.rows[:R])
+        out = {k: int(getattr(res, k)) for k in ("n_a", "n_b", "count_a", "count_b", "n_masked_a", "n_masked_b",
+                                                 "n_non_finite_a", "n_non_finite_b")}
+        out.update(rows=row_ids, q=quantiles, xy=None if xy is None else (spec.row_x, spec.row_y), permutations=P,
+                   level=float(level), seed=int(spec.seed), row=[])
+        for j in range(R):
+            r = res.row[j]
+            out["row"].append({"mean_a": r.mean_a, "std_a": r.std_a, "mean_b": r.mean_b, "std_b": r.std_b,
+                               "quantile_a": list(r.quantile_a[:nq]), "quantile_b": list(r.quantile_b[:nq]),
+                               "shift": list(r.shift[:nq]), "ks_num": int(r.ks_num), "u2_a": int(r.u2_a), "ks_at": r.ks_at,
+                               "ks_sign": int(r.ks_sign), "prob_superiority": r.prob_superiority,
+                               "ks": test(r.ks), "mw": test(r.mw), "cvm": test(r.cvm)})
+        out["energy"] = dict(test(res.energy), d_ab=res.d_ab, d_aa=res.d_aa, d_bb=res.d_bb) if res.bivariate else None
+
+        # what the plot needs, never the samples: ECDF knots on a fixed grid of levels and the moments of the two clouds
+        # (knots=0: neither)
+        K = max(0, min(int(knots), 512, out["count_a"], out["count_b"]))
+        levels = np.linspace(0.0, 1.0, K) if K > 1 else np.zeros(K)
+        ecdf = {"levels": levels, "a": np.zeros((R, 0)), "b": np.zeros((R, 0))}
+        if xy is not None:
+            out["cloud_a"] = out["cloud_b"] = None
+        for name, summ, mask, extra in (("a", summary_a, mask_a, extra_a), ("b", summary_b, mask_b, extra_b)):
+            if K == 0:
+                break
+            vals = [extra if r == _abi.CMP_ROW_EXTRA else summ[r] for r in row_ids]
+            if xy is not None:
+                vals += [summ[spec.row_x], summ[spec.row_y]]
+            keep = torch.ones(summ.shape[1], dtype=torch.bool, device=self.device) if mask is None else mask == 0
+            for v in vals:
+                keep = keep & torch.isfinite(v)
+            vals = [v[keep] for v in vals]
+            m = int(vals[0].shape[0])
+            at = torch.from_numpy(np.floor(levels * (m - 1)).astype(np.int64)).to(self.device)
+            ecdf[name] = np.stack([torch.sort(v).values[at].cpu().numpy() for v in vals[:R]])
+            if xy is not None:
+                pts = torch.stack(vals[R:R + 2])
+                out["cloud_" + name] = {"mean": pts.mean(dim=1).cpu().numpy(), "cov": torch.cov(pts, correction=0).cpu().numpy()}
+        out["ecdf"] = ecdf
+        if keep_null:
+            out["null_values"] = null
+        return out
+
     def _seeds_on_device(self, seeds):
         """The 32-bit seeds of the device streams: n."""
         if not (seeds.is_cuda and seeds.device == self.device and seeds.dtype in (torch.uint32, torch.int32)

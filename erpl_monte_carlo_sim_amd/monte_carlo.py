@@ -683,6 +683,29 @@ class MonteCarloAnalyzer:
         `top` factors, saved as monte_carlo_given_data.png in the output directory; returns that directory."""
         return plots.plot_given_data_sensitivity(self, sensitivity, save_plots, top)
 
+    def compare_runs(self, analysis_a, analysis_b, **kw):
+        """Did two runs come from the same law (no reference counterpart)?  `analysis.compare_runs` - per row the
+        Kolmogorov-Smirnov, Mann-Whitney and Cramer-von Mises tests with the shift function, the energy test of the two
+        impact clouds, every p-value from relabellings of the pooled flights - on two analysis dicts of either kind, as
+        `confidence_intervals` takes its inputs.  kw: rows, quantiles, xy, permutations, level, seed, keep_null."""
+        from . import analysis as ana
+        eng = shared_engine(self.device)
+
+        def inputs(analysis):
+            if "summary" in analysis:
+                return analysis["summary"], analysis.get("status")
+            summ = ana.summary_from_results(analysis["results"])
+            return torch.as_tensor(summ, device=eng.device).contiguous(), None
+
+        (a, status_a), (b, status_b) = inputs(analysis_a), inputs(analysis_b)
+        return ana.compare_runs(a, b, status_a=status_a, status_b=status_b, engine=eng, **kw)
+
+    def plot_run_comparison(self, comparison, save_plots=True):
+        """No reference counterpart: per row the two distribution functions with the Kolmogorov-Smirnov location, the shift
+        function and the null histogram (when the nulls were kept), and the two impact clouds with the energy statistic,
+        saved as monte_carlo_run_comparison.png in the output directory; returns that directory."""
+        return plots.plot_run_comparison(self, comparison, save_plots)
+
     def impact_probability(self, analysis, **kw):
         """Where it comes down, as probabilities (no reference counterpart): `analysis.impact_probability` - the kernel
         density of the impact points, the thresholds of the regions that hold 50 / 90 / 99 % of the landings and the

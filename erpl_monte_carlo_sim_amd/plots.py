@@ -353,6 +353,92 @@ def given_data_figure(result, top=4):
     return fig
 
 
+def run_comparison_figure(cmp):
+    """The dict of analysis.compare_runs (or TrajectoryEngine.compare): per row three panels - the two empirical
+    distribution functions from the ECDF knots with the Kolmogorov-Smirnov location marked, the shift function (quantile of B
+    minus quantile of A at the requested fractions), and the histogram of the null values of the Kolmogorov-Smirnov numerator
+    with the observed one when the nulls were kept (otherwise the three p-values as text) - and a last row with the 1- and
+    2-sigma ellipses of the two impact clouds, the energy statistic and its p-value.  No sample is needed."""
+    rows = cmp["row"]
+    R = len(rows)
+    has_cloud = cmp.get("energy") is not None and cmp.get("cloud_a") is not None and cmp.get("cloud_b") is not None
+    fig = _figure((13.0, 3.0 * (R + (1 if has_cloud else 0)) + 0.8))
+    axes = np.asarray(fig.subplots(R + (1 if has_cloud else 0), 3, squeeze=False))
+    levels = np.asarray(cmp["ecdf"]["levels"], dtype=np.float64)
+    null = cmp.get("null_values")
+    if null is not None and hasattr(null, "cpu"):
+        null = null.cpu().numpy()
+    q = np.asarray(cmp["q"], dtype=np.float64)
+    for j, row in enumerate(rows):
+        name = row.get("name", f"row {cmp['rows'][j]}")
+        ax = axes[j, 0]
+        if len(levels):
+            ax.step(np.asarray(cmp["ecdf"]["a"])[j], levels, where="post", color="tab:blue", label=f"A ({cmp['count_a']})")
+            ax.step(np.asarray(cmp["ecdf"]["b"])[j], levels, where="post", color="tab:orange", label=f"B ({cmp['count_b']})")
+        if np.isfinite(row["ks_at"]):
+            ax.axvline(row["ks_at"], color="black", linestyle=":", linewidth=0.9,
+                       label=f"D = {row['ks']['statistic']:.4f} at {row['ks_at']:.6g}")
+        ax.set_title(f"{name}: distribution functions", fontsize=9)
+        ax.set_ylabel("F")
+        ax.grid(True, alpha=0.3)
+        ax.legend(loc="best", fontsize=7)
+        ax = axes[j, 1]
+        if len(q):
+            ax.plot(q, np.asarray(row["shift"], dtype=np.float64), marker="o", color="tab:green")
+        ax.axhline(0.0, color="black", linewidth=0.7)
+        ax.set_title(f"{name}: shift function (B - A)", fontsize=9)
+        ax.set_xlabel("quantile")
+        ax.grid(True, alpha=0.3)
+        ax = axes[j, 2]
+        text = ", ".join(f"p({k}) = {row[k]['p_value']:.3g}" for k in ("ks", "mw", "cvm"))
+        if null is not None and null.shape[1] > 0:
+            ax.hist(null[3 * j], bins=min(40, max(5, null.shape[1] // 10)), color="0.7")
+            ax.axvline(row["ks_num"], color="tab:red", label=f"observed K = {row['ks_num']}")
+            ax.legend(loc="best", fontsize=7)
+            ax.set_title(f"{name}: null of K; {text}", fontsize=8)
+        else:
+            ax.text(0.5, 0.5, row.get("verdict", text), ha="center", va="center", wrap=True, fontsize=8, transform=ax.transAxes)
+            ax.set_title(f"{name}: {text}", fontsize=8)
+            ax.set_xticks([])
+            ax.set_yticks([])
+    if has_cloud:
+        ax = axes[R, 0]
+        t = np.linspace(0.0, 2.0 * np.pi, 181)
+        circle = np.vstack([np.cos(t), np.sin(t)])
+        for key, color, label in (("cloud_a", "tab:blue", "A"), ("cloud_b", "tab:orange", "B")):
+            c = cmp[key]
+            mean, cov = np.asarray(c["mean"], dtype=np.float64), np.asarray(c["cov"], dtype=np.float64)
+            w, v = np.linalg.eigh(cov)
+            half = v @ np.diag(np.sqrt(np.maximum(w, 0.0)))
+            for k in (1.0, 2.0):
+                e = mean[:, None] + k * (half @ circle)
+                ax.plot(e[0], e[1], color=color, linewidth=1.2 if k == 1.0 else 0.7, label=label if k == 1.0 else None)
+            ax.plot(mean[0], mean[1], marker="+", color=color)
+        e = cmp["energy"]
+        ax.set_title(f"impact clouds (1, 2 sigma): E = {e['statistic']:.5g}, p = {e['p_value']:.3g}", fontsize=9)
+        ax.set_xlabel("impact x")
+        ax.set_ylabel("impact y")
+        ax.grid(True, alpha=0.3)
+        ax.legend(loc="best", fontsize=7)
+        ax = axes[R, 1]
+        ax.bar(["d_aa", "d_ab", "d_bb"], [e["d_aa"], e["d_ab"], e["d_bb"]], color=["tab:blue", "0.5", "tab:orange"])
+        ax.set_title("mean distances", fontsize=9)
+        ax.grid(True, axis="y", alpha=0.3)
+        ax = axes[R, 2]
+        if null is not None and null.shape[1] > 0:
+            ax.hist(null[3 * R], bins=min(40, max(5, null.shape[1] // 10)), color="0.7")
+            ax.axvline(e["statistic"], color="tab:red", label="observed E")
+            ax.legend(loc="best", fontsize=7)
+            ax.set_title("null of E", fontsize=9)
+        else:
+            ax.text(0.5, 0.5, cmp.get("energy_verdict", ""), ha="center", va="center", wrap=True, fontsize=8, transform=ax.transAxes)
+            ax.set_xticks([])
+            ax.set_yticks([])
+    fig.suptitle(f"Run comparison ({int(cmp['permutations'])} permutations, level {float(cmp['level']):g})")
+    fig.tight_layout()
+    return fig
+
+
 def save_figure(fig, output_dir, name):
     path = os.path.join(output_dir, name)
     fig.savefig(path, dpi=DPI, bbox_inches="tight")
@@ -557,4 +643,15 @@ def plot_given_data_sensitivity(analyzer, sensitivity, save_plots=True, top=4):
     if save_plots:
         output_dir = analyzer._create_output_directory()
         print(f"Given-data sensitivity plot saved to: {save_figure(fig, output_dir, 'monte_carlo_given_data.png')}")
+    return output_dir
+
+
+def plot_run_comparison(analyzer, comparison, save_plots=True):
+    """The tests of MonteCarloAnalyzer.compare_runs (no reference counterpart) as monte_carlo_run_comparison.png; returns the
+    output directory (None without save_plots)."""
+    fig = run_comparison_figure(comparison)
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Run comparison plot saved to: {save_figure(fig, output_dir, 'monte_carlo_run_comparison.png')}")
     return output_dir

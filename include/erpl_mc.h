@@ -1065,6 +1065,120 @@ int erpl_mc_dependence(erpl_ctx* ctx, const double* factors, const double* summa
                        const uint8_t* mask, int64_t n, const erpl_dep_spec* spec, erpl_dependence* result,
                        int64_t* tables, double* class_stats, double* null_out, void* hip_stream);
 
+/* Did two runs come from the same law?  Two-sample tests between run A and run B ON THE DEVICE, each next to its
+ * permutation null: per row the Kolmogorov-Smirnov, Mann-Whitney and Cramer-von Mises statistics with the shift function
+ * (the differences of the quantiles), and for the impact clouds the bivariate energy statistic of Szekely and Rizzo, which
+ * also sees what no marginal test can (two clouds with equal marginals and opposite correlation).  The reference has nothing
+ * like it.
+ *
+ * Input, conventions of erpl_mc_correlation and erpl_mc_bootstrap: `summary_a` [ERPL_SUMMARY_DIM][n_a], `mask_a` [n_a] (NULL:
+ * every sample counts), `extra_a` [n_a] (NULL unless a row is ERPL_CMP_ROW_EXTRA), the same for B with its own n_b, and the
+ * optional `null_out` are caller-owned DEVICE memory; spec and result are host memory.  The work is enqueued on `hip_stream`
+ * behind what is there and the call returns when the result (and null_out) is filled; the workspace belongs to the context,
+ * grows only (about 5 (n_a + n_b) + N (40 + 20 n_rows) bytes, the sort's scratch, the label bits - 8 N ceil((P + 1) / 64)
+ * bytes, at most 256 MiB at a time: the permutations are processed in blocks of as many 64-bit words of labels per member
+ * as fit - and below 100 MiB of partial sums) and is freed by erpl_mc_destroy.
+ *
+ * Population: ONE per run, by listwise deletion - mask byte 0 AND every requested row finite, row_x and row_y included when
+ * the bivariate test is on - in ascending sample order; m_a = count_a, m_b = count_b.  The POOLED members are A's in sample
+ * order, then B's: pooled index i < N = m_a + m_b.  An empty side: counts, every statistic NaN, every integer 0, no error.
+ * Per side and row: mean, std (population) and the quantiles q by the passes of erpl_mc_analyze (the same bits where the
+ * populations coincide); shift[k] = quantile_b[k] - quantile_a[k].
+ * Ranks: the pooled values of a row are sorted ((key, i) ascending; -0.0 ties with +0.0); a tie class is a run of equal
+ * values; 2 r, the doubled 1-based mid-rank, is an integer.  With c_A / c_B the numbers of A / B members up to and including
+ * a sorted position, in exact 64-bit integers (128 bits for the sums of squares):
+ *   ks_num  K   = max over the LAST positions of the tie classes of |m_b c_A - m_a c_B|;  D = (double)K / ((double)m_a (double)m_b);
+ *                 ks_at = the value of the first class (ascending) that reaches K, ks_sign = the sign of m_b c_A - m_a c_B there
+ *   u2_a  2 U_A = sum over A of 2 r - m_a (m_a + 1);  prob_superiority = (double)(2 U_A) / (2.0 (double)m_a (double)m_b), the
+ *                 share of pairs (a, b) with a > b, ties counting half;  mw.statistic = (double)|2 U_A - m_a m_b|
+ *   cvm   T     = U / (m_a m_b N) - (4 m_a m_b - 1) / (6 N),  U = m_a sum over A of (r - c_A)^2 + m_b sum over B of (r - c_B)^2,
+ *                 c the inclusive count of the member's own side at its sorted position (a class's own-side counts are the same
+ *                 set however the class is ordered): scipy.stats.cramervonmises_2samp(a, b).statistic.  The two sums of
+ *                 (2 r - 2 c)^2 are EXACT 128-bit integers; the host forms G = 3 (m_a S_A + m_b S_B) - 2 m_a m_b (4 m_a m_b - 1)
+ *                 exactly and T = (double)G / (double)(12 m_a m_b N) (N <= 2^30; beyond, in long double): no cancellation is
+ *                 left, T carries three roundings.
+ * Energy (row_x >= 0): z = (x, y), d_ij = sqrt((x_i - x_j)^2 + (y_i - y_j)^2) in double without contraction;
+ *   E = 2 d_ab - d_aa - d_bb,  d_aa = S_AA / m_a^2, d_ab = S_AB / (m_a m_b), d_bb = S_BB / m_b^2 (V-statistic: the zero diagonal
+ *   counts), equal to - sum_i sum_j w_i w_j d_ij with w = 1 / m_a on A and - 1 / m_b on B.  Summation order: pooled member i
+ *   (one thread) adds d_ij over the A members j of one slice of the pooled order in ascending j (r_i), and over all j of the
+ *   slice (t_i); S_AA takes r_i of the A members i, S_AB r_i of the B members, S_BB t_i - r_i of the B members; the 256
+ *   members of a tile are folded in the fixed order of the other analysis calls, then the partial sums in ascending (tile,
+ *   slice) order.  Tiles and slices are functions of (N, P) alone.  Cost: N^2 ceil((P + 1) / 64) distances and N^2 (P + 1)
+ *   additions - 3e12 at N = 54 074, P = 999 - hence the limit ERPL_CMP_ENERGY_MAX_POINTS on N (its label bits: 34 MB at
+ *   P = 4096); row_x = -1 runs everything else at any size.
+ * Permutation null: P relabellings of the pooled members that keep the group sizes, every statistic recomputed under each by
+ * THE SAME code as the observed one (which is the relabelling "identity").  THE LABEL CONTRACT: the key of pooled member i in
+ * permutation p is the 64-bit draw number i of replicate p of erpl_mc_bootstrap's draw contract (Philox pair i >> 1, word A
+ * if i is even, else B, with this spec's seed); side A of permutation p is the m_a members with the smallest (key, i) pairs.
+ * Keys are regenerated, never stored; the m_a-th smallest pair of a permutation is found by radix selection.
+ * erpl_mc_compare_labels is the same rule on the host.  Per test: exceed = #{p : T_p >= T_obs} - compared in 64-bit integers
+ * for KS (K) and Mann-Whitney (|2 U_A - m_a m_b|), in double for cvm and energy -, p_value = (exceed + 1) / (P + 1), null_mean
+ * (ascending p) and null_hi, the order statistic `level` of the null values (linear interpolation, as np.quantile), of D,
+ * |2 U_A - m_a m_b|, T and E.  P == 0: p_value, null_mean, null_hi NaN, exceed 0, nothing is drawn, nothing depends on seed.
+ * null_out [3 n_rows + 1][P] (row 3 n_rows exists also when row_x < 0: NaN): row 3 j the K_p, row 3 j + 1 the 2 U_A,p (both as
+ * doubles: exact while m_a m_b <= 2^52), row 3 j + 2 the T_p of spec->rows[j], the last row the E_p.
+ * No floating-point atomics, every sum in a fixed order: two calls on the same inputs return the same bytes.  Swapping the
+ * runs keeps K, D, T and |2 U_A - m_a m_b| (another labelling: the null differs) and turns U_A into m_a m_b - U_A.
+ *
+ * Errors: ERPL_ERR_INVALID, before any device work and with a message that names the argument, in this order: a NULL spec,
+ * summary_a, summary_b or result; n_a, then n_b, <= 0 or >= 2^31; n_rows outside 1..4; a row outside 0..16 or listed twice;
+ * row 16 without extra_a, then without extra_b; n_q outside 0..8; q outside [0, 1]; row_x >= 0: row_x or row_y outside 0..15 or
+ * equal; permutations outside 0..4096; null_out with permutations == 0; level not in (0, 1) (looked at only when
+ * permutations > 0); the context last.  After the populations are counted: row_x >= 0 and N > ERPL_CMP_ENERGY_MAX_POINTS
+ * ("... spec->row_x = -1 runs the rank tests alone"). */
+#define ERPL_CMP_MAX_ROWS 4
+#define ERPL_CMP_ROW_EXTRA 16            /* = ERPL_BOOT_ROW_EXTRA: the callers' device rows extra_a / extra_b */
+#define ERPL_CMP_MAX_PERMUTATIONS 4096
+#define ERPL_CMP_ENERGY_MAX_POINTS 65536 /* pooled N of the bivariate test */
+
+typedef struct erpl_cmp_spec {
+  int32_t n_rows;                        /* 1..ERPL_CMP_MAX_ROWS */
+  int32_t rows[ERPL_CMP_MAX_ROWS];       /* distinct; 0..15 = summary rows, ERPL_CMP_ROW_EXTRA = extra_a / extra_b */
+  int32_t n_q;                           /* 0..ERPL_ANALYSIS_MAX_Q */
+  int32_t row_x, row_y;                  /* the plane of the energy test; row_x < 0: no bivariate test */
+  int32_t permutations;                  /* P, 0..ERPL_CMP_MAX_PERMUTATIONS; 0 = no null */
+  int32_t reserved;
+  double q[ERPL_ANALYSIS_MAX_Q];         /* quantile fractions in [0, 1] */
+  double level;                          /* in (0, 1); looked at only if permutations > 0 */
+  uint64_t seed;
+} erpl_cmp_spec;
+
+typedef struct erpl_cmp_test {
+  double statistic, p_value, null_mean, null_hi;
+  int64_t exceed;                        /* null values >= the observed one */
+} erpl_cmp_test;
+
+typedef struct erpl_cmp_row {
+  double mean_a, std_a, mean_b, std_b;
+  double quantile_a[ERPL_ANALYSIS_MAX_Q], quantile_b[ERPL_ANALYSIS_MAX_Q], shift[ERPL_ANALYSIS_MAX_Q];
+  int64_t ks_num;                        /* K */
+  int64_t u2_a;                          /* 2 U_A */
+  double ks_at;                          /* where the supremum is first reached */
+  int32_t ks_sign;                       /* +1: A's distribution function is the larger one there, -1: B's, 0: K == 0 */
+  int32_t reserved;
+  double prob_superiority;               /* U_A / (m_a m_b) */
+  erpl_cmp_test ks, mw, cvm;             /* statistic: D, |2 U_A - m_a m_b|, T */
+} erpl_cmp_row;
+
+typedef struct erpl_compare {
+  int64_t n_a, n_b, count_a, count_b, n_masked_a, n_masked_b, n_non_finite_a, n_non_finite_b;
+  int32_t n_rows, n_q, permutations, bivariate;   /* bivariate: 1 if the energy test ran */
+  erpl_cmp_row row[ERPL_CMP_MAX_ROWS];            /* of spec->rows[j] */
+  double d_ab, d_aa, d_bb;                        /* the three mean distances behind energy.statistic */
+  erpl_cmp_test energy;
+} erpl_compare;
+
+/* Host only: rows {APOGEE_ALT, RANGE, FLIGHT_TIME}, the q of erpl_mc_analysis_defaults, row_x / row_y = IMPACT_X / IMPACT_Y,
+ * 999 permutations, level 0.95, seed 0. */
+int erpl_mc_compare_defaults(erpl_cmp_spec* spec);
+int erpl_mc_compare(erpl_ctx* ctx, const double* summary_a, const uint8_t* mask_a, int64_t n_a, const double* summary_b,
+                    const uint8_t* mask_b, int64_t n_b, const double* extra_a, const double* extra_b,
+                    const erpl_cmp_spec* spec, erpl_compare* result, double* null_out, void* hip_stream);
+/* Host only, no context, no device: the labels of permutation `permutation` of m_a + m_b pooled members, out[i] = 1: side A.
+ * Exactly m_a ones.  ERPL_ERR_INVALID for a NULL out, a negative m_a or m_b, m_a + m_b == 0 or >= 2^32, or a permutation
+ * outside 0..2^32 - 1. */
+int erpl_mc_compare_labels(uint64_t seed, int64_t permutation, int64_t m_a, int64_t m_b, uint8_t* out);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
