@@ -266,6 +266,25 @@ class ErplCorridorSpec(C.Structure):
                 ("n_q", C.c_int32), ("reserved", C.c_int32), ("q", _Q)]
 
 
+# erpl_mc_impact_points: channels of the values [IIP_CH_COUNT][n_nodes][ld], rows of the summary [IIP_DIM][n_traj]
+IIP_DIM = 16
+IIP_MAX_NODES = 4096
+IIP_MAX_STEPS = 1 << 20
+IIP_MAX_VERTICES = 64
+(IIP_CH_X, IIP_CH_Y, IIP_CH_RANGE, IIP_CH_TFALL, IIP_CH_VIMPACT) = range(5)
+IIP_CH_COUNT = 5
+(IIP_MAX_RANGE, IIP_MAX_RANGE_TIME, IIP_MAX_RANGE_X, IIP_MAX_RANGE_Y, IIP_BURNOUT_TIME, IIP_BURNOUT_X, IIP_BURNOUT_Y,
+ IIP_APOGEE_X, IIP_APOGEE_Y, IIP_MAX_RATE, IIP_MAX_RATE_TIME, IIP_EXIT_TIME, IIP_EXIT_X, IIP_EXIT_Y, IIP_LANDED,
+ IIP_NODES) = range(16)
+
+
+class ErplIipSpec(C.Structure):
+    _fields_ = [("n_nodes", C.c_int32), ("record_stride", C.c_int32), ("max_steps", C.c_int32), ("n_vertices", C.c_int32),
+                ("dt", C.c_double), ("ground", C.c_double), ("drag_scale", C.c_double),
+                ("origin_x", C.c_double), ("origin_y", C.c_double),
+                ("keep_x", C.c_double * IIP_MAX_VERTICES), ("keep_y", C.c_double * IIP_MAX_VERTICES)]
+
+
 # erpl_mc_sobol
 SOBOL_MAX_FACTORS = 32
 SOBOL_MAX_ROWS = 4
@@ -368,6 +387,7 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_set_config", "erpl_mc_reserve", "erpl_mc_run_batch", "erpl_mc_set_launch",
            "erpl_mc_last_stats", "erpl_mc_ticket_stats", "erpl_mc_set_profiling", "erpl_mc_last_kernel_ms",
            "erpl_mc_kernel_ms_history", "erpl_mc_debug_counters", "erpl_mc_extract_histories", "erpl_mc_flight_envelope", "erpl_mc_set_chunk",
+           "erpl_mc_impact_points_defaults", "erpl_mc_impact_points",
            "erpl_mc_legacy_random_streams", "erpl_mc_legacy_wind_profiles", "erpl_mc_set_waves_per_simd",
            "erpl_mc_set_overlap", "erpl_mc_submit_batch", "erpl_mc_wait_batch", "erpl_mc_synchronize",
            "erpl_mc_debug_eval", "erpl_mc_synth_wind", "erpl_mc_set_adopt", "erpl_mc_get_overlap",
@@ -448,6 +468,9 @@ def load_library(path=None):
     lib.erpl_mc_extract_histories.argtypes = [C.c_void_p, C.POINTER(ErplBatch), C.c_int64, C.c_void_p, C.c_int64,
                                               C.c_double, C.c_void_p, C.c_void_p]
     lib.erpl_mc_flight_envelope.argtypes = [C.c_void_p, C.POINTER(ErplBatch), C.POINTER(ErplOut), C.c_void_p, C.c_void_p]
+    lib.erpl_mc_impact_points_defaults.argtypes = [C.POINTER(ErplIipSpec)]
+    lib.erpl_mc_impact_points.argtypes = [C.c_void_p, C.POINTER(ErplBatch), C.POINTER(ErplOut), C.POINTER(ErplIipSpec), C.c_void_p,
+                                          C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
     lib.erpl_mc_analysis_defaults.argtypes = [C.POINTER(ErplAnalysisSpec)]
     lib.erpl_mc_analyze.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplAnalysisSpec),
                                     C.POINTER(ErplAnalysis), C.c_void_p, C.c_void_p]

@@ -289,23 +289,46 @@ def envelope_statistics(envelope, mask=None, engine=None, rows=None, quantiles=(
     that a row counts its finite values (the burnout rows of a flight that ends before burnout are NaN).  rows: _abi.ENV_*
     indices (default all 16).  Returns {name: {'count', 'mean', 'std', 'min', 'max', 'quantiles'}}, names from
     ENVELOPE_NAMES; every number of a row without a counted value is NaN."""
-    from . import _abi
-    engine = _engine_of(envelope, engine)
-    rows = list(range(_abi.ENV_DIM)) if rows is None else [int(r) for r in rows]
+    return _summary_like_statistics(envelope, ENVELOPE_NAMES, mask, engine, rows, quantiles)
+
+
+def _summary_like_statistics(matrix, names, mask, engine, rows, quantiles):
+    """erpl_mc_analyze under infinite bounds on a [16, m] matrix that is laid out like a summary (a flight envelope, an IIP
+    summary) over the columns whose mask byte is 0, as {names[r]: {...}}."""
+    engine = _engine_of(matrix, engine)
+    rows = list(range(len(names))) if rows is None else [int(r) for r in rows]
     quantiles = [float(q) for q in quantiles]
     if mask is not None:
-        envelope = envelope[:, mask == 0].contiguous()
-    if envelope.shape[1] == 0:
+        matrix = matrix[:, mask == 0].contiguous()
+    if matrix.shape[1] == 0:
         nan = float("nan")
-        return {ENVELOPE_NAMES[r]: {"count": 0, "mean": nan, "std": nan, "min": nan, "max": nan,
-                                    "quantiles": [nan] * len(quantiles)} for r in rows}
+        return {names[r]: {"count": 0, "mean": nan, "std": nan, "min": nan, "max": nan,
+                           "quantiles": [nan] * len(quantiles)} for r in rows}
     inf = float("inf")
-    res, _ = engine.analyze(envelope, None, rows=rows, quantiles=quantiles,
+    res, _ = engine.analyze(matrix, None, rows=rows, quantiles=quantiles,
                             bounds={"max_apogee": inf, "min_apogee": -inf, "max_range": inf, "max_flight_time": inf,
                                     "energy_apogee": inf})
-    return {ENVELOPE_NAMES[r]: {"count": int(res.row[j].count), "mean": res.row[j].mean, "std": res.row[j].std,
-                                "min": res.row[j].min, "max": res.row[j].max,
-                                "quantiles": list(res.row[j].quantile[:len(quantiles)])} for j, r in enumerate(rows)}
+    return {names[r]: {"count": int(res.row[j].count), "mean": res.row[j].mean, "std": res.row[j].std,
+                       "min": res.row[j].min, "max": res.row[j].max,
+                       "quantiles": list(res.row[j].quantile[:len(quantiles)])} for j, r in enumerate(rows)}
+
+
+# ---------------------------------------------------------------------------------- the instantaneous impact points
+IIP_NAMES = ("max_range", "max_range_time", "max_range_x", "max_range_y", "burnout_time", "burnout_x", "burnout_y",
+             "apogee_x", "apogee_y", "max_rate", "max_rate_time", "exit_time", "exit_x", "exit_y", "landed_nodes",
+             "nodes")   # _abi.IIP_* order
+IIP_CHANNELS = ("x", "y", "range", "fall_time", "impact_speed")   # _abi.IIP_CH_* order
+
+
+def impact_point_statistics(summary, mask=None, engine=None, rows=None, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95)):
+    """Statistics of an IIP summary (float64 [16, m] on the device, TrajectoryEngine.impact_points) over the columns whose
+    `mask` byte is 0 (uint8 [m] on the device; None: every column), built the way envelope_statistics is: erpl_mc_analyze
+    under infinite bounds, exact order statistics, sums in its fixed order.  Its finiteness rule on rows 0, 4 and 5 stays: a
+    column whose max_range, burnout_time or burnout_x is not finite - no landed node, a capture that ends before burnout,
+    a burnout node that did not land - counts in no row; beyond that a row counts its finite values (the exit rows are
+    NaN for a trajectory that stays inside).  rows: _abi.IIP_* indices (default all 16).  Returns
+    {name: {'count', 'mean', 'std', 'min', 'max', 'quantiles'}}, names from IIP_NAMES."""
+    return _summary_like_statistics(summary, IIP_NAMES, mask, engine, rows, quantiles)
 
 
 # ---------------------------------------------------------------------------------- the trajectory corridor

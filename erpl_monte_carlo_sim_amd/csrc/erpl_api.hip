@@ -779,6 +779,73 @@ int erpl_mc_flight_envelope(erpl_ctx* c, const erpl_batch* b, const erpl_out* o,
   return ERPL_OK;
 }
 
+int erpl_mc_impact_points_defaults(erpl_iip_spec* spec) {
+  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "NULL spec");
+  memset(spec, 0, sizeof(*spec));
+  spec->n_nodes = 64; spec->record_stride = 1; spec->max_steps = 20000;
+  spec->dt = 0.05; spec->drag_scale = 1.0;
+  return ERPL_OK;
+}
+
+int erpl_mc_impact_points(erpl_ctx* c, const erpl_batch* b, const erpl_out* o, const erpl_iip_spec* s, double* values,
+                          int64_t ld, int64_t col0, double* summary, void* stream) {
+  if (!b) return erpl_fail(ERPL_ERR_INVALID, "NULL batch");
+  if (!o) return erpl_fail(ERPL_ERR_INVALID, "NULL out");
+  if (!s) return erpl_fail(ERPL_ERR_INVALID, "NULL spec");
+  if (!values) return erpl_fail(ERPL_ERR_INVALID, "NULL values");
+  if (s->n_nodes < 1 || s->n_nodes > ERPL_IIP_MAX_NODES)
+    return erpl_fail(ERPL_ERR_INVALID, "n_nodes = %d out of range 1..%d", s->n_nodes, ERPL_IIP_MAX_NODES);
+  if (s->record_stride < 1) return erpl_fail(ERPL_ERR_INVALID, "record_stride = %d: at least 1", s->record_stride);
+  if (s->max_steps < 1 || s->max_steps > ERPL_IIP_MAX_STEPS)
+    return erpl_fail(ERPL_ERR_INVALID, "max_steps = %d out of range 1..%d", s->max_steps, ERPL_IIP_MAX_STEPS);
+  if (s->n_vertices != 0 && (s->n_vertices < 3 || s->n_vertices > ERPL_IIP_MAX_VERTICES))
+    return erpl_fail(ERPL_ERR_INVALID, "n_vertices = %d: 0 or 3..%d", s->n_vertices, ERPL_IIP_MAX_VERTICES);
+  if (!std::isfinite(s->dt) || !(s->dt > 0.0)) return erpl_fail(ERPL_ERR_INVALID, "dt = %g: finite and > 0", s->dt);
+  if (!std::isfinite(s->ground)) return erpl_fail(ERPL_ERR_INVALID, "ground = %g: finite", s->ground);
+  if (!std::isfinite(s->drag_scale) || !(s->drag_scale >= 0.0))
+    return erpl_fail(ERPL_ERR_INVALID, "drag_scale = %g: finite and >= 0", s->drag_scale);
+  if (!std::isfinite(s->origin_x)) return erpl_fail(ERPL_ERR_INVALID, "origin_x = %g: finite", s->origin_x);
+  if (!std::isfinite(s->origin_y)) return erpl_fail(ERPL_ERR_INVALID, "origin_y = %g: finite", s->origin_y);
+  for (int i = 0; i < s->n_vertices; ++i)
+    if (!std::isfinite(s->keep_x[i]) || !std::isfinite(s->keep_y[i]))
+      return erpl_fail(ERPL_ERR_INVALID, "keep-in vertex %d = (%g, %g): finite", i, s->keep_x[i], s->keep_y[i]);
+  if (b->precision != ERPL_PREC_F64 && b->precision != ERPL_PREC_F64_FAST)
+    return erpl_fail(ERPL_ERR_INVALID, "precision = %d: the impact points need a batch with fp64 wind tables", b->precision);
+  if (b->n <= 0) return erpl_fail(ERPL_ERR_INVALID, "batch n = %lld: at least one sample", (long long)b->n);
+  if (o->n_traj < 0 || o->n_traj > 2147483647LL)
+    return erpl_fail(ERPL_ERR_INVALID, "n_traj = %lld out of range 0..2^31 - 1", (long long)o->n_traj);
+  if (col0 < 0) return erpl_fail(ERPL_ERR_INVALID, "col0 = %lld: not negative", (long long)col0);
+  if (ld - col0 < o->n_traj)   // (col0 >= 0: no overflow, and a negative ld is refused here too)
+    return erpl_fail(ERPL_ERR_INVALID, "ld = %lld: the %lld columns from col0 = %lld on do not fit", (long long)ld,
+                     (long long)o->n_traj, (long long)col0);
+  if (o->n_traj > 0) {
+    if (o->traj_cap < 1) return erpl_fail(ERPL_ERR_INVALID, "traj_cap = %lld: at least one record per trajectory", (long long)o->traj_cap);
+    if (!o->traj_ids) return erpl_fail(ERPL_ERR_INVALID, "NULL traj_ids");
+    if (!o->traj) return erpl_fail(ERPL_ERR_INVALID, "NULL traj");
+    if (!o->traj_len) return erpl_fail(ERPL_ERR_INVALID, "NULL traj_len");
+    if (!b->rocket) return erpl_fail(ERPL_ERR_INVALID, "NULL rocket");
+    if (!b->motor) return erpl_fail(ERPL_ERR_INVALID, "NULL motor");
+    if (!check_wind_args(b)) return erpl_fail(ERPL_ERR_INVALID, "bad wind arguments (k_wind, alt_grid, wind)");
+  }
+  if (!c) return erpl_fail(ERPL_ERR_INVALID, "NULL ctx");
+  if (!c->has_cfg) return erpl_fail(ERPL_ERR_CONFIG, "erpl_mc_set_config has not been called");
+  if (o->n_traj == 0) return ERPL_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  ErplKArgs a;
+  fill_common_args(c, b, a);
+  a.n_traj = o->n_traj; a.traj_ids = o->traj_ids; a.traj_cap = o->traj_cap; a.traj = o->traj; a.traj_len = o->traj_len;
+  ErplIipArgs q;
+  q.n_nodes = s->n_nodes; q.record_stride = s->record_stride; q.max_steps = s->max_steps; q.reserved = 0;
+  q.dt = s->dt; q.ground = s->ground; q.drag_scale = s->drag_scale; q.origin_x = s->origin_x; q.origin_y = s->origin_y;
+  q.values = values; q.ld = ld; q.col0 = col0; q.summary = summary;
+  ErplIipKeepIn keep;
+  memset(&keep, 0, sizeof(keep));
+  keep.n = s->n_vertices;
+  for (int i = 0; i < s->n_vertices; ++i) { keep.x[i] = s->keep_x[i]; keep.y[i] = s->keep_y[i]; }
+  KERNEL_TRY(erpl_launch_iip_f64(a, &c->h_tables.s64, q, keep, stream));
+  return ERPL_OK;
+}
+
 int erpl_mc_debug_eval(erpl_ctx* c, const erpl_batch* b, int what, int64_t m, const double* in, double* out, void* stream) {
   if (!c || !b || !in || !out) return erpl_fail(ERPL_ERR_INVALID, "NULL argument");
   if (!c->has_cfg) return erpl_fail(ERPL_ERR_CONFIG, "erpl_mc_set_config has not been called");

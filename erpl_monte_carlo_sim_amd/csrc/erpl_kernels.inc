@@ -16,7 +16,8 @@
 // the queue, to hand the last lanes of a thinning wave to fuller waves (lane adoption) and (with step-chunked
 // launches) to park still-flying lanes densely for the next launch.  Kernel 3 (fp64 only) evaluates the
 // per-step diagnostic histories of _extract_results (:496-552); kernel 4 (fp64 only) reduces every captured trajectory
-// of a batch to its flight envelope through the same per-record evaluation.
+// of a batch to its flight envelope through the same per-record evaluation; kernels 5 to 7 (fp64 only) let every chosen
+// record of a captured trajectory fall to the ground without thrust and summarise where it comes down.
 //
 // ERPL_FAITHFUL keeps the reference's operation order (double normalisation, trig of
 // atan2, IEEE divisions); the two throughput builds allow algebraically identical shortcuts (no trig, reciprocal
@@ -39,5 +40,6 @@
 #include "erpl_k_debug.h"    // one stored record's evaluation, kernel 3 (gate only) and the known-answer debug kernel
 #if ERPL_FAITHFUL
 #include "erpl_k_envelope.h" // kernel 4 (gate only): the flight envelope of every captured trajectory
+#include "erpl_k_iip.h"      // kernels 5 - 7 (gate only): the instantaneous impact points of every captured trajectory
 #endif
-#include "erpl_k_launch.h"   // host: erpl_launch_<suffix>, the sweep, extract, envelope and debug launchers
+#include "erpl_k_launch.h"   // host: erpl_launch_<suffix>, the sweep, extract, envelope, impact-point and debug launchers

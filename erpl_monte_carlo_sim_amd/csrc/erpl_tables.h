@@ -160,6 +160,26 @@ int erpl_launch_extract_f64(const ErplKArgs& a, const void* scalars, double time
 int erpl_launch_envelope_f64(const ErplKArgs& a, const void* scalars, void* stream);
 }
 
+// What the kernels of erpl_mc_impact_points take besides ErplKArgs (by value): the scalar fields of erpl_iip_spec and
+// the caller's buffers; the keep-in vertices go to the summary kernel alone.
+struct ErplIipArgs {
+  int32_t n_nodes, record_stride, max_steps, reserved;
+  double dt, ground, drag_scale, origin_x, origin_y;
+  double* values;    // [ERPL_IIP_CH_COUNT][n_nodes][ld]
+  int64_t ld, col0;
+  double* summary;   // [ERPL_IIP_DIM][n_traj] or NULL
+};
+struct ErplIipKeepIn {
+  int32_t n, reserved;
+  double x[ERPL_IIP_MAX_VERTICES], y[ERPL_IIP_MAX_VERTICES];
+};
+extern "C++" {
+// the instantaneous impact points of every captured trajectory (fp64 only): a.n_traj / traj_ids / traj_cap / traj / traj_len
+// as erpl_out has them (n_traj < 2^31, q.n_nodes <= ERPL_IIP_MAX_NODES); the prefix kernel, the fall kernel, then
+// (q.summary != NULL) the summary kernel, one behind the other on the same stream
+int erpl_launch_iip_f64(const ErplKArgs& a, const void* scalars, const ErplIipArgs& q, const ErplIipKeepIn& keep, void* stream);
+}
+
 // ---- erpl_mc_analyze: outlier filter + exact statistics on the summary (erpl_analysis.hip) ----
 #define ERPL_ANA_BLOCK 256        // threads per workgroup of the streaming passes
 #define ERPL_ANA_MAX_BLOCKS 1024  // their grid: min(this, ceil(n / ERPL_ANA_BLOCK)) - a function of n alone, so the

@@ -421,7 +421,7 @@ class MonteCarloAnalyzer:
         return out
 
     def _captured_run(self, who, what, initial_conditions, n_samples, stride, seed, precision, planar, capture_bytes, reduce):
-        """The capturing loop of `flight_envelope` and `trajectory_corridor`: the samples of run_monte_carlo_device (sub-batch
+        """The capturing loop of `flight_envelope`, `trajectory_corridor` and `impact_point_trace`: the samples of run_monte_carlo_device (sub-batch
         j from seed + rank + 1000003 * j) flown with every trajectory captured at every `stride`-th step, in sub-batches of
         capture_bytes // (cap * 120) samples (at most DEVICE_CHUNK); `reduce(eng, db, first_sample, traj, traj_len)`
         enqueues what the caller makes of a sub-batch's capture, and the capture buffer is released behind it.  One rank
@@ -505,6 +505,82 @@ class MonteCarloAnalyzer:
                               "precision": precision, "stride": run["stride"], "records_per_sample": run["cap"],
                               "sub_batches": run["sub_batches"], "sub_batch_samples": run["per_batch"]}
         return out
+
+    def impact_point_trace(self, initial_conditions, n_samples, stride=10, nodes=64, record_stride=None, keep_in=None,
+                           seed=1234, precision="f64_fast", planar=False, capture_bytes=4 << 30, dt=0.05, max_steps=20000,
+                           ground=0.0, drag_scale=1.0, origin=(0.0, 0.0), quantiles=(0.05, 0.25, 0.5, 0.75, 0.95),
+                           level=0.95):
+        """If the flight is terminated at time t, where does the vehicle come down - for a whole dispersion run: the samples
+        of `flight_envelope` (same draws, same sub-batches, every trajectory captured at every `stride`-th step) and, of each
+        capture, `nodes` records `record_stride` apart (None: the stride that spreads the nodes over max_time) fall to
+        z = `ground` without thrust on the device (TrajectoryEngine.impact_points: frozen mass, zero-incidence power-off
+        drag times drag_scale, the sample's own wind, no parachute; dt / max_steps bound the fall), each sub-batch into its
+        window of columns of one [5, nodes, n] matrix; the capture is released behind the kernel.  keep_in: a keep-in
+        polygon of 3 to 64 (x, y) vertices or None.  One rank only (ValueError before any work).
+
+        Returns a dict: 'time' [nodes] (the nominal time of node k since rail exit, k * record_stride * stride * dt_flight),
+        'q', 'channels' (analysis.IIP_CHANNELS) and per channel 'count' / 'mean' / 'std' / 'min' / 'max' [nodes] and
+        'quantiles' [n_q, nodes] over the samples that pass the outlier filter (erpl_mc_corridor_bands on the IIP matrix);
+        'statistics' (analysis.impact_point_statistics of the summary rows over the same samples); 'exit_probability', the
+        share of those samples whose IIP ever leaves the keep-in area, with its Wilson interval 'exit_interval' at `level`
+        (NaN and (0, 1) without a polygon) and 'exit_count'; 'values' and 'iip_summary' (on the device), 'iip_names',
+        'keep_in', 'summary', 'status', 'reasons', 'n_samples' / 'n_outliers' and 'performance'."""
+        nodes, stride = int(nodes), int(stride)
+        if not 1 <= nodes <= _abi.IIP_MAX_NODES:
+            raise ValueError(f"1 to {_abi.IIP_MAX_NODES} nodes")
+        if int(n_samples) < 1 or stride < 1:
+            raise ValueError("n_samples and stride must be at least 1")
+        flight_dt = min(self.dt_initial, 0.005)
+        if record_stride is None:
+            record_stride = max(1, int(np.ceil(self.max_time / flight_dt / stride)) // nodes)
+        record_stride = int(record_stride)
+        if record_stride < 1:
+            raise ValueError("record_stride must be at least 1")
+        keep = None if keep_in is None else [(float(x), float(y)) for x, y in keep_in]
+        box, summaries = {}, []
+
+        def fall(eng, db, a, traj, tlen):
+            if "values" not in box:
+                box["values"] = torch.full((_abi.IIP_CH_COUNT, nodes, int(n_samples)), float("nan"), dtype=torch.float64,
+                                           device=eng.device)
+            _, s = eng.impact_points(db, eng._keep, traj, tlen, nodes=nodes, record_stride=record_stride, dt=dt,
+                                     max_steps=max_steps, ground=ground, drag_scale=drag_scale, origin=origin, keep_in=keep,
+                                     out=box["values"], col0=a)
+            summaries.append(s)
+
+        eng, summ, status, run = self._captured_run("impact_point_trace", "impact points", initial_conditions, n_samples,
+                                                    stride, seed, precision, planar, capture_bytes, fall)
+        iip = summaries[0] if len(summaries) == 1 else torch.cat(summaries, dim=1).contiguous()
+        torch.cuda.synchronize(eng.device)
+        t1 = time.time()
+        _, res, why = analysis._filter(summ, status, eng)
+        b = eng.corridor_bands(box["values"], why, quantiles=quantiles)
+        out = {"time": np.arange(nodes, dtype=np.float64) * (record_stride * run["stride"] * flight_dt), "q": b["q"],
+               "channels": list(analysis.IIP_CHANNELS), "n_counted": b["n_counted"]}
+        for j, name in enumerate(analysis.IIP_CHANNELS):
+            out[name] = {k: b[k][j] for k in ("count", "mean", "std", "min", "max", "quantiles")}
+        out["statistics"] = analysis.impact_point_statistics(iip, why, engine=eng, quantiles=quantiles)
+        counted = why == 0
+        n_counted = int(counted.sum())
+        n_exit = int((counted & torch.isfinite(iip[_abi.IIP_EXIT_TIME])).sum())
+        out["exit_count"] = n_exit
+        out["exit_probability"] = n_exit / n_counted if (keep is not None and n_counted) else float("nan")
+        out["exit_interval"] = analysis.wilson_interval(n_exit, n_counted, level) if keep is not None else (0.0, 1.0)
+        out["interval_level"] = float(level)
+        t2 = time.time()
+        out.update({"summary": summ, "status": status, "reasons": why, "values": box["values"], "iip_summary": iip,
+                    "iip_names": list(analysis.IIP_NAMES), "keep_in": keep, "record_stride": record_stride,
+                    "n_samples": int(res.n_valid), "n_outliers": int(res.n_outliers)})
+        out["performance"] = {"total_time": t2 - run["t0"], "capture_and_fall_s": t1 - run["t0"], "statistics_s": t2 - t1,
+                              "precision": precision, "stride": run["stride"], "records_per_sample": run["cap"],
+                              "sub_batches": run["sub_batches"], "sub_batch_samples": run["per_batch"]}
+        return out
+
+    def plot_impact_point_trace(self, trace, save_plots=True):
+        """No reference counterpart: the IIP trace of `impact_point_trace` - IIP range over time with its bands, the ground
+        track of the median IIP with the keep-in outline, the exit times - as monte_carlo_impact_points.png in the output
+        directory; returns that directory."""
+        return plots.plot_impact_point_trace(self, trace, save_plots)
 
     def plot_trajectory_corridor(self, corridor, save_plots=True):
         """No reference counterpart: the corridor of `trajectory_corridor` - per channel the median, the outer and inner

@@ -271,6 +271,56 @@ def corridor_figure(result):
     return fig
 
 
+def impact_point_figure(result):
+    """The IIP trace from the dict of MonteCarloAnalyzer.impact_point_trace: the IIP range over the time of termination
+    (the median - the quantile nearest 0.5 - and the outer and inner quantile bands), the ground track of the median IIP
+    with the keep-in outline, and the exit times (one mark per quantile of statistics['exit_time'])."""
+    q = np.asarray(result["q"], dtype=np.float64)
+    t = np.asarray(result["time"], dtype=np.float64)
+    fig = _figure((13, 5))
+    ax_r, ax_xy = fig.subplots(1, 2)
+    order = np.argsort(q)
+    mid = int(np.argmin(np.abs(q - 0.5))) if len(q) else None
+    rng = result["range"]
+    quant = np.asarray(rng["quantiles"], dtype=np.float64)
+    for depth, alpha in ((0, 0.2), (1, 0.35)):   # the outer pair, then the inner one
+        if len(q) >= 2 * (depth + 1):
+            lo, hi = order[depth], order[len(q) - 1 - depth]
+            ax_r.fill_between(t, quant[lo], quant[hi], alpha=alpha, color="tab:red", linewidth=0,
+                              label=f"{100 * q[lo]:g} - {100 * q[hi]:g} %")
+    centre = (lambda ch: np.asarray(ch["quantiles"], dtype=np.float64)[mid]) if mid is not None else \
+        (lambda ch: np.asarray(ch["mean"], dtype=np.float64))
+    ax_r.plot(t, centre(rng), color="tab:red", linewidth=1.5, label=f"{100 * q[mid]:g} %" if mid is not None else "mean")
+    exits = (result.get("statistics") or {}).get("exit_time")
+    if exits and exits.get("count", 0) > 0:
+        for v in exits["quantiles"]:
+            if np.isfinite(v):
+                ax_r.axvline(float(v), color="black", linewidth=0.8, linestyle="--")
+    p = result.get("exit_probability", float("nan"))
+    title = "IIP Range over Termination Time"
+    if np.isfinite(p):
+        lo, hi = result.get("exit_interval", (0.0, 1.0))
+        title += f"\nP(IIP leaves keep-in) = {100 * p:.2f} % [{100 * lo:.2f}, {100 * hi:.2f}]"
+    ax_r.set_title(title)
+    ax_r.set_xlabel("Time of Termination since Rail Exit (s)")
+    ax_r.set_ylabel("IIP Range (m)")
+    ax_r.grid(True, alpha=0.3)
+    ax_r.legend(loc="best", fontsize=8)
+    ax_xy.plot(centre(result["x"]), centre(result["y"]), color="tab:red", linewidth=1.5, marker=".", markersize=3,
+               label="median IIP" if mid is not None else "mean IIP")
+    keep = result.get("keep_in")
+    if keep:
+        kx, ky = [v[0] for v in keep] + [keep[0][0]], [v[1] for v in keep] + [keep[0][1]]
+        ax_xy.plot(kx, ky, color="black", linewidth=1.2, label="keep-in area")
+    ax_xy.set_title(f"IIP Ground Track ({int(result.get('n_counted', 0))} samples)")
+    ax_xy.set_xlabel("X (m)")
+    ax_xy.set_ylabel("Y (m)")
+    ax_xy.grid(True, alpha=0.3)
+    ax_xy.legend(loc="best", fontsize=8)
+    fig.tight_layout()
+    return fig
+
+
 def sobol_figure(result):
     """The dict of analysis.sobol_indices as paired bars: per row one panel, per group the first-order index S1 and the
     total-effect index ST side by side in the order of `group_names`, their bootstrap percentile intervals (lo, hi) as
@@ -591,6 +641,17 @@ def plot_trajectory_corridor(analyzer, corridor, save_plots=True):
     if save_plots:
         output_dir = analyzer._create_output_directory()
         print(f"Trajectory corridor plot saved to: {save_figure(fig, output_dir, 'monte_carlo_corridor.png')}")
+    return output_dir
+
+
+def plot_impact_point_trace(analyzer, trace, save_plots=True):
+    """The IIP trace of MonteCarloAnalyzer.impact_point_trace (no reference counterpart) as monte_carlo_impact_points.png;
+    returns the output directory (None without save_plots)."""
+    fig = impact_point_figure(trace)
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Impact point trace plot saved to: {save_figure(fig, output_dir, 'monte_carlo_impact_points.png')}")
     return output_dir
 
 

@@ -359,6 +359,88 @@ enum { ERPL_ENV_MAX_Q = 0, ERPL_ENV_MAX_Q_TIME = 1, ERPL_ENV_MAX_Q_ALT = 2, ERPL
        ERPL_ENV_BURNOUT_SPEED = 12, ERPL_ENV_BURNOUT_STABILITY = 13, ERPL_ENV_APOGEE_RECORD = 14, ERPL_ENV_USABLE = 15 };
 int erpl_mc_flight_envelope(erpl_ctx* ctx, const erpl_batch* batch, const erpl_out* out, double* envelope, void* hip_stream);
 
+/* The instantaneous impact points (IIP) of every captured trajectory of a run ON THE DEVICE (no reference counterpart): if
+ * the flight is terminated at the time of a stored record - thrust ends, nothing else changes - where does the vehicle
+ * come down?  Every chosen record (a NODE) of every trajectory falls from its own position and velocity to the ground plane
+ * under gravity, drag and the sample's own wind; the trace of impact points over the flight, and what a range-safety
+ * officer reads off it: how far the IIP ever gets, how fast it moves, when it first leaves a keep-in area.
+ * `batch` and `out` as for erpl_mc_flight_envelope: the batch the records came from (fp64 wind tables: ERPL_PREC_F64 or
+ * ERPL_PREC_F64_FAST; rocket, motor, alt_grid and wind are read, ic is not) and the erpl_out of that run (n_traj, traj_ids,
+ * traj_cap, traj and traj_len are read).  `values` is CALLER-OWNED device memory, double [ERPL_IIP_CH_COUNT][n_nodes][ld]:
+ * trajectory j writes column col0 + j of all ERPL_IIP_CH_COUNT * n_nodes rows and nothing else - the layout of
+ * erpl_mc_corridor_resample, so erpl_mc_corridor_bands bands the matrix as it is and sub-batches fill their own windows of
+ * columns.  `summary` is CALLER-OWNED device memory, double [ERPL_IIP_DIM][n_traj] (accepted wherever a summary is), or
+ * NULL.  Asynchronous on `hip_stream`: no workspace, no host result, no host wait.
+ *
+ * Nodes.  u = the usable prefix of erpl_mc_flight_envelope (the first record with a non-finite time or state entry, len if
+ *   there is none), ts(r) = rec[r][0] - rec[0][0].  Node k sits on record r_k = k * record_stride and is EVALUATED iff
+ *   r_k < u.  An evaluated node is OF PHYSICAL SIZE iff sqrt((vx*vx + vy*vy) + vz*vz) <= 1e6 and z >= -1e5 (the thresholds
+ *   at which the throughput build hands a blown-up lane over).  A node that is not evaluated, not of physical size or does
+ *   not land has NaN in all five channels.
+ * The fall of one node, in fp64 through the device functions of the ERPL_PREC_F64 build, no contraction:
+ *   state s = (x, y, z, vx, vy, vz) of the record; mass and centre of gravity FROZEN at mass_props(max(pf, 0)) of the record.
+ *   RHS at a state, in this order: atmosphere(z) -> T, P; rho = P / (Rg * T); g = gravity(z); w = the sample's wind at z
+ *     (zero without a table); vr = v - w; vn = sqrt((vr0*vr0 + vr1*vr1) + vr2*vr2); mach = vn / sqrt((1.4 * 287.053) * T);
+ *     cd = the drag coefficient at that Mach number with alpha = beta = 0, power off, times drag_scale;
+ *     k = ((((0.5 * rho) * vn) * cd) * reference_area) / mass;  ds = (vx, vy, vz, -k*vr0, -k*vr1, -k*vr2 - g).
+ *   Classic RK4, h2 = 0.5 * dt: stage states s + h2*k1, s + h2*k2, s + dt*k3;
+ *     s' = s + (dt / 6.0) * ((k1 + 2.0*k2) + (2.0*k3 + k4)), each operation rounded on its own.
+ *   A start with z <= ground: X, Y the record's own, TFALL = 0, VIMPACT = |v|.  Otherwise step n = 0, 1, ... until
+ *     s' holds a non-finite entry (the node does not land), or
+ *     z' <= ground: with wq = (z - ground) / (z - z'): X = x + (x' - x) * wq, Y likewise, TFALL = ((double)n + wq) * dt,
+ *       VIMPACT = the norm of v + (v' - v) * wq, summed as above, or
+ *     n + 1 == max_steps (the node does not land).
+ *   RANGE = sqrt(dx*dx + dy*dy) of (X - origin_x, Y - origin_y).
+ *   The impact point is where the polyline of RK4 states crosses the ground plane: continuous in the inputs even where the
+ *   crossing moves to a neighbouring step, so no step count is part of the contract.
+ * The model and its limits: a ballistic fall at zero incidence with the power-off drag curve; no lift, no attitude, no
+ *   parachute, no tumbling model beyond drag_scale (0: vacuum, > 1: a body with more drag than the streamlined vehicle);
+ *   flat, non-rotating earth.
+ * Summary of trajectory j.  Only LANDED nodes (finite channels) take part in a value; ties go to the lowest node; a row
+ *   without a candidate is NaN (the envelope's (value, index) total order, no atomics).
+ *   MAX_RANGE with MAX_RANGE_TIME = ts of the node, MAX_RANGE_X / _Y its IIP.
+ *   BURNOUT_TIME = ts of the first evaluated node with ts > burn_time[id], given whenever that node exists;
+ *     BURNOUT_X / _Y its IIP, NaN if it did not land.
+ *   APOGEE_X / _Y: the IIP of the first evaluated node that holds the largest record altitude among evaluated nodes.
+ *   MAX_RATE: the largest sqrt(dX*dX + dY*dY) / (ts(r_{k+1}) - ts(r_k)) over consecutive nodes k, k + 1 that both landed
+ *     and have a positive time difference; MAX_RATE_TIME = ts(r_k).
+ *   EXIT_TIME, EXIT_X, EXIT_Y: ts and IIP of the first landed node whose IIP is OUTSIDE the keep-in polygon keep_x / keep_y
+ *     [n_vertices]: not inside by the even-odd crossing rule exactly as erpl_mc_impact_density states it for its zones, every
+ *     operation rounded on its own.  NaN without a polygon or without such a node.
+ *   LANDED, NODES: the number of landed and of evaluated nodes, as doubles.
+ * The bytes of column j of `values` and of `summary` depend only on the trajectory's own records, its sample's parameters
+ * and the spec - not on what shares its wave, its workgroup or the launch.
+ * Errors: ERPL_ERR_INVALID, before any device work and with a message that names the argument, in this order: NULL batch /
+ * out / spec / values; the spec fields in struct order, each against the range beside it; a keep-in vertex that is not
+ * finite; a precision other than the two fp64 values; batch->n <= 0; n_traj < 0 or >= 2^31; col0 < 0; ld < col0 + n_traj;
+ * with n_traj > 0: traj_cap < 1, NULL traj_ids / traj / traj_len / rocket / motor, bad wind arguments; the context last
+ * (without a config: ERPL_ERR_CONFIG).  n_traj == 0 is a no-op that returns ERPL_OK. */
+#define ERPL_IIP_DIM 16           /* = ERPL_SUMMARY_DIM: an IIP summary is accepted wherever a summary is */
+#define ERPL_IIP_MAX_NODES 4096   /* = ERPL_CORRIDOR_MAX_NODES */
+#define ERPL_IIP_MAX_STEPS (1 << 20)
+#define ERPL_IIP_MAX_VERTICES 64
+enum { ERPL_IIP_CH_X = 0, ERPL_IIP_CH_Y = 1, ERPL_IIP_CH_RANGE = 2, ERPL_IIP_CH_TFALL = 3, ERPL_IIP_CH_VIMPACT = 4,
+       ERPL_IIP_CH_COUNT = 5 };
+enum { ERPL_IIP_MAX_RANGE = 0, ERPL_IIP_MAX_RANGE_TIME = 1, ERPL_IIP_MAX_RANGE_X = 2, ERPL_IIP_MAX_RANGE_Y = 3,
+       ERPL_IIP_BURNOUT_TIME = 4, ERPL_IIP_BURNOUT_X = 5, ERPL_IIP_BURNOUT_Y = 6, ERPL_IIP_APOGEE_X = 7, ERPL_IIP_APOGEE_Y = 8,
+       ERPL_IIP_MAX_RATE = 9, ERPL_IIP_MAX_RATE_TIME = 10, ERPL_IIP_EXIT_TIME = 11, ERPL_IIP_EXIT_X = 12, ERPL_IIP_EXIT_Y = 13,
+       ERPL_IIP_LANDED = 14, ERPL_IIP_NODES = 15 };
+typedef struct erpl_iip_spec {
+  int32_t n_nodes;         /* 1..ERPL_IIP_MAX_NODES */
+  int32_t record_stride;   /* >= 1: node k is record k * record_stride */
+  int32_t max_steps;       /* 1..ERPL_IIP_MAX_STEPS */
+  int32_t n_vertices;      /* 0 (no keep-in area) or 3..ERPL_IIP_MAX_VERTICES */
+  double dt;               /* finite, > 0 */
+  double ground;           /* finite */
+  double drag_scale;       /* finite, >= 0 (0: no drag; > 1: a tumbling body) */
+  double origin_x, origin_y; /* finite: RANGE is measured from here */
+  double keep_x[ERPL_IIP_MAX_VERTICES], keep_y[ERPL_IIP_MAX_VERTICES];
+} erpl_iip_spec;
+/* host only: 64 nodes, record_stride 1, max_steps 20000, dt 0.05, ground 0, drag_scale 1, origin (0, 0), no polygon */
+int erpl_mc_impact_points_defaults(erpl_iip_spec* spec);
+int erpl_mc_impact_points(erpl_ctx* ctx, const erpl_batch* batch, const erpl_out* out, const erpl_iip_spec* spec,
+                          double* values, int64_t ld, int64_t col0, double* summary, void* hip_stream);
+
 /* Host-side input preparation (no device work): the first `m` outputs of NumPy's legacy
  * `np.random.RandomState(seed)` for each of `n` integer seeds, bit for bit - the reference draws
  * every sample's dispersions, motor perturbation and wind turbulence from such per-sample streams
