@@ -44,6 +44,7 @@ ENV_DIM = 16
 END_MAX_TIME, END_GROUND, END_ALTITUDE, END_COAST, END_APOGEE = range(5)
 ST_APOGEE_LATCHED, ST_CHUTE, ST_NAN, ST_INCOMPLETE = 1 << 8, 1 << 9, 1 << 10, 1 << 11
 ERR_INCOMPLETE = -5
+ERR_INTERNAL = -6
 
 _M = C.c_double * MAX_MACH_KNOTS
 _T = C.c_double * MAX_CURVE_KNOTS
@@ -376,6 +377,18 @@ class ErplCompare(C.Structure):
                 ("d_ab", C.c_double), ("d_aa", C.c_double), ("d_bb", C.c_double), ("energy", ErplCmpTest)]
 
 
+# erpl_mc_design
+DESIGN_MAX_ROWS = 4096
+DESIGN_RANDOM, DESIGN_LHS, DESIGN_LHS_CENTRED = 0, 1, 2
+DESIGN_UNIFORM, DESIGN_NORMAL = 0, 1
+DESIGN_KINDS = {"random": DESIGN_RANDOM, "lhs": DESIGN_LHS, "lhs_centred": DESIGN_LHS_CENTRED}
+
+
+class ErplDesignSpec(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("rows", C.c_int32), ("first_row", C.c_int32), ("reserved", C.c_int32),
+                ("n", C.c_int64), ("block", C.c_int64), ("seed", C.c_uint64)]
+
+
 LIB_NAME = "liberpl_mc.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
@@ -402,7 +415,8 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_sobol_defaults", "erpl_mc_sobol",
            "erpl_mc_dependence_defaults", "erpl_mc_dependence",
            "erpl_mc_compare_defaults", "erpl_mc_compare", "erpl_mc_compare_labels",
-           "erpl_mc_legacy_random_streams_device", "erpl_mc_legacy_wind_profiles_device")
+           "erpl_mc_legacy_random_streams_device", "erpl_mc_legacy_wind_profiles_device",
+           "erpl_mc_design_defaults", "erpl_mc_design", "erpl_mc_design_host")
 
 _lib = None
 
@@ -511,6 +525,10 @@ def load_library(path=None):
                                                          C.c_int32, C.c_void_p]
     lib.erpl_mc_legacy_wind_profiles_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 9 + \
         [C.c_int32, C.c_void_p]
+    lib.erpl_mc_design_defaults.argtypes = [C.POINTER(ErplDesignSpec)]
+    lib.erpl_mc_design.argtypes = [C.c_void_p, C.POINTER(ErplDesignSpec), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                   C.c_void_p]
+    lib.erpl_mc_design_host.argtypes = [C.POINTER(ErplDesignSpec), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if a declared symbol is not exported
         if name not in ("erpl_mc_last_error",):

@@ -487,13 +487,55 @@ def confidence_intervals(summary, status=None, engine=None, rows=None, quantiles
     apogee, range, flight time).  Returns, per row name (ROW_NAMES), {'mean': {estimate, se, lo, hi}, 'std': {..},
     'percentiles': [{..}, ..]} - se the bootstrap standard error, (lo, hi) the `level` percentile interval - plus
     'n_samples', 'n_outliers', 'count' (the population: kept and finite in every row), 'quantiles', 'level',
-    'replicates' and 'seed'."""
+    'replicates' and 'seed'.
+
+    The bootstrap assumes i.i.d. columns.  The columns of a Latin hypercube run (run_monte_carlo_device(design='lhs')) are
+    not: they are negatively dependent, the mean of a near-additive output varies far less than resampling its columns
+    suggests, and these intervals are conservative (too wide) for such a run.  Its valid error bar comes from independent
+    replicates of the design: `replicate_intervals`."""
     engine, res, why = _filter(summary, status, engine)
     b = engine.bootstrap(summary, why, rows=rows, quantiles=quantiles, replicates=replicates, level=level, seed=seed)
     out = {ROW_NAMES[r]: {"mean": _interval(s["mean"]), "std": _interval(s["std"]),
                           "percentiles": [_interval(p) for p in s["quantiles"]]} for r, s in zip(b["rows"], b["stats"])}
     out["n_samples"], out["n_outliers"], out["count"] = int(res.n_valid), int(res.n_outliers), b["count"]
     out["quantiles"], out["level"], out["replicates"], out["seed"] = b["q"], b["level"], b["replicates"], b["seed"]
+    return out
+
+
+def replicate_intervals(summary, status, block, rows=None, level=0.95, engine=None):
+    """The error bar of a replicated design run (run_monte_carlo_device(design=..., design_replicates=R) with
+    block = n_samples / R): the columns [j block, (j + 1) block) of `summary` are R independent replicates of one design,
+    so the R replicate means of a row are i.i.d. whatever the dependence inside a replicate.  Per requested row (default
+    apogee, range, flight time) the mean of every replicate through erpl_mc_analyze on that column slice - outliers
+    filtered and non-finite values dropped as everywhere - and across the replicates the mean of means, its standard error
+    s / sqrt(R) (s with R - 1 in the denominator) and the Student-t interval at `level` with R - 1 degrees of freedom.
+    Returns, per row name (ROW_NAMES), {'replicate_means': [..], 'replicate_counts': [..], 'mean', 'se', 'lo', 'hi'}, plus
+    'replicates', 'block' and 'level'.  R = 1: se, lo and hi are NaN, one hypercube has no error bar of its own."""
+    from scipy import stats as sps
+
+    from . import _abi
+    engine = _engine_of(summary, engine)
+    n, block = int(summary.shape[1]), int(block)
+    if block < 1 or n % block != 0:
+        raise ValueError(f"block = {block} does not divide the {n} columns of the summary")
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError("level must lie in (0, 1)")
+    rows = [_abi.SUM_APOGEE_ALT, _abi.SUM_RANGE, _abi.SUM_FLIGHT_TIME] if rows is None else [int(r) for r in rows]
+    R = n // block
+    means, counts = np.empty((len(rows), R)), np.empty((len(rows), R), dtype=np.int64)
+    for j in range(R):
+        cols = slice(j * block, (j + 1) * block)
+        res, _ = engine.analyze(summary[:, cols].contiguous(), None if status is None else status[cols].contiguous(),
+                                rows=rows, quantiles=[])
+        for i in range(len(rows)):
+            means[i, j], counts[i, j] = res.row[i].mean, res.row[i].count
+    out = {"replicates": R, "block": block, "level": float(level)}
+    for i, r in enumerate(rows):
+        mean = float(np.mean(means[i]))
+        se = float(np.std(means[i], ddof=1) / np.sqrt(R)) if R > 1 else float("nan")
+        half = float(sps.t.ppf(0.5 + 0.5 * float(level), R - 1)) * se if R > 1 else float("nan")
+        out[ROW_NAMES[r]] = {"replicate_means": means[i].tolist(), "replicate_counts": counts[i].tolist(), "mean": mean,
+                             "se": se, "lo": mean - half, "hi": mean + half}
     return out
 
 

@@ -466,6 +466,8 @@ int erpl_mc_destroy(erpl_ctx* c) {
   (void)hipFree(c->legacy_buf);
   if (c->legacy_pin) (void)hipHostFree(c->legacy_pin);
   for (hipEvent_t e : c->legacy_ev) if (e) (void)hipEventDestroy(e);
+  if (c->design_flag) (void)hipHostFree(c->design_flag);
+  if (c->design_ev) (void)hipEventDestroy(c->design_ev);
   delete c;
   return ERPL_OK;
 }
@@ -636,6 +638,7 @@ int report_incomplete(int64_t t, unsigned long long lost) {
 // are acknowledged afterwards (erpl_mc_check_batch(T) keeps answering for T itself while T's record is in the ring).
 int check_all(erpl_ctx* c) {
   ERPL_TRY(wait_all_host(c));
+  ERPL_TRY(erpl_design_check_flag(c));
   int64_t bad = c->recycled_incomplete;
   unsigned long long lost = 0ull;
   for (int i = 0; i < ERPL_TICKET_RING; ++i) {

@@ -1,5 +1,5 @@
 // erpl_host.h — what the host units of the C ABI share (erpl_api.hip, erpl_sampling.hip, erpl_stats_api.hip,
-// erpl_legacy_device.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
+// erpl_legacy_device.hip, erpl_design.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
 // Internal, never installed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -228,7 +228,14 @@ struct erpl_ctx {
   char* legacy_pin = nullptr;
   size_t legacy_pin_cap = 0;
   hipEvent_t legacy_ev[2] = {};
+  // erpl_mc_design: the pinned word its kernel raises when a cycle walk is given up, and the event behind the latest call
+  // (both made by the first call; erpl_design_check_flag reads them for the blocking checks)
+  int* design_flag = nullptr;
+  hipEvent_t design_ev = nullptr;
 };
+
+// erpl_design.hip
+__attribute__((visibility("hidden"))) int erpl_design_check_flag(erpl_ctx* c);
 
 // The scale of an accepted pair of the legacy polar Gaussian (LegacyRS::next_gauss, and the host phase of the device
 // streams): the one copy, so that both go through the same libm log with the same rounding of the quotient.

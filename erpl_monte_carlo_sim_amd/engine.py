@@ -732,6 +732,36 @@ class TrajectoryEngine:
             out["ranks"] = rk
         return out
 
+    def design(self, rows_kinds, n, seed, kind="lhs", block=0, first=0, count=None, first_row=0, out=None):
+        """Columns first .. first + count - 1 (default: all from `first`) of the design (seed, kind, n, block, first_row) of
+        erpl_mc_design, drawn on the device: one row per entry of `rows_kinds` (_abi.DESIGN_UNIFORM: the probability in
+        (0, 1); _abi.DESIGN_NORMAL: its normal quantile; a sequence or a bytes object), the global rows first_row ...
+        kind: 'random', 'lhs' or 'lhs_centred' (or the _abi.DESIGN_* value); block: the columns of a replicate, a divisor
+        of n, 0 = n.  Counter-based: a window equals those columns of the whole design bit for bit, wherever and in
+        whatever pieces it is generated.  out: None (a new float64 [rows, count] tensor) or a float64 device tensor
+        [rows, ld] with unit column stride and ld >= count, of which columns 0 .. count - 1 are written.  Asynchronous on
+        the current stream; returns the tensor."""
+        kinds = bytes(bytearray(int(k) for k in rows_kinds))
+        n, first = int(n), int(first)
+        count = n - first if count is None else int(count)
+        spec = self._defaults(_abi.ErplDesignSpec, "erpl_mc_design_defaults")
+        spec.kind = _abi.DESIGN_KINDS[kind] if isinstance(kind, str) else int(kind)
+        spec.rows, spec.first_row, spec.n, spec.block = len(kinds), int(first_row), n, int(block)
+        spec.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if out is None:
+            out = torch.empty((len(kinds), max(count, 0)), dtype=torch.float64, device=self.device)
+        if not (torch.is_tensor(out) and out.is_cuda and out.device == self.device and out.dtype == torch.float64
+                and out.dim() == 2 and out.shape[0] == len(kinds) and out.shape[1] >= count
+                and (out.shape[1] == 0 or out.stride(1) == 1) and (out.shape[0] == 1 or out.stride(0) >= out.shape[1])):
+            raise ValueError(f"out must be a float64 [{len(kinds)}, >= {count}] tensor on {self.device} with unit column stride")
+        ld = out.stride(0) if out.shape[0] > 1 else max(out.shape[1], 1)
+        st = torch.cuda.current_stream(self.device)
+        if count == 0 and out.numel() == 0:   # an empty tensor has no storage to point at, and count == 0 writes nothing
+            return out
+        self._call("erpl_mc_design", C.byref(spec), kinds, first, count, C.c_void_p(out.data_ptr()), ld,
+                   C.c_void_p(st.cuda_stream))
+        return out
+
     def bootstrap(self, summary, mask=None, rows=None, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), replicates=2000, level=0.95,
                   seed=0, extra=None, want_replicates=False):
         """How sure the statistics of a run are (erpl_mc_bootstrap): the non-parametric bootstrap of mean, std and

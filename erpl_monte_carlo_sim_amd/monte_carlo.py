@@ -284,7 +284,7 @@ class MonteCarloAnalyzer:
         return out
 
     def run_monte_carlo_device(self, initial_conditions, n_samples, seed=1234, precision="f64_fast", planar=False,
-                               keep_factors=False):
+                               keep_factors=False, design=None, design_replicates=1):
         """Throughput form for 100 k - 10 M samples (BASELINE configs 3-5): dispersions are drawn on the
         device (`sampling.synthetic_dispersions`, same distributions, torch generator), each rank
         integrates `n_samples / world` of them, summaries are all-gathered and the outlier filter +
@@ -300,10 +300,33 @@ class MonteCarloAnalyzer:
 
         keep_factors=True keeps the per-sample draws (`sampling.FACTOR_NAMES`) and adds out["factors"] (float64
         [F, n_samples] on the device, sample order of out["summary"]) and out["factor_names"], the input of
-        `analysis.drivers`.  One rank only: factors are not gathered across ranks (ValueError before any work)."""
+        `analysis.drivers`.  One rank only: factors are not gathered across ranks (ValueError before any work).
+
+        design: None (the draws above: the reference's JOINT law from torch's generator, sub-batch j from
+        seed + rank + 1000003 * j, bit for bit as before), or 'random', 'lhs' or 'lhs_centred': the run flies ONE global
+        design of n_samples columns (`sampling.design_draws`, erpl_mc_design) of which every rank and every sub-batch
+        generates its own window, so its inputs depend on (seed, n_samples, design, design_replicates) alone and not on the
+        world size or on DEVICE_CHUNK.  Such a run is drawn under the INDEPENDENT law of
+        `sampling.synthetic_dispersions(draws=...)` - a deliberate deviation from the reference's joint law, as in
+        `sobol_indices`: a design stratifies every primitive by itself, and under the joint law one normal is the thrust
+        multiplier, `position_x` and the first turbulence innovation at once.  'lhs' stratifies each of the 17 + 3 K + 2
+        primitives (Latin hypercube sampling: the variance of the mean of a near-additive output such as the apogee falls
+        well below the i.i.d. one).  design_replicates = R splits the design into R independent Latin hypercubes of
+        n_samples / R columns each (ValueError if R does not divide n_samples): `analysis.replicate_intervals` with
+        block = n_samples / R gives the valid error bar of such a run, which the columns of ONE hypercube cannot give.
+        out["design"] records kind, seed, block and replicates."""
         from . import sampling
         if keep_factors and dist.world()[1] > 1:
             raise ValueError("keep_factors=True is limited to a world size of 1: factors are not gathered across ranks")
+        if design is not None:
+            if design not in _abi.DESIGN_KINDS:
+                raise ValueError(f"design: None or one of {list(_abi.DESIGN_KINDS)}")
+            design_replicates = int(design_replicates)
+            if design_replicates < 1 or n_samples % design_replicates != 0:
+                raise ValueError(f"design_replicates = {design_replicates} does not divide n_samples = {n_samples}")
+            design_block = n_samples // design_replicates
+            use_base = self.base_wind_profile is not None and self.base_altitude_profile is not None
+            design_K = len(self.base_altitude_profile) if use_base else 100   # synthetic_dispersions' default grid
         eng = shared_engine(self.device)
         eng.set_config(self._config())
         rank, ws = dist.world()
@@ -332,11 +355,16 @@ class MonteCarloAnalyzer:
                 group = []
                 for j in range(g0, min(g0 + GROUP, len(starts))):
                     a = starts[j]
+                    cnt = min(self.DEVICE_CHUNK, m - a)
+                    draws = None
+                    if design is not None:   # this sub-batch's window of the global design (a rank without samples: any column)
+                        draws = sampling.design_draws(n_samples, design_K, eng.device, seed, design=design, block=design_block,
+                                                      first=min(lo + a, n_samples - cnt), count=cnt, engine=eng)
                     group.append(sampling.synthetic_dispersions(
-                        min(self.DEVICE_CHUNK, m - a), self.rocket, self.motor, self.wind_model, initial_conditions, eng.device,
+                        cnt, self.rocket, self.motor, self.wind_model, initial_conditions, eng.device,
                         precision=prec, seed=seed + rank + 1000003 * j, uncertainty=self.uncertainty_params,
                         base_altitude_profile=self.base_altitude_profile, base_wind_profile=self.base_wind_profile,
-                        planar=planar, engine=eng))
+                        planar=planar, engine=eng, draws=draws))
                 gen_s += time.time() - tg
                 for db in group:
                     parts.append(eng.submit(db))
@@ -377,6 +405,8 @@ class MonteCarloAnalyzer:
         if keep_factors:
             fac = fparts[0] if len(fparts) == 1 else torch.cat(fparts, dim=1)
             out["factors"], out["factor_names"] = fac[:, : hi - lo].contiguous(), list(fnames)
+        if design is not None:
+            out["design"] = {"kind": design, "seed": int(seed), "block": design_block, "replicates": design_replicates}
         out["performance"] = {"total_time": t3 - t0, "simulations_per_second": n_samples / (t3 - t0), "gpus_used": ws,
                               "precision": precision, "generate_s": gen_s, "integrate_and_gather_s": t2 - t0 - gen_s,
                               "statistics_s": t3 - t2, "sub_batches": len(parts), "in_flight": eng.get_overlap()}
@@ -647,7 +677,7 @@ class MonteCarloAnalyzer:
                                         replicates=replicates, level=level, seed=seed)
 
     def sobol_indices(self, initial_conditions, n_base=16384, groups=None, rows=None, seed=1234, precision="f64_fast",
-                      planar=False, filter_outliers=False, replicates=1000, level=0.95, bootstrap_seed=0):
+                      planar=False, filter_outliers=False, replicates=1000, level=0.95, bootstrap_seed=0, design=None):
         """Which dispersion drives what, interactions included (no reference counterpart; at its 4 k flights/s nobody
         flies (k + 2) n_base flights for it): the variance-based (Sobol) first-order and total-effect indices of `groups`
         of inputs on summary rows `rows` (default first apogee altitude and time, rail-exit speed: outputs every flight
@@ -660,6 +690,9 @@ class MonteCarloAnalyzer:
         mapping name -> rows of the primitive tensor (disjoint, at most 32).  A and B are `sampling.primitive_draws` at
         `seed` and `seed + 1`; block b of the k + 2 blocks (A, B, A with group i from B) is flown through eng.submit in
         sub-batches of at most DEVICE_CHUNK, inputs released per ticket, as run_monte_carlo_device does.
+        design: None keeps those draws; 'random', 'lhs' or 'lhs_centred' takes A and B from `sampling.design_draws`
+        (erpl_mc_design) at `seed` and `seed + 1` instead: two independent designs of n_base columns, every primitive
+        stratified with 'lhs'.
         filter_outliers=True masks a design row when erpl_mc_analyze gives ANY of its k + 2 flights a reason.
         One rank only (ValueError before any work): a design is not gathered across ranks.
 
@@ -691,8 +724,12 @@ class MonteCarloAnalyzer:
         prec = _abi.PRECISIONS[precision]
         torch.cuda.synchronize(eng.device)
         t0 = time.time()
-        A = sampling.primitive_draws(n_base, K, eng.device, seed)
-        B = sampling.primitive_draws(n_base, K, eng.device, seed + 1)
+        if design is None:
+            A = sampling.primitive_draws(n_base, K, eng.device, seed)
+            B = sampling.primitive_draws(n_base, K, eng.device, seed + 1)
+        else:
+            A = sampling.design_draws(n_base, K, eng.device, seed, design=design, engine=eng)
+            B = sampling.design_draws(n_base, K, eng.device, seed + 1, design=design, engine=eng)
         parts, inflight = [], []
         keep = 2 * eng.get_overlap()
         for P in sampling.pick_freeze_blocks(A, B, dict(items)):
@@ -727,6 +764,8 @@ class MonteCarloAnalyzer:
         torch.cuda.synchronize(eng.device)
         t2 = time.time()
         out["groups"] = {name: list(r) for name, r in items}
+        if design is not None:
+            out["design"] = {"kind": design, "seed": int(seed), "block": n_base, "replicates": 1}
         out["summary"], out["status"], out["mask"] = summ, status, mask
         flights = (k + 2) * n_base
         out["performance"] = {"flights": flights, "fly_s": t1 - t0, "flights_per_second": flights / max(t1 - t0, 1e-9),

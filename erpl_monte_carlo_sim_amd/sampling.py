@@ -76,6 +76,21 @@ def primitive_draws(n, K, device, seed):
     return torch.cat([z, uni]).contiguous()
 
 
+def design_draws(n, K, device, seed, design="lhs", block=0, first=0, count=None, engine=None):
+    """Columns first .. first + count - 1 (default: all from `first`) of the float64 [17 + 3 K + 2, n] primitives of the
+    independent law as ONE design of n columns (erpl_mc_design): the row kinds of `primitive_draws`, normals and in the last
+    two rows uniforms - here in (0, 1), which every consumer of the [0, 1) rows accepts.  design: 'random' (independent
+    draws), 'lhs' (every row stratified: each of the m strata of a replicate holds one column) or 'lhs_centred'; block = m:
+    n / m independent replicates of m columns each, 0 = n.  Counter-based on (seed, row, column): a window is the same bits
+    whatever rank or sub-batch generates it."""
+    device = torch.device(device)
+    if engine is None:
+        from .simulator import shared_engine
+        engine = shared_engine(device)
+    kinds = [_abi.DESIGN_NORMAL] * (17 + 3 * int(K)) + [_abi.DESIGN_UNIFORM] * 2
+    return engine.design(kinds, n, seed, kind=design, block=block, first=first, count=count)
+
+
 def primitive_groups(K, liquid=True):
     """The default factors of a pick-freeze design: an ordered mapping group name -> rows of the primitive tensor.  Rows 16
     (and 15 for a solid motor: its burn-time and impulse draws, drawn then unused) belong to no group."""

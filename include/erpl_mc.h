@@ -51,8 +51,9 @@ typedef enum erpl_status {
   ERPL_ERR_HIP = -2,       /* a HIP runtime call failed */
   ERPL_ERR_NO_DEVICE = -3, /* no usable GPU: the product path never falls back to a CPU */
   ERPL_ERR_CONFIG = -4,    /* run_batch before set_config */
-  ERPL_ERR_INCOMPLETE = -5 /* a lane hand-over of a finished batch timed out: the samples whose status word still
+  ERPL_ERR_INCOMPLETE = -5,/* a lane hand-over of a finished batch timed out: the samples whose status word still
                               carries ERPL_ST_INCOMPLETE were not integrated (erpl_mc_set_adopt) */
+  ERPL_ERR_INTERNAL = -6   /* a defensive bound of the library's own code was reached (erpl_mc_design) */
 } erpl_status;
 
 enum { ERPL_MOTOR_LIQUID = 0, ERPL_MOTOR_SOLID = 1 };
@@ -506,6 +507,72 @@ int erpl_mc_legacy_wind_profiles_device(erpl_ctx* ctx, const uint32_t* seeds, in
 int erpl_mc_synth_wind(erpl_ctx* ctx, int64_t n, int32_t k, const double* normals, const double* sigma,
                        const double* rho, const double* innov, const double* base, const double* scale,
                        const double* mean_u, const double* mean_v, void* wind, int32_t precision, void* hip_stream);
+
+/* The primitives of a run as ONE design, drawn ON THE DEVICE (no reference counterpart): independent draws or Latin
+ * hypercube samples, counter-based, so that any window of columns of one global design is generated anywhere, without
+ * communication, and a run flown from it does not depend on the world size or on the sub-batches.  A design is defined by
+ * (seed, kind, n, block, first_row): a matrix of rows x n doubles.  A call produces its columns first .. first + count - 1
+ * into out[rows][ld], caller-owned device memory (host memory for erpl_mc_design_host) with ld >= count; the entries
+ * [.., count .. ld - 1] are never written.  `kinds` [rows] is host memory and says per row whether the value is the
+ * probability p itself (ERPL_DESIGN_UNIFORM, in (0, 1)) or the normal quantile of p (ERPL_DESIGN_NORMAL).  The spec is host
+ * memory.  erpl_mc_design enqueues on `hip_stream` behind what is there and returns without waiting, as erpl_mc_synth_wind
+ * does; it needs no workspace (a pinned flag word and an event, made by the first call, freed by erpl_mc_destroy).
+ * ERPL_ERR_INVALID, before any device work and with a message that names the argument, for: a NULL spec, kinds or out; an
+ * unknown spec->kind; rows < 1, first_row < 0 or first_row + rows > ERPL_DESIGN_MAX_ROWS; n < 1 or n >= 2^31; block
+ * negative, above n or not dividing n; first or count negative or first + count > n; ld < count; a byte of `kinds` that
+ * is neither ERPL_DESIGN_UNIFORM nor ERPL_DESIGN_NORMAL - in this order, the context last.  count == 0 is ERPL_OK and
+ * writes nothing.  Two calls with the same arguments return the same bytes, and a window equals the same columns of the
+ * full call, bit for bit.
+ *
+ * Kinds: ERPL_DESIGN_RANDOM p = u; ERPL_DESIGN_LHS p = (pi + u) / m; ERPL_DESIGN_LHS_CENTRED p = (pi + 0.5) / m.
+ * Blocks and replicates: block = m (1 <= m <= n, n % m == 0) makes the design n / m independent Latin hypercubes of m
+ * columns each, the replicates; column i has the replicate rho = i / m and the local index l = i % m; block = 0 means
+ * m = n.  In every row of every replicate each stratum [k / m, (k + 1) / m) holds exactly one p.
+ * Round keys of (row r, replicate rho), r the GLOBAL row, first_row + the row in the call: Philox4x32-10 (as in
+ * erpl_mc_bootstrap) with the key (seed & 0xffffffff, seed >> 32) on the counters (r, 0, rho, 2) and (r, 1, rho, 2);
+ * k0..k3 are the four words of the first, k4 and k5 the words 0 and 1 of the second.
+ * Permutation pi = perm(l) over [0, m): b the smallest integer >= 1 with 4^b >= m, M = 2^b - 1; start with x = l and
+ * repeat until x < m: L = x >> b, R = x & M; six rounds r = 0..5 of (L, R) = (R, L ^ (fmix32((R + k_r) mod 2^32) & M));
+ * x = (L << b) | R - cycle walking on a six-round Feistel network; fmix32 is the MurmurHash3 finaliser (x ^= x >> 16;
+ * x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35; x ^= x >> 16).  The network is a bijection of [0, 4^b) and the cycle
+ * through l < m comes back to l, so the walk ends, each trip below m with probability above 1/4.  A walk of 4096 trips
+ * is given up all the same (only wrong code gets there): the value is NaN and the call an ERPL_ERR_INTERNAL, which
+ * erpl_mc_design_host returns itself and erpl_mc_design leaves to the next blocking check of ALL batches of the context:
+ * erpl_mc_synchronize, or erpl_mc_check_batch with ticket <= 0, which wait for the latest design call too and report
+ * the error once.
+ * Jitter: Philox with the same key on the counter (j & 0xffffffff, j >> 32, r, 1), j = i >> 1, i the GLOBAL column; the
+ * draw is o0 | o1 << 32 for even i and o2 | o3 << 32 for odd i; u = ((draw >> 11) + 0.5) * 2^-53.  The tags 1 and 2 in
+ * counter word 3 keep these streams apart from those of erpl_mc_bootstrap, erpl_mc_sobol and erpl_mc_compare (tag 0).
+ * Probability: s = (double)pi + u, and the double just below pi + 1 where s >= pi + 1; p = s / m.  That keeps p in its
+ * stratum and strictly inside (0, 1): the double just below m, divided by m, rounds to at most 1 - 2^-53.  For
+ * ERPL_DESIGN_RANDOM the one u that the + 0.5 rounds up to 1 is taken as 1 - 2^-53.  Permutation, jitter and p are
+ * integer work plus correctly rounded + and /: the same bits on the host and on the device.
+ * Normal rows: Wichura's algorithm AS 241, PPND16 (Applied Statistics 37, 1988): q = p - 0.5; |q| <= 0.425:
+ * r = 0.180625 - q^2, z = q A(r) / B(r); otherwise r = sqrt(-log(min(p, 1 - p))), z = C(r - 1.6) / D(r - 1.6) for r <= 5
+ * and E(r - 5) / F(r - 5) beyond, with the sign of q; polynomials of degree 7 by Horner.  A NumPy run of these formulae
+ * against scipy.special.ndtri on 2.4 million probabilities, tails down to 1e-300 included, differed by at most
+ * 1.06e-15 max(1, |z|); log and sqrt are the platform's, so host and device may differ in the last bits of a normal row. */
+#define ERPL_DESIGN_MAX_ROWS 4096
+enum { ERPL_DESIGN_RANDOM = 0, ERPL_DESIGN_LHS = 1, ERPL_DESIGN_LHS_CENTRED = 2 };   /* erpl_design_spec.kind */
+enum { ERPL_DESIGN_UNIFORM = 0, ERPL_DESIGN_NORMAL = 1 };                            /* a byte of `kinds` */
+
+typedef struct erpl_design_spec {
+  int32_t kind;                          /* ERPL_DESIGN_RANDOM / _LHS / _LHS_CENTRED */
+  int32_t rows;                          /* rows of this call, >= 1 */
+  int32_t first_row;                     /* global row of its first row; first_row + rows <= ERPL_DESIGN_MAX_ROWS */
+  int32_t reserved;
+  int64_t n;                             /* columns of the whole design, 1 <= n < 2^31 */
+  int64_t block;                         /* m: columns of a replicate, a divisor of n; 0 = n */
+  uint64_t seed;
+} erpl_design_spec;
+
+/* Host only: ERPL_DESIGN_LHS, rows 1, first_row 0, n 1, block 0, seed 0. */
+int erpl_mc_design_defaults(erpl_design_spec* spec);
+int erpl_mc_design(erpl_ctx* ctx, const erpl_design_spec* spec, const uint8_t* kinds, int64_t first, int64_t count,
+                   double* out, int64_t ld, void* hip_stream);
+/* Host only, no context, no device: the same code into host memory. */
+int erpl_mc_design_host(const erpl_design_spec* spec, const uint8_t* kinds, int64_t first, int64_t count, double* out,
+                        int64_t ld);
 
 /* Outlier filter + statistics of a finished run ON THE DEVICE, replacing MonteCarloAnalyzer.
  * _filter_physics_outliers + _analyze_results (monte_carlo.py:337-398, :400-473) for the scalar results:
