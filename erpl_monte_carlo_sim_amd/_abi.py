@@ -389,6 +389,36 @@ class ErplDesignSpec(C.Structure):
                 ("n", C.c_int64), ("block", C.c_int64), ("seed", C.c_uint64)]
 
 
+# erpl_mc_surrogate
+SUR_MAX_VARS = 32
+SUR_MAX_ROWS = 4
+SUR_ROW_EXTRA = 16
+SUR_MAX_DEGREE = 12
+SUR_MAX_ORDER = 4
+SUR_MAX_TERMS = 1024
+SUR_MAX_HOLDOUT = 1 << 20
+
+
+class ErplSurSpec(C.Structure):
+    _fields_ = [("n_vars", C.c_int32), ("n_rows", C.c_int32), ("rows", C.c_int32 * SUR_MAX_ROWS), ("degree", C.c_int32),
+                ("order", C.c_int32), ("holdout", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ErplSurRow(C.Structure):
+    _fields_ = [("fit_ok", C.c_int32), ("reserved", C.c_int32), ("mean", C.c_double), ("variance_pce", C.c_double),
+                ("tss_fit", C.c_double), ("rss_fit", C.c_double), ("r2", C.c_double),
+                ("tss_val", C.c_double), ("rss_val", C.c_double), ("q2", C.c_double),
+                ("first", C.c_double * SUR_MAX_VARS), ("total", C.c_double * SUR_MAX_VARS)]
+
+
+class ErplSurrogate(C.Structure):
+    _fields_ = [("n", C.c_int64), ("count", C.c_int64), ("n_masked", C.c_int64), ("n_non_finite", C.c_int64),
+                ("n_fit", C.c_int64), ("n_val", C.c_int64),
+                ("n_vars", C.c_int32), ("n_rows", C.c_int32), ("degree", C.c_int32), ("order", C.c_int32),
+                ("holdout", C.c_int32), ("n_terms", C.c_int32),
+                ("pivot_min", C.c_double), ("pivot_max", C.c_double), ("row", ErplSurRow * SUR_MAX_ROWS)]
+
+
 LIB_NAME = "liberpl_mc.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
@@ -416,7 +446,9 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_dependence_defaults", "erpl_mc_dependence",
            "erpl_mc_compare_defaults", "erpl_mc_compare", "erpl_mc_compare_labels",
            "erpl_mc_legacy_random_streams_device", "erpl_mc_legacy_wind_profiles_device",
-           "erpl_mc_design_defaults", "erpl_mc_design", "erpl_mc_design_host")
+           "erpl_mc_design_defaults", "erpl_mc_design", "erpl_mc_design_host",
+           "erpl_mc_surrogate_defaults", "erpl_mc_surrogate_terms", "erpl_mc_surrogate", "erpl_mc_surrogate_predict",
+           "erpl_mc_surrogate_predict_host")
 
 _lib = None
 
@@ -529,6 +561,14 @@ def load_library(path=None):
     lib.erpl_mc_design.argtypes = [C.c_void_p, C.POINTER(ErplDesignSpec), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                    C.c_void_p]
     lib.erpl_mc_design_host.argtypes = [C.POINTER(ErplDesignSpec), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
+    lib.erpl_mc_surrogate_defaults.argtypes = [C.POINTER(ErplSurSpec)]
+    lib.erpl_mc_surrogate_terms.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p]
+    lib.erpl_mc_surrogate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                      C.POINTER(ErplSurSpec), C.POINTER(ErplSurrogate)] + [C.c_void_p] * 6
+    lib.erpl_mc_surrogate_predict.argtypes = [C.c_void_p, C.POINTER(ErplSurSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                              C.c_int64, C.c_void_p, C.c_void_p]
+    lib.erpl_mc_surrogate_predict_host.argtypes = [C.POINTER(ErplSurSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                                   C.c_void_p]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if a declared symbol is not exported
         if name not in ("erpl_mc_last_error",):

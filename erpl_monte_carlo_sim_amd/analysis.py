@@ -661,6 +661,70 @@ def finish_given_data(out):
     return out
 
 
+# ---------------------------------------------------------------------------------- polynomial chaos surrogate
+def surrogate_terms(n_vars, degree, order):
+    """The terms of the polynomial chaos basis of erpl_mc_surrogate (host only, no device): int8 [P, 4, 2], per term the
+    (variable, degree) of its up to 4 factors in ascending variable order, unused slots (-1, 0); term 0 is the constant."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    P = C.c_int32(0)
+    _abi.check(lib, lib.erpl_mc_surrogate_terms(int(n_vars), int(degree), int(order), C.byref(P), None), "erpl_mc_surrogate_terms")
+    terms = np.empty((P.value, 4, 2), dtype=np.int8)
+    _abi.check(lib, lib.erpl_mc_surrogate_terms(int(n_vars), int(degree), int(order), C.byref(P), C.c_void_p(terms.ctypes.data)),
+               "erpl_mc_surrogate_terms")
+    return terms
+
+
+def polynomial_chaos(summary, factors, kinds, names, status=None, engine=None, rows=None, extra=None, degree=2, order=2, holdout=5,
+                     top=10):
+    """A polynomial chaos surrogate of a run of INDEPENDENT primitives (a run flown with design=...): erpl_mc_analyze for
+    the reason bytes (as `drivers`), then erpl_mc_surrogate (TrajectoryEngine.surrogate) of the rows of `factors` (float64
+    [V, n] device tensor of primitives, `kinds` their laws) on up to 4 summary rows over the samples the filter keeps.
+    Returns the dict of TrajectoryEngine.surrogate plus 'names', 'row_names', 'n_samples', 'n_outliers', 'ranking' (per row
+    the variable names by total index descending, NaN last) and 'interactions' (per row the `top` largest pair indices as
+    (name_i, name_j, index), descending).
+
+    Reading it: first / total / pair are shares of the variance the surrogate EXPLAINS; r2 is the share of the outcome's
+    variance the chosen variables explain at all (the turbulence rows of a flight are not among them), q2 the same on the
+    members held out of the fit - trust the indices and the emulator as far as q2 goes."""
+    engine = _engine_of(summary, engine)
+    names = list(names)
+    if len(names) != int(factors.shape[0]):
+        raise ValueError(f"{len(names)} names for {int(factors.shape[0])} variable rows")
+    engine, res, why = _filter(summary, status, engine)
+    out = engine.surrogate(factors, kinds, summary, why, rows=rows, extra=extra, degree=degree, order=order, holdout=holdout)
+    out["names"] = names
+    out["row_names"] = [ROW_NAMES[r] if r < len(ROW_NAMES) else "extra" for r in out["rows"]]
+    out["n_samples"], out["n_outliers"] = int(res.n_valid), int(res.n_outliers)
+    if out["n_val"] > 0:   # predicted against flown on (at most 4096 of) the held-out members, for the plot
+        import torch
+        from . import _abi
+        pred = engine.surrogate_predict(out["model"], factors)
+        y = torch.stack([extra if r == _abi.SUR_ROW_EXTRA else summary[r] for r in out["rows"]])
+        members = torch.nonzero((why == 0) & torch.isfinite(factors).all(0) & torch.isfinite(y).all(0)).flatten()
+        held = members[holdout - 1::holdout][:4096]
+        out["validation"] = {"samples": held.cpu().numpy(), "flown": y[:, held].cpu().numpy(),
+                             "predicted": pred[:, held].cpu().numpy()}
+    return finish_polynomial_chaos(out, top)
+
+
+def finish_polynomial_chaos(out, top=10):
+    """What `polynomial_chaos` adds to the dict of TrajectoryEngine.surrogate that needs no device: 'ranking' and
+    'interactions' (in place)."""
+    names = out["names"]
+    V = len(names)
+    out["ranking"], out["interactions"] = [], []
+    for j in range(len(out["rows"])):
+        total = np.asarray(out["total"][j], dtype=np.float64)
+        out["ranking"].append([names[v] for v in np.argsort(-np.where(np.isnan(total), -1.0, total), kind="stable")])
+        pair = np.asarray(out["pair"][j], dtype=np.float64)
+        found = [(pair[a, b], a, b) for a in range(V) for b in range(a + 1, V) if np.isfinite(pair[a, b])]
+        found.sort(key=lambda e: -e[0])
+        out["interactions"].append([(names[a], names[b], float(v)) for v, a, b in found[:top]])
+    return out
+
+
 # ---------------------------------------------------------------------------------- two runs: the same law?
 def permutation_labels(seed, permutation, m_a, m_b):
     """Side A (True) of permutation `permutation` of erpl_mc_compare with `seed`, for m_a + m_b pooled members (A's counted

@@ -462,10 +462,12 @@ int erpl_mc_destroy(erpl_ctx* c) {
   for (int i = 0; i < ERPL_TICKET_RING; ++i) if (c->ring_done[i]) (void)hipEventDestroy(c->ring_done[i]);
   if (c->ring_counters) (void)hipHostFree(c->ring_counters);
   c->ana.release(); c->dist.release(); c->corr.release(); c->boot.release(); c->dens.release(); c->corridor.release(); c->sobol.release();
-  c->dep.release(); c->cmp.release(); c->cmp_pop.release();
+  c->dep.release(); c->cmp.release(); c->cmp_pop.release(); c->sur.release(); c->sur_model.release();
   (void)hipFree(c->legacy_buf);
   if (c->legacy_pin) (void)hipHostFree(c->legacy_pin);
   for (hipEvent_t e : c->legacy_ev) if (e) (void)hipEventDestroy(e);
+  if (c->sur_pin) (void)hipHostFree(c->sur_pin);
+  if (c->sur_ev) (void)hipEventDestroy(c->sur_ev);
   if (c->design_flag) (void)hipHostFree(c->design_flag);
   if (c->design_ev) (void)hipEventDestroy(c->design_ev);
   delete c;

@@ -83,6 +83,12 @@ struct DepHost {
   ErplDepEst est[ERPL_DEP_MAX_ROWS * ERPL_DEP_MAX_FACTORS];
 };
 
+// erpl_mc_surrogate: pinned copies of what its launches hand back - the population counters and the sums of the residual passes
+struct SurHost {
+  unsigned long long counter[4];
+  double out[ERPL_SUR_MAX_ROWS][4];
+};
+
 // erpl_mc_compare: pinned copies of what its launches hand back - per side the population counters and the moments and order
 // statistics of the requested rows (summary rows, `extra`)
 struct CmpHost {
@@ -220,6 +226,15 @@ struct erpl_ctx {
   // the block of `corr`, its row moments on that of `ana`
   ErplStatUnit<void, CmpHost> cmp;
   ErplStatUnit<void, char> cmp_pop;
+  // erpl_mc_surrogate: the sums of its residual passes in the fixed block, the pieces of erpl_stat_layout.h in the buffer; its
+  // population pass runs on the block of `corr`.  erpl_mc_surrogate_predict: the model it evaluates, nothing else
+  ErplStatUnit<ErplSurWork, SurHost> sur;
+  ErplStatUnit<void, char> sur_model;
+  // the model on its way up: pinned, so that the copy of erpl_mc_surrogate_predict is asynchronous, and the event behind the
+  // latest copy out of it (the next call waits for that copy alone before it writes the staging again)
+  char* sur_pin = nullptr;
+  size_t sur_pin_cap = 0;
+  hipEvent_t sur_ev = nullptr;
   // erpl_mc_legacy_random_streams_device / _wind_profiles_device: one device buffer (flag, op tables, knot constants, the
   // MT19937 states of a tile and two sets of its accepted pairs) and its pinned staging (the tables on their way up, r2
   // down and f up, per set), both bounded by the tile; an event per set behind the tile's copy to the host

@@ -1,7 +1,7 @@
 // erpl_stat_layout.h — how erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density, erpl_mc_sobol,
-// erpl_mc_dependence and erpl_mc_compare cut the device buffer each of them grows into pieces: pure functions of the call's
-// sizes (no HIP; the scratch size of the rocPRIM calls comes in as a number), so that tests/test_stat_layout.py,
-// tests/test_dependence_layout.py and tests/test_compare_layout.py check every offset on the CPU, through
+// erpl_mc_dependence, erpl_mc_compare and erpl_mc_surrogate cut the device buffer each of them grows into pieces: pure functions
+// of the call's sizes (no HIP; the scratch size of the rocPRIM calls comes in as a number), so that tests/test_stat_layout.py,
+// tests/test_dependence_layout.py, tests/test_compare_layout.py and tests/test_surrogate_abi.py check every offset on the CPU, through
 // erpl_stat_layout_table, before a kernel writes through one.  Every piece starts at a multiple of 256 bytes; `need` is the
 // end of the last one.
 #pragma once
@@ -139,6 +139,45 @@ inline ErplDepLayout erpl_dep_layout(int64_t n, int F, int R, int M, int H, int 
   l.cstat = c.take(8 * 6 * pairs * (size_t)M);
   l.tab = c.take(8 * pairs * (size_t)M * (size_t)H);
   l.null = c.take(8 * 4 * pairs * (size_t)P);
+  l.need = c.end;
+  return l;
+}
+
+// erpl_mc_surrogate over n samples, V variables, R rows, P terms (cols = P + R): [pop n bytes][src n u32][count][scratch of the
+// select][model: the four tables, 32 kind bytes, P terms of 8 bytes, R P coefficients][psi cols rows of ld doubles, ld = the
+// members of a chunk: min(ERPL_SUR_CHUNK, n) rounded up to ERPL_SUR_KT][part slices pairs tiles of 128 x 128 doubles, slices =
+// erpl_sur_max_slices(ld, P): the most that ANY chunk of at most ld members is cut into][gram cols cols doubles][yhat R rows
+// of n doubles].
+// erpl_mc_surrogate_predict needs the model piece alone: erpl_sur_model_bytes.
+struct ErplSurLayout {
+  size_t pop, src, count, temp, model, psi, part, gram, yhat, temp_bytes, need;
+  size_t m_kinds, m_terms, m_coef, model_bytes;   // within the model piece (the tables at 0)
+  int64_t ld;
+  int slices;
+};
+inline void erpl_sur_model_pieces(int R, int P, ErplSurLayout* l) {
+  l->m_kinds = 4 * 8 * (ERPL_SUR_MAX_DEGREE + 1);
+  l->m_terms = l->m_kinds + ERPL_SUR_MAX_VARS;
+  l->m_coef = l->m_terms + 8 * (size_t)P;
+  l->model_bytes = l->m_coef + 8 * (size_t)R * (size_t)P;
+}
+inline ErplSurLayout erpl_sur_layout(int64_t n, int R, int P, size_t temp_bytes) {
+  const size_t un = (size_t)n, cols = (size_t)(P + R);
+  ErplCarve c;
+  ErplSurLayout l = {};
+  erpl_sur_model_pieces(R, P, &l);
+  l.ld = ((n < ERPL_SUR_CHUNK ? n : ERPL_SUR_CHUNK) + ERPL_SUR_KT - 1) / ERPL_SUR_KT * ERPL_SUR_KT;
+  l.slices = erpl_sur_max_slices(l.ld, P);
+  l.pop = c.take(un);
+  l.src = c.take(4 * un);
+  l.count = c.take(8);
+  l.temp_bytes = erpl_scratch_piece(temp_bytes);
+  l.temp = c.take(l.temp_bytes);
+  l.model = c.take(l.model_bytes);
+  l.psi = c.take(8 * cols * (size_t)l.ld);
+  l.part = c.take(8 * (size_t)l.slices * (size_t)erpl_sur_pairs((int)cols) * ERPL_SUR_TILE * ERPL_SUR_TILE);
+  l.gram = c.take(8 * cols * cols);
+  l.yhat = c.take(8 * un * (size_t)R);
   l.need = c.end;
   return l;
 }

@@ -12,6 +12,12 @@
 //                                                                           val[R] xy keys idx temp sidx[R] r2e[R] thr bits cnt part
 //                                                                           rank at_value epart eout temp_bytes words wb chunks
 //                                                                           slices need
+//   sur <n> <R> <P> <temp_bytes>                                         -> pop src count temp model psi part gram yhat temp_bytes
+//                                                                           m_kinds m_terms m_coef model_bytes ld slices need
+//   surslices <lo> <hi> <P>                                              -> the most slices erpl_sur_slices cuts a chunk of lo .. hi
+//                                                                           members into (-1: a chunk its slices do not cover), the
+//                                                                           first length that has them, erpl_sur_max_slices(hi, P)
+//   surslice <len> <P>                                                   -> slices slice_len of one chunk
 #include <stdio.h>
 
 #include <initializer_list>
@@ -66,6 +72,26 @@ int main() {
       for (size_t v : {l.thr, l.bits, l.cnt, l.part, l.rank, l.at_value, l.epart, l.eout, l.temp_bytes}) put(v);
       for (int v : {l.words, l.wb, l.chunks, l.slices}) put((size_t)v);
       put(l.need, "\n");
+    } else if (sscanf(line, "sur %lld %d %d %zu", &n, &a, &b, &temp) == 4 && a >= 1 && a <= ERPL_SUR_MAX_ROWS) {
+      const ErplSurLayout l = erpl_sur_layout(n, a, b, temp);
+      for (size_t v : {l.pop, l.src, l.count, l.temp, l.model, l.psi, l.part, l.gram, l.yhat, l.temp_bytes, l.m_kinds, l.m_terms, l.m_coef,
+                       l.model_bytes, (size_t)l.ld, (size_t)l.slices})
+        put(v);
+      put(l.need, "\n");
+    } else if (sscanf(line, "surslices %lld %lld %d", &n, &nodes, &a) == 3 && n >= 1 && nodes >= n) {
+      // every chunk length from <lo> to <hi>: the most slices any of them is cut into, and the first length that has them
+      int most = 0, len = 0;
+      long long at = n;
+      for (long long k = n; k <= nodes; ++k) {
+        const int s = erpl_sur_slices(k, a, &len);
+        if (s > most) { most = s; at = k; }
+        if ((long long)s * len < k || len % ERPL_SUR_KT != 0) { most = -1; at = k; break; }   // the slices do not cover the chunk
+      }
+      printf("%d %lld %d\n", most, at, erpl_sur_max_slices(nodes, a));
+    } else if (sscanf(line, "surslice %lld %d", &n, &a) == 2 && n >= 1) {
+      int len = 0;
+      const int s = erpl_sur_slices(n, a, &len);
+      printf("%d %d\n", s, len);
     } else {
       fprintf(stderr, "bad request: %s", line);
       return 1;

@@ -619,3 +619,45 @@ extern "C++" {
 int erpl_launch_cmp_prepare(const ErplCmpArgs& a, void* stream);           // src, var -> val, xy, sidx, r2e, thr
 int erpl_launch_cmp_block(const ErplCmpArgs& a, int w0, int wl, void* stream);   // the words w0 .. w0 + wl - 1 -> rank, at_value, eout
 }
+
+// ---- erpl_mc_surrogate (erpl_surrogate.hip) ----
+// The fitted members go through the passes ERPL_SUR_CHUNK at a time: Psi of a chunk is materialised as cols = P + n_rows rows
+// (the terms, then the requested outcomes) of `ld` members, and A A^T of that matrix is summed per 128 x 128 tile of its
+// upper triangle (pairs = tiles (tiles + 1) / 2) and per slice of the chunk's members.  The slices of a chunk and their
+// length are functions of the chunk's length and of P alone (not of n_rows: the tiles are counted as if every row were
+// requested); so is the order in which erpl_sur_fold adds the partials, and with it every bit of G and b.
+#define ERPL_SUR_CHUNK 32768            // fitted members per chunk
+#define ERPL_SUR_TILE 128               // rows / columns of an output tile: four waves with a 64 x 64 quarter each
+#define ERPL_SUR_KT 16                  // members per LDS stage of the Gram kernel
+#define ERPL_SUR_TARGET_BLOCKS 512      // a chunk is cut into slices until the Gram launch has about this many workgroups
+#define ERPL_SUR_MIN_SLICE 256          // members a slice has at the least
+#define ERPL_SUR_U_BYTES 65536          // LDS of the univariate values of a workgroup's samples (basis, predict)
+inline int erpl_sur_tiles(int cols) { return (cols + ERPL_SUR_TILE - 1) / ERPL_SUR_TILE; }
+inline int erpl_sur_pairs(int cols) { return erpl_sur_tiles(cols) * (erpl_sur_tiles(cols) + 1) / 2; }
+// The most slices a chunk of at most `len` members of a P-term fit is cut into: what the partial tiles are sized by.  It
+// grows with len, and erpl_sur_slices never returns more (its slice length is at least len over this number); the number
+// of slices itself is NOT monotone in len - the rounding of the slice length to ERPL_SUR_KT can save slices of a longer chunk.
+inline int erpl_sur_max_slices(int64_t len, int P) {
+  int64_t s = ERPL_SUR_TARGET_BLOCKS / erpl_sur_pairs(P + ERPL_SUR_MAX_ROWS), most = (len + ERPL_SUR_MIN_SLICE - 1) / ERPL_SUR_MIN_SLICE;
+  if (s > most) s = most;
+  return (int)(s < 1 ? 1 : s);
+}
+// slices of a chunk of `len` members; *slice_len: members per slice, a multiple of ERPL_SUR_KT
+inline int erpl_sur_slices(int64_t len, int P, int* slice_len) {
+  const int64_t s = erpl_sur_max_slices(len, P);
+  const int64_t per = ((len + s - 1) / s + ERPL_SUR_KT - 1) / ERPL_SUR_KT * ERPL_SUR_KT;
+  *slice_len = (int)per;
+  return (int)((len + per - 1) / per);
+}
+// samples (= threads) per workgroup of the basis and predict kernels: the largest power of two whose univariate values
+// (n_vars degree doubles per sample) fit ERPL_SUR_U_BYTES, at most 256 and at least 16 (32 x 12 doubles: 21 samples fit)
+inline int erpl_sur_group(int n_vars, int degree) {
+  int t = 256;
+  while (t > 16 && (size_t)t * (size_t)n_vars * (size_t)degree * 8 > ERPL_SUR_U_BYTES) t >>= 1;
+  return t;
+}
+struct ErplSurWork {
+  double part[ERPL_SUR_MAX_ROWS][4][ERPL_ANA_MAX_BLOCKS];   // the sums of a residual pass: partials per row, sum and workgroup
+  double mean[ERPL_SUR_MAX_ROWS][2];                        // of the fitted / the held-out members
+  double out[ERPL_SUR_MAX_ROWS][4];                         // tss_fit, rss_fit, tss_val, rss_val
+};

@@ -942,6 +942,93 @@ class TrajectoryEngine:
             out["null_values"] = null
         return out
 
+    def surrogate(self, factors, kinds, summary, mask=None, rows=None, extra=None, degree=2, order=2, holdout=0, want_gram=False):
+        """A polynomial chaos surrogate of ONE run of independent primitives (erpl_mc_surrogate), no extra flights: the
+        least-squares fit of orthonormal Hermite / Legendre polynomials of the rows of `factors` (float64 [V, n] on the
+        device, V <= 32; `kinds`: _abi.DESIGN_UNIFORM for a U(0, 1) row, _abi.DESIGN_NORMAL for an N(0, 1) row, as
+        `design` draws them) to up to 4 rows (summary rows, or _abi.SUR_ROW_EXTRA for the float64 [n] device tensor
+        `extra`; default apogee, range, flight time), over ONE population: mask byte 0 and every variable and requested row
+        finite.  Terms: total degree <= `degree` (1..12), at most `order` (1..4) variables each, at most 1024 of them.
+        holdout = k >= 2 keeps every k-th member out of the fit and validates on it (q2); 0 fits every member.
+        Returns a dict: n, count, n_masked, n_non_finite, n_fit, n_val, rows, n_vars, degree, order, holdout, n_terms,
+        pivot_min / pivot_max, fit_ok, mean, variance_pce, tss_fit, rss_fit, r2, tss_val, rss_val, q2 ([R]), first / total
+        ([R, V]), pair ([R, V, V]: the second-order index of {i, j}), and 'model' = {kinds, degree, order, terms ([P, 4, 2]
+        int8), coefficients ([R, P]), rows} for `surrogate_predict`.  want_gram adds 'gram' ([P, P]) and 'rhs' ([R, P]).
+        The indices are shares of the EXPLAINED variance; r2 is the share the variables explain at all.  Where the fit
+        fails (fewer fitted members than terms, a pivot that is not positive) fit_ok is False and what depends on the
+        coefficients is NaN."""
+        n, mask_p = self._summary_and_mask(summary, mask)
+        if not (torch.is_tensor(factors) and factors.is_cuda and factors.device == self.device and factors.dtype == torch.float64
+                and factors.dim() == 2 and factors.shape[1] == n and factors.is_contiguous()):
+            raise ValueError(f"factors must be a contiguous float64 [V, n] tensor on {self.device}")
+        V = int(factors.shape[0])
+        if not 1 <= V <= _abi.SUR_MAX_VARS:
+            raise ValueError(f"1 to {_abi.SUR_MAX_VARS} variables")
+        kinds = bytes(bytearray(int(k) for k in kinds))
+        if len(kinds) != V:
+            raise ValueError(f"kinds must have one entry per row of factors ({V})")
+        if extra is not None and not (extra.is_cuda and extra.device == self.device and extra.dtype == torch.float64
+                                      and tuple(extra.shape) == (n,) and extra.is_contiguous()):
+            raise ValueError(f"extra must be a contiguous float64 [n] tensor on {self.device}")
+        spec = self._defaults(_abi.ErplSurSpec, "erpl_mc_surrogate_defaults")
+        self._set_rows(spec, rows, 1, _abi.SUR_MAX_ROWS)
+        spec.n_vars, spec.degree, spec.order, spec.holdout = V, int(degree), int(order), int(holdout)
+        P = C.c_int32(0)
+        _abi.check(self.lib, self.lib.erpl_mc_surrogate_terms(V, spec.degree, spec.order, C.byref(P), None), "erpl_mc_surrogate_terms")
+        P, R = int(P.value), spec.n_rows
+        coef = np.empty((R, P), dtype=np.float64)
+        terms = np.empty((P, 4, 2), dtype=np.int8)
+        pair = np.empty((R, V, V), dtype=np.float64)
+        gram = np.empty((P, P), dtype=np.float64) if want_gram else None
+        rhs = np.empty((R, P), dtype=np.float64) if want_gram else None
+        res = _abi.ErplSurrogate()
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_surrogate", C.c_void_p(factors.data_ptr()), kinds, C.c_void_p(summary.data_ptr()),
+                   C.c_void_p(extra.data_ptr()) if extra is not None else None, mask_p, n, C.byref(spec), C.byref(res),
+                   C.c_void_p(coef.ctypes.data), C.c_void_p(terms.ctypes.data),
+                   C.c_void_p(gram.ctypes.data) if want_gram else None, C.c_void_p(rhs.ctypes.data) if want_gram else None,
+                   C.c_void_p(pair.ctypes.data), C.c_void_p(st.cuda_stream))
+        out = {k: int(getattr(res, k)) for k in ("n", "count", "n_masked", "n_non_finite", "n_fit", "n_val", "n_vars", "degree",
+                                                 "order", "holdout", "n_terms")}
+        out["rows"] = list(spec.rows[:R])
+        out["pivot_min"], out["pivot_max"] = res.pivot_min, res.pivot_max
+        out["fit_ok"] = np.array([bool(res.row[j].fit_ok) for j in range(R)])
+        for key in ("mean", "variance_pce", "tss_fit", "rss_fit", "r2", "tss_val", "rss_val", "q2"):
+            out[key] = np.array([getattr(res.row[j], key) for j in range(R)], dtype=np.float64)
+        out["first"] = np.array([list(res.row[j].first[:V]) for j in range(R)], dtype=np.float64)
+        out["total"] = np.array([list(res.row[j].total[:V]) for j in range(R)], dtype=np.float64)
+        out["pair"] = pair
+        out["model"] = {"kinds": kinds, "degree": spec.degree, "order": spec.order, "terms": terms, "coefficients": coef,
+                        "rows": out["rows"]}
+        if want_gram:
+            out["gram"], out["rhs"] = gram, rhs
+        return out
+
+    def surrogate_predict(self, model, X, out=None, n=None):
+        """The fitted outcomes of `model` (the 'model' of `surrogate`) at the columns 0 .. n - 1 (default: all) of X, a
+        float64 [V, ld] device tensor with unit column stride, without a flight (erpl_mc_surrogate_predict): a float64
+        [R, ld] device tensor (`out`, or a new one; with n < ld the columns from n on are left as they are), one row per
+        row of the model.  A point with a non-finite input gives NaN.  Asynchronous on the current stream."""
+        kinds = bytes(model["kinds"])
+        coef = np.ascontiguousarray(model["coefficients"], dtype=np.float64)
+        V, R = len(kinds), int(coef.shape[0])
+        if not (torch.is_tensor(X) and X.is_cuda and X.device == self.device and X.dtype == torch.float64 and X.dim() == 2
+                and X.shape[0] == V and X.is_contiguous()):
+            raise ValueError(f"X must be a contiguous float64 [{V}, ld] tensor on {self.device}")
+        ld = int(X.shape[1])
+        n = ld if n is None else int(n)
+        if out is None:
+            out = torch.empty((R, ld), dtype=torch.float64, device=self.device)
+        if not (torch.is_tensor(out) and out.is_cuda and out.device == self.device and out.dtype == torch.float64
+                and tuple(out.shape) == (R, ld) and out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float64 [{R}, {ld}] tensor on {self.device}")
+        spec = self._defaults(_abi.ErplSurSpec, "erpl_mc_surrogate_defaults")
+        spec.n_vars, spec.n_rows, spec.degree, spec.order = V, R, int(model["degree"]), int(model["order"])
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_surrogate_predict", C.byref(spec), kinds, C.c_void_p(coef.ctypes.data), C.c_void_p(X.data_ptr()), ld, n,
+                   C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream))
+        return out
+
     def compare(self, summary_a, summary_b, mask_a=None, mask_b=None, rows=None, extra_a=None, extra_b=None,
                 quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), xy=(_abi.SUM_IMPACT_X, _abi.SUM_IMPACT_Y), permutations=999, level=0.95,
                 seed=0, keep_null=False, knots=512):

@@ -798,6 +798,49 @@ class MonteCarloAnalyzer:
         `top` factors, saved as monte_carlo_given_data.png in the output directory; returns that directory."""
         return plots.plot_given_data_sensitivity(self, sensitivity, save_plots, top)
 
+    def surrogate(self, analysis, variables=None, rows=None, degree=2, order=2, holdout=5):
+        """A polynomial chaos surrogate of a run flown with `run_monte_carlo_device(design=...)` (no reference counterpart,
+        no extra flights): `analysis.polynomial_chaos` - first-order, total and pair Sobol indices, r2 / q2 and a model for
+        `TrajectoryEngine.surrogate_predict` - of the chosen primitives on up to 4 summary rows.  Only the chosen primitive
+        rows are regenerated, from analysis["design"] through `TrajectoryEngine.design(first_row=...)`: the bits the run flew.
+        variables: None (`sampling.scalar_primitives`: every scalar primitive, without the turbulence innovations and the
+        dead draw) or a mapping name -> primitive row, at most 32.  ValueError for a run without `design`: under the
+        reference's joint law the inputs are not independent (one normal is the thrust multiplier, position_x and the first
+        turbulence innovation at once), and the basis is orthonormal only under independent inputs with known laws."""
+        from . import analysis as ana, sampling
+        from .flatten import motor_kind
+        if "design" not in analysis:
+            raise ValueError("surrogate needs a run flown with run_monte_carlo_device(design=...): the inputs of the joint law are "
+                             "not independent, and a polynomial chaos basis is orthonormal only under independent inputs")
+        if dist.world()[1] > 1:
+            raise ValueError("surrogate is limited to a world size of 1")
+        eng = shared_engine(self.device)
+        use_base = self.base_wind_profile is not None and self.base_altitude_profile is not None
+        K = len(self.base_altitude_profile) if use_base else 100      # as run_monte_carlo_device drew the design
+        if variables is None:
+            variables = sampling.scalar_primitives(K, motor_kind(self.motor) != _abi.MOTOR_SOLID)
+        names, prim = [str(k) for k in variables], [int(r) for r in dict(variables).values()]
+        n_prim = sampling.primitive_rows(K)
+        if not 1 <= len(prim) <= _abi.SUR_MAX_VARS or len(set(prim)) != len(prim) or not all(0 <= r < n_prim for r in prim):
+            raise ValueError(f"variables: 1 to {_abi.SUR_MAX_VARS} distinct primitive rows in 0..{n_prim - 1}")
+        d = analysis["design"]
+        summ = analysis["summary"]
+        n = int(summ.shape[1])
+        kinds = [_abi.DESIGN_NORMAL if r < 17 + 3 * K else _abi.DESIGN_UNIFORM for r in prim]
+        factors = torch.empty((len(prim), n), dtype=torch.float64, device=eng.device)
+        for i, r in enumerate(prim):
+            eng.design([kinds[i]], n, d["seed"], kind=d["kind"], block=d["block"], first_row=r, out=factors[i:i + 1])
+        out = ana.polynomial_chaos(summ, factors, kinds, names, status=analysis.get("status"), engine=eng, rows=rows, degree=degree,
+                                   order=order, holdout=holdout)
+        out["factors"], out["primitive_rows"] = factors, prim
+        return out
+
+    def plot_surrogate(self, surrogate, save_plots=True):
+        """No reference counterpart: per row the first-order and total indices of the variables, the largest pair indices
+        and predicted against flown on the held-out members, saved as monte_carlo_surrogate.png in the output directory;
+        returns that directory."""
+        return plots.plot_surrogate(self, surrogate, save_plots)
+
     def compare_runs(self, analysis_a, analysis_b, **kw):
         """Did two runs come from the same law (no reference counterpart)?  `analysis.compare_runs` - per row the
         Kolmogorov-Smirnov, Mann-Whitney and Cramer-von Mises tests with the shift function, the energy test of the two

@@ -356,6 +356,53 @@ def sobol_figure(result):
     return fig
 
 
+def surrogate_figure(result, top=8):
+    """The dict of analysis.polynomial_chaos: per row three panels - the first-order and total indices of the variables as
+    paired bars in the order of `names`, the `top` largest pair indices as horizontal bars, and predicted against flown on
+    the held-out members (result['validation'], where there is one) with the diagonal.  A NaN index draws no bar."""
+    names = list(result["names"])
+    rows = list(result["row_names"])
+    V = len(names)
+    fig = _figure((max(11.0, 0.45 * V + 8.0), 3.2 * len(rows) + 0.8))
+    axes = np.atleast_2d(fig.subplots(len(rows), 3, gridspec_kw={"width_ratios": [2.2, 1.3, 1.0]}))
+    x = np.arange(V, dtype=np.float64)
+    val = result.get("validation")
+    for j, row in enumerate(rows):
+        ax = axes[j, 0]
+        for which, label, shift, color in (("first", "first order", -0.2, "tab:blue"), ("total", "total", 0.2, "tab:orange")):
+            ax.bar(x + shift, np.nan_to_num(np.asarray(result[which], dtype=np.float64)[j], nan=0.0), width=0.4, color=color, label=label)
+        r2, q2 = float(np.asarray(result["r2"])[j]), float(np.asarray(result["q2"])[j])
+        ax.set_title(f"{row}: r2 = {r2:.4f}, q2 = {q2:.4f} ({int(result['n_fit'])} fitted, {int(result['n_val'])} held out)", fontsize=9)
+        ax.set_ylabel("share of the explained variance")
+        ax.set_xticks(x)
+        ax.set_xticklabels(names, rotation=45, ha="right", fontsize=7)
+        ax.grid(True, axis="y", alpha=0.3)
+        if j == 0:
+            ax.legend(loc="best", fontsize=8)
+        ax = axes[j, 1]
+        pairs = list(result["interactions"][j])[:top]
+        ax.barh(np.arange(len(pairs)), [p[2] for p in pairs], color="tab:green")
+        ax.set_yticks(np.arange(len(pairs)))
+        ax.set_yticklabels([f"{a} x {b}" for a, b, _ in pairs], fontsize=7)
+        ax.invert_yaxis()
+        ax.set_title("largest pair indices", fontsize=9)
+        ax.grid(True, axis="x", alpha=0.3)
+        ax = axes[j, 2]
+        if val is not None and np.asarray(val["flown"]).shape[1] > 0:
+            flown, pred = np.asarray(val["flown"], dtype=np.float64)[j], np.asarray(val["predicted"], dtype=np.float64)[j]
+            ax.plot(flown, pred, ".", markersize=2, alpha=0.5)
+            ends = [float(np.nanmin(flown)), float(np.nanmax(flown))]
+            ax.plot(ends, ends, color="black", linewidth=0.8)
+            ax.set_xlabel("flown")
+            ax.set_ylabel("predicted")
+            ax.set_title("held-out members", fontsize=9)
+        else:
+            ax.set_axis_off()
+    fig.suptitle(f"Polynomial chaos surrogate: degree {int(result['degree'])}, order {int(result['order'])}, {int(result['n_terms'])} terms")
+    fig.tight_layout()
+    return fig
+
+
 def given_data_figure(result, top=4):
     """The dict of analysis.given_data_sensitivity: per row two panels.  Left: delta of every factor as a bar, in the order
     of `factor_names`, with the null band - a tick at null_mean and a line up to null_hi - where there are shifts; a bar
@@ -693,6 +740,17 @@ def plot_sobol(analyzer, sobol, save_plots=True):
     if save_plots:
         output_dir = analyzer._create_output_directory()
         print(f"Sobol indices plot saved to: {save_figure(fig, output_dir, 'monte_carlo_sobol.png')}")
+    return output_dir
+
+
+def plot_surrogate(analyzer, surrogate, save_plots=True):
+    """The surrogate of MonteCarloAnalyzer.surrogate (no reference counterpart) as monte_carlo_surrogate.png; returns the
+    output directory (None without save_plots)."""
+    fig = surrogate_figure(surrogate)
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Surrogate plot saved to: {save_figure(fig, output_dir, 'monte_carlo_surrogate.png')}")
     return output_dir
 
 

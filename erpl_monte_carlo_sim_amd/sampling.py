@@ -105,6 +105,19 @@ def primitive_groups(K, liquid=True):
     return groups
 
 
+def scalar_primitives(K, liquid=True):
+    """The default variables of a polynomial chaos surrogate: an ordered mapping name -> row of the primitive tensor for the
+    scalar primitives of `primitive_groups` - every group but the 3 K turbulence innovations and the dead draw - a
+    three-row group as name_x, name_y, name_z."""
+    out = {}
+    for name, rows in primitive_groups(K, liquid).items():
+        if name in ("turbulence", "dead_draw"):
+            continue
+        for i, r in enumerate(rows):
+            out[name if len(rows) == 1 else f"{name}_{'xyz'[i]}"] = r
+    return out
+
+
 def check_groups(groups, n_rows):
     """`groups` as a list of (name, rows): at most 32, each non-empty, rows inside the primitive tensor, none shared."""
     items = [(str(name), [int(r) for r in rows]) for name, rows in dict(groups).items()]

@@ -1328,6 +1328,120 @@ int erpl_mc_compare(erpl_ctx* ctx, const double* summary_a, const uint8_t* mask_
  * outside 0..2^32 - 1. */
 int erpl_mc_compare_labels(uint64_t seed, int64_t permutation, int64_t m_a, int64_t m_b, uint8_t* out);
 
+/* A polynomial chaos surrogate of ONE run whose inputs are independent primitives with known laws - the rows of
+ * erpl_mc_design: a least-squares fit of orthonormal Hermite / Legendre polynomials of the inputs to up to 4 outcomes, ON
+ * THE DEVICE.  From the run that was flown anyway it gives the first-order, total AND second-order (pair) Sobol indices,
+ * without the (k + 2) N flights of erpl_mc_sobol, and an emulator that evaluates the fitted outcome at new input points
+ * without a flight, next to its validation error on held-out members.  The reference has nothing like it.
+ *
+ * Variables: `factors` [n_vars][n] is fp64 DEVICE memory, n_vars 1..32; `kinds` [n_vars] is HOST bytes: ERPL_DESIGN_UNIFORM
+ * (law U(0, 1)) or ERPL_DESIGN_NORMAL (law N(0, 1)).  `summary` [ERPL_SUMMARY_DIM][n], `extra` [n] (NULL unless a row is
+ * ERPL_SUR_ROW_EXTRA) and `mask` [n] (NULL: every sample counts) are device memory; spec, result and every output of
+ * erpl_mc_surrogate are HOST memory.
+ * Univariate basis, degree 0..p, p = spec->degree in 1..12, orthonormal under the variable's law and built only from *, -
+ * and four tables made on the host at call time, so that host and device give the same bits (no FMA contraction):
+ *   uniform  x = 2u - 1; P_0 = 1, P_1 = x, P_{k+1} = ((a_k x) P_k) - (b_k P_{k-1}), a_k = (2k+1)/(k+1), b_k = k/(k+1), each
+ *            rounded once; psi_k = s_k P_k, s_k = sqrt(2k+1)
+ *   normal   He_0 = 1, He_1 = z, He_{k+1} = (z He_k) - ((double)k He_{k-1}); psi_k = h_k He_k, h_k = 1.0 / sqrt((double)k!)
+ * Terms: every multi-index alpha with |alpha|_1 <= degree and at most spec->order (1..4) non-zero entries, in ONE order:
+ * total degree ascending; within a degree the number of variables ascending; within that the variable tuple in
+ * lexicographic order; within that the degree tuple in lexicographic order.  Term 0 is the constant.  Their number is
+ * P = 1 + sum_{g=1..p} sum_{o=1..min(order,g,n_vars)} C(n_vars,o) C(g-1,o-1) <= ERPL_SUR_MAX_TERMS: (n_vars, degree, order) =
+ * (32, 2, 2) gives 561, (25, 3, 2) gives 976, (11, 4, 3) gives 1035, which is refused.  A term's value Psi_alpha is the
+ * product of its psi factors in ascending variable order, starting from the first factor (no leading 1.0 *).
+ * `terms` is int8 [P][4][2] = (variable, degree) of every factor, unused slots (-1, 0).
+ * Population: ONE, by listwise deletion as in erpl_mc_dependence - mask byte 0 AND every variable finite AND every requested
+ * row finite - in ascending sample order, dense index d; count + n_masked + n_non_finite == n.  spec->holdout = 0: every
+ * member is fitted; holdout = k in 2..2^20: member d is held out iff d mod k == k - 1.  n_fit and n_val count the two.
+ * Fit: ordinary least squares through the normal equations.  G = sum psi psi^T (P x P) and b_j = sum psi y_j over the
+ * fitted members come from the device: Psi is materialised 32768 fitted members at a time, every 128 x 128 tile of the
+ * upper triangle is summed by its own workgroups over slices of the chunk, each in ascending member order, and the
+ * partial sums are added in slice order, chunk after chunk.  The slices, and with them the order of every
+ * sum and the bits of G and b, are functions of (n_fit, P) alone: a row fitted alone and among four gives the same b.  (The
+ * requested rows ride along as n_rows extra rows of the product, so the number of tiles, and the grid, depends on n_rows
+ * too; the slices are cut as if four rows were requested.)  There are no floating-point atomics, and two calls return the
+ * same bytes.  (These sums use fused multiply-adds - the
+ * fp64 matrix instruction of gfx950: G and b are held to a bound, not to the bits of a host formula.)  The Cholesky factorisation of G and the two triangular solves
+ * run on the host in the library.  fit_ok = 1 iff n_fit >= P and every pivot (the squared diagonal of the factor) is finite
+ * and > 0; otherwise the coefficients and everything derived from them are NaN and the call is still ERPL_OK.  pivot_min and
+ * pivot_max are the smallest and largest pivot (NaN when n_fit == 0).
+ * Residuals: the device evaluates the fitted polynomial at every member as erpl_mc_surrogate_predict does and forms, in
+ * the fixed order of the other analysis calls, tss_fit = sum (y - mean_fit)^2 and rss_fit = sum (y - yhat)^2 over the
+ * fitted members, r2 = 1 - rss_fit / tss_fit, and the same over the held-out members around THEIR mean: tss_val, rss_val,
+ * q2.  A zero tss gives NaN; holdout = 0 gives NaN for the three and n_val = 0.
+ * From the coefficients, on the host in ascending term index: mean = c_0; variance_pce = sum_{alpha != 0} c_alpha^2;
+ * first[i] = the sum over the terms whose only variable is i, divided by variance_pce; total[i] = the sum over the terms
+ * that contain i, divided by variance_pce; pair_out [n_rows][n_vars][n_vars] (optional) = the sum over the terms whose
+ * variables are exactly {i, j}, divided by variance_pce, at [i][j] and [j][i], zero on the diagonal.  variance_pce == 0:
+ * every index NaN, the diagonal of pair_out included (as after a fit that failed).  THE INDICES ARE SHARES OF THE EXPLAINED VARIANCE: with inputs that are not among the variables (the turbulence
+ * rows of a flight) r2 is the share the variables explain at all.
+ * Outputs: coefficients [n_rows][P]; optional terms (above), gram_out [P][P] (symmetric, both sides filled), rhs_out
+ * [n_rows][P] and pair_out.  The work is enqueued on `hip_stream` behind what is there and the call returns when the result
+ * is filled; the workspace belongs to the context, grows only (about 5 n bytes and the select's scratch, 262144 (P + n_rows)
+ * bytes of Psi, at most 64 MiB of partial sums, 8 (P + n_rows)^2 bytes of sums and 8 n n_rows bytes of fitted values) and is
+ * freed by erpl_mc_destroy.
+ *
+ * erpl_mc_surrogate_predict evaluates a model - spec (n_vars, n_rows, degree, order; rows and holdout are not looked at),
+ * kinds and coefficients [n_rows][P], all host memory - at the columns 0..n-1 of X [n_vars][ld] into out [n_rows][ld], both
+ * device memory: acc starts at c_0, then acc = acc + (c_alpha Psi_alpha) in ascending term index; a sample with a
+ * non-finite input gives NaN; columns from n on are left as they are.  It enqueues on `hip_stream` and returns without
+ * waiting, as erpl_mc_design does; the model travels through a buffer of the context, so calls of one context go to one
+ * stream or are separated by a synchronisation.  erpl_mc_surrogate_predict_host runs the same code into host memory
+ * (X and out host memory, no context) and returns the same bits.  erpl_mc_surrogate_terms (host only, no context) gives
+ * P in *n_terms and, unless `terms` is NULL, the terms.
+ *
+ * Errors: ERPL_ERR_INVALID, before any device work and with a message that names the argument, in this order.
+ * erpl_mc_surrogate: a NULL spec, factors, kinds, summary, result or coefficients; n <= 0 or n >= 2^31; n_vars outside
+ * 1..32; n_rows outside 1..4; degree outside 1..12; order outside 1..4; holdout neither 0 nor in 2..2^20; a kind byte that
+ * is neither constant; a row outside 0..16 or listed twice; row 16 without `extra`; P > ERPL_SUR_MAX_TERMS; the context last.
+ * erpl_mc_surrogate_predict and _predict_host: a NULL spec, kinds, coefficients, X or out; n <= 0 or n >= 2^31; n_vars,
+ * n_rows, degree, order as above; a kind byte; P > ERPL_SUR_MAX_TERMS; ld < n; the context last.
+ * erpl_mc_surrogate_terms: a NULL n_terms; n_vars, degree, order as above; P > ERPL_SUR_MAX_TERMS. */
+#define ERPL_SUR_MAX_VARS 32
+#define ERPL_SUR_MAX_ROWS 4
+#define ERPL_SUR_ROW_EXTRA 16            /* = ERPL_DEP_ROW_EXTRA: the caller's device row `extra` */
+#define ERPL_SUR_MAX_DEGREE 12
+#define ERPL_SUR_MAX_ORDER 4
+#define ERPL_SUR_MAX_TERMS 1024
+#define ERPL_SUR_MAX_HOLDOUT 1048576
+
+typedef struct erpl_sur_spec {
+  int32_t n_vars;                        /* 1..ERPL_SUR_MAX_VARS */
+  int32_t n_rows;                        /* 1..ERPL_SUR_MAX_ROWS */
+  int32_t rows[ERPL_SUR_MAX_ROWS];       /* distinct; 0..15 = summary rows, ERPL_SUR_ROW_EXTRA = `extra` */
+  int32_t degree;                        /* 1..ERPL_SUR_MAX_DEGREE: the largest total degree of a term */
+  int32_t order;                         /* 1..ERPL_SUR_MAX_ORDER: the most variables a term has */
+  int32_t holdout;                       /* 0, or k in 2..ERPL_SUR_MAX_HOLDOUT: every k-th member validates */
+  int32_t reserved;
+} erpl_sur_spec;
+
+typedef struct erpl_sur_row {
+  int32_t fit_ok, reserved;
+  double mean, variance_pce;
+  double tss_fit, rss_fit, r2;
+  double tss_val, rss_val, q2;
+  double first[ERPL_SUR_MAX_VARS], total[ERPL_SUR_MAX_VARS];
+} erpl_sur_row;
+
+typedef struct erpl_surrogate {
+  int64_t n, count, n_masked, n_non_finite;   /* count + n_masked + n_non_finite == n */
+  int64_t n_fit, n_val;                       /* n_fit + n_val == count */
+  int32_t n_vars, n_rows, degree, order, holdout, n_terms;
+  double pivot_min, pivot_max;
+  erpl_sur_row row[ERPL_SUR_MAX_ROWS];        /* of spec->rows[j] */
+} erpl_surrogate;
+
+/* Host only: rows {APOGEE_ALT, RANGE, FLIGHT_TIME}, degree 2, order 2, holdout 0, n_vars = 0 (the caller fills it in). */
+int erpl_mc_surrogate_defaults(erpl_sur_spec* spec);
+int erpl_mc_surrogate_terms(int32_t n_vars, int32_t degree, int32_t order, int32_t* n_terms, int8_t* terms);
+int erpl_mc_surrogate(erpl_ctx* ctx, const double* factors, const uint8_t* kinds, const double* summary, const double* extra,
+                      const uint8_t* mask, int64_t n, const erpl_sur_spec* spec, erpl_surrogate* result, double* coefficients,
+                      int8_t* terms, double* gram_out, double* rhs_out, double* pair_out, void* hip_stream);
+int erpl_mc_surrogate_predict(erpl_ctx* ctx, const erpl_sur_spec* spec, const uint8_t* kinds, const double* coefficients,
+                              const double* X, int64_t ld, int64_t n, double* out, void* hip_stream);
+int erpl_mc_surrogate_predict_host(const erpl_sur_spec* spec, const uint8_t* kinds, const double* coefficients, const double* X,
+                                   int64_t ld, int64_t n, double* out);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
