@@ -419,6 +419,53 @@ class ErplSurrogate(C.Structure):
                 ("pivot_min", C.c_double), ("pivot_max", C.c_double), ("row", ErplSurRow * SUR_MAX_ROWS)]
 
 
+# erpl_mc_tally_*
+TALLY_MAX_ROWS = 8
+TALLY_MAX_BINS = 1024
+TALLY_MAX_THRESHOLDS = 8
+TALLY_MAX_K = 64
+TALLY_MAX_Q = 8
+TALLY_MAX_GRID = 256
+TALLY_MAX_ZONES = 8
+TALLY_MAX_VERTICES = 256
+TALLY_HEADER_WORDS, TALLY_ROW_WORDS, TALLY_GRID_WORDS, TALLY_ACC_WORDS = 16, 12, 10, 70   # the layout of a state
+
+
+class ErplTallySpec(C.Structure):
+    _fields_ = [("max_apogee", C.c_double), ("min_apogee", C.c_double), ("max_range", C.c_double),
+                ("max_flight_time", C.c_double), ("energy_apogee", C.c_double),
+                ("n_rows", C.c_int32), ("rows", C.c_int32 * TALLY_MAX_ROWS), ("bins", C.c_int32 * TALLY_MAX_ROWS),
+                ("n_thresholds", C.c_int32 * TALLY_MAX_ROWS), ("k", C.c_int32), ("n_q", C.c_int32),
+                ("lo", C.c_double * TALLY_MAX_ROWS), ("hi", C.c_double * TALLY_MAX_ROWS), ("centre", C.c_double * TALLY_MAX_ROWS),
+                ("threshold", (C.c_double * TALLY_MAX_THRESHOLDS) * TALLY_MAX_ROWS), ("q", C.c_double * TALLY_MAX_Q),
+                ("row_x", C.c_int32), ("row_y", C.c_int32), ("bins_x", C.c_int32), ("bins_y", C.c_int32),
+                ("lo_x", C.c_double), ("hi_x", C.c_double), ("lo_y", C.c_double), ("hi_y", C.c_double),
+                ("n_zones", C.c_int32), ("zone_first", C.c_int32 * (TALLY_MAX_ZONES + 1)),
+                ("zone_x", C.c_double * TALLY_MAX_VERTICES), ("zone_y", C.c_double * TALLY_MAX_VERTICES)]
+
+
+class ErplTallyExtreme(C.Structure):
+    _fields_ = [("value", C.c_double), ("id", C.c_int64)]
+
+
+class ErplTallyRow(C.Structure):
+    _fields_ = [("count", C.c_int64), ("below", C.c_int64), ("above", C.c_int64), ("moment_skipped", C.c_int64),
+                ("exceed", C.c_int64 * TALLY_MAX_THRESHOLDS),
+                ("sum_d", C.c_double), ("sum_d2", C.c_double), ("mean", C.c_double), ("var", C.c_double), ("std", C.c_double),
+                ("min", C.c_double), ("max", C.c_double),
+                ("quantile", C.c_double * TALLY_MAX_Q), ("quantile_exact", C.c_int32 * TALLY_MAX_Q),
+                ("n_smallest", C.c_int32), ("n_largest", C.c_int32),
+                ("smallest", ErplTallyExtreme * TALLY_MAX_K), ("largest", ErplTallyExtreme * TALLY_MAX_K)]
+
+
+class ErplTally(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_valid", C.c_int64), ("n_outliers", C.c_int64),
+                ("reason_counts", C.c_int64 * 6), ("termination_counts", C.c_int64 * 5),
+                ("n_status_nan", C.c_int64), ("n_incomplete", C.c_int64),
+                ("grid_counted", C.c_int64), ("grid_outside", C.c_int64), ("zone_inside", C.c_int64 * TALLY_MAX_ZONES),
+                ("row", ErplTallyRow * TALLY_MAX_ROWS)]
+
+
 LIB_NAME = "liberpl_mc.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
@@ -448,7 +495,9 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_legacy_random_streams_device", "erpl_mc_legacy_wind_profiles_device",
            "erpl_mc_design_defaults", "erpl_mc_design", "erpl_mc_design_host",
            "erpl_mc_surrogate_defaults", "erpl_mc_surrogate_terms", "erpl_mc_surrogate", "erpl_mc_surrogate_predict",
-           "erpl_mc_surrogate_predict_host")
+           "erpl_mc_surrogate_predict_host",
+           "erpl_mc_tally_defaults", "erpl_mc_tally_words", "erpl_mc_tally_add", "erpl_mc_tally_merge", "erpl_mc_tally_result",
+           "erpl_mc_tally_add_host", "erpl_mc_tally_merge_host", "erpl_mc_tally_result_host")
 
 _lib = None
 
@@ -569,6 +618,16 @@ def load_library(path=None):
                                               C.c_int64, C.c_void_p, C.c_void_p]
     lib.erpl_mc_surrogate_predict_host.argtypes = [C.POINTER(ErplSurSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                                    C.c_void_p]
+    lib.erpl_mc_tally_defaults.argtypes = [C.POINTER(ErplTallySpec)]
+    lib.erpl_mc_tally_words.argtypes = [C.POINTER(ErplTallySpec), C.POINTER(C.c_int64)]
+    lib.erpl_mc_tally_add.argtypes = [C.c_void_p, C.POINTER(ErplTallySpec), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                      C.c_int64, C.c_void_p]
+    lib.erpl_mc_tally_merge.argtypes = [C.c_void_p, C.POINTER(ErplTallySpec), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.erpl_mc_tally_result.argtypes = [C.c_void_p, C.POINTER(ErplTallySpec), C.c_void_p, C.POINTER(ErplTally), C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
+    lib.erpl_mc_tally_add_host.argtypes = [C.POINTER(ErplTallySpec), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64]
+    lib.erpl_mc_tally_merge_host.argtypes = [C.POINTER(ErplTallySpec), C.c_void_p, C.c_void_p]
+    lib.erpl_mc_tally_result_host.argtypes = [C.POINTER(ErplTallySpec), C.c_void_p, C.POINTER(ErplTally), C.c_void_p, C.c_void_p]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if a declared symbol is not exported
         if name not in ("erpl_mc_last_error",):

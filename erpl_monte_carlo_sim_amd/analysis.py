@@ -781,3 +781,223 @@ def finish_comparison(out):
                                  f"(E = {e['statistic']:.6g}, null {100 * out['level']:.0f} % = {e['null_hi']:.6g}, "
                                  f"p = {e['p_value']:.3g})")
     return out
+
+
+# ---------------------------------------------------------------------------------- the tally: a run in bounded memory
+def _row_id(row):
+    """A summary row by its name (ROW_NAMES) or its _abi.SUM_* index."""
+    if isinstance(row, str):
+        if row not in ROW_NAMES:
+            raise ValueError(f"unknown summary row {row!r}: one of {ROW_NAMES}")
+        return ROW_NAMES.index(row)
+    return int(row)
+
+
+def tally_spec(rows=None, ranges=None, bins=None, centres=None, thresholds=None, k=None, quantiles=None, bounds=None,
+               grid_rows=None, grid_bins=None, grid_ranges=None, zones=None):
+    """The spec of a tally (erpl_mc_tally_*; _abi.ErplTallySpec) from keyword arguments, every one of them optional on top of
+    the library's defaults (erpl_mc_tally_defaults: apogee 0..80 km, range 0..200 km, flight time 0..600 s, 1000 bins,
+    k = 16, the impact point on 128 x 128 cells over +-200 km).  A pure host function.
+    rows: up to 8 summary rows by name (ROW_NAMES) or index; with rows given, ranges is required: one (lo, hi) per row
+    (streaming has no range from the data).  bins: one int or one per row; centres: one per row (default mid-range);
+    thresholds: {row: [values]} or one list per row; k: extremes held per row and side (0..64); quantiles: fractions in
+    [0, 1]; bounds: the dict of TrajectoryEngine.analyze; grid_rows: (row_x, row_y); grid_bins: one int or (bins_x, bins_y);
+    grid_ranges: ((lo_x, hi_x), (lo_y, hi_y)); zones: polygons, each an array of (x, y) vertices."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    spec = _abi.ErplTallySpec()
+    _abi.check(lib, lib.erpl_mc_tally_defaults(C.byref(spec)), "erpl_mc_tally_defaults")
+    if rows is not None:
+        rows = [_row_id(r) for r in rows]
+        if len(rows) > _abi.TALLY_MAX_ROWS:
+            raise ValueError(f"at most {_abi.TALLY_MAX_ROWS} rows")
+        if ranges is None or len(ranges) != len(rows):
+            raise ValueError("ranges: one (lo, hi) per row - a tally has no range from the data")
+        spec.n_rows = len(rows)
+        for j, r in enumerate(rows):
+            spec.rows[j], spec.bins[j], spec.n_thresholds[j] = r, 1000, 0
+            spec.lo[j], spec.hi[j] = float(ranges[j][0]), float(ranges[j][1])
+            spec.centre[j] = 0.5 * (spec.lo[j] + spec.hi[j])
+    elif ranges is not None:
+        if len(ranges) != spec.n_rows:
+            raise ValueError("ranges: one (lo, hi) per row")
+        for j, (lo, hi) in enumerate(ranges):
+            spec.lo[j], spec.hi[j] = float(lo), float(hi)
+            spec.centre[j] = 0.5 * (spec.lo[j] + spec.hi[j])
+    m = spec.n_rows
+    if bins is not None:
+        bins = [int(bins)] * m if np.isscalar(bins) else [int(b) for b in bins]
+        if len(bins) != m:
+            raise ValueError("bins: one int or one per row")
+        spec.bins[:m] = bins
+    if centres is not None:
+        if len(centres) != m:
+            raise ValueError("centres: one per row")
+        spec.centre[:m] = [float(c) for c in centres]
+    if thresholds is not None:
+        if isinstance(thresholds, dict):
+            listed = list(spec.rows[:m])
+            per_row = [[] for _ in range(m)]
+            for r, values in thresholds.items():
+                if _row_id(r) not in listed:
+                    raise ValueError(f"thresholds: row {r!r} is not tallied")
+                per_row[listed.index(_row_id(r))] = list(values)
+        else:
+            per_row = [list(t) for t in thresholds]
+        if len(per_row) != m or any(len(t) > _abi.TALLY_MAX_THRESHOLDS for t in per_row):
+            raise ValueError(f"thresholds: one list of at most {_abi.TALLY_MAX_THRESHOLDS} per row")
+        for j, values in enumerate(per_row):
+            spec.n_thresholds[j] = len(values)
+            for t, v in enumerate(values):
+                spec.threshold[j][t] = float(v)
+    if k is not None:
+        spec.k = int(k)
+    if quantiles is not None:
+        quantiles = [float(q) for q in quantiles]
+        if len(quantiles) > _abi.TALLY_MAX_Q:
+            raise ValueError(f"at most {_abi.TALLY_MAX_Q} quantiles")
+        spec.n_q = len(quantiles)
+        spec.q[:len(quantiles)] = quantiles
+    for key, val in (bounds or {}).items():
+        if key not in ("max_apogee", "min_apogee", "max_range", "max_flight_time", "energy_apogee"):
+            raise ValueError(f"unknown bound {key!r}")
+        setattr(spec, key, float(val))
+    if grid_rows is not None:
+        spec.row_x, spec.row_y = _row_id(grid_rows[0]), _row_id(grid_rows[1])
+    if grid_bins is not None:
+        spec.bins_x, spec.bins_y = (int(grid_bins),) * 2 if np.isscalar(grid_bins) else (int(grid_bins[0]), int(grid_bins[1]))
+    if grid_ranges is not None:
+        (spec.lo_x, spec.hi_x), (spec.lo_y, spec.hi_y) = [(float(lo), float(hi)) for lo, hi in grid_ranges]
+    if zones is not None:
+        zones = [np.asarray(z, dtype=np.float64).reshape(-1, 2) for z in zones]
+        if len(zones) > _abi.TALLY_MAX_ZONES or sum(len(z) for z in zones) > _abi.TALLY_MAX_VERTICES:
+            raise ValueError(f"at most {_abi.TALLY_MAX_ZONES} zones of {_abi.TALLY_MAX_VERTICES} vertices together")
+        spec.n_zones, at = len(zones), 0
+        for z, poly in enumerate(zones):
+            spec.zone_first[z] = at
+            spec.zone_x[at:at + len(poly)] = poly[:, 0].tolist()
+            spec.zone_y[at:at + len(poly)] = poly[:, 1].tolist()
+            at += len(poly)
+        spec.zone_first[len(zones)] = at
+    return spec
+
+
+def tally_words(spec):
+    """The size of a tally's state in int64 words (erpl_mc_tally_words: refuses a bad spec with the library's message)."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    words = C.c_int64()
+    _abi.check(lib, lib.erpl_mc_tally_words(C.byref(spec), C.byref(words)), "erpl_mc_tally_words")
+    return int(words.value)
+
+
+def tally_edges(lo, hi, bins):
+    """The bin edges of a tallied row or grid axis: those of erpl_mc_histogram (np.linspace's two roundings, the last edge
+    exact)."""
+    e = np.arange(bins + 1, dtype=np.float64) * np.float64((hi - lo) / bins) + np.float64(lo)
+    e[bins] = hi
+    return e
+
+
+def tally_statistics(result, level=0.95):
+    """A tally's result (the dict of TrajectoryEngine.tally_result or tally_result_host) in the shape of
+    `device_statistics` where a counterpart exists - n_samples, n_outliers, per tallied row name {'mean', 'std', 'min',
+    'max', 'percentiles'}, reason_counts, termination_counts, n_non_finite - plus, per row: 'count', 'below', 'above',
+    'moment_skipped', 'percentiles_exact', 'histogram' {'edges', 'counts'}, 'exceedance' [{'threshold', 'count',
+    'probability', 'interval'}] (probability = count / counted values of the row, Wilson score interval at `level`),
+    'smallest' / 'largest' [(value, id)]; 'grid' {'counts', 'edges_x', 'edges_y', 'counted', 'outside'} and 'zones'
+    [{'vertices', 'inside', 'probability', 'interval'}] (probability = inside / grid counted).  A pure host function."""
+    from . import _abi
+    spec, res = result["spec"], result["result"]
+    m, nq = spec.n_rows, spec.n_q
+    out = {"n": int(res.n), "n_samples": int(res.n_valid), "n_failed": 0, "n_outliers": int(res.n_outliers), "interval_level": float(level),
+           "reason_counts": {name: int(res.reason_counts[b]) for b, name in enumerate(_abi.WHY_NAMES)},
+           "termination_counts": {name: int(res.termination_counts[b]) for b, name in enumerate(_abi.END_NAMES)},
+           "n_non_finite": int(res.n_status_nan), "q": list(spec.q[:nq]), "rows": {}}
+    for j in range(m):
+        r, row = spec.rows[j], res.row[j]
+        count = int(row.count)
+        d = {"row": int(r), "count": count, "below": int(row.below), "above": int(row.above), "moment_skipped": int(row.moment_skipped),
+             "mean": row.mean, "std": row.std, "var": row.var, "min": row.min, "max": row.max, "centre": spec.centre[j],
+             "sum_d": row.sum_d, "sum_d2": row.sum_d2,
+             "percentiles": list(row.quantile[:nq]), "percentiles_exact": [bool(e) for e in row.quantile_exact[:nq]],
+             "histogram": {"edges": tally_edges(spec.lo[j], spec.hi[j], spec.bins[j]),
+                           "counts": result["hist_counts"][j, :spec.bins[j]].copy()},
+             "exceedance": [{"threshold": spec.threshold[j][t], "count": int(row.exceed[t]),
+                             "probability": int(row.exceed[t]) / count if count else float("nan"),
+                             "interval": wilson_interval(int(row.exceed[t]), count, level)} for t in range(spec.n_thresholds[j])],
+             "smallest": [(row.smallest[e].value, int(row.smallest[e].id)) for e in range(row.n_smallest)],
+             "largest": [(row.largest[e].value, int(row.largest[e].id)) for e in range(row.n_largest)]}
+        out["rows"][ROW_NAMES[r]] = d
+        out[ROW_NAMES[r]] = {key: d[key] for key in ("mean", "std", "min", "max", "percentiles")}
+    counted = int(res.grid_counted)
+    out["grid"] = {"rows": (int(spec.row_x), int(spec.row_y)), "counts": result["grid_counts"],
+                   "edges_x": tally_edges(spec.lo_x, spec.hi_x, spec.bins_x), "edges_y": tally_edges(spec.lo_y, spec.hi_y, spec.bins_y),
+                   "counted": counted, "outside": int(res.grid_outside)}
+    out["zones"] = []
+    for z in range(spec.n_zones):
+        v0, v1 = spec.zone_first[z], spec.zone_first[z + 1]
+        inside = int(res.zone_inside[z])
+        out["zones"].append({"vertices": np.column_stack([spec.zone_x[v0:v1], spec.zone_y[v0:v1]]), "inside": inside,
+                             "probability": inside / counted if counted else float("nan"),
+                             "interval": wilson_interval(inside, counted, level)})
+    return out
+
+
+def _tally_result_dict(spec, res, hist, grid):
+    return {"spec": spec, "result": res, "hist_counts": hist, "grid_counts": grid.reshape(spec.bins_x, spec.bins_y)}
+
+
+def tally_add_host(spec, state, summary, status=None, first_id=0):
+    """erpl_mc_tally_add_host: folds the NumPy window summary ([16, n] float64, C order) / status ([n] int32 or None) into
+    the NumPy int64 state, in place - the device's rule on host memory, the same bytes."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    summary = np.ascontiguousarray(summary, dtype=np.float64)
+    if summary.ndim != 2 or summary.shape[0] != _abi.SUMMARY_DIM:
+        raise ValueError(f"summary must be [{_abi.SUMMARY_DIM}, n]")
+    n = summary.shape[1]
+    if status is not None:
+        status = np.ascontiguousarray(status, dtype=np.int32)
+        if status.shape != (n,):
+            raise ValueError("status must be [n]")
+    if not (isinstance(state, np.ndarray) and state.dtype == np.int64 and state.flags.c_contiguous and state.size == tally_words(spec)):
+        raise ValueError("state must be a contiguous int64 array of tally_words(spec) words")
+    _abi.check(lib, lib.erpl_mc_tally_add_host(C.byref(spec), C.c_void_p(state.ctypes.data), C.c_void_p(summary.ctypes.data), max(n, 1),
+                                               C.c_void_p(status.ctypes.data) if status is not None else None, n, int(first_id)),
+               "erpl_mc_tally_add_host")
+    return state
+
+
+def tally_merge_host(spec, dst, src):
+    """erpl_mc_tally_merge_host: dst += src, two NumPy int64 states of `spec`, in place."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    words = tally_words(spec)
+    for s in (dst, src):
+        if not (isinstance(s, np.ndarray) and s.dtype == np.int64 and s.flags.c_contiguous and s.size == words):
+            raise ValueError("dst and src must be contiguous int64 arrays of tally_words(spec) words")
+    _abi.check(lib, lib.erpl_mc_tally_merge_host(C.byref(spec), C.c_void_p(dst.ctypes.data), C.c_void_p(src.ctypes.data)),
+               "erpl_mc_tally_merge_host")
+    return dst
+
+
+def tally_result_host(spec, state):
+    """erpl_mc_tally_result_host of a NumPy int64 state: the dict `tally_statistics` takes ({'spec', 'result':
+    _abi.ErplTally, 'hist_counts' int64 [8, 1024], 'grid_counts' int64 [bins_x, bins_y]})."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    state = np.ascontiguousarray(state, dtype=np.int64)
+    if state.size != tally_words(spec):
+        raise ValueError("state must hold tally_words(spec) words")
+    res = _abi.ErplTally()
+    hist = np.zeros((_abi.TALLY_MAX_ROWS, _abi.TALLY_MAX_BINS), dtype=np.int64)
+    grid = np.zeros(spec.bins_x * spec.bins_y, dtype=np.int64)
+    _abi.check(lib, lib.erpl_mc_tally_result_host(C.byref(spec), C.c_void_p(state.ctypes.data), C.byref(res), C.c_void_p(hist.ctypes.data),
+                                                  C.c_void_p(grid.ctypes.data)), "erpl_mc_tally_result_host")
+    return _tally_result_dict(spec, res, hist, grid)

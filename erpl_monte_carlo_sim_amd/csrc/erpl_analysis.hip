@@ -11,6 +11,7 @@
 // commute.  So the result is the same bits in every call.  No floating-point atomics.  Compiled with -ffp-contract=off:
 // (x - mean)^2 is rounded as np.std rounds it.
 #include "erpl_stat_device.h"
+#include "erpl_tally.h"
 
 namespace {
 
@@ -22,6 +23,7 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_classify(const ErplAn
   const double* __restrict__ apo_p = a.summary + (int64_t)ERPL_SUM_APOGEE_ALT * n;
   const double* __restrict__ rng_p = a.summary + (int64_t)ERPL_SUM_RANGE * n;
   const double* __restrict__ ft_p = a.summary + (int64_t)ERPL_SUM_FLIGHT_TIME * n;
+  const ErplFilter f = {a.max_apogee, a.min_apogee, a.max_range, a.max_flight_time, a.energy_apogee};
   unsigned long long cnt[ERPL_ANA_COUNTERS];
 #pragma unroll
   for (int k = 0; k < ERPL_ANA_COUNTERS; ++k) cnt[k] = 0ull;
@@ -32,12 +34,7 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_classify(const ErplAn
     int why = 0, st = -1;
     if (in) {
       const double apo = apo_p[i], rng = rng_p[i], ft = ft_p[i];
-      if (!finite_bits(apo) || !finite_bits(rng) || !finite_bits(ft)) why |= ERPL_WHY_NON_FINITE;
-      if (apo > a.max_apogee) why |= ERPL_WHY_APOGEE_HIGH;
-      else if (apo < a.min_apogee) why |= ERPL_WHY_APOGEE_LOW;
-      if (rng > a.max_range) why |= ERPL_WHY_RANGE;
-      if (ft > a.max_flight_time) why |= ERPL_WHY_FLIGHT_TIME;
-      if (apo > a.energy_apogee) why |= ERPL_WHY_ENERGY;
+      why = erpl_why_of(f, apo, rng, ft);   // the one definition of the reason bits (erpl_tally.h)
       a.why[i] = (uint8_t)why;
       if (a.reasons) a.reasons[i] = (uint8_t)why;
       if (a.status) st = a.status[i];

@@ -470,6 +470,7 @@ int erpl_mc_destroy(erpl_ctx* c) {
   if (c->sur_ev) (void)hipEventDestroy(c->sur_ev);
   if (c->design_flag) (void)hipHostFree(c->design_flag);
   if (c->design_ev) (void)hipEventDestroy(c->design_ev);
+  c->tally.release();
   delete c;
   return ERPL_OK;
 }

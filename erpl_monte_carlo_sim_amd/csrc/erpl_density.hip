@@ -22,6 +22,7 @@
 // its sources in index order, slices are added in slice order.  No floating-point atomics.  Compiled with
 // -ffp-contract=off: the crossing expression is rounded as NumPy rounds it.
 #include "erpl_stat_device.h"
+#include "erpl_tally.h"
 
 namespace {
 
@@ -226,9 +227,7 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dens_zones(const ErplDens
       bool c = false;
       for (int vi = v0, vj = v1 - 1; vi < v1; vj = vi++) {
         const double xi = s_vx[vi], yi = s_vy[vi], xj = s_vx[vj], yj = s_vy[vj];
-        if ((yi > py) != (yj > py)) {
-          if (px < (xj - xi) * (py - yi) / (yj - yi) + xi) c = !c;
-        }
+        if (erpl_zone_flips(px, py, xi, yi, xj, yj)) c = !c;   // the one definition of the crossing rule (erpl_tally.h)
       }
       in[z] += __popcll(__ballot(use && c));
     }

@@ -13,18 +13,13 @@
 // the same bits in every call.  No floating-point atomics.  Compiled with -ffp-contract=off: the guess, (x - mean)^2 and
 // dx*dx + dy*dy are rounded as NumPy rounds them.
 #include "erpl_stat_device.h"
+#include "erpl_tally.h"
 
 namespace {
 
-// The bin of x in [lo, hi] among `bins` equal-width bins with edge values e[0..bins], as np.histogram finds it
-// (_histograms_impl.py: f_indices, then one step down and one step up against the edges).  The clamps cannot act for x in
-// [lo, hi]; they keep every read of e[] inside the row whatever the arithmetic does.
+// the bin of x among the edge values e[0..bins]: np.histogram's rule, defined once for these kernels and the tally (erpl_tally.h)
 __device__ __forceinline__ int bin_of(double x, double lo, double hi, int bins, const double* e) {
-  const double f = ((x - lo) / (hi - lo)) * (double)bins;
-  int k = f >= (double)bins ? bins - 1 : (f > 0.0 ? (int)f : 0);
-  if (x < e[k] && k > 0) k -= 1;
-  if (k < bins - 1 && x >= e[k + 1]) k += 1;
-  return k;
+  return erpl_bin_of(x, lo, hi, bins, e);
 }
 
 // ---- range: min / max of row rows[blockIdx.y] over the samples that count

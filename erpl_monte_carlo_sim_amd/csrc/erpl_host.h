@@ -1,5 +1,5 @@
 // erpl_host.h — what the host units of the C ABI share (erpl_api.hip, erpl_sampling.hip, erpl_stats_api.hip,
-// erpl_legacy_device.hip, erpl_design.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
+// erpl_legacy_device.hip, erpl_design.hip, erpl_tally.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
 // Internal, never installed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -247,6 +247,9 @@ struct erpl_ctx {
   // (both made by the first call; erpl_design_check_flag reads them for the blocking checks)
   int* design_flag = nullptr;
   hipEvent_t design_ev = nullptr;
+  // erpl_mc_tally_*: the device workspace of erpl_tally.hip (the spec, the candidate lists of the extremes) in the buffer, the
+  // spec that is on the device in the pinned mirror
+  ErplStatUnit<void, erpl_tally_spec> tally;
 };
 
 // erpl_design.hip

@@ -17,6 +17,7 @@
 
 #include "erpl_host.h"
 #include "erpl_philox.h"
+#include "erpl_tally.h"
 
 namespace {
 
@@ -228,11 +229,10 @@ bool settle_range(bool automatic, double found_lo, double found_hi, double* lo, 
 }
 
 // np.linspace(lo, hi, bins + 1): two roundings per edge (this file is compiled without contraction), the last edge exact
+// (the edge rule is ErplEdges of erpl_tally.h: the tally computes the same edges on the device)
 void fill_edges(double lo, double hi, int bins, double* e) {
-  const double delta = hi - lo, div = (double)bins, step = delta / div;
-  if (step != 0.0) for (int i = 0; i < bins; ++i) e[i] = (double)i * step + lo;
-  else for (int i = 0; i < bins; ++i) e[i] = ((double)i / div) * delta + lo;
-  e[bins] = hi;
+  const ErplEdges edge = erpl_edges_of(lo, hi, bins);
+  for (int i = 0; i <= bins; ++i) e[i] = edge[i];
 }
 
 // A histogram call from "args filled" to "edges on the device": the range pass if some axis is automatic, the range in use

@@ -762,6 +762,64 @@ class TrajectoryEngine:
                    C.c_void_p(st.cuda_stream))
         return out
 
+    # ---- the tally (erpl_mc_tally_*): a run of any length folded into a fixed-size int64 state on the device
+    def tally_new(self, spec=None):
+        """(spec, state): an empty tally of `spec` (analysis.tally_spec; None: the library's defaults) - the state is a
+        zeroed int64 device tensor of erpl_mc_tally_words(spec) words.  A bad spec is refused with the library's message."""
+        from . import analysis
+        spec = analysis.tally_spec() if spec is None else spec
+        return spec, torch.zeros((analysis.tally_words(spec),), dtype=torch.int64, device=self.device)
+
+    def _check_tally_state(self, spec, state, what="state"):
+        from . import analysis
+        if not (torch.is_tensor(state) and state.device == self.device and state.dtype == torch.int64 and state.dim() == 1
+                and state.is_contiguous() and state.numel() == analysis.tally_words(spec)):
+            raise ValueError(f"{what} must be a contiguous int64 tensor of tally_words(spec) words on {self.device}")
+
+    def tally_add(self, spec, state, summary, status=None, first_id=0, n=None):
+        """Folds the first n columns (default: all) of a window summary (float64 [16, ld] on the device, unit column stride)
+        and its status words into `state` (erpl_mc_tally_add); column i has the id first_id + i.  Asynchronous on the
+        current torch stream: a batch from `submit` is ordered in with `wait(ticket)` first."""
+        self._check_tally_state(spec, state)
+        if not (summary.is_cuda and summary.device == self.device and summary.dtype == torch.float64 and summary.dim() == 2
+                and summary.shape[0] == _abi.SUMMARY_DIM and summary.stride(1) == 1 and summary.stride(0) >= summary.shape[1]):
+            raise ValueError(f"summary must be a float64 [{_abi.SUMMARY_DIM}, ld] tensor on {self.device} with unit column stride")
+        n = int(summary.shape[1]) if n is None else int(n)
+        if n > summary.shape[1]:
+            raise ValueError(f"n = {n} exceeds the {summary.shape[1]} columns of summary")
+        if status is not None and not (status.device == self.device and status.dtype == torch.int32 and status.dim() == 1
+                                       and status.shape[0] >= n and status.is_contiguous()):
+            raise ValueError(f"status must be a contiguous int32 [>= n] tensor on {self.device}")
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_tally_add", C.byref(spec), C.c_void_p(state.data_ptr()), C.c_void_p(summary.data_ptr()),
+                   int(summary.stride(0)), C.c_void_p(status.data_ptr()) if status is not None else None, n, int(first_id),
+                   C.c_void_p(st.cuda_stream))
+        return state
+
+    def tally_merge(self, spec, dst, src):
+        """dst += src, two states of `spec` (erpl_mc_tally_merge): the bytes of dst are those of one tally of both sets of
+        samples, in whatever order tallies are merged.  Asynchronous on the current torch stream."""
+        self._check_tally_state(spec, dst, "dst")
+        self._check_tally_state(spec, src, "src")
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_tally_merge", C.byref(spec), C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()),
+                   C.c_void_p(st.cuda_stream))
+        return dst
+
+    def tally_result(self, spec, state):
+        """What a tally holds (erpl_mc_tally_result; blocks on the current torch stream): the dict analysis.tally_statistics
+        takes - 'spec', 'result' (_abi.ErplTally), 'hist_counts' (int64 [8, 1024]), 'grid_counts' (int64 [bins_x, bins_y]).
+        Raises _abi.IncompleteBatch for tallied status words with ST_INCOMPLETE."""
+        from . import analysis
+        self._check_tally_state(spec, state)
+        res = _abi.ErplTally()
+        hist = np.zeros((_abi.TALLY_MAX_ROWS, _abi.TALLY_MAX_BINS), dtype=np.int64)
+        grid = np.zeros(spec.bins_x * spec.bins_y, dtype=np.int64)
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_tally_result", C.byref(spec), C.c_void_p(state.data_ptr()), C.byref(res), C.c_void_p(hist.ctypes.data),
+                   C.c_void_p(grid.ctypes.data), C.c_void_p(st.cuda_stream))
+        return analysis._tally_result_dict(spec, res, hist, grid)
+
     def bootstrap(self, summary, mask=None, rows=None, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), replicates=2000, level=0.95,
                   seed=0, extra=None, want_replicates=False):
         """How sure the statistics of a run are (erpl_mc_bootstrap): the non-parametric bootstrap of mean, std and

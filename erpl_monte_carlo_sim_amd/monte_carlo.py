@@ -283,6 +283,65 @@ class MonteCarloAnalyzer:
                                   "cores_used": self.n_cores, "gpus_used": ws}
         return out
 
+    def _fly_sub_batches(self, eng, initial_conditions, n_samples, lo, hi, rank, seed, prec, planar, design, submitted, retired=None):
+        """The sub-batch loop of `run_monte_carlo_device` and `run_monte_carlo_tally`: this rank's samples [lo, hi) of the run
+        in sub-batches of DEVICE_CHUNK (the draws of sub-batch j come from seed + rank and j alone, so a run is
+        reproducible for a given n_samples, world size and seed; with design = (kind, block, K) every sub-batch takes its
+        window of the one global design), every one handed to erpl_mc_submit_batch as soon as it is drawn: generation, up
+        to `depth` integrations and their tails overlap on the GPU.  `submitted(a, cnt, db, outs)` is called behind the
+        submission of the sub-batch of cnt samples at offset a (outs: its summary and status tensors, not yet written);
+        `retired(a, cnt, ticket, outs)`, if given, once ITS ticket has been checked - the batch has finished - and before
+        its inputs and, unless the caller kept them, its outputs go back to the allocator.  Returns the seconds spent
+        drawing, with every batch finished and checked (raises if a lane hand-over timed out)."""
+        from . import sampling
+        m = max(hi - lo, 1)
+        gen_s = 0.0
+        inflight = []
+        starts = list(range(0, m, self.DEVICE_CHUNK))
+        # Sub-batches drawn before any of them is submitted: a sample budget (4 M samples, ~10 GB of wind tables at
+        # K = 100), not a count.  A generation kernel enqueued behind a running flight launch waits for its waves to
+        # drain, so a group is drawn on an idle stream first (1.5 ms per sub-batch) and then handed over in one go;
+        # the next group is drawn while the tails of this one fly.  A sub-batch's inputs are released as soon as ITS
+        # ticket has been checked (erpl_mc_check_batch waits for that batch alone).
+        GROUP = max(1, (4 << 20) // self.DEVICE_CHUNK)
+        keep = 2 * eng.get_overlap() + GROUP
+
+        def retire(ticket, a, cnt, inputs, outs):
+            eng.check(ticket)     # only once the batch has finished may its inputs go back to the allocator
+            if retired is not None:
+                retired(a, cnt, ticket, outs)
+
+        for g0 in range(0, len(starts), GROUP):
+            tg = time.time()
+            group = []
+            for j in range(g0, min(g0 + GROUP, len(starts))):
+                a = starts[j]
+                cnt = min(self.DEVICE_CHUNK, m - a)
+                draws = None
+                if design is not None:   # this sub-batch's window of the global design (a rank without samples: any column)
+                    kind, block, K = design
+                    draws = sampling.design_draws(n_samples, K, eng.device, seed, design=kind, block=block,
+                                                  first=min(lo + a, n_samples - cnt), count=cnt, engine=eng)
+                group.append((a, cnt, sampling.synthetic_dispersions(
+                    cnt, self.rocket, self.motor, self.wind_model, initial_conditions, eng.device,
+                    precision=prec, seed=seed + rank + 1000003 * j, uncertainty=self.uncertainty_params,
+                    base_altitude_profile=self.base_altitude_profile, base_wind_profile=self.base_wind_profile,
+                    planar=planar, engine=eng, draws=draws)))
+            gen_s += time.time() - tg
+            for a, cnt, db in group:
+                outs = eng.submit(db)
+                submitted(a, cnt, db, outs)
+                inflight.append((eng.last_ticket, a, cnt, db, outs if retired is not None else None))    # inputs outlive their batch
+            del group, db, outs
+            while len(inflight) > keep:
+                retire(*inflight.pop(0))
+        eng.wait()
+        eng.check()                # host-blocking; raises if a lane hand-over timed out
+        while inflight and retired is not None:
+            retire(*inflight.pop(0))
+        inflight.clear()
+        return gen_s
+
     def run_monte_carlo_device(self, initial_conditions, n_samples, seed=1234, precision="f64_fast", planar=False,
                                keep_factors=False, design=None, design_replicates=1):
         """Throughput form for 100 k - 10 M samples (BASELINE configs 3-5): dispersions are drawn on the
@@ -334,51 +393,19 @@ class MonteCarloAnalyzer:
         prec = _abi.PRECISIONS[precision]
         torch.cuda.synchronize(eng.device)
         t0 = time.time()
-        # This rank's samples in sub-batches of DEVICE_CHUNK (the draws of sub-batch j come from seed + rank and j alone, so a
-        # run is reproducible for a given n_samples, world size and seed), every one handed to erpl_mc_submit_batch
-        # as soon as it is drawn: generation, up to `depth` integrations and their tails overlap on the GPU.
-        m = max(hi - lo, 1)
-        gen_s = 0.0
-        parts, inflight, fparts, fnames = [], [], [], None
-        starts = list(range(0, m, self.DEVICE_CHUNK))
-        # Sub-batches drawn before any of them is submitted: a sample budget (4 M samples, ~10 GB of wind tables at
-        # K = 100), not a count.  A generation kernel enqueued behind a running flight launch waits for its waves to
-        # drain, so a group is drawn on an idle stream first (1.5 ms per sub-batch) and then handed over in one go;
-        # the next group is drawn while the tails of this one fly.  A sub-batch's inputs are released as soon as ITS
-        # ticket has been checked (erpl_mc_check_batch waits for that batch alone).
-        GROUP = max(1, (4 << 20) // self.DEVICE_CHUNK)
-        keep = 2 * eng.get_overlap() + GROUP
-        err = None
+        parts, fparts, fnames = [], [], None
+        err, gen_s = None, 0.0
+
+        def submitted(a, cnt, db, outs):
+            nonlocal fnames
+            parts.append(outs)
+            if keep_factors:
+                fparts.append(db.factors)
+                fnames = db.factor_names
+
         try:
-            for g0 in range(0, len(starts), GROUP):
-                tg = time.time()
-                group = []
-                for j in range(g0, min(g0 + GROUP, len(starts))):
-                    a = starts[j]
-                    cnt = min(self.DEVICE_CHUNK, m - a)
-                    draws = None
-                    if design is not None:   # this sub-batch's window of the global design (a rank without samples: any column)
-                        draws = sampling.design_draws(n_samples, design_K, eng.device, seed, design=design, block=design_block,
-                                                      first=min(lo + a, n_samples - cnt), count=cnt, engine=eng)
-                    group.append(sampling.synthetic_dispersions(
-                        cnt, self.rocket, self.motor, self.wind_model, initial_conditions, eng.device,
-                        precision=prec, seed=seed + rank + 1000003 * j, uncertainty=self.uncertainty_params,
-                        base_altitude_profile=self.base_altitude_profile, base_wind_profile=self.base_wind_profile,
-                        planar=planar, engine=eng, draws=draws))
-                gen_s += time.time() - tg
-                for db in group:
-                    parts.append(eng.submit(db))
-                    if keep_factors:
-                        fparts.append(db.factors)
-                        fnames = db.factor_names
-                    inflight.append((eng.last_ticket, db))    # inputs outlive their batch
-                while len(inflight) > keep:
-                    ticket, inputs = inflight.pop(0)
-                    eng.check(ticket)     # only once the batch has finished may its inputs go back to the allocator
-                    del inputs
-            eng.wait()
-            eng.check()                # host-blocking; raises if a lane hand-over timed out
-            inflight.clear()
+            gen_s = self._fly_sub_batches(eng, initial_conditions, n_samples, lo, hi, rank, seed, prec, planar,
+                                          None if design is None else (design, design_block, design_K), submitted)
             summ = parts[0][0] if len(parts) == 1 else torch.cat([p[0] for p in parts], dim=1)
             status = parts[0][1] if len(parts) == 1 else torch.cat([p[1] for p in parts])
             summ, status = summ[:, : hi - lo], status[: hi - lo]
@@ -411,6 +438,127 @@ class MonteCarloAnalyzer:
                               "precision": precision, "generate_s": gen_s, "integrate_and_gather_s": t2 - t0 - gen_s,
                               "statistics_s": t3 - t2, "sub_batches": len(parts), "in_flight": eng.get_overlap()}
         return out
+
+    def run_monte_carlo_tally(self, initial_conditions, n_samples, tally=None, seed=1234, precision="f64_fast", planar=False,
+                              design=None, design_replicates=1):
+        """`run_monte_carlo_device` for runs too long to keep: the same sub-batch loop, draws and seeds (bit for bit the same
+        flights), but no summary is kept - every sub-batch is folded into a tally (erpl_mc_tally_add, first_id = its global
+        sample index) as soon as its ticket has been checked, and its outputs are released with its inputs.  Device memory
+        does not depend on n_samples.  Across ranks there is one all-gather of the state words, merged in rank order
+        (erpl_mc_tally_merge: the bytes do not depend on that order); a failing rank still joins, with a state that makes
+        every rank refuse the result.  tally: the spec (analysis.tally_spec; None: the library's defaults).  n_samples: up
+        to 2^31 - 1 with a design, no limit but the int64 counts without one.
+        Returns the dict of analysis.tally_statistics plus 'spec', 'state' (the int64 device tensor: equal runs give equal
+        bytes, and with a design they do not depend on DEVICE_CHUNK or on the world size), 'result' (the dict of
+        TrajectoryEngine.tally_result), 'n_total', 'seed', 'precision', 'planar', 'initial_conditions', 'design' (None, or
+        kind / seed / block / replicates: what `refly` needs) and 'performance' (with 'peak_memory_bytes')."""
+        n_samples = int(n_samples)
+        design_args = None
+        if design is not None:
+            if design not in _abi.DESIGN_KINDS:
+                raise ValueError(f"design: None or one of {list(_abi.DESIGN_KINDS)}")
+            design_replicates = int(design_replicates)
+            if design_replicates < 1 or n_samples % design_replicates != 0:
+                raise ValueError(f"design_replicates = {design_replicates} does not divide n_samples = {n_samples}")
+            use_base = self.base_wind_profile is not None and self.base_altitude_profile is not None
+            design_args = (design, n_samples // design_replicates, len(self.base_altitude_profile) if use_base else 100)
+        eng = shared_engine(self.device)
+        eng.set_config(self._config())
+        spec, state = eng.tally_new(tally)
+        rank, ws = dist.world()
+        lo, hi, _ = dist.shard_bounds(n_samples, rank, ws)
+        prec = _abi.PRECISIONS[precision]
+        torch.cuda.synchronize(eng.device)
+        torch.cuda.reset_peak_memory_stats(eng.device)
+        t0 = time.time()
+        n_sub = [0]
+
+        def retired(a, cnt, ticket, outs):
+            n_sub[0] += 1
+            use = min(cnt, hi - lo - a)   # a rank without samples flies one column that is not tallied
+            if use > 0:
+                eng.wait(ticket)          # orders the finished batch into the current stream
+                eng.tally_add(spec, state, outs[0], outs[1], first_id=lo + a, n=use)
+
+        err, gen_s = None, 0.0
+        try:
+            gen_s = self._fly_sub_batches(eng, initial_conditions, n_samples, lo, hi, rank, seed, prec, planar, design_args,
+                                          lambda a, cnt, db, outs: None, retired)
+        except Exception as e:   # noqa: BLE001 - re-raised below
+            if ws == 1:
+                raise
+            # the other ranks are waiting in the all-gather: take part with a state marked incomplete, then raise
+            err = e
+            torch.cuda.synchronize(eng.device)
+            state.zero_()
+            state[14] = max(hi - lo, 1)   # n_incomplete: every rank's tally_result refuses
+        if ws > 1:
+            nccl = torch.distributed.get_backend() == "nccl"
+            mine = state if nccl else state.cpu()
+            gathered = torch.empty((ws * mine.numel(),), dtype=torch.int64, device=mine.device)
+            torch.distributed.all_gather_into_tensor(gathered, mine)
+            gathered = gathered.to(eng.device).view(ws, -1)
+            state = torch.zeros_like(state)
+            for r in range(ws):
+                eng.tally_merge(spec, state, gathered[r].contiguous())
+        if err is not None:
+            raise err
+        result = eng.tally_result(spec, state)   # blocks; raises _abi.IncompleteBatch if a shard failed
+        t1 = time.time()
+        out = analysis.tally_statistics(result)
+        out.update({"spec": spec, "state": state, "result": result, "n_total": n_samples, "seed": int(seed), "precision": precision,
+                    "planar": bool(planar), "initial_conditions": dict(initial_conditions), "design": None})
+        if design is not None:
+            out["design"] = {"kind": design, "seed": int(seed), "block": design_args[1], "replicates": design_replicates}
+        out["performance"] = {"total_time": t1 - t0, "simulations_per_second": n_samples / (t1 - t0), "gpus_used": ws,
+                              "precision": precision, "generate_s": gen_s, "sub_batches": n_sub[0], "in_flight": eng.get_overlap(),
+                              "state_bytes": int(state.numel()) * 8,
+                              "peak_memory_bytes": int(torch.cuda.max_memory_allocated(eng.device))}
+        return out
+
+    def refly(self, run, ids, stride=10, initial_conditions=None):
+        """Flies named samples of a design run again, with capture: `run` is the dict of `run_monte_carlo_tally` (or any
+        dict with its keys 'design', 'n_total', 'precision', 'planar', 'initial_conditions'), `ids` global sample ids - the
+        ids a tally holds with its extremes.  Column i of a design run is a function of (seed, n, design, i) alone
+        (erpl_mc_design), so the named columns are generated again (`sampling.design_draws(first=id, count=1)`) and flown
+        with every `stride`-th step captured.  Returns {'ids', 'summary' float64 [16, len(ids)], 'status', 'traj',
+        'traj_len', 'stride'} on the device: the input of TrajectoryEngine.flight_envelope / corridor_resample on the worst
+        cases.  A run with design=None cannot be re-flown: its draws come per sub-batch from torch's generator, so a column
+        is no function of its id (ValueError)."""
+        from . import sampling
+        design = run.get("design")
+        if design is None:
+            raise ValueError("refly needs a run flown with design='random', 'lhs' or 'lhs_centred': the draws of a design=None run "
+                             "come per sub-batch from torch's generator, so a sample cannot be regenerated from its id")
+        ids = [int(i) for i in ids]
+        n_total = int(run["n_total"])
+        if not ids or min(ids) < 0 or max(ids) >= n_total:
+            raise ValueError(f"ids: at least one, each in 0..{n_total - 1}")
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError("stride must be at least 1")
+        ic = run["initial_conditions"] if initial_conditions is None else initial_conditions
+        eng = shared_engine(self.device)
+        eng.set_config(self._config())
+        use_base = self.base_wind_profile is not None and self.base_altitude_profile is not None
+        K = len(self.base_altitude_profile) if use_base else 100
+        draws = torch.cat([sampling.design_draws(n_total, K, eng.device, design["seed"], design=design["kind"], block=design["block"],
+                                                 first=i, count=1, engine=eng) for i in ids], dim=1).contiguous()
+        db = sampling.synthetic_dispersions(
+            len(ids), self.rocket, self.motor, self.wind_model, ic, eng.device, precision=_abi.PRECISIONS[run["precision"]],
+            seed=design["seed"], uncertainty=self.uncertainty_params, base_altitude_profile=self.base_altitude_profile,
+            base_wind_profile=self.base_wind_profile, planar=run["planar"], engine=eng, draws=draws)
+        dt = min(self.dt_initial, 0.005)
+        cap = int(np.ceil(self.max_time / dt / stride)) + 4
+        summ, status, traj, tlen = eng.run(db, traj_ids=np.arange(len(ids)), traj_stride=stride, traj_cap=cap)
+        eng.synchronize()
+        return {"ids": ids, "summary": summ, "status": status, "traj": traj, "traj_len": tlen, "stride": stride}
+
+    def plot_exceedance(self, tally, row="range", save_plots=True, level=0.95):
+        """The complementary distribution of a tallied row on a log axis, from the dict of `run_monte_carlo_tally`
+        (plots.plot_exceedance)."""
+        from . import plots
+        return plots.plot_exceedance(self, tally, row, save_plots, level)
 
     def flight_envelope(self, initial_conditions, n_samples, stride=10, seed=1234, precision="f64_fast", planar=False,
                         capture_bytes=4 << 30):

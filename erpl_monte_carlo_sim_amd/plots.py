@@ -536,6 +536,46 @@ def run_comparison_figure(cmp):
     return fig
 
 
+def exceedance_figure(tally, row="range", level=0.95):
+    """The complementary distribution P(X > x) of one tallied row (the dict of analysis.tally_statistics /
+    MonteCarloAnalyzer.run_monte_carlo_tally; row: its name) on a log axis: a step through the bin edges from the histogram
+    counts (the mass above the range included), the held largest values as points at (value, rank / count) - the part of the
+    tail the bins are too coarse for - and the Wilson score band at `level` around the steps.  A probability of zero has no
+    place on a log axis: the curve ends at the last edge with mass above it."""
+    from .analysis import wilson_interval
+    r = tally["rows"][row]
+    count = int(r["count"])
+    fig = _figure((7.0, 4.5))
+    ax = fig.subplots(1, 1)
+    edges = np.asarray(r["histogram"]["edges"], dtype=np.float64)
+    counts = np.asarray(r["histogram"]["counts"], dtype=np.int64)
+    # counted values above edge i: the bins from i on and the mass above the range
+    above = int(r["above"]) + np.concatenate([np.cumsum(counts[::-1])[::-1], [0]])
+    have = above > 0
+    if count > 0 and have.any():
+        x, k = edges[have], above[have]
+        band = np.array([wilson_interval(int(v), count, level) for v in k])
+        ax.step(x, k / count, where="post", color="tab:blue", label="histogram")
+        ax.fill_between(x, np.maximum(band[:, 0], 0.5 / count), band[:, 1], step="post", color="tab:blue", alpha=0.2,
+                        label=f"{100 * level:.0f} % Wilson band")
+    largest = r["largest"]
+    if count > 0 and largest:
+        # the e-th largest value is exceeded by e values (e = 0: by none, drawn at half a count)
+        ax.plot([v for v, _ in largest], [max(e, 0.5) / count for e in range(len(largest))], "o", color="tab:red", markersize=3,
+                label=f"{len(largest)} largest held")
+    for t in r["exceedance"]:
+        ax.axvline(t["threshold"], color="black", linewidth=0.6, linestyle="--")
+    ax.set_yscale("log")
+    ax.set_xlabel(row)
+    ax.set_ylabel("P(X > x)")
+    ax.set_title(f"{row}: exceedance over {count} counted flights")
+    ax.grid(True, which="both", alpha=0.3)
+    if count > 0:
+        ax.legend(loc="best", fontsize=8)
+    fig.tight_layout()
+    return fig
+
+
 def save_figure(fig, output_dir, name):
     path = os.path.join(output_dir, name)
     fig.savefig(path, dpi=DPI, bbox_inches="tight")
@@ -773,4 +813,15 @@ def plot_run_comparison(analyzer, comparison, save_plots=True):
     if save_plots:
         output_dir = analyzer._create_output_directory()
         print(f"Run comparison plot saved to: {save_figure(fig, output_dir, 'monte_carlo_run_comparison.png')}")
+    return output_dir
+
+
+def plot_exceedance(analyzer, tally, row="range", save_plots=True, level=0.95):
+    """The exceedance curve of a tallied row (no reference counterpart) as monte_carlo_exceedance_<row>.png; returns the output
+    directory (None without save_plots)."""
+    fig = exceedance_figure(tally, row, level)
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Exceedance plot saved to: {save_figure(fig, output_dir, f'monte_carlo_exceedance_{row}.png')}")
     return output_dir

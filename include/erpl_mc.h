@@ -1442,6 +1442,141 @@ int erpl_mc_surrogate_predict(erpl_ctx* ctx, const erpl_sur_spec* spec, const ui
 int erpl_mc_surrogate_predict_host(const erpl_sur_spec* spec, const uint8_t* kinds, const double* coefficients, const double* X,
                                    int64_t ld, int64_t n, double* out);
 
+/* A tally: a run of any length folded into bounded memory.  Every analysis above takes one resident [16][n] summary; a
+ * tally is a fixed-size, caller-owned device array of int64 words into which each sub-batch is folded as soon as it has
+ * flown (erpl_mc_tally_add), after which its summary may be dropped, and which ranks combine by erpl_mc_tally_merge instead
+ * of gathering samples.  THE BYTES OF THE STATE DEPEND ON THE SET OF (sample, id) PAIRS FOLDED IN AND ON THE SPEC, AND ON
+ * NOTHING ELSE: not on how the run was cut into windows, not on the order of the adds or merges, not on the number of
+ * ranks, not on host or device.  So nothing in it is a floating-point running sum: counts are integers, the two moment sums
+ * of a row go through an exact fixed-point accumulator (below), and the extremes are a sorted set.  The empty tally is all
+ * zero bytes: hipMemset, or torch.zeros.
+ *
+ * Filter: the reason bits of erpl_mc_analyze from the same five bounds; a sample is valid iff it carries none.  The header
+ * counts (n, n_valid, reason_counts, termination_counts, n_status_nan, n_incomplete) are those of erpl_analysis.
+ * Rows: up to ERPL_TALLY_MAX_ROWS summary rows, each with a fixed finite range lo < hi, `bins` equal-width bins, a `centre`
+ * and up to ERPL_TALLY_MAX_THRESHOLDS thresholds.  A value x is counted iff the sample is valid and x is finite.  Bin rule and
+ * edges are those of erpl_mc_histogram (edges[i] = i * ((hi - lo) / bins) + lo, the last one hi); below / above count the
+ * counted values outside [lo, hi]; exceed[t] counts x > threshold[t].
+ * Moments: d = x - centre, rounded once.  d is added EXACTLY to a long fixed-point accumulator; hi = d * d (rounded) and
+ * lo = fma(d, d, -hi) are added exactly to a second one, so that it holds the exact sum of d^2.  A value with
+ * |d| >= 2^500 (or d not finite) is counted everywhere else, kept out of both accumulators and counted in moment_skipped; a
+ * value with |d| < 2^-485 contributes lo = 0 (its hi is the rounded product).  sum_d and sum_d2 are the accumulators rounded
+ * once to double (ties to even); mean = centre + sum_d / count, var = (sum_d2 - sum_d * (sum_d / count)) / count,
+ * std = sqrt(var), each operation rounded on its own; NaN for count == 0.  The sums are exact, but the subtraction in var
+ * cancels: its relative error is about 2^-53 (1 + (centre - mean)^2 / var).  With the centre within a standard deviation of
+ * the mean, mean and std agree with erpl_mc_analyze to 1e-12 relative; with the DEFAULT mid-range centres the bound is
+ * 2^-52 (1 + (centre - mean)^2 / var) on std (tested; on 4096 flights the largest deviation measured was 1e-11, on a flight
+ * time of 13.1 +- 0.86 s against the centre of 300 s).  A caller who needs the last digits takes the centre from a pilot
+ * run, like the ranges.
+ * Extremes: per row the k smallest and the k largest counted values, each with its global sample id first_id + column.  The
+ * order is the library's radix key of the bit pattern (-0 < +0), ties go to the lower id; fewer than k counted values: fewer
+ * held.  smallest[0] is the minimum, largest[0] the maximum (min / max are NaN with k == 0 or nothing counted).
+ * Quantiles: np.percentile's (linear) virtual index v = (count - 1) q of q[i] and its order statistics floor(v),
+ * floor(v) + 1 (both the last one for v >= count - 1).  If both are among the held smallest or largest, quantile[i] is np.percentile's value to the bit and
+ * quantile_exact[i] = 1.  Otherwise an order statistic that is not held is placed inside its bin by linear interpolation on
+ * the cumulative counts (rank r with c values in bin b, `before` counted values before it: edges[b] + (edges[b + 1] -
+ * edges[b]) (r - before + 0.5) / c), the two are interpolated as NumPy does, quantile_exact[i] = 0 and the error is at most
+ * one bin width; if such an order statistic lies in the below / above mass, the quantile is NaN.
+ * Impact grid: the pair (row_x, row_y), counted iff the sample is valid and both values are finite; bins_x x bins_y cells by
+ * the rule of erpl_mc_histogram_xy over fixed ranges, `grid_outside` counts the counted samples off the grid; zone_inside[z]
+ * counts the counted samples inside polygon z by the crossing rule of erpl_mc_impact_density (zones laid out as in
+ * erpl_density_spec).
+ *
+ * State: erpl_mc_tally_words gives its size in int64 words for a spec (16 header words; per row 12 counts, `bins` bin counts,
+ * 2 x 70 accumulator words and 2 + 4 k words of extremes; 10 grid counts and bins_x * bins_y cells, in that order).  An
+ * accumulator is 70 digits of 32 bits, one per word, digit i weighing 2^(32 i - 1088), always in canonical form (digits
+ * 0..68 in [0, 2^32), digit 69 the sign): one value, one representation.  State, spec and calls must agree: a state is
+ * only ever used with the spec it was sized for. */
+#define ERPL_TALLY_MAX_ROWS 8
+#define ERPL_TALLY_MAX_BINS 1024        /* = ERPL_HIST_MAX_BINS */
+#define ERPL_TALLY_MAX_THRESHOLDS 8
+#define ERPL_TALLY_MAX_K 64
+#define ERPL_TALLY_MAX_Q 8              /* = ERPL_ANALYSIS_MAX_Q */
+#define ERPL_TALLY_MAX_GRID 256         /* per axis, = ERPL_HIST2D_MAX_BINS */
+#define ERPL_TALLY_MAX_ZONES 8          /* = ERPL_DENSITY_MAX_ZONES */
+#define ERPL_TALLY_MAX_VERTICES 256     /* of all zones together */
+
+typedef struct erpl_tally_spec {
+  double max_apogee, min_apogee, max_range, max_flight_time, energy_apogee;   /* as erpl_analysis_spec */
+  int32_t n_rows;                                   /* 0..ERPL_TALLY_MAX_ROWS */
+  int32_t rows[ERPL_TALLY_MAX_ROWS];                /* summary rows, distinct, 0..15 */
+  int32_t bins[ERPL_TALLY_MAX_ROWS];                /* 1..ERPL_TALLY_MAX_BINS */
+  int32_t n_thresholds[ERPL_TALLY_MAX_ROWS];        /* 0..ERPL_TALLY_MAX_THRESHOLDS */
+  int32_t k;                                        /* 0..ERPL_TALLY_MAX_K extremes held per row and side */
+  int32_t n_q;                                      /* 0..ERPL_TALLY_MAX_Q */
+  double lo[ERPL_TALLY_MAX_ROWS], hi[ERPL_TALLY_MAX_ROWS];   /* finite, lo < hi */
+  double centre[ERPL_TALLY_MAX_ROWS];               /* finite */
+  double threshold[ERPL_TALLY_MAX_ROWS][ERPL_TALLY_MAX_THRESHOLDS];   /* not NaN */
+  double q[ERPL_TALLY_MAX_Q];                       /* in [0, 1] */
+  int32_t row_x, row_y;                             /* the impact grid: distinct, 0..15 */
+  int32_t bins_x, bins_y;                           /* 1..ERPL_TALLY_MAX_GRID */
+  double lo_x, hi_x, lo_y, hi_y;                    /* finite, lo < hi */
+  int32_t n_zones;                                  /* 0..ERPL_TALLY_MAX_ZONES */
+  int32_t zone_first[ERPL_TALLY_MAX_ZONES + 1];     /* zone z: vertices zone_first[z] .. zone_first[z + 1] - 1; [0] = 0 */
+  double zone_x[ERPL_TALLY_MAX_VERTICES], zone_y[ERPL_TALLY_MAX_VERTICES];
+} erpl_tally_spec;
+
+typedef struct erpl_tally_extreme {
+  double value;
+  int64_t id;
+} erpl_tally_extreme;
+
+typedef struct erpl_tally_row {
+  int64_t count, below, above, moment_skipped;
+  int64_t exceed[ERPL_TALLY_MAX_THRESHOLDS];
+  double sum_d, sum_d2, mean, var, std, min, max;
+  double quantile[ERPL_TALLY_MAX_Q];
+  int32_t quantile_exact[ERPL_TALLY_MAX_Q];
+  int32_t n_smallest, n_largest;
+  erpl_tally_extreme smallest[ERPL_TALLY_MAX_K], largest[ERPL_TALLY_MAX_K];   /* smallest ascending, largest descending */
+} erpl_tally_row;
+
+typedef struct erpl_tally {
+  int64_t n, n_valid, n_outliers;
+  int64_t reason_counts[6], termination_counts[5], n_status_nan, n_incomplete;   /* as erpl_analysis */
+  int64_t grid_counted, grid_outside;
+  int64_t zone_inside[ERPL_TALLY_MAX_ZONES];
+  erpl_tally_row row[ERPL_TALLY_MAX_ROWS];          /* row[j] describes spec->rows[j] */
+} erpl_tally;
+
+/* Host only: the bounds of erpl_mc_analysis_defaults; rows {APOGEE_ALT, RANGE, FLIGHT_TIME} over 0..80 km, 0..200 km,
+ * 0..600 s (the filter bounds as ranges), 1000 bins each, centre = mid-range, no thresholds, k = 16, q {0.05, 0.25, 0.5,
+ * 0.75, 0.95}; grid {IMPACT_X, IMPACT_Y}, 128 x 128 over +-200 km, no zones. */
+int erpl_mc_tally_defaults(erpl_tally_spec* spec);
+/* Host only: checks the spec (the refusals below) and returns the size of its state in int64 words. */
+int erpl_mc_tally_words(const erpl_tally_spec* spec, int64_t* words);
+/* Folds the window summary [ERPL_SUMMARY_DIM][ld] (n columns in use), status [n] (may be NULL) into `state`; sample i of the
+ * window has the id first_id + i.  summary, status and state are CALLER-OWNED device memory.  _add and _merge (dst += src,
+ * both of this spec) enqueue on `hip_stream` and return: they never block the host, except that a call with another spec
+ * than the context's previous tally call first waits for the device.  A batch handed over with erpl_mc_submit_batch is
+ * ordered into the stream with erpl_mc_wait_batch first.  The workspace (the spec on the device, the candidate lists of the
+ * extremes) belongs to the context; tally calls on one context are serialised by the caller.
+ * _result copies the state to the host, blocks on the stream and is the host finalisation of _result_host and nothing else.
+ * hist_counts: host int64 [ERPL_TALLY_MAX_ROWS][ERPL_TALLY_MAX_BINS] (row j uses the first bins[j] of its line, the rest is
+ * zero), grid_counts: host int64 [bins_x][bins_y], x-major; either may be NULL.
+ * The _host calls are the same rule on host memory: no context, no device; their states are the same bytes.
+ * Errors: ERPL_ERR_INVALID, before any device work and with a message that names the argument: a NULL spec; the spec - a NaN
+ * bound, n_rows, a row outside 0..15 or listed twice, then per row bins, a non-finite or empty range, a non-finite centre,
+ * n_thresholds, a NaN threshold, then k, n_q, a q outside [0, 1], row_x, row_y, row_x == row_y, bins_x, bins_y, the ranges
+ * of the grid, n_zones, zone_first, a polygon under 3 vertices, more than 256 vertices, a non-finite vertex; then a NULL
+ * state / dst / src / summary / result, n <= 0, n > 2^31 - 1 (per call: the carries of the accumulators are propagated once
+ * per window), ld < n, first_id < 0 or first_id + n overflowing; the context last.
+ * Cost of the extremes: a window in which more than 2048 values of one row beat the k-th held value on one side - always the
+ * first window into an empty tally, later only a row whose tail keeps improving - is settled by ONE workgroup per row and
+ * side scanning the whole row (exact and bounded; about 3 - 4 ms per 2^20 columns instead of 0.2 - 0.4 ms for the call).
+ * _result: ERPL_ERR_INVALID if a count word has passed 2^62; ERPL_ERR_INCOMPLETE, with the result filled, if
+ * n_incomplete > 0. */
+int erpl_mc_tally_add(erpl_ctx* ctx, const erpl_tally_spec* spec, int64_t* state, const double* summary, int64_t ld,
+                      const int32_t* status, int64_t n, int64_t first_id, void* hip_stream);
+int erpl_mc_tally_merge(erpl_ctx* ctx, const erpl_tally_spec* spec, int64_t* dst, const int64_t* src, void* hip_stream);
+int erpl_mc_tally_result(erpl_ctx* ctx, const erpl_tally_spec* spec, const int64_t* state, erpl_tally* result,
+                         int64_t* hist_counts, int64_t* grid_counts, void* hip_stream);
+int erpl_mc_tally_add_host(const erpl_tally_spec* spec, int64_t* state, const double* summary, int64_t ld,
+                           const int32_t* status, int64_t n, int64_t first_id);
+int erpl_mc_tally_merge_host(const erpl_tally_spec* spec, int64_t* dst, const int64_t* src);
+int erpl_mc_tally_result_host(const erpl_tally_spec* spec, const int64_t* state, erpl_tally* result, int64_t* hist_counts,
+                              int64_t* grid_counts);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
