@@ -466,6 +466,28 @@ class ErplTally(C.Structure):
                 ("row", ErplTallyRow * TALLY_MAX_ROWS)]
 
 
+# erpl_mc_subset_*
+SUBSET_MAX_STEPS = 65535
+SUBSET_MAX_SLOTS = 4
+
+
+class ErplSubsetSpec(C.Structure):
+    _fields_ = [("max_apogee", C.c_double), ("min_apogee", C.c_double), ("max_range", C.c_double),
+                ("max_flight_time", C.c_double), ("energy_apogee", C.c_double),
+                ("row", C.c_int32), ("sign", C.c_int32), ("use_centre", C.c_int32), ("reserved", C.c_int32),
+                ("cx", C.c_double), ("cy", C.c_double), ("seed", C.c_uint64), ("level", C.c_uint32), ("step", C.c_uint32)]
+
+
+class ErplSubsetGather(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("ld_src", C.c_int64), ("ld_dst", C.c_int64),
+                ("rows", C.c_int32), ("elem_size", C.c_int32)]
+
+
+class ErplSubsetTriple(C.Structure):
+    _fields_ = [("cand", C.c_void_p), ("cur", C.c_void_p), ("next", C.c_void_p), ("ld_cand", C.c_int64), ("ld", C.c_int64),
+                ("rows", C.c_int32), ("elem_size", C.c_int32)]
+
+
 LIB_NAME = "liberpl_mc.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
@@ -497,7 +519,10 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_surrogate_defaults", "erpl_mc_surrogate_terms", "erpl_mc_surrogate", "erpl_mc_surrogate_predict",
            "erpl_mc_surrogate_predict_host",
            "erpl_mc_tally_defaults", "erpl_mc_tally_words", "erpl_mc_tally_add", "erpl_mc_tally_merge", "erpl_mc_tally_result",
-           "erpl_mc_tally_add_host", "erpl_mc_tally_merge_host", "erpl_mc_tally_result_host")
+           "erpl_mc_tally_add_host", "erpl_mc_tally_merge_host", "erpl_mc_tally_result_host",
+           "erpl_mc_subset_defaults", "erpl_mc_subset_limit_state", "erpl_mc_subset_limit_state_host",
+           "erpl_mc_subset_seeds", "erpl_mc_subset_seeds_host", "erpl_mc_subset_propose", "erpl_mc_subset_propose_host",
+           "erpl_mc_subset_commit", "erpl_mc_subset_commit_host", "erpl_mc_subset_chain_stats", "erpl_mc_subset_chain_stats_host")
 
 _lib = None
 
@@ -628,6 +653,17 @@ def load_library(path=None):
     lib.erpl_mc_tally_add_host.argtypes = [C.POINTER(ErplTallySpec), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64]
     lib.erpl_mc_tally_merge_host.argtypes = [C.POINTER(ErplTallySpec), C.c_void_p, C.c_void_p]
     lib.erpl_mc_tally_result_host.argtypes = [C.POINTER(ErplTallySpec), C.c_void_p, C.POINTER(ErplTally), C.c_void_p, C.c_void_p]
+    lib.erpl_mc_subset_defaults.argtypes = [C.POINTER(ErplSubsetSpec)]
+    limit_state = [C.POINTER(ErplSubsetSpec), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    seeds = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ErplSubsetGather), C.c_int32]
+    propose = [C.POINTER(ErplSubsetSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
+               C.c_int64, C.c_void_p, C.c_int64]
+    commit = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ErplSubsetTriple), C.c_int32, C.c_int64, C.c_void_p]
+    chain_stats = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    for name, args in (("limit_state", limit_state), ("seeds", seeds), ("propose", propose), ("commit", commit),
+                       ("chain_stats", chain_stats)):
+        getattr(lib, f"erpl_mc_subset_{name}").argtypes = [C.c_void_p] + args + [C.c_void_p]   # ctx .. hip_stream
+        getattr(lib, f"erpl_mc_subset_{name}_host").argtypes = args
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if a declared symbol is not exported
         if name not in ("erpl_mc_last_error",):

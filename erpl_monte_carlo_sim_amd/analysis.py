@@ -4,6 +4,8 @@ Same bounds, keys and reason strings as monte_carlo.py:337-398 / :400-473 of the
 evaluated on arrays (one pass over the gathered per-sample summaries) instead of a Python loop
 over result dicts.  Checked against tests/golden/stats.json.
 """
+import math
+
 import numpy as np
 
 MAX_REASONABLE_APOGEE = 80000.0
@@ -1001,3 +1003,429 @@ def tally_result_host(spec, state):
     _abi.check(lib, lib.erpl_mc_tally_result_host(C.byref(spec), C.c_void_p(state.ctypes.data), C.byref(res), C.c_void_p(hist.ctypes.data),
                                                   C.c_void_p(grid.ctypes.data)), "erpl_mc_tally_result_host")
     return _tally_result_dict(spec, res, hist, grid)
+
+
+# ---------------------------------------------------------------------------------- subset simulation: rare-event probabilities
+def subset_spec(row="range", tail="upper", centre=None, bounds=None, seed=0, level=0, step=1):
+    """The spec of erpl_mc_subset_limit_state / _propose (_abi.ErplSubsetSpec) on top of the library's defaults: g is the
+    summary row `row` (ROW_NAMES or index) for tail='upper', minus it for 'lower'; with centre=(cx, cy) the miss distance of
+    the impact point instead.  bounds: the dict of TrajectoryEngine.analyze.  A pure host function."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    spec = _abi.ErplSubsetSpec()
+    _abi.check(lib, lib.erpl_mc_subset_defaults(C.byref(spec)), "erpl_mc_subset_defaults")
+    if tail not in ("upper", "lower"):
+        raise ValueError("tail: 'upper' or 'lower'")
+    spec.row, spec.sign = _row_id(row), 1 if tail == "upper" else -1
+    if centre is not None:
+        spec.use_centre, spec.cx, spec.cy = 1, float(centre[0]), float(centre[1])
+    for key, val in (bounds or {}).items():
+        if key not in ("max_apogee", "min_apogee", "max_range", "max_flight_time", "energy_apogee"):
+            raise ValueError(f"unknown bound {key!r}")
+        setattr(spec, key, float(val))
+    spec.seed, spec.level, spec.step = int(seed) & 0xFFFFFFFFFFFFFFFF, int(level), int(step)
+    return spec
+
+
+def _np_ptr(a):
+    import ctypes as C
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def _np_matrix(a, dtype, what):
+    """A NumPy matrix the _host calls may read or write in place: 1-D or 2-D, unit column stride.  Returns (rows, ld)."""
+    if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.ndim in (1, 2) and (a.shape[-1] <= 1 or a.strides[-1] == a.itemsize)):
+        raise ValueError(f"{what} must be a {np.dtype(dtype).name} NumPy array with unit column stride")
+    if a.ndim == 1 or a.shape[0] == 1:
+        return 1, max(int(a.shape[-1]), 1)
+    if a.strides[0] % a.itemsize or a.strides[0] // a.itemsize < a.shape[1]:
+        raise ValueError(f"{what}: rows must not overlap")
+    return int(a.shape[0]), a.strides[0] // a.itemsize
+
+
+def subset_limit_state_host(spec, summary, status=None):
+    """erpl_mc_subset_limit_state_host: g [n] of the NumPy summary [16, n] / status [n] (or None)."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    summary = np.ascontiguousarray(summary, dtype=np.float64)
+    n = summary.shape[1]
+    status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+    g = np.empty(n, dtype=np.float64)
+    _abi.check(lib, lib.erpl_mc_subset_limit_state_host(C.byref(spec), _np_ptr(summary), _np_ptr(status), n, n, _np_ptr(g)),
+               "erpl_mc_subset_limit_state_host")
+    return g
+
+
+def subset_seeds_host(g, n_seeds, gathers=(), threshold=None):
+    """erpl_mc_subset_seeds_host on NumPy arrays: the n_seeds samples of g that went furthest (ties to the lower id).  gathers:
+    up to 4 (src, dst) pairs of matrices [rows, n] / [rows, >= n_seeds] (or vectors) of one dtype of 1, 4 or 8 bytes; the
+    selected columns of src go, ascending in id, to columns 0 .. n_seeds - 1 of dst, in place.  Returns (idx int32 [n_seeds],
+    selected uint8 [n], threshold, n_alive).  n_seeds = 0: the indicator of the given `threshold` and its count (as n_alive).
+    A died-out level raises _abi.ErplError."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    g = np.ascontiguousarray(g, dtype=np.float64)
+    n, n_seeds = g.size, int(n_seeds)
+    idx, sel = np.empty(max(n_seeds, 0), dtype=np.int32), np.empty(n, dtype=np.uint8)
+    thr, alive = C.c_double(0.0 if threshold is None else float(threshold)), C.c_int64(0)
+    slots = (_abi.ErplSubsetGather * max(len(gathers), 1))()
+    for q, (src, dst) in enumerate(gathers):
+        rows, ld_src = _np_matrix(src, src.dtype, "a gather's src")
+        rows_d, ld_dst = _np_matrix(dst, src.dtype, "a gather's dst")
+        if rows_d != rows:
+            raise ValueError("a gather's src and dst: the same rows")
+        slots[q].src, slots[q].dst, slots[q].ld_src, slots[q].ld_dst = src.ctypes.data, dst.ctypes.data, ld_src, ld_dst
+        slots[q].rows, slots[q].elem_size = rows, src.itemsize
+    _abi.check(lib, lib.erpl_mc_subset_seeds_host(_np_ptr(g), n, n_seeds, _np_ptr(idx), _np_ptr(sel), C.byref(thr), C.byref(alive),
+                                                  slots, len(gathers)), "erpl_mc_subset_seeds_host")
+    return idx, sel, thr.value, int(alive.value)
+
+
+def _subset_rows(kinds, rho, s, w):
+    kinds = bytes(bytearray(int(k) for k in kinds))
+    R = len(kinds)
+    rho = np.ascontiguousarray(np.broadcast_to(np.asarray(rho, dtype=np.float64), (R,)))
+    s = np.sqrt(1.0 - rho * rho) if s is None else np.ascontiguousarray(np.broadcast_to(np.asarray(s, dtype=np.float64), (R,)))
+    w = s.copy() if w is None else np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.float64), (R,)))
+    return kinds, R, rho, s, w
+
+
+def subset_propose_host(spec, kinds, rho, cur, first_chain=0, out=None, s=None, w=None):
+    """erpl_mc_subset_propose_host: the candidates of the chains first_chain .. first_chain + count - 1 whose current states are
+    the columns of the NumPy matrix cur [R, count] (unit column stride), for (spec.seed, spec.level, spec.step).  rho, s, w:
+    scalars or one per row; s defaults to sqrt(1 - rho^2), w to s.  Returns out (new, or the given [R, >= count] matrix)."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    kinds, R, rho, s, w = _subset_rows(kinds, rho, s, w)
+    rows, ld = _np_matrix(cur, np.float64, "cur")
+    count = int(cur.shape[-1])
+    if out is None:
+        out = np.empty((R, count), dtype=np.float64)
+    rows_o, ld_o = _np_matrix(out, np.float64, "out")
+    if rows != R or rows_o != R:
+        raise ValueError(f"cur and out must have {R} rows")
+    _abi.check(lib, lib.erpl_mc_subset_propose_host(C.byref(spec), kinds, _np_ptr(rho), _np_ptr(s), _np_ptr(w), R, _np_ptr(cur), ld,
+                                                    int(first_chain), count, _np_ptr(out), ld_o), "erpl_mc_subset_propose_host")
+    return out
+
+
+def subset_commit_host(threshold, g_cand, g_cur, g_next, triples=()):
+    """erpl_mc_subset_commit_host on NumPy arrays, in place: g_next and the `next` of every (cand, cur, next) triple take the
+    candidate's column where g_cand >= threshold and the current one otherwise.  Returns the number accepted."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    count = int(g_cand.shape[-1])
+    for a in (g_cand, g_cur, g_next):
+        _np_matrix(a, np.float64, "g_cand, g_cur and g_next")
+    slots = (_abi.ErplSubsetTriple * max(len(triples), 1))()
+    for q, (cand, cur, nxt) in enumerate(triples):
+        rows, ld_cand = _np_matrix(cand, cand.dtype, "a triple's cand")
+        rows_c, ld = _np_matrix(cur, cand.dtype, "a triple's cur")
+        rows_n, ld_n = _np_matrix(nxt, cand.dtype, "a triple's next")
+        if not (rows == rows_c == rows_n) or (rows > 1 and ld != ld_n):
+            raise ValueError("a triple's cand, cur and next: the same rows, cur and next the same leading dimension")
+        slots[q].cand, slots[q].cur, slots[q].next = cand.ctypes.data, cur.ctypes.data, nxt.ctypes.data
+        slots[q].ld_cand, slots[q].ld, slots[q].rows, slots[q].elem_size = ld_cand, ld, rows, cand.itemsize
+    thr, acc = C.c_double(float(threshold)), C.c_int64(0)
+    _abi.check(lib, lib.erpl_mc_subset_commit_host(C.byref(thr), _np_ptr(g_cand), _np_ptr(g_cur), _np_ptr(g_next), slots, len(triples),
+                                                   count, C.byref(acc)), "erpl_mc_subset_commit_host")
+    return int(acc.value)
+
+
+def subset_chain_stats_host(selected, chains, steps):
+    """erpl_mc_subset_chain_stats_host: (n1, pair int64 [steps - 1]) of the step-major indicator bytes [steps * chains]."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    selected = np.ascontiguousarray(selected, dtype=np.uint8)
+    if selected.size != int(chains) * int(steps):
+        raise ValueError("selected must hold steps * chains bytes")
+    n1, pair = C.c_int64(0), np.zeros(max(int(steps) - 1, 1), dtype=np.int64)
+    _abi.check(lib, lib.erpl_mc_subset_chain_stats_host(_np_ptr(selected), int(chains), int(steps), C.byref(n1), _np_ptr(pair)),
+               "erpl_mc_subset_chain_stats_host")
+    return int(n1.value), pair[:int(steps) - 1]
+
+
+def subset_delta(n1, pair, chains, steps, chained):
+    """(p, delta, gamma) of a level from its chain statistics (Au & Beck 2001): p = n1 / N, R(k) = pair[k - 1] / (N - k C) - p^2,
+    gamma = 2 sum_k (1 - k / T) R(k) / (p (1 - p)) (0 for chained=False, level 0), delta^2 = (1 - p) / (p N) (1 + gamma)."""
+    C_, T = int(chains), int(steps)
+    N = C_ * T
+    p = n1 / N
+    gamma = 0.0
+    if chained and 0 < n1 < N and T > 1:
+        k = np.arange(1, T, dtype=np.float64)
+        Rk = np.asarray(pair, dtype=np.float64) / (N - k * C_) - p * p
+        gamma = float(2.0 * np.sum((1.0 - k / T) * Rk) / (p * (1.0 - p)))
+    delta2 = (1.0 - p) / (p * N) * (1.0 + gamma) if n1 > 0 else float("nan")
+    return p, math.sqrt(max(delta2, 0.0)) if delta2 == delta2 else float("nan"), gamma
+
+
+class _SubsetHost:
+    """The steps of a level on NumPy arrays (the _host calls)."""
+    def empty(self, rows, n, like):
+        return np.empty((rows, n) if rows else (n,), dtype=like.dtype)
+
+    def check(self, a, shape, dtype, what):
+        if not (isinstance(a, np.ndarray) and a.dtype == dtype and tuple(a.shape) == shape):
+            raise ValueError(f"{what} must be a {np.dtype(dtype).name} NumPy array of shape {shape}")
+        return np.ascontiguousarray(a)
+
+    def seeds(self, g, n_seeds, gathers):
+        _, sel, thr, alive = subset_seeds_host(g, n_seeds, gathers)
+        return sel, thr, alive
+
+    def alive(self, g):
+        return int(np.count_nonzero(g > -np.inf))
+
+    def indicator(self, g, threshold):
+        return subset_seeds_host(g, 0, threshold=threshold)[1]
+
+    def propose(self, spec, kinds, rho, s, w, cur, cand):
+        subset_propose_host(spec, kinds, rho, cur, 0, cand, s, w)
+
+    def begin_level(self, threshold):
+        self.threshold, self.accepted = threshold, 0
+
+    def commit(self, g_cand, g_cur, g_next, triples):
+        self.accepted += subset_commit_host(self.threshold, g_cand, g_cur, g_next, triples)
+
+    def chain_stats(self, sel, chains, steps):
+        return subset_chain_stats_host(sel, chains, steps)
+
+    def read_accepted(self):
+        return self.accepted
+
+    def numpy(self, a):
+        return np.array(a, copy=True)
+
+
+class _SubsetDevice:
+    """The steps of a level on device tensors (TrajectoryEngine.subset_*); the accept count stays on the device for a level."""
+    def __init__(self, engine):
+        import torch
+        self.eng, self.torch = engine, torch
+        self.acc = torch.zeros(1, dtype=torch.int64, device=engine.device)
+
+    def empty(self, rows, n, like):
+        return self.torch.empty((rows, n) if rows else (n,), dtype=like.dtype, device=self.eng.device)
+
+    def check(self, a, shape, dtype, what):
+        tdt = {np.float64: self.torch.float64, np.int32: self.torch.int32}[dtype]
+        if not (self.torch.is_tensor(a) and a.device == self.eng.device and a.dtype == tdt and tuple(a.shape) == shape):
+            raise ValueError(f"{what} must be a {np.dtype(dtype).name} tensor of shape {shape} on {self.eng.device}")
+        return a.contiguous()
+
+    def seeds(self, g, n_seeds, gathers):
+        _, sel, thr, alive = self.eng.subset_seeds(g, n_seeds, gathers)
+        both = self.torch.stack([thr, alive.to(self.torch.float64)]).cpu()   # one wait for the two words (alive < 2^31: exact)
+        return sel, float(both[0]), int(both[1])
+
+    def alive(self, g):
+        return int((g > -math.inf).sum())
+
+    def indicator(self, g, threshold):
+        thr = self.torch.tensor(float(threshold), dtype=self.torch.float64, device=self.eng.device)
+        return self.eng.subset_seeds(g, 0, threshold=thr)[1]
+
+    def propose(self, spec, kinds, rho, s, w, cur, cand):
+        self.eng.subset_propose(spec, kinds, rho, cur, 0, cand, s, w)
+
+    def begin_level(self, threshold):
+        self.threshold = self.torch.tensor(float(threshold), dtype=self.torch.float64, device=self.eng.device)
+        self.acc.zero_()
+
+    def commit(self, g_cand, g_cur, g_next, triples):
+        self.eng.subset_commit(self.threshold, g_cand, g_cur, g_next, triples, self.acc)
+
+    def chain_stats(self, sel, chains, steps):
+        n1, pair = self.eng.subset_chain_stats(sel, chains, steps)
+        both = self.torch.cat([n1.view(1), pair]).cpu().numpy()
+        return int(both[0]), both[1:]
+
+    def read_accepted(self):
+        return int(self.acc)
+
+    def numpy(self, a):
+        return a.cpu().numpy()
+
+
+def _subset_level_rows(value, level, R, what):
+    """rho or width of chain level `level` (1-based): a scalar, one value per level (the last one repeats) or [levels][R]."""
+    a = np.asarray(value, dtype=np.float64)
+    if a.ndim == 0:
+        return np.full(R, float(a))
+    a = a[min(level - 1, a.shape[0] - 1)]
+    if a.ndim == 0:
+        return np.full(R, float(a))
+    if a.shape != (R,):
+        raise ValueError(f"{what}: a scalar, one value per level or [levels][{R}]")
+    return np.ascontiguousarray(a)
+
+
+def subset_simulation(evaluate, draws0, kinds, *, chains, steps, target=None, max_levels=12, rho=0.8, width=None, seed=0,
+                      engine=None, interval_level=0.95, curve_points=256):
+    """Subset simulation (Au & Beck 2001, with the conditional-sampling proposal of Papaioannou et al. 2015) of P(g > target)
+    over ANY evaluator, through the five steps of erpl_mc_subset_*.
+
+    evaluate(draws [R, c]) -> g [c], or (g, summary [16, c] or None, status int32 [c] or None); it is called once with the
+    N = chains * steps columns of level 0 and then with `chains` candidates per round.  draws0: the float64 [R, N] primitives
+    of level 0 under the independent law - a device tensor (the device calls of `engine`, default the shared one; evaluate
+    gets and returns device tensors) or a NumPy array (the _host calls).  kinds: one _abi.DESIGN_NORMAL / DESIGN_UNIFORM per
+    row.  A NaN g counts as -inf.
+
+    Every level selects the `chains` samples that went furthest as seeds (their g's smallest is the level's threshold) and
+    grows each into a chain of `steps` states by steps - 1 rounds of propose -> evaluate -> commit.  The run stops at the
+    first level whose threshold reaches `target`: the last factor is the share of that level's population with g >= target.
+    Otherwise it stops after max_levels thresholds (with a target: the last factor is the share in the population grown
+    from the last threshold, and 'reached' is False; target=None: P is that of the last threshold).  rho: the correlation of
+    the proposal on normal rows - a scalar, one value per level or [levels][R]; width: the step of the uniform rows, likewise,
+    default sqrt(1 - rho^2).
+
+    Returns a dict: 'probability', 'cov' (Au & Beck's sqrt(sum delta_l^2): it ignores the correlation between levels and runs
+    low - 0.18 estimated against 0.20 observed at 1e-6), 'interval' (log-normal, at interval_level), 'reached', 'levels' (one
+    dict per factor: 'threshold', 'p', 'delta', 'gamma', 'n1', and 'acceptance': the share of the candidates that the chains
+    grown from this threshold accepted, None where none were grown), 'thresholds', 'curve' (float64 [m, 2]: x
+    ascending and P(g >= x), stitched from all levels down to the last population's largest g), 'curve_cov' (per point the
+    c.o.v. of the factors its level is conditioned on: the band of the curve, without the binomial part), 'population' ('draws',
+    'summary', 'status', 'g', 'indicator': the last level's population, step-major; with a target the indicator marks
+    the failure sample), 'level0' ('g', 'summary', 'status' as evaluate returned them for draws0), 'evaluations' (columns
+    handed to evaluate: N + (steps - 1) * chains per further level) and 'samples' (populations held x N).
+    'warnings': a list of texts, empty for a healthy run - a level whose chains accepted under 1 % of their candidates, or whose
+    threshold does not exceed the one before: the chains do not move (a failure region that is an island in the space of the
+    primitives is not reached by local steps), and then NEITHER the probability NOR its c.o.v. is to be trusted.
+    A level with fewer than `chains` samples of g > -inf has died out: ValueError at level 0, before any proposal, and
+    _abi.ErplError later."""
+    from . import _abi
+    from scipy.special import ndtri
+    C_, T = int(chains), int(steps)
+    if C_ < 1 or not 1 <= T <= _abi.SUBSET_MAX_STEPS:
+        raise ValueError(f"chains >= 1 and 1 <= steps <= {_abi.SUBSET_MAX_STEPS}")
+    N, max_levels = C_ * T, int(max_levels)
+    if max_levels < 1:
+        raise ValueError("max_levels >= 1")
+    kinds = bytes(bytearray(int(k) for k in kinds))
+    R = len(kinds)
+    if isinstance(draws0, np.ndarray):
+        be = _SubsetHost()
+    else:
+        if engine is None:
+            from .simulator import shared_engine
+            engine = shared_engine(draws0.device)
+        be = _SubsetDevice(engine)
+    pop = be.check(draws0, (R, N), np.float64, "draws0")
+
+    def call(x, c):
+        out = evaluate(x)
+        g, summ, st = out if isinstance(out, tuple) else (out, None, None)
+        g = be.check(g, (c,), np.float64, "g of evaluate")
+        summ = None if summ is None else be.check(summ, (_abi.SUMMARY_DIM, c), np.float64, "summary of evaluate")
+        st = None if st is None else be.check(st, (c,), np.int32, "status of evaluate")
+        return g, summ, st
+
+    g, summ, status = call(pop, N)
+    level0 = {"g": g, "summary": summ, "status": status}
+    evaluations, populations = N, 1
+    alive0 = be.alive(g)
+    if alive0 < C_:
+        raise ValueError(f"level 0 holds {alive0} valid samples (g > -inf), fewer than chains = {C_}")
+    nxt, g_nxt = be.empty(R, N, pop), be.empty(0, N, g)
+    summ_nxt = None if summ is None else be.empty(_abi.SUMMARY_DIM, N, summ)
+    status_nxt = None if status is None else be.empty(0, N, status)
+    cand = be.empty(R, C_, pop)
+    levels, curve, P, reached, sel = [], [], 1.0, False, None
+    z = float(ndtri(0.5 + 0.5 * float(interval_level)))
+
+    def factor(sel, threshold, chained):
+        n1, pair = be.chain_stats(sel, C_, T)
+        p, delta, gamma = subset_delta(n1, pair, C_, T, chained)
+        levels.append({"threshold": float(threshold), "p": p, "delta": delta, "gamma": gamma, "acceptance": None, "n1": n1})
+        return p
+
+    def stitch(g_host, P_level, upto):
+        """The points of this level's population below `upto` (None: all): x ascending, P(g >= x) = P_level * share."""
+        x = np.sort(g_host[g_host > -np.inf])
+        share = (x.size - np.arange(x.size)) / N
+        keep = np.ones(x.size, dtype=bool) if upto is None else x < upto
+        x, share = x[keep], share[keep]
+        if x.size > curve_points:
+            pick = np.unique(np.linspace(0, x.size - 1, curve_points).round().astype(np.int64))
+            x, share = x[pick], share[pick]
+        before = math.sqrt(sum(lv["delta"] ** 2 for lv in levels))      # of the factors that condition this level
+        curve.append(np.column_stack([x, P_level * share, np.full(x.size, before)]))
+
+    for level in range(max_levels + 1):
+        if level == max_levels:   # no threshold reached the target (or none was asked for): the population of the last one
+            if target is not None:
+                sel = be.indicator(g, target)
+                P_before = P
+                P *= factor(sel, target, True)
+                stitch(be.numpy(g), P_before, None)
+            else:
+                sel = be.indicator(g, -math.inf)
+                stitch(be.numpy(g), P, None)
+            break
+        gathers = [(pop, nxt), (g, g_nxt)]
+        if summ is not None:
+            gathers.append((summ, summ_nxt))
+        if status is not None:
+            gathers.append((status, status_nxt))
+        sel, thr, alive = be.seeds(g, C_, gathers)
+        if alive < C_:
+            raise _abi.ErplError(f"subset simulation: level {level} has died out ({alive} samples with g > -inf, {C_} seeds needed)")
+        if target is not None and thr >= target:
+            sel = be.indicator(g, target)
+            P_before = P
+            P *= factor(sel, target, level > 0)
+            stitch(be.numpy(g), P_before, None)
+            reached = True
+            break
+        stitch(be.numpy(g), P, thr)
+        P *= factor(sel, thr, level > 0)
+        rho_l = _subset_level_rows(rho, level + 1, R, "rho")
+        s_l = np.sqrt(1.0 - rho_l * rho_l)
+        w_l = s_l if width is None else _subset_level_rows(width, level + 1, R, "width")
+        be.begin_level(thr)
+        spec = subset_spec(seed=seed, level=level + 1)
+        for t in range(1, T):
+            spec.step = t
+            a, b = (t - 1) * C_, t * C_
+            be.propose(spec, kinds, rho_l, s_l, w_l, nxt[:, a:b], cand)
+            gc, sc, stc = call(cand, C_)
+            evaluations += C_
+            triples = [(cand, nxt[:, a:b], nxt[:, b:b + C_])]
+            if summ is not None:
+                triples.append((sc, summ_nxt[:, a:b], summ_nxt[:, b:b + C_]))
+            if status is not None:
+                triples.append((stc, status_nxt[a:b], status_nxt[b:b + C_]))
+            be.commit(gc, g_nxt[a:b], g_nxt[b:b + C_], triples)
+        levels[-1]["acceptance"] = be.read_accepted() / (C_ * (T - 1)) if T > 1 else None
+        if level == 0:   # level 0 is the caller's (draws0) and the result's ('level0'): the chains never write into it
+            pop, g, summ, status = be.empty(R, N, pop), be.empty(0, N, g), None if summ is None else be.empty(_abi.SUMMARY_DIM, N, summ), \
+                None if status is None else be.empty(0, N, status)
+        pop, nxt, g, g_nxt = nxt, pop, g_nxt, g
+        summ, summ_nxt, status, status_nxt = summ_nxt, summ, status_nxt, status
+        populations += 1
+    # What the estimate cannot see by itself: chains that do not move.  A failure region that is an island in the space of
+    # the primitives (a second mode the bulk does not lead to) is not reached by local steps; the levels then slice one frozen
+    # sample ever thinner, P falls by p0 per level and delta stays small.
+    warnings = []
+    for l, lv in enumerate(levels):
+        if lv["acceptance"] is not None and lv["acceptance"] < 0.01:
+            warnings.append(f"level {l}: the chains grown from the threshold {lv['threshold']:.6g} accepted {lv['acceptance']:.2g} of "
+                            "their candidates - they do not move; the probability and its c.o.v. are not to be trusted "
+                            "(a larger rho takes smaller steps; a failure mode the bulk does not lead to needs direct sampling)")
+        if 0 < l < len(levels) - (1 if target is not None else 0) and lv["threshold"] <= levels[l - 1]["threshold"]:
+            warnings.append(f"level {l}: the threshold {lv['threshold']:.6g} does not exceed the one before - the seeds are copies")
+    cov = math.sqrt(sum(lv["delta"] ** 2 for lv in levels)) if levels else 0.0
+    sigma = math.sqrt(math.log1p(cov * cov)) if cov == cov else float("nan")
+    return {"probability": P, "cov": cov, "interval": (P * math.exp(-z * sigma), P * math.exp(z * sigma)),
+            "interval_level": float(interval_level), "reached": reached, "target": target, "levels": levels,
+            "thresholds": [lv["threshold"] for lv in levels], "curve": np.concatenate(curve)[:, :2], "curve_cov": np.concatenate(curve)[:, 2],
+            "population": {"draws": pop, "summary": summ, "status": status, "g": g, "indicator": sel}, "level0": level0,
+            "chains": C_, "steps": T, "evaluations": evaluations, "samples": populations * N, "warnings": warnings}

@@ -471,6 +471,9 @@ int erpl_mc_destroy(erpl_ctx* c) {
   if (c->design_flag) (void)hipHostFree(c->design_flag);
   if (c->design_ev) (void)hipEventDestroy(c->design_ev);
   c->tally.release();
+  c->subset.release();
+  if (c->subset_pin) (void)hipHostFree(c->subset_pin);
+  if (c->subset_ev) (void)hipEventDestroy(c->subset_ev);
   delete c;
   return ERPL_OK;
 }

@@ -1,5 +1,5 @@
 // erpl_host.h — what the host units of the C ABI share (erpl_api.hip, erpl_sampling.hip, erpl_stats_api.hip,
-// erpl_legacy_device.hip, erpl_design.hip, erpl_tally.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
+// erpl_legacy_device.hip, erpl_design.hip, erpl_tally.hip, erpl_subset.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
 // Internal, never installed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -250,6 +250,11 @@ struct erpl_ctx {
   // erpl_mc_tally_*: the device workspace of erpl_tally.hip (the spec, the candidate lists of the extremes) in the buffer, the
   // spec that is on the device in the pinned mirror
   ErplStatUnit<void, erpl_tally_spec> tally;
+  // erpl_mc_subset_*: the device workspace of erpl_subset.hip (the state of a selection, the rows' parameters of a proposal,
+  // the tile counts of the compaction) in the buffer; the pinned staging of the parameters and the event behind its latest copy
+  ErplStatUnit<void, char> subset;
+  char* subset_pin = nullptr;
+  hipEvent_t subset_ev = nullptr;
 };
 
 // erpl_design.hip

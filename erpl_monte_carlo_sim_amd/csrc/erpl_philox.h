@@ -11,6 +11,8 @@
 //   index    (u * m) >> 64 of a 64-bit draw u: a dense population index below m, bias at most m / 2^64
 //   label    erpl_mc_compare: the key of pooled member i in permutation p is draw i of replicate p; side A is the m_a members
 //            with the smallest (key, i) pairs.  With (thr_key, thr_idx) the m_a-th smallest pair, the label is one comparison.
+// Counter word 3 is a TAG that keeps the families apart: 0 the bootstrap family above, 1 the jitter and 2 the round keys of
+// erpl_mc_design (erpl_design.h), 3 the proposals of erpl_mc_subset_propose (erpl_subset.h).
 #pragma once
 #include <stdint.h>
 

@@ -762,6 +762,128 @@ class TrajectoryEngine:
                    C.c_void_p(st.cuda_stream))
         return out
 
+    # ---- subset simulation (erpl_mc_subset_*): the five steps of a level on device tensors; analysis.subset_simulation drives them
+    def _matrix(self, t, what):
+        """A device matrix the subset calls read or write in place: 1-D or 2-D with unit column stride.  (rows, ld, bytes)."""
+        if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dim() in (1, 2)
+                and (t.shape[-1] <= 1 or t.stride(-1) == 1) and t.element_size() in (1, 4, 8)):
+            raise ValueError(f"{what} must be a 1-D or 2-D tensor on {self.device} with unit column stride and 1, 4 or 8 byte elements")
+        if t.dim() == 1 or t.shape[0] == 1:
+            return 1, max(int(t.shape[-1]), 1), t.element_size()
+        if t.stride(0) < t.shape[1]:
+            raise ValueError(f"{what}: rows must not overlap")
+        return int(t.shape[0]), int(t.stride(0)), t.element_size()
+
+    def _vector(self, t, n, dtype, what):
+        if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype == dtype and t.dim() == 1
+                and t.shape[0] == n and (n <= 1 or t.stride(0) == 1)):
+            raise ValueError(f"{what} must be a {dtype} [{n}] tensor on {self.device} with unit stride")
+        return C.c_void_p(t.data_ptr())
+
+    def subset_limit_state(self, spec, summary, status=None, out=None):
+        """erpl_mc_subset_limit_state: g [n] of the summary [16, n] (unit column stride) / status [n] under `spec`
+        (analysis.subset_spec).  Asynchronous on the current stream."""
+        rows, ld, _ = self._matrix(summary, "summary")
+        n = int(summary.shape[1])
+        if rows != _abi.SUMMARY_DIM or summary.dtype != torch.float64:
+            raise ValueError(f"summary must be float64 [{_abi.SUMMARY_DIM}, n]")
+        g = torch.empty(n, dtype=torch.float64, device=self.device) if out is None else out
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_subset_limit_state", C.byref(spec), C.c_void_p(summary.data_ptr()),
+                   None if status is None else self._vector(status, n, torch.int32, "status"), ld, n,
+                   self._vector(g, n, torch.float64, "out"), C.c_void_p(st.cuda_stream))
+        return g
+
+    def subset_seeds(self, g, n_seeds, gathers=(), threshold=None):
+        """erpl_mc_subset_seeds: the n_seeds samples of g [n] that went furthest, ties to the lower id.  gathers: up to 4
+        (src, dst) pairs of device matrices [rows, n] / [rows, >= n_seeds] (or vectors) of one dtype; the selected columns of
+        src go, ascending in id, to columns 0 .. n_seeds - 1 of dst.  Returns (idx int32 [n_seeds], selected uint8 [n],
+        threshold float64 [], n_alive int64 []) on the device, asynchronously: a caller compares n_alive with n_seeds (a level
+        with fewer samples of g > -inf has died out).  n_seeds = 0: only the indicator of the given device `threshold` and,
+        in n_alive, its count."""
+        n, n_seeds = int(g.shape[0]), int(n_seeds)
+        gp = self._vector(g, n, torch.float64, "g")
+        idx = torch.empty(max(n_seeds, 1), dtype=torch.int32, device=self.device)
+        sel = torch.empty(n, dtype=torch.uint8, device=self.device)
+        thr = torch.zeros((), dtype=torch.float64, device=self.device) if threshold is None else threshold
+        if not (torch.is_tensor(thr) and thr.device == self.device and thr.dtype == torch.float64 and thr.numel() == 1):
+            raise ValueError("threshold must be a float64 device tensor of one element")
+        alive = torch.zeros((), dtype=torch.int64, device=self.device)
+        slots = (_abi.ErplSubsetGather * max(len(gathers), 1))()
+        for q, (src, dst) in enumerate(gathers):
+            rows, ld_src, size = self._matrix(src, "a gather's src")
+            rows_d, ld_dst, size_d = self._matrix(dst, "a gather's dst")
+            if rows != rows_d or src.dtype != dst.dtype or src.shape[-1] != n or dst.shape[-1] < n_seeds:
+                raise ValueError("a gather's src [rows, n] and dst [rows, >= n_seeds]: the same rows and dtype")
+            slots[q].src, slots[q].dst, slots[q].ld_src, slots[q].ld_dst = src.data_ptr(), dst.data_ptr(), ld_src, ld_dst
+            slots[q].rows, slots[q].elem_size = rows, size
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_subset_seeds", gp, n, n_seeds, C.c_void_p(idx.data_ptr()), C.c_void_p(sel.data_ptr()),
+                   C.c_void_p(thr.data_ptr()), C.c_void_p(alive.data_ptr()), slots, len(gathers), C.c_void_p(st.cuda_stream))
+        return idx[:n_seeds], sel, thr, alive
+
+    def subset_propose(self, spec, kinds, rho, cur, first_chain=0, out=None, s=None, w=None):
+        """erpl_mc_subset_propose: the candidates of the chains first_chain .. first_chain + count - 1 whose current states are
+        the columns of the device matrix cur [R, count] (unit column stride; a block of a step-major population is fine),
+        for (spec.seed, spec.level, spec.step).  kinds: one _abi.DESIGN_NORMAL / DESIGN_UNIFORM per row; rho, s, w: scalars
+        or one per row (host values); s defaults to sqrt(1 - rho^2), w to s.  Returns out (new, or the given [R, >= count]
+        matrix).  Asynchronous on the current stream."""
+        from .analysis import _subset_rows
+        kinds, R, rho, s, w = _subset_rows(kinds, rho, s, w)
+        rows, ld, _ = self._matrix(cur, "cur")
+        count = int(cur.shape[-1])
+        if out is None:
+            out = torch.empty((R, count), dtype=torch.float64, device=self.device)
+        rows_o, ld_o, _ = self._matrix(out, "out")
+        if rows != R or rows_o != R or cur.dtype != torch.float64 or out.dtype != torch.float64 or out.shape[-1] < count:
+            raise ValueError(f"cur and out must be float64 matrices of {R} rows, out with at least {count} columns")
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_subset_propose", C.byref(spec), kinds, C.c_void_p(rho.ctypes.data), C.c_void_p(s.ctypes.data),
+                   C.c_void_p(w.ctypes.data), R, C.c_void_p(cur.data_ptr()), ld, int(first_chain), count, C.c_void_p(out.data_ptr()),
+                   ld_o, C.c_void_p(st.cuda_stream))
+        return out
+
+    def subset_commit(self, threshold, g_cand, g_cur, g_next, triples=(), n_accepted=None):
+        """erpl_mc_subset_commit, in place: g_next [count] and the `next` of every (cand, cur, next) triple of device matrices
+        ([rows, count], or vectors; one dtype per triple) take the candidate's column where g_cand >= threshold (a float64
+        device tensor of one element) and the current one otherwise.  The number accepted is added to n_accepted (an int64
+        device tensor of one element; None: a new zero), which is returned.  Asynchronous on the current stream."""
+        count = int(g_cand.shape[0])
+        if n_accepted is None:
+            n_accepted = torch.zeros((), dtype=torch.int64, device=self.device)
+        if not (torch.is_tensor(threshold) and threshold.device == self.device and threshold.dtype == torch.float64
+                and threshold.numel() == 1 and n_accepted.device == self.device and n_accepted.dtype == torch.int64
+                and n_accepted.numel() == 1):
+            raise ValueError("threshold: a float64 and n_accepted: an int64 device tensor of one element")
+        slots = (_abi.ErplSubsetTriple * max(len(triples), 1))()
+        for q, (cand, cur, nxt) in enumerate(triples):
+            rows, ld_cand, size = self._matrix(cand, "a triple's cand")
+            rows_c, ld, _ = self._matrix(cur, "a triple's cur")
+            rows_n, ld_n, _ = self._matrix(nxt, "a triple's next")
+            if not (rows == rows_c == rows_n and cand.dtype == cur.dtype == nxt.dtype and (rows == 1 or ld == ld_n)
+                    and cand.shape[-1] >= count and cur.shape[-1] >= count and nxt.shape[-1] >= count):
+                raise ValueError("a triple's cand, cur and next: the same rows and dtype, at least count columns, cur and next "
+                                 "the same leading dimension")
+            slots[q].cand, slots[q].cur, slots[q].next = cand.data_ptr(), cur.data_ptr(), nxt.data_ptr()
+            slots[q].ld_cand, slots[q].ld, slots[q].rows, slots[q].elem_size = ld_cand, ld, rows, size
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_subset_commit", C.c_void_p(threshold.data_ptr()), self._vector(g_cand, count, torch.float64, "g_cand"),
+                   self._vector(g_cur, count, torch.float64, "g_cur"), self._vector(g_next, count, torch.float64, "g_next"),
+                   slots, len(triples), count, C.c_void_p(n_accepted.data_ptr()), C.c_void_p(st.cuda_stream))
+        return n_accepted
+
+    def subset_chain_stats(self, selected, chains, steps):
+        """erpl_mc_subset_chain_stats of the step-major indicator bytes [steps * chains]: (n1 int64 [], pair int64 [steps - 1])
+        on the device, asynchronously; analysis.subset_delta makes p, delta and gamma of them."""
+        chains, steps = int(chains), int(steps)
+        sp = self._vector(selected, chains * steps, torch.uint8, "selected")
+        n1 = torch.zeros((), dtype=torch.int64, device=self.device)
+        pair = torch.zeros(max(steps - 1, 1), dtype=torch.int64, device=self.device)
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_subset_chain_stats", sp, chains, steps, C.c_void_p(n1.data_ptr()), C.c_void_p(pair.data_ptr()),
+                   C.c_void_p(st.cuda_stream))
+        return n1, pair[:steps - 1]
+
     # ---- the tally (erpl_mc_tally_*): a run of any length folded into a fixed-size int64 state on the device
     def tally_new(self, spec=None):
         """(spec, state): an empty tally of `spec` (analysis.tally_spec; None: the library's defaults) - the state is a

@@ -9,6 +9,7 @@ motor perturbation stay on the host, the per-sample wind tables are built on the
 (`wind_on_device`; on the host without it); all are bit-identical to the reference (flatten.py);
 the integration itself runs only on the GPU.
 """
+import math
 import os
 import time
 
@@ -553,6 +554,107 @@ class MonteCarloAnalyzer:
         summ, status, traj, tlen = eng.run(db, traj_ids=np.arange(len(ids)), traj_stride=stride, traj_cap=cap)
         eng.synchronize()
         return {"ids": ids, "summary": summ, "status": status, "traj": traj, "traj_len": tlen, "stride": stride}
+
+    def rare_event(self, initial_conditions, n_per_level=131072, p0=0.125, row="range", tail="upper", target=None, centre=None,
+                   max_levels=12, rho=0.8, seed=1234, precision="f64_fast", planar=False, design="random", bounds=None):
+        """P(row > target) at the 1e-5 .. 1e-7 level by subset simulation (analysis.subset_simulation over flights) instead of
+        the 10^8 - 10^9 flights a tally needs: level 0 is the design run of n_per_level flights (`sampling.design_draws` at
+        `seed`, the INDEPENDENT law of `synthetic_dispersions(draws=...)`, bit for bit the flights of
+        `run_monte_carlo_device(design=design)`), every further level keeps the n_per_level * p0 flights that went furthest
+        and grows each into a chain of 1 / p0 states whose candidates are flown in sub-batches of DEVICE_CHUNK.
+        row / tail / centre: the limit state g - a summary row (ROW_NAMES or index), its 'upper' or 'lower' tail (g = -row),
+        or with centre=(cx, cy) the miss distance of the impact point; a flight the outlier filter drops never counts
+        (g = -inf).  target: in units of g (a lower tail: minus the value); None: max_levels levels and the curve down to
+        p0^max_levels.  rho: the correlation of the proposal (scalar, per level or [levels][rows]).  bounds: the filter's
+        bounds where they are not the defaults (the dict of TrajectoryEngine.analyze, e.g. {'max_range': 20000.0}).
+        READ 'warnings' (printed when verbose): subset simulation reaches a tail that the bulk leads to by small steps.  Where the
+        tail is a separate mode - the planar set's ranges beyond 60 km are freak flights, an island among the primitives - the
+        chains stop moving (acceptance near 0), the levels slice one frozen sample, and the estimate falls below the truth by
+        orders of magnitude with a small c.o.v.; such a tail needs `run_monte_carlo_tally`.
+        ValueError before any work: 1 / p0 no integer >= 2, n_per_level * p0 no integer, a world size above 1 (the chains
+        of a level are not split across ranks).
+        Returns the dict of analysis.subset_simulation ('probability', 'cov', 'interval', 'levels', 'curve', 'population',
+        'level0', 'evaluations', 'warnings', ...) plus 'conditional_inputs': for every scalar primitive of `sampling.scalar_primitives`
+        its {'mean', 'std'} over the failure sample (the last population's columns with indicator 1), next to the (0, 1) of
+        a normal and the (0.5, 0.289) of a uniform under the unconditional law - which input a failing flight needs;
+        'spec', 'seed', 'precision', 'planar', 'design', 'kinds' and 'performance'.
+        The primitives of the failure sample are returned (population['draws'], float64 [17 + 3 K + 2, n_per_level] on the
+        device), so the failures can be flown again with capture, as `refly` does for a design run:
+        `db = sampling.synthetic_dispersions(m, ..., draws=population['draws'][:, cols].contiguous())`, then
+        `eng.run(db, traj_ids=np.arange(m), traj_stride=stride, traj_cap=cap)`."""
+        from . import sampling
+        steps = int(round(1.0 / float(p0)))
+        if steps < 2 or abs(steps * float(p0) - 1.0) > 1e-12:
+            raise ValueError(f"p0 = {p0}: 1 / p0 must be an integer >= 2")
+        n_per_level = int(n_per_level)
+        if n_per_level < steps or n_per_level % steps != 0:
+            raise ValueError(f"n_per_level * p0 = {n_per_level} / {steps} must be an integer >= 1")
+        if dist.world()[1] > 1:
+            raise ValueError("rare_event is limited to a world size of 1: the chains of a level are not split across ranks")
+        if design not in _abi.DESIGN_KINDS:
+            raise ValueError(f"design: one of {list(_abi.DESIGN_KINDS)}")
+        chains = n_per_level // steps
+        eng = shared_engine(self.device)
+        eng.set_config(self._config())
+        prec = _abi.PRECISIONS[precision]
+        use_base = self.base_wind_profile is not None and self.base_altitude_profile is not None
+        K = len(self.base_altitude_profile) if use_base else 100
+        kinds = [_abi.DESIGN_NORMAL] * (17 + 3 * K) + [_abi.DESIGN_UNIFORM] * 2
+        spec = analysis.subset_spec(row=row, tail=tail, centre=centre, bounds=bounds)
+        flown = [0]
+
+        def evaluate(draws):
+            """Flies the columns of `draws` in sub-batches of DEVICE_CHUNK; g from their summaries on the device."""
+            c = int(draws.shape[1])
+            parts, keep = [], []
+            for a in range(0, c, self.DEVICE_CHUNK):
+                cnt = min(self.DEVICE_CHUNK, c - a)
+                db = sampling.synthetic_dispersions(
+                    cnt, self.rocket, self.motor, self.wind_model, initial_conditions, eng.device, precision=prec, seed=seed,
+                    uncertainty=self.uncertainty_params, base_altitude_profile=self.base_altitude_profile,
+                    base_wind_profile=self.base_wind_profile, planar=planar, engine=eng, draws=draws[:, a:a + cnt].contiguous())
+                parts.append(eng.submit(db))
+                keep.append(db)                  # inputs outlive their batch
+            eng.wait()
+            eng.check()                          # host-blocking: only now may the inputs go back to the allocator
+            flown[0] += c
+            summ = parts[0][0] if len(parts) == 1 else torch.cat([p[0] for p in parts], dim=1)
+            status = parts[0][1] if len(parts) == 1 else torch.cat([p[1] for p in parts])
+            return eng.subset_limit_state(spec, summ, status), summ, status
+
+        torch.cuda.synchronize(eng.device)
+        t0 = time.time()
+        draws0 = sampling.design_draws(n_per_level, K, eng.device, seed, design=design, engine=eng)
+        out = analysis.subset_simulation(evaluate, draws0, kinds, chains=chains, steps=steps, target=target, max_levels=max_levels,
+                                         rho=rho, seed=seed, engine=eng)
+        if self.verbose:
+            for text in out["warnings"]:
+                print(f"rare_event: {text}")
+        pop = out["population"]
+        fail = pop["indicator"].bool()
+        n_fail = int(fail.sum())
+        cond = {}
+        liquid = flatten.motor_kind(self.motor) != _abi.MOTOR_SOLID
+        for name, r in sampling.scalar_primitives(K, liquid).items():
+            x = pop["draws"][r][fail]
+            uniform = kinds[r] == _abi.DESIGN_UNIFORM
+            cond[name] = {"row": int(r), "mean": float(x.mean()) if n_fail else float("nan"),
+                          "std": float(x.std(unbiased=False)) if n_fail else float("nan"),
+                          "unconditional": (0.5, math.sqrt(1.0 / 12.0)) if uniform else (0.0, 1.0)}
+        torch.cuda.synchronize(eng.device)
+        t1 = time.time()
+        out.update({"conditional_inputs": cond, "n_failures": n_fail, "spec": spec, "seed": int(seed), "precision": precision,
+                    "planar": bool(planar), "design": design, "kinds": kinds, "n_per_level": n_per_level, "p0": 1.0 / steps,
+                    "row": analysis.ROW_NAMES[spec.row] if centre is None else "miss_distance", "tail": tail,
+                    "initial_conditions": dict(initial_conditions),
+                    "performance": {"total_time": t1 - t0, "evaluations": out["evaluations"], "flights": flown[0],
+                                    "flights_per_second": flown[0] / (t1 - t0), "precision": precision}})
+        return out
+
+    def plot_rare_event(self, result, save_plots=True, tally=None):
+        """The exceedance curve of `rare_event` on a log axis with its band and the level thresholds, optionally over the
+        exceedance of a tally run of the same row (plots.rare_event_figure)."""
+        return plots.plot_rare_event(self, result, save_plots, tally)
 
     def plot_exceedance(self, tally, row="range", save_plots=True, level=0.95):
         """The complementary distribution of a tallied row on a log axis, from the dict of `run_monte_carlo_tally`

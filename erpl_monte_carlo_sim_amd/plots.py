@@ -576,6 +576,53 @@ def exceedance_figure(tally, row="range", level=0.95):
     return fig
 
 
+def rare_event_figure(result, tally=None, row=None):
+    """The exceedance curve P(g >= x) of a subset simulation (the dict of analysis.subset_simulation /
+    MonteCarloAnalyzer.rare_event) on a log axis, down to its probability: the stitched curve, its log-normal band from the
+    c.o.v. of the factors each point is conditioned on ('curve_cov'; at the result's interval_level), the level thresholds as
+    dashed lines and the estimate itself with its interval at the target.  tally: optionally the dict of
+    `run_monte_carlo_tally` whose row `row` (default: the result's) is drawn under it as the steps of `exceedance_figure` -
+    direct Monte Carlo, where it still has counts.  A lower tail (g = -row) is drawn against g."""
+    from scipy.special import ndtri
+    curve = np.asarray(result["curve"], dtype=np.float64).reshape(-1, 2)
+    cov = np.asarray(result.get("curve_cov", np.zeros(len(curve))), dtype=np.float64)
+    z = float(ndtri(0.5 + 0.5 * float(result.get("interval_level", 0.95))))
+    name = row or result.get("row", "g")
+    fig = _figure((7.0, 4.5))
+    ax = fig.subplots(1, 1)
+    if tally is not None and name in tally.get("rows", {}):
+        r = tally["rows"][name]
+        count = int(r["count"])
+        edges = np.asarray(r["histogram"]["edges"], dtype=np.float64)
+        above = int(r["above"]) + np.concatenate([np.cumsum(np.asarray(r["histogram"]["counts"], dtype=np.int64)[::-1])[::-1], [0]])
+        have = above > 0
+        if count > 0 and have.any():
+            ax.step(edges[have], above[have] / count, where="post", color="tab:gray", label=f"direct Monte Carlo, {count} flights")
+    keep = curve[:, 1] > 0
+    if keep.any():
+        x, p = curve[keep, 0], curve[keep, 1]
+        spread = np.exp(z * np.sqrt(np.log1p(cov[keep] ** 2)))
+        ax.plot(x, p, color="tab:blue", label="subset simulation")
+        ax.fill_between(x, p / spread, p * spread, color="tab:blue", alpha=0.2,
+                        label=f"{100 * float(result.get('interval_level', 0.95)):.0f} % band")
+    for lv in result.get("levels", []):
+        ax.axvline(lv["threshold"], color="black", linewidth=0.6, linestyle="--")
+    P = float(result["probability"])
+    if result.get("target") is not None and P > 0:
+        lo, hi = result["interval"]
+        ax.errorbar([result["target"]], [P], yerr=[[P - lo], [hi - P]], fmt="o", color="tab:red", markersize=4, capsize=3,
+                    label=f"P = {P:.3g} (c.o.v. {result['cov']:.2f})")
+    ax.set_yscale("log")
+    ax.set_xlabel(name if result.get("tail", "upper") == "upper" else f"-{name}")
+    ax.set_ylabel("P(g >= x)")
+    ax.set_title(f"{name}: {len(result.get('levels', []))} levels, {int(result.get('evaluations', 0))} evaluations")
+    ax.grid(True, which="both", alpha=0.3)
+    if ax.get_legend_handles_labels()[0]:
+        ax.legend(loc="best", fontsize=8)
+    fig.tight_layout()
+    return fig
+
+
 def save_figure(fig, output_dir, name):
     path = os.path.join(output_dir, name)
     fig.savefig(path, dpi=DPI, bbox_inches="tight")
@@ -824,4 +871,16 @@ def plot_exceedance(analyzer, tally, row="range", save_plots=True, level=0.95):
     if save_plots:
         output_dir = analyzer._create_output_directory()
         print(f"Exceedance plot saved to: {save_figure(fig, output_dir, f'monte_carlo_exceedance_{row}.png')}")
+    return output_dir
+
+
+def plot_rare_event(analyzer, result, save_plots=True, tally=None):
+    """The exceedance curve of `MonteCarloAnalyzer.rare_event` (no reference counterpart) as monte_carlo_rare_event_<row>.png;
+    returns the output directory (None without save_plots)."""
+    fig = rare_event_figure(result, tally)
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        name = f"monte_carlo_rare_event_{result.get('row', 'g')}.png"
+        print(f"Rare-event plot saved to: {save_figure(fig, output_dir, name)}")
     return output_dir

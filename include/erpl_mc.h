@@ -1577,6 +1577,125 @@ int erpl_mc_tally_merge_host(const erpl_tally_spec* spec, int64_t* dst, const in
 int erpl_mc_tally_result_host(const erpl_tally_spec* spec, const int64_t* state, erpl_tally* result, int64_t* hist_counts,
                               int64_t* grid_counts);
 
+/* Subset simulation: rare-event probabilities P(g > x) of 1e-5 .. 1e-7 from some 10^5 - 10^6 flights instead of the
+ * 10^8 - 10^9 a tally needs (Au & Beck 2001; the conditional-sampling proposal in standard-normal space of Papaioannou et
+ * al. 2015).  P is written as a product of conditional probabilities; each is estimated by Markov chains that start from
+ * the samples of the level before that went furthest.  The library provides the five steps of a level; the loop over
+ * levels and the evaluation of the candidates (flying them) are the caller's (analysis.subset_simulation in Python).
+ *
+ * Layout: a level's population is a matrix [R][ld] of N = T * C columns, C chains of T steps, STEP-MAJOR: the column of
+ * step t of chain j is t * C + j, so that a round reads one contiguous block of C columns and writes the next.  The
+ * level's [16][N] summaries, its status words, its g and its indicator bytes are laid out alike.
+ * Limit state (erpl_mc_subset_limit_state): without a centre g = sign * summary[row]; with use_centre
+ * g = sign * sqrt(dx * dx + dy * dy), dx = IMPACT_X - cx, dy = IMPACT_Y - cy, one rounding per operation.  g = -inf where the
+ * sample carries a reason bit of erpl_mc_analyze (the five bounds of the spec), where its status word carries ERPL_ST_NAN
+ * or ERPL_ST_INCOMPLETE, or where the value is not finite.  A NaN g handed in by a caller counts as -inf below.
+ * Order: a is before b iff g_a > g_b, or g_a == g_b and id_a < id_b (the library's radix key of the bit pattern:
+ * -0.0 is below +0.0).  The seeds of a level are the first n_seeds samples in this order; `threshold` is the g of the last
+ * of them, selected[i] = 1 exactly for them, idx lists them ascending in id, and every listed matrix has its selected
+ * columns gathered, in that order, into columns 0 .. n_seeds - 1 of its dst (block 0 of the next level).  n_alive
+ * receives the number of samples with g > -inf.  Fewer than n_seeds of those: the level has died out - the _host call
+ * returns ERPL_ERR_INVALID and writes nothing but n_alive; the device call never waits, so it writes n_alive and a
+ * selection that takes -inf samples in id order, and ITS CALLER compares n_alive with n_seeds before going on.
+ * With n_seeds = 0 the call reads `threshold` instead and writes only selected[i] = (g_i >= threshold) and their count
+ * into n_alive: the indicator of the last level.
+ * Proposal (erpl_mc_subset_propose) for chain j (global: first_chain + the column of the call), row r, level l, step t:
+ * Philox4x32-10 with the key (seed & 0xffffffff, seed >> 32) on the counter (j >> 1, r | t << 16, l, 3); even j takes
+ * o0 | o1 << 32, odd j o2 | o3 << 32; u = ((draw >> 11) + 0.5) * 2^-53, the one u that rounds up to 1 taken as 1 - 2^-53.
+ * Tag 3 in counter word 3 keeps the stream apart from erpl_mc_bootstrap's family (0) and erpl_mc_design's (1, 2).
+ * A normal row gets x' = rho[r] * x + s[r] * PPND16(u) (AS 241, as erpl_mc_design), s[r] = sqrt(1 - rho[r]^2) computed by
+ * the caller; a uniform row v = x + w[r] * (u - 0.5), + 1 if v < 0, then - 1 if v >= 1, and where rounding leaves v <= 0 or
+ * v >= 1 the neighbouring double inside (0, 1): a symmetric step on the circle.  A window of chains equals those columns
+ * of the whole, bit for bit.  Host and device give the same bits on uniform rows; on normal rows, where PPND16 goes
+ * through the platform's log and sqrt, either side satisfies |x' - (rho x + s Phi^-1(u))| <= s * 8e-15 * max(1, |xi|) +
+ * 2^-50 * (|rho x| + |s xi|), xi = Phi^-1(u) (the bar of erpl_mc_design's normal rows plus the three roundings): host and
+ * device differ by at most twice that.
+ * Commit (erpl_mc_subset_commit): candidate c is accepted iff g_cand[c] >= *threshold (false for a NaN); g_next and
+ * the `next` column of every triple take the candidate's values if accepted and the current ones otherwise; the number
+ * accepted is ADDED to *n_accepted.
+ * Chain statistics (erpl_mc_subset_chain_stats) of an indicator I (a byte per column, counted as I != 0): n1 = sum I and,
+ * for k = 1 .. T - 1, pair[k - 1] = sum over chains j and steps t < T - k of I[t C + j] * I[(t + k) C + j].  On the host,
+ * with p = n1 / N: R(k) = pair[k - 1] / (N - k C) - p^2, gamma = 2 sum_k (1 - k / T) R(k) / (p (1 - p)),
+ * delta^2 = (1 - p) / (p N) (1 + gamma) (gamma = 0 at level 0), P = prod p_l, c.o.v. = sqrt(sum delta_l^2): Au & Beck's
+ * estimate.  It ignores the correlation between levels and runs low (0.18 estimated against 0.20 observed at 1e-6).
+ *
+ * The device calls take CALLER-OWNED device memory (kinds, rho, s, w and every spec are host memory), enqueue on
+ * `hip_stream` and return without waiting; their workspace belongs to the context (it grows with n and is freed by
+ * erpl_mc_destroy); calls on one context are serialised by the caller.  They use integer atomics only and are bitwise
+ * repeatable.  The _host calls are the same rule on host memory: no context, no device.
+ * Errors: ERPL_ERR_INVALID, before any device work and with a message that names the argument, in this order -
+ * limit_state: NULL spec / summary / g, a NaN bound, row outside 0..15, sign other than +1 / -1, a non-finite centre with
+ *   use_centre, n < 1 or n > 2^31 - 1, ld < n;
+ * seeds: NULL g / selected / threshold / n_alive, n < 1 or n > 2^31 - 1, n_seeds < 0 or > n, NULL idx with n_seeds > 0,
+ *   n_gathers outside 0..4 (or > 0 with n_seeds = 0), a NULL gathers, then per gather a NULL src / dst, rows outside
+ *   1..4096, an elem_size other than 1, 4 or 8, ld_src < n, ld_dst < n_seeds; "the level has died out" (host only);
+ * propose: NULL spec / kinds / rho / s / w / cur / cand, rows outside 1..ERPL_DESIGN_MAX_ROWS, step > 65535, first_chain < 0,
+ *   count < 0, first_chain + count > 2^31 - 1, ld < count, ld_cand < count, then per row a kind that is neither
+ *   ERPL_DESIGN_UNIFORM nor ERPL_DESIGN_NORMAL, rho, s or w outside [0, 1] (or NaN);
+ * commit: NULL threshold / g_cand / g_cur / g_next / n_accepted, n_triples outside 0..4, a NULL triples, then per triple a NULL
+ *   cand / cur / next, rows outside 1..4096, an elem_size other than 1, 4 or 8, ld_cand < count, ld < count; count < 0;
+ * chain_stats: NULL selected / n1, chains < 1, steps outside 1..65535, chains * steps > 2^31 - 1, NULL pair with steps > 1;
+ * the context last. */
+#define ERPL_SUBSET_MAX_STEPS 65535
+#define ERPL_SUBSET_MAX_SLOTS 4
+
+typedef struct erpl_subset_spec {
+  double max_apogee, min_apogee, max_range, max_flight_time, energy_apogee;   /* as erpl_analysis_spec */
+  int32_t row;                           /* summary row of g, 0..15 (unused with use_centre) */
+  int32_t sign;                          /* +1: the upper tail of the row, -1: the lower tail */
+  int32_t use_centre;                    /* != 0: g is the miss distance from (cx, cy) */
+  int32_t reserved;
+  double cx, cy;
+  uint64_t seed;                         /* of the proposals */
+  uint32_t level, step;                  /* of the proposals: level < 2^32, step <= ERPL_SUBSET_MAX_STEPS */
+} erpl_subset_spec;
+
+typedef struct erpl_subset_gather {      /* dst[r][k] = src[r][idx[k]], r < rows, k < n_seeds */
+  const void* src;
+  void* dst;
+  int64_t ld_src, ld_dst;                /* in elements */
+  int32_t rows, elem_size;               /* 1..4096; 1, 4 or 8 bytes */
+} erpl_subset_gather;
+
+typedef struct erpl_subset_triple {      /* next[r][c] = accepted(c) ? cand[r][c] : cur[r][c], r < rows, c < count */
+  const void* cand;
+  const void* cur;
+  void* next;
+  int64_t ld_cand, ld;                   /* in elements; ld serves cur and next */
+  int32_t rows, elem_size;
+} erpl_subset_triple;
+
+/* Host only: the bounds of erpl_mc_analysis_defaults, row ERPL_SUM_RANGE, sign +1, no centre, seed 0, level 0, step 1. */
+int erpl_mc_subset_defaults(erpl_subset_spec* spec);
+/* summary [ERPL_SUMMARY_DIM][ld], status [n] (may be NULL), g [n] */
+int erpl_mc_subset_limit_state(erpl_ctx* ctx, const erpl_subset_spec* spec, const double* summary, const int32_t* status,
+                               int64_t ld, int64_t n, double* g, void* hip_stream);
+int erpl_mc_subset_limit_state_host(const erpl_subset_spec* spec, const double* summary, const int32_t* status, int64_t ld,
+                                    int64_t n, double* g);
+/* g [n], idx int32 [n_seeds], selected uint8 [n], threshold: one double, n_alive: one int64 */
+int erpl_mc_subset_seeds(erpl_ctx* ctx, const double* g, int64_t n, int64_t n_seeds, int32_t* idx, uint8_t* selected,
+                         double* threshold, int64_t* n_alive, const erpl_subset_gather* gathers, int32_t n_gathers,
+                         void* hip_stream);
+int erpl_mc_subset_seeds_host(const double* g, int64_t n, int64_t n_seeds, int32_t* idx, uint8_t* selected, double* threshold,
+                              int64_t* n_alive, const erpl_subset_gather* gathers, int32_t n_gathers);
+/* cur [rows][ld], cand [rows][ld_cand]: columns 0 .. count - 1 are the chains first_chain .. first_chain + count - 1 */
+int erpl_mc_subset_propose(erpl_ctx* ctx, const erpl_subset_spec* spec, const uint8_t* kinds, const double* rho, const double* s,
+                           const double* w, int32_t rows, const double* cur, int64_t ld, int64_t first_chain, int64_t count,
+                           double* cand, int64_t ld_cand, void* hip_stream);
+int erpl_mc_subset_propose_host(const erpl_subset_spec* spec, const uint8_t* kinds, const double* rho, const double* s,
+                                const double* w, int32_t rows, const double* cur, int64_t ld, int64_t first_chain, int64_t count,
+                                double* cand, int64_t ld_cand);
+/* threshold: one double; g_cand, g_cur, g_next [count]; n_accepted: one int64, added to */
+int erpl_mc_subset_commit(erpl_ctx* ctx, const double* threshold, const double* g_cand, const double* g_cur, double* g_next,
+                          const erpl_subset_triple* triples, int32_t n_triples, int64_t count, int64_t* n_accepted,
+                          void* hip_stream);
+int erpl_mc_subset_commit_host(const double* threshold, const double* g_cand, const double* g_cur, double* g_next,
+                               const erpl_subset_triple* triples, int32_t n_triples, int64_t count, int64_t* n_accepted);
+/* selected uint8 [steps * chains], step-major; n1: one int64; pair int64 [steps - 1] */
+int erpl_mc_subset_chain_stats(erpl_ctx* ctx, const uint8_t* selected, int64_t chains, int64_t steps, int64_t* n1, int64_t* pair,
+                               void* hip_stream);
+int erpl_mc_subset_chain_stats_host(const uint8_t* selected, int64_t chains, int64_t steps, int64_t* n1, int64_t* pair);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
