@@ -1,7 +1,10 @@
-"""SURVEY 8f-2 / 8f-3 on the device: the on-device dispersion + wind synthesis (sampling.synthetic_dispersions,
-erpl_mc_synth_wind) against the bit-exact host generator (flatten.dispersed_batch, pinned to inputs captured
-inside the reference), and the on-device outlier filter + statistics against the reference's own
-_analyze_results numbers (tests/golden/stats.json)."""
+"""SURVEY 8f-2 / 8f-3 on the device.  The on-device dispersion + wind synthesis (sampling.synthetic_dispersions,
+erpl_mc_synth_wind) is tested twice: in distribution against the bit-exact host generator (flatten.dispersed_batch,
+pinned to inputs captured inside the reference) - KS, mean, std and knot-to-knot correlation at N = 24 000, at six of the
+K knots - and, through `draws=`, value for value: every tensor of the returned batch against NumPy on the host copy of the
+draws (the reference-pinned builders of flatten where they apply, tests/synth_wind_ref.py for the wind table's error
+bound).  The kernel's own C-ABI tests are in tests/test_gpu_synth_wind.py.  Last, the on-device outlier filter +
+statistics against the reference's own _analyze_results numbers (tests/golden/stats.json)."""
 import numpy as np
 import pytest
 import torch
@@ -10,6 +13,7 @@ from scipy import stats as sps
 from erpl_monte_carlo_sim_amd import _abi, analysis, flatten, models, sampling
 
 import helpers as H
+import synth_wind_ref as R
 
 pytestmark = pytest.mark.gpu
 
@@ -149,6 +153,201 @@ def test_generated_batches_obey_the_input_contract(engine):
     with pytest.raises(_abi.ErplError, match="input contract"):
         sampling.synthetic_dispersions(512, models.Rocket(), models.LiquidMotor(), wm, H.EXAMPLE_IC, engine.device,
                                        uncertainty={"mass_uncertainty": 5.0}, engine=engine)   # negative masses
+
+
+# ------------------------------------------------------------------ value for value: synthetic_dispersions(draws=...)
+# The default path (draws=None) is this same arithmetic on the joint rows of the generator's own z:
+# tests/test_gpu_sobol.py::test_the_default_law_is_untouched_and_the_draws_are_the_same_arithmetic feeds z[0:14], z[0:3],
+# z[0:3 K] and the uniforms through `draws` and gets the default batch back to the bit.  So what follows pins the inputs of
+# the benchmark's Set S shards and of run_monte_carlo_device too, not only the independent law of the sensitivity runs.
+N_EXACT = 257
+K_POWER = 12
+EPS = float(np.finfo(np.float64).eps)
+# every row live: a position sigma (0 in the example table), attitude sigmas of 1 rad so that every term of the quaternion
+# product matters, wind ranges that start off zero
+UNC_LIVE = dict(H.UNCERTAINTY, initial_position=[0.7, 1.3, 0.4], initial_attitude=[1.0, 1.0, 1.0],
+                wind_speed_range=[1.5, 6.5], wind_direction_range=[0.25, 2 * np.pi - 0.5])
+# Largest deviations of the device's trigonometric rows from a long-double evaluation of the same inputs, measured on the
+# MI355X over the eight cases below (see the docstring of the test), in units of eps and of eps |speed|; the test asserts
+# four times these, so that other seeds and angles pass, and never more than the bound of a 2-ulp cos / sin.
+QUAT_MEASURED, QUAT_CAP = 1.100, 16.0
+MEAN_MEASURED, MEAN_CAP = 0.674, 4.0
+
+
+def host_restatement(kind, csv, planar, D):
+    """Every tensor synthetic_dispersions(draws=D) returns but the wind table, from the host copy D of the draws: the
+    reference-pinned builder for ic / rocket, flatten.py's motor rows restated on the motor normals, NumPy for the rest."""
+    u, n = UNC_LIVE, D.shape[1]
+    K = len(H.CSV_ALT) if csv else K_POWER
+    assert D.shape[0] == 17 + 3 * K + 2
+    z, zm, zw, uni = D[0:14], D[14:17], D[17:17 + 3 * K], D[17 + 3 * K:]
+    sc = lambda key: np.asarray(u[key], dtype=np.float64)[None, :]
+    lo_s, hi_s = u["wind_speed_range"]
+    lo_d, hi_d = u["wind_direction_range"]
+    P = {"initial_position_offset": sc("initial_position") * z[0:3].T,
+         "initial_velocity_offset": sc("initial_velocity") * z[3:6].T,
+         "initial_attitude_offset": sc("initial_attitude") * z[6:9].T,
+         "initial_angular_velocity_offset": sc("initial_angular_velocity") * z[9:12].T,
+         "mass_multiplier": 1.0 + u["mass_uncertainty"] * z[12],
+         "thrust_multiplier": 1.0 + u["thrust_uncertainty"] * z[13],     # the reference's dead draw
+         "wind_speed": lo_s + (hi_s - lo_s) * uni[0],
+         "wind_direction": lo_d + (hi_d - lo_d) * uni[1],
+         "random_seed": np.arange(n, dtype=np.int64)}
+    rocket, motor = models.Rocket(), H.make_motor(kind)
+    kw = dict(base_altitude_profile=H.CSV_ALT, base_wind_profile=H.CSV_WIND) if csv else {}
+    hb = flatten.dispersed_batch(rocket, motor, models.WindModel(), H.EXAMPLE_IC, P, planar=planar, with_wind=False, **kw)
+    att = np.array(H.EXAMPLE_IC["attitude"], dtype=np.float64)[None, :] \
+        + P["initial_attitude_offset"] * (np.array([0, 1, 0])[None, :] if planar else 1.0)
+    # flatten.py:520-539 on the motor normals of the independent law (dispersed_batch draws its own from RandomState(seed))
+    prop = hb.rocket[1]
+    k = 1.0 + motor.thrust_uncertainty * zm[0]
+    if kind == "solid":
+        mdot = 4.26 * k
+        mt = [k, motor.nozzle_exit_area * k, mdot, prop / mdot]
+    else:
+        kf = 1.0 + motor.mass_flow_uncertainty * zm[1]
+        tv = motor.thrust_vacuum * k
+        mdot = motor.mass_flow_rate * kf
+        mt = [tv, (tv - motor.thrust_sea_level * k) / 101325.0, mdot, prop / mdot]
+    g = zw.copy().reshape(K, 3, n)
+    if planar:
+        g[:, 1, :] = 0.0
+    return dict(K=K, P=P, hb=hb, att=att.T, motor=np.array(mt), k_thrust=k, mdot=mdot, g=g.reshape(3 * K, n),
+                alt=np.asarray(H.CSV_ALT, dtype=np.float64) if csv else np.linspace(0, 25000, K_POWER))
+
+
+def quaternion_longdouble(att):
+    r, p, y = (att[i].astype(np.longdouble) / 2 for i in range(3))
+    cr, sr, cp, sp, cy, sy = np.cos(r), np.sin(r), np.cos(p), np.sin(p), np.cos(y), np.sin(y)
+    return np.stack([cr * cp * cy + sr * sp * sy, sr * cp * cy - cr * sp * sy,
+                     cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy])
+
+
+def bit_equal(dev, host):
+    d, h = dev.cpu().numpy(), np.ascontiguousarray(host, dtype=np.float64)
+    return d.dtype == np.float64 and d.shape == h.shape and np.array_equal(d.view(np.int64), h.view(np.int64))
+
+
+def ulps_off(dev, host):
+    d, h = dev.cpu().numpy(), np.asarray(host, dtype=np.float64)
+    return float((np.abs(d - h) / H.ulp(h, np.float64)).max())
+
+
+@pytest.mark.parametrize("planar", [False, True], ids=["full", "planar"])
+@pytest.mark.parametrize("csv", [True, False], ids=["csv", "power12"])
+@pytest.mark.parametrize("kind", ["liquid", "solid"])
+def test_every_tensor_of_the_batch_is_the_host_restatement_of_its_draws(engine, kind, csv, planar):
+    """synthetic_dispersions(draws=D) is a pure function of D: every tensor it returns against NumPy on the host copy of D.
+    ic[0:6], ic[10:13], rocket: flatten.dispersed_batch on the offsets built from D - only +, -, x: equal to the bit.
+    motor: the x / + rows equal to the bit; the two rows with a division (burn time, the liquid motor's exit area) and the
+    mass-flow factor are asserted within 1 ulp - measured on the MI355X: the burn time (tensor / tensor) IS equal to the
+    bit in all eight cases; the exit area and the mass-flow factor (tensor / Python scalar, which torch evaluates as a
+    product with the rounded reciprocal) are 1 ulp off.
+    quaternion, mean wind: through the device's cos / sin; against a long-double evaluation, asserted at four times the
+    largest deviation measured on the MI355X over these eight cases - quaternion 1.100 eps (absolute), mean wind
+    0.674 eps |speed|; asserted: 4.4 eps and 2.7 eps |speed| - and never above 16 eps / 4 eps |speed|, the bounds of a
+    2-ulp cos / sin.  (Wind table there: at most 1.16 eps E.)
+    wind: flatten._ar1_profiles on the host copy of the turbulence rows and the device's own mean-wind rows (pinned just
+    before), within 8 eps E (tests/synth_wind_ref.py); the fp32 table is the rounding of the fp64 one."""
+    n = N_EXACT
+    K = len(H.CSV_ALT) if csv else K_POWER
+    draws = sampling.primitive_draws(n, K, engine.device, seed=20 + 4 * (kind == "solid") + 2 * csv + planar)
+    D = draws.cpu().numpy()
+    kw = dict(base_altitude_profile=H.CSV_ALT, base_wind_profile=H.CSV_WIND) if csv else dict(n_wind_knots=K_POWER)
+    disperse = lambda prec: sampling.synthetic_dispersions(
+        n, models.Rocket(), H.make_motor(kind), models.WindModel(), H.EXAMPLE_IC, engine.device, precision=prec,
+        uncertainty=UNC_LIVE, planar=planar, engine=engine, draws=draws, **kw)
+    db = disperse(_abi.PREC_F64)
+    torch.cuda.synchronize()
+    h = host_restatement(kind, csv, planar, D)
+    hb, P = h["hb"], h["P"]
+
+    # the batch as DeviceBatch documents it
+    assert db.n == n and db.k_wind == K and db.precision == _abi.PREC_F64
+    assert bit_equal(db.alt_grid, h["alt"]) and db.alt_grid.shape == (K,)
+    liquid = kind == "liquid"
+    F = 19 if liquid else 18
+    assert db.factor_names == [k for k in sampling.FACTOR_NAMES if liquid or k != "motor_mass_flow_multiplier"]
+    for t, shape in ((db.ic, (13, n)), (db.rocket, (2, n)), (db.motor, (4, n)), (db.wind, (K, 3, n)), (db.factors, (F, n)),
+                     (db.alt_grid, (K,))):
+        assert tuple(t.shape) == shape and t.dtype == torch.float64 and t.is_contiguous() and t.device == engine.device
+
+    # +, -, x only: the reference-pinned builder, to the bit
+    assert bit_equal(db.ic[0:6], hb.ic[0:6]) and bit_equal(db.ic[10:13], hb.ic[10:13])
+    assert bit_equal(db.rocket, hb.rocket)
+    assert np.ptp(hb.ic[0]) > 0 and np.ptp(hb.ic[1]) > 0        # the position rows are live
+
+    # motor
+    f = dict(zip(db.factor_names, db.factors))
+    mt = h["motor"]
+    assert bit_equal(db.motor[0], mt[0]) and bit_equal(db.motor[2], mt[2])
+    divided = {"burn": ulps_off(db.motor[3], mt[3])}
+    if liquid:
+        divided["Ae"] = ulps_off(db.motor[1], mt[1])
+        divided["mass-flow factor"] = ulps_off(f["motor_mass_flow_multiplier"], h["mdot"] / models.LiquidMotor().mass_flow_rate)
+    else:
+        assert bit_equal(db.motor[1], mt[1])
+    print("rows with a division, largest deviation in ulp:", divided)
+    assert all(v <= 1.0 for v in divided.values()), divided
+
+    # factors: every row
+    for r, name in enumerate(("position_x", "position_y", "position_z", "velocity_x", "velocity_y", "velocity_z")):
+        assert bit_equal(f[name], hb.ic[r]), name
+    for r, name in enumerate(("attitude_roll", "attitude_pitch", "attitude_yaw")):
+        assert bit_equal(f[name], h["att"][r]), name
+    for r, name in enumerate(("angular_velocity_x", "angular_velocity_y", "angular_velocity_z")):
+        assert bit_equal(f[name], hb.ic[10 + r]), name
+    assert bit_equal(f["mass_multiplier"], P["mass_multiplier"]) and bit_equal(f["motor_thrust_multiplier"], h["k_thrust"])
+    assert bit_equal(f["wind_speed"], P["wind_speed"]) and bit_equal(f["wind_direction"], P["wind_direction"])
+    speed, direction = P["wind_speed"], P["wind_direction"].astype(np.longdouble)
+    mu, mv = f["wind_mean_u"].cpu().numpy(), f["wind_mean_v"].cpu().numpy()
+    dev_u = np.abs(mu - speed * np.cos(direction)) / (EPS * np.abs(speed))
+    dev_v = np.abs(mv - speed * np.sin(direction)) / (EPS * np.abs(speed))
+    if planar:
+        assert bit_equal(f["wind_mean_v"], np.zeros(n))
+        dev_v = np.zeros(n)
+    mean_dev = float(max(dev_u.max(), dev_v.max()))
+
+    # quaternion
+    q = db.ic[6:10].cpu().numpy()
+    quat_dev = float((np.abs(q - quaternion_longdouble(h["att"])) / EPS).max())
+    print(f"trig rows: quaternion {quat_dev:.3f} eps, mean wind {mean_dev:.3f} eps |speed|")
+    assert 4 * QUAT_MEASURED <= QUAT_CAP and 4 * MEAN_MEASURED <= MEAN_CAP
+    assert quat_dev <= 4 * QUAT_MEASURED and mean_dev <= 4 * MEAN_MEASURED
+
+    # wind: the reference-pinned host recursion on the turbulence rows + the mean-wind rows the kernel was given
+    wm, alt, g = models.WindModel(), h["alt"], h["g"]
+    sigma, rho, innov = models.knot_constants(wm, alt)
+    rho, innov = [0.0] + list(rho[1:]), [0.0] + list(innov[1:])
+    if csv:
+        base = np.array(H.CSV_WIND, dtype=np.float64)
+        if planar:
+            base[:, 1] = 0.0
+        scale = np.ones(K)
+        host = flatten._ar1_profiles(wm, alt, g, base=base)
+        host[:, 0, :] += mu                                      # as flatten.dispersed_batch adds the uniform offset
+        host[:, 1, :] += mv
+    else:
+        base = None
+        scale = np.array([(np.float64(a) / 10.0) ** wm.power_law_exponent for a in alt])
+        host = flatten._ar1_profiles(wm, alt, g, mean_u=[s * mu for s in scale], mean_v=[s * mv for s in scale])
+    args = (g, sigma, rho, innov, base, scale, mu, mv)
+    E = R.bound(*args)
+    wind = db.wind.cpu().numpy()
+    x, y = R.excess(wind, host, E), R.excess(wind, R.reference(*args), E)
+    print(f"wind: device - _ar1_profiles {x:.2f} eps E, device - long double {y:.2f} eps E")
+    assert x <= R.TOL and y <= R.TOL
+    if planar:
+        assert np.array_equal(wind[:, 1, :], np.zeros((K, n)))
+    else:
+        assert np.ptp(wind[:, 1, :]) > 0
+
+    # the fp32 batch: the same rows, the table rounded
+    d32 = disperse(_abi.PREC_F32)
+    torch.cuda.synchronize()
+    assert d32.wind.dtype == torch.float32 and d32.wind.is_contiguous() and torch.equal(d32.wind, db.wind.float())
+    for a, b in ((d32.ic, db.ic), (d32.rocket, db.rocket), (d32.motor, db.motor), (d32.factors, db.factors)):
+        assert torch.equal(a.view(torch.int64), b.view(torch.int64))
 
 
 # ------------------------------------------------------------------ f-3: device statistics on the device
