@@ -381,11 +381,22 @@ class ErplCompare(C.Structure):
 DESIGN_MAX_ROWS = 4096
 DESIGN_RANDOM, DESIGN_LHS, DESIGN_LHS_CENTRED = 0, 1, 2
 DESIGN_UNIFORM, DESIGN_NORMAL = 0, 1
-DESIGN_KINDS = {"random": DESIGN_RANDOM, "lhs": DESIGN_LHS, "lhs_centred": DESIGN_LHS_CENTRED}
+# erpl_mc_qmc.  DESIGN_QMC is the name of the Sobol' design in the Python layer alone: erpl_mc_design refuses it as a kind
+DESIGN_QMC = 3
+QMC_MAX_DIMS = 1024
+QMC_RAW, QMC_OWEN = 0, 1
+QMC_SCRAMBLES = {"raw": QMC_RAW, "owen": QMC_OWEN}
+QMC_PADS = {"random": DESIGN_RANDOM, "lhs": DESIGN_LHS}
+DESIGN_KINDS = {"random": DESIGN_RANDOM, "lhs": DESIGN_LHS, "lhs_centred": DESIGN_LHS_CENTRED, "qmc": DESIGN_QMC}
 
 
 class ErplDesignSpec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("rows", C.c_int32), ("first_row", C.c_int32), ("reserved", C.c_int32),
+                ("n", C.c_int64), ("block", C.c_int64), ("seed", C.c_uint64)]
+
+
+class ErplQmcSpec(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("first_row", C.c_int32), ("scramble", C.c_int32), ("pad", C.c_int32),
                 ("n", C.c_int64), ("block", C.c_int64), ("seed", C.c_uint64)]
 
 
@@ -516,6 +527,7 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_compare_defaults", "erpl_mc_compare", "erpl_mc_compare_labels",
            "erpl_mc_legacy_random_streams_device", "erpl_mc_legacy_wind_profiles_device",
            "erpl_mc_design_defaults", "erpl_mc_design", "erpl_mc_design_host",
+           "erpl_mc_qmc_defaults", "erpl_mc_qmc", "erpl_mc_qmc_host",
            "erpl_mc_surrogate_defaults", "erpl_mc_surrogate_terms", "erpl_mc_surrogate", "erpl_mc_surrogate_predict",
            "erpl_mc_surrogate_predict_host",
            "erpl_mc_tally_defaults", "erpl_mc_tally_words", "erpl_mc_tally_add", "erpl_mc_tally_merge", "erpl_mc_tally_result",
@@ -635,6 +647,10 @@ def load_library(path=None):
     lib.erpl_mc_design.argtypes = [C.c_void_p, C.POINTER(ErplDesignSpec), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                    C.c_void_p]
     lib.erpl_mc_design_host.argtypes = [C.POINTER(ErplDesignSpec), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
+    lib.erpl_mc_qmc_defaults.argtypes = [C.POINTER(ErplQmcSpec)]
+    lib.erpl_mc_qmc.argtypes = [C.c_void_p, C.POINTER(ErplQmcSpec), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                C.c_int64, C.c_void_p]
+    lib.erpl_mc_qmc_host.argtypes = [C.POINTER(ErplQmcSpec), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
     lib.erpl_mc_surrogate_defaults.argtypes = [C.POINTER(ErplSurSpec)]
     lib.erpl_mc_surrogate_terms.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p]
     lib.erpl_mc_surrogate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

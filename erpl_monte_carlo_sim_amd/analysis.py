@@ -512,7 +512,9 @@ def replicate_intervals(summary, status, block, rows=None, level=0.95, engine=No
     filtered and non-finite values dropped as everywhere - and across the replicates the mean of means, its standard error
     s / sqrt(R) (s with R - 1 in the denominator) and the Student-t interval at `level` with R - 1 degrees of freedom.
     Returns, per row name (ROW_NAMES), {'replicate_means': [..], 'replicate_counts': [..], 'mean', 'se', 'lo', 'hi'}, plus
-    'replicates', 'block' and 'level'.  R = 1: se, lo and hi are NaN, one hypercube has no error bar of its own."""
+    'replicates', 'block' and 'level'.  R = 1: se, lo and hi are NaN, one hypercube has no error bar of its own.
+    The replicates of design='qmc' are independently scrambled nets and this is their error bar too; the bootstrap
+    (`bootstrap_intervals`) is no more valid for the columns of a net than for those of a hypercube."""
     from scipy import stats as sps
 
     from . import _abi

@@ -470,6 +470,7 @@ int erpl_mc_destroy(erpl_ctx* c) {
   if (c->sur_ev) (void)hipEventDestroy(c->sur_ev);
   if (c->design_flag) (void)hipHostFree(c->design_flag);
   if (c->design_ev) (void)hipEventDestroy(c->design_ev);
+  (void)hipFree(c->qmc_v);
   c->tally.release();
   c->subset.release();
   if (c->subset_pin) (void)hipHostFree(c->subset_pin);

@@ -93,6 +93,17 @@ __attribute__((visibility("hidden"))) int erpl_design_check_flag(erpl_ctx* c) {
   return design_capped();
 }
 
+// the pinned flag word and the event of the context, made by the first call of erpl_mc_design or erpl_mc_qmc
+__attribute__((visibility("hidden"))) int erpl_design_flag_init(erpl_ctx* c) {
+  if (c->design_flag) return ERPL_OK;
+  HIP_TRY(hipEventCreateWithFlags(&c->design_ev, hipEventDisableTiming));
+  int* flag = nullptr;
+  HIP_TRY(hipHostMalloc((void**)&flag, sizeof(int), hipHostMallocDefault));
+  *flag = 0;
+  c->design_flag = flag;
+  return ERPL_OK;
+}
+
 extern "C" {
 
 int erpl_mc_design_defaults(erpl_design_spec* spec) {
@@ -110,13 +121,7 @@ int erpl_mc_design(erpl_ctx* c, const erpl_design_spec* spec, const uint8_t* kin
   if (!c) return erpl_fail(ERPL_ERR_INVALID, "NULL ctx");
   if (count == 0) return ERPL_OK;
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->design_flag) {
-    HIP_TRY(hipEventCreateWithFlags(&c->design_ev, hipEventDisableTiming));
-    int* flag = nullptr;
-    HIP_TRY(hipHostMalloc((void**)&flag, sizeof(int), hipHostMallocDefault));
-    *flag = 0;
-    c->design_flag = flag;
-  }
+  ERPL_TRY(erpl_design_flag_init(c));
   ErplDesignArgs a = {};
   a.seed = spec->seed;
   a.first = first; a.count = count; a.ld = ld;

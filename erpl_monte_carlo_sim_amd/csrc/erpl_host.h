@@ -1,5 +1,5 @@
 // erpl_host.h — what the host units of the C ABI share (erpl_api.hip, erpl_sampling.hip, erpl_stats_api.hip,
-// erpl_legacy_device.hip, erpl_design.hip, erpl_tally.hip, erpl_subset.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
+// erpl_legacy_device.hip, erpl_design.hip, erpl_qmc.hip, erpl_tally.hip, erpl_subset.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
 // Internal, never installed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -247,6 +247,9 @@ struct erpl_ctx {
   // (both made by the first call; erpl_design_check_flag reads them for the blocking checks)
   int* design_flag = nullptr;
   hipEvent_t design_ev = nullptr;
+  // erpl_mc_qmc: the direction numbers V[ERPL_QMC_MAX_DIMS][32] on the device (128 KB, made by the first call); its pad rows
+  // raise design_flag and its calls record design_ev, so the blocking checks cover them as they cover erpl_mc_design
+  uint32_t* qmc_v = nullptr;
   // erpl_mc_tally_*: the device workspace of erpl_tally.hip (the spec, the candidate lists of the extremes) in the buffer, the
   // spec that is on the device in the pinned mirror
   ErplStatUnit<void, erpl_tally_spec> tally;
@@ -259,6 +262,7 @@ struct erpl_ctx {
 
 // erpl_design.hip
 __attribute__((visibility("hidden"))) int erpl_design_check_flag(erpl_ctx* c);
+__attribute__((visibility("hidden"))) int erpl_design_flag_init(erpl_ctx* c);
 
 // The scale of an accepted pair of the legacy polar Gaussian (LegacyRS::next_gauss, and the host phase of the device
 // streams): the one copy, so that both go through the same libm log with the same rounding of the quotient.

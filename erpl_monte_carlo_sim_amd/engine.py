@@ -736,7 +736,7 @@ class TrajectoryEngine:
         """Columns first .. first + count - 1 (default: all from `first`) of the design (seed, kind, n, block, first_row) of
         erpl_mc_design, drawn on the device: one row per entry of `rows_kinds` (_abi.DESIGN_UNIFORM: the probability in
         (0, 1); _abi.DESIGN_NORMAL: its normal quantile; a sequence or a bytes object), the global rows first_row ...
-        kind: 'random', 'lhs' or 'lhs_centred' (or the _abi.DESIGN_* value); block: the columns of a replicate, a divisor
+        kind: 'random', 'lhs' or 'lhs_centred' (or the _abi.DESIGN_* value; 'qmc' is `qmc` below, refused here); block: the columns of a replicate, a divisor
         of n, 0 = n.  Counter-based: a window equals those columns of the whole design bit for bit, wherever and in
         whatever pieces it is generated.  out: None (a new float64 [rows, count] tensor) or a float64 device tensor
         [rows, ld] with unit column stride and ld >= count, of which columns 0 .. count - 1 are written.  Asynchronous on
@@ -759,6 +759,43 @@ class TrajectoryEngine:
         if count == 0 and out.numel() == 0:   # an empty tensor has no storage to point at, and count == 0 writes nothing
             return out
         self._call("erpl_mc_design", C.byref(spec), kinds, first, count, C.c_void_p(out.data_ptr()), ld,
+                   C.c_void_p(st.cuda_stream))
+        return out
+
+    def qmc(self, rows_kinds, n, seed, dims=None, scramble="owen", pad="random", block=0, first=0, count=None, first_row=0,
+            out=None):
+        """Columns first .. first + count - 1 (default: all from `first`) of the scrambled Sobol' design (seed, n, block,
+        scramble, pad, first_row, dims) of erpl_mc_qmc, drawn on the device: one row per entry of `rows_kinds` as in `design`.
+        dims: per row its Sobol' dimension 0 .. 1023 or -1 for a pad row, which is the row `design(kind=pad)` writes for the
+        same global row; None: the global row where that is below 1024, -1 beyond.  scramble: 'owen' or 'raw' (or the
+        _abi.QMC_* value; 'raw' is for comparisons, not for flights); pad: 'random' or 'lhs'.  block: the columns of a
+        replicate, an independently scrambled copy of the net; 0 = n.  With block 0 and pad 'random' no column depends on n:
+        a longer run continues a shorter one.  Counter-based, `out`, the stream and the return value as `design`."""
+        kinds = bytes(bytearray(int(k) for k in rows_kinds))
+        n, first = int(n), int(first)
+        count = n - first if count is None else int(count)
+        spec = self._defaults(_abi.ErplQmcSpec, "erpl_mc_qmc_defaults")
+        spec.scramble = _abi.QMC_SCRAMBLES[scramble] if isinstance(scramble, str) else int(scramble)
+        spec.pad = _abi.QMC_PADS[pad] if isinstance(pad, str) else int(pad)
+        spec.rows, spec.first_row, spec.n, spec.block = len(kinds), int(first_row), n, int(block)
+        spec.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        dims_arg = None
+        if dims is not None:
+            dims = [int(d) for d in dims]
+            if len(dims) != len(kinds):
+                raise ValueError(f"dims has {len(dims)} entries for {len(kinds)} rows")
+            dims_arg = (C.c_int32 * len(dims))(*dims)
+        if out is None:
+            out = torch.empty((len(kinds), max(count, 0)), dtype=torch.float64, device=self.device)
+        if not (torch.is_tensor(out) and out.is_cuda and out.device == self.device and out.dtype == torch.float64
+                and out.dim() == 2 and out.shape[0] == len(kinds) and out.shape[1] >= count
+                and (out.shape[1] == 0 or out.stride(1) == 1) and (out.shape[0] == 1 or out.stride(0) >= out.shape[1])):
+            raise ValueError(f"out must be a float64 [{len(kinds)}, >= {count}] tensor on {self.device} with unit column stride")
+        ld = out.stride(0) if out.shape[0] > 1 else max(out.shape[1], 1)
+        st = torch.cuda.current_stream(self.device)
+        if count == 0 and out.numel() == 0:   # an empty tensor has no storage to point at, and count == 0 writes nothing
+            return out
+        self._call("erpl_mc_qmc", C.byref(spec), kinds, dims_arg, first, count, C.c_void_p(out.data_ptr()), ld,
                    C.c_void_p(st.cuda_stream))
         return out
 

@@ -288,7 +288,8 @@ class MonteCarloAnalyzer:
         """The sub-batch loop of `run_monte_carlo_device` and `run_monte_carlo_tally`: this rank's samples [lo, hi) of the run
         in sub-batches of DEVICE_CHUNK (the draws of sub-batch j come from seed + rank and j alone, so a run is
         reproducible for a given n_samples, world size and seed; with design = (kind, block, K) every sub-batch takes its
-        window of the one global design), every one handed to erpl_mc_submit_batch as soon as it is drawn: generation, up
+        window of the one global design, and with (kind, block, K, s) the run is the columns s .. s + n_samples - 1 of a design
+        of s + n_samples columns), every one handed to erpl_mc_submit_batch as soon as it is drawn: generation, up
         to `depth` integrations and their tails overlap on the GPU.  `submitted(a, cnt, db, outs)` is called behind the
         submission of the sub-batch of cnt samples at offset a (outs: its summary and status tensors, not yet written);
         `retired(a, cnt, ticket, outs)`, if given, once ITS ticket has been checked - the batch has finished - and before
@@ -320,9 +321,10 @@ class MonteCarloAnalyzer:
                 cnt = min(self.DEVICE_CHUNK, m - a)
                 draws = None
                 if design is not None:   # this sub-batch's window of the global design (a rank without samples: any column)
-                    kind, block, K = design
-                    draws = sampling.design_draws(n_samples, K, eng.device, seed, design=kind, block=block,
-                                                  first=min(lo + a, n_samples - cnt), count=cnt, engine=eng)
+                    kind, block, K = design[:3]
+                    s0 = design[3] if len(design) > 3 else 0
+                    draws = sampling.design_draws(s0 + n_samples, K, eng.device, seed, design=kind, block=block,
+                                                  first=s0 + min(lo + a, n_samples - cnt), count=cnt, engine=eng)
                 group.append((a, cnt, sampling.synthetic_dispersions(
                     cnt, self.rocket, self.motor, self.wind_model, initial_conditions, eng.device,
                     precision=prec, seed=seed + rank + 1000003 * j, uncertainty=self.uncertainty_params,
@@ -363,15 +365,17 @@ class MonteCarloAnalyzer:
         `analysis.drivers`.  One rank only: factors are not gathered across ranks (ValueError before any work).
 
         design: None (the draws above: the reference's JOINT law from torch's generator, sub-batch j from
-        seed + rank + 1000003 * j, bit for bit as before), or 'random', 'lhs' or 'lhs_centred': the run flies ONE global
-        design of n_samples columns (`sampling.design_draws`, erpl_mc_design) of which every rank and every sub-batch
+        seed + rank + 1000003 * j, bit for bit as before), or 'random', 'lhs', 'lhs_centred' or 'qmc': the run flies ONE global
+        design of n_samples columns (`sampling.design_draws`, erpl_mc_design, erpl_mc_qmc) of which every rank and every sub-batch
         generates its own window, so its inputs depend on (seed, n_samples, design, design_replicates) alone and not on the
         world size or on DEVICE_CHUNK.  Such a run is drawn under the INDEPENDENT law of
         `sampling.synthetic_dispersions(draws=...)` - a deliberate deviation from the reference's joint law, as in
         `sobol_indices`: a design stratifies every primitive by itself, and under the joint law one normal is the thrust
         multiplier, `position_x` and the first turbulence innovation at once.  'lhs' stratifies each of the 17 + 3 K + 2
         primitives (Latin hypercube sampling: the variance of the mean of a near-additive output such as the apogee falls
-        well below the i.i.d. one).  design_replicates = R splits the design into R independent Latin hypercubes of
+        well below the i.i.d. one).  'qmc' is a scrambled Sobol' design (erpl_mc_qmc) on the dimensions of
+        `sampling.qmc_dims`: it balances the low-order interactions of the primitives too, and its replicates are
+        independently scrambled nets.  design_replicates = R splits the design into R independent Latin hypercubes of
         n_samples / R columns each (ValueError if R does not divide n_samples): `analysis.replicate_intervals` with
         block = n_samples / R gives the valid error bar of such a run, which the columns of ONE hypercube cannot give.
         out["design"] records kind, seed, block and replicates."""
@@ -440,8 +444,20 @@ class MonteCarloAnalyzer:
                               "statistics_s": t3 - t2, "sub_batches": len(parts), "in_flight": eng.get_overlap()}
         return out
 
+    @staticmethod
+    def _check_first_sample(design, design_replicates, n_samples, first_sample):
+        """The refusals of `run_monte_carlo_tally(first_sample=)`.  first_sample = 0 is every run there was before it: nothing
+        is checked here, whatever n_samples is (a design's own limit of 2^31 - 1 columns is the library's to report)."""
+        if first_sample == 0:
+            return
+        if design != "qmc" or int(design_replicates) != 1:
+            raise ValueError("first_sample: only design='qmc' with one replicate is a sequence that can be continued; the columns "
+                             "of every other design depend on n_samples")
+        if first_sample < 0 or first_sample + n_samples >= 2 ** 31:
+            raise ValueError(f"first_sample = {first_sample} is negative or first_sample + n_samples reaches 2^31")
+
     def run_monte_carlo_tally(self, initial_conditions, n_samples, tally=None, seed=1234, precision="f64_fast", planar=False,
-                              design=None, design_replicates=1):
+                              design=None, design_replicates=1, first_sample=0):
         """`run_monte_carlo_device` for runs too long to keep: the same sub-batch loop, draws and seeds (bit for bit the same
         flights), but no summary is kept - every sub-batch is folded into a tally (erpl_mc_tally_add, first_id = its global
         sample index) as soon as its ticket has been checked, and its outputs are released with its inputs.  Device memory
@@ -449,11 +465,16 @@ class MonteCarloAnalyzer:
         (erpl_mc_tally_merge: the bytes do not depend on that order); a failing rank still joins, with a state that makes
         every rank refuse the result.  tally: the spec (analysis.tally_spec; None: the library's defaults).  n_samples: up
         to 2^31 - 1 with a design, no limit but the int64 counts without one.
+        first_sample = s (design='qmc' alone, one replicate; ValueError otherwise): the run is the columns s .. s + n_samples - 1
+        of the ONE Sobol' sequence of `seed` (block 0, pad 'random': no column depends on the length), with those sample ids,
+        so a tally merged (TrajectoryEngine.tally_merge) from the runs [0, n) and [n, 2 n) equals the tally of one run of
+        2 n byte for byte: a run that proved too short is continued, not flown again.
         Returns the dict of analysis.tally_statistics plus 'spec', 'state' (the int64 device tensor: equal runs give equal
         bytes, and with a design they do not depend on DEVICE_CHUNK or on the world size), 'result' (the dict of
         TrajectoryEngine.tally_result), 'n_total', 'seed', 'precision', 'planar', 'initial_conditions', 'design' (None, or
-        kind / seed / block / replicates: what `refly` needs) and 'performance' (with 'peak_memory_bytes')."""
-        n_samples = int(n_samples)
+        kind / seed / block / replicates: what `refly` needs), 'first_sample' and 'performance' (with 'peak_memory_bytes')."""
+        n_samples, first_sample = int(n_samples), int(first_sample)
+        self._check_first_sample(design, design_replicates, n_samples, first_sample)
         design_args = None
         if design is not None:
             if design not in _abi.DESIGN_KINDS:
@@ -463,6 +484,8 @@ class MonteCarloAnalyzer:
                 raise ValueError(f"design_replicates = {design_replicates} does not divide n_samples = {n_samples}")
             use_base = self.base_wind_profile is not None and self.base_altitude_profile is not None
             design_args = (design, n_samples // design_replicates, len(self.base_altitude_profile) if use_base else 100)
+            if first_sample:
+                design_args = (design, 0, design_args[2], first_sample)
         eng = shared_engine(self.device)
         eng.set_config(self._config())
         spec, state = eng.tally_new(tally)
@@ -479,7 +502,7 @@ class MonteCarloAnalyzer:
             use = min(cnt, hi - lo - a)   # a rank without samples flies one column that is not tallied
             if use > 0:
                 eng.wait(ticket)          # orders the finished batch into the current stream
-                eng.tally_add(spec, state, outs[0], outs[1], first_id=lo + a, n=use)
+                eng.tally_add(spec, state, outs[0], outs[1], first_id=first_sample + lo + a, n=use)
 
         err, gen_s = None, 0.0
         try:
@@ -508,7 +531,8 @@ class MonteCarloAnalyzer:
         t1 = time.time()
         out = analysis.tally_statistics(result)
         out.update({"spec": spec, "state": state, "result": result, "n_total": n_samples, "seed": int(seed), "precision": precision,
-                    "planar": bool(planar), "initial_conditions": dict(initial_conditions), "design": None})
+                    "planar": bool(planar), "initial_conditions": dict(initial_conditions), "design": None,
+                    "first_sample": first_sample})
         if design is not None:
             out["design"] = {"kind": design, "seed": int(seed), "block": design_args[1], "replicates": design_replicates}
         out["performance"] = {"total_time": t1 - t0, "simulations_per_second": n_samples / (t1 - t0), "gpus_used": ws,
@@ -519,9 +543,9 @@ class MonteCarloAnalyzer:
 
     def refly(self, run, ids, stride=10, initial_conditions=None):
         """Flies named samples of a design run again, with capture: `run` is the dict of `run_monte_carlo_tally` (or any
-        dict with its keys 'design', 'n_total', 'precision', 'planar', 'initial_conditions'), `ids` global sample ids - the
-        ids a tally holds with its extremes.  Column i of a design run is a function of (seed, n, design, i) alone
-        (erpl_mc_design), so the named columns are generated again (`sampling.design_draws(first=id, count=1)`) and flown
+        dict with its keys 'design', 'n_total', 'precision', 'planar', 'initial_conditions' and, for a continued run,
+        'first_sample'), `ids` global sample ids - the ids a tally holds with its extremes.  Column i of a design run is a function of (seed, n, design, i) alone
+        (erpl_mc_design, erpl_mc_qmc), so the named columns are generated again (`sampling.design_draws(first=id, count=1)`) and flown
         with every `stride`-th step captured.  Returns {'ids', 'summary' float64 [16, len(ids)], 'status', 'traj',
         'traj_len', 'stride'} on the device: the input of TrajectoryEngine.flight_envelope / corridor_resample on the worst
         cases.  A run with design=None cannot be re-flown: its draws come per sub-batch from torch's generator, so a column
@@ -529,12 +553,13 @@ class MonteCarloAnalyzer:
         from . import sampling
         design = run.get("design")
         if design is None:
-            raise ValueError("refly needs a run flown with design='random', 'lhs' or 'lhs_centred': the draws of a design=None run "
+            raise ValueError("refly needs a run flown with design='random', 'lhs', 'lhs_centred' or 'qmc': the draws of a design=None run "
                              "come per sub-batch from torch's generator, so a sample cannot be regenerated from its id")
         ids = [int(i) for i in ids]
-        n_total = int(run["n_total"])
-        if not ids or min(ids) < 0 or max(ids) >= n_total:
-            raise ValueError(f"ids: at least one, each in 0..{n_total - 1}")
+        first_sample = int(run.get("first_sample", 0))
+        n_total = first_sample + int(run["n_total"])       # the columns of the design the run is a window of
+        if not ids or min(ids) < first_sample or max(ids) >= n_total:
+            raise ValueError(f"ids: at least one, each in {first_sample}..{n_total - 1}")
         stride = int(stride)
         if stride < 1:
             raise ValueError("stride must be at least 1")
@@ -940,8 +965,8 @@ class MonteCarloAnalyzer:
         mapping name -> rows of the primitive tensor (disjoint, at most 32).  A and B are `sampling.primitive_draws` at
         `seed` and `seed + 1`; block b of the k + 2 blocks (A, B, A with group i from B) is flown through eng.submit in
         sub-batches of at most DEVICE_CHUNK, inputs released per ticket, as run_monte_carlo_device does.
-        design: None keeps those draws; 'random', 'lhs' or 'lhs_centred' takes A and B from `sampling.design_draws`
-        (erpl_mc_design) at `seed` and `seed + 1` instead: two independent designs of n_base columns, every primitive
+        design: None keeps those draws; 'random', 'lhs', 'lhs_centred' or 'qmc' takes A and B from `sampling.design_draws`
+        (erpl_mc_design, erpl_mc_qmc) at `seed` and `seed + 1` instead: two independent designs of n_base columns, every primitive
         stratified with 'lhs'.
         filter_outliers=True masks a design row when erpl_mc_analyze gives ANY of its k + 2 flights a reason.
         One rank only (ValueError before any work): a design is not gathered across ranks.
@@ -1052,7 +1077,7 @@ class MonteCarloAnalyzer:
         """A polynomial chaos surrogate of a run flown with `run_monte_carlo_device(design=...)` (no reference counterpart,
         no extra flights): `analysis.polynomial_chaos` - first-order, total and pair Sobol indices, r2 / q2 and a model for
         `TrajectoryEngine.surrogate_predict` - of the chosen primitives on up to 4 summary rows.  Only the chosen primitive
-        rows are regenerated, from analysis["design"] through `TrajectoryEngine.design(first_row=...)`: the bits the run flew.
+        rows are regenerated, from analysis["design"] through `TrajectoryEngine.design(first_row=...)` (`.qmc` for design='qmc'): the bits the run flew.
         variables: None (`sampling.scalar_primitives`: every scalar primitive, without the turbulence innovations and the
         dead draw) or a mapping name -> primitive row, at most 32.  ValueError for a run without `design`: under the
         reference's joint law the inputs are not independent (one normal is the thrust multiplier, position_x and the first
@@ -1078,8 +1103,12 @@ class MonteCarloAnalyzer:
         n = int(summ.shape[1])
         kinds = [_abi.DESIGN_NORMAL if r < 17 + 3 * K else _abi.DESIGN_UNIFORM for r in prim]
         factors = torch.empty((len(prim), n), dtype=torch.float64, device=eng.device)
+        qdims = sampling.qmc_dims(K) if d["kind"] == "qmc" else None      # as `sampling.design_draws` laid the rows out
         for i, r in enumerate(prim):
-            eng.design([kinds[i]], n, d["seed"], kind=d["kind"], block=d["block"], first_row=r, out=factors[i:i + 1])
+            if qdims is not None:
+                eng.qmc([kinds[i]], n, d["seed"], dims=[qdims[r]], block=d["block"], first_row=r, out=factors[i:i + 1])
+            else:
+                eng.design([kinds[i]], n, d["seed"], kind=d["kind"], block=d["block"], first_row=r, out=factors[i:i + 1])
         out = ana.polynomial_chaos(summ, factors, kinds, names, status=analysis.get("status"), engine=eng, rows=rows, degree=degree,
                                    order=order, holdout=holdout)
         out["factors"], out["primitive_rows"] = factors, prim

@@ -82,13 +82,30 @@ def design_draws(n, K, device, seed, design="lhs", block=0, first=0, count=None,
     two rows uniforms - here in (0, 1), which every consumer of the [0, 1) rows accepts.  design: 'random' (independent
     draws), 'lhs' (every row stratified: each of the m strata of a replicate holds one column) or 'lhs_centred'; block = m:
     n / m independent replicates of m columns each, 0 = n.  Counter-based on (seed, row, column): a window is the same bits
-    whatever rank or sub-batch generates it."""
+    whatever rank or sub-batch generates it.  design 'qmc' (erpl_mc_qmc): a scrambled Sobol' design on the dimensions of
+    `qmc_dims(K)`, the rows without a dimension padded with independent draws; its replicates are independently scrambled
+    nets, and with block = 0 no column depends on n, so the columns [n, 2 n) of a design of 2 n continue a design of n."""
     device = torch.device(device)
     if engine is None:
         from .simulator import shared_engine
         engine = shared_engine(device)
     kinds = [_abi.DESIGN_NORMAL] * (17 + 3 * int(K)) + [_abi.DESIGN_UNIFORM] * 2
+    if design == "qmc":
+        return engine.qmc(kinds, n, seed, dims=qmc_dims(K), scramble="owen", pad="random", block=block, first=first, count=count)
     return engine.design(kinds, n, seed, kind=design, block=block, first=first, count=count)
+
+
+def qmc_dims(K, liquid=True):
+    """The Sobol' dimension of every row of the primitive tensor for `design_draws(design='qmc')`, -1 for a pad row.  The
+    low dimensions of a Sobol' sequence are its best, so the scalar primitives of `scalar_primitives` take them, in its
+    order - wind speed and direction, the last two ROWS, among them - then the 3 K turbulence innovations in row order as
+    far as the 1024 dimensions of erpl_mc_qmc go.  What is left of those, and the dead draws, are pad rows."""
+    K = int(K)
+    dims = [-1] * primitive_rows(K)
+    order = list(scalar_primitives(K, liquid).values()) + list(range(17, 17 + 3 * K))
+    for d, r in enumerate(order[:_abi.QMC_MAX_DIMS]):
+        dims[r] = d
+    return dims
 
 
 def primitive_groups(K, liquid=True):

@@ -574,6 +574,75 @@ int erpl_mc_design(erpl_ctx* ctx, const erpl_design_spec* spec, const uint8_t* k
 int erpl_mc_design_host(const erpl_design_spec* spec, const uint8_t* kinds, int64_t first, int64_t count, double* out,
                         int64_t ld);
 
+/* The primitives of a run as a SCRAMBLED SOBOL' DESIGN padded with a hypercube, drawn ON THE DEVICE (no reference
+ * counterpart): a digital net balances the low-order interactions of its rows as well as each row, and it is a sequence -
+ * column i does not depend on n, so a run can be continued and stay balanced.  Everything of erpl_mc_design carries over:
+ * the design is a matrix of rows x n doubles defined by (seed, n, block, scramble, pad, first_row, dims); a call produces its
+ * columns first .. first + count - 1 into out[rows][ld] (device memory; host memory for erpl_mc_qmc_host), ld >= count, the
+ * entries [.., count .. ld - 1] never written; `kinds` [rows] as there; counter-based, so any window is generated anywhere,
+ * without communication; asynchronous on `hip_stream`; count == 0 is ERPL_OK and writes nothing; two calls with the same
+ * arguments return the same bytes and a window equals the same columns of the full call, bit for bit.  `kinds`, `dims` and
+ * the spec are host memory.  The device copy of the direction numbers (128 KB) belongs to the context, is made by the first
+ * call (which therefore blocks once) and freed by erpl_mc_destroy.
+ * Dimensions: dims[r] is the Sobol' dimension 0 .. ERPL_QMC_MAX_DIMS - 1 of row r of the call, or -1 for a PAD row.
+ * dims == NULL means dims[r] = first_row + r where that is below ERPL_QMC_MAX_DIMS, and -1 beyond.  Two rows of one call
+ * must not share a dimension (they would be the same numbers up to the scramble): refused.  CALLS WITH DIFFERENT first_row
+ * MUST NOT SHARE A DIMENSION EITHER, AND NOTHING CHECKS THAT.
+ * ERPL_ERR_INVALID, before any device work and with a message that names the argument, for: a NULL spec, kinds or out; an
+ * unknown spec->scramble; a spec->pad that is neither ERPL_DESIGN_RANDOM nor ERPL_DESIGN_LHS; then rows / first_row, n,
+ * block, first, count, first + count, ld and the bytes of `kinds` exactly as erpl_mc_design; a dims[r] below -1 or of
+ * ERPL_QMC_MAX_DIMS or more; two rows on one dimension - in this order, the context last.
+ *
+ * Replicate and index: rho = i / m, l = i % m, block = m, 0 meaning m = n, as in erpl_mc_design.  The replicates are
+ * independently scrambled copies of the first m points.  n may be any value in 1 .. 2^31 - 1 and m need not be a power of
+ * two; THE BALANCE PROPERTIES HOLD FOR ALIGNED BLOCKS OF 2^k COLUMNS of a replicate (l in [j 2^k, (j + 1) 2^k)): in every
+ * row such a block puts one p into each interval [t / 2^k, (t + 1) / 2^k), and the rows together form a (t, s)-sequence
+ * in base 2 with the quality of the Joe-Kuo numbers.
+ * Raw point: x = XOR over the set bits j of l (j = 0 .. 30) of V[d][j], d = dims[r]: direct binary order, not Gray code
+ * (with k = inverse_gray(i) this x is 2^32 times point k of scipy.stats.qmc.Sobol(scramble=False, bits=32)).  V[d][j] are
+ * the 32-bit direction numbers of S. Joe and F. Y. Kuo (new-joe-kuo-6.21201, SIAM J. Sci. Comput. 30, 2008):
+ * V[0][j] = 2^(31 - j); for d >= 1 with the primitive polynomial x^s + a_1 x^(s-1) + .. + a_(s-1) x + 1 and the initial
+ * m_1 .. m_s: m_k = 2 a_1 m_(k-1) ^ 4 a_2 m_(k-2) ^ .. ^ 2^(s-1) a_(s-1) m_(k-s+1) ^ 2^s m_(k-s) ^ m_(k-s) and
+ * V[d][j] = m_(j+1) 2^(31 - j).
+ * ERPL_QMC_OWEN, a nested uniform scramble applied lazily: for k = 0 .. 31, counted from the most significant bit, output
+ * bit k is bit k of x XOR flip_k, flip_k = fmix32(fmix32((s_k + k0) mod 2^32) ^ k1) >> 31, s_k = (1 << k) | (x >> (32 - k))
+ * - the k bits of the UNSCRAMBLED x above bit k under a sentinel bit, s_0 = 1 - with fmix32 as in erpl_mc_design and
+ * k0, k1 the words 0 and 1 of Philox4x32-10 under the key (seed & 0xffffffff, seed >> 32) on the counter (r, 0, rho, 4), r
+ * the GLOBAL row.  Tag 4 in counter word 3 keeps the keys apart from the families 0 .. 3 (erpl_mc_bootstrap, erpl_mc_design,
+ * erpl_mc_subset_propose).  Every node of the binary tree of prefixes has its own coin, so the scrambled points of a row
+ * are again a net and each is uniform on its own.  Probability: s = (double)x' + u with u the jitter of erpl_mc_design for
+ * (seed, r, i) - the low bits are fresh draws - and the double just below x' + 1 where s >= x' + 1; p = s 2^-32, in
+ * [x' 2^-32, (x' + 1) 2^-32) and strictly inside (0, 1).
+ * ERPL_QMC_RAW, for tests and for hosts that compare with a library: no scramble and no jitter, p = (x + 0.5) 2^-32.  ITS
+ * FIRST COLUMN (l = 0) IS THE POINT 2^-33 IN EVERY ROW, AND ITS ROWS ARE THE SAME FOR EVERY SEED AND REPLICATE: NOT TO BE FLOWN.
+ * Normal rows: PPND16 of p, as erpl_mc_design.
+ * Pad rows (Owen's padding: Sobol' points in very high dimensions are poor, and what is left over is individually
+ * unimportant): exactly the value erpl_mc_design writes for (seed, kind = spec->pad, n, block, the same global row, i) - bit
+ * for bit on uniform rows.  With pad = ERPL_DESIGN_LHS a pad row depends on n (or block) as every hypercube does; with
+ * ERPL_DESIGN_RANDOM and block = 0 no column of the design depends on n.  A cycle walk of a pad row that is given up is
+ * reported as by erpl_mc_design: erpl_mc_qmc_host returns ERPL_ERR_INTERNAL, erpl_mc_qmc leaves it to erpl_mc_synchronize
+ * or erpl_mc_check_batch(ticket <= 0), which wait for the latest erpl_mc_design or erpl_mc_qmc call. */
+#define ERPL_QMC_MAX_DIMS 1024
+enum { ERPL_QMC_RAW = 0, ERPL_QMC_OWEN = 1 };   /* erpl_qmc_spec.scramble */
+
+typedef struct erpl_qmc_spec {
+  int32_t rows;                          /* rows of this call, >= 1 */
+  int32_t first_row;                     /* global row of its first row; first_row + rows <= ERPL_DESIGN_MAX_ROWS */
+  int32_t scramble;                      /* ERPL_QMC_RAW / ERPL_QMC_OWEN */
+  int32_t pad;                           /* ERPL_DESIGN_RANDOM or ERPL_DESIGN_LHS: the rule of the rows with dims[r] < 0 */
+  int64_t n;                             /* columns of the whole design, 1 <= n < 2^31 */
+  int64_t block;                         /* m: columns of a replicate, a divisor of n; 0 = n */
+  uint64_t seed;
+} erpl_qmc_spec;
+
+/* Host only: ERPL_QMC_OWEN, pad ERPL_DESIGN_RANDOM, rows 1, first_row 0, n 1, block 0, seed 0. */
+int erpl_mc_qmc_defaults(erpl_qmc_spec* spec);
+int erpl_mc_qmc(erpl_ctx* ctx, const erpl_qmc_spec* spec, const uint8_t* kinds, const int32_t* dims, int64_t first,
+                int64_t count, double* out, int64_t ld, void* hip_stream);
+/* Host only, no context, no device: the same code into host memory. */
+int erpl_mc_qmc_host(const erpl_qmc_spec* spec, const uint8_t* kinds, const int32_t* dims, int64_t first, int64_t count,
+                     double* out, int64_t ld);
+
 /* Outlier filter + statistics of a finished run ON THE DEVICE, replacing MonteCarloAnalyzer.
  * _filter_physics_outliers + _analyze_results (monte_carlo.py:337-398, :400-473) for the scalar results:
  * which samples are physically unreasonable and why, and count / mean / population std / min / max / quantiles
