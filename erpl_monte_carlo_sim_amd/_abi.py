@@ -499,6 +499,36 @@ class ErplSubsetTriple(C.Structure):
                 ("rows", C.c_int32), ("elem_size", C.c_int32)]
 
 
+# erpl_mc_reweight
+RW_MAX_LAW = 32
+RW_MAX_ROWS = 4
+RW_ROW_EXTRA = 16
+RW_MAX_THRESHOLDS = 8
+RW_MAX_Q = 8
+
+
+class ErplRwSpec(C.Structure):
+    _fields_ = [("n_law", C.c_int32), ("kind", C.c_uint8 * RW_MAX_LAW), ("reserved", C.c_int32),
+                ("mu", C.c_double * RW_MAX_LAW), ("s", C.c_double * RW_MAX_LAW),
+                ("a", C.c_double * RW_MAX_LAW), ("b", C.c_double * RW_MAX_LAW),
+                ("n_rows", C.c_int32), ("rows", C.c_int32 * RW_MAX_ROWS), ("n_thresholds", C.c_int32 * RW_MAX_ROWS),
+                ("n_q", C.c_int32), ("threshold", (C.c_double * RW_MAX_THRESHOLDS) * RW_MAX_ROWS), ("q", C.c_double * RW_MAX_Q)]
+
+
+class ErplRwRowStats(C.Structure):
+    _fields_ = [("mean", C.c_double), ("mean_se", C.c_double), ("var", C.c_double), ("std", C.c_double),
+                ("min", C.c_double), ("max", C.c_double), ("quantile", C.c_double * RW_MAX_Q),
+                ("exceed_w", C.c_int64 * RW_MAX_THRESHOLDS), ("p", C.c_double * RW_MAX_THRESHOLDS),
+                ("p_se", C.c_double * RW_MAX_THRESHOLDS)]
+
+
+class ErplReweight(C.Structure):
+    _fields_ = [("n", C.c_int64), ("count", C.c_int64), ("n_masked", C.c_int64), ("n_non_finite", C.c_int64),
+                ("n_outside", C.c_int64), ("n_zero", C.c_int64), ("sum_w", C.c_int64), ("max_w", C.c_int64),
+                ("Q", C.c_int32), ("reserved", C.c_int32), ("sum_w2", C.c_double), ("ess", C.c_double),
+                ("ess_expected_share", C.c_double), ("row", ErplRwRowStats * RW_MAX_ROWS)]
+
+
 LIB_NAME = "liberpl_mc.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
@@ -534,7 +564,8 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_tally_add_host", "erpl_mc_tally_merge_host", "erpl_mc_tally_result_host",
            "erpl_mc_subset_defaults", "erpl_mc_subset_limit_state", "erpl_mc_subset_limit_state_host",
            "erpl_mc_subset_seeds", "erpl_mc_subset_seeds_host", "erpl_mc_subset_propose", "erpl_mc_subset_propose_host",
-           "erpl_mc_subset_commit", "erpl_mc_subset_commit_host", "erpl_mc_subset_chain_stats", "erpl_mc_subset_chain_stats_host")
+           "erpl_mc_subset_commit", "erpl_mc_subset_commit_host", "erpl_mc_subset_chain_stats", "erpl_mc_subset_chain_stats_host",
+           "erpl_mc_reweight_defaults", "erpl_mc_reweight", "erpl_mc_reweight_host")
 
 _lib = None
 
@@ -680,6 +711,11 @@ def load_library(path=None):
                        ("chain_stats", chain_stats)):
         getattr(lib, f"erpl_mc_subset_{name}").argtypes = [C.c_void_p] + args + [C.c_void_p]   # ctx .. hip_stream
         getattr(lib, f"erpl_mc_subset_{name}_host").argtypes = args
+    lib.erpl_mc_reweight_defaults.argtypes = [C.POINTER(ErplRwSpec)]
+    reweight = [C.POINTER(ErplRwSpec), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                C.POINTER(ErplReweight), C.c_void_p, C.c_void_p]
+    lib.erpl_mc_reweight.argtypes = [C.c_void_p] + reweight + [C.c_void_p]   # ctx .. hip_stream
+    lib.erpl_mc_reweight_host.argtypes = reweight
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if a declared symbol is not exported
         if name not in ("erpl_mc_last_error",):

@@ -1431,3 +1431,145 @@ def subset_simulation(evaluate, draws0, kinds, *, chains, steps, target=None, ma
             "thresholds": [lv["threshold"] for lv in levels], "curve": np.concatenate(curve)[:, :2], "curve_cov": np.concatenate(curve)[:, 2],
             "population": {"draws": pop, "summary": summ, "status": status, "g": g, "indicator": sel}, "level0": level0,
             "chains": C_, "steps": T, "evaluations": evaluations, "samples": populations * N, "warnings": warnings}
+
+
+# ---------------------------------------------------------------------------------- reweighting: a flown run under another law
+def reweight_spec(kinds, law, rows=None, thresholds=None, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95)):
+    """The spec of erpl_mc_reweight (_abi.ErplRwSpec) on top of the library's defaults.  kinds: per law row
+    _abi.DESIGN_NORMAL or _abi.DESIGN_UNIFORM; law: per law row the target, (mu, s) in flown sigmas for a normal row and
+    (a, b) within the flown (0, 1) for a uniform row.  rows: up to 4 summary rows (ROW_NAMES or index, _abi.RW_ROW_EXTRA for
+    `extra`; default apogee, range, flight time); thresholds: None or a mapping row -> up to 8 thresholds (keys as in
+    `rows`); quantiles: up to 8.  A pure host function; the values are checked by the library."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    spec = _abi.ErplRwSpec()
+    _abi.check(lib, lib.erpl_mc_reweight_defaults(C.byref(spec)), "erpl_mc_reweight_defaults")
+    kinds = [int(k) for k in kinds]
+    law = [tuple(float(v) for v in p) for p in law]
+    if len(kinds) != len(law) or not 1 <= len(kinds) <= _abi.RW_MAX_LAW or any(len(p) != 2 for p in law):
+        raise ValueError(f"kinds and law: one entry per law row, 1 to {_abi.RW_MAX_LAW} of them, law entries (mu, s) or (a, b)")
+    spec.n_law = len(kinds)
+    for r, (k, p) in enumerate(zip(kinds, law)):
+        spec.kind[r] = k & 0xFF
+        if k == _abi.DESIGN_NORMAL:
+            spec.mu[r], spec.s[r] = p
+        else:
+            spec.a[r], spec.b[r] = p
+    if rows is not None:
+        ids = [_abi.RW_ROW_EXTRA if r == "extra" else _row_id(r) for r in rows]
+        if not 1 <= len(ids) <= _abi.RW_MAX_ROWS:
+            raise ValueError(f"1 to {_abi.RW_MAX_ROWS} rows")
+        spec.n_rows = len(ids)
+        spec.rows[:len(ids)] = ids
+    have = list(spec.rows[:spec.n_rows])
+    for key, values in (thresholds or {}).items():
+        r = _abi.RW_ROW_EXTRA if key == "extra" else _row_id(key)
+        if r not in have:
+            raise ValueError(f"thresholds: row {key!r} is not among the requested rows")
+        values = [float(v) for v in values]
+        if len(values) > _abi.RW_MAX_THRESHOLDS:
+            raise ValueError(f"at most {_abi.RW_MAX_THRESHOLDS} thresholds per row")
+        j = have.index(r)
+        spec.n_thresholds[j] = len(values)
+        spec.threshold[j][:len(values)] = values
+    quantiles = [float(q) for q in quantiles]
+    if len(quantiles) > _abi.RW_MAX_Q:
+        raise ValueError(f"at most {_abi.RW_MAX_Q} quantiles")
+    spec.n_q = len(quantiles)
+    spec.q[:len(quantiles)] = quantiles
+    return spec
+
+
+def reweight_result_dict(spec, res):
+    """An _abi.ErplReweight as a plain dict: the counts, Q, sum_w, max_w (Python ints), sum_w2, ess, ess_expected_share and
+    'rows': per requested row id its mean, mean_se, var, std, min, max, q / quantiles and thresholds / exceed_w / p / p_se."""
+    out = {k: int(getattr(res, k)) for k in ("n", "count", "n_masked", "n_non_finite", "n_outside", "n_zero", "Q", "sum_w", "max_w")}
+    out.update(sum_w2=res.sum_w2, ess=res.ess, ess_expected_share=res.ess_expected_share)
+    nq = spec.n_q
+    out["rows"] = {}
+    for j in range(spec.n_rows):
+        r, nt = res.row[j], spec.n_thresholds[j]
+        out["rows"][int(spec.rows[j])] = {
+            "mean": r.mean, "mean_se": r.mean_se, "var": r.var, "std": r.std, "min": r.min, "max": r.max,
+            "q": list(spec.q[:nq]), "quantiles": list(r.quantile[:nq]), "thresholds": list(spec.threshold[j][:nt]),
+            "exceed_w": [int(v) for v in r.exceed_w[:nt]], "p": list(r.p[:nt]), "p_se": list(r.p_se[:nt])}
+    return out
+
+
+def reweight_host(factors, kinds, law, summary, mask=None, rows=None, extra=None, thresholds=None,
+                  quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), want_weights=False):
+    """erpl_mc_reweight_host on NumPy arrays - TrajectoryEngine.reweight without a device, the same integers and the same
+    log-weights: factors float64 [n_law, n] (unit column stride), summary float64 [16, n] (likewise), mask uint8 [n] or None,
+    extra float64 [n] or None.  Returns the dict of `reweight_result_dict`; want_weights adds 'logw' (float64 [n]) and
+    'weights' (int64 [n])."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    spec = reweight_spec(kinds, law, rows, thresholds, quantiles)
+    n_law, ld = _np_matrix(factors, np.float64, "factors")
+    n = int(factors.shape[-1])
+    s_rows, ld_s = _np_matrix(summary, np.float64, "summary")
+    if n_law != spec.n_law or s_rows != _abi.SUMMARY_DIM or summary.shape[1] != n:
+        raise ValueError(f"factors must be [{spec.n_law}, n] and summary [{_abi.SUMMARY_DIM}, n]")
+    if mask is not None:
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        if mask.shape != (n,):
+            raise ValueError("mask must be [n]")
+    if extra is not None:
+        extra = np.ascontiguousarray(extra, dtype=np.float64)
+        if extra.shape != (n,):
+            raise ValueError("extra must be [n]")
+    logw = np.empty(n, dtype=np.float64) if want_weights else None
+    weights = np.empty(n, dtype=np.int64) if want_weights else None
+    res = _abi.ErplReweight()
+    _abi.check(lib, lib.erpl_mc_reweight_host(C.byref(spec), _np_ptr(factors), ld, _np_ptr(summary), ld_s, _np_ptr(extra), _np_ptr(mask), n,
+                                              C.byref(res), _np_ptr(logw), _np_ptr(weights)), "erpl_mc_reweight_host")
+    out = reweight_result_dict(spec, res)
+    if want_weights:
+        out["logw"], out["weights"] = logw, weights
+    return out
+
+
+def finish_reweighted(out):
+    """What `reweighted_statistics` adds to the dict of TrajectoryEngine.reweight that needs no device (in place): 'ess_share'
+    = ess / (count + n_outside) - the share of the FLOWN samples, those outside the target's support included, which is what
+    ess_expected_share is the expectation of - 'max_weight_share' = max_w / sum_w, 'row_names', and 'warnings' - an infinite weight variance
+    (ess_expected_share == 0: a normal row widened to s^2 >= 2), ess < 100, max_weight_share > 0.1, an empty support."""
+    from . import _abi
+    empty = out["count"] == 0 or out["sum_w"] == 0
+    out["ess_share"] = math.nan if empty else out["ess"] / (out["count"] + out["n_outside"])
+    out["max_weight_share"] = math.nan if empty else out["max_w"] / out["sum_w"]
+    out["row_names"] = ["extra" if r == _abi.RW_ROW_EXTRA else ROW_NAMES[r] for r in out["rows"]]
+    warnings = []
+    if out["ess_expected_share"] == 0.0:
+        warnings.append("the variance of the weights is infinite (a normal row is widened to s^2 >= 2): no error bar holds")
+    if empty:
+        warnings.append("the support is empty: no flown sample lies inside the target law")
+    else:
+        if out["ess"] < 100.0:
+            warnings.append(f"the effective sample size is {out['ess']:.1f}, below 100: fly a new run")
+        if out["max_weight_share"] > 0.1:
+            warnings.append(f"one sample carries {100.0 * out['max_weight_share']:.1f} % of the weight")
+    out["warnings"] = warnings
+    return out
+
+
+def reweighted_statistics(summary, factors, kinds, law, status=None, engine=None, rows=None, extra=None, thresholds=None,
+                          quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), want_weights=False):
+    """The statistics of a flown run of INDEPENDENT primitives (a run flown with design=...) under another input law, without
+    a new run: erpl_mc_analyze for the reason bytes (as `drivers`), then erpl_mc_reweight (TrajectoryEngine.reweight) of
+    the changed primitive rows `factors` (float64 [n_law, n] device tensor; `kinds`, `law` as in `reweight_spec`) over the
+    samples the filter keeps.  Returns the dict of TrajectoryEngine.reweight - per row mean +- mean_se, std, quantiles and
+    the exceedance probabilities p +- p_se - plus 'n_samples', 'n_outliers' and what `finish_reweighted` adds: ess_share,
+    max_weight_share, row_names and warnings.
+
+    Reading it: the error bars are the delta method for a ratio of sums over i.i.d. columns - conservative for an 'lhs' or
+    'qmc' run.  Trust the answer as far as ess goes: narrowing a law works, widening one does not (the heaviest tail
+    samples take the weight), and ess_share is a product over the changed rows, so changing many at once costs
+    exponentially."""
+    engine, res, why = _filter(summary, status, engine)
+    out = engine.reweight(factors, kinds, law, summary, mask=why, rows=rows, extra=extra, thresholds=thresholds, quantiles=quantiles,
+                          want_weights=want_weights)
+    out["n_samples"], out["n_outliers"] = int(res.n_valid), int(res.n_outliers)
+    return finish_reweighted(out)

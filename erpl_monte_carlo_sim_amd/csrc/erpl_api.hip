@@ -475,6 +475,8 @@ int erpl_mc_destroy(erpl_ctx* c) {
   c->subset.release();
   if (c->subset_pin) (void)hipHostFree(c->subset_pin);
   if (c->subset_ev) (void)hipEventDestroy(c->subset_ev);
+  c->reweight.release();
+  if (c->reweight_pin) (void)hipHostFree(c->reweight_pin);
   delete c;
   return ERPL_OK;
 }

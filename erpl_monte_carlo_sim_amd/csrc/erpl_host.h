@@ -1,5 +1,5 @@
 // erpl_host.h — what the host units of the C ABI share (erpl_api.hip, erpl_sampling.hip, erpl_stats_api.hip,
-// erpl_legacy_device.hip, erpl_design.hip, erpl_qmc.hip, erpl_tally.hip, erpl_subset.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
+// erpl_legacy_device.hip, erpl_design.hip, erpl_qmc.hip, erpl_tally.hip, erpl_subset.hip, erpl_reweight.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
 // Internal, never installed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -258,6 +258,10 @@ struct erpl_ctx {
   ErplStatUnit<void, char> subset;
   char* subset_pin = nullptr;
   hipEvent_t subset_ev = nullptr;
+  // erpl_mc_reweight: the pieces of erpl_stat_layout.h in the buffer (the partials and the selection state of
+  // erpl_reweight.hip, the log-weights and the weights the caller does not keep); the pinned copy of the sums it hands back
+  ErplStatUnit<void, char> reweight;
+  char* reweight_pin = nullptr;
 };
 
 // erpl_design.hip

@@ -1,5 +1,6 @@
 // erpl_stat_device.h — what the statistics units (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip,
-// erpl_bootstrap.hip, erpl_density.hip, erpl_corridor.hip, erpl_sobol.hip, erpl_dependence.hip, erpl_compare.hip) share:
+// erpl_bootstrap.hip, erpl_density.hip, erpl_corridor.hip, erpl_sobol.hip, erpl_dependence.hip, erpl_compare.hip,
+// erpl_reweight.hip) share:
 // the grid of their streaming passes, the order-preserving keys, the run of equal keys behind a mid-rank, THE fixed-order
 // reduction and the steps of the radix selection.
 // Internal: never installed.
@@ -209,6 +210,28 @@ __device__ __forceinline__ void select_count(unsigned int (*hist)[ERPL_ANA_BINS]
       if ((int)(threadIdx.x & 63) == lead_lane) atomicAdd(&hist[lead[m]][d0], (unsigned int)__popcll(mask));
     } else if (hit) {
       atomicAdd(&hist[lead[m]][digit], 1u);
+    }
+  }
+}
+
+// The weighted sibling (erpl_reweight.hip): the key counts w times, the bins are 64-bit.  A wave whose hits share one bin adds
+// their weights up with a shuffle tree first (integer adds: the order does not matter) and makes one add of it.
+__device__ __forceinline__ void select_count_weighted(u64 (*hist)[ERPL_ANA_BINS], const int* lead, const u64* prefix, int nlead,
+                                                      bool use, u64 key, int shift, u64 w) {
+  const u64 above = shift >= 56 ? 0ull : (~0ull << (shift + 8));
+  const unsigned int digit = (unsigned int)(key >> shift) & (ERPL_ANA_BINS - 1);
+  for (int m = 0; m < nlead; ++m) {
+    const bool hit = use && ((key ^ prefix[m]) & above) == 0ull;
+    const u64 mask = __ballot(hit);
+    if (mask == 0ull) continue;
+    const int lead_lane = __ffsll((long long)mask) - 1;
+    const unsigned int d0 = (unsigned int)__shfl((int)digit, lead_lane);
+    if (__ballot(hit && digit != d0) == 0ull) {
+      u64 s = hit ? w : 0ull;
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+      if ((threadIdx.x & 63) == 0 && s) atomicAdd(&hist[lead[m]][d0], s);
+    } else if (hit && w) {
+      atomicAdd(&hist[lead[m]][digit], w);
     }
   }
 }

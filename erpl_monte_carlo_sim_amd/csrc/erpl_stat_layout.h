@@ -1,5 +1,5 @@
 // erpl_stat_layout.h — how erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density, erpl_mc_sobol,
-// erpl_mc_dependence, erpl_mc_compare and erpl_mc_surrogate cut the device buffer each of them grows into pieces: pure functions
+// erpl_mc_dependence, erpl_mc_compare, erpl_mc_surrogate and erpl_mc_reweight cut the device buffer each of them grows into pieces: pure functions
 // of the call's sizes (no HIP; the scratch size of the rocPRIM calls comes in as a number), so that tests/test_stat_layout.py,
 // tests/test_dependence_layout.py, tests/test_compare_layout.py and tests/test_surrogate_abi.py check every offset on the CPU, through
 // erpl_stat_layout_table, before a kernel writes through one.  Every piece starts at a multiple of 256 bytes; `need` is the
@@ -234,5 +234,20 @@ inline ErplCompareLayout erpl_compare_layout(int64_t n_a, int64_t n_b, int64_t N
   l.epart = d.take(bivariate ? 8 * 3 * cols * tiles * (size_t)l.slices : 0);
   l.eout = d.take(8 * 3 * all);
   l.need = d.end;
+  return l;
+}
+
+// erpl_mc_reweight over n columns: [work: the partials of the workgroups, the state of the selection and the sums handed back,
+// work_bytes of them (the struct is erpl_reweight.hip's)][logw n doubles unless the caller keeps them][weights n int64 unless
+// the caller keeps them]
+struct ErplRwLayout { size_t work, logw, weights, need; };
+inline ErplRwLayout erpl_rw_layout(int64_t n, bool caller_keeps_logw, bool caller_keeps_weights, size_t work_bytes) {
+  const size_t un = (size_t)n;
+  ErplCarve c;
+  ErplRwLayout l = {};
+  l.work = c.take(work_bytes);
+  l.logw = c.take(caller_keeps_logw ? 0 : 8 * un);
+  l.weights = c.take(caller_keeps_weights ? 0 : 8 * un);
+  l.need = c.end;
   return l;
 }

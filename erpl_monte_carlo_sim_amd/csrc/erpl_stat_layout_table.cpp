@@ -18,6 +18,7 @@
 //                                                                           members into (-1: a chunk its slices do not cover), the
 //                                                                           first length that has them, erpl_sur_max_slices(hi, P)
 //   surslice <len> <P>                                                   -> slices slice_len of one chunk
+//   rw <n> <caller_keeps_logw> <caller_keeps_weights> <work_bytes>       -> work logw weights need
 #include <stdio.h>
 
 #include <initializer_list>
@@ -92,6 +93,10 @@ int main() {
       int len = 0;
       const int s = erpl_sur_slices(n, a, &len);
       printf("%d %d\n", s, len);
+    } else if (sscanf(line, "rw %lld %d %d %zu", &n, &a, &b, &temp) == 4) {
+      const ErplRwLayout l = erpl_rw_layout(n, a != 0, b != 0, temp);
+      for (size_t v : {l.work, l.logw, l.weights}) put(v);
+      put(l.need, "\n");
     } else {
       fprintf(stderr, "bad request: %s", line);
       return 1;

@@ -1221,6 +1221,43 @@ class TrajectoryEngine:
             out["gram"], out["rhs"] = gram, rhs
         return out
 
+    def reweight(self, factors, kinds, law, summary, mask=None, rows=None, extra=None, thresholds=None,
+                 quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), want_weights=False):
+        """The statistics of a flown run under ANOTHER input law, by importance weights (erpl_mc_reweight), no new run.
+        `factors` (float64 [n_law, n] on the device, unit column stride, n_law <= 32) holds the primitive rows whose law
+        changes, as `design` / `qmc` drew them; `kinds`: _abi.DESIGN_NORMAL for a row flown under N(0, 1), _abi.DESIGN_UNIFORM
+        for U(0, 1); `law`: per row the target, (mu, s) in flown sigmas or (a, b) within (0, 1) (analysis.reweight_spec,
+        which also takes rows, thresholds and quantiles).  One population: mask byte 0, every law row and requested row
+        finite, inside the support of every uniform target.  Weights are integers W = floor(2^Q exp(l - l_max)), so sum_w,
+        max_w, the exceedances and the weighted order statistics are exact and the same bits in every call; the doubles are
+        folded in a fixed order.  Returns the dict of analysis.reweight_result_dict; want_weights adds 'logw' (float64 [n]:
+        NaN where masked or non-finite, -inf outside the support) and 'weights' (int64 [n]) device tensors, bit-equal to
+        analysis.reweight_host.  An empty population is no error: the integers are 0 and the doubles NaN."""
+        from . import analysis
+        rows_s, ld_s, _ = self._matrix(summary, "summary")
+        n = int(summary.shape[-1])
+        if rows_s != _abi.SUMMARY_DIM or summary.dtype != torch.float64 or summary.dim() != 2:
+            raise ValueError(f"summary must be float64 [{_abi.SUMMARY_DIM}, n]")
+        n_law, ld, _ = self._matrix(factors, "factors")
+        if factors.dtype != torch.float64 or int(factors.shape[-1]) != n:
+            raise ValueError("factors must be float64 [n_law, n]")
+        spec = analysis.reweight_spec(kinds, law, rows, thresholds, quantiles)
+        if n_law != spec.n_law:
+            raise ValueError(f"kinds and law must have one entry per row of factors ({n_law})")
+        mask_p = None if mask is None else self._vector(mask, n, torch.uint8, "mask")
+        extra_p = None if extra is None else self._vector(extra, n, torch.float64, "extra")
+        logw = torch.empty(n, dtype=torch.float64, device=self.device) if want_weights else None
+        weights = torch.empty(n, dtype=torch.int64, device=self.device) if want_weights else None
+        res = _abi.ErplReweight()
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_reweight", C.byref(spec), C.c_void_p(factors.data_ptr()), ld, C.c_void_p(summary.data_ptr()), ld_s,
+                   extra_p, mask_p, n, C.byref(res), C.c_void_p(logw.data_ptr()) if want_weights else None,
+                   C.c_void_p(weights.data_ptr()) if want_weights else None, C.c_void_p(st.cuda_stream))
+        out = analysis.reweight_result_dict(spec, res)
+        if want_weights:
+            out["logw"], out["weights"] = logw, weights
+        return out
+
     def surrogate_predict(self, model, X, out=None, n=None):
         """The fitted outcomes of `model` (the 'model' of `surrogate`) at the columns 0 .. n - 1 (default: all) of X, a
         float64 [V, ld] device tensor with unit column stride, without a flight (erpl_mc_surrogate_predict): a float64

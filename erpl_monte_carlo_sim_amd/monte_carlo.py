@@ -1114,6 +1114,50 @@ class MonteCarloAnalyzer:
         out["factors"], out["primitive_rows"] = factors, prim
         return out
 
+    def reweight(self, analysis, uncertainty=None, motor=None, shift=None, rows=None, thresholds=None,
+                 quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), planar=False):
+        """What a run flown with `run_monte_carlo_device(design=...)` says under ANOTHER input law (no reference counterpart,
+        no extra flights): `analysis.reweighted_statistics` - per row mean +- se, std, quantiles and exceedance
+        probabilities +- se, with ess, ess_share, ess_expected_share, max_weight_share and warnings - for the target
+        `uncertainty` table (entries on top of the flown `uncertainty_params`), a target `motor` (its thrust_uncertainty /
+        mass_flow_uncertainty against the flown motor's) and `shift` (a mean in flown sigmas per primitive), through
+        `sampling.law_change`.  Only the changed primitive rows are regenerated, from analysis["design"] through
+        `TrajectoryEngine.design(first_row=...)` (`.qmc` for design='qmc'): the bits the run flew.  planar: the run was flown
+        with planar=True, the rows Set P zeroes are left out.  ValueError for a run without `design`: under the reference's
+        joint law the inputs are not independent (one normal is the thrust multiplier, position_x and the first turbulence
+        innovation at once), and the density ratio is not a product of row factors."""
+        from . import analysis as ana, sampling
+        from .flatten import motor_kind
+        if "design" not in analysis:
+            raise ValueError("reweight needs a run flown with run_monte_carlo_device(design=...): the inputs of the joint law are not "
+                             "independent, and the density ratio of two laws is a product of row factors only for independent inputs")
+        if dist.world()[1] > 1:
+            raise ValueError("reweight is limited to a world size of 1")
+        eng = shared_engine(self.device)
+        use_base = self.base_wind_profile is not None and self.base_altitude_profile is not None
+        K = len(self.base_altitude_profile) if use_base else 100      # as run_monte_carlo_device drew the design
+        change = sampling.law_change(K, motor_kind(self.motor) != _abi.MOTOR_SOLID, self.uncertainty_params, uncertainty, motor=self.motor,
+                                     target_motor=motor, shift=shift, planar=planar)
+        if not change:
+            raise ValueError("the target law is the flown one: no primitive changes")
+        prim = list(change)
+        kinds = [change[r][0] for r in prim]
+        law = [change[r][1:3] if change[r][0] == _abi.DESIGN_NORMAL else change[r][3:5] for r in prim]
+        d = analysis["design"]
+        summ = analysis["summary"]
+        n = int(summ.shape[1])
+        factors = torch.empty((len(prim), n), dtype=torch.float64, device=eng.device)
+        qdims = sampling.qmc_dims(K) if d["kind"] == "qmc" else None      # as `sampling.design_draws` laid the rows out
+        for i, r in enumerate(prim):
+            if qdims is not None:
+                eng.qmc([kinds[i]], n, d["seed"], dims=[qdims[r]], block=d["block"], first_row=r, out=factors[i:i + 1])
+            else:
+                eng.design([kinds[i]], n, d["seed"], kind=d["kind"], block=d["block"], first_row=r, out=factors[i:i + 1])
+        out = ana.reweighted_statistics(summ, factors, kinds, law, status=analysis.get("status"), engine=eng, rows=rows,
+                                        thresholds=thresholds, quantiles=quantiles)
+        out["primitive_rows"], out["law"] = prim, change
+        return out
+
     def plot_surrogate(self, surrogate, save_plots=True):
         """No reference counterpart: per row the first-order and total indices of the variables, the largest pair indices
         and predicted against flown on the held-out members, saved as monte_carlo_surrogate.png in the output directory;

@@ -135,6 +135,101 @@ def scalar_primitives(K, liquid=True):
     return out
 
 
+_SIGMA_ROWS = {"initial_position": (0, 1, 2), "initial_velocity": (3, 4, 5), "initial_attitude": (6, 7, 8),
+               "initial_angular_velocity": (9, 10, 11)}
+_PLANAR_ZEROED = (4, 6, 8, 9, 11)    # velocity y, roll, yaw, angular velocity x and z: Set P multiplies them by zero
+
+
+def law_change(K, liquid, flown, target, motor=None, target_motor=None, shift=None, planar=False):
+    """The primitives whose law differs between two uncertainty tables of `synthetic_dispersions(draws=...)`, as erpl_mc_reweight
+    takes them: an ordered mapping primitive row -> (kind, mu, s, a, b), ascending in the row, at most 32.
+
+    flown, target: uncertainty tables (None or partial: DEFAULT_UNCERTAINTY, then `flown`, then `target` on top).  The sigma
+    entries initial_position, initial_velocity, initial_attitude and initial_angular_velocity are per component and, like
+    mass_uncertainty (row 12), give a normal row with s = target / flown: the flown value is base + sigma z, so under the
+    target z ~ N(0, s^2) in flown sigmas.  wind_speed_range and wind_direction_range (the last two rows) give a uniform
+    row with (a, b) = the target range within the flown one.  The motor's thrust_uncertainty (row 14) and, for a liquid
+    motor, mass_flow_uncertainty (row 15) are read from `motor` (flown) and `target_motor`.  shift: a mapping
+    `scalar_primitives` name (or the row of a normal primitive) -> mu, the target mean in flown sigmas.
+    planar=True leaves out the rows Set P zeroes: they reach no outcome, and weighting them only adds noise.
+
+    ValueError: a flown sigma of 0 with another target (nothing was varied: there is nothing to reweight); a target sigma of
+    0 (a point law has no density ratio); a target range that is not inside the flown one (a weight cannot create samples);
+    a key without a primitive - thrust_uncertainty of the table (the reference's dead draw: the motor's own entry is the
+    live one) and atmospheric_density_uncertainty; more than 32 changed rows."""
+    K, liquid = int(K), bool(liquid)
+    base = {k: (list(v) if isinstance(v, (list, tuple)) else v) for k, v in DEFAULT_UNCERTAINTY.items()}
+    for table in (flown, target):
+        for key in (table or {}):
+            if key not in DEFAULT_UNCERTAINTY:
+                raise ValueError(f"{key!r} is no entry of the uncertainty table")
+    base.update(flown or {})
+    new = dict(base)
+    new.update(target or {})
+    first_uniform = 17 + 3 * K
+    sigma_of, normal = {}, {}
+
+    def normal_row(row, s_flown, s_new, what):
+        s_flown, s_new = float(s_flown), float(s_new)
+        sigma_of[row] = s_flown
+        if s_new == s_flown:
+            return
+        if s_flown == 0.0:
+            raise ValueError(f"{what}: the flown sigma is 0 and the target is not - the run did not vary it, there is nothing to reweight")
+        if not s_new > 0.0:
+            raise ValueError(f"{what}: the target sigma is 0 - a point law has no density ratio to the flown one")
+        normal[row] = [0.0, s_new / s_flown]
+
+    for key, rows in _SIGMA_ROWS.items():
+        for i, r in enumerate(rows):
+            normal_row(r, base[key][i], new[key][i], f"{key}[{i}]")
+    normal_row(12, base["mass_uncertainty"], new["mass_uncertainty"], "mass_uncertainty")
+    for key in ("thrust_uncertainty", "atmospheric_density_uncertainty"):
+        if new[key] != base[key]:
+            raise ValueError(f"{key} of the uncertainty table has no primitive: its draw is dead (the motor's own thrust_uncertainty "
+                             f"is the live one)")
+    if motor is not None:
+        tm = motor if target_motor is None else target_motor
+        normal_row(14, motor.thrust_uncertainty, tm.thrust_uncertainty, "motor.thrust_uncertainty")
+        if liquid:
+            normal_row(15, motor.mass_flow_uncertainty, tm.mass_flow_uncertainty, "motor.mass_flow_uncertainty")
+    elif target_motor is not None:
+        raise ValueError("target_motor needs the flown `motor`")
+    uniform = {}
+    for key, row in (("wind_speed_range", first_uniform), ("wind_direction_range", first_uniform + 1)):
+        lo, hi = (float(v) for v in base[key])
+        lo2, hi2 = (float(v) for v in new[key])
+        if (lo2, hi2) == (lo, hi):
+            continue
+        if not (lo <= lo2 < hi2 <= hi):
+            raise ValueError(f"{key}: the target range [{lo2}, {hi2}] is not a range inside the flown [{lo}, {hi}] - weights cannot "
+                             f"create samples where none were flown")
+        uniform[row] = ((lo2 - lo) / (hi - lo), (hi2 - lo) / (hi - lo))
+    names = scalar_primitives(K, liquid)
+    dead = {13, 16} | (set() if liquid else {15})
+    for name, mu in (shift or {}).items():
+        row = names[name] if name in names else name
+        if isinstance(row, str) or not 0 <= int(row) < first_uniform or int(row) in dead:
+            raise ValueError(f"shift: {name!r} is neither a normal primitive of scalar_primitives nor the row of one")
+        row = int(row)
+        if sigma_of.get(row, 1.0) == 0.0:
+            raise ValueError(f"shift: the flown sigma of {name!r} is 0 - the run did not vary it")
+        normal.setdefault(row, [0.0, 1.0])[0] = float(mu)
+    out = {}
+    for row in sorted(set(normal) | set(uniform)):
+        if planar and row in _PLANAR_ZEROED:
+            continue
+        if row in normal:
+            if normal[row] != [0.0, 1.0]:
+                out[row] = (_abi.DESIGN_NORMAL, normal[row][0], normal[row][1], 0.0, 1.0)
+        else:
+            out[row] = (_abi.DESIGN_UNIFORM, 0.0, 1.0) + uniform[row]
+    if len(out) > _abi.RW_MAX_LAW:
+        raise ValueError(f"{len(out)} primitive rows change, more than the {_abi.RW_MAX_LAW} erpl_mc_reweight takes: the effective sample "
+                         f"size is a product over the rows and would be gone long before")
+    return out
+
+
 def check_groups(groups, n_rows):
     """`groups` as a list of (name, rows): at most 32, each non-empty, rows inside the primitive tensor, none shared."""
     items = [(str(name), [int(r) for r in rows]) for name, rows in dict(groups).items()]

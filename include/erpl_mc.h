@@ -1765,6 +1765,101 @@ int erpl_mc_subset_chain_stats(erpl_ctx* ctx, const uint8_t* selected, int64_t c
                                void* hip_stream);
 int erpl_mc_subset_chain_stats_host(const uint8_t* selected, int64_t chains, int64_t steps, int64_t* n1, int64_t* pair);
 
+/* Reweighting (erpl_mc_reweight): the statistics of a FLOWN run under ANOTHER input law, without a new run.  The primitives
+ * of a design run are independent with known laws (rows of N(0, 1) and U(0, 1), erpl_mc_design / erpl_mc_qmc), so the
+ * density ratio of a new law to the flown one is a product of closed-form row factors; importance weights then turn the
+ * flown run into a run under the new law, with an error bar and an effective sample size that says when not to believe it.
+ *
+ * Law: `factors` [n_law][ld] holds the n_law (1 .. ERPL_RW_MAX_LAW) primitive rows whose law changes; kind[r] is
+ * ERPL_DESIGN_NORMAL (flown z ~ N(0, 1), target N(mu[r], s[r]^2): t = (z - mu) / s, l_r = c_r + 0.5 * (z * z - t * t),
+ * c_r = -log(s)) or ERPL_DESIGN_UNIFORM (flown u ~ U(0, 1), target U(a[r], b[r]), 0 <= a < b <= 1: l_r = c_r = -log(b - a)
+ * where a <= u <= b, -inf elsewhere).  c_r is computed once on the host with libm's log, on both paths; the log-weight of
+ * column i is l_i = (((0.0 + l_0) + l_1) + ..) in row order, every operation rounded once: the same bits on the device and
+ * on the host.
+ * Weights are INTEGERS, so that every sum of them is exact and commutes: Q = min(52, 62 - ceil(log2 n)) and
+ * W_i = (int64) floor(2^Q * e(l_i - l_max)), l_max the maximum over the population and e a portable exp (range reduction by
+ * fdlibm's split of ln 2, a degree-13 Taylor polynomial in Horner form, ldexp; within 1 ulp of libm on [-64, 0], 0 below
+ * -64, e(0) = 1, never above 1) that is the same bits on both sides.  The heaviest column has W = 2^Q exactly, every W is
+ * exact in a double and sum_w <= 2^62.
+ * Population (one): mask byte 0 (NULL mask: all), every law row and every requested outcome row finite in the column,
+ * l_i > -inf.  The columns are counted in this order: n_masked, n_non_finite, n_outside (l_i = -inf), count; n_zero of the
+ * population have W = 0 (more than 64 below the heaviest in log-weight).
+ * Outcome rows: up to ERPL_RW_MAX_ROWS summary rows (0..15) or ERPL_RW_ROW_EXTRA for the caller's device row `extra` [n]
+ * (a miss distance, a 0 / 1 zone indicator), each with up to ERPL_RW_MAX_THRESHOLDS thresholds; up to ERPL_RW_MAX_Q quantiles.
+ * Exact: sum_w, max_w, exceed_w = sum W [x > thr], and quantile q = the value at 0-based rank T - 1 of the multiset in which
+ * column i occurs W_i times, T = clamp((uint64) ceil(q * (double) sum_w), 1, sum_w) - NumPy's np.quantile(x, q, weights = W,
+ * method = "inverted_cdf"); a value of the row, sign of a zero included (-0.0 sorts just below +0.0).
+ * Doubles, with S = sum_w: sum_w2 = sum W^2, ess = S^2 / sum_w2; per row mean = sum W x / S, var = sum W (x - mean)^2 / S,
+ * std = sqrt(var), mean_se = sqrt(sum W^2 (x - mean)^2) / S, min / max over W > 0; per threshold p = exceed_w / S and
+ * p_se = sqrt((1 - 2 p) A2 + p^2 sum_w2) / S, A2 = sum W^2 [x > thr] (the radicand taken as 0 where rounding leaves it
+ * below).  The error bars are the delta method for a ratio of sums over independent, identically distributed columns.  They
+ * are accumulated per thread in index order and folded in a fixed order: no floating-point atomics, the same bits in
+ * every call; erpl_mc_reweight_host adds the same terms in index order with a compensated sum, so the two agree to rounding
+ * (1e-12 relative; the mean to 1e-12 * sum W |x| / S).
+ * ess_expected_share = 1 / prod_r E[w_r^2] in closed form: E[w_r^2] = exp(mu^2 / (2 - s^2)) / (s sqrt(2 - s^2)) for a normal row
+ * with s^2 < 2 and 1 / (b - a) for a uniform row; 0 when a normal row has s^2 >= 2, where the variance of the weights is
+ * infinite.  It is a property of the law alone and is reported for every call.
+ * Optional outputs, either may be NULL: `logw` double [n] (NaN for a masked or non-finite column, -inf outside the
+ * support) and `weights` int64 [n], both bit-equal between the device and the host.
+ * An empty population (count == 0, or sum_w == 0) is not an error: sum_w, max_w and every exceed_w are 0 and every double
+ * that depends on the data is NaN.
+ *
+ * erpl_mc_reweight reads DEVICE memory (factors, summary [ERPL_SUMMARY_DIM][ld_s], extra, mask, logw, weights; the spec and
+ * the result are host memory), runs on `hip_stream` and is asynchronous up to the copy of the result, for which it waits;
+ * its workspace belongs to the context.  Integer atomics only.  erpl_mc_reweight_host is the same rule on host memory: no
+ * context, no device.
+ * Errors: ERPL_ERR_INVALID, before any device work and with a message that names the argument, in this order: NULL spec;
+ * n_law outside 1..32; per law row a kind that is neither ERPL_DESIGN_NORMAL nor ERPL_DESIGN_UNIFORM, then for a normal row
+ * a non-finite mu, an s that is not finite or <= 0, for a uniform row a / b outside 0 <= a < b <= 1; n_rows outside 1..4; a
+ * row id outside 0..16; a row listed twice; row 16 without `extra`; an n_thresholds outside 0..8; a NaN threshold; n_q
+ * outside 0..8; a q outside [0, 1]; NULL factors / summary / result; n <= 0 or n > 2^31 - 1; ld < n or ld_s < n; the
+ * context last. */
+#define ERPL_RW_MAX_LAW 32
+#define ERPL_RW_MAX_ROWS 4
+#define ERPL_RW_ROW_EXTRA 16              /* row id of the optional caller-supplied device row `extra` */
+#define ERPL_RW_MAX_THRESHOLDS 8
+#define ERPL_RW_MAX_Q 8
+
+typedef struct erpl_rw_spec {
+  int32_t n_law;                         /* 1..ERPL_RW_MAX_LAW */
+  uint8_t kind[ERPL_RW_MAX_LAW];         /* ERPL_DESIGN_NORMAL / ERPL_DESIGN_UNIFORM */
+  int32_t reserved;
+  double mu[ERPL_RW_MAX_LAW], s[ERPL_RW_MAX_LAW];   /* normal rows: the target N(mu, s^2), in flown sigmas */
+  double a[ERPL_RW_MAX_LAW], b[ERPL_RW_MAX_LAW];    /* uniform rows: the target U(a, b) within the flown (0, 1) */
+  int32_t n_rows, rows[ERPL_RW_MAX_ROWS];
+  int32_t n_thresholds[ERPL_RW_MAX_ROWS];
+  int32_t n_q;
+  double threshold[ERPL_RW_MAX_ROWS][ERPL_RW_MAX_THRESHOLDS];
+  double q[ERPL_RW_MAX_Q];
+} erpl_rw_spec;
+
+typedef struct erpl_rw_row_stats {       /* entry j describes spec->rows[j] */
+  double mean, mean_se, var, std, min, max;
+  double quantile[ERPL_RW_MAX_Q];
+  int64_t exceed_w[ERPL_RW_MAX_THRESHOLDS];
+  double p[ERPL_RW_MAX_THRESHOLDS], p_se[ERPL_RW_MAX_THRESHOLDS];
+} erpl_rw_row_stats;
+
+typedef struct erpl_reweight {
+  int64_t n, count, n_masked, n_non_finite, n_outside, n_zero;
+  int64_t sum_w, max_w;
+  int32_t Q, reserved;
+  double sum_w2, ess, ess_expected_share;
+  erpl_rw_row_stats row[ERPL_RW_MAX_ROWS];
+} erpl_reweight;
+
+/* Host only: one normal identity row (every row mu 0, s 1, a 0, b 1), rows {APOGEE_ALT, RANGE, FLIGHT_TIME}, no thresholds,
+ * q {0.05, 0.25, 0.5, 0.75, 0.95}. */
+int erpl_mc_reweight_defaults(erpl_rw_spec* spec);
+/* factors [n_law][ld], summary [ERPL_SUMMARY_DIM][ld_s], extra [n] or NULL, mask uint8 [n] or NULL, logw double [n] or NULL,
+ * weights int64 [n] or NULL */
+int erpl_mc_reweight(erpl_ctx* ctx, const erpl_rw_spec* spec, const double* factors, int64_t ld, const double* summary,
+                     int64_t ld_s, const double* extra, const uint8_t* mask, int64_t n, erpl_reweight* result, double* logw,
+                     int64_t* weights, void* hip_stream);
+int erpl_mc_reweight_host(const erpl_rw_spec* spec, const double* factors, int64_t ld, const double* summary, int64_t ld_s,
+                          const double* extra, const uint8_t* mask, int64_t n, erpl_reweight* result, double* logw,
+                          int64_t* weights);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
