@@ -286,6 +286,24 @@ class ErplIipSpec(C.Structure):
                 ("keep_x", C.c_double * IIP_MAX_VERTICES), ("keep_y", C.c_double * IIP_MAX_VERTICES)]
 
 
+# erpl_mc_debris: values [IIP_CH_COUNT][n_nodes * n_fragments][ld] (row k * n_fragments + f), summary [DEBRIS_DIM][n_traj]
+DEBRIS_DIM = 16
+DEBRIS_MAX_FRAGMENTS = 64
+DEBRIS_MAX_HALVINGS = 16
+(DEBRIS_MAX_RANGE, DEBRIS_MAX_RANGE_TIME, DEBRIS_MAX_RANGE_X, DEBRIS_MAX_RANGE_Y, DEBRIS_MAX_RANGE_FRAGMENT, DEBRIS_EXIT_TIME,
+ DEBRIS_EXIT_FRAGMENT, DEBRIS_EXIT_X, DEBRIS_EXIT_Y, DEBRIS_MAX_TFALL, DEBRIS_MAX_TFALL_TIME, DEBRIS_MAX_SPREAD,
+ DEBRIS_MAX_SPREAD_TIME, DEBRIS_OUTSIDE, DEBRIS_LANDED, DEBRIS_NODES) = range(16)
+
+
+class ErplDebrisSpec(C.Structure):
+    _fields_ = [("n_nodes", C.c_int32), ("record_stride", C.c_int32), ("max_steps", C.c_int32), ("n_vertices", C.c_int32),
+                ("n_fragments", C.c_int32), ("seed", C.c_uint64),
+                ("dt", C.c_double), ("ground", C.c_double), ("origin_x", C.c_double), ("origin_y", C.c_double),
+                ("stiff_limit", C.c_double),
+                ("beta", C.c_double * DEBRIS_MAX_FRAGMENTS), ("dv", C.c_double * DEBRIS_MAX_FRAGMENTS),
+                ("keep_x", C.c_double * IIP_MAX_VERTICES), ("keep_y", C.c_double * IIP_MAX_VERTICES)]
+
+
 # erpl_mc_sobol
 SOBOL_MAX_FACTORS = 32
 SOBOL_MAX_ROWS = 4
@@ -541,6 +559,7 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_last_stats", "erpl_mc_ticket_stats", "erpl_mc_set_profiling", "erpl_mc_last_kernel_ms",
            "erpl_mc_kernel_ms_history", "erpl_mc_debug_counters", "erpl_mc_extract_histories", "erpl_mc_flight_envelope", "erpl_mc_set_chunk",
            "erpl_mc_impact_points_defaults", "erpl_mc_impact_points",
+           "erpl_mc_debris_defaults", "erpl_mc_debris", "erpl_mc_debris_directions_host",
            "erpl_mc_legacy_random_streams", "erpl_mc_legacy_wind_profiles", "erpl_mc_set_waves_per_simd",
            "erpl_mc_set_overlap", "erpl_mc_submit_batch", "erpl_mc_wait_batch", "erpl_mc_synchronize",
            "erpl_mc_debug_eval", "erpl_mc_synth_wind", "erpl_mc_set_adopt", "erpl_mc_get_overlap",
@@ -634,6 +653,10 @@ def load_library(path=None):
     lib.erpl_mc_impact_points_defaults.argtypes = [C.POINTER(ErplIipSpec)]
     lib.erpl_mc_impact_points.argtypes = [C.c_void_p, C.POINTER(ErplBatch), C.POINTER(ErplOut), C.POINTER(ErplIipSpec), C.c_void_p,
                                           C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.erpl_mc_debris_defaults.argtypes = [C.POINTER(ErplDebrisSpec)]
+    lib.erpl_mc_debris.argtypes = [C.c_void_p, C.POINTER(ErplBatch), C.POINTER(ErplOut), C.POINTER(ErplDebrisSpec), C.c_void_p,
+                                   C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.erpl_mc_debris_directions_host.argtypes = [C.c_uint64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
     lib.erpl_mc_analysis_defaults.argtypes = [C.POINTER(ErplAnalysisSpec)]
     lib.erpl_mc_analyze.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplAnalysisSpec),
                                     C.POINTER(ErplAnalysis), C.c_void_p, C.c_void_p]

@@ -333,6 +333,43 @@ def impact_point_statistics(summary, mask=None, engine=None, rows=None, quantile
     return _summary_like_statistics(summary, IIP_NAMES, mask, engine, rows, quantiles)
 
 
+# ---------------------------------------------------------------------------------- the debris footprint
+DEBRIS_NAMES = ("max_range", "max_range_time", "max_range_x", "max_range_y", "max_range_fragment", "exit_time", "exit_fragment",
+                "exit_x", "exit_y", "max_fall_time", "max_fall_time_time", "max_spread", "max_spread_time", "outside_jobs",
+                "landed_jobs", "nodes")   # _abi.DEBRIS_* order
+DEBRIS_CHANNELS = IIP_CHANNELS   # the channels of erpl_mc_debris are those of erpl_mc_impact_points
+
+
+def debris_directions(seed, sample_ids, node, fragment):
+    """The break-up directions erpl_mc_debris draws for fragment `fragment` at node `node` of the samples with the global ids
+    `sample_ids`: float64 [3, n] (NumPy), unit vectors, the device's bits (erpl_mc_debris_directions_host).  They depend on
+    (seed, id, node, fragment) alone.  Needs the library, no GPU."""
+    from . import _abi
+    lib = _abi.load_library()
+    ids = np.ascontiguousarray(sample_ids, dtype=np.int64).reshape(-1)
+    out = np.empty((3, len(ids)), dtype=np.float64)
+    _abi.check(lib, lib.erpl_mc_debris_directions_host(int(seed) & 0xFFFFFFFFFFFFFFFF, ids.ctypes.data, len(ids), int(node),
+                                                       int(fragment), out.ctypes.data), "erpl_mc_debris_directions_host")
+    return out
+
+
+def debris_statistics(summary, mask=None, engine=None, rows=None, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95)):
+    """Statistics of a debris summary (float64 [16, m] on the device, TrajectoryEngine.debris) over the columns whose `mask`
+    byte is 0, built the way impact_point_statistics is.  erpl_mc_analyze counts a column only if its rows 0, 4 and 5 are
+    finite; row 5 of this summary is exit_time, NaN for every trajectory whose fragments stay inside, so the matrix is handed
+    over with rows 5 (exit_time) and 9 (max_fall_time) exchanged: a column counts iff a job of it landed (max_range,
+    max_range_fragment and max_fall_time are finite together), and beyond that a row counts its finite values.  rows:
+    _abi.DEBRIS_* indices (default all 16).  Returns {name: {'count', 'mean', 'std', 'min', 'max', 'quantiles'}}, names from
+    DEBRIS_NAMES."""
+    from . import _abi
+    swap = list(range(_abi.DEBRIS_DIM))
+    swap[_abi.DEBRIS_EXIT_TIME], swap[_abi.DEBRIS_MAX_TFALL] = _abi.DEBRIS_MAX_TFALL, _abi.DEBRIS_EXIT_TIME
+    rows = list(range(_abi.DEBRIS_DIM)) if rows is None else [int(r) for r in rows]
+    res = _summary_like_statistics(summary[swap].contiguous(), tuple(DEBRIS_NAMES[r] for r in swap), mask, engine,
+                                   [swap[r] for r in rows], quantiles)
+    return {DEBRIS_NAMES[r]: res[DEBRIS_NAMES[r]] for r in rows}
+
+
 # ---------------------------------------------------------------------------------- the trajectory corridor
 CORRIDOR_CHANNEL_NAMES = ("x", "y", "z", "downrange", "vx", "vy", "vz", "speed")   # _abi.CH_* order
 

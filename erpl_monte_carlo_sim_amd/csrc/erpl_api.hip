@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "erpl_host.h"
+#include "erpl_debris.h"
 
 // The one error buffer of the library (erpl_host.h): every unit writes it through erpl_fail.
 static thread_local char g_err[512] = "";
@@ -855,6 +856,108 @@ int erpl_mc_impact_points(erpl_ctx* c, const erpl_batch* b, const erpl_out* o, c
   keep.n = s->n_vertices;
   for (int i = 0; i < s->n_vertices; ++i) { keep.x[i] = s->keep_x[i]; keep.y[i] = s->keep_y[i]; }
   KERNEL_TRY(erpl_launch_iip_f64(a, &c->h_tables.s64, q, keep, stream));
+  return ERPL_OK;
+}
+
+int erpl_mc_debris_defaults(erpl_debris_spec* spec) {
+  if (!spec) return erpl_fail(ERPL_ERR_INVALID, "NULL spec");
+  memset(spec, 0, sizeof(*spec));
+  spec->n_nodes = 16; spec->record_stride = 1; spec->max_steps = 20000; spec->n_fragments = 1;
+  spec->dt = 0.05; spec->stiff_limit = 0.25;
+  spec->beta[0] = (double)INFINITY;
+  return ERPL_OK;
+}
+
+int erpl_mc_debris(erpl_ctx* c, const erpl_batch* b, const erpl_out* o, const erpl_debris_spec* s, double* values, int64_t ld,
+                   int64_t col0, double* summary, void* stream) {
+  if (!b) return erpl_fail(ERPL_ERR_INVALID, "NULL batch");
+  if (!o) return erpl_fail(ERPL_ERR_INVALID, "NULL out");
+  if (!s) return erpl_fail(ERPL_ERR_INVALID, "NULL spec");
+  if (!values) return erpl_fail(ERPL_ERR_INVALID, "NULL values");
+  if (s->n_nodes < 1 || s->n_nodes > ERPL_IIP_MAX_NODES)
+    return erpl_fail(ERPL_ERR_INVALID, "n_nodes = %d out of range 1..%d", s->n_nodes, ERPL_IIP_MAX_NODES);
+  if (s->record_stride < 1) return erpl_fail(ERPL_ERR_INVALID, "record_stride = %d: at least 1", s->record_stride);
+  if (s->max_steps < 1 || s->max_steps > ERPL_IIP_MAX_STEPS)
+    return erpl_fail(ERPL_ERR_INVALID, "max_steps = %d out of range 1..%d", s->max_steps, ERPL_IIP_MAX_STEPS);
+  if (s->n_vertices != 0 && (s->n_vertices < 3 || s->n_vertices > ERPL_IIP_MAX_VERTICES))
+    return erpl_fail(ERPL_ERR_INVALID, "n_vertices = %d: 0 or 3..%d", s->n_vertices, ERPL_IIP_MAX_VERTICES);
+  if (s->n_fragments < 1 || s->n_fragments > ERPL_DEBRIS_MAX_FRAGMENTS)
+    return erpl_fail(ERPL_ERR_INVALID, "n_fragments = %d out of range 1..%d", s->n_fragments, ERPL_DEBRIS_MAX_FRAGMENTS);
+  if ((int64_t)s->n_nodes * s->n_fragments > ERPL_CORRIDOR_MAX_NODES)
+    return erpl_fail(ERPL_ERR_INVALID, "n_nodes * n_fragments = %lld: the product is at most %d rows per channel",
+                     (long long)s->n_nodes * s->n_fragments, ERPL_CORRIDOR_MAX_NODES);
+  if (!std::isfinite(s->dt) || !(s->dt > 0.0)) return erpl_fail(ERPL_ERR_INVALID, "dt = %g: finite and > 0", s->dt);
+  if (!std::isfinite(s->ground)) return erpl_fail(ERPL_ERR_INVALID, "ground = %g: finite", s->ground);
+  if (!std::isfinite(s->origin_x)) return erpl_fail(ERPL_ERR_INVALID, "origin_x = %g: finite", s->origin_x);
+  if (!std::isfinite(s->origin_y)) return erpl_fail(ERPL_ERR_INVALID, "origin_y = %g: finite", s->origin_y);
+  if (!(s->stiff_limit > 0.0 && s->stiff_limit <= 1.0))
+    return erpl_fail(ERPL_ERR_INVALID, "stiff_limit = %g: in (0, 1]", s->stiff_limit);
+  for (int f = 0; f < s->n_fragments; ++f) {
+    if (!(s->beta[f] > 0.0)) return erpl_fail(ERPL_ERR_INVALID, "beta of fragment %d = %g: > 0 (+inf: no drag)", f, s->beta[f]);
+    if (!std::isfinite(s->dv[f]) || !(s->dv[f] >= 0.0))
+      return erpl_fail(ERPL_ERR_INVALID, "dv of fragment %d = %g: finite and >= 0", f, s->dv[f]);
+  }
+  for (int i = 0; i < s->n_vertices; ++i)
+    if (!std::isfinite(s->keep_x[i]) || !std::isfinite(s->keep_y[i]))
+      return erpl_fail(ERPL_ERR_INVALID, "keep-in vertex %d = (%g, %g): finite", i, s->keep_x[i], s->keep_y[i]);
+  if (b->precision != ERPL_PREC_F64 && b->precision != ERPL_PREC_F64_FAST)
+    return erpl_fail(ERPL_ERR_INVALID, "precision = %d: the debris footprint needs a batch with fp64 wind tables", b->precision);
+  if (b->n <= 0) return erpl_fail(ERPL_ERR_INVALID, "batch n = %lld: at least one sample", (long long)b->n);
+  if (o->n_traj < 0 || o->n_traj > 2147483647LL)
+    return erpl_fail(ERPL_ERR_INVALID, "n_traj = %lld out of range 0..2^31 - 1", (long long)o->n_traj);
+  if (col0 < 0) return erpl_fail(ERPL_ERR_INVALID, "col0 = %lld: not negative", (long long)col0);
+  if (ld - col0 < o->n_traj)   // (col0 >= 0: no overflow, and a negative ld is refused here too)
+    return erpl_fail(ERPL_ERR_INVALID, "ld = %lld: the %lld columns from col0 = %lld on do not fit", (long long)ld,
+                     (long long)o->n_traj, (long long)col0);
+  if (o->n_traj > 0) {
+    if (o->traj_cap < 1) return erpl_fail(ERPL_ERR_INVALID, "traj_cap = %lld: at least one record per trajectory", (long long)o->traj_cap);
+    if (!o->traj_ids) return erpl_fail(ERPL_ERR_INVALID, "NULL traj_ids");
+    if (!o->traj) return erpl_fail(ERPL_ERR_INVALID, "NULL traj");
+    if (!o->traj_len) return erpl_fail(ERPL_ERR_INVALID, "NULL traj_len");
+    if (!b->rocket) return erpl_fail(ERPL_ERR_INVALID, "NULL rocket");
+    if (!b->motor) return erpl_fail(ERPL_ERR_INVALID, "NULL motor");
+    if (!check_wind_args(b)) return erpl_fail(ERPL_ERR_INVALID, "bad wind arguments (k_wind, alt_grid, wind)");
+  }
+  if (!c) return erpl_fail(ERPL_ERR_INVALID, "NULL ctx");
+  if (!c->has_cfg) return erpl_fail(ERPL_ERR_CONFIG, "erpl_mc_set_config has not been called");
+  if (o->n_traj == 0) return ERPL_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  ErplKArgs a;
+  fill_common_args(c, b, a);
+  a.n_traj = o->n_traj; a.traj_ids = o->traj_ids; a.traj_cap = o->traj_cap; a.traj = o->traj; a.traj_len = o->traj_len;
+  ErplDebrisArgs q;
+  q.n_nodes = s->n_nodes; q.record_stride = s->record_stride; q.max_steps = s->max_steps; q.n_fragments = s->n_fragments;
+  q.seed = s->seed;
+  q.dt = s->dt; q.ground = s->ground; q.origin_x = s->origin_x; q.origin_y = s->origin_y; q.stiff_limit = s->stiff_limit;
+  q.values = values; q.ld = ld; q.col0 = col0; q.summary = summary;
+  ErplDebrisFragments fr;
+  memset(&fr, 0, sizeof(fr));
+  for (int f = 0; f < s->n_fragments; ++f) { fr.beta[f] = s->beta[f]; fr.dv[f] = s->dv[f]; fr.order[f] = (uint8_t)f; }
+  // the dispatch order: the lightest fragments (the longest falls) first
+  std::stable_sort(fr.order, fr.order + s->n_fragments, [&](uint8_t x, uint8_t y) { return s->beta[x] < s->beta[y]; });
+  ErplIipKeepIn keep;
+  memset(&keep, 0, sizeof(keep));
+  keep.n = s->n_vertices;
+  for (int i = 0; i < s->n_vertices; ++i) { keep.x[i] = s->keep_x[i]; keep.y[i] = s->keep_y[i]; }
+  KERNEL_TRY(erpl_launch_debris_f64(a, &c->h_tables.s64, q, fr, keep, stream));
+  return ERPL_OK;
+}
+
+int erpl_mc_debris_directions_host(uint64_t seed, const int64_t* sample_ids, int64_t n, int32_t node, int32_t fragment,
+                                   double* dir) {
+  if (n < 0) return erpl_fail(ERPL_ERR_INVALID, "n = %lld: not negative", (long long)n);
+  if (node < 0 || node >= ERPL_IIP_MAX_NODES) return erpl_fail(ERPL_ERR_INVALID, "node = %d out of range 0..%d", node, ERPL_IIP_MAX_NODES - 1);
+  if (fragment < 0 || fragment >= ERPL_DEBRIS_MAX_FRAGMENTS)
+    return erpl_fail(ERPL_ERR_INVALID, "fragment = %d out of range 0..%d", fragment, ERPL_DEBRIS_MAX_FRAGMENTS - 1);
+  if (n > 0 && !sample_ids) return erpl_fail(ERPL_ERR_INVALID, "NULL sample_ids");
+  if (n > 0 && !dir) return erpl_fail(ERPL_ERR_INVALID, "NULL dir");
+  for (int64_t i = 0; i < n; ++i)
+    if (sample_ids[i] < 0) return erpl_fail(ERPL_ERR_INVALID, "sample_ids[%lld] = %lld: not negative", (long long)i, (long long)sample_ids[i]);
+  for (int64_t i = 0; i < n; ++i) {
+    double d[3];
+    erpl_debris_direction(seed, (uint64_t)sample_ids[i], (uint32_t)node, (uint32_t)fragment, d);
+    for (int cc = 0; cc < 3; ++cc) dir[(int64_t)cc * n + i] = d[cc];
+  }
   return ERPL_OK;
 }
 

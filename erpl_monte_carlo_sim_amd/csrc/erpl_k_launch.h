@@ -1,5 +1,5 @@
 // erpl_k_launch.h — the host side of a kernel unit: erpl_launch_<suffix> (rail + flight launches of one batch), the
-// gate unit's sweep, extract, envelope and impact-point launchers, the debug launcher.
+// gate unit's sweep, extract, envelope, impact-point and debris launchers, the debug launcher.
 
 // One flight launch, from g, b, dyn_lds, st, a, S of the launcher that uses it.  SPEC >= 0 compiles the two launch
 // constants of the RHS in (bit 0 = a wind table is present, bit 1 = solid motor); trajectory capture reads them at run
@@ -115,6 +115,21 @@ int erpl_launch_iip_f64(const ErplKArgs& a, const void* scalars, const ErplIipAr
                      a, S, q);
   if (q.summary)
     hipLaunchKernelGGL(erpl_iip_summary_f64, dim3((unsigned)a.n_traj), dim3(kIipBlock), 0, (hipStream_t)stream, a, q, keep);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+int erpl_launch_debris_f64(const ErplKArgs& a, const void* scalars, const ErplDebrisArgs& q, const ErplDebrisFragments& fr,
+                           const ErplIipKeepIn& keep, void* stream) {
+  if (a.n_traj <= 0 || q.n_nodes <= 0 || q.n_fragments <= 0) return 0;
+  const ErplScalars<real> S = *(const ErplScalars<real>*)scalars;
+  const size_t dyn_lds = (size_t)(a.k_wind > 0 ? a.k_wind : 1) * sizeof(real);   // the wind altitude grid
+  const unsigned per_traj = (unsigned)((a.n_traj + kDebrisBlock - 1) / kDebrisBlock);
+  hipLaunchKernelGGL(erpl_debris_prefix_f64, dim3((unsigned)a.n_traj), dim3(kDebrisBlock), 0, (hipStream_t)stream, a, q);
+  hipLaunchKernelGGL(erpl_debris_fall_f64, dim3(per_traj, (unsigned)(q.n_nodes * q.n_fragments)), dim3(kDebrisBlock), dyn_lds,
+                     (hipStream_t)stream, a, S, q, fr);
+  if (q.summary)
+    hipLaunchKernelGGL(erpl_debris_summary_f64, dim3((unsigned)a.n_traj), dim3(kDebrisBlock), 0, (hipStream_t)stream, a, q, keep);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }

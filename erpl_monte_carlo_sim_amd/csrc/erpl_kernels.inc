@@ -17,7 +17,8 @@
 // launches) to park still-flying lanes densely for the next launch.  Kernel 3 (fp64 only) evaluates the
 // per-step diagnostic histories of _extract_results (:496-552); kernel 4 (fp64 only) reduces every captured trajectory
 // of a batch to its flight envelope through the same per-record evaluation; kernels 5 to 7 (fp64 only) let every chosen
-// record of a captured trajectory fall to the ground without thrust and summarise where it comes down.
+// record of a captured trajectory fall to the ground without thrust and summarise where it comes down; kernels 8 to 10
+// (fp64 only) do the same for the fragments of a vehicle that breaks up there.
 //
 // ERPL_FAITHFUL keeps the reference's operation order (double normalisation, trig of
 // atan2, IEEE divisions); the two throughput builds allow algebraically identical shortcuts (no trig, reciprocal
@@ -41,5 +42,7 @@
 #if ERPL_FAITHFUL
 #include "erpl_k_envelope.h" // kernel 4 (gate only): the flight envelope of every captured trajectory
 #include "erpl_k_iip.h"      // kernels 5 - 7 (gate only): the instantaneous impact points of every captured trajectory
+#include "erpl_debris.h"     // the direction, step and tick rules the host shares with kernels 8 - 10
+#include "erpl_k_debris.h"   // kernels 8 - 10 (gate only): where the fragments fall if the vehicle breaks up at a node
 #endif
-#include "erpl_k_launch.h"   // host: erpl_launch_<suffix>, the sweep, extract, envelope, impact-point and debug launchers
+#include "erpl_k_launch.h"   // host: erpl_launch_<suffix>, the sweep, extract, envelope, impact-point, debris and debug launchers

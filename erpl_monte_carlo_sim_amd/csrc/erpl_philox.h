@@ -13,7 +13,7 @@
 //            with the smallest (key, i) pairs.  With (thr_key, thr_idx) the m_a-th smallest pair, the label is one comparison.
 // Counter word 3 is a TAG that keeps the families apart: 0 the bootstrap family above, 1 the jitter and 2 the round keys of
 // erpl_mc_design (erpl_design.h), 3 the proposals of erpl_mc_subset_propose (erpl_subset.h), 4 the scramble keys
-// of erpl_mc_qmc (erpl_qmc.h).
+// of erpl_mc_qmc (erpl_qmc.h), 5 the break-up directions of erpl_mc_debris (erpl_debris.h).
 #pragma once
 #include <stdint.h>
 

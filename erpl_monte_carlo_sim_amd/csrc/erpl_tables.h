@@ -180,6 +180,27 @@ extern "C++" {
 int erpl_launch_iip_f64(const ErplKArgs& a, const void* scalars, const ErplIipArgs& q, const ErplIipKeepIn& keep, void* stream);
 }
 
+// What the kernels of erpl_mc_debris take besides ErplKArgs (by value): the scalar fields of erpl_debris_spec and the
+// caller's buffers; the fragments go to the fall kernel alone, the keep-in vertices (ErplIipKeepIn) to the summary kernel.
+struct ErplDebrisArgs {
+  int32_t n_nodes, record_stride, max_steps, n_fragments;
+  uint64_t seed;
+  double dt, ground, origin_x, origin_y, stiff_limit;
+  double* values;    // [ERPL_IIP_CH_COUNT][n_nodes * n_fragments][ld]
+  int64_t ld, col0;
+  double* summary;   // [ERPL_DEBRIS_DIM][n_traj] or NULL
+};
+struct ErplDebrisFragments {
+  double beta[ERPL_DEBRIS_MAX_FRAGMENTS], dv[ERPL_DEBRIS_MAX_FRAGMENTS];
+  uint8_t order[ERPL_DEBRIS_MAX_FRAGMENTS];   // the fragment dispatched r-th: ascending beta, ties by index
+};
+extern "C++" {
+// the debris footprint of every captured trajectory (fp64 only): a.* as for erpl_launch_iip_f64; the prefix kernel, the fall
+// kernel, then (q.summary != NULL) the summary kernel, one behind the other on the same stream
+int erpl_launch_debris_f64(const ErplKArgs& a, const void* scalars, const ErplDebrisArgs& q, const ErplDebrisFragments& fr,
+                           const ErplIipKeepIn& keep, void* stream);
+}
+
 // ---- erpl_mc_analyze: outlier filter + exact statistics on the summary (erpl_analysis.hip) ----
 #define ERPL_ANA_BLOCK 256        // threads per workgroup of the streaming passes
 #define ERPL_ANA_MAX_BLOCKS 1024  // their grid: min(this, ceil(n / ERPL_ANA_BLOCK)) - a function of n alone, so the

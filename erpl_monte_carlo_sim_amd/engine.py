@@ -387,6 +387,71 @@ class TrajectoryEngine:
                    C.c_void_p(summ.data_ptr()) if summ is not None else None, C.c_void_p(st.cuda_stream))
         return out, summ
 
+    def debris(self, db, traj_ids, traj, traj_len, fragments, nodes=16, record_stride=1, dt=0.05, max_steps=20000, ground=0.0,
+               stiff_limit=0.25, seed=0, origin=(0.0, 0.0), keep_in=None, out=None, col0=0, summary=True, stream=None):
+        """Where the fragments fall if the vehicle breaks up (erpl_mc_debris; the definitions are in include/erpl_mc.h): at
+        node k = record k * record_stride every fragment (beta, dv) of `fragments` - a sequence of 1 to 64 pairs, beta the
+        ballistic coefficient m / (Cd A) in kg/m^2 (float('inf'): no drag), dv the speed in m/s the break-up adds in an
+        isotropic direction drawn from (seed, sample id, node, fragment) - falls to the plane z = ground under gravity, its
+        drag and the sample's own wind, by RK4 steps of dt that are halved while drag rate * step exceeds stiff_limit, at most
+        max_steps of them.  `db`, traj_ids, traj, traj_len, keep_in, col0 and `stream` as for impact_points.  Trajectory j
+        fills column col0 + j of `out`, a float64 [5, nodes * len(fragments), ld] device tensor (channels _abi.IIP_CH_*, row
+        k * len(fragments) + f; default: a new one with ld = col0 + m, NaN everywhere).  Returns (out, summary): summary
+        float64 [16, m] on the device (rows _abi.DEBRIS_*), or None with summary=False.  Asynchronous."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype == dtype and t.is_contiguous()
+        if not (ok(traj, torch.float64) and traj.dim() == 3 and traj.shape[2] == _abi.TRAJ_DIM):
+            raise ValueError(f"traj must be a contiguous float64 [m, cap, {_abi.TRAJ_DIM}] tensor on {self.device}")
+        m, cap = int(traj.shape[0]), int(traj.shape[1])
+        if not (ok(traj_ids, torch.int64) and tuple(traj_ids.shape) == (m,)):
+            raise ValueError(f"traj_ids must be a contiguous int64 [m] tensor on {self.device}")
+        if not (ok(traj_len, torch.int64) and tuple(traj_len.shape) == (m,)):
+            raise ValueError(f"traj_len must be a contiguous int64 [m] tensor on {self.device}")
+        nodes, record_stride, max_steps = int(nodes), int(record_stride), int(max_steps)
+        fragments = [(float(beta), float(dv)) for beta, dv in fragments]
+        # (the Python ints, before a 32-bit field can truncate them)
+        if not 1 <= len(fragments) <= _abi.DEBRIS_MAX_FRAGMENTS:
+            raise ValueError(f"1 to {_abi.DEBRIS_MAX_FRAGMENTS} fragments")
+        if not 1 <= nodes <= _abi.IIP_MAX_NODES or nodes * len(fragments) > _abi.CORRIDOR_MAX_NODES:
+            raise ValueError(f"1 to {_abi.IIP_MAX_NODES} nodes, at most {_abi.CORRIDOR_MAX_NODES} nodes * fragments")
+        if not 1 <= record_stride < 2 ** 31:
+            raise ValueError("record_stride must be 1 to 2**31 - 1")
+        if not 1 <= max_steps <= _abi.IIP_MAX_STEPS:
+            raise ValueError(f"max_steps must be 1 to {_abi.IIP_MAX_STEPS}")
+        spec = self._defaults(_abi.ErplDebrisSpec, "erpl_mc_debris_defaults")
+        spec.n_nodes, spec.record_stride, spec.max_steps, spec.n_fragments = nodes, record_stride, max_steps, len(fragments)
+        spec.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        spec.dt, spec.ground, spec.stiff_limit = float(dt), float(ground), float(stiff_limit)
+        spec.origin_x, spec.origin_y = float(origin[0]), float(origin[1])
+        for f, (beta, dv) in enumerate(fragments):
+            spec.beta[f], spec.dv[f] = beta, dv
+        if keep_in is not None:
+            keep_in = [(float(x), float(y)) for x, y in keep_in]
+            if not 3 <= len(keep_in) <= _abi.IIP_MAX_VERTICES:
+                raise ValueError(f"3 to {_abi.IIP_MAX_VERTICES} keep-in vertices")
+            spec.n_vertices = len(keep_in)
+            for i, (x, y) in enumerate(keep_in):
+                spec.keep_x[i], spec.keep_y[i] = x, y
+        shape = (_abi.IIP_CH_COUNT, nodes * len(fragments))
+        col0 = int(col0)
+        if out is None:
+            out = torch.full(shape + (col0 + m,), float("nan"), dtype=torch.float64, device=self.device)
+        if not (ok(out, torch.float64) and out.dim() == 3 and tuple(out.shape[:2]) == shape):
+            raise ValueError(f"out must be a contiguous float64 [{shape[0]}, {shape[1]}, ld] tensor on {self.device}")
+        ld = int(out.shape[2])
+        if col0 < 0 or col0 + m > ld:
+            raise ValueError(f"columns {col0}..{col0 + m} do not fit ld = {ld}")
+        summ = torch.empty((_abi.DEBRIS_DIM, m), dtype=torch.float64, device=self.device) if summary else None
+        if m == 0:   # (an empty tensor has no address to hand over)
+            return out, summ
+        b = self._batch_struct(db)
+        o = _abi.ErplOut()
+        o.n_traj, o.traj_ids, o.traj_cap = m, traj_ids.data_ptr(), cap
+        o.traj, o.traj_len = traj.data_ptr(), traj_len.data_ptr()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_debris", C.byref(b), C.byref(o), C.byref(spec), C.c_void_p(out.data_ptr()), ld, col0,
+                   C.c_void_p(summ.data_ptr()) if summ is not None else None, C.c_void_p(st.cuda_stream))
+        return out, summ
+
     def corridor_spec(self, channels=None, nodes=None, t0=None, dt=None, hold=False, quantiles=None):
         """The library's erpl_corridor_spec (erpl_mc_corridor_defaults: altitude, downrange, speed; 256 nodes 1 s apart
         from 0; 5/25/50/75/95 %) with what is given overridden.  channels: _abi.CH_* indices."""

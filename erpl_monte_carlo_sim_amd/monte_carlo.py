@@ -881,6 +881,107 @@ class MonteCarloAnalyzer:
                               "sub_batches": run["sub_batches"], "sub_batch_samples": run["per_batch"]}
         return out
 
+    def debris_footprint(self, initial_conditions, n_samples, fragments, stride=10, nodes=16, record_stride=None, keep_in=None,
+                         maps=(), map_bins=50, seed=1234, debris_seed=None, precision="f64_fast", planar=False,
+                         capture_bytes=4 << 30, dt=0.05, max_steps=20000, ground=0.0, stiff_limit=0.25, origin=(0.0, 0.0),
+                         quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), level=0.95):
+        """If the vehicle breaks up at time t, where do its pieces come down - for a whole dispersion run: the samples of
+        `impact_point_trace` (same draws, same sub-batches, same nodes) and, at every node, the fragments
+        `fragments` = [(beta, dv), ...] - beta the ballistic coefficient m / (Cd A) in kg/m^2 (float('inf'): no drag), dv the
+        speed in m/s the break-up adds in an isotropic direction drawn from (debris_seed + 1000003 * sub-batch, sample of the
+        sub-batch, node, fragment); debris_seed defaults to `seed` - fall to z = `ground` on the device (TrajectoryEngine.debris: gravity, the fragment's
+        drag, the sample's own wind; RK4 steps of dt halved while drag rate * step exceeds stiff_limit), each sub-batch into
+        its window of columns of one [5, nodes * F, n] matrix.  maps: (node, fragment) pairs whose footprint is wanted as a
+        map_bins x map_bins count grid (erpl_mc_histogram_xy on the X and Y rows of that pair).  One rank only.  Because the draw's sample id
+        is the index within the sub-batch and its seed carries the sub-batch number, the directions of a run depend on how it is
+        cut into sub-batches (`capture_bytes`), exactly as its dispersions do: the same arguments give the same bytes, another
+        `capture_bytes` another, equally valid, draw.  TrajectoryEngine.debris itself draws from (seed, id, node, fragment) alone.
+
+        Returns a dict: 'time' [nodes], 'fragments', 'q', 'channels' and per channel 'count' / 'mean' / 'std' / 'min' /
+        'max' [nodes, F] and 'quantiles' [n_q, nodes, F] over the samples that pass the outlier filter
+        (erpl_mc_corridor_bands on the matrix as it is); 'statistics' (analysis.debris_statistics over the same samples);
+        'exit_probability', the share of those samples with a fragment that lands outside the keep-in area, with its
+        Wilson interval 'exit_interval' at `level` (NaN and (0, 1) without a polygon) and 'exit_count'; 'maps', a dict
+        (node, fragment) -> {'counts', 'edges_x', 'edges_y', 'info'}; 'values' and 'debris_summary' (on the device),
+        'debris_names', 'keep_in', 'summary', 'status', 'reasons', 'n_samples' / 'n_outliers' and 'performance'."""
+        nodes, stride = int(nodes), int(stride)
+        frags = [(float(beta), float(dv)) for beta, dv in fragments]
+        F = len(frags)
+        if not 1 <= F <= _abi.DEBRIS_MAX_FRAGMENTS:
+            raise ValueError(f"1 to {_abi.DEBRIS_MAX_FRAGMENTS} fragments")
+        if not 1 <= nodes <= _abi.IIP_MAX_NODES or nodes * F > _abi.CORRIDOR_MAX_NODES:
+            raise ValueError(f"1 to {_abi.IIP_MAX_NODES} nodes, at most {_abi.CORRIDOR_MAX_NODES} nodes * fragments")
+        for beta, dv in frags:
+            if not beta > 0.0 or not (np.isfinite(dv) and dv >= 0.0):
+                raise ValueError("a fragment needs beta > 0 and a finite dv >= 0")
+        if int(n_samples) < 1 or stride < 1:
+            raise ValueError("n_samples and stride must be at least 1")
+        flight_dt = min(self.dt_initial, 0.005)
+        if record_stride is None:
+            record_stride = max(1, int(np.ceil(self.max_time / flight_dt / stride)) // nodes)
+        record_stride = int(record_stride)
+        if record_stride < 1:
+            raise ValueError("record_stride must be at least 1")
+        maps = [(int(k), int(f)) for k, f in maps]
+        for k, f in maps:
+            if not (0 <= k < nodes and 0 <= f < F):
+                raise ValueError(f"map ({k}, {f}): node below {nodes} and fragment below {F}")
+        keep = None if keep_in is None else [(float(x), float(y)) for x, y in keep_in]
+        debris_seed = int(seed if debris_seed is None else debris_seed)
+        box, summaries = {}, []
+
+        def fall(eng, db, a, traj, tlen):
+            if "values" not in box:
+                box["values"] = torch.full((_abi.IIP_CH_COUNT, nodes * F, int(n_samples)), float("nan"), dtype=torch.float64,
+                                           device=eng.device)
+            # (a sub-batch numbers its samples from 0: sub-batch j draws under debris_seed + 1000003 * j, as its dispersions do)
+            _, s = eng.debris(db, eng._keep, traj, tlen, frags, nodes=nodes, record_stride=record_stride, dt=dt,
+                              max_steps=max_steps, ground=ground, stiff_limit=stiff_limit,
+                              seed=debris_seed + 1000003 * len(summaries), origin=origin, keep_in=keep, out=box["values"], col0=a)
+            summaries.append(s)
+
+        eng, summ, status, run = self._captured_run("debris_footprint", "debris footprints", initial_conditions, n_samples,
+                                                    stride, seed, precision, planar, capture_bytes, fall)
+        deb = summaries[0] if len(summaries) == 1 else torch.cat(summaries, dim=1).contiguous()
+        torch.cuda.synchronize(eng.device)
+        t1 = time.time()
+        _, res, why = analysis._filter(summ, status, eng)
+        vals = box["values"]
+        b = eng.corridor_bands(vals, why, quantiles=quantiles)
+        out = {"time": np.arange(nodes, dtype=np.float64) * (record_stride * run["stride"] * flight_dt), "q": b["q"],
+               "fragments": frags, "channels": list(analysis.DEBRIS_CHANNELS), "n_counted": b["n_counted"]}
+        for j, name in enumerate(analysis.DEBRIS_CHANNELS):
+            out[name] = {k: b[k][j].reshape(nodes, F) for k in ("count", "mean", "std", "min", "max")}
+            out[name]["quantiles"] = b["quantiles"][j].reshape(-1, nodes, F)
+        out["statistics"] = analysis.debris_statistics(deb, why, engine=eng, quantiles=quantiles)
+        counted = why == 0
+        n_counted = int(counted.sum())
+        n_exit = int((counted & torch.isfinite(deb[_abi.DEBRIS_EXIT_TIME])).sum())
+        out["exit_count"] = n_exit
+        out["exit_probability"] = n_exit / n_counted if (keep is not None and n_counted) else float("nan")
+        out["exit_interval"] = analysis.wilson_interval(n_exit, n_counted, level) if keep is not None else (0.0, 1.0)
+        out["interval_level"] = float(level)
+        out["maps"] = {}
+        for k, f in maps:
+            pair = torch.zeros((_abi.SUMMARY_DIM, int(n_samples)), dtype=torch.float64, device=eng.device)
+            pair[0], pair[1] = vals[_abi.IIP_CH_X, k * F + f], vals[_abi.IIP_CH_Y, k * F + f]
+            counts, ex, ey, info = eng.histogram2d(pair, why, 0, 1, bins=map_bins)
+            out["maps"][(k, f)] = {"counts": counts, "edges_x": ex, "edges_y": ey, "info": info}
+        t2 = time.time()
+        out.update({"summary": summ, "status": status, "reasons": why, "values": vals, "debris_summary": deb,
+                    "debris_names": list(analysis.DEBRIS_NAMES), "keep_in": keep, "record_stride": record_stride,
+                    "debris_seed": debris_seed, "n_samples": int(res.n_valid), "n_outliers": int(res.n_outliers)})
+        out["performance"] = {"total_time": t2 - run["t0"], "capture_and_fall_s": t1 - run["t0"], "statistics_s": t2 - t1,
+                              "precision": precision, "stride": run["stride"], "records_per_sample": run["cap"],
+                              "sub_batches": run["sub_batches"], "sub_batch_samples": run["per_batch"]}
+        return out
+
+    def plot_debris_footprint(self, footprint, node=None, save_plots=True):
+        """No reference counterpart: the footprint of `debris_footprint` - per fragment the median and the outer band of the
+        impact range over the time of break-up, the footprint at `node` (default: the last one) with the keep-in outline - as
+        monte_carlo_debris.png in the output directory; returns that directory."""
+        return plots.plot_debris_footprint(self, footprint, node, save_plots)
+
     def plot_impact_point_trace(self, trace, save_plots=True):
         """No reference counterpart: the IIP trace of `impact_point_trace` - IIP range over time with its bands, the ground
         track of the median IIP with the keep-in outline, the exit times - as monte_carlo_impact_points.png in the output

@@ -321,6 +321,71 @@ def impact_point_figure(result):
     return fig
 
 
+def debris_footprint_figure(result, node=None):
+    """The debris footprint from the dict of MonteCarloAnalyzer.debris_footprint: per fragment the median impact range (the
+    quantile nearest 0.5) with its outermost quantile band over the time of break-up, and the footprint at `node` (default
+    the last one) - per fragment the box of the outermost X and Y quantiles about the median impact, the count grid of
+    result['maps'] where that (node, fragment) has one - with the keep-in outline."""
+    q = np.asarray(result["q"], dtype=np.float64)
+    t = np.asarray(result["time"], dtype=np.float64)
+    frags = list(result["fragments"])
+    node = len(t) - 1 if node is None else int(node)
+    if not 0 <= node < len(t):
+        raise ValueError(f"node must be 0 to {len(t) - 1}")
+    fig = _figure((13, 5))
+    ax_r, ax_xy = fig.subplots(1, 2)
+    order = np.argsort(q)
+    mid = int(np.argmin(np.abs(q - 0.5))) if len(q) else None
+    lo, hi = (order[0], order[-1]) if len(q) >= 2 else (None, None)
+    centre = (lambda ch: np.asarray(ch["quantiles"], dtype=np.float64)[mid]) if mid is not None else \
+        (lambda ch: np.asarray(ch["mean"], dtype=np.float64))
+    rng_q = np.asarray(result["range"]["quantiles"], dtype=np.float64)      # [n_q, nodes, F]
+    colors = [f"C{f % 10}" for f in range(len(frags))]
+    for f, (beta, dv) in enumerate(frags):
+        label = f"beta {beta:g} kg/m2, dv {dv:g} m/s"
+        if lo is not None:
+            ax_r.fill_between(t, rng_q[lo][:, f], rng_q[hi][:, f], alpha=0.15, color=colors[f], linewidth=0)
+        ax_r.plot(t, centre(result["range"])[:, f], color=colors[f], linewidth=1.4, label=label)
+    p = result.get("exit_probability", float("nan"))
+    title = "Debris Impact Range over Break-up Time"
+    if lo is not None:
+        title += f" (median, {100 * q[lo]:g} - {100 * q[hi]:g} %)"
+    if np.isfinite(p):
+        a, b = result.get("exit_interval", (0.0, 1.0))
+        title += f"\nP(a fragment leaves keep-in) = {100 * p:.2f} % [{100 * a:.2f}, {100 * b:.2f}]"
+    ax_r.set_title(title)
+    ax_r.set_xlabel("Time of Break-up since Rail Exit (s)")
+    ax_r.set_ylabel("Impact Range (m)")
+    ax_r.grid(True, alpha=0.3)
+    ax_r.legend(loc="best", fontsize=7)
+    maps = result.get("maps") or {}
+    for f in range(len(frags)):
+        m = maps.get((node, f))
+        if m is not None and np.asarray(m["counts"]).sum() > 0:
+            counts = np.asarray(m["counts"], dtype=np.float64)
+            ax_xy.pcolormesh(np.asarray(m["edges_x"]), np.asarray(m["edges_y"]), np.where(counts > 0, counts, np.nan).T,
+                             cmap="Greys", alpha=0.6, shading="flat")
+        cx, cy = centre(result["x"])[node, f], centre(result["y"])[node, f]
+        if lo is not None:
+            xq, yq = np.asarray(result["x"]["quantiles"], dtype=np.float64), np.asarray(result["y"]["quantiles"], dtype=np.float64)
+            x0, x1, y0, y1 = xq[lo][node, f], xq[hi][node, f], yq[lo][node, f], yq[hi][node, f]
+            if np.isfinite([x0, x1, y0, y1]).all():
+                ax_xy.plot([x0, x1, x1, x0, x0], [y0, y0, y1, y1, y0], color=colors[f], linewidth=1.0)
+        if np.isfinite(cx) and np.isfinite(cy):
+            ax_xy.plot([cx], [cy], color=colors[f], marker="o", markersize=4, linestyle="none")
+    keep = result.get("keep_in")
+    if keep:
+        kx, ky = [v[0] for v in keep] + [keep[0][0]], [v[1] for v in keep] + [keep[0][1]]
+        ax_xy.plot(kx, ky, color="black", linewidth=1.2, label="keep-in area")
+        ax_xy.legend(loc="best", fontsize=8)
+    ax_xy.set_title(f"Footprint of a Break-up at {t[node]:g} s ({int(result.get('n_counted', 0))} samples)")
+    ax_xy.set_xlabel("X (m)")
+    ax_xy.set_ylabel("Y (m)")
+    ax_xy.grid(True, alpha=0.3)
+    fig.tight_layout()
+    return fig
+
+
 def sobol_figure(result):
     """The dict of analysis.sobol_indices as paired bars: per row one panel, per group the first-order index S1 and the
     total-effect index ST side by side in the order of `group_names`, their bootstrap percentile intervals (lo, hi) as
@@ -786,6 +851,17 @@ def plot_impact_point_trace(analyzer, trace, save_plots=True):
     if save_plots:
         output_dir = analyzer._create_output_directory()
         print(f"Impact point trace plot saved to: {save_figure(fig, output_dir, 'monte_carlo_impact_points.png')}")
+    return output_dir
+
+
+def plot_debris_footprint(analyzer, footprint, node=None, save_plots=True):
+    """The footprint of MonteCarloAnalyzer.debris_footprint (no reference counterpart) as monte_carlo_debris.png; returns the
+    output directory (None without save_plots)."""
+    fig = debris_footprint_figure(footprint, node)
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Debris footprint plot saved to: {save_figure(fig, output_dir, 'monte_carlo_debris.png')}")
     return output_dir
 
 

@@ -442,6 +442,93 @@ int erpl_mc_impact_points_defaults(erpl_iip_spec* spec);
 int erpl_mc_impact_points(erpl_ctx* ctx, const erpl_batch* batch, const erpl_out* out, const erpl_iip_spec* spec,
                           double* values, int64_t ld, int64_t col0, double* summary, void* hip_stream);
 
+/* The debris footprint of every captured trajectory of a run ON THE DEVICE (no reference counterpart): if the vehicle BREAKS
+ * UP at the time of a stored record, where do its pieces come down?  erpl_mc_impact_points lets the intact vehicle fall; here
+ * every node of every trajectory sheds n_fragments fragments, each with its own ballistic coefficient beta = m / (Cd A) and
+ * its own break-up speed dv, and every fragment falls to the ground plane under gravity, its drag and the sample's own wind.
+ * `batch`, `out`, `values`, `summary` and the stream as for erpl_mc_impact_points.  A JOB is (trajectory j, node k, fragment
+ * f).  `values` is CALLER-OWNED device memory, double [ERPL_IIP_CH_COUNT][n_nodes * n_fragments][ld], channels ERPL_IIP_CH_*;
+ * the row of a channel is k * n_fragments + f; trajectory j writes column col0 + j of all its rows and nothing else - so
+ * erpl_mc_corridor_bands bands the matrix as it is, and the X and Y rows of one (k, f) are a pair of rows for
+ * erpl_mc_histogram_xy: the footprint map of that fragment at that time.  `summary` is CALLER-OWNED device memory, double
+ * [ERPL_DEBRIS_DIM][n_traj], or NULL.
+ *
+ * Nodes: evaluated as for erpl_mc_impact_points (k * record_stride below the usable prefix).
+ * The break-up.  dv[f] == 0: the record's velocity, bit for bit.  Otherwise v_c = v_c + dv[f] * d_c, d a unit vector that
+ *   depends on (seed, traj_ids[j], k, f) alone - not on the batch, the window of columns or the launch:
+ *   Marsaglia's rejection method.  Try t = 0 .. 15 draws Philox4x32-10 (csrc/erpl_philox.h) with key (seed & 0xffffffff,
+ *   seed >> 32) and counter (id & 0xffffffff, id >> 32, (t << 18) | (k << 6) | f, 5), id = traj_ids[j]; A = o0 | o1 << 32,
+ *   B = o2 | o3 << 32; a = ((double)(A >> 12) + 0.5) * 2^-51 - 1.0, b likewise from B; s = a*a + b*b.  The first try with
+ *   s < 1.0 gives d = ((2.0*a) * sqrt(1.0 - s), (2.0*b) * sqrt(1.0 - s), 1.0 - 2.0*s); without one, d = (0, 0, 1).  Every
+ *   operation rounds once: erpl_mc_debris_directions_host gives the device's bits.
+ *   The job is OF PHYSICAL SIZE iff the state AFTER the impulse has sqrt((vx*vx + vy*vy) + vz*vz) <= 1e6 and z >= -1e5.
+ * The fall, in fp64 through the device functions of the ERPL_PREC_F64 build, no contraction:
+ *   RHS at a state: atmosphere(z) -> T, P; rho = P / (Rg * T); g = gravity(z); w = the sample's wind at z; vr = v - w;
+ *     vn = sqrt((vr0*vr0 + vr1*vr1) + vr2*vr2); k = ((0.5 * rho) * vn) / beta[f];
+ *     ds = (vx, vy, vz, -k*vr0, -k*vr1, -k*vr2 - g).  No Mach table, no aerodynamic coefficients, no mass properties.
+ *   Step rule: k0 = the k of the step's own first RHS evaluation; m = the smallest integer in 0..ERPL_DEBRIS_MAX_HALVINGS
+ *     with k0 * (dt * 2^-m) <= stiff_limit, ERPL_DEBRIS_MAX_HALVINGS if there is none.  (A fixed-step RK4 is unstable past
+ *     k * h = 2.8 and overshoots the ground in one step for a light fragment: DESIGN.md 8.18.)
+ *   Classic RK4 with h = dt * 2^-m, h2 = (0.5 * dt) * 2^-m, h6 = (dt / 6.0) * 2^-m: stage states s + h2*k1, s + h2*k2,
+ *     s + h*k3; s' = s + h6 * ((k1 + 2.0*k2) + (2.0*k3 + k4)).
+ *   Time is counted in integer ticks of dt * 2^-16: a step adds 2^(16 - m).
+ *   A start with z <= ground (after the impulse): X, Y the record's own, TFALL = 0, VIMPACT = |v|.  Otherwise steps until
+ *     s' holds a non-finite entry (the job does not land), or
+ *     z' <= ground: wq = (z - ground) / (z - z'); X = x + (x' - x) * wq, Y likewise,
+ *       TFALL = ((double)ticks + wq * 2^(16 - m)) * (dt * 2^-16), VIMPACT = the norm of v + (v' - v) * wq, or
+ *     max_steps RK4 steps of any size are done (the job does not land).
+ *   RANGE = sqrt(dx*dx + dy*dy) of (X - origin_x, Y - origin_y).
+ *   With beta = +inf and dv = 0 no step is halved and all five channels are those of erpl_mc_impact_points with
+ *   drag_scale = 0, to the bit.
+ *   A job that is not evaluated, not of physical size or does not land has NaN in all five channels.
+ * Summary of trajectory j.  Only LANDED jobs take part; candidates are ordered by (value, k * n_fragments + f), so ties go
+ *   to the earliest node and there to the lowest fragment; a row without a candidate is NaN.  ts as for the impact points.
+ *   MAX_RANGE with MAX_RANGE_TIME = ts of its node, MAX_RANGE_X / _Y its impact, MAX_RANGE_FRAGMENT its f.
+ *   EXIT_TIME: ts of the first node at which any fragment lands OUTSIDE the keep-in polygon (the crossing rule of
+ *     erpl_mc_impact_points); EXIT_FRAGMENT the lowest such f there, EXIT_X / _Y its impact.  NaN without a polygon.
+ *   MAX_TFALL with MAX_TFALL_TIME = ts of its node: how long the air space stays hazardous.
+ *   MAX_SPREAD: the largest over nodes of sqrt(dx*dx + dy*dy), dx = max X - min X and dy = max Y - min Y over the node's
+ *     landed jobs (0 for a node with one landed job; a node without one is no candidate); MAX_SPREAD_TIME = ts of the node.
+ *   OUTSIDE: the number of landed jobs outside the polygon (0 if all are inside); NaN without a polygon.
+ *   LANDED, NODES: the number of landed jobs and of evaluated nodes, as doubles.
+ * Errors: ERPL_ERR_INVALID, before any device work and with a message that names the argument, in this order: NULL batch /
+ * out / spec / values; n_nodes, record_stride, max_steps, n_vertices as for erpl_mc_impact_points; n_fragments; the product
+ * n_nodes * n_fragments; dt, ground, origin_x, origin_y; stiff_limit; beta[f] then dv[f] of every fragment f in turn; a
+ * keep-in vertex that is not finite; then everything erpl_mc_impact_points checks from the precision on, the context last.
+ * n_traj == 0 is a no-op that returns ERPL_OK. */
+#define ERPL_DEBRIS_DIM 16             /* = ERPL_SUMMARY_DIM */
+#define ERPL_DEBRIS_MAX_FRAGMENTS 64
+#define ERPL_DEBRIS_MAX_HALVINGS 16
+enum { ERPL_DEBRIS_MAX_RANGE = 0, ERPL_DEBRIS_MAX_RANGE_TIME = 1, ERPL_DEBRIS_MAX_RANGE_X = 2, ERPL_DEBRIS_MAX_RANGE_Y = 3,
+       ERPL_DEBRIS_MAX_RANGE_FRAGMENT = 4, ERPL_DEBRIS_EXIT_TIME = 5, ERPL_DEBRIS_EXIT_FRAGMENT = 6, ERPL_DEBRIS_EXIT_X = 7,
+       ERPL_DEBRIS_EXIT_Y = 8, ERPL_DEBRIS_MAX_TFALL = 9, ERPL_DEBRIS_MAX_TFALL_TIME = 10, ERPL_DEBRIS_MAX_SPREAD = 11,
+       ERPL_DEBRIS_MAX_SPREAD_TIME = 12, ERPL_DEBRIS_OUTSIDE = 13, ERPL_DEBRIS_LANDED = 14, ERPL_DEBRIS_NODES = 15 };
+typedef struct erpl_debris_spec {
+  int32_t n_nodes;         /* 1..ERPL_IIP_MAX_NODES */
+  int32_t record_stride;   /* >= 1 */
+  int32_t max_steps;       /* 1..ERPL_IIP_MAX_STEPS: RK4 steps of any size */
+  int32_t n_vertices;      /* 0 or 3..ERPL_IIP_MAX_VERTICES */
+  int32_t n_fragments;     /* 1..ERPL_DEBRIS_MAX_FRAGMENTS; n_nodes * n_fragments <= ERPL_CORRIDOR_MAX_NODES */
+  uint64_t seed;
+  double dt;               /* finite, > 0 */
+  double ground;           /* finite */
+  double origin_x, origin_y; /* finite */
+  double stiff_limit;      /* in (0, 1] */
+  double beta[ERPL_DEBRIS_MAX_FRAGMENTS];   /* kg/m^2 = m / (Cd A): > 0, +inf allowed (no drag) */
+  double dv[ERPL_DEBRIS_MAX_FRAGMENTS];     /* m/s, finite, >= 0: the speed the break-up imparts, direction isotropic */
+  double keep_x[ERPL_IIP_MAX_VERTICES], keep_y[ERPL_IIP_MAX_VERTICES];
+} erpl_debris_spec;
+/* host only: 16 nodes, record_stride 1, max_steps 20000, dt 0.05, ground 0, origin (0, 0), stiff_limit 0.25, seed 0, one
+ * fragment with beta = +inf and dv = 0, no polygon */
+int erpl_mc_debris_defaults(erpl_debris_spec* spec);
+int erpl_mc_debris(erpl_ctx* ctx, const erpl_batch* batch, const erpl_out* out, const erpl_debris_spec* spec,
+                   double* values, int64_t ld, int64_t col0, double* summary, void* hip_stream);
+/* Host only: the break-up directions of fragment `fragment` at node `node` for the n global sample ids `sample_ids`,
+ * dir [3][n] (component c of id i at dir[c * n + i]), the bits the device draws.  ERPL_ERR_INVALID for a NULL pointer with
+ * n > 0, n < 0, a negative id, node outside 0..ERPL_IIP_MAX_NODES - 1, fragment outside 0..ERPL_DEBRIS_MAX_FRAGMENTS - 1. */
+int erpl_mc_debris_directions_host(uint64_t seed, const int64_t* sample_ids, int64_t n, int32_t node, int32_t fragment,
+                                   double* dir);
+
 /* Host-side input preparation (no device work): the first `m` outputs of NumPy's legacy
  * `np.random.RandomState(seed)` for each of `n` integer seeds, bit for bit - the reference draws
  * every sample's dispersions, motor perturbation and wind turbulence from such per-sample streams
