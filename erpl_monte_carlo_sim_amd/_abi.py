@@ -547,6 +547,34 @@ class ErplReweight(C.Structure):
                 ("ess_expected_share", C.c_double), ("row", ErplRwRowStats * RW_MAX_ROWS)]
 
 
+# erpl_mc_casualty: per_node / per_fragment [CASUALTY_SPLIT_DIM][.], groups [n_nodes * n_fragments][CASUALTY_GROUP_DIM]
+CASUALTY_MAX_GRID = 1024
+CASUALTY_MAX_LEVELS = 8
+CASUALTY_SPLIT_DIM = 5
+CASUALTY_GROUP_DIM = 8
+CASUALTY_EC, CASUALTY_LANDED, CASUALTY_LETHAL, CASUALTY_OFF_GRID, CASUALTY_MISSING = range(5)
+(CASUALTY_G_COUNT, CASUALTY_G_S, CASUALTY_G_MEAN_X, CASUALTY_G_MEAN_Y, CASUALTY_G_HXX, CASUALTY_G_HXY, CASUALTY_G_HYY,
+ CASUALTY_G_W) = range(8)
+
+
+class ErplCasualtySpec(C.Structure):
+    _fields_ = [("n_nodes", C.c_int32), ("n_fragments", C.c_int32), ("bins_x", C.c_int32), ("bins_y", C.c_int32),
+                ("smooth", C.c_int32), ("n_levels", C.c_int32), ("ke_min", C.c_double),
+                ("lo_x", C.c_double), ("hi_x", C.c_double), ("lo_y", C.c_double), ("hi_y", C.c_double),
+                ("bw_scale", C.c_double), ("h_floor", C.c_double), ("level", C.c_double * CASUALTY_MAX_LEVELS),
+                ("pieces", C.c_double * DEBRIS_MAX_FRAGMENTS), ("area", C.c_double * DEBRIS_MAX_FRAGMENTS),
+                ("mass", C.c_double * DEBRIS_MAX_FRAGMENTS)]
+
+
+class ErplCasualty(C.Structure):
+    _fields_ = [("m_c", C.c_int64), ("landed", C.c_int64), ("lethal", C.c_int64), ("off_grid", C.c_int64),
+                ("missing", C.c_int64), ("ec_max_col", C.c_int64), ("q", C.c_int32), ("reserved", C.c_int32),
+                ("ec", C.c_double), ("ec_std", C.c_double), ("ec_se", C.c_double), ("ec_max", C.c_double),
+                ("ec_map", C.c_double), ("w_max", C.c_double), ("cell_area", C.c_double),
+                ("ec_smooth", C.c_double), ("mix_mass", C.c_double),
+                ("level_area", C.c_double * CASUALTY_MAX_LEVELS), ("level_area_smooth", C.c_double * CASUALTY_MAX_LEVELS)]
+
+
 LIB_NAME = "liberpl_mc.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
@@ -584,7 +612,8 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_subset_defaults", "erpl_mc_subset_limit_state", "erpl_mc_subset_limit_state_host",
            "erpl_mc_subset_seeds", "erpl_mc_subset_seeds_host", "erpl_mc_subset_propose", "erpl_mc_subset_propose_host",
            "erpl_mc_subset_commit", "erpl_mc_subset_commit_host", "erpl_mc_subset_chain_stats", "erpl_mc_subset_chain_stats_host",
-           "erpl_mc_reweight_defaults", "erpl_mc_reweight", "erpl_mc_reweight_host")
+           "erpl_mc_reweight_defaults", "erpl_mc_reweight", "erpl_mc_reweight_host",
+           "erpl_mc_casualty_defaults", "erpl_mc_casualty")
 
 _lib = None
 
@@ -739,6 +768,11 @@ def load_library(path=None):
                 C.POINTER(ErplReweight), C.c_void_p, C.c_void_p]
     lib.erpl_mc_reweight.argtypes = [C.c_void_p] + reweight + [C.c_void_p]   # ctx .. hip_stream
     lib.erpl_mc_reweight_host.argtypes = reweight
+    lib.erpl_mc_casualty_defaults.argtypes = [C.POINTER(ErplCasualtySpec)]
+    # ctx, values, ld, m, mask, spec, p_fail, population, ec_traj, per_node, per_fragment, groups, hazard, hazard_words, risk_smooth,
+    # result, hip_stream
+    lib.erpl_mc_casualty.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(ErplCasualtySpec)] + \
+        [C.c_void_p] * 9 + [C.POINTER(ErplCasualty), C.c_void_p]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if a declared symbol is not exported
         if name not in ("erpl_mc_last_error",):

@@ -520,7 +520,7 @@ def _interval(s):
 
 
 def confidence_intervals(summary, status=None, engine=None, rows=None, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95),
-                         replicates=2000, level=0.95, seed=0):
+                         replicates=2000, level=0.95, seed=0, extra=None):
     """Bootstrap confidence intervals of the statistics `native_statistics` reports, on the device: erpl_mc_analyze for
     the reason bytes, then erpl_mc_bootstrap over the samples that carry none.  rows: up to 4 summary rows (default
     apogee, range, flight time).  Returns, per row name (ROW_NAMES), {'mean': {estimate, se, lo, hi}, 'std': {..},
@@ -531,10 +531,17 @@ def confidence_intervals(summary, status=None, engine=None, rows=None, quantiles
     The bootstrap assumes i.i.d. columns.  The columns of a Latin hypercube run (run_monte_carlo_device(design='lhs')) are
     not: they are negatively dependent, the mean of a near-additive output varies far less than resampling its columns
     suggests, and these intervals are conservative (too wide) for such a run.  Its valid error bar comes from independent
-    replicates of the design: `replicate_intervals`."""
+    replicates of the design: `replicate_intervals`.
+
+    extra: a float64 [n] device tensor of one more value per sample (the 'ec_traj' of `casualty_expectation`, say); it joins
+    the rows as _abi.BOOT_ROW_EXTRA - by default behind apogee, range and flight time - and is reported under 'extra'."""
+    from . import _abi
     engine, res, why = _filter(summary, status, engine)
-    b = engine.bootstrap(summary, why, rows=rows, quantiles=quantiles, replicates=replicates, level=level, seed=seed)
-    out = {ROW_NAMES[r]: {"mean": _interval(s["mean"]), "std": _interval(s["std"]),
+    if extra is not None and rows is None:
+        rows = (_abi.SUM_APOGEE_ALT, _abi.SUM_RANGE, _abi.SUM_FLIGHT_TIME, _abi.BOOT_ROW_EXTRA)
+    b = engine.bootstrap(summary, why, rows=rows, quantiles=quantiles, replicates=replicates, level=level, seed=seed, extra=extra)
+    name_of = lambda r: ROW_NAMES[r] if r < len(ROW_NAMES) else "extra"   # noqa: E731
+    out = {name_of(r): {"mean": _interval(s["mean"]), "std": _interval(s["std"]),
                           "percentiles": [_interval(p) for p in s["quantiles"]]} for r, s in zip(b["rows"], b["stats"])}
     out["n_samples"], out["n_outliers"], out["count"] = int(res.n_valid), int(res.n_outliers), b["count"]
     out["quantiles"], out["level"], out["replicates"], out["seed"] = b["q"], b["level"], b["replicates"], b["seed"]
@@ -1610,3 +1617,116 @@ def reweighted_statistics(summary, factors, kinds, law, status=None, engine=None
                           want_weights=want_weights)
     out["n_samples"], out["n_outliers"] = int(res.n_valid), int(res.n_outliers)
     return finish_reweighted(out)
+
+
+# ---------------------------------------------------------------------------------- the casualty expectation of a footprint
+CASUALTY_COUNTS = ("landed", "lethal", "off_grid", "missing")   # rows 1..4 of per_node / per_fragment (_abi.CASUALTY_*)
+
+
+def failure_probabilities(times, rate, t_end=None):
+    """The probability that a launched vehicle breaks up in the interval every node stands for: p_k = exp(-L(t_k)) -
+    exp(-L(t_k+1)) with L the integral of the failure rate (1/s) from 0.  times: the node times, ascending, >= 0; rate: a
+    constant, or one value per node that holds from its node to the next (and from 0 to the first node).  The last node
+    takes the interval to the end of the rate table, t_end: by default one more interval of the length of the one before
+    it (a single node needs t_end).  Returns float64 [len(times)]; the values sum to at most 1."""
+    t = np.asarray(times, dtype=np.float64).reshape(-1)
+    if len(t) < 1 or not np.isfinite(t).all() or t[0] < 0.0 or (np.diff(t) <= 0.0).any():
+        raise ValueError("times: at least one finite value, not negative, ascending")
+    if t_end is None:
+        if len(t) < 2:
+            raise ValueError("a single node needs t_end")
+        t_end = t[-1] + (t[-1] - t[-2])
+    t_end = float(t_end)
+    if not (np.isfinite(t_end) and t_end > t[-1]):
+        raise ValueError("t_end must lie behind the last node")
+    r = np.asarray(rate, dtype=np.float64)
+    r = np.full(len(t), float(r)) if r.ndim == 0 else r.reshape(-1)
+    if len(r) != len(t) or not np.isfinite(r).all() or (r < 0.0).any():
+        raise ValueError("rate: a constant or one value per node, finite and not negative")
+    knots = np.append(t, t_end)
+    L = r[0] * t[0] + np.concatenate(([0.0], np.cumsum(r * np.diff(knots))))   # L at every knot
+    return np.exp(-L[:-1]) - np.exp(-L[1:])
+
+
+def casualty_spec(n_nodes, fragments, bins, ranges, ke_min=15.0, smooth=True, bw_scale=1.0, h_floor=1.0, levels=(1e-6, 1e-5)):
+    """The spec of erpl_mc_casualty (_abi.ErplCasualtySpec) on top of the library's defaults, every argument checked as a
+    Python int or float before a 32-bit field can truncate it.  fragments: (pieces, area, mass) triples; bins: (bins_x,
+    bins_y); ranges: ((lo_x, hi_x), (lo_y, hi_y))."""
+    import ctypes as C
+    from . import _abi
+    n_nodes = int(n_nodes)
+    frags = [tuple(float(v) for v in f) for f in fragments]
+    if not 1 <= len(frags) <= _abi.DEBRIS_MAX_FRAGMENTS or any(len(f) != 3 for f in frags):
+        raise ValueError(f"1 to {_abi.DEBRIS_MAX_FRAGMENTS} fragments, each (pieces, area, mass)")
+    if not 1 <= n_nodes <= _abi.IIP_MAX_NODES or n_nodes * len(frags) > _abi.CORRIDOR_MAX_NODES:
+        raise ValueError(f"1 to {_abi.IIP_MAX_NODES} nodes, at most {_abi.CORRIDOR_MAX_NODES} nodes * fragments")
+    for f in frags:
+        if not all(np.isfinite(v) and v >= 0.0 for v in f):
+            raise ValueError("pieces, area and mass of a fragment must be finite and not negative")
+    bins_x, bins_y = (int(b) for b in bins)
+    if not (1 <= bins_x <= _abi.CASUALTY_MAX_GRID and 1 <= bins_y <= _abi.CASUALTY_MAX_GRID):
+        raise ValueError(f"1 to {_abi.CASUALTY_MAX_GRID} cells per axis")
+    (lo_x, hi_x), (lo_y, hi_y) = ((float(a), float(b)) for a, b in ranges)
+    if not (np.isfinite([lo_x, hi_x, lo_y, hi_y]).all() and lo_x < hi_x and lo_y < hi_y):
+        raise ValueError("ranges: ((lo_x, hi_x), (lo_y, hi_y)), finite, lo < hi")
+    ke_min, bw_scale, h_floor = float(ke_min), float(bw_scale), float(h_floor)
+    if not (np.isfinite(ke_min) and ke_min >= 0.0):
+        raise ValueError("ke_min must be finite and not negative")
+    if not (np.isfinite(bw_scale) and bw_scale > 0.0 and np.isfinite(h_floor) and h_floor > 0.0):
+        raise ValueError("bw_scale and h_floor must be finite and positive")
+    levels = [float(v) for v in levels]
+    if len(levels) > _abi.CASUALTY_MAX_LEVELS or not all(0.0 < v < 1.0 for v in levels):
+        raise ValueError(f"at most {_abi.CASUALTY_MAX_LEVELS} levels, each in (0, 1)")
+    lib = _abi.load_library()
+    spec = _abi.ErplCasualtySpec()
+    _abi.check(lib, lib.erpl_mc_casualty_defaults(C.byref(spec)), "erpl_mc_casualty_defaults")
+    spec.n_nodes, spec.n_fragments, spec.bins_x, spec.bins_y = n_nodes, len(frags), bins_x, bins_y
+    spec.smooth, spec.n_levels, spec.ke_min = int(bool(smooth)), len(levels), ke_min
+    spec.lo_x, spec.hi_x, spec.lo_y, spec.hi_y, spec.bw_scale, spec.h_floor = lo_x, hi_x, lo_y, hi_y, bw_scale, h_floor
+    for i in range(_abi.CASUALTY_MAX_LEVELS):
+        spec.level[i] = levels[i] if i < len(levels) else 0.0
+    for f, (pieces, area, mass) in enumerate(frags):
+        spec.pieces[f], spec.area[f], spec.mass[f] = pieces, area, mass
+    return spec
+
+
+def casualty_result_dict(spec, res, p_fail, per_node, per_fragment, groups, hazard, words, risk):
+    """What erpl_mc_casualty hands back as a dict: m_c and the job counts, ec / ec_std / ec_se / ec_max / ec_max_col, ec_map,
+    ec_smooth, mix_mass, q, w_max, cell_area, levels with level_area / level_area_smooth, 'per_node' and 'per_fragment'
+    ({'ec', 'landed', 'lethal', 'off_grid', 'missing'} -> NumPy), 'groups' ([rows, 8], _abi.CASUALTY_G_*), 'hazard',
+    'hazard_words', 'risk_count' (hazard / cell_area), 'risk_smooth' (None without smoothing), the edges and centres of the
+    raster, 'p_fail' and 'missing_share', the share of the jobs of counted columns that carry no landing."""
+    K, F, nl = spec.n_nodes, spec.n_fragments, spec.n_levels
+    split = lambda a: dict(zip(("ec",) + CASUALTY_COUNTS, (a[i].copy() for i in range(5))))   # noqa: E731
+    ex, ey = np.linspace(spec.lo_x, spec.hi_x, spec.bins_x + 1), np.linspace(spec.lo_y, spec.hi_y, spec.bins_y + 1)
+    jobs = int(res.m_c) * K * F
+    out = {k: int(getattr(res, k)) for k in ("m_c", "landed", "lethal", "off_grid", "missing", "ec_max_col", "q")}
+    out.update({k: float(getattr(res, k)) for k in ("ec", "ec_std", "ec_se", "ec_max", "ec_map", "w_max", "cell_area", "ec_smooth",
+                                                    "mix_mass")})
+    out.update({"n_nodes": K, "n_fragments": F, "levels": list(spec.level[:nl]), "level_area": list(res.level_area[:nl]),
+                "level_area_smooth": list(res.level_area_smooth[:nl]), "per_node": split(per_node),
+                "per_fragment": split(per_fragment), "groups": groups, "hazard": hazard, "hazard_words": words,
+                "risk_count": hazard / float(res.cell_area), "risk_smooth": risk, "edges_x": ex, "edges_y": ey,
+                "centres_x": 0.5 * (ex[:-1] + ex[1:]), "centres_y": 0.5 * (ey[:-1] + ey[1:]),
+                "ranges": ((spec.lo_x, spec.hi_x), (spec.lo_y, spec.hi_y)), "p_fail": np.asarray(p_fail, dtype=np.float64).copy(),
+                "ke_min": float(spec.ke_min), "missing_share": int(res.missing) / jobs if jobs else float("nan")})
+    return out
+
+
+def casualty_expectation(values, fragments, p_fail, population, ranges, mask=None, engine=None, times=None, **kw):
+    """The casualty expectation of a debris footprint, assembled on the host around TrajectoryEngine.casualty (its arguments;
+    `population` may be a NumPy array, it is uploaded).  On top of that call's dict: 'time' (the node times, if given),
+    'population' (the device tensor), 'ec_contribution' [nodes] = p_fail * per_node['ec'] - what every break-up time adds to
+    ec - and 'fragment_share' [fragments] = per_fragment['ec'] / ec."""
+    import torch
+    engine = _engine_of(values, engine)
+    if not torch.is_tensor(population):
+        population = torch.as_tensor(np.ascontiguousarray(population, dtype=np.float64), device=engine.device)
+    out = engine.casualty(values, fragments, p_fail, population.contiguous(), ranges, mask=mask, **kw)
+    out["time"] = None if times is None else np.asarray(times, dtype=np.float64).copy()
+    out["population"] = population
+    out["fragments"] = [tuple(float(v) for v in f) for f in fragments]
+    out["ec_contribution"] = out["p_fail"] * out["per_node"]["ec"]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["fragment_share"] = out["per_fragment"]["ec"] / out["ec"]
+    return out

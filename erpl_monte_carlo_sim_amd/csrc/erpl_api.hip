@@ -477,6 +477,7 @@ int erpl_mc_destroy(erpl_ctx* c) {
   if (c->subset_pin) (void)hipHostFree(c->subset_pin);
   if (c->subset_ev) (void)hipEventDestroy(c->subset_ev);
   c->reweight.release();
+  c->casualty.release();
   if (c->reweight_pin) (void)hipHostFree(c->reweight_pin);
   delete c;
   return ERPL_OK;

@@ -1,5 +1,5 @@
 // erpl_host.h — what the host units of the C ABI share (erpl_api.hip, erpl_sampling.hip, erpl_stats_api.hip,
-// erpl_legacy_device.hip, erpl_design.hip, erpl_qmc.hip, erpl_tally.hip, erpl_subset.hip, erpl_reweight.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
+// erpl_legacy_device.hip, erpl_design.hip, erpl_qmc.hip, erpl_tally.hip, erpl_subset.hip, erpl_reweight.hip, erpl_casualty.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
 // Internal, never installed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -262,6 +262,9 @@ struct erpl_ctx {
   // erpl_reweight.hip, the log-weights and the weights the caller does not keep); the pinned copy of the sums it hands back
   ErplStatUnit<void, char> reweight;
   char* reweight_pin = nullptr;
+  // erpl_mc_casualty: the pieces erpl_casualty.hip lists (its fixed block, the words of the map, the dense members of the groups,
+  // the partials of the smoothing pass) in the buffer; what comes back is small or caller-sized and needs no pinned mirror
+  ErplStatUnit<void, char> casualty;
 };
 
 // erpl_design.hip

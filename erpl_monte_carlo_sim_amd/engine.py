@@ -452,6 +452,53 @@ class TrajectoryEngine:
                    C.c_void_p(summ.data_ptr()) if summ is not None else None, C.c_void_p(st.cuda_stream))
         return out, summ
 
+    def casualty(self, values, fragments, p_fail, population, ranges, mask=None, m=None, ke_min=15.0, smooth=True, bw_scale=1.0,
+                 h_floor=1.0, levels=(1e-6, 1e-5), want_traj=True):
+        """The casualty expectation of a debris footprint (erpl_mc_casualty; the definitions are in include/erpl_mc.h).
+        values: the float64 [5, nodes * len(fragments), ld] device tensor of `debris` (or of `impact_points` with one
+        fragment), of which the first m columns are read (default ld); fragments: 1 to 64 triples (pieces, casualty area
+        in m^2, mass in kg); p_fail: the probability of a break-up in the interval of every node (host values, at most 1
+        together; analysis.failure_probabilities); population: float64 [bins_x, bins_y] device tensor, persons / m^2, 1 to
+        1024 cells per axis over ranges = ((lo_x, hi_x), (lo_y, hi_y)); mask uint8 [m] on the device, a column counts iff
+        its byte is 0.  Enqueued on the current torch stream; blocks the host until the result is there.  Returns the dict
+        of analysis.casualty_result_dict; 'ec_traj' (float64 [m] on the device, NaN where the column is not counted; None
+        with want_traj=False) and the inputs stay on the device."""
+        from . import analysis
+        if not (torch.is_tensor(values) and values.is_cuda and values.device == self.device and values.dtype == torch.float64
+                and values.dim() == 3 and values.is_contiguous() and values.shape[0] == _abi.IIP_CH_COUNT):
+            raise ValueError(f"values must be a contiguous float64 [{_abi.IIP_CH_COUNT}, nodes * fragments, ld] tensor on {self.device}")
+        rows, ld = int(values.shape[1]), int(values.shape[2])
+        m = ld if m is None else int(m)
+        if not 1 <= m <= ld or m >= 2 ** 31:
+            raise ValueError(f"m = {m}: 1 to ld = {ld} columns, fewer than 2**31")
+        if mask is not None and not (torch.is_tensor(mask) and mask.device == self.device and mask.dtype == torch.uint8
+                                     and tuple(mask.shape) == (m,) and mask.is_contiguous()):
+            raise ValueError(f"mask must be a contiguous uint8 [m] tensor on {self.device}")
+        if not (torch.is_tensor(population) and population.is_cuda and population.device == self.device
+                and population.dtype == torch.float64 and population.dim() == 2 and population.is_contiguous()):
+            raise ValueError(f"population must be a contiguous float64 [bins_x, bins_y] tensor on {self.device}")
+        p_fail = np.ascontiguousarray(np.asarray(p_fail, dtype=np.float64).reshape(-1))
+        spec = analysis.casualty_spec(len(p_fail), fragments, tuple(population.shape), ranges, ke_min, smooth, bw_scale, h_floor, levels)
+        K, F = spec.n_nodes, spec.n_fragments
+        if K * F != rows:
+            raise ValueError(f"values holds {rows} rows per channel, p_fail and fragments make {K} * {F}")
+        cells = (spec.bins_x, spec.bins_y)
+        per_node, per_fragment = np.zeros((_abi.CASUALTY_SPLIT_DIM, K)), np.zeros((_abi.CASUALTY_SPLIT_DIM, F))
+        groups = np.zeros((rows, _abi.CASUALTY_GROUP_DIM))
+        hazard, words = np.zeros(cells), np.zeros(cells, dtype=np.int64)
+        risk = np.zeros(cells) if spec.smooth else None
+        ec = torch.empty((m,), dtype=torch.float64, device=self.device) if want_traj else None
+        res = _abi.ErplCasualty()
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)   # noqa: E731
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_casualty", C.c_void_p(values.data_ptr()), ld, m, C.c_void_p(mask.data_ptr()) if mask is not None else None,
+                   C.byref(spec), ptr(p_fail), C.c_void_p(population.data_ptr()), C.c_void_p(ec.data_ptr()) if want_traj else None,
+                   ptr(per_node), ptr(per_fragment), ptr(groups), ptr(hazard), ptr(words), ptr(risk), C.byref(res),
+                   C.c_void_p(st.cuda_stream))
+        out = analysis.casualty_result_dict(spec, res, p_fail, per_node, per_fragment, groups, hazard, words, risk)
+        out["ec_traj"] = ec
+        return out
+
     def corridor_spec(self, channels=None, nodes=None, t0=None, dt=None, hold=False, quantiles=None):
         """The library's erpl_corridor_spec (erpl_mc_corridor_defaults: altitude, downrange, speed; 256 nodes 1 s apart
         from 0; 5/25/50/75/95 %) with what is given overridden.  channels: _abi.CH_* indices."""

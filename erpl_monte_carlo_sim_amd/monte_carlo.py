@@ -976,6 +976,42 @@ class MonteCarloAnalyzer:
                               "sub_batches": run["sub_batches"], "sub_batch_samples": run["per_batch"]}
         return out
 
+    def casualty_expectation(self, footprint, population, ranges, fragments, p_fail=None, failure_rate=None, ke_min=15.0,
+                             smooth=True, bw_scale=1.0, h_floor=1.0, levels=(1e-6, 1e-5)):
+        """The number a range signs (no reference counterpart): the casualty expectation Ec and the individual-risk map of
+        the footprint `debris_footprint` returned - its 'values', 'reasons', 'time' and 'fragments' are read.  population:
+        persons / m^2 on a [bins_x, bins_y] raster over ranges = ((lo_x, hi_x), (lo_y, hi_y)) (NumPy or device tensor);
+        fragments: one (pieces, casualty area in m^2, mass in kg) per fragment class of the footprint; p_fail: the probability
+        of a break-up per node, or failure_rate (1/s, a constant or one value per node) from which
+        `analysis.failure_probabilities` makes them over footprint['time'].  A fragment is lethal from ke_min joules on.
+        Returns the dict of `analysis.casualty_expectation`; its 'ec_traj' is a per-sample row for `confidence_intervals`
+        (extra=...), `drivers` and `dependence`."""
+        from . import analysis as ana
+        frags = [tuple(float(v) for v in f) for f in fragments]
+        if len(frags) != len(footprint["fragments"]):
+            raise ValueError(f"the footprint has {len(footprint['fragments'])} fragment classes, {len(frags)} were given")
+        if (p_fail is None) == (failure_rate is None):
+            raise ValueError("give p_fail or failure_rate")
+        times = np.asarray(footprint["time"], dtype=np.float64)
+        if p_fail is None:
+            p_fail = ana.failure_probabilities(times, failure_rate, t_end=None if len(times) > 1 else times[0] + 1.0)
+        p_fail = np.asarray(p_fail, dtype=np.float64).reshape(-1)
+        if len(p_fail) != len(times):
+            raise ValueError(f"p_fail holds {len(p_fail)} values, the footprint has {len(times)} nodes")
+        bins = tuple(population.shape) if hasattr(population, "shape") else np.asarray(population).shape
+        if len(bins) != 2:
+            raise ValueError("population must be a [bins_x, bins_y] raster")
+        ana.casualty_spec(len(p_fail), frags, bins, ranges, ke_min, smooth, bw_scale, h_floor, levels)   # refuses before any device work
+        return ana.casualty_expectation(footprint["values"], frags, p_fail, population, ranges, mask=footprint["reasons"],
+                                        engine=shared_engine(self.device), times=times, ke_min=ke_min, smooth=smooth,
+                                        bw_scale=bw_scale, h_floor=h_floor, levels=levels)
+
+    def plot_casualty(self, casualty, save_plots=True):
+        """No reference counterpart: the result of `casualty_expectation` - the smoothed risk map with its level contours
+        over the population raster, Ec given a break-up at t, the contribution of every fragment class - as
+        monte_carlo_casualty.png in the output directory; returns that directory."""
+        return plots.plot_casualty(self, casualty, save_plots)
+
     def plot_debris_footprint(self, footprint, node=None, save_plots=True):
         """No reference counterpart: the footprint of `debris_footprint` - per fragment the median and the outer band of the
         impact range over the time of break-up, the footprint at `node` (default: the last one) with the keep-in outline - as
@@ -1038,16 +1074,17 @@ class MonteCarloAnalyzer:
         return ana.drivers(torch.as_tensor(summ, device=eng.device).contiguous(),
                            torch.as_tensor(fac, device=eng.device).contiguous(), names, engine=eng, rows=rows)
 
-    def confidence_intervals(self, analysis, replicates=2000, level=0.95, seed=0):
+    def confidence_intervals(self, analysis, replicates=2000, level=0.95, seed=0, extra=None):
         """How sure the statistics of an analysis are (no reference counterpart): `analysis.confidence_intervals` - bootstrap
         standard errors and percentile intervals of mean, std and the five percentiles of apogee, range and flight time -
         on either kind of analysis dict, as `drivers` takes its inputs: the device 'summary' / 'status' of
-        run_monte_carlo_device, or the summary columns of analysis['results'] uploaded."""
+        run_monte_carlo_device, or the summary columns of analysis['results'] uploaded.  extra: one more per-sample row on
+        the device (the 'ec_traj' of `casualty_expectation`), reported under 'extra'."""
         from . import analysis as ana
         eng = shared_engine(self.device)
         if "summary" in analysis:
             return ana.confidence_intervals(analysis["summary"], status=analysis.get("status"), engine=eng,
-                                            replicates=replicates, level=level, seed=seed)
+                                            replicates=replicates, level=level, seed=seed, extra=extra)
         summ = ana.summary_from_results(analysis["results"])
         return ana.confidence_intervals(torch.as_tensor(summ, device=eng.device).contiguous(), engine=eng,
                                         replicates=replicates, level=level, seed=seed)

@@ -386,6 +386,59 @@ def debris_footprint_figure(result, node=None):
     return fig
 
 
+def casualty_figure(result):
+    """The dict of analysis.casualty_expectation in three panels: the individual-risk map - the smoothed one, or the counted
+    one where the call did not smooth - as an image with one contour per level of result['levels'] over the outlines of the
+    population raster; Ec given a break-up at t over the time of break-up (the node index without times) with what every
+    node adds to Ec, p_fail * Ec|t, on a second axis; one bar per fragment class with its contribution to Ec."""
+    pop = result.get("population")
+    pop = None if pop is None else np.asarray(pop.cpu() if hasattr(pop, "cpu") else pop, dtype=np.float64)
+    smooth = result.get("risk_smooth") is not None
+    risk = np.asarray(result["risk_smooth"] if smooth else result["risk_count"], dtype=np.float64)
+    ex, ey = np.asarray(result["edges_x"]), np.asarray(result["edges_y"])
+    cx, cy = np.asarray(result["centres_x"]), np.asarray(result["centres_y"])
+    fig = _figure((16, 5))
+    ax_m, ax_t, ax_f = fig.subplots(1, 3)
+    mesh = ax_m.pcolormesh(ex, ey, np.ma.masked_less_equal(risk.T, 0.0), cmap="magma_r", shading="flat")
+    fig.colorbar(mesh, ax=ax_m, label="individual risk per launch")
+    if pop is not None and pop.shape == risk.shape and len(cx) > 1 and len(cy) > 1 and pop.max() > pop.min():
+        ax_m.contour(cx, cy, pop.T, levels=[0.5 * (pop.min() + pop.max())], colors="tab:blue", linewidths=0.8, linestyles="dashed")
+    levels = sorted(float(v) for v in result.get("levels", ()))
+    drawn = [lv for lv in levels if len(cx) > 1 and len(cy) > 1 and risk.min() < lv < risk.max()]
+    if drawn:
+        cs = ax_m.contour(cx, cy, risk.T, levels=drawn, colors="black", linewidths=1.0)
+        ax_m.clabel(cs, fmt=lambda v: f"{v:.0e}", fontsize=7)
+    kind = "smoothed" if smooth else "counted"
+    ax_m.set_title(f"Individual Risk ({kind}); Ec = {result['ec']:.3g} +- {result['ec_se']:.2g}\n"
+                   f"missing jobs {100 * result['missing_share']:.1f} %, off the raster {result['off_grid']}")
+    ax_m.set_xlabel("X (m)")
+    ax_m.set_ylabel("Y (m)")
+    node_ec = np.asarray(result["per_node"]["ec"], dtype=np.float64)
+    t = result.get("time")
+    t = np.arange(len(node_ec), dtype=np.float64) if t is None else np.asarray(t, dtype=np.float64)
+    ax_t.plot(t, node_ec, color="tab:red", linewidth=1.4, label="Ec given break-up at t")
+    ax_t.set_xlabel("Time of Break-up (s)" if result.get("time") is not None else "Node")
+    ax_t.set_ylabel("Expected Casualties given Break-up")
+    ax_t.grid(True, alpha=0.3)
+    ax_c = ax_t.twinx()
+    ax_c.bar(t, np.asarray(result["ec_contribution"], dtype=np.float64), width=0.6 * (t[1] - t[0] if len(t) > 1 else 1.0),
+             color="tab:gray", alpha=0.4, label="contribution to Ec")
+    ax_c.set_ylabel("p_fail * Ec given Break-up")
+    ax_t.set_title("Ec over the Time of Break-up")
+    ax_t.legend(loc="upper left", fontsize=8)
+    frag_ec = np.asarray(result["per_fragment"]["ec"], dtype=np.float64)
+    frags = list(result.get("fragments") or [None] * len(frag_ec))
+    labels = [f"{f}" if fr is None else f"{fr[0]:g} x {fr[1]:g} m2, {fr[2]:g} kg" for f, fr in enumerate(frags)]
+    ax_f.bar(np.arange(len(frag_ec)), frag_ec, color=[f"C{f % 10}" for f in range(len(frag_ec))])
+    ax_f.set_xticks(np.arange(len(frag_ec)))
+    ax_f.set_xticklabels(labels, rotation=30, ha="right", fontsize=7)
+    ax_f.set_ylabel("Contribution to Ec")
+    ax_f.set_title("Ec by Fragment Class")
+    ax_f.grid(True, axis="y", alpha=0.3)
+    fig.tight_layout()
+    return fig
+
+
 def sobol_figure(result):
     """The dict of analysis.sobol_indices as paired bars: per row one panel, per group the first-order index S1 and the
     total-effect index ST side by side in the order of `group_names`, their bootstrap percentile intervals (lo, hi) as
@@ -862,6 +915,17 @@ def plot_debris_footprint(analyzer, footprint, node=None, save_plots=True):
     if save_plots:
         output_dir = analyzer._create_output_directory()
         print(f"Debris footprint plot saved to: {save_figure(fig, output_dir, 'monte_carlo_debris.png')}")
+    return output_dir
+
+
+def plot_casualty(analyzer, casualty, save_plots=True):
+    """The result of MonteCarloAnalyzer.casualty_expectation (no reference counterpart) as monte_carlo_casualty.png; returns the
+    output directory (None without save_plots)."""
+    fig = casualty_figure(casualty)
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Casualty expectation plot saved to: {save_figure(fig, output_dir, 'monte_carlo_casualty.png')}")
     return output_dir
 
 

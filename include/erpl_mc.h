@@ -529,6 +529,112 @@ int erpl_mc_debris(erpl_ctx* ctx, const erpl_batch* batch, const erpl_out* out, 
 int erpl_mc_debris_directions_host(uint64_t seed, const int64_t* sample_ids, int64_t n, int32_t node, int32_t fragment,
                                    double* dir);
 
+/* The casualty expectation of a debris footprint ON THE DEVICE (no reference counterpart): the expected number of people hit,
+ * Ec = sum over break-up times and fragment classes of (probability of break-up) * (pieces) * (casualty area) * (population
+ * density where the piece lands), its split by node and by fragment class, the hazard map in exact integers and the smoothed
+ * individual-risk map.  `values` is the matrix of erpl_mc_debris - or of erpl_mc_impact_points with n_fragments = 1 - as it
+ * is: CALLER-OWNED device memory, double [ERPL_IIP_CH_COUNT][n_nodes * n_fragments][ld], row r = k * n_fragments + f, of which
+ * the first m columns are read.  `mask` as for erpl_mc_corridor_bands: NULL = every column, otherwise column j is COUNTED iff
+ * mask[j] == 0; m_c is the number of counted columns.  p_fail: HOST memory [n_nodes], p_fail[k] the probability that a
+ * launched vehicle breaks up in the interval node k stands for.  population: DEVICE memory [bins_x][bins_y], persons / m^2,
+ * cell (ix, iy) at population[ix * bins_y + iy].  The work is enqueued on `hip_stream`; the call returns when the result is
+ * filled.  The workspace belongs to the context.
+ *
+ * A JOB is (column j, node k, fragment f); every operation below rounds on its own (no contraction).
+ *   LANDED iff X, Y and VIMPACT of the job are all finite.  A NaN job (not evaluated, not of physical size or not landed:
+ *     the matrix does not say which) contributes NOTHING and is counted in `missing`.  The denominator of every expectation
+ *     is m_c for every node, on purpose: p_fail[k] is the probability that a LAUNCHED vehicle breaks up at node k, and a
+ *     flight that is already down at that time cannot.  The share of missing jobs is reported so that a zero contribution
+ *     cannot hide a hazard: read `missing` next to every Ec.
+ *   LETHAL iff landed and (0.5 * mass[f]) * (V * V) >= ke_min (ke_min = 0: every landed job).
+ *   Cell: erpl_mc_histogram_xy's rule over the fixed ranges - on the raster iff lo_x <= X <= hi_x and lo_y <= Y <= hi_y, the
+ *     bin of np.histogram on both axes over the edges np.linspace(lo, hi, bins + 1).  A lethal job off the raster has
+ *     density 0 and is counted in `off_grid`.
+ *   c_f = pieces[f] * area[f]; hazard h = c_f * population[cell] of a lethal job on the raster, else 0.
+ *   All counts (landed, lethal, off_grid, missing) are over the counted columns.
+ * ec_traj[j] (DEVICE memory [m], or NULL): e = 0; for k in order { s = 0; for f in order s += h; e += p_fail[k] * s }; NaN
+ *   for a column that is not counted.  An ordinary per-sample row: the `extra` of erpl_mc_bootstrap, _correlation, _dependence.
+ * Totals, by the fixed-order reductions every statistics call uses: ec = mean of the counted e_j, ec_std (divisor m_c - 1),
+ *   ec_se = ec_std / sqrt(m_c), ec_max = the largest e_j and ec_max_col its column (ties: the lowest; -1 if m_c = 0).
+ *   S_kf = sum over counted j of h_jkf.  m_c = 0: ec, ec_std, ec_se and ec_max are NaN.
+ * per_node (HOST, [ERPL_CASUALTY_SPLIT_DIM][n_nodes], or NULL): row 0 ec_node[k] = (sum_f S_kf, in f order) / m_c - Ec GIVEN
+ *   a break-up at node k, which is what a termination rule weighs; rows 1..4 landed, lethal, off_grid, missing as doubles.
+ * per_fragment (HOST, [ERPL_CASUALTY_SPLIT_DIM][n_fragments], or NULL): row 0 ec_fragment[f] = (sum_k p_fail[k] * S_kf, in k
+ *   order) / m_c; rows 1..4 as above.  sum_k p_fail[k] * ec_node[k] = sum_f ec_fragment[f] = ec up to rounding.
+ * groups (HOST, [n_nodes * n_fragments][ERPL_CASUALTY_GROUP_DIM], or NULL): per row r m_kf (the lethal jobs of counted
+ *   columns, on the raster or not), S_kf, mean_x, mean_y, h_xx, h_xy, h_yy, w_kf.  Mean and H are NaN for an empty group and
+ *   with smooth = 0.
+ * Hazard map.  w_kf = p_fail[k] * c_f, w_max their maximum; Q = min(40, 62 - bit_length(m * n_nodes * n_fragments));
+ *   W_kf = floor((w_kf / w_max) * 2^Q) (0 if w_max = 0), on the host.  Every lethal on-raster job of a counted column adds
+ *   W_kf to the 64-bit integer M of its cell: integer adds alone, so the bytes of M depend on the SET of jobs, not on their
+ *   order.  hazard (HOST, [bins_x][bins_y], or NULL): hazard[c] = (double)M[c] * ((w_max * 2^-Q) / m_c), the expected casualty
+ *   area deposited on the cell; hazard[c] / cell_area, cell_area = ((hi_x - lo_x) / bins_x) * ((hi_y - lo_y) / bins_y), is the
+ *   probability that a person standing there is hit.  ec_map = sum_c hazard[c] * population[c], in cell order: it agrees with
+ *   ec to within lethal * w_max * 2^-Q * max(population) / m_c plus rounding.  level_area[i]: cell_area times the number of
+ *   cells with hazard[c] / cell_area >= level[i].  hazard_words (HOST, int64 [bins_x][bins_y], or NULL): M itself.
+ * Smoothed individual risk (smooth = 1; the hot path).  Group r = (k, f): its m_kf lethal landed jobs of counted columns, in
+ *   column order.  Mean and sample covariance S (divisor m_kf - 1; the zero matrix for m_kf < 2) from two fixed-order passes;
+ *   H_r = (bw_scale * m_kf^(-1/6))^2 S + h_floor^2 I: the floor makes every non-empty group solid (planar runs, whose Y is
+ *   constant, included) and stands for the size of what is being hit.  At the centre g = (0.5 * (ex[ix] + ex[ix + 1]),
+ *   0.5 * (ey[iy] + ey[iy + 1])) of every cell, e the edges above:
+ *     risk_smooth(g) = sum_r (w_r / m_c) sum_{j in group r} exp(-0.5 (g - x_j)' H_r^-1 (g - x_j)) / (2 pi sqrt(det H_r))
+ *   evaluated as erpl_mc_impact_density evaluates its pairs: members and centres are centred on the group's mean and mapped
+ *   through the inverse Cholesky factor of H_r (u = w11 dx, v = fma(w21, dx, w22 dy)), a pair costs two subtractions, one
+ *   product, one FMA, one product by -0.5, exp and one addition.  Order: a thread adds the members of a group in column
+ *   order, t = t + norm_r * (sum of the group), rows r ascending inside a slice; slice s holds the rows s * per ..
+ *   s * per + per - 1 with per = ceil(R / min(R, ceil(1024 / ceil(cells / 1024)))), R = n_nodes * n_fragments - a function of
+ *   the shapes alone; the slices of a cell are added in slice order.  No floating-point atomics: two calls return the same
+ *   bytes.  A group whose H is not finite and positive definite (coordinates beyond 1e150) is left out.
+ *   risk_smooth (HOST, [bins_x][bins_y], or NULL).  ec_smooth = sum_g risk_smooth(g) * population(g) * cell_area;
+ *   mix_mass = sum_g risk_smooth(g) * cell_area / sum_r (w_r m_kf / m_c): the share of the smoothed mass the raster covers
+ *   (NaN if the denominator is 0); level_area_smooth[i] as level_area.  With smooth = 0 these are NaN and risk_smooth is not
+ *   written.
+ * Errors: ERPL_ERR_INVALID, before any device work and with a message that names the argument, in this order: NULL values /
+ * spec / p_fail / population / result; n_nodes; n_fragments; the product n_nodes * n_fragments; per fragment pieces, then
+ * area, then mass; ke_min; bins_x, bins_y, then the two ranges; smooth, bw_scale, h_floor; the levels; a p_fail[k] that is
+ * not finite or negative, or their sum above 1 + 1e-12; m <= 0 or m >= 2^31; ld < m; Q < 16; the context last.  A population
+ * entry that is negative or not finite is found by the first device pass: ERPL_ERR_INVALID after that pass, before anything
+ * is written to an output.  w_max == 0 is no error: everything is zero. */
+#define ERPL_CASUALTY_MAX_GRID 1024     /* cells per axis */
+#define ERPL_CASUALTY_MAX_LEVELS 8
+#define ERPL_CASUALTY_SPLIT_DIM 5
+#define ERPL_CASUALTY_GROUP_DIM 8
+enum { ERPL_CASUALTY_EC = 0, ERPL_CASUALTY_LANDED = 1, ERPL_CASUALTY_LETHAL = 2, ERPL_CASUALTY_OFF_GRID = 3,
+       ERPL_CASUALTY_MISSING = 4 };
+enum { ERPL_CASUALTY_G_COUNT = 0, ERPL_CASUALTY_G_S = 1, ERPL_CASUALTY_G_MEAN_X = 2, ERPL_CASUALTY_G_MEAN_Y = 3,
+       ERPL_CASUALTY_G_HXX = 4, ERPL_CASUALTY_G_HXY = 5, ERPL_CASUALTY_G_HYY = 6, ERPL_CASUALTY_G_W = 7 };
+typedef struct erpl_casualty_spec {
+  int32_t n_nodes;         /* 1..ERPL_IIP_MAX_NODES */
+  int32_t n_fragments;     /* 1..ERPL_DEBRIS_MAX_FRAGMENTS; n_nodes * n_fragments <= ERPL_CORRIDOR_MAX_NODES */
+  int32_t bins_x, bins_y;  /* 1..ERPL_CASUALTY_MAX_GRID */
+  int32_t smooth;          /* 0 / 1 */
+  int32_t n_levels;        /* 0..ERPL_CASUALTY_MAX_LEVELS */
+  double ke_min;           /* J, finite, >= 0 */
+  double lo_x, hi_x, lo_y, hi_y;   /* finite, lo < hi */
+  double bw_scale;         /* finite, > 0 */
+  double h_floor;          /* m, finite, > 0 */
+  double level[ERPL_CASUALTY_MAX_LEVELS];        /* individual risk, each in (0, 1) */
+  double pieces[ERPL_DEBRIS_MAX_FRAGMENTS];      /* finite, >= 0: how many pieces the class stands for */
+  double area[ERPL_DEBRIS_MAX_FRAGMENTS];        /* m^2, finite, >= 0: casualty area of one piece */
+  double mass[ERPL_DEBRIS_MAX_FRAGMENTS];        /* kg, finite, >= 0 */
+} erpl_casualty_spec;
+typedef struct erpl_casualty {
+  int64_t m_c, landed, lethal, off_grid, missing;   /* counted columns; jobs of counted columns */
+  int64_t ec_max_col;
+  int32_t q, reserved;
+  double ec, ec_std, ec_se, ec_max;
+  double ec_map, w_max, cell_area;
+  double ec_smooth, mix_mass;
+  double level_area[ERPL_CASUALTY_MAX_LEVELS], level_area_smooth[ERPL_CASUALTY_MAX_LEVELS];
+} erpl_casualty;
+/* host only: 16 nodes, one fragment (1 piece, 1 m^2, 1 kg), ke_min 15 J, a 64 x 64 raster over [-1000, 1000]^2, smooth 1,
+ * bw_scale 1, h_floor 1 m, levels 1e-6 and 1e-5 */
+int erpl_mc_casualty_defaults(erpl_casualty_spec* spec);
+int erpl_mc_casualty(erpl_ctx* ctx, const double* values, int64_t ld, int64_t m, const uint8_t* mask,
+                     const erpl_casualty_spec* spec, const double* p_fail, const double* population, double* ec_traj,
+                     double* per_node, double* per_fragment, double* groups, double* hazard, int64_t* hazard_words,
+                     double* risk_smooth, erpl_casualty* result, void* hip_stream);
+
 /* Host-side input preparation (no device work): the first `m` outputs of NumPy's legacy
  * `np.random.RandomState(seed)` for each of `n` integer seeds, bit for bit - the reference draws
  * every sample's dispersions, motor perturbation and wind turbulence from such per-sample streams
