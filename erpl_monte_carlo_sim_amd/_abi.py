@@ -253,6 +253,23 @@ class ErplDensity(C.Structure):
                 ("zone_inside", C.c_int64 * DENSITY_MAX_ZONES), ("sample_density", ErplRowStats)]
 
 
+# erpl_mc_impact_density_weighted
+class ErplDensityW(C.Structure):
+    _fields_ = [("count", C.c_int64), ("solid", C.c_int32), ("peak_ix", C.c_int32), ("peak_iy", C.c_int32),
+                ("reserved", C.c_int32),
+                ("mean_x", C.c_double), ("mean_y", C.c_double),
+                ("cov_xx", C.c_double), ("cov_xy", C.c_double), ("cov_yy", C.c_double),
+                ("h_xx", C.c_double), ("h_xy", C.c_double), ("h_yy", C.c_double), ("det", C.c_double),
+                ("norm", C.c_double),
+                ("lo_x", C.c_double), ("hi_x", C.c_double), ("lo_y", C.c_double), ("hi_y", C.c_double),
+                ("peak", C.c_double), ("grid_mass", C.c_double),
+                ("zone_w", C.c_int64 * DENSITY_MAX_ZONES), ("zone_a2", C.c_double * DENSITY_MAX_ZONES),
+                ("n_masked", C.c_int64), ("n_non_finite", C.c_int64), ("n_zero", C.c_int64),
+                ("sum_w", C.c_int64), ("max_w", C.c_int64), ("sum_w2", C.c_double), ("ess", C.c_double),
+                ("threshold", C.c_double * DENSITY_MAX_LEVELS), ("content_w", C.c_int64 * DENSITY_MAX_LEVELS),
+                ("f_min", C.c_double), ("f_max", C.c_double)]
+
+
 # erpl_mc_corridor_resample / erpl_mc_corridor_bands
 CORRIDOR_MAX_CHANNELS = 8
 CORRIDOR_MAX_NODES = 4096
@@ -597,7 +614,7 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_dispersion_defaults", "erpl_mc_dispersion",
            "erpl_mc_correlation_defaults", "erpl_mc_correlation",
            "erpl_mc_bootstrap_defaults", "erpl_mc_bootstrap", "erpl_mc_bootstrap_indices",
-           "erpl_mc_impact_density_defaults", "erpl_mc_impact_density",
+           "erpl_mc_impact_density_defaults", "erpl_mc_impact_density", "erpl_mc_impact_density_weighted",
            "erpl_mc_corridor_defaults", "erpl_mc_corridor_resample", "erpl_mc_corridor_bands",
            "erpl_mc_sobol_defaults", "erpl_mc_sobol",
            "erpl_mc_dependence_defaults", "erpl_mc_dependence",
@@ -707,6 +724,9 @@ def load_library(path=None):
     lib.erpl_mc_impact_density_defaults.argtypes = [C.POINTER(ErplDensitySpec)]
     lib.erpl_mc_impact_density.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ErplDensitySpec), C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.POINTER(ErplDensity), C.c_void_p, C.c_void_p]
+    lib.erpl_mc_impact_density_weighted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                    C.POINTER(ErplDensitySpec), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.POINTER(ErplDensityW), C.c_void_p, C.c_void_p]
     lib.erpl_mc_corridor_defaults.argtypes = [C.POINTER(ErplCorridorSpec)]
     lib.erpl_mc_corridor_resample.argtypes = [C.c_void_p, C.POINTER(ErplOut), C.POINTER(ErplCorridorSpec), C.c_void_p, C.c_int64,
                                               C.c_int64, C.c_void_p]

@@ -1619,6 +1619,46 @@ def reweighted_statistics(summary, factors, kinds, law, status=None, engine=None
     return finish_reweighted(out)
 
 
+def reweighted_impact(summary, factors, kinds, law, status=None, engine=None, target=None, cep_quantiles=(0.5, 0.9, 0.95),
+                      **density_kw):
+    """The impact probability map of a flown run of INDEPENDENT primitives under another input law, without a new run, in
+    three steps on the device: erpl_mc_analyze for the reason bytes (as `reweighted_statistics`); erpl_mc_reweight with
+    want_weights over the one row `extra` = the miss distance about `target` ((x, y), default the launch site at the
+    origin); erpl_mc_impact_density_weighted (TrajectoryEngine.impact_density_weighted, `density_kw` are its keywords:
+    nodes, ranges, pad, bandwidth, levels, zones, sample_density, rows) with those weights.  Returns the map's dict plus
+    'cep' ({'q', 'quantiles', 'mean', 'mean_se'}: the weighted quantiles of the miss distance), per zone 'probability' =
+    weight / sum_w with 'se' by the formula of erpl_mc_reweight's p_se and 'interval' = probability -+ 1.96 se within
+    [0, 1], 'n_samples' / 'n_outliers' of the filter, and of the reweighting: Q, n_outside, ess_expected_share and what
+    `finish_reweighted` adds - ess_share, max_weight_share, warnings.  ('ess' is the map's: over the samples that have an
+    impact point.)  Read it as `reweighted_statistics` says: trust the map as far as ess goes."""
+    import torch
+    from . import _abi
+    engine, res, why = _filter(summary, status, engine)
+    rows = density_kw.get("rows", (_abi.SUM_IMPACT_X, _abi.SUM_IMPACT_Y))
+    tx, ty = (0.0, 0.0) if target is None else (float(target[0]), float(target[1]))
+    miss = torch.hypot(summary[int(rows[0])] - tx, summary[int(rows[1])] - ty).contiguous()
+    rw = engine.reweight(factors, kinds, law, summary, mask=why, rows=[_abi.RW_ROW_EXTRA], extra=miss,
+                         quantiles=cep_quantiles, want_weights=True)
+    out = engine.impact_density_weighted(summary, rw["weights"], why, **density_kw)
+    out["n_samples"], out["n_outliers"] = int(res.n_valid), int(res.n_outliers)
+    r = rw["rows"][_abi.RW_ROW_EXTRA]
+    out["target"] = (tx, ty)
+    out["cep"] = {"q": r["q"], "quantiles": r["quantiles"], "mean": r["mean"], "mean_se": r["mean_se"]}
+    s_d = math.ldexp(float(out["sum_w"]), -out["max_w"].bit_length())   # sum_w2 and a2 are in weights scaled alike
+    for z in out["zones"]:
+        if out["sum_w"] == 0:
+            z["probability"], z["se"], z["interval"] = math.nan, math.nan, (0.0, 1.0)
+            continue
+        prob = z["weight"] / out["sum_w"]
+        z["probability"] = prob
+        z["se"] = math.sqrt(max((1.0 - 2.0 * prob) * z["a2"] + prob * prob * out["sum_w2"], 0.0)) / s_d
+        z["interval"] = (max(0.0, prob - 1.96 * z["se"]), min(1.0, prob + 1.96 * z["se"]))
+    fin = finish_reweighted(rw)
+    for k in ("Q", "n_outside", "ess_expected_share", "ess_share", "max_weight_share", "warnings"):
+        out[k] = fin[k]
+    return out
+
+
 # ---------------------------------------------------------------------------------- the casualty expectation of a footprint
 CASUALTY_COUNTS = ("landed", "lethal", "off_grid", "missing")   # rows 1..4 of per_node / per_fragment (_abi.CASUALTY_*)
 

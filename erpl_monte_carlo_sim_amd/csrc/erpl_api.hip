@@ -462,7 +462,7 @@ int erpl_mc_destroy(erpl_ctx* c) {
   for (int i = 0; i < 3 * ERPL_PROFILE_RING; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
   for (int i = 0; i < ERPL_TICKET_RING; ++i) if (c->ring_done[i]) (void)hipEventDestroy(c->ring_done[i]);
   if (c->ring_counters) (void)hipHostFree(c->ring_counters);
-  c->ana.release(); c->dist.release(); c->corr.release(); c->boot.release(); c->dens.release(); c->corridor.release(); c->sobol.release();
+  c->ana.release(); c->dist.release(); c->corr.release(); c->boot.release(); c->dens.release(); c->densw.release(); c->corridor.release(); c->sobol.release();
   c->dep.release(); c->cmp.release(); c->cmp_pop.release(); c->sur.release(); c->sur_model.release();
   (void)hipFree(c->legacy_buf);
   if (c->legacy_pin) (void)hipHostFree(c->legacy_pin);

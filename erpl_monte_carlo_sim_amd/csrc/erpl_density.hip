@@ -334,6 +334,13 @@ int erpl_launch_dens_pairs(const double* qry, int64_t queries, const double* src
   return (int)hipGetLastError();
 }
 
+int erpl_launch_dens_fold(const double* partial, int slices, int64_t queries, double norm, double* out, const uint32_t* scatter,
+                          void* stream) {
+  hipLaunchKernelGGL(erpl_dens_fold, dim3(grid_of(queries)), dim3(ERPL_ANA_BLOCK), 0, (hipStream_t)stream, partial, slices,
+                     queries, norm, out, scatter);
+  return (int)hipGetLastError();
+}
+
 int erpl_launch_dens_peak(ErplDensWork* work, const double* density, int64_t nodes, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int nb = grid_of(nodes);

@@ -66,6 +66,14 @@ struct DensHost {
   ErplDensIn in;
 };
 
+// erpl_mc_impact_density_weighted: the same mirror of ErplDensWWork
+struct DensWHost {
+  ErplDensWMoments mom;
+  ErplDensWOut out;
+  ErplDensOut peak;
+  ErplDensIn in;
+};
+
 // erpl_mc_sobol: pinned copies of what its launches hand back - per row the population counters and the extremes of the
 // blocks A and B (erpl_launch_corr_population), the sums of the estimates and the summary over the replicates
 struct SobolHost {
@@ -213,6 +221,8 @@ struct erpl_ctx {
   ErplStatUnit<ErplCorrWork, ErplCorrOut> corr;
   ErplStatUnit<void, BootHost> boot;
   ErplStatUnit<ErplDensWork, DensHost> dens;
+  // erpl_mc_impact_density_weighted: the pieces of erpl_densw_layout in the buffer
+  ErplStatUnit<ErplDensWWork, DensWHost> densw;
   // erpl_mc_corridor_bands: the row records its kernel hands back, nothing else (no fixed block, no pinned mirror)
   ErplStatUnit<void, char> corridor;
   // erpl_mc_sobol: the partial sums of its estimates and the row records of its summary in the fixed block, the pieces of

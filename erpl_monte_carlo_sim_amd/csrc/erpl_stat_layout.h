@@ -1,5 +1,5 @@
 // erpl_stat_layout.h — how erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density, erpl_mc_sobol,
-// erpl_mc_dependence, erpl_mc_compare, erpl_mc_surrogate and erpl_mc_reweight cut the device buffer each of them grows into pieces: pure functions
+// erpl_mc_dependence, erpl_mc_compare, erpl_mc_surrogate, erpl_mc_reweight and erpl_mc_impact_density_weighted cut the device buffer each of them grows into pieces: pure functions
 // of the call's sizes (no HIP; the scratch size of the rocPRIM calls comes in as a number), so that tests/test_stat_layout.py,
 // tests/test_dependence_layout.py, tests/test_compare_layout.py and tests/test_surrogate_abi.py check every offset on the CPU, through
 // erpl_stat_layout_table, before a kernel writes through one.  Every piece starts at a multiple of 256 bytes; `need` is the
@@ -83,6 +83,30 @@ inline ErplDensLayout erpl_dens_layout(int64_t n, int64_t nodes, bool want_sampl
   l.temp_bytes = erpl_scratch_piece(temp_bytes);
   l.temp = c.take(l.temp_bytes);
   l.pts = c.take(16 * un);
+  l.nodes = c.take(16 * un_nodes);
+  l.dens = c.take(8 * un_nodes);
+  l.row = c.take(want_samples && !caller_keeps_row ? 8 * un : 0);
+  const size_t queries = want_samples && un > un_nodes ? un : un_nodes;
+  l.part = c.take(8 * ((size_t)ERPL_DENS_TARGET_BLOCKS * ERPL_DENS_TILE + queries));
+  l.need = c.end;
+  return l;
+}
+
+// erpl_mc_impact_density_weighted: the pieces of erpl_mc_impact_density with the scaled weights of the counted points behind
+// the points: [pop n bytes][src n u32][count][scratch of the select][points n (x, y), then (u, v)][ws n doubles][nodes (u, v)]
+// [node densities][the sample row, if there is one and the caller does not keep it][partial sums as in erpl_dens_layout]
+struct ErplDensWLayout { size_t pop, src, count, temp, pts, ws, nodes, dens, row, part, temp_bytes, need; };
+inline ErplDensWLayout erpl_densw_layout(int64_t n, int64_t nodes, bool want_samples, bool caller_keeps_row, size_t temp_bytes) {
+  const size_t un = (size_t)n, un_nodes = (size_t)nodes;
+  ErplCarve c;
+  ErplDensWLayout l = {};
+  l.pop = c.take(un);
+  l.src = c.take(4 * un);
+  l.count = c.take(8);
+  l.temp_bytes = erpl_scratch_piece(temp_bytes);
+  l.temp = c.take(l.temp_bytes);
+  l.pts = c.take(16 * un);
+  l.ws = c.take(8 * un);
   l.nodes = c.take(16 * un_nodes);
   l.dens = c.take(8 * un_nodes);
   l.row = c.take(want_samples && !caller_keeps_row ? 8 * un : 0);

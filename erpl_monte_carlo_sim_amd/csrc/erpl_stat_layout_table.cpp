@@ -19,6 +19,8 @@
 //                                                                           first length that has them, erpl_sur_max_slices(hi, P)
 //   surslice <len> <P>                                                   -> slices slice_len of one chunk
 //   rw <n> <caller_keeps_logw> <caller_keeps_weights> <work_bytes>       -> work logw weights need
+//   wdens <n> <nodes> <want_samples> <caller_keeps_row> <temp_bytes>     -> pop src count temp pts ws nodes dens row part temp_bytes
+//                                                                           need
 #include <stdio.h>
 
 #include <initializer_list>
@@ -96,6 +98,10 @@ int main() {
     } else if (sscanf(line, "rw %lld %d %d %zu", &n, &a, &b, &temp) == 4) {
       const ErplRwLayout l = erpl_rw_layout(n, a != 0, b != 0, temp);
       for (size_t v : {l.work, l.logw, l.weights}) put(v);
+      put(l.need, "\n");
+    } else if (sscanf(line, "wdens %lld %lld %d %d %zu", &n, &nodes, &a, &b, &temp) == 5) {
+      const ErplDensWLayout l = erpl_densw_layout(n, nodes, a != 0, b != 0, temp);
+      for (size_t v : {l.pop, l.src, l.count, l.temp, l.pts, l.ws, l.nodes, l.dens, l.row, l.part, l.temp_bytes}) put(v);
       put(l.need, "\n");
     } else {
       fprintf(stderr, "bad request: %s", line);

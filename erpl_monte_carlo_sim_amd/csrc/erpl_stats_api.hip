@@ -1,8 +1,9 @@
 // erpl_stats_api.hip — host halves of the analysis entry points of the C ABI (include/erpl_mc.h): erpl_mc_analyze,
 // erpl_mc_histogram, erpl_mc_histogram_xy, erpl_mc_dispersion, erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density,
+// erpl_mc_impact_density_weighted,
 // erpl_mc_corridor_resample, erpl_mc_corridor_bands, erpl_mc_sobol, erpl_mc_dependence, erpl_mc_compare and their defaults.
 // Argument checks, workspace, launches (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip, erpl_bootstrap.hip,
-// erpl_density.hip, erpl_corridor.hip, erpl_sobol.hip, erpl_dependence.hip, erpl_compare.hip)
+// erpl_density.hip, erpl_density_w.hip, erpl_corridor.hip, erpl_sobol.hip, erpl_dependence.hip, erpl_compare.hip)
 // and what the host finishes in double precision.  The refusals come in one order
 // everywhere - spec fields, n, pointers, context (erpl_mc_bootstrap: the order its header comment lists) - and need no
 // device; tests/golden/stats_refusals.json pins their texts.  What the entry points share comes first: the pieces of the
@@ -17,6 +18,7 @@
 
 #include "erpl_host.h"
 #include "erpl_philox.h"
+#include "erpl_reweight.h"
 #include "erpl_tally.h"
 
 namespace {
@@ -952,6 +954,152 @@ int erpl_mc_impact_density(erpl_ctx* c, const double* summary, const uint8_t* ma
   result->peak_iy = solid ? (int32_t)((int64_t)h.out.peak_at % ny) : -1;
   const bool described = solid && want_samples;
   finish_row_stats(described ? c->ana.host->row[0] : ErplAnaRow(), q, spec->n_levels, described, result->sample_density);
+  return ERPL_OK;
+}
+
+// The weighted map: the host half of erpl_mc_impact_density above with the passes of erpl_density_w.hip where a weight enters
+// (population, moments, zones, pairs, regions) and the launchers of erpl_density.hip where none does (whiten, nodes, fold, peak,
+// fill_nan, on the ErplDensWork inside the block).
+int erpl_mc_impact_density_weighted(erpl_ctx* c, const double* summary, const uint8_t* mask, const int64_t* weights, int64_t n,
+                                    const erpl_density_spec* spec, double* grid_x, double* grid_y, double* density,
+                                    erpl_density_w* result, double* sample_density, void* stream) {
+  NEED(spec);
+  ERPL_TRY(check_density_spec(spec));
+  ERPL_TRY(check_n(n, (1ll << 31) - 1, ": the select carries 31-bit sample indices"));
+  NEED(summary); NEED(grid_x); NEED(grid_y); NEED(density); NEED(weights); NEED(result); NEED_AS(c, "ctx");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int nx = spec->nodes_x, ny = spec->nodes_y;
+  const size_t nodes = (size_t)nx * (size_t)ny;
+  const bool want_samples = spec->n_levels > 0 || sample_density;
+
+  size_t temp_bytes = 0;
+  LAUNCH_TRY(erpl_boot_temp_bytes(n, &temp_bytes), "select sizing failed");
+  const ErplDensWLayout at = erpl_densw_layout(n, (int64_t)nodes, want_samples, sample_density != nullptr, temp_bytes);
+  ERPL_TRY(c->densw.first_use());
+  ERPL_TRY(c->densw.grow(at.need));
+  char* buf = c->densw.buf;
+  ErplDensWWork* work = c->densw.work;
+  DensWHost& h = *c->densw.host;
+  uint32_t* src = (uint32_t*)(buf + at.src);
+  double* pts = (double*)(buf + at.pts);
+  double* ws = (double*)(buf + at.ws);
+  double* nodes_uv = (double*)(buf + at.nodes);
+  double* dens = (double*)(buf + at.dens);
+  double* row = sample_density ? sample_density : (double*)(buf + at.row);
+  double* partial = (double*)(buf + at.part);
+
+  ErplDensWArgs a;
+  memset(&a, 0, sizeof(a));
+  a.summary = summary; a.mask = mask; a.weights = weights; a.work = work; a.pop = (uint8_t*)(buf + at.pop); a.n = n;
+  a.row_x = spec->row_x; a.row_y = spec->row_y; a.n_zones = spec->n_zones; a.Q = erpl_rw_q(n);
+  ErplBootPrep p;   // the select of erpl_mc_bootstrap: pop -> src and the count, in sample order
+  memset(&p, 0, sizeof(p));
+  p.pop = a.pop; p.src = src; p.count = (unsigned long long*)(buf + at.count); p.temp = buf + at.temp;
+  p.temp_bytes = at.temp_bytes; p.n = n;
+  KERNEL_TRY(erpl_launch_densw_population(a, stream));
+  LAUNCH_TRY(erpl_launch_boot_compact(p, stream), "select failed");
+  KERNEL_TRY(erpl_launch_densw_moments(a, src, p.count, pts, ws, stream));
+  HIP_TRY(hipMemcpyAsync(&h.mom, &work->mom, sizeof(ErplDensWMoments), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (h.mom.first_bad < (double)n)
+    return erpl_fail(ERPL_ERR_INVALID, "weights[%lld] is outside 0 .. 2^%d", (long long)h.mom.first_bad, a.Q);
+
+  // what the host settles in double: the covariance, H, whether the estimate is solid, the map, the ranges and the nodes
+  const double nan = NAN;
+  const int64_t m = (int64_t)h.mom.count;
+  memset(result, 0, sizeof(*result));
+  const double s_d = h.mom.s_d, dof = s_d - h.mom.sum_w2 / s_d;   // 0 for one point: the covariance is NaN there
+  const bool any = finish_cloud(result, h.mom.count, h.mom.mean_x, h.mom.mean_y, h.mom.sxx / dof, h.mom.sxy / dof, h.mom.syy / dof);
+  result->n_masked = (int64_t)h.mom.n_masked; result->n_non_finite = (int64_t)h.mom.n_non_finite;
+  result->n_zero = (int64_t)h.mom.n_zero;
+  result->sum_w = (int64_t)h.mom.sum_w; result->max_w = (int64_t)h.mom.max_w;
+  result->sum_w2 = any ? h.mom.sum_w2 : nan;
+  result->ess = any ? s_d * s_d / h.mom.sum_w2 : nan;
+  double hxx = spec->h_xx, hxy = spec->h_xy, hyy = spec->h_yy;
+  if (spec->bandwidth == ERPL_BW_SCOTT) {
+    const double factor = spec->bw_scale * pow(result->ess, -1.0 / 6.0), f2 = factor * factor;
+    hxx = f2 * result->cov_xx; hxy = f2 * result->cov_xy; hyy = f2 * result->cov_yy;
+  }
+  const double det = hxx * hyy - hxy * hxy;
+  const bool solid = any && std::isfinite(hxx) && std::isfinite(hxy) && std::isfinite(hyy) && std::isfinite(det) &&
+                     hxx > 0.0 && hyy > 0.0 && det > 1e-12 * hxx * hyy && !(spec->bandwidth == ERPL_BW_SCOTT && m < 3);
+  result->solid = solid ? 1 : 0;
+  result->h_xx = any ? hxx : nan; result->h_xy = any ? hxy : nan; result->h_yy = any ? hyy : nan;
+  result->det = any ? det : nan;
+  const double norm = solid ? 1.0 / (s_d * (2.0 * M_PI) * sqrt(det)) : nan;
+  result->norm = norm;
+  const bool auto_x = std::isnan(spec->lo_x), auto_y = std::isnan(spec->lo_y);
+  const double pad_x = solid ? spec->pad * sqrt(hxx) : 0.0, pad_y = solid ? spec->pad * sqrt(hyy) : 0.0;
+  double lo_x = spec->lo_x, hi_x = spec->hi_x, lo_y = spec->lo_y, hi_y = spec->hi_y;
+  if (!settle_range(auto_x, h.mom.min_x - pad_x, h.mom.max_x + pad_x, &lo_x, &hi_x))
+    return erpl_fail(ERPL_ERR_INVALID, "spec->row_x = %d: the range of the counted values, %g to %g, is wider than a double holds",
+                     spec->row_x, lo_x, hi_x);
+  if (!settle_range(auto_y, h.mom.min_y - pad_y, h.mom.max_y + pad_y, &lo_y, &hi_y))
+    return erpl_fail(ERPL_ERR_INVALID, "spec->row_y = %d: the range of the counted values, %g to %g, is wider than a double holds",
+                     spec->row_y, lo_y, hi_y);
+  result->lo_x = lo_x; result->hi_x = hi_x; result->lo_y = lo_y; result->hi_y = hi_y;
+  memset(&h.in, 0, sizeof(h.in));
+  fill_edges(lo_x, hi_x, nx - 1, h.in.grid_x);   // np.linspace(lo, hi, nodes)
+  fill_edges(lo_y, hi_y, ny - 1, h.in.grid_y);
+  const int n_vert = spec->n_zones > 0 ? spec->zone_first[spec->n_zones] : 0;
+  memcpy(h.in.zone_x, spec->zone_x, (size_t)n_vert * sizeof(double));
+  memcpy(h.in.zone_y, spec->zone_y, (size_t)n_vert * sizeof(double));
+  for (int z = 0; z <= spec->n_zones; ++z) h.in.zone_first[z] = spec->zone_first[z];
+  HIP_TRY(hipMemcpyAsync(&work->d.in, &h.in, sizeof(ErplDensIn), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(&work->d.out, 0, sizeof(ErplDensOut), st));
+  HIP_TRY(hipMemsetAsync(&work->out, 0, sizeof(ErplDensWOut), st));
+  KERNEL_TRY(erpl_launch_densw_zones(a, pts, ws, m, stream));   // before the points are whitened
+
+  int64_t per_slice = 0;
+  if (solid) {
+    // H = C C': u = dx / c11, v = (dy - c21 u) / c22
+    const double c11 = sqrt(hxx), c21 = hxy / c11, c22 = sqrt(hyy - c21 * c21);
+    ErplDensMap map;
+    map.mean_x = h.mom.mean_x; map.mean_y = h.mom.mean_y;
+    map.w11 = 1.0 / c11; map.w22 = 1.0 / c22; map.w21 = -c21 * map.w11 * map.w22;
+    KERNEL_TRY(erpl_launch_dens_whiten(pts, m, map, stream));
+    KERNEL_TRY(erpl_launch_dens_nodes(&work->d, nx, ny, map, nodes_uv, stream));
+    KERNEL_TRY(erpl_launch_densw_pairs(nodes_uv, (int64_t)nodes, pts, ws, m, partial, stream));
+    KERNEL_TRY(erpl_launch_dens_fold(partial, erpl_dens_slices(m, (int64_t)nodes, &per_slice), (int64_t)nodes, norm, dens, nullptr, stream));
+    KERNEL_TRY(erpl_launch_dens_peak(&work->d, dens, (int64_t)nodes, stream));
+  }
+  if (want_samples) {
+    KERNEL_TRY(erpl_launch_dens_fill_nan(row, n, stream));
+    if (solid) {
+      KERNEL_TRY(erpl_launch_densw_pairs(pts, m, pts, ws, m, partial, stream));
+      KERNEL_TRY(erpl_launch_dens_fold(partial, erpl_dens_slices(m, m, &per_slice), m, norm, row, src, stream));
+      // the region of content level[k] is bounded by the density below which 1 - level[k] of the WEIGHT lies
+      unsigned long long rank[ERPL_DENSITY_MAX_LEVELS] = {0};
+      for (int k = 0; k < spec->n_levels; ++k) rank[k] = erpl_rw_target(1.0 - spec->level[k], h.mom.sum_w) - 1ull;
+      KERNEL_TRY(erpl_launch_densw_regions(a, row, rank, spec->n_levels, stream));
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(&h.peak, &work->d.out, sizeof(ErplDensOut), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&h.out, &work->out, sizeof(ErplDensWOut), hipMemcpyDeviceToHost, st));
+  if (solid) HIP_TRY(hipMemcpyAsync(density, dens, 8 * nodes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+
+  memcpy(grid_x, h.in.grid_x, (size_t)nx * sizeof(double));
+  memcpy(grid_y, h.in.grid_y, (size_t)ny * sizeof(double));
+  if (!solid) for (size_t k = 0; k < nodes; ++k) density[k] = nan;
+  for (int z = 0; z < ERPL_DENSITY_MAX_ZONES; ++z) {
+    result->zone_w[z] = z < spec->n_zones ? (int64_t)h.out.zone_w[z] : 0;
+    result->zone_a2[z] = z < spec->n_zones ? h.out.zone_a2[z] : 0.0;
+  }
+  const double cell = ((hi_x - lo_x) / (double)(nx - 1)) * ((hi_y - lo_y) / (double)(ny - 1));
+  result->peak = solid ? h.peak.peak : nan;
+  result->grid_mass = solid ? h.peak.sum * cell : nan;
+  result->peak_ix = solid ? (int32_t)((int64_t)h.peak.peak_at / ny) : -1;
+  result->peak_iy = solid ? (int32_t)((int64_t)h.peak.peak_at % ny) : -1;
+  const bool described = solid && want_samples;
+  for (int k = 0; k < ERPL_DENSITY_MAX_LEVELS; ++k) {
+    const bool has = described && k < spec->n_levels;
+    result->threshold[k] = has ? double_of_key(h.out.key[k]) : nan;
+    result->content_w[k] = has ? (int64_t)h.out.content_w[k] : 0;
+  }
+  result->f_min = described ? h.out.f_min : nan;
+  result->f_max = described ? h.out.f_max : nan;
   return ERPL_OK;
 }
 

@@ -468,6 +468,71 @@ int erpl_launch_dens_pairs(const double* qry, int64_t queries, const double* src
                            double* out, const uint32_t* scatter, void* stream);
 int erpl_launch_dens_peak(ErplDensWork* work, const double* density, int64_t nodes, void* stream);   // -> work->out.sum / peak / peak_at
 int erpl_launch_dens_fill_nan(double* row, int64_t n, void* stream);
+// the fold of erpl_launch_dens_pairs on its own: the weighted pair kernel (erpl_density_w.hip) leaves its slices to it
+int erpl_launch_dens_fold(const double* partial, int slices, int64_t queries, double norm, double* out, const uint32_t* scatter,
+                          void* stream);
+}
+
+// ---- erpl_mc_impact_density_weighted (erpl_density_w.hip) ----
+// The passes of erpl_density.hip with an integer weight per sample.  Whiten, nodes, fold, peak and fill_nan are THE launchers
+// above, run on `d`; the population, the moments, the zones, the pair kernel and the selection are the unit's own.  The pair
+// kernel has the shape of erpl_dens_pairs, with (u, v, w) per source in its LDS tile (24 KB).
+struct ErplDensWMoments {           // what the population and the moment passes hand back
+  unsigned long long count, n_masked, n_non_finite, n_zero, sum_w, max_w;
+  double first_bad;                       // the lowest column whose weight is outside 0 .. 2^Q (+inf: none)
+  int32_t K, reserved;                    // the bit length of max_w: w = W 2^-K
+  double s_d, sum_w2;                     // sum_w 2^-K, sum w w
+  double mean_x, mean_y, sxx, sxy, syy;   // sums of w dx dx, w dx dy, w dy dy about the mean
+  double min_x, max_x, min_y, max_y;      // +inf / -inf: nothing counted
+};
+struct ErplDensWOut {               // what the zone pass and the selection hand back
+  unsigned long long zone_w[ERPL_DENSITY_MAX_ZONES];
+  double zone_a2[ERPL_DENSITY_MAX_ZONES];
+  unsigned long long key[ERPL_DENSITY_MAX_LEVELS];        // key_of_signed of the thresholds
+  unsigned long long content_w[ERPL_DENSITY_MAX_LEVELS];
+  double f_min, f_max;
+};
+struct ErplDensWSelect {            // the state of the weighted radix selection, one target per level
+  unsigned long long prefix[ERPL_DENSITY_MAX_LEVELS], rank[ERPL_DENSITY_MAX_LEVELS];
+  int32_t leader[ERPL_DENSITY_MAX_LEVELS];
+};
+struct ErplDensWWork {
+  ErplDensWork d;                   // the block of the launchers of erpl_density.hip: in, out.sum / peak / peak_at, psum, pext
+  unsigned long long pcnt[ERPL_ANA_MAX_BLOCKS][4];        // population: masked, non-finite, zero, counted per workgroup
+  unsigned long long psum_w[ERPL_ANA_MAX_BLOCKS];
+  double pmax_w[ERPL_ANA_MAX_BLOCKS], pbad[ERPL_ANA_MAX_BLOCKS];
+  double za2[ERPL_ANA_MAX_BLOCKS][ERPL_DENSITY_MAX_ZONES];                  // zone sums of w w per workgroup (zone_w: d.zpart)
+  unsigned long long cpart[ERPL_ANA_MAX_BLOCKS][ERPL_DENSITY_MAX_LEVELS];   // contents per workgroup
+  unsigned long long hist[ERPL_DENSITY_MAX_LEVELS][ERPL_ANA_BINS];          // 64-bit digit histograms of the selection
+  ErplDensWSelect sel;
+  ErplDensWMoments mom;
+  ErplDensWOut out;
+};
+struct ErplDensWArgs {
+  const double* summary;   // [ERPL_SUMMARY_DIM][n]
+  const uint8_t* mask;     // [n] or NULL
+  const int64_t* weights;  // [n]
+  ErplDensWWork* work;
+  uint8_t* pop;            // [n] workspace: 0 = counted
+  int64_t n;
+  int32_t row_x, row_y, n_zones, Q;   // Q: a weight is admitted in 0 .. 2^Q
+};
+extern "C++" {
+// Each enqueues its passes on `stream` and returns a hipError_t (0 = launched).
+int erpl_launch_densw_population(const ErplDensWArgs& a, void* stream);   // -> a.pop, work->mom (counts, sum_w, max_w, K, s_d, first_bad)
+// src[d] = the sample of dense member d < *count: the counted points into xy[*count][2], their scaled weights into ws[*count],
+// and the weighted moments -> work->mom
+int erpl_launch_densw_moments(const ErplDensWArgs& a, const uint32_t* src, const unsigned long long* count, double* xy, double* ws,
+                              void* stream);
+// over the dense points BEFORE they are whitened: work->d.in -> work->out.zone_w / zone_a2
+int erpl_launch_densw_zones(const ErplDensWArgs& a, const double* xy, const double* ws, int64_t m, void* stream);
+// THE weighted pair kernel: partial[slice][q] = sum over the slice's sources of w exp(-|qry[q] - src[i]|^2 / 2), in index order;
+// the slices are erpl_dens_slices(m, queries) and erpl_launch_dens_fold adds them
+int erpl_launch_densw_pairs(const double* qry, int64_t queries, const double* src, const double* ws, int64_t m, double* partial,
+                            void* stream);
+// the weighted selection over row[n] (the f_j; a.pop, a.weights) for n_levels targets, rank[k] = T_k - 1 (0-based, from the
+// host: it knows sum_w), then the contents and the extremes -> work->out.key / content_w / f_min / f_max
+int erpl_launch_densw_regions(const ErplDensWArgs& a, const double* row, const unsigned long long* rank, int n_levels, void* stream);
 }
 
 // ---- erpl_mc_corridor_resample / erpl_mc_corridor_bands (erpl_corridor.hip) ----

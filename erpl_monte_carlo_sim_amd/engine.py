@@ -728,21 +728,9 @@ class TrajectoryEngine:
             out["miss_distance"] = r
         return out
 
-    def impact_density(self, summary, mask=None, rows=(_abi.SUM_IMPACT_X, _abi.SUM_IMPACT_Y), nodes=(128, 128), ranges=None,
-                       pad=3.0, bandwidth=None, levels=(0.5, 0.9, 0.99), zones=None, sample_density=False):
-        """The impact probability map (erpl_mc_impact_density): a Gaussian kernel density estimate of the (rows[0], rows[1])
-        cloud over the samples with mask byte 0 and both values finite, evaluated at the nodes[0] x nodes[1] nodes of a grid
-        (2..512 per axis).  ranges: None or ((lo_x, hi_x) | None, (lo_y, hi_y) | None), None = min / max of the counted
-        values -+ `pad` bandwidth standard deviations.  bandwidth: None = Scott's rule (scipy.stats.gaussian_kde's default),
-        a float = Scott's rule times that factor, a 2 x 2 matrix = H as given.  levels: contents of the highest-density
-        regions; zones: polygons, each an array of (x, y) vertices.  Returns a dict: count, solid, mean, covariance (divisor
-        count - 1), bandwidth_matrix, det, norm, ranges, grid_x, grid_y, density ([nodes_x, nodes_y], x-major), peak,
-        peak_node, grid_mass, levels, thresholds (density >= thresholds[k] is the region of content levels[k]),
-        sample_density_stats (count / mean / std / min / max / q / quantiles / order_lo / order_hi of the density at the
-        samples), zones ([{'vertices', 'inside'}]).  sample_density=True adds 'sample_density', the float64 [n] device
-        tensor of the density at every sample (NaN where it is not counted); with no levels and without it the pass over
-        all pairs of samples is skipped."""
-        n, mask_p = self._summary_and_mask(summary, mask)
+    def _density_spec(self, rows, nodes, ranges, pad, bandwidth, levels, zones):
+        """The erpl_density_spec of impact_density / impact_density_weighted from their keywords, and the host arrays of a
+        call: (spec, levels, zones, nx, ny, grid_x, grid_y, density)."""
         levels = self._fractions(levels, _abi.DENSITY_MAX_LEVELS, "levels")
         zones = [np.asarray(z, dtype=np.float64).reshape(-1, 2) for z in (zones or [])]
         if len(zones) > _abi.DENSITY_MAX_ZONES:
@@ -775,6 +763,24 @@ class TrajectoryEngine:
         nx, ny = max(2, min(spec.nodes_x, cap)), max(2, min(spec.nodes_y, cap))   # out-of-range nodes are refused below
         gx, gy = np.zeros(cap, dtype=np.float64), np.zeros(cap, dtype=np.float64)
         dens = np.zeros(nx * ny, dtype=np.float64)
+        return spec, levels, zones, nx, ny, gx, gy, dens
+
+    def impact_density(self, summary, mask=None, rows=(_abi.SUM_IMPACT_X, _abi.SUM_IMPACT_Y), nodes=(128, 128), ranges=None,
+                       pad=3.0, bandwidth=None, levels=(0.5, 0.9, 0.99), zones=None, sample_density=False):
+        """The impact probability map (erpl_mc_impact_density): a Gaussian kernel density estimate of the (rows[0], rows[1])
+        cloud over the samples with mask byte 0 and both values finite, evaluated at the nodes[0] x nodes[1] nodes of a grid
+        (2..512 per axis).  ranges: None or ((lo_x, hi_x) | None, (lo_y, hi_y) | None), None = min / max of the counted
+        values -+ `pad` bandwidth standard deviations.  bandwidth: None = Scott's rule (scipy.stats.gaussian_kde's default),
+        a float = Scott's rule times that factor, a 2 x 2 matrix = H as given.  levels: contents of the highest-density
+        regions; zones: polygons, each an array of (x, y) vertices.  Returns a dict: count, solid, mean, covariance (divisor
+        count - 1), bandwidth_matrix, det, norm, ranges, grid_x, grid_y, density ([nodes_x, nodes_y], x-major), peak,
+        peak_node, grid_mass, levels, thresholds (density >= thresholds[k] is the region of content levels[k]),
+        sample_density_stats (count / mean / std / min / max / q / quantiles / order_lo / order_hi of the density at the
+        samples), zones ([{'vertices', 'inside'}]).  sample_density=True adds 'sample_density', the float64 [n] device
+        tensor of the density at every sample (NaN where it is not counted); with no levels and without it the pass over
+        all pairs of samples is skipped."""
+        n, mask_p = self._summary_and_mask(summary, mask)
+        spec, levels, zones, nx, ny, gx, gy, dens = self._density_spec(rows, nodes, ranges, pad, bandwidth, levels, zones)
         row = torch.empty((n,), dtype=torch.float64, device=self.device) if sample_density else None
         res = _abi.ErplDensity()
         st = torch.cuda.current_stream(self.device)
@@ -792,6 +798,46 @@ class TrajectoryEngine:
                "levels": levels, "thresholds": list(sd.quantile[:nl]),
                "sample_density_stats": self._row_stats_dict(sd, [1.0 - p for p in levels]),
                "zones": [{"vertices": poly, "inside": int(res.zone_inside[z])} for z, poly in enumerate(zones)]}
+        if sample_density:
+            out["sample_density"] = row
+        return out
+
+    def impact_density_weighted(self, summary, weights, mask=None, rows=(_abi.SUM_IMPACT_X, _abi.SUM_IMPACT_Y), nodes=(128, 128),
+                                ranges=None, pad=3.0, bandwidth=None, levels=(0.5, 0.9, 0.99), zones=None, sample_density=False):
+        """The impact probability map under weights (erpl_mc_impact_density_weighted): `impact_density` of a flown run under
+        another law.  weights: the int64 [n] device tensor TrajectoryEngine.reweight(want_weights=True) returns, 0 <= W <=
+        2^Q; a sample counts iff its mask byte is 0, both values are finite and W > 0.  The keywords are those of
+        `impact_density`; bandwidth None / a float is Scott's rule on the effective sample size (scipy's `neff`).  Returns a
+        dict: count, n_masked, n_non_finite, n_zero, sum_w, max_w (Python ints), sum_w2 (in weights scaled by 2^-bit_length(
+        max_w)), ess, solid, mean, covariance (np.cov(aweights=)), bandwidth_matrix, det, norm, ranges, grid_x, grid_y,
+        density, peak, peak_node, grid_mass, levels, thresholds (np.quantile(f, 1 - level, weights=, method="inverted_cdf")
+        of the density at the samples), content_w (the weight at or above each threshold), f_min, f_max, zones ([{'vertices',
+        'weight', 'a2'}]: the exact weight inside and the sum of the squared scaled weights inside).  sample_density=True
+        adds 'sample_density', the float64 [n] device tensor (NaN where a sample is not counted)."""
+        n, mask_p = self._summary_and_mask(summary, mask)
+        if not (torch.is_tensor(weights) and weights.dtype == torch.int64 and weights.device == summary.device
+                and tuple(weights.shape) == (n,) and weights.is_contiguous()):
+            raise ValueError(f"weights must be a contiguous int64 [{n}] tensor on the summary's device")
+        spec, levels, zones, nx, ny, gx, gy, dens = self._density_spec(rows, nodes, ranges, pad, bandwidth, levels, zones)
+        row = torch.empty((n,), dtype=torch.float64, device=self.device) if sample_density else None
+        res = _abi.ErplDensityW()
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_impact_density_weighted", C.c_void_p(summary.data_ptr()), mask_p, C.c_void_p(weights.data_ptr()), n,
+                   C.byref(spec), C.c_void_p(gx.ctypes.data), C.c_void_p(gy.ctypes.data), C.c_void_p(dens.ctypes.data),
+                   C.byref(res), C.c_void_p(row.data_ptr()) if sample_density else None, C.c_void_p(st.cuda_stream))
+        nl = len(levels)
+        out = {k: int(getattr(res, k)) for k in ("count", "n_masked", "n_non_finite", "n_zero", "sum_w", "max_w")}
+        out.update({"sum_w2": res.sum_w2, "ess": res.ess, "solid": bool(res.solid), "rows": (spec.row_x, spec.row_y),
+                    "mean": [res.mean_x, res.mean_y],
+                    "covariance": [[res.cov_xx, res.cov_xy], [res.cov_xy, res.cov_yy]],
+                    "bandwidth_matrix": [[res.h_xx, res.h_xy], [res.h_xy, res.h_yy]], "det": res.det, "norm": res.norm,
+                    "ranges": ((res.lo_x, res.hi_x), (res.lo_y, res.hi_y)),
+                    "grid_x": gx[:nx].copy(), "grid_y": gy[:ny].copy(), "density": dens.reshape(nx, ny),
+                    "peak": res.peak, "peak_node": (int(res.peak_ix), int(res.peak_iy)), "grid_mass": res.grid_mass,
+                    "levels": levels, "thresholds": list(res.threshold[:nl]),
+                    "content_w": [int(v) for v in res.content_w[:nl]], "f_min": res.f_min, "f_max": res.f_max,
+                    "zones": [{"vertices": poly, "weight": int(res.zone_w[z]), "a2": res.zone_a2[z]}
+                              for z, poly in enumerate(zones)]})
         if sample_density:
             out["sample_density"] = row
         return out

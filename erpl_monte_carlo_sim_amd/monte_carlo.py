@@ -1252,19 +1252,10 @@ class MonteCarloAnalyzer:
         out["factors"], out["primitive_rows"] = factors, prim
         return out
 
-    def reweight(self, analysis, uncertainty=None, motor=None, shift=None, rows=None, thresholds=None,
-                 quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), planar=False):
-        """What a run flown with `run_monte_carlo_device(design=...)` says under ANOTHER input law (no reference counterpart,
-        no extra flights): `analysis.reweighted_statistics` - per row mean +- se, std, quantiles and exceedance
-        probabilities +- se, with ess, ess_share, ess_expected_share, max_weight_share and warnings - for the target
-        `uncertainty` table (entries on top of the flown `uncertainty_params`), a target `motor` (its thrust_uncertainty /
-        mass_flow_uncertainty against the flown motor's) and `shift` (a mean in flown sigmas per primitive), through
-        `sampling.law_change`.  Only the changed primitive rows are regenerated, from analysis["design"] through
-        `TrajectoryEngine.design(first_row=...)` (`.qmc` for design='qmc'): the bits the run flew.  planar: the run was flown
-        with planar=True, the rows Set P zeroes are left out.  ValueError for a run without `design`: under the reference's
-        joint law the inputs are not independent (one normal is the thrust multiplier, position_x and the first turbulence
-        innovation at once), and the density ratio is not a product of row factors."""
-        from . import analysis as ana, sampling
+    def _law_change_factors(self, analysis, uncertainty, motor, shift, planar):
+        """What `reweight` and `reweighted_impact` share: the changed primitive rows of the target law (sampling.law_change)
+        regenerated from analysis["design"] - (engine, summary, factors, kinds, law, primitive rows, change)."""
+        from . import sampling
         from .flatten import motor_kind
         if "design" not in analysis:
             raise ValueError("reweight needs a run flown with run_monte_carlo_device(design=...): the inputs of the joint law are not "
@@ -1291,10 +1282,46 @@ class MonteCarloAnalyzer:
                 eng.qmc([kinds[i]], n, d["seed"], dims=[qdims[r]], block=d["block"], first_row=r, out=factors[i:i + 1])
             else:
                 eng.design([kinds[i]], n, d["seed"], kind=d["kind"], block=d["block"], first_row=r, out=factors[i:i + 1])
+        return eng, summ, factors, kinds, law, prim, change
+
+    def reweight(self, analysis, uncertainty=None, motor=None, shift=None, rows=None, thresholds=None,
+                 quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), planar=False):
+        """What a run flown with `run_monte_carlo_device(design=...)` says under ANOTHER input law (no reference counterpart,
+        no extra flights): `analysis.reweighted_statistics` - per row mean +- se, std, quantiles and exceedance
+        probabilities +- se, with ess, ess_share, ess_expected_share, max_weight_share and warnings - for the target
+        `uncertainty` table (entries on top of the flown `uncertainty_params`), a target `motor` (its thrust_uncertainty /
+        mass_flow_uncertainty against the flown motor's) and `shift` (a mean in flown sigmas per primitive), through
+        `sampling.law_change`.  Only the changed primitive rows are regenerated, from analysis["design"] through
+        `TrajectoryEngine.design(first_row=...)` (`.qmc` for design='qmc'): the bits the run flew.  planar: the run was flown
+        with planar=True, the rows Set P zeroes are left out.  ValueError for a run without `design`: under the reference's
+        joint law the inputs are not independent (one normal is the thrust multiplier, position_x and the first turbulence
+        innovation at once), and the density ratio is not a product of row factors."""
+        from . import analysis as ana
+        eng, summ, factors, kinds, law, prim, change = self._law_change_factors(analysis, uncertainty, motor, shift, planar)
         out = ana.reweighted_statistics(summ, factors, kinds, law, status=analysis.get("status"), engine=eng, rows=rows,
                                         thresholds=thresholds, quantiles=quantiles)
         out["primitive_rows"], out["law"] = prim, change
         return out
+
+    def reweighted_impact(self, analysis, uncertainty=None, motor=None, shift=None, zones=None, target=None,
+                          cep_quantiles=(0.5, 0.9, 0.95), planar=False, **density_kw):
+        """Where it comes down under ANOTHER input law (no reference counterpart, no extra flights):
+        `analysis.reweighted_impact` - the weighted impact probability map with its 50 / 90 / 99 % regions, the probability
+        +- se of landing inside `zones`, the weighted miss-distance quantiles 'cep', ess and warnings - of a run flown with
+        `run_monte_carlo_device(design=...)`, for the target law given as in `reweight` (uncertainty, motor, shift, planar).
+        density_kw: nodes, ranges, pad, bandwidth, levels, sample_density, rows."""
+        from . import analysis as ana
+        eng, summ, factors, kinds, law, prim, change = self._law_change_factors(analysis, uncertainty, motor, shift, planar)
+        out = ana.reweighted_impact(summ, factors, kinds, law, status=analysis.get("status"), engine=eng, target=target,
+                                    cep_quantiles=cep_quantiles, zones=zones, **density_kw)
+        out["primitive_rows"], out["law"] = prim, change
+        return out
+
+    def plot_reweighted_impact(self, reweighted, save_plots=True):
+        """No reference counterpart: the dict of `reweighted_impact` as monte_carlo_reweighted_impact.png (the figure of
+        `plot_impact_probability`, titled with the effective sample size) and reweighted_impact.json; returns the output
+        directory."""
+        return plots.plot_reweighted_impact(self, reweighted, save_plots)
 
     def plot_surrogate(self, surrogate, save_plots=True):
         """No reference counterpart: per row the first-order and total indices of the variables, the largest pair indices

@@ -231,6 +231,17 @@ def impact_probability_figure(result, launch_site=(0.0, 0.0)):
     return fig
 
 
+def reweighted_impact_figure(result, launch_site=(0.0, 0.0)):
+    """The weighted impact probability map from the dict of analysis.reweighted_impact, drawn by `impact_probability_figure`
+    (the zones carry 'probability' and 'interval' = probability -+ 1.96 se), titled with the effective sample size."""
+    view = dict(result)
+    view["zones"] = [dict(z, inside=z["weight"]) for z in result["zones"]]
+    fig = impact_probability_figure(view, launch_site)
+    ess = result.get("ess", float("nan"))
+    fig.axes[0].set_title(f"Impact Probability under the target law ({result['count']} impacts, effective {ess:.0f})")
+    return fig
+
+
 CORRIDOR_LABELS = {"x": "x (m)", "y": "y (m)", "z": "Altitude (m)", "downrange": "Downrange (m)", "vx": "vx (m/s)",
                    "vy": "vy (m/s)", "vz": "vz (m/s)", "speed": "Speed (m/s)"}
 
@@ -881,6 +892,22 @@ def plot_impact_probability(analyzer, analysis, save_plots=True, zones=None, **k
         output_dir = analyzer._create_output_directory()
         print(f"Impact probability plot saved to: {save_figure(fig, output_dir, 'monte_carlo_impact_probability.png')}")
         with open(os.path.join(output_dir, "impact_probability.json"), "w") as fh:
+            json.dump(to_serializable(res), fh, indent=2)
+    return output_dir
+
+
+def plot_reweighted_impact(analyzer, reweighted, save_plots=True):
+    """The map of MonteCarloAnalyzer.reweighted_impact (no reference counterpart): writes monte_carlo_reweighted_impact.png
+    and reweighted_impact.json (the dict without the per-sample row); returns the output directory (None without
+    save_plots)."""
+    from .reports import to_serializable
+    res = {k: v for k, v in reweighted.items() if k != "sample_density"}
+    fig = reweighted_impact_figure(res)
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Reweighted impact plot saved to: {save_figure(fig, output_dir, 'monte_carlo_reweighted_impact.png')}")
+        with open(os.path.join(output_dir, "reweighted_impact.json"), "w") as fh:
             json.dump(to_serializable(res), fh, indent=2)
     return output_dir
 

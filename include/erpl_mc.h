@@ -2053,6 +2053,68 @@ int erpl_mc_reweight_host(const erpl_rw_spec* spec, const double* factors, int64
                           const double* extra, const uint8_t* mask, int64_t n, erpl_reweight* result, double* logw,
                           int64_t* weights);
 
+/* The impact probability map UNDER WEIGHTS (erpl_mc_impact_density_weighted): erpl_mc_impact_density of a flown run under
+ * another input law.  `weights` is the int64 [n] device row erpl_mc_reweight writes; everything erpl_mc_impact_density
+ * states holds here - the spec (erpl_density_spec, unchanged), the conventions, the grid and its ranges, the zones and
+ * their crossing rule, the whitening, the exponent of a pair, the summation order over erpl_dens_slices(m, queries), the
+ * rule of `solid` and the order of the refusals - except for what follows.
+ * Population: a sample is COUNTED iff its mask byte is 0, both rows are finite and W_i > 0.  The samples are counted in this
+ * order: n_masked, n_non_finite, n_zero (W_i == 0), count (= m, in sample order).
+ * Admitted weights: 0 <= W_i <= 2^Q, Q = min(52, 62 - ceil(log2 n)) of erpl_mc_reweight, for EVERY column, masked or not; so
+ * sum_w <= 2^62.  A weight outside is ERPL_ERR_INVALID after the first pass, where the call waits anyway, with a message that
+ * names the lowest offending column; no output has been written then.  A NULL `weights` is refused among the pointers, just
+ * before `result`.
+ * Scaled weights: K = the bit length of max_w, w_i = ldexp((double) W_i, -K) (exact, in (0, 1)), S_d = ldexp((double) sum_w,
+ * -K).
+ * Exact (integer adds only, so they commute): sum_w, max_w; zone_w[z] = sum W_i [sample i inside zone z]; content_w[k] =
+ * sum W_j [f_j >= threshold[k]].
+ * Moments, two passes over the dense gathered population in the fixed order of erpl_mc_impact_density, every operation
+ * rounded once: mean = (sum w x) / S_d; sum_w2 = sum w w (in scaled weights: multiply by 4^K for the sum of W^2);
+ * ess = S_d^2 / sum_w2; with dx = x - mean_x, dy = y - mean_y: cov_xy = (sum w (dx dy)) / (S_d - sum_w2 / S_d), cov_xx and
+ * cov_yy likewise - np.cov(aweights = W, bias = False), the covariance of scipy.stats.gaussian_kde(weights = W); per zone
+ * zone_a2[z] = sum w w [inside], also in scaled weights.  min / max of both rows are over the counted samples.
+ * Bandwidth: ERPL_BW_SCOTT: H = (bw_scale ess^(-1/6))^2 cov (scipy's `neff` rule); ERPL_BW_MATRIX as given.
+ * Density: f(g) = norm * sum_i w_i exp(-(g - x_i)' H^-1 (g - x_i) / 2), norm = 1 / (S_d 2 pi sqrt(det)); a term enters its
+ * slice's running sum as acc = fma(w_i, exp(-0.5 e), acc), e = fma(dv, dv, du du).  f_j = f(x_j), own term included, into
+ * the optional device row `sample_density` [n], NaN where the sample is not counted.
+ * Regions: threshold[k] is the value at 0-based rank T - 1 of the multiset in which f_j occurs W_j times,
+ * T = clamp((uint64) ceil((1 - level[k]) * (double) sum_w), 1, sum_w): np.quantile(f, 1 - level[k], weights = W,
+ * method = "inverted_cdf"), a value of the row; hence content_w[k] >= level[k] * sum_w.  f_min / f_max are over the counted
+ * samples.
+ * Not solid (solid = 0): count == 0, H not finite, det <= 1e-12 h_xx h_yy, or ERPL_BW_SCOTT with m < 3.  Then every density,
+ * peak, grid_mass, norm, threshold, f_min and f_max is NaN, every content_w is 0 and peak_ix = peak_iy = -1; the counts,
+ * sum_w, max_w, the moments that exist, the ranges, the grid nodes, zone_w and zone_a2 are valid.  Not an error.  With
+ * count == 0: sum_w = max_w = 0 and sum_w2, ess NaN.
+ * No floating-point atomics (integer atomics in the selection's histograms): two calls on the same inputs return the same
+ * bytes.  The workspace belongs to the context and grows only (37 bytes per sample, 24 per node, 8 MiB of partial sums, the
+ * select's scratch). */
+typedef struct erpl_density_w {
+  int64_t count;                        /* m: mask byte 0, both rows finite, W > 0 */
+  int32_t solid;                        /* 1: the densities are numbers */
+  int32_t peak_ix, peak_iy;             /* node of the peak, -1 if not solid */
+  int32_t reserved;
+  double mean_x, mean_y;
+  double cov_xx, cov_xy, cov_yy;        /* divisor S_d - sum_w2 / S_d */
+  double h_xx, h_xy, h_yy, det;         /* H in use */
+  double norm;                          /* 1 / (S_d 2 pi sqrt(det)) */
+  double lo_x, hi_x, lo_y, hi_y;        /* the ranges in use */
+  double peak, grid_mass;
+  int64_t zone_w[ERPL_DENSITY_MAX_ZONES];      /* sum W inside */
+  double zone_a2[ERPL_DENSITY_MAX_ZONES];      /* sum w^2 inside, scaled weights */
+  int64_t n_masked, n_non_finite, n_zero;
+  int64_t sum_w, max_w;
+  double sum_w2, ess;                   /* sum w^2 in scaled weights; ess = S_d^2 / sum_w2 */
+  double threshold[ERPL_DENSITY_MAX_LEVELS];   /* t_k: f >= t_k is the region of content level[k] */
+  int64_t content_w[ERPL_DENSITY_MAX_LEVELS];  /* sum W [f_j >= t_k] */
+  double f_min, f_max;                  /* of the f_j */
+} erpl_density_w;
+
+/* weights: device int64 [n]; grid_x, grid_y, density: host memory as for erpl_mc_impact_density; sample_density: optional
+ * caller-owned device double [n]. */
+int erpl_mc_impact_density_weighted(erpl_ctx* ctx, const double* summary, const uint8_t* mask, const int64_t* weights,
+                                    int64_t n, const erpl_density_spec* spec, double* grid_x, double* grid_y,
+                                    double* density, erpl_density_w* result, double* sample_density, void* hip_stream);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
