@@ -284,6 +284,28 @@ class ErplCorridorSpec(C.Structure):
                 ("n_q", C.c_int32), ("reserved", C.c_int32), ("q", _Q)]
 
 
+# erpl_mc_corridor_drivers
+CDRV_MAX_FACTORS = 32
+CDRV_MAX_ROWS = 32768
+
+_DF_D = C.c_double * CDRV_MAX_FACTORS
+
+
+class ErplCdrvSpec(C.Structure):
+    _fields_ = [("n_factors", C.c_int32), ("n_rows", C.c_int32), ("regression", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ErplCdrvResult(C.Structure):
+    _fields_ = [("m", C.c_int64), ("n_base", C.c_int64), ("n_masked", C.c_int64), ("n_factor_non_finite", C.c_int64),
+                ("constant", C.c_int32 * CDRV_MAX_FACTORS),
+                ("mean", _DF_D), ("std", _DF_D), ("min", _DF_D), ("max", _DF_D)]
+
+
+class ErplCdrvRow(C.Structure):
+    _fields_ = [("count", C.c_int64), ("mean", C.c_double), ("std", C.c_double), ("min", C.c_double), ("max", C.c_double),
+                ("r2", C.c_double), ("pivot_min", C.c_double), ("constant", C.c_int32), ("regression_ok", C.c_int32)]
+
+
 # erpl_mc_impact_points: channels of the values [IIP_CH_COUNT][n_nodes][ld], rows of the summary [IIP_DIM][n_traj]
 IIP_DIM = 16
 IIP_MAX_NODES = 4096
@@ -630,7 +652,8 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_subset_seeds", "erpl_mc_subset_seeds_host", "erpl_mc_subset_propose", "erpl_mc_subset_propose_host",
            "erpl_mc_subset_commit", "erpl_mc_subset_commit_host", "erpl_mc_subset_chain_stats", "erpl_mc_subset_chain_stats_host",
            "erpl_mc_reweight_defaults", "erpl_mc_reweight", "erpl_mc_reweight_host",
-           "erpl_mc_casualty_defaults", "erpl_mc_casualty")
+           "erpl_mc_casualty_defaults", "erpl_mc_casualty",
+           "erpl_mc_corridor_drivers_defaults", "erpl_mc_corridor_drivers")
 
 _lib = None
 
@@ -793,6 +816,11 @@ def load_library(path=None):
     # result, hip_stream
     lib.erpl_mc_casualty.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(ErplCasualtySpec)] + \
         [C.c_void_p] * 9 + [C.POINTER(ErplCasualty), C.c_void_p]
+    lib.erpl_mc_corridor_drivers_defaults.argtypes = [C.POINTER(ErplCdrvSpec)]
+    # ctx, factors, ldf, values, ld, mask, m, spec, result, rows, pearson, src, hip_stream
+    lib.erpl_mc_corridor_drivers.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                             C.POINTER(ErplCdrvSpec), C.POINTER(ErplCdrvResult), C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if a declared symbol is not exported
         if name not in ("erpl_mc_last_error",):

@@ -405,6 +405,57 @@ def trajectory_corridor(values, channels=("z", "downrange", "speed"), t0=0.0, dt
     return out
 
 
+def rank_corridor_drivers(pearson, count, factor_names):
+    """'share', 'ranking' and 'lead' of `corridor_drivers` from pearson [C, T, F] and count [C, T]: share = pearson^2, the
+    linear variance share; per channel the factor names ordered by their largest share over the nodes with count >= 2 (a
+    factor without a number there last, ties in factor order); per channel and node the name of the factor with the largest
+    share (None where no factor has one)."""
+    pearson = np.asarray(pearson, dtype=np.float64)
+    share = pearson * pearson
+    usable = np.where((np.asarray(count) >= 2)[..., None], share, np.nan)
+    ranking, lead = [], []
+    for c in range(share.shape[0]):
+        some = ~np.all(np.isnan(usable[c]), axis=0)
+        best = np.full(share.shape[2], -1.0)
+        if usable[c].size:
+            best[some] = np.nanmax(usable[c][:, some], axis=0)
+        ranking.append([factor_names[f] for f in np.argsort(-best, kind="stable")])
+        row = []
+        for k in range(share.shape[1]):
+            v = usable[c, k]
+            row.append(None if np.all(np.isnan(v)) else factor_names[int(np.nanargmax(v))])
+        lead.append(row)
+    return share, ranking, lead
+
+
+def corridor_drivers(values, factors, factor_names, channels=None, t0=0.0, dt=1.0, mask=None, engine=None, m=None,
+                     regression=True):
+    """Which dispersion drives what, and when: for every (channel, node) row of a time-resolved matrix (float64 [C, T, ld] on
+    the device - the corridor of TrajectoryEngine.corridor_resample, the matrix of `impact_points` or of `debris`) and every
+    row of `factors` (float64 [F, ldf] on the device) the Pearson correlation and the standardised regression coefficient over
+    the columns whose `mask` byte is 0 and that are finite in that row - each node has its own population, the flights still
+    defined there - by one erpl_mc_corridor_drivers call.  channels: the names of the C channels (default 'channel 0' ..).
+    Returns the dict of TrajectoryEngine.corridor_drivers plus 'time' [T] (t0 + k dt), 'channels', 'factor_names', 'share'
+    (pearson^2 [C, T, F], the linear variance share), 'ranking' (per channel the factor names by their largest share over
+    the nodes with count >= 2) and 'lead' (per channel and node the leading factor's name, None where there is none)."""
+    engine = _engine_of(values, engine)
+    factor_names = list(factor_names)
+    if len(factor_names) != int(factors.shape[0]):
+        raise ValueError(f"{len(factor_names)} factor names for {int(factors.shape[0])} factor rows")
+    if values.dim() != 3:
+        raise ValueError("values must be a [C, T, ld] matrix")
+    n_ch, n_nodes = int(values.shape[0]), int(values.shape[1])
+    channels = [f"channel {c}" for c in range(n_ch)] if channels is None else \
+        [CORRIDOR_CHANNEL_NAMES[c] if not isinstance(c, str) else c for c in channels]
+    if len(channels) != n_ch:
+        raise ValueError(f"{len(channels)} channels for a matrix of {n_ch}")
+    out = engine.corridor_drivers(factors, values, mask=mask, m=m, regression=regression)
+    out["time"] = float(t0) + np.arange(n_nodes, dtype=np.float64) * float(dt)
+    out["channels"], out["factor_names"] = channels, factor_names
+    out["share"], out["ranking"], out["lead"] = rank_corridor_drivers(out["pearson"], out["count"], factor_names)
+    return out
+
+
 # ---------------------------------------------------------------------------------- drivers: which dispersion drives what
 ROW_NAMES = ("apogee_altitude", "apogee_time", "first_apogee_altitude", "first_apogee_time", "range", "flight_time",
              "rail_exit_time", "rail_exit_speed", "impact_x", "impact_y", "impact_z", "n_steps",

@@ -478,6 +478,7 @@ int erpl_mc_destroy(erpl_ctx* c) {
   if (c->subset_ev) (void)hipEventDestroy(c->subset_ev);
   c->reweight.release();
   c->casualty.release();
+  c->cdrv.release();
   if (c->reweight_pin) (void)hipHostFree(c->reweight_pin);
   delete c;
   return ERPL_OK;

@@ -1,5 +1,5 @@
 // erpl_host.h — what the host units of the C ABI share (erpl_api.hip, erpl_sampling.hip, erpl_stats_api.hip,
-// erpl_legacy_device.hip, erpl_design.hip, erpl_qmc.hip, erpl_tally.hip, erpl_subset.hip, erpl_reweight.hip, erpl_casualty.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
+// erpl_legacy_device.hip, erpl_design.hip, erpl_qmc.hip, erpl_tally.hip, erpl_subset.hip, erpl_reweight.hip, erpl_casualty.hip, erpl_corridor_drivers.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
 // Internal, never installed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -275,6 +275,9 @@ struct erpl_ctx {
   // erpl_mc_casualty: the pieces erpl_casualty.hip lists (its fixed block, the words of the map, the dense members of the groups,
   // the partials of the smoothing pass) in the buffer; what comes back is small or caller-sized and needs no pinned mirror
   ErplStatUnit<void, char> casualty;
+  // erpl_mc_corridor_drivers: the pieces of erpl_cdrv_layout (erpl_stat_layout.h) in the buffer; what comes back is caller-sized
+  // and needs no pinned mirror
+  ErplStatUnit<void, char> cdrv;
 };
 
 // erpl_design.hip

@@ -1,5 +1,5 @@
 // erpl_stat_layout.h — how erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density, erpl_mc_sobol,
-// erpl_mc_dependence, erpl_mc_compare, erpl_mc_surrogate, erpl_mc_reweight and erpl_mc_impact_density_weighted cut the device buffer each of them grows into pieces: pure functions
+// erpl_mc_dependence, erpl_mc_compare, erpl_mc_surrogate, erpl_mc_reweight, erpl_mc_impact_density_weighted and erpl_mc_corridor_drivers cut the device buffer each of them grows into pieces: pure functions
 // of the call's sizes (no HIP; the scratch size of the rocPRIM calls comes in as a number), so that tests/test_stat_layout.py,
 // tests/test_dependence_layout.py, tests/test_compare_layout.py and tests/test_surrogate_abi.py check every offset on the CPU, through
 // erpl_stat_layout_table, before a kernel writes through one.  Every piece starts at a multiple of 256 bytes; `need` is the
@@ -272,6 +272,82 @@ inline ErplRwLayout erpl_rw_layout(int64_t n, bool caller_keeps_logw, bool calle
   l.work = c.take(work_bytes);
   l.logw = c.take(caller_keeps_logw ? 0 : 8 * un);
   l.weights = c.take(caller_keeps_weights ? 0 : 8 * un);
+  l.need = c.end;
+  return l;
+}
+
+// erpl_mc_corridor_drivers over m columns, R rows, F factors.  The shapes of its passes are functions of m (and of F and
+// `regression` for the widths) alone, never of R: a row's results do not depend on which other rows are in the call.
+#define ERPL_CDRV_TILE_ROWS 32          // rows of `values` per workgroup of the product pass: two 16-row blocks of memberships, two of y'
+#define ERPL_CDRV_KT 16                 // members per LDS stage of the product pass
+#define ERPL_CDRV_LIN 48                // the linear columns of a row: x'_0 .. x'_31, the ones at 32, zeros behind them
+#define ERPL_CDRV_ONE 32
+#define ERPL_CDRV_ZERO 33
+#define ERPL_CDRV_SEG 65536             // columns a segment of the moment passes has at the least
+#define ERPL_CDRV_MAX_SEGS 64
+#define ERPL_CDRV_SLICE 4096            // members a slice of the product pass has at the least
+#define ERPL_CDRV_MAX_SLICES 32
+#define ERPL_CDRV_PART_BYTES ((size_t)256 << 20)   // the partial tiles of one launch of the product pass
+// segments of the moment passes; *seg_len: columns per segment, a multiple of 256
+inline int erpl_cdrv_segments(int64_t m, int64_t* seg_len) {
+  int64_t s = (m + ERPL_CDRV_SEG - 1) / ERPL_CDRV_SEG;
+  if (s > ERPL_CDRV_MAX_SEGS) s = ERPL_CDRV_MAX_SEGS;
+  const int64_t per = ((m + s - 1) / s + 255) / 256 * 256;
+  *seg_len = per;
+  return (int)((m + per - 1) / per);
+}
+// slices of the product pass; *slice_len: members per slice, a multiple of ERPL_CDRV_KT
+inline int erpl_cdrv_slices(int64_t m, int64_t* slice_len) {
+  int64_t s = (m + ERPL_CDRV_SLICE - 1) / ERPL_CDRV_SLICE;
+  if (s > ERPL_CDRV_MAX_SLICES) s = ERPL_CDRV_MAX_SLICES;
+  const int64_t per = ((m + s - 1) / s + ERPL_CDRV_KT - 1) / ERPL_CDRV_KT * ERPL_CDRV_KT;
+  *slice_len = per;
+  return (int)((m + per - 1) / per);
+}
+// the product columns x'_f x'_g a row carries: the F squares first, then - with the regression - the pairs f < g row by row
+inline int erpl_cdrv_products(int F, bool regression) { return regression ? F * (F + 1) / 2 : F; }
+inline int erpl_cdrv_product_index(int F, int f, int g) { return f == g ? f : F + f * (2 * F - f - 1) / 2 + (g - f - 1); }
+inline int erpl_cdrv_product_blocks(int F, bool regression) { return (erpl_cdrv_products(F, regression) + 15) / 16; }
+// doubles of a row of sums: [memberships x linear columns 48][memberships x products, whole blocks of 16][y' x linear columns 48]
+// [sum y'^2][padding to a multiple of 4]
+inline int erpl_cdrv_row_doubles(int F, bool regression) {
+  return (2 * ERPL_CDRV_LIN + 16 * erpl_cdrv_product_blocks(F, regression) + 1 + 3) / 4 * 4;
+}
+// tiles of ERPL_CDRV_TILE_ROWS rows one launch of the product pass takes: what fits ERPL_CDRV_PART_BYTES, at least one
+inline int erpl_cdrv_chunk_tiles(int64_t m, int F, bool regression) {
+  int64_t len;
+  const size_t tile = 8 * (size_t)ERPL_CDRV_TILE_ROWS * (size_t)erpl_cdrv_row_doubles(F, regression) * (size_t)erpl_cdrv_slices(m, &len);
+  const size_t t = ERPL_CDRV_PART_BYTES / tile;
+  return (int)(t < 1 ? 1 : t);
+}
+// [base m bytes][counts 4 u64][fstat F records of 8 doubles][rstat R records of 8 doubles][mpart max(F, R) segs 4 doubles: the
+// partials of a moment pass][part chunk_tiles slices tiles of 32 rows of row_doubles][sums chunk_tiles 32 rows of row_doubles]
+// [pairs R F (row, factor) int32 pairs: the pairs whose extremes are asked for][ext R F (min, max)]
+struct ErplCdrvLayout {
+  size_t base, count, fstat, rstat, mpart, part, sums, pairs, ext, need;
+  int64_t seg_len, slice_len;
+  int segs, slices, chunk_tiles, row_doubles;
+};
+inline ErplCdrvLayout erpl_cdrv_layout(int64_t m, int R, int F, bool regression) {
+  const size_t um = (size_t)m, uR = (size_t)R, uF = (size_t)F;
+  ErplCarve c;
+  ErplCdrvLayout l = {};
+  l.segs = erpl_cdrv_segments(m, &l.seg_len);
+  l.slices = erpl_cdrv_slices(m, &l.slice_len);
+  l.row_doubles = erpl_cdrv_row_doubles(F, regression);
+  l.chunk_tiles = erpl_cdrv_chunk_tiles(m, F, regression);
+  const size_t tiles = (uR + ERPL_CDRV_TILE_ROWS - 1) / ERPL_CDRV_TILE_ROWS;
+  const size_t chunk = tiles < (size_t)l.chunk_tiles ? tiles : (size_t)l.chunk_tiles;
+  const size_t tile_bytes = 8 * (size_t)ERPL_CDRV_TILE_ROWS * (size_t)l.row_doubles;
+  l.base = c.take(um);
+  l.count = c.take(32);
+  l.fstat = c.take(64 * uF);
+  l.rstat = c.take(64 * uR);
+  l.mpart = c.take(32 * (uR > uF ? uR : uF) * (size_t)l.segs);
+  l.part = c.take(tile_bytes * chunk * (size_t)l.slices);
+  l.sums = c.take(tile_bytes * chunk);
+  l.pairs = c.take(8 * uR * uF);
+  l.ext = c.take(16 * uR * uF);
   l.need = c.end;
   return l;
 }

@@ -21,6 +21,9 @@
 //   rw <n> <caller_keeps_logw> <caller_keeps_weights> <work_bytes>       -> work logw weights need
 //   wdens <n> <nodes> <want_samples> <caller_keeps_row> <temp_bytes>     -> pop src count temp pts ws nodes dens row part temp_bytes
 //                                                                           need
+//   cdrv <m> <R> <F> <regression>                                        -> base count fstat rstat mpart part sums pairs ext
+//                                                                           seg_len slice_len segs slices chunk_tiles row_doubles
+//                                                                           need
 #include <stdio.h>
 
 #include <initializer_list>
@@ -102,6 +105,12 @@ int main() {
     } else if (sscanf(line, "wdens %lld %lld %d %d %zu", &n, &nodes, &a, &b, &temp) == 5) {
       const ErplDensWLayout l = erpl_densw_layout(n, nodes, a != 0, b != 0, temp);
       for (size_t v : {l.pop, l.src, l.count, l.temp, l.pts, l.ws, l.nodes, l.dens, l.row, l.part, l.temp_bytes}) put(v);
+      put(l.need, "\n");
+    } else if (sscanf(line, "cdrv %lld %d %d %d", &n, &a, &b, &c) == 4 && n >= 1 && a >= 1 && b >= 1 && b <= ERPL_CDRV_MAX_FACTORS) {
+      const ErplCdrvLayout l = erpl_cdrv_layout(n, a, b, c != 0);
+      for (size_t v : {l.base, l.count, l.fstat, l.rstat, l.mpart, l.part, l.sums, l.pairs, l.ext, (size_t)l.seg_len, (size_t)l.slice_len,
+                       (size_t)l.segs, (size_t)l.slices, (size_t)l.chunk_tiles, (size_t)l.row_doubles})
+        put(v);
       put(l.need, "\n");
     } else {
       fprintf(stderr, "bad request: %s", line);

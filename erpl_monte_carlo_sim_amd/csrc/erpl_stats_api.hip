@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "erpl_cdrv.h"
 #include "erpl_host.h"
 #include "erpl_philox.h"
 #include "erpl_reweight.h"
@@ -443,46 +444,7 @@ void corr_from_gram(const double* g, int V, const int32_t* constant, bool any, d
     }
 }
 
-// Standardised regression of every non-constant row on the non-constant factors: R_ff beta = r_fy by Cholesky.  The k-th
-// pivot is 1 - R^2 of factor k on the factors before it.  false: a pivot below 1e-10 or not finite (everything stays NaN).
-bool regress(const double* corr, int V, int F, int R, const int32_t* constant, double (*coef)[ERPL_CORR_MAX_FACTORS],
-             double* r2) {
-  int use[ERPL_CORR_MAX_FACTORS], m = 0;
-  for (int f = 0; f < F; ++f) if (!constant[f]) use[m++] = f;
-  static thread_local double L[ERPL_CORR_MAX_FACTORS][ERPL_CORR_MAX_FACTORS];
-  for (int i = 0; i < m; ++i)
-    for (int j = 0; j <= i; ++j) {
-      double s = corr[(size_t)use[i] * V + use[j]];
-      for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
-      if (i == j) {
-        if (!(s >= 1e-10) || !std::isfinite(s)) return false;
-        L[i][i] = sqrt(s);
-      } else {
-        L[i][j] = s / L[j][j];
-      }
-    }
-  for (int j = 0; j < R; ++j) {
-    if (constant[F + j]) continue;
-    double y[ERPL_CORR_MAX_FACTORS], beta[ERPL_CORR_MAX_FACTORS];
-    for (int i = 0; i < m; ++i) {
-      double s = corr[(size_t)(F + j) * V + use[i]];
-      for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
-      y[i] = s / L[i][i];
-    }
-    for (int i = m - 1; i >= 0; --i) {
-      double s = y[i];
-      for (int k = i + 1; k < m; ++k) s -= L[k][i] * beta[k];
-      beta[i] = s / L[i][i];
-    }
-    double fit = 0.0;
-    for (int i = 0; i < m; ++i) {
-      coef[j][use[i]] = beta[i];
-      fit += beta[i] * corr[(size_t)(F + j) * V + use[i]];
-    }
-    r2[j] = fit;
-  }
-  return true;
-}
+// (the standardised regression of the rows on the factors is erpl_regress of erpl_cdrv.h: erpl_mc_corridor_drivers shares it)
 
 }  // namespace
 
@@ -582,7 +544,7 @@ int erpl_mc_correlation(erpl_ctx* c, const double* factors, const double* summar
         for (int f = 0; f < ERPL_CORR_MAX_FACTORS; ++f) fit.src[j][f] = nan;
         fit.r2[j] = nan;
       }
-      ok = regress(m, V, F, R, result->constant, fit.src, fit.r2);
+      ok = erpl_regress(m, V, F, R, result->constant, fit.src, fit.r2);
       if (ok) {
         memcpy(pass ? result->srrc : result->src, fit.src, sizeof(fit.src));
         memcpy(pass ? result->r2_rank : result->r2, fit.r2, sizeof(fit.r2));

@@ -592,6 +592,61 @@ class TrajectoryEngine:
         out["n_counted"] = int(counted.value)
         return out
 
+    def corridor_drivers(self, factors, values, mask=None, m=None, regression=True):
+        """Which factor drives which row of a time-resolved matrix, each row over ITS OWN population
+        (erpl_mc_corridor_drivers; the definitions are in include/erpl_mc.h): factors float64 [F, ldf] and values float64
+        [C, T, ld] or [R, ld] on the device - a corridor, an impact-point or a debris matrix as it is - of which the first m
+        columns are read (default: the shorter of the two); mask uint8 [m] on the device, a column counts iff its byte is 0.
+        Enqueued on the current torch stream; blocks the host until the result is there.  Returns a dict of NumPy arrays
+        shaped like `values` without its column axis: 'count' int64, 'mean', 'std', 'min', 'max', 'r2', 'pivot_min' float64,
+        'constant', 'regression_ok' bool; 'pearson' and 'src' float64 [..., F] ('src' None without the regression); and
+        'm', 'n_base', 'n_masked', 'n_factor_non_finite', 'factor_mean' / '_std' / '_min' / '_max' / '_constant' [F]."""
+        ok = lambda t: torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype == torch.float64 and t.is_contiguous()
+        if not (ok(factors) and factors.dim() == 2):
+            raise ValueError(f"factors must be a contiguous float64 [F, ldf] tensor on {self.device}")
+        if not (ok(values) and values.dim() in (2, 3)):
+            raise ValueError(f"values must be a contiguous float64 [C, T, ld] or [R, ld] tensor on {self.device}")
+        F, ldf = (int(s) for s in factors.shape)
+        shape, ld = tuple(int(s) for s in values.shape[:-1]), int(values.shape[-1])
+        R = int(np.prod(shape))
+        m = min(ld, ldf) if m is None else int(m)
+        if not 1 <= F <= _abi.CDRV_MAX_FACTORS:
+            raise ValueError(f"1 to {_abi.CDRV_MAX_FACTORS} factors")
+        if not 1 <= R <= _abi.CDRV_MAX_ROWS:
+            raise ValueError(f"1 to {_abi.CDRV_MAX_ROWS} rows")
+        if not 1 <= m <= min(ld, ldf):
+            raise ValueError(f"m = {m} outside 1..{min(ld, ldf)}")
+        if mask is not None and not (torch.is_tensor(mask) and mask.device == self.device and mask.dtype == torch.uint8
+                                     and tuple(mask.shape) == (m,) and mask.is_contiguous()):
+            raise ValueError(f"mask must be a contiguous uint8 [m] tensor on {self.device}")
+        spec = self._defaults(_abi.ErplCdrvSpec, "erpl_mc_corridor_drivers_defaults")
+        spec.n_factors, spec.n_rows, spec.regression = F, R, int(bool(regression))
+        res = _abi.ErplCdrvResult()
+        rows = (_abi.ErplCdrvRow * R)()
+        pearson = np.empty((R, F), dtype=np.float64)
+        src = np.empty((R, F), dtype=np.float64) if regression else None
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_corridor_drivers", C.c_void_p(factors.data_ptr()), ldf, C.c_void_p(values.data_ptr()), ld,
+                   C.c_void_p(mask.data_ptr()) if mask is not None else None, m, C.byref(spec), C.byref(res),
+                   C.cast(rows, C.c_void_p), C.c_void_p(pearson.ctypes.data),
+                   C.c_void_p(src.ctypes.data) if regression else None, C.c_void_p(st.cuda_stream))
+        # erpl_cdrv_row is 8 eight-byte words: count, mean, std, min, max, r2, pivot_min, then (constant, regression_ok)
+        raw = np.frombuffer(rows, dtype=np.float64).reshape(R, 8)
+        flags = np.frombuffer(rows, dtype=np.int32).reshape(R, 16)
+        out = {"count": np.frombuffer(rows, dtype=np.int64).reshape(R, 8)[:, 0].reshape(shape).copy()}
+        for k, name in enumerate(("mean", "std", "min", "max", "r2", "pivot_min")):
+            out[name] = raw[:, 1 + k].reshape(shape).copy()
+        out["constant"] = flags[:, 14].reshape(shape) != 0
+        out["regression_ok"] = flags[:, 15].reshape(shape) != 0
+        out["pearson"] = pearson.reshape(shape + (F,))
+        out["src"] = src.reshape(shape + (F,)) if regression else None
+        out.update({"m": int(res.m), "n_base": int(res.n_base), "n_masked": int(res.n_masked),
+                    "n_factor_non_finite": int(res.n_factor_non_finite),
+                    "factor_constant": np.array(res.constant[:F], dtype=np.int32) != 0})
+        for k in ("mean", "std", "min", "max"):
+            out["factor_" + k] = np.array(getattr(res, k)[:F], dtype=np.float64)
+        return out
+
     def analysis_defaults(self):
         """The reference's outlier bounds, rows and quantiles (erpl_mc_analysis_defaults)."""
         return self._defaults(_abi.ErplAnalysisSpec, "erpl_mc_analysis_defaults")

@@ -725,13 +725,15 @@ class MonteCarloAnalyzer:
                               "sub_batches": len(envs), "sub_batch_samples": run["per_batch"]}
         return out
 
-    def _captured_run(self, who, what, initial_conditions, n_samples, stride, seed, precision, planar, capture_bytes, reduce):
+    def _captured_run(self, who, what, initial_conditions, n_samples, stride, seed, precision, planar, capture_bytes, reduce,
+                      factors=None):
         """The capturing loop of `flight_envelope`, `trajectory_corridor` and `impact_point_trace`: the samples of run_monte_carlo_device (sub-batch
         j from seed + rank + 1000003 * j) flown with every trajectory captured at every `stride`-th step, in sub-batches of
         capture_bytes // (cap * 120) samples (at most DEVICE_CHUNK); `reduce(eng, db, first_sample, traj, traj_len)`
         enqueues what the caller makes of a sub-batch's capture, and the capture buffer is released behind it.  One rank
-        only (`who` / `what` word the refusal).  Returns (engine, summary [16, n], status [n], {'t0', 'stride', 'cap',
-        'per_batch', 'sub_batches'}) once everything has run."""
+        only (`who` / `what` word the refusal).  factors: a list that receives (db.factors, db.factor_names) of every sub-batch
+        - the draws are otherwise released with the sub-batch.  Returns (engine, summary [16, n], status [n], {'t0', 'stride',
+        'cap', 'per_batch', 'sub_batches'}) once everything has run."""
         from . import sampling
         if dist.world()[1] > 1:
             raise ValueError(f"{who} is limited to a world size of 1: {what} are not gathered across ranks")
@@ -757,6 +759,8 @@ class MonteCarloAnalyzer:
                 planar=planar, engine=eng)
             summ, status, traj, tlen = eng.run(db, traj_ids=np.arange(nb), traj_stride=stride, traj_cap=cap)
             reduce(eng, db, a, traj, tlen)
+            if factors is not None:
+                factors.append((db.factors, db.factor_names))
             summs.append(summ)
             stats.append(status)
             del traj, tlen, db   # (stream-ordered: the allocator hands the capture buffer on behind the caller's kernel)
@@ -765,9 +769,16 @@ class MonteCarloAnalyzer:
         return eng, cat(summs, 1), cat(stats, 0), {"t0": t0, "stride": stride, "cap": cap, "per_batch": per_batch,
                                                    "sub_batches": len(summs)}
 
+    @staticmethod
+    def _kept_factors(out, kept):
+        """out['factors'] ([F, n] on the device, the sample order of out['summary']) and out['factor_names'] from what
+        `_captured_run` collected per sub-batch."""
+        out["factors"] = kept[0][0].contiguous() if len(kept) == 1 else torch.cat([f for f, _ in kept], dim=1).contiguous()
+        out["factor_names"] = list(kept[0][1])
+
     def trajectory_corridor(self, initial_conditions, n_samples, stride=10, seed=1234, precision="f64_fast", planar=False,
                             capture_bytes=4 << 30, nodes=256, t_end=None, channels=("z", "downrange", "speed"),
-                            quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), hold=True):
+                            quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), hold=True, keep_factors=False):
         """Where the vehicle is at time t and how wide the spread is there, for a whole dispersion run: the samples of
         `flight_envelope` (same draws, same sub-batches, every trajectory captured at every `stride`-th step) are brought
         onto `nodes` time nodes from 0 to `t_end` (default max_time) on the device, each sub-batch into its window of
@@ -780,7 +791,9 @@ class MonteCarloAnalyzer:
 
         Returns the dict of analysis.trajectory_corridor ('time', 'q', 'channels', per channel 'count' / 'mean' / 'std' /
         'min' / 'max' [T] and 'quantiles' [n_q, T]) plus 'summary', 'status', 'reasons', 'n_samples' / 'n_outliers' of the
-        filter, 'values' (the resampled matrix, on the device) and 'performance'."""
+        filter, 'values' (the resampled matrix, on the device) and 'performance'.  keep_factors=True keeps the per-sample
+        draws and adds 'factors' (float64 [F, n] on the device, the sample order of 'summary') and 'factor_names', the input
+        of `corridor_drivers`."""
         nodes = int(nodes)
         if nodes < 2:
             raise ValueError("at least 2 nodes")
@@ -797,8 +810,9 @@ class MonteCarloAnalyzer:
                                            device=eng.device)
             eng.corridor_resample(traj, tlen, idx, nodes, 0.0, step, hold=hold, out=box["values"], col0=a)
 
+        kept = [] if keep_factors else None
         eng, summ, status, run = self._captured_run("trajectory_corridor", "corridors", initial_conditions, n_samples,
-                                                    stride, seed, precision, planar, capture_bytes, resample)
+                                                    stride, seed, precision, planar, capture_bytes, resample, factors=kept)
         torch.cuda.synchronize(eng.device)
         t1 = time.time()
         _, res, why = analysis._filter(summ, status, eng)
@@ -806,6 +820,8 @@ class MonteCarloAnalyzer:
         t2 = time.time()
         out.update({"summary": summ, "status": status, "reasons": why, "values": box["values"],
                     "n_samples": int(res.n_valid), "n_outliers": int(res.n_outliers)})
+        if keep_factors:
+            self._kept_factors(out, kept)
         out["performance"] = {"total_time": t2 - run["t0"], "capture_and_resample_s": t1 - run["t0"], "bands_s": t2 - t1,
                               "precision": precision, "stride": run["stride"], "records_per_sample": run["cap"],
                               "sub_batches": run["sub_batches"], "sub_batch_samples": run["per_batch"]}
@@ -814,7 +830,7 @@ class MonteCarloAnalyzer:
     def impact_point_trace(self, initial_conditions, n_samples, stride=10, nodes=64, record_stride=None, keep_in=None,
                            seed=1234, precision="f64_fast", planar=False, capture_bytes=4 << 30, dt=0.05, max_steps=20000,
                            ground=0.0, drag_scale=1.0, origin=(0.0, 0.0), quantiles=(0.05, 0.25, 0.5, 0.75, 0.95),
-                           level=0.95):
+                           level=0.95, keep_factors=False):
         """If the flight is terminated at time t, where does the vehicle come down - for a whole dispersion run: the samples
         of `flight_envelope` (same draws, same sub-batches, every trajectory captured at every `stride`-th step) and, of each
         capture, `nodes` records `record_stride` apart (None: the stride that spreads the nodes over max_time) fall to
@@ -829,7 +845,8 @@ class MonteCarloAnalyzer:
         'statistics' (analysis.impact_point_statistics of the summary rows over the same samples); 'exit_probability', the
         share of those samples whose IIP ever leaves the keep-in area, with its Wilson interval 'exit_interval' at `level`
         (NaN and (0, 1) without a polygon) and 'exit_count'; 'values' and 'iip_summary' (on the device), 'iip_names',
-        'keep_in', 'summary', 'status', 'reasons', 'n_samples' / 'n_outliers' and 'performance'."""
+        'keep_in', 'summary', 'status', 'reasons', 'n_samples' / 'n_outliers' and 'performance'.  keep_factors=True adds
+        'factors' and 'factor_names' as in `trajectory_corridor`."""
         nodes, stride = int(nodes), int(stride)
         if not 1 <= nodes <= _abi.IIP_MAX_NODES:
             raise ValueError(f"1 to {_abi.IIP_MAX_NODES} nodes")
@@ -853,8 +870,9 @@ class MonteCarloAnalyzer:
                                      out=box["values"], col0=a)
             summaries.append(s)
 
+        kept = [] if keep_factors else None
         eng, summ, status, run = self._captured_run("impact_point_trace", "impact points", initial_conditions, n_samples,
-                                                    stride, seed, precision, planar, capture_bytes, fall)
+                                                    stride, seed, precision, planar, capture_bytes, fall, factors=kept)
         iip = summaries[0] if len(summaries) == 1 else torch.cat(summaries, dim=1).contiguous()
         torch.cuda.synchronize(eng.device)
         t1 = time.time()
@@ -876,6 +894,8 @@ class MonteCarloAnalyzer:
         out.update({"summary": summ, "status": status, "reasons": why, "values": box["values"], "iip_summary": iip,
                     "iip_names": list(analysis.IIP_NAMES), "keep_in": keep, "record_stride": record_stride,
                     "n_samples": int(res.n_valid), "n_outliers": int(res.n_outliers)})
+        if keep_factors:
+            self._kept_factors(out, kept)
         out["performance"] = {"total_time": t2 - run["t0"], "capture_and_fall_s": t1 - run["t0"], "statistics_s": t2 - t1,
                               "precision": precision, "stride": run["stride"], "records_per_sample": run["cap"],
                               "sub_batches": run["sub_batches"], "sub_batch_samples": run["per_batch"]}
@@ -884,7 +904,7 @@ class MonteCarloAnalyzer:
     def debris_footprint(self, initial_conditions, n_samples, fragments, stride=10, nodes=16, record_stride=None, keep_in=None,
                          maps=(), map_bins=50, seed=1234, debris_seed=None, precision="f64_fast", planar=False,
                          capture_bytes=4 << 30, dt=0.05, max_steps=20000, ground=0.0, stiff_limit=0.25, origin=(0.0, 0.0),
-                         quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), level=0.95):
+                         quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), level=0.95, keep_factors=False):
         """If the vehicle breaks up at time t, where do its pieces come down - for a whole dispersion run: the samples of
         `impact_point_trace` (same draws, same sub-batches, same nodes) and, at every node, the fragments
         `fragments` = [(beta, dv), ...] - beta the ballistic coefficient m / (Cd A) in kg/m^2 (float('inf'): no drag), dv the
@@ -903,7 +923,8 @@ class MonteCarloAnalyzer:
         'exit_probability', the share of those samples with a fragment that lands outside the keep-in area, with its
         Wilson interval 'exit_interval' at `level` (NaN and (0, 1) without a polygon) and 'exit_count'; 'maps', a dict
         (node, fragment) -> {'counts', 'edges_x', 'edges_y', 'info'}; 'values' and 'debris_summary' (on the device),
-        'debris_names', 'keep_in', 'summary', 'status', 'reasons', 'n_samples' / 'n_outliers' and 'performance'."""
+        'debris_names', 'keep_in', 'summary', 'status', 'reasons', 'n_samples' / 'n_outliers' and 'performance'.
+        keep_factors=True adds 'factors' and 'factor_names' as in `trajectory_corridor`."""
         nodes, stride = int(nodes), int(stride)
         frags = [(float(beta), float(dv)) for beta, dv in fragments]
         F = len(frags)
@@ -940,8 +961,9 @@ class MonteCarloAnalyzer:
                               seed=debris_seed + 1000003 * len(summaries), origin=origin, keep_in=keep, out=box["values"], col0=a)
             summaries.append(s)
 
+        kept = [] if keep_factors else None
         eng, summ, status, run = self._captured_run("debris_footprint", "debris footprints", initial_conditions, n_samples,
-                                                    stride, seed, precision, planar, capture_bytes, fall)
+                                                    stride, seed, precision, planar, capture_bytes, fall, factors=kept)
         deb = summaries[0] if len(summaries) == 1 else torch.cat(summaries, dim=1).contiguous()
         torch.cuda.synchronize(eng.device)
         t1 = time.time()
@@ -971,10 +993,37 @@ class MonteCarloAnalyzer:
         out.update({"summary": summ, "status": status, "reasons": why, "values": vals, "debris_summary": deb,
                     "debris_names": list(analysis.DEBRIS_NAMES), "keep_in": keep, "record_stride": record_stride,
                     "debris_seed": debris_seed, "n_samples": int(res.n_valid), "n_outliers": int(res.n_outliers)})
+        if keep_factors:
+            self._kept_factors(out, kept)
         out["performance"] = {"total_time": t2 - run["t0"], "capture_and_fall_s": t1 - run["t0"], "statistics_s": t2 - t1,
                               "precision": precision, "stride": run["stride"], "records_per_sample": run["cap"],
                               "sub_batches": run["sub_batches"], "sub_batch_samples": run["per_batch"]}
         return out
+
+    def corridor_drivers(self, captured, regression=True):
+        """Which dispersion drives what, and when (no reference counterpart): the dict of `trajectory_corridor`,
+        `impact_point_trace` or `debris_footprint` flown with keep_factors=True - its 'values', 'reasons' (the mask),
+        'factors' and 'factor_names' are read - through `analysis.corridor_drivers`: per channel, node and factor the
+        correlation and the standardised regression coefficient over the flights that pass the outlier filter and are still
+        defined at that node, with 'share', 'ranking' and 'lead'.  Without factors: a ValueError that names keep_factors=True."""
+        from . import analysis as ana
+        if "factors" not in captured or "factor_names" not in captured:
+            raise ValueError("the captured run carries no factors: fly it with keep_factors=True")
+        t = np.asarray(captured["time"], dtype=np.float64)
+        out = ana.corridor_drivers(captured["values"], captured["factors"], captured["factor_names"],
+                                   channels=list(captured["channels"]), t0=float(t[0]) if len(t) else 0.0,
+                                   dt=float(t[1] - t[0]) if len(t) > 1 else 1.0, mask=captured["reasons"],
+                                   engine=shared_engine(self.device), regression=regression)
+        if "fragments" in captured:   # the rows of a debris matrix are (node, fragment) pairs: every time once per fragment
+            out["fragments"] = captured["fragments"]
+            out["time"] = np.repeat(t, len(captured["fragments"]))
+        return out
+
+    def plot_corridor_drivers(self, drivers, save_plots=True, top=4):
+        """No reference counterpart: the result of `corridor_drivers` - per channel the signed correlation of the `top` factors
+        over time and under it their stacked shares with r2 as the outline - as monte_carlo_corridor_drivers.png in the output
+        directory (with save_plots); returns the figure."""
+        return plots.plot_corridor_drivers(self, drivers, save_plots, top)
 
     def casualty_expectation(self, footprint, population, ranges, fragments, p_fail=None, failure_rate=None, ke_min=15.0,
                              smooth=True, bw_scale=1.0, h_floor=1.0, levels=(1e-6, 1e-5)):

@@ -282,6 +282,45 @@ def corridor_figure(result):
     return fig
 
 
+def corridor_drivers_figure(result, top=4):
+    """Which dispersion drives what, and when, from the dict of analysis.corridor_drivers: per channel two panels over time -
+    the signed correlation of the `top` factors of the channel's ranking, and under it their stacked linear variance shares
+    (pearson^2, the remaining factors as 'others') with r2 of the standardised regression as the outline.  A node without a
+    number leaves a gap."""
+    names = list(result["channels"])
+    t = np.arange(len(result["time"]), dtype=np.float64) if "fragments" in result else np.asarray(result["time"], dtype=np.float64)
+    pearson = np.asarray(result["pearson"], dtype=np.float64)
+    share = np.nan_to_num(np.asarray(result["share"], dtype=np.float64), nan=0.0)
+    r2 = np.asarray(result["r2"], dtype=np.float64)
+    factor_names = list(result["factor_names"])
+    fig = _figure((10, 4.4 * len(names) + 0.6))
+    axes = np.atleast_2d(fig.subplots(2 * len(names), 1, sharex=True).reshape(len(names), 2)) if len(names) else []
+    for c, name in enumerate(names):
+        ax, bx = axes[c]
+        lead = [factor_names.index(n) for n in result["ranking"][c][:max(1, int(top))]]
+        for f in lead:
+            ax.plot(t, pearson[c, :, f], linewidth=1.3, label=factor_names[f])
+        ax.axhline(0.0, color="gray", linewidth=0.6)
+        ax.set_ylim(-1.05, 1.05)
+        ax.set_ylabel(f"{CORRIDOR_LABELS.get(name, name)}\ncorrelation")
+        ax.grid(True, alpha=0.3)
+        ax.legend(loc="best", fontsize=7, ncol=2)
+        rest = [f for f in range(len(factor_names)) if f not in lead]
+        stacks = [share[c, :, f] for f in lead] + ([share[c][:, rest].sum(axis=1)] if rest else [])
+        bx.stackplot(t, *stacks, labels=[factor_names[f] for f in lead] + (["others"] if rest else []), alpha=0.7)
+        if np.any(np.isfinite(r2[c])):
+            bx.plot(t, r2[c], color="black", linewidth=1.2, label="r2")
+        bx.set_ylabel("variance share")
+        bx.set_ylim(bottom=0.0)
+        bx.grid(True, alpha=0.3)
+    if len(names):
+        axes[0][0].set_title(f"Corridor Drivers ({int(result.get('n_base', 0))} samples)")
+        axes[-1][1].legend(loc="best", fontsize=7, ncol=2)
+        axes[-1][1].set_xlabel("Row (node, fragment)" if "fragments" in result else "Time (s)")
+    fig.tight_layout()
+    return fig
+
+
 def impact_point_figure(result):
     """The IIP trace from the dict of MonteCarloAnalyzer.impact_point_trace: the IIP range over the time of termination
     (the median - the quantile nearest 0.5 - and the outer and inner quantile bands), the ground track of the median IIP
@@ -921,6 +960,16 @@ def plot_trajectory_corridor(analyzer, corridor, save_plots=True):
         output_dir = analyzer._create_output_directory()
         print(f"Trajectory corridor plot saved to: {save_figure(fig, output_dir, 'monte_carlo_corridor.png')}")
     return output_dir
+
+
+def plot_corridor_drivers(analyzer, drivers, save_plots=True, top=4):
+    """The drivers of MonteCarloAnalyzer.corridor_drivers (no reference counterpart) as monte_carlo_corridor_drivers.png with
+    save_plots; returns the figure."""
+    fig = corridor_drivers_figure(drivers, top)
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Corridor drivers plot saved to: {save_figure(fig, output_dir, 'monte_carlo_corridor_drivers.png')}")
+    return fig
 
 
 def plot_impact_point_trace(analyzer, trace, save_plots=True):

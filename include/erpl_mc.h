@@ -2115,6 +2115,77 @@ int erpl_mc_impact_density_weighted(erpl_ctx* ctx, const double* summary, const 
                                     int64_t n, const erpl_density_spec* spec, double* grid_x, double* grid_y,
                                     double* density, erpl_density_w* result, double* sample_density, void* hip_stream);
 
+/* Which dispersion drives what, AND WHEN (erpl_mc_corridor_drivers): for every row of a time-resolved matrix - the corridor
+ * [C][T][ld] of erpl_mc_corridor_resample, the instantaneous-impact-point matrix of erpl_mc_impact_points, the debris matrix of
+ * erpl_mc_debris, passed as it is with n_rows = channels x nodes, no copy - and every per-sample factor, the Pearson
+ * correlation and the standardised regression coefficient over THAT ROW'S OWN population: the flights still defined at the
+ * node.  erpl_mc_correlation answers the same question for summary rows over one common population.
+ * Conventions of erpl_mc_corridor_bands and erpl_mc_correlation: `factors` is [n_factors][ldf], `values` [n_rows][ld], `mask`
+ * uint8 [m] or NULL (a column counts iff its byte is 0, NULL = every column), all caller-owned device memory of which only
+ * the first m columns are read (the padding may hold anything); spec, result, rows ([n_rows]), pearson ([n_rows][n_factors])
+ * and src (the same shape, or NULL) are host memory.  The work is enqueued on `hip_stream` behind what is there and the call
+ * returns when the result is filled; the workspace belongs to the context, grows only and is freed by erpl_mc_destroy.
+ * ERPL_ERR_INVALID, before any device work and with a message that names the argument, in THIS order: a NULL spec, factors,
+ * values, result, rows, pearson; m <= 0 or m >= 2^31; ld < m; ldf < m; n_factors outside 1..32; n_rows outside
+ * 1..ERPL_CDRV_MAX_ROWS; regression not 0 or 1; src given with regression = 0 or missing with regression = 1; the context is
+ * checked last.
+ *
+ * Populations.  Base population P0: mask byte 0 AND every factor finite.  n_masked counts the non-zero mask bytes,
+ * n_factor_non_finite the columns with mask byte 0 and some factor that is not finite: n_base + n_masked +
+ * n_factor_non_finite == m.  Per factor over P0: mean = sum / n_base, std = sqrt(sum (x - mean)^2 / n_base) from a centred
+ * second pass, min / max exact, constant = (min == max); n_base == 0: every double NaN, constant 0.
+ * Population of row r: P_r = P0 and values[r][i] finite.  rows[r]: count = |P_r| and mean, std (as above, divided by count),
+ * min, max, constant of the row over P_r (count == 0: NaN, constant 0; count == 1: constant 1).
+ * Pearson: pearson[r][f] = S_xy / (sqrt(S_xx) sqrt(S_yy)), S the centred cross-product sums over P_r - the factor is centred
+ * over P_r, not over P0.  NaN where count < 2, where the row is constant over P_r or where the factor is (its exact min ==
+ * max over P_r; -0.0 == +0.0).
+ * Regression (regression = 1; on the host, erpl_mc_correlation's routine): over the factors that are not constant on P_r,
+ * R_ff(r) beta = r_fy(r) by Cholesky, R_ff(r) the factor correlation matrix over P_r; src[r][f] = beta_f (NaN for a factor
+ * constant on P_r), r2 = sum beta_f r_fy, pivot_min the smallest pivot met (the failing one included; NaN when no factor is in
+ * use).  A pivot below 1e-10 or not finite: regression_ok = 0 for that row alone, its src and r2 NaN, its pearson stays - a row
+ * with count <= the number of factors therefore fails by itself.  count < 2: regression_ok = 0, pivot_min NaN.  A constant row
+ * has src and r2 NaN and the regression_ok of its factors.  regression = 0: src must be NULL, r2 / pivot_min NaN,
+ * regression_ok 0.
+ * Sums.  Pass 0 writes the base byte of every column and the P0 statistics of the factors; pass 1 count, mean, std, min, max of
+ * every row; with x' = (x - mean_P0) / std_P0 (0 for a factor constant on P0), y' = (y - mean_r) / std_r (0 for a constant
+ * row) and m_r the 0/1 membership of P_r, the product pass forms per row sum m_r x'_f, sum m_r x'_f^2, sum m_r y' x'_f,
+ * sum m_r y', sum m_r y'^2 and, with regression = 1, sum m_r x'_f x'_g for f < g: one streaming rectangular product in fp64
+ * on the matrix cores, the standardisation, the masking and the products formed on the way into the operands, never in
+ * device memory.  The host recovers S_ab = sum a b - (sum a)(sum b) / count.  Where those sums do not prove a factor
+ * non-constant over P_r (S_xx <= 1e-6 sum x'^2), a last pass takes its exact extremes over P_r.
+ * m is cut into segments (moments) and slices (products) that are functions of m alone, the partials of a row are folded in
+ * slice order, no floating-point atomics, every loop bounded: two calls on the same input return the same bytes, and a row's
+ * results do not depend on which other rows are in the call.
+ * Not here: rank (Spearman) correlation - a factor's ranks within P_r differ from row to row, which is another kernel. */
+#define ERPL_CDRV_MAX_FACTORS 32        /* = ERPL_CORR_MAX_FACTORS */
+#define ERPL_CDRV_MAX_ROWS 32768        /* 8 channels x 4096 nodes */
+
+typedef struct erpl_cdrv_spec {
+  int32_t n_factors;                    /* 1..32 */
+  int32_t n_rows;                       /* 1..ERPL_CDRV_MAX_ROWS */
+  int32_t regression;                   /* 0: pearson only; 1: also src, r2 */
+  int32_t reserved;
+} erpl_cdrv_spec;
+
+typedef struct erpl_cdrv_result {
+  int64_t m, n_base, n_masked, n_factor_non_finite;
+  int32_t constant[ERPL_CDRV_MAX_FACTORS];   /* factor f: min == max over P0 */
+  double mean[ERPL_CDRV_MAX_FACTORS], std[ERPL_CDRV_MAX_FACTORS], min[ERPL_CDRV_MAX_FACTORS], max[ERPL_CDRV_MAX_FACTORS];
+} erpl_cdrv_result;
+
+typedef struct erpl_cdrv_row {
+  int64_t count;                        /* |P_r| */
+  double mean, std, min, max;           /* of the row over P_r */
+  double r2, pivot_min;
+  int32_t constant, regression_ok;
+} erpl_cdrv_row;
+
+/* Host only: regression = 1, n_factors = n_rows = 0 (the caller fills them in). */
+int erpl_mc_corridor_drivers_defaults(erpl_cdrv_spec* spec);
+int erpl_mc_corridor_drivers(erpl_ctx* ctx, const double* factors, int64_t ldf, const double* values, int64_t ld,
+                             const uint8_t* mask, int64_t m, const erpl_cdrv_spec* spec, erpl_cdrv_result* result,
+                             erpl_cdrv_row* rows, double* pearson, double* src, void* hip_stream);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
