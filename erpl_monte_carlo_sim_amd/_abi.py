@@ -306,6 +306,30 @@ class ErplCdrvRow(C.Structure):
                 ("r2", C.c_double), ("pivot_min", C.c_double), ("constant", C.c_int32), ("regression_ok", C.c_int32)]
 
 
+# erpl_mc_corridor_depth
+DEPTH_MAX_CHANNELS = 8
+DEPTH_MAX_NODES = 4096
+DEPTH_LDS_MAX = 16384
+
+_DP_I = C.c_int64 * DEPTH_MAX_CHANNELS
+_DP_D = C.c_double * DEPTH_MAX_CHANNELS
+
+
+class ErplDepthSpec(C.Structure):
+    _fields_ = [("n_channels", C.c_int32), ("n_nodes", C.c_int32), ("central", C.c_double), ("factor", C.c_double),
+                ("lds_limit", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ErplDepthRow(C.Structure):
+    _fields_ = [("count", C.c_int64), ("n_central_here", C.c_int64), ("central_lo", C.c_double), ("central_hi", C.c_double),
+                ("fence_lo", C.c_double), ("fence_hi", C.c_double), ("whisker_lo", C.c_double), ("whisker_hi", C.c_double)]
+
+
+class ErplDepthResult(C.Structure):
+    _fields_ = [("m", C.c_int64), ("n_masked", C.c_int64), ("n_defined", _DP_I), ("n_central", _DP_I), ("n_outliers", _DP_I),
+                ("median", _DP_I), ("threshold", _DP_D), ("depth_max", _DP_D)]
+
+
 # erpl_mc_impact_points: channels of the values [IIP_CH_COUNT][n_nodes][ld], rows of the summary [IIP_DIM][n_traj]
 IIP_DIM = 16
 IIP_MAX_NODES = 4096
@@ -653,7 +677,8 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_subset_commit", "erpl_mc_subset_commit_host", "erpl_mc_subset_chain_stats", "erpl_mc_subset_chain_stats_host",
            "erpl_mc_reweight_defaults", "erpl_mc_reweight", "erpl_mc_reweight_host",
            "erpl_mc_casualty_defaults", "erpl_mc_casualty",
-           "erpl_mc_corridor_drivers_defaults", "erpl_mc_corridor_drivers")
+           "erpl_mc_corridor_drivers_defaults", "erpl_mc_corridor_drivers",
+           "erpl_mc_corridor_depth_defaults", "erpl_mc_corridor_depth")
 
 _lib = None
 
@@ -821,6 +846,10 @@ def load_library(path=None):
     lib.erpl_mc_corridor_drivers.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.POINTER(ErplCdrvSpec), C.POINTER(ErplCdrvResult), C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p]
+    lib.erpl_mc_corridor_depth_defaults.argtypes = [C.POINTER(ErplDepthSpec)]
+    # ctx, values, ld, mask, m, spec, result, rows, depth, mei, nodes, n_out, first_out, central, hip_stream
+    lib.erpl_mc_corridor_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(ErplDepthSpec),
+                                           C.POINTER(ErplDepthResult)] + [C.c_void_p] * 8
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if a declared symbol is not exported
         if name not in ("erpl_mc_last_error",):

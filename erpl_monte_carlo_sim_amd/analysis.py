@@ -456,6 +456,75 @@ def corridor_drivers(values, factors, factor_names, channels=None, t0=0.0, dt=1.
     return out
 
 
+def outliergram(depth, mei, n):
+    """The shape outliers of Arribas-Gil & Romo (2014) from the modified band depth and the modified epigraph index of curves
+    that share one population of n at every node: a curve that crosses no other lies ON the parabola
+    depth = a0 + a1 mei + a2 n^2 mei^2 with a0 = a2 = -2 / (n (n - 1)) and a1 = 2 (n + 1) / (n - 1), a curve that crosses many
+    lies below it.  Returns (d, flags): d = the parabola minus depth (NaN where depth or mei is), flags = d > Q3 + 1.5 IQR over
+    the finite distances - and d > 1e-13, so that the rounding of curves that cross nothing (|d| of a few 1e-15) flags none."""
+    depth, mei = np.asarray(depth, dtype=np.float64), np.asarray(mei, dtype=np.float64)
+    n = float(n)
+    if n < 2:
+        return np.full(depth.shape, np.nan), np.zeros(depth.shape, dtype=bool)
+    a0 = a2 = -2.0 / (n * (n - 1.0))
+    a1 = 2.0 * (n + 1.0) / (n - 1.0)
+    d = a0 + a1 * mei + a2 * n * n * mei * mei - depth
+    ok = np.isfinite(d)
+    if not ok.any():
+        return d, np.zeros(depth.shape, dtype=bool)
+    q1, q3 = np.quantile(d[ok], (0.25, 0.75))
+    with np.errstate(invalid="ignore"):
+        return d, ok & (d > q3 + 1.5 * (q3 - q1)) & (d > 1e-13)
+
+
+def trajectory_depth(values, channels=None, t0=0.0, dt=1.0, mask=None, engine=None, central=0.5, factor=1.5, m=None, lds_limit=0):
+    """Which flown trajectory is the typical one and which flights are unusual as curves: the modified band depth, the
+    functional boxplot and the outliergram of a time-resolved matrix (float64 [C, T, ld] on the device - the corridor of
+    TrajectoryEngine.corridor_resample, the matrix of `impact_points` or of `debris`) over the columns whose `mask` byte is 0,
+    by one erpl_mc_corridor_depth call per matrix.  channels: the names of the C channels (default 'channel 0' ..).
+    Returns a dict: 'time' [T] (t0 + k dt), 'channels', 'central_share', 'factor', 'n_masked', 'warnings' and per channel name
+    {'depth', 'mei' [m] (NumPy), 'nodes' [m], 'median' (the deepest column, -1 if none), 'median_curve' [T] (that column of
+    the matrix), 'central', 'fence', 'whisker' (each {'lo', 'hi'} [T]), 'count' [T], 'n_defined', 'n_central',
+    'magnitude_outliers' (the columns that leave the fences: a list of {'column', 'first_node', 'nodes'}), 'shape_outliers'
+    (the columns the outliergram flags, with 'outliergram_distance' [m]) - the outliergram needs one population at every
+    counted node of the channel (a matrix resampled with hold=True over flights that ran to their end); where the populations
+    differ 'shape_outliers' is None and 'warnings' says so}."""
+    engine = _engine_of(values, engine)
+    if values.dim() != 3:
+        raise ValueError("values must be a [C, T, ld] matrix")
+    n_ch, n_nodes = int(values.shape[0]), int(values.shape[1])
+    channels = [f"channel {c}" for c in range(n_ch)] if channels is None else \
+        [CORRIDOR_CHANNEL_NAMES[c] if not isinstance(c, str) else c for c in channels]
+    if len(channels) != n_ch:
+        raise ValueError(f"{len(channels)} channels for a matrix of {n_ch}")
+    r = engine.corridor_depth(values, mask=mask, m=m, central=central, factor=factor, lds_limit=lds_limit)
+    out = {"time": float(t0) + np.arange(n_nodes, dtype=np.float64) * float(dt), "channels": channels,
+           "central_share": float(central), "factor": float(factor), "n_masked": r["n_masked"], "warnings": []}
+    cols = {k: r[k].cpu().numpy() for k in ("depth", "mei", "nodes", "n_out", "first_out")}
+    for c, name in enumerate(channels):
+        med = int(r["median"][c])
+        ch = {"depth": cols["depth"][c], "mei": cols["mei"][c], "nodes": cols["nodes"][c], "median": med,
+              "median_curve": values[c, :, med].cpu().numpy() if med >= 0 else np.full(n_nodes, np.nan),
+              "central": {"lo": r["central_lo"][c], "hi": r["central_hi"][c]},
+              "fence": {"lo": r["fence_lo"][c], "hi": r["fence_hi"][c]},
+              "whisker": {"lo": r["whisker_lo"][c], "hi": r["whisker_hi"][c]},
+              "count": r["count"][c], "n_defined": int(r["n_defined"][c]), "n_central": int(r["n_central"][c]),
+              "threshold": float(r["threshold"][c])}
+        defined = cols["nodes"][c] > 0
+        ch["magnitude_outliers"] = [{"column": int(j), "first_node": int(cols["first_out"][c][j]), "nodes": int(cols["n_out"][c][j])}
+                                    for j in np.flatnonzero(defined & (cols["n_out"][c] > 0))]
+        counted = r["count"][c][r["count"][c] >= 2]
+        same = len(counted) > 0 and np.all(counted == counted[0]) and np.all(cols["nodes"][c][defined] == len(counted))
+        if same:
+            d, flags = outliergram(np.where(defined, ch["depth"], np.nan), ch["mei"], int(counted[0]))
+            ch["outliergram_distance"], ch["shape_outliers"] = d, [int(j) for j in np.flatnonzero(flags)]
+        else:
+            ch["outliergram_distance"], ch["shape_outliers"] = None, None
+            out["warnings"].append(f"{name}: the populations of the nodes differ, no outliergram (resample with hold=True)")
+        out[name] = ch
+    return out
+
+
 # ---------------------------------------------------------------------------------- drivers: which dispersion drives what
 ROW_NAMES = ("apogee_altitude", "apogee_time", "first_apogee_altitude", "first_apogee_time", "range", "flight_time",
              "rail_exit_time", "rail_exit_speed", "impact_x", "impact_y", "impact_z", "n_steps",

@@ -479,6 +479,7 @@ int erpl_mc_destroy(erpl_ctx* c) {
   c->reweight.release();
   c->casualty.release();
   c->cdrv.release();
+  c->depth.release();
   if (c->reweight_pin) (void)hipHostFree(c->reweight_pin);
   delete c;
   return ERPL_OK;

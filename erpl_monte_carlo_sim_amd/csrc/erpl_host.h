@@ -278,6 +278,8 @@ struct erpl_ctx {
   // erpl_mc_corridor_drivers: the pieces of erpl_cdrv_layout (erpl_stat_layout.h) in the buffer; what comes back is caller-sized
   // and needs no pinned mirror
   ErplStatUnit<void, char> cdrv;
+  // erpl_mc_corridor_depth: the pieces of erpl_depth_layout (erpl_depth.h) in the buffer; what comes back is small or caller-sized
+  ErplStatUnit<void, char> depth;
 };
 
 // erpl_design.hip

@@ -1,6 +1,6 @@
 // erpl_stat_device.h — what the statistics units (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip,
 // erpl_bootstrap.hip, erpl_density.hip, erpl_corridor.hip, erpl_sobol.hip, erpl_dependence.hip, erpl_compare.hip,
-// erpl_reweight.hip, erpl_density_w.hip) share:
+// erpl_reweight.hip, erpl_density_w.hip, erpl_corridor_depth.hip) share:
 // the grid of their streaming passes, the order-preserving keys, the run of equal keys behind a mid-rank, THE fixed-order
 // reduction and the steps of the radix selection.
 // Internal: never installed.

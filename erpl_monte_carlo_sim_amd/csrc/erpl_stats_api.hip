@@ -1,9 +1,9 @@
 // erpl_stats_api.hip — host halves of the analysis entry points of the C ABI (include/erpl_mc.h): erpl_mc_analyze,
 // erpl_mc_histogram, erpl_mc_histogram_xy, erpl_mc_dispersion, erpl_mc_correlation, erpl_mc_bootstrap, erpl_mc_impact_density,
 // erpl_mc_impact_density_weighted,
-// erpl_mc_corridor_resample, erpl_mc_corridor_bands, erpl_mc_sobol, erpl_mc_dependence, erpl_mc_compare and their defaults.
+// erpl_mc_corridor_resample, erpl_mc_corridor_bands, erpl_mc_corridor_depth, erpl_mc_sobol, erpl_mc_dependence, erpl_mc_compare and their defaults.
 // Argument checks, workspace, launches (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip, erpl_bootstrap.hip,
-// erpl_density.hip, erpl_density_w.hip, erpl_corridor.hip, erpl_sobol.hip, erpl_dependence.hip, erpl_compare.hip)
+// erpl_density.hip, erpl_density_w.hip, erpl_corridor.hip, erpl_corridor_depth.hip, erpl_sobol.hip, erpl_dependence.hip, erpl_compare.hip)
 // and what the host finishes in double precision.  The refusals come in one order
 // everywhere - spec fields, n, pointers, context (erpl_mc_bootstrap: the order its header comment lists) - and need no
 // device; tests/golden/stats_refusals.json pins their texts.  What the entry points share comes first: the pieces of the
@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "erpl_cdrv.h"
+#include "erpl_depth.h"
 #include "erpl_host.h"
 #include "erpl_philox.h"
 #include "erpl_reweight.h"
@@ -1157,6 +1158,70 @@ int erpl_mc_corridor_bands(erpl_ctx* c, const double* values, const uint8_t* mas
   HIP_TRY(hipStreamSynchronize(st));
   for (int r = 0; r < rows; ++r) finish_row_stats(h[(size_t)r], spec->q, spec->n_q, true, bands[r]);
   if (n_counted) *n_counted = (int64_t)h[(size_t)rows].count;
+  return ERPL_OK;
+}
+
+// ------------------------------------------------- erpl_mc_corridor_depth
+int erpl_mc_corridor_depth_defaults(erpl_depth_spec* spec) {
+  NEED(spec);
+  memset(spec, 0, sizeof(*spec));
+  spec->central = 0.5;
+  spec->factor = 1.5;
+  return ERPL_OK;
+}
+
+int erpl_mc_corridor_depth(erpl_ctx* c, const double* values, int64_t ld, const uint8_t* mask, int64_t m, const erpl_depth_spec* spec,
+                           erpl_depth_result* result, erpl_depth_row* rows, double* depth, double* mei, int32_t* nodes, int32_t* n_out,
+                           int32_t* first_out, uint8_t* central, void* stream) {
+  NEED(spec); NEED(values); NEED(result); NEED(rows); NEED(depth); NEED(mei); NEED(nodes); NEED(n_out); NEED(first_out); NEED(central);
+  if (m <= 0 || m > 2147483647LL) return erpl_fail(ERPL_ERR_INVALID, "m = %lld outside 1..2^31 - 1", (long long)m);
+  if (ld < m) return erpl_fail(ERPL_ERR_INVALID, "ld = %lld is below m = %lld", (long long)ld, (long long)m);
+  ERPL_TRY(check_int(spec->n_channels, "n_channels", -1, 1, ERPL_DEPTH_MAX_CHANNELS));
+  ERPL_TRY(check_int(spec->n_nodes, "n_nodes", -1, 1, ERPL_DEPTH_MAX_NODES));
+  if (!(spec->central > 0.0 && spec->central <= 1.0)) return erpl_fail(ERPL_ERR_INVALID, "spec->central = %g outside (0, 1]", spec->central);
+  if (!(spec->factor >= 0.0 && std::isfinite(spec->factor)))
+    return erpl_fail(ERPL_ERR_INVALID, "spec->factor = %g: finite and >= 0", spec->factor);
+  if (spec->lds_limit < 0) return erpl_fail(ERPL_ERR_INVALID, "spec->lds_limit = %d is negative", spec->lds_limit);
+  NEED_AS(c, "ctx");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int C = spec->n_channels, T = spec->n_nodes;
+
+  const ErplDepthLayout sizing = erpl_depth_layout(m, C, T, spec->lds_limit, 0);
+  size_t temp_bytes = 0;
+  LAUNCH_TRY(erpl_depth_temp_bytes(m, sizing.group, &temp_bytes), "sizing the sorts failed");
+  const ErplDepthLayout at = erpl_depth_layout(m, C, T, spec->lds_limit, temp_bytes);
+  ERPL_TRY(c->depth.grow(at.need));
+  char* buf = c->depth.buf;
+  ErplDepthArgs a;
+  memset(&a, 0, sizeof(a));
+  a.values = values; a.mask = mask; a.m = m; a.ld = ld; a.n_channels = C; a.n_nodes = T;
+  a.central = spec->central; a.factor = spec->factor;
+  a.depth = depth; a.mei = mei; a.nodes = nodes; a.n_out = n_out; a.first_out = first_out; a.central_flag = central;
+  a.pair = (uint32_t*)(buf + at.pair); a.rown = (int32_t*)(buf + at.rown); a.keys = (unsigned long long*)(buf + at.keys);
+  a.offs = (uint32_t*)(buf + at.offs); a.temp = buf + at.temp; a.temp_bytes = temp_bytes;
+  a.chan = (ErplDepthChan*)(buf + at.chan); a.rows = (erpl_depth_row*)(buf + at.rows);
+  a.count = (unsigned long long*)(buf + at.count);
+  a.group = at.group; a.lds = at.lds ? 1 : 0;
+  KERNEL_TRY(erpl_launch_depth(a, stream));
+  ErplDepthChan chan[ERPL_DEPTH_MAX_CHANNELS];
+  unsigned long long masked = 0ull;
+  HIP_TRY(hipMemcpyAsync(chan, a.chan, (size_t)C * sizeof(ErplDepthChan), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(rows, a.rows, (size_t)C * T * sizeof(erpl_depth_row), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&masked, a.count, sizeof(masked), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  memset(result, 0, sizeof(*result));
+  result->m = m;
+  result->n_masked = (int64_t)masked;
+  for (int k = 0; k < ERPL_DEPTH_MAX_CHANNELS; ++k) {
+    const bool in = k < C;
+    result->n_defined[k] = in ? chan[k].n_defined : 0;
+    result->n_central[k] = in ? chan[k].n_central : 0;
+    result->n_outliers[k] = in ? (int64_t)chan[k].n_outliers : 0;
+    result->median[k] = in ? chan[k].median : -1;
+    result->threshold[k] = in ? chan[k].threshold : (double)NAN;
+    result->depth_max[k] = in ? chan[k].depth_max : (double)NAN;
+  }
   return ERPL_OK;
 }
 

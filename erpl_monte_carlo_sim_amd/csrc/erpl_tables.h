@@ -563,6 +563,43 @@ int erpl_launch_corridor_resample(const ErplCorridorResampleArgs& a, void* strea
 int erpl_launch_corridor_bands(const ErplCorridorBandsArgs& a, void* stream);
 }
 
+// ---- erpl_mc_corridor_depth (erpl_corridor_depth.hip) ----
+// What the passes leave per channel, and everything the launches need: the caller's arrays and the pieces of erpl_depth_layout
+// (erpl_depth.h) in the context's buffer.
+struct ErplDepthChan {         // 64 bytes
+  int64_t n_defined, n_central;
+  unsigned long long n_outliers;
+  int64_t median;
+  double threshold, depth_max;
+  int64_t spare[2];
+};
+struct ErplDepthArgs {
+  const double* values;      // [n_channels][n_nodes][ld]
+  const uint8_t* mask;       // [m] or NULL
+  int64_t m, ld;
+  int32_t n_channels, n_nodes;
+  double central, factor;
+  double *depth, *mei;       // the caller's [n_channels][m] arrays
+  int32_t *nodes, *n_out, *first_out;
+  uint8_t* central_flag;
+  uint32_t* pair;            // [n_nodes][m][2]
+  int32_t* rown;             // [n_nodes]
+  unsigned long long* keys;  // [2][max(group, 1)][m]
+  uint32_t* offs;            // [group + 1]
+  void* temp;
+  size_t temp_bytes;
+  ErplDepthChan* chan;       // [n_channels]
+  erpl_depth_row* rows;      // [n_channels n_nodes]
+  unsigned long long* count; // [4]
+  int32_t group, lds;        // erpl_depth_layout's
+};
+extern "C++" {
+// the scratch the sorts of a call over m columns need, with `group` rows per group of the global path (0: the LDS path)
+int erpl_depth_temp_bytes(int64_t m, int group, size_t* bytes);
+// enqueues every pass on `stream` and returns a hipError_t (0 = launched)
+int erpl_launch_depth(const ErplDepthArgs& a, void* stream);
+}
+
 // ---- erpl_mc_sobol (erpl_sobol.hip) ----
 // Prepare compacts the population of every requested row into RECORDS: rec[r][d][0 .. k + 1] = the k + 2 block values
 // (A, B, AB_0 .. AB_k-1) of dense member d of row r, contiguous.  A draw of the replicate kernel is then one contiguous

@@ -647,6 +647,58 @@ class TrajectoryEngine:
             out["factor_" + k] = np.array(getattr(res, k)[:F], dtype=np.float64)
         return out
 
+    def corridor_depth(self, values, mask=None, m=None, central=0.5, factor=1.5, lds_limit=0):
+        """Band depth and the functional boxplot of a time-resolved matrix (erpl_mc_corridor_depth; the definitions are in
+        include/erpl_mc.h): values float64 [C, T, ld] on the device - a corridor, an impact-point or a debris matrix as it is -
+        of which the first m columns are read (default: ld); mask uint8 [m] on the device, a column counts iff its byte is 0.
+        Enqueued on the current torch stream; blocks the host until the result is there.  Returns a dict: NumPy row arrays
+        [C, T] 'count', 'n_central_here' int64 and 'central_lo', 'central_hi', 'fence_lo', 'fence_hi', 'whisker_lo',
+        'whisker_hi' float64; per channel [C] 'n_defined', 'n_central', 'n_outliers', 'median' int64 and 'threshold',
+        'depth_max' float64; 'm', 'n_masked'; and the per-column arrays as DEVICE tensors [C, m]: 'depth', 'mei' float64,
+        'nodes', 'n_out', 'first_out' int32, 'central' uint8."""
+        if not (torch.is_tensor(values) and values.is_cuda and values.device == self.device and values.dtype == torch.float64
+                and values.is_contiguous() and values.dim() == 3):
+            raise ValueError(f"values must be a contiguous float64 [C, T, ld] tensor on {self.device}")
+        Cn, T, ld = (int(s) for s in values.shape)
+        m = ld if m is None else int(m)
+        if not 1 <= Cn <= _abi.DEPTH_MAX_CHANNELS:
+            raise ValueError(f"1 to {_abi.DEPTH_MAX_CHANNELS} channels")
+        if not 1 <= T <= _abi.DEPTH_MAX_NODES:
+            raise ValueError(f"1 to {_abi.DEPTH_MAX_NODES} nodes")
+        if not 1 <= m <= ld:
+            raise ValueError(f"m = {m} outside 1..{ld}")
+        if mask is not None and not (torch.is_tensor(mask) and mask.device == self.device and mask.dtype == torch.uint8
+                                     and tuple(mask.shape) == (m,) and mask.is_contiguous()):
+            raise ValueError(f"mask must be a contiguous uint8 [m] tensor on {self.device}")
+        spec = self._defaults(_abi.ErplDepthSpec, "erpl_mc_corridor_depth_defaults")
+        spec.n_channels, spec.n_nodes, spec.central, spec.factor, spec.lds_limit = Cn, T, float(central), float(factor), int(lds_limit)
+        res = _abi.ErplDepthResult()
+        rows = (_abi.ErplDepthRow * (Cn * T))()
+        cols = {"depth": torch.empty((Cn, m), dtype=torch.float64, device=self.device),
+                "mei": torch.empty((Cn, m), dtype=torch.float64, device=self.device),
+                "nodes": torch.empty((Cn, m), dtype=torch.int32, device=self.device),
+                "n_out": torch.empty((Cn, m), dtype=torch.int32, device=self.device),
+                "first_out": torch.empty((Cn, m), dtype=torch.int32, device=self.device),
+                "central": torch.empty((Cn, m), dtype=torch.uint8, device=self.device)}
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_corridor_depth", C.c_void_p(values.data_ptr()), ld,
+                   C.c_void_p(mask.data_ptr()) if mask is not None else None, m, C.byref(spec), C.byref(res),
+                   C.cast(rows, C.c_void_p), *(C.c_void_p(cols[k].data_ptr()) for k in ("depth", "mei", "nodes", "n_out", "first_out",
+                                                                                         "central")), C.c_void_p(st.cuda_stream))
+        # erpl_depth_row is 8 eight-byte words: count, n_central_here, then the six doubles
+        raw = np.frombuffer(rows, dtype=np.float64).reshape(Cn, T, 8)
+        ints = np.frombuffer(rows, dtype=np.int64).reshape(Cn, T, 8)
+        out = {"count": ints[:, :, 0].copy(), "n_central_here": ints[:, :, 1].copy()}
+        for k, name in enumerate(("central_lo", "central_hi", "fence_lo", "fence_hi", "whisker_lo", "whisker_hi")):
+            out[name] = raw[:, :, 2 + k].copy()
+        for name in ("n_defined", "n_central", "n_outliers", "median"):
+            out[name] = np.array(getattr(res, name)[:Cn], dtype=np.int64)
+        for name in ("threshold", "depth_max"):
+            out[name] = np.array(getattr(res, name)[:Cn], dtype=np.float64)
+        out.update({"m": int(res.m), "n_masked": int(res.n_masked)})
+        out.update(cols)
+        return out
+
     def analysis_defaults(self):
         """The reference's outlier bounds, rows and quantiles (erpl_mc_analysis_defaults)."""
         return self._defaults(_abi.ErplAnalysisSpec, "erpl_mc_analysis_defaults")

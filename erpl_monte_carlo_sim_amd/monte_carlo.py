@@ -1025,6 +1025,31 @@ class MonteCarloAnalyzer:
         directory (with save_plots); returns the figure."""
         return plots.plot_corridor_drivers(self, drivers, save_plots, top)
 
+    def trajectory_depth(self, captured, central=0.5, factor=1.5):
+        """Which flown trajectory is the typical one, and which flights are unusual as curves (no reference counterpart;
+        analyze_outlier.py opens one flight by hand): the dict of `trajectory_corridor`, `impact_point_trace` or
+        `debris_footprint` - its 'values', 'reasons' (the mask), 'time' and 'channels' are read - through
+        `analysis.trajectory_depth`: per channel the band depth of every flight that passes the outlier filter, the deepest
+        flight ('median', with 'median_curve'), the envelope of the `central` share of the flights, its fences `factor` envelope
+        widths outside it, the flights that leave the fences and the flights the outliergram flags for their shape.  Columns
+        are sample indices of captured['summary']: the median flight and the outliers can be flown again."""
+        from . import analysis as ana
+        t = np.asarray(captured["time"], dtype=np.float64)
+        out = ana.trajectory_depth(captured["values"], channels=list(captured["channels"]), t0=float(t[0]) if len(t) else 0.0,
+                                   dt=float(t[1] - t[0]) if len(t) > 1 else 1.0, mask=captured["reasons"],
+                                   engine=shared_engine(self.device), central=central, factor=factor)
+        if "fragments" in captured:   # the rows of a debris matrix are (node, fragment) pairs: every time once per fragment
+            out["fragments"] = captured["fragments"]
+            out["time"] = np.repeat(t, len(captured["fragments"]))
+        return out
+
+    def plot_functional_boxplot(self, depth, values=None, save_plots=True, most=20):
+        """No reference counterpart: the result of `trajectory_depth` - per channel the central region as a band, the median
+        flight as a line, the whiskers and (with `values`, the matrix the depth was taken of) up to `most` outlying flights
+        drawn one by one - as monte_carlo_functional_boxplot.png in the output directory (with save_plots); returns the
+        figure."""
+        return plots.plot_functional_boxplot(self, depth, values, save_plots, most)
+
     def casualty_expectation(self, footprint, population, ranges, fragments, p_fail=None, failure_rate=None, ke_min=15.0,
                              smooth=True, bw_scale=1.0, h_floor=1.0, levels=(1e-6, 1e-5)):
         """The number a range signs (no reference counterpart): the casualty expectation Ec and the individual-risk map of

@@ -321,6 +321,43 @@ def corridor_drivers_figure(result, top=4):
     return fig
 
 
+def functional_boxplot_figure(result, values=None, most=20):
+    """The functional boxplot (Sun & Genton 2011) from the dict of analysis.trajectory_depth: per channel the central region
+    as a band, the median flight - a flight that was flown - as a line, the whiskers (the envelope of the flights that never
+    leave the fences) and, with `values` (the [C, T, ld] matrix the depth was taken of, a tensor or an array), up to `most`
+    of the magnitude outliers (red) and of the shape outliers (orange) drawn one by one."""
+    names = list(result["channels"])
+    t = np.arange(len(result["time"]), dtype=np.float64) if "fragments" in result else np.asarray(result["time"], dtype=np.float64)
+    fig = _figure((10, 3.4 * len(names) + 0.6))
+    axes = np.atleast_1d(fig.subplots(len(names), 1, sharex=True)) if len(names) else []
+    for c, name in enumerate(names):
+        ax, ch = axes[c], result[name]
+        ax.fill_between(t, ch["central"]["lo"], ch["central"]["hi"], color="tab:blue", alpha=0.35,
+                        label=f"central {100.0 * result['central_share']:.0f} %")
+        ax.plot(t, ch["whisker"]["lo"], color="tab:blue", linewidth=0.9, label="whiskers")
+        ax.plot(t, ch["whisker"]["hi"], color="tab:blue", linewidth=0.9)
+        drawn = 0
+        if values is not None:
+            for key, colour in (("magnitude_outliers", "tab:red"), ("shape_outliers", "tab:orange")):
+                cols = [o["column"] if isinstance(o, dict) else o for o in (ch[key] or [])][:max(0, int(most))]
+                for i, j in enumerate(cols):
+                    col = values[c, :, j]
+                    col = col.cpu().numpy() if hasattr(col, "cpu") else np.asarray(col)
+                    ax.plot(t, col, color=colour, linewidth=0.7, alpha=0.8, label=key.replace("_", " ") if i == 0 else None)
+                    drawn += 1
+        ax.plot(t, ch["median_curve"], color="black", linewidth=1.4, label=f"median flight (sample {ch['median']})")
+        ax.set_ylabel(CORRIDOR_LABELS.get(name, name))
+        ax.grid(True, alpha=0.3)
+        ax.legend(loc="best", fontsize=7, ncol=2)
+        ax.set_title(f"{name}: {ch['n_defined']} flights, {len(ch['magnitude_outliers'])} leave the fences, "
+                     f"{'no outliergram' if ch['shape_outliers'] is None else str(len(ch['shape_outliers'])) + ' shape outliers'}",
+                     fontsize=9)
+    if len(names):
+        axes[-1].set_xlabel("Row (node, fragment)" if "fragments" in result else "Time (s)")
+    fig.tight_layout()
+    return fig
+
+
 def impact_point_figure(result):
     """The IIP trace from the dict of MonteCarloAnalyzer.impact_point_trace: the IIP range over the time of termination
     (the median - the quantile nearest 0.5 - and the outer and inner quantile bands), the ground track of the median IIP
@@ -969,6 +1006,16 @@ def plot_corridor_drivers(analyzer, drivers, save_plots=True, top=4):
     if save_plots:
         output_dir = analyzer._create_output_directory()
         print(f"Corridor drivers plot saved to: {save_figure(fig, output_dir, 'monte_carlo_corridor_drivers.png')}")
+    return fig
+
+
+def plot_functional_boxplot(analyzer, depth, values=None, save_plots=True, most=20):
+    """The result of MonteCarloAnalyzer.trajectory_depth (no reference counterpart) as monte_carlo_functional_boxplot.png with
+    save_plots; returns the figure."""
+    fig = functional_boxplot_figure(depth, values, most)
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Functional boxplot saved to: {save_figure(fig, output_dir, 'monte_carlo_functional_boxplot.png')}")
     return fig
 
 

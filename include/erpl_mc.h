@@ -2186,6 +2186,90 @@ int erpl_mc_corridor_drivers(erpl_ctx* ctx, const double* factors, int64_t ldf, 
                              const uint8_t* mask, int64_t m, const erpl_cdrv_spec* spec, erpl_cdrv_result* result,
                              erpl_cdrv_row* rows, double* pearson, double* src, void* hip_stream);
 
+/* Which flown trajectory is the typical one, and which flights are unusual AS CURVES (erpl_mc_corridor_depth): the modified band
+ * depth of every column of a time-resolved matrix (Lopez-Pintado & Romo 2009, in the rank form of Sun, Genton & Nychka 2012),
+ * the modified epigraph index beside it (the second axis of the outliergram of Arribas-Gil & Romo 2014) and the functional
+ * boxplot (Sun & Genton 2011): the deepest flown column, the envelope of the central share of the columns, its fences, the
+ * columns that leave the fences and the whiskers of the rest.  The matrix is the corridor [C][T][ld] of
+ * erpl_mc_corridor_resample, the matrix of erpl_mc_impact_points or of erpl_mc_debris, passed as it is, no copy.
+ * Conventions of erpl_mc_corridor_bands and erpl_mc_corridor_drivers: row (c, k) is the m doubles at
+ * values + (c * n_nodes + k) * ld, `mask` is uint8 [m] or NULL (a column is counted iff its byte is 0, NULL = every column),
+ * both caller-owned device memory of which only the first m columns are read (the padding may hold anything).  depth, mei
+ * (double), nodes, n_out, first_out (int32) and central (uint8) are caller-owned DEVICE arrays [n_channels][m]; spec, result
+ * and rows ([n_channels * n_nodes], row (c, k) at c * n_nodes + k) are host memory.  The work is enqueued on `hip_stream`
+ * behind what is there and the call returns when result and rows are filled; the workspace belongs to the context, grows
+ * only and is freed by erpl_mc_destroy.
+ * ERPL_ERR_INVALID, before any device work and with a message that names the argument, in THIS order: a NULL spec, values,
+ * result, rows, depth, mei, nodes, n_out, first_out, central; m <= 0 or m >= 2^31; ld < m; n_channels outside 1..8; n_nodes
+ * outside 1..4096; central outside (0, 1] (NaN included); factor negative or not finite; lds_limit < 0; the context is
+ * checked last.
+ *
+ * Definitions, with C2(n) = n (n - 1) / 2.
+ * 1. The population of a row is P(c,k) = { j < m : column j counted and x[c,k,j] finite }, n = |P(c,k)|.  A node is COUNTED
+ *    when n >= 2.
+ * 2. For j in P(c,k): a = #{ i in P : x_i < x_j }, b = #{ i in P : x_i > x_j }, IEEE comparisons (-0.0 ties +0.0), and
+ *    cov = C2(n) - C2(a) - C2(b): the number of pairs of members of P, pairs with j itself included, whose band [min, max]
+ *    contains x_j.  64-bit integers.
+ * 3. Per (c, j), K = the counted nodes k with j in P(c,k), in ascending k: nodes = |K|,
+ *    depth = (sum over K, ascending, of (double)cov / (double)C2(n)) / (double)nodes,
+ *    mei = (sum over K of (double)(n - a) / (double)n) / (double)nodes; each sum starts from +0.0 with one add per node, no
+ *    contraction; both NaN where nodes = 0.  (The conversions are exact up to m = 2^26 and round once beyond.)
+ * 4. Per channel, D = { j : nodes > 0 }, n_defined = |D|; h = ceil(central * (double)n_defined) clamped to [1, n_defined];
+ *    threshold = the h-th largest depth over D; S = { j in D : depth >= threshold } (ties all belong), central[c][j] its
+ *    indicator, n_central = |S|; median = the lowest j with the largest depth, depth_max that depth.  n_defined = 0:
+ *    threshold and depth_max NaN, median -1, the counts 0.
+ * 5. Per row: central_lo / central_hi = min / max of x over S and P(c,k); w = hi - lo, fence_lo = lo - factor * w,
+ *    fence_hi = hi + factor * w, one rounding per operation; all four NaN where the intersection is empty.  count = n,
+ *    n_central_here = |S and P(c,k)|.
+ * 6. Per (c, j): n_out = #{ k : j in P(c,k), both fences of (c, k) finite, x < fence_lo or x > fence_hi }, first_out the
+ *    smallest such k or -1.  Per channel n_outliers = #{ j in D : n_out > 0 }.
+ * 7. Per row: whisker_lo / whisker_hi = min / max of x over P(c,k) and D and { n_out = 0 }, NaN where empty.
+ * The sign of a zero minimum or maximum is not part of the contract.
+ *
+ * Passes.  Per channel the rank pass writes (a, b) of every element into a workspace of that channel's rows (n_nodes * m * 8
+ * bytes): a row of up to ERPL_DEPTH_LDS_MAX columns (spec.lds_limit, if positive and smaller) is sorted as keys in LDS by one
+ * workgroup, longer rows by a radix sort in device memory, and every column finds the run of its own key in the sorted row
+ * by bisection - both paths give the same integers.  A thread per column then adds its terms node by node.  Threshold and
+ * median come from a sort of the channel's depths, envelope, fences and whiskers from a workgroup per row folding in the
+ * fixed order of the statistics units, the outlier counts from a thread per column.  Integer atomics only (n_outliers): two
+ * calls on the same input return the same bytes, and one channel's outputs do not depend on which other channels are in
+ * the call.
+ * Not here: a joint depth over several channels, depth across ranks. */
+#define ERPL_DEPTH_MAX_CHANNELS 8       /* = ERPL_CORRIDOR_MAX_CHANNELS */
+#define ERPL_DEPTH_MAX_NODES 4096       /* = ERPL_CORRIDOR_MAX_NODES */
+#define ERPL_DEPTH_LDS_MAX 16384        /* the built-in limit of the LDS path: 128 KB of 8-byte keys in the 160 KB of a CU */
+
+typedef struct erpl_depth_spec {
+  int32_t n_channels;                   /* 1..8 */
+  int32_t n_nodes;                      /* 1..4096 */
+  double central;                       /* in (0, 1]: the share of the defined columns the central region holds */
+  double factor;                        /* >= 0, finite: the fences lie factor * (hi - lo) outside the central envelope */
+  int32_t lds_limit;                    /* 0: the built-in limit of the LDS path; > 0: rows with more columns take the global
+                                           path (clamped to the built-in limit) */
+  int32_t reserved;
+} erpl_depth_spec;
+
+typedef struct erpl_depth_row {         /* 64 bytes */
+  int64_t count;                        /* n = |P(c,k)| */
+  int64_t n_central_here;               /* |S and P(c,k)| */
+  double central_lo, central_hi;
+  double fence_lo, fence_hi;
+  double whisker_lo, whisker_hi;
+} erpl_depth_row;
+
+typedef struct erpl_depth_result {
+  int64_t m, n_masked;                  /* n_masked: the non-zero mask bytes */
+  int64_t n_defined[ERPL_DEPTH_MAX_CHANNELS], n_central[ERPL_DEPTH_MAX_CHANNELS], n_outliers[ERPL_DEPTH_MAX_CHANNELS];
+  int64_t median[ERPL_DEPTH_MAX_CHANNELS];      /* a column, or -1 */
+  double threshold[ERPL_DEPTH_MAX_CHANNELS], depth_max[ERPL_DEPTH_MAX_CHANNELS];
+} erpl_depth_result;
+
+/* Host only: central = 0.5, factor = 1.5, lds_limit = 0, n_channels = n_nodes = 0 (the caller fills them in). */
+int erpl_mc_corridor_depth_defaults(erpl_depth_spec* spec);
+int erpl_mc_corridor_depth(erpl_ctx* ctx, const double* values, int64_t ld, const uint8_t* mask, int64_t m,
+                           const erpl_depth_spec* spec, erpl_depth_result* result, erpl_depth_row* rows, double* depth,
+                           double* mei, int32_t* nodes, int32_t* n_out, int32_t* first_out, uint8_t* central, void* hip_stream);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
