@@ -317,8 +317,7 @@ __global__ __launch_bounds__(kFlightBlock, MINW) void ERPL_CAT(erpl_flight_, ERP
           }
           if (fl & kRecFresh) {
             traj_record<TRAJ>(ln, traj_len, false);
-            if (!(ln.t < max_time)) {  // while t < max_time never entered
-              traj_record<TRAJ>(ln, traj_len, true);
+            if (!(ln.t < max_time)) {  // while t < max_time never entered: the record above is the only one (:212-216)
               if (TRAJ && ln.traj_slot >= 0) ca->traj_len[ln.traj_slot] = traj_len;
               lane_finish(ln, ERPL_END_MAX_TIME);
             }

@@ -175,7 +175,8 @@ typedef struct erpl_out {
   int32_t* status;        /* [n] */
   int64_t n_traj;         /* samples to record */
   const int64_t* traj_ids;/* [n_traj] sample indices (device) */
-  int64_t traj_stride;    /* record every traj_stride-th step (step 0 = rail-exit state, last step always) */
+  int64_t traj_stride;    /* record every traj_stride-th step (step 0 = rail-exit state, last step always; a flight
+                             that takes no step - rail time >= max_time - has that one record) */
   int64_t traj_cap;       /* records per sample */
   double* traj;           /* [n_traj][traj_cap][ERPL_TRAJ_DIM] */
   int64_t* traj_len;      /* [n_traj] records written */

@@ -4,8 +4,10 @@ The files were recorded by tools/record_flight_bits.py on the commit before the 
 register copies of polynomial coefficients, LDS records addressed by byte offset, the step counter taken out of the step): a
 change of that kind may not alter what any floating-point instruction computes, in any of the three builds.  Batches and calls are those of
 flight_bits_cases.py: the four specialisations the launcher picks (wind table or none, liquid or solid motor) on 256
-Set S samples with the full termination logic, a planar CSV-wind batch flown to the ground under the parachute, and the
-trajectory-capture build with four captured samples."""
+Set S samples with the full termination logic, a planar CSV-wind batch flown to the ground under the parachute, the
+trajectory-capture build with four captured samples, and the steered groups of flight_event_cases.py which end in every way the event
+logic knows (recorded later, on the commit that added them: its only kernel change is the record count the capture instantiation
+reports for a flight whose loop is never entered, which none of these cases captures - the older files did not change)."""
 import os
 
 import numpy as np

@@ -6,7 +6,8 @@ every later build to.
 Run it on a build whose results are the contract (the commit BEFORE a change that must leave them alone), never to make a
 failing comparison pass.  The batches and the calls are those of tests/flight_bits_cases.py.  Refuses to write anything
 unless every Set S recording has a flight that ends on the ground, one that leaves through the altitude limit, one that
-runs out of time and one that turned NaN, and the parachute case a flight under the parachute."""
+runs out of time and one that turned NaN, the parachute case a flight under the parachute, and the steered case a coast
+time-out, an altitude exit, a landing and a flight that ran out of time."""
 import argparse
 import os
 import sys
