@@ -610,6 +610,28 @@ class ErplReweight(C.Structure):
                 ("ess_expected_share", C.c_double), ("row", ErplRwRowStats * RW_MAX_ROWS)]
 
 
+# erpl_mc_corridor_bands_weighted
+BANDS_W_MAX_THRESHOLDS = 4
+
+
+class ErplBandsWSpec(C.Structure):
+    _fields_ = [("n_channels", C.c_int32), ("n_nodes", C.c_int32), ("n_q", C.c_int32), ("reserved", C.c_int32),
+                ("q", C.c_double * RW_MAX_Q), ("n_thresholds", C.c_int32 * CORRIDOR_MAX_CHANNELS),
+                ("threshold", (C.c_double * BANDS_W_MAX_THRESHOLDS) * CORRIDOR_MAX_CHANNELS)]
+
+
+class ErplBandsWRow(C.Structure):   # 28 eight-byte words
+    _fields_ = [("count", C.c_int64), ("n_non_finite", C.c_int64), ("n_zero", C.c_int64), ("sum_w", C.c_int64),
+                ("exceed_w", C.c_int64 * BANDS_W_MAX_THRESHOLDS), ("quantile", C.c_double * RW_MAX_Q),
+                ("min", C.c_double), ("max", C.c_double), ("mean", C.c_double), ("var", C.c_double), ("std", C.c_double),
+                ("mean_se", C.c_double), ("sum_w2", C.c_double), ("ess", C.c_double), ("a2", C.c_double * BANDS_W_MAX_THRESHOLDS)]
+
+
+class ErplBandsWResult(C.Structure):
+    _fields_ = [("m", C.c_int64), ("n_masked", C.c_int64), ("n_counted", C.c_int64), ("max_w", C.c_int64),
+                ("K", C.c_int32), ("Q", C.c_int32)]
+
+
 # erpl_mc_casualty: per_node / per_fragment [CASUALTY_SPLIT_DIM][.], groups [n_nodes * n_fragments][CASUALTY_GROUP_DIM]
 CASUALTY_MAX_GRID = 1024
 CASUALTY_MAX_LEVELS = 8
@@ -678,7 +700,8 @@ EXPORTS = ("erpl_mc_abi_version", "erpl_mc_last_error", "erpl_mc_create", "erpl_
            "erpl_mc_reweight_defaults", "erpl_mc_reweight", "erpl_mc_reweight_host",
            "erpl_mc_casualty_defaults", "erpl_mc_casualty",
            "erpl_mc_corridor_drivers_defaults", "erpl_mc_corridor_drivers",
-           "erpl_mc_corridor_depth_defaults", "erpl_mc_corridor_depth")
+           "erpl_mc_corridor_depth_defaults", "erpl_mc_corridor_depth",
+           "erpl_mc_corridor_bands_weighted_defaults", "erpl_mc_corridor_bands_weighted", "erpl_mc_corridor_bands_weighted_host")
 
 _lib = None
 
@@ -850,6 +873,12 @@ def load_library(path=None):
     # ctx, values, ld, mask, m, spec, result, rows, depth, mei, nodes, n_out, first_out, central, hip_stream
     lib.erpl_mc_corridor_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(ErplDepthSpec),
                                            C.POINTER(ErplDepthResult)] + [C.c_void_p] * 8
+    lib.erpl_mc_corridor_bands_weighted_defaults.argtypes = [C.POINTER(ErplBandsWSpec)]
+    # values, mask, weights, m, ld, spec, rows, result
+    bands_w = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(ErplBandsWSpec), C.c_void_p,
+               C.POINTER(ErplBandsWResult)]
+    lib.erpl_mc_corridor_bands_weighted.argtypes = [C.c_void_p] + bands_w + [C.c_void_p]   # ctx .. hip_stream
+    lib.erpl_mc_corridor_bands_weighted_host.argtypes = bands_w
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if a declared symbol is not exported
         if name not in ("erpl_mc_last_error",):

@@ -1779,6 +1779,160 @@ def reweighted_impact(summary, factors, kinds, law, status=None, engine=None, ta
     return out
 
 
+def bands_weighted_spec(n_channels, n_nodes, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), thresholds=None):
+    """The spec of erpl_mc_corridor_bands_weighted (_abi.ErplBandsWSpec) on top of the library's defaults.  quantiles: up to
+    8; thresholds: None, or per channel (a sequence of n_channels entries, or a mapping channel index -> entry) up to 4
+    thresholds.  A pure host function; the values are checked by the library."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    spec = _abi.ErplBandsWSpec()
+    _abi.check(lib, lib.erpl_mc_corridor_bands_weighted_defaults(C.byref(spec)), "erpl_mc_corridor_bands_weighted_defaults")
+    n_channels, n_nodes = int(n_channels), int(n_nodes)
+    if not 1 <= n_channels <= _abi.CORRIDOR_MAX_CHANNELS:
+        raise ValueError(f"1 to {_abi.CORRIDOR_MAX_CHANNELS} channels")
+    if not 1 <= n_nodes <= _abi.CORRIDOR_MAX_NODES:
+        raise ValueError(f"1 to {_abi.CORRIDOR_MAX_NODES} nodes")
+    spec.n_channels, spec.n_nodes = n_channels, n_nodes
+    quantiles = [float(q) for q in quantiles]
+    if len(quantiles) > _abi.RW_MAX_Q:
+        raise ValueError(f"at most {_abi.RW_MAX_Q} quantiles")
+    spec.n_q = len(quantiles)
+    spec.q[:len(quantiles)] = quantiles
+    if thresholds is not None:
+        items = thresholds.items() if hasattr(thresholds, "items") else enumerate(thresholds)
+        for c, values in items:
+            c = int(c)
+            if not 0 <= c < n_channels:
+                raise ValueError(f"thresholds: channel {c} outside 0..{n_channels - 1}")
+            values = [] if values is None else [float(v) for v in values]
+            if len(values) > _abi.BANDS_W_MAX_THRESHOLDS:
+                raise ValueError(f"at most {_abi.BANDS_W_MAX_THRESHOLDS} thresholds per channel")
+            spec.n_thresholds[c] = len(values)
+            spec.threshold[c][:len(values)] = values
+    return spec
+
+
+def bands_weighted_result_dict(spec, rows, res):
+    """The records of erpl_mc_corridor_bands_weighted as a dict of NumPy arrays: 'count', 'n_non_finite', 'n_zero', 'sum_w'
+    int64 [C, T]; 'min', 'max', 'mean', 'var', 'std', 'mean_se', 'sum_w2', 'ess' float64 [C, T]; 'quantiles' float64
+    [C, n_q, T]; 'exceed_w' int64, 'a2', 'p', 'p_se' float64 [C, 4, T] (entries past a channel's thresholds: 0 / NaN; p and
+    p_se by erpl_mc_reweight's formula); 'q', 'thresholds' (per channel a list) and Python ints 'm', 'n_masked', 'n_counted',
+    'max_w', 'K', 'Q'."""
+    from . import _abi
+    Cn, T, nq, nt = spec.n_channels, spec.n_nodes, spec.n_q, _abi.BANDS_W_MAX_THRESHOLDS
+    words = 12 + _abi.RW_MAX_Q + 2 * nt   # erpl_bands_w_row in eight-byte words
+    ints = np.frombuffer(rows, dtype=np.int64).reshape(Cn, T, words)
+    raw = np.frombuffer(rows, dtype=np.float64).reshape(Cn, T, words)
+    out = {name: ints[:, :, k].copy() for k, name in enumerate(("count", "n_non_finite", "n_zero", "sum_w"))}
+    out["exceed_w"] = np.ascontiguousarray(ints[:, :, 4:4 + nt].transpose(0, 2, 1))
+    at = 4 + nt
+    out["quantiles"] = np.ascontiguousarray(raw[:, :, at:at + nq].transpose(0, 2, 1))
+    at += _abi.RW_MAX_Q
+    for k, name in enumerate(("min", "max", "mean", "var", "std", "mean_se", "sum_w2", "ess")):
+        out[name] = raw[:, :, at + k].copy()
+    out["a2"] = np.ascontiguousarray(raw[:, :, at + 8:at + 8 + nt].transpose(0, 2, 1))
+    K = int(res.K)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        s_d = np.ldexp(out["sum_w"].astype(np.float64), -K)[:, None, :]
+        p = out["exceed_w"].astype(np.float64) / out["sum_w"].astype(np.float64)[:, None, :]
+        v = (1.0 - 2.0 * p) * out["a2"] + (p * p) * out["sum_w2"][:, None, :]
+        out["p"], out["p_se"] = p, np.sqrt(np.maximum(v, 0.0)) / s_d
+    for c in range(Cn):
+        out["p"][c, spec.n_thresholds[c]:], out["p_se"][c, spec.n_thresholds[c]:] = np.nan, np.nan
+    out["q"] = list(spec.q[:nq])
+    out["thresholds"] = [list(spec.threshold[c][:spec.n_thresholds[c]]) for c in range(Cn)]
+    out.update({k: int(getattr(res, k)) for k in ("m", "n_masked", "n_counted", "max_w", "K", "Q")})
+    return out
+
+
+def bands_weighted_host(values, weights, mask=None, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), thresholds=None, m=None):
+    """erpl_mc_corridor_bands_weighted_host on NumPy arrays - TrajectoryEngine.corridor_bands_weighted without a device, the
+    same integers and the same order statistics: values float64 [C, T, ld] (C-contiguous) of which the first m columns are
+    read (default ld), weights int64 [m], mask uint8 [m] or None.  Returns the dict of `bands_weighted_result_dict`."""
+    import ctypes as C
+    from . import _abi
+    lib = _abi.load_library()
+    if not (isinstance(values, np.ndarray) and values.dtype == np.float64 and values.ndim == 3 and values.flags.c_contiguous):
+        raise ValueError("values must be a C-contiguous float64 [C, T, ld] array")
+    Cn, T, ld = (int(s) for s in values.shape)
+    m = ld if m is None else int(m)
+    if not 1 <= m <= ld:
+        raise ValueError(f"m = {m} outside 1..{ld}")
+    spec = bands_weighted_spec(Cn, T, quantiles, thresholds)
+    weights = np.ascontiguousarray(weights, dtype=np.int64)
+    if weights.shape != (m,):
+        raise ValueError("weights must be int64 [m]")
+    if mask is not None:
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        if mask.shape != (m,):
+            raise ValueError("mask must be uint8 [m]")
+    rows = (_abi.ErplBandsWRow * (Cn * T))()
+    res = _abi.ErplBandsWResult()
+    _abi.check(lib, lib.erpl_mc_corridor_bands_weighted_host(_np_ptr(values), _np_ptr(mask), _np_ptr(weights), m, ld, C.byref(spec),
+                                                             C.cast(rows, C.c_void_p), C.byref(res)),
+               "erpl_mc_corridor_bands_weighted_host")
+    return bands_weighted_result_dict(spec, rows, res)
+
+
+def reweighted_corridor(values, t0, step, channels, factors, kinds, law, mask=None, engine=None,
+                        quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), thresholds=None, m=None):
+    """The time-resolved bands of a captured matrix (float64 [C, T, ld] on the device: a corridor, an impact-point or a debris
+    matrix flown from a design of INDEPENDENT primitives) under another input law, without a new run.  ONE erpl_mc_reweight
+    call gives the weights: the changed primitive rows `factors` (float64 [n_law, m] device tensor; `kinds`, `law` as in
+    `reweight_spec`) over the columns whose `mask` byte is 0, with a row of zeros as the one requested row - so the weight
+    population is the mask and the support of the target alone, whatever the matrix holds.  Then
+    erpl_mc_corridor_bands_weighted describes every row over ITS OWN population under those weights, and
+    erpl_mc_corridor_bands describes the same matrix as flown, for comparison.  `channels`: the names of the C channels; nodes
+    at t0 + k step; m: the columns read (default: the columns of `factors`).
+    Returns a dict: 'time' [T], 'channels', 'q', 'thresholds', per channel name 'reweighted' ({'count', 'mean', 'mean_se',
+    'std', 'min', 'max', 'ess', 'sum_w' [T], 'quantiles' [n_q, T], 'p', 'p_se', 'exceed_w' [n_thr, T]}) and 'flown' (the
+    unweighted {'count', 'mean', 'std', 'min', 'max', 'quantiles'}), the call record ('m', 'n_masked', 'n_counted', 'max_w',
+    'K', 'Q') and of the reweighting 'count' (the columns the mask keeps inside the target's support), 'n_zero' (those of them
+    whose weight rounds to 0), 'n_outside', 'sum_w', 'ess', 'ess_expected_share', 'ess_share', 'max_weight_share' and 'warnings'
+    (`finish_reweighted`, plus the nodes whose own effective sample size is below 100).
+
+    Reading it: the weighted quantile is the inverted-cdf order statistic, a flown value, not the interpolated one of the
+    flown bands; mean_se is the delta-method error of a ratio of sums over i.i.d. columns.  Per node, `ess` says where not
+    to believe the band: late nodes hold fewer flights, and a few heavy ones may carry them."""
+    import torch
+    from . import _abi
+    engine = _engine_of(values, engine)
+    if values.dim() != 3:
+        raise ValueError("values must be a [C, T, ld] matrix")
+    n_ch, n_nodes, ld = (int(s) for s in values.shape)
+    channels = [CORRIDOR_CHANNEL_NAMES[c] if not isinstance(c, str) else c for c in channels]
+    if len(channels) != n_ch:
+        raise ValueError(f"{len(channels)} channels for a matrix of {n_ch}")
+    m = int(factors.shape[-1]) if m is None else int(m)
+    if not 1 <= m <= ld:
+        raise ValueError(f"m = {m} outside 1..{ld}")
+    zeros = torch.zeros(m, dtype=torch.float64, device=values.device)
+    summary = torch.zeros((_abi.SUMMARY_DIM, m), dtype=torch.float64, device=values.device)   # no summary row is requested
+    rw = engine.reweight(factors, kinds, law, summary, mask=mask, rows=[_abi.RW_ROW_EXTRA], extra=zeros, quantiles=(),
+                         want_weights=True)
+    w = engine.corridor_bands_weighted(values, rw["weights"], mask=mask, quantiles=quantiles, thresholds=thresholds, m=m)
+    b = engine.corridor_bands(values, mask, quantiles=quantiles, m=m)
+    fin = finish_reweighted(rw)
+    out = {"time": float(t0) + np.arange(n_nodes, dtype=np.float64) * float(step), "channels": channels, "q": w["q"],
+           "thresholds": w["thresholds"]}
+    out.update({k: w[k] for k in ("m", "n_masked", "n_counted", "max_w", "K", "Q")})
+    out.update({k: fin[k] for k in ("count", "n_zero", "n_outside", "sum_w", "ess", "ess_expected_share", "ess_share",
+                                    "max_weight_share")})
+    warnings = list(fin["warnings"])
+    for c, name in enumerate(channels):
+        nt = len(w["thresholds"][c])
+        rew = {k: w[k][c] for k in ("count", "mean", "mean_se", "std", "min", "max", "ess", "sum_w", "quantiles")}
+        rew.update({k: w[k][c][:nt] for k in ("p", "p_se", "exceed_w")})
+        out[name] = {"reweighted": rew, "flown": {k: b[k][c] for k in ("count", "mean", "std", "min", "max", "quantiles")}}
+        thin = np.flatnonzero((rew["count"] > 0) & (rew["ess"] < 100.0))
+        if len(thin):
+            warnings.append(f"{name}: the effective sample size is below 100 at {len(thin)} of {n_nodes} nodes "
+                            f"(from node {int(thin[0])})")
+    out["warnings"] = warnings
+    return out
+
+
 # ---------------------------------------------------------------------------------- the casualty expectation of a footprint
 CASUALTY_COUNTS = ("landed", "lethal", "off_grid", "missing")   # rows 1..4 of per_node / per_fragment (_abi.CASUALTY_*)
 

@@ -480,6 +480,7 @@ int erpl_mc_destroy(erpl_ctx* c) {
   c->casualty.release();
   c->cdrv.release();
   c->depth.release();
+  c->bands_w.release();
   if (c->reweight_pin) (void)hipHostFree(c->reweight_pin);
   delete c;
   return ERPL_OK;

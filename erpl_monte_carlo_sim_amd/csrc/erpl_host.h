@@ -1,5 +1,5 @@
 // erpl_host.h — what the host units of the C ABI share (erpl_api.hip, erpl_sampling.hip, erpl_stats_api.hip,
-// erpl_legacy_device.hip, erpl_design.hip, erpl_qmc.hip, erpl_tally.hip, erpl_subset.hip, erpl_reweight.hip, erpl_casualty.hip, erpl_corridor_drivers.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
+// erpl_legacy_device.hip, erpl_design.hip, erpl_qmc.hip, erpl_tally.hip, erpl_subset.hip, erpl_reweight.hip, erpl_casualty.hip, erpl_corridor_drivers.hip, erpl_corridor_w.hip): the error text behind erpl_mc_last_error, the context, and the host patterns that exist once.
 // Internal, never installed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -280,6 +280,8 @@ struct erpl_ctx {
   ErplStatUnit<void, char> cdrv;
   // erpl_mc_corridor_depth: the pieces of erpl_depth_layout (erpl_depth.h) in the buffer; what comes back is small or caller-sized
   ErplStatUnit<void, char> depth;
+  // erpl_mc_corridor_bands_weighted: the slots of its first pass and a record per row (erpl_corridor_w.hip)
+  ErplStatUnit<void, char> bands_w;
 };
 
 // erpl_design.hip

@@ -1,6 +1,6 @@
 // erpl_stat_device.h — what the statistics units (erpl_analysis.hip, erpl_distributions.hip, erpl_correlation.hip,
 // erpl_bootstrap.hip, erpl_density.hip, erpl_corridor.hip, erpl_sobol.hip, erpl_dependence.hip, erpl_compare.hip,
-// erpl_reweight.hip, erpl_density_w.hip, erpl_corridor_depth.hip) share:
+// erpl_reweight.hip, erpl_density_w.hip, erpl_corridor_depth.hip, erpl_corridor_w.hip) share:
 // the grid of their streaming passes, the order-preserving keys, the run of equal keys behind a mid-rank, THE fixed-order
 // reduction and the steps of the radix selection.
 // Internal: never installed.
@@ -214,7 +214,7 @@ __device__ __forceinline__ void select_count(unsigned int (*hist)[ERPL_ANA_BINS]
   }
 }
 
-// The weighted sibling (erpl_reweight.hip, erpl_density_w.hip): the key counts w times, the bins are 64-bit.  A wave whose hits share one bin adds
+// The weighted sibling (erpl_reweight.hip, erpl_density_w.hip, erpl_corridor_w.hip): the key counts w times, the bins are 64-bit.  A wave whose hits share one bin adds
 // their weights up with a shuffle tree first (integer adds: the order does not matter) and makes one add of it.
 __device__ __forceinline__ void select_count_weighted(u64 (*hist)[ERPL_ANA_BINS], const int* lead, const u64* prefix, int nlead,
                                                       bool use, u64 key, int shift, u64 w) {

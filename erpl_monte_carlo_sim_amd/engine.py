@@ -592,6 +592,38 @@ class TrajectoryEngine:
         out["n_counted"] = int(counted.value)
         return out
 
+    def corridor_bands_weighted(self, values, weights, mask=None, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), thresholds=None, m=None):
+        """Every (channel, node) row of a time-resolved matrix described under the integer weights of `reweight`
+        (erpl_mc_corridor_bands_weighted; the definitions are in include/erpl_mc.h): values float64 [C, T, ld] on the device -
+        a corridor, an impact-point or a debris matrix as it is - of which the first m columns are read (default ld); weights
+        int64 [m] on the device, each in 0..2^Q; mask uint8 [m] on the device, a column counts iff its byte is 0; thresholds:
+        per channel up to 4 (analysis.bands_weighted_spec).  Each row over ITS OWN population: mask byte 0, the value finite,
+        W > 0.  Enqueued on the current torch stream; blocks the host until the result is there.  Returns the dict of
+        analysis.bands_weighted_result_dict: NumPy arrays [C, T] and [C, n_q, T], Python ints for the call record.  The
+        quantiles are inverted-cdf order statistics (values of the row), not the interpolated ones of `corridor_bands`."""
+        from . import analysis
+        if not (torch.is_tensor(values) and values.is_cuda and values.device == self.device and values.dtype == torch.float64
+                and values.dim() == 3 and values.is_contiguous()):
+            raise ValueError(f"values must be a contiguous float64 [C, T, ld] tensor on {self.device}")
+        n_ch, n_nodes, ld = (int(s) for s in values.shape)
+        m = ld if m is None else int(m)
+        if not 1 <= m <= ld:
+            raise ValueError(f"m = {m} outside 1..{ld}")
+        if not (torch.is_tensor(weights) and weights.device == self.device and weights.dtype == torch.int64
+                and tuple(weights.shape) == (m,) and weights.is_contiguous()):
+            raise ValueError(f"weights must be a contiguous int64 [m] tensor on {self.device}")
+        if mask is not None and not (torch.is_tensor(mask) and mask.device == self.device and mask.dtype == torch.uint8
+                                     and tuple(mask.shape) == (m,) and mask.is_contiguous()):
+            raise ValueError(f"mask must be a contiguous uint8 [m] tensor on {self.device}")
+        spec = analysis.bands_weighted_spec(n_ch, n_nodes, quantiles, thresholds)
+        rows = (_abi.ErplBandsWRow * (n_ch * n_nodes))()
+        res = _abi.ErplBandsWResult()
+        st = torch.cuda.current_stream(self.device)
+        self._call("erpl_mc_corridor_bands_weighted", C.c_void_p(values.data_ptr()),
+                   C.c_void_p(mask.data_ptr()) if mask is not None else None, C.c_void_p(weights.data_ptr()), m, ld, C.byref(spec),
+                   C.cast(rows, C.c_void_p), C.byref(res), C.c_void_p(st.cuda_stream))
+        return analysis.bands_weighted_result_dict(spec, rows, res)
+
     def corridor_drivers(self, factors, values, mask=None, m=None, regression=True):
         """Which factor drives which row of a time-resolved matrix, each row over ITS OWN population
         (erpl_mc_corridor_drivers; the definitions are in include/erpl_mc.h): factors float64 [F, ldf] and values float64

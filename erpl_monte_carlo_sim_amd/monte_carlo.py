@@ -688,7 +688,7 @@ class MonteCarloAnalyzer:
         return plots.plot_exceedance(self, tally, row, save_plots, level)
 
     def flight_envelope(self, initial_conditions, n_samples, stride=10, seed=1234, precision="f64_fast", planar=False,
-                        capture_bytes=4 << 30):
+                        capture_bytes=4 << 30, design=None):
         """What the vehicle goes through on the way up, for every sample of a dispersion run: the samples of
         `run_monte_carlo_device` (same draws: sub-batch j from seed + rank + 1000003 * j) are flown with EVERY trajectory
         captured at every `stride`-th step and each capture is reduced on the device to its flight envelope
@@ -707,11 +707,16 @@ class MonteCarloAnalyzer:
         throughput build fuses a few products differently - DESIGN.md section 4), 'envelope' float64 [16, n] on the
         device with 'envelope_names' (analysis.ENVELOPE_NAMES, rows _abi.ENV_*), 'reasons' (uint8 [n], the outlier
         filter's reason bits), 'n_samples' / 'n_outliers' of that filter, 'statistics' (analysis.envelope_statistics
-        over the samples that pass it) and 'performance'."""
+        over the samples that pass it) and 'performance'.
+
+        design: None (the draws above), or 'random', 'lhs', 'lhs_centred' or 'qmc': the run flies ONE design of n_samples columns
+        under the independent law, as `run_monte_carlo_device(design=...)` does, every sub-batch its own window of it, so its
+        inputs no longer depend on `capture_bytes`; the result carries 'design' and can be reweighted, fitted (`surrogate`)
+        and flown again (`refly`) like a device run."""
         envs = []
         eng, summ, status, run = self._captured_run(
             "flight_envelope", "envelopes", initial_conditions, n_samples, stride, seed, precision, planar, capture_bytes,
-            lambda eng, db, a, traj, tlen: envs.append(eng.flight_envelope(db, eng._keep, traj, tlen)))
+            lambda eng, db, a, traj, tlen: envs.append(eng.flight_envelope(db, eng._keep, traj, tlen)), design=design)
         env = envs[0] if len(envs) == 1 else torch.cat(envs, dim=1).contiguous()
         torch.cuda.synchronize(eng.device)
         t1 = time.time()
@@ -723,18 +728,26 @@ class MonteCarloAnalyzer:
         out["performance"] = {"total_time": t2 - run["t0"], "capture_and_envelope_s": t1 - run["t0"], "statistics_s": t2 - t1,
                               "precision": precision, "stride": run["stride"], "records_per_sample": run["cap"],
                               "sub_batches": len(envs), "sub_batch_samples": run["per_batch"]}
+        if run["design"] is not None:
+            out["design"] = run["design"]
         return out
 
     def _captured_run(self, who, what, initial_conditions, n_samples, stride, seed, precision, planar, capture_bytes, reduce,
-                      factors=None):
+                      factors=None, design=None):
         """The capturing loop of `flight_envelope`, `trajectory_corridor` and `impact_point_trace`: the samples of run_monte_carlo_device (sub-batch
         j from seed + rank + 1000003 * j) flown with every trajectory captured at every `stride`-th step, in sub-batches of
         capture_bytes // (cap * 120) samples (at most DEVICE_CHUNK); `reduce(eng, db, first_sample, traj, traj_len)`
         enqueues what the caller makes of a sub-batch's capture, and the capture buffer is released behind it.  One rank
         only (`who` / `what` word the refusal).  factors: a list that receives (db.factors, db.factor_names) of every sub-batch
-        - the draws are otherwise released with the sub-batch.  Returns (engine, summary [16, n], status [n], {'t0', 'stride',
-        'cap', 'per_batch', 'sub_batches'}) once everything has run."""
+        - the draws are otherwise released with the sub-batch.  design: None (those draws, bit for bit), or a kind of
+        _abi.DESIGN_KINDS: sub-batch [a, a + nb) takes the columns a .. a + nb - 1 of ONE design of n_samples columns
+        (`sampling.design_draws`, the independent law, K as `run_monte_carlo_device` chooses it), so the inputs of the run no
+        longer depend on `capture_bytes`; an unknown kind is a ValueError before the engine is created.  Returns (engine,
+        summary [16, n], status [n], {'t0', 'stride', 'cap', 'per_batch', 'sub_batches', 'design'}) once everything has run;
+        'design' is None or the {'kind', 'seed', 'block', 'replicates'} entry of a design run."""
         from . import sampling
+        if design is not None and design not in _abi.DESIGN_KINDS:
+            raise ValueError(f"design: None or one of {list(_abi.DESIGN_KINDS)}")
         if dist.world()[1] > 1:
             raise ValueError(f"{who} is limited to a world size of 1: {what} are not gathered across ranks")
         n_samples, stride = int(n_samples), int(stride)
@@ -747,16 +760,23 @@ class MonteCarloAnalyzer:
         dt = min(self.dt_initial, 0.005)
         cap = int(np.ceil(self.max_time / dt / stride)) + 4
         per_batch = max(1, min(self.DEVICE_CHUNK, int(capture_bytes) // (cap * _abi.TRAJ_DIM * 8)))
+        if design is not None:
+            use_base = self.base_wind_profile is not None and self.base_altitude_profile is not None
+            design_K = len(self.base_altitude_profile) if use_base else 100   # synthetic_dispersions' default grid
         torch.cuda.synchronize(eng.device)
         t0 = time.time()
         summs, stats = [], []
         for j, a in enumerate(range(0, n_samples, per_batch)):
             nb = min(per_batch, n_samples - a)
+            draws = None
+            if design is not None:   # this sub-batch's window of the one design of the run
+                draws = sampling.design_draws(n_samples, design_K, eng.device, seed, design=design, block=n_samples, first=a, count=nb,
+                                              engine=eng)
             db = sampling.synthetic_dispersions(
                 nb, self.rocket, self.motor, self.wind_model, initial_conditions, eng.device, precision=prec,
                 seed=seed + rank + 1000003 * j, uncertainty=self.uncertainty_params,
                 base_altitude_profile=self.base_altitude_profile, base_wind_profile=self.base_wind_profile,
-                planar=planar, engine=eng)
+                planar=planar, engine=eng, draws=draws)
             summ, status, traj, tlen = eng.run(db, traj_ids=np.arange(nb), traj_stride=stride, traj_cap=cap)
             reduce(eng, db, a, traj, tlen)
             if factors is not None:
@@ -766,8 +786,9 @@ class MonteCarloAnalyzer:
             del traj, tlen, db   # (stream-ordered: the allocator hands the capture buffer on behind the caller's kernel)
         eng.synchronize()        # host-blocking; raises if a lane hand-over timed out
         cat = lambda parts, dim: parts[0] if len(parts) == 1 else torch.cat(parts, dim=dim).contiguous()
+        record = None if design is None else {"kind": design, "seed": int(seed), "block": n_samples, "replicates": 1}
         return eng, cat(summs, 1), cat(stats, 0), {"t0": t0, "stride": stride, "cap": cap, "per_batch": per_batch,
-                                                   "sub_batches": len(summs)}
+                                                   "sub_batches": len(summs), "design": record}
 
     @staticmethod
     def _kept_factors(out, kept):
@@ -778,7 +799,7 @@ class MonteCarloAnalyzer:
 
     def trajectory_corridor(self, initial_conditions, n_samples, stride=10, seed=1234, precision="f64_fast", planar=False,
                             capture_bytes=4 << 30, nodes=256, t_end=None, channels=("z", "downrange", "speed"),
-                            quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), hold=True, keep_factors=False):
+                            quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), hold=True, keep_factors=False, design=None):
         """Where the vehicle is at time t and how wide the spread is there, for a whole dispersion run: the samples of
         `flight_envelope` (same draws, same sub-batches, every trajectory captured at every `stride`-th step) are brought
         onto `nodes` time nodes from 0 to `t_end` (default max_time) on the device, each sub-batch into its window of
@@ -793,7 +814,8 @@ class MonteCarloAnalyzer:
         'min' / 'max' [T] and 'quantiles' [n_q, T]) plus 'summary', 'status', 'reasons', 'n_samples' / 'n_outliers' of the
         filter, 'values' (the resampled matrix, on the device) and 'performance'.  keep_factors=True keeps the per-sample
         draws and adds 'factors' (float64 [F, n] on the device, the sample order of 'summary') and 'factor_names', the input
-        of `corridor_drivers`."""
+        of `corridor_drivers`.  design: as in `flight_envelope` - with a design the inputs of the run do not depend on
+        `capture_bytes`, the result carries 'design', and `reweighted_corridor` reports its bands under another input law."""
         nodes = int(nodes)
         if nodes < 2:
             raise ValueError("at least 2 nodes")
@@ -812,7 +834,8 @@ class MonteCarloAnalyzer:
 
         kept = [] if keep_factors else None
         eng, summ, status, run = self._captured_run("trajectory_corridor", "corridors", initial_conditions, n_samples,
-                                                    stride, seed, precision, planar, capture_bytes, resample, factors=kept)
+                                                    stride, seed, precision, planar, capture_bytes, resample, factors=kept,
+                                                    design=design)
         torch.cuda.synchronize(eng.device)
         t1 = time.time()
         _, res, why = analysis._filter(summ, status, eng)
@@ -825,12 +848,14 @@ class MonteCarloAnalyzer:
         out["performance"] = {"total_time": t2 - run["t0"], "capture_and_resample_s": t1 - run["t0"], "bands_s": t2 - t1,
                               "precision": precision, "stride": run["stride"], "records_per_sample": run["cap"],
                               "sub_batches": run["sub_batches"], "sub_batch_samples": run["per_batch"]}
+        if run["design"] is not None:
+            out["design"] = run["design"]
         return out
 
     def impact_point_trace(self, initial_conditions, n_samples, stride=10, nodes=64, record_stride=None, keep_in=None,
                            seed=1234, precision="f64_fast", planar=False, capture_bytes=4 << 30, dt=0.05, max_steps=20000,
                            ground=0.0, drag_scale=1.0, origin=(0.0, 0.0), quantiles=(0.05, 0.25, 0.5, 0.75, 0.95),
-                           level=0.95, keep_factors=False):
+                           level=0.95, keep_factors=False, design=None):
         """If the flight is terminated at time t, where does the vehicle come down - for a whole dispersion run: the samples
         of `flight_envelope` (same draws, same sub-batches, every trajectory captured at every `stride`-th step) and, of each
         capture, `nodes` records `record_stride` apart (None: the stride that spreads the nodes over max_time) fall to
@@ -846,7 +871,8 @@ class MonteCarloAnalyzer:
         share of those samples whose IIP ever leaves the keep-in area, with its Wilson interval 'exit_interval' at `level`
         (NaN and (0, 1) without a polygon) and 'exit_count'; 'values' and 'iip_summary' (on the device), 'iip_names',
         'keep_in', 'summary', 'status', 'reasons', 'n_samples' / 'n_outliers' and 'performance'.  keep_factors=True adds
-        'factors' and 'factor_names' as in `trajectory_corridor`."""
+        'factors' and 'factor_names' as in `trajectory_corridor`.  design: as in `flight_envelope` - with a design the inputs
+        of the run do not depend on `capture_bytes` and the result carries 'design'."""
         nodes, stride = int(nodes), int(stride)
         if not 1 <= nodes <= _abi.IIP_MAX_NODES:
             raise ValueError(f"1 to {_abi.IIP_MAX_NODES} nodes")
@@ -872,7 +898,8 @@ class MonteCarloAnalyzer:
 
         kept = [] if keep_factors else None
         eng, summ, status, run = self._captured_run("impact_point_trace", "impact points", initial_conditions, n_samples,
-                                                    stride, seed, precision, planar, capture_bytes, fall, factors=kept)
+                                                    stride, seed, precision, planar, capture_bytes, fall, factors=kept,
+                                                    design=design)
         iip = summaries[0] if len(summaries) == 1 else torch.cat(summaries, dim=1).contiguous()
         torch.cuda.synchronize(eng.device)
         t1 = time.time()
@@ -899,12 +926,14 @@ class MonteCarloAnalyzer:
         out["performance"] = {"total_time": t2 - run["t0"], "capture_and_fall_s": t1 - run["t0"], "statistics_s": t2 - t1,
                               "precision": precision, "stride": run["stride"], "records_per_sample": run["cap"],
                               "sub_batches": run["sub_batches"], "sub_batch_samples": run["per_batch"]}
+        if run["design"] is not None:
+            out["design"] = run["design"]
         return out
 
     def debris_footprint(self, initial_conditions, n_samples, fragments, stride=10, nodes=16, record_stride=None, keep_in=None,
                          maps=(), map_bins=50, seed=1234, debris_seed=None, precision="f64_fast", planar=False,
                          capture_bytes=4 << 30, dt=0.05, max_steps=20000, ground=0.0, stiff_limit=0.25, origin=(0.0, 0.0),
-                         quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), level=0.95, keep_factors=False):
+                         quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), level=0.95, keep_factors=False, design=None):
         """If the vehicle breaks up at time t, where do its pieces come down - for a whole dispersion run: the samples of
         `impact_point_trace` (same draws, same sub-batches, same nodes) and, at every node, the fragments
         `fragments` = [(beta, dv), ...] - beta the ballistic coefficient m / (Cd A) in kg/m^2 (float('inf'): no drag), dv the
@@ -924,7 +953,9 @@ class MonteCarloAnalyzer:
         Wilson interval 'exit_interval' at `level` (NaN and (0, 1) without a polygon) and 'exit_count'; 'maps', a dict
         (node, fragment) -> {'counts', 'edges_x', 'edges_y', 'info'}; 'values' and 'debris_summary' (on the device),
         'debris_names', 'keep_in', 'summary', 'status', 'reasons', 'n_samples' / 'n_outliers' and 'performance'.
-        keep_factors=True adds 'factors' and 'factor_names' as in `trajectory_corridor`."""
+        keep_factors=True adds 'factors' and 'factor_names' as in `trajectory_corridor`.  design: as in `flight_envelope` - with
+        a design the DISPERSIONS of the run do not depend on `capture_bytes` (the break-up directions still do, as said above)
+        and the result carries 'design'."""
         nodes, stride = int(nodes), int(stride)
         frags = [(float(beta), float(dv)) for beta, dv in fragments]
         F = len(frags)
@@ -963,7 +994,8 @@ class MonteCarloAnalyzer:
 
         kept = [] if keep_factors else None
         eng, summ, status, run = self._captured_run("debris_footprint", "debris footprints", initial_conditions, n_samples,
-                                                    stride, seed, precision, planar, capture_bytes, fall, factors=kept)
+                                                    stride, seed, precision, planar, capture_bytes, fall, factors=kept,
+                                                    design=design)
         deb = summaries[0] if len(summaries) == 1 else torch.cat(summaries, dim=1).contiguous()
         torch.cuda.synchronize(eng.device)
         t1 = time.time()
@@ -998,6 +1030,8 @@ class MonteCarloAnalyzer:
         out["performance"] = {"total_time": t2 - run["t0"], "capture_and_fall_s": t1 - run["t0"], "statistics_s": t2 - t1,
                               "precision": precision, "stride": run["stride"], "records_per_sample": run["cap"],
                               "sub_batches": run["sub_batches"], "sub_batch_samples": run["per_batch"]}
+        if run["design"] is not None:
+            out["design"] = run["design"]
         return out
 
     def corridor_drivers(self, captured, regression=True):
@@ -1396,6 +1430,34 @@ class MonteCarloAnalyzer:
         `plot_impact_probability`, titled with the effective sample size) and reweighted_impact.json; returns the output
         directory."""
         return plots.plot_reweighted_impact(self, reweighted, save_plots)
+
+    def reweighted_corridor(self, captured, uncertainty=None, motor=None, shift=None, planar=False,
+                            quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), thresholds=None):
+        """The time-resolved bands of a captured run under ANOTHER input law (no reference counterpart, no extra flights):
+        `captured` is the dict of `trajectory_corridor`, `impact_point_trace` or `debris_footprint` flown with design=... -
+        its 'values', 'reasons' (the mask), 'time', 'channels', 'summary' and 'design' are read - and the target law is
+        given as in `reweight` (uncertainty, motor, shift, planar).  `analysis.reweighted_corridor`: one erpl_mc_reweight
+        call for the weights, erpl_mc_corridor_bands_weighted for the bands under them, erpl_mc_corridor_bands for the
+        flown bands beside them; per channel 'reweighted' and 'flown', per node the effective sample size, and the
+        warnings of the reweighting.  thresholds: per channel (index -> up to 4 values) the exceedance probabilities
+        wanted at every node.  ValueError for a dict without 'design', as `reweight`."""
+        from . import analysis as ana
+        eng, summ, factors, kinds, law, prim, change = self._law_change_factors(captured, uncertainty, motor, shift, planar)
+        t = np.asarray(captured["time"], dtype=np.float64)
+        out = ana.reweighted_corridor(captured["values"], float(t[0]) if len(t) else 0.0, float(t[1] - t[0]) if len(t) > 1 else 1.0,
+                                      list(captured["channels"]), factors, kinds, law, mask=captured["reasons"], engine=eng,
+                                      quantiles=quantiles, thresholds=thresholds)
+        if "fragments" in captured:   # the rows of a debris matrix are (node, fragment) pairs: every time once per fragment
+            out["fragments"] = captured["fragments"]
+            out["time"] = np.repeat(t, len(captured["fragments"]))
+        out["primitive_rows"], out["law"] = prim, change
+        return out
+
+    def plot_reweighted_corridor(self, reweighted, save_plots=True):
+        """No reference counterpart: the dict of `reweighted_corridor` as monte_carlo_reweighted_corridor.png - per channel the
+        flown bands dashed, the reweighted bands solid and the per-node effective sample size on a second axis - and
+        reweighted_corridor.json next to it; returns the output directory."""
+        return plots.plot_reweighted_corridor(self, reweighted, save_plots)
 
     def plot_surrogate(self, surrogate, save_plots=True):
         """No reference counterpart: per row the first-order and total indices of the variables, the largest pair indices

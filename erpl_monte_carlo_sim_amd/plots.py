@@ -282,6 +282,49 @@ def corridor_figure(result):
     return fig
 
 
+def reweighted_corridor_figure(result):
+    """The corridor under another input law from the dict of analysis.reweighted_corridor: one panel per channel over time -
+    the flown bands dashed (the outermost pair of quantiles and the one nearest 0.5), the reweighted bands solid with the
+    band between the outermost pair filled - and the effective sample size behind every node on a twin axis."""
+    names = list(result["channels"])
+    q = np.asarray(result["q"], dtype=np.float64)
+    t = np.asarray(result["time"], dtype=np.float64)
+    fig = _figure((10, 3.2 * len(names) + 0.6))
+    axes = np.atleast_1d(fig.subplots(len(names), 1, sharex=True))
+    order = np.argsort(q)
+    mid = int(np.argmin(np.abs(q - 0.5))) if len(q) else None
+    for ax, name in zip(axes, names):
+        rew, flown = result[name]["reweighted"], result[name]["flown"]
+        qr = np.asarray(rew["quantiles"], dtype=np.float64)
+        qf = np.asarray(flown["quantiles"], dtype=np.float64)
+        if len(q) >= 2:
+            lo, hi = order[0], order[-1]
+            ax.fill_between(t, qr[lo], qr[hi], alpha=0.2, color="tab:red", linewidth=0)
+            for k in (lo, hi):
+                ax.plot(t, qf[k], color="tab:blue", linewidth=1.0, linestyle="--",
+                        label=f"flown {100 * q[lo]:g} - {100 * q[hi]:g} %" if k == lo else None)
+                ax.plot(t, qr[k], color="tab:red", linewidth=1.0,
+                        label=f"reweighted {100 * q[lo]:g} - {100 * q[hi]:g} %" if k == lo else None)
+        if mid is not None:
+            ax.plot(t, qf[mid], color="tab:blue", linewidth=1.5, linestyle="--", label=f"flown {100 * q[mid]:g} %")
+            ax.plot(t, qr[mid], color="tab:red", linewidth=1.5, label=f"reweighted {100 * q[mid]:g} %")
+        else:
+            ax.plot(t, np.asarray(flown["mean"], dtype=np.float64), color="tab:blue", linewidth=1.5, linestyle="--", label="flown mean")
+            ax.plot(t, np.asarray(rew["mean"], dtype=np.float64), color="tab:red", linewidth=1.5, label="reweighted mean")
+        ax.set_ylabel(CORRIDOR_LABELS.get(name, name))
+        ax.grid(True, alpha=0.3)
+        twin = ax.twinx()
+        twin.plot(t, np.asarray(rew["ess"], dtype=np.float64), color="gray", linewidth=0.8, linestyle=":")
+        twin.set_ylabel("Effective samples")
+        twin.set_ylim(bottom=0)
+    ess = result.get("ess", float("nan"))
+    axes[0].set_title(f"Trajectory Corridor under the target law ({int(result.get('n_counted', 0))} samples, effective {ess:.0f})")
+    axes[0].legend(loc="best", fontsize=8)
+    axes[-1].set_xlabel("Time (s)")
+    fig.tight_layout()
+    return fig
+
+
 def corridor_drivers_figure(result, top=4):
     """Which dispersion drives what, and when, from the dict of analysis.corridor_drivers: per channel two panels over time -
     the signed correlation of the `top` factors of the channel's ranking, and under it their stacked linear variance shares
@@ -996,6 +1039,21 @@ def plot_trajectory_corridor(analyzer, corridor, save_plots=True):
     if save_plots:
         output_dir = analyzer._create_output_directory()
         print(f"Trajectory corridor plot saved to: {save_figure(fig, output_dir, 'monte_carlo_corridor.png')}")
+    return output_dir
+
+
+def plot_reweighted_corridor(analyzer, reweighted, save_plots=True):
+    """The corridor of MonteCarloAnalyzer.reweighted_corridor (no reference counterpart): writes
+    monte_carlo_reweighted_corridor.png and reweighted_corridor.json next to it; returns the output directory (None without
+    save_plots)."""
+    from .reports import to_serializable
+    fig = reweighted_corridor_figure(reweighted)
+    output_dir = None
+    if save_plots:
+        output_dir = analyzer._create_output_directory()
+        print(f"Reweighted corridor plot saved to: {save_figure(fig, output_dir, 'monte_carlo_reweighted_corridor.png')}")
+        with open(os.path.join(output_dir, "reweighted_corridor.json"), "w") as fh:
+            json.dump(to_serializable(reweighted), fh, indent=2)
     return output_dir
 
 

@@ -2271,6 +2271,81 @@ int erpl_mc_corridor_depth(erpl_ctx* ctx, const double* values, int64_t ld, cons
                            const erpl_depth_spec* spec, erpl_depth_result* result, erpl_depth_row* rows, double* depth,
                            double* mei, int32_t* nodes, int32_t* n_out, int32_t* first_out, uint8_t* central, void* hip_stream);
 
+/* The corridor under ANOTHER input law: every (channel, node) row of a time-resolved matrix - the corridor [C][T][ld] of
+ * erpl_mc_corridor_resample, the matrix of erpl_mc_impact_points or of erpl_mc_debris, passed as it is, no copy - described
+ * with the int64 weight row erpl_mc_reweight writes.  Conventions of erpl_mc_corridor_bands: row (c, k) is the m doubles at
+ * values + (c * n_nodes + k) * ld, `mask` is uint8 [m] or NULL (a column counts iff its byte is 0), `weights` int64 [m]; all
+ * three are caller-owned device memory of which only the first m columns are read (the padding is never read).  spec, rows
+ * ([n_channels * n_nodes], row (c, k) at c * n_nodes + k) and result are host memory.  The work is enqueued on `hip_stream`
+ * and the call returns when rows and result are filled (two host waits: the first pass over the weights, then the rows); the
+ * workspace belongs to the context, grows only and is freed by erpl_mc_destroy.  The _host call is the same rule on host
+ * memory: no context, no device.
+ *
+ * Admitted weights (the rule of erpl_mc_impact_density_weighted): 0 <= W_i <= 2^Q with Q = min(52, 62 - ceil(log2 m)) for
+ * EVERY column, masked or not.  A first pass over the weight row finds max_w over all m columns and the lowest column whose
+ * weight is outside that range; such a column is ERPL_ERR_INVALID, named in the message, and no output has been written.
+ * K = the bit length of max_w and w_i = ldexp((double)W_i, -K).  All weights zero is no error: every row is empty.
+ *
+ * The population of a row is its OWN: mask byte 0, the value finite, W_i > 0; `count` members.  n_non_finite = mask byte 0
+ * and the value not finite; n_zero = mask byte 0, the value finite, W_i == 0.
+ * Exact (integer adds only, the same bits in every call and on the host): sum_w = sum W; exceed_w[j] = sum W [x >
+ * threshold[c][j]]; quantile q = the value at 0-based rank T - 1 of the multiset in which column i occurs W_i times with
+ * T = clamp((uint64) ceil(q * (double) sum_w), 1, sum_w), erpl_mc_reweight's expression:
+ * np.quantile(x, q, weights=W, method="inverted_cdf"), a value of the row, -0.0 sorting below +0.0; min and max.
+ * This is NOT the linear rule between two order statistics of erpl_mc_corridor_bands: under constant weights the two
+ * differ, and a quantile here is always a flown value.
+ * Doubles, with S_d = ldexp((double)sum_w, -K): mean = (sum w x) / S_d; var = (sum w (x - mean)^2) / S_d, std = sqrt(var);
+ * mean_se = sqrt(sum w^2 (x - mean)^2) / S_d; sum_w2 = sum w w, ess = S_d^2 / sum_w2; a2[j] = sum w^2 [x > threshold[c][j]]
+ * (p = exceed_w / sum_w and its standard error follow by erpl_mc_reweight's p_se formula with sum_w2 and a2).  Thread t of
+ * a row's workgroup adds the columns t, t + 256, .. in index order, the partials are folded in the fixed order of the
+ * statistics units, no floating-point atomics, no FMA contraction; the host twin adds the same terms in index order with a
+ * compensated sum.  The two agree as erpl_mc_reweight states it: 1e-12 relative, the mean to 1e-12 * sum W |x| / S.
+ * An empty row has its integers 0 and its doubles NaN, no error.  The bytes of a row's record depend on that row, the mask,
+ * the weights and the spec alone, not on which other rows are in the call.
+ *
+ * ERPL_ERR_INVALID before any device work, with a message that names the argument, in THIS order: a NULL spec; n_channels
+ * outside 1..ERPL_CORRIDOR_MAX_CHANNELS, n_nodes outside 1..ERPL_CORRIDOR_MAX_NODES, n_q outside 0..ERPL_RW_MAX_Q, a q
+ * outside [0, 1] or NaN, an n_thresholds outside 0..ERPL_BANDS_W_MAX_THRESHOLDS, a NaN threshold; NULL values, weights,
+ * rows, result; m <= 0 or m > 2^31 - 1; ld < m; the context last.
+ * One workgroup per row and ONE launch for all rows: a moments pass, a centred pass and the eight digit passes of the radix
+ * selection with W in the place of 1, the 64-bit histograms in LDS alone. */
+#define ERPL_BANDS_W_MAX_THRESHOLDS 4
+
+typedef struct erpl_bands_w_spec {
+  int32_t n_channels;                    /* 1..ERPL_CORRIDOR_MAX_CHANNELS */
+  int32_t n_nodes;                       /* 1..ERPL_CORRIDOR_MAX_NODES */
+  int32_t n_q;                           /* 0..ERPL_RW_MAX_Q */
+  int32_t reserved;
+  double q[ERPL_RW_MAX_Q];               /* each in [0, 1] */
+  int32_t n_thresholds[ERPL_CORRIDOR_MAX_CHANNELS];   /* per channel, 0..ERPL_BANDS_W_MAX_THRESHOLDS */
+  double threshold[ERPL_CORRIDOR_MAX_CHANNELS][ERPL_BANDS_W_MAX_THRESHOLDS];
+} erpl_bands_w_spec;
+
+typedef struct erpl_bands_w_row {        /* 224 bytes */
+  int64_t count, n_non_finite, n_zero;
+  int64_t sum_w;
+  int64_t exceed_w[ERPL_BANDS_W_MAX_THRESHOLDS];
+  double quantile[ERPL_RW_MAX_Q];
+  double min, max, mean, var, std, mean_se;
+  double sum_w2, ess;                    /* in the scaled weights w */
+  double a2[ERPL_BANDS_W_MAX_THRESHOLDS];
+} erpl_bands_w_row;
+
+typedef struct erpl_bands_w_result {
+  int64_t m, n_masked, n_counted;        /* n_counted = m - n_masked: the columns whose mask byte is 0 */
+  int64_t max_w;                         /* over all m columns */
+  int32_t K;                             /* the bit length of max_w */
+  int32_t Q;
+} erpl_bands_w_result;
+
+/* Host only: 5 / 25 / 50 / 75 / 95 %, no thresholds, n_channels = n_nodes = 0 (the caller fills them in). */
+int erpl_mc_corridor_bands_weighted_defaults(erpl_bands_w_spec* spec);
+int erpl_mc_corridor_bands_weighted(erpl_ctx* ctx, const double* values, const uint8_t* mask, const int64_t* weights, int64_t m,
+                                    int64_t ld, const erpl_bands_w_spec* spec, erpl_bands_w_row* rows,
+                                    erpl_bands_w_result* result, void* hip_stream);
+int erpl_mc_corridor_bands_weighted_host(const double* values, const uint8_t* mask, const int64_t* weights, int64_t m, int64_t ld,
+                                         const erpl_bands_w_spec* spec, erpl_bands_w_row* rows, erpl_bands_w_result* result);
+
 /* Known-answer evaluation ON THE DEVICE (tests): one function of the hot path per lane, through the
  * device functions the flight kernel of `batch->precision` inlines.  Case j (0 <= j < m) uses the
  * per-sample parameters and wind table of sample j % batch->n; in / out are device double arrays
