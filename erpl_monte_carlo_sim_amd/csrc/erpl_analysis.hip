@@ -115,12 +115,8 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_finish_first(const Er
     o.count = cnt; o.sum = sum; o.vmin = mn; o.vmax = mx; o.m2 = 0.0;
     o.mean = sum / (double)cnt;   // NaN for an empty row; the host reports every double of such a row as NaN
     // ranks of the two order statistics behind every quantile (np.percentile, linear)
-    ErplAnaSelect& s = w->sel[r];
-    for (int t = 0; t < ERPL_ANA_TARGETS; ++t) {
-      const unsigned long long rank = cnt > 0ull && t < 2 * a.n_q ? select_rank(cnt, a.q[t >> 1], t) : 0ull;
-      s.prefix[t] = 0ull; s.rank[t] = rank; s.leader[t] = 0;
-      o.key[t] = 0ull;
-    }
+    for (int t = 0; t < ERPL_ANA_TARGETS; ++t)
+      select_start(w->sel[r], o.key, t, cnt > 0ull && t < 2 * a.n_q ? select_rank(cnt, a.q[t >> 1], t) : 0ull);
   }
 }
 
@@ -130,73 +126,23 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_finish_second(const E
   if (threadIdx.x == 0) a.work->res.row[blockIdx.x].m2 = m2;
 }
 
-// ---- one selection pass: histogram of the digit at `shift` of the keys that match a target's prefix above it.  Targets
-// with the same prefix see the same keys: only the first of them (its leader) keeps a histogram.
+// ---- the selection (select_pass / select_step of erpl_stat_device.h): a digit pass over row rows[blockIdx.y], where a
+// valid finite value counts once; between the passes workgroup r settles the digit for row r
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_ana_histogram(const ErplAnaArgs a, const int shift) {
-  __shared__ unsigned int s_hist[ERPL_ANA_TARGETS][ERPL_ANA_BINS];   // 16 KB
-  __shared__ unsigned long long s_prefix[ERPL_ANA_TARGETS];
-  __shared__ int s_lead[ERPL_ANA_TARGETS];
-  __shared__ int s_nlead;
-  const int r = blockIdx.y, nt = 2 * a.n_q;
-  const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
+  const int r = blockIdx.y;
+  const int64_t n = a.n;
   const double* __restrict__ x = a.summary + (int64_t)a.rows[r] * n;
   const uint8_t* __restrict__ why = a.why;
-  const ErplAnaSelect& sel = a.work->sel[r];
-  for (int k = threadIdx.x; k < ERPL_ANA_TARGETS * ERPL_ANA_BINS; k += ERPL_ANA_BLOCK) (&s_hist[0][0])[k] = 0u;
-  if (threadIdx.x == 0) {
-    int m = 0;
-    for (int t = 0; t < nt; ++t)
-      if (sel.leader[t] == t) { s_lead[m] = t; s_prefix[m] = sel.prefix[t]; ++m; }
-    s_nlead = m;
-  }
-  __syncthreads();
-  const int nlead = s_nlead;
-  const int64_t first = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + (threadIdx.x & ~63);
-  for (int64_t base = first; base < n; base += stride) {   // uniform over the wave (ballots below)
-    const int64_t i = base + (threadIdx.x & 63);
-    bool use = false;
-    unsigned long long key = 0ull;
-    if (i < n) {
-      const double v = x[i];
-      use = why[i] == 0 && finite_bits(v);
-      key = key_of_signed(v);
-    }
-    select_count(s_hist, s_lead, s_prefix, nlead, use, key, shift);
-  }
-  __syncthreads();
-  for (int m = 0; m < nlead; ++m) {
-    const int t = s_lead[m];
-    for (int b = threadIdx.x; b < ERPL_ANA_BINS; b += ERPL_ANA_BLOCK) {
-      const unsigned int c = s_hist[t][b];
-      if (c) atomicAdd(&a.work->hist[r][t][b], (unsigned long long)c);
-    }
-  }
+  select_pass<unsigned int>(a.work->sel[r], a.work->hist[r], 2 * a.n_q, n, shift, [=](int64_t i, u64* key, unsigned int*) {
+    const double v = x[i];
+    *key = key_of_signed(v);
+    return why[i] == 0 && finite_bits(v);
+  });
 }
 
-// ---- between the passes: wave t of workgroup r scans the histogram of target t's group, fixes the digit that holds its
-// rank and reduces the rank to that bin; then the groups are formed again and the histograms are cleared.
 __global__ __launch_bounds__(64 * ERPL_ANA_TARGETS) void erpl_ana_scan(const ErplAnaArgs a, const int shift) {
-  __shared__ unsigned long long s_prefix[ERPL_ANA_TARGETS];
-  const int r = blockIdx.x, t = threadIdx.x >> 6, lane = threadIdx.x & 63, nt = 2 * a.n_q;
-  ErplAnaSelect& sel = a.work->sel[r];
-  if (t < nt) {
-    const unsigned long long* h = a.work->hist[r][sel.leader[t]];
-    const unsigned long long rank = sel.rank[t];
-    unsigned long long prefix = sel.prefix[t], before = 0ull;
-    int d = 0;
-    if (lane == 0) s_prefix[t] = prefix;   // stays if no bin holds the rank: an empty row
-    if (select_scan(h, rank, lane, &d, &before)) {   // exactly one lane
-      prefix |= (unsigned long long)d << shift;
-      sel.prefix[t] = prefix;
-      sel.rank[t] = rank - before;
-      a.work->res.row[r].key[t] = prefix;
-      s_prefix[t] = prefix;
-    }
-  }
-  __syncthreads();   // every histogram has been read, every prefix is known
-  if (lane == 0 && t < nt) sel.leader[t] = select_leader(s_prefix, t);
-  unsigned long long* h = &a.work->hist[r][0][0];
-  for (int k = threadIdx.x; k < ERPL_ANA_TARGETS * ERPL_ANA_BINS; k += 64 * ERPL_ANA_TARGETS) h[k] = 0ull;
+  const int r = blockIdx.x;
+  select_step(a.work->sel[r], a.work->hist[r], a.work->res.row[r].key, 2 * a.n_q, shift);
 }
 
 }  // namespace

@@ -120,33 +120,13 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corridor_resample(const E
 // ---- bands: row blockIdx.x of the matrix through the moments and the selection of a described row
 
 // One workgroup reads a whole row and only 768 of them exist with the default spec, so every pass keeps kBandLoads loads
-// per thread in flight: the values i0, i0 + 256, .. of the row, ok[k] = the column exists and counts.  A value past the
-// row is 0.0, never read from memory.
+// per thread in flight (band_fetch of erpl_stat_device.h).
 constexpr int kBandLoads = 4;
-__device__ __forceinline__ void band_fetch(const double* __restrict__ x, const uint8_t* __restrict__ mask, int64_t m, int64_t i0,
-                                           double (&v)[kBandLoads], bool (&ok)[kBandLoads]) {
-  uint8_t byte[kBandLoads];
-#pragma unroll
-  for (int k = 0; k < kBandLoads; ++k) {
-    const int64_t i = i0 + (int64_t)k * ERPL_ANA_BLOCK;
-    ok[k] = i < m;
-    v[k] = ok[k] ? x[i] : 0.0;
-    byte[k] = ok[k] && mask ? mask[i] : (uint8_t)0;
-  }
-#pragma unroll
-  for (int k = 0; k < kBandLoads; ++k) ok[k] = ok[k] && byte[k] == 0;
-}
 
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corridor_bands(const ErplCorridorBandsArgs a) {
-  __shared__ unsigned int s_hist[ERPL_ANA_TARGETS][ERPL_ANA_BINS];   // 16 KB
-  __shared__ u64 s_prefix[ERPL_ANA_TARGETS], s_rank[ERPL_ANA_TARGETS];   // per target
-  __shared__ int s_leader[ERPL_ANA_TARGETS];
-  __shared__ u64 s_lead_prefix[ERPL_ANA_TARGETS];                    // per group
-  __shared__ int s_lead[ERPL_ANA_TARGETS];
-  __shared__ int s_nlead;
   __shared__ double s_mean;
   __shared__ u64 s_cnt;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nt = 2 * a.n_q;
+  const int tid = threadIdx.x;
   const int64_t m = a.m;
   const double* __restrict__ x = a.values + (int64_t)blockIdx.x * a.ld;
   const uint8_t* __restrict__ mask = a.mask;
@@ -202,50 +182,9 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_corridor_bands(const Erpl
   block_fold<Add>(m2);
   if (tid == 0) o.m2 = m2;
 
-  // selection: every target starts with no digit fixed, in one group
-  if (tid < ERPL_ANA_TARGETS) {
-    s_prefix[tid] = 0ull;
-    s_rank[tid] = count > 0ull && tid < nt ? select_rank(count, a.q[tid >> 1], tid) : 0ull;
-  }
-  if (count > 0ull && nt > 0) {   // (uniform over the workgroup)
-    for (int shift = 56; shift >= 0; shift -= 8) {
-      __syncthreads();   // the prefixes of the pass before are in place, its histograms have been read
-      for (int k = tid; k < ERPL_ANA_TARGETS * ERPL_ANA_BINS; k += ERPL_ANA_BLOCK) (&s_hist[0][0])[k] = 0u;
-      if (tid < nt) s_leader[tid] = select_leader(s_prefix, tid);
-      __syncthreads();
-      if (tid == 0) {
-        int g = 0;
-        for (int t = 0; t < nt; ++t)
-          if (s_leader[t] == t) { s_lead[g] = t; s_lead_prefix[g] = s_prefix[t]; ++g; }
-        s_nlead = g;
-      }
-      __syncthreads();
-      const int nlead = s_nlead;
-      // uniform over the wave (ballots): every lane makes every call, a lane past the row brings no key
-      for (int64_t base = (int64_t)wave * 64; base < m; base += kBandLoads * ERPL_ANA_BLOCK) {
-        double v[kBandLoads];
-        bool ok[kBandLoads];
-        band_fetch(x, mask, m, base + lane, v, ok);
-#pragma unroll
-        for (int k = 0; k < kBandLoads; ++k)
-          select_count(s_hist, s_lead, s_lead_prefix, nlead, ok[k] && finite_bits(v[k]), key_of_signed(v[k]), shift);
-      }
-      __syncthreads();
-      // wave w scans for the targets w, w + kWaves, ..: the digit that holds the rank, the rank within that bin
-      for (int t = wave; t < nt; t += kWaves) {
-        int d = 0;
-        u64 below = 0ull;
-        if (select_scan(s_hist[s_leader[t]], s_rank[t], lane, &d, &below)) {   // exactly one lane
-          s_prefix[t] |= (u64)d << shift;
-          s_rank[t] -= below;
-        }
-      }
-    }
-    __syncthreads();
-  } else {
-    __syncthreads();
-  }
-  if (tid < ERPL_ANA_TARGETS) o.key[tid] = tid < nt ? s_prefix[tid] : 0ull;
+  // the selection: the two order statistics behind every quantile, among the finite unmasked values
+  select_row<ERPL_ANA_TARGETS, kBandLoads>(x, mask, m, 2 * a.n_q, count,
+                                           [&](int t) { return select_rank(count, a.q[t >> 1], t); }, o.key);
 }
 
 }  // namespace

@@ -7,9 +7,12 @@
 //                             a weight outside 0 .. 2^Q refuses the call before a row record is written, and K is settled.
 //   bw_rows                   THE hot kernel, one workgroup per row and one launch for all rows, the shape of
 //                             erpl_corridor_bands: a moments pass, a centred pass, then the eight digit passes of the radix
-//                             selection of erpl_stat_device.h with W in the place of 1 (select_count_weighted, select_scan), its
-//                             64-bit histograms in LDS alone (16 KB), one target per quantile.  A row is read ten times by one
+//                             selection of erpl_stat_device.h with W in the place of 1 (select_count on 64-bit bins, select_scan),
+//                             its 64-bit histograms in LDS alone (16 KB), one target per quantile.  A row is read ten times by one
 //                             workgroup, so every pass keeps kLoads columns per thread in flight, the weight next to the value.
+//                             The eight passes are select_row of erpl_stat_device.h written out with a weight: the shared body
+//                             measured a little slower here (profiles/select_refactor_ab.json) and no cause was found, so the
+//                             kernel stays as it was.  A fix to the pass structure there has to be made here as well.
 // Sums are accumulated per thread in index order (thread t: t, t + 256, ..) and folded in the fixed order of
 // erpl_stat_device.h: the order depends on m alone.  Integer LDS atomics only.  Compiled with -ffp-contract=off: w * x,
 // (x - mean)^2 and the products with w round once each, as the host twin rounds them.
@@ -210,8 +213,8 @@ __global__ __launch_bounds__(kBlock) void bw_rows(const BwArgs a) {
         bw_fetch(x, wt, mask, m, base + lane, v, W, ok);
 #pragma unroll
         for (int k = 0; k < kLoads; ++k)
-          select_count_weighted(s_hist, s_lead, s_lead_prefix, nlead, ok[k] && finite_bits(v[k]) && W[k] != 0ull, key_of_signed(v[k]),
-                                shift, W[k]);
+          select_count(s_hist, s_lead, s_lead_prefix, nlead, ok[k] && finite_bits(v[k]) && W[k] != 0ull, key_of_signed(v[k]), shift,
+                       W[k]);
       }
       __syncthreads();
       // wave w scans for the targets w, w + kWaves, ..: the digit that holds the rank, the rank within that bin

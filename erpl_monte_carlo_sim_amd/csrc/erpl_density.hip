@@ -14,7 +14,8 @@
 //             ERPL_DENS_TILE queries - ERPL_DENS_Q per thread, independent exp chains side by side - and one slice of the
 //             sources, staged through a 16 KB LDS tile and read back at one address per wave (a broadcast).  Per pair two
 //             subtractions, one product, one explicit FMA (the unit is built without contraction), one product by -0.5,
-//             ocml's exp and one addition.
+//             ocml's exp and one addition.  The weighted map (erpl_density_w.hip) runs the same kernel with a weight per
+//             source: a 24 KB tile, and an explicit FMA in the place of the addition.
 //   fold      the slices of a query added in slice order, times the normalisation; the sample pass scatters to the row
 //   zones     one streaming pass: the even-odd crossing rule against the vertices (staged in LDS), ballots and popcounts
 //   peak      sum and maximum of the nodes, then the first node that holds the maximum, by fixed-order folds
@@ -144,10 +145,15 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dens_nodes(const ErplDens
 
 // ---- pairs: workgroup (bx, by) adds the sources by * per_slice .. min(m, (by + 1) * per_slice) - 1, in index order, for
 // the queries bx * ERPL_DENS_TILE + k * ERPL_ANA_BLOCK + thread, k < ERPL_DENS_Q, into partial[by][query].
+// WEIGHTED (erpl_mc_impact_density_weighted): source j counts ws[j] times - its weight rides in the LDS tile, (u, v, w) and
+// 24 KB, and the addition becomes one explicit FMA, acc = fma(w, exp(-0.5 e), acc).  Otherwise ws is not looked at.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dens_pairs(const double2* __restrict__ qry, const int64_t nq,
-                                                                  const double2* __restrict__ src, const int64_t m,
-                                                                  const int64_t per_slice, double* __restrict__ partial) {
+                                                                  const double2* __restrict__ src, const double* __restrict__ ws,
+                                                                  const int64_t m, const int64_t per_slice,
+                                                                  double* __restrict__ partial) {
   __shared__ double2 s_src[ERPL_DENS_TILE];
+  __shared__ double s_w[WEIGHTED ? ERPL_DENS_TILE : 1];   // (unused, and gone, without weights)
   const int tid = threadIdx.x;
   const int64_t q0 = (int64_t)blockIdx.x * ERPL_DENS_TILE + tid;
   const int64_t first = (int64_t)blockIdx.y * per_slice;
@@ -162,15 +168,20 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void erpl_dens_pairs(const double2*
   for (int64_t base = first; base < last; base += ERPL_DENS_TILE) {
     const int cnt = (int)(last - base < ERPL_DENS_TILE ? last - base : ERPL_DENS_TILE);
     __syncthreads();   // the tile before has been read
-    for (int j = tid; j < cnt; j += ERPL_ANA_BLOCK) s_src[j] = src[base + j];
+    for (int j = tid; j < cnt; j += ERPL_ANA_BLOCK) {
+      s_src[j] = src[base + j];
+      if (WEIGHTED) s_w[j] = ws[base + j];
+    }
     __syncthreads();
     for (int j = 0; j < cnt; ++j) {
       const double2 s = s_src[j];   // one address per wave: a broadcast
+      const double wj = WEIGHTED ? s_w[j] : 1.0;
 #pragma unroll
       for (int k = 0; k < ERPL_DENS_Q; ++k) {
         const double du = qu[k] - s.x, dv = qv[k] - s.y;
         const double e = __builtin_fma(dv, dv, du * du);
-        acc[k] += exp(-0.5 * e);
+        if (WEIGHTED) acc[k] = __builtin_fma(wj, exp(-0.5 * e), acc[k]);
+        else acc[k] += exp(-0.5 * e);
       }
     }
   }
@@ -321,16 +332,30 @@ int erpl_launch_dens_nodes(const ErplDensWork* work, int nx, int ny, const ErplD
   return (int)hipGetLastError();
 }
 
-int erpl_launch_dens_pairs(const double* qry, int64_t queries, const double* src, int64_t m, double norm, double* partial,
-                           double* out, const uint32_t* scatter, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
+// the pair kernel over the slices of erpl_dens_slices; returns their number
+template <bool WEIGHTED>
+static int launch_pairs(const double* qry, int64_t queries, const double* src, const double* ws, int64_t m, double* partial,
+                        hipStream_t st) {
   int64_t per_slice = 0;
   const int slices = erpl_dens_slices(m, queries, &per_slice);
   const int64_t blocks = (queries + ERPL_DENS_TILE - 1) / ERPL_DENS_TILE;
-  hipLaunchKernelGGL(erpl_dens_pairs, dim3((unsigned)blocks, (unsigned)slices), dim3(ERPL_ANA_BLOCK), 0, st,
-                     (const double2*)qry, queries, (const double2*)src, m, per_slice, partial);
+  hipLaunchKernelGGL(erpl_dens_pairs<WEIGHTED>, dim3((unsigned)blocks, (unsigned)slices), dim3(ERPL_ANA_BLOCK), 0, st,
+                     (const double2*)qry, queries, (const double2*)src, ws, m, per_slice, partial);
+  return slices;
+}
+
+int erpl_launch_dens_pairs(const double* qry, int64_t queries, const double* src, int64_t m, double norm, double* partial,
+                           double* out, const uint32_t* scatter, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int slices = launch_pairs<false>(qry, queries, src, nullptr, m, partial, st);
   hipLaunchKernelGGL(erpl_dens_fold, dim3(grid_of(queries)), dim3(ERPL_ANA_BLOCK), 0, st, partial, slices, queries, norm, out,
                      scatter);
+  return (int)hipGetLastError();
+}
+
+int erpl_launch_densw_pairs(const double* qry, int64_t queries, const double* src, const double* ws, int64_t m, double* partial,
+                            void* stream) {
+  launch_pairs<true>(qry, queries, src, ws, m, partial, (hipStream_t)stream);
   return (int)hipGetLastError();
 }
 

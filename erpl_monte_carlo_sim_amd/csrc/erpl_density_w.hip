@@ -1,6 +1,7 @@
 // erpl_density_w.hip — the device passes of erpl_mc_impact_density_weighted: the impact probability map of a flown run under
 // another law, every sample with the integer weight erpl_mc_reweight gave it.  The passes are those of erpl_density.hip;
-// whiten, nodes, fold, peak and fill_nan ARE its launchers (on the ErplDensWork inside ErplDensWWork), the rest is here:
+// whiten, nodes, fold, peak and fill_nan ARE its launchers (on the ErplDensWork inside ErplDensWWork), and so is the pair
+// kernel (erpl_launch_densw_pairs: the weighted instantiation of erpl_dens_pairs).  The rest is here:
 //
 //   population  one streaming pass: the byte of every sample (0 = counted: mask byte 0, both rows finite, W > 0), the counts
 //               in the order of the header, sum W and max W over the counted samples and the lowest column whose weight is
@@ -9,14 +10,11 @@
 //   moments     two passes over the dense arrays on the grid of the count: sum w x, sum w y, sum w w and the extremes, then
 //               sum w (dx dx), w (dx dy), w (dy dy) about the mean read on the device
 //   zones       over the dense points before they are whitened: per polygon sum W (integers: W = w 2^K, exact) and sum w w
-//   pairs       THE hot loop, the shape of erpl_dens_pairs: ERPL_DENS_TILE queries per workgroup, ERPL_DENS_Q per thread, the
-//               sources staged through a 24 KB LDS tile of (u, v, w) and read back at one address per wave.  Per pair what
-//               erpl_dens_pairs issues with the addition replaced by one explicit FMA: acc = fma(w, exp(-0.5 e), acc)
-//   regions     the most-significant-digit radix selection of erpl_reweight.hip over the f_j with W_j in the place of 1
-//               (select_count_weighted / select_scan of erpl_stat_device.h: 64-bit bins in LDS flushed to 64-bit global bins,
-//               a scan kernel between the passes), then one pass for sum W [f >= t_k], min f and max f
+//   regions     the radix selection of erpl_stat_device.h in its global-bin form over the f_j, sample j counting W_j times
+//               (64-bit bins in LDS flushed to 64-bit global bins, a scan kernel between the passes), then one pass for
+//               sum W [f >= t_k], min f and max f
 // The order of every floating-point sum is fixed (erpl_stat_device.h; erpl_dens_slices for the pairs); the integer sums
-// commute.  Integer atomics only (the histograms).  Compiled with -ffp-contract=off: the FMAs are written out.
+// commute.  Integer atomics only (the histograms).  Compiled with -ffp-contract=off: every product of a sum rounds once.
 #include "erpl_stat_device.h"
 #include "erpl_reweight.h"
 
@@ -207,126 +205,29 @@ __global__ __launch_bounds__(ERPL_ANA_BLOCK) void dw_finish_zones(ErplDensWWork*
   }
 }
 
-// ---- pairs: workgroup (bx, by) adds the sources by * per_slice .. min(m, (by + 1) * per_slice) - 1, in index order, for
-// the queries bx * ERPL_DENS_TILE + k * ERPL_ANA_BLOCK + thread, k < ERPL_DENS_Q, into partial[by][query].
-__global__ __launch_bounds__(ERPL_ANA_BLOCK) void dw_pairs(const double2* __restrict__ qry, const int64_t nq,
-                                                           const double2* __restrict__ src, const double* __restrict__ ws,
-                                                           const int64_t m, const int64_t per_slice, double* __restrict__ partial) {
-  __shared__ double2 s_src[ERPL_DENS_TILE];
-  __shared__ double s_w[ERPL_DENS_TILE];
-  const int tid = threadIdx.x;
-  const int64_t q0 = (int64_t)blockIdx.x * ERPL_DENS_TILE + tid;
-  const int64_t first = (int64_t)blockIdx.y * per_slice;
-  const int64_t last = first + per_slice < m ? first + per_slice : m;
-  double qu[ERPL_DENS_Q], qv[ERPL_DENS_Q], acc[ERPL_DENS_Q];
-#pragma unroll
-  for (int k = 0; k < ERPL_DENS_Q; ++k) {
-    const int64_t q = q0 + (int64_t)k * ERPL_ANA_BLOCK;
-    const double2 p = q < nq ? qry[q] : make_double2(0.0, 0.0);   // a lane without a query computes and stores nothing
-    qu[k] = p.x; qv[k] = p.y; acc[k] = 0.0;
-  }
-  for (int64_t base = first; base < last; base += ERPL_DENS_TILE) {
-    const int cnt = (int)(last - base < ERPL_DENS_TILE ? last - base : ERPL_DENS_TILE);
-    __syncthreads();   // the tile before has been read
-    for (int j = tid; j < cnt; j += ERPL_ANA_BLOCK) { s_src[j] = src[base + j]; s_w[j] = ws[base + j]; }
-    __syncthreads();
-    for (int j = 0; j < cnt; ++j) {
-      const double2 s = s_src[j];   // one address per wave: a broadcast
-      const double wj = s_w[j];
-#pragma unroll
-      for (int k = 0; k < ERPL_DENS_Q; ++k) {
-        const double du = qu[k] - s.x, dv = qv[k] - s.y;
-        const double e = __builtin_fma(dv, dv, du * du);
-        acc[k] = __builtin_fma(wj, exp(-0.5 * e), acc[k]);
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < ERPL_DENS_Q; ++k) {
-    const int64_t q = q0 + (int64_t)k * ERPL_ANA_BLOCK;
-    if (q < nq) partial[(int64_t)blockIdx.y * nq + q] = acc[k];
-  }
-}
-
-// ---- regions: the weighted selection over the f_j
+// ---- regions: the weighted selection over the f_j (erpl_stat_device.h, global bins)
 
 // every target in one group (no digit is fixed yet), its rank from the host, the histograms empty
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void dw_select_init(ErplDensWWork* w, const DwTargets t) {
-  if (threadIdx.x < kL) {
-    w->sel.prefix[threadIdx.x] = 0ull;
-    w->sel.leader[threadIdx.x] = 0;
-    w->sel.rank[threadIdx.x] = (int)threadIdx.x < t.n_levels ? t.rank[threadIdx.x] : 0ull;
-    w->out.key[threadIdx.x] = 0ull;
-  }
-  u64* h = &w->hist[0][0];
-  for (int k = threadIdx.x; k < kL * ERPL_ANA_BINS; k += ERPL_ANA_BLOCK) h[k] = 0ull;
+  if (threadIdx.x < kL) select_start(w->sel, w->out.key, threadIdx.x, (int)threadIdx.x < t.n_levels ? t.rank[threadIdx.x] : 0ull);
+  select_clear<ERPL_ANA_BLOCK>(&w->hist[0][0], kL * ERPL_ANA_BINS);
 }
 
-// One pass: per group of targets that still share a key prefix, the weight in every value of the digit at `shift` among the
-// keys that match the prefix above it.  Only the first target of a group (its leader) keeps a histogram.
+// a digit pass over the row: a counted sample of non-zero weight counts W times
 __global__ __launch_bounds__(ERPL_ANA_BLOCK) void dw_hist(const ErplDensWArgs a, const double* __restrict__ row, const int n_levels,
                                                           const int shift) {
-  __shared__ u64 s_hist[kL][ERPL_ANA_BINS];      // 16 KB
-  __shared__ u64 s_prefix[kL];
-  __shared__ int s_lead[kL];
-  __shared__ int s_nlead;
-  const int64_t n = a.n, stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
   const int64_t* __restrict__ wt = a.weights;
   const uint8_t* __restrict__ pop = a.pop;
-  const ErplDensWSelect& sel = a.work->sel;
-  for (int k = threadIdx.x; k < kL * ERPL_ANA_BINS; k += ERPL_ANA_BLOCK) (&s_hist[0][0])[k] = 0ull;
-  if (threadIdx.x == 0) {
-    int g = 0;
-    for (int t = 0; t < n_levels; ++t)
-      if (sel.leader[t] == t) { s_lead[g] = t; s_prefix[g] = sel.prefix[t]; ++g; }
-    s_nlead = g;
-  }
-  __syncthreads();
-  const int nlead = s_nlead;
-  const int64_t first = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + (threadIdx.x & ~63);
-  for (int64_t base = first; base < n; base += stride) {   // uniform over the wave (ballots below)
-    const int64_t i = base + (threadIdx.x & 63);
-    u64 wi = 0ull, key = 0ull;
-    if (i < n && pop[i] == 0) {
-      wi = (u64)wt[i];
-      key = key_of_signed(row[i]);
-    }
-    select_count_weighted(s_hist, s_lead, s_prefix, nlead, wi != 0ull, key, shift, wi);
-  }
-  __syncthreads();
-  for (int g = 0; g < nlead; ++g) {
-    const int t = s_lead[g];
-    for (int b = threadIdx.x; b < ERPL_ANA_BINS; b += ERPL_ANA_BLOCK) {
-      const u64 c = s_hist[t][b];
-      if (c) atomicAdd(&a.work->hist[t][b], c);
-    }
-  }
+  select_pass<u64>(a.work->sel, a.work->hist, n_levels, a.n, shift, [=](int64_t i, u64* key, u64* w) {
+    if (pop[i] != 0) return false;
+    *w = (u64)wt[i];
+    *key = key_of_signed(row[i]);
+    return *w != 0ull;
+  });
 }
 
-// Between the passes: wave t scans the histogram of target t's group, fixes the digit that holds its rank and reduces the rank
-// to that bin; then the groups are formed again and the histograms are cleared.
 __global__ __launch_bounds__(64 * kL) void dw_scan(ErplDensWWork* w, const int n_levels, const int shift) {
-  __shared__ u64 s_prefix[kL];
-  const int t = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  ErplDensWSelect& sel = w->sel;
-  if (t < n_levels) {
-    const u64* h = w->hist[sel.leader[t]];
-    const u64 rank = sel.rank[t];
-    u64 prefix = sel.prefix[t], before = 0ull;
-    int d = 0;
-    if (lane == 0) s_prefix[t] = prefix;             // stays if no bin holds the rank
-    if (select_scan(h, rank, lane, &d, &before)) {   // exactly one lane
-      prefix |= (u64)d << shift;
-      sel.prefix[t] = prefix;
-      sel.rank[t] = rank - before;
-      w->out.key[t] = prefix;
-      s_prefix[t] = prefix;
-    }
-  }
-  __syncthreads();   // every histogram has been read, every prefix is known
-  if (lane == 0 && t < n_levels) sel.leader[t] = select_leader(s_prefix, t);
-  u64* h = &w->hist[0][0];
-  for (int k = threadIdx.x; k < kL * ERPL_ANA_BINS; k += 64 * kL) h[k] = 0ull;
+  select_step(w->sel, w->hist, w->out.key, n_levels, shift);
 }
 
 // the weight at or above every threshold, and the extremes of the f_j
@@ -400,16 +301,6 @@ int erpl_launch_densw_zones(const ErplDensWArgs& a, const double* xy, const doub
   const int nb = grid_of(m);
   hipLaunchKernelGGL(dw_zones, dim3(nb), dim3(ERPL_ANA_BLOCK), 0, st, a.work, a.n_zones, (const double2*)xy, ws, m);
   hipLaunchKernelGGL(dw_finish_zones, dim3(1), dim3(ERPL_ANA_BLOCK), 0, st, a.work, a.n_zones, nb);
-  return (int)hipGetLastError();
-}
-
-int erpl_launch_densw_pairs(const double* qry, int64_t queries, const double* src, const double* ws, int64_t m, double* partial,
-                            void* stream) {
-  int64_t per_slice = 0;
-  const int slices = erpl_dens_slices(m, queries, &per_slice);
-  const int64_t blocks = (queries + ERPL_DENS_TILE - 1) / ERPL_DENS_TILE;
-  hipLaunchKernelGGL(dw_pairs, dim3((unsigned)blocks, (unsigned)slices), dim3(ERPL_ANA_BLOCK), 0, (hipStream_t)stream,
-                     (const double2*)qry, queries, (const double2*)src, ws, m, per_slice, partial);
   return (int)hipGetLastError();
 }
 

@@ -13,8 +13,9 @@
 //   rw_rows<false>     rows in blockIdx.y: sum W x, min, max, per threshold sum W [x > thr] and sum W^2 [x > thr]
 //   rw_finish_rows     a workgroup per row: the mean, and the ranks of the order statistics
 //   rw_rows<true>      sum W (x - mean)^2, sum W^2 (x - mean)^2 with the mean read on the device, and their finish
-//   rw_hist / rw_scan  the most-significant-digit radix selection of erpl_analysis.hip with W in the place of 1: eight passes
-//                      of one 8-bit digit, 64-bit bins in LDS flushed to 64-bit global bins, a scan kernel between them
+//   rw_hist / rw_scan  the radix selection of erpl_stat_device.h in its global-bin form, a column counting W times: eight
+//                      passes of one 8-bit digit, 64-bit bins in LDS flushed to 64-bit global bins, a scan kernel between them
+//                      (this unit's own copy of select_pass / select_step around the shared steps: see at the kernels)
 // What binds them (DESIGN.md section 8.17 has the measurements, or says UNMEASURED): rw_logw reads 8 (n_law + rows) + 1 bytes
 // per column and writes 8, every later pass reads 8 or 16 and the weights pass writes 8 - HBM bytes above some 10^6 columns,
 // launch latency below (24 launches).
@@ -28,10 +29,7 @@ constexpr int kBlock = ERPL_ANA_BLOCK;          // 256: the folds of erpl_stat_d
 constexpr int kMaxBlocks = ERPL_ANA_MAX_BLOCKS;
 constexpr int kR = ERPL_RW_MAX_ROWS, kT = ERPL_RW_MAX_THRESHOLDS, kQ = ERPL_RW_MAX_Q;
 
-struct RwSelect {
-  u64 prefix[kQ], rank[kQ];
-  int32_t leader[kQ];
-};
+typedef ErplSelect<kQ> RwSelect;
 
 // the device workspace in front of the two column arrays (erpl_rw_layout): what the call hands back, the state of the
 // selection, and a slot per workgroup for every partial
@@ -224,6 +222,10 @@ __global__ __launch_bounds__(kBlock) void rw_finish_rows(const RwArgs a, const i
 
 // ---------------------------------------------------------------- the weighted selection
 
+// These two kernels are select_pass / select_step of erpl_stat_device.h written out: with the shared bodies the call at
+// 131 072 columns measured 2.8 % slower than with these (profiles/select_refactor_ab.json), and no cause was found in the
+// assembly, so they stay as they were.  A fix to the pass structure there has to be made here as well.
+
 // One pass: per group of targets that still share a key prefix, the weight in every value of the digit at `shift` among the
 // keys that match the prefix above it.  Only the first target of a group (its leader) keeps a histogram.
 __global__ __launch_bounds__(kBlock) void rw_hist(const RwArgs a, const int shift) {
@@ -252,7 +254,7 @@ __global__ __launch_bounds__(kBlock) void rw_hist(const RwArgs a, const int shif
       wi = (u64)wt[i];
       if (wi) key = key_of_signed(erpl_rw_outcome(a.summary, a.ld_s, a.extra, row, i));
     }
-    select_count_weighted(s_hist, s_lead, s_prefix, nlead, wi != 0ull, key, shift, wi);
+    select_count(s_hist, s_lead, s_prefix, nlead, wi != 0ull, key, shift, wi);
   }
   __syncthreads();
   for (int m = 0; m < nlead; ++m) {

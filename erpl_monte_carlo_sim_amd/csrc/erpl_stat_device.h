@@ -2,7 +2,9 @@
 // erpl_bootstrap.hip, erpl_density.hip, erpl_corridor.hip, erpl_sobol.hip, erpl_dependence.hip, erpl_compare.hip,
 // erpl_reweight.hip, erpl_density_w.hip, erpl_corridor_depth.hip, erpl_corridor_w.hip) share:
 // the grid of their streaming passes, the order-preserving keys, the run of equal keys behind a mid-rank, THE fixed-order
-// reduction and the steps of the radix selection.
+// reduction and THE radix selection: its single steps (erpl_subset.hip and erpl_compare.hip select one target with them)
+// and, around them, the passes of units that select many (erpl_analysis.hip, erpl_density_w.hip with bins in global
+// memory; erpl_corridor.hip with bins in LDS alone; erpl_reweight.hip and erpl_corridor_w.hip keep copies of their own).
 // Internal: never installed.
 //
 // The order is the contract: the last bit of every sum and the sign of a zero minimum depend on it, and "the same bits in
@@ -179,9 +181,18 @@ __device__ __forceinline__ u64 counters_fold(const u64 (&cnt)[K]) {
   return s;
 }
 
-// ---- the most-significant-digit radix selection of erpl_analysis.hip and erpl_corridor.hip: one 8-bit digit per pass, a
-// histogram per group of targets that still share a key prefix.  The units differ in where the histograms live (64-bit
-// global bins behind LDS tiles there, LDS alone here); what a pass decides is written once, below.
+// ---- the most-significant-digit radix selection: all order statistics of a row together, one 8-bit digit per pass, a
+// histogram per group of targets that still share a key prefix.  A key counts once (32-bit LDS bins) or with an integer
+// weight (64-bit bins).  The single steps come first; erpl_subset.hip and erpl_compare.hip, which select one target,
+// call them directly.  The passes around them are written here, in two forms:
+//   global bins     the row is streamed by grid_of(n) workgroups, whose LDS histograms are flushed to 64-bit global bins;
+//                   one kernel per digit (select_pass) and one between the digits (select_step), the state in an
+//                   ErplSelect: erpl_analysis.hip, erpl_density_w.hip
+//   LDS alone       one workgroup owns the row and runs the eight digits inside one kernel (select_row): erpl_corridor.hip
+// The callers bring what differs: how a column yields (use, key, weight), and the rule that turns a quantile into a rank.
+// Three copies of these passes remain outside, each around the shared steps: rw_hist / rw_scan of erpl_reweight.hip and the
+// last third of bw_rows of erpl_corridor_w.hip, which measured slower with the shared bodies (profiles/
+// select_refactor_ab.json), and the replicate kernel of erpl_bootstrap.hip, which selects on 32-bit positions.
 
 // The rank of target t among the cnt > 0 counted values of a row: targets 2 i and 2 i + 1 are the two order statistics
 // behind quantile q (np.percentile, linear): lo = floor(q (cnt - 1)) and min(lo + 1, cnt - 1).
@@ -194,8 +205,17 @@ __device__ __forceinline__ u64 select_rank(u64 cnt, double q, int t) {
 
 // One key into the LDS histograms of a pass: hist[lead[m]] counts the digit at `shift` of the keys that match
 // prefix[m] above it, m < nlead.  Every lane of the wave calls it (ballots); use = false: the lane brings no key.
-__device__ __forceinline__ void select_count(unsigned int (*hist)[ERPL_ANA_BINS], const int* lead, const u64* prefix, int nlead,
-                                             bool use, u64 key, int shift) {
+// Count is the type of an LDS bin and decides what a key counts for:
+//   unsigned int   once; w is not looked at
+//   u64            w times (an integer weight)
+// Heavily tied data puts a whole wave into one bin: then the wave makes one add instead of 64 serialised ones - of the
+// lane count, by the leading lane, or of the weights added up with a shuffle tree (integer adds: the order does not
+// matter), by lane 0.
+template <class Count>
+__device__ __forceinline__ void select_count(Count (*hist)[ERPL_ANA_BINS], const int* lead, const u64* prefix, int nlead, bool use,
+                                             u64 key, int shift, Count w) {
+  constexpr bool kOnce = std::is_same<Count, unsigned int>::value;
+  static_assert(kOnce || std::is_same<Count, u64>::value, "32-bit bins count keys, 64-bit bins add weights");
   // bits above the digit of this pass (none in the first pass: every key matches)
   const u64 above = shift >= 56 ? 0ull : (~0ull << (shift + 8));
   const unsigned int digit = (unsigned int)(key >> shift) & (ERPL_ANA_BINS - 1);
@@ -203,35 +223,18 @@ __device__ __forceinline__ void select_count(unsigned int (*hist)[ERPL_ANA_BINS]
     const bool hit = use && ((key ^ prefix[m]) & above) == 0ull;
     const u64 mask = __ballot(hit);
     if (mask == 0ull) continue;
-    // heavily tied data puts a whole wave into one bin: one add of the lane count instead of 64 serialised ones
     const int lead_lane = __ffsll((long long)mask) - 1;
     const unsigned int d0 = (unsigned int)__shfl((int)digit, lead_lane);
     if (__ballot(hit && digit != d0) == 0ull) {
-      if ((int)(threadIdx.x & 63) == lead_lane) atomicAdd(&hist[lead[m]][d0], (unsigned int)__popcll(mask));
-    } else if (hit) {
-      atomicAdd(&hist[lead[m]][digit], 1u);
-    }
-  }
-}
-
-// The weighted sibling (erpl_reweight.hip, erpl_density_w.hip, erpl_corridor_w.hip): the key counts w times, the bins are 64-bit.  A wave whose hits share one bin adds
-// their weights up with a shuffle tree first (integer adds: the order does not matter) and makes one add of it.
-__device__ __forceinline__ void select_count_weighted(u64 (*hist)[ERPL_ANA_BINS], const int* lead, const u64* prefix, int nlead,
-                                                      bool use, u64 key, int shift, u64 w) {
-  const u64 above = shift >= 56 ? 0ull : (~0ull << (shift + 8));
-  const unsigned int digit = (unsigned int)(key >> shift) & (ERPL_ANA_BINS - 1);
-  for (int m = 0; m < nlead; ++m) {
-    const bool hit = use && ((key ^ prefix[m]) & above) == 0ull;
-    const u64 mask = __ballot(hit);
-    if (mask == 0ull) continue;
-    const int lead_lane = __ffsll((long long)mask) - 1;
-    const unsigned int d0 = (unsigned int)__shfl((int)digit, lead_lane);
-    if (__ballot(hit && digit != d0) == 0ull) {
-      u64 s = hit ? w : 0ull;
-      for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-      if ((threadIdx.x & 63) == 0 && s) atomicAdd(&hist[lead[m]][d0], s);
-    } else if (hit && w) {
-      atomicAdd(&hist[lead[m]][digit], w);
+      if constexpr (kOnce) {
+        if ((int)(threadIdx.x & 63) == lead_lane) atomicAdd(&hist[lead[m]][d0], (unsigned int)__popcll(mask));
+      } else {
+        u64 s = hit ? w : 0ull;
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+        if ((threadIdx.x & 63) == 0 && s) atomicAdd(&hist[lead[m]][d0], s);
+      }
+    } else if (hit && (kOnce || w)) {
+      atomicAdd(&hist[lead[m]][digit], kOnce ? (Count)1 : w);
     }
   }
 }
@@ -264,6 +267,158 @@ __device__ __forceinline__ int select_leader(const u64* prefix, int t) {
   int lead = t;
   for (int u = t - 1; u >= 0; --u) if (prefix[u] == prefix[t]) lead = u;
   return lead;
+}
+
+// the groups of a pass: the leaders among the nt targets and their prefixes, in target order.  One thread.
+__device__ __forceinline__ int select_groups(const int* leader, const u64* prefix, int nt, int* lead, u64* lead_prefix) {
+  int g = 0;
+  for (int t = 0; t < nt; ++t)
+    if (leader[t] == t) { lead[g] = t; lead_prefix[g] = prefix[t]; ++g; }
+  return g;
+}
+
+template <int THREADS>
+__device__ __forceinline__ void select_clear(u64* bins, int count) {
+  for (int k = threadIdx.x; k < count; k += THREADS) bins[k] = 0ull;
+}
+
+// target t of a selection that begins: no digit fixed, in one group with every other target
+template <int NT, class Key>
+__device__ __forceinline__ void select_start(ErplSelect<NT>& sel, Key* key, int t, u64 rank) {
+  sel.prefix[t] = 0ull; sel.rank[t] = rank; sel.leader[t] = 0;
+  key[t] = 0ull;
+}
+
+// ---- global bins.  The body of a digit pass, for a workgroup of ERPL_ANA_BLOCK threads on a grid of gridDim.x of them
+// over the n columns of a row: the digit at `shift` of the keys that match a target's prefix above it, per group of
+// targets (only its leader keeps a histogram), in LDS and from there into bins[leader].  fetch(i, &key, &w), i < n, says
+// whether column i counts and, if so, gives its key and (64-bit bins) its weight; key and w come in as 0.
+template <class Count, int NT, class Fetch>
+__device__ __forceinline__ void select_pass(const ErplSelect<NT>& sel, u64 (*bins)[ERPL_ANA_BINS], int nt, int64_t n, int shift,
+                                            Fetch fetch) {
+  __shared__ Count s_hist[NT][ERPL_ANA_BINS];   // 16 KB
+  __shared__ u64 s_prefix[NT];
+  __shared__ int s_lead[NT];
+  __shared__ int s_nlead;
+  const int64_t stride = (int64_t)gridDim.x * ERPL_ANA_BLOCK;
+  for (int k = threadIdx.x; k < NT * ERPL_ANA_BINS; k += ERPL_ANA_BLOCK) (&s_hist[0][0])[k] = 0;
+  if (threadIdx.x == 0) s_nlead = select_groups(sel.leader, sel.prefix, nt, s_lead, s_prefix);
+  __syncthreads();
+  const int nlead = s_nlead;
+  const int64_t first = (int64_t)blockIdx.x * ERPL_ANA_BLOCK + (threadIdx.x & ~63);
+  for (int64_t base = first; base < n; base += stride) {   // uniform over the wave (ballots below)
+    const int64_t i = base + (threadIdx.x & 63);
+    bool use = false;
+    u64 key = 0ull;
+    Count w = 0;
+    if (i < n) use = fetch(i, &key, &w);
+    select_count(s_hist, s_lead, s_prefix, nlead, use, key, shift, w);
+  }
+  __syncthreads();
+  for (int m = 0; m < nlead; ++m) {
+    const int t = s_lead[m];
+    for (int b = threadIdx.x; b < ERPL_ANA_BINS; b += ERPL_ANA_BLOCK) {
+      const Count c = s_hist[t][b];
+      if (c) atomicAdd(&bins[t][b], (u64)c);
+    }
+  }
+}
+
+// Between the passes, for ONE workgroup of 64 NT threads: wave t scans the histogram of target t's group, fixes the digit
+// that holds its rank (key[t] follows the prefix) and reduces the rank to that bin; then the groups are formed again and
+// the bins are cleared.
+template <int NT, class Key>
+__device__ __forceinline__ void select_step(ErplSelect<NT>& sel, u64 (*bins)[ERPL_ANA_BINS], Key* key, int nt, int shift) {
+  __shared__ u64 s_prefix[NT];
+  const int t = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (t < nt) {
+    const u64* h = bins[sel.leader[t]];
+    const u64 rank = sel.rank[t];
+    u64 prefix = sel.prefix[t], before = 0ull;
+    int d = 0;
+    if (lane == 0) s_prefix[t] = prefix;             // stays if no bin holds the rank: an empty row
+    if (select_scan(h, rank, lane, &d, &before)) {   // exactly one lane
+      prefix |= (u64)d << shift;
+      sel.prefix[t] = prefix;
+      sel.rank[t] = rank - before;
+      key[t] = prefix;
+      s_prefix[t] = prefix;
+    }
+  }
+  __syncthreads();   // every histogram has been read, every prefix is known
+  if (lane == 0 && t < nt) sel.leader[t] = select_leader(s_prefix, t);
+  select_clear<64 * NT>(&bins[0][0], NT * ERPL_ANA_BINS);
+}
+
+// ---- LDS alone: one workgroup of ERPL_ANA_BLOCK threads per row of m columns, a key counting once.
+
+// The columns i0, i0 + 256, .. of a row, LOADS loads per thread in flight: the value and ok[k] = the column exists and its
+// mask byte is 0.  A value past the row is 0.0, never read from memory.
+template <int LOADS>
+__device__ __forceinline__ void band_fetch(const double* __restrict__ x, const uint8_t* __restrict__ mask, int64_t m, int64_t i0,
+                                           double (&v)[LOADS], bool (&ok)[LOADS]) {
+  uint8_t byte[LOADS];
+#pragma unroll
+  for (int k = 0; k < LOADS; ++k) {
+    const int64_t i = i0 + (int64_t)k * ERPL_ANA_BLOCK;
+    ok[k] = i < m;
+    v[k] = ok[k] ? x[i] : 0.0;
+    byte[k] = ok[k] && mask ? mask[i] : (uint8_t)0;
+  }
+#pragma unroll
+  for (int k = 0; k < LOADS; ++k) ok[k] = ok[k] && byte[k] == 0;
+}
+
+// The whole selection of a row: nt <= NT targets, target t at rank_of(t) among the count > 0 finite unmasked values;
+// count = 0 or nt = 0: no pass.  Every target starts with no digit fixed; then eight passes of {clear, leaders, groups,
+// count, scan}.  key[t] = the key of target t, 0 for t >= nt and for an empty row.  Every thread calls it; the barriers
+// inside also order what the caller put into LDS before the call.
+template <int NT, int LOADS, class RankOf, class Key>
+__device__ __forceinline__ void select_row(const double* __restrict__ x, const uint8_t* __restrict__ mask, int64_t m, int nt, u64 count,
+                                           RankOf rank_of, Key* key) {
+  __shared__ unsigned int s_hist[NT][ERPL_ANA_BINS];   // 16 KB
+  __shared__ u64 s_prefix[NT], s_rank[NT];             // per target
+  __shared__ int s_leader[NT];
+  __shared__ u64 s_lead_prefix[NT];                    // per group
+  __shared__ int s_lead[NT];
+  __shared__ int s_nlead;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid < NT) {
+    s_prefix[tid] = 0ull;
+    s_rank[tid] = count > 0ull && tid < nt ? rank_of(tid) : 0ull;
+  }
+  if (count > 0ull && nt > 0) {   // (uniform over the workgroup)
+    for (int shift = 56; shift >= 0; shift -= 8) {
+      __syncthreads();   // the prefixes of the pass before are in place, its histograms have been read
+      for (int k = tid; k < NT * ERPL_ANA_BINS; k += ERPL_ANA_BLOCK) (&s_hist[0][0])[k] = 0u;
+      if (tid < nt) s_leader[tid] = select_leader(s_prefix, tid);
+      __syncthreads();
+      if (tid == 0) s_nlead = select_groups(s_leader, s_prefix, nt, s_lead, s_lead_prefix);
+      __syncthreads();
+      const int nlead = s_nlead;
+      // uniform over the wave (ballots): every lane makes every call, a lane past the row brings no key
+      for (int64_t base = (int64_t)wave * 64; base < m; base += LOADS * ERPL_ANA_BLOCK) {
+        double v[LOADS];
+        bool ok[LOADS];
+        band_fetch(x, mask, m, base + lane, v, ok);
+#pragma unroll
+        for (int k = 0; k < LOADS; ++k)
+          select_count(s_hist, s_lead, s_lead_prefix, nlead, ok[k] && finite_bits(v[k]), key_of_signed(v[k]), shift, 1u);
+      }
+      __syncthreads();
+      // wave w scans for the targets w, w + kWaves, ..: the digit that holds the rank, the rank within that bin
+      for (int t = wave; t < nt; t += kWaves) {
+        int d = 0;
+        u64 below = 0ull;
+        if (select_scan(s_hist[s_leader[t]], s_rank[t], lane, &d, &below)) {   // exactly one lane
+          s_prefix[t] |= (u64)d << shift;
+          s_rank[t] -= below;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < NT) key[tid] = tid < nt ? s_prefix[tid] : 0ull;
 }
 
 }  // namespace

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(kBlock) void subset_hist(const double* __restrict__
     const int64_t i = base + threadIdx.x;
     const bool use = i < n;
     const double v = use ? g[i] : 0.0;
-    select_count(hist, &lead, &prefix, 1, use, erpl_subset_key(v), shift);
+    select_count(hist, &lead, &prefix, 1, use, erpl_subset_key(v), shift, 1u);
     if (shift == 56) alive += (u64)__popcll(__ballot(use && erpl_subset_alive(v)));
   }
   __syncthreads();

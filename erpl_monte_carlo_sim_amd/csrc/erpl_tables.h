@@ -219,12 +219,17 @@ struct ErplAnaResult {
   unsigned long long counter[ERPL_ANA_COUNTERS];
   ErplAnaRow row[ERPL_ANALYSIS_MAX_ROWS];
 };
-// Selection state of one row: what is fixed of every target's key so far, its rank among the keys that share that
-// prefix, and the first target with the same prefix (targets that share a prefix share one histogram).
-struct ErplAnaSelect {
-  unsigned long long prefix[ERPL_ANA_TARGETS], rank[ERPL_ANA_TARGETS];
-  int32_t leader[ERPL_ANA_TARGETS];
+// Selection state of one row with NT targets (the passes: erpl_stat_device.h): what is fixed of every target's key so far,
+// its rank among the keys that share that prefix, and the first target with the same prefix (targets that share a prefix
+// share one histogram).
+extern "C++" {
+template <int NT>
+struct ErplSelect {
+  unsigned long long prefix[NT], rank[NT];
+  int32_t leader[NT];
 };
+}
+typedef ErplSelect<ERPL_ANA_TARGETS> ErplAnaSelect;
 // The fixed part of the workspace (the per-sample reason bytes are a second allocation that grows with n).
 struct ErplAnaWork {
   ErplAnaResult res;
@@ -468,15 +473,15 @@ int erpl_launch_dens_pairs(const double* qry, int64_t queries, const double* src
                            double* out, const uint32_t* scatter, void* stream);
 int erpl_launch_dens_peak(ErplDensWork* work, const double* density, int64_t nodes, void* stream);   // -> work->out.sum / peak / peak_at
 int erpl_launch_dens_fill_nan(double* row, int64_t n, void* stream);
-// the fold of erpl_launch_dens_pairs on its own: the weighted pair kernel (erpl_density_w.hip) leaves its slices to it
+// the fold of erpl_launch_dens_pairs on its own: the weighted pair kernel (erpl_launch_densw_pairs) leaves its slices to it
 int erpl_launch_dens_fold(const double* partial, int slices, int64_t queries, double norm, double* out, const uint32_t* scatter,
                           void* stream);
 }
 
 // ---- erpl_mc_impact_density_weighted (erpl_density_w.hip) ----
 // The passes of erpl_density.hip with an integer weight per sample.  Whiten, nodes, fold, peak and fill_nan are THE launchers
-// above, run on `d`; the population, the moments, the zones, the pair kernel and the selection are the unit's own.  The pair
-// kernel has the shape of erpl_dens_pairs, with (u, v, w) per source in its LDS tile (24 KB).
+// above, run on `d`; the population, the moments, the zones and the selection are the unit's own.  The pair kernel is the
+// weighted instantiation of erpl_dens_pairs (erpl_density.hip), with (u, v, w) per source in its LDS tile (24 KB).
 struct ErplDensWMoments {           // what the population and the moment passes hand back
   unsigned long long count, n_masked, n_non_finite, n_zero, sum_w, max_w;
   double first_bad;                       // the lowest column whose weight is outside 0 .. 2^Q (+inf: none)
@@ -492,10 +497,7 @@ struct ErplDensWOut {               // what the zone pass and the selection hand
   unsigned long long content_w[ERPL_DENSITY_MAX_LEVELS];
   double f_min, f_max;
 };
-struct ErplDensWSelect {            // the state of the weighted radix selection, one target per level
-  unsigned long long prefix[ERPL_DENSITY_MAX_LEVELS], rank[ERPL_DENSITY_MAX_LEVELS];
-  int32_t leader[ERPL_DENSITY_MAX_LEVELS];
-};
+typedef ErplSelect<ERPL_DENSITY_MAX_LEVELS> ErplDensWSelect;   // the weighted radix selection, one target per level
 struct ErplDensWWork {
   ErplDensWork d;                   // the block of the launchers of erpl_density.hip: in, out.sum / peak / peak_at, psum, pext
   unsigned long long pcnt[ERPL_ANA_MAX_BLOCKS][4];        // population: masked, non-finite, zero, counted per workgroup
