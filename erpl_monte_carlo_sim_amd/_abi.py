@@ -24,8 +24,9 @@ MOTOR_LIQUID, MOTOR_SOLID = 0, 1
 PREC_F64, PREC_F32, PREC_F64_FAST = 0, 1, 2
 PRECISIONS = {"f64": PREC_F64, "f32": PREC_F32, "f64_fast": PREC_F64_FAST}
 MAX_OVERLAP = 8
-DBG_ATMOSPHERE, DBG_AERO, DBG_RHS, DBG_MATH, DBG_RHS_SEQ = 0, 1, 2, 3, 4
+DBG_ATMOSPHERE, DBG_AERO, DBG_RHS, DBG_MATH, DBG_RHS_SEQ, DBG_MINMAX = 0, 1, 2, 3, 4, 5
 DBG_MATH_ROWS = 16
+DBG_MINMAX_ROWS = 8
 FLAG_STOP_AT_APOGEE = 1
 FLAG_CAPTURE_POSITION_ONLY = 2
 

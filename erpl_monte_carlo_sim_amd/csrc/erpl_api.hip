@@ -968,7 +968,9 @@ int erpl_mc_debris_directions_host(uint64_t seed, const int64_t* sample_ids, int
 int erpl_mc_debug_eval(erpl_ctx* c, const erpl_batch* b, int what, int64_t m, const double* in, double* out, void* stream) {
   if (!c || !b || !in || !out) return erpl_fail(ERPL_ERR_INVALID, "NULL argument");
   if (!c->has_cfg) return erpl_fail(ERPL_ERR_CONFIG, "erpl_mc_set_config has not been called");
-  if (what < ERPL_DBG_ATMOSPHERE || what > ERPL_DBG_RHS_SEQ) return erpl_fail(ERPL_ERR_INVALID, "unknown function %d", what);
+  if (what < ERPL_DBG_ATMOSPHERE || what > ERPL_DBG_MINMAX) return erpl_fail(ERPL_ERR_INVALID, "unknown function %d", what);
+  if (what == ERPL_DBG_MINMAX && b->precision != ERPL_PREC_F64_FAST)   // (the other builds' kernels have no such branch)
+    return erpl_fail(ERPL_ERR_INVALID, "ERPL_DBG_MINMAX: the fp64 throughput build only");
   if (b->n < 1 || m < 0 || !b->rocket || !b->motor) return erpl_fail(ERPL_ERR_INVALID, "need at least one sample with parameters");
   if (!check_wind_args(b)) return erpl_fail(ERPL_ERR_INVALID, "bad wind arguments");
   if (m == 0) return ERPL_OK;

@@ -131,6 +131,9 @@ __global__ __launch_bounds__(256) void erpl_extract_f64(const ErplKArgs a, const
 //    v2 m_rsq(v2), v2 = max(x^2 + y^2, 1e-30) as the fast RHS forms them     12, 13 alpha, beta once more through the single
 //    m_atan2_half<false>(y, x, r, x), m_atan2_half<true>(y, |x|, r, x) (fp64 throughput build)
 //    14 m_next_up(x)       15 m_sqrt(x)
+//   ERPL_DBG_MINMAX      (fp64 throughput build only) in: x, y, z   out: the ERPL_DBG_MINMAX_ROWS rows below
+//     0 m_max(x, y)         1 m_min(x, y)          2 m_clamp(x, y, z)               3 m_max(x, 0)
+//     4 m_max(x, 1e-30)     5 m_clamp(x, -kBig, kBig)   6 m_clamp_abs_uniform(x, S.stall_angle)   7 m_add_zero(x)
 __global__ __launch_bounds__(256) void ERPL_CAT(erpl_debug_, ERPL_SUFFIX)(const ErplKArgs a, const ErplScalars<real> S,
                                                                          const int what, const int64_t m,
                                                                          const double* __restrict__ in,
@@ -226,6 +229,13 @@ __global__ __launch_bounds__(256) void ERPL_CAT(erpl_debug_, ERPL_SUFFIX)(const 
 #endif
 #pragma unroll
     for (int k = 0; k < ERPL_DBG_MATH_ROWS; ++k) out[k * m + j] = (double)o[k];
+#if ERPL_FAST_F64
+  } else if (what == ERPL_DBG_MINMAX) {
+    const real x = in[0 * m + j], y = in[1 * m + j], z = in[2 * m + j];
+    out[0 * m + j] = m_max(x, y); out[1 * m + j] = m_min(x, y); out[2 * m + j] = m_clamp(x, y, z);
+    out[3 * m + j] = m_max(x, (real)0); out[4 * m + j] = m_max(x, (real)1e-30); out[5 * m + j] = m_clamp(x, -kBig, kBig);
+    out[6 * m + j] = m_clamp_abs_uniform(x, S.stall_angle); out[7 * m + j] = m_add_zero(x);
+#endif
   } else {
     // ERPL_DBG_RHS: the one column j.  ERPL_DBG_RHS_SEQ: every n-th column from j on, the caches carried over.
     const int64_t stride = (what == ERPL_DBG_RHS_SEQ) ? n : m;

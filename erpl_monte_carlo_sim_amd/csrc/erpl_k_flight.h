@@ -456,7 +456,11 @@ __global__ __launch_bounds__(kFlightBlock, MINW) void ERPL_CAT(erpl_flight_, ERP
       }
       {
         const real sp2 = (real)((yn[3] * yn[3] + yn[4] * yn[4]) + vz * vz);
+#if ERPL_FAST_F64
+        ln.max_speed2 = m_max(sp2, ln.max_speed2);   // (the running maximum is never NaN, and a NaN sp2 leaves it: the select below)
+#else
         ln.max_speed2 = (sp2 > ln.max_speed2) ? sp2 : ln.max_speed2;
+#endif
 #if ERPL_FAST_F64
         // (a NaN speed: the non-finite paths below.  The altitude test keeps the air density of the NEXT step - the
         // troposphere formula has no lower clamp, environment.py:28-33 - in the range the speed bound was derived for)

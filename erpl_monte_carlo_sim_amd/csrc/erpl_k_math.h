@@ -15,7 +15,9 @@ __device__ __forceinline__ double m_rcp(double a) { return 1.0 / a; }   // (the 
 __device__ __forceinline__ float m_abs(float x) { return fabsf(x); }
 // min / max / copysign in the working precision (NaN handling of fmin/fmax: the non-NaN operand)
 __device__ __forceinline__ float m_max(float a, float b) { return fmaxf(a, b); }
-__device__ __forceinline__ double m_max(double a, double b) { return fmax(a, b); }
+#if !ERPL_FAST_F64
+__device__ __forceinline__ double m_max(double a, double b) { return fmax(a, b); }   // (the fp64 throughput build has its own below)
+#endif
 __device__ __forceinline__ float m_copysign(float a, float b) { return copysignf(a, b); }
 __device__ __forceinline__ double m_copysign(double a, double b) { return copysign(a, b); }
 // smallest value above a positive finite x (half-open ranges over closed layer bounds)
@@ -91,7 +93,57 @@ __device__ __forceinline__ double m_rsq(double x) {
 // classifies: 17): within 2 * 1.24 + 0.5 = 2.98 ulp (the ulp of rsq(x) weighs up to two of the root's, and the product
 // rounds once).  0 and +inf give NaN where sqrt gives 0 and +inf: both callers feed a state that is past saving.
 __device__ __forceinline__ double m_sqrt_pos(double x) { return x * m_rsq(x); }
-__device__ __forceinline__ double m_clamp(double x, double lo, double hi) { return fmin(fmax(x, lo), hi); }
+// max / min / clamp as ONE v_max_f64 / v_min_f64 each.  fmax / fmin first quiet every operand the compiler cannot prove free of
+// signalling NaNs - a value read from LDS, a kernel argument, anything computed in another basic block - with a
+// v_max_f64 x, x, x of its own (IEEE mode): 21 vector instructions per RK4 step.  The instruction itself already returns the
+// other operand for a quiet NaN; the two forms differ for a SIGNALLING NaN alone (quieted here, dropped there), which no
+// arithmetic instruction produces and the host refuses in the inputs.  Asserted bit for bit against numpy.fmax / fmin on the
+// device by tests/test_gpu_step_diet_bits.py.  The second operand: a compile-time constant goes in as an inline constant
+// (0, +-1) or through a scalar register pair, as the compiler folds it into fmax; anything else is a vector register.
+// For a later caller: (1) the kernels run in IEEE mode (the default of a compute kernel; with it off the instruction passes a
+// signalling NaN on unquieted); (2) put a constant SECOND - as the first operand it is copied into a vector pair; (3) whether
+// b is a constant is decided after inlining (__builtin_constant_p on a parameter of a forced-inline function): at -O0 every
+// call takes the vector form, which is right but moves constants through registers.
+#define ERPL_MINMAX_F64(name_, op_)                                                                     \
+  __device__ __forceinline__ double name_(double a, double b) {                                         \
+    double r;                                                                                           \
+    if (__builtin_constant_p(b)) {                                                                      \
+      if (b == 0.0 && !__builtin_signbit(b)) asm(op_ " %0, %1, 0" : "=v"(r) : "v"(a));                  \
+      else if (b == 1.0) asm(op_ " %0, %1, 1.0" : "=v"(r) : "v"(a));                                    \
+      else if (b == -1.0) asm(op_ " %0, %1, -1.0" : "=v"(r) : "v"(a));                                  \
+      else asm(op_ " %0, %1, %2" : "=v"(r) : "v"(a), "s"(b));                                           \
+    } else {                                                                                            \
+      asm(op_ " %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));                                                \
+    }                                                                                                   \
+    return r;                                                                                           \
+  }
+ERPL_MINMAX_F64(m_max, "v_max_f64")
+ERPL_MINMAX_F64(m_min, "v_min_f64")
+#undef ERPL_MINMAX_F64
+__device__ __forceinline__ double m_clamp(double x, double lo, double hi) { return m_min(m_max(x, lo), hi); }
+// m_clamp(|x|, -1, hi) with hi wave-uniform (a kernel argument): the source modifier and the scalar operand, which the
+// compiler folds into fmax / fmin and cannot fold into an asm operand, written out.  UNIFORM ONLY: hi goes in through a
+// scalar register, so of a lane-varying hi every lane would silently get the first active lane's - pass members of the
+// by-value kernel arguments (S.*) or constants, nothing computed per lane.
+__device__ __forceinline__ double m_clamp_abs_uniform(double x, double hi) {
+  double r;
+  asm("v_max_f64 %0, |%1|, -1.0\n\tv_min_f64 %0, %0, %2" : "=&v"(r) : "v"(x), "s"(hi));
+  return r;
+}
+// 0 + x as the v_add_f64 it is when the zero is a register the compiler knows nothing about - written out, so that the
+// contraction of x into FMAs is the one an unknown addend gets (a visible constant zero re-associates it)
+__device__ __forceinline__ double m_add_zero(double x) {
+  double r;
+  asm("v_add_f64 %0, 0, %1" : "=v"(r) : "v"(x));
+  return r;
+}
+// A zero written where the call stands: as a plain constant, the zero of a value that another path computes is moved ahead of
+// the branch and paid for on every path
+__device__ __forceinline__ double m_zero_here() {
+  double r;
+  asm volatile("v_mov_b64 %0, 0" : "=v"(r));
+  return r;
+}
 // exp2 / log2 / atan for the operand ranges of this RHS, without the special-case ladders of a general
 // libm (those cost ~40 % of its instructions, and with one wave per SIMD every instruction is 4 cycles);
 // NaN in -> NaN out, results overflow / underflow to inf / 0 through v_ldexp_f64.  Errors: m_exp2 <= 2 ulp (denormal

@@ -44,7 +44,11 @@ __device__ __forceinline__ void fast_aero(const ErplScalars<real>& S, const real
     const real sf = m_max((real)1 - over * S.inv_stall_span, (real)0);
     cd *= (real)1 + ((real)0.5 * over) * S.inv_stall_span;
     cy *= sf;
+#if ERPL_FAST_F64
+    cl = cl_alpha * m_copysign(m_clamp_abs_uniform(alpha, S.stall_angle) * sf, alpha);    // min(|alpha|, stall)
+#else
     cl = cl_alpha * m_copysign(m_clamp(abs_alpha, (real)-1, S.stall_angle) * sf, alpha);  // min(|alpha|, stall)
+#endif
   }
   const real sm = (S.cp_location + cps) - cg;
   cma = -cl_alpha * sm;
@@ -136,7 +140,18 @@ __device__ __forceinline__ void rocket_dynamics_at(const Shared& C, LaneParams& 
   } else {
     thrust = burning ? p.thrust - p.Ae * P : (real)0;
   }
+#if ERPL_FAST_F64
+  // The sums of the lateral forces and of the moments start from zero - but as initialisers ahead of the two branches the
+  // zeros cost four 64-bit moves in every evaluation, for the lanes that skip the aerodynamic block: in flight next to none.
+  // Here every path sets them: the aerodynamic block adds to a CONSTANT zero (m_add_zero: the same addition, x + 0 is not x
+  // for x = -0), and the lanes it is not for - parachute out, or nothing to push against - write their zeros in a block of
+  // their own, which the wave skips when it has no such lane and which holds the parachute drag.
+  real fb0 = thrust, fb1, fb2, mb1, mb2;
+#define ERPL_SUM_FROM_ZERO(v_, x_) v_ = m_add_zero(x_)
+#else
   real fb0 = thrust, fb1 = 0, fb2 = 0, mb1 = 0, mb2 = 0;
+#define ERPL_SUM_FROM_ZERO(v_, x_) v_ += x_
+#endif
   ERPL_STAMP(ss.seg[2], ss.last);
   // ---- parachute latch (:366-369) and drag (:372-377) ----
   // A wave-skipped branch, not selects: the parachute is out in <1 % of all evaluations, and on this
@@ -144,6 +159,13 @@ __device__ __forceinline__ void rocket_dynamics_at(const Shared& C, LaneParams& 
   // v_cndmask cost ~4.1 cycles each per SIMD vs ~2.7 for an FMA) - measured -5 % time.  The other
   // small conditionals stay predicated: as branches they cost more (phi copies, exec bookkeeping).
   if (h <= S.chute_alt) { if (!chute && y[5] < 0) chute = true; }  // below 500 m only
+#if ERPL_FAST_F64
+  const bool aero = !chute && qdyn > 0;
+  if (!aero) {
+    ERPL_RARE_BLOCK();
+    fb1 = 0; fb2 = 0;
+    mb1 = m_zero_here(); mb2 = m_zero_here();   // (as plain constants the compiler hoists these two back ahead of the branch)
+#endif
   if (chute) {
     const real rs2 = (vb0 * vb0 + vb1 * vb1) + vb2 * vb2;
     const real rs = m_sqrt(rs2);
@@ -153,7 +175,12 @@ __device__ __forceinline__ void rocket_dynamics_at(const Shared& C, LaneParams& 
       fb0 += kc * vb0; fb1 += kc * vb1; fb2 += kc * vb2;
     }
   }
+#if ERPL_FAST_F64
+  }
+  if (aero) {  // aerodynamics (:378-411, rocket.py:138-218)
+#else
   if (!chute && qdyn > 0) {  // aerodynamics (:378-411, rocket.py:138-218)
+#endif
     const real vxz2 = m_max(vb0 * vb0 + vb2 * vb2, (real)1e-30);
     const real rxz = m_rsq(vxz2);
     // The |v_body| < 1e-6 m/s dead zones of utils.py:160-172 force alpha/beta to 0 there; here the
@@ -181,12 +208,13 @@ __device__ __forceinline__ void rocket_dynamics_at(const Shared& C, LaneParams& 
     const real qs = qdyn * S.ref_area;
     const real drag = qs * cd, lift = qs * cl, side = qs * cy;
     fb0 += (sb * side - (ca * cb) * drag) - (sa * cb) * lift;
-    fb1 += (-(ca * sb) * drag - cb * side) - (sa * sb) * lift;
-    fb2 += sa * drag - ca * lift;
+    ERPL_SUM_FROM_ZERO(fb1, (-(ca * sb) * drag - cb * side) - (sa * sb) * lift);
+    ERPL_SUM_FROM_ZERO(fb2, sa * drag - ca * lift);
     const real qsd = qdyn * S.area_diam;
     mb1 = qsd * (cma * alpha);
     mb2 = qsd * (cma * beta);
   }
+#undef ERPL_SUM_FROM_ZERO
   ERPL_STAMP(ss.seg[3], ss.last);
   const real wx = y[10], wy = y[11], wz = y[12];
   mb1 -= S.pitch_damping * wy;  // :414-415

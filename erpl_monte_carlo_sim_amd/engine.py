@@ -252,7 +252,7 @@ class TrajectoryEngine:
         x = torch.as_tensor(np.ascontiguousarray(np.atleast_2d(inputs), dtype=np.float64), device=self.device)
         m = int(x.shape[1])
         rows = {_abi.DBG_ATMOSPHERE: 4, _abi.DBG_AERO: 5, _abi.DBG_RHS: 15, _abi.DBG_MATH: _abi.DBG_MATH_ROWS,
-                _abi.DBG_RHS_SEQ: 15}[what]
+                _abi.DBG_RHS_SEQ: 15, _abi.DBG_MINMAX: _abi.DBG_MINMAX_ROWS}[what]
         out = torch.full((rows, m), float("nan"), dtype=torch.float64, device=self.device)
         b = self._batch_struct(db)
         st = torch.cuda.current_stream(self.device)

@@ -2358,9 +2358,13 @@ int erpl_mc_corridor_bands_weighted_host(const double* values, const uint8_t* ma
  * table is in csrc/erpl_k_debug.h), NaN where the build has none;
  * ERPL_DBG_RHS_SEQ: the layout of ERPL_DBG_RHS, but batch->n lanes, one per sample: lane i evaluates the columns
  * i, i + n, i + 2n, ... < m in that order through one set of cached wind / Mach / atmosphere intervals that is cleared
- * before the first column only (the latch is each column's input: the values are those of ERPL_DBG_RHS). */
-enum { ERPL_DBG_ATMOSPHERE = 0, ERPL_DBG_AERO = 1, ERPL_DBG_RHS = 2, ERPL_DBG_MATH = 3, ERPL_DBG_RHS_SEQ = 4 };
+ * before the first column only (the latch is each column's input: the values are those of ERPL_DBG_RHS);
+ * ERPL_DBG_MINMAX (ERPL_PREC_F64_FAST only, ERPL_ERR_INVALID otherwise): in x, y, z -> out ERPL_DBG_MINMAX_ROWS rows, the
+ * single-instruction max / min / clamp forms of the fp64 throughput build with every kind of second operand they take
+ * (the table is in csrc/erpl_k_debug.h). */
+enum { ERPL_DBG_ATMOSPHERE = 0, ERPL_DBG_AERO = 1, ERPL_DBG_RHS = 2, ERPL_DBG_MATH = 3, ERPL_DBG_RHS_SEQ = 4, ERPL_DBG_MINMAX = 5 };
 #define ERPL_DBG_MATH_ROWS 16
+#define ERPL_DBG_MINMAX_ROWS 8
 int erpl_mc_debug_eval(erpl_ctx* ctx, const erpl_batch* batch, int what, int64_t m, const double* in, double* out,
                        void* hip_stream);
 
